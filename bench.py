@@ -22,6 +22,14 @@ independent frame pair (weak scaling, no data-path collective); the one collecti
 all-gather (RCCL) after the per-rank LM solves, reported separately.
 
 Prints ONE JSON line on rank 0.
+
+A plain run does what the headline needs and nothing else: set-up, warm-up, the K timed steps, the line (metric, value,
+unit, dtype, ms_per_step, the configuration).  --full adds everything else the line used to carry: the check of the timed
+steps against ea_batch_eval, the kernel durations and roofline, the materialised mode, the LM, C4, sharded and
+other-workload measurements and the CPU baselines (--no-extras / --no-cpu-baseline drop parts of it again).
+--dump-outputs DIR writes what the last execution of the timed call handed its caller -- cost, JtJ, Jtr, n_invalid of
+every step, float64, leading axis = step, rank 0 -- as DIR/<name>.npy, with the steps' indices in DIR/step_index.npy.
+The inputs are seeded: the same arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -171,6 +179,25 @@ def cpu_baseline_all_cores(cfg, loss, budget_s=6.0):
             "sample": "analytic-Jacobian oracle, %d threads x shards of the first %d points, fp64, %.1f s" % (cores, n, el)}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES, seed=0):
+    """--dump-outputs: `arrays` (leading axis = step) as float64 path/<name>.npy, and the steps' indices as
+    path/step_index.npy.  Above `limit` bytes in all, a fixed seeded sample of the steps is written (always with the last)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    K = next(iter(arrays.values())).shape[0]
+    per_step = sum(a.nbytes for a in arrays.values()) // K + 8   # (+ the step's index)
+    idx = np.arange(K)
+    if K * per_step > limit:
+        keep = max(1, limit // per_step)
+        idx = np.append(np.sort(np.random.default_rng(seed).choice(K - 1, keep - 1, replace=False)), K - 1)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a[idx])
+    np.save(os.path.join(path, "step_index.npy"), idx.astype(np.float64))
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -264,6 +291,10 @@ def main():
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--workload", default="c2", choices=["c2", "c5"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks and secondary measurements (roofline, materialised mode, LM, C4, other workloads, CPU baselines)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed call returned (cost, JtJ, Jtr, n_invalid per step) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true")
     ap.add_argument("--no-device-allreduce", action="store_true",
@@ -412,6 +443,43 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     value = world * n_pts * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        # (poses: every step of the last timed call; --serial-steps: the result its last step left, as a one-step axis)
+        res = ({k: v for k, v in out_k.items() if not k.startswith("_")} if mode == "poses"
+               else {k: v[None] for k, v in B.bench_result().items()})
+        dump_outputs(args.dump_outputs, res)
+    head = None
+    if rank == 0:
+        head = {"metric": "edge-point residual+Jacobian evals/sec", "value": value, "unit": "evals/s",
+                "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+                "vs_baseline": None, "dtype": tag, "data": "synthetic",
+                "config": {"workload": desc, "points_per_gpu": int(n_pts), "dt_image": "%dx%d" % (W, H),
+                           "parallelism": "independent frame pairs, one per GPU; single RCCL pose all-gather",
+                           "tiles": B.info("num_tiles"), "points_per_thread": B.info("points_per_thread"),
+                           "lds_bytes": B.info("lds_bytes"), "point_order_tile_px": P.point_order,
+                           "timed_region": graph or "eager launches",
+                           "untimed_warmup": "%d launch-by-launch steps at one pose, the upload of the K poses, one run of the timed call, then %d rehearsals of the whole bracket (the last bracket is the one reported)" % (max(args.warmup, 1), warm_replays)
+                                             if mode == "poses" else "%d launch-by-launch steps, then %d rehearsals of the whole bracket" % (max(args.warmup, 1), warm_replays),
+                           "bracket_barrier": None if dist is None else ("shared-memory epoch barrier (one node)" if node_barrier is not None else "torch.distributed.barrier")}}
+
+    def finish(out, watchdog=None):
+        B.close()
+        P.close()
+        if comm is not None:
+            comm.close()
+        if dist is not None:
+            dist.barrier()
+            if node_barrier is not None:
+                node_barrier.close()
+            dist.destroy_process_group()
+        if watchdog is not None:
+            watchdog.cancel()
+        if rank == 0:
+            line_out.write(json.dumps(out) + "\n")
+            line_out.flush()
+    if not args.full:
+        return finish(head)
     # what the bracket itself costs on idle GPUs (N > 1: the closing barrier is a collective inside the timed region; at
     # K = 20 steps of ~3 us it is comparable to the work): reported beside the value, not subtracted from it
     bracket_ms = None
@@ -582,19 +650,8 @@ def main():
     # time must not cost the scaling record) and ends the process; every rank runs one.
     base = None
     if rank == 0:
-        base = {"metric": "edge-point residual+Jacobian evals/sec", "value": value, "unit": "evals/s",
-                "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-                "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-                "vs_baseline": None, "dtype": tag, "data": "synthetic",
-                "config": {"workload": desc, "points_per_gpu": int(n_pts), "dt_image": "%dx%d" % (W, H),
-                           "parallelism": "independent frame pairs, one per GPU; single RCCL pose all-gather",
-                           "tiles": B.info("num_tiles"), "points_per_thread": B.info("points_per_thread"),
-                           "lds_bytes": B.info("lds_bytes"), "point_order_tile_px": P.point_order,
-                           "timed_region": graph or "eager launches",
-                           "untimed_warmup": "%d launch-by-launch steps at one pose, the upload of the K poses, one run of the timed call, then %d rehearsals of the whole bracket (the last bracket is the one reported)" % (max(args.warmup, 1), warm_replays)
-                                             if mode == "poses" else "%d launch-by-launch steps, then %d rehearsals of the whole bracket" % (max(args.warmup, 1), warm_replays),
-                           "closing_barrier_and_sync_ms_on_idle_gpus": bracket_ms,
-                           "bracket_barrier": None if dist is None else ("shared-memory epoch barrier (one node)" if node_barrier is not None else "torch.distributed.barrier")},
+        head["config"]["closing_barrier_and_sync_ms_on_idle_gpus"] = bracket_ms
+        base = dict(head, **{
                 # the same workload with the trust-region loop's dependency (evaluation -> fold, two dependent launches per
                 # step, replayed from a graph): what ONE evaluation costs when the next one needs its result
                 "value_serial_dependent_steps": world * n_pts / (step_ms_serial * 1e-3) if step_ms_serial else None,
@@ -602,7 +659,7 @@ def main():
                 "calls": {"timed": "ea_batch_eval_resident_poses (K poses resident)" if mode == "poses" else "ea_batch_bench_steps (hook)",
                           "single_eval_call_ms": "ea_batch_eval: pose upload, evaluation, fold, synchronisation -- wall clock",
                           "eval_poses_call_ms": "ea_batch_eval_poses(K = steps): pose upload + device-side pose constants + the K evaluations -- wall clock"},
-                "roofline": roofline, "materialised_mode": mat}
+                "roofline": roofline, "materialised_mode": mat})
     extras, others, leg = {}, {}, ["start"]
 
     def compose(note=None):
@@ -948,19 +1005,7 @@ def main():
                 extras["cpu_baseline_all_cores"] = {"error": repr(e)}
         out = compose()
     leg[0] = "teardown"
-    B.close()
-    P.close()
-    if comm is not None:
-        comm.close()
-    if dist is not None:
-        dist.barrier()
-        if node_barrier is not None:
-            node_barrier.close()
-        dist.destroy_process_group()
-    watchdog.cancel()
-    if rank == 0:
-        line_out.write(json.dumps(out) + "\n")
-        line_out.flush()
+    finish(out, watchdog)
 
 
 if __name__ == "__main__":

@@ -4,7 +4,7 @@
 #   pass 1: SQ_BUSY_CYCLES SQ_WAVES SQ_INSTS_VALU   (SQ_BUSY_CYCLES is summed over the 32 shader engines' sequencers: / 32;
 #           SQ_INSTS_VALU of the pose-batched launch feeds the bench line's vector-issue bound)
 #   pass 2: GRBM_GUI_ACTIVE           (summed over the 8 XCDs: / 8; contains the command processor's share of a dispatch)
-# counters only (no trace domains), separate passes, over `bench.py --workload W --steps 200 --no-extras --no-cpu-baseline`.
+# counters only (no trace domains), separate passes, over `bench.py --workload W --steps 200 --full --no-extras --no-cpu-baseline`.
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/pmc_busy; mkdir -p $O
 STEPS=${STEPS:-20}
@@ -12,7 +12,7 @@ for w in ${WORKLOADS:-c2 c5}; do
   for pass in "SQ_BUSY_CYCLES SQ_WAVES SQ_INSTS_VALU" "GRBM_GUI_ACTIVE"; do
     tag=$(echo $pass | cut -d' ' -f1)
     rm -rf $O/${w}_$tag
-    (cd /tmp && timeout -k 10 200 rocprofv3 --pmc $pass -d $O/${w}_$tag -o p --output-format csv -- python3 $R/bench.py --workload $w --steps $STEPS --warmup 5 --no-extras --no-cpu-baseline > $O/${w}_$tag.log 2>&1)
+    (cd /tmp && timeout -k 10 200 rocprofv3 --pmc $pass -d $O/${w}_$tag -o p --output-format csv -- python3 $R/bench.py --workload $w --steps $STEPS --warmup 5 --full --no-extras --no-cpu-baseline > $O/${w}_$tag.log 2>&1)
     rc=$?; echo "$w $tag rc=$rc"
     if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo "timed out: stopping"; exit 1; fi
   done

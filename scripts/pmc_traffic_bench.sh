@@ -9,7 +9,7 @@ STEPS=${STEPS:-20}
 for w in c2 c5; do
   for ctr in FETCH_SIZE WRITE_SIZE; do
     rm -rf $O/${w}_$ctr
-    (cd /tmp && timeout -k 10 200 rocprofv3 --pmc $ctr -d $O/${w}_$ctr -o p --output-format csv -- python3 $R/bench.py --workload $w --steps $STEPS --warmup 5 --no-extras --no-cpu-baseline > $O/${w}_$ctr.log 2>&1)
+    (cd /tmp && timeout -k 10 200 rocprofv3 --pmc $ctr -d $O/${w}_$ctr -o p --output-format csv -- python3 $R/bench.py --workload $w --steps $STEPS --warmup 5 --full --no-extras --no-cpu-baseline > $O/${w}_$ctr.log 2>&1)
     rc=$?; echo "$w $ctr rc=$rc"
     if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo "timed out: stopping"; exit 1; fi
   done

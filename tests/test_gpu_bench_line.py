@@ -1,4 +1,4 @@
-"""bench.py's contract, checked on the line the driver's command prints: `python bench.py --gpus 1 --steps 20 --warmup 5`
+"""bench.py's contract, checked on the line `python bench.py --gpus 1 --steps 20 --warmup 5 --full` prints
 (here with the CPU sample shortened to a tenth; everything else as the driver runs it).  One JSON line on stdout; metric, unit and config of
 BASELINE.json's C2; value = points x steps / time of the timed region; the roofline object's fraction follows from its
 achieved and peak figures and its achieved figure from the algorithmic bytes and the kernel's measured duration; the CPU
@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_driver_command_prints_one_valid_line(hip):
     env = dict(os.environ, EA_BENCH_CPU_SAMPLE_SCALE="0.1")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full"],
                          capture_output=True, text=True, env=env, cwd=ROOT, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -60,3 +60,41 @@ def test_driver_command_prints_one_valid_line(hip):
     assert "ea_eval_rows_kernel" in m["kernel"] and 0.0 < m["frac"] < 1.0
     assert d["lm_iters_per_s_at_1e5_pts"] > 1e4 and d.get("incomplete") is None
     assert set(d["other_workloads"]) >= {"c5_fp32_1e6pts_2048x1536", "batch32_c2_fp64", "batch32_c2_fp32"}
+
+
+def test_plain_run_prints_the_headline_and_dumps_what_the_timed_call_computed(hip, tmp_path):
+    """`python bench.py --gpus 1 --steps 20 --warmup 5` without --full: the headline alone (no secondary measurement), and
+    --dump-outputs writes the K results of the last timed call, which are ea_batch_eval's at the K seeded step poses."""
+    dump = tmp_path / "out"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+                          "--dump-outputs", str(dump)], capture_output=True, text=True, cwd=ROOT, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, out.stdout
+    d = json.loads(lines[0])
+    assert d["metric"] == "edge-point residual+Jacobian evals/sec" and d["unit"] == "evals/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f64" and d["steps"] == 20 and d["warmup"] == 5 and d["value"] > 1e9
+    assert abs(d["value"] - d["config"]["points_per_gpu"] * 1e3 / d["ms_per_step"]) <= 1e-6 * d["value"]
+    assert "ea_batch_eval_resident_poses" in d["config"]["timed_region"]
+    for k in ("roofline", "materialised_mode", "cpu_baseline", "other_workloads", "lm_iters_per_s_at_1e5_pts"):
+        assert k not in d, k
+    import numpy as np
+    import bench
+    got = {k: np.load(str(dump / (k + ".npy"))) for k in ("cost", "JtJ", "Jtr", "n_invalid", "step_index")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["cost"].shape == (20, 1) and got["JtJ"].shape == (20, 1, 6, 6) and got["Jtr"].shape == (20, 1, 6)
+    assert got["n_invalid"].shape == (20, 1) and np.array_equal(got["step_index"], np.arange(20))
+    cfg, dtype, _, loss, _ = bench.build_workload("c2", 0)
+    Q, T = bench.step_poses(20, 1000)
+    P = hip.Problem(*cfg["K"], dtype=dtype, device=0)
+    P.set_points(cfg["xyz"]); P.set_dt_grid(cfg["grid"]); P.set_loss(*loss)
+    B = hip.Batch([P])
+    for k in (0, 10, 19):
+        want = B.eval(Q[k], T[k])
+        sc = np.abs(want["JtJ"]).max()
+        assert np.allclose(got["cost"][k], want["cost"], rtol=1e-12, atol=0)
+        assert np.allclose(got["JtJ"][k], want["JtJ"], rtol=1e-11, atol=1e-12 * sc)
+        assert np.allclose(got["Jtr"][k], want["Jtr"], rtol=1e-10, atol=1e-12 * np.sqrt(sc * max(float(np.max(want["cost"])), 1e-300)))
+        assert np.array_equal(got["n_invalid"][k], want["n_invalid"])
+    assert not np.array_equal(got["cost"][0], got["cost"][19])
+    B.close(); P.close()
