@@ -41,6 +41,8 @@ EXPORTED = [
     "ea_problem_set_ref_frame_ros_scaled", "ea_problem_set_now_frame_ros_scaled", "ea_resize_half",
     "ea_problem_get_points", "ea_problem_get_dt",
     "ea_problem_set_distortion", "ea_problem_set_second_camera", "ea_problem_add_term", "ea_problem_clear_terms",
+    "ea_default_covariance_options", "ea_problem_covariance", "ea_batch_covariance", "ea_tracker_set_covariance",
+    "ea_tracker_last_covariance",
 ]
 
 # measurement hooks (edge_alignment_amd/csrc/ea_hip_dev.h): bound by bench.py, the A/B scripts and the tests that pin the
@@ -95,6 +97,20 @@ class Summary(C.Structure):
                 ("it_step_norm", C.c_double * MAX_TRACE),
                 ("it_relative_decrease", C.c_double * MAX_TRACE),
                 ("it_radius", C.c_double * MAX_TRACE), ("it_successful", C.c_int * MAX_TRACE)]
+
+
+COV_SPARSE_QR, COV_DENSE_SVD = 0, 1
+
+
+class CovarianceOptions(C.Structure):
+    _fields_ = [("algorithm", C.c_int), ("min_reciprocal_condition_number", C.c_double), ("null_space_rank", C.c_int),
+                ("apply_loss_function", C.c_int)]
+
+
+class Covariance(C.Structure):
+    _fields_ = [("ok", C.c_int), ("why", C.c_int), ("rank", C.c_int), ("n_invalid", C.c_int64), ("cost", C.c_double),
+                ("eigenvalues", C.c_double * 6), ("tangent", C.c_double * 36), ("qq", C.c_double * 16),
+                ("qt", C.c_double * 12), ("tt", C.c_double * 9)]
 
 
 _lib = None
@@ -206,6 +222,13 @@ def load():
     L.ea_problem_set_second_camera.argtypes = [vp, dp, dp]
     L.ea_problem_add_term.argtypes = [vp, vp]
     L.ea_problem_clear_terms.argtypes = [vp]
+    covp, covop = C.POINTER(Covariance), C.POINTER(CovarianceOptions)
+    L.ea_default_covariance_options.argtypes = [covop]
+    L.ea_default_covariance_options.restype = None
+    L.ea_problem_covariance.argtypes = [vp, dp, dp, covop, covp]
+    L.ea_batch_covariance.argtypes = [vp, dp, dp, covop, covp]
+    L.ea_tracker_set_covariance.argtypes = [vp, covop]
+    L.ea_tracker_last_covariance.argtypes = [vp, covp]
     _lib = L
     return L
 
@@ -241,6 +264,29 @@ def default_options(**kw):
 
 _TRACE_FIELDS = ("it_cost", "it_cost_change", "it_gradient_max_norm", "it_step_norm", "it_relative_decrease", "it_radius")
 _TRACE_OFF = Summary.it_cost.offset // 8
+
+
+def covariance_options(**kw):
+    """ea_covariance_options: defaults of ceres::Covariance::Options (SPARSE_QR, 1e-14, 0, apply_loss_function) with
+    keyword overrides; algorithm may be given as "sparse_qr" / "dense_svd" """
+    o = CovarianceOptions()
+    load().ea_default_covariance_options(C.byref(o))
+    for k, v in kw.items():
+        if k == "algorithm" and isinstance(v, str):
+            v = {"sparse_qr": COV_SPARSE_QR, "dense_svd": COV_DENSE_SVD}[v.lower()]
+        if not hasattr(o, k):
+            raise KeyError(k)
+        setattr(o, k, int(v) if k != "min_reciprocal_condition_number" else float(v))
+    return o
+
+
+def covariance_to_dict(c):
+    """ea_covariance -> dict of numpy arrays: tangent (6, 6), qq (4, 4), qt (4, 3), tt (3, 3), eigenvalues (6,)"""
+    def arr(a, shape):
+        return np.frombuffer(a, dtype=np.float64).reshape(shape).copy()
+    return dict(ok=bool(c.ok), why=c.why, rank=c.rank, n_invalid=c.n_invalid, cost=c.cost,
+                eigenvalues=arr(c.eigenvalues, (6,)), tangent=arr(c.tangent, (6, 6)), qq=arr(c.qq, (4, 4)),
+                qt=arr(c.qt, (4, 3)), tt=arr(c.tt, (3, 3)))
 
 
 def summary_to_dict(s):
@@ -579,6 +625,14 @@ class Problem:
         _check(load().ea_solve(self._h, C.byref(o), _dp(q), _dp(t), C.byref(s)))
         return q, t, summary_to_dict(s)
 
+    def covariance(self, q, t, **opts):
+        """ceres::Covariance at (q, t) (ea_problem_covariance); opts: fields of ea_covariance_options -> covariance_to_dict"""
+        q, t = _f64(q), _f64(t)
+        o = covariance_options(**opts)
+        c = Covariance()
+        _check(load().ea_problem_covariance(self._h, _dp(q), _dp(t), C.byref(o), C.byref(c)))
+        return covariance_to_dict(c)
+
 
 class Tracker:
     """frame-to-frame driver: push_frame aligns the previous frame's edge points against the new frame"""
@@ -602,6 +656,17 @@ class Tracker:
                                             depth_u16.ctypes.data_as(C.POINTER(C.c_uint16)), H, W, z_scaling, C.byref(o),
                                             _dp(q), _dp(t), C.byref(s), C.byref(aligned)))
         return q, t, (summary_to_dict(s) if aligned.value else None)
+
+    def set_covariance(self, enabled=True, **opts):
+        """covariance of every aligned frame at the pose push_frame returns (ea_tracker_set_covariance); False = off"""
+        o = covariance_options(**opts) if enabled else None
+        _check(load().ea_tracker_set_covariance(self._h, C.byref(o) if o is not None else None))
+
+    def last_covariance(self):
+        """the covariance of the last push (covariance_to_dict); EAError(EA_ERR_STATE) when it did not align"""
+        c = Covariance()
+        _check(load().ea_tracker_last_covariance(self._h, C.byref(c)))
+        return covariance_to_dict(c)
 
     def close(self):
         if self._h:
@@ -750,6 +815,14 @@ class Batch:
         _check(load().ea_batch_eval(self._h, _dp(q), _dp(t), _dp(cost), _dp(JtJ), _dp(Jtr),
                                     bad.ctypes.data_as(C.POINTER(C.c_int64))))
         return dict(cost=cost, JtJ=JtJ, Jtr=Jtr, n_invalid=bad)
+
+    def covariance(self, q, t, **opts):
+        """ea_batch_covariance: one covariance per problem at q (n, 4), t (n, 3) -> list of covariance_to_dict"""
+        q, t = _f64(q).reshape(-1, 4), _f64(t).reshape(-1, 3)
+        o = covariance_options(**opts)
+        out = (Covariance * len(self))()
+        _check(load().ea_batch_covariance(self._h, _dp(q), _dp(t), C.byref(o), out))
+        return [covariance_to_dict(c) for c in out]
 
     def _pose_outputs(self, K):
         n = len(self)

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/ea_hip.h"
+#include "ea_cov.h"
 #include "ea_hip_dev.h"
 #include "ea_lm.h"
 #include "ea_spin.h"
@@ -470,6 +471,12 @@ struct ea_batch {
   int64_t rows_cap = 0;
   unsigned int *d_rows_invalid = nullptr;
   int t_rows_staged = -1, t_rows_nt = -1;
+  // covariance (ea_batch_covariance): descriptors with the loss forced to trivial (apply_loss_function = 0) and the
+  // results, written by the device into pinned host memory (dv_cov = the device's view of h_cov)
+  unsigned char *h_cdesc = nullptr;
+  ProblemDesc *d_cprobs = nullptr;
+  int cdesc_cap = 0;
+  ea_covariance *h_cov = nullptr, *dv_cov = nullptr;
 };
 
 static int check_device(int device) {
@@ -901,6 +908,8 @@ static void kposes_free(ea_batch *b) {
 
 static void batch_free_device(ea_batch *b) {
   kposes_free(b);
+  cached_free(b->d_cprobs); cached_host_free(b->h_cdesc); cached_host_free(b->h_cov);
+  b->d_cprobs = nullptr; b->h_cdesc = nullptr; b->cdesc_cap = 0; b->h_cov = nullptr; b->dv_cov = nullptr;
   (void)hipFree(b->d_rows_r); (void)hipFree(b->d_rows_J); (void)hipFree(b->d_rows_invalid);
   b->d_rows_r = b->d_rows_J = nullptr; b->d_rows_invalid = nullptr; b->rows_cap = 0;
   if (b->bench_graph) { (void)hipGraphExecDestroy(b->bench_graph); b->bench_graph = nullptr; b->bench_graph_steps = 0; b->bench_riding_steps = 0; }
@@ -2425,6 +2434,129 @@ extern "C" int ea_cost(ea_problem *p, const double q[4], const double t[3], doub
   return ea_eval(p, q, t, cost, nullptr, nullptr, n_invalid);
 }
 
+// ---- pose covariance (ceres::Covariance at one pose per problem; ea_cov.h) ----------------------------------------------
+// One call = the evaluation ea_batch_eval runs (same descriptors, launch shape and fold, so the covariance inverts exactly
+// the JtJ ea_eval returns at that pose) -> fold into the device result array -> ea_cov_kernel, one lane per problem: the
+// 6x6 Jacobi decomposition, the rank rule, the (pseudo-)inverse and the ambient lift, written straight into pinned host
+// memory; the kernel's last workgroup raises the completion flag the host polls (wait_results).  Three launches, one
+// synchronisation.  The covariance is a few thousand flops per problem on one lane: a separate kernel behind the fold costs
+// one launch gap (~1.5 us) and leaves the fold and the solve kernels exactly as they are.  Nothing of the pose-batched
+// path (ea_batch_set_poses) is touched: resident poses survive.
+static __global__ __launch_bounds__(64) void ea_cov_kernel(const EvalOut *__restrict__ sums, const PoseState *__restrict__ poses,
+                                                           CovOptions o, int count, ea_covariance *__restrict__ out,
+                                                           unsigned int *__restrict__ counter, int *__restrict__ host_flag, int seq) {
+  const int i = (int)(blockIdx.x * 64 + threadIdx.x);
+  if (i < count) cov_from_acc(sums[i].acc, poses[i].q, 1, o, &out[i]);
+  __threadfence_system();  // (this wavefront's stores to host memory are visible before it counts itself in)
+  if (threadIdx.x == 0) {
+    const unsigned int prev = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    if (prev == gridDim.x - 1) {
+      __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __threadfence_system();
+      __hip_atomic_store(host_flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+}
+
+extern "C" void ea_default_covariance_options(ea_covariance_options *o) {
+  if (!o) return;
+  o->algorithm = EA_COV_SPARSE_QR;
+  o->min_reciprocal_condition_number = 1e-14;
+  o->null_space_rank = 0;
+  o->apply_loss_function = 1;
+}
+
+static int check_cov_options(const ea_covariance_options *o) {
+  if (o->algorithm != EA_COV_SPARSE_QR && o->algorithm != EA_COV_DENSE_SVD) return fail(EA_ERR_INVALID_ARG, "unknown covariance algorithm");
+  if (o->null_space_rank < -1 || o->null_space_rank > 6) return fail(EA_ERR_INVALID_ARG, "null_space_rank outside [-1, 6]");
+  if (!(o->min_reciprocal_condition_number >= 0.0)) return fail(EA_ERR_INVALID_ARG, "min_reciprocal_condition_number must be >= 0");
+  return EA_OK;
+}
+
+// no problem or batch exists without a device; this answers the "no device" question before a handle is dereferenced
+static int require_device() {
+  int cnt = 0;
+  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0)
+    return fail(EA_ERR_NO_DEVICE, "no HIP device available (libea_hip has no CPU fallback)");
+  return EA_OK;
+}
+
+static int64_t problem_points(const ea_problem *p) {
+  int64_t n = p->n;
+  for (const ea_problem *t : p->terms) n += t->n;
+  return n;
+}
+
+static int batch_covariance(ea_batch *b, const double *q, const double *t, const ea_covariance_options *o, ea_covariance *out) {
+  int rc = batch_build(b);
+  if (rc != EA_OK) return rc;
+  const int count = (int)b->probs.size();
+  if (!b->h_cov) {
+    HIPCHK(cached_host_malloc(reinterpret_cast<void **>(&b->h_cov), (size_t)count * sizeof(ea_covariance), hipHostMallocMapped, b->device));
+    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&b->dv_cov), b->h_cov, 0));
+  }
+  // raw rows: the same descriptors with the loss forced to trivial (the problems keep their loss, versions and resident poses)
+  const ProblemDesc *probs = b->d_probs;
+  if (!o->apply_loss_function) {
+    const ProblemDesc *hd = reinterpret_cast<const ProblemDesc *>(b->h_desc);  // (batch_build's staging block)
+    bool forced = false;
+    for (int j = 0; j < b->nterms; ++j) forced = forced || hd[j].loss_kind != EA_LOSS_TRIVIAL;
+    if (forced) {
+      if (b->cdesc_cap < b->nterms) {
+        HIPCHK(hipStreamSynchronize(b->stream));
+        cached_free(b->d_cprobs); cached_host_free(b->h_cdesc);
+        b->d_cprobs = nullptr; b->h_cdesc = nullptr; b->cdesc_cap = 0;
+        HIPCHK(cached_malloc(reinterpret_cast<void **>(&b->d_cprobs), (size_t)b->nterms * sizeof(ProblemDesc), b->device));
+        HIPCHK(cached_host_malloc(reinterpret_cast<void **>(&b->h_cdesc), (size_t)b->nterms * sizeof(ProblemDesc), hipHostMallocDefault, b->device));
+        b->cdesc_cap = b->nterms;
+      }
+      ProblemDesc *cd = reinterpret_cast<ProblemDesc *>(b->h_cdesc);
+      for (int j = 0; j < b->nterms; ++j) { cd[j] = hd[j]; cd[j].loss_kind = EA_LOSS_TRIVIAL; }
+      // (the previous call out of this staging block is complete: every call returns on its results)
+      HIPCHK(hipMemcpyAsync(b->d_cprobs, cd, (size_t)b->nterms * sizeof(ProblemDesc), hipMemcpyHostToDevice, b->stream));
+      probs = b->d_cprobs;
+    }
+  }
+  if ((rc = batch_upload_poses(b, q, t)) != EA_OK) return rc;
+  HIPCHK(launch_eval_fused(b->dtype, b->ppt, b->nt, b->any_variant, probs, b->nterms, b->chunk, b->max_chunks, b->xcd_remap, b->d_poses,
+                           b->d_partials, b->lds_bytes, b->wide, b->terms_are_groups, b->buffer_loads, b->img32, b->x0, b->y0, b->z0,
+                           b->n0, b->stream));
+  HIPCHK(launch_reduce(b->d_groups, count, b->d_partials, b->d_out, b->stream));
+  const CovOptions co = {o->algorithm, o->min_reciprocal_condition_number, o->null_space_rank};
+  b->done_seq = b->done_seq == 0x7fffffff ? 1 : b->done_seq + 1;
+  hipLaunchKernelGGL(ea_cov_kernel, dim3((count + 63) / 64), dim3(64), 0, b->stream, b->d_out, b->d_poses, co, count, b->dv_cov,
+                     b->d_done_count, b->d_progress + 3 * (size_t)count, b->done_seq);
+  HIPCHK(hipGetLastError());
+  if ((rc = wait_results(b)) != EA_OK) return rc;
+  std::memcpy(out, b->h_cov, (size_t)count * sizeof(ea_covariance));
+  for (int i = 0; i < count; ++i)
+    if (problem_points(b->probs[(size_t)i]) == 0) {  // zero sums: "no points" rather than "rank deficient"
+      out[i].ok = 0; out[i].why = 3; out[i].rank = 0;
+    }
+  return EA_OK;
+}
+
+extern "C" int ea_batch_covariance(ea_batch *b, const double *q, const double *t, const ea_covariance_options *o, ea_covariance *out) {
+  if (!b || !q || !t || !o || !out) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  int rc = check_cov_options(o);
+  if (rc == EA_OK) rc = require_device();
+  if (rc != EA_OK) return rc;
+  return batch_covariance(b, q, t, o, out);
+}
+
+extern "C" int ea_problem_covariance(ea_problem *p, const double q[4], const double t[3], const ea_covariance_options *o,
+                                     ea_covariance *out) {
+  if (!p || !q || !t || !o || !out) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  int rc = check_cov_options(o);
+  if (rc == EA_OK) rc = require_device();
+  if (rc != EA_OK) return rc;
+  ea_batch *b;
+  if ((rc = self_batch(p, &b)) != EA_OK) return rc;
+  if ((rc = batch_build(b)) != EA_OK) return rc;  // (no DT image: EA_ERR_STATE, as ea_eval)
+  if (problem_points(p) == 0) return fail(EA_ERR_STATE, "no edge points (ea_problem_set_points)");
+  return batch_covariance(b, q, t, o, out);
+}
+
 // the reference's integer-pixel cost report (standalone_edge_align.cpp:2494-2567, :2704-2776)
 extern "C" int ea_problem_pixel_cost(ea_problem *p, const double q[4], const double t[3], ea_pixel_cost *out) {
   if (!q || !t || !out) return fail(EA_ERR_INVALID_ARG, "NULL argument");
@@ -2827,6 +2959,10 @@ struct ea_tracker {
   int flavour = 0;      // 0: get_aX / get_distance_transform, 1: Canny (get_aX_canny / get_distance_transform2)
   int frames = 0;
   double q[4] = {1, 0, 0, 0}, t[3] = {0, 0, 0};
+  // ea_tracker_set_covariance: the covariance of every aligned frame at the pose it returns
+  bool cov_on = false, cov_valid = false;
+  ea_covariance_options cov_opt{};
+  ea_covariance cov_last{};
 };
 
 extern "C" int ea_tracker_create(ea_tracker **out, const ea_camera *cam, int dtype, int device, int flavour) {
@@ -2865,6 +3001,7 @@ extern "C" int ea_tracker_push_frame(ea_tracker *tr, const uint8_t *bgr, const u
   std::memcpy(q_new, tr->q, sizeof(q_new));
   std::memcpy(t_new, tr->t, sizeof(t_new));
   RefPointsJob job;
+  tr->cov_valid = false;
   if (tr->frames > 0 && ea_problem_num_points(tr->p) > 0) {
     rc = tr->flavour == 0 ? ea_problem_set_now_frame(tr->p, bgr, height, width, 35, 1, 1)
                           : ea_problem_set_now_frame_canny(tr->p, bgr, nullptr, height, width, 30, 90, 1, 0.0, 1.0);
@@ -2884,6 +3021,23 @@ extern "C" int ea_tracker_push_frame(ea_tracker *tr, const uint8_t *bgr, const u
     if (s.termination != EA_FAILURE) {
       std::memcpy(q_new, q, sizeof(q));
       std::memcpy(t_new, t, sizeof(t));
+    }
+    if (tr->cov_on) {
+      // The solve's points and DT image are still the problem's: ea_problem_covariance returns only once its results have
+      // landed, i.e. once its evaluation on the batch's stream has read them, and ref_points_finish -- the only step that
+      // overwrites the points -- is enqueued on the null stream after that.  ref_points_begin, already in flight on the null
+      // stream, writes nothing but the workspace of the frame producers, which the evaluation does not read.
+      std::memset(&tr->cov_last, 0, sizeof(tr->cov_last));
+      if (s.termination != EA_FAILURE) {
+        rc = ea_problem_covariance(tr->p, q, t, &tr->cov_opt, &tr->cov_last);
+        if (rc != EA_OK) {
+          if (job.started) (void)hipDeviceSynchronize();
+          return rc;
+        }
+      } else {
+        tr->cov_last.why = 4;  // no pose to take the covariance at
+      }
+      tr->cov_valid = true;
     }
     if (summary) *summary = s;
     if (aligned) *aligned = 1;
@@ -2908,6 +3062,26 @@ extern "C" int ea_tracker_push_frame(ea_tracker *tr, const uint8_t *bgr, const u
   std::memcpy(q_rel, tr->q, sizeof(tr->q));
   std::memcpy(t_rel, tr->t, sizeof(tr->t));
   tr->frames += 1;
+  return EA_OK;
+}
+
+extern "C" int ea_tracker_set_covariance(ea_tracker *tr, const ea_covariance_options *o) {
+  if (!tr) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (o) {
+    const int rc = check_cov_options(o);
+    if (rc != EA_OK) return rc;
+    tr->cov_opt = *o;
+  }
+  tr->cov_on = o != nullptr;
+  tr->cov_valid = false;
+  return EA_OK;
+}
+
+extern "C" int ea_tracker_last_covariance(ea_tracker *tr, ea_covariance *out) {
+  if (!tr || !out) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (!tr->cov_on) return fail(EA_ERR_STATE, "covariance is off (ea_tracker_set_covariance)");
+  if (!tr->cov_valid) return fail(EA_ERR_STATE, "the last push did not align a frame");
+  *out = tr->cov_last;
   return EA_OK;
 }
 

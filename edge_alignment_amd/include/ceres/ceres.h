@@ -384,6 +384,14 @@ class ProblemAccess {  // keeps Problem's internals private to user code
     return rc;
   }
 
+  // the (quaternion, translation) pair every block of the problem shares; false for an empty problem
+  static bool PoseBlocks(const Problem *problem, double **q, double **t) {
+    if (problem->blocks_.empty()) return false;
+    *q = problem->blocks_[0].q;
+    *t = problem->blocks_[0].t;
+    return true;
+  }
+
   static bool Evaluate(Problem *problem, const Problem::EvaluateOptions &opt, double *cost, std::vector<double> *residuals,
                        std::vector<double> *gradient, CRSMatrix *jacobian) {
     const auto &blocks = problem->blocks_;
@@ -500,3 +508,5 @@ inline void Solve(const Solver::Options &options, Problem *problem, Solver::Summ
 }
 
 }  // namespace ceres
+
+#include "covariance.h"

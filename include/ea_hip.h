@@ -331,6 +331,52 @@ int ea_batch_eval_poses(ea_batch *b, int K, const double *q, const double *t, do
 int ea_batch_set_poses(ea_batch *b, int K, const double *q, const double *t);
 int ea_batch_eval_resident_poses(ea_batch *b, double *cost, double *JtJ, double *Jtr, int64_t *n_invalid);
 
+/* ---- pose covariance: ceres::Covariance (Ceres <= 2.1) at one pose per problem ----------------------------------------
+ * C = (JtJ)^-1 over the tangent coordinates [delta(3) | t(3)]: the JtJ ea_eval returns at that pose (every term of the
+ * problem summed in), loss-corrected rows sum rho' J J^T when apply_loss_function != 0 (every shipped loss has
+ * rho'' <= 0), raw rows sum J J^T otherwise.  A residual block whose functor fails at the pose (n_invalid > 0) leaves
+ * the covariance "not computed", as Ceres' failed Jacobian evaluation does.
+ * Rank: eigenvalues lambda_1 >= ... >= lambda_6 of JtJ (the squared singular values of J).
+ *   EA_COV_DENSE_SVD: max_rank = 6 - null_space_rank; for i < max_rank lambda_i / lambda_1 >= min_reciprocal_condition_number,
+ *     a failure = "not computed" when null_space_rank >= 0, truncation from there on when it is -1; C = the
+ *     pseudo-inverse over the kept eigenpairs.
+ *   EA_COV_SPARSE_QR (Ceres' default): full rank required, C = the plain inverse.  DEVIATION: Ceres decides the rank by
+ *     SuiteSparseQR's column-norm tolerance; here by the DENSE_SVD test with null_space_rank = 0.
+ * Ambient blocks (GetCovarianceBlock): qq = L C_dd L^T, qt = L C_dt, tt = C_tt, with L the 4x3
+ * QuaternionParameterization::ComputeJacobian at q as given (not normalised).
+ * A rank-deficient system is a RESULT (ok = 0), not an error.  The evaluation, the decomposition and the lift run on the
+ * device, behind one synchronisation; resident poses (ea_batch_set_poses) are left in place. */
+typedef enum { EA_COV_SPARSE_QR = 0, EA_COV_DENSE_SVD = 1 } ea_cov_algorithm;
+typedef struct {
+  int algorithm;                           /* ea_cov_algorithm */
+  double min_reciprocal_condition_number;  /* 1e-14 */
+  int null_space_rank;                     /* 0; -1 = automatic truncation (DENSE_SVD) */
+  int apply_loss_function;                 /* 1 */
+} ea_covariance_options;
+typedef struct {
+  int ok;                  /* 1: computed */
+  int why;                 /* 0 ok, 1 rank deficient / ill-conditioned, 2 invalid residual blocks, 3 no points,
+                              4 (tracker) the solve failed */
+  int rank;                /* eigenpairs kept */
+  int64_t n_invalid;       /* blocks whose functor failed at the pose */
+  double cost;             /* 1/2 sum rho(r^2) (1/2 sum r^2 with the loss off) */
+  double eigenvalues[6];   /* of JtJ, descending */
+  double tangent[36];      /* 6x6 row-major, [delta | t] */
+  double qq[16], qt[12], tt[9];  /* ambient blocks, row-major */
+} ea_covariance;
+void ea_default_covariance_options(ea_covariance_options *o);  /* SPARSE_QR, 1e-14, 0, 1 */
+/* q, t: the pose; EA_ERR_STATE for a problem without points or DT image (as ea_eval) */
+int ea_problem_covariance(ea_problem *p, const double q[4], const double t[3], const ea_covariance_options *o,
+                          ea_covariance *out);
+/* q: count x 4, t: count x 3, out: count entries; a problem without points gives ok = 0, why = 3 */
+int ea_batch_covariance(ea_batch *b, const double *q, const double *t, const ea_covariance_options *o, ea_covariance *out);
+/* o = NULL: off (default).  On: every ea_tracker_push_frame that solves computes the covariance at the pose it returns,
+ * from the points and DT image that solve used (before the new frame's points replace them). */
+int ea_tracker_set_covariance(ea_tracker *tr, const ea_covariance_options *o);
+/* the covariance of the last push (ok = 0 when its solve failed); EA_ERR_STATE when the last push did not align or
+ * covariance is off */
+int ea_tracker_last_covariance(ea_tracker *tr, ea_covariance *out);
+
 /* ---- materialised mode: the "EAResidue batch Evaluate" view -------------------------------------------------------
  * Replaces N calls of ceres::AutoDiffCostFunction<EAResidue,1,4,3>::Evaluate followed by the parameterisation's 4x3
  * plus-Jacobian (standalone/utils.h:48-92, standalone_edge_align.cpp:261-278): residual r and the effective 1x6 row

@@ -1,0 +1,32 @@
+// Host build of the product's covariance code (edge_alignment_amd/csrc/ea_cov.h, the code ea_cov_kernel runs) and of the
+// ceres:: facade's QuaternionParameterization::Plus.  Test-only: the CPU suite checks the decomposition, the rank rules,
+// the pseudo-inverse and the ambient lift against numpy without a GPU.
+#include <cstring>
+
+#include "ea_cov.h"
+#include "ceres/ceres.h"
+
+extern "C" {
+
+// JtJ (6x6 row-major, symmetric) -> eigenvalues (descending) and eigenvectors (columns of V, row-major)
+void ea_cov_host_eigh(const double A[36], double lam[6], double V[36]) { ea::cov_eigh(A, lam, V); }
+
+// the whole per-problem computation from a JtJ, an invalid-block count and the pose's quaternion
+void ea_cov_host_compute(const double A[36], double n_invalid, const double q[4], const ea_covariance_options *o,
+                         ea_covariance *out) {
+  double acc[ea::kAccSlots];
+  std::memset(acc, 0, sizeof(acc));
+  int k = 0;
+  for (int a = 0; a < 6; ++a)
+    for (int c = a; c < 6; ++c) acc[ea::kAccJtJ + k++] = A[6 * a + c];
+  acc[ea::kAccInvalid] = n_invalid;
+  const ea::CovOptions co = {o->algorithm, o->min_reciprocal_condition_number, o->null_space_rank};
+  ea::cov_from_acc(acc, q, 1, co, out);
+}
+
+// the facade's x (+) delta, for Jacobians by differences that do not trust the hand-written L
+void ea_cov_host_quat_plus(const double x[4], const double delta[3], double out[4]) {
+  ceres::QuaternionParameterization().Plus(x, delta, out);
+}
+
+}  // extern "C"

@@ -1,0 +1,236 @@
+"""Pose covariance on the device (ea_problem_covariance / ea_batch_covariance / the tracker / ceres::Covariance) against
+the oracle's JtJ, ea_eval's JtJ and numpy: C = (JtJ)^-1 in the tangent ordering [delta | t], ambient blocks through the
+quaternion parameterisation's Jacobian, Ceres' rank rules on degenerate systems."""
+import os
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+from edge_alignment_amd import synth
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+G = os.path.join(ROOT, "tests", "golden", "rgbd")
+K = (525.0, 525.0, 319.5, 239.5)
+
+
+def _rel(a, b):
+    return np.abs(np.asarray(a) - np.asarray(b)).max() / max(np.abs(np.asarray(b)).max(), 1e-300)
+
+
+def _L(q):
+    return np.array([[-q[1], -q[2], -q[3]], [q[0], q[3], -q[2]], [-q[3], q[0], q[1]], [q[2], -q[1], q[0]]])
+
+
+def _check_lift(c, q):
+    L, T = _L(q), c["tangent"]
+    assert _rel(c["qq"], L @ T[:3, :3] @ L.T) <= 1e-12
+    assert _rel(c["qt"], L @ T[:3, 3:]) <= 1e-12
+    assert np.array_equal(c["tt"], T[3:, 3:])
+
+
+def _bundled_problem(hip, bundled_pair, stride, dtype=None):
+    P = hip.Problem(*bundled_pair["K"], dtype=hip.EA_F64 if dtype is None else dtype)
+    X = bundled_pair["aX"][:3, ::stride].T.copy()
+    P.set_points(X)
+    P.set_dt_grid(bundled_pair["grids"][3])
+    return P, X
+
+
+@pytest.mark.parametrize("stride", [30, 1])
+def test_bundled_pair_at_solved_pose(hip, oracle, bundled_pair, stride):
+    P, X = _bundled_problem(hip, bundled_pair, stride)
+    q, t, s = P.solve([1, 0, 0, 0], [0, 0, 0])
+    assert s["termination"] == hip.CONVERGENCE
+    c = P.covariance(q, t)
+    assert c["ok"] and c["why"] == 0 and c["rank"] == 6 and c["n_invalid"] == 0
+    O = oracle.OracleProblem(bundled_pair["grids"][3], *bundled_pair["K"])
+    eo = O.eval(X, q, t)
+    assert _rel(c["tangent"], np.linalg.inv(eo["JtJ"])) <= 1e-8
+    g = P.eval(q, t)
+    assert _rel(c["tangent"], np.linalg.inv(g["JtJ"])) <= 1e-12
+    assert c["cost"] == g["cost"]
+    assert _rel(c["eigenvalues"], np.linalg.eigvalsh(g["JtJ"])[::-1]) <= 1e-12
+    _check_lift(c, q)
+    # DENSE_SVD on a full-rank system: the same inverse
+    d = P.covariance(q, t, algorithm="dense_svd")
+    assert d["ok"] and np.array_equal(d["tangent"], c["tangent"])
+    P.close()
+
+
+def test_raw_rows_without_loss(hip, bundled_pair):
+    P, X = _bundled_problem(hip, bundled_pair, 30)
+    q, t, _ = P.solve([1, 0, 0, 0], [0, 0, 0])
+    before = P.eval(q, t)
+    c = P.covariance(q, t, apply_loss_function=0)
+    r, J = P.eval_points(q, t, corrected=False)
+    assert c["ok"]
+    assert _rel(c["tangent"], np.linalg.inv(J.T @ J)) <= 1e-10
+    assert c["cost"] == pytest.approx(0.5 * np.sum(r * r), rel=1e-12)
+    # the problem keeps its loss: the loss-corrected system afterwards is what it was
+    after = P.eval(q, t)
+    assert np.array_equal(after["JtJ"], before["JtJ"]) and after["cost"] == before["cost"]
+    assert _rel(P.covariance(q, t)["tangent"], np.linalg.inv(before["JtJ"])) <= 1e-12
+    P.close()
+
+
+def _c4_batch(hip, dtype, n=32):
+    from oracle import preprocess_np as pp
+    rgb = {k: pp.load_rgb_as_bgr(os.path.join(G, "rgb_%d.png" % k)) for k in range(1, 6)}
+    dep = {k: pp.load_depth_u16(os.path.join(G, "depth_%d.png" % k)) for k in range(1, 6)}
+    pairs = [(a, b) for a in range(1, 6) for b in range(1, 6) if a != b]
+    rng = np.random.default_rng(4)
+    Ps, q0s, t0s = [], [], []
+    for i in range(n):
+        a, b = pairs[i % len(pairs)]
+        P = hip.Problem(*K, dtype=dtype)
+        P.set_ref_frame(rgb[a], dep[a])
+        P.set_now_frame(rgb[b])
+        Ps.append(P)
+        q0s.append(synth.quat_from_axis_angle(rng.normal(size=3), np.deg2rad(rng.uniform(0, 1.0))))
+        t0s.append(rng.uniform(-0.02, 0.02, 3) / np.sqrt(3))
+    return Ps, np.array(q0s), np.array(t0s)
+
+
+# fp32 batches: the per-point products are float and the batch and the lone problem take different launch shapes, so the
+# two JtJ differ by float rounding (~1e-6 relative); their inverses by that times the condition number (~1e2)
+@pytest.mark.parametrize("dtype_name,tol", [("EA_F64", 1e-12), ("EA_F32", 1e-3)])
+def test_c4_batch_matches_single_problems(hip, dtype_name, tol):
+    dtype = getattr(hip, dtype_name)
+    Ps, q0, t0 = _c4_batch(hip, dtype)
+    B = hip.Batch(Ps)
+    q, t, ss = B.solve(q0, t0)
+    assert all(s["termination"] != hip.FAILURE for s in ss)
+    # resident poses of the pose-batched path survive a covariance call
+    Kp = 3
+    qk = np.repeat(q[None], Kp, axis=0)
+    tk = np.repeat(t[None], Kp, axis=0) + 1e-3 * np.arange(Kp)[:, None, None]
+    B.set_poses(qk, tk)
+    res0 = B.eval_resident_poses()
+    cb = B.covariance(q, t)
+    res1 = B.eval_resident_poses()
+    for k in ("cost", "JtJ", "Jtr", "n_invalid"):
+        assert np.array_equal(res0[k], res1[k]), k
+    be = B.eval(q, t)
+    for i, P in enumerate(Ps):
+        ci = P.covariance(q[i], t[i])
+        assert cb[i]["ok"] and ci["ok"]
+        assert _rel(cb[i]["tangent"], ci["tangent"]) <= tol, i
+        assert _rel(cb[i]["tangent"], np.linalg.inv(be["JtJ"][i])) <= (1e-12 if dtype == hip.EA_F64 else 1e-9)
+        _check_lift(cb[i], q[i])
+    B.close()
+    for P in Ps:
+        P.close()
+
+
+def test_second_camera_term_is_covered(hip):
+    K1 = (130.0, 132.0, 79.5, 59.5)
+    K2 = (128.0, 129.0, 81.0, 58.0)
+    T12 = synth.rigid_4x4(synth.quat_from_axis_angle([0.1, 1.0, 0.2], 0.04), [0.11, 0.004, -0.012])
+    Q = synth.quat_from_axis_angle([1, 2, 3], np.deg2rad(1.0))
+    fams = synth.make_stereo_problem(120, 160, 4000, 2500, 6, K1, K2, T12, Q, np.array([0.01, -0.005, 0.02]))
+    P1 = hip.Problem(*K1)
+    P1.set_points(fams[0]["xyz"]); P1.set_dt_grid(fams[0]["grid"])
+    P2 = hip.Problem(*K2)
+    P2.set_points(fams[1]["xyz"]); P2.set_dt_grid(fams[1]["grid"]); P2.set_second_camera(T12)
+    P1.add_term(P2)
+    q, t, s = P1.solve([1, 0, 0, 0], [0, 0, 0])
+    c = P1.covariance(q, t)
+    g = P1.eval(q, t)
+    g1 = P1.eval_points(q, t)  # (the first family alone)
+    assert c["ok"] and _rel(c["tangent"], np.linalg.inv(g["JtJ"])) <= 1e-12
+    assert not np.allclose(np.linalg.inv(g1[1].T @ g1[1]), c["tangent"], rtol=1e-3)  # the second family is in it
+    assert P1.covariance(q, t, apply_loss_function=0)["ok"]
+    _check_lift(c, q)
+    P1.close(); P2.close()
+
+
+def test_degenerate_systems(hip, bundled_pair):
+    P, X = _bundled_problem(hip, bundled_pair, 30)
+    P1 = hip.Problem(*bundled_pair["K"])
+    P1.set_points(X[:1])
+    P1.set_dt_grid(bundled_pair["grids"][3])
+    q, t = np.array([1.0, 0, 0, 0]), np.zeros(3)
+    for opts in (dict(), dict(algorithm="dense_svd", null_space_rank=0)):
+        c = P1.covariance(q, t, **opts)
+        assert not c["ok"] and c["why"] == 1
+    c = P1.covariance(q, t, algorithm="dense_svd", null_space_rank=-1)
+    A = P1.eval(q, t)["JtJ"]
+    assert c["ok"] and c["rank"] == 1
+    assert _rel(c["tangent"], np.linalg.pinv(A)) <= 1e-10
+    # a pose that moves a point into the functor's z guard (|z| < 0.01): a failed residual block
+    tb = np.array([0.0, 0.0, -X[0, 2]])
+    assert P.eval(q, tb)["n_invalid"] > 0
+    c = P.covariance(q, tb)
+    assert not c["ok"] and c["why"] == 2 and c["n_invalid"] > 0
+    # no points: EA_ERR_STATE, as ea_eval
+    P0 = hip.Problem(*bundled_pair["K"])
+    P0.set_dt_grid(bundled_pair["grids"][3])
+    with pytest.raises(hip.EAError) as ei:
+        P0.covariance(q, t)
+    assert ei.value.code == hip.EA_ERR_STATE
+    P.close(); P1.close(); P0.close()
+
+
+def test_tracker_covariance(hip):
+    from oracle import preprocess_np as pp
+    seq = [(pp.load_rgb_as_bgr(os.path.join(G, "rgb_%d.png" % i)), pp.load_depth_u16(os.path.join(G, "depth_%d.png" % i))) for i in range(1, 4)]
+    Ton = hip.Tracker(*K, dtype=hip.EA_F64, loss=(hip.LOSS_CAUCHY, 1.0))
+    Toff = hip.Tracker(*K, dtype=hip.EA_F64, loss=(hip.LOSS_CAUCHY, 1.0))
+    Ton.set_covariance(True)
+    P = hip.Problem(*K, dtype=hip.EA_F64)
+    P.set_loss(hip.LOSS_CAUCHY, 1.0)
+    for k, (bgr, depth) in enumerate(seq):
+        q, t, s = Ton.push_frame(bgr, depth)
+        q2, t2, _ = Toff.push_frame(bgr, depth)
+        assert np.array_equal(q, q2) and np.array_equal(t, t2)  # covariance on or off: the same poses, bit for bit
+        if k == 0:
+            with pytest.raises(hip.EAError) as ei:
+                Ton.last_covariance()
+            assert ei.value.code == hip.EA_ERR_STATE
+        else:
+            c = Ton.last_covariance()
+            P.set_now_frame(bgr)
+            ref = P.covariance(q, t)  # same producers, the previous frame's points and this frame's DT image
+            assert c["ok"] and ref["ok"]
+            assert _rel(c["tangent"], ref["tangent"]) <= 1e-10
+            _check_lift(c, q)
+        P.set_ref_frame(bgr, depth)
+    with pytest.raises(hip.EAError):
+        Toff.last_covariance()  # off
+    Ton.close(); Toff.close(); P.close()
+
+
+def test_ceres_facade_prints_the_c_abi_blocks(hip, bundled_pair, tmp_path):
+    from edge_alignment_amd import capi
+    lib_dir = os.path.dirname(capi.LIB_PATH)
+    exe = str(tmp_path / "covariance_example")
+    subprocess.check_call(["g++", "-O1", "-std=c++14", "-Wall", "-Werror", "-I", os.path.join(ROOT, "edge_alignment_amd", "include"),
+                           "-o", exe, os.path.join(ROOT, "tests", "cpp", "covariance_example.cpp"),
+                           "-L", lib_dir, "-lea_hip", "-Wl,-rpath," + lib_dir, "-Wl,-rpath,/opt/rocm/lib"])
+    grid = bundled_pair["grids"][3]
+    W, H = grid.shape
+    aX = bundled_pair["aX"]
+    path = str(tmp_path / "problem.bin")
+    with open(path, "wb") as f:
+        f.write(struct.pack("<iii", aX.shape[1], H, W))
+        f.write(struct.pack("<dddd", *bundled_pair["K"]))
+        f.write(np.ascontiguousarray(aX.T, dtype=np.float64).tobytes())
+        f.write(np.ascontiguousarray(grid, dtype=np.float64).tobytes())
+    out = subprocess.run([exe, path, "30"], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stdout + out.stderr
+    v = {ln.split()[0]: np.array([float(x) for x in ln.split()[1:]]) for ln in out.stdout.splitlines() if ln.strip()}
+    P, _ = _bundled_problem(hip, bundled_pair, 30)
+    c = P.covariance(v["q"], v["t"])
+    assert c["ok"]
+    assert np.array_equal(v["qq"].reshape(4, 4), c["qq"]) and np.array_equal(v["qt"].reshape(4, 3), c["qt"])
+    assert np.array_equal(v["tt"].reshape(3, 3), c["tt"])
+    assert np.array_equal(v["tangent"].reshape(6, 6), c["tangent"])
+    assert np.array_equal(v["tangent_qq"].reshape(3, 3), c["tangent"][:3, :3])
+    assert np.array_equal(v["tangent_qt"].reshape(3, 3), c["tangent"][:3, 3:])
+    full = v["full"].reshape(7, 7)
+    assert np.array_equal(full[:4, :4], c["qq"]) and np.array_equal(full[:4, 4:], c["qt"])
+    assert np.array_equal(full[4:, :4], c["qt"].T) and np.array_equal(full[4:, 4:], c["tt"])
+    P.close()
