@@ -42,7 +42,7 @@ EXPORTED = [
     "ea_problem_get_points", "ea_problem_get_dt",
     "ea_problem_set_distortion", "ea_problem_set_second_camera", "ea_problem_add_term", "ea_problem_clear_terms",
     "ea_default_covariance_options", "ea_problem_covariance", "ea_batch_covariance", "ea_tracker_set_covariance",
-    "ea_tracker_last_covariance",
+    "ea_tracker_last_covariance", "ea_problem_set_normal_prior", "ea_tracker_set_motion_prior",
 ]
 
 # measurement hooks (edge_alignment_amd/csrc/ea_hip_dev.h): bound by bench.py, the A/B scripts and the tests that pin the
@@ -229,6 +229,8 @@ def load():
     L.ea_batch_covariance.argtypes = [vp, dp, dp, covop, covp]
     L.ea_tracker_set_covariance.argtypes = [vp, covop]
     L.ea_tracker_last_covariance.argtypes = [vp, covp]
+    L.ea_problem_set_normal_prior.argtypes = [vp, C.c_int, dp, C.c_int, dp]
+    L.ea_tracker_set_motion_prior.argtypes = [vp, C.c_double, C.c_double]
     _lib = L
     return L
 
@@ -633,6 +635,19 @@ class Problem:
         _check(load().ea_problem_covariance(self._h, _dp(q), _dp(t), C.byref(o), C.byref(c)))
         return covariance_to_dict(c)
 
+    def set_normal_prior(self, block, A, b):
+        """ceres::NormalPrior(A, b) on block 0 (q, A k x 4) or 1 (t, A k x 3) (ea_problem_set_normal_prior)"""
+        n = 4 if block == 0 else 3
+        A = np.ascontiguousarray(np.asarray(A, dtype=np.float64))
+        b = _f64(b).ravel()
+        if block in (0, 1) and (A.ndim != 2 or A.shape[1] != n or b.size != n):  # (a bad block index: the library says so)
+            raise ValueError("NormalPrior on block %d: A must be k x %d and b of size %d (got A %s, b %d)" % (block, n, n, A.shape, b.size))
+        _check(load().ea_problem_set_normal_prior(self._h, int(block), _dp(A), A.shape[0], _dp(b)))
+
+    def clear_normal_prior(self, block):
+        """drops the prior on block 0 (q) or 1 (t)"""
+        _check(load().ea_problem_set_normal_prior(self._h, int(block), None, 0, None))
+
 
 class Tracker:
     """frame-to-frame driver: push_frame aligns the previous frame's edge points against the new frame"""
@@ -661,6 +676,10 @@ class Tracker:
         """covariance of every aligned frame at the pose push_frame returns (ea_tracker_set_covariance); False = off"""
         o = covariance_options(**opts) if enabled else None
         _check(load().ea_tracker_set_covariance(self._h, C.byref(o) if o is not None else None))
+
+    def set_motion_prior(self, sigma_rot, sigma_trans):
+        """NormalPriors centred on each solve's start pose, A = I / sigma (ea_tracker_set_motion_prior); 0 = block off"""
+        _check(load().ea_tracker_set_motion_prior(self._h, float(sigma_rot), float(sigma_trans)))
 
     def last_covariance(self):
         """the covariance of the last push (covariance_to_dict); EAError(EA_ERR_STATE) when it did not align"""

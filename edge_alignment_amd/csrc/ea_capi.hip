@@ -23,6 +23,7 @@
 #include "ea_cov.h"
 #include "ea_hip_dev.h"
 #include "ea_lm.h"
+#include "ea_prior.h"
 #include "ea_spin.h"
 #include "ea_types.h"
 
@@ -54,13 +55,14 @@ hipError_t launch_reduce_nt(int nt, const GroupDesc *groups, int count, const do
                             hipStream_t stream);
 hipError_t launch_lm_step(const GroupDesc *groups, int count, const double *partials, PoseState *poses,
                           LMState *states, LMCold *cold, LMTrace *traces, const LMOptions &opt, int *running_flags,
-                          LMState *host_states, LMTrace *host_traces, const GroupDesc &first, int post_done, hipStream_t stream);
+                          LMState *host_states, LMTrace *host_traces, const GroupDesc &first, int post_done, hipStream_t stream,
+                          int priors /* the PriorDesc table sits behind `groups` (one per problem) */);
 hipError_t launch_lm_iter(int dtype, int ppt, const ProblemDesc *probs, int count, int chunk, int max_chunks, int xcd_remap,
                           PoseState *poses, const double *rows_in, double *rows_out, int buffer_loads, int img32,
                           const void *x0, const void *y0, const void *z0, int n0, const GroupDesc *groups,
                           const LMState *st_in, LMState *st_out, const LMCold *cold_in, LMCold *cold_out, LMTrace *traces,
                           const LMOptions &opt, int *progress, LMState *host_states, LMTrace *host_traces,
-                          const GroupDesc &first, int post_done, hipStream_t stream);
+                          const GroupDesc &first, int post_done, hipStream_t stream, int priors /* as launch_lm_step */);
 hipError_t launch_pad_image(int dtype, const void *src, int H, int W, void *dst, int pitch, float *dst32, int *inexact,
                             hipStream_t stream);
 hipError_t launch_make_poses(const double *qt, int n, int count, const ProblemDesc *probs, const GroupDesc *groups,
@@ -333,6 +335,8 @@ struct ea_problem {
   double T12[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   double T12inv[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   std::vector<ea_problem *> terms;       // further residual families sharing this problem's pose
+  PriorDesc prior = {};                  // NormalPriors on q / t (ea_problem_set_normal_prior; ea_prior.h)
+  int term_of = 0;                       // how many problems hold this one as a term (a term carries no prior)
   int64_t n = 0;
   void *d_x = nullptr, *d_y = nullptr, *d_z = nullptr;
   bool own_points = false;
@@ -477,6 +481,13 @@ struct ea_batch {
   ProblemDesc *d_cprobs = nullptr;
   int cdesc_cap = 0;
   ea_covariance *h_cov = nullptr, *dv_cov = nullptr;
+  // NormalPriors: one PriorDesc per problem right behind the groups in d_desc_block (where the PRIOR instantiations of the LM
+  // kernels look for them), uploaded with them when any problem has one; any_prior = 0: the prior-free instantiations run and
+  // d_priors is NULL.  The host copy serves the results folded into host memory and the host-side state machine of
+  // ea_solve_sharded.
+  PriorDesc *d_priors = nullptr;
+  std::vector<PriorDesc> h_priors;
+  int any_prior = 0;
 };
 
 static int check_device(int device) {
@@ -650,6 +661,7 @@ extern "C" void ea_batch_destroy(ea_batch *b);
 extern "C" void ea_problem_destroy(ea_problem *p) {
   if (!p) return;
   (void)hipSetDevice(p->device);
+  for (ea_problem *tm : p->terms) tm->term_of--;
   if (p->self) ea_batch_destroy(p->self);
   free_points(p);
   if (p->d_dt) cached_free(p->d_dt);
@@ -699,14 +711,55 @@ extern "C" int ea_problem_add_term(ea_problem *p, ea_problem *term) {
   if (!term->terms.empty()) return fail(EA_ERR_INVALID_ARG, "a term cannot have terms of its own");
   if (p->device != term->device || p->dtype != term->dtype) return fail(EA_ERR_INVALID_ARG, "terms must share device and dtype");
   if (std::find(p->terms.begin(), p->terms.end(), term) != p->terms.end()) return fail(EA_ERR_INVALID_ARG, "term already added");
+  if (term->prior.has_q || term->prior.has_t)
+    return fail(EA_ERR_INVALID_ARG, "a problem with a normal prior cannot be a term (the prior belongs on the head problem)");
   p->terms.push_back(term);
+  term->term_of++;
   p->version++;
   return EA_OK;
 }
 
 extern "C" int ea_problem_clear_terms(ea_problem *p) {
   if (!p) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  for (ea_problem *tm : p->terms) tm->term_of--;
   p->terms.clear();
+  p->version++;
+  return EA_OK;
+}
+
+// ceres::NormalPrior(A, b) on block 0 (q, n = 4) or 1 (t, n = 3): H = A^T A is formed here in fp64 and kept with b (ea_prior.h)
+extern "C" int ea_problem_set_normal_prior(ea_problem *p, int block, const double *A, int k, const double *b) {
+  // (the arguments are checked first, the problem last: every check here needs no device)
+  if (block != 0 && block != 1) return fail(EA_ERR_INVALID_ARG, "block must be 0 (quaternion) or 1 (translation)");
+  if (k < 0) return fail(EA_ERR_INVALID_ARG, "k must be >= 0");
+  const bool clear = !A || k == 0;
+  const int n = block == 0 ? 4 : 3;
+  if (!clear) {
+    if (!b) return fail(EA_ERR_INVALID_ARG, "b must not be NULL when A is given");
+    for (int64_t i = 0; i < (int64_t)k * n; ++i)
+      if (!(std::fabs(A[i]) <= DBL_MAX)) return fail(EA_ERR_INVALID_ARG, "A must be finite");
+    for (int i = 0; i < n; ++i)
+      if (!(std::fabs(b[i]) <= DBL_MAX)) return fail(EA_ERR_INVALID_ARG, "b must be finite");
+  }
+  if (!p) return fail(EA_ERR_INVALID_ARG, "NULL problem");
+  if (p->term_of > 0) return fail(EA_ERR_INVALID_ARG, "a problem that is a term cannot carry a normal prior");
+  double H[16] = {0};
+  if (!clear)
+    for (int r = 0; r < k; ++r)
+      for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) H[n * i + j] += A[(size_t)r * n + i] * A[(size_t)r * n + j];
+  for (int i = 0; i < n * n; ++i)
+    if (!(std::fabs(H[i]) <= DBL_MAX)) return fail(EA_ERR_INVALID_ARG, "A^T A overflows");
+  PriorDesc &pr = p->prior;
+  if (block == 0) {
+    for (int i = 0; i < 16; ++i) pr.Hq[i] = H[i];
+    for (int i = 0; i < 4; ++i) pr.bq[i] = clear ? 0.0 : b[i];
+    pr.has_q = clear ? 0 : 1;
+  } else {
+    for (int i = 0; i < 9; ++i) pr.Ht[i] = H[i];
+    for (int i = 0; i < 3; ++i) pr.bt[i] = clear ? 0.0 : b[i];
+    pr.has_t = clear ? 0 : 1;
+  }
   p->version++;
   return EA_OK;
 }
@@ -1189,11 +1242,20 @@ static int batch_build(ea_batch *b) {
     b->d_desc_block = nullptr; b->d_probs = nullptr; b->d_groups = nullptr;
     b->terms_cap = b->nterms + 8;
     HIPCHK(cached_malloc(reinterpret_cast<void **>(&b->d_desc_block),
-                         (size_t)b->terms_cap * sizeof(ProblemDesc) + b->probs.size() * sizeof(GroupDesc), b->device));
+                         (size_t)b->terms_cap * sizeof(ProblemDesc) + b->probs.size() * (sizeof(GroupDesc) + sizeof(PriorDesc)),
+                         b->device));
   }
   static_assert(sizeof(ProblemDesc) % alignof(GroupDesc) == 0, "the groups sit right behind the terms");
   b->d_probs = reinterpret_cast<ProblemDesc *>(b->d_desc_block);
   b->d_groups = reinterpret_cast<GroupDesc *>(b->d_desc_block + (size_t)b->nterms * sizeof(ProblemDesc));
+  b->h_priors.resize(b->probs.size());
+  b->any_prior = 0;
+  for (size_t i = 0; i < b->probs.size(); ++i) {
+    b->h_priors[i] = b->probs[i]->prior;
+    b->any_prior |= (b->h_priors[i].has_q || b->h_priors[i].has_t) ? 1 : 0;
+  }
+  static_assert(sizeof(GroupDesc) % alignof(PriorDesc) == 0, "the priors sit right behind the groups");
+  b->d_priors = b->any_prior ? reinterpret_cast<PriorDesc *>(b->d_groups + b->probs.size()) : nullptr;
   if (b->t_test_fail_build) {  // (tests/test_gpu_robustness.py: a build that fails here must leave the batch dirty)
     b->t_test_fail_build = 0;
     return fail(EA_ERR_ALLOC, "batch build: injected allocation failure (test hook)");
@@ -1209,17 +1271,19 @@ static int batch_build(ea_batch *b) {
   }
   {
     const size_t pb = descs.size() * sizeof(ProblemDesc), gb = groups.size() * sizeof(GroupDesc);
+    const size_t rb = b->any_prior ? b->h_priors.size() * sizeof(PriorDesc) : 0;
     if (!b->desc_done) HIPCHK(hipEventCreateWithFlags(&b->desc_done, hipEventDisableTiming));
     else HIPCHK(hipEventSynchronize(b->desc_done));  // the staging block is free again (it always is by now)
-    if (b->h_desc_cap < pb + gb) {
+    if (b->h_desc_cap < pb + gb + rb) {
       if (b->h_desc) cached_host_free(b->h_desc);
       b->h_desc = nullptr;
-      b->h_desc_cap = ((pb + gb) * 2 + 1024 + 4095) & ~(size_t)4095;  // (whole pages: batches of equal shape find each other's block)
+      b->h_desc_cap = ((pb + gb + rb) * 2 + 1024 + 4095) & ~(size_t)4095;  // (whole pages: batches of equal shape find each other's block)
       HIPCHK(cached_host_malloc(reinterpret_cast<void **>(&b->h_desc), b->h_desc_cap, hipHostMallocDefault, b->device));
     }
     std::memcpy(b->h_desc, descs.data(), pb);
     std::memcpy(b->h_desc + pb, groups.data(), gb);
-    HIPCHK(hipMemcpyAsync(b->d_desc_block, b->h_desc, pb + gb, hipMemcpyHostToDevice, b->stream));
+    if (rb) std::memcpy(b->h_desc + pb + gb, b->h_priors.data(), rb);
+    HIPCHK(hipMemcpyAsync(b->d_desc_block, b->h_desc, pb + gb + rb, hipMemcpyHostToDevice, b->stream));
     HIPCHK(hipEventRecord(b->desc_done, b->stream));
   }
   // LDS staging of the DT footprint is available but off by default: on MI355X the unaligned 16-byte
@@ -1327,6 +1391,21 @@ static int wait_results(ea_batch *b) {
   return EA_OK;
 }
 
+// Whole-problem results land in pinned host memory: the priors' terms are added there, at the pose of each result (n results,
+// result j belonging to problem j % count, its pose at qt(j) = 7 doubles q | t).  The fold kernels stay as they are.
+template <typename PoseFn>
+static void add_priors_host(const ea_batch *b, EvalOut *out, size_t n, PoseFn qt) {
+  if (!b->any_prior) return;
+  const size_t count = b->probs.size();
+  for (size_t j = 0; j < n; ++j) {
+    const PriorDesc &pr = b->h_priors[j % count];
+    if (!pr.has_q && !pr.has_t) continue;
+    double x[7];
+    qt(j, x);
+    prior_add(pr, x, out[j].acc);
+  }
+}
+
 extern "C" int ea_batch_eval(ea_batch *b, const double *q, const double *t, double *cost, double *JtJ,
                              double *Jtr, int64_t *n_invalid) {
   if (!b || !q || !t) return fail(EA_ERR_INVALID_ARG, "NULL argument");
@@ -1352,6 +1431,10 @@ extern "C" int ea_batch_eval(ea_batch *b, const double *q, const double *t, doub
   // of a 31 us call); the kernel's end makes them visible
   HIPCHK(launch_last_fold(b, b->d_groups, count, b->d_partials, b->dv_out));
   if ((rc = wait_results(b)) != EA_OK) return rc;
+  add_priors_host(b, b->h_out, (size_t)count, [&](size_t j, double x[7]) {
+    for (int k = 0; k < 4; ++k) x[k] = q[4 * j + k];
+    for (int k = 0; k < 3; ++k) x[4 + k] = t[3 * j + k];
+  });
   unpack_eval_out(b, count, cost, JtJ, Jtr, n_invalid);
   return EA_OK;
 }
@@ -1514,6 +1597,9 @@ extern "C" int ea_batch_eval_resident_poses(ea_batch *b, double *cost, double *J
   if ((rc = enqueue_resident_poses(b, K, true, true)) != EA_OK) return rc;
   if ((rc = wait_results(b)) != EA_OK) return rc;
   const size_t n = (size_t)K * (size_t)count;
+  add_priors_host(b, b->h_kout, n, [&](size_t j, double x[7]) {  // (h_kqt: the staging block of ea_batch_set_poses)
+    for (int k = 0; k < 7; ++k) x[k] = b->h_kqt[7 * j + k];
+  });
   if (cost || JtJ || Jtr || n_invalid) unpack_eval_out(b->h_kout, (int)n, cost, JtJ, Jtr, n_invalid);
   return EA_OK;
 }
@@ -1705,12 +1791,13 @@ static int solve_pump(SolveRun &r, const LMOptions &lo) {
       const int in = r.enq & 1, out = in ^ 1;
       HIPCHK(launch_lm_iter(b->dtype, b->ppt, b->d_probs, count, b->chunk, b->max_chunks, b->xcd_remap, b->d_poses, rows[in], rows[out],
                             b->buffer_loads, b->img32, b->x0, b->y0, b->z0, b->n0, b->d_groups, st[in], st[out], cold[in], cold[out],
-                            b->d_traces, lo, b->d_progress, b->dv_states, b->dv_traces, b->group0, /*post_done=*/0, b->stream));
+                            b->d_traces, lo, b->d_progress, b->dv_states, b->dv_traces, b->group0, /*post_done=*/0, b->stream,
+                            b->any_prior));
     } else {
       int rc = batch_launch_eval(b);
       if (rc != EA_OK) return rc;
       HIPCHK(launch_lm_step(b->d_groups, count, b->d_partials, b->d_poses, b->d_states, b->d_cold, b->d_traces, lo,
-                            b->d_progress, b->dv_states, b->dv_traces, b->group0, 0, b->stream));
+                            b->d_progress, b->dv_states, b->dv_traces, b->group0, 0, b->stream, b->any_prior));
     }
     ++r.enq;
     r.spins = 0;
@@ -2442,11 +2529,26 @@ extern "C" int ea_cost(ea_problem *p, const double q[4], const double t[3], doub
 // synchronisation.  The covariance is a few thousand flops per problem on one lane: a separate kernel behind the fold costs
 // one launch gap (~1.5 us) and leaves the fold and the solve kernels exactly as they are.  Nothing of the pose-batched
 // path (ea_batch_set_poses) is touched: resident poses survive.
+// PRIOR: the problems' NormalPriors (a table of `count`) enter the system first, at the pose of the evaluation -- as
+// ceres::Covariance counts every residual block; apply_loss_function does not concern them.
+template <bool PRIOR>
 static __global__ __launch_bounds__(64) void ea_cov_kernel(const EvalOut *__restrict__ sums, const PoseState *__restrict__ poses,
                                                            CovOptions o, int count, ea_covariance *__restrict__ out,
-                                                           unsigned int *__restrict__ counter, int *__restrict__ host_flag, int seq) {
+                                                           unsigned int *__restrict__ counter, int *__restrict__ host_flag, int seq,
+                                                           const PriorDesc *__restrict__ priors) {
   const int i = (int)(blockIdx.x * 64 + threadIdx.x);
-  if (i < count) cov_from_acc(sums[i].acc, poses[i].q, 1, o, &out[i]);
+  if constexpr (PRIOR) {
+    if (i < count) {
+      double acc[kAccSlots], x[7];
+      for (int k = 0; k < kAccSlots; ++k) acc[k] = sums[i].acc[k];
+      for (int k = 0; k < 4; ++k) x[k] = poses[i].q[k];
+      for (int k = 0; k < 3; ++k) x[4 + k] = poses[i].t[k];
+      prior_add(priors[i], x, acc);
+      cov_from_acc(acc, poses[i].q, 1, o, &out[i]);
+    }
+  } else {
+    if (i < count) cov_from_acc(sums[i].acc, poses[i].q, 1, o, &out[i]);
+  }
   __threadfence_system();  // (this wavefront's stores to host memory are visible before it counts itself in)
   if (threadIdx.x == 0) {
     const unsigned int prev = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
@@ -2524,8 +2626,12 @@ static int batch_covariance(ea_batch *b, const double *q, const double *t, const
   HIPCHK(launch_reduce(b->d_groups, count, b->d_partials, b->d_out, b->stream));
   const CovOptions co = {o->algorithm, o->min_reciprocal_condition_number, o->null_space_rank};
   b->done_seq = b->done_seq == 0x7fffffff ? 1 : b->done_seq + 1;
-  hipLaunchKernelGGL(ea_cov_kernel, dim3((count + 63) / 64), dim3(64), 0, b->stream, b->d_out, b->d_poses, co, count, b->dv_cov,
-                     b->d_done_count, b->d_progress + 3 * (size_t)count, b->done_seq);
+  if (b->d_priors)
+    hipLaunchKernelGGL(ea_cov_kernel<true>, dim3((count + 63) / 64), dim3(64), 0, b->stream, b->d_out, b->d_poses, co, count, b->dv_cov,
+                       b->d_done_count, b->d_progress + 3 * (size_t)count, b->done_seq, b->d_priors);
+  else
+    hipLaunchKernelGGL(ea_cov_kernel<false>, dim3((count + 63) / 64), dim3(64), 0, b->stream, b->d_out, b->d_poses, co, count, b->dv_cov,
+                       b->d_done_count, b->d_progress + 3 * (size_t)count, b->done_seq, nullptr);
   HIPCHK(hipGetLastError());
   if ((rc = wait_results(b)) != EA_OK) return rc;
   std::memcpy(out, b->h_cov, (size_t)count * sizeof(ea_covariance));
@@ -2691,6 +2797,8 @@ extern "C" int ea_solve_sharded(ea_problem *p, const ea_options *opt_in, ea_allr
       std::memset(acc, 0, sizeof(acc));
     }
     if (allreduce(acc, kAccSlots, user) != 0) return fail(EA_ERR_STATE, "the all-reduce callback reported a failure");
+    // the prior once, on the reduced sums (every rank holds the same prior and adds the same bits)
+    if (b->any_prior) prior_add(b->h_priors[0], pose, acc);
     LMPending pend;
     if (st.num_evals == 0) lm_begin_rt(&st, &cold, &tr, &lo, acc, &pend);
     else lm_advance_rt(&st, &cold, &tr, &lo, acc, &pend);
@@ -2743,9 +2851,11 @@ extern "C" int ea_solve_sharded_device(ea_problem *p, const ea_options *opt_in, 
   if (rc != EA_OK) return rc;
   if (!b->d_one_row) {
     const GroupDesc one = {0, 1, 0, 1};
-    HIPCHK(hipMalloc(&b->d_one_row, sizeof(GroupDesc)));
+    HIPCHK(hipMalloc(&b->d_one_row, sizeof(GroupDesc) + sizeof(PriorDesc)));  // (+ the prior table of one problem behind it)
     HIPCHK(hipMemcpy(b->d_one_row, &one, sizeof(one), hipMemcpyHostToDevice));
   }
+  if (b->any_prior)  // the step kernel adds the prior once, to the reduced sums: it reads it behind its one-row group table
+    HIPCHK(hipMemcpyAsync(b->d_one_row + 1, b->d_priors, sizeof(PriorDesc), hipMemcpyDeviceToDevice, b->stream));
   // Look-ahead rule.  The host keeps `ahead` iterations queued; iteration i + ahead is enqueued once iteration i is
   // COMPLETE (the step kernel posts that behind its flag) unless the solve had finished by iteration i.  The decision
   // depends on (i, the iteration the solve finished at) only -- quantities every rank agrees on, whenever its host happens
@@ -2764,7 +2874,7 @@ extern "C" int ea_solve_sharded_device(ea_problem *p, const ea_options *opt_in, 
       return fail(EA_ERR_STATE, "the all-reduce callback reported a failure");
     }
     HIPCHK(launch_lm_step(b->d_one_row, 1, device_sums, b->d_poses, b->d_states, b->d_cold, b->d_traces, lo, b->d_progress,
-                          b->dv_states, b->dv_traces, GroupDesc{0, 1, 0, 1}, /*post_done=*/1, b->stream));
+                          b->dv_states, b->dv_traces, GroupDesc{0, 1, 0, 1}, /*post_done=*/1, b->stream, b->any_prior));
     ++r.enq;
     return EA_OK;
   };
@@ -2881,7 +2991,8 @@ extern "C" int ea_internal_solve_sharded_rows(ea_problem *p, const ea_options *o
     const int in = r.enq & 1, out = in ^ 1;
     HIPCHK(launch_lm_iter(b->dtype, b->ppt, b->d_probs, 1, b->chunk, b->max_chunks, b->xcd_remap, b->d_poses, rows[in], rows[out],
                           b->buffer_loads, b->img32, b->x0, b->y0, b->z0, b->n0, b->d_groups, st[in], st[out], cold[in], cold[out],
-                          b->d_traces, lo, b->d_progress, b->dv_states, b->dv_traces, fold_range, /*post_done=*/1, b->stream));
+                          b->d_traces, lo, b->d_progress, b->dv_states, b->dv_traces, fold_range, /*post_done=*/1, b->stream,
+                          b->any_prior));
     int rc2 = exchange(rows[out]);
     if (rc2 != EA_OK) return rc2;
     ++r.enq;
@@ -2963,6 +3074,10 @@ struct ea_tracker {
   bool cov_on = false, cov_valid = false;
   ea_covariance_options cov_opt{};
   ea_covariance cov_last{};
+  // ea_tracker_set_motion_prior: NormalPriors centred on each solve's start pose, A = I / sigma (0 = that block off)
+  double sigma_rot = 0.0, sigma_trans = 0.0;
+  bool motion_set = false;  // the problem carries priors this tracker installed: `installed` (a caller's later prior differs)
+  PriorDesc installed = {};
 };
 
 extern "C" int ea_tracker_create(ea_tracker **out, const ea_camera *cam, int dtype, int device, int flavour) {
@@ -3012,6 +3127,20 @@ extern "C" int ea_tracker_push_frame(ea_tracker *tr, const uint8_t *bgr, const u
     double q[4], t[3];
     std::memcpy(q, tr->q, sizeof(q));
     std::memcpy(t, tr->t, sizeof(t));
+    if (tr->sigma_rot > 0.0 || tr->sigma_trans > 0.0) {
+      // the motion prior: centred on the constant-velocity prediction the solve starts from (replaces the caller's priors)
+      double Aq[16] = {0}, At[9] = {0};
+      for (int i = 0; i < 4; ++i) Aq[5 * i] = tr->sigma_rot > 0.0 ? 1.0 / tr->sigma_rot : 0.0;
+      for (int i = 0; i < 3; ++i) At[4 * i] = tr->sigma_trans > 0.0 ? 1.0 / tr->sigma_trans : 0.0;
+      rc = ea_problem_set_normal_prior(tr->p, 0, tr->sigma_rot > 0.0 ? Aq : nullptr, 4, q);
+      if (rc == EA_OK) rc = ea_problem_set_normal_prior(tr->p, 1, tr->sigma_trans > 0.0 ? At : nullptr, 3, t);
+      if (rc != EA_OK) {
+        if (job.started) (void)hipDeviceSynchronize();
+        return rc;
+      }
+      tr->motion_set = true;
+      tr->installed = tr->p->prior;
+    }
     ea_summary s;
     rc = ea_solve(tr->p, opt, q, t, &s);
     if (rc != EA_OK) {
@@ -3074,6 +3203,24 @@ extern "C" int ea_tracker_set_covariance(ea_tracker *tr, const ea_covariance_opt
   }
   tr->cov_on = o != nullptr;
   tr->cov_valid = false;
+  return EA_OK;
+}
+
+extern "C" int ea_tracker_set_motion_prior(ea_tracker *tr, double sigma_rot, double sigma_trans) {
+  if (!tr) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (!(sigma_rot >= 0.0 && sigma_rot <= DBL_MAX) || !(sigma_trans >= 0.0 && sigma_trans <= DBL_MAX))
+    return fail(EA_ERR_INVALID_ARG, "sigmas must be finite and >= 0");
+  if (sigma_rot == 0.0 && sigma_trans == 0.0 && tr->motion_set) {
+    // off again: a block still holding the prior this tracker installed is cleared; one the caller has set since is kept
+    const PriorDesc &cur = tr->p->prior, &ins = tr->installed;
+    if (cur.has_q && ins.has_q && std::memcmp(cur.Hq, ins.Hq, sizeof(cur.Hq)) == 0 && std::memcmp(cur.bq, ins.bq, sizeof(cur.bq)) == 0)
+      (void)ea_problem_set_normal_prior(tr->p, 0, nullptr, 0, nullptr);
+    if (cur.has_t && ins.has_t && std::memcmp(cur.Ht, ins.Ht, sizeof(cur.Ht)) == 0 && std::memcmp(cur.bt, ins.bt, sizeof(cur.bt)) == 0)
+      (void)ea_problem_set_normal_prior(tr->p, 1, nullptr, 0, nullptr);
+    tr->motion_set = false;
+  }
+  tr->sigma_rot = sigma_rot;
+  tr->sigma_trans = sigma_trans;
   return EA_OK;
 }
 

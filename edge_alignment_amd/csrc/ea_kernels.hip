@@ -39,6 +39,7 @@ extern __device__ int g_lm_probe_row;
   } while (0)
 #endif
 #include "ea_lm.h"
+#include "ea_prior.h"
 #include "ea_types.h"
 
 namespace ea {
@@ -1574,13 +1575,42 @@ __global__ __launch_bounds__(NT) void ea_eval_fold_kernel(
   eval_fused_body<T, PPT, 0, NT, false, BUF, IMG32>(x0, y0, z0, n0, shape, chunks_per_xcd, probs, poses, partials, lds_texels);
 }
 
+// PRIOR instantiations of the LM kernels.  Problem p's PriorDesc (ea_prior.h; the table sits behind the group table) is
+// fetched one 8-byte word per lane beside the state words, before the fold (prior_word), and parked in LDS with them
+// (prior_lds) -- its load is not a dependent round trip on the state machine's critical path.  After the barrier lane 0 adds
+// the priors to the folded sums in LDS, at the pose they were evaluated at -- st.x before the first evaluation, st.cand
+// after -- and the workgroup waits for it.  The state machine then reads s_acc exactly as the prior-free instantiation does:
+// its code is the same, so a problem without a prior in a batch with priors takes bit for bit the steps of its own solve.
+constexpr int kPriorWords = (int)(sizeof(PriorDesc) / 8);
+__device__ __forceinline__ PriorDesc &prior_lds() {
+  __shared__ PriorDesc s_prior;  // (only the PRIOR instantiations reference it)
+  return s_prior;
+}
+__device__ __forceinline__ double prior_word(const GroupDesc *__restrict__ groups, int nprob, int p, int tid) {
+  return tid < kPriorWords ? reinterpret_cast<const double *>(reinterpret_cast<const PriorDesc *>(groups + nprob) + p)[tid] : 0.0;
+}
+__device__ __forceinline__ void prior_into_lds(const LMState &s_st, double *s_acc, int tid) {
+  if (tid == 0) {
+    double acc[kAccSlots];
+#pragma unroll
+    for (int i = 0; i < kAccSlots; ++i) acc[i] = s_acc[i];
+    prior_add(prior_lds(), s_st.num_evals == 0 ? s_st.x : s_st.cand, acc);
+#pragma unroll
+    for (int i = 0; i < kAccSlots; ++i) s_acc[i] = acc[i];
+  }
+  __syncthreads();
+}
+
 // LM step: fold this problem's partial rows, advance the trust-region state machine, publish the
 // next pose to evaluate.  One workgroup per problem.  The state machine is scalar fp64 work on
 // lane 0 (pure latency: ~1/3 of an LM iteration), so everything around it is arranged to overlap:
 // the state words travel while the partial rows are fetched (sixteen 16-byte loads in flight per lane), the
 // host's progress counter is posted before the arithmetic, lane 0 works on a register copy of the
 // state, and the pose's float mirrors / the write-back are lane-parallel.
-template <int STRAT>
+// PRIOR: the problems' NormalPriors are added to the folded sums before the state machine reads them (prior_into_lds).  The
+// prior table sits right behind the group table (one PriorDesc per problem: batch_build lays them out so), so no argument is
+// added: the PRIOR = false instantiations are the code this kernel was before priors existed.
+template <int STRAT, bool PRIOR>
 __global__ __launch_bounds__(kLmThreads) void ea_lm_step_kernel(
     const GroupDesc *__restrict__ groups, const double *__restrict__ partials,
     PoseState *__restrict__ poses, LMState *__restrict__ states, LMCold *__restrict__ cold,
@@ -1621,6 +1651,8 @@ __global__ __launch_bounds__(kLmThreads) void ea_lm_step_kernel(
   const int running = states[p].running;
   const int evals_before = states[p].num_evals;  // (a register copy: the LDS copy is rewritten by lane 0 below)
   const double state_word = tid < kStateWords ? reinterpret_cast<const double *>(states + p)[tid] : 0.0;
+  double pw = 0.0;
+  if constexpr (PRIOR) pw = prior_word(groups, gridDim.x, p, tid);
   EA_LM_STAMP(1, ev_);
   // The rows are fetched WITHOUT waiting for the running flag: the flag's round trip (0.5 us of the 2.5 us this kernel spends
   // before its first arithmetic, in-kernel stamps) then travels beside the rows' instead of in front of it.  A finished
@@ -1628,7 +1660,11 @@ __global__ __launch_bounds__(kLmThreads) void ea_lm_step_kernel(
   reduce_tiles<kLmThreads, 8>(partials, gd.tile_begin, gd.tile_end, s_part, s_acc);
   if (!running) return;  // uniform
   if (tid < kStateWords) reinterpret_cast<double *>(&s_st)[tid] = state_word;
+  if constexpr (PRIOR) {
+    if (tid < kPriorWords) reinterpret_cast<double *>(&prior_lds())[tid] = pw;
+  }
   __syncthreads();
+  if constexpr (PRIOR) prior_into_lds(s_st, s_acc, tid);
   EA_LM_STAMP(2, ev_);
   // the host only uses this counter to decide how far ahead to enqueue: posted by another wavefront before the
   // arithmetic, so the PCIe write is neither the last thing the kernel waits for nor in lane 0's memory counter
@@ -1734,7 +1770,9 @@ __global__ __launch_bounds__(kLmThreads) void ea_lm_step_kernel(
 // wavefront, and the state machine works on that copy; the writer stores its copy for the next launch.
 // One plain residual family per problem, 256-thread workgroups, stencil rows from L2; the host only takes this path when the
 // whole grid is resident at once (<= 256 workgroups), see solve_start.
-template <typename T, int PPT, bool BUF, bool IMG32, int STRAT>
+// PRIOR: as in ea_lm_step_kernel (the prior table behind `groups`): the prior enters the folded sums in LDS once per
+// workgroup, before the writer's and every evaluating wavefront's state machine read them, so they stay in lockstep.
+template <typename T, int PPT, bool BUF, bool IMG32, int STRAT, bool PRIOR>
 __global__ __launch_bounds__(kLmThreads) void ea_lm_iter_kernel(
     // the 14 preloaded dwords: what problem 0's point loads and ROW loads need -- the fold is the head of every workgroup's
     // dependent chain, and its loads must not wait for a scalar load of the argument segment (tile0_* = problem 0's row range)
@@ -1796,6 +1834,8 @@ __global__ __launch_bounds__(kLmThreads) void ea_lm_iter_kernel(
   const int evals_before = st_in[p].num_evals;
   const double state_word = tid < kStateWords ? reinterpret_cast<const double *>(st_in + p)[tid] : 0.0;
   const double cold_word = (tid & 63) < kColdWords ? reinterpret_cast<const double *>(cold_in + p)[tid & 63] : 0.0;
+  double pw = 0.0;
+  if constexpr (PRIOR) pw = prior_word(groups, gridDim.y, p, tid);
   // ---- the step, in every workgroup: fold of the previous launch's rows + the state machine on lane 0.
   // The rows are fetched at once, beside the uniforms above and not behind them (as ea_lm_step_kernel does): a launch that
   // finds its problem finished has folded rows nobody reads and leaves below.
@@ -1829,7 +1869,11 @@ __global__ __launch_bounds__(kLmThreads) void ea_lm_iter_kernel(
   }
   if (tid < kStateWords) reinterpret_cast<double *>(&s_st)[tid] = state_word;
   if ((tid & 63) < kColdWords) reinterpret_cast<double *>(&s_cold[tid >> 6])[tid & 63] = cold_word;  // (own wavefront's copy)
+  if constexpr (PRIOR) {
+    if (tid < kPriorWords) reinterpret_cast<double *>(&prior_lds())[tid] = pw;
+  }
   __syncthreads();
+  if constexpr (PRIOR) prior_into_lds(s_st, s_acc, tid);
   EA_LM_STAMP_PUT(0, evals_before, t_enter_);
   EA_LM_STAMP(1, evals_before);  // folded
   if (writer) {
@@ -2306,14 +2350,18 @@ hipError_t launch_reduce_done(const GroupDesc *groups, int count, const double *
 
 hipError_t launch_lm_step(const GroupDesc *groups, int count, const double *partials, PoseState *poses,
                           LMState *states, LMCold *cold, LMTrace *traces, const LMOptions &opt, int *progress,
-                          LMState *host_states, LMTrace *host_traces, const GroupDesc &first, int post_done, hipStream_t stream) {
+                          LMState *host_states, LMTrace *host_traces, const GroupDesc &first, int post_done, hipStream_t stream,
+                          int priors) {
+#define EA_STEP(S, P)                                                                                                            \
+  hipLaunchKernelGGL((ea_lm_step_kernel<S, P>), dim3(count), dim3(kLmThreads), 0, stream, groups, partials, poses, states, cold, \
+                     traces, opt, progress, host_states, host_traces, first, post_done)
   if (count <= 0) return hipSuccess;
-  if (opt.strategy == 0)
-    hipLaunchKernelGGL(ea_lm_step_kernel<0>, dim3(count), dim3(kLmThreads), 0, stream, groups, partials, poses,
-                       states, cold, traces, opt, progress, host_states, host_traces, first, post_done);
-  else
-    hipLaunchKernelGGL(ea_lm_step_kernel<1>, dim3(count), dim3(kLmThreads), 0, stream, groups, partials, poses,
-                       states, cold, traces, opt, progress, host_states, host_traces, first, post_done);
+  if (opt.strategy == 0) {
+    if (priors) EA_STEP(0, true); else EA_STEP(0, false);
+  } else {
+    if (priors) EA_STEP(1, true); else EA_STEP(1, false);
+  }
+#undef EA_STEP
   return hipGetLastError();
 }
 
@@ -2324,17 +2372,18 @@ hipError_t launch_lm_iter(int dtype, int ppt, const ProblemDesc *probs, int coun
                           const void *x0, const void *y0, const void *z0, int n0, const GroupDesc *groups,
                           const LMState *st_in, LMState *st_out, const LMCold *cold_in, LMCold *cold_out, LMTrace *traces,
                           const LMOptions &opt, int *progress, LMState *host_states, LMTrace *host_traces,
-                          const GroupDesc &first, int post_done, hipStream_t stream) {
+                          const GroupDesc &first, int post_done, hipStream_t stream, int priors) {
   if (count <= 0) return hipSuccess;
   if (chunk <= 0 || chunk > 0xffff || chunk != kLmThreads * ppt) return hipErrorInvalidValue;
   const int chunks_per_xcd = (max_chunks + 1 + 7) / 8;
   const dim3 grid(xcd_remap ? chunks_per_xcd * 8 : max_chunks + 1, count);
   const int shape = chunk | ((xcd_remap ? 1 : 0) << 16) | (1 << 17);
   const size_t shmem = (size_t)kHdrBytes;
-#define EA_ITER_S(T, P, B, I, S)                                                                                           \
-  hipLaunchKernelGGL((ea_lm_iter_kernel<T, P, B, I, S>), grid, dim3(kLmThreads), shmem, stream, x0, y0, z0, n0, shape,     \
+#define EA_ITER_SP(T, P, B, I, S, R)                                                                                       \
+  hipLaunchKernelGGL((ea_lm_iter_kernel<T, P, B, I, S, R>), grid, dim3(kLmThreads), shmem, stream, x0, y0, z0, n0, shape,  \
                      chunks_per_xcd, rows_in, first.tile_begin, first.tile_end, probs, poses, rows_out, groups, st_in, st_out, \
                      cold_in, cold_out, traces, opt, progress, host_states, host_traces, post_done)
+#define EA_ITER_S(T, P, B, I, S) do { if (priors) EA_ITER_SP(T, P, B, I, S, true); else EA_ITER_SP(T, P, B, I, S, false); } while (0)
 #define EA_ITER(T, P, B, I) do { if (opt.strategy == 0) EA_ITER_S(T, P, B, I, 0); else EA_ITER_S(T, P, B, I, 1); } while (0)
 #define EA_ITER_B(T, P, I) do { if (buffer_loads) EA_ITER(T, P, true, I); else EA_ITER(T, P, false, I); } while (0)
   if (dtype == 1) {
@@ -2349,6 +2398,7 @@ hipError_t launch_lm_iter(int dtype, int ppt, const ProblemDesc *probs, int coun
 #undef EA_ITER_B
 #undef EA_ITER
 #undef EA_ITER_S
+#undef EA_ITER_SP
   return hipGetLastError();
 }
 

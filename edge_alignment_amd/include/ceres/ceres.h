@@ -51,6 +51,8 @@ struct EABlockInfo {
   double T12inv[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
 };
 
+class NormalPrior;
+
 class CostFunction {
  public:
   virtual ~CostFunction() {}
@@ -62,6 +64,80 @@ class CostFunction {
   }
   // true if this block is an edge-alignment block; fills info
   virtual bool DescribeEdgeAlignmentBlock(EABlockInfo *) const { return false; }
+  // non-NULL if this block is a ceres::NormalPrior
+  virtual const NormalPrior *AsNormalPrior() const { return nullptr; }
+};
+
+// ---- minimal dense matrix / vector (ceres::Matrix, ceres::Vector are Eigen types in Ceres; these are enough to build a
+// NormalPrior without Eigen -- NormalPrior also takes Eigen objects directly) ------------------------------------------
+class Matrix {
+ public:
+  Matrix() : r_(0), c_(0) {}
+  Matrix(int rows, int cols) : r_(rows), c_(cols), v_((size_t)rows * cols, 0.0) {}
+  int rows() const { return r_; }
+  int cols() const { return c_; }
+  double &operator()(int i, int j) { return v_[(size_t)i * c_ + j]; }
+  double operator()(int i, int j) const { return v_[(size_t)i * c_ + j]; }
+  Matrix &setZero() { std::fill(v_.begin(), v_.end(), 0.0); return *this; }
+  Matrix &setIdentity() {
+    setZero();
+    for (int i = 0; i < r_ && i < c_; ++i) (*this)(i, i) = 1.0;
+    return *this;
+  }
+  const double *data() const { return v_.data(); }  // row-major
+ private:
+  int r_, c_;
+  std::vector<double> v_;
+};
+
+class Vector {
+ public:
+  Vector() {}
+  explicit Vector(int n) : v_((size_t)n, 0.0) {}
+  int size() const { return (int)v_.size(); }
+  double &operator()(int i) { return v_[(size_t)i]; }
+  double operator()(int i) const { return v_[(size_t)i]; }
+  double &operator[](int i) { return v_[(size_t)i]; }
+  double operator[](int i) const { return v_[(size_t)i]; }
+  Vector &setZero() { std::fill(v_.begin(), v_.end(), 0.0); return *this; }
+  const double *data() const { return v_.data(); }
+ private:
+  std::vector<double> v_;
+};
+
+// ceres/normal_prior.h (Ceres <= 2.1): residual A (x - b) on ONE parameter block of size b.size(), A k x n.  Evaluate is the
+// honest host computation (Jacobian = A, in the block's ambient coordinates); the solve folds the prior into the device's
+// normal equations as H = A^T A (ea_problem_set_normal_prior).  Ceres takes a Matrix and a Vector; here anything with
+// rows() / cols() / operator()(i, j) and size() / operator()(i) -- ceres::Matrix / Vector above, or Eigen types.
+class NormalPrior : public CostFunction {
+ public:
+  template <typename MatrixT, typename VectorT>
+  NormalPrior(const MatrixT &A, const VectorT &b) : k_((int)A.rows()), n_((int)A.cols()) {
+    A_.resize((size_t)k_ * n_);
+    b_.resize((size_t)b.size());
+    for (int i = 0; i < k_; ++i)
+      for (int j = 0; j < n_; ++j) A_[(size_t)i * n_ + j] = A(i, j);
+    for (int j = 0; j < (int)b.size(); ++j) b_[(size_t)j] = b(j);
+  }
+  bool Evaluate(double const *const *parameters, double *residuals, double **jacobians) const override {
+    if (!parameters || !parameters[0] || !residuals || (int)b_.size() != n_) return false;
+    const double *x = parameters[0];
+    for (int i = 0; i < k_; ++i) {
+      double s = 0.0;
+      for (int j = 0; j < n_; ++j) s += A_[(size_t)i * n_ + j] * (x[j] - b_[(size_t)j]);
+      residuals[i] = s;
+    }
+    if (jacobians && jacobians[0]) std::copy(A_.begin(), A_.end(), jacobians[0]);
+    return true;
+  }
+  const NormalPrior *AsNormalPrior() const override { return this; }
+  int num_residuals() const { return k_; }
+  int parameter_block_size() const { return (int)b_.size(); }
+  const std::vector<double> &A() const { return A_; }  // k x n row-major
+  const std::vector<double> &b() const { return b_; }
+ private:
+  int k_, n_;
+  std::vector<double> A_, b_;
 };
 
 // AutoDiffCostFunction<Functor, 1, 4, 3>: owns the functor like Ceres does.  The functor must
@@ -187,19 +263,31 @@ class Problem {
     b.t = t;
     blocks_.push_back(b);
   }
+  // ceres::NormalPrior on one parameter block: problem.AddResidualBlock(new NormalPrior(A, b), NULL, x).  The facade hosts
+  // NormalPriors on the pose the EAResidue blocks share, without a loss, at most one per block (ProblemAccess::Build);
+  // any other single-block cost function is kept and refused there.
+  void AddResidualBlock(CostFunction *cost, LossFunction *loss, double *x) {
+    costs_.push_back(cost);
+    if (loss && (losses_.empty() || losses_.back() != loss)) losses_.push_back(loss);
+    priors_.push_back(PriorBlock{cost, loss, x, blocks_.size()});
+  }
   // standalone_edge_align.cpp:277-278
   void SetParameterization(double *values, LocalParameterization *p) {
     params_.push_back(p);
     if (p && p->IsQuaternion()) quat_param_on_ = values;
   }
-  int NumResidualBlocks() const { return (int)blocks_.size(); }
-  int NumResiduals() const { return (int)blocks_.size(); }
+  int NumResidualBlocks() const { return (int)(blocks_.size() + priors_.size()); }
+  int NumResiduals() const {
+    int n = (int)blocks_.size();
+    for (const auto &pb : priors_) n += pb.cost->AsNormalPrior() ? pb.cost->AsNormalPrior()->num_residuals() : 0;
+    return n;
+  }
   int NumParameterBlocks() const { return blocks_.empty() ? 0 : 2; }  // the quaternion and the translation
   int NumParameters() const { return blocks_.empty() ? 0 : 7; }
 
   // src/SolveEA.cpp:241  problem.Evaluate(Problem::EvaluateOptions(), &cost, &residuals, NULL, NULL)
-  // cost = 1/2 sum rho(r^2); residuals: one per block in the order they were added, loss-corrected like Ceres'
-  // apply_loss_function = true; gradient: the 6 tangent-space entries (J^T r); jacobian: one row per block in the same
+  // cost = 1/2 sum rho(r^2); residuals: one per block in the order they were added (k per NormalPrior block), loss-corrected like
+  // Ceres' apply_loss_function = true; gradient: the 6 tangent-space entries (J^T r); jacobian: one row per block in the same
   // order, six columns [d r / d delta (3) | d r / d t (3)] -- the parameter blocks' local sizes in the order
   // AddResidualBlock names them (quaternion, translation) -- as a compressed-row matrix with dense rows.
   struct EvaluateOptions {
@@ -229,7 +317,15 @@ class Problem {
       for (int i = 0; i < 16; ++i) if (x.T12[i] != y.T12[i] || x.T12inv[i] != y.T12inv[i]) return false;
     return true;
   }
+  // a single-block residual (NormalPrior): `before` = EAResidue blocks added ahead of it (its place in block order)
+  struct PriorBlock {
+    CostFunction *cost;
+    LossFunction *loss;
+    double *x;
+    size_t before;
+  };
   std::vector<Block> blocks_;
+  std::vector<PriorBlock> priors_;
   std::vector<EABlockInfo> fams_;   // distinct functor descriptions (X, Y, Z of the entry unused)
   int last_fam_ = -1;
   std::vector<CostFunction *> costs_;
@@ -340,6 +436,7 @@ class ProblemAccess {  // keeps Problem's internals private to user code
   static int Build(Problem *problem, int dtype, int device, std::vector<ea_problem *> *ps_out,
                    std::vector<std::vector<int>> *order, std::string *err) {
     const auto &blocks = problem->blocks_;
+    if (blocks.empty()) { *err = "a NormalPrior needs EAResidue blocks on the same pose (a problem of priors only cannot be hosted)"; return -1000; }
     const auto &b0 = blocks[0];
     struct Family { const Problem::Block *first; std::vector<double> xyz; std::vector<int> idx; };
     std::vector<Family> fams;
@@ -360,6 +457,20 @@ class ProblemAccess {  // keeps Problem's internals private to user code
       f->idx.push_back((int)i);
     }
     if (problem->quat_param_on_ != b0.q) { *err = "the quaternion block needs QuaternionParameterization (problem.SetParameterization)"; return -1000; }
+    const NormalPrior *prior_on[2] = {nullptr, nullptr};  // (q, t)
+    for (const auto &pb : problem->priors_) {
+      const NormalPrior *np = pb.cost->AsNormalPrior();
+      if (!np) { *err = "single-block residual is not a NormalPrior (this facade only hosts NormalPriors beside the EAResidue blocks)"; return -1000; }
+      if (pb.loss) { *err = "a NormalPrior block cannot take a loss function"; return -1000; }
+      const int blk = pb.x == b0.q ? 0 : (pb.x == b0.t ? 1 : -1);
+      if (blk < 0) { *err = "a NormalPrior must sit on the (quaternion, translation) pair the EAResidue blocks share"; return -1000; }
+      if (np->parameter_block_size() != (blk == 0 ? 4 : 3) || (int)np->A().size() != np->num_residuals() * (blk == 0 ? 4 : 3) ||
+          np->num_residuals() < 1) {
+        *err = "NormalPrior size does not match its parameter block (A k x 4 on the quaternion, k x 3 on the translation)"; return -1000;
+      }
+      if (prior_on[blk]) { *err = "at most one NormalPrior per parameter block"; return -1000; }
+      prior_on[blk] = np;
+    }
     std::vector<ea_problem *> &ps = *ps_out;
     ps.assign(fams.size(), nullptr);
     order->clear();
@@ -381,6 +492,10 @@ class ProblemAccess {  // keeps Problem's internals private to user code
       }
       if (rc == EA_OK && k > 0) rc = ea_problem_add_term(ps[0], ps[k]);
     }
+    for (int blk = 0; blk < 2 && rc == EA_OK; ++blk)  // the priors go on the head problem: every term shares its pose
+      if (prior_on[blk])
+        rc = ea_problem_set_normal_prior(ps[0], blk, prior_on[blk]->A().data(), prior_on[blk]->num_residuals(),
+                                         prior_on[blk]->b().data());
     return rc;
   }
 
@@ -395,18 +510,32 @@ class ProblemAccess {  // keeps Problem's internals private to user code
   static bool Evaluate(Problem *problem, const Problem::EvaluateOptions &opt, double *cost, std::vector<double> *residuals,
                        std::vector<double> *gradient, CRSMatrix *jacobian) {
     const auto &blocks = problem->blocks_;
+    const auto &priors = problem->priors_;
+    // rows in block order: EAResidue block i sits behind the rows of every prior added before it
+    const size_t nrows = (size_t)problem->NumResiduals();
+    std::vector<size_t> row_of(blocks.size()), prior_row(priors.size());
+    {
+      size_t row = 0, j = 0;
+      for (size_t i = 0; i <= blocks.size(); ++i) {
+        for (; j < priors.size() && priors[j].before == i; ++j) {
+          prior_row[j] = row;
+          row += priors[j].cost->AsNormalPrior() ? (size_t)priors[j].cost->AsNormalPrior()->num_residuals() : 0;
+        }
+        if (i < blocks.size()) row_of[i] = row++;
+      }
+    }
     if (jacobian) {
-      jacobian->num_rows = (int)blocks.size();
+      jacobian->num_rows = (int)nrows;
       jacobian->num_cols = blocks.empty() ? 0 : 6;
-      jacobian->rows.assign(blocks.size() + 1, 0);
-      jacobian->cols.assign(blocks.size() * 6, 0);
-      jacobian->values.assign(blocks.size() * 6, 0.0);
-      for (size_t i = 0; i < blocks.size(); ++i) {
+      jacobian->rows.assign(nrows + 1, 0);
+      jacobian->cols.assign(nrows * 6, 0);
+      jacobian->values.assign(nrows * 6, 0.0);
+      for (size_t i = 0; i < nrows; ++i) {
         jacobian->rows[i + 1] = (int)(6 * (i + 1));
         for (int a = 0; a < 6; ++a) jacobian->cols[6 * i + a] = a;
       }
     }
-    if (blocks.empty()) {
+    if (blocks.empty() && priors.empty()) {
       if (cost) *cost = 0.0;
       if (residuals) residuals->clear();
       if (gradient) gradient->clear();
@@ -416,20 +545,51 @@ class ProblemAccess {  // keeps Problem's internals private to user code
     std::vector<std::vector<int>> order;
     std::string err;
     int rc = Build(problem, opt.ea_dtype, opt.ea_device, &ps, &order, &err);
+    if (rc != EA_OK) {  // (nothing was created; a problem of priors only has no blocks[0] to read the pose from)
+      for (auto *p : ps)
+        if (p) ea_problem_destroy(p);
+      return false;
+    }
     const double *q = blocks[0].q, *t = blocks[0].t;
     double c = 0.0, JtJ[36], Jtr[6];
     int64_t bad = 0;
     if (rc == EA_OK) rc = ea_eval(ps[0], q, t, &c, JtJ, Jtr, &bad);  // the problem with all its terms
     if (rc == EA_OK && (residuals || jacobian)) {
-      if (residuals) residuals->assign(blocks.size(), 0.0);
+      if (residuals) residuals->assign(nrows, 0.0);
       for (size_t k = 0; k < ps.size() && rc == EA_OK; ++k) {
         std::vector<double> r(order[k].size()), J(jacobian ? order[k].size() * 6 : 0);
         // a term evaluated on its own: its residuals (and 1x6 rows) in the order its blocks were added
         rc = ea_eval_points(ps[k], q, t, r.data(), jacobian ? J.data() : nullptr, opt.apply_loss_function ? 1 : 0);
         for (size_t i = 0; i < r.size(); ++i) {
-          if (residuals) (*residuals)[order[k][i]] = r[i];
+          const size_t row = row_of[(size_t)order[k][i]];
+          if (residuals) (*residuals)[row] = r[i];
           if (jacobian)
-            for (int a = 0; a < 6; ++a) jacobian->values[6 * (size_t)order[k][i] + a] = J[6 * i + a];
+            for (int a = 0; a < 6; ++a) jacobian->values[6 * row + a] = J[6 * i + a];
+        }
+      }
+      // the NormalPriors' rows on the host: r = A (x - b), tangent Jacobian A P(q) on the quaternion, A on the translation
+      for (size_t j = 0; j < priors.size(); ++j) {
+        const NormalPrior *np = priors[j].cost->AsNormalPrior();
+        const int k = np->num_residuals(), n = np->parameter_block_size();
+        std::vector<double> r((size_t)k), A((size_t)k * n);
+        const double *x = priors[j].x;
+        double *jac[1] = {A.data()};
+        np->Evaluate(&x, r.data(), jac);
+        const bool on_q = priors[j].x == q;
+        double P[12];
+        if (on_q) QuaternionParameterization().ComputeJacobian(q, P);
+        for (int i = 0; i < k; ++i) {
+          const size_t row = prior_row[j] + (size_t)i;
+          if (residuals) (*residuals)[row] = r[(size_t)i];
+          if (!jacobian) continue;
+          for (int a = 0; a < 3; ++a) {
+            double v = 0.0;
+            if (on_q)
+              for (int m = 0; m < 4; ++m) v += A[(size_t)i * 4 + m] * P[3 * m + a];
+            else
+              v = A[(size_t)i * 3 + a];
+            jacobian->values[6 * row + (on_q ? 0 : 3) + a] = v;
+          }
         }
       }
     }
@@ -445,16 +605,17 @@ class ProblemAccess {  // keeps Problem's internals private to user code
     Solver::Summary &s = *summary;
     s = Solver::Summary();
     const auto &blocks = problem->blocks_;
-    s.num_residual_blocks = s.num_residuals = (int)blocks.size();
+    s.num_residual_blocks = problem->NumResidualBlocks();
+    s.num_residuals = problem->NumResiduals();
     auto fail = [&](const std::string &m) { s.termination_type = FAILURE; s.message = m; };
     if (options.minimizer_type != TRUST_REGION) return fail("only TRUST_REGION is supported");
-    if (blocks.empty()) { s.termination_type = CONVERGENCE; s.message = "No residual blocks."; s.initial_cost = s.final_cost = 0; s.num_successful_steps = s.num_unsuccessful_steps = 0; return; }
-    const auto &b0 = blocks[0];
+    if (blocks.empty() && problem->priors_.empty()) { s.termination_type = CONVERGENCE; s.message = "No residual blocks."; s.initial_cost = s.final_cost = 0; s.num_successful_steps = s.num_unsuccessful_steps = 0; return; }
     std::vector<ea_problem *> ps;
     std::vector<std::vector<int>> order;
     std::string berr;
     int rc = Build(problem, options.ea_dtype, options.ea_device, &ps, &order, &berr);
     if (rc == -1000) return fail(berr);
+    const auto &b0 = blocks[0];  // (Build refused a problem without EAResidue blocks)
     ea_options o;
     ea_default_options(&o);
     o.max_num_iterations = options.max_num_iterations;

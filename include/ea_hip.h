@@ -187,7 +187,8 @@ int ea_problem_set_second_camera(ea_problem *p, const double trans_1to2[16], con
 /* Several residual families on ONE pose — the reference adds camera-1 and camera-2 blocks to the same
  * ceres::Problem with the same (q,t) (standalone_edge_align.cpp:791-803, :3205-3218).  `term` keeps its own
  * points, DT image, intrinsics, loss and variant; it must outlive `p` (borrowed).  ea_eval / ea_solve on `p`
- * then cover p and all its terms. */
+ * then cover p and all its terms.  Destroy the head (or ea_problem_clear_terms it) before its terms: ea_problem_destroy of
+ * the head updates every term it still holds. */
 int ea_problem_add_term(ea_problem *p, ea_problem *term);
 int ea_problem_clear_terms(ea_problem *p);
 
@@ -376,6 +377,31 @@ int ea_tracker_set_covariance(ea_tracker *tr, const ea_covariance_options *o);
 /* the covariance of the last push (ok = 0 when its solve failed); EA_ERR_STATE when the last push did not align or
  * covariance is off */
 int ea_tracker_last_covariance(ea_tracker *tr, ea_covariance *out);
+
+/* ---- pose priors: ceres::NormalPrior(A, b) on the q or t block (Ceres <= 2.1) ----------------------------------------
+ * Residual r = A (x - b) with A k x n (k >= 1, n = 4 for q, 3 for t), cost 1/2 |A (x - b)|^2, no loss function; tangent
+ * Jacobian A P(q) on q (P = QuaternionParameterization::ComputeJacobian), A on t.  It enters the solve only through the 6x6
+ * system: H = A^T A (formed once here in fp64 and kept with b -- a deviation from keeping A, at rounding level) adds P^T H P
+ * or H to JtJ, P^T H (q - b) or H (t - b) to Jtr and 1/2 (x - b)^T H (x - b) to the cost, always in fp64 (fp32 problems
+ * too).  Priors on q and t are independent.
+ * Included: ea_eval, ea_cost, ea_batch_eval, ea_batch_eval_poses / _resident_poses, every solve (ea_solve, ea_batch_solve,
+ * ea_solve_pyramid per level, the sharded forms), ea_problem_covariance / ea_batch_covariance (whatever
+ * apply_loss_function says: a prior has no loss; a prior can make a rank-deficient system full rank).
+ * NOT included: the per-point outputs -- ea_eval_points, the rows API (ea_eval_rows*, ea_batch_eval_rows*), and
+ * ea_problem_pixel_cost.
+ * Sharded solves add the prior once, to the all-reduced system, on every rank: every rank must set the same prior.
+ * block: 0 = quaternion, 1 = translation; A: k x n row-major; A == NULL or k == 0 clears the block's prior.
+ * EA_ERR_INVALID_ARG (checked before anything else): bad block, k < 0, non-finite A or b, b == NULL with A given, and a
+ * problem that is a term of another (ea_problem_add_term, which in turn refuses a term that carries a prior).
+ * Bumps the problem's version: batches holding it rebuild their tables. */
+int ea_problem_set_normal_prior(ea_problem *p, int block, const double *A, int k, const double *b);
+/* Motion prior of the tracker: each push's solve carries NormalPriors centred on its start pose (the constant-velocity
+ * prediction), A = I4 / sigma_rot on q and A = I3 / sigma_trans on t.  sigma_rot is in quaternion-component units: about
+ * half the rotation angle in radians for small rotations.  sigma_trans is in the units of t.  0 disables that block; both
+ * 0 (the default) = off.  While on, it replaces any prior set on ea_tracker_problem() at every push; switching it off clears
+ * a block only while it still holds the prior the last push installed (a prior the caller set since is kept).  Tracker
+ * covariance (ea_tracker_set_covariance) includes it. */
+int ea_tracker_set_motion_prior(ea_tracker *tr, double sigma_rot, double sigma_trans);
 
 /* ---- materialised mode: the "EAResidue batch Evaluate" view -------------------------------------------------------
  * Replaces N calls of ceres::AutoDiffCostFunction<EAResidue,1,4,3>::Evaluate followed by the parameterisation's 4x3
