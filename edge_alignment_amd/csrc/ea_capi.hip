@@ -22,79 +22,11 @@
 #include "../../include/ea_hip.h"
 #include "ea_cov.h"
 #include "ea_hip_dev.h"
+#include "ea_launch.h"
 #include "ea_lm.h"
 #include "ea_prior.h"
 #include "ea_spin.h"
 #include "ea_types.h"
-
-namespace ea {
-hipError_t launch_eval_fused(int dtype, int ppt, int nt, int variant, const ProblemDesc *probs, int nterms, int chunk,
-                             int max_chunks, int xcd_remap, const PoseState *poses, double *partials,
-                             int lds_bytes, int wide, int terms_are_groups, int buffer_loads, int img32, const void *x0, const void *y0,
-                             const void *z0, int n0, hipStream_t stream);
-hipError_t launch_eval_poses(int dtype, int ppt, int nt, int variant, const ProblemDesc *probs, int nterms, int chunk,
-                             int max_chunks, int xcd_remap, const PoseState *poses, double *partials,
-                             int lds_bytes, int wide, int terms_are_groups, int buffer_loads, int img32, const void *x0, const void *y0,
-                             const void *z0, int n0, hipStream_t stream);
-hipError_t launch_pixel_cost(int dtype, const ProblemDesc *probs, int problem, int n, const PoseState *poses, void *partials,
-                             hipStream_t stream);
-hipError_t launch_eval_rows(int dtype, int variant, int buffer_loads, int img32, int layout, int staged, const ProblemDesc *probs, int nterms,
-                            long long max_n, const PoseState *poses, int corrected, int nontemporal, long long total_rows,
-                            void *r_out, void *J_out, unsigned int *n_invalid, hipStream_t stream);
-hipError_t launch_eval_points(int dtype, const ProblemDesc *probs, int problem, int n, const PoseState *poses,
-                              double *r_out, double *J_out, int corrected, hipStream_t stream);
-hipError_t launch_reduce(const GroupDesc *groups, int count, const double *partials, EvalOut *out,
-                         hipStream_t stream);
-hipError_t launch_reduce_done(const GroupDesc *groups, int count, const double *partials, EvalOut *out, unsigned int *counter,
-                              int *host_flag, int seq, hipStream_t stream);
-hipError_t launch_eval_fold(int dtype, int ppt, int nt, const ProblemDesc *probs, int nterms, int chunk, int max_chunks,
-                            int xcd_remap, const PoseState *poses, double *partials, int buffer_loads, int img32, const void *x0,
-                            const void *y0, const void *z0, int n0, const GroupDesc *groups, const double *prev_rows,
-                            EvalOut *prev_out, hipStream_t stream);
-hipError_t launch_reduce_nt(int nt, const GroupDesc *groups, int count, const double *partials, EvalOut *out,
-                            hipStream_t stream);
-hipError_t launch_lm_step(const GroupDesc *groups, int count, const double *partials, PoseState *poses,
-                          LMState *states, LMCold *cold, LMTrace *traces, const LMOptions &opt, int *running_flags,
-                          LMState *host_states, LMTrace *host_traces, const GroupDesc &first, int post_done, hipStream_t stream,
-                          int priors /* the PriorDesc table sits behind `groups` (one per problem) */);
-hipError_t launch_lm_iter(int dtype, int ppt, const ProblemDesc *probs, int count, int chunk, int max_chunks, int xcd_remap,
-                          PoseState *poses, const double *rows_in, double *rows_out, int buffer_loads, int img32,
-                          const void *x0, const void *y0, const void *z0, int n0, const GroupDesc *groups,
-                          const LMState *st_in, LMState *st_out, const LMCold *cold_in, LMCold *cold_out, LMTrace *traces,
-                          const LMOptions &opt, int *progress, LMState *host_states, LMTrace *host_traces,
-                          const GroupDesc &first, int post_done, hipStream_t stream, int priors /* as launch_lm_step */);
-hipError_t launch_pad_image(int dtype, const void *src, int H, int W, void *dst, int pitch, float *dst32, int *inexact,
-                            hipStream_t stream);
-hipError_t launch_make_poses(const double *qt, int n, int count, const ProblemDesc *probs, const GroupDesc *groups,
-                             PoseState *out, hipStream_t stream);
-hipError_t launch_grid_to_image(int dtype, const double *grid, int W, int H, void *dst, int pitch, float *dst32, int *inexact,
-                                hipStream_t stream);
-hipError_t launch_aos_to_soa(int dtype, const double *src, long long n, int stride, void *x, void *y, void *z, hipStream_t stream);
-hipError_t launch_selftest_reduce(const float *in, float *a, float *b, float *c, float *d, double *o32, double *o64,
-                                  hipStream_t stream);
-// ea_preprocess.hip
-hipError_t launch_resize_half_bgr8(const uint8_t *src, int H, int W, uint8_t *dst, hipStream_t s);
-hipError_t launch_resize_half_f32(const float *src, int H, int W, float *dst, int nan_to_zero, hipStream_t s);
-hipError_t launch_nan_to_zero(float *img, size_t n, hipStream_t s);
-hipError_t launch_edge_strength(const uint8_t *bgr, int H, int W, uint8_t *gray, uint8_t *lap, hipStream_t s);
-hipError_t launch_threshold_median(const uint8_t *lap, int H, int W, int thr, int median, uint8_t *mask, hipStream_t s);
-hipError_t launch_chamfer(const uint8_t *mask, int H, int W, int *G, int *scratch, int *dist_fix, float *dist_f32,
-                          unsigned int *minmax, hipStream_t s);
-hipError_t launch_canny(const uint8_t *bgr, int H, int W, int low, int high, int l2_bgr, const uint8_t *keep, uint8_t *gray,
-                        int *mag, uint8_t *dir, uint8_t *label, uint8_t *edges, uint8_t *inv, int *changed, int *rounds_out,
-                        hipStream_t s);
-hipError_t launch_edge_scatter_ros(int dtype, const uint8_t *edges, const float *depth, int H, int W, const int *block_offsets,
-                                   double fx, double fy, double cx, double cy, void *X, void *Y, void *Z, int capacity,
-                                   hipStream_t s);
-hipError_t launch_dt_store(int dtype, const int *dist_fix, const float *dist_f32, int H, int W, const unsigned int *minmax,
-                           int normalize, double lo, double hi, void *dst, int pitch, float *plain, float *dst32, hipStream_t s);
-hipError_t launch_gate_by_mask(uint8_t *grad, const uint8_t *mask, int H, int W, hipStream_t s);
-hipError_t launch_edge_count_scan(const uint8_t *lap, const uint16_t *depth, int H, int W, int thr, int *block_counts,
-                                  int *total, hipStream_t s);
-hipError_t launch_edge_scatter(int dtype, const uint8_t *lap, const uint16_t *depth, int H, int W, int thr,
-                               const int *block_offsets, double fx, double fy, double cx, double cy, double z_scaling,
-                               void *X, void *Y, void *Z, int capacity, hipStream_t s);
-}  // namespace ea
 
 using namespace ea;
 
@@ -105,7 +37,7 @@ static int fail(int code, const std::string &msg) {
   return code;
 }
 
-// for the library's other translation units (ea_comm.hip): the thread-local error message, a batch's stream
+// (ea_launch.h) for ea_comm.hip
 extern "C" int ea_internal_fail(int code, const char *msg) { return fail(code, msg ? msg : ""); }
 
 #define HIPCHK(expr)                                                                          \
@@ -655,8 +587,6 @@ static void tile_order(const ea_problem *p, const double *xyz, int64_t n, int64_
   order.resize((size_t)n);
   for (int64_t i = 0; i < n; ++i) { const uint32_t k = key[(size_t)i]; order[(size_t)head[(size_t)(k >> 12) * nx + (k & 4095)]++] = (int32_t)i; }
 }
-
-extern "C" void ea_batch_destroy(ea_batch *b);
 
 extern "C" void ea_problem_destroy(ea_problem *p) {
   if (!p) return;
@@ -1631,7 +1561,6 @@ extern "C" int ea_batch_bench_resident_poses(ea_batch *b, int reps, int evaluati
 // EMPTY kernel of grid x block threads, replayed between one event pair -- milliseconds per node.  What a launch of any
 // size costs when it does nothing; a kernel's duration cannot go below it, so (algorithmic bytes / floor) bounds the
 // roofline fraction a small launch can reach.
-namespace ea { hipError_t launch_empty(int grid, int block, hipStream_t stream); }
 extern "C" int ea_bench_graph_floor(int device, int nodes, int grid, int block, double *ms_per_node) {
   if (!ms_per_node || nodes < 1 || grid < 1 || block < 1 || block > 1024) return fail(EA_ERR_INVALID_ARG, "bad argument");
   int rc = check_device(device);
@@ -1717,6 +1646,31 @@ struct SolveRun {
 
 static double resolve_timeout_ms(const ea_options &o) { return o.solve_timeout_ms == 0.0 ? 5000.0 : o.solve_timeout_ms; }
 
+// the caller's options (NULL: the defaults), validated
+static int resolve_options(const ea_options *opt_in, ea_options *o) {
+  if (opt_in) *o = *opt_in; else ea_default_options(o);
+  return check_options(*o);
+}
+
+// Value-initialised: a field LMOptions gains and this mapping forgets is zero in every driver, not stack garbage in one.
+static LMOptions lm_options(const ea_options &o) {
+  LMOptions lo{};
+  lo.max_num_iterations = o.max_num_iterations;
+  lo.function_tolerance = o.function_tolerance;
+  lo.gradient_tolerance = o.gradient_tolerance;
+  lo.parameter_tolerance = o.parameter_tolerance;
+  lo.initial_trust_region_radius = o.initial_trust_region_radius;
+  lo.max_trust_region_radius = o.max_trust_region_radius;
+  lo.min_trust_region_radius = o.min_trust_region_radius;
+  lo.min_relative_decrease = o.min_relative_decrease;
+  lo.min_lm_diagonal = o.min_lm_diagonal;
+  lo.max_lm_diagonal = o.max_lm_diagonal;
+  lo.max_num_consecutive_invalid_steps = o.max_num_consecutive_invalid_steps;
+  lo.jacobi_scaling = o.jacobi_scaling;
+  lo.strategy = o.strategy;
+  return lo;
+}
+
 static int solve_start(SolveRun &r, const ea_options &o, const LMOptions &lo, const double *q, const double *t) {
   ea_batch *b = r.b;
   int rc = batch_build(b);
@@ -1764,6 +1718,23 @@ static int solve_start(SolveRun &r, const ea_options &o, const LMOptions &lo, co
   return EA_OK;
 }
 
+// One launch of ea_lm_iter_kernel: launch j = enq + 1 steps on what launch j - 1 left in the buffers of parity (j - 1) and
+// evaluates into those of parity j (launch 0 is a plain evaluation into parity 0, the caller's).  `count` problems fold
+// the rows of `fold`; *evaluated (nullable): the rows this launch writes.
+static int solve_launch_iter(SolveRun &r, const LMOptions &lo, int count, const GroupDesc &fold, int post_done,
+                             double **evaluated = nullptr) {
+  ea_batch *b = r.b;
+  LMState *st[2] = {b->d_states, reinterpret_cast<LMState *>(b->d_iter_alt)};
+  LMCold *cold[2] = {b->d_cold, reinterpret_cast<LMCold *>(b->d_iter_alt + (size_t)b->iter_alt_count * sizeof(LMState))};
+  double *rows[2] = {b->d_partials, b->d_partials_alt};
+  const int in = r.enq & 1, out = in ^ 1;
+  HIPCHK(launch_lm_iter(b->dtype, b->ppt, b->d_probs, count, b->chunk, b->max_chunks, b->xcd_remap, b->d_poses, rows[in], rows[out],
+                        b->buffer_loads, b->img32, b->x0, b->y0, b->z0, b->n0, b->d_groups, st[in], st[out], cold[in], cold[out],
+                        b->d_traces, lo, b->d_progress, b->dv_states, b->dv_traces, fold, post_done, b->stream, b->any_prior));
+  if (evaluated) *evaluated = rows[out];
+  return EA_OK;
+}
+
 // one look at the run's progress words; enqueues the next (evaluate, step) pair when the device is less than
 // `ahead` pairs ahead of the host
 static int solve_pump(SolveRun &r, const LMOptions &lo) {
@@ -1779,20 +1750,12 @@ static int solve_pump(SolveRun &r, const LMOptions &lo) {
   if (done != r.seen) { r.seen = done; r.moved = true; }
   if (r.enq < r.budget && r.enq - done < r.ahead) {
     if (r.fused) {
-      // launch j = enq + 1 steps on what launch j - 1 left in the buffers of parity (j - 1) and evaluates into those of parity j;
-      // launch 0 is the plain evaluation at the start pose
-      if (r.enq == 0) {
+      if (r.enq == 0) {  // launch 0: the plain evaluation at the start pose
         int rc = batch_launch_eval(b);
         if (rc != EA_OK) return rc;
       }
-      LMState *st[2] = {b->d_states, reinterpret_cast<LMState *>(b->d_iter_alt)};
-      LMCold *cold[2] = {b->d_cold, reinterpret_cast<LMCold *>(b->d_iter_alt + (size_t)b->iter_alt_count * sizeof(LMState))};
-      double *rows[2] = {b->d_partials, b->d_partials_alt};
-      const int in = r.enq & 1, out = in ^ 1;
-      HIPCHK(launch_lm_iter(b->dtype, b->ppt, b->d_probs, count, b->chunk, b->max_chunks, b->xcd_remap, b->d_poses, rows[in], rows[out],
-                            b->buffer_loads, b->img32, b->x0, b->y0, b->z0, b->n0, b->d_groups, st[in], st[out], cold[in], cold[out],
-                            b->d_traces, lo, b->d_progress, b->dv_states, b->dv_traces, b->group0, /*post_done=*/0, b->stream,
-                            b->any_prior));
+      int rc = solve_launch_iter(r, lo, count, b->group0, /*post_done=*/0);
+      if (rc != EA_OK) return rc;
     } else {
       int rc = batch_launch_eval(b);
       if (rc != EA_OK) return rc;
@@ -1872,6 +1835,64 @@ static void solve_report(const SolveRun &r, const ea_options &o, double ms, doub
   }
 }
 
+// The end of every on-device solve: the runs' results (solve_collect), the wall time since the entry point began, then
+// poses, summaries and the printed trace (solve_report).
+static int solve_finish(SolveRun *runs, size_t nruns, const ea_options &o, std::chrono::steady_clock::time_point t0, double *q,
+                        double *t, ea_summary *summaries) {
+  for (size_t k = 0; k < nruns; ++k) {
+    int rc = solve_collect(runs[k], o, summaries != nullptr);
+    if (rc != EA_OK) return rc;
+  }
+  const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  for (size_t k = 0; k < nruns; ++k) {
+    const SolveRun &r = runs[k];
+    solve_report(r, o, ms, q + 4 * r.first, t + 3 * r.first, summaries ? summaries + r.first : nullptr);
+  }
+  return EA_OK;
+}
+
+// Look-ahead rule of the point-sharded solves that keep the exchange on the stream.  The host keeps `ahead` iterations
+// queued; iteration i + ahead is enqueued once iteration i is COMPLETE (the step kernel posts that behind its flag) unless
+// the solve had finished by iteration i.  The decision depends on (i, the iteration the solve finished at) only --
+// quantities every rank agrees on, whenever its host happens to look -- so every rank enqueues exactly (finishing
+// iteration + ahead) iterations and the collectives match up without the ranks talking about it.  The device never waits
+// for the host: the next iteration is in the queue while this one runs.  (Round 2 enqueued rounds of four behind an event
+// wait: the device idled while the host looked and enqueued, 5.1e4 against 8.1e4 iterations/s unsharded on one rank.)
+// enqueue_iteration() puts one iteration (launches + collective) on the stream; *finished: the solve was seen finished,
+// its result delivered -- else it was cut short by the launch budget and has to be fetched (r.fetch).
+template <typename Enqueue>
+static int solve_lookahead(SolveRun &r, const ea_options &o, Enqueue &enqueue_iteration, bool *finished) {
+  ea_batch *b = r.b;
+  const double timeout_ms = resolve_timeout_ms(o);
+  int rc;
+  *finished = false;
+  for (int k = 0; k < r.ahead && r.enq < r.budget; ++k) {
+    if ((rc = enqueue_iteration()) != EA_OK) return rc;
+    ++r.enq;
+  }
+  for (int i = 0; i < r.enq; ++i) {
+    SpinWait wait(timeout_ms);
+    int seen = -1;
+    while (__atomic_load_n(&b->h_progress[2], __ATOMIC_ACQUIRE) < i + 1) {
+      const int started = __atomic_load_n(&b->h_progress[1], __ATOMIC_ACQUIRE);
+      if (started != seen) { seen = started; wait.progress(); }
+      else if (wait.poll()) {
+        b->needs_drain = true;
+        return fail(EA_ERR_HIP, "sharded solve deadline: no progress on the device (is every rank taking part in the collective?)");
+      }
+    }
+    // the flag as iteration i left it; the final state was delivered in front of it
+    if (__atomic_load_n(&b->h_progress[0], __ATOMIC_ACQUIRE) == 0 && b->hd_states[0].num_evals <= i + 1) { *finished = true; break; }
+    if (r.enq < r.budget) {
+      if ((rc = enqueue_iteration()) != EA_OK) return rc;
+      ++r.enq;
+    }
+  }
+  r.fetch = !*finished;
+  r.done = true;
+  return EA_OK;
+}
+
 // Sub-batches for the concurrent solve: contiguous slices of the parent's problems, each with its own stream and
 // buffers, created on first use and kept.
 static int batch_parts(ea_batch *b, int parts) {
@@ -1894,22 +1915,8 @@ extern "C" int ea_batch_solve(ea_batch *b, const ea_options *opt_in, double *q, 
   static_assert(EA_MAX_TRACE == kTrace, "trace length mismatch");
   const auto t0 = std::chrono::steady_clock::now();
   ea_options o;
-  if (opt_in) o = *opt_in; else ea_default_options(&o);
-  if (int vrc = check_options(o)) return vrc;
-  LMOptions lo;
-  lo.max_num_iterations = o.max_num_iterations;
-  lo.function_tolerance = o.function_tolerance;
-  lo.gradient_tolerance = o.gradient_tolerance;
-  lo.parameter_tolerance = o.parameter_tolerance;
-  lo.initial_trust_region_radius = o.initial_trust_region_radius;
-  lo.max_trust_region_radius = o.max_trust_region_radius;
-  lo.min_trust_region_radius = o.min_trust_region_radius;
-  lo.min_relative_decrease = o.min_relative_decrease;
-  lo.min_lm_diagonal = o.min_lm_diagonal;
-  lo.max_lm_diagonal = o.max_lm_diagonal;
-  lo.max_num_consecutive_invalid_steps = o.max_num_consecutive_invalid_steps;
-  lo.jacobi_scaling = o.jacobi_scaling;
-  lo.strategy = o.strategy;
+  if (int vrc = resolve_options(opt_in, &o)) return vrc;
+  const LMOptions lo = lm_options(o);
   const int count = (int)b->probs.size();
   // Concurrent halves: a batch of many problems is solved as two sub-batches on two streams, pumped by this one
   // thread.  Inside a batch the evaluation (all CUs busy) and the LM step (one workgroup per problem, pure latency)
@@ -1972,13 +1979,7 @@ extern "C" int ea_batch_solve(ea_batch *b, const ea_options *opt_in, double *q, 
       return fail(EA_ERR_HIP, msg);
     }
   }
-  for (SolveRun &r : runs) {
-    int rc = solve_collect(r, o, summaries != nullptr);
-    if (rc != EA_OK) return rc;
-  }
-  const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  for (SolveRun &r : runs) solve_report(r, o, ms, q + 4 * r.first, t + 3 * r.first, summaries ? summaries + r.first : nullptr);
-  return EA_OK;
+  return solve_finish(runs.data(), runs.size(), o, t0, q, t, summaries);
 }
 
 extern "C" int ea_batch_bench_eval(ea_batch *b, const double *q, const double *t, int warmup, int steps,
@@ -2463,12 +2464,6 @@ extern "C" int ea_batch_get_info(const ea_batch *b, const char *key, int64_t *va
 
 // ---- single-problem conveniences = batch of one ------------------------------------------------
 
-extern "C" int ea_batch_row_offsets(ea_batch *b, int64_t *offsets);
-extern "C" int ea_batch_eval_rows(ea_batch *b, const double *q, const double *t, int corrected, int layout, void *r_host,
-                                  void *J_host, int64_t capacity_rows, int64_t *n_invalid);
-extern "C" int ea_batch_eval_rows_device(ea_batch *b, const double *q, const double *t, int corrected, int layout, void *r_dev,
-                                         void *J_dev, int64_t capacity_rows, int64_t *n_invalid);
-
 static int self_batch(ea_problem *p, ea_batch **out) {
   if (!p) return fail(EA_ERR_INVALID_ARG, "NULL problem");
   if (!p->self) {
@@ -2753,27 +2748,13 @@ extern "C" int ea_solve_sharded(ea_problem *p, const ea_options *opt_in, ea_allr
   if (!p || !allreduce || !q || !t) return fail(EA_ERR_INVALID_ARG, "NULL argument");
   const auto t0 = std::chrono::steady_clock::now();
   ea_options o;
-  if (opt_in) o = *opt_in; else ea_default_options(&o);
-  if (int vrc = check_options(o)) return vrc;
+  if (int vrc = resolve_options(opt_in, &o)) return vrc;
   ea_batch *b = nullptr;
   int rc = self_batch(p, &b);
   if (rc != EA_OK) return rc;
   rc = batch_build(b);
   if (rc != EA_OK) return rc;
-  LMOptions lo;
-  lo.max_num_iterations = o.max_num_iterations;
-  lo.function_tolerance = o.function_tolerance;
-  lo.gradient_tolerance = o.gradient_tolerance;
-  lo.parameter_tolerance = o.parameter_tolerance;
-  lo.initial_trust_region_radius = o.initial_trust_region_radius;
-  lo.max_trust_region_radius = o.max_trust_region_radius;
-  lo.min_trust_region_radius = o.min_trust_region_radius;
-  lo.min_relative_decrease = o.min_relative_decrease;
-  lo.min_lm_diagonal = o.min_lm_diagonal;
-  lo.max_lm_diagonal = o.max_lm_diagonal;
-  lo.max_num_consecutive_invalid_steps = o.max_num_consecutive_invalid_steps;
-  lo.jacobi_scaling = o.jacobi_scaling;
-  lo.strategy = o.strategy;
+  const LMOptions lo = lm_options(o);
   LMState st;
   LMCold cold;
   std::memset(&cold, 0, sizeof(cold));
@@ -2799,10 +2780,7 @@ extern "C" int ea_solve_sharded(ea_problem *p, const ea_options *opt_in, ea_allr
     if (allreduce(acc, kAccSlots, user) != 0) return fail(EA_ERR_STATE, "the all-reduce callback reported a failure");
     // the prior once, on the reduced sums (every rank holds the same prior and adds the same bits)
     if (b->any_prior) prior_add(b->h_priors[0], pose, acc);
-    LMPending pend;
-    if (st.num_evals == 0) lm_begin_rt(&st, &cold, &tr, &lo, acc, &pend);
-    else lm_advance_rt(&st, &cold, &tr, &lo, acc, &pend);
-    lm_flush(&pend, &cold, &tr, acc);
+    lm_feed(&st, &cold, &tr, &lo, acc);
   }
   if (st.running) return fail(EA_ERR_STATE, "sharded solve did not terminate");
   for (int k = 0; k < 4; ++k) q[k] = st.x[k];
@@ -2826,25 +2804,11 @@ extern "C" int ea_solve_sharded_device(ea_problem *p, const ea_options *opt_in, 
   if (reinterpret_cast<uintptr_t>(device_sums) % 16 != 0) return fail(EA_ERR_INVALID_ARG, "device_sums must be 16-byte aligned");
   const auto t0 = std::chrono::steady_clock::now();
   ea_options o;
-  if (opt_in) o = *opt_in; else ea_default_options(&o);
-  if (int vrc = check_options(o)) return vrc;
+  if (int vrc = resolve_options(opt_in, &o)) return vrc;
   ea_batch *b = nullptr;
   int rc = self_batch(p, &b);
   if (rc != EA_OK) return rc;
-  LMOptions lo;
-  lo.max_num_iterations = o.max_num_iterations;
-  lo.function_tolerance = o.function_tolerance;
-  lo.gradient_tolerance = o.gradient_tolerance;
-  lo.parameter_tolerance = o.parameter_tolerance;
-  lo.initial_trust_region_radius = o.initial_trust_region_radius;
-  lo.max_trust_region_radius = o.max_trust_region_radius;
-  lo.min_trust_region_radius = o.min_trust_region_radius;
-  lo.min_relative_decrease = o.min_relative_decrease;
-  lo.min_lm_diagonal = o.min_lm_diagonal;
-  lo.max_lm_diagonal = o.max_lm_diagonal;
-  lo.max_num_consecutive_invalid_steps = o.max_num_consecutive_invalid_steps;
-  lo.jacobi_scaling = o.jacobi_scaling;
-  lo.strategy = o.strategy;
+  const LMOptions lo = lm_options(o);
   SolveRun r;
   r.b = b;
   rc = solve_start(r, o, lo, q, t);  // builds the batch, uploads pose + state, arms the progress words
@@ -2856,15 +2820,6 @@ extern "C" int ea_solve_sharded_device(ea_problem *p, const ea_options *opt_in, 
   }
   if (b->any_prior)  // the step kernel adds the prior once, to the reduced sums: it reads it behind its one-row group table
     HIPCHK(hipMemcpyAsync(b->d_one_row + 1, b->d_priors, sizeof(PriorDesc), hipMemcpyDeviceToDevice, b->stream));
-  // Look-ahead rule.  The host keeps `ahead` iterations queued; iteration i + ahead is enqueued once iteration i is
-  // COMPLETE (the step kernel posts that behind its flag) unless the solve had finished by iteration i.  The decision
-  // depends on (i, the iteration the solve finished at) only -- quantities every rank agrees on, whenever its host happens
-  // to look -- so every rank enqueues exactly (finishing iteration + ahead) iterations and the collectives match up
-  // without the ranks talking about it.  The device never waits for the host: the next iteration is in the queue while
-  // this one runs.  (Round 2 enqueued rounds of four behind an event wait: the device idled while the host looked and
-  // enqueued, 5.1e4 against 8.1e4 iterations/s unsharded on one rank.)
-  const int ahead = o.iterations_per_sync > 0 ? o.iterations_per_sync : 2;
-  const double timeout_ms = resolve_timeout_ms(o);
   auto enqueue_iteration = [&]() -> int {
     int rc2 = batch_launch_eval(b);  // (an empty shard launches nothing; its fold below yields zeros)
     if (rc2 != EA_OK) return rc2;
@@ -2875,43 +2830,16 @@ extern "C" int ea_solve_sharded_device(ea_problem *p, const ea_options *opt_in, 
     }
     HIPCHK(launch_lm_step(b->d_one_row, 1, device_sums, b->d_poses, b->d_states, b->d_cold, b->d_traces, lo, b->d_progress,
                           b->dv_states, b->dv_traces, GroupDesc{0, 1, 0, 1}, /*post_done=*/1, b->stream, b->any_prior));
-    ++r.enq;
     return EA_OK;
   };
-  for (int k = 0; k < ahead && r.enq < r.budget; ++k)
-    if ((rc = enqueue_iteration()) != EA_OK) return rc;
-  bool finished = false;
-  for (int i = 0; i < r.enq; ++i) {
-    SpinWait wait(timeout_ms);
-    int seen = -1;
-    while (__atomic_load_n(&b->h_progress[2], __ATOMIC_ACQUIRE) < i + 1) {
-      const int started = __atomic_load_n(&b->h_progress[1], __ATOMIC_ACQUIRE);
-      if (started != seen) { seen = started; wait.progress(); }
-      else if (wait.poll()) {
-        b->needs_drain = true;
-        return fail(EA_ERR_HIP, "sharded solve deadline: no progress on the device (is every rank taking part in the collective?)");
-      }
-    }
-    // the flag as iteration i left it; the final state was delivered in front of it
-    if (__atomic_load_n(&b->h_progress[0], __ATOMIC_ACQUIRE) == 0 && b->hd_states[0].num_evals <= i + 1) { finished = true; break; }
-    if (r.enq < r.budget && (rc = enqueue_iteration()) != EA_OK) return rc;
-  }
+  bool finished;
+  if ((rc = solve_lookahead(r, o, enqueue_iteration, &finished)) != EA_OK) return rc;
   // the iterations queued past the end find the solve finished and return at once, their collectives still run (on every
   // rank alike); the caller's buffer must outlive them
   HIPCHK(hipStreamSynchronize(b->stream));
-  r.fetch = !finished;
-  r.done = true;
-  rc = solve_collect(r, o, summary != nullptr);
-  if (rc != EA_OK) return rc;
-  const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  solve_report(r, o, ms, q, t, summary);
-  return EA_OK;
+  return solve_finish(&r, 1, o, t0, q, t, summary);
 }
 
-// Coarse-to-fine driver (BASELINE config C3; the reference has no pyramid -- SURVEY 8f row 4): levels[0] is the finest
-// level; the solve starts on levels[nlevels-1] and carries the pose down level by level.  Every level is a complete
-// problem (its own points, DT image and intrinsics scaled by the caller).  A level that fails (termination FAILURE)
-// stops the descent and its status is returned through the summaries; q, t hold the last pose reached.
 // The point-sharded solve in the one-launch-per-iteration form (ea_solve_sharded_comm).  Between evaluation and step sits the
 // exchange; with ea_lm_iter_kernel every workgroup folds the rows itself, so what is exchanged is the ROWS: launch j
 // evaluates this rank's shard into its rows, ONE in-place all-reduce sums every rank's rows (a few tens of KB instead of 256
@@ -2928,25 +2856,11 @@ extern "C" int ea_internal_solve_sharded_rows(ea_problem *p, const ea_options *o
   *used = 0;
   const auto t0 = std::chrono::steady_clock::now();
   ea_options o;
-  if (opt_in) o = *opt_in; else ea_default_options(&o);
-  if (int vrc = check_options(o)) return vrc;
+  if (int vrc = resolve_options(opt_in, &o)) return vrc;
   ea_batch *b = nullptr;
   int rc = self_batch(p, &b);
   if (rc != EA_OK) return rc;
-  LMOptions lo;
-  lo.max_num_iterations = o.max_num_iterations;
-  lo.function_tolerance = o.function_tolerance;
-  lo.gradient_tolerance = o.gradient_tolerance;
-  lo.parameter_tolerance = o.parameter_tolerance;
-  lo.initial_trust_region_radius = o.initial_trust_region_radius;
-  lo.max_trust_region_radius = o.max_trust_region_radius;
-  lo.min_trust_region_radius = o.min_trust_region_radius;
-  lo.min_relative_decrease = o.min_relative_decrease;
-  lo.min_lm_diagonal = o.min_lm_diagonal;
-  lo.max_lm_diagonal = o.max_lm_diagonal;
-  lo.max_num_consecutive_invalid_steps = o.max_num_consecutive_invalid_steps;
-  lo.jacobi_scaling = o.jacobi_scaling;
-  lo.strategy = o.strategy;
+  const LMOptions lo = lm_options(o);
   SolveRun r;
   r.b = b;
   rc = solve_start(r, o, lo, q, t);  // builds the batch, uploads pose + state, arms the progress words, decides r.fused
@@ -2966,12 +2880,9 @@ extern "C" int ea_internal_solve_sharded_rows(ea_problem *p, const ea_options *o
     HIPCHK(cached_malloc(reinterpret_cast<void **>(&b->d_partials_alt), (size_t)cap * kAccSlots * sizeof(double), b->device));
     b->tiles_cap_alt = cap;
   }
-  double *rows[2] = {b->d_partials, b->d_partials_alt};
   if (max_rows > b->ntiles)
-    for (int k = 0; k < 2; ++k)
-      HIPCHK(hipMemsetAsync(rows[k] + (size_t)b->ntiles * kAccSlots, 0, (size_t)(max_rows - b->ntiles) * kAccSlots * sizeof(double), b->stream));
-  LMState *st[2] = {b->d_states, reinterpret_cast<LMState *>(b->d_iter_alt)};
-  LMCold *cold[2] = {b->d_cold, reinterpret_cast<LMCold *>(b->d_iter_alt + (size_t)b->iter_alt_count * sizeof(LMState))};
+    for (double *rows : {b->d_partials, b->d_partials_alt})
+      HIPCHK(hipMemsetAsync(rows + (size_t)b->ntiles * kAccSlots, 0, (size_t)(max_rows - b->ntiles) * kAccSlots * sizeof(double), b->stream));
   const GroupDesc fold_range = {0, max_rows, 0, 1};
   auto exchange = [&](double *buf) -> int {
     if (allreduce(buf, max_rows * kAccSlots, (void *)b->stream, user) != 0) {
@@ -2980,56 +2891,32 @@ extern "C" int ea_internal_solve_sharded_rows(ea_problem *p, const ea_options *o
     }
     return EA_OK;
   };
-  // the look-ahead rule of ea_solve_sharded_device: iteration i + ahead goes out once iteration i is complete unless the solve
-  // had finished by iteration i -- every rank enqueues the same number of launches and collectives
-  const int ahead = o.iterations_per_sync > 0 ? o.iterations_per_sync : 2;
-  const double timeout_ms = resolve_timeout_ms(o);
   rc = batch_launch_eval(b);  // launch 0: the evaluation at the start pose
   if (rc != EA_OK) return rc;
-  if ((rc = exchange(rows[0])) != EA_OK) return rc;
+  if ((rc = exchange(b->d_partials)) != EA_OK) return rc;
+  // (solve_lookahead: every rank enqueues the same number of launches and collectives)
   auto enqueue_iteration = [&]() -> int {
-    const int in = r.enq & 1, out = in ^ 1;
-    HIPCHK(launch_lm_iter(b->dtype, b->ppt, b->d_probs, 1, b->chunk, b->max_chunks, b->xcd_remap, b->d_poses, rows[in], rows[out],
-                          b->buffer_loads, b->img32, b->x0, b->y0, b->z0, b->n0, b->d_groups, st[in], st[out], cold[in], cold[out],
-                          b->d_traces, lo, b->d_progress, b->dv_states, b->dv_traces, fold_range, /*post_done=*/1, b->stream,
-                          b->any_prior));
-    int rc2 = exchange(rows[out]);
+    double *evaluated = nullptr;
+    int rc2 = solve_launch_iter(r, lo, 1, fold_range, /*post_done=*/1, &evaluated);
     if (rc2 != EA_OK) return rc2;
-    ++r.enq;
-    return EA_OK;
+    return exchange(evaluated);
   };
-  for (int k = 0; k < ahead && r.enq < r.budget; ++k)
-    if ((rc = enqueue_iteration()) != EA_OK) return rc;
-  bool finished = false;
-  for (int i = 0; i < r.enq; ++i) {
-    SpinWait wait(timeout_ms);
-    int seen = -1;
-    while (__atomic_load_n(&b->h_progress[2], __ATOMIC_ACQUIRE) < i + 1) {
-      const int started = __atomic_load_n(&b->h_progress[1], __ATOMIC_ACQUIRE);
-      if (started != seen) { seen = started; wait.progress(); }
-      else if (wait.poll()) {
-        b->needs_drain = true;
-        return fail(EA_ERR_HIP, "sharded solve deadline: no progress on the device (is every rank taking part in the collective?)");
-      }
-    }
-    if (__atomic_load_n(&b->h_progress[0], __ATOMIC_ACQUIRE) == 0 && b->hd_states[0].num_evals <= i + 1) { finished = true; break; }
-    if (r.enq < r.budget && (rc = enqueue_iteration()) != EA_OK) return rc;
-  }
+  bool finished;
+  if ((rc = solve_lookahead(r, o, enqueue_iteration, &finished)) != EA_OK) return rc;
   // A finished solve has delivered its result into pinned host memory in front of the flag seen above: return on it.  The
   // launches and collectives queued past the end (every rank alike) drain behind our back -- they touch only buffers the
   // library owns, and whatever uses this stream or the communicator next is ordered behind them (ea_comm_destroy waits for
   // the stream of its last solve).  Only a solve cut short by the launch budget has to wait and fetch.
   if (!finished) HIPCHK(hipStreamSynchronize(b->stream));
-  r.fetch = !finished;
-  r.done = true;
-  rc = solve_collect(r, o, summary != nullptr);
-  if (rc != EA_OK) return rc;
-  const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  solve_report(r, o, ms, q, t, summary);
+  if ((rc = solve_finish(&r, 1, o, t0, q, t, summary)) != EA_OK) return rc;
   *used = 1;
   return EA_OK;
 }
 
+// Coarse-to-fine driver (BASELINE config C3; the reference has no pyramid -- SURVEY 8f row 4): levels[0] is the finest
+// level; the solve starts on levels[nlevels-1] and carries the pose down level by level.  Every level is a complete
+// problem (its own points, DT image and intrinsics scaled by the caller).  A level that fails (termination FAILURE)
+// stops the descent and its status is returned through the summaries; q, t hold the last pose reached.
 extern "C" int ea_solve_pyramid(ea_problem *const *levels, int nlevels, const ea_options *opt, double q[4], double t[3],
                                 ea_summary *summaries) {
   if (!levels || nlevels < 1 || !q || !t) return fail(EA_ERR_INVALID_ARG, "bad argument");
@@ -3048,18 +2935,93 @@ extern "C" int ea_solve_pyramid(ea_problem *const *levels, int nlevels, const ea
   return EA_OK;
 }
 
-static int ref_points_from_last_now(ea_problem *p, int kind, const uint16_t *depth, int height, int width, double z_scaling,
-                                    int threshold);  // (with the frame producers below)
-struct RefPointsJob;
-static int ref_points_begin(ea_problem *p, int kind, const uint16_t *depth, int height, int width, int threshold, RefPointsJob *job);
-static int ref_points_finish(ea_problem *p, const RefPointsJob &job, int height, int width, double z_scaling, int threshold);
-// what ref_points_begin left in flight on the null stream: the depth frame on its way up and the per-block edge counts
+// ---- the reference frame's edge points out of the frame producers' workspace (the producers themselves: further down) ----
+
+namespace {
+struct WsCarver {
+  unsigned char *base;
+  size_t off = 0;
+  template <typename U> U *take(size_t n) {
+    off = (off + 255) & ~(size_t)255;
+    U *r = reinterpret_cast<U *>(base + off);
+    off += n * sizeof(U);
+    return r;
+  }
+};
+}  // namespace
+
+// The new reference frame's edge points from what the "now" producer left in the workspace, in two halves so that the tracker
+// can put the first -- depth upload and per-block edge counts, both asynchronous on the null stream -- in front of the solve of
+// the previous reference (which runs on the batch's own non-blocking stream and touches neither the workspace nor the depth)
+// and the second -- count read-back, compaction -- behind it.  ref_points_finish is also the tail of the full producers
+// (ea_problem_set_ref_frame[_masked|_canny]), which fill the job from their own carve of the workspace.
+// What ref_points_begin left in flight on the null stream: the depth frame on its way up and the per-block edge counts
 struct RefPointsJob {
   bool started = false;
   uint8_t *d_edges = nullptr;
   uint16_t *d_depth = nullptr;
   int *d_counts = nullptr, *d_total = nullptr;
 };
+
+static int ref_points_begin(ea_problem *p, int kind, const uint16_t *depth, int height, int width, int threshold, RefPointsJob *job) {
+  job->started = false;
+  if (p->ws_now_kind != kind || p->ws_now_h != height || p->ws_now_w != width || (int64_t)height * width < 4096)
+    return EA_ERR_STATE;
+  HIPCHK(hipSetDevice(p->device));
+  const size_t np = (size_t)height * width;
+  // the carve of the producer that ran, to find its buffers again
+  WsCarver ws{p->ws};
+  uint8_t *d_bgr = ws.take<uint8_t>(np * 3);
+  uint8_t *d_gray = ws.take<uint8_t>(np);
+  uint8_t *d_edges;
+  if (kind == 1) {
+    d_edges = ws.take<uint8_t>(np);  // d_lap
+  } else {
+    (void)ws.take<int>(np);      // magnitudes
+    (void)ws.take<uint8_t>(np);  // direction classes
+    (void)ws.take<uint8_t>(np);  // labels
+    d_edges = ws.take<uint8_t>(np);
+  }
+  // the colour frame and its gray version are not needed any more: depth and the block counts take their place
+  uint16_t *d_depth = reinterpret_cast<uint16_t *>(d_bgr);
+  const int nblocks = (int)((np + 1023) / 1024);
+  int *d_counts = reinterpret_cast<int *>(d_gray);
+  int *d_total = d_counts + nblocks;
+  p->ws_now_kind = 0;
+  HIPCHK(hipMemcpyAsync(d_depth, depth, np * 2, hipMemcpyHostToDevice, nullptr));
+  HIPCHK(launch_edge_count_scan(d_edges, d_depth, height, width, threshold, d_counts, d_total, nullptr));
+  job->started = true;
+  job->d_edges = d_edges; job->d_depth = d_depth; job->d_counts = d_counts; job->d_total = d_total;
+  return EA_OK;
+}
+
+static int ref_points_finish(ea_problem *p, const RefPointsJob &job, int height, int width, double z_scaling, int threshold) {
+  if (!job.started) return EA_ERR_STATE;
+  int total = 0;
+  HIPCHK(hipMemcpy(&total, job.d_total, sizeof(int), hipMemcpyDeviceToHost));
+  p->version++;
+  int rc = reserve_points(p, total);
+  if (rc != EA_OK) return rc;
+  if (total > 0) {
+    HIPCHK(launch_edge_scatter(p->dtype, job.d_edges, job.d_depth, height, width, threshold, job.d_counts, p->cam.fx, p->cam.fy, p->cam.cx,
+                               p->cam.cy, z_scaling, p->d_x, p->d_y, p->d_z, total, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+  }
+  p->n = total;
+  return EA_OK;
+}
+
+// Edge points of the frame the last set_now_frame[_canny] call processed, from what that call left in the workspace
+// (Laplacian strength / Canny edge map): only the depth image goes up, no second upload or filtering of the colour
+// frame.  Same thresholds, same compaction and back-projection as ea_problem_set_ref_frame[_canny] => the same points.
+// Returns EA_ERR_STATE when the workspace does not hold that frame (the caller then takes the full path).
+static int ref_points_from_last_now(ea_problem *p, int kind, const uint16_t *depth, int height, int width, double z_scaling,
+                                    int threshold) {
+  RefPointsJob job;
+  int rc = ref_points_begin(p, kind, depth, height, width, threshold, &job);
+  if (rc != EA_OK) return rc;
+  return ref_points_finish(p, job, height, width, z_scaling, threshold);
+}
 
 // ---- frame-to-frame driver (the reference aligns one stored pair, src/ea.cpp:155-200) -------------
 // Every pushed frame is aligned against the previous one: its DT image is produced, the previous frame's edge points
@@ -3259,19 +3221,6 @@ extern "C" int ea_selftest_wave_reduce(int device, const float *in, double *out3
 
 // ---- frame producers: raw images -> edge points / DT image, on the device -------
 
-namespace {
-struct WsCarver {
-  unsigned char *base;
-  size_t off = 0;
-  template <typename U> U *take(size_t n) {
-    off = (off + 255) & ~(size_t)255;
-    U *r = reinterpret_cast<U *>(base + off);
-    off += n * sizeof(U);
-    return r;
-  }
-};
-}  // namespace
-
 static int ensure_ws(ea_problem *p, size_t bytes) {
   p->ws_now_kind = 0;  // every producer starts by calling this: whatever the workspace held is about to be overwritten
   if (p->ws_bytes >= bytes) return EA_OK;
@@ -3314,82 +3263,7 @@ static int ref_frame_impl(ea_problem *p, const uint8_t *bgr, const uint8_t *mask
     HIPCHK(launch_gate_by_mask(d_lap, d_keep, height, width, nullptr));
   }
   HIPCHK(launch_edge_count_scan(d_lap, d_depth, height, width, threshold, d_counts, d_total, nullptr));
-  int total = 0;
-  HIPCHK(hipMemcpy(&total, d_total, sizeof(int), hipMemcpyDeviceToHost));
-  p->version++;
-  rc = reserve_points(p, total);
-  if (rc != EA_OK) return rc;
-  if (total > 0) {
-    HIPCHK(launch_edge_scatter(p->dtype, d_lap, d_depth, height, width, threshold, d_counts, p->cam.fx, p->cam.fy, p->cam.cx,
-                               p->cam.cy, z_scaling, p->d_x, p->d_y, p->d_z, total, nullptr));
-    HIPCHK(hipDeviceSynchronize());
-  }
-  p->n = total;
-  return EA_OK;
-}
-
-// Edge points of the frame the last set_now_frame[_canny] call processed, from what that call left in the workspace
-// (Laplacian strength / Canny edge map): only the depth image goes up, no second upload or filtering of the colour
-// frame.  Same thresholds, same compaction and back-projection as ea_problem_set_ref_frame[_canny] => the same points.
-// Returns EA_ERR_STATE when the workspace does not hold that frame (the caller then takes the full path).
-// The new reference frame's edge points from what the "now" producer left in the workspace, in two halves so that the tracker
-// can put the first -- depth upload and per-block edge counts, both asynchronous on the null stream -- in front of the solve of
-// the previous reference (which runs on the batch's own non-blocking stream and touches neither the workspace nor the depth)
-// and the second -- count read-back, compaction -- behind it.
-static int ref_points_begin(ea_problem *p, int kind, const uint16_t *depth, int height, int width, int threshold, RefPointsJob *job) {
-  job->started = false;
-  if (p->ws_now_kind != kind || p->ws_now_h != height || p->ws_now_w != width || (int64_t)height * width < 4096)
-    return EA_ERR_STATE;
-  HIPCHK(hipSetDevice(p->device));
-  const size_t np = (size_t)height * width;
-  // the carve of the producer that ran, to find its buffers again
-  WsCarver ws{p->ws};
-  uint8_t *d_bgr = ws.take<uint8_t>(np * 3);
-  uint8_t *d_gray = ws.take<uint8_t>(np);
-  uint8_t *d_edges;
-  if (kind == 1) {
-    d_edges = ws.take<uint8_t>(np);  // d_lap
-  } else {
-    (void)ws.take<int>(np);      // magnitudes
-    (void)ws.take<uint8_t>(np);  // direction classes
-    (void)ws.take<uint8_t>(np);  // labels
-    d_edges = ws.take<uint8_t>(np);
-  }
-  // the colour frame and its gray version are not needed any more: depth and the block counts take their place
-  uint16_t *d_depth = reinterpret_cast<uint16_t *>(d_bgr);
-  const int nblocks = (int)((np + 1023) / 1024);
-  int *d_counts = reinterpret_cast<int *>(d_gray);
-  int *d_total = d_counts + nblocks;
-  p->ws_now_kind = 0;
-  HIPCHK(hipMemcpyAsync(d_depth, depth, np * 2, hipMemcpyHostToDevice, nullptr));
-  HIPCHK(launch_edge_count_scan(d_edges, d_depth, height, width, threshold, d_counts, d_total, nullptr));
-  job->started = true;
-  job->d_edges = d_edges; job->d_depth = d_depth; job->d_counts = d_counts; job->d_total = d_total;
-  return EA_OK;
-}
-
-static int ref_points_finish(ea_problem *p, const RefPointsJob &job, int height, int width, double z_scaling, int threshold) {
-  if (!job.started) return EA_ERR_STATE;
-  int total = 0;
-  HIPCHK(hipMemcpy(&total, job.d_total, sizeof(int), hipMemcpyDeviceToHost));
-  p->version++;
-  int rc = reserve_points(p, total);
-  if (rc != EA_OK) return rc;
-  if (total > 0) {
-    HIPCHK(launch_edge_scatter(p->dtype, job.d_edges, job.d_depth, height, width, threshold, job.d_counts, p->cam.fx, p->cam.fy, p->cam.cx,
-                               p->cam.cy, z_scaling, p->d_x, p->d_y, p->d_z, total, nullptr));
-    HIPCHK(hipDeviceSynchronize());
-  }
-  p->n = total;
-  return EA_OK;
-}
-
-static int ref_points_from_last_now(ea_problem *p, int kind, const uint16_t *depth, int height, int width, double z_scaling,
-                                    int threshold) {
-  RefPointsJob job;
-  int rc = ref_points_begin(p, kind, depth, height, width, threshold, &job);
-  if (rc != EA_OK) return rc;
-  return ref_points_finish(p, job, height, width, z_scaling, threshold);
+  return ref_points_finish(p, RefPointsJob{true, d_lap, d_depth, d_counts, d_total}, height, width, z_scaling, threshold);
 }
 
 extern "C" int ea_problem_set_ref_frame(ea_problem *p, const uint8_t *bgr, const uint16_t *depth, int height, int width,
@@ -3501,18 +3375,7 @@ extern "C" int ea_problem_set_ref_frame_canny(ea_problem *p, const uint8_t *bgr,
   if (rc != EA_OK) return rc;
   // ref: utils.cpp:441 -- all_grad(i) > 0 && Z > 0 on the 0/255 edge map
   HIPCHK(launch_edge_count_scan(d_edges, d_depth, height, width, 0, d_counts, d_total, nullptr));
-  int total = 0;
-  HIPCHK(hipMemcpy(&total, d_total, sizeof(int), hipMemcpyDeviceToHost));
-  p->version++;
-  rc = reserve_points(p, total);
-  if (rc != EA_OK) return rc;
-  if (total > 0) {
-    HIPCHK(launch_edge_scatter(p->dtype, d_edges, d_depth, height, width, 0, d_counts, p->cam.fx, p->cam.fy, p->cam.cx,
-                               p->cam.cy, z_scaling, p->d_x, p->d_y, p->d_z, total, nullptr));
-    HIPCHK(hipDeviceSynchronize());
-  }
-  p->n = total;
-  return EA_OK;
+  return ref_points_finish(p, RefPointsJob{true, d_edges, d_depth, d_counts, d_total}, height, width, z_scaling, 0);
 }
 
 // Canny flavour of the current frame: get_distance_transform2 / _masked / _NoNormalize / _masked_NoNormalize
@@ -3828,7 +3691,6 @@ extern "C" int ea_problem_get_dt(ea_problem *p, double *image, int *height, int 
 }
 
 #ifdef EA_STAMPS
-namespace ea { hipError_t set_stamp_buffer(unsigned long long *buf); hipError_t set_lm_stamp_buffer(unsigned long long *buf); }
 static unsigned long long *g_lm_stamps_dev = nullptr;
 // diagnostic library only: stamps of the LM step kernel of problem 0 for the next solve(s); 64 x 8 words
 extern "C" int ea_debug_lm_stamps_begin(void) {

@@ -29,14 +29,8 @@
 #include <vector>
 
 #include "../../include/ea_hip.h"
+#include "ea_launch.h"  // (the ea_internal_* functions of ea_capi.hip)
 #include "ea_types.h"
-
-// ea_capi.hip
-extern "C" int ea_internal_fail(int code, const char *msg);
-extern "C" void *ea_internal_batch_stream(ea_batch *b, int *device);
-extern "C" int ea_internal_solve_sharded_rows(ea_problem *p, const ea_options *opt, ea_device_allreduce_fn allreduce,
-                                              int (*agree)(int vals[2], void *user), void *user, double q[4], double t[3],
-                                              ea_summary *summary, int *used);
 
 namespace {
 

@@ -38,6 +38,7 @@ extern __device__ int g_lm_probe_row;
     }                                                                                               \
   } while (0)
 #endif
+#include "ea_launch.h"
 #include "ea_lm.h"
 #include "ea_prior.h"
 #include "ea_types.h"
@@ -2078,7 +2079,7 @@ __global__ __launch_bounds__(256) void ea_aos_to_soa_kernel(const double *__rest
 #endif  // !EA_TU_VARIANT
 
 // ------------------------------------------------------------------------------------------------
-// launchers (called from ea_capi.cpp)
+// launchers (declared in ea_launch.h, called from ea_capi.hip)
 
 // The fused evaluation lives in two translation units: this file as it is (plain functor, every launch shape) and the
 // same file compiled with -DEA_TU_VARIANT through ea_kernels_var.hip (the distortion / second-camera functors only).
@@ -2126,11 +2127,6 @@ hipError_t launch_eval_fused_var(int tag, int dtype, int ppt, const ProblemDesc 
                                           buffer_loads, x0, y0, z0, n0, stream);
 }
 #else
-hipError_t launch_eval_fused_var(int tag, int dtype, int ppt, const ProblemDesc *probs, int nterms, int chunk, int max_chunks,
-                                 int xcd_remap, const PoseState *poses, double *partials, int terms_are_groups,
-                                 int buffer_loads, const void *x0, const void *y0, const void *z0, int n0,
-                                 hipStream_t stream);  // ea_kernels_var.hip
-
 template <int TAG>
 static hipError_t launch_eval_fused_t(int dtype, int ppt, int nt, int variant, const ProblemDesc *probs, int nterms, int chunk,
                                       int max_chunks, int xcd_remap, const PoseState *poses, double *partials,
@@ -2199,9 +2195,6 @@ hipError_t launch_eval_poses(int dtype, int ppt, int nt, int variant, const Prob
   return launch_eval_fused_t<1>(dtype, ppt, nt, variant, probs, nterms, chunk, max_chunks, xcd_remap, poses, partials, lds_bytes, wide,
                                 terms_are_groups, buffer_loads, img32, x0, y0, z0, n0, stream);
 }
-
-hipError_t launch_reduce_nt(int nt, const GroupDesc *groups, int count, const double *partials, EvalOut *out,
-                            hipStream_t stream);
 
 // evaluation into `partials` + the fold of `prev_rows` -> `prev_out` in one launch (ea_eval_fold_kernel)
 hipError_t launch_eval_fold(int dtype, int ppt, int nt, const ProblemDesc *probs, int nterms, int chunk, int max_chunks,

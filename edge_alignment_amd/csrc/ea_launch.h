@@ -1,0 +1,100 @@
+// ea_launch.h — what the library's translation units call in one another, each function declared once: the kernel
+// launchers of ea_kernels.hip / ea_kernels_var.hip / ea_preprocess.hip and the functions ea_capi.hip keeps for ea_comm.hip.
+// The defining files include it too: an extern "C" definition that drifts from its declaration here does not compile (a
+// hand-copied prototype in the caller would have linked and passed garbage); a drifted launcher fails to link, as before.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/ea_hip.h"
+#include "ea_lm.h"
+#include "ea_types.h"
+
+namespace ea {
+// ea_kernels.hip
+hipError_t launch_eval_fused(int dtype, int ppt, int nt, int variant, const ProblemDesc *probs, int nterms, int chunk,
+                             int max_chunks, int xcd_remap, const PoseState *poses, double *partials,
+                             int lds_bytes, int wide, int terms_are_groups, int buffer_loads, int img32, const void *x0, const void *y0,
+                             const void *z0, int n0, hipStream_t stream);
+hipError_t launch_eval_poses(int dtype, int ppt, int nt, int variant, const ProblemDesc *probs, int nterms, int chunk,
+                             int max_chunks, int xcd_remap, const PoseState *poses, double *partials,
+                             int lds_bytes, int wide, int terms_are_groups, int buffer_loads, int img32, const void *x0, const void *y0,
+                             const void *z0, int n0, hipStream_t stream);
+hipError_t launch_pixel_cost(int dtype, const ProblemDesc *probs, int problem, int n, const PoseState *poses, void *partials,
+                             hipStream_t stream);
+hipError_t launch_eval_rows(int dtype, int variant, int buffer_loads, int img32, int layout, int staged, const ProblemDesc *probs, int nterms,
+                            long long max_n, const PoseState *poses, int corrected, int nontemporal, long long total_rows,
+                            void *r_out, void *J_out, unsigned int *n_invalid, hipStream_t stream);
+hipError_t launch_eval_points(int dtype, const ProblemDesc *probs, int problem, int n, const PoseState *poses,
+                              double *r_out, double *J_out, int corrected, hipStream_t stream);
+hipError_t launch_reduce(const GroupDesc *groups, int count, const double *partials, EvalOut *out,
+                         hipStream_t stream);
+hipError_t launch_reduce_done(const GroupDesc *groups, int count, const double *partials, EvalOut *out, unsigned int *counter,
+                              int *host_flag, int seq, hipStream_t stream);
+hipError_t launch_eval_fold(int dtype, int ppt, int nt, const ProblemDesc *probs, int nterms, int chunk, int max_chunks,
+                            int xcd_remap, const PoseState *poses, double *partials, int buffer_loads, int img32, const void *x0,
+                            const void *y0, const void *z0, int n0, const GroupDesc *groups, const double *prev_rows,
+                            EvalOut *prev_out, hipStream_t stream);
+hipError_t launch_reduce_nt(int nt, const GroupDesc *groups, int count, const double *partials, EvalOut *out,
+                            hipStream_t stream);
+hipError_t launch_lm_step(const GroupDesc *groups, int count, const double *partials, PoseState *poses,
+                          LMState *states, LMCold *cold, LMTrace *traces, const LMOptions &opt, int *running_flags,
+                          LMState *host_states, LMTrace *host_traces, const GroupDesc &first, int post_done, hipStream_t stream,
+                          int priors /* the PriorDesc table sits behind `groups` (one per problem) */);
+hipError_t launch_lm_iter(int dtype, int ppt, const ProblemDesc *probs, int count, int chunk, int max_chunks, int xcd_remap,
+                          PoseState *poses, const double *rows_in, double *rows_out, int buffer_loads, int img32,
+                          const void *x0, const void *y0, const void *z0, int n0, const GroupDesc *groups,
+                          const LMState *st_in, LMState *st_out, const LMCold *cold_in, LMCold *cold_out, LMTrace *traces,
+                          const LMOptions &opt, int *progress, LMState *host_states, LMTrace *host_traces,
+                          const GroupDesc &first, int post_done, hipStream_t stream, int priors /* as launch_lm_step */);
+hipError_t launch_pad_image(int dtype, const void *src, int H, int W, void *dst, int pitch, float *dst32, int *inexact,
+                            hipStream_t stream);
+hipError_t launch_make_poses(const double *qt, int n, int count, const ProblemDesc *probs, const GroupDesc *groups,
+                             PoseState *out, hipStream_t stream);
+hipError_t launch_grid_to_image(int dtype, const double *grid, int W, int H, void *dst, int pitch, float *dst32, int *inexact,
+                                hipStream_t stream);
+hipError_t launch_aos_to_soa(int dtype, const double *src, long long n, int stride, void *x, void *y, void *z, hipStream_t stream);
+hipError_t launch_selftest_reduce(const float *in, float *a, float *b, float *c, float *d, double *o32, double *o64,
+                                  hipStream_t stream);
+// ea_kernels_var.hip (the same file under -DEA_TU_VARIANT); tag 1: the launch of ea_batch_eval_poses
+hipError_t launch_eval_fused_var(int tag, int dtype, int ppt, const ProblemDesc *probs, int nterms, int chunk, int max_chunks,
+                                 int xcd_remap, const PoseState *poses, double *partials, int terms_are_groups,
+                                 int buffer_loads, const void *x0, const void *y0, const void *z0, int n0,
+                                 hipStream_t stream);
+hipError_t launch_empty(int grid, int block, hipStream_t stream);
+#ifdef EA_STAMPS
+hipError_t set_stamp_buffer(unsigned long long *buf);
+hipError_t set_lm_stamp_buffer(unsigned long long *buf);
+#endif
+// ea_preprocess.hip
+hipError_t launch_resize_half_bgr8(const uint8_t *src, int H, int W, uint8_t *dst, hipStream_t s);
+hipError_t launch_resize_half_f32(const float *src, int H, int W, float *dst, int nan_to_zero, hipStream_t s);
+hipError_t launch_nan_to_zero(float *img, size_t n, hipStream_t s);
+hipError_t launch_edge_strength(const uint8_t *bgr, int H, int W, uint8_t *gray, uint8_t *lap, hipStream_t s);
+hipError_t launch_threshold_median(const uint8_t *lap, int H, int W, int thr, int median, uint8_t *mask, hipStream_t s);
+hipError_t launch_chamfer(const uint8_t *mask, int H, int W, int *G, int *scratch, int *dist_fix, float *dist_f32,
+                          unsigned int *minmax, hipStream_t s);
+hipError_t launch_canny(const uint8_t *bgr, int H, int W, int low, int high, int l2_bgr, const uint8_t *keep, uint8_t *gray,
+                        int *mag, uint8_t *dir, uint8_t *label, uint8_t *edges, uint8_t *inv, int *changed, int *rounds_out,
+                        hipStream_t s);
+hipError_t launch_edge_scatter_ros(int dtype, const uint8_t *edges, const float *depth, int H, int W, const int *block_offsets,
+                                   double fx, double fy, double cx, double cy, void *X, void *Y, void *Z, int capacity,
+                                   hipStream_t s);
+hipError_t launch_dt_store(int dtype, const int *dist_fix, const float *dist_f32, int H, int W, const unsigned int *minmax,
+                           int normalize, double lo, double hi, void *dst, int pitch, float *plain, float *dst32, hipStream_t s);
+hipError_t launch_gate_by_mask(uint8_t *grad, const uint8_t *mask, int H, int W, hipStream_t s);
+hipError_t launch_edge_count_scan(const uint8_t *lap, const uint16_t *depth, int H, int W, int thr, int *block_counts,
+                                  int *total, hipStream_t s);
+hipError_t launch_edge_scatter(int dtype, const uint8_t *lap, const uint16_t *depth, int H, int W, int thr,
+                               const int *block_offsets, double fx, double fy, double cx, double cy, double z_scaling,
+                               void *X, void *Y, void *Z, int capacity, hipStream_t s);
+}  // namespace ea
+
+// ea_capi.hip, for the library's other translation units (ea_comm.hip): the thread-local error message, a batch's stream,
+// the point-sharded solve in the one-launch-per-iteration form
+extern "C" int ea_internal_fail(int code, const char *msg);
+extern "C" void *ea_internal_batch_stream(ea_batch *b, int *device);
+extern "C" int ea_internal_solve_sharded_rows(ea_problem *p, const ea_options *opt, ea_device_allreduce_fn allreduce,
+                                              int (*agree)(int vals[2], void *user), void *user, double q[4], double t[3],
+                                              ea_summary *summary, int *used);

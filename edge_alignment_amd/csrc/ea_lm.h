@@ -795,7 +795,7 @@ EA_HD inline void lm_advance(LMState *s, LMCold *c, LMTrace *tr, const LMOptions
   lm_prepare_next<STRAT, LITE>(s, c, tr, o, acc, fresh);
 }
 
-// run-time strategy (host shim)
+// run-time strategy (the host-side loops: ea_solve_sharded, tests/lm_host_shim.cpp)
 EA_HD inline void lm_begin_rt(LMState *s, LMCold *c, LMTrace *tr, const LMOptions *o, const double acc[kAccSlots],
                               LMPending *pend) {
   if (o->strategy == 0) lm_begin<0>(s, c, tr, o, acc, pend); else lm_begin<1>(s, c, tr, o, acc, pend);
@@ -803,6 +803,15 @@ EA_HD inline void lm_begin_rt(LMState *s, LMCold *c, LMTrace *tr, const LMOption
 EA_HD inline void lm_advance_rt(LMState *s, LMCold *c, LMTrace *tr, const LMOptions *o, const double acc[kAccSlots],
                                 LMPending *pend) {
   if (o->strategy == 0) lm_advance<0>(s, c, tr, o, acc, pend); else lm_advance<1>(s, c, tr, o, acc, pend);
+}
+
+// One evaluation's sums (at s->x for the first, at s->cand after that) through the state machine: the body of a host-side
+// solve loop `while (s->running)`.  The device kernels interleave the flush with their LDS traffic and spell this out.
+EA_HD inline void lm_feed(LMState *s, LMCold *c, LMTrace *tr, const LMOptions *o, const double acc[kAccSlots]) {
+  LMPending pend;
+  if (s->num_evals == 0) lm_begin_rt(s, c, tr, o, acc, &pend);
+  else lm_advance_rt(s, c, tr, o, acc, &pend);
+  lm_flush(&pend, c, tr, acc);
 }
 
 }  // namespace ea

@@ -31,6 +31,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ea_launch.h"
 #include "ea_types.h"
 
 namespace ea {

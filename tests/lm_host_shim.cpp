@@ -30,10 +30,7 @@ int ea_lm_host_solve(const ea::LMOptions *o, const double q[4], const double t[3
   int guard = o->max_num_iterations + 4;
   while (s.running && guard-- > 0) {
     cb(s.num_evals == 0 ? s.x : s.cand, acc, user);
-    ea::LMPending pend;
-    if (s.num_evals == 0) ea::lm_begin_rt(&s, &c, &tr, o, acc, &pend);
-    else ea::lm_advance_rt(&s, &c, &tr, o, acc, &pend);
-    ea::lm_flush(&pend, &c, &tr, acc);
+    ea::lm_feed(&s, &c, &tr, o, acc);
   }
   std::memcpy(out->x, s.x, sizeof(out->x));
   out->iteration = s.iteration; out->termination = s.termination; out->why = s.why;
