@@ -1245,10 +1245,20 @@ static void host_pose_state(const ea_problem *p, const double *q, const double *
   make_pose_state(x, p->rot_transposed, 1, ps);
 }
 
+// what the batch's build fixed about its evaluation launches; kposes: in the shape of the pose-batched evaluation (kposes_shape)
+static EvalLaunch eval_launch(const ea_batch *b, bool kposes = false) {
+  EvalLaunch s;
+  s.dtype = b->dtype; s.variant = b->any_variant;
+  s.ppt = kposes ? b->kp_ppt : b->ppt; s.nt = kposes ? b->kp_nt : b->nt;
+  s.chunk = kposes ? b->kp_chunk : b->chunk; s.max_chunks = kposes ? b->kp_max_chunks : b->max_chunks;
+  s.xcd_remap = b->xcd_remap; s.lds_bytes = b->lds_bytes; s.wide = b->wide; s.terms_are_groups = b->terms_are_groups;
+  s.buffer_loads = b->buffer_loads; s.img32 = b->img32;
+  s.x0 = b->x0; s.y0 = b->y0; s.z0 = b->z0; s.n0 = b->n0;
+  return s;
+}
+
 static int batch_launch_eval(ea_batch *b, const PoseState *poses = nullptr) {
-  HIPCHK(launch_eval_fused(b->dtype, b->ppt, b->nt, b->any_variant, b->d_probs, b->nterms, b->chunk, b->max_chunks,
-                           b->xcd_remap, poses ? poses : b->d_poses, b->d_partials, b->lds_bytes, b->wide, b->terms_are_groups, b->buffer_loads, b->img32,
-                           b->x0, b->y0, b->z0, b->n0, b->stream));
+  HIPCHK(launch_eval_fused(eval_launch(b), b->d_probs, b->nterms, poses ? poses : b->d_poses, b->d_partials, b->stream));
   return EA_OK;
 }
 
@@ -1507,9 +1517,8 @@ static int enqueue_resident_poses(ea_batch *b, int K, bool folds = true, bool fl
   const int count = (int)b->probs.size(), G = b->kp_G;
   for (int start = 0; start < K; start += G) {
     const int g = std::min(G, K - start);
-    HIPCHK(launch_eval_poses(b->dtype, b->kp_ppt, b->kp_nt, b->any_variant, b->d_kprobs, g * b->nterms, b->kp_chunk, b->kp_max_chunks,
-                             b->xcd_remap, b->d_kposes + (size_t)start * count, b->d_krows, b->lds_bytes, b->wide,
-                             b->terms_are_groups, b->buffer_loads, b->img32, b->x0, b->y0, b->z0, b->n0, b->stream));
+    HIPCHK(launch_eval_poses(eval_launch(b, /*kposes=*/true), b->d_kprobs, g * b->nterms, b->d_kposes + (size_t)start * count,
+                             b->d_krows, b->stream));
     if (!folds) continue;
     if (flag_last && start + g >= K) HIPCHK(launch_last_fold(b, b->d_kgroups, g * count, b->d_krows, b->dv_kout + (size_t)start * count));
     else HIPCHK(launch_reduce(b->d_kgroups, g * count, b->d_krows, b->dv_kout + (size_t)start * count, b->stream));
@@ -1718,6 +1727,16 @@ static int solve_start(SolveRun &r, const ea_options &o, const LMOptions &lo, co
   return EA_OK;
 }
 
+// the batch's LM state for a launch of the step / iteration kernel: `first` = the row range problem 0 folds
+static LMLaunch lm_launch(const ea_batch *b, const LMOptions &lo, const GroupDesc &first, int post_done) {
+  LMLaunch lm;
+  lm.poses = b->d_poses; lm.states = b->d_states; lm.cold = b->d_cold; lm.traces = b->d_traces;
+  lm.opt = &lo; lm.progress = b->d_progress;
+  lm.host_states = b->dv_states; lm.host_traces = b->dv_traces;  // (final delivery into pinned host memory)
+  lm.first = first; lm.post_done = post_done; lm.priors = b->any_prior;
+  return lm;
+}
+
 // One launch of ea_lm_iter_kernel: launch j = enq + 1 steps on what launch j - 1 left in the buffers of parity (j - 1) and
 // evaluates into those of parity j (launch 0 is a plain evaluation into parity 0, the caller's).  `count` problems fold
 // the rows of `fold`; *evaluated (nullable): the rows this launch writes.
@@ -1728,9 +1747,9 @@ static int solve_launch_iter(SolveRun &r, const LMOptions &lo, int count, const 
   LMCold *cold[2] = {b->d_cold, reinterpret_cast<LMCold *>(b->d_iter_alt + (size_t)b->iter_alt_count * sizeof(LMState))};
   double *rows[2] = {b->d_partials, b->d_partials_alt};
   const int in = r.enq & 1, out = in ^ 1;
-  HIPCHK(launch_lm_iter(b->dtype, b->ppt, b->d_probs, count, b->chunk, b->max_chunks, b->xcd_remap, b->d_poses, rows[in], rows[out],
-                        b->buffer_loads, b->img32, b->x0, b->y0, b->z0, b->n0, b->d_groups, st[in], st[out], cold[in], cold[out],
-                        b->d_traces, lo, b->d_progress, b->dv_states, b->dv_traces, fold, post_done, b->stream, b->any_prior));
+  LMIterPairs io;
+  io.rows_in = rows[in]; io.rows_out = rows[out]; io.st_in = st[in]; io.st_out = st[out]; io.cold_in = cold[in]; io.cold_out = cold[out];
+  HIPCHK(launch_lm_iter(eval_launch(b), b->d_probs, count, b->d_groups, lm_launch(b, lo, fold, post_done), io, b->stream));
   if (evaluated) *evaluated = rows[out];
   return EA_OK;
 }
@@ -1759,8 +1778,7 @@ static int solve_pump(SolveRun &r, const LMOptions &lo) {
     } else {
       int rc = batch_launch_eval(b);
       if (rc != EA_OK) return rc;
-      HIPCHK(launch_lm_step(b->d_groups, count, b->d_partials, b->d_poses, b->d_states, b->d_cold, b->d_traces, lo,
-                            b->d_progress, b->dv_states, b->dv_traces, b->group0, 0, b->stream, b->any_prior));
+      HIPCHK(launch_lm_step(b->d_groups, count, b->d_partials, lm_launch(b, lo, b->group0, /*post_done=*/0), b->stream));
     }
     ++r.enq;
     r.spins = 0;
@@ -2098,9 +2116,9 @@ static hipError_t enqueue_riding_steps(ea_batch *b, int steps) {
       if (lr != EA_OK) e = hipErrorUnknown;
     } else {
       const int prev = (i - 1) & 1;
-      e = launch_eval_fold(b->dtype, b->ppt, b->nt, b->d_probs, b->nterms, b->chunk, b->max_chunks, b->xcd_remap, b->d_poses,
-                           rows, b->buffer_loads, b->img32, b->x0, b->y0, b->z0, b->n0, b->d_groups,
-                           b->d_bench_rows + row_doubles * (size_t)prev, b->d_bench_out + (size_t)count * (size_t)prev, b->stream);
+      RidingFold fold;
+      fold.groups = b->d_groups; fold.prev_rows = b->d_bench_rows + row_doubles * (size_t)prev; fold.prev_out = b->d_bench_out + (size_t)count * (size_t)prev;
+      e = launch_eval_fold(eval_launch(b), b->d_probs, b->nterms, b->d_poses, rows, fold, b->stream);
     }
   }
   if (e == hipSuccess)
@@ -2325,8 +2343,11 @@ static int check_device_pointer(const ea_batch *b, const void *ptr, const char *
 }
 
 static int rows_launch(ea_batch *b, int corrected, int layout, int staged, int nontemporal, void *r_dev, void *J_dev) {
-  HIPCHK(launch_eval_rows(b->dtype, b->any_variant, b->buffer_loads, b->img32, layout, staged, b->d_probs, b->nterms, b->max_n, b->d_poses,
-                          corrected ? 1 : 0, nontemporal, b->total_rows, r_dev, J_dev, b->d_rows_invalid, b->stream));
+  RowsLaunch s;
+  s.dtype = b->dtype; s.variant = b->any_variant; s.buffer_loads = b->buffer_loads; s.img32 = b->img32;
+  s.layout = layout; s.staged = staged; s.corrected = corrected ? 1 : 0; s.nontemporal = nontemporal;
+  s.max_n = b->max_n; s.total_rows = b->total_rows;
+  HIPCHK(launch_eval_rows(s, b->d_probs, b->nterms, b->d_poses, r_dev, J_dev, b->d_rows_invalid, b->stream));
   return EA_OK;
 }
 
@@ -2615,9 +2636,7 @@ static int batch_covariance(ea_batch *b, const double *q, const double *t, const
     }
   }
   if ((rc = batch_upload_poses(b, q, t)) != EA_OK) return rc;
-  HIPCHK(launch_eval_fused(b->dtype, b->ppt, b->nt, b->any_variant, probs, b->nterms, b->chunk, b->max_chunks, b->xcd_remap, b->d_poses,
-                           b->d_partials, b->lds_bytes, b->wide, b->terms_are_groups, b->buffer_loads, b->img32, b->x0, b->y0, b->z0,
-                           b->n0, b->stream));
+  HIPCHK(launch_eval_fused(eval_launch(b), probs, b->nterms, b->d_poses, b->d_partials, b->stream));
   HIPCHK(launch_reduce(b->d_groups, count, b->d_partials, b->d_out, b->stream));
   const CovOptions co = {o->algorithm, o->min_reciprocal_condition_number, o->null_space_rank};
   b->done_seq = b->done_seq == 0x7fffffff ? 1 : b->done_seq + 1;
@@ -2828,8 +2847,7 @@ extern "C" int ea_solve_sharded_device(ea_problem *p, const ea_options *opt_in, 
       b->needs_drain = true;
       return fail(EA_ERR_STATE, "the all-reduce callback reported a failure");
     }
-    HIPCHK(launch_lm_step(b->d_one_row, 1, device_sums, b->d_poses, b->d_states, b->d_cold, b->d_traces, lo, b->d_progress,
-                          b->dv_states, b->dv_traces, GroupDesc{0, 1, 0, 1}, /*post_done=*/1, b->stream, b->any_prior));
+    HIPCHK(launch_lm_step(b->d_one_row, 1, device_sums, lm_launch(b, lo, GroupDesc{0, 1, 0, 1}, /*post_done=*/1), b->stream));
     return EA_OK;
   };
   bool finished;

@@ -1115,12 +1115,6 @@ __global__ __launch_bounds__(NT) void ea_eval_poses_kernel(
   eval_fused_body<T, PPT, MODE, NT, VAR, BUF, IMG32>(x0, y0, z0, n0, shape, chunks_per_xcd, probs, poses, partials, lds_texels);
 }
 
-typedef void (*EvalKernelFn)(const void *, const void *, const void *, int, int, int, const ProblemDesc *, const PoseState *, double *, int);
-template <int TAG, typename T, int PPT, int MODE, int NT, bool VAR, bool BUF, bool IMG32>
-struct EvalKernel { static constexpr EvalKernelFn fn = &ea_eval_fused_kernel<T, PPT, MODE, NT, VAR, BUF, IMG32>; };
-template <typename T, int PPT, int MODE, int NT, bool VAR, bool BUF, bool IMG32>
-struct EvalKernel<1, T, PPT, MODE, NT, VAR, BUF, IMG32> { static constexpr EvalKernelFn fn = &ea_eval_poses_kernel<T, PPT, MODE, NT, VAR, BUF, IMG32>; };
-
 #ifndef EA_TU_VARIANT
 // ------------------------------------------------------------------------------------------------
 // per-point outputs (parity / "EAResidue batch Evaluate" view): r[n], J[n*6]
@@ -2081,170 +2075,133 @@ __global__ __launch_bounds__(256) void ea_aos_to_soa_kernel(const double *__rest
 // ------------------------------------------------------------------------------------------------
 // launchers (declared in ea_launch.h, called from ea_capi.hip)
 
+// A run-time value becomes a template argument through these three: f is a generic lambda that receives the value as a
+// std::integral_constant (spelled decltype(V)::value inside it) or, for the element type, a TypeTag.  A value outside a
+// dispatch_int list is refused: nothing is rounded to a neighbouring kernel.  Which combinations a kernel template is
+// compiled for is stated once per launcher, by an `if constexpr` in front of its one hipLaunchKernelGGL.
+template <typename T> struct TypeTag { typedef T type; };
+template <typename F> static inline hipError_t dispatch_bool(int v, F &&f) { return v ? f(std::true_type{}) : f(std::false_type{}); }
+template <int... Vs, typename F> static inline hipError_t dispatch_int(int v, F &&f) {
+  hipError_t e = hipErrorInvalidValue;
+  (void)((v == Vs ? (e = f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+  return e;
+}
+template <typename F> static inline hipError_t dispatch_dtype(int dtype, F &&f) {
+  return dtype == 1 ? f(TypeTag<float>{}) : f(TypeTag<double>{});
+}
+
+// grid, the packed `shape` word, the LDS tile and the dynamic LDS size of a launch of the fused family: `chunks` workgroups
+// per term in x (rounded to the 8 XCDs under xcd_remap), one term per y
+struct FusedGrid { dim3 grid; int chunks_per_xcd, shape, lds_texels; size_t shmem; };
+static hipError_t fused_grid(const EvalLaunch &s, int nterms, int chunks, FusedGrid *g) {
+  if (s.chunk <= 0 || s.chunk > 0xffff) return hipErrorInvalidValue;  // (NT * PPT <= 4096)
+  g->chunks_per_xcd = (chunks + 7) / 8;
+  g->grid = dim3(s.xcd_remap ? g->chunks_per_xcd * 8 : chunks, nterms);
+  g->shape = s.chunk | ((s.xcd_remap ? 1 : 0) << 16) | ((s.terms_are_groups ? 1 : 0) << 17);
+  const int esz = s.dtype == 1 ? 4 : 8;
+  g->lds_texels = s.lds_bytes > 0 ? s.lds_bytes / esz : 0;
+  g->shmem = (size_t)kHdrBytes + (size_t)g->lds_texels * esz;
+  return hipSuccess;
+}
+
+// The launch shapes the evaluation kernels are compiled for, shared by the fused, fold and iteration launchers: fp32 takes
+// 1, 2 or 4 points per lane at either workgroup size; fp64 (over either image type) has no PPT = 4 and runs 1024-thread
+// workgroups at one point per lane only (128-VGPR budget)
+template <typename T, int PPT, int NT> constexpr bool shape_exists() {
+  return sizeof(T) == 4 || PPT == 1 || (PPT == 2 && NT == 256);
+}
+
 // The fused evaluation lives in two translation units: this file as it is (plain functor, every launch shape) and the
 // same file compiled with -DEA_TU_VARIANT through ea_kernels_var.hip (the distortion / second-camera functors only).
 // They differ in ONE compiler setting: the plain kernels are scheduled for instruction-level parallelism
 // (-mllvm -amdgpu-sched-strategy=max-ilp: -2 .. -4 % kernel time), which costs the variant kernels a wave of occupancy in
 // fp64 (123 -> 136 VGPRs) and 4-7 % of their time -- they keep the default strategy (build.py; profiles/LOG.md section 5b).
-#define EA_LAUNCH_B(T, P, L, N, V, B)                                                              \
-  hipLaunchKernelGGL((EvalKernel<TAG, T, P, L, N, V, B, false>::fn), grid, dim3(N), shmem, stream, x0, y0, z0, n0, shape, \
-                     chunks_per_xcd, probs, poses, partials, lds_texels)
-#define EA_LAUNCH(T, P, L, N, V)                                                                   \
-  do {                                                                                             \
-    if (buffer_loads && (L) == 0) EA_LAUNCH_B(T, P, 0, N, V, true); else EA_LAUNCH_B(T, P, L, N, V, false); \
-  } while (0)
-#define EA_LAUNCH_PROLOGUE                                                                          \
-  if (nterms <= 0 || max_chunks <= 0) return hipSuccess;                                            \
-  const int chunks_per_xcd = (max_chunks + 7) / 8;                                                  \
-  const dim3 grid(xcd_remap ? chunks_per_xcd * 8 : max_chunks, nterms);                             \
-  if (chunk <= 0 || chunk > 0xffff) return hipErrorInvalidValue; /* (NT * PPT <= 4096) */           \
-  const int shape = chunk | ((xcd_remap ? 1 : 0) << 16) | ((terms_are_groups ? 1 : 0) << 17);       \
-  const int esz = dtype == 1 ? 4 : 8;                                                               \
-  const int lds_texels = lds_bytes > 0 ? lds_bytes / esz : 0;                                       \
-  const size_t shmem = (size_t)kHdrBytes + (size_t)lds_texels * esz;
+// kVarTU decides which half a translation unit compiles: fused_exists() below, and the #ifdef around the launchers.
+#ifdef EA_TU_VARIANT
+constexpr bool kVarTU = true;
+#else
+constexpr bool kVarTU = false;
+#endif
+// MODE 0: stencil rows from L2, 1: the footprint staged through LDS (flat addressing only), 2: fp32 with fp64 sums from the
+// lane's sum on (no staging).  The fp32 mirror (IMG32) is fp64 arithmetic on the L2 path.  The variant functors: 256-thread
+// workgroups, L2 path, 1-2 points per lane.
+template <typename T, int PPT, int MODE, int NT, bool VAR, bool BUF, bool IMG32> constexpr bool fused_exists() {
+  if (VAR != kVarTU || !shape_exists<T, PPT, NT>()) return false;
+  if (VAR) return NT == 256 && PPT <= 2 && MODE == 0 && !IMG32;
+  if (IMG32) return sizeof(T) == 8 && MODE == 0;
+  return MODE == 0 || (MODE == 1 && !BUF) || (MODE == 2 && sizeof(T) == 4);
+}
+
+// tag 0: ea_eval_fused_kernel, tag 1: the same kernel under the name ea_eval_poses_kernel (the launches of ea_batch_eval_poses)
+static hipError_t launch_fused_family(int tag, const EvalLaunch &s, const ProblemDesc *probs, int nterms, const PoseState *poses,
+                                      double *partials, hipStream_t stream) {
+  if (nterms <= 0 || s.max_chunks <= 0) return hipSuccess;
+  FusedGrid g;
+  if (hipError_t e = fused_grid(s, nterms, s.max_chunks, &g)) return e;
+  const int mode = g.lds_texels > 0 ? 1 : s.wide ? 2 : 0;
+  return dispatch_bool(tag, [&](auto TAG) { return dispatch_dtype(s.dtype, [&](auto TT) {
+    return dispatch_int<1, 2, 4>(s.ppt, [&](auto PPT) { return dispatch_int<256, 1024>(s.nt, [&](auto NT) {
+      return dispatch_int<0, 1, 2>(mode, [&](auto MODE) { return dispatch_bool(s.buffer_loads && mode != 1, [&](auto BUF) {
+        return dispatch_bool(s.img32, [&](auto IMG32) {
+          typedef typename decltype(TT)::type T;
+          constexpr int P = decltype(PPT)::value, M = decltype(MODE)::value, N = decltype(NT)::value;
+          constexpr bool B = decltype(BUF)::value, I = decltype(IMG32)::value;
+          if constexpr (!fused_exists<T, P, M, N, kVarTU, B, I>()) return hipErrorInvalidValue;
+          else {
+            constexpr auto kernel = decltype(TAG)::value ? &ea_eval_poses_kernel<T, P, M, N, kVarTU, B, I>
+                                                         : &ea_eval_fused_kernel<T, P, M, N, kVarTU, B, I>;
+            hipLaunchKernelGGL(kernel, g.grid, dim3(N), g.shmem, stream, s.x0, s.y0, s.z0, s.n0, g.shape, g.chunks_per_xcd, probs,
+                               poses, partials, g.lds_texels);
+            return hipGetLastError();
+          }
+        }); }); });
+    }); }); }); });
+}
 
 #ifdef EA_TU_VARIANT
-// distortion / second-camera terms: 256-thread workgroups, L2 path, 1-2 points per lane
-template <int TAG>
-static hipError_t launch_eval_fused_var_t(int dtype, int ppt, const ProblemDesc *probs, int nterms, int chunk, int max_chunks,
-                                          int xcd_remap, const PoseState *poses, double *partials, int terms_are_groups,
-                                          int buffer_loads, const void *x0, const void *y0, const void *z0, int n0,
-                                          hipStream_t stream) {
-  const int lds_bytes = 0;
-  EA_LAUNCH_PROLOGUE
-  if (dtype == 1) { if (ppt == 1) EA_LAUNCH(float, 1, 0, 256, true); else EA_LAUNCH(float, 2, 0, 256, true); }
-  else { if (ppt == 1) EA_LAUNCH(double, 1, 0, 256, true); else EA_LAUNCH(double, 2, 0, 256, true); }
-  return hipGetLastError();
-}
-// tag 1: the launch of ea_batch_eval_poses (kernel name ea_eval_poses_kernel)
-hipError_t launch_eval_fused_var(int tag, int dtype, int ppt, const ProblemDesc *probs, int nterms, int chunk, int max_chunks,
-                                 int xcd_remap, const PoseState *poses, double *partials, int terms_are_groups,
-                                 int buffer_loads, const void *x0, const void *y0, const void *z0, int n0,
-                                 hipStream_t stream) {
-  return tag ? launch_eval_fused_var_t<1>(dtype, ppt, probs, nterms, chunk, max_chunks, xcd_remap, poses, partials, terms_are_groups,
-                                          buffer_loads, x0, y0, z0, n0, stream)
-             : launch_eval_fused_var_t<0>(dtype, ppt, probs, nterms, chunk, max_chunks, xcd_remap, poses, partials, terms_are_groups,
-                                          buffer_loads, x0, y0, z0, n0, stream);
+hipError_t launch_eval_fused_var(int tag, const EvalLaunch &s, const ProblemDesc *probs, int nterms, const PoseState *poses,
+                                 double *partials, hipStream_t stream) {
+  return launch_fused_family(tag, s, probs, nterms, poses, partials, stream);
 }
 #else
-template <int TAG>
-static hipError_t launch_eval_fused_t(int dtype, int ppt, int nt, int variant, const ProblemDesc *probs, int nterms, int chunk,
-                                      int max_chunks, int xcd_remap, const PoseState *poses, double *partials,
-                                      int lds_bytes, int wide, int terms_are_groups, int buffer_loads, int img32, const void *x0, const void *y0,
-                                      const void *z0, int n0, hipStream_t stream) {
-  if (variant)
-    return launch_eval_fused_var(TAG, dtype, ppt, probs, nterms, chunk, max_chunks, xcd_remap, poses, partials, terms_are_groups,
-                                 buffer_loads, x0, y0, z0, n0, stream);
-  EA_LAUNCH_PROLOGUE
-  if (img32) {
-    // fp64 arithmetic over the fp32-stored image (every term has ProblemDesc::dt32): the L2 path only
-    if (dtype != 0 || lds_texels > 0) return hipErrorInvalidValue;
-#define EA_LAUNCH_I(P, N)                                                                                              \
-  do {                                                                                                                 \
-    if (buffer_loads)                                                                                                  \
-      hipLaunchKernelGGL((EvalKernel<TAG, double, P, 0, N, false, true, true>::fn), grid, dim3(N), shmem, stream, x0, y0, z0, n0, shape, \
-                         chunks_per_xcd, probs, poses, partials, lds_texels);                                          \
-    else                                                                                                               \
-      hipLaunchKernelGGL((EvalKernel<TAG, double, P, 0, N, false, false, true>::fn), grid, dim3(N), shmem, stream, x0, y0, z0, n0, shape, \
-                         chunks_per_xcd, probs, poses, partials, lds_texels);                                          \
-  } while (0)
-    if (nt == 1024) EA_LAUNCH_I(1, 1024);
-    else if (ppt == 1) EA_LAUNCH_I(1, 256);
-    else EA_LAUNCH_I(2, 256);
-#undef EA_LAUNCH_I
-    return hipGetLastError();
-  }
-#define EA_LAUNCH_L(T, P, N)                                                          \
-  do {                                                                                \
-    if (lds_texels > 0) EA_LAUNCH(T, P, 1, N, false); else EA_LAUNCH(T, P, 0, N, false); \
-  } while (0)
-  if (dtype == 1 && wide && lds_texels == 0) {
-    // fp64 sums from the lane's sum on (MODE 2; ea_batch_set_tuning "wide_accumulate")
-#define EA_LAUNCH_W(P, N) do { if (buffer_loads) EA_LAUNCH_B(float, P, 2, N, false, true); else EA_LAUNCH_B(float, P, 2, N, false, false); } while (0)
-    if (nt == 1024) { if (ppt == 1) EA_LAUNCH_W(1, 1024); else if (ppt == 2) EA_LAUNCH_W(2, 1024); else EA_LAUNCH_W(4, 1024); }
-    else if (ppt == 1) EA_LAUNCH_W(1, 256);
-    else if (ppt == 2) EA_LAUNCH_W(2, 256);
-    else EA_LAUNCH_W(4, 256);
-#undef EA_LAUNCH_W
-  } else if (dtype == 1) {
-    if (nt == 1024) { if (ppt == 1) EA_LAUNCH_L(float, 1, 1024); else if (ppt == 2) EA_LAUNCH_L(float, 2, 1024); else EA_LAUNCH_L(float, 4, 1024); }
-    else if (ppt == 1) EA_LAUNCH_L(float, 1, 256);
-    else if (ppt == 2) EA_LAUNCH_L(float, 2, 256);
-    else EA_LAUNCH_L(float, 4, 256);
-  } else {
-    if (nt == 1024) EA_LAUNCH_L(double, 1, 1024);
-    else if (ppt == 1) EA_LAUNCH_L(double, 1, 256);
-    else EA_LAUNCH_L(double, 2, 256);
-  }
-#undef EA_LAUNCH_L
-  return hipGetLastError();
+hipError_t launch_eval_fused(const EvalLaunch &s, const ProblemDesc *probs, int nterms, const PoseState *poses, double *partials,
+                             hipStream_t stream) {
+  return s.variant ? launch_eval_fused_var(0, s, probs, nterms, poses, partials, stream)
+                   : launch_fused_family(0, s, probs, nterms, poses, partials, stream);
+}
+hipError_t launch_eval_poses(const EvalLaunch &s, const ProblemDesc *probs, int nterms, const PoseState *poses, double *partials,
+                             hipStream_t stream) {
+  return s.variant ? launch_eval_fused_var(1, s, probs, nterms, poses, partials, stream)
+                   : launch_fused_family(1, s, probs, nterms, poses, partials, stream);
 }
 
-hipError_t launch_eval_fused(int dtype, int ppt, int nt, int variant, const ProblemDesc *probs, int nterms, int chunk,
-                             int max_chunks, int xcd_remap, const PoseState *poses, double *partials,
-                             int lds_bytes, int wide, int terms_are_groups, int buffer_loads, int img32, const void *x0, const void *y0,
-                             const void *z0, int n0, hipStream_t stream) {
-  return launch_eval_fused_t<0>(dtype, ppt, nt, variant, probs, nterms, chunk, max_chunks, xcd_remap, poses, partials, lds_bytes, wide,
-                                terms_are_groups, buffer_loads, img32, x0, y0, z0, n0, stream);
-}
-// the same launch under the kernel name ea_eval_poses_kernel: G poses x terms in grid y (ea_batch_eval_poses)
-hipError_t launch_eval_poses(int dtype, int ppt, int nt, int variant, const ProblemDesc *probs, int nterms, int chunk,
-                             int max_chunks, int xcd_remap, const PoseState *poses, double *partials,
-                             int lds_bytes, int wide, int terms_are_groups, int buffer_loads, int img32, const void *x0, const void *y0,
-                             const void *z0, int n0, hipStream_t stream) {
-  return launch_eval_fused_t<1>(dtype, ppt, nt, variant, probs, nterms, chunk, max_chunks, xcd_remap, poses, partials, lds_bytes, wide,
-                                terms_are_groups, buffer_loads, img32, x0, y0, z0, n0, stream);
-}
-
-// evaluation into `partials` + the fold of `prev_rows` -> `prev_out` in one launch (ea_eval_fold_kernel)
-hipError_t launch_eval_fold(int dtype, int ppt, int nt, const ProblemDesc *probs, int nterms, int chunk, int max_chunks,
-                            int xcd_remap, const PoseState *poses, double *partials, int buffer_loads, int img32, const void *x0,
-                            const void *y0, const void *z0, int n0, const GroupDesc *groups, const double *prev_rows,
-                            EvalOut *prev_out, hipStream_t stream) {
-  const int lds_bytes = 0, terms_are_groups = 1;
+// evaluation into `partials` + the fold of fold.prev_rows -> fold.prev_out in one launch (ea_eval_fold_kernel): plain
+// single-family problems on the L2 path
+hipError_t launch_eval_fold(const EvalLaunch &s, const ProblemDesc *probs, int nterms, const PoseState *poses, double *partials,
+                            const RidingFold &fold, hipStream_t stream) {
+  if (s.variant || s.lds_bytes > 0 || s.wide || !s.terms_are_groups) return hipErrorInvalidValue;
   // a batch without a single point has nothing to evaluate, but the previous step's fold is still owed (its result slot
   // must not keep what an earlier owner of the memory left there): the stand-alone fold in the riders' summation order
-  if (nterms > 0 && max_chunks <= 0) return launch_reduce_nt(nt, groups, nterms, prev_rows, prev_out, stream);
-  EA_LAUNCH_PROLOGUE
-  const dim3 grid_f(grid.x + 1, grid.y);
-  if (img32) {
-    if (dtype != 0) return hipErrorInvalidValue;
-#define EA_LAUNCH_FI(P, N)                                                                                            \
-  do {                                                                                                                \
-    if (buffer_loads)                                                                                                 \
-      hipLaunchKernelGGL((ea_eval_fold_kernel<double, P, N, true, true>), grid_f, dim3(N), shmem, stream, x0, y0, z0, n0, shape,  \
-                         chunks_per_xcd, probs, poses, partials, lds_texels, groups, prev_rows, prev_out);            \
-    else                                                                                                              \
-      hipLaunchKernelGGL((ea_eval_fold_kernel<double, P, N, false, true>), grid_f, dim3(N), shmem, stream, x0, y0, z0, n0, shape, \
-                         chunks_per_xcd, probs, poses, partials, lds_texels, groups, prev_rows, prev_out);            \
-  } while (0)
-    if (nt == 1024) EA_LAUNCH_FI(1, 1024);
-    else if (ppt == 1) EA_LAUNCH_FI(1, 256);
-    else EA_LAUNCH_FI(2, 256);
-#undef EA_LAUNCH_FI
-    return hipGetLastError();
-  }
-#define EA_LAUNCH_F(T, P, N)                                                                                          \
-  do {                                                                                                                \
-    if (buffer_loads)                                                                                                 \
-      hipLaunchKernelGGL((ea_eval_fold_kernel<T, P, N, true>), grid_f, dim3(N), shmem, stream, x0, y0, z0, n0, shape,  \
-                         chunks_per_xcd, probs, poses, partials, lds_texels, groups, prev_rows, prev_out);            \
-    else                                                                                                              \
-      hipLaunchKernelGGL((ea_eval_fold_kernel<T, P, N, false>), grid_f, dim3(N), shmem, stream, x0, y0, z0, n0, shape, \
-                         chunks_per_xcd, probs, poses, partials, lds_texels, groups, prev_rows, prev_out);            \
-  } while (0)
-  if (dtype == 1) {
-    if (nt == 1024) { if (ppt == 1) EA_LAUNCH_F(float, 1, 1024); else if (ppt == 2) EA_LAUNCH_F(float, 2, 1024); else EA_LAUNCH_F(float, 4, 1024); }
-    else if (ppt == 1) EA_LAUNCH_F(float, 1, 256);
-    else if (ppt == 2) EA_LAUNCH_F(float, 2, 256);
-    else EA_LAUNCH_F(float, 4, 256);
-  } else {
-    if (nt == 1024) EA_LAUNCH_F(double, 1, 1024);
-    else if (ppt == 1) EA_LAUNCH_F(double, 1, 256);
-    else EA_LAUNCH_F(double, 2, 256);
-  }
-#undef EA_LAUNCH_F
-  return hipGetLastError();
+  if (nterms > 0 && s.max_chunks <= 0) return launch_reduce_nt(s.nt, fold.groups, nterms, fold.prev_rows, fold.prev_out, stream);
+  if (nterms <= 0) return hipSuccess;
+  FusedGrid g;
+  if (hipError_t e = fused_grid(s, nterms, s.max_chunks, &g)) return e;
+  const dim3 grid_f(g.grid.x + 1, g.grid.y);  // (the fold workgroup: behind the evaluation's, after the rounding to the XCDs)
+  return dispatch_dtype(s.dtype, [&](auto TT) { return dispatch_int<1, 2, 4>(s.ppt, [&](auto PPT) {
+    return dispatch_int<256, 1024>(s.nt, [&](auto NT) { return dispatch_bool(s.buffer_loads, [&](auto BUF) {
+      return dispatch_bool(s.img32, [&](auto IMG32) {
+        typedef typename decltype(TT)::type T;
+        constexpr int P = decltype(PPT)::value, N = decltype(NT)::value;
+        constexpr bool I = decltype(IMG32)::value;
+        if constexpr (!shape_exists<T, P, N>() || (I && sizeof(T) != 8)) return hipErrorInvalidValue;
+        else {
+          hipLaunchKernelGGL((ea_eval_fold_kernel<T, P, N, decltype(BUF)::value, I>), grid_f, dim3(N), g.shmem, stream, s.x0, s.y0,
+                             s.z0, s.n0, g.shape, g.chunks_per_xcd, probs, poses, partials, g.lds_texels, fold.groups,
+                             fold.prev_rows, fold.prev_out);
+          return hipGetLastError();
+        }
+      }); }); });
+  }); });
 }
 
 // the stand-alone fold in the order the riding folds of an nt-thread evaluation use
@@ -2260,71 +2217,47 @@ hipError_t launch_eval_points(int dtype, const ProblemDesc *probs, int problem, 
                               double *r_out, double *J_out, int corrected, hipStream_t stream) {
   if (n <= 0) return hipSuccess;
   const int grid = (n + kBlockThreads - 1) / kBlockThreads;
-  if (dtype == 1)
-    hipLaunchKernelGGL((ea_eval_points_kernel<float>), dim3(grid), dim3(kBlockThreads), 0, stream, probs, problem,
-                       poses, r_out, J_out, corrected);
-  else
-    hipLaunchKernelGGL((ea_eval_points_kernel<double>), dim3(grid), dim3(kBlockThreads), 0, stream, probs, problem,
-                       poses, r_out, J_out, corrected);
-  return hipGetLastError();
+  return dispatch_dtype(dtype, [&](auto TT) {
+    hipLaunchKernelGGL((ea_eval_points_kernel<typename decltype(TT)::type>), dim3(grid), dim3(kBlockThreads), 0, stream, probs,
+                       problem, poses, r_out, J_out, corrected);
+    return hipGetLastError();
+  });
 }
 
-// materialised mode: rows of every term of the batch into the caller's device arrays (ea_eval_rows_kernel)
-hipError_t launch_eval_rows(int dtype, int variant, int buffer_loads, int img32, int layout, int staged, const ProblemDesc *probs, int nterms,
-                            long long max_n, const PoseState *poses, int corrected, int nontemporal, long long total_rows,
-                            void *r_out, void *J_out, unsigned int *n_invalid, hipStream_t stream) {
-  if (nterms <= 0 || max_n <= 0) return hipSuccess;
-  const int chunks = (int)((max_n + kBlockThreads - 1) / kBlockThreads);
+// materialised mode: rows of every term of the batch into the caller's device arrays (ea_eval_rows_kernel).  The distortion /
+// second-camera terms address flat; the column-major layout has no staged form; the fp32 mirror is fp64 over plain terms.
+hipError_t launch_eval_rows(const RowsLaunch &s, const ProblemDesc *probs, int nterms, const PoseState *poses, void *r_out,
+                            void *J_out, unsigned int *n_invalid, hipStream_t stream) {
+  if (nterms <= 0 || s.max_n <= 0) return hipSuccess;
+  const int chunks = (int)((s.max_n + kBlockThreads - 1) / kBlockThreads);
   const int chunks_per_xcd = (chunks + 7) / 8;
   const dim3 grid(chunks_per_xcd * 8, nterms);
-#define EA_ROWS(T, V, B, L, S)                                                                                              \
-  hipLaunchKernelGGL((ea_eval_rows_kernel<T, V, B, L, S>), grid, dim3(kBlockThreads), 0, stream, probs, poses, chunks_per_xcd, \
-                     corrected, nontemporal, total_rows, static_cast<T *>(r_out), static_cast<T *>(J_out), n_invalid)
-#define EA_ROWS_L(T, V, B)                                                                    \
-  do {                                                                                        \
-    if (layout == 1) EA_ROWS(T, V, B, 1, false);                                              \
-    else if (staged) EA_ROWS(T, V, B, 0, true);                                               \
-    else EA_ROWS(T, V, B, 0, false);                                                          \
-  } while (0)
-  if (img32) {  // fp64 rows over the fp32-stored image
-    if (dtype != 0 || variant) return hipErrorInvalidValue;
-#define EA_ROWS_I(B)                                                                                                            \
-  do {                                                                                                                          \
-    if (layout == 1)                                                                                                            \
-      hipLaunchKernelGGL((ea_eval_rows_kernel<double, false, B, 1, false, true>), grid, dim3(kBlockThreads), 0, stream, probs, poses, chunks_per_xcd, \
-                         corrected, nontemporal, total_rows, static_cast<double *>(r_out), static_cast<double *>(J_out), n_invalid); \
-    else if (staged)                                                                                                            \
-      hipLaunchKernelGGL((ea_eval_rows_kernel<double, false, B, 0, true, true>), grid, dim3(kBlockThreads), 0, stream, probs, poses, chunks_per_xcd, \
-                         corrected, nontemporal, total_rows, static_cast<double *>(r_out), static_cast<double *>(J_out), n_invalid); \
-    else                                                                                                                        \
-      hipLaunchKernelGGL((ea_eval_rows_kernel<double, false, B, 0, false, true>), grid, dim3(kBlockThreads), 0, stream, probs, poses, chunks_per_xcd, \
-                         corrected, nontemporal, total_rows, static_cast<double *>(r_out), static_cast<double *>(J_out), n_invalid); \
-  } while (0)
-    if (buffer_loads) EA_ROWS_I(true); else EA_ROWS_I(false);
-#undef EA_ROWS_I
-  } else if (variant) {  // distortion / second-camera terms: flat addressing
-    if (dtype == 1) EA_ROWS_L(float, true, false); else EA_ROWS_L(double, true, false);
-  } else if (buffer_loads) {
-    if (dtype == 1) EA_ROWS_L(float, false, true); else EA_ROWS_L(double, false, true);
-  } else {
-    if (dtype == 1) EA_ROWS_L(float, false, false); else EA_ROWS_L(double, false, false);
-  }
-#undef EA_ROWS_L
-#undef EA_ROWS
-  return hipGetLastError();
+  return dispatch_dtype(s.dtype, [&](auto TT) { return dispatch_bool(s.variant, [&](auto VAR) {
+    return dispatch_bool(s.buffer_loads && !s.variant, [&](auto BUF) { return dispatch_int<0, 1>(s.layout, [&](auto LAYOUT) {
+      return dispatch_bool(s.staged && s.layout == 0, [&](auto STAGED) { return dispatch_bool(s.img32, [&](auto IMG32) {
+        typedef typename decltype(TT)::type T;
+        constexpr bool V = decltype(VAR)::value, B = decltype(BUF)::value, S = decltype(STAGED)::value, I = decltype(IMG32)::value;
+        constexpr int L = decltype(LAYOUT)::value;
+        if constexpr ((V && B) || (L == 1 && S) || (I && (sizeof(T) != 8 || V))) return hipErrorInvalidValue;
+        else {
+          hipLaunchKernelGGL((ea_eval_rows_kernel<T, V, B, L, S, I>), grid, dim3(kBlockThreads), 0, stream, probs, poses,
+                             chunks_per_xcd, s.corrected, s.nontemporal, s.total_rows, static_cast<T *>(r_out),
+                             static_cast<T *>(J_out), n_invalid);
+          return hipGetLastError();
+        }
+      }); }); });
+    }); }); });
 }
 
 hipError_t launch_pixel_cost(int dtype, const ProblemDesc *probs, int problem, int n, const PoseState *poses, void *partials,
                              hipStream_t stream) {
   if (n <= 0) return hipSuccess;
   const int grid = (n + kBlockThreads - 1) / kBlockThreads;
-  if (dtype == 1)
-    hipLaunchKernelGGL((ea_pixel_cost_kernel<float>), dim3(grid), dim3(kBlockThreads), 0, stream, probs, problem, poses,
-                       static_cast<PixelCostPartial *>(partials));
-  else
-    hipLaunchKernelGGL((ea_pixel_cost_kernel<double>), dim3(grid), dim3(kBlockThreads), 0, stream, probs, problem, poses,
-                       static_cast<PixelCostPartial *>(partials));
-  return hipGetLastError();
+  return dispatch_dtype(dtype, [&](auto TT) {
+    hipLaunchKernelGGL((ea_pixel_cost_kernel<typename decltype(TT)::type>), dim3(grid), dim3(kBlockThreads), 0, stream, probs,
+                       problem, poses, static_cast<PixelCostPartial *>(partials));
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_reduce(const GroupDesc *groups, int count, const double *partials, EvalOut *out,
@@ -2341,58 +2274,42 @@ hipError_t launch_reduce_done(const GroupDesc *groups, int count, const double *
   return hipGetLastError();
 }
 
-hipError_t launch_lm_step(const GroupDesc *groups, int count, const double *partials, PoseState *poses,
-                          LMState *states, LMCold *cold, LMTrace *traces, const LMOptions &opt, int *progress,
-                          LMState *host_states, LMTrace *host_traces, const GroupDesc &first, int post_done, hipStream_t stream,
-                          int priors) {
-#define EA_STEP(S, P)                                                                                                            \
-  hipLaunchKernelGGL((ea_lm_step_kernel<S, P>), dim3(count), dim3(kLmThreads), 0, stream, groups, partials, poses, states, cold, \
-                     traces, opt, progress, host_states, host_traces, first, post_done)
+hipError_t launch_lm_step(const GroupDesc *groups, int count, const double *partials, const LMLaunch &lm, hipStream_t stream) {
   if (count <= 0) return hipSuccess;
-  if (opt.strategy == 0) {
-    if (priors) EA_STEP(0, true); else EA_STEP(0, false);
-  } else {
-    if (priors) EA_STEP(1, true); else EA_STEP(1, false);
-  }
-#undef EA_STEP
-  return hipGetLastError();
+  return dispatch_bool(lm.opt->strategy != 0, [&](auto STRAT) { return dispatch_bool(lm.priors, [&](auto PRIOR) {
+    hipLaunchKernelGGL((ea_lm_step_kernel<decltype(STRAT)::value ? 1 : 0, decltype(PRIOR)::value>), dim3(count), dim3(kLmThreads), 0,
+                       stream, groups, partials, lm.poses, lm.states, lm.cold, lm.traces, *lm.opt, lm.progress, lm.host_states,
+                       lm.host_traces, lm.first, lm.post_done);
+    return hipGetLastError();
+  }); });
 }
 
 // ea_lm_iter_kernel: launch j of a solve reads what launch j - 1 wrote (state, cold system, rows) and writes the other
-// buffer of each pair.  The grid is one workgroup larger than the evaluation's (the writer), rounded to the 8 XCDs.
-hipError_t launch_lm_iter(int dtype, int ppt, const ProblemDesc *probs, int count, int chunk, int max_chunks, int xcd_remap,
-                          PoseState *poses, const double *rows_in, double *rows_out, int buffer_loads, int img32,
-                          const void *x0, const void *y0, const void *z0, int n0, const GroupDesc *groups,
-                          const LMState *st_in, LMState *st_out, const LMCold *cold_in, LMCold *cold_out, LMTrace *traces,
-                          const LMOptions &opt, int *progress, LMState *host_states, LMTrace *host_traces,
-                          const GroupDesc &first, int post_done, hipStream_t stream, int priors) {
+// buffer of each pair.  One plain residual family per problem in 256-thread workgroups on the L2 path; no fp32 x IMG32.
+hipError_t launch_lm_iter(const EvalLaunch &s, const ProblemDesc *probs, int count, const GroupDesc *groups, const LMLaunch &lm,
+                          const LMIterPairs &io, hipStream_t stream) {
   if (count <= 0) return hipSuccess;
-  if (chunk <= 0 || chunk > 0xffff || chunk != kLmThreads * ppt) return hipErrorInvalidValue;
-  const int chunks_per_xcd = (max_chunks + 1 + 7) / 8;
-  const dim3 grid(xcd_remap ? chunks_per_xcd * 8 : max_chunks + 1, count);
-  const int shape = chunk | ((xcd_remap ? 1 : 0) << 16) | (1 << 17);
-  const size_t shmem = (size_t)kHdrBytes;
-#define EA_ITER_SP(T, P, B, I, S, R)                                                                                       \
-  hipLaunchKernelGGL((ea_lm_iter_kernel<T, P, B, I, S, R>), grid, dim3(kLmThreads), shmem, stream, x0, y0, z0, n0, shape,  \
-                     chunks_per_xcd, rows_in, first.tile_begin, first.tile_end, probs, poses, rows_out, groups, st_in, st_out, \
-                     cold_in, cold_out, traces, opt, progress, host_states, host_traces, post_done)
-#define EA_ITER_S(T, P, B, I, S) do { if (priors) EA_ITER_SP(T, P, B, I, S, true); else EA_ITER_SP(T, P, B, I, S, false); } while (0)
-#define EA_ITER(T, P, B, I) do { if (opt.strategy == 0) EA_ITER_S(T, P, B, I, 0); else EA_ITER_S(T, P, B, I, 1); } while (0)
-#define EA_ITER_B(T, P, I) do { if (buffer_loads) EA_ITER(T, P, true, I); else EA_ITER(T, P, false, I); } while (0)
-  if (dtype == 1) {
-    if (img32) return hipErrorInvalidValue;
-    if (ppt == 1) EA_ITER_B(float, 1, false); else if (ppt == 2) EA_ITER_B(float, 2, false); else if (ppt == 4) EA_ITER_B(float, 4, false);
-    else return hipErrorInvalidValue;
-  } else if (img32) {
-    if (ppt == 1) EA_ITER_B(double, 1, true); else if (ppt == 2) EA_ITER_B(double, 2, true); else return hipErrorInvalidValue;
-  } else {
-    if (ppt == 1) EA_ITER_B(double, 1, false); else if (ppt == 2) EA_ITER_B(double, 2, false); else return hipErrorInvalidValue;
-  }
-#undef EA_ITER_B
-#undef EA_ITER
-#undef EA_ITER_S
-#undef EA_ITER_SP
-  return hipGetLastError();
+  if (s.variant || s.lds_bytes > 0 || s.wide || !s.terms_are_groups || s.nt != kLmThreads || s.chunk != kLmThreads * s.ppt)
+    return hipErrorInvalidValue;
+  FusedGrid g;
+  // the grid is one workgroup wider than the evaluation's (the writer), THEN rounded to the 8 XCDs
+  if (hipError_t e = fused_grid(s, count, s.max_chunks + 1, &g)) return e;
+  return dispatch_dtype(s.dtype, [&](auto TT) { return dispatch_int<1, 2, 4>(s.ppt, [&](auto PPT) {
+    return dispatch_bool(s.buffer_loads, [&](auto BUF) { return dispatch_bool(s.img32, [&](auto IMG32) {
+      return dispatch_bool(lm.opt->strategy != 0, [&](auto STRAT) { return dispatch_bool(lm.priors, [&](auto PRIOR) {
+        typedef typename decltype(TT)::type T;
+        constexpr int P = decltype(PPT)::value;
+        constexpr bool I = decltype(IMG32)::value;
+        if constexpr (!shape_exists<T, P, kLmThreads>() || (I && sizeof(T) != 8)) return hipErrorInvalidValue;
+        else {
+          hipLaunchKernelGGL((ea_lm_iter_kernel<T, P, decltype(BUF)::value, I, decltype(STRAT)::value ? 1 : 0, decltype(PRIOR)::value>),
+                             g.grid, dim3(kLmThreads), g.shmem, stream, s.x0, s.y0, s.z0, s.n0, g.shape, g.chunks_per_xcd, io.rows_in,
+                             lm.first.tile_begin, lm.first.tile_end, probs, lm.poses, io.rows_out, groups, io.st_in, io.st_out,
+                             io.cold_in, io.cold_out, lm.traces, *lm.opt, lm.progress, lm.host_states, lm.host_traces, lm.post_done);
+          return hipGetLastError();
+        }
+      }); }); });
+    }); }); });
 }
 
 #ifdef EA_STAMPS
@@ -2446,8 +2363,5 @@ hipError_t launch_grid_to_image(int dtype, const double *grid, int W, int H, voi
 }
 
 #endif  // EA_TU_VARIANT
-#undef EA_LAUNCH_PROLOGUE
-#undef EA_LAUNCH
-#undef EA_LAUNCH_B
 
 }  // namespace ea

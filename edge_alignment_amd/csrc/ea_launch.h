@@ -2,6 +2,8 @@
 // launchers of ea_kernels.hip / ea_kernels_var.hip / ea_preprocess.hip and the functions ea_capi.hip keeps for ea_comm.hip.
 // The defining files include it too: an extern "C" definition that drifts from its declaration here does not compile (a
 // hand-copied prototype in the caller would have linked and passed garbage); a drifted launcher fails to link, as before.
+// What a launcher takes is a struct filled by name plus what varies per call: no list of look-alike ints in which two swapped
+// arguments would still compile.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -12,42 +14,74 @@
 #include "ea_types.h"
 
 namespace ea {
+// What is fixed about the launches of the fused evaluation family (ea_eval_fused / _poses / _fold / ea_lm_iter kernels) once
+// a batch is built: the launch shape and the preloaded arguments.  Filled by name (ea_capi.hip: eval_launch); the launchers
+// refuse a (dtype, ppt, nt, ...) combination no kernel is compiled for with hipErrorInvalidValue.
+struct EvalLaunch {
+  int dtype = 0;             // EA_F64 / EA_F32
+  int ppt = 1, nt = 256;     // points per lane {1, 2, 4}, workgroup size {256, 1024}
+  int variant = 0;           // distortion / second-camera terms (the kernels of ea_kernels_var.hip)
+  int chunk = 256;           // points per workgroup = nt * ppt
+  int max_chunks = 0;        // workgroups of the widest term
+  int xcd_remap = 1;
+  int lds_bytes = 0;         // > 0: the DT footprint is staged through LDS (MODE 1)
+  int wide = 0;              // fp32 sums in fp64 from the lane's sum on (MODE 2)
+  int terms_are_groups = 1;  // one term per problem
+  int buffer_loads = 0;      // raw-buffer addressing of image and points
+  int img32 = 0;             // fp64 arithmetic over the fp32 mirror of the image
+  const void *x0 = nullptr, *y0 = nullptr, *z0 = nullptr;  // problem 0's points and their count
+  int n0 = 0;
+};
+// the fold that rides in an evaluation's launch: the previous step's rows into its result slots
+struct RidingFold { const GroupDesc *groups; const double *prev_rows; EvalOut *prev_out; };
+// the LM state an ea_lm_step_kernel / ea_lm_iter_kernel launch works on; `priors`: the PriorDesc table sits behind the
+// launch's `groups` (one per problem)
+struct LMLaunch {
+  PoseState *poses; LMState *states; LMCold *cold; LMTrace *traces;
+  const LMOptions *opt;
+  int *progress;
+  LMState *host_states; LMTrace *host_traces;
+  GroupDesc first;
+  int post_done, priors;
+};
+// what ea_lm_iter_kernel adds: launch j reads what launch j - 1 wrote and writes the other buffer of each pair (the `out`
+// buffers take the place of LMLaunch::states / cold, which the launcher does not read)
+struct LMIterPairs {
+  const double *rows_in; double *rows_out;
+  const LMState *st_in; LMState *st_out;
+  const LMCold *cold_in; LMCold *cold_out;
+};
+struct RowsLaunch {
+  int dtype = 0, variant = 0, buffer_loads = 0, img32 = 0;
+  int layout = 0;   // 0 = J row-major [rows][6], 1 = column-major [6][rows]
+  int staged = 0;   // (layout 0 only)
+  int corrected = 0, nontemporal = 0;
+  long long max_n = 0, total_rows = 0;
+};
+
 // ea_kernels.hip
-hipError_t launch_eval_fused(int dtype, int ppt, int nt, int variant, const ProblemDesc *probs, int nterms, int chunk,
-                             int max_chunks, int xcd_remap, const PoseState *poses, double *partials,
-                             int lds_bytes, int wide, int terms_are_groups, int buffer_loads, int img32, const void *x0, const void *y0,
-                             const void *z0, int n0, hipStream_t stream);
-hipError_t launch_eval_poses(int dtype, int ppt, int nt, int variant, const ProblemDesc *probs, int nterms, int chunk,
-                             int max_chunks, int xcd_remap, const PoseState *poses, double *partials,
-                             int lds_bytes, int wide, int terms_are_groups, int buffer_loads, int img32, const void *x0, const void *y0,
-                             const void *z0, int n0, hipStream_t stream);
+hipError_t launch_eval_fused(const EvalLaunch &s, const ProblemDesc *probs, int nterms, const PoseState *poses, double *partials,
+                             hipStream_t stream);
+// the same launch under the kernel name ea_eval_poses_kernel: G poses x terms in grid y (ea_batch_eval_poses)
+hipError_t launch_eval_poses(const EvalLaunch &s, const ProblemDesc *probs, int nterms, const PoseState *poses, double *partials,
+                             hipStream_t stream);
 hipError_t launch_pixel_cost(int dtype, const ProblemDesc *probs, int problem, int n, const PoseState *poses, void *partials,
                              hipStream_t stream);
-hipError_t launch_eval_rows(int dtype, int variant, int buffer_loads, int img32, int layout, int staged, const ProblemDesc *probs, int nterms,
-                            long long max_n, const PoseState *poses, int corrected, int nontemporal, long long total_rows,
-                            void *r_out, void *J_out, unsigned int *n_invalid, hipStream_t stream);
+hipError_t launch_eval_rows(const RowsLaunch &s, const ProblemDesc *probs, int nterms, const PoseState *poses, void *r_out,
+                            void *J_out, unsigned int *n_invalid, hipStream_t stream);
 hipError_t launch_eval_points(int dtype, const ProblemDesc *probs, int problem, int n, const PoseState *poses,
                               double *r_out, double *J_out, int corrected, hipStream_t stream);
 hipError_t launch_reduce(const GroupDesc *groups, int count, const double *partials, EvalOut *out,
                          hipStream_t stream);
 hipError_t launch_reduce_done(const GroupDesc *groups, int count, const double *partials, EvalOut *out, unsigned int *counter,
                               int *host_flag, int seq, hipStream_t stream);
-hipError_t launch_eval_fold(int dtype, int ppt, int nt, const ProblemDesc *probs, int nterms, int chunk, int max_chunks,
-                            int xcd_remap, const PoseState *poses, double *partials, int buffer_loads, int img32, const void *x0,
-                            const void *y0, const void *z0, int n0, const GroupDesc *groups, const double *prev_rows,
-                            EvalOut *prev_out, hipStream_t stream);
+hipError_t launch_eval_fold(const EvalLaunch &s, const ProblemDesc *probs, int nterms, const PoseState *poses, double *partials,
+                            const RidingFold &fold, hipStream_t stream);
 hipError_t launch_reduce_nt(int nt, const GroupDesc *groups, int count, const double *partials, EvalOut *out,
                             hipStream_t stream);
-hipError_t launch_lm_step(const GroupDesc *groups, int count, const double *partials, PoseState *poses,
-                          LMState *states, LMCold *cold, LMTrace *traces, const LMOptions &opt, int *running_flags,
-                          LMState *host_states, LMTrace *host_traces, const GroupDesc &first, int post_done, hipStream_t stream,
-                          int priors /* the PriorDesc table sits behind `groups` (one per problem) */);
-hipError_t launch_lm_iter(int dtype, int ppt, const ProblemDesc *probs, int count, int chunk, int max_chunks, int xcd_remap,
-                          PoseState *poses, const double *rows_in, double *rows_out, int buffer_loads, int img32,
-                          const void *x0, const void *y0, const void *z0, int n0, const GroupDesc *groups,
-                          const LMState *st_in, LMState *st_out, const LMCold *cold_in, LMCold *cold_out, LMTrace *traces,
-                          const LMOptions &opt, int *progress, LMState *host_states, LMTrace *host_traces,
-                          const GroupDesc &first, int post_done, hipStream_t stream, int priors /* as launch_lm_step */);
+hipError_t launch_lm_step(const GroupDesc *groups, int count, const double *partials, const LMLaunch &lm, hipStream_t stream);
+hipError_t launch_lm_iter(const EvalLaunch &s, const ProblemDesc *probs, int count, const GroupDesc *groups, const LMLaunch &lm,
+                          const LMIterPairs &io, hipStream_t stream);
 hipError_t launch_pad_image(int dtype, const void *src, int H, int W, void *dst, int pitch, float *dst32, int *inexact,
                             hipStream_t stream);
 hipError_t launch_make_poses(const double *qt, int n, int count, const ProblemDesc *probs, const GroupDesc *groups,
@@ -57,11 +91,10 @@ hipError_t launch_grid_to_image(int dtype, const double *grid, int W, int H, voi
 hipError_t launch_aos_to_soa(int dtype, const double *src, long long n, int stride, void *x, void *y, void *z, hipStream_t stream);
 hipError_t launch_selftest_reduce(const float *in, float *a, float *b, float *c, float *d, double *o32, double *o64,
                                   hipStream_t stream);
-// ea_kernels_var.hip (the same file under -DEA_TU_VARIANT); tag 1: the launch of ea_batch_eval_poses
-hipError_t launch_eval_fused_var(int tag, int dtype, int ppt, const ProblemDesc *probs, int nterms, int chunk, int max_chunks,
-                                 int xcd_remap, const PoseState *poses, double *partials, int terms_are_groups,
-                                 int buffer_loads, const void *x0, const void *y0, const void *z0, int n0,
-                                 hipStream_t stream);
+// ea_kernels_var.hip (the same file under -DEA_TU_VARIANT): what launch_eval_fused (tag 0) / launch_eval_poses (tag 1) hand on
+// when s.variant is set
+hipError_t launch_eval_fused_var(int tag, const EvalLaunch &s, const ProblemDesc *probs, int nterms, const PoseState *poses,
+                                 double *partials, hipStream_t stream);
 hipError_t launch_empty(int grid, int block, hipStream_t stream);
 #ifdef EA_STAMPS
 hipError_t set_stamp_buffer(unsigned long long *buf);
