@@ -43,6 +43,7 @@ EXPORTED = [
     "ea_problem_set_distortion", "ea_problem_set_second_camera", "ea_problem_add_term", "ea_problem_clear_terms",
     "ea_default_covariance_options", "ea_problem_covariance", "ea_batch_covariance", "ea_tracker_set_covariance",
     "ea_tracker_last_covariance", "ea_problem_set_normal_prior", "ea_tracker_set_motion_prior",
+    "ea_problem_set_constant_parameters", "ea_problem_get_constant_parameters",
 ]
 
 # measurement hooks (edge_alignment_amd/csrc/ea_hip_dev.h): bound by bench.py, the A/B scripts and the tests that pin the
@@ -231,6 +232,8 @@ def load():
     L.ea_tracker_last_covariance.argtypes = [vp, covp]
     L.ea_problem_set_normal_prior.argtypes = [vp, C.c_int, dp, C.c_int, dp]
     L.ea_tracker_set_motion_prior.argtypes = [vp, C.c_double, C.c_double]
+    L.ea_problem_set_constant_parameters.argtypes = [vp, C.POINTER(C.c_int)]
+    L.ea_problem_get_constant_parameters.argtypes = [vp, C.POINTER(C.c_int)]
     _lib = L
     return L
 
@@ -648,6 +651,25 @@ class Problem:
         """drops the prior on block 0 (q) or 1 (t)"""
         _check(load().ea_problem_set_normal_prior(self._h, int(block), None, 0, None))
 
+    def set_constant_parameters(self, mask):
+        """holds tangent coordinates constant, mask[6] in [delta0 delta1 delta2 | tx ty tz] order, non-zero = held; None = all
+        variable (ea_problem_set_constant_parameters)"""
+        _check(load().ea_problem_set_constant_parameters(self._h, _constant_mask(mask)))
+
+    def get_constant_parameters(self):
+        m = (C.c_int * 6)()
+        _check(load().ea_problem_get_constant_parameters(self._h, m))
+        return [int(v) for v in m]
+
+
+def _constant_mask(mask):
+    if mask is None:
+        return None
+    mask = [int(bool(v)) for v in mask]
+    if len(mask) != 6:
+        raise ValueError("the constant-parameter mask has 6 entries [delta0 delta1 delta2 | tx ty tz] (got %d)" % len(mask))
+    return (C.c_int * 6)(*mask)
+
 
 class Tracker:
     """frame-to-frame driver: push_frame aligns the previous frame's edge points against the new frame"""
@@ -680,6 +702,11 @@ class Tracker:
     def set_motion_prior(self, sigma_rot, sigma_trans):
         """NormalPriors centred on each solve's start pose, A = I / sigma (ea_tracker_set_motion_prior); 0 = block off"""
         _check(load().ea_tracker_set_motion_prior(self._h, float(sigma_rot), float(sigma_trans)))
+
+    def set_constant_parameters(self, mask):
+        """the mask of ea_problem_set_constant_parameters on the tracker's problem: it holds for every push"""
+        L = load()
+        _check(L.ea_problem_set_constant_parameters(L.ea_tracker_problem(self._h), _constant_mask(mask)))
 
     def last_covariance(self):
         """the covariance of the last push (covariance_to_dict); EAError(EA_ERR_STATE) when it did not align"""

@@ -269,6 +269,7 @@ struct ea_problem {
   std::vector<ea_problem *> terms;       // further residual families sharing this problem's pose
   PriorDesc prior = {};                  // NormalPriors on q / t (ea_problem_set_normal_prior; ea_prior.h)
   int term_of = 0;                       // how many problems hold this one as a term (a term carries no prior)
+  int held = 0;                          // tangent coordinates held constant, bit i of [delta | t] (ea_problem_set_constant_parameters)
   int64_t n = 0;
   void *d_x = nullptr, *d_y = nullptr, *d_z = nullptr;
   bool own_points = false;
@@ -413,13 +414,17 @@ struct ea_batch {
   ProblemDesc *d_cprobs = nullptr;
   int cdesc_cap = 0;
   ea_covariance *h_cov = nullptr, *dv_cov = nullptr;
-  // NormalPriors: one PriorDesc per problem right behind the groups in d_desc_block (where the PRIOR instantiations of the LM
-  // kernels look for them), uploaded with them when any problem has one; any_prior = 0: the prior-free instantiations run and
+  // NormalPriors: one PriorDesc per problem right behind the groups in d_desc_block (where the SIDE instantiations of the LM
+  // kernels look for them), uploaded with them when any problem has one or holds tangent coordinates constant (PriorDesc::held
+  // rides the same table, and the same instantiations apply the mask); any_side = 0: the prior-free instantiations run and
   // d_priors is NULL.  The host copy serves the results folded into host memory and the host-side state machine of
   // ea_solve_sharded.
+  // (any_side / d_priors / h_priors: "side table" = whatever rides beside the groups; PriorDesc is its record and also
+  // carries the mask -- held is kept twice on purpose: LMState::held is what the solve kernels read with the state they
+  // fetch anyway, PriorDesc::held what ea_cov_kernel, which has no LMState, reads)
   PriorDesc *d_priors = nullptr;
   std::vector<PriorDesc> h_priors;
-  int any_prior = 0;
+  int any_side = 0;
 };
 
 static int check_device(int device) {
@@ -643,6 +648,8 @@ extern "C" int ea_problem_add_term(ea_problem *p, ea_problem *term) {
   if (std::find(p->terms.begin(), p->terms.end(), term) != p->terms.end()) return fail(EA_ERR_INVALID_ARG, "term already added");
   if (term->prior.has_q || term->prior.has_t)
     return fail(EA_ERR_INVALID_ARG, "a problem with a normal prior cannot be a term (the prior belongs on the head problem)");
+  if (term->held)
+    return fail(EA_ERR_INVALID_ARG, "a problem with constant parameters cannot be a term (the mask belongs on the head problem)");
   p->terms.push_back(term);
   term->term_of++;
   p->version++;
@@ -691,6 +698,25 @@ extern "C" int ea_problem_set_normal_prior(ea_problem *p, int block, const doubl
     pr.has_t = clear ? 0 : 1;
   }
   p->version++;
+  return EA_OK;
+}
+
+// Problem::SetParameterBlockConstant / SubsetParameterization: the tangent coordinates a solve does not move and the
+// covariance leaves out, in the solver's ordering [delta0 delta1 delta2 | tx ty tz].  Kept on the head problem like the prior.
+extern "C" int ea_problem_set_constant_parameters(ea_problem *p, const int tangent_constant[6]) {
+  if (!p) return fail(EA_ERR_INVALID_ARG, "NULL problem");
+  if (p->term_of > 0) return fail(EA_ERR_INVALID_ARG, "a problem that is a term cannot carry constant parameters");
+  int held = 0;
+  if (tangent_constant)
+    for (int i = 0; i < 6; ++i) held |= tangent_constant[i] ? 1 << i : 0;
+  p->held = held;
+  p->version++;
+  return EA_OK;
+}
+
+extern "C" int ea_problem_get_constant_parameters(const ea_problem *p, int tangent_constant[6]) {
+  if (!p || !tangent_constant) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  for (int i = 0; i < 6; ++i) tangent_constant[i] = (p->held >> i) & 1;
   return EA_OK;
 }
 
@@ -1179,13 +1205,14 @@ static int batch_build(ea_batch *b) {
   b->d_probs = reinterpret_cast<ProblemDesc *>(b->d_desc_block);
   b->d_groups = reinterpret_cast<GroupDesc *>(b->d_desc_block + (size_t)b->nterms * sizeof(ProblemDesc));
   b->h_priors.resize(b->probs.size());
-  b->any_prior = 0;
+  b->any_side = 0;
   for (size_t i = 0; i < b->probs.size(); ++i) {
     b->h_priors[i] = b->probs[i]->prior;
-    b->any_prior |= (b->h_priors[i].has_q || b->h_priors[i].has_t) ? 1 : 0;
+    b->h_priors[i].held = b->probs[i]->held;  // (the table's other passenger: constant tangent coordinates)
+    b->any_side |= (b->h_priors[i].has_q || b->h_priors[i].has_t || b->h_priors[i].held) ? 1 : 0;
   }
   static_assert(sizeof(GroupDesc) % alignof(PriorDesc) == 0, "the priors sit right behind the groups");
-  b->d_priors = b->any_prior ? reinterpret_cast<PriorDesc *>(b->d_groups + b->probs.size()) : nullptr;
+  b->d_priors = b->any_side ? reinterpret_cast<PriorDesc *>(b->d_groups + b->probs.size()) : nullptr;
   if (b->t_test_fail_build) {  // (tests/test_gpu_robustness.py: a build that fails here must leave the batch dirty)
     b->t_test_fail_build = 0;
     return fail(EA_ERR_ALLOC, "batch build: injected allocation failure (test hook)");
@@ -1201,7 +1228,7 @@ static int batch_build(ea_batch *b) {
   }
   {
     const size_t pb = descs.size() * sizeof(ProblemDesc), gb = groups.size() * sizeof(GroupDesc);
-    const size_t rb = b->any_prior ? b->h_priors.size() * sizeof(PriorDesc) : 0;
+    const size_t rb = b->any_side ? b->h_priors.size() * sizeof(PriorDesc) : 0;
     if (!b->desc_done) HIPCHK(hipEventCreateWithFlags(&b->desc_done, hipEventDisableTiming));
     else HIPCHK(hipEventSynchronize(b->desc_done));  // the staging block is free again (it always is by now)
     if (b->h_desc_cap < pb + gb + rb) {
@@ -1335,7 +1362,7 @@ static int wait_results(ea_batch *b) {
 // result j belonging to problem j % count, its pose at qt(j) = 7 doubles q | t).  The fold kernels stay as they are.
 template <typename PoseFn>
 static void add_priors_host(const ea_batch *b, EvalOut *out, size_t n, PoseFn qt) {
-  if (!b->any_prior) return;
+  if (!b->any_side) return;
   const size_t count = b->probs.size();
   for (size_t j = 0; j < n; ++j) {
     const PriorDesc &pr = b->h_priors[j % count];
@@ -1686,7 +1713,7 @@ static int solve_start(SolveRun &r, const ea_options &o, const LMOptions &lo, co
   if (rc != EA_OK) return rc;
   const int count = r.count = (int)b->probs.size();
   for (int i = 0; i < count; ++i) {
-    lm_init(&b->h_states[i], &lo, q + 4 * i, t + 3 * i, b->probs[i]->rot_transposed);
+    lm_init(&b->h_states[i], &lo, q + 4 * i, t + 3 * i, b->probs[i]->rot_transposed, b->probs[i]->held);
     host_pose_state(b->probs[i], q + 4 * i, t + 3 * i, &b->h_poses[i]);
     b->h_progress[i] = 1;          // running
     b->h_progress[count + i] = 0;  // evaluations whose step kernel has started
@@ -1733,7 +1760,7 @@ static LMLaunch lm_launch(const ea_batch *b, const LMOptions &lo, const GroupDes
   lm.poses = b->d_poses; lm.states = b->d_states; lm.cold = b->d_cold; lm.traces = b->d_traces;
   lm.opt = &lo; lm.progress = b->d_progress;
   lm.host_states = b->dv_states; lm.host_traces = b->dv_traces;  // (final delivery into pinned host memory)
-  lm.first = first; lm.post_done = post_done; lm.priors = b->any_prior;
+  lm.first = first; lm.post_done = post_done; lm.side = b->any_side;
   return lm;
 }
 
@@ -2545,22 +2572,23 @@ extern "C" int ea_cost(ea_problem *p, const double q[4], const double t[3], doub
 // synchronisation.  The covariance is a few thousand flops per problem on one lane: a separate kernel behind the fold costs
 // one launch gap (~1.5 us) and leaves the fold and the solve kernels exactly as they are.  Nothing of the pose-batched
 // path (ea_batch_set_poses) is touched: resident poses survive.
-// PRIOR: the problems' NormalPriors (a table of `count`) enter the system first, at the pose of the evaluation -- as
-// ceres::Covariance counts every residual block; apply_loss_function does not concern them.
-template <bool PRIOR>
+// SIDE: the problems' NormalPriors (a table of `count`) enter the system first, at the pose of the evaluation -- as
+// ceres::Covariance counts every residual block; apply_loss_function does not concern them.  The same table carries the
+// constant tangent coordinates (PriorDesc::held): the covariance is that of the reduced system (ea_cov.h), priors first.
+template <bool SIDE>
 static __global__ __launch_bounds__(64) void ea_cov_kernel(const EvalOut *__restrict__ sums, const PoseState *__restrict__ poses,
                                                            CovOptions o, int count, ea_covariance *__restrict__ out,
                                                            unsigned int *__restrict__ counter, int *__restrict__ host_flag, int seq,
                                                            const PriorDesc *__restrict__ priors) {
   const int i = (int)(blockIdx.x * 64 + threadIdx.x);
-  if constexpr (PRIOR) {
+  if constexpr (SIDE) {
     if (i < count) {
       double acc[kAccSlots], x[7];
       for (int k = 0; k < kAccSlots; ++k) acc[k] = sums[i].acc[k];
       for (int k = 0; k < 4; ++k) x[k] = poses[i].q[k];
       for (int k = 0; k < 3; ++k) x[4 + k] = poses[i].t[k];
       prior_add(priors[i], x, acc);
-      cov_from_acc(acc, poses[i].q, 1, o, &out[i]);
+      cov_from_acc(acc, poses[i].q, 1, o, &out[i], priors[i].held);
     }
   } else {
     if (i < count) cov_from_acc(sums[i].acc, poses[i].q, 1, o, &out[i]);
@@ -2780,7 +2808,7 @@ extern "C" int ea_solve_sharded(ea_problem *p, const ea_options *opt_in, ea_allr
   std::vector<LMTrace> trv(1);
   LMTrace &tr = trv[0];
   std::memset(&tr, 0, sizeof(tr));
-  lm_init(&st, &lo, q, t, p->rot_transposed);
+  lm_init(&st, &lo, q, t, p->rot_transposed, p->held);
   int guard = o.max_num_iterations + 4;
   while (st.running && guard-- > 0) {
     const double *pose = st.num_evals == 0 ? st.x : st.cand;
@@ -2797,8 +2825,9 @@ extern "C" int ea_solve_sharded(ea_problem *p, const ea_options *opt_in, ea_allr
       std::memset(acc, 0, sizeof(acc));
     }
     if (allreduce(acc, kAccSlots, user) != 0) return fail(EA_ERR_STATE, "the all-reduce callback reported a failure");
-    // the prior once, on the reduced sums (every rank holds the same prior and adds the same bits)
-    if (b->any_prior) prior_add(b->h_priors[0], pose, acc);
+    // the prior once, on the reduced sums (every rank holds the same prior and adds the same bits); constant coordinates:
+    // lm_feed masks the system it is given, so the mask too is applied to the all-reduced sums
+    if (b->any_side) prior_add(b->h_priors[0], pose, acc);
     lm_feed(&st, &cold, &tr, &lo, acc);
   }
   if (st.running) return fail(EA_ERR_STATE, "sharded solve did not terminate");
@@ -2837,7 +2866,7 @@ extern "C" int ea_solve_sharded_device(ea_problem *p, const ea_options *opt_in, 
     HIPCHK(hipMalloc(&b->d_one_row, sizeof(GroupDesc) + sizeof(PriorDesc)));  // (+ the prior table of one problem behind it)
     HIPCHK(hipMemcpy(b->d_one_row, &one, sizeof(one), hipMemcpyHostToDevice));
   }
-  if (b->any_prior)  // the step kernel adds the prior once, to the reduced sums: it reads it behind its one-row group table
+  if (b->any_side)  // the step kernel adds the prior once, to the reduced sums: it reads it behind its one-row group table
     HIPCHK(hipMemcpyAsync(b->d_one_row + 1, b->d_priors, sizeof(PriorDesc), hipMemcpyDeviceToDevice, b->stream));
   auto enqueue_iteration = [&]() -> int {
     int rc2 = batch_launch_eval(b);  // (an empty shard launches nothing; its fold below yields zeros)

@@ -49,10 +49,18 @@ EA_HD inline void cov_unpack_jtj(const double *acc, double A[36]) {
 // Symmetric eigen-decomposition by cyclic Jacobi rotations: lam descending, V (row-major) holds the eigenvector of lam[j]
 // in column j.  A rotation is skipped when |a_pq| <= 1e-17 sqrt(|a_pp a_qq|) (the relative criterion that keeps small
 // eigenvalues of a positive definite matrix accurate); the loop ends after a sweep without rotation or kCovSweeps sweeps.
-EA_HD inline void cov_eigh(const double Ain[36], double lam[6], double V[36]) {
+// held (bit i = tangent coordinate i constant): the decomposition of the REDUCED matrix over the free coordinates.  The held
+// rows and columns are exact zeros, so no rotation ever touches them -- the rotations are those of the cyclic Jacobi method on
+// the m x m sub-matrix, in its order -- and their eigenpairs (0, e_i) are sorted behind the m free ones whatever the sign of
+// a free eigenvalue: lam holds the sub-matrix's m eigenvalues, descending, then zeros, and no placeholder takes part in the
+// rank rule.  held = 0 is the code without the parameter.
+EA_HD inline void cov_eigh(const double Ain[36], double lam[6], double V[36], int held = 0) {
   double A[36];
   EA_COV_UNROLL
-  for (int i = 0; i < 36; ++i) { A[i] = Ain[i]; V[i] = (i % 7 == 0) ? 1.0 : 0.0; }
+  for (int i = 0; i < 36; ++i) {
+    A[i] = (((held >> (i / 6)) | (held >> (i % 6))) & 1) ? 0.0 : Ain[i];
+    V[i] = (i % 7 == 0) ? 1.0 : 0.0;
+  }
   for (int sweep = 0; sweep < kCovSweeps; ++sweep) {
     int rotated = 0;
     EA_COV_UNROLL
@@ -93,14 +101,16 @@ EA_HD inline void cov_eigh(const double Ain[36], double lam[6], double V[36]) {
     if (!rotated) break;
   }
   double d[6];
+  bool h[6];  // column j is a held coordinate's (0, e_j)
   EA_COV_UNROLL
-  for (int i = 0; i < 6; ++i) d[i] = A[7 * i];
+  for (int i = 0; i < 6; ++i) { d[i] = A[7 * i]; h[i] = ((held >> i) & 1) != 0; }
   EA_COV_UNROLL
   for (int i = 0; i < 5; ++i)  // bubble network, descending, columns of V along (fixed indices: selects, no scratch)
     EA_COV_UNROLL
     for (int j = 0; j < 5 - i; ++j)
-      if (d[j] < d[j + 1]) {
+      if (h[j] != h[j + 1] ? h[j] : d[j] < d[j + 1]) {
         const double tl = d[j]; d[j] = d[j + 1]; d[j + 1] = tl;
+        const bool th = h[j]; h[j] = h[j + 1]; h[j + 1] = th;
         EA_COV_UNROLL
         for (int k = 0; k < 6; ++k) { const double tv = V[6 * k + j]; V[6 * k + j] = V[6 * k + j + 1]; V[6 * k + j + 1] = tv; }
       }
@@ -113,9 +123,11 @@ EA_HD inline void cov_eigh(const double Ain[36], double lam[6], double V[36]) {
 // and makes the covariance "not computed" otherwise.  SPARSE_QR: the same test with null_space_rank = 0.
 // Returns the number of kept eigenpairs, or -1 for "not computed".  lambda_1 <= 0 (no information at all) is "not
 // computed" unless nothing is to be kept.
-EA_HD inline int cov_rank(const double lam[6], const CovOptions &o) {
+// m: the size of the (reduced) system, lam[0 .. m) its eigenvalues -- max_rank = m - null_space_rank, SPARSE_QR asks for
+// rank m.  m = 0 (every coordinate constant): nothing to compute, rank 0.
+EA_HD inline int cov_rank(const double lam[6], const CovOptions &o, int m = 6) {
   const int nsr = o.algorithm == EA_COV_SPARSE_QR ? 0 : o.null_space_rank;
-  const int max_rank = nsr < 0 ? 6 : 6 - nsr;
+  const int max_rank = nsr < 0 ? m : m - nsr;
   if (max_rank <= 0) return 0;
   if (!(lam[0] > 0.0)) return nsr < 0 ? 0 : -1;
   int rank = 0;
@@ -181,7 +193,11 @@ EA_HD inline void cov_lift(const double q[4], const double C[36], double qq[16],
 // One problem's covariance from its 32 accumulator slots (ea_eval's sums at pose q) into the public result struct.
 // points = rows the evaluation covered (0: "no points", why 3).  The result is built in a local copy and stored once: on
 // the device `out` is pinned host memory, where every read of a field already written would be a round trip over PCIe.
-EA_HD inline void cov_from_acc(const double *acc, const double q[4], int64_t points, const CovOptions &o, ea_covariance *out) {
+// held: the tangent coordinates that are constant (ea_problem_set_constant_parameters) -- decomposition and rank rule run on
+// the reduced system, `tangent` has zero rows and columns there and the ambient blocks are lifted from it (a constant block
+// gives zero blocks); with all six held ok = 1, rank = 0 and everything is zero.
+EA_HD inline void cov_from_acc(const double *acc, const double q[4], int64_t points, const CovOptions &o, ea_covariance *out,
+                               int held = 0) {
   ea_covariance r;
   r.ok = 0; r.why = 0; r.rank = 0;
   r.n_invalid = (int64_t)llround(acc[kAccInvalid]);
@@ -196,8 +212,11 @@ EA_HD inline void cov_from_acc(const double *acc, const double q[4], int64_t poi
   } else {
     double A[36], V[36];
     cov_unpack_jtj(acc, A);
-    cov_eigh(A, r.eigenvalues, V);
-    const int rank = r.n_invalid > 0 ? -2 : cov_rank(r.eigenvalues, o);
+    int m = 6;
+    EA_COV_UNROLL
+    for (int i = 0; i < 6; ++i) m -= (held >> i) & 1;
+    cov_eigh(A, r.eigenvalues, V, held);
+    const int rank = r.n_invalid > 0 ? -2 : cov_rank(r.eigenvalues, o, m);
     if (rank == -2) {
       r.why = 2;  // Ceres fails the Jacobian evaluation
     } else if (rank < 0) {

@@ -1570,15 +1570,20 @@ __global__ __launch_bounds__(NT) void ea_eval_fold_kernel(
   eval_fused_body<T, PPT, 0, NT, false, BUF, IMG32>(x0, y0, z0, n0, shape, chunks_per_xcd, probs, poses, partials, lds_texels);
 }
 
-// PRIOR instantiations of the LM kernels.  Problem p's PriorDesc (ea_prior.h; the table sits behind the group table) is
+// SIDE instantiations of the LM kernels.  Problem p's PriorDesc (ea_prior.h; the table sits behind the group table) is
 // fetched one 8-byte word per lane beside the state words, before the fold (prior_word), and parked in LDS with them
 // (prior_lds) -- its load is not a dependent round trip on the state machine's critical path.  After the barrier lane 0 adds
 // the priors to the folded sums in LDS, at the pose they were evaluated at -- st.x before the first evaluation, st.cand
 // after -- and the workgroup waits for it.  The state machine then reads s_acc exactly as the prior-free instantiation does:
 // its code is the same, so a problem without a prior in a batch with priors takes bit for bit the steps of its own solve.
+// Constant tangent coordinates (ea_problem_set_constant_parameters) ride the same instantiations: a batch with a mask on any
+// problem has the table (a record without priors adds nothing), and behind the priors lane 0 replaces the held rows and columns
+// of the sums by a unit diagonal and the held gradient by zero (lm_mask_system, ea_lm.h; the mask itself travels in
+// LMState::held, where lm_init put it).  The state machine runs with MASK = SIDE: x_norm over the non-constant blocks and
+// the all-held exit; with nothing held it is the arithmetic of the mask-free code, bit for bit.
 constexpr int kPriorWords = (int)(sizeof(PriorDesc) / 8);
 __device__ __forceinline__ PriorDesc &prior_lds() {
-  __shared__ PriorDesc s_prior;  // (only the PRIOR instantiations reference it)
+  __shared__ PriorDesc s_prior;  // (only the SIDE instantiations reference it)
   return s_prior;
 }
 __device__ __forceinline__ double prior_word(const GroupDesc *__restrict__ groups, int nprob, int p, int tid) {
@@ -1590,6 +1595,7 @@ __device__ __forceinline__ void prior_into_lds(const LMState &s_st, double *s_ac
 #pragma unroll
     for (int i = 0; i < kAccSlots; ++i) acc[i] = s_acc[i];
     prior_add(prior_lds(), s_st.num_evals == 0 ? s_st.x : s_st.cand, acc);
+    lm_mask_system(s_st.held, acc);
 #pragma unroll
     for (int i = 0; i < kAccSlots; ++i) s_acc[i] = acc[i];
   }
@@ -1602,10 +1608,10 @@ __device__ __forceinline__ void prior_into_lds(const LMState &s_st, double *s_ac
 // the state words travel while the partial rows are fetched (sixteen 16-byte loads in flight per lane), the
 // host's progress counter is posted before the arithmetic, lane 0 works on a register copy of the
 // state, and the pose's float mirrors / the write-back are lane-parallel.
-// PRIOR: the problems' NormalPriors are added to the folded sums before the state machine reads them (prior_into_lds).  The
+// SIDE: the problems' NormalPriors are added to the folded sums before the state machine reads them (prior_into_lds).  The
 // prior table sits right behind the group table (one PriorDesc per problem: batch_build lays them out so), so no argument is
-// added: the PRIOR = false instantiations are the code this kernel was before priors existed.
-template <int STRAT, bool PRIOR>
+// added: the SIDE = false instantiations are the code this kernel was before priors existed.
+template <int STRAT, bool SIDE>
 __global__ __launch_bounds__(kLmThreads) void ea_lm_step_kernel(
     const GroupDesc *__restrict__ groups, const double *__restrict__ partials,
     PoseState *__restrict__ poses, LMState *__restrict__ states, LMCold *__restrict__ cold,
@@ -1647,7 +1653,7 @@ __global__ __launch_bounds__(kLmThreads) void ea_lm_step_kernel(
   const int evals_before = states[p].num_evals;  // (a register copy: the LDS copy is rewritten by lane 0 below)
   const double state_word = tid < kStateWords ? reinterpret_cast<const double *>(states + p)[tid] : 0.0;
   double pw = 0.0;
-  if constexpr (PRIOR) pw = prior_word(groups, gridDim.x, p, tid);
+  if constexpr (SIDE) pw = prior_word(groups, gridDim.x, p, tid);
   EA_LM_STAMP(1, ev_);
   // The rows are fetched WITHOUT waiting for the running flag: the flag's round trip (0.5 us of the 2.5 us this kernel spends
   // before its first arithmetic, in-kernel stamps) then travels beside the rows' instead of in front of it.  A finished
@@ -1655,11 +1661,11 @@ __global__ __launch_bounds__(kLmThreads) void ea_lm_step_kernel(
   reduce_tiles<kLmThreads, 8>(partials, gd.tile_begin, gd.tile_end, s_part, s_acc);
   if (!running) return;  // uniform
   if (tid < kStateWords) reinterpret_cast<double *>(&s_st)[tid] = state_word;
-  if constexpr (PRIOR) {
+  if constexpr (SIDE) {
     if (tid < kPriorWords) reinterpret_cast<double *>(&prior_lds())[tid] = pw;
   }
   __syncthreads();
-  if constexpr (PRIOR) prior_into_lds(s_st, s_acc, tid);
+  if constexpr (SIDE) prior_into_lds(s_st, s_acc, tid);
   EA_LM_STAMP(2, ev_);
   // the host only uses this counter to decide how far ahead to enqueue: posted by another wavefront before the
   // arithmetic, so the PCIe write is neither the last thing the kernel waits for nor in lane 0's memory counter
@@ -1672,8 +1678,8 @@ __global__ __launch_bounds__(kLmThreads) void ea_lm_step_kernel(
     lm_copy_state(&st, &s_st);
 #pragma unroll
     for (int i = 0; i < kAccSlots; ++i) acc[i] = s_acc[i];
-    if (EA_UNLIKELY(st.num_evals == 0)) lm_begin<STRAT>(&st, cold + p, traces + p, &opt, acc, &pend);
-    else lm_advance<STRAT>(&st, cold + p, traces + p, &opt, acc, &pend);
+    if (EA_UNLIKELY(st.num_evals == 0)) lm_begin<STRAT, false, SIDE>(&st, cold + p, traces + p, &opt, acc, &pend);
+    else lm_advance<STRAT, false, SIDE>(&st, cold + p, traces + p, &opt, acc, &pend);
     EA_LM_STAMP(3, ev_);
     make_pose_core(st.cand, st.rot_transposed, st.running, &s_ps, /*zero_unused_G=*/false);
     lm_copy_state(&s_st, &st);
@@ -1765,9 +1771,9 @@ __global__ __launch_bounds__(kLmThreads) void ea_lm_step_kernel(
 // wavefront, and the state machine works on that copy; the writer stores its copy for the next launch.
 // One plain residual family per problem, 256-thread workgroups, stencil rows from L2; the host only takes this path when the
 // whole grid is resident at once (<= 256 workgroups), see solve_start.
-// PRIOR: as in ea_lm_step_kernel (the prior table behind `groups`): the prior enters the folded sums in LDS once per
+// SIDE: as in ea_lm_step_kernel (the prior table behind `groups`): the prior enters the folded sums in LDS once per
 // workgroup, before the writer's and every evaluating wavefront's state machine read them, so they stay in lockstep.
-template <typename T, int PPT, bool BUF, bool IMG32, int STRAT, bool PRIOR>
+template <typename T, int PPT, bool BUF, bool IMG32, int STRAT, bool SIDE>
 __global__ __launch_bounds__(kLmThreads) void ea_lm_iter_kernel(
     // the 14 preloaded dwords: what problem 0's point loads and ROW loads need -- the fold is the head of every workgroup's
     // dependent chain, and its loads must not wait for a scalar load of the argument segment (tile0_* = problem 0's row range)
@@ -1830,7 +1836,7 @@ __global__ __launch_bounds__(kLmThreads) void ea_lm_iter_kernel(
   const double state_word = tid < kStateWords ? reinterpret_cast<const double *>(st_in + p)[tid] : 0.0;
   const double cold_word = (tid & 63) < kColdWords ? reinterpret_cast<const double *>(cold_in + p)[tid & 63] : 0.0;
   double pw = 0.0;
-  if constexpr (PRIOR) pw = prior_word(groups, gridDim.y, p, tid);
+  if constexpr (SIDE) pw = prior_word(groups, gridDim.y, p, tid);
   // ---- the step, in every workgroup: fold of the previous launch's rows + the state machine on lane 0.
   // The rows are fetched at once, beside the uniforms above and not behind them (as ea_lm_step_kernel does): a launch that
   // finds its problem finished has folded rows nobody reads and leaves below.
@@ -1864,11 +1870,11 @@ __global__ __launch_bounds__(kLmThreads) void ea_lm_iter_kernel(
   }
   if (tid < kStateWords) reinterpret_cast<double *>(&s_st)[tid] = state_word;
   if ((tid & 63) < kColdWords) reinterpret_cast<double *>(&s_cold[tid >> 6])[tid & 63] = cold_word;  // (own wavefront's copy)
-  if constexpr (PRIOR) {
+  if constexpr (SIDE) {
     if (tid < kPriorWords) reinterpret_cast<double *>(&prior_lds())[tid] = pw;
   }
   __syncthreads();
-  if constexpr (PRIOR) prior_into_lds(s_st, s_acc, tid);
+  if constexpr (SIDE) prior_into_lds(s_st, s_acc, tid);
   EA_LM_STAMP_PUT(0, evals_before, t_enter_);
   EA_LM_STAMP(1, evals_before);  // folded
   if (writer) {
@@ -1882,8 +1888,8 @@ __global__ __launch_bounds__(kLmThreads) void ea_lm_iter_kernel(
       lm_copy_state(&st, &s_st);
 #pragma unroll
       for (int i = 0; i < kAccSlots; ++i) acc[i] = s_acc[i];
-      if (EA_UNLIKELY(st.num_evals == 0)) lm_begin<STRAT>(&st, &s_cold[0], traces + p, &opt, acc, &pend);
-      else lm_advance<STRAT>(&st, &s_cold[0], traces + p, &opt, acc, &pend);
+      if (EA_UNLIKELY(st.num_evals == 0)) lm_begin<STRAT, false, SIDE>(&st, &s_cold[0], traces + p, &opt, acc, &pend);
+      else lm_advance<STRAT, false, SIDE>(&st, &s_cold[0], traces + p, &opt, acc, &pend);
       make_pose_core(st.cand, st.rot_transposed, st.running, &s_pose[0], /*zero_unused_G=*/false);
       lm_copy_state(&s_st, &st);
       s_trace_it = pend.trace_it;
@@ -1961,8 +1967,8 @@ __global__ __launch_bounds__(kLmThreads) void ea_lm_iter_kernel(
 #pragma unroll
     for (int i = 0; i < kAccSlots; ++i) acc[i] = s_acc[i];
     LMCold *cold = &s_cold[tid >> 6];
-    if (EA_UNLIKELY(st.num_evals == 0)) lm_begin<STRAT, true>(&st, cold, nullptr, &opt, acc, &pend);
-    else lm_advance<STRAT, true>(&st, cold, nullptr, &opt, acc, &pend);
+    if (EA_UNLIKELY(st.num_evals == 0)) lm_begin<STRAT, true, SIDE>(&st, cold, nullptr, &opt, acc, &pend);
+    else lm_advance<STRAT, true, SIDE>(&st, cold, nullptr, &opt, acc, &pend);
     EA_LM_STAMP(2, evals_before);  // state machine done
     make_pose_core(st.cand, st.rot_transposed, st.running, &s_ps, /*zero_unused_G=*/false);
     running_v = st.running;
@@ -2276,8 +2282,8 @@ hipError_t launch_reduce_done(const GroupDesc *groups, int count, const double *
 
 hipError_t launch_lm_step(const GroupDesc *groups, int count, const double *partials, const LMLaunch &lm, hipStream_t stream) {
   if (count <= 0) return hipSuccess;
-  return dispatch_bool(lm.opt->strategy != 0, [&](auto STRAT) { return dispatch_bool(lm.priors, [&](auto PRIOR) {
-    hipLaunchKernelGGL((ea_lm_step_kernel<decltype(STRAT)::value ? 1 : 0, decltype(PRIOR)::value>), dim3(count), dim3(kLmThreads), 0,
+  return dispatch_bool(lm.opt->strategy != 0, [&](auto STRAT) { return dispatch_bool(lm.side, [&](auto SIDE) {
+    hipLaunchKernelGGL((ea_lm_step_kernel<decltype(STRAT)::value ? 1 : 0, decltype(SIDE)::value>), dim3(count), dim3(kLmThreads), 0,
                        stream, groups, partials, lm.poses, lm.states, lm.cold, lm.traces, *lm.opt, lm.progress, lm.host_states,
                        lm.host_traces, lm.first, lm.post_done);
     return hipGetLastError();
@@ -2296,13 +2302,13 @@ hipError_t launch_lm_iter(const EvalLaunch &s, const ProblemDesc *probs, int cou
   if (hipError_t e = fused_grid(s, count, s.max_chunks + 1, &g)) return e;
   return dispatch_dtype(s.dtype, [&](auto TT) { return dispatch_int<1, 2, 4>(s.ppt, [&](auto PPT) {
     return dispatch_bool(s.buffer_loads, [&](auto BUF) { return dispatch_bool(s.img32, [&](auto IMG32) {
-      return dispatch_bool(lm.opt->strategy != 0, [&](auto STRAT) { return dispatch_bool(lm.priors, [&](auto PRIOR) {
+      return dispatch_bool(lm.opt->strategy != 0, [&](auto STRAT) { return dispatch_bool(lm.side, [&](auto SIDE) {
         typedef typename decltype(TT)::type T;
         constexpr int P = decltype(PPT)::value;
         constexpr bool I = decltype(IMG32)::value;
         if constexpr (!shape_exists<T, P, kLmThreads>() || (I && sizeof(T) != 8)) return hipErrorInvalidValue;
         else {
-          hipLaunchKernelGGL((ea_lm_iter_kernel<T, P, decltype(BUF)::value, I, decltype(STRAT)::value ? 1 : 0, decltype(PRIOR)::value>),
+          hipLaunchKernelGGL((ea_lm_iter_kernel<T, P, decltype(BUF)::value, I, decltype(STRAT)::value ? 1 : 0, decltype(SIDE)::value>),
                              g.grid, dim3(kLmThreads), g.shmem, stream, s.x0, s.y0, s.z0, s.n0, g.shape, g.chunks_per_xcd, io.rows_in,
                              lm.first.tile_begin, lm.first.tile_end, probs, lm.poses, io.rows_out, groups, io.st_in, io.st_out,
                              io.cold_in, io.cold_out, lm.traces, *lm.opt, lm.progress, lm.host_states, lm.host_traces, lm.post_done);

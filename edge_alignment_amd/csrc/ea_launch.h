@@ -34,15 +34,15 @@ struct EvalLaunch {
 };
 // the fold that rides in an evaluation's launch: the previous step's rows into its result slots
 struct RidingFold { const GroupDesc *groups; const double *prev_rows; EvalOut *prev_out; };
-// the LM state an ea_lm_step_kernel / ea_lm_iter_kernel launch works on; `priors`: the PriorDesc table sits behind the
-// launch's `groups` (one per problem)
+// the LM state an ea_lm_step_kernel / ea_lm_iter_kernel launch works on; `side`: the side table (PriorDesc records: NormalPriors and the constant-coordinate mask) sits behind the
+// launch's `groups` (one per problem) -- some problem carries a NormalPrior or holds tangent coordinates constant
 struct LMLaunch {
   PoseState *poses; LMState *states; LMCold *cold; LMTrace *traces;
   const LMOptions *opt;
   int *progress;
   LMState *host_states; LMTrace *host_traces;
   GroupDesc first;
-  int post_done, priors;
+  int post_done, side;
 };
 // what ea_lm_iter_kernel adds: launch j reads what launch j - 1 wrote and writes the other buffer of each pair (the `out`
 // buffers take the place of LMLaunch::states / cold, which the launcher does not read)

@@ -59,7 +59,7 @@ struct LMState {
   int num_successful, num_unsuccessful, num_consecutive_invalid;
   int num_evals;    // whole-problem evaluations performed
   int rot_transposed;
-  int pad_;
+  int held;         // tangent coordinates held constant, bit i = coordinate i of [delta0 delta1 delta2 | tx ty tz] (0: all free)
 };
 
 // Cold state: written once per accepted step, read back only after a rejected / invalid step (the system at x is
@@ -83,7 +83,7 @@ EA_HD inline void lm_copy_state(LMState *d, const LMState *s) {
   d->reuse_diagonal = s->reuse_diagonal; d->dl_reuse = s->dl_reuse; d->iteration = s->iteration; d->running = s->running;
   d->termination = s->termination; d->why = s->why; d->num_successful = s->num_successful; d->num_unsuccessful = s->num_unsuccessful;
   d->num_consecutive_invalid = s->num_consecutive_invalid; d->num_evals = s->num_evals; d->rot_transposed = s->rot_transposed;
-  d->pad_ = s->pad_;
+  d->held = s->held;
 }
 
 // packed upper-triangle index of (a,b), a <= b, 6x6
@@ -329,12 +329,48 @@ EA_HD inline void lm_finish(LMState *s, int termination, int why) {
   s->why = why;
 }
 
+// ---- constant tangent coordinates (Problem::SetParameterBlockConstant / SubsetParameterization) ----------------------
+//
+// Ceres removes constant coordinates from the program; here the 6x6 system keeps its shape and the held rows and columns are
+// replaced by a unit diagonal, the held gradient entries by zero (lm_mask_system, once per evaluation, behind the priors).
+// Every cross term between a free and a held coordinate is then an exact zero, so the factorisation, the model cost change
+// and Plus() give the step of the reduced system bit for bit, and a held coordinate's step is (minus) zero: held t components
+// and, with all three delta held, q come back with the bits they went in with.  Jacobi scaling, the LM diagonal, the step
+// norm and gradient_max_norm see nothing of the held coordinates but exact zeros.  Only x_norm needs the mask itself
+// (lm_x_norm).  The held columns of an evaluation are not looked at: Ceres does not evaluate Jacobians of constant blocks.
+constexpr int kHeldAll = 0x3f, kHeldDelta = 0x07, kHeldTrans = 0x38;
+
+EA_HD inline void lm_mask_system(int held, double acc[kAccSlots]) {
+  if (EA_LIKELY(!held)) return;
+#pragma unroll
+  for (int a = 0; a < 6; ++a) {
+    if ((held >> a) & 1) acc[kAccJtr + a] = 0.0;
+#pragma unroll
+    for (int b = a; b < 6; ++b)
+      if (((held >> a) | (held >> b)) & 1) acc[kAccJtJ + sym6(a, b)] = a == b ? 1.0 : 0.0;
+  }
+}
+
+// |x| over the ambient coordinates of the non-constant blocks (TrustRegionMinimizer's x_norm on the reduced program): q counts
+// while any delta is free, t -- the whole block -- while any of its components is.  Nothing held: the norm_n(x, 7) of the
+// mask-free code, term for term in the same order.
+EA_HD inline double lm_x_norm(const double x[7], int held) {
+  const bool use_q = (held & kHeldDelta) != kHeldDelta, use_t = (held & kHeldTrans) != kHeldTrans;
+  double s = 0.0;
+#pragma unroll
+  for (int i = 0; i < 7; ++i) {
+    const double v = (i < 4 ? use_q : use_t) ? x[i] : 0.0;
+    s += v * v;
+  }
+  return sqrt(s);
+}
+
 EA_HD inline void lm_init(LMState *s, const LMOptions *o, const double q[4], const double t[3],
-                          int rot_transposed) {
+                          int rot_transposed, int held = 0) {
   for (int i = 0; i < 4; ++i) s->x[i] = q[i];
   for (int i = 0; i < 3; ++i) s->x[4 + i] = t[i];
   for (int i = 0; i < 7; ++i) s->cand[i] = s->x[i];
-  s->x_norm = norm_n(s->x, 7);
+  s->x_norm = held ? lm_x_norm(s->x, held) : norm_n(s->x, 7);
   s->cost = 0.0;
   for (int i = 0; i < 6; ++i) { s->S[i] = 1.0; s->diagonal[i] = 0.0; }
   s->radius = o->initial_trust_region_radius;
@@ -349,7 +385,7 @@ EA_HD inline void lm_init(LMState *s, const LMOptions *o, const double q[4], con
   s->num_successful = s->num_unsuccessful = s->num_consecutive_invalid = 0;
   s->num_evals = 0;
   s->rot_transposed = rot_transposed;
-  s->pad_ = 0;
+  s->held = held & kHeldAll;
 }
 
 // The evaluation at s->x delivered `acc`: take the cost and
@@ -546,7 +582,9 @@ EA_HD inline bool lm_eval_usable(const double acc[kAccSlots]) {
 }
 
 // after the evaluation at the initial pose
-template <int STRAT, bool LITE = false>
+// MASK: s->held may be non-zero (acc has been through lm_mask_system).  MASK = false is the code from before constant
+// coordinates existed; MASK = true with nothing held gives the same bits.
+template <int STRAT, bool LITE = false, bool MASK = false>
 EA_HD inline void lm_begin(LMState *s, LMCold *c, LMTrace *tr, const LMOptions *o, const double acc[kAccSlots],
                            LMPending *pend) {
   pend->store_system = 0;
@@ -555,6 +593,16 @@ EA_HD inline void lm_begin(LMState *s, LMCold *c, LMTrace *tr, const LMOptions *
   // a functor returning false, or a non-finite residual / Jacobian (lm_eval_usable), fails the evaluation: at the start
   // point the solve ends with FAILURE and the parameters untouched
   if (EA_UNLIKELY(!lm_eval_usable(acc))) { lm_finish(s, 2, 6); return; }
+  if constexpr (MASK) {
+    // every coordinate held: Ceres' "no non-constant parameter blocks" -- the cost is evaluated once and reported as
+    // initial and final cost, no step is taken, CONVERGENCE / function tolerance with zero iterations
+    if (EA_UNLIKELY(s->held == kHeldAll)) {
+      s->cost = acc[kAccCost];
+      lm_pend_trace(s, pend, 0, 0.0, 0.0, 0.0, 1);
+      lm_finish(s, 0, 1);
+      return;
+    }
+  }
   lm_take_system<LITE>(s, pend, acc);
   if (o->jacobi_scaling)
     for (int i = 0; i < 6; ++i) s->S[i] = 1.0 / (1.0 + sqrt(acc[kAccJtJ + sym6(i, i)]));
@@ -569,7 +617,7 @@ EA_HD inline void lm_begin(LMState *s, LMCold *c, LMTrace *tr, const LMOptions *
 // the join, and on the one lane that runs this code a register move costs what an FMA costs -- roughly a third of the
 // instructions of an iteration were moves.  Works on locals and commits at the end: on anything unusual it returns false with
 // *s and *pend untouched, and the caller runs the general form.
-template <int STRAT, bool LITE>
+template <int STRAT, bool LITE, bool MASK = false>
 EA_HD inline bool lm_advance_fast(LMState *s, LMCold *c, const LMOptions *o, const double acc[kAccSlots], LMPending *pend) {
   if (EA_UNLIKELY(!lm_eval_usable(acc))) return false;
   const double cand_cost = acc[kAccCost];
@@ -585,7 +633,8 @@ EA_HD inline bool lm_advance_fast(LMState *s, LMCold *c, const LMOptions *o, con
   // accepted: the system of this evaluation is the system at the new x
   double x_norm = s->x_norm, gradient_max_norm = s->gradient_max_norm;
   if constexpr (!LITE) {
-    x_norm = norm_n(s->cand, 7);
+    if constexpr (MASK) x_norm = lm_x_norm(s->cand, s->held);
+    else x_norm = norm_n(s->cand, 7);
     double neg[6], xp[7], m = 0.0;
 #pragma unroll
     for (int i = 0; i < 6; ++i) neg[i] = -acc[kAccJtr + i];
@@ -728,13 +777,13 @@ EA_HD inline bool lm_advance_fast(LMState *s, LMCold *c, const LMOptions *o, con
 }
 
 // after the evaluation at s->cand
-template <int STRAT, bool LITE = false>
+template <int STRAT, bool LITE = false, bool MASK = false>
 EA_HD inline void lm_advance(LMState *s, LMCold *c, LMTrace *tr, const LMOptions *o, const double acc[kAccSlots],
                              LMPending *pend) {
   pend->store_system = 0;
   pend->trace_it = -1;
 #ifndef EA_LM_NO_FAST_PATH  // (tests/test_lm_host_logic.py builds the host shim both ways: the two must agree bit for bit)
-  if (EA_LIKELY((lm_advance_fast<STRAT, LITE>(s, c, o, acc, pend)))) return;
+  if (EA_LIKELY((lm_advance_fast<STRAT, LITE, MASK>(s, c, o, acc, pend)))) return;
 #endif
   s->num_evals += 1;
   const bool eval_ok = lm_eval_usable(acc);  // (false: the step is rejected like one that raised the cost)
@@ -760,7 +809,10 @@ EA_HD inline void lm_advance(LMState *s, LMCold *c, LMTrace *tr, const LMOptions
   if (EA_LIKELY(rel > o->min_relative_decrease)) {
 #pragma unroll
     for (int i = 0; i < 7; ++i) s->x[i] = s->cand[i];
-    if constexpr (!LITE) s->x_norm = norm_n(s->x, 7);
+    if constexpr (!LITE) {
+      if constexpr (MASK) s->x_norm = lm_x_norm(s->x, s->held);
+      else s->x_norm = norm_n(s->x, 7);
+    }
     lm_take_system<LITE>(s, pend, acc);
     fresh = true;
     EA_LM_PROBE(1);
@@ -798,17 +850,27 @@ EA_HD inline void lm_advance(LMState *s, LMCold *c, LMTrace *tr, const LMOptions
 // run-time strategy (the host-side loops: ea_solve_sharded, tests/lm_host_shim.cpp)
 EA_HD inline void lm_begin_rt(LMState *s, LMCold *c, LMTrace *tr, const LMOptions *o, const double acc[kAccSlots],
                               LMPending *pend) {
-  if (o->strategy == 0) lm_begin<0>(s, c, tr, o, acc, pend); else lm_begin<1>(s, c, tr, o, acc, pend);
+  if (s->held) { if (o->strategy == 0) lm_begin<0, false, true>(s, c, tr, o, acc, pend); else lm_begin<1, false, true>(s, c, tr, o, acc, pend); }
+  else if (o->strategy == 0) lm_begin<0>(s, c, tr, o, acc, pend); else lm_begin<1>(s, c, tr, o, acc, pend);
 }
 EA_HD inline void lm_advance_rt(LMState *s, LMCold *c, LMTrace *tr, const LMOptions *o, const double acc[kAccSlots],
                                 LMPending *pend) {
-  if (o->strategy == 0) lm_advance<0>(s, c, tr, o, acc, pend); else lm_advance<1>(s, c, tr, o, acc, pend);
+  if (s->held) { if (o->strategy == 0) lm_advance<0, false, true>(s, c, tr, o, acc, pend); else lm_advance<1, false, true>(s, c, tr, o, acc, pend); }
+  else if (o->strategy == 0) lm_advance<0>(s, c, tr, o, acc, pend); else lm_advance<1>(s, c, tr, o, acc, pend);
 }
 
 // One evaluation's sums (at s->x for the first, at s->cand after that) through the state machine: the body of a host-side
 // solve loop `while (s->running)`.  The device kernels interleave the flush with their LDS traffic and spell this out.
-EA_HD inline void lm_feed(LMState *s, LMCold *c, LMTrace *tr, const LMOptions *o, const double acc[kAccSlots]) {
+// With coordinates held (lm_init's `held`) the sums are masked here, behind whatever priors the caller has added.
+EA_HD inline void lm_feed(LMState *s, LMCold *c, LMTrace *tr, const LMOptions *o, const double acc_in[kAccSlots]) {
   LMPending pend;
+  double masked[kAccSlots];
+  const double *acc = acc_in;
+  if (s->held) {
+    for (int i = 0; i < kAccSlots; ++i) masked[i] = acc_in[i];
+    lm_mask_system(s->held, masked);
+    acc = masked;
+  }
   if (s->num_evals == 0) lm_begin_rt(s, c, tr, o, acc, &pend);
   else lm_advance_rt(s, c, tr, o, acc, &pend);
   lm_flush(&pend, c, tr, acc);

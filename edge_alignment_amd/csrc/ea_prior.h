@@ -30,6 +30,10 @@ struct PriorDesc {
   double Ht[9];   // A^T A of the translation block, 3x3 row-major
   double bt[3];
   int32_t has_q, has_t;
+  // The side table's other passenger: the tangent coordinates the solve and the covariance hold constant (bit i = coordinate
+  // i of [delta | t]; ea_problem_set_constant_parameters).  prior_add does not read it: priors enter first, the mask is
+  // applied to the sums afterwards (lm_mask_system in ea_lm.h, cov_from_acc in ea_cov.h).
+  int32_t held, pad_;
 };
 
 static_assert(sizeof(PriorDesc) % 8 == 0, "PriorDesc sits in an array of doubles-aligned records");

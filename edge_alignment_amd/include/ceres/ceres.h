@@ -182,6 +182,8 @@ class LocalParameterization {
   virtual int GlobalSize() const = 0;
   virtual int LocalSize() const = 0;
   virtual bool IsQuaternion() const { return false; }
+  // non-NULL for a SubsetParameterization: constancy[i] != 0 = coordinate i held constant
+  virtual const std::vector<char> *SubsetConstancy() const { return nullptr; }
 };
 // q+ = [cos|d|, sin|d|/|d| d] (x) q  — applied on the device by the LM-step kernel; the host forms below are Ceres'
 // public definition (local_parameterization.cc), for callers that probe the parameterisation themselves
@@ -211,6 +213,35 @@ class QuaternionParameterization : public LocalParameterization {
   int GlobalSize() const override { return 4; }
   int LocalSize() const override { return 3; }
   bool IsQuaternion() const override { return true; }
+};
+
+// ceres/local_parameterization.h (Ceres <= 2.1): the coordinates listed in constant_parameters are held, the others take
+// the step.  The facade hosts it on the translation block (ea_problem_set_constant_parameters); on the quaternion block
+// ceres::Solve reports it as unsupported.  The host forms are Ceres' definitions.
+class SubsetParameterization : public LocalParameterization {
+ public:
+  SubsetParameterization(int size, const std::vector<int> &constant_parameters)
+      : constancy_((size_t)(size > 0 ? size : 0), 0), local_size_(size > 0 ? size : 0) {
+    for (int i : constant_parameters)
+      if (i >= 0 && i < size && !constancy_[(size_t)i]) { constancy_[(size_t)i] = 1; --local_size_; }
+  }
+  bool Plus(const double *x, const double *delta, double *x_plus_delta) const override {
+    for (size_t i = 0, j = 0; i < constancy_.size(); ++i) x_plus_delta[i] = constancy_[i] ? x[i] : x[i] + delta[j++];
+    return true;
+  }
+  bool ComputeJacobian(const double *, double *jacobian) const override {  // GlobalSize x LocalSize, row-major
+    for (size_t i = 0, j = 0; i < constancy_.size(); ++i) {
+      for (int c = 0; c < local_size_; ++c) jacobian[i * (size_t)local_size_ + (size_t)c] = 0.0;
+      if (!constancy_[i]) jacobian[i * (size_t)local_size_ + j++] = 1.0;
+    }
+    return true;
+  }
+  int GlobalSize() const override { return (int)constancy_.size(); }
+  int LocalSize() const override { return local_size_; }
+  const std::vector<char> *SubsetConstancy() const override { return &constancy_; }
+ private:
+  std::vector<char> constancy_;
+  int local_size_;
 };
 
 // ---- problem --------------------------------------------------------------------------------
@@ -275,6 +306,25 @@ class Problem {
   void SetParameterization(double *values, LocalParameterization *p) {
     params_.push_back(p);
     if (p && p->IsQuaternion()) quat_param_on_ = values;
+    // the last parameterization set on a block holds: a later non-subset one takes the block's held coordinates back
+    for (size_t i = 0; i < subsets_.size(); ++i)
+      if (subsets_[i].first == values) { subsets_.erase(subsets_.begin() + (long)i); break; }
+    if (p && p->SubsetConstancy()) subsets_.push_back(std::make_pair(values, (const LocalParameterization *)p));
+  }
+  // Parameter blocks are added by AddResidualBlock; these exist for code that names them first.  `size` is not recorded: the
+  // block sizes are those of the EAResidue blocks (4, 3), and Build checks a SubsetParameterization's size against them.
+  void AddParameterBlock(double *, int) {}
+  void AddParameterBlock(double *values, int, LocalParameterization *p) { SetParameterization(values, p); }
+  // A constant block is removed from the program: ceres::Solve leaves it bit for bit as it is and ceres::Covariance returns
+  // zero blocks for it (ea_problem_set_constant_parameters).  Problem::Evaluate is not affected.
+  void SetParameterBlockConstant(double *values) {
+    if (!IsParameterBlockConstant(values)) constant_.push_back(values);
+  }
+  void SetParameterBlockVariable(double *values) {
+    constant_.erase(std::remove(constant_.begin(), constant_.end(), values), constant_.end());
+  }
+  bool IsParameterBlockConstant(double *values) const {
+    return std::find(constant_.begin(), constant_.end(), values) != constant_.end();
   }
   int NumResidualBlocks() const { return (int)(blocks_.size() + priors_.size()); }
   int NumResiduals() const {
@@ -332,6 +382,8 @@ class Problem {
   std::vector<LossFunction *> losses_;
   std::vector<LocalParameterization *> params_;
   double *quat_param_on_ = nullptr;
+  std::vector<double *> constant_;                                          // SetParameterBlockConstant
+  std::vector<std::pair<double *, const LocalParameterization *>> subsets_;  // SubsetParameterization per block
   friend class ProblemAccess;
 };
 
@@ -368,6 +420,8 @@ struct Solver {
     int num_successful_steps = -1, num_unsuccessful_steps = -1;
     int num_residual_blocks = 0, num_residuals = 0;
     int num_parameter_blocks = 2, num_parameters = 7, num_effective_parameters = 6;
+    // the program Solve ran after constant blocks and constant coordinates were removed (blocks, ambient and tangent sizes)
+    int num_parameter_blocks_reduced = 2, num_parameters_reduced = 7, num_effective_parameters_reduced = 6;
     double total_time_in_seconds = -1;
     ea_summary detail{};
 
@@ -383,14 +437,16 @@ struct Solver {
       char buf[2048];
       std::snprintf(buf, sizeof(buf),
                     "\nSolver Summary (edge_alignment_amd, MI355X gfx950; ceres:: facade)\n\n"
-                    "Parameter blocks %26d\nParameters %32d\nEffective parameters %22d\n"
+                    "                                     Original                  Reduced\n"
+                    "Parameter blocks %26d %24d\nParameters %32d %24d\nEffective parameters %22d %24d\n"
                     "Residual blocks %27d\nResidual %34d\n\n"
                     "Minimizer                        TRUST_REGION\n"
                     "Linear solver          6x6 normal equations (device)\n\n"
                     "Cost:\nInitial %35.6e\nFinal %37.6e\nChange %36.6e\n\n"
                     "Minimizer iterations %22d\nSuccessful steps %26d\nUnsuccessful steps %24d\n\n"
                     "Time (in seconds):\nTotal %37.4f\n\nTermination: %28s (%s)\n",
-                    num_parameter_blocks, num_parameters, num_effective_parameters, num_residual_blocks,
+                    num_parameter_blocks, num_parameter_blocks_reduced, num_parameters, num_parameters_reduced,
+                    num_effective_parameters, num_effective_parameters_reduced, num_residual_blocks,
                     num_residuals, initial_cost, final_cost, initial_cost - final_cost,
                     num_successful_steps + num_unsuccessful_steps, num_successful_steps, num_unsuccessful_steps,
                     total_time_in_seconds, TermName(), message.c_str());
@@ -434,7 +490,7 @@ class ProblemAccess {  // keeps Problem's internals private to user code
   // family k's blocks in the order they were added.  Returns EA_OK, a libea_hip error code, or -1000 with *err set
   // for a problem this facade cannot host.
   static int Build(Problem *problem, int dtype, int device, std::vector<ea_problem *> *ps_out,
-                   std::vector<std::vector<int>> *order, std::string *err) {
+                   std::vector<std::vector<int>> *order, std::string *err, int *held_out = nullptr) {
     const auto &blocks = problem->blocks_;
     if (blocks.empty()) { *err = "a NormalPrior needs EAResidue blocks on the same pose (a problem of priors only cannot be hosted)"; return -1000; }
     const auto &b0 = blocks[0];
@@ -471,6 +527,10 @@ class ProblemAccess {  // keeps Problem's internals private to user code
       if (prior_on[blk]) { *err = "at most one NormalPrior per parameter block"; return -1000; }
       prior_on[blk] = np;
     }
+    int held[6];
+    if (!ConstantMask(problem, held, err)) return -1000;
+    if (held_out)  // (the mask the problem was built with: ceres::Solve derives the summary's reduced counts from it)
+      for (int i = 0; i < 6; ++i) held_out[i] = held[i];
     std::vector<ea_problem *> &ps = *ps_out;
     ps.assign(fams.size(), nullptr);
     order->clear();
@@ -492,11 +552,34 @@ class ProblemAccess {  // keeps Problem's internals private to user code
       }
       if (rc == EA_OK && k > 0) rc = ea_problem_add_term(ps[0], ps[k]);
     }
+    if (rc == EA_OK && (held[0] | held[1] | held[2] | held[3] | held[4] | held[5]))  // the mask too goes on the head problem
+      rc = ea_problem_set_constant_parameters(ps[0], held);
     for (int blk = 0; blk < 2 && rc == EA_OK; ++blk)  // the priors go on the head problem: every term shares its pose
       if (prior_on[blk])
         rc = ea_problem_set_normal_prior(ps[0], blk, prior_on[blk]->A().data(), prior_on[blk]->num_residuals(),
                                          prior_on[blk]->b().data());
     return rc;
+  }
+
+  // SetParameterBlockConstant / SubsetParameterization -> the tangent mask of ea_problem_set_constant_parameters
+  // ([delta(3) | t(3)]); false with *err set for what the facade cannot host
+  static bool ConstantMask(const Problem *problem, int held[6], std::string *err) {
+    for (int i = 0; i < 6; ++i) held[i] = 0;
+    if (problem->blocks_.empty()) return true;
+    double *q = problem->blocks_[0].q, *t = problem->blocks_[0].t;
+    for (const auto &sb : problem->subsets_) {
+      if (sb.first == q) { *err = "SubsetParameterization on the quaternion block is not supported (SetParameterBlockConstant holds all of it)"; return false; }
+      if (sb.first != t) { *err = "a SubsetParameterization must sit on the translation block the EAResidue blocks share"; return false; }
+      const std::vector<char> &c = *sb.second->SubsetConstancy();
+      if (c.size() != 3) { *err = "SubsetParameterization size does not match the translation block (3)"; return false; }
+      for (int i = 0; i < 3; ++i) held[3 + i] = c[(size_t)i] ? 1 : 0;
+    }
+    for (double *cb : problem->constant_) {
+      if (cb == q) held[0] = held[1] = held[2] = 1;
+      else if (cb == t) held[3] = held[4] = held[5] = 1;
+      else { *err = "SetParameterBlockConstant names a block that is not the (quaternion, translation) pair of the EAResidue blocks"; return false; }
+    }
+    return true;
   }
 
   // the (quaternion, translation) pair every block of the problem shares; false for an empty problem
@@ -613,9 +696,16 @@ class ProblemAccess {  // keeps Problem's internals private to user code
     std::vector<ea_problem *> ps;
     std::vector<std::vector<int>> order;
     std::string berr;
-    int rc = Build(problem, options.ea_dtype, options.ea_device, &ps, &order, &berr);
+    int held[6] = {0, 0, 0, 0, 0, 0};
+    int rc = Build(problem, options.ea_dtype, options.ea_device, &ps, &order, &berr, held);
     if (rc == -1000) return fail(berr);
     const auto &b0 = blocks[0];  // (Build refused a problem without EAResidue blocks)
+    {
+      const int free_q = 3 - held[0] - held[1] - held[2], free_t = 3 - held[3] - held[4] - held[5];
+      s.num_parameter_blocks_reduced = (free_q > 0) + (free_t > 0);
+      s.num_parameters_reduced = (free_q > 0 ? 4 : 0) + (free_t > 0 ? 3 : 0);
+      s.num_effective_parameters_reduced = free_q + free_t;
+    }
     ea_options o;
     ea_default_options(&o);
     o.max_num_iterations = options.max_num_iterations;

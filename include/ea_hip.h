@@ -403,6 +403,34 @@ int ea_problem_set_normal_prior(ea_problem *p, int block, const double *A, int k
  * covariance (ea_tracker_set_covariance) includes it. */
 int ea_tracker_set_motion_prior(ea_tracker *tr, double sigma_rot, double sigma_trans);
 
+/* ---- constant parameters: Problem::SetParameterBlockConstant / SubsetParameterization (Ceres <= 2.1) ------------------
+ * tangent_constant[6] in the solver's ordering [delta0 delta1 delta2 | tx ty tz]; non-zero = held.  NULL = all variable.
+ * What Ceres <= 2.1 can express: all three delta held = SetParameterBlockConstant(q); any subset of t held =
+ * SubsetParameterization(3, ...) on t, all three = SetParameterBlockConstant(t).  EXTENSION: holding only some of the delta
+ * -- the update rotation's delta then stays in the span of the free axes (q itself is still updated by
+ * QuaternionParameterization::Plus with that delta); Ceres has no counterpart.
+ * Solves (ea_solve, ea_batch_solve with a mask per problem, ea_solve_pyramid with each level's own mask, the sharded forms,
+ * the tracker) remove the held coordinates from the program as Ceres does: the step is the LM / dogleg step of the reduced
+ * m x m system over the free coordinates; Jacobi scaling, the LM diagonal, the model cost change, the step norm and the
+ * gradient max-norm come from the free columns only; x_norm of the parameter-tolerance test covers the ambient coordinates
+ * of the non-constant blocks (q while any delta is free, t while any component is).  Held t components, and q when all delta
+ * are held, come back bit-identical to the input.  Priors are added first, the mask afterwards: a prior on a constant block
+ * contributes only to the reported cost.  All six held: one cost evaluation, no step, EA_CONVERGENCE / EA_WHY_FUNCTION_TOL,
+ * num_iterations = 0, initial_cost == final_cost (Ceres' "no non-constant parameter blocks"); a failed evaluation there
+ * gives EA_FAILURE / EA_WHY_INITIAL_EVAL_FAILED.  The held columns of an evaluation are not inspected.
+ * Covariance (ea_problem_covariance, ea_batch_covariance, the tracker's): decomposition and rank rule run on the reduced
+ * m x m JtJ (DENSE_SVD: max_rank = m - null_space_rank; SPARSE_QR: full rank m); `tangent` has zero rows and columns for
+ * held coordinates, `eigenvalues` the m values in descending order followed by zeros, the ambient blocks are lifted from
+ * the reduced result (a constant block gives zero blocks); all six held: ok = 1, rank = 0, everything zero.
+ * NOT affected -- these return the full 6x6 system as without a mask: ea_eval, ea_cost, ea_batch_eval, ea_batch_eval_poses /
+ * _resident_poses, ea_eval_points, the rows API.
+ * Stored on the head problem only: EA_ERR_INVALID_ARG for a problem that is a term of another, and ea_problem_add_term
+ * refuses a term that carries a mask.  Sharded solves apply the mask to the all-reduced system: every rank must set the same
+ * mask.  Bumps the problem's version; survives ea_problem_set_points, ea_problem_set_dt and the frame producers, so a mask
+ * set on ea_tracker_problem() holds for every push. */
+int ea_problem_set_constant_parameters(ea_problem *p, const int tangent_constant[6]);
+int ea_problem_get_constant_parameters(const ea_problem *p, int tangent_constant[6]);
+
 /* ---- materialised mode: the "EAResidue batch Evaluate" view -------------------------------------------------------
  * Replaces N calls of ceres::AutoDiffCostFunction<EAResidue,1,4,3>::Evaluate followed by the parameterisation's 4x3
  * plus-Jacobian (standalone/utils.h:48-92, standalone_edge_align.cpp:261-278): residual r and the effective 1x6 row

@@ -1,5 +1,5 @@
 """Cost of a NormalPrior in the solve (profiles/LOG.md, pose priors): LM iterations/s of one fp64 problem of 1e5 points
-(config_c2_twin, Cauchy(1)), without a prior and with weak priors on q and t (the prior-free kernels vs the PRIOR
+(config_c2_twin, Cauchy(1)), without a prior and with weak priors on q and t (the prior-free kernels vs the SIDE
 instantiations of ea_lm_iter_kernel / ea_lm_step_kernel).  The prior is centred on the start pose with sigmas large enough
 that the solve takes the same path; iterations/s = iterations of one solve / best-of-rounds median solve time.  Alternating
 rounds, so drift of the box hits both forms alike."""
