@@ -24,6 +24,7 @@
 #include "ea_hip_dev.h"
 #include "ea_launch.h"
 #include "ea_lm.h"
+#include "ea_poses_map.h"
 #include "ea_prior.h"
 #include "ea_spin.h"
 #include "ea_types.h"
@@ -302,6 +303,9 @@ struct ea_problem {
   int ws_now_kind = 0, ws_now_h = 0, ws_now_w = 0;
 };
 
+// one fold of a pose-batched call: the sequence number its completion raises the pinned flag to, and the poses it covers
+struct KposesMark { int seq, start, g; };
+
 struct ea_batch {
   std::vector<ea_problem *> probs;
   std::vector<uint64_t> versions;
@@ -383,9 +387,13 @@ struct ea_batch {
   // the launch shape of the pose-batched evaluation -- a throughput shape (more points per lane than the latency shape one
   // evaluation of the same batch takes) -- and the partial rows / widest term it implies per pose
   int kp_ppt = 1, kp_nt = 256, kp_chunk = 256, kp_ntiles = 0, kp_max_chunks = 0;
+  unsigned char *d_kblock = nullptr;  // flat form: [PosesRow x rows | ProblemDesc x nterms | GroupDesc x count], the two below point into it
   ProblemDesc *d_kprobs = nullptr;
   GroupDesc *d_kgroups = nullptr;
-  double *d_krows = nullptr;
+  double *d_krows = nullptr;          // flat form: two arrays of kp_rows_cap poses each; grid form: one
+  int kp_rows_cap = 0;
+  int t_kp_order = 0;                 // tuning key "poses_order": 1 = an XCD walks the rows of a pose instead of the poses of a row (A/B)
+  std::vector<KposesMark> kp_marks;   // the folds of the last call: sequence number, first pose, poses
   // one launch per LM iteration (ea_lm_iter_kernel): the second buffer of each pair a launch reads / writes -- states and cold
   // systems [LMState x count | LMCold x count] and partial rows -- beside d_states, d_cold, d_partials
   unsigned char *d_iter_alt = nullptr;
@@ -906,6 +914,7 @@ static void bench_ring_free(ea_batch *b) {
 }
 
 static void kposes_free_tables(ea_batch *b);
+static bool kposes_flat(const ea_batch *b);
 
 static void kposes_free(ea_batch *b) {
   kposes_free_tables(b);
@@ -1411,18 +1420,28 @@ extern "C" int ea_batch_eval(ea_batch *b, const double *q, const double *t, doub
 // ceres::Problem::Evaluate once per pose (src/SolveEA.cpp:241 is the reference's one call of it).  One evaluation through
 // ea_batch_eval is a launch pair and a synchronisation (~30 us on a 5e4-point pair, 3 us of which are the kernel, run by
 // 196 workgroups on a 256-CU chip).  K independent evaluations do not have to queue up behind each other: the POSE is one
-// more batch dimension.  The evaluation kernel already takes (workgroup column, term) grids with a descriptor and a pose
-// per term; here the descriptor table is replicated G times -- copy g of term j keeps j's points and image and owns its own
-// partial rows and pose slot g -- so ONE launch of (chunks, G x terms) workgroups evaluates every point at G poses, one
-// fold launch of G x count workgroups folds them straight into pinned host memory (the sums of pose k are those
-// ea_batch_eval returns at pose k up to rounding: the pose path cuts the points into chunks of its own, kposes_shape),
-// and K poses are ceil(K / G) such pairs behind one synchronisation.  Every (point, pose) pair runs the whole per-point arithmetic; nothing is shared between poses but the
-// bytes of the points and the image, which the later poses find in the caches.  (Round 3 first chained K launches with the
-// fold of evaluation k-1 riding in launch k -- 3.3 us per C2 evaluation, one small launch at a time; G poses per launch
-// fill the chip.)
+// more batch dimension.  A launch evaluates G poses of the batch: `rows` chunks per pose (all terms together, one partial row
+// each) x G poses = one flat list of work items, dealt evenly over the 8 XCDs (ea_poses_map.h; a per-pose deal cannot be
+// even when `rows` does not divide by 8 -- C2's 98 chunks left one XCD half idle), each XCD walking the poses of its own
+// run of chunks back to back.  The kernel (ea_eval_poses_kernel) derives pose, term and chunk from the item: it reads the
+// batch's own descriptors -- a copy behind a small row table, built once per build of the batch -- and pose slot
+// pose * count + group, and writes partial row pose * rows + row.  Nothing is replicated per pose, so a larger K costs
+// ea_batch_set_poses rows and result slots only.  K poses are n = ceil(K / G) launches of ceil(K / n) poses behind one
+// synchronisation.  The fold of launch i -- one 256-lane workgroup per (pose, problem), straight into pinned host memory
+// -- rides in FRONT of launch i + 1 (two row arrays alternate), only the last launch's is a launch of its own, in the
+// same workgroups and summation order: a result does not depend on the launch its pose fell into.  Every fold raises a
+// pinned flag to its own sequence number, and the host unpacks the results of launch i while launch i + 1 runs.  (The sums
+// of pose k are those ea_batch_eval returns at pose k up to rounding: the pose path cuts the points into chunks of its
+// own, kposes_shape.)  Every (point, pose) pair runs the whole per-point arithmetic; nothing is shared between poses but
+// the bytes of the points and the image, which the later poses find in the caches.
+// Variant functors, LDS staging, wide_accumulate and terms that share a pose keep the form this one replaced: descriptor
+// and group tables replicated G times, a (chunks, G x terms) grid of ea_eval_fused_kernel's body under the name
+// ea_eval_poses_grid_kernel, and a stand-alone 1024-lane fold behind every launch.
+// (Round 3 first chained K launches with the fold of evaluation k-1 riding in launch k -- 3.3 us per C2 evaluation, one
+// small launch at a time; G poses per launch fill the chip.)
 
 // G: poses per launch -- enough workgroups to fill the chip several times over (~32k), within the grid's y limit and 64 MB
-// of partial rows
+// of partial rows (both arrays of the flat form together)
 // Launch shape.  One evaluation of a batch is shaped for latency (one point per lane on frame-sized problems: as many
 // wavefronts as possible, few partial rows for the LM step to fold); a launch of G poses is throughput-bound, where more
 // points per lane amortise the wavefront butterfly and 256-lane workgroups keep the occupancy
@@ -1450,51 +1469,90 @@ static int kposes_group(const ea_batch *b, int K) {
   const int64_t wgs = std::max<int64_t>(1, (int64_t)b->kp_ntiles);
   int64_t g = (32768 + wgs - 1) / wgs;
   g = std::min<int64_t>(g, 65535 / std::max(1, b->nterms));
-  g = std::min<int64_t>(g, ((int64_t)64 << 20) / (wgs * kAccSlots * (int64_t)sizeof(double)));
+  g = std::min<int64_t>(g, ((int64_t)64 << 20) / ((kposes_flat(b) ? 2 : 1) * wgs * kAccSlots * (int64_t)sizeof(double)));
   if (b->t_kp_G > 0) g = std::min<int64_t>(g, b->t_kp_G);
   return (int)std::max<int64_t>(1, std::min<int64_t>(g, K));
 }
 
+// a batch ea_eval_poses_kernel covers: the plain functor on the L2 path, one term per problem (any dtype, addressing and
+// image type); the others keep the (chunks, G x terms) grid over replicated tables and a stand-alone fold per launch
+static bool kposes_flat(const ea_batch *b) { return !b->any_variant && b->lds_bytes == 0 && !b->wide && b->terms_are_groups; }
+
 static void kposes_free_tables(ea_batch *b) {
-  cached_free(b->d_kprobs); cached_free(b->d_kgroups); cached_free(b->d_krows);
-  b->d_kprobs = nullptr; b->d_kgroups = nullptr; b->d_krows = nullptr;
-  b->kp_G = 0;
+  if (b->d_kblock) cached_free(b->d_kblock);
+  else { cached_free(b->d_kprobs); cached_free(b->d_kgroups); }
+  cached_free(b->d_krows);
+  b->d_kblock = nullptr; b->d_kprobs = nullptr; b->d_kgroups = nullptr; b->d_krows = nullptr;
+  b->kp_G = 0; b->kp_rows_cap = 0;
 }
 
-// the replicated descriptor / group tables and the partial rows of G poses; rebuilt when the batch was (kp_G = 0)
+// What the pose-batched launches read beside the batch's own tables, and the partial rows of G poses; the tables are rebuilt
+// when the batch was (kp_G = 0), the rows grow with G.
+//   flat form: ONE block [PosesRow x rows | ProblemDesc x nterms | GroupDesc x count] -- the row table (ea_poses_map.h), a
+//     copy of the descriptors right behind it (the kernel finds the table at probs - rows) and the group table in the pose
+//     path's own chunking -- built once per build of the batch, whatever G; two row arrays of G poses each, which the
+//     launches of a call alternate between (the riders of launch i + 1 read what launch i wrote).
+//   grid form: the descriptor / group tables replicated G times and one row array of G poses.
 static int kposes_tables(ea_batch *b, int G) {
-  if (b->kp_G >= G && !(b->t_kp_G > 0 && b->kp_G > b->t_kp_G)) return EA_OK;
+  const bool fresh = b->kp_G == 0, flat = kposes_flat(b);
+  if (!fresh && G <= b->kp_rows_cap) { b->kp_G = G; return EA_OK; }
   HIPCHK(hipStreamSynchronize(b->stream));
-  kposes_free_tables(b);
   const size_t nterms = (size_t)b->nterms, count = b->probs.size(), rows = (size_t)b->kp_ntiles;
+  if (fresh || !flat) kposes_free_tables(b);
+  else { cached_free(b->d_krows); b->d_krows = nullptr; b->kp_rows_cap = 0; }
   const ProblemDesc *hd = reinterpret_cast<const ProblemDesc *>(b->h_desc);                          // (batch_build's staging block)
   const GroupDesc *hg = reinterpret_cast<const GroupDesc *>(b->h_desc + nterms * sizeof(ProblemDesc));
   // the partial rows of one pose in the pose path's own chunking (kposes_shape)
   std::vector<int32_t> row0(nterms + 1, 0);
   for (size_t j = 0; j < nterms; ++j) row0[j + 1] = row0[j] + (int32_t)(((int64_t)hd[j].n + b->kp_chunk - 1) / b->kp_chunk);
-  std::vector<ProblemDesc> descs((size_t)G * nterms);
-  std::vector<GroupDesc> groups((size_t)G * count);
-  for (int g = 0; g < G; ++g) {
+  const size_t row_bytes = std::max<size_t>(1, (flat ? 2 : 1) * (size_t)G * rows) * kAccSlots * sizeof(double);
+  if (flat && !b->d_kblock) {
+    const size_t tb = rows * sizeof(PosesRow), pb = nterms * sizeof(ProblemDesc), gb = count * sizeof(GroupDesc);
+    static_assert(sizeof(PosesRow) == 16 && alignof(ProblemDesc) <= 16, "the descriptors sit right behind the row table");
+    std::vector<unsigned char> blk(tb + pb + gb);
+    PosesRow *tab = reinterpret_cast<PosesRow *>(blk.data());
+    ProblemDesc *descs = reinterpret_cast<ProblemDesc *>(blk.data() + tb);
+    GroupDesc *groups = reinterpret_cast<GroupDesc *>(blk.data() + tb + pb);
     for (size_t j = 0; j < nterms; ++j) {
-      ProblemDesc d = hd[j];
-      d.tile_begin = row0[j] + (int32_t)(g * rows); d.tile_end = row0[j + 1] + (int32_t)(g * rows);
-      d.group += (int32_t)(g * count);
-      descs[(size_t)g * nterms + j] = d;
+      for (int32_t r = row0[j]; r < row0[j + 1]; ++r) tab[r] = PosesRow{(int32_t)j, row0[j], (int32_t)count, 0};
+      descs[j] = hd[j];
+      descs[j].tile_begin = row0[j]; descs[j].tile_end = row0[j + 1];
     }
     for (size_t i = 0; i < count; ++i) {
-      GroupDesc gd = hg[i];
-      gd.tile_begin = row0[(size_t)hg[i].term_begin] + (int32_t)(g * rows); gd.tile_end = row0[(size_t)hg[i].term_end] + (int32_t)(g * rows);
-      gd.term_begin += (int32_t)(g * nterms); gd.term_end += (int32_t)(g * nterms);
-      groups[(size_t)g * count + i] = gd;
+      groups[i] = hg[i];
+      groups[i].tile_begin = row0[(size_t)hg[i].term_begin]; groups[i].tile_end = row0[(size_t)hg[i].term_end];
     }
+    HIPCHK(cached_malloc(reinterpret_cast<void **>(&b->d_kblock), std::max<size_t>(16, blk.size()), b->device));
+    b->d_kprobs = reinterpret_cast<ProblemDesc *>(b->d_kblock + tb);
+    b->d_kgroups = reinterpret_cast<GroupDesc *>(b->d_kblock + tb + pb);
+    if (!blk.empty()) HIPCHK(hipMemcpyAsync(b->d_kblock, blk.data(), blk.size(), hipMemcpyHostToDevice, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));  // (the host vector goes out of scope)
+  } else if (!flat) {
+    std::vector<ProblemDesc> descs((size_t)G * nterms);
+    std::vector<GroupDesc> groups((size_t)G * count);
+    for (int g = 0; g < G; ++g) {
+      for (size_t j = 0; j < nterms; ++j) {
+        ProblemDesc d = hd[j];
+        d.tile_begin = row0[j] + (int32_t)(g * rows); d.tile_end = row0[j + 1] + (int32_t)(g * rows);
+        d.group += (int32_t)(g * count);
+        descs[(size_t)g * nterms + j] = d;
+      }
+      for (size_t i = 0; i < count; ++i) {
+        GroupDesc gd = hg[i];
+        gd.tile_begin = row0[(size_t)hg[i].term_begin] + (int32_t)(g * rows); gd.tile_end = row0[(size_t)hg[i].term_end] + (int32_t)(g * rows);
+        gd.term_begin += (int32_t)(g * nterms); gd.term_end += (int32_t)(g * nterms);
+        groups[(size_t)g * count + i] = gd;
+      }
+    }
+    HIPCHK(cached_malloc(reinterpret_cast<void **>(&b->d_kprobs), std::max<size_t>(1, descs.size()) * sizeof(ProblemDesc), b->device));
+    HIPCHK(cached_malloc(reinterpret_cast<void **>(&b->d_kgroups), groups.size() * sizeof(GroupDesc), b->device));
+    if (!descs.empty()) HIPCHK(hipMemcpyAsync(b->d_kprobs, descs.data(), descs.size() * sizeof(ProblemDesc), hipMemcpyHostToDevice, b->stream));
+    HIPCHK(hipMemcpyAsync(b->d_kgroups, groups.data(), groups.size() * sizeof(GroupDesc), hipMemcpyHostToDevice, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));  // (the host vectors go out of scope)
   }
-  HIPCHK(cached_malloc(reinterpret_cast<void **>(&b->d_kprobs), std::max<size_t>(1, descs.size()) * sizeof(ProblemDesc), b->device));
-  HIPCHK(cached_malloc(reinterpret_cast<void **>(&b->d_kgroups), groups.size() * sizeof(GroupDesc), b->device));
-  HIPCHK(cached_malloc(reinterpret_cast<void **>(&b->d_krows), std::max<size_t>(1, (size_t)G * rows) * kAccSlots * sizeof(double), b->device));
-  if (!descs.empty()) HIPCHK(hipMemcpyAsync(b->d_kprobs, descs.data(), descs.size() * sizeof(ProblemDesc), hipMemcpyHostToDevice, b->stream));
-  HIPCHK(hipMemcpyAsync(b->d_kgroups, groups.data(), groups.size() * sizeof(GroupDesc), hipMemcpyHostToDevice, b->stream));
-  HIPCHK(hipMemsetAsync(b->d_krows, 0, std::max<size_t>(1, (size_t)G * rows) * kAccSlots * sizeof(double), b->stream));
-  HIPCHK(hipStreamSynchronize(b->stream));  // (the host vectors go out of scope)
+  HIPCHK(cached_malloc(reinterpret_cast<void **>(&b->d_krows), row_bytes, b->device));
+  HIPCHK(hipMemsetAsync(b->d_krows, 0, row_bytes, b->stream));
+  b->kp_rows_cap = G;
   b->kp_G = G;
   return EA_OK;
 }
@@ -1539,18 +1597,65 @@ extern "C" int ea_batch_set_poses(ea_batch *b, int K, const double *q, const dou
   return EA_OK;
 }
 
-// the K evaluations of the resident poses on the batch's stream, G poses per launch pair, results into dv_kout[k * count + i]
+static int next_done_seq(ea_batch *b) { return b->done_seq = b->done_seq == 0x7fffffff ? 1 : b->done_seq + 1; }
+// the pinned flag only ever moves forward through the sequence numbers of a call: "has reached", not "equals" -- the host may
+// look after a later launch of the same call has raised it again
+static bool seq_reached(int flag, int seq) { return (unsigned)flag - (unsigned)seq < 0x40000000u; }
+
+// The K evaluations of the resident poses on the batch's stream, results into dv_kout[k * count + i]: launches of
+// ceil(K / n) poses, n = ceil(K / G) (the last one takes the remainder).  Flat form: the fold of launch i rides in front of
+// launch i + 1, the last launch's is a stand-alone launch of the same workgroups; every fold raises the pinned flag to a
+// sequence number of its own (consecutive within the call; b->kp_marks keeps them for the caller that unpacks as it goes).
+// Grid form: an evaluation + fold pair per launch, the last fold raises the flag (flag_last).
 static int enqueue_resident_poses(ea_batch *b, int K, bool folds = true, bool flag_last = false) {
-  const int count = (int)b->probs.size(), G = b->kp_G;
-  for (int start = 0; start < K; start += G) {
-    const int g = std::min(G, K - start);
-    HIPCHK(launch_eval_poses(eval_launch(b, /*kposes=*/true), b->d_kprobs, g * b->nterms, b->d_kposes + (size_t)start * count,
-                             b->d_krows, b->stream));
-    if (!folds) continue;
-    if (flag_last && start + g >= K) HIPCHK(launch_last_fold(b, b->d_kgroups, g * count, b->d_krows, b->dv_kout + (size_t)start * count));
-    else HIPCHK(launch_reduce(b->d_kgroups, g * count, b->d_krows, b->dv_kout + (size_t)start * count, b->stream));
+  const int count = (int)b->probs.size(), per = poses_launch_size(K, b->kp_G), rows = b->kp_ntiles;
+  b->kp_marks.clear();
+  if (!kposes_flat(b)) {
+    for (int start = 0; start < K; start += per) {
+      const int g = std::min(per, K - start);
+      HIPCHK(launch_eval_poses_grid(eval_launch(b, /*kposes=*/true), b->d_kprobs, g * b->nterms, b->d_kposes + (size_t)start * count,
+                                    b->d_krows, b->stream));
+      if (!folds) continue;
+      if (flag_last && start + g >= K) HIPCHK(launch_last_fold(b, b->d_kgroups, g * count, b->d_krows, b->dv_kout + (size_t)start * count));
+      else HIPCHK(launch_reduce(b->d_kgroups, g * count, b->d_krows, b->dv_kout + (size_t)start * count, b->stream));
+    }
+    return EA_OK;
   }
+  if (b->done_seq > 0x7fffffff - (K + per - 1) / per - 2) b->done_seq = 0;  // (a call's sequence numbers do not straddle the wrap)
+  const EvalLaunch shape = eval_launch(b, /*kposes=*/true);
+  PosesLaunch pl;
+  pl.rows = rows; pl.order = b->t_kp_order; pl.single = b->nterms == 1;
+  PosesFold owed;  // the fold the launches so far still owe (n = 0: none)
+  owed.count = count; owed.rows_per_pose = rows; owed.groups = b->d_kgroups;
+  owed.counter = b->d_done_count; owed.host_flag = b->d_progress + 3 * (size_t)count;
+  auto owe = [&](int start, int g, const double *from) {
+    owed.n = g * count; owed.rows = from; owed.out = b->dv_kout + (size_t)start * count; owed.seq = next_done_seq(b);
+    b->kp_marks.push_back({owed.seq, start, g});
+  };
+  if (rows == 0) {  // not a single point in the batch: nothing to evaluate, K x count zero results owed
+    if (folds) { owe(0, K, b->d_krows); HIPCHK(launch_poses_fold(b->kp_nt, owed, b->stream)); }
+    return EA_OK;
+  }
+  int i = 0;
+  for (int start = 0; start < K; start += per, ++i) {
+    double *into = b->d_krows + (size_t)(i & 1) * (size_t)b->kp_rows_cap * (size_t)rows * kAccSlots;
+    pl.g = std::min(per, K - start);
+    HIPCHK(launch_eval_poses(shape, pl, b->d_kprobs, b->d_kposes + (size_t)start * count, into, owed, b->stream));
+    if (folds) owe(start, pl.g, into);
+  }
+  if (folds) HIPCHK(launch_poses_fold(b->kp_nt, owed, b->stream));
   return EA_OK;
+}
+
+// results [first, first + n) of the last call (n a multiple of the problem count): priors added at each result's own pose,
+// then out into the caller's arrays
+static void kposes_unpack(ea_batch *b, size_t first, size_t n, double *cost, double *JtJ, double *Jtr, int64_t *n_invalid) {
+  add_priors_host(b, b->h_kout + first, n, [&](size_t j, double x[7]) {  // (h_kqt: the staging block of ea_batch_set_poses)
+    for (int k = 0; k < 7; ++k) x[k] = b->h_kqt[7 * (first + j) + k];
+  });
+  if (cost || JtJ || Jtr || n_invalid)
+    unpack_eval_out(b->h_kout + first, (int)n, cost ? cost + first : nullptr, JtJ ? JtJ + 36 * first : nullptr,
+                    Jtr ? Jtr + 6 * first : nullptr, n_invalid ? n_invalid + first : nullptr);
 }
 
 extern "C" int ea_batch_eval_resident_poses(ea_batch *b, double *cost, double *JtJ, double *Jtr, int64_t *n_invalid) {
@@ -1559,14 +1664,29 @@ extern "C" int ea_batch_eval_resident_poses(ea_batch *b, double *cost, double *J
   if (rc != EA_OK) return rc;
   const int K = b->kp_K;
   if (K < 1 || b->kp_G < 1) return fail(EA_ERR_STATE, "no poses resident (ea_batch_set_poses first; a change of the batch's problems drops them)");
-  const int count = (int)b->probs.size();
+  const size_t count = b->probs.size();
   if ((rc = enqueue_resident_poses(b, K, true, true)) != EA_OK) return rc;
-  if ((rc = wait_results(b)) != EA_OK) return rc;
-  const size_t n = (size_t)K * (size_t)count;
-  add_priors_host(b, b->h_kout, n, [&](size_t j, double x[7]) {  // (h_kqt: the staging block of ea_batch_set_poses)
-    for (int k = 0; k < 7; ++k) x[k] = b->h_kqt[7 * j + k];
-  });
-  if (cost || JtJ || Jtr || n_invalid) unpack_eval_out(b->h_kout, (int)n, cost, JtJ, Jtr, n_invalid);
+  // The results of launch i are unpacked as soon as its fold has raised the flag -- launch i + 1 is still running then --
+  // so that only the last launch's remain behind the final wait.  The poll is bounded like wait_results: should a flag not
+  // show up, the stream is synchronised (everything is complete then, and a device error surfaces as the error it is).
+  size_t done = 0;
+  bool drained = false;
+  for (size_t m = 0; m + 1 < b->kp_marks.size() && !drained; ++m) {
+    const KposesMark &mk = b->kp_marks[m];
+    SpinWait wait(2000.0);
+    while (!seq_reached(__atomic_load_n(&b->h_progress[3 * count], __ATOMIC_ACQUIRE), mk.seq)) {
+      if (wait.poll()) {
+        HIPCHK(hipStreamSynchronize(b->stream));
+        drained = true;
+        break;
+      }
+    }
+    if (drained) break;
+    kposes_unpack(b, done, (size_t)mk.g * count, cost, JtJ, Jtr, n_invalid);
+    done += (size_t)mk.g * count;
+  }
+  if (!drained && (rc = wait_results(b)) != EA_OK) return rc;
+  kposes_unpack(b, done, (size_t)K * count - done, cost, JtJ, Jtr, n_invalid);
   return EA_OK;
 }
 
@@ -1589,7 +1709,7 @@ extern "C" int ea_batch_bench_resident_poses(ea_batch *b, int reps, int evaluati
   float ms = 0.f;
   HIPCHK(hipEventElapsedTime(&ms, evp.e0, evp.e1));
   *ms_per_run = (double)ms / reps;
-  if (launches) *launches = (b->kp_K + b->kp_G - 1) / b->kp_G;
+  if (launches) { const int per = poses_launch_size(b->kp_K, b->kp_G); *launches = (b->kp_K + per - 1) / per; }
   return EA_OK;
 }
 
@@ -2482,6 +2602,7 @@ extern "C" int ea_batch_set_tuning(ea_batch *b, const char *key, int value) {
   else if (k == "fused_iterations") { b->t_fused = value; return EA_OK; }
   else if (k == "zero_copy_poses") { b->t_zero_copy = value; return EA_OK; }
   else if (k == "poses_per_launch") { b->t_kp_G = value > 0 ? value : 0; b->kp_K = 0; return EA_OK; }  // (resident poses are dropped)
+  else if (k == "poses_order") { b->t_kp_order = value ? 1 : 0; return EA_OK; }
   else return fail(EA_ERR_INVALID_ARG, "unknown tuning key: " + k);
   b->built = false;
   return EA_OK;

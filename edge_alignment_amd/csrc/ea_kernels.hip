@@ -39,6 +39,7 @@ extern __device__ int g_lm_probe_row;
   } while (0)
 #endif
 #include "ea_launch.h"
+#include "ea_poses_map.h"
 #include "ea_lm.h"
 #include "ea_prior.h"
 #include "ea_types.h"
@@ -1102,18 +1103,19 @@ __global__ __launch_bounds__(NT) void ea_eval_fused_kernel(
   eval_fused_body<T, PPT, MODE, NT, VAR, BUF, IMG32>(x0, y0, z0, n0, shape, chunks_per_xcd, probs, poses, partials, lds_texels);
 }
 
-// The same kernel under a second name, for the launches of ea_batch_eval_poses (grid y = G poses x terms over a descriptor
-// table replicated G times): rocprofv3 --kernel-trace --stats then keeps the pose-batched launches -- the dominant kernel
-// of bench.py's timed region -- apart from the one-pose launches of the solves and of ea_batch_eval in the same process,
-// and its average duration can be read off the summary.  Body, arguments and instantiations are identical.
+// The same kernel under a second name, for the pose-batched launches of the batches ea_eval_poses_kernel below does not
+// cover (variant functors, LDS staging, wide_accumulate, terms that share a pose): grid y = G poses x terms over a
+// descriptor table replicated G times.  rocprofv3 --kernel-trace --stats keeps them apart from the one-pose launches of the
+// solves and of ea_batch_eval in the same process.  Body, arguments and instantiations are those of ea_eval_fused_kernel.
 template <typename T, int PPT, int MODE, int NT, bool VAR, bool BUF, bool IMG32 = false>
-__global__ __launch_bounds__(NT) void ea_eval_poses_kernel(
+__global__ __launch_bounds__(NT) void ea_eval_poses_grid_kernel(
     const void *__restrict__ x0, const void *__restrict__ y0, const void *__restrict__ z0, int n0,
     int shape, int chunks_per_xcd,
     const ProblemDesc *__restrict__ probs, const PoseState *__restrict__ poses,
     double *__restrict__ partials, int lds_texels) {
   eval_fused_body<T, PPT, MODE, NT, VAR, BUF, IMG32>(x0, y0, z0, n0, shape, chunks_per_xcd, probs, poses, partials, lds_texels);
 }
+
 
 #ifndef EA_TU_VARIANT
 // ------------------------------------------------------------------------------------------------
@@ -1568,6 +1570,130 @@ __global__ __launch_bounds__(NT) void ea_eval_fold_kernel(
     return;
   }
   eval_fused_body<T, PPT, 0, NT, false, BUF, IMG32>(x0, y0, z0, n0, shape, chunks_per_xcd, probs, poses, partials, lds_texels);
+}
+
+// One result of a pose-batched launch folded by one workgroup of NT threads, in the order reduce_tiles<NT, 4> gives a
+// workgroup of this size -- riding in the next evaluation launch or in the stand-alone fold that closes a call, the same
+// sums.  Wavefront 0 stores the 32 words; its lane 0 makes them visible system-wide, counts itself in, and the last
+// arrival of the launch re-arms the counter and raises the pinned flag to the launch's sequence number.
+template <int NT>
+__device__ __forceinline__ void poses_fold_one(const PosesFold &f, int r) {
+  __shared__ __align__(16) double s_part[reduce_tiles_lds<NT>()];
+  int pose, problem;
+  poses_rider(r, f.count, &pose, &problem);
+  const GroupDesc gd = f.groups[problem];
+  const int base = pose * f.rows_per_pose;
+  reduce_tiles<NT, 4>(f.rows, base + gd.tile_begin, base + gd.tile_end, s_part, f.out[r].acc);
+  if (threadIdx.x == 0) {
+    __threadfence_system();
+    const unsigned int prev = __hip_atomic_fetch_add(f.counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    if (prev == (unsigned)f.n - 1u) {
+      __hip_atomic_store(f.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __threadfence_system();
+      __hip_atomic_store(f.host_flag, f.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+}
+
+// The pose-batched evaluation of the plain functor on the L2 path: g poses of a batch in ONE one-dimensional launch whose
+// work items -- (row of a pose, pose) pairs -- are dealt evenly over the 8 XCDs (ea_poses_map.h), with the fold of the
+// PREVIOUS launch's rows riding in front.  A short head of its own in front of the unchanged fused_chunk: chunks, per-point
+// code, reductions and the row index pose * rows + row are those of the (chunks, G x terms) grid it replaces, so every
+// partial row holds the same bits.  The first 14 dwords still arrive with the wave: term 0's points and count, the packed
+// shape, g and rows, the descriptor and pose tables -- all an item of a single-term batch needs to find its pose, its
+// descriptor and its points without a dependent load, at EVERY pose (the 2-D grid issued the early point loads for pose 0
+// only).  A batch of several terms reads one 16-byte entry of the row table first; the table sits right in front of the
+// descriptors (probs - rows entries), so that no further pointer has to be fetched for it.
+template <typename T, int PPT, int MODE, int NT, bool VAR, bool BUF, bool IMG32 = false>
+__global__ __launch_bounds__(NT) void ea_eval_poses_kernel(
+    const void *__restrict__ x0, const void *__restrict__ y0, const void *__restrict__ z0, int n0,
+    int shape, int g, int rows,
+    const ProblemDesc *__restrict__ probs, const PoseState *__restrict__ poses,
+    double *__restrict__ partials, PosesFold fold) {
+  static_assert(MODE == 0 && !VAR, "plain functor, stencil rows from L2");
+  constexpr int chunk = NT * PPT;
+  extern __shared__ __align__(16) unsigned char smem[];
+  double *s_red = reinterpret_cast<double *>(smem);
+  int *s_box = reinterpret_cast<int *>(smem + kRedBytes);
+  const PosesWork w = poses_work(blockIdx.x, shape, rows, g, fold.n);
+  if (w.kind != 2) {  // (uniform)
+    if (w.kind == 1) poses_fold_one<NT>(fold, w.rider);
+    return;
+  }
+  const PosesChunk pc = poses_chunk(w, shape, rows, reinterpret_cast<const PosesRow *>(probs) - rows);
+  const int c = pc.chunk;
+  const long long start = (long long)c * chunk;
+  const int tid = threadIdx.x;
+  T X[PPT], Y[PPT], Z[PPT];
+  const bool early = BUF && pc.term == 0 && n0 > 0;  // (uniform)
+  if constexpr (BUF) {
+    if (early) {
+      if (start >= n0) return;
+      const int count0 = min(chunk, (int)(n0 - start));
+      const __amdgpu_buffer_rsrc_t rx = make_raw_buffer(static_cast<const T *>(x0) + start, (unsigned)count0 * (unsigned)sizeof(T));
+      const __amdgpu_buffer_rsrc_t ry = make_raw_buffer(static_cast<const T *>(y0) + start, (unsigned)count0 * (unsigned)sizeof(T));
+      const __amdgpu_buffer_rsrc_t rz = make_raw_buffer(static_cast<const T *>(z0) + start, (unsigned)count0 * (unsigned)sizeof(T));
+#pragma unroll
+      for (int k = 0; k < PPT; ++k) {
+        const int poff = min(tid + k * NT, count0 - 1) * (int)sizeof(T);
+        X[k] = buf_load_elem<T>(rx, poff); Y[k] = buf_load_elem<T>(ry, poff); Z[k] = buf_load_elem<T>(rz, poff);
+      }
+    }
+  }
+  // descriptor and pose by value, as ONE batch of scalar loads behind one wait (eval_fused_body)
+  const ProblemDesc pd = probs[pc.term];
+  PoseLite<T> ps;
+  int active;
+  {
+    const PoseState *psp = poses + pc.slot;
+    const T *R_ = Uni<T>::R(*psp), *t_ = Uni<T>::t(*psp);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) ps.R[i] = R_[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) ps.t[i] = t_[i];
+    ps.unit_q = psp->unit_q;
+    ps.full = psp;
+    active = psp->active;
+    asm volatile("" ::"s"(pd.x), "s"(pd.y), "s"(pd.z), "s"(IMG32 ? pd.dt32 : pd.dt), "s"(pd.n), "s"(pd.W), "s"(pd.H), "s"(pd.pitch),
+                 "s"(Uni<T>::fx(pd)), "s"(Uni<T>::fy(pd)), "s"(Uni<T>::cx(pd)), "s"(Uni<T>::cy(pd)),
+                 "s"(Uni<T>::loss_a(pd)), "s"(Uni<T>::loss_inv_b(pd)), "s"(Uni<T>::z_guard(pd)), "s"(Uni<T>::z_eps(pd)),
+                 "s"(pd.loss_kind), "s"(pd.variant));
+    asm volatile("" : "+s"(active), "+s"(ps.unit_q), "+s"(ps.R[0]), "+s"(ps.R[1]), "+s"(ps.R[2]), "+s"(ps.R[3]), "+s"(ps.R[4]),
+                      "+s"(ps.R[5]), "+s"(ps.R[6]), "+s"(ps.R[7]), "+s"(ps.R[8]), "+s"(ps.t[0]), "+s"(ps.t[1]), "+s"(ps.t[2]));
+  }
+  if (start >= pd.n || !active) return;
+  const int count = min(chunk, (int)(pd.n - start));
+  const GPtr<T> px = (GPtr<T>)(static_cast<const T *>(pd.x) + start);
+  const GPtr<T> py = (GPtr<T>)(static_cast<const T *>(pd.y) + start);
+  const GPtr<T> pz = (GPtr<T>)(static_cast<const T *>(pd.z) + start);
+  // coalesced point loads; lanes past the end of the chunk re-read its last point
+  if constexpr (BUF) {
+    if (!early) {
+      const __amdgpu_buffer_rsrc_t rx = make_raw_buffer((const T *)px, (unsigned)count * (unsigned)sizeof(T));
+      const __amdgpu_buffer_rsrc_t ry = make_raw_buffer((const T *)py, (unsigned)count * (unsigned)sizeof(T));
+      const __amdgpu_buffer_rsrc_t rz = make_raw_buffer((const T *)pz, (unsigned)count * (unsigned)sizeof(T));
+#pragma unroll
+      for (int k = 0; k < PPT; ++k) {
+        const int poff = min(tid + k * NT, count - 1) * (int)sizeof(T);
+        X[k] = buf_load_elem<T>(rx, poff); Y[k] = buf_load_elem<T>(ry, poff); Z[k] = buf_load_elem<T>(rz, poff);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) {
+      const int jj = min(tid + k * NT, count - 1);
+      X[k] = px[jj]; Y[k] = py[jj]; Z[k] = pz[jj];
+    }
+  }
+  const double sum = fused_chunk<T, PPT, 0, NT, false, BUF, IMG32, PoseLite<T>>(pd, ps, X, Y, Z, count, s_red, s_box, (T *)nullptr, 0,
+                                                                                 tid < kAccSlots ? tid : -1);
+  if (tid < kAccSlots) partials[(size_t)pc.out_row * kAccSlots + tid] = sum;
+}
+
+// the fold that closes a call of the pose-batched path: the last launch's rows, as its riders would have folded them
+template <int NT>
+__global__ __launch_bounds__(NT) void ea_poses_fold_kernel(PosesFold fold) {
+  poses_fold_one<NT>(fold, blockIdx.x);
 }
 
 // SIDE instantiations of the LM kernels.  Problem p's PriorDesc (ea_prior.h; the table sits behind the group table) is
@@ -2138,7 +2264,8 @@ template <typename T, int PPT, int MODE, int NT, bool VAR, bool BUF, bool IMG32>
   return MODE == 0 || (MODE == 1 && !BUF) || (MODE == 2 && sizeof(T) == 4);
 }
 
-// tag 0: ea_eval_fused_kernel, tag 1: the same kernel under the name ea_eval_poses_kernel (the launches of ea_batch_eval_poses)
+// tag 0: ea_eval_fused_kernel, tag 1: the same kernel under the name ea_eval_poses_grid_kernel (the pose-batched launches of the
+// batches ea_eval_poses_kernel does not cover)
 static hipError_t launch_fused_family(int tag, const EvalLaunch &s, const ProblemDesc *probs, int nterms, const PoseState *poses,
                                       double *partials, hipStream_t stream) {
   if (nterms <= 0 || s.max_chunks <= 0) return hipSuccess;
@@ -2154,7 +2281,7 @@ static hipError_t launch_fused_family(int tag, const EvalLaunch &s, const Proble
           constexpr bool B = decltype(BUF)::value, I = decltype(IMG32)::value;
           if constexpr (!fused_exists<T, P, M, N, kVarTU, B, I>()) return hipErrorInvalidValue;
           else {
-            constexpr auto kernel = decltype(TAG)::value ? &ea_eval_poses_kernel<T, P, M, N, kVarTU, B, I>
+            constexpr auto kernel = decltype(TAG)::value ? &ea_eval_poses_grid_kernel<T, P, M, N, kVarTU, B, I>
                                                          : &ea_eval_fused_kernel<T, P, M, N, kVarTU, B, I>;
             hipLaunchKernelGGL(kernel, g.grid, dim3(N), g.shmem, stream, s.x0, s.y0, s.z0, s.n0, g.shape, g.chunks_per_xcd, probs,
                                poses, partials, g.lds_texels);
@@ -2175,10 +2302,42 @@ hipError_t launch_eval_fused(const EvalLaunch &s, const ProblemDesc *probs, int 
   return s.variant ? launch_eval_fused_var(0, s, probs, nterms, poses, partials, stream)
                    : launch_fused_family(0, s, probs, nterms, poses, partials, stream);
 }
-hipError_t launch_eval_poses(const EvalLaunch &s, const ProblemDesc *probs, int nterms, const PoseState *poses, double *partials,
-                             hipStream_t stream) {
+hipError_t launch_eval_poses_grid(const EvalLaunch &s, const ProblemDesc *probs, int nterms, const PoseState *poses, double *partials,
+                                  hipStream_t stream) {
   return s.variant ? launch_eval_fused_var(1, s, probs, nterms, poses, partials, stream)
                    : launch_fused_family(1, s, probs, nterms, poses, partials, stream);
+}
+
+// ea_eval_poses_kernel: g poses of a batch of `rows` partial rows per pose in one launch, `fold` (fold.n riders, 0 = none)
+// riding in front (ea_poses_map.h).  Plain functor, L2 path, one term per problem.
+hipError_t launch_eval_poses(const EvalLaunch &s, const PosesLaunch &p, const ProblemDesc *probs, const PoseState *poses,
+                             double *partials, const PosesFold &fold, hipStream_t stream) {
+  if (s.variant || s.lds_bytes > 0 || s.wide || !s.terms_are_groups || s.chunk != s.nt * s.ppt) return hipErrorInvalidValue;
+  if (p.g <= 0 || p.rows <= 0 || fold.n < 0 || (int64_t)p.rows * p.g > (int64_t)1 << 28) return hipErrorInvalidValue;
+  const int shape = poses_shape(s.xcd_remap != 0, p.order, p.single != 0, fold.n);
+  const dim3 grid(poses_grid(p.rows, p.g, fold.n));
+  return dispatch_dtype(s.dtype, [&](auto TT) { return dispatch_int<1, 2, 4>(s.ppt, [&](auto PPT) {
+    return dispatch_int<256, 1024>(s.nt, [&](auto NT) { return dispatch_bool(s.buffer_loads, [&](auto BUF) {
+      return dispatch_bool(s.img32, [&](auto IMG32) {
+        typedef typename decltype(TT)::type T;
+        constexpr int P = decltype(PPT)::value, N = decltype(NT)::value;
+        constexpr bool B = decltype(BUF)::value, I = decltype(IMG32)::value;
+        if constexpr (!fused_exists<T, P, 0, N, false, B, I>()) return hipErrorInvalidValue;
+        else {
+          hipLaunchKernelGGL((ea_eval_poses_kernel<T, P, 0, N, false, B, I>), grid, dim3(N), (size_t)kHdrBytes, stream, s.x0, s.y0,
+                             s.z0, s.n0, shape, p.g, p.rows, probs, poses, partials, fold);
+          return hipGetLastError();
+        }
+      }); }); });
+  }); });
+}
+
+// the fold that closes a call: fold.n results in workgroups of nt threads, the riders' summation order
+hipError_t launch_poses_fold(int nt, const PosesFold &fold, hipStream_t stream) {
+  if (fold.n <= 0) return hipErrorInvalidValue;  // (somebody has to raise the flag)
+  if (nt == 1024) hipLaunchKernelGGL(ea_poses_fold_kernel<1024>, dim3(fold.n), dim3(1024), 0, stream, fold);
+  else hipLaunchKernelGGL(ea_poses_fold_kernel<256>, dim3(fold.n), dim3(256), 0, stream, fold);
+  return hipGetLastError();
 }
 
 // evaluation into `partials` + the fold of fold.prev_rows -> fold.prev_out in one launch (ea_eval_fold_kernel): plain

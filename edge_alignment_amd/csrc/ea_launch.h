@@ -34,6 +34,20 @@ struct EvalLaunch {
 };
 // the fold that rides in an evaluation's launch: the previous step's rows into its result slots
 struct RidingFold { const GroupDesc *groups; const double *prev_rows; EvalOut *prev_out; };
+// a launch of ea_eval_poses_kernel: g poses x `rows` partial rows per pose; order: 0 = an XCD walks the poses of a row back to
+// back, 1 = the rows of a pose; single: one term in the batch (no row table is read)
+struct PosesLaunch { int g = 0, rows = 0, order = 0, single = 0; };
+// What the folds of the pose-batched path work on: `n` results (pose-major: result r = pose r / count, problem r % count)
+// whose rows lie in `rows` (pose p's at p * rows_per_pose + the problem's range in `groups`, the group table in the pose
+// path's own chunking), folded into out[r]; counter / host_flag / seq: the completion signal of ea_reduce_done_kernel.
+struct PosesFold {
+  int n = 0, count = 1, rows_per_pose = 0, seq = 0;
+  const GroupDesc *groups = nullptr;
+  const double *rows = nullptr;
+  EvalOut *out = nullptr;
+  unsigned int *counter = nullptr;
+  int *host_flag = nullptr;
+};
 // the LM state an ea_lm_step_kernel / ea_lm_iter_kernel launch works on; `side`: the side table (PriorDesc records: NormalPriors and the constant-coordinate mask) sits behind the
 // launch's `groups` (one per problem) -- some problem carries a NormalPrior or holds tangent coordinates constant
 struct LMLaunch {
@@ -62,9 +76,15 @@ struct RowsLaunch {
 // ea_kernels.hip
 hipError_t launch_eval_fused(const EvalLaunch &s, const ProblemDesc *probs, int nterms, const PoseState *poses, double *partials,
                              hipStream_t stream);
-// the same launch under the kernel name ea_eval_poses_kernel: G poses x terms in grid y (ea_batch_eval_poses)
-hipError_t launch_eval_poses(const EvalLaunch &s, const ProblemDesc *probs, int nterms, const PoseState *poses, double *partials,
-                             hipStream_t stream);
+// the same launch under the kernel name ea_eval_poses_grid_kernel: G poses x terms in grid y over tables replicated G times
+// (the pose-batched launches of variant functors, LDS staging, wide_accumulate and terms that share a pose)
+hipError_t launch_eval_poses_grid(const EvalLaunch &s, const ProblemDesc *probs, int nterms, const PoseState *poses,
+                                  double *partials, hipStream_t stream);
+// ea_eval_poses_kernel: the flat, XCD-balanced launch of g poses with the previous launch's fold riding in front; `probs`
+// has the batch's row table (PosesRow x rows, ea_poses_map.h) right in front of it
+hipError_t launch_eval_poses(const EvalLaunch &s, const PosesLaunch &p, const ProblemDesc *probs, const PoseState *poses,
+                             double *partials, const PosesFold &fold, hipStream_t stream);
+hipError_t launch_poses_fold(int nt, const PosesFold &fold, hipStream_t stream);
 hipError_t launch_pixel_cost(int dtype, const ProblemDesc *probs, int problem, int n, const PoseState *poses, void *partials,
                              hipStream_t stream);
 hipError_t launch_eval_rows(const RowsLaunch &s, const ProblemDesc *probs, int nterms, const PoseState *poses, void *r_out,
@@ -91,7 +111,7 @@ hipError_t launch_grid_to_image(int dtype, const double *grid, int W, int H, voi
 hipError_t launch_aos_to_soa(int dtype, const double *src, long long n, int stride, void *x, void *y, void *z, hipStream_t stream);
 hipError_t launch_selftest_reduce(const float *in, float *a, float *b, float *c, float *d, double *o32, double *o64,
                                   hipStream_t stream);
-// ea_kernels_var.hip (the same file under -DEA_TU_VARIANT): what launch_eval_fused (tag 0) / launch_eval_poses (tag 1) hand on
+// ea_kernels_var.hip (the same file under -DEA_TU_VARIANT): what launch_eval_fused (tag 0) / launch_eval_poses_grid (tag 1) hand on
 // when s.variant is set
 hipError_t launch_eval_fused_var(int tag, const EvalLaunch &s, const ProblemDesc *probs, int nterms, const PoseState *poses,
                                  double *partials, hipStream_t stream);

@@ -1,0 +1,85 @@
+// ea_poses_map.h — which piece of a pose-batched evaluation launch a workgroup takes (ea_eval_poses_kernel), as pure
+// functions the kernel and the host share: the host sizes the grid with them and tests them without a device
+// (tests/poses_map_host_shim.cpp).
+//
+// A launch evaluates g poses of a batch whose points are cut into `rows` chunks per pose (all terms together: one partial
+// row per chunk), T = rows * g work items in all, and may carry `riders`: workgroups that fold the rows the PREVIOUS launch
+// left behind, one per (pose, problem) of that launch.  The grid is one-dimensional:
+//
+//   workgroups [0, slots)            slots = riders rounded up to 8: rider L for L < riders, nothing otherwise.  They are
+//                                    dispatched first, so the previous launch's results land early.
+//   workgroups [slots, slots + 8 per) per = ceil(T / 8): workgroup slots + e takes item (e & 7) * per + (e >> 3).
+//
+// Workgroups are dealt round-robin over the 8 XCDs (observed, not promised): XCD x then owns the contiguous items
+// [x per, x per + per) -- no XCD more than `per` of them, at most 7 workgroups of the launch without one -- and because
+// `slots` is a multiple of 8 the riders do not shift the deal.  A per-pose partition cannot be even when `rows` does not
+// divide by 8 (C2: 98 chunks = 7 XCDs x 13 + 1 x 7); a partition of the whole launch can.
+//
+// Item -> (row, pose), order 0: row = t / g, pose = t % g.  An XCD keeps a contiguous run of rows -- its points and image
+// rows stay in its own L2 -- and walks all poses of a chunk back to back.  Order 1: pose = t / rows, row = t % rows.
+// The partial row written is pose * rows + row in either order.
+#pragma once
+#include <stdint.h>
+
+#include "ea_types.h"
+
+namespace ea {
+
+// one entry per row of a pose: the term that owns it, that term's first row, and the batch's problem count (the pose slot
+// of (pose, term) is pose * count + group, and every entry carries `count` so that one 16-byte load answers everything)
+struct PosesRow { int32_t term, row0, count, pad_; };
+
+// the `shape` word of ea_eval_poses_kernel: bit 0 = XCD deal on, bit 1 = item order, bit 2 = a single term (no row table
+// is read), bits 3.. = rider slots / 8
+constexpr int kPosesXcd = 1, kPosesOrder1 = 2, kPosesSingle = 4;
+EA_HD inline int poses_rider_slots(int riders) { return (riders + 7) & ~7; }
+EA_HD inline int poses_shape(bool xcd, int order, bool single, int riders) {
+  return (xcd ? kPosesXcd : 0) | (order ? kPosesOrder1 : 0) | (single ? kPosesSingle : 0) | poses_rider_slots(riders);
+}
+EA_HD inline int poses_shape_slots(int shape) { return shape & ~7; }
+EA_HD inline int poses_per_xcd(int rows, int g) { return (rows * g + 7) >> 3; }
+// workgroups of a launch
+EA_HD inline unsigned poses_grid(int rows, int g, int riders) {
+  return (unsigned)poses_rider_slots(riders) + 8u * (unsigned)poses_per_xcd(rows, g);
+}
+
+struct PosesWork {
+  int kind;        // 0 = nothing, 1 = rider, 2 = evaluation item
+  int rider;       // kind 1: which (pose, problem) of the previous launch
+  int pose, row;   // kind 2: pose of this launch, row of that pose
+};
+EA_HD inline PosesWork poses_work(unsigned L, int shape, int rows, int g, int riders) {
+  PosesWork w = {0, 0, 0, 0};
+  const unsigned slots = (unsigned)poses_shape_slots(shape);
+  if (L < slots) {
+    if (L < (unsigned)riders) { w.kind = 1; w.rider = (int)L; }
+    return w;
+  }
+  const unsigned e = L - slots;
+  const int T = rows * g, per = poses_per_xcd(rows, g);
+  const unsigned t = (shape & kPosesXcd) ? (e & 7u) * (unsigned)per + (e >> 3) : e;
+  if ((e >> 3) >= (unsigned)per || t >= (unsigned)T) return w;
+  w.kind = 2;
+  if (shape & kPosesOrder1) { w.pose = (int)(t / (unsigned)rows); w.row = (int)(t % (unsigned)rows); }
+  else { w.row = (int)(t / (unsigned)g); w.pose = (int)(t % (unsigned)g); }
+  return w;
+}
+// kind 2 -> (term, chunk, pose slot, partial row); `table` is read unless the batch has a single term
+struct PosesChunk { int term, chunk, slot, out_row; };
+EA_HD inline PosesChunk poses_chunk(const PosesWork &w, int shape, int rows, const PosesRow *table) {
+  PosesChunk c = {0, w.row, w.pose, w.pose * rows + w.row};
+  if (!(shape & kPosesSingle)) {
+    const PosesRow r = table[w.row];
+    c.term = r.term; c.chunk = w.row - r.row0; c.slot = w.pose * r.count + r.term;
+  }
+  return c;
+}
+// rider r of a launch whose previous launch evaluated problems [0, count): pose r / count, problem r % count
+EA_HD inline void poses_rider(int r, int count, int *pose, int *problem) { *pose = r / count; *problem = r % count; }
+
+// K poses in launches of at most G: n = ceil(K / G) launches of ceil(K / n) poses, the last one takes the remainder
+// (filling every launch to G can end on a launch of a few poses that costs a whole launch and fold of its own)
+EA_HD inline int poses_launches(int K, int G) { return (K + G - 1) / G; }
+EA_HD inline int poses_launch_size(int K, int G) { const int n = poses_launches(K, G); return (K + n - 1) / n; }
+
+}  // namespace ea
