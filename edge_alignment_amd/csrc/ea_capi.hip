@@ -1,5 +1,6 @@
 // ea_capi.hip — host driver behind include/ea_hip.h: HBM residency, tile lists, launches,
-// the device-resident trust-region loop, and the measurement hooks.  No CPU compute fallback:
+// the device-resident trust-region loop, and the measurement hooks (frame producers and tracker: ea_frames.hip; what the two
+// files share: ea_capi_internal.h).  No CPU compute fallback:
 // without a gfx950 device every compute entry point returns EA_ERR_NO_DEVICE.
 
 #include <hip/hip_runtime.h>
@@ -20,6 +21,7 @@
 #include <vector>
 
 #include "../../include/ea_hip.h"
+#include "ea_capi_internal.h"
 #include "ea_cov.h"
 #include "ea_hip_dev.h"
 #include "ea_launch.h"
@@ -33,7 +35,7 @@ using namespace ea;
 
 static thread_local std::string g_err;
 
-static int fail(int code, const std::string &msg) {
+int ea::fail(int code, const std::string &msg) {
   g_err = msg;
   return code;
 }
@@ -41,23 +43,9 @@ static int fail(int code, const std::string &msg) {
 // (ea_launch.h) for ea_comm.hip
 extern "C" int ea_internal_fail(int code, const char *msg) { return fail(code, msg ? msg : ""); }
 
-#define HIPCHK(expr)                                                                          \
-  do {                                                                                        \
-    hipError_t e_ = (expr);                                                                   \
-    if (e_ != hipSuccess)                                                                     \
-      return fail(e_ == hipErrorNoDevice ? EA_ERR_NO_DEVICE : EA_ERR_HIP,                     \
-                  std::string(#expr) + ": " + hipGetErrorString(e_));                        \
-  } while (0)
-
-// scope guards for the temporaries of the measurement / test hooks, so that an early HIPCHK return frees them
+// scope guards for the temporaries of the measurement / test hooks, so that an early HIPCHK return frees them (DevBuf:
+// ea_capi_internal.h)
 namespace {
-hipError_t cached_malloc(void **out, size_t bytes, int device);  // (the resource cache below)
-void cached_free(void *p);
-struct DevBuf {
-  void *p = nullptr;
-  ~DevBuf() { if (p) cached_free(p); }  // (blocks that did not come from the cache fall through to hipFree)
-  template <typename U> U *as() const { return static_cast<U *>(p); }
-};
 struct EventPair {
   hipEvent_t e0 = nullptr, e1 = nullptr;
   ~EventPair() {
@@ -97,8 +85,10 @@ struct ResourceCache {
 ResourceCache &cache() { static ResourceCache *c = new ResourceCache; return *c; }  // (never destroyed: frees at exit race the runtime's teardown)
 constexpr size_t kCacheMaxBytes = (size_t)1 << 30;
 constexpr size_t kCacheMaxEntries = 256;
+void release_cached_memory_locked_free();
+}  // namespace
 
-hipError_t cached_malloc(void **out, size_t bytes, int device) {
+hipError_t ea::cached_malloc(void **out, size_t bytes, int device) {
   *out = nullptr;
   if (bytes == 0) bytes = 256;
   bytes = (bytes + 255) & ~(size_t)255;
@@ -130,7 +120,6 @@ hipError_t cached_malloc(void **out, size_t bytes, int device) {
   hipError_t e = hipMalloc(&p, bytes);
   if (e != hipSuccess) {  // the cache may be what is in the way: give it back and try once more
     (void)hipGetLastError();
-    extern void release_cached_memory_locked_free();
     release_cached_memory_locked_free();
     e = hipMalloc(&p, bytes);
     if (e != hipSuccess) return e;
@@ -141,7 +130,7 @@ hipError_t cached_malloc(void **out, size_t bytes, int device) {
   return hipSuccess;
 }
 
-void cached_free(void *p) {
+void ea::cached_free(void *p) {
   if (!p) return;
   ResourceCache &c = cache();
   CachedBlock blk{p, 0, -1, 0u};
@@ -162,6 +151,7 @@ void cached_free(void *p) {
   (void)hipFree(p);
 }
 
+namespace {
 hipError_t cached_host_malloc(void **out, size_t bytes, unsigned flags, int device) {
   *out = nullptr;
   if (bytes == 0) bytes = 64;
@@ -253,55 +243,6 @@ extern "C" int ea_release_cached_memory(void) {
   release_cached_memory_locked_free();
   return EA_OK;
 }
-
-struct ea_problem {
-  int device = 0;
-  int dtype = EA_F64;
-  ea_camera cam{};
-  int loss_kind = EA_LOSS_CAUCHY;  // the reference's `new CauchyLoss(1.)`
-  double loss_a = 1.0;
-  double z_guard = 0.01, z_eps = 0.0;
-  int rot_transposed = 0;
-  // residual variants (utils.h:102-421)
-  int variant = 0;                       // bit 0 distortion, bit 1 second camera
-  double dist[5] = {0, 0, 0, 0, 0};      // k1, k2, p1, p2, k3
-  double T12[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-  double T12inv[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-  std::vector<ea_problem *> terms;       // further residual families sharing this problem's pose
-  PriorDesc prior = {};                  // NormalPriors on q / t (ea_problem_set_normal_prior; ea_prior.h)
-  int term_of = 0;                       // how many problems hold this one as a term (a term carries no prior)
-  int held = 0;                          // tangent coordinates held constant, bit i of [delta | t] (ea_problem_set_constant_parameters)
-  int64_t n = 0;
-  void *d_x = nullptr, *d_y = nullptr, *d_z = nullptr;
-  bool own_points = false;
-  // storage order of the points in HBM (ea_problem_set_point_order): order[i] = caller's index of stored point i;
-  // empty = the caller's order
-  int order_tile = -1, order_tile_used = 0;
-  std::vector<int32_t> order;
-  void *d_dt = nullptr;
-  size_t dt_cap = 0;   // bytes allocated behind d_dt: a frame of the same size reuses the allocation
-  // fp64 problems: the float32 mirror of the image (same padded layout and pitch in texels) and whether it holds every
-  // value exactly -- then the plain fp64 kernels read it instead (ProblemDesc::dt32): one 16-byte load per stencil row
-  float *d_dt32 = nullptr;
-  size_t dt32_cap = 0;
-  bool dt32_exact = false;
-  size_t pts_cap = 0;  // bytes allocated behind each of d_x, d_y, d_z when own_points (hipFree / hipMalloc per frame
-                       // cost more than the whole pre-processing of a 640x480 frame)
-  int W = 0, H = 0, pitch = 0;
-  uint64_t version = 1;  // bumped by every setter; batches rebuild their descriptors lazily
-  ea_batch *self = nullptr;
-  hipStream_t stream = nullptr;
-  // scratch for the frame pre-processing kernels (grown on demand, reused across frames)
-  unsigned char *ws = nullptr;
-  size_t ws_bytes = 0;
-  // full-resolution frames on their way to a half-resolution level (ea_problem_set_*_frame_ros_scaled)
-  unsigned char *stage = nullptr;
-  size_t stage_bytes = 0;
-  // what the last producer call left in the workspace: 1 = set_now_frame (Laplacian strength), 2 = set_now_frame_canny
-  // (edge map, no mask), 0 = nothing reusable; with the frame's extent.  The tracker extracts the same frame's edge
-  // points from it instead of uploading and filtering the frame a second time.
-  int ws_now_kind = 0, ws_now_h = 0, ws_now_w = 0;
-};
 
 // one fold of a pose-batched call: the sequence number its completion raises the pinned flag to, and the poses it covers
 struct KposesMark { int seq, start, g; };
@@ -435,7 +376,7 @@ struct ea_batch {
   int any_side = 0;
 };
 
-static int check_device(int device) {
+int ea::check_device(int device) {
   int cnt = 0;
   hipError_t e = hipGetDeviceCount(&cnt);
   if (e != hipSuccess || cnt <= 0)
@@ -553,7 +494,7 @@ static void free_points(ea_problem *p) {
 
 // Room for n points in arrays the problem owns: the previous allocation when it is large enough (and not more than
 // four times too large), a fresh one otherwise.  Leaves the problem without points (n = 0) either way.
-static int reserve_points(ea_problem *p, int64_t n) {
+int ea::reserve_points(ea_problem *p, int64_t n) {
   const size_t need = (size_t)n * (p->dtype == EA_F32 ? 4 : 8);
   if (p->own_points && p->pts_cap >= need && p->pts_cap <= 4 * need + 4096) {
     p->n = 0;
@@ -806,7 +747,7 @@ extern "C" int ea_problem_set_points_device(ea_problem *p, const void *x, const 
   return EA_OK;
 }
 
-static int alloc_dt(ea_problem *p, int W, int H) {
+int ea::alloc_dt(ea_problem *p, int W, int H) {
   p->W = W; p->H = H;
   p->pitch = (W + 2 * kImagePad + 3) & ~3;
   const size_t esz = p->dtype == EA_F32 ? 4 : 8;
@@ -2733,7 +2674,7 @@ extern "C" void ea_default_covariance_options(ea_covariance_options *o) {
   o->apply_loss_function = 1;
 }
 
-static int check_cov_options(const ea_covariance_options *o) {
+int ea::check_cov_options(const ea_covariance_options *o) {
   if (o->algorithm != EA_COV_SPARSE_QR && o->algorithm != EA_COV_DENSE_SVD) return fail(EA_ERR_INVALID_ARG, "unknown covariance algorithm");
   if (o->null_space_rank < -1 || o->null_space_rank > 6) return fail(EA_ERR_INVALID_ARG, "null_space_rank outside [-1, 6]");
   if (!(o->min_reciprocal_condition_number >= 0.0)) return fail(EA_ERR_INVALID_ARG, "min_reciprocal_condition_number must be >= 0");
@@ -3103,265 +3044,6 @@ extern "C" int ea_solve_pyramid(ea_problem *const *levels, int nlevels, const ea
   return EA_OK;
 }
 
-// ---- the reference frame's edge points out of the frame producers' workspace (the producers themselves: further down) ----
-
-namespace {
-struct WsCarver {
-  unsigned char *base;
-  size_t off = 0;
-  template <typename U> U *take(size_t n) {
-    off = (off + 255) & ~(size_t)255;
-    U *r = reinterpret_cast<U *>(base + off);
-    off += n * sizeof(U);
-    return r;
-  }
-};
-}  // namespace
-
-// The new reference frame's edge points from what the "now" producer left in the workspace, in two halves so that the tracker
-// can put the first -- depth upload and per-block edge counts, both asynchronous on the null stream -- in front of the solve of
-// the previous reference (which runs on the batch's own non-blocking stream and touches neither the workspace nor the depth)
-// and the second -- count read-back, compaction -- behind it.  ref_points_finish is also the tail of the full producers
-// (ea_problem_set_ref_frame[_masked|_canny]), which fill the job from their own carve of the workspace.
-// What ref_points_begin left in flight on the null stream: the depth frame on its way up and the per-block edge counts
-struct RefPointsJob {
-  bool started = false;
-  uint8_t *d_edges = nullptr;
-  uint16_t *d_depth = nullptr;
-  int *d_counts = nullptr, *d_total = nullptr;
-};
-
-static int ref_points_begin(ea_problem *p, int kind, const uint16_t *depth, int height, int width, int threshold, RefPointsJob *job) {
-  job->started = false;
-  if (p->ws_now_kind != kind || p->ws_now_h != height || p->ws_now_w != width || (int64_t)height * width < 4096)
-    return EA_ERR_STATE;
-  HIPCHK(hipSetDevice(p->device));
-  const size_t np = (size_t)height * width;
-  // the carve of the producer that ran, to find its buffers again
-  WsCarver ws{p->ws};
-  uint8_t *d_bgr = ws.take<uint8_t>(np * 3);
-  uint8_t *d_gray = ws.take<uint8_t>(np);
-  uint8_t *d_edges;
-  if (kind == 1) {
-    d_edges = ws.take<uint8_t>(np);  // d_lap
-  } else {
-    (void)ws.take<int>(np);      // magnitudes
-    (void)ws.take<uint8_t>(np);  // direction classes
-    (void)ws.take<uint8_t>(np);  // labels
-    d_edges = ws.take<uint8_t>(np);
-  }
-  // the colour frame and its gray version are not needed any more: depth and the block counts take their place
-  uint16_t *d_depth = reinterpret_cast<uint16_t *>(d_bgr);
-  const int nblocks = (int)((np + 1023) / 1024);
-  int *d_counts = reinterpret_cast<int *>(d_gray);
-  int *d_total = d_counts + nblocks;
-  p->ws_now_kind = 0;
-  HIPCHK(hipMemcpyAsync(d_depth, depth, np * 2, hipMemcpyHostToDevice, nullptr));
-  HIPCHK(launch_edge_count_scan(d_edges, d_depth, height, width, threshold, d_counts, d_total, nullptr));
-  job->started = true;
-  job->d_edges = d_edges; job->d_depth = d_depth; job->d_counts = d_counts; job->d_total = d_total;
-  return EA_OK;
-}
-
-static int ref_points_finish(ea_problem *p, const RefPointsJob &job, int height, int width, double z_scaling, int threshold) {
-  if (!job.started) return EA_ERR_STATE;
-  int total = 0;
-  HIPCHK(hipMemcpy(&total, job.d_total, sizeof(int), hipMemcpyDeviceToHost));
-  p->version++;
-  int rc = reserve_points(p, total);
-  if (rc != EA_OK) return rc;
-  if (total > 0) {
-    HIPCHK(launch_edge_scatter(p->dtype, job.d_edges, job.d_depth, height, width, threshold, job.d_counts, p->cam.fx, p->cam.fy, p->cam.cx,
-                               p->cam.cy, z_scaling, p->d_x, p->d_y, p->d_z, total, nullptr));
-    HIPCHK(hipDeviceSynchronize());
-  }
-  p->n = total;
-  return EA_OK;
-}
-
-// Edge points of the frame the last set_now_frame[_canny] call processed, from what that call left in the workspace
-// (Laplacian strength / Canny edge map): only the depth image goes up, no second upload or filtering of the colour
-// frame.  Same thresholds, same compaction and back-projection as ea_problem_set_ref_frame[_canny] => the same points.
-// Returns EA_ERR_STATE when the workspace does not hold that frame (the caller then takes the full path).
-static int ref_points_from_last_now(ea_problem *p, int kind, const uint16_t *depth, int height, int width, double z_scaling,
-                                    int threshold) {
-  RefPointsJob job;
-  int rc = ref_points_begin(p, kind, depth, height, width, threshold, &job);
-  if (rc != EA_OK) return rc;
-  return ref_points_finish(p, job, height, width, z_scaling, threshold);
-}
-
-// ---- frame-to-frame driver (the reference aligns one stored pair, src/ea.cpp:155-200) -------------
-// Every pushed frame is aligned against the previous one: its DT image is produced, the previous frame's edge points
-// are solved against it starting from the last relative pose (constant-velocity prior), then the new frame's edge
-// points become the reference.  All of it stays on the device; one ea_problem is reused.
-struct ea_tracker {
-  ea_problem *p = nullptr;
-  int flavour = 0;      // 0: get_aX / get_distance_transform, 1: Canny (get_aX_canny / get_distance_transform2)
-  int frames = 0;
-  double q[4] = {1, 0, 0, 0}, t[3] = {0, 0, 0};
-  // ea_tracker_set_covariance: the covariance of every aligned frame at the pose it returns
-  bool cov_on = false, cov_valid = false;
-  ea_covariance_options cov_opt{};
-  ea_covariance cov_last{};
-  // ea_tracker_set_motion_prior: NormalPriors centred on each solve's start pose, A = I / sigma (0 = that block off)
-  double sigma_rot = 0.0, sigma_trans = 0.0;
-  bool motion_set = false;  // the problem carries priors this tracker installed: `installed` (a caller's later prior differs)
-  PriorDesc installed = {};
-};
-
-extern "C" int ea_tracker_create(ea_tracker **out, const ea_camera *cam, int dtype, int device, int flavour) {
-  if (!out) return fail(EA_ERR_INVALID_ARG, "NULL argument");
-  if (flavour != 0 && flavour != 1) return fail(EA_ERR_INVALID_ARG, "unknown pre-processing flavour");
-  ea_tracker *tr = new (std::nothrow) ea_tracker;
-  if (!tr) return fail(EA_ERR_ALLOC, "out of host memory");
-  const int rc = ea_problem_create(&tr->p, cam, dtype, device);
-  if (rc != EA_OK) { delete tr; return rc; }
-  tr->flavour = flavour;
-  *out = tr;
-  return EA_OK;
-}
-
-extern "C" void ea_tracker_destroy(ea_tracker *tr) {
-  if (!tr) return;
-  ea_problem_destroy(tr->p);
-  delete tr;
-}
-
-extern "C" ea_problem *ea_tracker_problem(ea_tracker *tr) { return tr ? tr->p : nullptr; }
-
-// q_rel, t_rel: pose of the previous frame in the new frame's coordinates (b_T_a with a = previous, b = new); identity
-// for the first frame.  aligned (nullable): 1 when a solve took place.  A failed solve keeps the prior for the next frame.
-extern "C" int ea_tracker_push_frame(ea_tracker *tr, const uint8_t *bgr, const uint16_t *depth, int height, int width,
-                                     double z_scaling, const ea_options *opt, double q_rel[4], double t_rel[3],
-                                     ea_summary *summary, int *aligned) {
-  if (!tr || !bgr || !depth || !q_rel || !t_rel) return fail(EA_ERR_INVALID_ARG, "NULL argument");
-  // every argument is checked before the tracker's problem is touched: a rejected call leaves the tracker as it was
-  if (!(z_scaling > 0.0)) return fail(EA_ERR_INVALID_ARG, "z_scaling must be > 0");
-  if (height < 1 || width < 1) return fail(EA_ERR_INVALID_ARG, "bad frame extent");
-  int rc = EA_OK;
-  if (aligned) *aligned = 0;
-  if (summary) std::memset(summary, 0, sizeof(*summary));
-  double q_new[4], t_new[3];
-  std::memcpy(q_new, tr->q, sizeof(q_new));
-  std::memcpy(t_new, tr->t, sizeof(t_new));
-  RefPointsJob job;
-  tr->cov_valid = false;
-  if (tr->frames > 0 && ea_problem_num_points(tr->p) > 0) {
-    rc = tr->flavour == 0 ? ea_problem_set_now_frame(tr->p, bgr, height, width, 35, 1, 1)
-                          : ea_problem_set_now_frame_canny(tr->p, bgr, nullptr, height, width, 30, 90, 1, 0.0, 1.0);
-    if (rc != EA_OK) return rc;
-    // the new frame's depth goes up and its edge pixels are counted WHILE the previous reference is solved against the image
-    // just produced (null stream beside the solve's non-blocking stream; neither touches what the other uses)
-    (void)ref_points_begin(tr->p, tr->flavour == 0 ? 1 : 2, depth, height, width, tr->flavour == 0 ? 35 : 0, &job);
-    double q[4], t[3];
-    std::memcpy(q, tr->q, sizeof(q));
-    std::memcpy(t, tr->t, sizeof(t));
-    if (tr->sigma_rot > 0.0 || tr->sigma_trans > 0.0) {
-      // the motion prior: centred on the constant-velocity prediction the solve starts from (replaces the caller's priors)
-      double Aq[16] = {0}, At[9] = {0};
-      for (int i = 0; i < 4; ++i) Aq[5 * i] = tr->sigma_rot > 0.0 ? 1.0 / tr->sigma_rot : 0.0;
-      for (int i = 0; i < 3; ++i) At[4 * i] = tr->sigma_trans > 0.0 ? 1.0 / tr->sigma_trans : 0.0;
-      rc = ea_problem_set_normal_prior(tr->p, 0, tr->sigma_rot > 0.0 ? Aq : nullptr, 4, q);
-      if (rc == EA_OK) rc = ea_problem_set_normal_prior(tr->p, 1, tr->sigma_trans > 0.0 ? At : nullptr, 3, t);
-      if (rc != EA_OK) {
-        if (job.started) (void)hipDeviceSynchronize();
-        return rc;
-      }
-      tr->motion_set = true;
-      tr->installed = tr->p->prior;
-    }
-    ea_summary s;
-    rc = ea_solve(tr->p, opt, q, t, &s);
-    if (rc != EA_OK) {
-      if (job.started) (void)hipDeviceSynchronize();  // (nothing of this frame may stay in flight behind a failed push)
-      return rc;
-    }
-    if (s.termination != EA_FAILURE) {
-      std::memcpy(q_new, q, sizeof(q));
-      std::memcpy(t_new, t, sizeof(t));
-    }
-    if (tr->cov_on) {
-      // The solve's points and DT image are still the problem's: ea_problem_covariance returns only once its results have
-      // landed, i.e. once its evaluation on the batch's stream has read them, and ref_points_finish -- the only step that
-      // overwrites the points -- is enqueued on the null stream after that.  ref_points_begin, already in flight on the null
-      // stream, writes nothing but the workspace of the frame producers, which the evaluation does not read.
-      std::memset(&tr->cov_last, 0, sizeof(tr->cov_last));
-      if (s.termination != EA_FAILURE) {
-        rc = ea_problem_covariance(tr->p, q, t, &tr->cov_opt, &tr->cov_last);
-        if (rc != EA_OK) {
-          if (job.started) (void)hipDeviceSynchronize();
-          return rc;
-        }
-      } else {
-        tr->cov_last.why = 4;  // no pose to take the covariance at
-      }
-      tr->cov_valid = true;
-    }
-    if (summary) *summary = s;
-    if (aligned) *aligned = 1;
-  }
-  // the frame's edge strength / edge map is still in the workspace when it has just been the "now" frame
-  rc = job.started ? ref_points_finish(tr->p, job, height, width, z_scaling, tr->flavour == 0 ? 35 : 0)
-                   : ref_points_from_last_now(tr->p, tr->flavour == 0 ? 1 : 2, depth, height, width, z_scaling, tr->flavour == 0 ? 35 : 0);
-  if (rc == EA_ERR_STATE)
-    rc = tr->flavour == 0 ? ea_problem_set_ref_frame(tr->p, bgr, depth, height, width, z_scaling, 35)
-                          : ea_problem_set_ref_frame_canny(tr->p, bgr, depth, height, width, z_scaling, 30, 90);
-  if (rc != EA_OK) {
-    // the DT image is the new frame's but no reference came out of it: drop the stale reference so that the next push
-    // starts a fresh chain instead of aligning frame k-1's points against frame k+2 from an advanced prior
-    (void)reserve_points(tr->p, 0);
-    tr->p->version++;
-    tr->frames = 0;
-    return rc;
-  }
-  // prior and frame count advance only with the new reference in place
-  std::memcpy(tr->q, q_new, sizeof(q_new));
-  std::memcpy(tr->t, t_new, sizeof(t_new));
-  std::memcpy(q_rel, tr->q, sizeof(tr->q));
-  std::memcpy(t_rel, tr->t, sizeof(tr->t));
-  tr->frames += 1;
-  return EA_OK;
-}
-
-extern "C" int ea_tracker_set_covariance(ea_tracker *tr, const ea_covariance_options *o) {
-  if (!tr) return fail(EA_ERR_INVALID_ARG, "NULL argument");
-  if (o) {
-    const int rc = check_cov_options(o);
-    if (rc != EA_OK) return rc;
-    tr->cov_opt = *o;
-  }
-  tr->cov_on = o != nullptr;
-  tr->cov_valid = false;
-  return EA_OK;
-}
-
-extern "C" int ea_tracker_set_motion_prior(ea_tracker *tr, double sigma_rot, double sigma_trans) {
-  if (!tr) return fail(EA_ERR_INVALID_ARG, "NULL argument");
-  if (!(sigma_rot >= 0.0 && sigma_rot <= DBL_MAX) || !(sigma_trans >= 0.0 && sigma_trans <= DBL_MAX))
-    return fail(EA_ERR_INVALID_ARG, "sigmas must be finite and >= 0");
-  if (sigma_rot == 0.0 && sigma_trans == 0.0 && tr->motion_set) {
-    // off again: a block still holding the prior this tracker installed is cleared; one the caller has set since is kept
-    const PriorDesc &cur = tr->p->prior, &ins = tr->installed;
-    if (cur.has_q && ins.has_q && std::memcmp(cur.Hq, ins.Hq, sizeof(cur.Hq)) == 0 && std::memcmp(cur.bq, ins.bq, sizeof(cur.bq)) == 0)
-      (void)ea_problem_set_normal_prior(tr->p, 0, nullptr, 0, nullptr);
-    if (cur.has_t && ins.has_t && std::memcmp(cur.Ht, ins.Ht, sizeof(cur.Ht)) == 0 && std::memcmp(cur.bt, ins.bt, sizeof(cur.bt)) == 0)
-      (void)ea_problem_set_normal_prior(tr->p, 1, nullptr, 0, nullptr);
-    tr->motion_set = false;
-  }
-  tr->sigma_rot = sigma_rot;
-  tr->sigma_trans = sigma_trans;
-  return EA_OK;
-}
-
-extern "C" int ea_tracker_last_covariance(ea_tracker *tr, ea_covariance *out) {
-  if (!tr || !out) return fail(EA_ERR_INVALID_ARG, "NULL argument");
-  if (!tr->cov_on) return fail(EA_ERR_STATE, "covariance is off (ea_tracker_set_covariance)");
-  if (!tr->cov_valid) return fail(EA_ERR_STATE, "the last push did not align a frame");
-  *out = tr->cov_last;
-  return EA_OK;
-}
-
 // ---- self-test of the wavefront reduction primitives (DPP row_mirror / row_half_mirror with bank
 // masks, v_permlane16/32_swap, quad_perm): in = 32 slots x 64 lanes (fp32); out32/out64 = the 32 wave
 // totals from the fp32 and fp64 reductions; stages (nullable) = 16+8+4+2 rows of 64 lanes.
@@ -3384,477 +3066,6 @@ extern "C" int ea_selftest_wave_reduce(int device, const float *in, double *out3
   if (e == hipSuccess) e = hipMemcpy(out64, d_o + 32, 32 * sizeof(double), hipMemcpyDeviceToHost);
   if (e == hipSuccess && stages) e = hipMemcpy(stages, d_st, 30 * 64 * sizeof(float), hipMemcpyDeviceToHost);
   if (e != hipSuccess) return fail(EA_ERR_HIP, hipGetErrorString(e));
-  return EA_OK;
-}
-
-// ---- frame producers: raw images -> edge points / DT image, on the device -------
-
-static int ensure_ws(ea_problem *p, size_t bytes) {
-  p->ws_now_kind = 0;  // every producer starts by calling this: whatever the workspace held is about to be overwritten
-  if (p->ws_bytes >= bytes) return EA_OK;
-  if (p->ws) { cached_free(p->ws); p->ws = nullptr; p->ws_bytes = 0; }
-  HIPCHK(cached_malloc(reinterpret_cast<void **>(&p->ws), bytes, p->device));
-  p->ws_bytes = bytes;
-  return EA_OK;
-}
-
-static size_t frame_ws_bytes(int H, int W) {
-  const size_t np = (size_t)H * W;
-  return np * 3 + np * 2 + np * 3 /*gray, lap, mask*/ + np * 4 * 2 /*G, dist*/ + np * 4 /*plain float*/ +
-         np * 4 + np * 4 + np /*Canny: magnitudes, direction / label / edge / keep bytes, mask*/ + 16 * 256 +
-         16 * (size_t)((H + 31) / 32 + 1) * W /*segment ends + carries*/ +
-         ((np + 1023) / 1024 + 8) * 4 + 64 * 256;
-}
-
-static int ref_frame_impl(ea_problem *p, const uint8_t *bgr, const uint8_t *mask, const uint16_t *depth, int height,
-                          int width, double z_scaling, int threshold) {
-  if (!p || !bgr || !depth) return fail(EA_ERR_INVALID_ARG, "NULL argument");
-  if (height < 3 || width < 3 || (int64_t)height * width > 0x3fffffff) return fail(EA_ERR_INVALID_ARG, "image extent out of range");
-  if (!(z_scaling > 0.0)) return fail(EA_ERR_INVALID_ARG, "z_scaling must be > 0");
-  HIPCHK(hipSetDevice(p->device));
-  int rc = ensure_ws(p, frame_ws_bytes(height, width));
-  if (rc != EA_OK) return rc;
-  const size_t np = (size_t)height * width;
-  WsCarver ws{p->ws};
-  uint8_t *d_bgr = ws.take<uint8_t>(np * 3);
-  uint16_t *d_depth = ws.take<uint16_t>(np);
-  uint8_t *d_gray = ws.take<uint8_t>(np), *d_lap = ws.take<uint8_t>(np);
-  uint8_t *d_keep = mask ? ws.take<uint8_t>(np) : nullptr;
-  const int nblocks = (int)((np + 1023) / 1024);
-  int *d_counts = ws.take<int>(nblocks + 1);
-  int *d_total = d_counts + nblocks;
-  HIPCHK(hipMemcpyAsync(d_bgr, bgr, np * 3, hipMemcpyHostToDevice, nullptr));
-  HIPCHK(hipMemcpyAsync(d_depth, depth, np * 2, hipMemcpyHostToDevice, nullptr));
-  HIPCHK(launch_edge_strength(d_bgr, height, width, d_gray, d_lap, nullptr));
-  if (mask) {
-    HIPCHK(hipMemcpyAsync(d_keep, mask, np, hipMemcpyHostToDevice, nullptr));
-    HIPCHK(launch_gate_by_mask(d_lap, d_keep, height, width, nullptr));
-  }
-  HIPCHK(launch_edge_count_scan(d_lap, d_depth, height, width, threshold, d_counts, d_total, nullptr));
-  return ref_points_finish(p, RefPointsJob{true, d_lap, d_depth, d_counts, d_total}, height, width, z_scaling, threshold);
-}
-
-extern "C" int ea_problem_set_ref_frame(ea_problem *p, const uint8_t *bgr, const uint16_t *depth, int height, int width,
-                                        double z_scaling, int threshold) {
-  return ref_frame_impl(p, bgr, nullptr, depth, height, width, z_scaling, threshold);
-}
-
-// get_aX_mask (ref: utils.cpp:283-369, call sites standalone_edge_align.cpp:1039, :1081): also requires mask > 0
-extern "C" int ea_problem_set_ref_frame_masked(ea_problem *p, const uint8_t *bgr, const uint8_t *mask, const uint16_t *depth,
-                                               int height, int width, double z_scaling, int threshold) {
-  if (!mask) return fail(EA_ERR_INVALID_ARG, "NULL argument");
-  return ref_frame_impl(p, bgr, mask, depth, height, width, z_scaling, threshold);
-}
-
-// mask (0 = edge / DT source) -> chamfer DT -> [normalise to [lo, hi]] -> the problem's padded DT image
-static int dt_from_mask(ea_problem *p, WsCarver &ws, const uint8_t *d_mask, int height, int width, int normalize,
-                        double lo, double hi, int **dist_out, float **plain_out, bool precise = false) {
-  // the row pass stages one image row of column distances in LDS (4 bytes per pixel, 64 KB)
-  if (width > 16384) return fail(EA_ERR_INVALID_ARG, "frames wider than 16384 pixels are not supported by the DT producers");
-  const size_t np = (size_t)height * width;
-  int *d_G = ws.take<int>(np), *d_dist = ws.take<int>(np);  // d_dist doubles as the float32 distance when `precise`
-  int *d_scan = ws.take<int>(4 * (size_t)((height + 31) / 32) * width);
-  float *d_plain = ws.take<float>(np);
-  unsigned int *d_minmax = ws.take<unsigned int>(2);
-  float *d_dist_f32 = precise ? reinterpret_cast<float *>(d_dist) : nullptr;
-  HIPCHK(launch_chamfer(d_mask, height, width, d_G, d_scan, d_dist, d_dist_f32, d_minmax, nullptr));
-  {
-    int rc = alloc_dt(p, width, height);
-    if (rc != EA_OK) return rc;
-  }
-  HIPCHK(launch_dt_store(p->dtype, d_dist, d_dist_f32, height, width, d_minmax, normalize, lo, hi, p->d_dt, p->pitch, d_plain,
-                         p->d_dt32, nullptr));
-  HIPCHK(hipDeviceSynchronize());
-  p->dt32_exact = p->d_dt32 != nullptr;  // the producers compute the distance transform in float32, as OpenCV does
-  p->version++;
-  if (dist_out) *dist_out = d_dist;
-  if (plain_out) *plain_out = d_plain;
-  return EA_OK;
-}
-
-static int run_dt(ea_problem *p, WsCarver &ws, const uint8_t *d_bgr, int height, int width, int threshold, int median,
-                  int normalize, uint8_t **lap_out, uint8_t **mask_out, int **dist_out, float **plain_out) {
-  const size_t np = (size_t)height * width;
-  uint8_t *d_gray = ws.take<uint8_t>(np), *d_lap = ws.take<uint8_t>(np), *d_mask = ws.take<uint8_t>(np);
-  HIPCHK(launch_edge_strength(d_bgr, height, width, d_gray, d_lap, nullptr));
-  HIPCHK(launch_threshold_median(d_lap, height, width, threshold, median, d_mask, nullptr));
-  if (lap_out) *lap_out = d_lap;
-  if (mask_out) *mask_out = d_mask;
-  return dt_from_mask(p, ws, d_mask, height, width, normalize, 0.0, 1.0, dist_out, plain_out);
-}
-
-// cv::Canny's integer thresholds (L1 magnitude): floor of the ordered pair.  NaN is refused; values beyond any magnitude an
-// 8-bit image can produce (|dx| + |dy| <= 2040) are clamped before the conversion, which is undefined for them otherwise.
-static int canny_thresholds(double t1, double t2, int *low, int *high) {
-  if (t1 != t1 || t2 != t2) return fail(EA_ERR_INVALID_ARG, "Canny threshold is NaN");
-  const double lo = std::min(t1, t2), hi = std::max(t1, t2);
-  *low = (int)std::floor(std::min(std::max(lo, -1e9), 1e9));
-  *high = (int)std::floor(std::min(std::max(hi, -1e9), 1e9));
-  return EA_OK;
-}
-
-// blur 3x3 -> gray -> Canny(low, high) [-> AND (keep > 1)]: edge map and its inverse in the workspace
-static int run_canny(WsCarver &ws, const uint8_t *d_bgr, const uint8_t *d_keep, int height, int width, int low, int high,
-                     uint8_t **edges_out, uint8_t **inv_out, int *rounds_out, int l2_bgr = 0) {
-  const size_t np = (size_t)height * width;
-  uint8_t *d_gray = ws.take<uint8_t>(np);
-  int *d_mag = ws.take<int>(np);
-  uint8_t *d_dir = ws.take<uint8_t>(np), *d_label = ws.take<uint8_t>(np);
-  uint8_t *d_edges = ws.take<uint8_t>(np), *d_inv = ws.take<uint8_t>(np);
-  int *d_changed = ws.take<int>(16);  // one change flag per launch of a hysteresis batch
-  HIPCHK(launch_canny(d_bgr, height, width, low, high, l2_bgr, d_keep, d_gray, d_mag, d_dir, d_label, d_edges, d_inv,
-                      d_changed, rounds_out, nullptr));
-  *edges_out = d_edges;
-  *inv_out = d_inv;
-  return EA_OK;
-}
-
-static int check_frame_args(const ea_problem *p, const void *bgr, int height, int width) {
-  if (!p || !bgr) return fail(EA_ERR_INVALID_ARG, "NULL argument");
-  if (height < 3 || width < 3 || height > 32768 || width > 32768 || (int64_t)height * width > 0x3fffffff)
-    return fail(EA_ERR_INVALID_ARG, "image extent out of range");
-  return EA_OK;
-}
-
-// Canny flavour of the reference frame: get_aX_canny (ref: utils.cpp:371-462)
-extern "C" int ea_problem_set_ref_frame_canny(ea_problem *p, const uint8_t *bgr, const uint16_t *depth, int height,
-                                              int width, double z_scaling, double low_threshold, double high_threshold) {
-  int rc = check_frame_args(p, bgr, height, width);
-  if (rc != EA_OK) return rc;
-  if (!depth) return fail(EA_ERR_INVALID_ARG, "NULL argument");
-  if (!(z_scaling > 0.0) || !(z_scaling <= DBL_MAX)) return fail(EA_ERR_INVALID_ARG, "z_scaling must be > 0 and finite");
-  int lo, hi;
-  rc = canny_thresholds(low_threshold, high_threshold, &lo, &hi);
-  if (rc != EA_OK) return rc;
-  HIPCHK(hipSetDevice(p->device));
-  rc = ensure_ws(p, frame_ws_bytes(height, width));
-  if (rc != EA_OK) return rc;
-  const size_t np = (size_t)height * width;
-  WsCarver ws{p->ws};
-  uint8_t *d_bgr = ws.take<uint8_t>(np * 3);
-  uint16_t *d_depth = ws.take<uint16_t>(np);
-  const int nblocks = (int)((np + 1023) / 1024);
-  int *d_counts = ws.take<int>(nblocks + 1);
-  int *d_total = d_counts + nblocks;
-  HIPCHK(hipMemcpyAsync(d_bgr, bgr, np * 3, hipMemcpyHostToDevice, nullptr));
-  HIPCHK(hipMemcpyAsync(d_depth, depth, np * 2, hipMemcpyHostToDevice, nullptr));
-  uint8_t *d_edges, *d_inv;
-  rc = run_canny(ws, d_bgr, nullptr, height, width, lo, hi, &d_edges, &d_inv, nullptr);
-  if (rc != EA_OK) return rc;
-  // ref: utils.cpp:441 -- all_grad(i) > 0 && Z > 0 on the 0/255 edge map
-  HIPCHK(launch_edge_count_scan(d_edges, d_depth, height, width, 0, d_counts, d_total, nullptr));
-  return ref_points_finish(p, RefPointsJob{true, d_edges, d_depth, d_counts, d_total}, height, width, z_scaling, 0);
-}
-
-// Canny flavour of the current frame: get_distance_transform2 / _masked / _NoNormalize / _masked_NoNormalize
-// (ref: utils.cpp:85-199).  mask (nullable): H x W bytes, edges survive where mask > 1.  normalize != 0: min-max to
-// [norm_lo, norm_hi] ((0,1) at :103, (0,255) at :138).  The debug outputs may be NULL.
-static int now_frame_canny(ea_problem *p, const uint8_t *bgr, const uint8_t *mask, int height, int width, double low_threshold,
-                           double high_threshold, int normalize, double norm_lo, double norm_hi, uint8_t *edges_out,
-                           int32_t *chamfer_fix_out, float *dt_out, int *rounds_out) {
-  int rc = check_frame_args(p, bgr, height, width);
-  if (rc != EA_OK) return rc;
-  int lo, hi;
-  rc = canny_thresholds(low_threshold, high_threshold, &lo, &hi);
-  if (rc != EA_OK) return rc;
-  if (normalize && (!(std::fabs(norm_lo) <= DBL_MAX) || !(std::fabs(norm_hi) <= DBL_MAX)))
-    return fail(EA_ERR_INVALID_ARG, "normalisation range must be finite");
-  HIPCHK(hipSetDevice(p->device));
-  rc = ensure_ws(p, frame_ws_bytes(height, width));
-  if (rc != EA_OK) return rc;
-  const size_t np = (size_t)height * width;
-  WsCarver ws{p->ws};
-  uint8_t *d_bgr = ws.take<uint8_t>(np * 3);
-  uint8_t *d_keep = mask ? ws.take<uint8_t>(np) : nullptr;
-  HIPCHK(hipMemcpyAsync(d_bgr, bgr, np * 3, hipMemcpyHostToDevice, nullptr));
-  if (mask) HIPCHK(hipMemcpyAsync(d_keep, mask, np, hipMemcpyHostToDevice, nullptr));
-  uint8_t *d_edges, *d_inv;
-  rc = run_canny(ws, d_bgr, d_keep, height, width, lo, hi, &d_edges, &d_inv, rounds_out);
-  if (rc != EA_OK) return rc;
-  int *d_dist;
-  float *d_plain;
-  rc = dt_from_mask(p, ws, d_inv, height, width, normalize, norm_lo, norm_hi, &d_dist, &d_plain);
-  if (rc != EA_OK) return rc;
-  if (edges_out) HIPCHK(hipMemcpy(edges_out, d_edges, np, hipMemcpyDeviceToHost));
-  if (chamfer_fix_out) HIPCHK(hipMemcpy(chamfer_fix_out, d_dist, np * 4, hipMemcpyDeviceToHost));
-  if (dt_out) HIPCHK(hipMemcpy(dt_out, d_plain, np * 4, hipMemcpyDeviceToHost));
-  if (!mask) { p->ws_now_kind = 2; p->ws_now_h = height; p->ws_now_w = width; }
-  return EA_OK;
-}
-
-// ---- ROS flavour of the producers (ref: src/SolveEA.cpp:29-119): Canny(rgb, 150, 100, 3, true) on the 3-channel image
-static int ros_thresholds(double t1, double t2, int *low, int *high) {
-  // cv::Canny with L2gradient: min(t, 32767)^2, ordered
-  if (t1 != t1 || t2 != t2) return fail(EA_ERR_INVALID_ARG, "Canny threshold is NaN");
-  double lo = std::max(std::min(t1, t2), -1e4), hi = std::max(std::max(t1, t2), -1e4);
-  lo = std::min(32767.0, lo); hi = std::min(32767.0, hi);
-  if (lo > 0) lo *= lo;
-  if (hi > 0) hi *= hi;
-  *low = (int)std::floor(lo);
-  *high = (int)std::floor(hi);
-  return EA_OK;
-}
-
-// Frames as the ROS callbacks receive them -> the resolution the node works at, on the device: `halvings` times
-// (depth: NaN -> 0, then) cv::resize(..., 0.5, 0.5) (src/ea.cpp:38, :56-62).  bgr / depth: host, full_h x full_w; the
-// results land in d_bgr / d_depth (device, full >> halvings).  halvings = 0: a plain upload.
-static int stage_scaled(ea_problem *p, const uint8_t *bgr, const float *depth, int full_h, int full_w, int halvings,
-                        uint8_t *d_bgr, float *d_depth) {
-  const size_t np = (size_t)full_h * full_w;
-  if (halvings == 0) {
-    HIPCHK(hipMemcpyAsync(d_bgr, bgr, np * 3, hipMemcpyHostToDevice, nullptr));
-    if (depth) HIPCHK(hipMemcpyAsync(d_depth, depth, np * 4, hipMemcpyHostToDevice, nullptr));
-    return EA_OK;
-  }
-  // stage: [bgr full | depth full | bgr half | depth half] (the ping-pong partner of the full-size pair)
-  const size_t need = np * 3 + np * 4 + np / 4 * 3 + np / 4 * 4 + 1024;
-  if (p->stage_bytes < need) {
-    if (p->stage) { cached_free(p->stage); p->stage = nullptr; p->stage_bytes = 0; }
-    HIPCHK(cached_malloc(reinterpret_cast<void **>(&p->stage), need, p->device));
-    p->stage_bytes = need;
-  }
-  WsCarver st{p->stage};
-  uint8_t *bgr_a = st.take<uint8_t>(np * 3), *bgr_b = nullptr;
-  float *dep_a = st.take<float>(np), *dep_b = nullptr;
-  bgr_b = st.take<uint8_t>(np / 4 * 3);
-  dep_b = st.take<float>(np / 4);
-  HIPCHK(hipMemcpyAsync(bgr_a, bgr, np * 3, hipMemcpyHostToDevice, nullptr));
-  if (depth) HIPCHK(hipMemcpyAsync(dep_a, depth, np * 4, hipMemcpyHostToDevice, nullptr));
-  int h = full_h, w = full_w;
-  for (int k = 0; k < halvings; ++k) {
-    const bool last = k == halvings - 1;
-    uint8_t *bo = last ? d_bgr : bgr_b;
-    float *dp = last ? d_depth : dep_b;
-    HIPCHK(launch_resize_half_bgr8(bgr_a, h, w, bo, nullptr));
-    if (depth) HIPCHK(launch_resize_half_f32(dep_a, h, w, dp, /*nan_to_zero=*/k == 0 ? 1 : 0, nullptr));
-    std::swap(bgr_a, bgr_b); std::swap(dep_a, dep_b);
-    h /= 2; w /= 2;
-  }
-  return EA_OK;
-}
-
-static int check_scaled_args(int height, int width, int halvings) {
-  if (halvings < 0 || halvings > 8) return fail(EA_ERR_INVALID_ARG, "halvings out of range");
-  if ((height % (1 << halvings)) != 0 || (width % (1 << halvings)) != 0)
-    return fail(EA_ERR_INVALID_ARG, "frame extent must be divisible by 2^halvings");
-  return EA_OK;
-}
-
-// SolveEA::setRefFrame (src/SolveEA.cpp:29-82): every edge pixel, depth CV_32F in metres, Z == 0 -> 1.0
-extern "C" int ea_problem_set_ref_frame_ros_scaled(ea_problem *p, const uint8_t *bgr, const float *depth, int full_height,
-                                                   int full_width, int halvings, double threshold1, double threshold2) {
-  int rc = check_frame_args(p, bgr, full_height, full_width);
-  if (rc != EA_OK) return rc;
-  if (!depth) return fail(EA_ERR_INVALID_ARG, "NULL argument");
-  rc = check_scaled_args(full_height, full_width, halvings);
-  if (rc != EA_OK) return rc;
-  int lo, hi;
-  rc = ros_thresholds(threshold1, threshold2, &lo, &hi);
-  if (rc != EA_OK) return rc;
-  const int height = full_height >> halvings, width = full_width >> halvings;
-  if (height < 3 || width < 3) return fail(EA_ERR_INVALID_ARG, "image extent out of range");
-  HIPCHK(hipSetDevice(p->device));
-  rc = ensure_ws(p, frame_ws_bytes(height, width));
-  if (rc != EA_OK) return rc;
-  const size_t np = (size_t)height * width;
-  WsCarver ws{p->ws};
-  uint8_t *d_bgr = ws.take<uint8_t>(np * 3);
-  float *d_depth = ws.take<float>(np);
-  const int nblocks = (int)((np + 1023) / 1024);
-  int *d_counts = ws.take<int>(nblocks + 1);
-  int *d_total = d_counts + nblocks;
-  rc = stage_scaled(p, bgr, depth, full_height, full_width, halvings, d_bgr, d_depth);
-  if (rc != EA_OK) return rc;
-  uint8_t *d_edges, *d_inv;
-  rc = run_canny(ws, d_bgr, nullptr, height, width, lo, hi, &d_edges, &d_inv, nullptr, /*l2_bgr=*/1);
-  if (rc != EA_OK) return rc;
-  HIPCHK(launch_edge_count_scan(d_edges, nullptr, height, width, 0, d_counts, d_total, nullptr));
-  int total = 0;
-  HIPCHK(hipMemcpy(&total, d_total, sizeof(int), hipMemcpyDeviceToHost));
-  p->version++;
-  rc = reserve_points(p, total);
-  if (rc != EA_OK) return rc;
-  if (total > 0) {
-    HIPCHK(launch_edge_scatter_ros(p->dtype, d_edges, d_depth, height, width, d_counts, p->cam.fx, p->cam.fy, p->cam.cx,
-                                   p->cam.cy, p->d_x, p->d_y, p->d_z, total, nullptr));
-    HIPCHK(hipDeviceSynchronize());
-  }
-  p->n = total;
-  return EA_OK;
-}
-
-extern "C" int ea_problem_set_ref_frame_ros(ea_problem *p, const uint8_t *bgr, const float *depth, int height, int width,
-                                            double threshold1, double threshold2) {
-  return ea_problem_set_ref_frame_ros_scaled(p, bgr, depth, height, width, 0, threshold1, threshold2);
-}
-
-// SolveEA::setNowFrame (src/SolveEA.cpp:86-119): Canny -> 255 - edges -> distanceTransform(L2, DIST_MASK_PRECISE) ->
-// normalize to [0, 255].  An image without a single edge has no defined result upstream either: EA_ERR_STATE.
-static int now_frame_ros_impl(ea_problem *p, const uint8_t *bgr, int full_height, int full_width, int halvings,
-                              double threshold1, double threshold2, uint8_t *edges_out, float *dt_out) {
-  int rc = check_frame_args(p, bgr, full_height, full_width);
-  if (rc != EA_OK) return rc;
-  rc = check_scaled_args(full_height, full_width, halvings);
-  if (rc != EA_OK) return rc;
-  int lo, hi;
-  rc = ros_thresholds(threshold1, threshold2, &lo, &hi);
-  if (rc != EA_OK) return rc;
-  const int height = full_height >> halvings, width = full_width >> halvings;
-  if (height < 3 || width < 3) return fail(EA_ERR_INVALID_ARG, "image extent out of range");
-  HIPCHK(hipSetDevice(p->device));
-  rc = ensure_ws(p, frame_ws_bytes(height, width));
-  if (rc != EA_OK) return rc;
-  const size_t np = (size_t)height * width;
-  WsCarver ws{p->ws};
-  uint8_t *d_bgr = ws.take<uint8_t>(np * 3);
-  const int nblocks = (int)((np + 1023) / 1024);
-  int *d_counts = ws.take<int>(nblocks + 1);
-  rc = stage_scaled(p, bgr, nullptr, full_height, full_width, halvings, d_bgr, nullptr);
-  if (rc != EA_OK) return rc;
-  uint8_t *d_edges, *d_inv;
-  rc = run_canny(ws, d_bgr, nullptr, height, width, lo, hi, &d_edges, &d_inv, nullptr, /*l2_bgr=*/1);
-  if (rc != EA_OK) return rc;
-  HIPCHK(launch_edge_count_scan(d_edges, nullptr, height, width, 0, d_counts, d_counts + nblocks, nullptr));
-  int total = 0;
-  HIPCHK(hipMemcpy(&total, d_counts + nblocks, sizeof(int), hipMemcpyDeviceToHost));
-  if (total == 0) return fail(EA_ERR_STATE, "no edge in the frame: the exact distance transform is undefined");
-  int *d_dist;
-  float *d_plain;
-  rc = dt_from_mask(p, ws, d_inv, height, width, 1, 0.0, 255.0, &d_dist, &d_plain, /*precise=*/true);
-  if (rc != EA_OK) return rc;
-  if (edges_out) HIPCHK(hipMemcpy(edges_out, d_edges, np, hipMemcpyDeviceToHost));
-  if (dt_out) HIPCHK(hipMemcpy(dt_out, d_plain, np * 4, hipMemcpyDeviceToHost));
-  return EA_OK;
-}
-
-extern "C" int ea_problem_debug_now_frame_ros(ea_problem *p, const uint8_t *bgr, int height, int width, double threshold1,
-                                              double threshold2, uint8_t *edges_out, float *dt_out) {
-  return now_frame_ros_impl(p, bgr, height, width, 0, threshold1, threshold2, edges_out, dt_out);
-}
-
-extern "C" int ea_problem_set_now_frame_ros(ea_problem *p, const uint8_t *bgr, int height, int width, double threshold1,
-                                            double threshold2) {
-  return now_frame_ros_impl(p, bgr, height, width, 0, threshold1, threshold2, nullptr, nullptr);
-}
-
-extern "C" int ea_problem_set_now_frame_ros_scaled(ea_problem *p, const uint8_t *bgr, int full_height, int full_width,
-                                                   int halvings, double threshold1, double threshold2) {
-  return now_frame_ros_impl(p, bgr, full_height, full_width, halvings, threshold1, threshold2, nullptr, nullptr);
-}
-
-// The half-resolution step by itself (host in, host out) for parity checks and for callers that build pyramid levels of
-// their own: kind 0 = bgr8 (height x width x 3 bytes), 1 = float32 with NaN -> 0 first (the depth callback, src/ea.cpp:56-62),
-// 2 = float32 as is.  dst: (height / 2) x (width / 2) of the same element type.
-extern "C" int ea_resize_half(int device, int kind, const void *src, int height, int width, void *dst) {
-  if (!src || !dst) return fail(EA_ERR_INVALID_ARG, "NULL argument");
-  if (kind < 0 || kind > 2) return fail(EA_ERR_INVALID_ARG, "kind must be 0 (bgr8), 1 (float32, NaN -> 0) or 2 (float32)");
-  if (height < 2 || width < 2 || (height & 1) || (width & 1) || (int64_t)height * width > 0x3fffffff)
-    return fail(EA_ERR_INVALID_ARG, "frame extent must be even and in range");
-  int rc = check_device(device);
-  if (rc != EA_OK) return rc;
-  HIPCHK(hipSetDevice(device));
-  const size_t np = (size_t)height * width, es = kind == 0 ? 3 : 4;
-  DevBuf a, b;
-  HIPCHK(cached_malloc(&a.p, np * es, device));
-  HIPCHK(cached_malloc(&b.p, np / 4 * es, device));
-  HIPCHK(hipMemcpy(a.p, src, np * es, hipMemcpyHostToDevice));
-  if (kind == 0) HIPCHK(launch_resize_half_bgr8(a.as<uint8_t>(), height, width, b.as<uint8_t>(), nullptr));
-  else HIPCHK(launch_resize_half_f32(a.as<float>(), height, width, b.as<float>(), kind == 1 ? 1 : 0, nullptr));
-  HIPCHK(hipMemcpy(dst, b.p, np / 4 * es, hipMemcpyDeviceToHost));
-  return EA_OK;
-}
-
-extern "C" int ea_problem_set_now_frame_canny(ea_problem *p, const uint8_t *bgr, const uint8_t *mask, int height, int width,
-                                              double low_threshold, double high_threshold, int normalize, double norm_lo,
-                                              double norm_hi) {
-  return now_frame_canny(p, bgr, mask, height, width, low_threshold, high_threshold, normalize, norm_lo, norm_hi, nullptr,
-                         nullptr, nullptr, nullptr);
-}
-
-extern "C" int ea_problem_debug_now_frame_canny(ea_problem *p, const uint8_t *bgr, const uint8_t *mask, int height,
-                                                int width, double low_threshold, double high_threshold, int normalize,
-                                                double norm_lo, double norm_hi, uint8_t *edges_out,
-                                                int32_t *chamfer_fix_out, float *dt_out, int *hysteresis_launches) {
-  return now_frame_canny(p, bgr, mask, height, width, low_threshold, high_threshold, normalize, norm_lo, norm_hi, edges_out,
-                         chamfer_fix_out, dt_out, hysteresis_launches);
-}
-
-extern "C" int ea_problem_set_now_frame(ea_problem *p, const uint8_t *bgr, int height, int width, int threshold,
-                                        int median, int normalize) {
-  if (!p || !bgr) return fail(EA_ERR_INVALID_ARG, "NULL argument");
-  if (height < 3 || width < 3 || height > 32768 || width > 32768) return fail(EA_ERR_INVALID_ARG, "image extent out of range");
-  HIPCHK(hipSetDevice(p->device));
-  int rc = ensure_ws(p, frame_ws_bytes(height, width));
-  if (rc != EA_OK) return rc;
-  WsCarver ws{p->ws};
-  uint8_t *d_bgr = ws.take<uint8_t>((size_t)height * width * 3);
-  HIPCHK(hipMemcpyAsync(d_bgr, bgr, (size_t)height * width * 3, hipMemcpyHostToDevice, nullptr));
-  rc = run_dt(p, ws, d_bgr, height, width, threshold, median, normalize, nullptr, nullptr, nullptr, nullptr);
-  if (rc == EA_OK) { p->ws_now_kind = 1; p->ws_now_h = height; p->ws_now_w = width; }
-  return rc;
-}
-
-// stages of the DT producer for parity checks: any output may be NULL
-extern "C" int ea_problem_debug_now_frame(ea_problem *p, const uint8_t *bgr, int height, int width, int threshold,
-                                          int median, int normalize, uint8_t *lap_out, uint8_t *mask_out,
-                                          int32_t *chamfer_fix_out, float *dt_out) {
-  if (!p || !bgr) return fail(EA_ERR_INVALID_ARG, "NULL argument");
-  if (height < 3 || width < 3 || height > 32768 || width > 32768) return fail(EA_ERR_INVALID_ARG, "image extent out of range");
-  HIPCHK(hipSetDevice(p->device));
-  int rc = ensure_ws(p, frame_ws_bytes(height, width));
-  if (rc != EA_OK) return rc;
-  WsCarver ws{p->ws};
-  const size_t np = (size_t)height * width;
-  uint8_t *d_bgr = ws.take<uint8_t>(np * 3);
-  HIPCHK(hipMemcpyAsync(d_bgr, bgr, np * 3, hipMemcpyHostToDevice, nullptr));
-  uint8_t *d_lap, *d_mask;
-  int *d_dist;
-  float *d_plain;
-  rc = run_dt(p, ws, d_bgr, height, width, threshold, median, normalize, &d_lap, &d_mask, &d_dist, &d_plain);
-  if (rc != EA_OK) return rc;
-  if (lap_out) HIPCHK(hipMemcpy(lap_out, d_lap, np, hipMemcpyDeviceToHost));
-  if (mask_out) HIPCHK(hipMemcpy(mask_out, d_mask, np, hipMemcpyDeviceToHost));
-  if (chamfer_fix_out) HIPCHK(hipMemcpy(chamfer_fix_out, d_dist, np * 4, hipMemcpyDeviceToHost));
-  if (dt_out) HIPCHK(hipMemcpy(dt_out, d_plain, np * 4, hipMemcpyDeviceToHost));
-  return EA_OK;
-}
-
-// read back what the problem holds in HBM: points as n x 3 doubles, DT as H x W doubles ([v][u])
-extern "C" int ea_problem_get_points(ea_problem *p, double *xyz, int64_t capacity) {
-  if (!p || (!xyz && p->n > 0)) return fail(EA_ERR_INVALID_ARG, "NULL argument");
-  if (capacity < p->n) return fail(EA_ERR_INVALID_ARG, "capacity smaller than the number of points");
-  if (p->n == 0) return EA_OK;
-  HIPCHK(hipSetDevice(p->device));
-  const size_t n = (size_t)p->n, esz = p->dtype == EA_F32 ? 4 : 8;
-  std::vector<unsigned char> buf(3 * n * esz);
-  HIPCHK(hipMemcpy(buf.data(), p->d_x, n * esz, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(buf.data() + n * esz, p->d_y, n * esz, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(buf.data() + 2 * n * esz, p->d_z, n * esz, hipMemcpyDeviceToHost));
-  const int32_t *ord = p->order.empty() ? nullptr : p->order.data();
-  for (int c = 0; c < 3; ++c)
-    for (size_t i = 0; i < n; ++i)
-      xyz[3 * (ord ? (size_t)ord[i] : i) + c] = p->dtype == EA_F32 ? (double)reinterpret_cast<float *>(buf.data())[c * n + i]
-                                                                  : reinterpret_cast<double *>(buf.data())[c * n + i];
-  return EA_OK;
-}
-
-extern "C" int ea_problem_get_dt(ea_problem *p, double *image, int *height, int *width) {
-  if (!p) return fail(EA_ERR_INVALID_ARG, "NULL argument");
-  if (height) *height = p->H;
-  if (width) *width = p->W;
-  if (!image) return EA_OK;
-  if (!p->d_dt) return fail(EA_ERR_STATE, "distance-transform image not set");
-  HIPCHK(hipSetDevice(p->device));
-  const size_t esz = p->dtype == EA_F32 ? 4 : 8;
-  const size_t rows = (size_t)p->H + 2 * kImagePad;
-  std::vector<unsigned char> buf((size_t)p->pitch * rows * esz);
-  HIPCHK(hipMemcpy(buf.data(), p->d_dt, buf.size(), hipMemcpyDeviceToHost));
-  for (int v = 0; v < p->H; ++v)
-    for (int u = 0; u < p->W; ++u) {
-      const size_t idx = (size_t)(v + kImagePad) * p->pitch + (u + kImagePad);
-      image[(size_t)v * p->W + u] = p->dtype == EA_F32 ? (double)reinterpret_cast<float *>(buf.data())[idx]
-                                                       : reinterpret_cast<double *>(buf.data())[idx];
-    }
   return EA_OK;
 }
 

@@ -1,0 +1,96 @@
+// ea_capi_internal.h — what the library's host translation units share behind include/ea_hip.h: ea_capi.hip (problems,
+// batches, solves; it defines everything declared here) and ea_frames.hip (frame producers, tracker).  Not for ea_comm.hip,
+// which sees problems and batches through the C-ABI and ea_launch.h only.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include <string>
+#include <vector>
+
+#include "../../include/ea_hip.h"
+#include "ea_prior.h"
+#include "ea_types.h"
+
+struct ea_problem {
+  int device = 0;
+  int dtype = EA_F64;
+  ea_camera cam{};
+  int loss_kind = EA_LOSS_CAUCHY;  // the reference's `new CauchyLoss(1.)`
+  double loss_a = 1.0;
+  double z_guard = 0.01, z_eps = 0.0;
+  int rot_transposed = 0;
+  // residual variants (utils.h:102-421)
+  int variant = 0;                       // bit 0 distortion, bit 1 second camera
+  double dist[5] = {0, 0, 0, 0, 0};      // k1, k2, p1, p2, k3
+  double T12[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  double T12inv[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  std::vector<ea_problem *> terms;       // further residual families sharing this problem's pose
+  ea::PriorDesc prior = {};                  // NormalPriors on q / t (ea_problem_set_normal_prior; ea_prior.h)
+  int term_of = 0;                       // how many problems hold this one as a term (a term carries no prior)
+  int held = 0;                          // tangent coordinates held constant, bit i of [delta | t] (ea_problem_set_constant_parameters)
+  int64_t n = 0;
+  void *d_x = nullptr, *d_y = nullptr, *d_z = nullptr;
+  bool own_points = false;
+  // storage order of the points in HBM (ea_problem_set_point_order): order[i] = caller's index of stored point i;
+  // empty = the caller's order
+  int order_tile = -1, order_tile_used = 0;
+  std::vector<int32_t> order;
+  void *d_dt = nullptr;
+  size_t dt_cap = 0;   // bytes allocated behind d_dt: a frame of the same size reuses the allocation
+  // fp64 problems: the float32 mirror of the image (same padded layout and pitch in texels) and whether it holds every
+  // value exactly -- then the plain fp64 kernels read it instead (ProblemDesc::dt32): one 16-byte load per stencil row
+  float *d_dt32 = nullptr;
+  size_t dt32_cap = 0;
+  bool dt32_exact = false;
+  size_t pts_cap = 0;  // bytes allocated behind each of d_x, d_y, d_z when own_points (hipFree / hipMalloc per frame
+                       // cost more than the whole pre-processing of a 640x480 frame)
+  int W = 0, H = 0, pitch = 0;
+  uint64_t version = 1;  // bumped by every setter; batches rebuild their descriptors lazily
+  ea_batch *self = nullptr;
+  hipStream_t stream = nullptr;
+  // scratch for the frame pre-processing kernels (grown on demand, reused across frames)
+  unsigned char *ws = nullptr;
+  size_t ws_bytes = 0;
+  // full-resolution frames on their way to a half-resolution level (ea_problem_set_*_frame_ros_scaled)
+  unsigned char *stage = nullptr;
+  size_t stage_bytes = 0;
+  // what the last producer call left in the workspace: 1 = set_now_frame (Laplacian strength), 2 = set_now_frame_canny
+  // (edge map, no mask), 0 = nothing reusable; with the frame's extent.  The tracker extracts the same frame's edge
+  // points from it instead of uploading and filtering the frame a second time.
+  int ws_now_kind = 0, ws_now_h = 0, ws_now_w = 0;
+};
+
+namespace ea {
+
+// the thread-local message behind ea_last_error(); returns `code`
+int fail(int code, const std::string &msg);
+
+#define HIPCHK(expr)                                                                          \
+  do {                                                                                        \
+    hipError_t e_ = (expr);                                                                   \
+    if (e_ != hipSuccess)                                                                     \
+      return fail(e_ == hipErrorNoDevice ? EA_ERR_NO_DEVICE : EA_ERR_HIP,                     \
+                  std::string(#expr) + ": " + hipGetErrorString(e_));                        \
+  } while (0)
+
+int check_device(int device);
+
+// the resource cache: freed device blocks are kept and handed out again (ea_capi.hip has the rules)
+hipError_t cached_malloc(void **out, size_t bytes, int device);
+void cached_free(void *p);
+// scope guard for a temporary device block, so that an early HIPCHK return frees it
+struct DevBuf {
+  void *p = nullptr;
+  ~DevBuf() { if (p) cached_free(p); }  // (blocks that did not come from the cache fall through to hipFree)
+  template <typename U> U *as() const { return static_cast<U *>(p); }
+};
+
+// room for n points in arrays the problem owns; leaves the problem without points (n = 0)
+int reserve_points(ea_problem *p, int64_t n);
+// the problem's padded W x H image (and its float32 mirror for fp64 problems), reusing an allocation that fits
+int alloc_dt(ea_problem *p, int W, int H);
+int check_cov_options(const ea_covariance_options *o);
+
+}  // namespace ea

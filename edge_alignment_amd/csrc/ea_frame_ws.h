@@ -1,0 +1,87 @@
+// ea_frame_ws.h — where every buffer of the frame producers (ea_frames.hip) lies in a problem's workspace, as one pure
+// function of the frame's extent that the host tests without a device (tests/frame_ws_host_shim.cpp).  Every producer and
+// the tracker's ref_points_begin name the regions they use; nobody carves the workspace by position, so a buffer added here
+// moves nothing a later call looks for, and ensure_ws takes the size to allocate from the same function.
+//
+// Regions of an H x W frame (np = H * W), each starting 256-byte aligned, laid out one behind the other without sharing:
+//
+//   region   bytes                  written / read by (ea_launch.h)
+//   bgr      3 np                   the uploaded colour frame; launch_edge_strength, launch_canny, launch_resize_half_bgr8 (its target)
+//   depth    4 np                   the depth frame, uint16 (2 np used) or float: launch_edge_count_scan, launch_edge_scatter[_ros]
+//   keep     np                     the caller's mask: launch_gate_by_mask, launch_canny (keep)
+//   gray     np                     launch_edge_strength, launch_canny
+//   lap      np                     launch_edge_strength -> launch_threshold_median, launch_edge_count_scan, launch_edge_scatter
+//   mask     np                     launch_threshold_median -> launch_chamfer
+//   mag      4 np                   launch_canny (ints)
+//   dir, label, edges, inv   np     launch_canny; edges -> launch_edge_count_scan / _scatter[_ros], inv -> launch_chamfer
+//   changed  16 ints                launch_canny: one change flag per launch of a hysteresis batch (8 used)
+//   counts   (nblocks + 1) ints     launch_edge_count_scan / launch_edge_scatter[_ros]: per-block counts, nblocks =
+//                                   ceil(np / 1024), and the total behind them
+//   G, dist  4 np                   launch_chamfer (ints; dist doubles as the float32 distance of the exact transform)
+//   scan     4 ceil(H / 32) W ints  launch_chamfer: segment ends and carries of the column pass
+//   plain    4 np                   launch_dt_store: the unpadded float image of the debug entry points
+//   minmax   2 words                launch_chamfer -> launch_dt_store
+//
+// The total: 31 np bytes of per-pixel regions; scan = 16 ceil(H / 32) W <= np / 2 + 16 W; counts = 4 (nblocks + 1) <=
+// np / 256 + 8; changed and minmax 72; and less than 256 bytes of rounding per region, 18 regions.  So
+//   frame_ws(H, W).total <= frame_ws_bound(H, W) = 32 np + 16 W + 19 * 256,
+// about 31.5 bytes per pixel (9.2 MiB for 640 x 480); for the largest frame any producer accepts (np <= 2^30) that is below
+// 2^36, far inside size_t.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+namespace ea {
+
+template <typename U> struct WsRegion {
+  size_t off = 0, bytes = 0;
+  template <typename V = U> V *at(unsigned char *base) const { return reinterpret_cast<V *>(base + off); }
+};
+
+struct FrameWs {
+  WsRegion<uint8_t> bgr, depth, keep, gray, lap, mask;
+  WsRegion<int> mag;
+  WsRegion<uint8_t> dir, label, edges, inv;
+  WsRegion<int> changed, counts, G, dist, scan;
+  WsRegion<float> plain;
+  WsRegion<unsigned int> minmax;
+  size_t total = 0;
+};
+
+// blocks of launch_edge_count_scan; the total lands in counts[frame_ws_blocks(H, W)]
+inline int frame_ws_blocks(int H, int W) { return (int)(((size_t)H * W + 1023) / 1024); }
+
+inline FrameWs frame_ws(int H, int W) {
+  const size_t np = (size_t)H * W;
+  FrameWs w;
+  size_t off = 0;
+  auto put = [&off](auto &r, size_t bytes) {
+    r.off = off;
+    r.bytes = bytes;
+    off = (off + bytes + 255) & ~(size_t)255;
+  };
+  put(w.bgr, 3 * np);
+  put(w.depth, 4 * np);
+  put(w.keep, np);
+  put(w.gray, np);
+  put(w.lap, np);
+  put(w.mask, np);
+  put(w.mag, 4 * np);
+  put(w.dir, np);
+  put(w.label, np);
+  put(w.edges, np);
+  put(w.inv, np);
+  put(w.changed, 16 * sizeof(int));
+  put(w.counts, ((size_t)frame_ws_blocks(H, W) + 1) * sizeof(int));
+  put(w.G, 4 * np);
+  put(w.dist, 4 * np);
+  put(w.scan, 4 * (size_t)((H + 31) / 32) * W * sizeof(int));
+  put(w.plain, 4 * np);
+  put(w.minmax, 2 * sizeof(unsigned int));
+  w.total = off;
+  return w;
+}
+
+inline size_t frame_ws_bound(int H, int W) { return 32 * (size_t)H * W + 16 * (size_t)W + 19 * 256; }
+
+}  // namespace ea

@@ -1,0 +1,700 @@
+// ea_frames.hip — the host side of everything that starts from raw frames: the frame producers behind
+// ea_problem_set_{ref,now}_frame* (raw images -> edge points / DT image through the kernels of ea_preprocess.hip, in a
+// workspace laid out by ea_frame_ws.h), ea_resize_half, the read-backs ea_problem_get_points / _get_dt, and the
+// frame-to-frame tracker ea_tracker_*.  Host code only: this file holds no kernel.
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstring>
+#include <new>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/ea_hip.h"
+#include "ea_capi_internal.h"
+#include "ea_frame_ws.h"
+#include "ea_launch.h"
+#include "ea_prior.h"
+#include "ea_types.h"
+
+using namespace ea;
+
+// ---- the reference frame's edge points out of the frame producers' workspace (the producers themselves: further down) ----
+
+// The edge points of a reference frame from the edge strength / edge map and the depth frame in the workspace, in two halves
+// so that the tracker can put the first -- depth upload and per-block edge counts, both asynchronous on the null stream -- in
+// front of the solve of the previous reference (which runs on the batch's own non-blocking stream and touches neither the
+// workspace nor the depth) and the second -- count read-back, compaction -- behind it.  The full producers
+// (ea_problem_set_ref_frame[_masked|_canny|_ros]) run the same two halves back to back (ref_points).
+// What the first half left in flight on the null stream, and what the second needs to know
+struct RefPointsJob {
+  bool started = false;
+  bool ros = false;                  // the ROS scatter: float depth in metres, every edge pixel a point
+  int threshold = 0;                 // a pixel is an edge where its strength exceeds this
+  const uint8_t *d_edges = nullptr;  // Laplacian strength or Canny edge map
+  const void *d_depth = nullptr;     // uint16, float for the ROS scatter
+  int *d_counts = nullptr, *d_total = nullptr;
+};
+
+// first half: per-block counts of the pixels of `edges` that become points, and their total.  The depth frame is in the
+// workspace already (or on its way there on the null stream).
+static int ref_points_count(ea_problem *p, const FrameWs &ws, const WsRegion<uint8_t> &edges, bool ros, int height, int width,
+                            int threshold, RefPointsJob *job) {
+  job->ros = ros;
+  job->threshold = threshold;
+  job->d_edges = edges.at(p->ws);
+  job->d_depth = ws.depth.at(p->ws);
+  job->d_counts = ws.counts.at(p->ws);
+  job->d_total = job->d_counts + frame_ws_blocks(height, width);
+  // (the ROS flavour keeps every edge pixel: no depth test)
+  HIPCHK(launch_edge_count_scan(job->d_edges, ros ? nullptr : static_cast<const uint16_t *>(job->d_depth), height, width, threshold,
+                                job->d_counts, job->d_total, nullptr));
+  job->started = true;
+  return EA_OK;
+}
+
+// a count the device has just produced (waits for the null stream)
+static int read_count(const int *d_count, int *count) {
+  HIPCHK(hipMemcpy(count, d_count, sizeof(int), hipMemcpyDeviceToHost));
+  return EA_OK;
+}
+
+// second half: the points themselves, compacted in raster order and back-projected
+static int ref_points_finish(ea_problem *p, const RefPointsJob &job, int height, int width, double z_scaling) {
+  if (!job.started) return EA_ERR_STATE;
+  int total = 0;
+  int rc = read_count(job.d_total, &total);
+  if (rc != EA_OK) return rc;
+  p->version++;
+  rc = reserve_points(p, total);
+  if (rc != EA_OK) return rc;
+  if (total > 0) {
+    if (job.ros)
+      HIPCHK(launch_edge_scatter_ros(p->dtype, job.d_edges, static_cast<const float *>(job.d_depth), height, width, job.d_counts,
+                                     p->cam.fx, p->cam.fy, p->cam.cx, p->cam.cy, p->d_x, p->d_y, p->d_z, total, nullptr));
+    else
+      HIPCHK(launch_edge_scatter(p->dtype, job.d_edges, static_cast<const uint16_t *>(job.d_depth), height, width, job.threshold,
+                                 job.d_counts, p->cam.fx, p->cam.fy, p->cam.cx, p->cam.cy, z_scaling, p->d_x, p->d_y, p->d_z, total,
+                                 nullptr));
+    HIPCHK(hipDeviceSynchronize());
+  }
+  p->n = total;
+  return EA_OK;
+}
+
+// both halves: the tail of every full reference producer
+static int ref_points(ea_problem *p, const FrameWs &ws, const WsRegion<uint8_t> &edges, bool ros, int height, int width,
+                      int threshold, double z_scaling) {
+  RefPointsJob job;
+  const int rc = ref_points_count(p, ws, edges, ros, height, width, threshold, &job);
+  return rc != EA_OK ? rc : ref_points_finish(p, job, height, width, z_scaling);
+}
+
+// The first half on what the last set_now_frame[_canny] call left in the workspace (kind 1: Laplacian strength in `lap`, 2:
+// the edge map in `edges`): only the depth frame goes up.  EA_ERR_STATE when the workspace does not hold that frame.
+static int ref_points_begin(ea_problem *p, int kind, const uint16_t *depth, int height, int width, int threshold, RefPointsJob *job) {
+  job->started = false;
+  if (p->ws_now_kind != kind || p->ws_now_h != height || p->ws_now_w != width) return EA_ERR_STATE;
+  HIPCHK(hipSetDevice(p->device));
+  const FrameWs ws = frame_ws(height, width);
+  p->ws_now_kind = 0;
+  HIPCHK(hipMemcpyAsync(ws.depth.at(p->ws), depth, (size_t)height * width * 2, hipMemcpyHostToDevice, nullptr));
+  return ref_points_count(p, ws, kind == 1 ? ws.lap : ws.edges, false, height, width, threshold, job);
+}
+
+// Edge points of the frame the last set_now_frame[_canny] call processed, from what that call left in the workspace
+// (Laplacian strength / Canny edge map): only the depth image goes up, no second upload or filtering of the colour
+// frame.  Same thresholds, same compaction and back-projection as ea_problem_set_ref_frame[_canny] => the same points.
+// Returns EA_ERR_STATE when the workspace does not hold that frame (the caller then takes the full path).
+static int ref_points_from_last_now(ea_problem *p, int kind, const uint16_t *depth, int height, int width, double z_scaling,
+                                    int threshold) {
+  RefPointsJob job;
+  int rc = ref_points_begin(p, kind, depth, height, width, threshold, &job);
+  if (rc != EA_OK) return rc;
+  return ref_points_finish(p, job, height, width, z_scaling);
+}
+
+// ---- frame-to-frame driver (the reference aligns one stored pair, src/ea.cpp:155-200) -------------
+// Every pushed frame is aligned against the previous one: its DT image is produced, the previous frame's edge points
+// are solved against it starting from the last relative pose (constant-velocity prior), then the new frame's edge
+// points become the reference.  All of it stays on the device; one ea_problem is reused.
+struct ea_tracker {
+  ea_problem *p = nullptr;
+  int flavour = 0;      // 0: get_aX / get_distance_transform, 1: Canny (get_aX_canny / get_distance_transform2)
+  int frames = 0;
+  double q[4] = {1, 0, 0, 0}, t[3] = {0, 0, 0};
+  // ea_tracker_set_covariance: the covariance of every aligned frame at the pose it returns
+  bool cov_on = false, cov_valid = false;
+  ea_covariance_options cov_opt{};
+  ea_covariance cov_last{};
+  // ea_tracker_set_motion_prior: NormalPriors centred on each solve's start pose, A = I / sigma (0 = that block off)
+  double sigma_rot = 0.0, sigma_trans = 0.0;
+  bool motion_set = false;  // the problem carries priors this tracker installed: `installed` (a caller's later prior differs)
+  PriorDesc installed = {};
+};
+
+extern "C" int ea_tracker_create(ea_tracker **out, const ea_camera *cam, int dtype, int device, int flavour) {
+  if (!out) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (flavour != 0 && flavour != 1) return fail(EA_ERR_INVALID_ARG, "unknown pre-processing flavour");
+  ea_tracker *tr = new (std::nothrow) ea_tracker;
+  if (!tr) return fail(EA_ERR_ALLOC, "out of host memory");
+  const int rc = ea_problem_create(&tr->p, cam, dtype, device);
+  if (rc != EA_OK) { delete tr; return rc; }
+  tr->flavour = flavour;
+  *out = tr;
+  return EA_OK;
+}
+
+extern "C" void ea_tracker_destroy(ea_tracker *tr) {
+  if (!tr) return;
+  ea_problem_destroy(tr->p);
+  delete tr;
+}
+
+extern "C" ea_problem *ea_tracker_problem(ea_tracker *tr) { return tr ? tr->p : nullptr; }
+
+// q_rel, t_rel: pose of the previous frame in the new frame's coordinates (b_T_a with a = previous, b = new); identity
+// for the first frame.  aligned (nullable): 1 when a solve took place.  A failed solve keeps the prior for the next frame.
+extern "C" int ea_tracker_push_frame(ea_tracker *tr, const uint8_t *bgr, const uint16_t *depth, int height, int width,
+                                     double z_scaling, const ea_options *opt, double q_rel[4], double t_rel[3],
+                                     ea_summary *summary, int *aligned) {
+  if (!tr || !bgr || !depth || !q_rel || !t_rel) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  // every argument is checked before the tracker's problem is touched: a rejected call leaves the tracker as it was
+  if (!(z_scaling > 0.0)) return fail(EA_ERR_INVALID_ARG, "z_scaling must be > 0");
+  if (height < 1 || width < 1) return fail(EA_ERR_INVALID_ARG, "bad frame extent");
+  int rc = EA_OK;
+  if (aligned) *aligned = 0;
+  if (summary) std::memset(summary, 0, sizeof(*summary));
+  double q_new[4], t_new[3];
+  std::memcpy(q_new, tr->q, sizeof(q_new));
+  std::memcpy(t_new, tr->t, sizeof(t_new));
+  RefPointsJob job;
+  tr->cov_valid = false;
+  if (tr->frames > 0 && ea_problem_num_points(tr->p) > 0) {
+    rc = tr->flavour == 0 ? ea_problem_set_now_frame(tr->p, bgr, height, width, 35, 1, 1)
+                          : ea_problem_set_now_frame_canny(tr->p, bgr, nullptr, height, width, 30, 90, 1, 0.0, 1.0);
+    if (rc != EA_OK) return rc;
+    // the new frame's depth goes up and its edge pixels are counted WHILE the previous reference is solved against the image
+    // just produced (null stream beside the solve's non-blocking stream; neither touches what the other uses)
+    (void)ref_points_begin(tr->p, tr->flavour == 0 ? 1 : 2, depth, height, width, tr->flavour == 0 ? 35 : 0, &job);
+    double q[4], t[3];
+    std::memcpy(q, tr->q, sizeof(q));
+    std::memcpy(t, tr->t, sizeof(t));
+    if (tr->sigma_rot > 0.0 || tr->sigma_trans > 0.0) {
+      // the motion prior: centred on the constant-velocity prediction the solve starts from (replaces the caller's priors)
+      double Aq[16] = {0}, At[9] = {0};
+      for (int i = 0; i < 4; ++i) Aq[5 * i] = tr->sigma_rot > 0.0 ? 1.0 / tr->sigma_rot : 0.0;
+      for (int i = 0; i < 3; ++i) At[4 * i] = tr->sigma_trans > 0.0 ? 1.0 / tr->sigma_trans : 0.0;
+      rc = ea_problem_set_normal_prior(tr->p, 0, tr->sigma_rot > 0.0 ? Aq : nullptr, 4, q);
+      if (rc == EA_OK) rc = ea_problem_set_normal_prior(tr->p, 1, tr->sigma_trans > 0.0 ? At : nullptr, 3, t);
+      if (rc != EA_OK) {
+        if (job.started) (void)hipDeviceSynchronize();
+        return rc;
+      }
+      tr->motion_set = true;
+      tr->installed = tr->p->prior;
+    }
+    ea_summary s;
+    rc = ea_solve(tr->p, opt, q, t, &s);
+    if (rc != EA_OK) {
+      if (job.started) (void)hipDeviceSynchronize();  // (nothing of this frame may stay in flight behind a failed push)
+      return rc;
+    }
+    if (s.termination != EA_FAILURE) {
+      std::memcpy(q_new, q, sizeof(q));
+      std::memcpy(t_new, t, sizeof(t));
+    }
+    if (tr->cov_on) {
+      // The solve's points and DT image are still the problem's: ea_problem_covariance returns only once its results have
+      // landed, i.e. once its evaluation on the batch's stream has read them, and ref_points_finish -- the only step that
+      // overwrites the points -- is enqueued on the null stream after that.  ref_points_begin, already in flight on the null
+      // stream, writes nothing but the workspace of the frame producers, which the evaluation does not read.
+      std::memset(&tr->cov_last, 0, sizeof(tr->cov_last));
+      if (s.termination != EA_FAILURE) {
+        rc = ea_problem_covariance(tr->p, q, t, &tr->cov_opt, &tr->cov_last);
+        if (rc != EA_OK) {
+          if (job.started) (void)hipDeviceSynchronize();
+          return rc;
+        }
+      } else {
+        tr->cov_last.why = 4;  // no pose to take the covariance at
+      }
+      tr->cov_valid = true;
+    }
+    if (summary) *summary = s;
+    if (aligned) *aligned = 1;
+  }
+  // the frame's edge strength / edge map is still in the workspace when it has just been the "now" frame
+  rc = job.started ? ref_points_finish(tr->p, job, height, width, z_scaling)
+                   : ref_points_from_last_now(tr->p, tr->flavour == 0 ? 1 : 2, depth, height, width, z_scaling, tr->flavour == 0 ? 35 : 0);
+  if (rc == EA_ERR_STATE)
+    rc = tr->flavour == 0 ? ea_problem_set_ref_frame(tr->p, bgr, depth, height, width, z_scaling, 35)
+                          : ea_problem_set_ref_frame_canny(tr->p, bgr, depth, height, width, z_scaling, 30, 90);
+  if (rc != EA_OK) {
+    // the DT image is the new frame's but no reference came out of it: drop the stale reference so that the next push
+    // starts a fresh chain instead of aligning frame k-1's points against frame k+2 from an advanced prior
+    (void)reserve_points(tr->p, 0);
+    tr->p->version++;
+    tr->frames = 0;
+    return rc;
+  }
+  // prior and frame count advance only with the new reference in place
+  std::memcpy(tr->q, q_new, sizeof(q_new));
+  std::memcpy(tr->t, t_new, sizeof(t_new));
+  std::memcpy(q_rel, tr->q, sizeof(tr->q));
+  std::memcpy(t_rel, tr->t, sizeof(tr->t));
+  tr->frames += 1;
+  return EA_OK;
+}
+
+extern "C" int ea_tracker_set_covariance(ea_tracker *tr, const ea_covariance_options *o) {
+  if (!tr) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (o) {
+    const int rc = check_cov_options(o);
+    if (rc != EA_OK) return rc;
+    tr->cov_opt = *o;
+  }
+  tr->cov_on = o != nullptr;
+  tr->cov_valid = false;
+  return EA_OK;
+}
+
+extern "C" int ea_tracker_set_motion_prior(ea_tracker *tr, double sigma_rot, double sigma_trans) {
+  if (!tr) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (!(sigma_rot >= 0.0 && sigma_rot <= DBL_MAX) || !(sigma_trans >= 0.0 && sigma_trans <= DBL_MAX))
+    return fail(EA_ERR_INVALID_ARG, "sigmas must be finite and >= 0");
+  if (sigma_rot == 0.0 && sigma_trans == 0.0 && tr->motion_set) {
+    // off again: a block still holding the prior this tracker installed is cleared; one the caller has set since is kept
+    const PriorDesc &cur = tr->p->prior, &ins = tr->installed;
+    if (cur.has_q && ins.has_q && std::memcmp(cur.Hq, ins.Hq, sizeof(cur.Hq)) == 0 && std::memcmp(cur.bq, ins.bq, sizeof(cur.bq)) == 0)
+      (void)ea_problem_set_normal_prior(tr->p, 0, nullptr, 0, nullptr);
+    if (cur.has_t && ins.has_t && std::memcmp(cur.Ht, ins.Ht, sizeof(cur.Ht)) == 0 && std::memcmp(cur.bt, ins.bt, sizeof(cur.bt)) == 0)
+      (void)ea_problem_set_normal_prior(tr->p, 1, nullptr, 0, nullptr);
+    tr->motion_set = false;
+  }
+  tr->sigma_rot = sigma_rot;
+  tr->sigma_trans = sigma_trans;
+  return EA_OK;
+}
+
+extern "C" int ea_tracker_last_covariance(ea_tracker *tr, ea_covariance *out) {
+  if (!tr || !out) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (!tr->cov_on) return fail(EA_ERR_STATE, "covariance is off (ea_tracker_set_covariance)");
+  if (!tr->cov_valid) return fail(EA_ERR_STATE, "the last push did not align a frame");
+  *out = tr->cov_last;
+  return EA_OK;
+}
+
+// ---- frame producers: raw images -> edge points / DT image, on the device -------
+
+static int ensure_ws(ea_problem *p, size_t bytes) {
+  p->ws_now_kind = 0;  // every producer starts by calling this: whatever the workspace held is about to be overwritten
+  if (p->ws_bytes >= bytes) return EA_OK;
+  if (p->ws) { cached_free(p->ws); p->ws = nullptr; p->ws_bytes = 0; }
+  HIPCHK(cached_malloc(reinterpret_cast<void **>(&p->ws), bytes, p->device));
+  p->ws_bytes = bytes;
+  return EA_OK;
+}
+
+// What every producer starts with once its arguments are checked: the problem's device, a workspace large enough for a
+// height x width frame laid out by name (ea_frame_ws.h), and the colour frame on its way into `bgr` (bgr == nullptr: the
+// caller brings it there itself, stage_scaled)
+static int frame_begin(ea_problem *p, const uint8_t *bgr, int height, int width, FrameWs *ws) {
+  HIPCHK(hipSetDevice(p->device));
+  *ws = frame_ws(height, width);
+  const int rc = ensure_ws(p, ws->total);
+  if (rc != EA_OK) return rc;
+  if (bgr) HIPCHK(hipMemcpyAsync(ws->bgr.at(p->ws), bgr, (size_t)height * width * 3, hipMemcpyHostToDevice, nullptr));
+  return EA_OK;
+}
+
+// a region of the workspace into a debug output of the caller's (nullable)
+template <typename U>
+static int read_region(ea_problem *p, const WsRegion<U> &r, size_t bytes, void *out) {
+  if (out) HIPCHK(hipMemcpy(out, r.at(p->ws), bytes, hipMemcpyDeviceToHost));
+  return EA_OK;
+}
+
+static int ref_frame_impl(ea_problem *p, const uint8_t *bgr, const uint8_t *mask, const uint16_t *depth, int height,
+                          int width, double z_scaling, int threshold) {
+  if (!p || !bgr || !depth) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (height < 3 || width < 3 || (int64_t)height * width > 0x3fffffff) return fail(EA_ERR_INVALID_ARG, "image extent out of range");
+  if (!(z_scaling > 0.0)) return fail(EA_ERR_INVALID_ARG, "z_scaling must be > 0");
+  FrameWs ws;
+  const int rc = frame_begin(p, bgr, height, width, &ws);
+  if (rc != EA_OK) return rc;
+  const size_t np = (size_t)height * width;
+  HIPCHK(hipMemcpyAsync(ws.depth.at(p->ws), depth, np * 2, hipMemcpyHostToDevice, nullptr));
+  HIPCHK(launch_edge_strength(ws.bgr.at(p->ws), height, width, ws.gray.at(p->ws), ws.lap.at(p->ws), nullptr));
+  if (mask) {
+    HIPCHK(hipMemcpyAsync(ws.keep.at(p->ws), mask, np, hipMemcpyHostToDevice, nullptr));
+    HIPCHK(launch_gate_by_mask(ws.lap.at(p->ws), ws.keep.at(p->ws), height, width, nullptr));
+  }
+  return ref_points(p, ws, ws.lap, false, height, width, threshold, z_scaling);
+}
+
+extern "C" int ea_problem_set_ref_frame(ea_problem *p, const uint8_t *bgr, const uint16_t *depth, int height, int width,
+                                        double z_scaling, int threshold) {
+  return ref_frame_impl(p, bgr, nullptr, depth, height, width, z_scaling, threshold);
+}
+
+// get_aX_mask (ref: utils.cpp:283-369, call sites standalone_edge_align.cpp:1039, :1081): also requires mask > 0
+extern "C" int ea_problem_set_ref_frame_masked(ea_problem *p, const uint8_t *bgr, const uint8_t *mask, const uint16_t *depth,
+                                               int height, int width, double z_scaling, int threshold) {
+  if (!mask) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  return ref_frame_impl(p, bgr, mask, depth, height, width, z_scaling, threshold);
+}
+
+// mask (0 = edge / DT source; the region `mask` or `inv`) -> chamfer DT in `dist` -> [normalise to [lo, hi]] -> the problem's
+// padded DT image, and the plain float image in `plain`
+static int dt_from_mask(ea_problem *p, const FrameWs &ws, const WsRegion<uint8_t> &mask, int height, int width, int normalize,
+                        double lo, double hi, bool precise = false) {
+  // the row pass stages one image row of column distances in LDS (4 bytes per pixel, 64 KB)
+  if (width > 16384) return fail(EA_ERR_INVALID_ARG, "frames wider than 16384 pixels are not supported by the DT producers");
+  int *d_dist = ws.dist.at(p->ws);  // doubles as the float32 distance when `precise`
+  float *d_dist_f32 = precise ? ws.dist.at<float>(p->ws) : nullptr;
+  unsigned int *d_minmax = ws.minmax.at(p->ws);
+  HIPCHK(launch_chamfer(mask.at(p->ws), height, width, ws.G.at(p->ws), ws.scan.at(p->ws), d_dist, d_dist_f32, d_minmax, nullptr));
+  {
+    int rc = alloc_dt(p, width, height);
+    if (rc != EA_OK) return rc;
+  }
+  HIPCHK(launch_dt_store(p->dtype, d_dist, d_dist_f32, height, width, d_minmax, normalize, lo, hi, p->d_dt, p->pitch,
+                         ws.plain.at(p->ws), p->d_dt32, nullptr));
+  HIPCHK(hipDeviceSynchronize());
+  p->dt32_exact = p->d_dt32 != nullptr;  // the producers compute the distance transform in float32, as OpenCV does
+  p->version++;
+  return EA_OK;
+}
+
+// `bgr` -> Laplacian strength in `lap` -> thresholded [median-filtered] `mask` -> dt_from_mask
+static int run_dt(ea_problem *p, const FrameWs &ws, int height, int width, int threshold, int median, int normalize) {
+  HIPCHK(launch_edge_strength(ws.bgr.at(p->ws), height, width, ws.gray.at(p->ws), ws.lap.at(p->ws), nullptr));
+  HIPCHK(launch_threshold_median(ws.lap.at(p->ws), height, width, threshold, median, ws.mask.at(p->ws), nullptr));
+  return dt_from_mask(p, ws, ws.mask, height, width, normalize, 0.0, 1.0);
+}
+
+// cv::Canny's integer thresholds (L1 magnitude): floor of the ordered pair.  NaN is refused; values beyond any magnitude an
+// 8-bit image can produce (|dx| + |dy| <= 2040) are clamped before the conversion, which is undefined for them otherwise.
+static int canny_thresholds(double t1, double t2, int *low, int *high) {
+  if (t1 != t1 || t2 != t2) return fail(EA_ERR_INVALID_ARG, "Canny threshold is NaN");
+  const double lo = std::min(t1, t2), hi = std::max(t1, t2);
+  *low = (int)std::floor(std::min(std::max(lo, -1e9), 1e9));
+  *high = (int)std::floor(std::min(std::max(hi, -1e9), 1e9));
+  return EA_OK;
+}
+
+// blur 3x3 -> gray -> Canny(low, high) [-> AND (keep > 1), `masked`]: edge map in `edges`, its inverse in `inv`
+static int run_canny(ea_problem *p, const FrameWs &ws, bool masked, int height, int width, int low, int high, int *rounds_out,
+                     int l2_bgr = 0) {
+  unsigned char *b = p->ws;
+  HIPCHK(launch_canny(ws.bgr.at(b), height, width, low, high, l2_bgr, masked ? ws.keep.at(b) : nullptr, ws.gray.at(b), ws.mag.at(b),
+                      ws.dir.at(b), ws.label.at(b), ws.edges.at(b), ws.inv.at(b), ws.changed.at(b), rounds_out, nullptr));
+  return EA_OK;
+}
+
+static int check_frame_args(const ea_problem *p, const void *bgr, int height, int width) {
+  if (!p || !bgr) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (height < 3 || width < 3 || height > 32768 || width > 32768 || (int64_t)height * width > 0x3fffffff)
+    return fail(EA_ERR_INVALID_ARG, "image extent out of range");
+  return EA_OK;
+}
+
+// Canny flavour of the reference frame: get_aX_canny (ref: utils.cpp:371-462)
+extern "C" int ea_problem_set_ref_frame_canny(ea_problem *p, const uint8_t *bgr, const uint16_t *depth, int height,
+                                              int width, double z_scaling, double low_threshold, double high_threshold) {
+  int rc = check_frame_args(p, bgr, height, width);
+  if (rc != EA_OK) return rc;
+  if (!depth) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (!(z_scaling > 0.0) || !(z_scaling <= DBL_MAX)) return fail(EA_ERR_INVALID_ARG, "z_scaling must be > 0 and finite");
+  int lo, hi;
+  rc = canny_thresholds(low_threshold, high_threshold, &lo, &hi);
+  if (rc != EA_OK) return rc;
+  FrameWs ws;
+  rc = frame_begin(p, bgr, height, width, &ws);
+  if (rc != EA_OK) return rc;
+  HIPCHK(hipMemcpyAsync(ws.depth.at(p->ws), depth, (size_t)height * width * 2, hipMemcpyHostToDevice, nullptr));
+  rc = run_canny(p, ws, false, height, width, lo, hi, nullptr);
+  if (rc != EA_OK) return rc;
+  // ref: utils.cpp:441 -- all_grad(i) > 0 && Z > 0 on the 0/255 edge map
+  return ref_points(p, ws, ws.edges, false, height, width, 0, z_scaling);
+}
+
+// Canny flavour of the current frame: get_distance_transform2 / _masked / _NoNormalize / _masked_NoNormalize
+// (ref: utils.cpp:85-199).  mask (nullable): H x W bytes, edges survive where mask > 1.  normalize != 0: min-max to
+// [norm_lo, norm_hi] ((0,1) at :103, (0,255) at :138).  The debug outputs may be NULL.
+static int now_frame_canny(ea_problem *p, const uint8_t *bgr, const uint8_t *mask, int height, int width, double low_threshold,
+                           double high_threshold, int normalize, double norm_lo, double norm_hi, uint8_t *edges_out,
+                           int32_t *chamfer_fix_out, float *dt_out, int *rounds_out) {
+  int rc = check_frame_args(p, bgr, height, width);
+  if (rc != EA_OK) return rc;
+  int lo, hi;
+  rc = canny_thresholds(low_threshold, high_threshold, &lo, &hi);
+  if (rc != EA_OK) return rc;
+  if (normalize && (!(std::fabs(norm_lo) <= DBL_MAX) || !(std::fabs(norm_hi) <= DBL_MAX)))
+    return fail(EA_ERR_INVALID_ARG, "normalisation range must be finite");
+  FrameWs ws;
+  rc = frame_begin(p, bgr, height, width, &ws);
+  if (rc != EA_OK) return rc;
+  const size_t np = (size_t)height * width;
+  if (mask) HIPCHK(hipMemcpyAsync(ws.keep.at(p->ws), mask, np, hipMemcpyHostToDevice, nullptr));
+  rc = run_canny(p, ws, mask != nullptr, height, width, lo, hi, rounds_out);
+  if (rc == EA_OK) rc = dt_from_mask(p, ws, ws.inv, height, width, normalize, norm_lo, norm_hi);
+  if (rc == EA_OK) rc = read_region(p, ws.edges, np, edges_out);
+  if (rc == EA_OK) rc = read_region(p, ws.dist, np * 4, chamfer_fix_out);
+  if (rc == EA_OK) rc = read_region(p, ws.plain, np * 4, dt_out);
+  if (rc != EA_OK) return rc;
+  // a masked edge map is not the one ea_problem_set_ref_frame_canny would produce from this frame: the tracker may not ride it
+  if (!mask) { p->ws_now_kind = 2; p->ws_now_h = height; p->ws_now_w = width; }
+  return EA_OK;
+}
+
+// ---- ROS flavour of the producers (ref: src/SolveEA.cpp:29-119): Canny(rgb, 150, 100, 3, true) on the 3-channel image
+static int ros_thresholds(double t1, double t2, int *low, int *high) {
+  // cv::Canny with L2gradient: min(t, 32767)^2, ordered
+  if (t1 != t1 || t2 != t2) return fail(EA_ERR_INVALID_ARG, "Canny threshold is NaN");
+  double lo = std::max(std::min(t1, t2), -1e4), hi = std::max(std::max(t1, t2), -1e4);
+  lo = std::min(32767.0, lo); hi = std::min(32767.0, hi);
+  if (lo > 0) lo *= lo;
+  if (hi > 0) hi *= hi;
+  *low = (int)std::floor(lo);
+  *high = (int)std::floor(hi);
+  return EA_OK;
+}
+
+namespace {
+struct WsCarver {
+  unsigned char *base;
+  size_t off = 0;
+  template <typename U> U *take(size_t n) {
+    off = (off + 255) & ~(size_t)255;
+    U *r = reinterpret_cast<U *>(base + off);
+    off += n * sizeof(U);
+    return r;
+  }
+};
+}  // namespace
+
+// Frames as the ROS callbacks receive them -> the resolution the node works at, on the device: `halvings` times
+// (depth: NaN -> 0, then) cv::resize(..., 0.5, 0.5) (src/ea.cpp:38, :56-62).  bgr / depth: host, full_h x full_w; the
+// results land in d_bgr / d_depth (device, full >> halvings).  halvings = 0: a plain upload.
+static int stage_scaled(ea_problem *p, const uint8_t *bgr, const float *depth, int full_h, int full_w, int halvings,
+                        uint8_t *d_bgr, float *d_depth) {
+  const size_t np = (size_t)full_h * full_w;
+  if (halvings == 0) {
+    HIPCHK(hipMemcpyAsync(d_bgr, bgr, np * 3, hipMemcpyHostToDevice, nullptr));
+    if (depth) HIPCHK(hipMemcpyAsync(d_depth, depth, np * 4, hipMemcpyHostToDevice, nullptr));
+    return EA_OK;
+  }
+  // stage: [bgr full | depth full | bgr half | depth half] (the ping-pong partner of the full-size pair)
+  const size_t need = np * 3 + np * 4 + np / 4 * 3 + np / 4 * 4 + 1024;
+  if (p->stage_bytes < need) {
+    if (p->stage) { cached_free(p->stage); p->stage = nullptr; p->stage_bytes = 0; }
+    HIPCHK(cached_malloc(reinterpret_cast<void **>(&p->stage), need, p->device));
+    p->stage_bytes = need;
+  }
+  WsCarver st{p->stage};
+  uint8_t *bgr_a = st.take<uint8_t>(np * 3), *bgr_b = nullptr;
+  float *dep_a = st.take<float>(np), *dep_b = nullptr;
+  bgr_b = st.take<uint8_t>(np / 4 * 3);
+  dep_b = st.take<float>(np / 4);
+  HIPCHK(hipMemcpyAsync(bgr_a, bgr, np * 3, hipMemcpyHostToDevice, nullptr));
+  if (depth) HIPCHK(hipMemcpyAsync(dep_a, depth, np * 4, hipMemcpyHostToDevice, nullptr));
+  int h = full_h, w = full_w;
+  for (int k = 0; k < halvings; ++k) {
+    const bool last = k == halvings - 1;
+    uint8_t *bo = last ? d_bgr : bgr_b;
+    float *dp = last ? d_depth : dep_b;
+    HIPCHK(launch_resize_half_bgr8(bgr_a, h, w, bo, nullptr));
+    if (depth) HIPCHK(launch_resize_half_f32(dep_a, h, w, dp, /*nan_to_zero=*/k == 0 ? 1 : 0, nullptr));
+    std::swap(bgr_a, bgr_b); std::swap(dep_a, dep_b);
+    h /= 2; w /= 2;
+  }
+  return EA_OK;
+}
+
+static int check_scaled_args(int height, int width, int halvings) {
+  if (halvings < 0 || halvings > 8) return fail(EA_ERR_INVALID_ARG, "halvings out of range");
+  if ((height % (1 << halvings)) != 0 || (width % (1 << halvings)) != 0)
+    return fail(EA_ERR_INVALID_ARG, "frame extent must be divisible by 2^halvings");
+  return EA_OK;
+}
+
+// SolveEA::setRefFrame (src/SolveEA.cpp:29-82): every edge pixel, depth CV_32F in metres, Z == 0 -> 1.0
+extern "C" int ea_problem_set_ref_frame_ros_scaled(ea_problem *p, const uint8_t *bgr, const float *depth, int full_height,
+                                                   int full_width, int halvings, double threshold1, double threshold2) {
+  int rc = check_frame_args(p, bgr, full_height, full_width);
+  if (rc != EA_OK) return rc;
+  if (!depth) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  rc = check_scaled_args(full_height, full_width, halvings);
+  if (rc != EA_OK) return rc;
+  int lo, hi;
+  rc = ros_thresholds(threshold1, threshold2, &lo, &hi);
+  if (rc != EA_OK) return rc;
+  const int height = full_height >> halvings, width = full_width >> halvings;
+  if (height < 3 || width < 3) return fail(EA_ERR_INVALID_ARG, "image extent out of range");
+  FrameWs ws;
+  rc = frame_begin(p, nullptr, height, width, &ws);
+  if (rc == EA_OK) rc = stage_scaled(p, bgr, depth, full_height, full_width, halvings, ws.bgr.at(p->ws), ws.depth.at<float>(p->ws));
+  if (rc == EA_OK) rc = run_canny(p, ws, false, height, width, lo, hi, nullptr, /*l2_bgr=*/1);
+  if (rc != EA_OK) return rc;
+  return ref_points(p, ws, ws.edges, /*ros=*/true, height, width, 0, /*z_scaling (metres already)=*/1.0);
+}
+
+extern "C" int ea_problem_set_ref_frame_ros(ea_problem *p, const uint8_t *bgr, const float *depth, int height, int width,
+                                            double threshold1, double threshold2) {
+  return ea_problem_set_ref_frame_ros_scaled(p, bgr, depth, height, width, 0, threshold1, threshold2);
+}
+
+// SolveEA::setNowFrame (src/SolveEA.cpp:86-119): Canny -> 255 - edges -> distanceTransform(L2, DIST_MASK_PRECISE) ->
+// normalize to [0, 255].  An image without a single edge has no defined result upstream either: EA_ERR_STATE.
+static int now_frame_ros_impl(ea_problem *p, const uint8_t *bgr, int full_height, int full_width, int halvings,
+                              double threshold1, double threshold2, uint8_t *edges_out, float *dt_out) {
+  int rc = check_frame_args(p, bgr, full_height, full_width);
+  if (rc != EA_OK) return rc;
+  rc = check_scaled_args(full_height, full_width, halvings);
+  if (rc != EA_OK) return rc;
+  int lo, hi;
+  rc = ros_thresholds(threshold1, threshold2, &lo, &hi);
+  if (rc != EA_OK) return rc;
+  const int height = full_height >> halvings, width = full_width >> halvings;
+  if (height < 3 || width < 3) return fail(EA_ERR_INVALID_ARG, "image extent out of range");
+  FrameWs ws;
+  rc = frame_begin(p, nullptr, height, width, &ws);
+  if (rc == EA_OK) rc = stage_scaled(p, bgr, nullptr, full_height, full_width, halvings, ws.bgr.at(p->ws), nullptr);
+  if (rc == EA_OK) rc = run_canny(p, ws, false, height, width, lo, hi, nullptr, /*l2_bgr=*/1);
+  if (rc != EA_OK) return rc;
+  int *d_counts = ws.counts.at(p->ws), *d_total = d_counts + frame_ws_blocks(height, width), total = 0;
+  HIPCHK(launch_edge_count_scan(ws.edges.at(p->ws), nullptr, height, width, 0, d_counts, d_total, nullptr));
+  rc = read_count(d_total, &total);
+  if (rc != EA_OK) return rc;
+  if (total == 0) return fail(EA_ERR_STATE, "no edge in the frame: the exact distance transform is undefined");
+  const size_t np = (size_t)height * width;
+  rc = dt_from_mask(p, ws, ws.inv, height, width, 1, 0.0, 255.0, /*precise=*/true);
+  if (rc == EA_OK) rc = read_region(p, ws.edges, np, edges_out);
+  if (rc == EA_OK) rc = read_region(p, ws.plain, np * 4, dt_out);
+  return rc;
+}
+
+extern "C" int ea_problem_debug_now_frame_ros(ea_problem *p, const uint8_t *bgr, int height, int width, double threshold1,
+                                              double threshold2, uint8_t *edges_out, float *dt_out) {
+  return now_frame_ros_impl(p, bgr, height, width, 0, threshold1, threshold2, edges_out, dt_out);
+}
+
+extern "C" int ea_problem_set_now_frame_ros(ea_problem *p, const uint8_t *bgr, int height, int width, double threshold1,
+                                            double threshold2) {
+  return now_frame_ros_impl(p, bgr, height, width, 0, threshold1, threshold2, nullptr, nullptr);
+}
+
+extern "C" int ea_problem_set_now_frame_ros_scaled(ea_problem *p, const uint8_t *bgr, int full_height, int full_width,
+                                                   int halvings, double threshold1, double threshold2) {
+  return now_frame_ros_impl(p, bgr, full_height, full_width, halvings, threshold1, threshold2, nullptr, nullptr);
+}
+
+// The half-resolution step by itself (host in, host out) for parity checks and for callers that build pyramid levels of
+// their own: kind 0 = bgr8 (height x width x 3 bytes), 1 = float32 with NaN -> 0 first (the depth callback, src/ea.cpp:56-62),
+// 2 = float32 as is.  dst: (height / 2) x (width / 2) of the same element type.
+extern "C" int ea_resize_half(int device, int kind, const void *src, int height, int width, void *dst) {
+  if (!src || !dst) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (kind < 0 || kind > 2) return fail(EA_ERR_INVALID_ARG, "kind must be 0 (bgr8), 1 (float32, NaN -> 0) or 2 (float32)");
+  if (height < 2 || width < 2 || (height & 1) || (width & 1) || (int64_t)height * width > 0x3fffffff)
+    return fail(EA_ERR_INVALID_ARG, "frame extent must be even and in range");
+  int rc = check_device(device);
+  if (rc != EA_OK) return rc;
+  HIPCHK(hipSetDevice(device));
+  const size_t np = (size_t)height * width, es = kind == 0 ? 3 : 4;
+  DevBuf a, b;
+  HIPCHK(cached_malloc(&a.p, np * es, device));
+  HIPCHK(cached_malloc(&b.p, np / 4 * es, device));
+  HIPCHK(hipMemcpy(a.p, src, np * es, hipMemcpyHostToDevice));
+  if (kind == 0) HIPCHK(launch_resize_half_bgr8(a.as<uint8_t>(), height, width, b.as<uint8_t>(), nullptr));
+  else HIPCHK(launch_resize_half_f32(a.as<float>(), height, width, b.as<float>(), kind == 1 ? 1 : 0, nullptr));
+  HIPCHK(hipMemcpy(dst, b.p, np / 4 * es, hipMemcpyDeviceToHost));
+  return EA_OK;
+}
+
+extern "C" int ea_problem_set_now_frame_canny(ea_problem *p, const uint8_t *bgr, const uint8_t *mask, int height, int width,
+                                              double low_threshold, double high_threshold, int normalize, double norm_lo,
+                                              double norm_hi) {
+  return now_frame_canny(p, bgr, mask, height, width, low_threshold, high_threshold, normalize, norm_lo, norm_hi, nullptr,
+                         nullptr, nullptr, nullptr);
+}
+
+extern "C" int ea_problem_debug_now_frame_canny(ea_problem *p, const uint8_t *bgr, const uint8_t *mask, int height,
+                                                int width, double low_threshold, double high_threshold, int normalize,
+                                                double norm_lo, double norm_hi, uint8_t *edges_out,
+                                                int32_t *chamfer_fix_out, float *dt_out, int *hysteresis_launches) {
+  return now_frame_canny(p, bgr, mask, height, width, low_threshold, high_threshold, normalize, norm_lo, norm_hi, edges_out,
+                         chamfer_fix_out, dt_out, hysteresis_launches);
+}
+
+extern "C" int ea_problem_set_now_frame(ea_problem *p, const uint8_t *bgr, int height, int width, int threshold,
+                                        int median, int normalize) {
+  if (!p || !bgr) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (height < 3 || width < 3 || height > 32768 || width > 32768) return fail(EA_ERR_INVALID_ARG, "image extent out of range");
+  FrameWs ws;
+  int rc = frame_begin(p, bgr, height, width, &ws);
+  if (rc == EA_OK) rc = run_dt(p, ws, height, width, threshold, median, normalize);
+  if (rc == EA_OK) { p->ws_now_kind = 1; p->ws_now_h = height; p->ws_now_w = width; }
+  return rc;
+}
+
+// stages of the DT producer for parity checks: any output may be NULL
+extern "C" int ea_problem_debug_now_frame(ea_problem *p, const uint8_t *bgr, int height, int width, int threshold,
+                                          int median, int normalize, uint8_t *lap_out, uint8_t *mask_out,
+                                          int32_t *chamfer_fix_out, float *dt_out) {
+  if (!p || !bgr) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (height < 3 || width < 3 || height > 32768 || width > 32768) return fail(EA_ERR_INVALID_ARG, "image extent out of range");
+  FrameWs ws;
+  int rc = frame_begin(p, bgr, height, width, &ws);
+  if (rc == EA_OK) rc = run_dt(p, ws, height, width, threshold, median, normalize);
+  const size_t np = (size_t)height * width;
+  if (rc == EA_OK) rc = read_region(p, ws.lap, np, lap_out);
+  if (rc == EA_OK) rc = read_region(p, ws.mask, np, mask_out);
+  if (rc == EA_OK) rc = read_region(p, ws.dist, np * 4, chamfer_fix_out);
+  if (rc == EA_OK) rc = read_region(p, ws.plain, np * 4, dt_out);
+  return rc;
+}
+
+// read back what the problem holds in HBM: points as n x 3 doubles, DT as H x W doubles ([v][u])
+extern "C" int ea_problem_get_points(ea_problem *p, double *xyz, int64_t capacity) {
+  if (!p || (!xyz && p->n > 0)) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (capacity < p->n) return fail(EA_ERR_INVALID_ARG, "capacity smaller than the number of points");
+  if (p->n == 0) return EA_OK;
+  HIPCHK(hipSetDevice(p->device));
+  const size_t n = (size_t)p->n, esz = p->dtype == EA_F32 ? 4 : 8;
+  std::vector<unsigned char> buf(3 * n * esz);
+  HIPCHK(hipMemcpy(buf.data(), p->d_x, n * esz, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(buf.data() + n * esz, p->d_y, n * esz, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(buf.data() + 2 * n * esz, p->d_z, n * esz, hipMemcpyDeviceToHost));
+  const int32_t *ord = p->order.empty() ? nullptr : p->order.data();
+  for (int c = 0; c < 3; ++c)
+    for (size_t i = 0; i < n; ++i)
+      xyz[3 * (ord ? (size_t)ord[i] : i) + c] = p->dtype == EA_F32 ? (double)reinterpret_cast<float *>(buf.data())[c * n + i]
+                                                                  : reinterpret_cast<double *>(buf.data())[c * n + i];
+  return EA_OK;
+}
+
+extern "C" int ea_problem_get_dt(ea_problem *p, double *image, int *height, int *width) {
+  if (!p) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (height) *height = p->H;
+  if (width) *width = p->W;
+  if (!image) return EA_OK;
+  if (!p->d_dt) return fail(EA_ERR_STATE, "distance-transform image not set");
+  HIPCHK(hipSetDevice(p->device));
+  const size_t esz = p->dtype == EA_F32 ? 4 : 8;
+  const size_t rows = (size_t)p->H + 2 * kImagePad;
+  std::vector<unsigned char> buf((size_t)p->pitch * rows * esz);
+  HIPCHK(hipMemcpy(buf.data(), p->d_dt, buf.size(), hipMemcpyDeviceToHost));
+  for (int v = 0; v < p->H; ++v)
+    for (int u = 0; u < p->W; ++u) {
+      const size_t idx = (size_t)(v + kImagePad) * p->pitch + (u + kImagePad);
+      image[(size_t)v * p->W + u] = p->dtype == EA_F32 ? (double)reinterpret_cast<float *>(buf.data())[idx]
+                                                       : reinterpret_cast<double *>(buf.data())[idx];
+    }
+  return EA_OK;
+}

@@ -319,6 +319,68 @@ def test_frame_to_frame_tracker(hip, flavour):
     T.close(); P.close()
 
 
+def _tracker_points(hip, T):
+    """the points of ea_tracker_problem(T) through ea_problem_get_points"""
+    L = hip.load()
+    h = L.ea_tracker_problem(T._h)
+    n = L.ea_problem_num_points(h)
+    xyz = np.zeros((n, 3))
+    assert L.ea_problem_get_points(h, xyz.ctypes.data_as(hip.C.POINTER(hip.C.c_double)), n) == 0
+    return xyz
+
+
+@pytest.mark.parametrize("flavour", [0, 1])
+def test_tracker_rides_the_workspace_on_small_and_odd_frames(hip, flavour):
+    """The tracker takes a pushed frame's edge points from what the "now" producer left in the workspace (Laplacian strength
+    / Canny edge map; only the depth goes up) instead of running the reference producer on the frame again.  That path must
+    give what the full path gives at every size: frames either side of 4096 pixels (below which the tracker used to take the
+    full path) and of one 1024-pixel count block, odd widths, several blocks.  After every push the tracker's points equal,
+    in count and bits, those of a plain problem after set_ref_frame[_canny] on the same frame, and pose, iteration count --
+    or the error of the solve -- equal the manual set_now / solve-from-prior / set_ref sequence."""
+    for k_size, (H, W) in enumerate([(63, 65), (64, 64), (33, 125), (31, 33), (17, 61), (130, 257)]):
+        Kc = (float(W), float(W), 0.5 * (W - 1), 0.5 * (H - 1))
+        rng = np.random.default_rng(300 + 10 * flavour + k_size)
+        scene = _random_frame(40 + k_size, H + 2, W + 2)   # three views of one scene, a pixel apart
+        T = hip.Tracker(*Kc, dtype=hip.EA_F64, flavour=flavour, loss=(hip.LOSS_CAUCHY, 1.0))
+        P = hip.Problem(*Kc, dtype=hip.EA_F64)
+        P.set_loss(hip.LOSS_CAUCHY, 1.0)
+        q_prior, t_prior = np.array([1.0, 0, 0, 0]), np.zeros(3)
+        for k in range(3):
+            bgr = scene[k:k + H, k:k + W].copy()
+            depth = rng.integers(0, 30000, (H, W)).astype(np.uint16)
+            depth[rng.random((H, W)) < 0.15] = 0
+            solved = k > 0 and P.num_points > 0
+            err = merr = None
+            try:
+                q, t, s = T.push_frame(bgr, depth)
+            except hip.EAError as e:
+                err = e.code
+            if solved:
+                (P.set_now_frame if flavour == 0 else P.set_now_frame_canny)(bgr)
+                try:
+                    qm, tm, sm = P.solve(q_prior, t_prior)
+                except hip.EAError as e:
+                    merr = e.code
+            print("RIDE flavour %d %dx%d push %d: %d points, solved %s, error %s / %s" % (flavour, H, W, k, P.num_points, solved, err, merr))
+            assert err == merr, (H, W, k)
+            if err is not None:
+                continue   # (a push whose solve fails keeps the previous reference, as the manual sequence does here)
+            if solved:
+                if sm["termination"] == hip.FAILURE:   # the tracker keeps its prior over a failed solve
+                    qm, tm = q_prior, t_prior
+                assert s is not None and s["num_iterations"] == sm["num_iterations"], (H, W, k)
+                assert np.array_equal(q, qm) and np.array_equal(t, tm), (H, W, k)
+                q_prior, t_prior = qm, tm
+            else:
+                assert s is None and np.array_equal(q, q_prior) and np.array_equal(t, t_prior), (H, W, k)
+            (P.set_ref_frame if flavour == 0 else P.set_ref_frame_canny)(bgr, depth)
+            got = _tracker_points(hip, T)
+            assert got.shape[0] == P.num_points, (H, W, k)
+            assert np.array_equal(got, P.get_points()), (H, W, k)
+        assert P.num_points > 0, (H, W)   # (the frames have edges: the comparison above was not of empty sets)
+        T.close(); P.close()
+
+
 def test_frames_in_page_locked_memory(hip):
     """ea_host_alloc: frames handed over from page-locked memory (direct DMA instead of the runtime's staged copy) give
     what the same frames give from ordinary memory, bit for bit; the block is plain host memory and can be freed."""
