@@ -29,7 +29,7 @@ EXPORTED = [
     "ea_problem_set_loss", "ea_problem_set_flavour", "ea_problem_num_points",
     "ea_eval", "ea_eval_points", "ea_cost", "ea_problem_pixel_cost", "ea_solve",
     "ea_release_cached_memory", "ea_host_alloc", "ea_host_free", "ea_batch_create", "ea_batch_destroy", "ea_batch_count", "ea_batch_eval", "ea_batch_solve",
-    "ea_batch_eval_poses", "ea_batch_set_poses", "ea_batch_eval_resident_poses",
+    "ea_batch_eval_poses", "ea_batch_set_poses", "ea_batch_eval_resident_poses", "ea_batch_solve_starts", "ea_solve_starts",
     "ea_solve_pyramid", "ea_solve_sharded", "ea_solve_sharded_device",
     "ea_comm_get_unique_id", "ea_comm_create", "ea_comm_create_all", "ea_comm_destroy", "ea_comm_rank", "ea_comm_size",
     "ea_comm_gather_poses", "ea_solve_sharded_comm", "ea_comm_get_info", "ea_hip_runtime_copies", "ea_tracker_create", "ea_tracker_destroy", "ea_tracker_problem", "ea_tracker_push_frame",
@@ -159,6 +159,8 @@ def load():
     L.ea_batch_eval_poses.argtypes = [vp, C.c_int, dp, dp, dp, dp, dp, i64p]
     L.ea_batch_set_poses.argtypes = [vp, C.c_int, dp, dp]
     L.ea_batch_eval_resident_poses.argtypes = [vp, dp, dp, dp, i64p]
+    L.ea_batch_solve_starts.argtypes = [vp, C.c_int, C.POINTER(Options), dp, dp, C.POINTER(Summary), C.POINTER(C.c_int)]
+    L.ea_solve_starts.argtypes = [vp, C.c_int, C.POINTER(Options), dp, dp, C.POINTER(Summary), C.POINTER(C.c_int)]
     L.ea_batch_bench_eval.argtypes = [vp, dp, dp, C.c_int, C.c_int, dp, dp]
     L.ea_batch_bench_steps.argtypes = [vp, C.c_int, dp]
     L.ea_batch_bench_capture.argtypes = [vp, C.c_int]
@@ -630,6 +632,17 @@ class Problem:
         _check(load().ea_solve(self._h, C.byref(o), _dp(q), _dp(t), C.byref(s)))
         return q, t, summary_to_dict(s)
 
+    def solve_starts(self, q, t, **opts):
+        """K solves from K starting poses in lock-step (ea_solve_starts): q (K, 4), t (K, 3) -> (q, t, K summaries, best)"""
+        q, t = _f64(q).reshape(-1, 4).copy(), _f64(t).reshape(-1, 3).copy()
+        K = q.shape[0]
+        assert t.shape[0] == K
+        o = default_options(**opts)
+        s = (Summary * K)()
+        best = C.c_int(-1)
+        _check(load().ea_solve_starts(self._h, K, C.byref(o), _dp(q), _dp(t), s, C.byref(best)))
+        return q, t, [summary_to_dict(x) for x in s], best.value
+
     def covariance(self, q, t, **opts):
         """ceres::Covariance at (q, t) (ea_problem_covariance); opts: fields of ea_covariance_options -> covariance_to_dict"""
         q, t = _f64(q), _f64(t)
@@ -925,6 +938,20 @@ class Batch:
         s = (Summary * len(self))()
         _check(load().ea_batch_solve(self._h, C.byref(o), _dp(q), _dp(t), s))
         return q, t, [summary_to_dict(x) for x in s]
+
+    def solve_starts(self, q, t, summaries=True, **opts):
+        """K solves of every problem from K starting poses in lock-step (ea_batch_solve_starts): q (K, n, 4), t (K, n, 3)
+        -> (q (K, n, 4), t (K, n, 3), K lists of n summaries (None with summaries=False), best (n,))"""
+        n = len(self)
+        q, t = _f64(q).reshape(-1, n, 4).copy(), _f64(t).reshape(-1, n, 3).copy()
+        K = q.shape[0]
+        assert t.shape[0] == K
+        o = default_options(**opts)
+        s = (Summary * (K * n))() if summaries else None
+        best = np.zeros(n, dtype=np.intc)
+        _check(load().ea_batch_solve_starts(self._h, K, C.byref(o), _dp(q), _dp(t), s, best.ctypes.data_as(C.POINTER(C.c_int))))
+        out = [[summary_to_dict(s[k * n + i]) for i in range(n)] for k in range(K)] if summaries else None
+        return q, t, out, best.astype(np.int64)
 
     def bench_eval(self, q, t, warmup, steps, kernel_pass=True):
         """(ms over `steps` fused evaluations, mean ms of the per-point kernel alone | None)"""

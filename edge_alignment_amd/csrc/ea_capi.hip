@@ -29,6 +29,7 @@
 #include "ea_poses_map.h"
 #include "ea_prior.h"
 #include "ea_spin.h"
+#include "ea_starts_map.h"
 #include "ea_types.h"
 
 using namespace ea;
@@ -373,7 +374,19 @@ struct ea_batch {
   // fetch anyway, PriorDesc::held what ea_cov_kernel, which has no LMState, reads)
   PriorDesc *d_priors = nullptr;
   std::vector<PriorDesc> h_priors;
-  int any_side = 0;
+  int any_side = 0;  // ea_batch_solve_starts: K trust-region runs per problem in lock-step.  One device block [q, t x N | LMState x N | live list 0 |
+  // alive | n_live pair, counter || live list 1 | PoseState x N | LMCold x N] (N = K x count slots; the part in front of || goes
+  // up in one copy from the pinned staging block h_ms_up), the device trace rows when summaries are asked for, and the pinned,
+  // device-mapped delivery block [the polled word | LMState x N | LMTrace x N]
+  int ms_cap_slots = 0, ms_cap_K = 0;
+  bool ms_has_traces = false;
+  unsigned char *d_ms = nullptr, *h_ms_up = nullptr, *h_ms_dl = nullptr, *dv_ms_dl = nullptr;
+  LMTrace *d_ms_traces = nullptr;
+  unsigned ms_tag = 0;           // the tag of the last call's posts (ea_starts_map.h: starts_word)
+  int last_starts_form = 0, last_starts_launches = 0;  // info keys "starts_form", "starts_launches"
+  int t_starts_events = 0;       // tuning key "starts_events": an event pair around the call's queued launches (measurement)
+  int last_starts_iterations = 0;
+  int64_t last_starts_device_ns = 0;  // info keys "starts_iterations" (enqueued), "starts_device_ns" (0 without the events)
 };
 
 int ea::check_device(int device) {
@@ -865,8 +878,16 @@ static void kposes_free(ea_batch *b) {
   b->kp_K = b->kp_cap = 0;
 }
 
+static void starts_free(ea_batch *b) {
+  cached_free(b->d_ms); cached_free(b->d_ms_traces);
+  cached_host_free(b->h_ms_up); cached_host_free(b->h_ms_dl);
+  b->d_ms = nullptr; b->d_ms_traces = nullptr; b->h_ms_up = nullptr; b->h_ms_dl = nullptr; b->dv_ms_dl = nullptr;
+  b->ms_cap_slots = b->ms_cap_K = 0; b->ms_has_traces = false;
+}
+
 static void batch_free_device(ea_batch *b) {
   kposes_free(b);
+  starts_free(b);
   cached_free(b->d_cprobs); cached_host_free(b->h_cdesc); cached_host_free(b->h_cov);
   b->d_cprobs = nullptr; b->h_cdesc = nullptr; b->cdesc_cap = 0; b->h_cov = nullptr; b->dv_cov = nullptr;
   (void)hipFree(b->d_rows_r); (void)hipFree(b->d_rows_J); (void)hipFree(b->d_rows_invalid);
@@ -2544,6 +2565,7 @@ extern "C" int ea_batch_set_tuning(ea_batch *b, const char *key, int value) {
   else if (k == "zero_copy_poses") { b->t_zero_copy = value; return EA_OK; }
   else if (k == "poses_per_launch") { b->t_kp_G = value > 0 ? value : 0; b->kp_K = 0; return EA_OK; }  // (resident poses are dropped)
   else if (k == "poses_order") { b->t_kp_order = value ? 1 : 0; return EA_OK; }
+  else if (k == "starts_events") { b->t_starts_events = value > 0 ? 1 : 0; return EA_OK; }
   else return fail(EA_ERR_INVALID_ARG, "unknown tuning key: " + k);
   b->built = false;
   return EA_OK;
@@ -2568,6 +2590,10 @@ extern "C" int ea_batch_get_info(const ea_batch *b, const char *key, int64_t *va
   else if (k == "poses_threads") *value = b->kp_nt;
   else if (k == "poses_tiles") *value = b->kp_ntiles;            // partial rows (= workgroups with work) per pose
   else if (k == "fused_iterations") *value = b->last_fused;      // the last solve ran one launch per LM iteration (ea_lm_iter_kernel)
+  else if (k == "starts_form") *value = b->last_starts_form;     // the last ea_batch_solve_starts: 1 = lock-step, 0 = one batch solve per start
+  else if (k == "starts_launches") *value = b->last_starts_launches;  // its evaluation launches (lock-step form)
+  else if (k == "starts_iterations") *value = b->last_starts_iterations;  // iterations it enqueued (look-ahead included)
+  else if (k == "starts_device_ns") *value = b->last_starts_device_ns;    // between the event pair of "starts_events" = 1
   else return fail(EA_ERR_INVALID_ARG, "unknown info key: " + k);
   return EA_OK;
 }
@@ -2843,6 +2869,246 @@ extern "C" int ea_solve(ea_problem *p, const ea_options *opt, double q[4], doubl
   int rc = self_batch(p, &b);
   if (rc != EA_OK) return rc;
   return ea_batch_solve(b, opt, q, t, summary);
+}
+
+// ---- K trust-region runs per problem, in lock-step on the device (ea_starts_map.h) --------------------------------------
+//
+// K independent solves of every problem of the batch from K starting poses.  An iteration is one (evaluate, step) launch pair
+// per piece of at most G positions of the live list: ea_eval_starts_kernel evaluates the starts still running, as
+// ea_batch_eval_poses would evaluate their poses, ea_lm_step_starts_kernel folds each start's rows and runs its state machine;
+// the iteration's last step launch compacts the list and posts {iterations complete, n_live} to ONE pinned word.  The host
+// keeps `ahead` iterations queued, sizes every grid from the last n_live it has seen (never smaller than the device's: a
+// position past the end returns at once) and polls that word alone.  No result depends on K, the other starts, G or the
+// moment another start ended: a start's rows are written and folded by its own workgroups in a fixed order.
+namespace {
+struct StartsLayout { size_t qt, states, live0, alive, nlive, counter, up_bytes, live1, poses, cold, bytes; };
+StartsLayout starts_layout(size_t N, size_t K) {
+  auto al = [](size_t v) { return (v + 15) & ~(size_t)15; };
+  StartsLayout L;
+  size_t o = 0;
+  L.qt = o; o = al(o + N * 7 * sizeof(double));
+  L.states = o; o = al(o + N * sizeof(LMState));
+  L.live0 = o; o = al(o + K * sizeof(int));
+  L.alive = o; o = al(o + K * sizeof(int));
+  L.nlive = o; L.counter = o + 2 * sizeof(int); o += 16;
+  L.up_bytes = o;
+  L.live1 = o; o = al(o + K * sizeof(int));
+  L.poses = o; o = al(o + N * sizeof(PoseState));
+  L.cold = o; o = al(o + N * sizeof(LMCold));
+  L.bytes = o;
+  return L;
+}
+constexpr size_t kStartsWordBytes = 64;
+}  // namespace
+
+static int starts_reserve(ea_batch *b, int N, int K, bool traces) {
+  if (N <= b->ms_cap_slots && K <= b->ms_cap_K && (!traces || b->ms_has_traces)) return EA_OK;
+  HIPCHK(hipStreamSynchronize(b->stream));  // (launches still reading the old arrays)
+  const int cap_n = std::max(N, b->ms_cap_slots), cap_k = std::max(K, b->ms_cap_K);
+  const bool tr = traces || b->ms_has_traces;
+  starts_free(b);
+  const StartsLayout L = starts_layout((size_t)cap_n, (size_t)cap_k);
+  HIPCHK(cached_malloc(reinterpret_cast<void **>(&b->d_ms), L.bytes, b->device));
+  HIPCHK(cached_host_malloc(reinterpret_cast<void **>(&b->h_ms_up), L.up_bytes, hipHostMallocDefault, b->device));
+  const size_t dl = kStartsWordBytes + (size_t)cap_n * (sizeof(LMState) + (tr ? sizeof(LMTrace) : 0));
+  HIPCHK(cached_host_malloc(reinterpret_cast<void **>(&b->h_ms_dl), dl, hipHostMallocMapped, b->device));
+  HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&b->dv_ms_dl), b->h_ms_dl, 0));
+  std::memset(b->h_ms_dl, 0, kStartsWordBytes);  // (tag 0 is never posted)
+  if (tr) HIPCHK(cached_malloc(reinterpret_cast<void **>(&b->d_ms_traces), (size_t)cap_n * sizeof(LMTrace), b->device));
+  b->ms_cap_slots = cap_n; b->ms_cap_K = cap_k; b->ms_has_traces = tr;
+  return EA_OK;
+}
+
+// best[i]: the start with the smallest final cost among those that did not fail (ties: the lowest), -1 if none
+static void starts_pick_best(int K, int count, const std::vector<int> &termination, const std::vector<double> &cost, int *best) {
+  for (int i = 0; i < count; ++i) {
+    int arg = -1;
+    for (int k = 0; k < K; ++k) {
+      const size_t s = (size_t)k * count + i;
+      if (termination[s] == EA_FAILURE || !(cost[s] == cost[s])) continue;
+      if (arg < 0 || cost[s] < cost[(size_t)arg * count + i]) arg = k;
+    }
+    best[i] = arg;
+  }
+}
+
+// the batches the lock-step form does not cover: one batch solve per start
+static int starts_fallback(ea_batch *b, int K, const ea_options *opt, double *q, double *t, ea_summary *summaries, int *best) {
+  const int count = (int)b->probs.size();
+  std::vector<ea_summary> own;
+  if (!summaries && best) own.resize((size_t)count);
+  std::vector<int> termination((size_t)K * count, EA_FAILURE);
+  std::vector<double> cost((size_t)K * count, 0.0);
+  for (int k = 0; k < K; ++k) {
+    ea_summary *sm = summaries ? summaries + (size_t)k * count : (best ? own.data() : nullptr);
+    const int rc = ea_batch_solve(b, opt, q + (size_t)k * count * 4, t + (size_t)k * count * 3, sm);
+    if (rc != EA_OK) return rc;
+    if (sm)
+      for (int i = 0; i < count; ++i) { termination[(size_t)k * count + i] = sm[i].termination; cost[(size_t)k * count + i] = sm[i].final_cost; }
+  }
+  if (best) starts_pick_best(K, count, termination, cost, best);
+  return EA_OK;
+}
+
+extern "C" int ea_batch_solve_starts(ea_batch *b, int K, const ea_options *opt_in, double *q, double *t, ea_summary *summaries,
+                                     int *best) {
+  if (!b || !q || !t) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (K < 1 || K > kMaxStartSlots) return fail(EA_ERR_INVALID_ARG, "K out of range: 1 <= K, K x problems <= 16384");
+  int rc = require_device();
+  if (rc != EA_OK) return rc;
+  const int count = (int)b->probs.size();
+  if ((int64_t)K * count > kMaxStartSlots) return fail(EA_ERR_INVALID_ARG, "too many starts: K x problems <= 16384");
+  const auto t0 = std::chrono::steady_clock::now();
+  ea_options o;
+  if (int vrc = resolve_options(opt_in, &o)) return vrc;
+  const LMOptions lo = lm_options(o);
+  if ((rc = batch_build(b)) != EA_OK) return rc;
+  const int kept_G = b->kp_K > 0 ? b->kp_G : 0;  // (resident poses keep the launch size they were set with)
+  if (b->kp_G == 0) kposes_shape(b);              // (once per build of the batch)
+  b->last_starts_launches = 0;
+  // (the step kernel folds in the order of a 256-lane workgroup: a pose shape tuned to 1024 threads takes the fall-back too)
+  if (!kposes_flat(b) || b->kp_nt != 256) {
+    b->last_starts_form = 0;
+    return starts_fallback(b, K, opt_in, q, t, summaries, best);
+  }
+  b->last_starts_form = 1;
+  const int N = K * count, G = kposes_group(b, K), rows = b->kp_ntiles;
+  rc = kposes_tables(b, G);
+  if (kept_G > 0) b->kp_G = kept_G;
+  if (rc != EA_OK) return rc;
+  const bool traces = summaries != nullptr || o.minimizer_progress_to_stdout;
+  if ((rc = starts_reserve(b, N, K, traces)) != EA_OK) return rc;
+  const StartsLayout L = starts_layout((size_t)N, (size_t)K);
+  // (the previous call's upload out of the staging block was consumed before its first kernel ran, and that call did not
+  // return before its kernels had posted)
+  double *h_qt = reinterpret_cast<double *>(b->h_ms_up + L.qt);
+  LMState *h_st = reinterpret_cast<LMState *>(b->h_ms_up + L.states);
+  int *h_live = reinterpret_cast<int *>(b->h_ms_up + L.live0), *h_alive = reinterpret_cast<int *>(b->h_ms_up + L.alive);
+  int *h_tail = reinterpret_cast<int *>(b->h_ms_up + L.nlive);
+  for (int s = 0; s < N; ++s) {
+    const ea_problem *p = b->probs[(size_t)(s % count)];
+    lm_init(&h_st[s], &lo, q + 4 * (size_t)s, t + 3 * (size_t)s, p->rot_transposed, p->held);
+    for (int k = 0; k < 7; ++k) h_qt[7 * (size_t)s + k] = h_st[s].x[k];
+  }
+  for (int k = 0; k < K; ++k) { h_live[k] = k; h_alive[k] = count; }
+  h_tail[0] = K; h_tail[1] = 0; h_tail[2] = 0; h_tail[3] = 0;
+  b->ms_tag = (b->ms_tag + 1) & 0x1ffffu;
+  if (b->ms_tag == 0) b->ms_tag = 1;
+  const unsigned tag = b->ms_tag;
+  if (b->t_test_stall_ms > 0)  // (tests: a device that shows no progress must trip the deadline)
+    HIPCHK(hipLaunchHostFunc(b->stream, [](void *ms) { std::this_thread::sleep_for(std::chrono::milliseconds((intptr_t)ms)); },
+                             (void *)(intptr_t)b->t_test_stall_ms));
+  HIPCHK(hipMemcpyAsync(b->d_ms, b->h_ms_up, L.up_bytes, hipMemcpyHostToDevice, b->stream));
+  PoseState *d_poses = reinterpret_cast<PoseState *>(b->d_ms + L.poses);
+  HIPCHK(launch_make_poses(reinterpret_cast<const double *>(b->d_ms + L.qt), N, count, b->d_probs, b->d_groups, d_poses, b->stream));
+  int *d_live[2] = {reinterpret_cast<int *>(b->d_ms + L.live0), reinterpret_cast<int *>(b->d_ms + L.live1)};
+  int *d_nlive = reinterpret_cast<int *>(b->d_ms + L.nlive);
+  LMState *hd_states = reinterpret_cast<LMState *>(b->h_ms_dl + kStartsWordBytes);
+  LMTrace *hd_traces = reinterpret_cast<LMTrace *>(b->h_ms_dl + kStartsWordBytes + (size_t)b->ms_cap_slots * sizeof(LMState));
+  StartsStep a;
+  a.groups = b->d_kgroups; a.side = b->d_groups; a.rows = b->d_krows;
+  a.poses = d_poses; a.states = reinterpret_cast<LMState *>(b->d_ms + L.states); a.cold = reinterpret_cast<LMCold *>(b->d_ms + L.cold);
+  a.traces = traces ? b->d_ms_traces : nullptr;
+  a.host_states = reinterpret_cast<LMState *>(b->dv_ms_dl + kStartsWordBytes);
+  a.host_traces = traces ? reinterpret_cast<LMTrace *>(b->dv_ms_dl + kStartsWordBytes + (size_t)b->ms_cap_slots * sizeof(LMState)) : nullptr;
+  a.alive = reinterpret_cast<int *>(b->d_ms + L.alive);
+  a.counter = reinterpret_cast<unsigned int *>(b->d_ms + L.counter);
+  a.host_word = reinterpret_cast<unsigned long long *>(b->dv_ms_dl);
+  a.count = count; a.rows_per_pose = rows; a.tag = tag;
+  const EvalLaunch shape = eval_launch(b, /*kposes=*/true);
+  PosesLaunch pl;
+  pl.rows = rows; pl.order = b->t_kp_order; pl.single = b->nterms == 1;
+  // iteration j over n (possibly stale) live positions: reads list j & 1, its last step launch writes list (j + 1) & 1
+  auto enqueue_iteration = [&](int j, int n) -> int {
+    const int per = starts_piece(n, G), in = j & 1;
+    a.live_in = d_live[in]; a.n_in = d_nlive + in; a.live_out = d_live[in ^ 1]; a.n_out = d_nlive + (in ^ 1);
+    a.iteration = (unsigned)j + 1u;
+    for (int off = 0; off < n; off += per) {
+      pl.g = std::min(per, n - off);
+      HIPCHK(launch_eval_starts(shape, pl, b->d_kprobs, d_poses, b->d_krows, a.live_in, a.n_in, off, b->stream));
+      a.off = off; a.last = off + pl.g >= n;
+      HIPCHK(launch_lm_step_starts(pl.g, a, lo, b->any_side, b->stream));
+      ++b->last_starts_launches;
+    }
+    return EA_OK;
+  };
+  const int ahead = o.iterations_per_sync > 0 ? o.iterations_per_sync : 2, budget = o.max_num_iterations + 2;
+  EventPair evp;  // ("starts_events": the device's own view of the queued launches, first to last)
+  if (b->t_starts_events) {
+    HIPCHK(hipEventCreate(&evp.e0));
+    HIPCHK(hipEventCreate(&evp.e1));
+    HIPCHK(hipEventRecord(evp.e0, b->stream));
+  }
+  const uint64_t *word = reinterpret_cast<const uint64_t *>(b->h_ms_dl);
+  int enq = 0, seen = 0, n_host = K;
+  unsigned spins = 0;
+  bool fetch = false;
+  SpinWait wait(resolve_timeout_ms(o));
+  for (;;) {
+    int it = 0, nl = K;
+    if (!starts_word_read(__atomic_load_n(word, __ATOMIC_ACQUIRE), tag, &it, &nl)) { it = 0; nl = K; }
+    if (it != seen) { seen = it; n_host = nl; wait.progress(); }
+    if (it > 0 && nl == 0) break;  // every start has ended and delivered
+    if (enq < budget && enq - it < ahead) {
+      if ((rc = enqueue_iteration(enq, n_host)) != EA_OK) return rc;
+      ++enq;
+      wait.progress();
+    } else if (enq >= budget && it >= enq) {
+      fetch = true;  // cut short by the launch budget: some start is still running
+      break;
+    } else if (wait.poll()) {
+      b->needs_drain = true;
+      char msg[160];
+      std::snprintf(msg, sizeof msg, "solve deadline: no progress on the device for %.0f ms (ea_options.solve_timeout_ms)", wait.timeout_ms());
+      return fail(EA_ERR_HIP, msg);
+    } else if ((++spins & 0x3fff) == 0) {  // nothing to enqueue and no progress for a while: is the stream still healthy?
+      const hipError_t qe = hipStreamQuery(b->stream);
+      if (qe != hipSuccess && qe != hipErrorNotReady) { b->needs_drain = true; return fail(EA_ERR_HIP, hipGetErrorString(qe)); }
+    }
+  }
+  b->last_starts_iterations = enq;
+  if (b->t_starts_events) {  // (waits for the launches queued ahead as well: they are part of what the call put on the device)
+    HIPCHK(hipEventRecord(evp.e1, b->stream));
+    HIPCHK(hipEventSynchronize(evp.e1));
+    float ems = 0.f;
+    HIPCHK(hipEventElapsedTime(&ems, evp.e0, evp.e1));
+    b->last_starts_device_ns = (int64_t)((double)ems * 1e6);
+  }
+  if (fetch) {  // the classic way: states (and trace rows) of every slot from the device, behind a synchronisation
+    HIPCHK(hipMemcpyAsync(hd_states, a.states, (size_t)N * sizeof(LMState), hipMemcpyDeviceToHost, b->stream));
+    if (traces) HIPCHK(hipMemcpyAsync(hd_traces, b->d_ms_traces, (size_t)N * sizeof(LMTrace), hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+  }
+  const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  std::vector<int> termination((size_t)N);
+  std::vector<double> cost((size_t)N);
+  for (int s = 0; s < N; ++s) {
+    const LMState &st = hd_states[s];
+    for (int k = 0; k < 4; ++k) q[4 * (size_t)s + k] = st.x[k];
+    for (int k = 0; k < 3; ++k) t[3 * (size_t)s + k] = st.x[4 + k];
+    termination[(size_t)s] = st.termination; cost[(size_t)s] = st.cost;
+    if (summaries) fill_summary(st, hd_traces[s], b->probs[(size_t)(s % count)]->n, ms, &summaries[s]);
+    if (o.minimizer_progress_to_stdout) {
+      const LMTrace &tr = hd_traces[s];
+      std::printf("start %d problem %d\niter      cost      cost_change  |gradient|   |step|    tr_ratio  tr_radius\n", s / count, s % count);
+      const int ni = st.why == EA_WHY_INITIAL_EVAL_FAILED ? 0 : std::min(st.iteration + 1, (int)kTrace);
+      for (int i = 0; i < ni; ++i)
+        std::printf("%4d  %.6e  % .2e    %.2e   %.2e  % .2e  %.2e\n", i, tr.it_cost[i], tr.it_cost_change[i], tr.it_gradient_max_norm[i],
+                    tr.it_step_norm[i], tr.it_relative_decrease[i], tr.it_radius[i]);
+    }
+  }
+  if (best) starts_pick_best(K, count, termination, cost, best);
+  return EA_OK;
+}
+
+extern "C" int ea_solve_starts(ea_problem *p, int K, const ea_options *opt, double *q, double *t, ea_summary *summaries, int *best) {
+  if (!p || !q || !t) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (K < 1 || K > kMaxStartSlots) return fail(EA_ERR_INVALID_ARG, "K out of range: 1 <= K <= 16384");
+  int rc = require_device();
+  if (rc != EA_OK) return rc;
+  ea_batch *b;
+  if ((rc = self_batch(p, &b)) != EA_OK) return rc;
+  return ea_batch_solve_starts(b, K, opt, q, t, summaries, best);
 }
 
 // ---- one problem sharded by points over several processes / GPUs ----------------------------------

@@ -40,6 +40,7 @@ extern __device__ int g_lm_probe_row;
 #endif
 #include "ea_launch.h"
 #include "ea_poses_map.h"
+#include "ea_starts_map.h"
 #include "ea_lm.h"
 #include "ea_prior.h"
 #include "ea_types.h"
@@ -1696,6 +1697,97 @@ __global__ __launch_bounds__(NT) void ea_poses_fold_kernel(PosesFold fold) {
   poses_fold_one<NT>(fold, blockIdx.x);
 }
 
+// The evaluation of a multi-start solve (ea_batch_solve_starts): ea_eval_poses_kernel's launch -- the same one-dimensional,
+// XCD-dealt item list, chunks, per-point code and row index pose * rows + row, so a start's partial rows hold the bits the
+// pose-batched evaluation gives for that pose -- over a piece of the LIVE LIST (ea_starts_map.h): item pose g of the launch is
+// position off + g of the list, evaluates start live[off + g] at its pose slot start * count + term, and writes the rows
+// g * rows + row.  n_live is a word on the device: the host sizes the grid from the last value it has seen, and positions
+// from n_live on return at once.  No riders: the step kernel of the pair folds the rows.
+template <typename T, int PPT, int MODE, int NT, bool VAR, bool BUF, bool IMG32 = false>
+__global__ __launch_bounds__(NT) void ea_eval_starts_kernel(
+    const void *__restrict__ x0, const void *__restrict__ y0, const void *__restrict__ z0, int n0,
+    int shape, int g, int rows,
+    const ProblemDesc *__restrict__ probs, const PoseState *__restrict__ poses,
+    double *__restrict__ partials, const int *__restrict__ live, const int *__restrict__ n_live, int off) {
+  static_assert(MODE == 0 && !VAR, "plain functor, stencil rows from L2");
+  constexpr int chunk = NT * PPT;
+  extern __shared__ __align__(16) unsigned char smem[];
+  double *s_red = reinterpret_cast<double *>(smem);
+  int *s_box = reinterpret_cast<int *>(smem + kRedBytes);
+  const PosesWork w = poses_work(blockIdx.x, shape, rows, g, 0);
+  if (w.kind != 2) return;  // (uniform)
+  if (!starts_position_live(off, w.pose, *n_live)) return;
+  const int start_k = live[off + w.pose];
+  const PosesChunk pc = starts_chunk(w, start_k, shape, rows, reinterpret_cast<const PosesRow *>(probs) - rows);
+  const int c = pc.chunk;
+  const long long start = (long long)c * chunk;
+  const int tid = threadIdx.x;
+  T X[PPT], Y[PPT], Z[PPT];
+  const bool early = BUF && pc.term == 0 && n0 > 0;  // (uniform)
+  if constexpr (BUF) {
+    if (early) {
+      if (start >= n0) return;
+      const int count0 = min(chunk, (int)(n0 - start));
+      const __amdgpu_buffer_rsrc_t rx = make_raw_buffer(static_cast<const T *>(x0) + start, (unsigned)count0 * (unsigned)sizeof(T));
+      const __amdgpu_buffer_rsrc_t ry = make_raw_buffer(static_cast<const T *>(y0) + start, (unsigned)count0 * (unsigned)sizeof(T));
+      const __amdgpu_buffer_rsrc_t rz = make_raw_buffer(static_cast<const T *>(z0) + start, (unsigned)count0 * (unsigned)sizeof(T));
+#pragma unroll
+      for (int k = 0; k < PPT; ++k) {
+        const int poff = min(tid + k * NT, count0 - 1) * (int)sizeof(T);
+        X[k] = buf_load_elem<T>(rx, poff); Y[k] = buf_load_elem<T>(ry, poff); Z[k] = buf_load_elem<T>(rz, poff);
+      }
+    }
+  }
+  // descriptor and pose by value, as ONE batch of scalar loads behind one wait (eval_fused_body)
+  const ProblemDesc pd = probs[pc.term];
+  PoseLite<T> ps;
+  int active;
+  {
+    const PoseState *psp = poses + pc.slot;
+    const T *R_ = Uni<T>::R(*psp), *t_ = Uni<T>::t(*psp);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) ps.R[i] = R_[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) ps.t[i] = t_[i];
+    ps.unit_q = psp->unit_q;
+    ps.full = psp;
+    active = psp->active;
+    asm volatile("" ::"s"(pd.x), "s"(pd.y), "s"(pd.z), "s"(IMG32 ? pd.dt32 : pd.dt), "s"(pd.n), "s"(pd.W), "s"(pd.H), "s"(pd.pitch),
+                 "s"(Uni<T>::fx(pd)), "s"(Uni<T>::fy(pd)), "s"(Uni<T>::cx(pd)), "s"(Uni<T>::cy(pd)),
+                 "s"(Uni<T>::loss_a(pd)), "s"(Uni<T>::loss_inv_b(pd)), "s"(Uni<T>::z_guard(pd)), "s"(Uni<T>::z_eps(pd)),
+                 "s"(pd.loss_kind), "s"(pd.variant));
+    asm volatile("" : "+s"(active), "+s"(ps.unit_q), "+s"(ps.R[0]), "+s"(ps.R[1]), "+s"(ps.R[2]), "+s"(ps.R[3]), "+s"(ps.R[4]),
+                      "+s"(ps.R[5]), "+s"(ps.R[6]), "+s"(ps.R[7]), "+s"(ps.R[8]), "+s"(ps.t[0]), "+s"(ps.t[1]), "+s"(ps.t[2]));
+  }
+  if (start >= pd.n || !active) return;
+  const int count = min(chunk, (int)(pd.n - start));
+  const GPtr<T> px = (GPtr<T>)(static_cast<const T *>(pd.x) + start);
+  const GPtr<T> py = (GPtr<T>)(static_cast<const T *>(pd.y) + start);
+  const GPtr<T> pz = (GPtr<T>)(static_cast<const T *>(pd.z) + start);
+  // coalesced point loads; lanes past the end of the chunk re-read its last point
+  if constexpr (BUF) {
+    if (!early) {
+      const __amdgpu_buffer_rsrc_t rx = make_raw_buffer((const T *)px, (unsigned)count * (unsigned)sizeof(T));
+      const __amdgpu_buffer_rsrc_t ry = make_raw_buffer((const T *)py, (unsigned)count * (unsigned)sizeof(T));
+      const __amdgpu_buffer_rsrc_t rz = make_raw_buffer((const T *)pz, (unsigned)count * (unsigned)sizeof(T));
+#pragma unroll
+      for (int k = 0; k < PPT; ++k) {
+        const int poff = min(tid + k * NT, count - 1) * (int)sizeof(T);
+        X[k] = buf_load_elem<T>(rx, poff); Y[k] = buf_load_elem<T>(ry, poff); Z[k] = buf_load_elem<T>(rz, poff);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) {
+      const int jj = min(tid + k * NT, count - 1);
+      X[k] = px[jj]; Y[k] = py[jj]; Z[k] = pz[jj];
+    }
+  }
+  const double sum = fused_chunk<T, PPT, 0, NT, false, BUF, IMG32, PoseLite<T>>(pd, ps, X, Y, Z, count, s_red, s_box, (T *)nullptr, 0,
+                                                                                 tid < kAccSlots ? tid : -1);
+  if (tid < kAccSlots) partials[(size_t)pc.out_row * kAccSlots + tid] = sum;
+}
+
 // SIDE instantiations of the LM kernels.  Problem p's PriorDesc (ea_prior.h; the table sits behind the group table) is
 // fetched one 8-byte word per lane beside the state words, before the fold (prior_word), and parked in LDS with them
 // (prior_lds) -- its load is not a dependent round trip on the state machine's critical path.  After the barrier lane 0 adds
@@ -1872,6 +1964,163 @@ __global__ __launch_bounds__(kLmThreads) void ea_lm_step_kernel(
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
   EA_LM_STAMP(5, ev_);
+}
+
+// ---- K trust-region runs per problem in lock-step (ea_batch_solve_starts) ------------------------------------------------
+//
+// The step of one (live position, problem) of a multi-start solve, one 256-lane workgroup each: ea_lm_step_kernel's body on
+// the slot live[off + pose] * count + problem.  The rows of the start are folded with reduce_tiles<256, 4> over
+// pose * rows + the problem's range -- poses_fold_one's order, so the sums a start steps on are what ea_batch_eval_poses
+// folds for that pose, wherever in the list the start sits.  Priors and the mask enter through LDS (prior_into_lds), lane 0
+// runs lm_begin / lm_advance on a member-by-member register copy of the state, the candidate pose is published lane-parallel
+// into the start's own slot (active = 0 once its solve has ended), and a start that ends delivers its final state and trace
+// rows into pinned host memory and takes itself off its start's count of running problems (alive).
+// Nobody waits for another workgroup: what a launch reads of the list, no launch of the same iteration writes (the list and
+// its length are ping-ponged by the iteration's parity), and the kernel boundary is the only ordering.
+template <int STRAT, bool SIDE>
+__device__ __forceinline__ void starts_step_one(const StartsStep &a, const LMOptions &opt, int pose, int problem, int start_k) {
+  __shared__ __align__(16) double s_part[reduce_tiles_lds<kLmThreads>()];
+  __shared__ double s_acc[kAccSlots];
+  __shared__ LMState s_st;
+  __shared__ PoseState s_ps;
+  __shared__ int s_trace_it;
+  constexpr int kStateWords = (int)(sizeof(LMState) / 8);
+  constexpr int kPoseDoubles = 4 + 3 + 9 + 27, kPoseFloats = 9 + 3 + 27;
+  const int tid = threadIdx.x;
+  const int p = start_k * a.count + problem;
+  const GroupDesc gd = a.groups[problem];
+  const int running = a.states[p].running;
+  const double state_word = tid < kStateWords ? reinterpret_cast<const double *>(a.states + p)[tid] : 0.0;
+  double pw = 0.0;
+  if constexpr (SIDE) pw = prior_word(a.side, a.count, problem, tid);
+  const int base = pose * a.rows_per_pose;
+  reduce_tiles<kLmThreads, 4>(a.rows, base + gd.tile_begin, base + gd.tile_end, s_part, s_acc);
+  if (!running) return;  // uniform: this problem of the start has ended, a sibling keeps the start in the list
+  if (tid < kStateWords) reinterpret_cast<double *>(&s_st)[tid] = state_word;
+  if constexpr (SIDE) {
+    if (tid < kPriorWords) reinterpret_cast<double *>(&prior_lds())[tid] = pw;
+  }
+  __syncthreads();
+  if constexpr (SIDE) prior_into_lds(s_st, s_acc, tid);
+  LMTrace *const tr = a.traces ? a.traces + p : nullptr;
+  LMTrace *const host_tr = a.host_traces ? a.host_traces + p : nullptr;
+  LMPending pend;
+  double acc[kAccSlots];
+  if (tid == 0) {
+    LMState st;
+    lm_copy_state(&st, &s_st);
+#pragma unroll
+    for (int i = 0; i < kAccSlots; ++i) acc[i] = s_acc[i];
+    if (EA_UNLIKELY(st.num_evals == 0)) lm_begin<STRAT, false, SIDE>(&st, a.cold + p, tr, &opt, acc, &pend);
+    else lm_advance<STRAT, false, SIDE>(&st, a.cold + p, tr, &opt, acc, &pend);
+    make_pose_core(st.cand, st.rot_transposed, st.running, &s_ps, /*zero_unused_G=*/false);
+    lm_copy_state(&s_st, &st);
+    s_trace_it = pend.trace_it;
+  }
+  __syncthreads();
+  if (tid < kStateWords) reinterpret_cast<double *>(a.states + p)[tid] = reinterpret_cast<const double *>(&s_st)[tid];
+  {
+    // pose: doubles copied by lanes 64.., float mirrors converted by lanes 128.., flags by lane 192 (ea_lm_step_kernel)
+    const double *pd_src = reinterpret_cast<const double *>(&s_ps);
+    const int d = tid - 64, f = tid - 128;
+    const bool skip_g = s_ps.unit_q != 0;
+    if (d >= 0 && d < kPoseDoubles) reinterpret_cast<double *>(a.poses + p)[d] = (skip_g && d >= 16) ? 0.0 : pd_src[d];
+    if (f >= 0 && f < kPoseFloats) {
+      const double v = f < 9 ? s_ps.R[f] : (f < 12 ? s_ps.t[f - 9] : (skip_g ? 0.0 : s_ps.G[f - 12]));
+      (&a.poses[p].Rf[0])[f] = (float)v;
+    }
+    if (tid == 192) { a.poses[p].unit_q = s_ps.unit_q; a.poses[p].active = s_ps.active; }
+  }
+  if (tid == 0) lm_flush(&pend, a.cold + p, tr, acc);
+  if (!s_st.running) {  // uniform: this solve ends with this launch -- final state and trace rows into pinned host memory
+    if (tid < kStateWords) reinterpret_cast<double *>(a.host_states + p)[tid] = reinterpret_cast<const double *>(&s_st)[tid];
+    if (host_tr) {
+      const int last = min(s_st.iteration, kTrace - 1);  // rows 0 .. last exist
+      auto copy_row = [&](int r) {
+        host_tr->it_cost[r] = tr->it_cost[r];
+        host_tr->it_cost_change[r] = tr->it_cost_change[r];
+        host_tr->it_gradient_max_norm[r] = tr->it_gradient_max_norm[r];
+        host_tr->it_step_norm[r] = tr->it_step_norm[r];
+        host_tr->it_relative_decrease[r] = tr->it_relative_decrease[r];
+        host_tr->it_radius[r] = tr->it_radius[r];
+        host_tr->it_successful[r] = tr->it_successful[r];
+      };
+      if (s_trace_it == last) {
+        // the usual end: rows < last come from earlier launches (one lane each), lane 0 holds the last one
+        if (tid < last) copy_row(tid);
+        if (tid == 0) {
+          LMPending h = pend;
+          h.store_system = 0;
+          lm_flush(&h, a.cold + p, host_tr, acc);
+        }
+      } else if (tid == 0) {
+        // rows written by this very launch through lm_trace (invalid steps): lane 0 wrote them, lane 0 copies them
+        __threadfence();
+        for (int r = 0; r <= last; ++r) copy_row(r);
+      }
+    }
+    __threadfence_system();
+    if (tid == 0) __hip_atomic_fetch_add(a.alive + start_k, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// One workgroup per (pose of the piece, problem).  In the iteration's LAST step launch every workgroup -- with or without
+// work -- counts itself in on an agent-scope counter once its stores are out; the last arrival re-arms the counter, rebuilds
+// the live list in order (a start stays while any of its problems runs: alive[start] > 0), writes the new length and posts
+// {tag, iterations complete, n_live} to the one pinned word the host polls, with release order.
+template <int STRAT, bool SIDE>
+__global__ __launch_bounds__(kLmThreads) void ea_lm_step_starts_kernel(StartsStep a, LMOptions opt_arg) {
+  __shared__ int s_is_last;
+  __shared__ unsigned long long s_masks[4];
+  static_assert(sizeof(LMState) % 8 == 0 && (int)(sizeof(LMState) / 8) <= kLmThreads, "one 8-byte state word per lane");
+  static_assert(offsetof(PoseState, Rf) == (4 + 3 + 9 + 27) * 8 && offsetof(PoseState, unit_q) == (4 + 3 + 9 + 27) * 8 + (9 + 3 + 27) * 4,
+                "PoseState layout");
+  LMOptions opt = opt_arg;
+  asm volatile("" : "+s"(opt.max_num_iterations), "+s"(opt.function_tolerance), "+s"(opt.gradient_tolerance),
+                    "+s"(opt.parameter_tolerance), "+s"(opt.initial_trust_region_radius), "+s"(opt.max_trust_region_radius),
+                    "+s"(opt.min_trust_region_radius), "+s"(opt.min_relative_decrease), "+s"(opt.min_lm_diagonal),
+                    "+s"(opt.max_lm_diagonal), "+s"(opt.max_num_consecutive_invalid_steps), "+s"(opt.jacobi_scaling),
+                    "+s"(opt.strategy));
+  const int tid = threadIdx.x;
+  const int n_live = *a.n_in;
+  int pose, problem;
+  starts_step_item(blockIdx.x, a.count, &pose, &problem);
+  if (starts_position_live(a.off, pose, n_live))  // (uniform)
+    starts_step_one<STRAT, SIDE>(a, opt, pose, problem, a.live_in[a.off + pose]);
+  if (!a.last) return;  // (uniform)
+  __syncthreads();      // every lane's stores are issued (and fenced where the host reads them) before lane 0 counts in
+  if (tid == 0) {
+    __threadfence_system();
+    const unsigned int prev = __hip_atomic_fetch_add(a.counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    s_is_last = prev == gridDim.x - 1;
+  }
+  __syncthreads();
+  if (!s_is_last) return;  // (uniform)
+  int kept = 0;
+  for (int first = 0; first < n_live; first += kLmThreads) {  // (uniform bounds)
+    const int i = first + tid;
+    int start_k = 0;
+    bool keep = false;
+    if (i < n_live) {
+      start_k = a.live_in[i];
+      keep = __hip_atomic_load(a.alive + start_k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > 0;
+    }
+    const unsigned long long m = __ballot(keep);
+    if ((tid & 63) == 0) s_masks[tid >> 6] = m;
+    __syncthreads();
+    uint64_t masks[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) masks[k] = s_masks[k];
+    if (keep) a.live_out[starts_compact_slot(masks, tid >> 6, tid & 63, kept)] = start_k;
+    kept += starts_compact_kept(masks);
+    __syncthreads();
+  }
+  if (tid == 0) {
+    *a.n_out = kept;
+    __hip_atomic_store(a.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __threadfence_system();
+    __hip_atomic_store(a.host_word, (unsigned long long)starts_word(a.tag, a.iteration, kept), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
 }
 
 // ---- one launch per LM iteration ----------------------------------------------------------------------------------------
@@ -2338,6 +2587,38 @@ hipError_t launch_poses_fold(int nt, const PosesFold &fold, hipStream_t stream) 
   if (nt == 1024) hipLaunchKernelGGL(ea_poses_fold_kernel<1024>, dim3(fold.n), dim3(1024), 0, stream, fold);
   else hipLaunchKernelGGL(ea_poses_fold_kernel<256>, dim3(fold.n), dim3(256), 0, stream, fold);
   return hipGetLastError();
+}
+
+// ea_eval_starts_kernel: ea_eval_poses_kernel's launch of p.g poses over the piece [off, off + p.g) of a live list
+hipError_t launch_eval_starts(const EvalLaunch &s, const PosesLaunch &p, const ProblemDesc *probs, const PoseState *poses,
+                              double *partials, const int *live, const int *n_live, int off, hipStream_t stream) {
+  if (s.variant || s.lds_bytes > 0 || s.wide || !s.terms_are_groups || s.chunk != s.nt * s.ppt || s.nt != kLmThreads) return hipErrorInvalidValue;
+  if (p.g <= 0 || p.rows < 0 || off < 0 || (int64_t)p.rows * p.g > (int64_t)1 << 28) return hipErrorInvalidValue;
+  if (p.rows == 0) return hipSuccess;  // not a single point in the batch
+  const int shape = poses_shape(s.xcd_remap != 0, p.order, p.single != 0, 0);
+  const dim3 grid(poses_grid(p.rows, p.g, 0));
+  return dispatch_dtype(s.dtype, [&](auto TT) { return dispatch_int<1, 2, 4>(s.ppt, [&](auto PPT) {
+    return dispatch_bool(s.buffer_loads, [&](auto BUF) { return dispatch_bool(s.img32, [&](auto IMG32) {
+      typedef typename decltype(TT)::type T;
+      constexpr int P = decltype(PPT)::value;
+      constexpr bool B = decltype(BUF)::value, I = decltype(IMG32)::value;
+      if constexpr (!fused_exists<T, P, 0, kLmThreads, false, B, I>()) return hipErrorInvalidValue;
+      else {
+        hipLaunchKernelGGL((ea_eval_starts_kernel<T, P, 0, kLmThreads, false, B, I>), grid, dim3(kLmThreads), (size_t)kHdrBytes, stream,
+                           s.x0, s.y0, s.z0, s.n0, shape, p.g, p.rows, probs, poses, partials, live, n_live, off);
+        return hipGetLastError();
+      }
+    }); });
+  }); });
+}
+
+hipError_t launch_lm_step_starts(int g, const StartsStep &a, const LMOptions &lo, int side, hipStream_t stream) {
+  if (g <= 0 || a.count <= 0 || (int64_t)g * a.count > kMaxStartSlots) return hipErrorInvalidValue;
+  return dispatch_bool(lo.strategy != 0, [&](auto STRAT) { return dispatch_bool(side, [&](auto SIDE) {
+    hipLaunchKernelGGL((ea_lm_step_starts_kernel<decltype(STRAT)::value ? 1 : 0, decltype(SIDE)::value>), dim3(starts_step_grid(g, a.count)),
+                       dim3(kLmThreads), 0, stream, a, lo);
+    return hipGetLastError();
+  }); });
 }
 
 // evaluation into `partials` + the fold of fold.prev_rows -> fold.prev_out in one launch (ea_eval_fold_kernel): plain

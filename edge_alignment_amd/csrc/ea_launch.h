@@ -65,6 +65,23 @@ struct LMIterPairs {
   const LMState *st_in; LMState *st_out;
   const LMCold *cold_in; LMCold *cold_out;
 };
+// A multi-start solve (ea_batch_solve_starts, ea_starts_map.h): what the (evaluate, step) pair of one piece of the live list
+// works on.  Every array is slot-major (slot = start * count + problem); live_in / n_in: the list of this iteration,
+// live_out / n_out: the one the iteration's last step launch (`last`) rebuilds for the next; alive[start]: problems of the
+// start still running; counter / host_word: the last arrival's count and the word it posts; traces / host_traces: nullable.
+struct StartsStep {
+  const GroupDesc *groups;  // row ranges in the pose path's chunking
+  const GroupDesc *side;    // the batch's own group table, side table behind it (SIDE instantiations)
+  const double *rows;
+  PoseState *poses; LMState *states; LMCold *cold; LMTrace *traces;
+  LMState *host_states; LMTrace *host_traces;
+  const int *live_in, *n_in;
+  int *live_out, *n_out, *alive;
+  unsigned int *counter;
+  unsigned long long *host_word;
+  int count, rows_per_pose, off, last;
+  unsigned iteration, tag;
+};
 struct RowsLaunch {
   int dtype = 0, variant = 0, buffer_loads = 0, img32 = 0;
   int layout = 0;   // 0 = J row-major [rows][6], 1 = column-major [6][rows]
@@ -85,6 +102,11 @@ hipError_t launch_eval_poses_grid(const EvalLaunch &s, const ProblemDesc *probs,
 hipError_t launch_eval_poses(const EvalLaunch &s, const PosesLaunch &p, const ProblemDesc *probs, const PoseState *poses,
                              double *partials, const PosesFold &fold, hipStream_t stream);
 hipError_t launch_poses_fold(int nt, const PosesFold &fold, hipStream_t stream);
+// ea_eval_starts_kernel: the poses live[off .. off + p.g) of a multi-start solve, as ea_eval_poses_kernel evaluates them,
+// without riders; positions from *n_live on return at once.  ea_lm_step_starts_kernel: g x a.count workgroups.
+hipError_t launch_eval_starts(const EvalLaunch &s, const PosesLaunch &p, const ProblemDesc *probs, const PoseState *poses,
+                              double *partials, const int *live, const int *n_live, int off, hipStream_t stream);
+hipError_t launch_lm_step_starts(int g, const StartsStep &a, const LMOptions &lo, int side, hipStream_t stream);
 hipError_t launch_pixel_cost(int dtype, const ProblemDesc *probs, int problem, int n, const PoseState *poses, void *partials,
                              hipStream_t stream);
 hipError_t launch_eval_rows(const RowsLaunch &s, const ProblemDesc *probs, int nterms, const PoseState *poses, void *r_out,

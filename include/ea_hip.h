@@ -332,6 +332,31 @@ int ea_batch_eval_poses(ea_batch *b, int K, const double *q, const double *t, do
 int ea_batch_set_poses(ea_batch *b, int K, const double *q, const double *t);
 int ea_batch_eval_resident_poses(ea_batch *b, double *cost, double *JtJ, double *Jtr, int64_t *n_invalid);
 
+/* Multi-start: K trust-region solves of every problem of the batch from K different starting poses, in lock-step on the device
+ * -- K independent ceres::Solve calls on the same ceres::Problem from K initial values, for a caller that does not trust one
+ * start (relocalisation, a dropped frame, a wide baseline) and wants the best of several.
+ * q: K x count x 4, t: K x count x 3 (start k of problem i at [k * count + i], the layout of ea_batch_eval_poses),
+ * overwritten with the K x count solved poses; summaries: K x count or NULL; best: count entries or NULL --
+ * the start with the smallest final_cost among those whose termination is not EA_FAILURE (ties: lowest k), -1 if none.
+ * Every start is a complete solve under `opt` (LM or dogleg, Ceres' radius rules and termination tests, its own summary and
+ * trace); the problem's NormalPriors and constant coordinates apply to every start of it; a start whose first evaluation fails
+ * ends with EA_WHY_INITIAL_EVAL_FAILED on its own.  Per iteration one pose-batched evaluation launch covers the starts still
+ * running and one step launch runs their state machines; finished starts leave the launches.  A start's result -- pose,
+ * iterations, trace -- is bit for bit what the same start gives alone (K = 1): it does not depend on K, on the other starts,
+ * on "poses_per_launch" or on when another start finished, and it_cost[0] is the cost ea_batch_eval_poses returns at the
+ * start pose.  (Against ea_batch_solve from the same start the iterates agree up to rounding only: the pose-batched launch
+ * cuts the partial rows differently.)
+ * Covered in lock-step: the batches ea_batch_eval_poses evaluates in its flat form -- plain functor, one term per problem,
+ * any dtype -- at the pose path's default 256-thread shape; every other batch (variant functors, shared-pose terms, LDS
+ * staging, "wide_accumulate", "threads" = 1024) is solved start after start through ea_batch_solve.  ea_batch_get_info
+ * "starts_form" reports which form the last call took (1 = lock-step), "starts_launches" its evaluation launches.
+ * K < 1 or K x count > 16384: EA_ERR_INVALID_ARG.  Poses made resident by ea_batch_set_poses SURVIVE the call:
+ * ea_batch_eval_resident_poses afterwards returns what it returned before. */
+int ea_batch_solve_starts(ea_batch *b, int K, const ea_options *opt, double *q, double *t,
+                          ea_summary *summaries, int *best);
+int ea_solve_starts(ea_problem *p, int K, const ea_options *opt, double *q, double *t,
+                    ea_summary *summaries, int *best);   /* one problem: count = 1 */
+
 /* ---- pose covariance: ceres::Covariance (Ceres <= 2.1) at one pose per problem ----------------------------------------
  * C = (JtJ)^-1 over the tangent coordinates [delta(3) | t(3)]: the JtJ ea_eval returns at that pose (every term of the
  * problem summed in), loss-corrected rows sum rho' J J^T when apply_loss_function != 0 (every shipped loss has
@@ -460,8 +485,10 @@ int ea_eval_rows_device(ea_problem *p, const double q[4], const double t[3], int
 /* ---- tuning ---------------------------------------------------------------------------- */
 /* tuning knobs: key in {"lds_bytes", "points_per_thread", "use_lds", "xcd_remap", "threads", "buffer_loads",
  * "solve_streams", "rows_staged", "rows_nontemporal", "wide_accumulate", "dt_f32", "poses_per_launch", "poll_results",
- * "fused_iterations", "zero_copy_poses"};
+ * "fused_iterations", "zero_copy_poses", "starts_events"};
  * value < 0 restores the default.
+ * "starts_events" = 1 (measurement): ea_batch_solve_starts brackets the launches it queues with an event pair and waits
+ * for it; ea_batch_get_info "starts_device_ns" / "starts_iterations" then report the device time and the iterations queued.
  * "dt_f32" = 0: an fp64 batch reads its fp64 images even where a float32 mirror holds them exactly (default: the mirror
  * when every term has one; results are bit-identical either way).  "poses_per_launch" = g > 0 caps the poses one
  * evaluation launch of ea_batch_eval_poses covers (default: enough to fill the chip, ~32k workgroups).  "poll_results" = 0:
