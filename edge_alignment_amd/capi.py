@@ -30,6 +30,7 @@ EXPORTED = [
     "ea_eval", "ea_eval_points", "ea_cost", "ea_problem_pixel_cost", "ea_solve",
     "ea_release_cached_memory", "ea_host_alloc", "ea_host_free", "ea_batch_create", "ea_batch_destroy", "ea_batch_count", "ea_batch_eval", "ea_batch_solve",
     "ea_batch_eval_poses", "ea_batch_set_poses", "ea_batch_eval_resident_poses", "ea_batch_solve_starts", "ea_solve_starts",
+    "ea_batch_cost_poses", "ea_batch_cost_resident_poses", "ea_batch_search_starts", "ea_search_starts",
     "ea_solve_pyramid", "ea_solve_sharded", "ea_solve_sharded_device",
     "ea_comm_get_unique_id", "ea_comm_create", "ea_comm_create_all", "ea_comm_destroy", "ea_comm_rank", "ea_comm_size",
     "ea_comm_gather_poses", "ea_solve_sharded_comm", "ea_comm_get_info", "ea_hip_runtime_copies", "ea_tracker_create", "ea_tracker_destroy", "ea_tracker_problem", "ea_tracker_push_frame",
@@ -161,6 +162,11 @@ def load():
     L.ea_batch_eval_resident_poses.argtypes = [vp, dp, dp, dp, i64p]
     L.ea_batch_solve_starts.argtypes = [vp, C.c_int, C.POINTER(Options), dp, dp, C.POINTER(Summary), C.POINTER(C.c_int)]
     L.ea_solve_starts.argtypes = [vp, C.c_int, C.POINTER(Options), dp, dp, C.POINTER(Summary), C.POINTER(C.c_int)]
+    L.ea_batch_cost_poses.argtypes = [vp, C.c_int, dp, dp, dp, i64p]
+    L.ea_batch_cost_resident_poses.argtypes = [vp, dp, i64p]
+    L.ea_batch_search_starts.argtypes = [vp, C.c_int, dp, dp, C.c_int, C.POINTER(Options), dp, dp, C.POINTER(C.c_int),
+                                         C.POINTER(Summary), C.POINTER(C.c_int)]
+    L.ea_search_starts.argtypes = L.ea_batch_search_starts.argtypes
     L.ea_batch_bench_eval.argtypes = [vp, dp, dp, C.c_int, C.c_int, dp, dp]
     L.ea_batch_bench_steps.argtypes = [vp, C.c_int, dp]
     L.ea_batch_bench_capture.argtypes = [vp, C.c_int]
@@ -643,6 +649,22 @@ class Problem:
         _check(load().ea_solve_starts(self._h, K, C.byref(o), _dp(q), _dp(t), s, C.byref(best)))
         return q, t, [summary_to_dict(x) for x in s], best.value
 
+    def search_starts(self, q, t, M, **opts):
+        """rank K candidate poses by cost-only evaluation, solve the M best in lock-step (ea_search_starts): q (K, 4), t (K, 3)
+        -> (q (M, 4), t (M, 3), picked (M,) candidate indices by rank, M summaries, best = index into the ranks)"""
+        q, t = _f64(q).reshape(-1, 4), _f64(t).reshape(-1, 3)
+        K, M = q.shape[0], int(M)
+        assert t.shape[0] == K
+        o = default_options(**opts)
+        m = max(M, 1)
+        qo, to = np.zeros((m, 4)), np.zeros((m, 3))
+        picked = np.full(m, -1, dtype=np.intc)
+        s = (Summary * m)()
+        best = C.c_int(-1)
+        _check(load().ea_search_starts(self._h, K, _dp(q), _dp(t), M, C.byref(o), _dp(qo), _dp(to),
+                                       picked.ctypes.data_as(C.POINTER(C.c_int)), s, C.byref(best)))
+        return qo, to, picked.astype(np.int64), [summary_to_dict(x) for x in s], best.value
+
     def covariance(self, q, t, **opts):
         """ceres::Covariance at (q, t) (ea_problem_covariance); opts: fields of ea_covariance_options -> covariance_to_dict"""
         q, t = _f64(q), _f64(t)
@@ -923,6 +945,54 @@ class Batch:
             ptrs = out["_ptrs"] = (_dp(out["cost"]), _dp(out["JtJ"]), _dp(out["Jtr"]), out["n_invalid"].ctypes.data_as(C.POINTER(C.c_int64)))
         _check(load().ea_batch_eval_resident_poses(self._h, *ptrs))
         return out
+
+    def cost_poses(self, q, t):
+        """cost-only evaluation of every problem at K poses (ea_batch_cost_poses): q (K, n, 4), t (K, n, 3) -> dict of
+        cost (K, n), n_invalid (K, n); the poses stay resident"""
+        n = len(self)
+        q, t = _f64(q).reshape(-1, n, 4), _f64(t).reshape(-1, n, 3)
+        K = q.shape[0]
+        assert t.shape[0] == K
+        cost, bad = np.zeros((K, n)), np.zeros((K, n), dtype=np.int64)
+        _check(load().ea_batch_cost_poses(self._h, K, _dp(q), _dp(t), _dp(cost), bad.ctypes.data_as(C.POINTER(C.c_int64))))
+        self._resident_K = K
+        return dict(cost=cost, n_invalid=bad)
+
+    def cost_resident_poses(self, out=None, fetch=True):
+        """the cost-only evaluation of the resident poses (ea_batch_cost_resident_poses); `out`: the dict of a previous call to
+        fill again; fetch=False: run and synchronise, hand nothing back"""
+        if not fetch:
+            _check(load().ea_batch_cost_resident_poses(self._h, None, None))
+            return None
+        if out is None:
+            K, n = self._resident_K, len(self)
+            out = dict(cost=np.zeros((K, n)), n_invalid=np.zeros((K, n), dtype=np.int64))
+        ptrs = out.get("_ptrs")
+        if ptrs is None:
+            ptrs = out["_ptrs"] = (_dp(out["cost"]), out["n_invalid"].ctypes.data_as(C.POINTER(C.c_int64)))
+        _check(load().ea_batch_cost_resident_poses(self._h, *ptrs))
+        return out
+
+    def search_starts(self, q, t, M, summaries=True, **opts):
+        """rank K candidate poses per problem by cost-only evaluation and solve the M best of each in lock-step
+        (ea_batch_search_starts): q (K, n, 4), t (K, n, 3) -> (q (M, n, 4), t (M, n, 3), picked (M, n) candidate indices by
+        rank, M lists of n summaries (None with summaries=False), best (n,) = index into the ranks).  Afterwards the K
+        candidates are the batch's resident poses."""
+        n = len(self)
+        q, t = _f64(q).reshape(-1, n, 4), _f64(t).reshape(-1, n, 3)
+        K, M = q.shape[0], int(M)
+        assert t.shape[0] == K
+        o = default_options(**opts)
+        m = max(M, 1)
+        qo, to = np.zeros((m, n, 4)), np.zeros((m, n, 3))
+        picked = np.full((m, n), -1, dtype=np.intc)
+        s = (Summary * (m * n))() if summaries else None
+        best = np.zeros(n, dtype=np.intc)
+        _check(load().ea_batch_search_starts(self._h, K, _dp(q), _dp(t), M, C.byref(o), _dp(qo), _dp(to),
+                                             picked.ctypes.data_as(C.POINTER(C.c_int)), s, best.ctypes.data_as(C.POINTER(C.c_int))))
+        self._resident_K = K
+        out = [[summary_to_dict(s[k * n + i]) for i in range(n)] for k in range(m)] if summaries else None
+        return qo, to, picked.astype(np.int64), out, best.astype(np.int64)
 
     def bench_resident_poses(self, reps, evaluations_only=False):
         """(ms per run of the resident poses' launches -- one event pair on the batch's stream around `reps` runs --,

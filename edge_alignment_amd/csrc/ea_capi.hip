@@ -28,6 +28,7 @@
 #include "ea_lm.h"
 #include "ea_poses_map.h"
 #include "ea_prior.h"
+#include "ea_search_rank.h"
 #include "ea_spin.h"
 #include "ea_starts_map.h"
 #include "ea_types.h"
@@ -336,6 +337,11 @@ struct ea_batch {
   int kp_rows_cap = 0;
   int t_kp_order = 0;                 // tuning key "poses_order": 1 = an XCD walks the rows of a pose instead of the poses of a row (A/B)
   std::vector<KposesMark> kp_marks;   // the folds of the last call: sequence number, first pose, poses
+  // ea_batch_cost_resident_poses: the narrow partials of one launch (kCostPartialBytes per row of a pose), tuning key
+  // "cost_form" (0: always the fall-back, the full evaluation with only the cost fetched) and what the last call ran
+  unsigned char *d_kcost = nullptr;
+  size_t kcost_bytes = 0;
+  int t_cost_form = 1, last_cost_form = 0;
   // one launch per LM iteration (ea_lm_iter_kernel): the second buffer of each pair a launch reads / writes -- states and cold
   // systems [LMState x count | LMCold x count] and partial rows -- beside d_states, d_cold, d_partials
   unsigned char *d_iter_alt = nullptr;
@@ -1443,9 +1449,9 @@ static bool kposes_flat(const ea_batch *b) { return !b->any_variant && b->lds_by
 static void kposes_free_tables(ea_batch *b) {
   if (b->d_kblock) cached_free(b->d_kblock);
   else { cached_free(b->d_kprobs); cached_free(b->d_kgroups); }
-  cached_free(b->d_krows);
-  b->d_kblock = nullptr; b->d_kprobs = nullptr; b->d_kgroups = nullptr; b->d_krows = nullptr;
-  b->kp_G = 0; b->kp_rows_cap = 0;
+  cached_free(b->d_krows); cached_free(b->d_kcost);
+  b->d_kblock = nullptr; b->d_kprobs = nullptr; b->d_kgroups = nullptr; b->d_krows = nullptr; b->d_kcost = nullptr;
+  b->kp_G = 0; b->kp_rows_cap = 0; b->kcost_bytes = 0;
 }
 
 // What the pose-batched launches read beside the batch's own tables, and the partial rows of G poses; the tables are rebuilt
@@ -1531,6 +1537,7 @@ static int kposes_reserve(ea_batch *b, int K) {
   HIPCHK(cached_host_malloc(reinterpret_cast<void **>(&b->h_kqt), n * 7 * sizeof(double), hipHostMallocDefault, b->device));
   HIPCHK(cached_host_malloc(reinterpret_cast<void **>(&b->h_kout), n * sizeof(EvalOut), hipHostMallocMapped, b->device));
   HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&b->dv_kout), b->h_kout, 0));
+  std::memset(b->h_kout, 0, n * sizeof(EvalOut));  // (a cost-only call fills two slots of a result; the priors add to all)
   b->kp_cap = cap;
   return EA_OK;
 }
@@ -1620,17 +1627,13 @@ static void kposes_unpack(ea_batch *b, size_t first, size_t n, double *cost, dou
                     Jtr ? Jtr + 6 * first : nullptr, n_invalid ? n_invalid + first : nullptr);
 }
 
-extern "C" int ea_batch_eval_resident_poses(ea_batch *b, double *cost, double *JtJ, double *Jtr, int64_t *n_invalid) {
-  if (!b) return fail(EA_ERR_INVALID_ARG, "NULL argument");
-  int rc = batch_build(b);
-  if (rc != EA_OK) return rc;
-  const int K = b->kp_K;
-  if (K < 1 || b->kp_G < 1) return fail(EA_ERR_STATE, "no poses resident (ea_batch_set_poses first; a change of the batch's problems drops them)");
+// The results of the launches enqueue_resident_poses / enqueue_resident_cost put on the stream, out of pinned memory.  The
+// results of launch i are unpacked as soon as its fold has raised the flag -- launch i + 1 is still running then -- so that
+// only the last launch's remain behind the final wait.  The poll is bounded like wait_results: should a flag not show up,
+// the stream is synchronised (everything is complete then, and a device error surfaces as the error it is).
+static int kposes_collect(ea_batch *b, int K, double *cost, double *JtJ, double *Jtr, int64_t *n_invalid) {
+  int rc;
   const size_t count = b->probs.size();
-  if ((rc = enqueue_resident_poses(b, K, true, true)) != EA_OK) return rc;
-  // The results of launch i are unpacked as soon as its fold has raised the flag -- launch i + 1 is still running then --
-  // so that only the last launch's remain behind the final wait.  The poll is bounded like wait_results: should a flag not
-  // show up, the stream is synchronised (everything is complete then, and a device error surfaces as the error it is).
   size_t done = 0;
   bool drained = false;
   for (size_t m = 0; m + 1 < b->kp_marks.size() && !drained; ++m) {
@@ -1650,6 +1653,83 @@ extern "C" int ea_batch_eval_resident_poses(ea_batch *b, double *cost, double *J
   if (!drained && (rc = wait_results(b)) != EA_OK) return rc;
   kposes_unpack(b, done, (size_t)K * count - done, cost, JtJ, Jtr, n_invalid);
   return EA_OK;
+}
+
+extern "C" int ea_batch_eval_resident_poses(ea_batch *b, double *cost, double *JtJ, double *Jtr, int64_t *n_invalid) {
+  if (!b) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  int rc = batch_build(b);
+  if (rc != EA_OK) return rc;
+  const int K = b->kp_K;
+  if (K < 1 || b->kp_G < 1) return fail(EA_ERR_STATE, "no poses resident (ea_batch_set_poses first; a change of the batch's problems drops them)");
+  if ((rc = enqueue_resident_poses(b, K, true, true)) != EA_OK) return rc;
+  return kposes_collect(b, K, cost, JtJ, Jtr, n_invalid);
+}
+
+// ---- cost-only evaluation of the resident poses (ea_batch_cost_resident_poses / ea_batch_cost_poses) --------------------
+// Everything around the kernel is the evaluation path's: the resident poses, G and the even split of K over launches, the
+// pose path's tables and launch shape, one synchronisation, results unpacked launch by launch, priors added on the host at
+// each result's own pose (the cost slot of prior_add).  The kernel pair is ea_cost_poses_kernel -- the same work items, one
+// 16-byte partial {cost, failed functors} per workgroup -- and ea_cost_fold_kernel as a launch of its own behind every
+// evaluation launch (one array of narrow partials; nothing rides), which writes the two values into the cost and invalid
+// slots of the result in pinned memory and raises the flag to the launch's sequence number.  A result is a fixed-order sum
+// over (chunk, lane, wave) and the rows of its pose: it does not depend on G, the split or the item order.
+static int enqueue_resident_cost(ea_batch *b, int K) {
+  const int count = (int)b->probs.size(), per = poses_launch_size(K, b->kp_G), rows = b->kp_ntiles;
+  b->kp_marks.clear();
+  if (b->done_seq > 0x7fffffff - (K + per - 1) / per - 2) b->done_seq = 0;  // (a call's sequence numbers do not straddle the wrap)
+  const size_t need = std::max<size_t>(1, (size_t)per * (size_t)rows) * kCostPartialBytes;
+  if (need > b->kcost_bytes) {
+    HIPCHK(hipStreamSynchronize(b->stream));
+    cached_free(b->d_kcost);
+    b->d_kcost = nullptr; b->kcost_bytes = 0;
+    HIPCHK(cached_malloc(reinterpret_cast<void **>(&b->d_kcost), need, b->device));
+    b->kcost_bytes = need;
+  }
+  PosesFold f;
+  f.count = count; f.rows_per_pose = rows; f.groups = b->d_kgroups; f.rows = reinterpret_cast<const double *>(b->d_kcost);
+  f.counter = b->d_done_count; f.host_flag = b->d_progress + 3 * (size_t)count;
+  auto fold = [&](int start, int g) -> hipError_t {
+    f.n = g * count; f.out = b->dv_kout + (size_t)start * count; f.seq = next_done_seq(b);
+    b->kp_marks.push_back({f.seq, start, g});
+    return launch_cost_fold(f, b->stream);
+  };
+  if (rows == 0) {  // not a single point in the batch: K x count zero results
+    HIPCHK(fold(0, K));
+    return EA_OK;
+  }
+  const EvalLaunch shape = eval_launch(b, /*kposes=*/true);
+  PosesLaunch pl;
+  pl.rows = rows; pl.order = b->t_kp_order; pl.single = b->nterms == 1;
+  for (int start = 0; start < K; start += per) {
+    pl.g = std::min(per, K - start);
+    HIPCHK(launch_cost_poses(shape, pl, b->d_kprobs, b->d_kposes + (size_t)start * count, b->d_kcost, b->stream));
+    HIPCHK(fold(start, pl.g));
+  }
+  return EA_OK;
+}
+
+// the batches the cost kernel serves: what ea_eval_poses_kernel covers, in 256-lane workgroups
+static bool kposes_cost_form(const ea_batch *b) { return b->t_cost_form != 0 && kposes_flat(b) && b->kp_nt == 256; }
+
+extern "C" int ea_batch_cost_resident_poses(ea_batch *b, double *cost, int64_t *n_invalid) {
+  if (!b) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  int rc = batch_build(b);
+  if (rc != EA_OK) return rc;
+  const int K = b->kp_K;
+  if (K < 1 || b->kp_G < 1) return fail(EA_ERR_STATE, "no poses resident (ea_batch_set_poses first; a change of the batch's problems drops them)");
+  if (!kposes_cost_form(b)) {  // the full evaluation, only the cost and the count fetched
+    b->last_cost_form = 0;
+    return ea_batch_eval_resident_poses(b, cost, nullptr, nullptr, n_invalid);
+  }
+  b->last_cost_form = 1;
+  if ((rc = enqueue_resident_cost(b, K)) != EA_OK) return rc;
+  return kposes_collect(b, K, cost, nullptr, nullptr, n_invalid);
+}
+
+extern "C" int ea_batch_cost_poses(ea_batch *b, int K, const double *q, const double *t, double *cost, int64_t *n_invalid) {
+  int rc = ea_batch_set_poses(b, K, q, t);
+  if (rc != EA_OK) return rc;
+  return ea_batch_cost_resident_poses(b, cost, n_invalid);
 }
 
 // (ea_hip_dev.h) `reps` runs of the resident poses' launches between one event pair on the batch's stream: milliseconds
@@ -2566,6 +2646,7 @@ extern "C" int ea_batch_set_tuning(ea_batch *b, const char *key, int value) {
   else if (k == "poses_per_launch") { b->t_kp_G = value > 0 ? value : 0; b->kp_K = 0; return EA_OK; }  // (resident poses are dropped)
   else if (k == "poses_order") { b->t_kp_order = value ? 1 : 0; return EA_OK; }
   else if (k == "starts_events") { b->t_starts_events = value > 0 ? 1 : 0; return EA_OK; }
+  else if (k == "cost_form") { b->t_cost_form = value ? 1 : 0; return EA_OK; }  // 0: cost-only calls run the full evaluation (A/B)
   else return fail(EA_ERR_INVALID_ARG, "unknown tuning key: " + k);
   b->built = false;
   return EA_OK;
@@ -2590,6 +2671,7 @@ extern "C" int ea_batch_get_info(const ea_batch *b, const char *key, int64_t *va
   else if (k == "poses_threads") *value = b->kp_nt;
   else if (k == "poses_tiles") *value = b->kp_ntiles;            // partial rows (= workgroups with work) per pose
   else if (k == "fused_iterations") *value = b->last_fused;      // the last solve ran one launch per LM iteration (ea_lm_iter_kernel)
+  else if (k == "cost_form") *value = b->last_cost_form;         // the last cost-only call: 1 = ea_cost_poses_kernel, 0 = the full evaluation
   else if (k == "starts_form") *value = b->last_starts_form;     // the last ea_batch_solve_starts: 1 = lock-step, 0 = one batch solve per start
   else if (k == "starts_launches") *value = b->last_starts_launches;  // its evaluation launches (lock-step form)
   else if (k == "starts_iterations") *value = b->last_starts_iterations;  // iterations it enqueued (look-ahead included)
@@ -3109,6 +3191,48 @@ extern "C" int ea_solve_starts(ea_problem *p, int K, const ea_options *opt, doub
   ea_batch *b;
   if ((rc = self_batch(p, &b)) != EA_OK) return rc;
   return ea_batch_solve_starts(b, K, opt, q, t, summaries, best);
+}
+
+// ---- ranked search in front of the multi-start solve -----------------------------------------------------------------------
+// K candidate poses per problem cost one cost-only evaluation each (ea_batch_cost_resident_poses); the host ranks them out of
+// pinned memory (ea_search_rank.h: eligible = finite cost and no failed functor, by ascending cost, ties to the lower index;
+// the ineligible behind them by index) and the M best per problem go into ea_batch_solve_starts.  The K candidates stay the
+// batch's resident poses.
+extern "C" int ea_batch_search_starts(ea_batch *b, int K, const double *q, const double *t, int M, const ea_options *opt,
+                                      double *q_out, double *t_out, int *picked, ea_summary *summaries, int *best) {
+  if (!b || !q || !t || !q_out || !t_out) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (K < 1 || K > (1 << 20)) return fail(EA_ERR_INVALID_ARG, "K out of range");
+  // (first for one problem, which needs nothing of the handle; then for the batch's own count)
+  if (!search_rank_args_ok(K, M, 1)) return fail(EA_ERR_INVALID_ARG, "M out of range: 1 <= M <= K, M x problems <= 16384");
+  const int count = (int)b->probs.size();
+  if (!search_rank_args_ok(K, M, count)) return fail(EA_ERR_INVALID_ARG, "M out of range: 1 <= M <= K, M x problems <= 16384");
+  int rc = ea_batch_cost_poses(b, K, q, t, nullptr, nullptr);
+  if (rc != EA_OK) return rc;
+  const size_t n = (size_t)K * count;
+  std::vector<double> cost(n);
+  std::vector<int64_t> bad(n);
+  unpack_eval_out(b->h_kout, (int)n, cost.data(), nullptr, nullptr, bad.data());  // (priors are in: kposes_unpack)
+  std::vector<int> own;
+  if (!picked) { own.resize((size_t)M * count); picked = own.data(); }
+  search_rank(K, M, count, cost.data(), bad.data(), picked);
+  for (size_t s = 0; s < (size_t)M * count; ++s) {
+    const size_t from = (size_t)picked[s] * count + s % count;
+    for (int k = 0; k < 4; ++k) q_out[4 * s + k] = q[4 * from + k];
+    for (int k = 0; k < 3; ++k) t_out[3 * s + k] = t[3 * from + k];
+  }
+  return ea_batch_solve_starts(b, M, opt, q_out, t_out, summaries, best);
+}
+
+extern "C" int ea_search_starts(ea_problem *p, int K, const double *q, const double *t, int M, const ea_options *opt,
+                                double *q_out, double *t_out, int *picked, ea_summary *summaries, int *best) {
+  if (!p || !q || !t || !q_out || !t_out) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (K < 1 || K > (1 << 20)) return fail(EA_ERR_INVALID_ARG, "K out of range");
+  if (!search_rank_args_ok(K, M, 1)) return fail(EA_ERR_INVALID_ARG, "M out of range: 1 <= M <= K, M x problems <= 16384");
+  int rc = require_device();
+  if (rc != EA_OK) return rc;
+  ea_batch *b;
+  if ((rc = self_batch(p, &b)) != EA_OK) return rc;
+  return ea_batch_search_starts(b, K, q, t, M, opt, q_out, t_out, picked, summaries, best);
 }
 
 // ---- one problem sharded by points over several processes / GPUs ----------------------------------

@@ -1697,6 +1697,263 @@ __global__ __launch_bounds__(NT) void ea_poses_fold_kernel(PosesFold fold) {
   poses_fold_one<NT>(fold, blockIdx.x);
 }
 
+// ---- cost-only pose-batched evaluation (ea_batch_cost_resident_poses) ---------------------------------------------------
+// What a ranking of candidate poses, a line search or a cost-surface probe asks for: 1/2 sum rho(r^2) and the failed-functor
+// count, nothing else.  ea_cost_poses_kernel takes ea_eval_poses_kernel's work items -- the same flat, XCD-dealt list, chunks,
+// descriptor / row-table fetch, point loads and pose slots -- and runs per point the projection, the four row loads, the
+// VALUE of the Catmull-Rom patch and rho: no derivative weights, no 1x6 row, no JtJ / Jtr products, two sums instead of 28.
+
+// the lanes' share of a work item of the pose-batched launches: descriptor and pose by value (ONE batch of scalar loads
+// behind one wait), the lane's PPT points (lanes past the end of the chunk re-read its last point).  false: nothing to
+// evaluate.  This is the head ea_eval_poses_kernel and ea_eval_starts_kernel carry inline, statement for statement; calling
+// it from those two changes the code the compiler emits for 23 of their instantiations (scripts/compare_device_code.py),
+// so they keep their own text and new kernels over the same work items start from here.
+template <typename T, int PPT, int NT, bool BUF, bool IMG32>
+__device__ __forceinline__ bool poses_item_head(const void *__restrict__ x0, const void *__restrict__ y0, const void *__restrict__ z0,
+                                                int n0, const ProblemDesc *__restrict__ probs, const PoseState *__restrict__ poses,
+                                                const PosesChunk &pc, ProblemDesc &pd, PoseLite<T> &ps, T (&X)[PPT], T (&Y)[PPT],
+                                                T (&Z)[PPT], int &count) {
+  constexpr int chunk = NT * PPT;
+  const long long start = (long long)pc.chunk * chunk;
+  const int tid = threadIdx.x;
+  const bool early = BUF && pc.term == 0 && n0 > 0;  // (uniform)
+  if constexpr (BUF) {
+    if (early) {
+      if (start >= n0) return false;
+      const int count0 = min(chunk, (int)(n0 - start));
+      const __amdgpu_buffer_rsrc_t rx = make_raw_buffer(static_cast<const T *>(x0) + start, (unsigned)count0 * (unsigned)sizeof(T));
+      const __amdgpu_buffer_rsrc_t ry = make_raw_buffer(static_cast<const T *>(y0) + start, (unsigned)count0 * (unsigned)sizeof(T));
+      const __amdgpu_buffer_rsrc_t rz = make_raw_buffer(static_cast<const T *>(z0) + start, (unsigned)count0 * (unsigned)sizeof(T));
+#pragma unroll
+      for (int k = 0; k < PPT; ++k) {
+        const int poff = min(tid + k * NT, count0 - 1) * (int)sizeof(T);
+        X[k] = buf_load_elem<T>(rx, poff); Y[k] = buf_load_elem<T>(ry, poff); Z[k] = buf_load_elem<T>(rz, poff);
+      }
+    }
+  }
+  pd = probs[pc.term];
+  int active;
+  {
+    const PoseState *psp = poses + pc.slot;
+    const T *R_ = Uni<T>::R(*psp), *t_ = Uni<T>::t(*psp);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) ps.R[i] = R_[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) ps.t[i] = t_[i];
+    ps.unit_q = psp->unit_q;
+    ps.full = psp;
+    active = psp->active;
+    asm volatile("" ::"s"(pd.x), "s"(pd.y), "s"(pd.z), "s"(IMG32 ? pd.dt32 : pd.dt), "s"(pd.n), "s"(pd.W), "s"(pd.H), "s"(pd.pitch),
+                 "s"(Uni<T>::fx(pd)), "s"(Uni<T>::fy(pd)), "s"(Uni<T>::cx(pd)), "s"(Uni<T>::cy(pd)),
+                 "s"(Uni<T>::loss_a(pd)), "s"(Uni<T>::loss_inv_b(pd)), "s"(Uni<T>::z_guard(pd)), "s"(Uni<T>::z_eps(pd)),
+                 "s"(pd.loss_kind), "s"(pd.variant));
+    asm volatile("" : "+s"(active), "+s"(ps.unit_q), "+s"(ps.R[0]), "+s"(ps.R[1]), "+s"(ps.R[2]), "+s"(ps.R[3]), "+s"(ps.R[4]),
+                      "+s"(ps.R[5]), "+s"(ps.R[6]), "+s"(ps.R[7]), "+s"(ps.R[8]), "+s"(ps.t[0]), "+s"(ps.t[1]), "+s"(ps.t[2]));
+  }
+  if (start >= pd.n || !active) return false;
+  count = min(chunk, (int)(pd.n - start));
+  const GPtr<T> px = (GPtr<T>)(static_cast<const T *>(pd.x) + start);
+  const GPtr<T> py = (GPtr<T>)(static_cast<const T *>(pd.y) + start);
+  const GPtr<T> pz = (GPtr<T>)(static_cast<const T *>(pd.z) + start);
+  if constexpr (BUF) {
+    if (!early) {
+      const __amdgpu_buffer_rsrc_t rx = make_raw_buffer((const T *)px, (unsigned)count * (unsigned)sizeof(T));
+      const __amdgpu_buffer_rsrc_t ry = make_raw_buffer((const T *)py, (unsigned)count * (unsigned)sizeof(T));
+      const __amdgpu_buffer_rsrc_t rz = make_raw_buffer((const T *)pz, (unsigned)count * (unsigned)sizeof(T));
+#pragma unroll
+      for (int k = 0; k < PPT; ++k) {
+        const int poff = min(tid + k * NT, count - 1) * (int)sizeof(T);
+        X[k] = buf_load_elem<T>(rx, poff); Y[k] = buf_load_elem<T>(ry, poff); Z[k] = buf_load_elem<T>(rz, poff);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) {
+      const int jj = min(tid + k * NT, count - 1);
+      X[k] = px[jj]; Y[k] = py[jj]; Z[k] = pz[jj];
+    }
+  }
+  return true;
+}
+
+// the four tap weights of cr_weights alone (the same expressions: the sample is bicubic's f to the bit)
+template <typename T>
+__device__ __forceinline__ void cr_weights_value(T x, T w[4]) {
+  const T x2 = x * x;
+  w[0] = x * t_fma<T>(x, t_fma<T>(T(-0.5), x, T(1)), T(-0.5));
+  w[1] = t_fma<T>(x2, t_fma<T>(T(1.5), x, T(-2.5)), T(1));
+  w[2] = x * t_fma<T>(x, t_fma<T>(T(-1.5), x, T(2)), T(0.5));
+  w[3] = x2 * t_fma<T>(T(0.5), x, T(-0.5));
+}
+// 16 taps -> value: bicubic's f, no Fu / Fv
+template <typename T, typename RowFn>
+__device__ __forceinline__ T bicubic_value(T fu, T fv, RowFn row) {
+  T wu[4], wv[4];
+  cr_weights_value<T>(fu, wu);
+  cr_weights_value<T>(fv, wv);
+  T f = T(0);
+#pragma unroll
+  for (int l = 0; l < 4; ++l) {
+    const Row4<T> r = row(l);
+    const T rs = t_fma<T>(wu[3], r.p3, t_fma<T>(wu[2], r.p2, t_fma<T>(wu[1], r.p1, wu[0] * r.p0)));
+    f = t_fma<T>(wv[l], rs, f);
+  }
+  return f;
+}
+
+// One value per lane summed over the wavefront without LDS: DPP inside a 16-lane row (L ^ 1, L ^ 2, L ^ 7, L ^ 15), then
+// v_permlane16_swap / v_permlane32_swap of two copies -- odd rows of one against even rows of the other, upper half-wave
+// against lower -- whose sum is the pairing L ^ 16 (L ^ 32).  Every lane ends with the same total; the order is fixed.
+template <int CTRL> __device__ __forceinline__ int lane_xchg(int x) { return __builtin_amdgcn_update_dpp(0, x, CTRL, 0xF, 0xF, true); }
+template <int W>
+__device__ __forceinline__ void swap_rows_b32(unsigned &a, unsigned &b) {
+  if constexpr (W == 32) asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 0" : "+v"(a), "+v"(b));
+  else asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 0" : "+v"(a), "+v"(b));
+}
+template <int W> __device__ __forceinline__ float swap_add(float x) {
+  unsigned a = __builtin_bit_cast(unsigned, x), b = a;
+  swap_rows_b32<W>(a, b);
+  return __builtin_bit_cast(float, a) + __builtin_bit_cast(float, b);
+}
+template <int W> __device__ __forceinline__ int swap_add(int x) {
+  unsigned a = (unsigned)x, b = a;
+  swap_rows_b32<W>(a, b);
+  return (int)(a + b);
+}
+template <int W> __device__ __forceinline__ double swap_add(double x) {
+  const unsigned long long u = __builtin_bit_cast(unsigned long long, x);
+  unsigned al = (unsigned)u, ah = (unsigned)(u >> 32), bl = al, bh = ah;
+  if constexpr (W == 32)
+    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %2\n\tv_permlane32_swap_b32 %1, %3\n\ts_nop 0" : "+v"(al), "+v"(ah), "+v"(bl), "+v"(bh));
+  else
+    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %2\n\tv_permlane16_swap_b32 %1, %3\n\ts_nop 0" : "+v"(al), "+v"(ah), "+v"(bl), "+v"(bh));
+  return __builtin_bit_cast(double, ((unsigned long long)ah << 32) | al) + __builtin_bit_cast(double, ((unsigned long long)bh << 32) | bl);
+}
+template <typename V>
+__device__ __forceinline__ V wave_sum1(V x) {
+  x += lane_xchg<kDppQuadXor1>(x);
+  x += lane_xchg<kDppQuadXor2>(x);
+  x += lane_xchg<kDppRowHalfMirror>(x);
+  x += lane_xchg<kDppRowMirror>(x);
+  x = swap_add<16>(x);
+  return swap_add<32>(x);
+}
+
+// one narrow partial per workgroup of the cost-only launches: 16 bytes at pose * rows + row
+struct __attribute__((aligned(16))) CostPartial { double cost, failed; };
+static_assert(sizeof(CostPartial) == kCostPartialBytes, "ea_launch.h");
+
+template <typename T, int PPT, int NT, bool BUF, bool IMG32 = false>
+__global__ __launch_bounds__(NT) void ea_cost_poses_kernel(
+    const void *__restrict__ x0, const void *__restrict__ y0, const void *__restrict__ z0, int n0,
+    int shape, int g, int rows,
+    const ProblemDesc *__restrict__ probs, const PoseState *__restrict__ poses,
+    CostPartial *__restrict__ partials) {
+  static_assert(!IMG32 || std::is_same<T, double>::value, "fp32-stored image: fp64 kernels");
+  typedef typename ImgOf<T, IMG32>::type IT;
+  __shared__ double s_cost[NT / 64];
+  __shared__ int s_bad[NT / 64];
+  const PosesWork w = poses_work(blockIdx.x, shape, rows, g, 0);
+  if (w.kind != 2) return;  // (uniform)
+  const PosesChunk pc = poses_chunk(w, shape, rows, reinterpret_cast<const PosesRow *>(probs) - rows);
+  const int tid = threadIdx.x;
+  ProblemDesc pd;
+  PoseLite<T> ps;
+  T X[PPT], Y[PPT], Z[PPT];
+  int count = 0;
+  if (!poses_item_head<T, PPT, NT, BUF, IMG32>(x0, y0, z0, n0, probs, poses, pc, pd, ps, X, Y, Z, count)) {
+    if (tid == 0) partials[pc.out_row] = CostPartial{0.0, 0.0};
+    return;
+  }
+  const int pitch = pd.pitch;
+  const void *img_base = IMG32 ? pd.dt32 : pd.dt;
+  const GPtr<IT> gimg = (GPtr<IT>)(static_cast<const IT *>(img_base) + (size_t)kImagePad * (size_t)pitch + kImagePad);
+  const __amdgpu_buffer_rsrc_t rimg =
+      make_raw_buffer(img_base, BUF ? (unsigned)pitch * (unsigned)(pd.H + 2 * kImagePad) * (unsigned)sizeof(IT) : 0u);
+  const int loss_kind = pd.loss_kind;
+  const T loss_a = Uni<T>::loss_a(pd), loss_inv_b = Uni<T>::loss_inv_b(pd);
+  // projection; lanes past the end of the chunk and lanes whose functor fails move to a harmless sample and get weight 0
+  Proj<T> pr[PPT];
+  bool valid[PPT];
+  int n_bad = 0;
+#pragma unroll
+  for (int k = 0; k < PPT; ++k) {
+    const bool inb = tid + k * NT < count;
+    project_point<T>(pd, ps, X[k], Y[k], Z[k], pr[k]);
+    valid[k] = inb && pr[k].state == 1;
+    n_bad += (inb && pr[k].state == 2) ? 1 : 0;
+    if (__any(!valid[k]) && !valid[k]) {  // (uniform test first: the common wavefront has nothing to fix up)
+      pr[k].iu = 0; pr[k].iv = 0; pr[k].fu = T(0); pr[k].fv = T(0);
+    }
+  }
+  T acc = T(0);
+#pragma unroll
+  for (int k = 0; k < PPT; ++k) {
+    T f;
+    if constexpr (BUF) {
+      // byte offset of texel (iv - 1, iu - 1) in the padded image; iv, iu >= -2 keeps it non-negative
+      const int voff = ((pr[k].iv + (kImagePad - 1)) * pitch + (pr[k].iu + (kImagePad - 1))) * (int)sizeof(IT);
+      f = bicubic_value<T>(pr[k].fu, pr[k].fv, [&](int l) { return RowLoad<T, IT>::buf(rimg, voff, l * pitch * (int)sizeof(IT)); });
+    } else {
+      const GPtr<IT> base = gimg + ((ptrdiff_t)(pr[k].iv - 1) * pitch + (pr[k].iu - 1));
+      f = bicubic_value<T>(pr[k].fu, pr[k].fv, [&](int l) { return RowLoad<T, IT>::flat(base + (ptrdiff_t)l * pitch); });
+    }
+    T rho, wt;
+    loss_eval<T>(loss_kind, loss_a, loss_inv_b, f * f, rho, wt);
+    rho = valid[k] ? rho : T(0);
+    acc = k == 0 ? T(0.5) * rho : t_fma<T>(T(0.5), rho, acc);
+  }
+  // a wavefront's sum in T, the workgroup's in fp64 through LDS in wave order: fixed by (chunk, lane, wave)
+  const T wsum = wave_sum1<T>(acc);
+  const int wbad = wave_sum1<int>(n_bad);
+  if ((tid & 63) == 0) { s_cost[tid >> 6] = (double)wsum; s_bad[tid >> 6] = wbad; }
+  __syncthreads();
+  if (tid == 0) {
+    double c = 0.0;
+    int nb = 0;
+#pragma unroll
+    for (int v = 0; v < NT / 64; ++v) { c += s_cost[v]; nb += s_bad[v]; }
+    partials[pc.out_row] = CostPartial{c, (double)nb};
+  }
+}
+
+// The fold of a cost-only launch: one 256-lane workgroup per (pose, problem) of the launch sums the pose's narrow partials
+// of the problem's rows -- lane l rows l, l + 256, .. in row order, the wavefronts' sums in wave order, all fp64 -- and writes
+// {cost, n_invalid} into the cost and invalid slots of the result in pinned host memory, then counts itself in and the last
+// arrival raises the pinned flag to the launch's sequence number (poses_fold_one's signal).
+template <int NT>
+__global__ __launch_bounds__(NT) void ea_cost_fold_kernel(PosesFold f) {
+  __shared__ double s_cost[NT / 64], s_bad[NT / 64];
+  const int tid = threadIdx.x, r = blockIdx.x;
+  int pose, problem;
+  poses_rider(r, f.count, &pose, &problem);
+  const GroupDesc gd = f.groups[problem];
+  const CostPartial *rows = reinterpret_cast<const CostPartial *>(f.rows) + (size_t)pose * f.rows_per_pose;
+  double c = 0.0, nb = 0.0;
+  for (int i = gd.tile_begin + tid; i < gd.tile_end; i += NT) {
+    const CostPartial p = rows[i];
+    c += p.cost; nb += p.failed;
+  }
+  c = wave_sum1<double>(c);
+  nb = wave_sum1<double>(nb);
+  if ((tid & 63) == 0) { s_cost[tid >> 6] = c; s_bad[tid >> 6] = nb; }
+  __syncthreads();
+  if (tid == 0) {
+    double ct = 0.0, nt = 0.0;
+#pragma unroll
+    for (int v = 0; v < NT / 64; ++v) { ct += s_cost[v]; nt += s_bad[v]; }
+    f.out[r].acc[kAccCost] = ct;
+    f.out[r].acc[kAccInvalid] = nt;
+    __threadfence_system();
+    const unsigned int prev = __hip_atomic_fetch_add(f.counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    if (prev == (unsigned)f.n - 1u) {
+      __hip_atomic_store(f.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __threadfence_system();
+      __hip_atomic_store(f.host_flag, f.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+}
+
 // The evaluation of a multi-start solve (ea_batch_solve_starts): ea_eval_poses_kernel's launch -- the same one-dimensional,
 // XCD-dealt item list, chunks, per-point code and row index pose * rows + row, so a start's partial rows hold the bits the
 // pose-batched evaluation gives for that pose -- over a piece of the LIVE LIST (ea_starts_map.h): item pose g of the launch is
@@ -2586,6 +2843,40 @@ hipError_t launch_poses_fold(int nt, const PosesFold &fold, hipStream_t stream) 
   if (fold.n <= 0) return hipErrorInvalidValue;  // (somebody has to raise the flag)
   if (nt == 1024) hipLaunchKernelGGL(ea_poses_fold_kernel<1024>, dim3(fold.n), dim3(1024), 0, stream, fold);
   else hipLaunchKernelGGL(ea_poses_fold_kernel<256>, dim3(fold.n), dim3(256), 0, stream, fold);
+  return hipGetLastError();
+}
+
+// ea_cost_poses_kernel: launch_eval_poses' launch shape without riders, one narrow partial per workgroup.  Compiled for
+// 256-lane workgroups in the shapes the evaluation kernels have; the fp32 mirror under fp64 arithmetic only.
+template <typename T, int PPT, int NT, bool IMG32> constexpr bool cost_exists() {
+  return NT == 256 && shape_exists<T, PPT, NT>() && (!IMG32 || sizeof(T) == 8);
+}
+hipError_t launch_cost_poses(const EvalLaunch &s, const PosesLaunch &p, const ProblemDesc *probs, const PoseState *poses,
+                             void *partials, hipStream_t stream) {
+  if (s.variant || s.lds_bytes > 0 || s.wide || !s.terms_are_groups || s.chunk != s.nt * s.ppt) return hipErrorInvalidValue;
+  if (p.g <= 0 || p.rows <= 0 || (int64_t)p.rows * p.g > (int64_t)1 << 28) return hipErrorInvalidValue;
+  const int shape = poses_shape(s.xcd_remap != 0, p.order, p.single != 0, 0);
+  const dim3 grid(poses_grid(p.rows, p.g, 0));
+  return dispatch_dtype(s.dtype, [&](auto TT) { return dispatch_int<1, 2, 4>(s.ppt, [&](auto PPT) {
+    return dispatch_int<256>(s.nt, [&](auto NT) { return dispatch_bool(s.buffer_loads, [&](auto BUF) {
+      return dispatch_bool(s.img32, [&](auto IMG32) {
+        typedef typename decltype(TT)::type T;
+        constexpr int P = decltype(PPT)::value, N = decltype(NT)::value;
+        constexpr bool B = decltype(BUF)::value, I = decltype(IMG32)::value;
+        if constexpr (!cost_exists<T, P, N, I>()) return hipErrorInvalidValue;
+        else {
+          hipLaunchKernelGGL((ea_cost_poses_kernel<T, P, N, B, I>), grid, dim3(N), 0, stream, s.x0, s.y0, s.z0, s.n0, shape, p.g,
+                             p.rows, probs, poses, static_cast<CostPartial *>(partials));
+          return hipGetLastError();
+        }
+      }); }); });
+  }); });
+}
+
+// the fold behind a cost-only launch: fold.n results, fold.rows = the launch's narrow partials
+hipError_t launch_cost_fold(const PosesFold &fold, hipStream_t stream) {
+  if (fold.n <= 0) return hipErrorInvalidValue;  // (somebody has to raise the flag)
+  hipLaunchKernelGGL(ea_cost_fold_kernel<256>, dim3(fold.n), dim3(256), 0, stream, fold);
   return hipGetLastError();
 }
 

@@ -102,6 +102,14 @@ hipError_t launch_eval_poses_grid(const EvalLaunch &s, const ProblemDesc *probs,
 hipError_t launch_eval_poses(const EvalLaunch &s, const PosesLaunch &p, const ProblemDesc *probs, const PoseState *poses,
                              double *partials, const PosesFold &fold, hipStream_t stream);
 hipError_t launch_poses_fold(int nt, const PosesFold &fold, hipStream_t stream);
+// ea_cost_poses_kernel: the cost-only form of launch_eval_poses' launch (256-lane workgroups; no riders) -- one narrow
+// partial {cost, failed functors} of kCostPartialBytes per workgroup at pose * rows + row of `partials`.
+// ea_cost_fold_kernel: fold.n results out of them (fold.rows = the narrow partials), {cost, n_invalid} into the cost and
+// invalid slots of fold.out[r], the flag raised to fold.seq.
+constexpr size_t kCostPartialBytes = 16;
+hipError_t launch_cost_poses(const EvalLaunch &s, const PosesLaunch &p, const ProblemDesc *probs, const PoseState *poses,
+                             void *partials, hipStream_t stream);
+hipError_t launch_cost_fold(const PosesFold &fold, hipStream_t stream);
 // ea_eval_starts_kernel: the poses live[off .. off + p.g) of a multi-start solve, as ea_eval_poses_kernel evaluates them,
 // without riders; positions from *n_live on return at once.  ea_lm_step_starts_kernel: g x a.count workgroups.
 hipError_t launch_eval_starts(const EvalLaunch &s, const PosesLaunch &p, const ProblemDesc *probs, const PoseState *poses,

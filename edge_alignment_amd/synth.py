@@ -29,6 +29,28 @@ def quat_mul(a, b):
                      a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0]])
 
 
+def quat_plus(q, delta):
+    """ceres::QuaternionParameterization::Plus: [cos |delta|, sin |delta| delta / |delta|] * q"""
+    q, delta = np.asarray(q, dtype=np.float64), np.asarray(delta, dtype=np.float64)
+    n = float(np.linalg.norm(delta))
+    if n == 0.0:
+        return q.copy()
+    return quat_mul(np.concatenate([[np.cos(n)], np.sin(n) / n * delta]), q)
+
+
+def pose_lattice(q0, t0, half_extent6, steps6):
+    """Candidate poses on a regular lattice around (q0, t0) in the tangent ordering [delta | t]: coordinate i takes steps6[i]
+    evenly spaced offsets in [-half_extent6[i], +half_extent6[i]] (one step: the offset 0), the rotation part applied through
+    quat_plus.  -> q (K, 4), t (K, 3), K = prod(steps6), the last coordinate running fastest."""
+    q0, t0 = np.asarray(q0, dtype=np.float64), np.asarray(t0, dtype=np.float64)
+    axes = [np.linspace(-float(h), float(h), int(s)) if int(s) > 1 else np.zeros(1) for h, s in zip(half_extent6, steps6)]
+    assert len(axes) == 6
+    offs = np.stack(np.meshgrid(*axes, indexing="ij"), axis=-1).reshape(-1, 6)
+    q = np.stack([quat_plus(q0, o[:3]) for o in offs])
+    t = t0[None, :] + offs[:, 3:]
+    return q, t
+
+
 def rotation_angle_between(q1, q2):
     """angle (rad) of the relative rotation between two unit quaternions"""
     q1 = np.asarray(q1, float) / np.linalg.norm(q1)

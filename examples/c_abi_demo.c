@@ -78,6 +78,20 @@ int main(int argc, char **argv) {
     }
     free(r); free(J);
   }
+  /* ranked search: three candidate starts (the identity and two shifted ones) cost one cost-only evaluation each, the two
+   * cheapest are solved in lock-step; reported on stderr (stdout stays the one line documented above) */
+  {
+    const double cq[3 * 4] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0}, ct[3 * 3] = {0, 0, 0, 0.02, 0, 0, 0, -0.02, 0.01};
+    double sq[2 * 4], st[2 * 3];
+    int picked[2] = {-1, -1}, best = -1;
+    rc = ea_search_starts(p, 3, cq, ct, 2, &opt, sq, st, picked, NULL, &best);
+    if (rc != EA_OK) {
+      fprintf(stderr, "libea_hip error %d: %s\n", rc, ea_last_error());
+      return 1;
+    }
+    fprintf(stderr, "search: candidates %d, %d solved, best rank %d -> t = %.9g %.9g %.9g\n", picked[0], picked[1], best,
+            best >= 0 ? st[3 * best] : 0.0, best >= 0 ? st[3 * best + 1] : 0.0, best >= 0 ? st[3 * best + 2] : 0.0);
+  }
   printf("%.17g %.17g %.17g %.17g %.17g %.17g %.17g %d %d %.17g %.17g\n", q[0], q[1], q[2], q[3], t[0], t[1], t[2],
          s.num_iterations, s.termination, s.final_cost, jtr_err);
   ea_problem_destroy(p);

@@ -357,6 +357,35 @@ int ea_batch_solve_starts(ea_batch *b, int K, const ea_options *opt, double *q, 
 int ea_solve_starts(ea_problem *p, int K, const ea_options *opt, double *q, double *t,
                     ea_summary *summaries, int *best);   /* one problem: count = 1 */
 
+/* Cost-only evaluation at K poses per problem: cost = 1/2 sum rho(r^2) (+ the problem's NormalPriors) and n_invalid, in the
+ * layout of ea_batch_eval_poses (cost, n_invalid: K x count, either may be NULL) -- what a line search, a cost-surface
+ * probe or a ranking of candidate poses needs.  A kernel of its own runs the projection, the four row loads, the VALUE of
+ * the bicubic patch and rho per (point, pose): no Jacobian row, no JtJ / Jtr products, two sums instead of 28.  The cost
+ * agrees with ea_batch_eval_poses' at the same pose up to rounding (the same points summed in another order), n_invalid
+ * exactly; a pose gives the same bits alone, in any split over launches ("poses_per_launch"), in either "poses_order" and
+ * in any company.  ea_batch_cost_poses = ea_batch_set_poses + ea_batch_cost_resident_poses; the poses stay resident, and
+ * the call may be interleaved with ea_batch_eval_resident_poses on the same poses.  No poses resident: EA_ERR_STATE.
+ * Covered by the cost kernel: the batches ea_batch_eval_poses evaluates in its flat form at 256-thread workgroups; every
+ * other batch (variant functors, shared-pose terms, LDS staging, "wide_accumulate", "threads" = 1024) runs the full
+ * evaluation with only the cost fetched.  ea_batch_get_info "cost_form": 1 = the cost kernel served the last call, 0 = the
+ * fall-back; ea_batch_set_tuning "cost_form" = 0 forces the fall-back (A/B). */
+int ea_batch_cost_poses(ea_batch *b, int K, const double *q, const double *t, double *cost, int64_t *n_invalid);
+int ea_batch_cost_resident_poses(ea_batch *b, double *cost, int64_t *n_invalid);
+/* Ranked search in front of the multi-start solve: K candidate poses per problem (q: K x count x 4, t: K x count x 3, not
+ * modified) are ranked by one cost-only evaluation each, and the M best of every problem are solved in lock-step
+ * (ea_batch_solve_starts with M starts).  A candidate is ELIGIBLE if its cost is finite and n_invalid == 0 (a start whose
+ * functor fails ends EA_WHY_INITIAL_EVAL_FAILED anyway, and a sum over fewer points would rank unfairly); ranks are the
+ * eligible candidates by ascending cost, ties to the lower candidate index, then the ineligible ones by ascending index.
+ * picked: M x count or NULL, picked[m * count + i] = the candidate of rank m for problem i.  q_out: M x count x 4, t_out:
+ * M x count x 3 = the solved poses of the picked starts; summaries: M x count or NULL; best: count entries or NULL, as in
+ * ea_batch_solve_starts over the M ranks (an index into the ranks, not into the candidates).  Requires 1 <= M <= K and
+ * M x count <= 16384: EA_ERR_INVALID_ARG otherwise, before anything touches the device.  Afterwards the K CANDIDATES are
+ * the batch's resident poses (whatever ea_batch_set_poses had made resident before is replaced). */
+int ea_batch_search_starts(ea_batch *b, int K, const double *q, const double *t, int M, const ea_options *opt,
+                           double *q_out, double *t_out, int *picked, ea_summary *summaries, int *best);
+int ea_search_starts(ea_problem *p, int K, const double *q, const double *t, int M, const ea_options *opt,
+                     double *q_out, double *t_out, int *picked, ea_summary *summaries, int *best);   /* count = 1 */
+
 /* ---- pose covariance: ceres::Covariance (Ceres <= 2.1) at one pose per problem ----------------------------------------
  * C = (JtJ)^-1 over the tangent coordinates [delta(3) | t(3)]: the JtJ ea_eval returns at that pose (every term of the
  * problem summed in), loss-corrected rows sum rho' J J^T when apply_loss_function != 0 (every shipped loss has
@@ -485,7 +514,7 @@ int ea_eval_rows_device(ea_problem *p, const double q[4], const double t[3], int
 /* ---- tuning ---------------------------------------------------------------------------- */
 /* tuning knobs: key in {"lds_bytes", "points_per_thread", "use_lds", "xcd_remap", "threads", "buffer_loads",
  * "solve_streams", "rows_staged", "rows_nontemporal", "wide_accumulate", "dt_f32", "poses_per_launch", "poll_results",
- * "fused_iterations", "zero_copy_poses", "starts_events"};
+ * "fused_iterations", "zero_copy_poses", "starts_events", "cost_form"};
  * value < 0 restores the default.
  * "starts_events" = 1 (measurement): ea_batch_solve_starts brackets the launches it queues with an event pair and waits
  * for it; ea_batch_get_info "starts_device_ns" / "starts_iterations" then report the device time and the iterations queued.

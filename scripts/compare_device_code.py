@@ -3,7 +3,8 @@
 kernels: nothing needs a GPU.)
 
   compare_device_code.py list  TREE OUTDIR     # device listings of TREE's kernel sources into OUTDIR (build.FLAGS of TREE)
-  compare_device_code.py diff  DIR_A DIR_B     # compare two such directories; exit status 1 if anything differs
+  compare_device_code.py diff  DIR_A DIR_B     # compare two such directories; exit status 1 if a kernel of A is missing from B
+                                               # or differs there (kernels only B has are listed, not counted)
 
 A listing is `hipcc <build.FLAGS minus -fPIC> <the source's extra flags> -S --cuda-device-only`, with the per-compilation
 `__hip_cuid_<hex>` replaced by a constant.  Whole files are compared first.  Where they differ the kernels are compared one
@@ -80,11 +81,15 @@ def diff(dir_a, dir_b):
         else:
             lost, added = sorted(set(ka) - set(kb)), sorted(set(kb) - set(ka))
             differ = sorted(n for n in set(ka) & set(kb) if ka[n] != kb[n])
-            if lost or added or differ:
+            if lost or differ:
                 bad += 1
                 verdict = "DIFFERENT: %d lost, %d added, %d bodies differ" % (len(lost), len(added), len(differ))
                 for n in (lost + added + differ)[:20]:
                     print("  !", n, file=sys.stderr)
+            elif added:  # new kernels beside the old ones: every kernel of A is in B with the same body
+                verdict = "%d kernels added; the %d of A: same names, every body identical after masking label ordinals" % (len(added), len(ka))
+                for n in added:
+                    print("  +", n, file=sys.stderr)
             else:
                 verdict = "same names, every body identical after masking label ordinals (%d kernels)" % len(ka)
         print("| `%s` | %d | %d / %d | %s |" % (os.path.basename(src), a.count("\n"), len(ka), len(kb), verdict))
