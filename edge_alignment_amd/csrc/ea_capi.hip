@@ -249,6 +249,7 @@ extern "C" int ea_release_cached_memory(void) {
 // one fold of a pose-batched call: the sequence number its completion raises the pinned flag to, and the poses it covers
 struct KposesMark { int seq, start, g; };
 
+constexpr int kPosesWaveExchangeDefault = 1;  // tuning key "poses_wave_exchange"
 struct ea_batch {
   std::vector<ea_problem *> probs;
   std::vector<uint64_t> versions;
@@ -336,6 +337,7 @@ struct ea_batch {
   double *d_krows = nullptr;          // flat form: two arrays of kp_rows_cap poses each; grid form: one
   int kp_rows_cap = 0;
   int t_kp_order = 0;                 // tuning key "poses_order": 1 = an XCD walks the rows of a pose instead of the poses of a row (A/B)
+  int t_kp_xchg = kPosesWaveExchangeDefault, kp_xchg = 0, last_kp_xchg = 0;  // tuning key "poses_wave_exchange"; what kposes_shape made of it; what the last pose-batched launch ran
   std::vector<KposesMark> kp_marks;   // the folds of the last call: sequence number, first pose, poses
   // ea_batch_cost_resident_poses: the narrow partials of one launch (kCostPartialBytes per row of a pose), tuning key
   // "cost_form" (0: always the fall-back, the full evaluation with only the cost fetched) and what the last call ran
@@ -1415,6 +1417,7 @@ extern "C" int ea_batch_eval(ea_batch *b, const double *q, const double *t, doub
 // points per lane amortise the wavefront butterfly and 256-lane workgroups keep the occupancy
 // (profiles/r03_ab_poses_shape.txt: C2 fp64 0.69 -> 0.58 us per evaluation at two points per lane, fp32 0.33 -> 0.27; C5
 // fp32 5.65 -> 4.50 at 256 x 4 instead of 1024 x 4).  Explicit tuning ("points_per_thread", "threads") wins.
+static bool kposes_flat(const ea_batch *b);
 static void kposes_shape(ea_batch *b) {
   int nt = 256, ppt = b->dtype == EA_F64 ? 2 : (b->max_n >= 200000 ? 4 : 2);
   if (b->lds_bytes > 0 || b->wide) { nt = b->nt; ppt = b->ppt; }          // (those forms keep the shape they were tuned at)
@@ -1424,6 +1427,8 @@ static void kposes_shape(ea_batch *b) {
   if (b->dtype == EA_F64 && ppt > 2) ppt = 2;
   if (b->any_variant) { nt = 256; ppt = std::min(ppt, 2); }
   b->kp_nt = nt; b->kp_ppt = ppt; b->kp_chunk = nt * ppt;
+  // the wave-exchange reduction (ea_wave_exchange.h): the fp64, 256-lane launches of ea_eval_poses_kernel / ea_eval_starts_kernel
+  b->kp_xchg = b->t_kp_xchg && b->dtype == EA_F64 && nt == 256 && kposes_flat(b);
   const ProblemDesc *hd = reinterpret_cast<const ProblemDesc *>(b->h_desc);
   int rows = 0, widest = 0;
   for (int j = 0; j < b->nterms; ++j) {
@@ -1579,6 +1584,7 @@ static bool seq_reached(int flag, int seq) { return (unsigned)flag - (unsigned)s
 static int enqueue_resident_poses(ea_batch *b, int K, bool folds = true, bool flag_last = false) {
   const int count = (int)b->probs.size(), per = poses_launch_size(K, b->kp_G), rows = b->kp_ntiles;
   b->kp_marks.clear();
+  b->last_kp_xchg = 0;
   if (!kposes_flat(b)) {
     for (int start = 0; start < K; start += per) {
       const int g = std::min(per, K - start);
@@ -1593,7 +1599,8 @@ static int enqueue_resident_poses(ea_batch *b, int K, bool folds = true, bool fl
   if (b->done_seq > 0x7fffffff - (K + per - 1) / per - 2) b->done_seq = 0;  // (a call's sequence numbers do not straddle the wrap)
   const EvalLaunch shape = eval_launch(b, /*kposes=*/true);
   PosesLaunch pl;
-  pl.rows = rows; pl.order = b->t_kp_order; pl.single = b->nterms == 1;
+  pl.rows = rows; pl.order = b->t_kp_order; pl.single = b->nterms == 1; pl.exchange = b->kp_xchg;
+  b->last_kp_xchg = rows > 0 ? b->kp_xchg : 0;
   PosesFold owed;  // the fold the launches so far still owe (n = 0: none)
   owed.count = count; owed.rows_per_pose = rows; owed.groups = b->d_kgroups;
   owed.counter = b->d_done_count; owed.host_flag = b->d_progress + 3 * (size_t)count;
@@ -1676,6 +1683,7 @@ extern "C" int ea_batch_eval_resident_poses(ea_batch *b, double *cost, double *J
 static int enqueue_resident_cost(ea_batch *b, int K) {
   const int count = (int)b->probs.size(), per = poses_launch_size(K, b->kp_G), rows = b->kp_ntiles;
   b->kp_marks.clear();
+  b->last_kp_xchg = 0;
   if (b->done_seq > 0x7fffffff - (K + per - 1) / per - 2) b->done_seq = 0;  // (a call's sequence numbers do not straddle the wrap)
   const size_t need = std::max<size_t>(1, (size_t)per * (size_t)rows) * kCostPartialBytes;
   if (need > b->kcost_bytes) {
@@ -2645,6 +2653,8 @@ extern "C" int ea_batch_set_tuning(ea_batch *b, const char *key, int value) {
   else if (k == "zero_copy_poses") { b->t_zero_copy = value; return EA_OK; }
   else if (k == "poses_per_launch") { b->t_kp_G = value > 0 ? value : 0; b->kp_K = 0; return EA_OK; }  // (resident poses are dropped)
   else if (k == "poses_order") { b->t_kp_order = value ? 1 : 0; return EA_OK; }
+  // (0: the per-wavefront butterfly; read when the pose path is shaped, so resident poses and the pose path's tables are dropped)
+  else if (k == "poses_wave_exchange") { b->t_kp_xchg = value < 0 ? kPosesWaveExchangeDefault : value != 0; b->kp_K = 0; b->kp_G = 0; return EA_OK; }
   else if (k == "starts_events") { b->t_starts_events = value > 0 ? 1 : 0; return EA_OK; }
   else if (k == "cost_form") { b->t_cost_form = value ? 1 : 0; return EA_OK; }  // 0: cost-only calls run the full evaluation (A/B)
   else return fail(EA_ERR_INVALID_ARG, "unknown tuning key: " + k);
@@ -2670,6 +2680,7 @@ extern "C" int ea_batch_get_info(const ea_batch *b, const char *key, int64_t *va
   else if (k == "poses_points_per_thread") *value = b->kp_ppt;   // launch shape of the pose-batched evaluation
   else if (k == "poses_threads") *value = b->kp_nt;
   else if (k == "poses_tiles") *value = b->kp_ntiles;            // partial rows (= workgroups with work) per pose
+  else if (k == "poses_wave_exchange") *value = b->last_kp_xchg;  // the last pose-batched launch: 1 = the wave-exchange reduction
   else if (k == "fused_iterations") *value = b->last_fused;      // the last solve ran one launch per LM iteration (ea_lm_iter_kernel)
   else if (k == "cost_form") *value = b->last_cost_form;         // the last cost-only call: 1 = ea_cost_poses_kernel, 0 = the full evaluation
   else if (k == "starts_form") *value = b->last_starts_form;     // the last ea_batch_solve_starts: 1 = lock-step, 0 = one batch solve per start
@@ -3099,7 +3110,8 @@ extern "C" int ea_batch_solve_starts(ea_batch *b, int K, const ea_options *opt_i
   a.count = count; a.rows_per_pose = rows; a.tag = tag;
   const EvalLaunch shape = eval_launch(b, /*kposes=*/true);
   PosesLaunch pl;
-  pl.rows = rows; pl.order = b->t_kp_order; pl.single = b->nterms == 1;
+  pl.rows = rows; pl.order = b->t_kp_order; pl.single = b->nterms == 1; pl.exchange = b->kp_xchg;
+  b->last_kp_xchg = rows > 0 ? b->kp_xchg : 0;
   // iteration j over n (possibly stale) live positions: reads list j & 1, its last step launch writes list (j + 1) & 1
   auto enqueue_iteration = [&](int j, int n) -> int {
     const int per = starts_piece(n, G), in = j & 1;

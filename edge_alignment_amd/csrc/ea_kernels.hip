@@ -44,6 +44,7 @@ extern __device__ int g_lm_probe_row;
 #include "ea_lm.h"
 #include "ea_prior.h"
 #include "ea_types.h"
+#include "ea_wave_exchange.h"
 
 namespace ea {
 
@@ -776,6 +777,102 @@ template <typename T, bool IMG32> struct ImgOf { typedef T type; };
 template <> struct ImgOf<double, true> { typedef float type; };
 
 // ------------------------------------------------------------------------------------------------
+// The wave-exchange reduction of a 256-lane fp64 workgroup (ea_wave_exchange.h has the ownership arithmetic and the LDS
+// layout): the four wavefronts add their 32 sums lane by lane through LDS in two halving rounds, so that each runs the
+// butterfly over the 8 slots it ends up owning instead of over all 32 -- 12 lane swaps per wavefront instead of 48, the
+// work spread evenly over the four SIMDs.  Which half a wavefront keeps is wave-uniform: branches, no per-lane selects.
+// Returns the finished sum of slot xchg_store_slot(wave, lane) in the lanes that have one.
+#define EA_SWAP4(OP) "s_nop 1\n\t" OP " %0, %4\n\t" OP " %1, %5\n\t" OP " %2, %6\n\t" OP " %3, %7\n\ts_nop 0"
+// the two-double twin of swap_f64x4<16>: a[k] <-> b[k] for k = 0, 1 between odd and even 16-lane rows
+__device__ __forceinline__ void swap16_f64x2(double *a, double *b) {
+  unsigned al[2], ah[2], bl[2], bh[2];
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const unsigned long long ua = __builtin_bit_cast(unsigned long long, a[k]), ub = __builtin_bit_cast(unsigned long long, b[k]);
+    al[k] = (unsigned)ua; ah[k] = (unsigned)(ua >> 32); bl[k] = (unsigned)ub; bh[k] = (unsigned)(ub >> 32);
+  }
+  asm volatile(EA_SWAP4("v_permlane16_swap_b32")
+               : "+v"(al[0]), "+v"(ah[0]), "+v"(al[1]), "+v"(ah[1]), "+v"(bl[0]), "+v"(bh[0]), "+v"(bl[1]), "+v"(bh[1]));
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    a[k] = __builtin_bit_cast(double, ((unsigned long long)ah[k] << 32) | al[k]);
+    b[k] = __builtin_bit_cast(double, ((unsigned long long)bh[k] << 32) | bl[k]);
+  }
+}
+
+// (The two halves of a uniform branch differ only in which registers they name, which invites the compiler to merge them
+// into one copy behind per-lane selects -- 64 v_cndmask_b32 -- or to join them through register copies.  An empty asm
+// statement of its own at either end of each half keeps the halves apart: nothing is hoisted, sunk or if-converted across it.)
+#define EA_XCHG_HALF(TAG, ...) do { asm volatile("; " TAG); __VA_ARGS__ asm volatile("; " TAG " end"); } while (0)
+// (... and the sums of a half, which have no side effect to hold them there, leave it through an asm statement's operands)
+#define EA_XCHG_PIN8(TAG, X) asm volatile("; " TAG : "+v"((X)[0]), "+v"((X)[1]), "+v"((X)[2]), "+v"((X)[3]), "+v"((X)[4]), "+v"((X)[5]), "+v"((X)[6]), "+v"((X)[7]))
+__device__ __forceinline__ double wave_exchange_reduce_f64(const double (&v)[32], int wave, int lane, unsigned char *lds /* kXchgBytes */) {
+  const int w = __builtin_amdgcn_readfirstlane(wave);
+  auto cells = [&](int region) { return reinterpret_cast<f64x2_t *>(lds + xchg_cell_offset(region, 0, lane)); };
+  constexpr int kPair = 1024 / (int)sizeof(f64x2_t);  // cells 2p, 2p + 1 of a lane: p * kPair vectors on
+  const bool hi16 = xchg_keep16(w) != 0, hi8 = xchg_keep8(w) != 0;  // (wave-uniform)
+  // round 1: w <-> w ^ 1, 16 of 32
+  double k[16];
+  {
+    f64x2_t *out = cells(xchg_write_region1(w));
+    auto store = [&](const double *from) {
+#pragma unroll
+      for (int p = 0; p < 8; ++p) { f64x2_t o; o[0] = from[2 * p]; o[1] = from[2 * p + 1]; out[p * kPair] = o; }
+    };
+    if (hi16) EA_XCHG_HALF("exchange 1: keep 16..31", store(v););
+    else EA_XCHG_HALF("exchange 1: keep 0..15", store(v + 16););
+    __syncthreads();
+    const f64x2_t *in = cells(xchg_read_region1(w));
+    f64x2_t a[8];
+#pragma unroll
+    for (int p = 0; p < 8; ++p) a[p] = in[p * kPair];
+    auto sum = [&](const double *kept) {
+#pragma unroll
+      for (int p = 0; p < 8; ++p) { k[2 * p] = kept[2 * p] + a[p][0]; k[2 * p + 1] = kept[2 * p + 1] + a[p][1]; }
+    };
+    if (hi16) EA_XCHG_HALF("exchange 1: sum 16..31", sum(v + 16); EA_XCHG_PIN8("16..23", k); EA_XCHG_PIN8("24..31", k + 8););
+    else EA_XCHG_HALF("exchange 1: sum 0..15", sum(v); EA_XCHG_PIN8("0..7", k); EA_XCHG_PIN8("8..15", k + 8););
+  }
+  // round 2: w <-> w ^ 2, 8 of 16, into the region this wavefront has just read
+  double e[8];
+  {
+    f64x2_t *out = cells(xchg_write_region2(w));
+    auto store = [&](const double *from) {
+#pragma unroll
+      for (int p = 0; p < 4; ++p) { f64x2_t o; o[0] = from[2 * p]; o[1] = from[2 * p + 1]; out[p * kPair] = o; }
+    };
+    if (hi8) EA_XCHG_HALF("exchange 2: keep 8..15", store(k););
+    else EA_XCHG_HALF("exchange 2: keep 0..7", store(k + 8););
+    __syncthreads();
+    const f64x2_t *in = cells(xchg_read_region2(w));
+    f64x2_t a[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) a[p] = in[p * kPair];
+    auto sum = [&](const double *kept) {
+#pragma unroll
+      for (int p = 0; p < 4; ++p) { e[2 * p] = kept[2 * p] + a[p][0]; e[2 * p + 1] = kept[2 * p + 1] + a[p][1]; }
+    };
+    if (hi8) EA_XCHG_HALF("exchange 2: sum 8..15", sum(k + 8); EA_XCHG_PIN8("8..15", e););
+    else EA_XCHG_HALF("exchange 2: sum 0..7", sum(k); EA_XCHG_PIN8("0..7", e););
+  }
+  // the butterfly over the 8 values this wavefront owns: L ^ 32, L ^ 16, L ^ 15 halve, L ^ 7, L ^ 2, L ^ 1 add the partner
+  swap_f64x4<32>(e, e + 4);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) e[i] += e[i + 4];
+  swap16_f64x2(e, e + 2);
+#pragma unroll
+  for (int i = 0; i < 2; ++i) e[i] += e[i + 2];
+  const bool upper = (lane & 8) != 0;
+  const double send = upper ? e[0] : e[1];
+  const double keep = upper ? e[1] : e[0];
+  double r = keep + lane_xchg<kDppRowMirror>(send);
+  r += lane_xchg<kDppRowHalfMirror>(r);
+  r += lane_xchg<kDppQuadXor2>(r);
+  r += lane_xchg<kDppQuadXor1>(r);
+  return r;
+}
+
+// ------------------------------------------------------------------------------------------------
 // fused evaluation kernel: residual + Jacobian + loss + JtJ/Jtr/cost partials, one row per workgroup
 //
 // grid = (8 * ceil(chunks/8), problems).  Workgroup (c, p) owns points [c*chunk, (c+1)*chunk) of
@@ -783,13 +880,19 @@ template <> struct ImgOf<double, true> { typedef float type; };
 // wavefront butterfly per wave and one cross-wave fold per workgroup -> one partial row.
 
 constexpr int kMaxWaves = 16;
+// MODE of ea_eval_poses_kernel / ea_eval_starts_kernel only: MODE 0's per-point code with the wave-exchange reduction (fp64, 256
+// lanes); the dynamic LDS of such a launch is the exchange buffer (kXchgBytes)
+constexpr int kModeExchange = 3;
 constexpr int kRedBytes = kMaxWaves * kAccSlots * 8;  // cross-wave scratch: up to 16 waves x 32 doubles
 constexpr int kHdrBytes = kRedBytes + kMaxWaves * 16;  // + bbox words, keeps the tile 16-byte aligned
 
 // One workgroup's share of an evaluation: NT lanes x PPT points -> the workgroup's partial row.
 // X/Y/Z hold the lane's points (lanes past `count` carry a copy of the chunk's last point); the return value is
 // slot `my_slot` of the row (0 when my_slot < 0).  `ps` may live in global memory (scalar loads) or LDS.
-template <typename T, int PPT, int MODE, int NT, bool VAR, bool BUF, bool IMG32, typename PS>
+// XCHG (fp64, 256 lanes, MODE 0): the wave-exchange reduction above instead of a 32-value butterfly per wavefront and the
+// cross-wave sum; s_red is then the kXchgBytes exchange buffer, my_slot is not read, and the return value is the sum of slot
+// xchg_store_slot(wave, lane) in the lanes that have one (another fixed summation order: the last place may differ).
+template <typename T, int PPT, int MODE, int NT, bool VAR, bool BUF, bool IMG32, typename PS, bool XCHG = false>
 __device__ __forceinline__ double fused_chunk(const ProblemDesc &pd, const PS &ps, const T (&X)[PPT],
                                               const T (&Y)[PPT], const T (&Z)[PPT], int count, double *s_red,
                                               int *s_box, T *s_tile, int lds_texels, int my_slot) {
@@ -798,6 +901,7 @@ __device__ __forceinline__ double fused_chunk(const ProblemDesc &pd, const PS &p
   constexpr bool USE_LDS = MODE == 1;
   constexpr bool WIDE = MODE == 2 && sizeof(T) == 4;
   static_assert(!IMG32 || (std::is_same<T, double>::value && MODE == 0 && !VAR), "fp32-stored image: plain fp64 kernels on the L2 path");
+  static_assert(!XCHG || (sizeof(T) == 8 && NT == 256 && MODE == 0), "wave exchange: fp64, four wavefronts, L2 path");
   typedef typename ImgOf<T, IMG32>::type IT;  // element type of the image in HBM
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -932,7 +1036,9 @@ __device__ __forceinline__ double fused_chunk(const ProblemDesc &pd, const PS &p
 #endif
   EA_STAMP(4);  // sampled + accumulated
   if (USE_LDS) __syncthreads();  // tile readers done before the scratch rows are written
-  if constexpr (WIDE) {
+  if constexpr (XCHG) {
+    return wave_exchange_reduce_f64(v, wave, lane, reinterpret_cast<unsigned char *>(s_red));
+  } else if constexpr (WIDE) {
     double w[32];
 #pragma unroll
     for (int i = 0; i < 32; ++i) w[i] = (double)v[i];
@@ -1611,7 +1717,8 @@ __global__ __launch_bounds__(NT) void ea_eval_poses_kernel(
     int shape, int g, int rows,
     const ProblemDesc *__restrict__ probs, const PoseState *__restrict__ poses,
     double *__restrict__ partials, PosesFold fold) {
-  static_assert(MODE == 0 && !VAR, "plain functor, stencil rows from L2");
+  static_assert((MODE == 0 || MODE == kModeExchange) && !VAR, "plain functor, stencil rows from L2");
+  constexpr bool XCHG = MODE == kModeExchange;
   constexpr int chunk = NT * PPT;
   extern __shared__ __align__(16) unsigned char smem[];
   double *s_red = reinterpret_cast<double *>(smem);
@@ -1686,9 +1793,14 @@ __global__ __launch_bounds__(NT) void ea_eval_poses_kernel(
       X[k] = px[jj]; Y[k] = py[jj]; Z[k] = pz[jj];
     }
   }
-  const double sum = fused_chunk<T, PPT, 0, NT, false, BUF, IMG32, PoseLite<T>>(pd, ps, X, Y, Z, count, s_red, s_box, (T *)nullptr, 0,
-                                                                                 tid < kAccSlots ? tid : -1);
-  if (tid < kAccSlots) partials[(size_t)pc.out_row * kAccSlots + tid] = sum;
+  const double sum = fused_chunk<T, PPT, 0, NT, false, BUF, IMG32, PoseLite<T>, XCHG>(pd, ps, X, Y, Z, count, s_red, s_box, (T *)nullptr, 0,
+                                                                                       tid < kAccSlots ? tid : -1);
+  if constexpr (XCHG) {  // (one lane per (wavefront, slot) holds the finished sum)
+    const int slot = xchg_store_slot(tid >> 6, tid & 63);
+    if (slot >= 0) partials[(size_t)pc.out_row * kAccSlots + slot] = sum;
+  } else {
+    if (tid < kAccSlots) partials[(size_t)pc.out_row * kAccSlots + tid] = sum;
+  }
 }
 
 // the fold that closes a call of the pose-batched path: the last launch's rows, as its riders would have folded them
@@ -1966,7 +2078,8 @@ __global__ __launch_bounds__(NT) void ea_eval_starts_kernel(
     int shape, int g, int rows,
     const ProblemDesc *__restrict__ probs, const PoseState *__restrict__ poses,
     double *__restrict__ partials, const int *__restrict__ live, const int *__restrict__ n_live, int off) {
-  static_assert(MODE == 0 && !VAR, "plain functor, stencil rows from L2");
+  static_assert((MODE == 0 || MODE == kModeExchange) && !VAR, "plain functor, stencil rows from L2");
+  constexpr bool XCHG = MODE == kModeExchange;
   constexpr int chunk = NT * PPT;
   extern __shared__ __align__(16) unsigned char smem[];
   double *s_red = reinterpret_cast<double *>(smem);
@@ -2040,9 +2153,14 @@ __global__ __launch_bounds__(NT) void ea_eval_starts_kernel(
       X[k] = px[jj]; Y[k] = py[jj]; Z[k] = pz[jj];
     }
   }
-  const double sum = fused_chunk<T, PPT, 0, NT, false, BUF, IMG32, PoseLite<T>>(pd, ps, X, Y, Z, count, s_red, s_box, (T *)nullptr, 0,
-                                                                                 tid < kAccSlots ? tid : -1);
-  if (tid < kAccSlots) partials[(size_t)pc.out_row * kAccSlots + tid] = sum;
+  const double sum = fused_chunk<T, PPT, 0, NT, false, BUF, IMG32, PoseLite<T>, XCHG>(pd, ps, X, Y, Z, count, s_red, s_box, (T *)nullptr, 0,
+                                                                                       tid < kAccSlots ? tid : -1);
+  if constexpr (XCHG) {  // (one lane per (wavefront, slot) holds the finished sum)
+    const int slot = xchg_store_slot(tid >> 6, tid & 63);
+    if (slot >= 0) partials[(size_t)pc.out_row * kAccSlots + slot] = sum;
+  } else {
+    if (tid < kAccSlots) partials[(size_t)pc.out_row * kAccSlots + tid] = sum;
+  }
 }
 
 // SIDE instantiations of the LM kernels.  Problem p's PriorDesc (ea_prior.h; the table sits behind the group table) is
@@ -2814,8 +2932,13 @@ hipError_t launch_eval_poses_grid(const EvalLaunch &s, const ProblemDesc *probs,
                    : launch_fused_family(1, s, probs, nterms, poses, partials, stream);
 }
 
+// the wave-exchange instantiations (MODE = kModeExchange) of ea_eval_poses_kernel / ea_eval_starts_kernel: fp64 in 256-lane
+// workgroups, at every shape the plain ones have
+template <typename T, int NT> constexpr bool exchange_exists() { return sizeof(T) == 8 && NT == 256; }
+
 // ea_eval_poses_kernel: g poses of a batch of `rows` partial rows per pose in one launch, `fold` (fold.n riders, 0 = none)
-// riding in front (ea_poses_map.h).  Plain functor, L2 path, one term per problem.
+// riding in front (ea_poses_map.h).  Plain functor, L2 path, one term per problem.  p.exchange asks for the wave-exchange
+// reduction (fp64 in 256-lane workgroups; refused elsewhere); the launch then takes kXchgBytes of dynamic LDS.
 hipError_t launch_eval_poses(const EvalLaunch &s, const PosesLaunch &p, const ProblemDesc *probs, const PoseState *poses,
                              double *partials, const PosesFold &fold, hipStream_t stream) {
   if (s.variant || s.lds_bytes > 0 || s.wide || !s.terms_are_groups || s.chunk != s.nt * s.ppt) return hipErrorInvalidValue;
@@ -2829,7 +2952,14 @@ hipError_t launch_eval_poses(const EvalLaunch &s, const PosesLaunch &p, const Pr
         constexpr int P = decltype(PPT)::value, N = decltype(NT)::value;
         constexpr bool B = decltype(BUF)::value, I = decltype(IMG32)::value;
         if constexpr (!fused_exists<T, P, 0, N, false, B, I>()) return hipErrorInvalidValue;
-        else {
+        else if (p.exchange) {
+          if constexpr (!exchange_exists<T, N>()) return hipErrorInvalidValue;
+          else {
+            hipLaunchKernelGGL((ea_eval_poses_kernel<T, P, kModeExchange, N, false, B, I>), grid, dim3(N), (size_t)kXchgBytes, stream,
+                               s.x0, s.y0, s.z0, s.n0, shape, p.g, p.rows, probs, poses, partials, fold);
+            return hipGetLastError();
+          }
+        } else {
           hipLaunchKernelGGL((ea_eval_poses_kernel<T, P, 0, N, false, B, I>), grid, dim3(N), (size_t)kHdrBytes, stream, s.x0, s.y0,
                              s.z0, s.n0, shape, p.g, p.rows, probs, poses, partials, fold);
           return hipGetLastError();
@@ -2894,7 +3024,14 @@ hipError_t launch_eval_starts(const EvalLaunch &s, const PosesLaunch &p, const P
       constexpr int P = decltype(PPT)::value;
       constexpr bool B = decltype(BUF)::value, I = decltype(IMG32)::value;
       if constexpr (!fused_exists<T, P, 0, kLmThreads, false, B, I>()) return hipErrorInvalidValue;
-      else {
+      else if (p.exchange) {
+        if constexpr (!exchange_exists<T, kLmThreads>()) return hipErrorInvalidValue;
+        else {
+          hipLaunchKernelGGL((ea_eval_starts_kernel<T, P, kModeExchange, kLmThreads, false, B, I>), grid, dim3(kLmThreads), (size_t)kXchgBytes,
+                             stream, s.x0, s.y0, s.z0, s.n0, shape, p.g, p.rows, probs, poses, partials, live, n_live, off);
+          return hipGetLastError();
+        }
+      } else {
         hipLaunchKernelGGL((ea_eval_starts_kernel<T, P, 0, kLmThreads, false, B, I>), grid, dim3(kLmThreads), (size_t)kHdrBytes, stream,
                            s.x0, s.y0, s.z0, s.n0, shape, p.g, p.rows, probs, poses, partials, live, n_live, off);
         return hipGetLastError();

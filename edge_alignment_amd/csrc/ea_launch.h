@@ -35,8 +35,9 @@ struct EvalLaunch {
 // the fold that rides in an evaluation's launch: the previous step's rows into its result slots
 struct RidingFold { const GroupDesc *groups; const double *prev_rows; EvalOut *prev_out; };
 // a launch of ea_eval_poses_kernel: g poses x `rows` partial rows per pose; order: 0 = an XCD walks the poses of a row back to
-// back, 1 = the rows of a pose; single: one term in the batch (no row table is read)
-struct PosesLaunch { int g = 0, rows = 0, order = 0, single = 0; };
+// back, 1 = the rows of a pose; single: one term in the batch (no row table is read); exchange: the wave-exchange reduction
+// (fp64 in 256-lane workgroups only; ea_wave_exchange.h)
+struct PosesLaunch { int g = 0, rows = 0, order = 0, single = 0, exchange = 0; };
 // What the folds of the pose-batched path work on: `n` results (pose-major: result r = pose r / count, problem r % count)
 // whose rows lie in `rows` (pose p's at p * rows_per_pose + the problem's range in `groups`, the group table in the pose
 // path's own chunking), folded into out[r]; counter / host_flag / seq: the completion signal of ea_reduce_done_kernel.

@@ -514,8 +514,13 @@ int ea_eval_rows_device(ea_problem *p, const double q[4], const double t[3], int
 /* ---- tuning ---------------------------------------------------------------------------- */
 /* tuning knobs: key in {"lds_bytes", "points_per_thread", "use_lds", "xcd_remap", "threads", "buffer_loads",
  * "solve_streams", "rows_staged", "rows_nontemporal", "wide_accumulate", "dt_f32", "poses_per_launch", "poll_results",
- * "fused_iterations", "zero_copy_poses", "starts_events", "cost_form"};
+ * "fused_iterations", "zero_copy_poses", "starts_events", "cost_form", "poses_wave_exchange"};
  * value < 0 restores the default.
+ * "poses_wave_exchange" = 0: the fp64 pose-batched evaluation in 256-lane workgroups (ea_batch_eval_poses, the evaluations of
+ * ea_batch_solve_starts) reduces with one 32-value butterfly per wavefront; default 1: the four wavefronts of a workgroup
+ * first add their sums lane by lane through LDS and each runs the butterfly over the 8 slots it is left with (another fixed
+ * summation order: results agree to rounding).  Setting it drops resident poses; ea_batch_get_info "poses_wave_exchange"
+ * reports what the last pose-batched launch ran (0 for fp32, 1024-lane workgroups and the forms the flat launch does not cover).
  * "starts_events" = 1 (measurement): ea_batch_solve_starts brackets the launches it queues with an event pair and waits
  * for it; ea_batch_get_info "starts_device_ns" / "starts_iterations" then report the device time and the iterations queued.
  * "dt_f32" = 0: an fp64 batch reads its fp64 images even where a float32 mirror holds them exactly (default: the mirror
