@@ -1076,6 +1076,115 @@ template <> __device__ __forceinline__ double uniform_scalar<double>(double v) {
   return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
 }
 
+// ---- the head of a work item -------------------------------------------------------------------------------------------
+// What every evaluation kernel does between knowing its (chunk, term, pose slot) and fused_chunk, written ONCE: the kernels'
+// promises of equal bits (a start's rows = the pose-batched rows, the fused iteration = the step pair, the flat launch = the
+// grid) and any change to what the common path reads rest on this text.  The ORDER of its statements is the point:
+//   1. term 0's points -- arrays and count came with the wave (kernarg preload) -- go out first, so that the coalesced point
+//      loads travel while descriptor and pose are fetched: one dependent memory round trip less in the chain descriptor ->
+//      points -> stencil rows that bounds a small launch;
+//   2. descriptor and pose by value, every uniform the common path reads named in front of the early exit, so that they go
+//      out as ONE batch of scalar loads behind one wait.  Left alone the compiler fetches what the exit test needs, then the
+//      pose's flag, then the rest: three dependent round trips at the head of every workgroup;
+//   3. the early exit, then the point loads of every other term, which had to wait for the descriptor.
+
+// A lane's PPT points of a chunk of `count` points, from the three arrays at the chunk's first point: coalesced, a point's
+// X, Y, Z issued together; lanes past the end of the chunk re-read its last point.  BUF: the chunk as three raw buffers, one
+// 32-bit offset per lane serves all three loads.
+template <typename T, int PPT, int NT, bool BUF>
+__device__ __forceinline__ void load_chunk_points(const T *px, const T *py, const T *pz, int count, T (&X)[PPT], T (&Y)[PPT],
+                                                  T (&Z)[PPT]) {
+  const int tid = threadIdx.x;
+  if constexpr (BUF) {
+    const __amdgpu_buffer_rsrc_t rx = make_raw_buffer(px, (unsigned)count * (unsigned)sizeof(T));
+    const __amdgpu_buffer_rsrc_t ry = make_raw_buffer(py, (unsigned)count * (unsigned)sizeof(T));
+    const __amdgpu_buffer_rsrc_t rz = make_raw_buffer(pz, (unsigned)count * (unsigned)sizeof(T));
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) {
+      const int poff = min(tid + k * NT, count - 1) * (int)sizeof(T);
+      X[k] = buf_load_elem<T>(rx, poff); Y[k] = buf_load_elem<T>(ry, poff); Z[k] = buf_load_elem<T>(rz, poff);
+    }
+  } else {
+    const GPtr<T> gx = (GPtr<T>)px, gy = (GPtr<T>)py, gz = (GPtr<T>)pz;
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) {
+      const int jj = min(tid + k * NT, count - 1);
+      X[k] = gx[jj]; Y[k] = gy[jj]; Z[k] = gz[jj];
+    }
+  }
+}
+
+// the descriptor words every evaluation reads, as operands of an `asm volatile("" :: ...)` that names them in one place
+#define EA_DESC_UNIFORMS(T, IMG32, pd)                                                                                     \
+  "s"(pd.x), "s"(pd.y), "s"(pd.z), "s"(IMG32 ? pd.dt32 : pd.dt), "s"(pd.n), "s"(pd.W), "s"(pd.H), "s"(pd.pitch),           \
+  "s"(Uni<T>::fx(pd)), "s"(Uni<T>::fy(pd)), "s"(Uni<T>::cx(pd)), "s"(Uni<T>::cy(pd)), "s"(Uni<T>::loss_a(pd)),             \
+  "s"(Uni<T>::loss_inv_b(pd)), "s"(Uni<T>::z_guard(pd)), "s"(Uni<T>::z_eps(pd)), "s"(pd.loss_kind)
+
+template <typename T>
+__device__ __forceinline__ void load_pose_lite(const PoseState *psp, PoseLite<T> &ps, int &active) {
+  const T *R_ = Uni<T>::R(*psp), *t_ = Uni<T>::t(*psp);
+#pragma unroll
+  for (int i = 0; i < 9; ++i) ps.R[i] = R_[i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) ps.t[i] = t_[i];
+  ps.unit_q = psp->unit_q;
+  ps.full = psp;
+  active = psp->active;
+}
+
+// Step 2: the pose at `psp` into scalars beside the descriptor `pd` (already assigned by value), both pinned.  GRID: the
+// (chunks, terms) grid of eval_fused_body also reads the descriptor's row base and pose group.
+template <typename T, bool IMG32, bool GRID>
+__device__ __forceinline__ void fetch_item_uniforms(const ProblemDesc &pd, const PoseState *psp, PoseLite<T> &ps, int &active) {
+  load_pose_lite<T>(psp, ps, active);
+  if constexpr (GRID) asm volatile("" ::EA_DESC_UNIFORMS(T, IMG32, pd), "s"(pd.tile_begin), "s"(pd.variant), "s"(pd.group));
+  else asm volatile("" ::EA_DESC_UNIFORMS(T, IMG32, pd), "s"(pd.variant));
+  asm volatile("" : "+s"(active), "+s"(ps.unit_q), "+s"(ps.R[0]), "+s"(ps.R[1]), "+s"(ps.R[2]), "+s"(ps.R[3]), "+s"(ps.R[4]),
+                    "+s"(ps.R[5]), "+s"(ps.R[6]), "+s"(ps.R[7]), "+s"(ps.R[8]), "+s"(ps.t[0]), "+s"(ps.t[1]), "+s"(ps.t[2]));
+}
+
+// Steps 1 to 3 for work item (chunk c_ of chunk_ points, term_, pose slot_), as the text of the kernel that names it: behind it
+// `pd` (const), `ps`, `X`, `Y`, `Z`, `count` and `start` are the kernel's locals.  NOTHING is the statement of an item with
+// nothing to evaluate (`return`, or what the kernel owes for an empty row first).  The pose is fetched SPECULATIVELY from
+// slot_, independent of the descriptor; under GRID_ with regroup_ (terms that share poses) a term whose group is another
+// slot fetches again (uniform, rare).  Reads the kernel's T, PPT, NT, BUF, IMG32 and x0, y0, z0, n0, probs, poses.
+// A macro and not a function: with the descriptor a const local of the kernel and the exits the kernel's own `return`,
+// the compiler emits the code of the heads written out (profiles/item_head_listing.md); handed out of a function -- through
+// references, or to the rest of the kernel as a continuation -- the fp64 exchange and the cost kernels merge the early and
+// the late point loads through register copies and the variant fp64 kernel grows by a tenth.  For the same reason a kernel's
+// `const int tid = threadIdx.x` stays in FRONT of the head.
+#define EA_ITEM_HEAD(GRID_, chunk_, c_, term_, slot_, regroup_, NOTHING)                                                   \
+  const long long start = (long long)(c_) * (chunk_);                                                                      \
+  T X[PPT], Y[PPT], Z[PPT];                                                                                                \
+  const bool early = BUF && (term_) == 0 && n0 > 0; /* (uniform) */                                                        \
+  if (early) {                                                                                                             \
+    if (start >= n0) { NOTHING; }                                                                                          \
+    load_chunk_points<T, PPT, NT, true>(static_cast<const T *>(x0) + start, static_cast<const T *>(y0) + start,            \
+                                        static_cast<const T *>(z0) + start, min((chunk_), (int)(n0 - start)), X, Y, Z);   \
+  }                                                                                                                        \
+  const ProblemDesc pd = probs[term_];                                                                                     \
+  PoseLite<T> ps;                                                                                                          \
+  int active;                                                                                                              \
+  fetch_item_uniforms<T, IMG32, GRID_>(pd, poses + (slot_), ps, active);                                                   \
+  if (GRID_ && (regroup_) && pd.group != (int)(slot_)) load_pose_lite<T>(poses + pd.group, ps, active);                    \
+  if (start >= pd.n || !active) { NOTHING; }                                                                               \
+  const int count = min((chunk_), (int)(pd.n - start));                                                                    \
+  if (!early)                                                                                                              \
+    load_chunk_points<T, PPT, NT, BUF>(static_cast<const T *>(pd.x) + start, static_cast<const T *>(pd.y) + start,         \
+                                       static_cast<const T *>(pd.z) + start, count, X, Y, Z)
+
+// a finished row sum into slot (tid, or the exchange's slot) of partial row `out_row`
+template <bool XCHG>
+__device__ __forceinline__ void store_row_sum(double *__restrict__ partials, int out_row, double sum) {
+  const int tid = threadIdx.x;
+  if constexpr (XCHG) {  // (one lane per (wavefront, slot) holds the finished sum)
+    const int slot = xchg_store_slot(tid >> 6, tid & 63);
+    if (slot >= 0) partials[(size_t)out_row * kAccSlots + slot] = sum;
+  } else {
+    if (tid < kAccSlots) partials[(size_t)out_row * kAccSlots + tid] = sum;
+  }
+}
+
 // NT = workgroup size (256 or 1024).  1024 = one workgroup per CU: four times fewer partial rows
 // to fold afterwards at the same points-per-lane latency.
 template <typename T, int PPT, int MODE, int NT, bool VAR, bool BUF, bool IMG32>
@@ -1095,95 +1204,9 @@ __device__ __forceinline__ void eval_fused_body(
   EA_STAMP(0);
   const int bx = blockIdx.x;
   const int c = xcd_remap ? (bx & 7) * chunks_per_xcd + (bx >> 3) : bx;
-  const long long start = (long long)c * chunk;
   const int tid = threadIdx.x;
-  T X[PPT], Y[PPT], Z[PPT];
-  // Problem 0 (every single-problem launch: C2, an LM iteration): its point arrays and count came with the wave, so the
-  // coalesced point loads go out now and travel while the descriptor and the pose are fetched -- one dependent memory
-  // round trip less in the chain descriptor -> points -> stencil rows that bounds a small launch.
-  const bool early = BUF && blockIdx.y == 0 && n0 > 0;  // (uniform)
-  if constexpr (BUF) {
-    if (early) {
-      if (start >= n0) return;
-      const int count0 = min(chunk, (int)(n0 - start));
-      const __amdgpu_buffer_rsrc_t rx = make_raw_buffer(static_cast<const T *>(x0) + start, (unsigned)count0 * (unsigned)sizeof(T));
-      const __amdgpu_buffer_rsrc_t ry = make_raw_buffer(static_cast<const T *>(y0) + start, (unsigned)count0 * (unsigned)sizeof(T));
-      const __amdgpu_buffer_rsrc_t rz = make_raw_buffer(static_cast<const T *>(z0) + start, (unsigned)count0 * (unsigned)sizeof(T));
-#pragma unroll
-      for (int k = 0; k < PPT; ++k) {
-        const int poff = min(tid + k * NT, count0 - 1) * (int)sizeof(T);
-        X[k] = buf_load_elem<T>(rx, poff); Y[k] = buf_load_elem<T>(ry, poff); Z[k] = buf_load_elem<T>(rz, poff);
-      }
-    }
-  }
-  // descriptor and pose by value: every scalar load is issued here, behind one wait, instead of a
-  // chain of dependent loads at the points of use
-  const ProblemDesc pd = probs[blockIdx.y];
-  // one pose per group of terms; when every problem is a single residual family the group index is
-  // the term index and the pose load does not have to wait for the descriptor
-  // The pose is fetched SPECULATIVELY from the slot of this term's own index -- the right one whenever every problem is a
-  // single residual family (terms_are_groups), and then independent of the descriptor -- into scalars, beside the
-  // descriptor.  Every uniform the common path reads is named in front of the early exit: descriptor and pose go out as
-  // ONE batch of scalar loads behind one wait.  Left alone the compiler fetches what the exit test needs, then the
-  // pose's flag, then the rest: three dependent round trips at the head of every workgroup.
-  PoseLite<T> ps;
-  int active;
-  {
-    const PoseState *psp = poses + blockIdx.y;
-    const T *R_ = Uni<T>::R(*psp), *t_ = Uni<T>::t(*psp);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) ps.R[i] = R_[i];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) ps.t[i] = t_[i];
-    ps.unit_q = psp->unit_q;
-    ps.full = psp;
-    active = psp->active;
-    asm volatile("" ::"s"(pd.x), "s"(pd.y), "s"(pd.z), "s"(IMG32 ? pd.dt32 : pd.dt), "s"(pd.n), "s"(pd.W), "s"(pd.H), "s"(pd.pitch),
-                 "s"(Uni<T>::fx(pd)), "s"(Uni<T>::fy(pd)), "s"(Uni<T>::cx(pd)), "s"(Uni<T>::cy(pd)),
-                 "s"(Uni<T>::loss_a(pd)), "s"(Uni<T>::loss_inv_b(pd)), "s"(Uni<T>::z_guard(pd)), "s"(Uni<T>::z_eps(pd)),
-                 "s"(pd.loss_kind), "s"(pd.tile_begin), "s"(pd.variant), "s"(pd.group));
-    asm volatile("" : "+s"(active), "+s"(ps.unit_q), "+s"(ps.R[0]), "+s"(ps.R[1]), "+s"(ps.R[2]), "+s"(ps.R[3]), "+s"(ps.R[4]),
-                      "+s"(ps.R[5]), "+s"(ps.R[6]), "+s"(ps.R[7]), "+s"(ps.R[8]), "+s"(ps.t[0]), "+s"(ps.t[1]), "+s"(ps.t[2]));
-    if (!terms_are_groups && pd.group != (int)blockIdx.y) {  // (uniform, rare: a term that shares another term's pose)
-      psp = poses + pd.group;
-      R_ = Uni<T>::R(*psp); t_ = Uni<T>::t(*psp);
-#pragma unroll
-      for (int i = 0; i < 9; ++i) ps.R[i] = R_[i];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) ps.t[i] = t_[i];
-      ps.unit_q = psp->unit_q;
-      ps.full = psp;
-      active = psp->active;
-    }
-  }
-  if (start >= pd.n || !active) return;
-  const int count = min(chunk, (int)(pd.n - start));
-  EA_STAMP(1);  // descriptor + pose.active arrived
-
-  const GPtr<T> px = (GPtr<T>)(static_cast<const T *>(pd.x) + start);
-  const GPtr<T> py = (GPtr<T>)(static_cast<const T *>(pd.y) + start);
-  const GPtr<T> pz = (GPtr<T>)(static_cast<const T *>(pd.z) + start);
-  // coalesced point loads; lanes past the end of the chunk re-read its last point
-  if constexpr (BUF) {
-    if (!early) {
-      // the chunk's points as three raw buffers: one 32-bit offset per lane serves all three loads
-      const __amdgpu_buffer_rsrc_t rx = make_raw_buffer((const T *)px, (unsigned)count * (unsigned)sizeof(T));
-      const __amdgpu_buffer_rsrc_t ry = make_raw_buffer((const T *)py, (unsigned)count * (unsigned)sizeof(T));
-      const __amdgpu_buffer_rsrc_t rz = make_raw_buffer((const T *)pz, (unsigned)count * (unsigned)sizeof(T));
-#pragma unroll
-      for (int k = 0; k < PPT; ++k) {
-        const int poff = min(tid + k * NT, count - 1) * (int)sizeof(T);
-        X[k] = buf_load_elem<T>(rx, poff); Y[k] = buf_load_elem<T>(ry, poff); Z[k] = buf_load_elem<T>(rz, poff);
-      }
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < PPT; ++k) {
-      const int j = tid + k * NT;
-      const int jj = min(j, count - 1);
-      X[k] = px[jj]; Y[k] = py[jj]; Z[k] = pz[jj];
-    }
-  }
+  EA_ITEM_HEAD(true, chunk, c, blockIdx.y, blockIdx.y, !terms_are_groups, return);
+  EA_STAMP(1);  // descriptor + pose.active arrived (the late point loads are out)
 #ifdef EA_STAMPS
   asm volatile("" ::"v"(X[0]), "v"(Y[0]), "v"(Z[0]));
 #endif
@@ -1623,6 +1646,19 @@ __global__ __launch_bounds__(kFoldThreads) void ea_reduce_kernel(const GroupDesc
   reduce_tiles<kFoldThreads, 4>(partials, gd.tile_begin, gd.tile_end, s_part, out[blockIdx.x].acc);
 }
 
+// One workgroup of a launch of n is done: its lane 0 makes the workgroup's stores visible system-wide (the fence waits for the
+// wavefront's stores) and counts itself in; the last arrival re-arms the counter and raises the flag in pinned host memory
+// to the launch's sequence number (release, system scope).  Call from lane 0 of the wavefront that stored.
+__device__ __forceinline__ void signal_done(unsigned int *counter, unsigned int n, int *host_flag, int seq) {
+  __threadfence_system();
+  const unsigned int prev = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+  if (prev == n - 1u) {
+    __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __threadfence_system();
+    __hip_atomic_store(host_flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
 // The same fold for the synchronous evaluations (ea_batch_eval, ea_batch_eval_poses), whose results go straight into pinned
 // host memory: the workgroup that finishes last raises a flag there, so that the host can poll for "every result has
 // landed" instead of waiting for the stream's completion signal (~10 us later).  Every workgroup's 32 result words are
@@ -1636,15 +1672,7 @@ __global__ __launch_bounds__(kFoldThreads) void ea_reduce_done_kernel(const Grou
   __shared__ __align__(16) double s_part[reduce_tiles_lds<kFoldThreads>()];
   const GroupDesc gd = groups[blockIdx.x];
   reduce_tiles<kFoldThreads, 4>(partials, gd.tile_begin, gd.tile_end, s_part, out[blockIdx.x].acc);
-  if (threadIdx.x == 0) {
-    __threadfence_system();
-    const unsigned int prev = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    if (prev == gridDim.x - 1) {
-      __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __threadfence_system();
-      __hip_atomic_store(host_flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  }
+  if (threadIdx.x == 0) signal_done(counter, gridDim.x, host_flag, seq);
 }
 
 // The fold as a 256-thread workgroup sums it when it rides in an evaluation launch (ea_eval_fold_kernel below; 8 rows in
@@ -1691,15 +1719,7 @@ __device__ __forceinline__ void poses_fold_one(const PosesFold &f, int r) {
   const GroupDesc gd = f.groups[problem];
   const int base = pose * f.rows_per_pose;
   reduce_tiles<NT, 4>(f.rows, base + gd.tile_begin, base + gd.tile_end, s_part, f.out[r].acc);
-  if (threadIdx.x == 0) {
-    __threadfence_system();
-    const unsigned int prev = __hip_atomic_fetch_add(f.counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    if (prev == (unsigned)f.n - 1u) {
-      __hip_atomic_store(f.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __threadfence_system();
-      __hip_atomic_store(f.host_flag, f.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  }
+  if (threadIdx.x == 0) signal_done(f.counter, (unsigned)f.n, f.host_flag, f.seq);
 }
 
 // The pose-batched evaluation of the plain functor on the L2 path: g poses of a batch in ONE one-dimensional launch whose
@@ -1719,7 +1739,6 @@ __global__ __launch_bounds__(NT) void ea_eval_poses_kernel(
     double *__restrict__ partials, PosesFold fold) {
   static_assert((MODE == 0 || MODE == kModeExchange) && !VAR, "plain functor, stencil rows from L2");
   constexpr bool XCHG = MODE == kModeExchange;
-  constexpr int chunk = NT * PPT;
   extern __shared__ __align__(16) unsigned char smem[];
   double *s_red = reinterpret_cast<double *>(smem);
   int *s_box = reinterpret_cast<int *>(smem + kRedBytes);
@@ -1729,78 +1748,11 @@ __global__ __launch_bounds__(NT) void ea_eval_poses_kernel(
     return;
   }
   const PosesChunk pc = poses_chunk(w, shape, rows, reinterpret_cast<const PosesRow *>(probs) - rows);
-  const int c = pc.chunk;
-  const long long start = (long long)c * chunk;
   const int tid = threadIdx.x;
-  T X[PPT], Y[PPT], Z[PPT];
-  const bool early = BUF && pc.term == 0 && n0 > 0;  // (uniform)
-  if constexpr (BUF) {
-    if (early) {
-      if (start >= n0) return;
-      const int count0 = min(chunk, (int)(n0 - start));
-      const __amdgpu_buffer_rsrc_t rx = make_raw_buffer(static_cast<const T *>(x0) + start, (unsigned)count0 * (unsigned)sizeof(T));
-      const __amdgpu_buffer_rsrc_t ry = make_raw_buffer(static_cast<const T *>(y0) + start, (unsigned)count0 * (unsigned)sizeof(T));
-      const __amdgpu_buffer_rsrc_t rz = make_raw_buffer(static_cast<const T *>(z0) + start, (unsigned)count0 * (unsigned)sizeof(T));
-#pragma unroll
-      for (int k = 0; k < PPT; ++k) {
-        const int poff = min(tid + k * NT, count0 - 1) * (int)sizeof(T);
-        X[k] = buf_load_elem<T>(rx, poff); Y[k] = buf_load_elem<T>(ry, poff); Z[k] = buf_load_elem<T>(rz, poff);
-      }
-    }
-  }
-  // descriptor and pose by value, as ONE batch of scalar loads behind one wait (eval_fused_body)
-  const ProblemDesc pd = probs[pc.term];
-  PoseLite<T> ps;
-  int active;
-  {
-    const PoseState *psp = poses + pc.slot;
-    const T *R_ = Uni<T>::R(*psp), *t_ = Uni<T>::t(*psp);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) ps.R[i] = R_[i];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) ps.t[i] = t_[i];
-    ps.unit_q = psp->unit_q;
-    ps.full = psp;
-    active = psp->active;
-    asm volatile("" ::"s"(pd.x), "s"(pd.y), "s"(pd.z), "s"(IMG32 ? pd.dt32 : pd.dt), "s"(pd.n), "s"(pd.W), "s"(pd.H), "s"(pd.pitch),
-                 "s"(Uni<T>::fx(pd)), "s"(Uni<T>::fy(pd)), "s"(Uni<T>::cx(pd)), "s"(Uni<T>::cy(pd)),
-                 "s"(Uni<T>::loss_a(pd)), "s"(Uni<T>::loss_inv_b(pd)), "s"(Uni<T>::z_guard(pd)), "s"(Uni<T>::z_eps(pd)),
-                 "s"(pd.loss_kind), "s"(pd.variant));
-    asm volatile("" : "+s"(active), "+s"(ps.unit_q), "+s"(ps.R[0]), "+s"(ps.R[1]), "+s"(ps.R[2]), "+s"(ps.R[3]), "+s"(ps.R[4]),
-                      "+s"(ps.R[5]), "+s"(ps.R[6]), "+s"(ps.R[7]), "+s"(ps.R[8]), "+s"(ps.t[0]), "+s"(ps.t[1]), "+s"(ps.t[2]));
-  }
-  if (start >= pd.n || !active) return;
-  const int count = min(chunk, (int)(pd.n - start));
-  const GPtr<T> px = (GPtr<T>)(static_cast<const T *>(pd.x) + start);
-  const GPtr<T> py = (GPtr<T>)(static_cast<const T *>(pd.y) + start);
-  const GPtr<T> pz = (GPtr<T>)(static_cast<const T *>(pd.z) + start);
-  // coalesced point loads; lanes past the end of the chunk re-read its last point
-  if constexpr (BUF) {
-    if (!early) {
-      const __amdgpu_buffer_rsrc_t rx = make_raw_buffer((const T *)px, (unsigned)count * (unsigned)sizeof(T));
-      const __amdgpu_buffer_rsrc_t ry = make_raw_buffer((const T *)py, (unsigned)count * (unsigned)sizeof(T));
-      const __amdgpu_buffer_rsrc_t rz = make_raw_buffer((const T *)pz, (unsigned)count * (unsigned)sizeof(T));
-#pragma unroll
-      for (int k = 0; k < PPT; ++k) {
-        const int poff = min(tid + k * NT, count - 1) * (int)sizeof(T);
-        X[k] = buf_load_elem<T>(rx, poff); Y[k] = buf_load_elem<T>(ry, poff); Z[k] = buf_load_elem<T>(rz, poff);
-      }
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < PPT; ++k) {
-      const int jj = min(tid + k * NT, count - 1);
-      X[k] = px[jj]; Y[k] = py[jj]; Z[k] = pz[jj];
-    }
-  }
+  EA_ITEM_HEAD(false, NT * PPT, pc.chunk, pc.term, pc.slot, false, return);
   const double sum = fused_chunk<T, PPT, 0, NT, false, BUF, IMG32, PoseLite<T>, XCHG>(pd, ps, X, Y, Z, count, s_red, s_box, (T *)nullptr, 0,
                                                                                        tid < kAccSlots ? tid : -1);
-  if constexpr (XCHG) {  // (one lane per (wavefront, slot) holds the finished sum)
-    const int slot = xchg_store_slot(tid >> 6, tid & 63);
-    if (slot >= 0) partials[(size_t)pc.out_row * kAccSlots + slot] = sum;
-  } else {
-    if (tid < kAccSlots) partials[(size_t)pc.out_row * kAccSlots + tid] = sum;
-  }
+  store_row_sum<XCHG>(partials, pc.out_row, sum);
 }
 
 // the fold that closes a call of the pose-batched path: the last launch's rows, as its riders would have folded them
@@ -1814,79 +1766,6 @@ __global__ __launch_bounds__(NT) void ea_poses_fold_kernel(PosesFold fold) {
 // count, nothing else.  ea_cost_poses_kernel takes ea_eval_poses_kernel's work items -- the same flat, XCD-dealt list, chunks,
 // descriptor / row-table fetch, point loads and pose slots -- and runs per point the projection, the four row loads, the
 // VALUE of the Catmull-Rom patch and rho: no derivative weights, no 1x6 row, no JtJ / Jtr products, two sums instead of 28.
-
-// the lanes' share of a work item of the pose-batched launches: descriptor and pose by value (ONE batch of scalar loads
-// behind one wait), the lane's PPT points (lanes past the end of the chunk re-read its last point).  false: nothing to
-// evaluate.  This is the head ea_eval_poses_kernel and ea_eval_starts_kernel carry inline, statement for statement; calling
-// it from those two changes the code the compiler emits for 23 of their instantiations (scripts/compare_device_code.py),
-// so they keep their own text and new kernels over the same work items start from here.
-template <typename T, int PPT, int NT, bool BUF, bool IMG32>
-__device__ __forceinline__ bool poses_item_head(const void *__restrict__ x0, const void *__restrict__ y0, const void *__restrict__ z0,
-                                                int n0, const ProblemDesc *__restrict__ probs, const PoseState *__restrict__ poses,
-                                                const PosesChunk &pc, ProblemDesc &pd, PoseLite<T> &ps, T (&X)[PPT], T (&Y)[PPT],
-                                                T (&Z)[PPT], int &count) {
-  constexpr int chunk = NT * PPT;
-  const long long start = (long long)pc.chunk * chunk;
-  const int tid = threadIdx.x;
-  const bool early = BUF && pc.term == 0 && n0 > 0;  // (uniform)
-  if constexpr (BUF) {
-    if (early) {
-      if (start >= n0) return false;
-      const int count0 = min(chunk, (int)(n0 - start));
-      const __amdgpu_buffer_rsrc_t rx = make_raw_buffer(static_cast<const T *>(x0) + start, (unsigned)count0 * (unsigned)sizeof(T));
-      const __amdgpu_buffer_rsrc_t ry = make_raw_buffer(static_cast<const T *>(y0) + start, (unsigned)count0 * (unsigned)sizeof(T));
-      const __amdgpu_buffer_rsrc_t rz = make_raw_buffer(static_cast<const T *>(z0) + start, (unsigned)count0 * (unsigned)sizeof(T));
-#pragma unroll
-      for (int k = 0; k < PPT; ++k) {
-        const int poff = min(tid + k * NT, count0 - 1) * (int)sizeof(T);
-        X[k] = buf_load_elem<T>(rx, poff); Y[k] = buf_load_elem<T>(ry, poff); Z[k] = buf_load_elem<T>(rz, poff);
-      }
-    }
-  }
-  pd = probs[pc.term];
-  int active;
-  {
-    const PoseState *psp = poses + pc.slot;
-    const T *R_ = Uni<T>::R(*psp), *t_ = Uni<T>::t(*psp);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) ps.R[i] = R_[i];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) ps.t[i] = t_[i];
-    ps.unit_q = psp->unit_q;
-    ps.full = psp;
-    active = psp->active;
-    asm volatile("" ::"s"(pd.x), "s"(pd.y), "s"(pd.z), "s"(IMG32 ? pd.dt32 : pd.dt), "s"(pd.n), "s"(pd.W), "s"(pd.H), "s"(pd.pitch),
-                 "s"(Uni<T>::fx(pd)), "s"(Uni<T>::fy(pd)), "s"(Uni<T>::cx(pd)), "s"(Uni<T>::cy(pd)),
-                 "s"(Uni<T>::loss_a(pd)), "s"(Uni<T>::loss_inv_b(pd)), "s"(Uni<T>::z_guard(pd)), "s"(Uni<T>::z_eps(pd)),
-                 "s"(pd.loss_kind), "s"(pd.variant));
-    asm volatile("" : "+s"(active), "+s"(ps.unit_q), "+s"(ps.R[0]), "+s"(ps.R[1]), "+s"(ps.R[2]), "+s"(ps.R[3]), "+s"(ps.R[4]),
-                      "+s"(ps.R[5]), "+s"(ps.R[6]), "+s"(ps.R[7]), "+s"(ps.R[8]), "+s"(ps.t[0]), "+s"(ps.t[1]), "+s"(ps.t[2]));
-  }
-  if (start >= pd.n || !active) return false;
-  count = min(chunk, (int)(pd.n - start));
-  const GPtr<T> px = (GPtr<T>)(static_cast<const T *>(pd.x) + start);
-  const GPtr<T> py = (GPtr<T>)(static_cast<const T *>(pd.y) + start);
-  const GPtr<T> pz = (GPtr<T>)(static_cast<const T *>(pd.z) + start);
-  if constexpr (BUF) {
-    if (!early) {
-      const __amdgpu_buffer_rsrc_t rx = make_raw_buffer((const T *)px, (unsigned)count * (unsigned)sizeof(T));
-      const __amdgpu_buffer_rsrc_t ry = make_raw_buffer((const T *)py, (unsigned)count * (unsigned)sizeof(T));
-      const __amdgpu_buffer_rsrc_t rz = make_raw_buffer((const T *)pz, (unsigned)count * (unsigned)sizeof(T));
-#pragma unroll
-      for (int k = 0; k < PPT; ++k) {
-        const int poff = min(tid + k * NT, count - 1) * (int)sizeof(T);
-        X[k] = buf_load_elem<T>(rx, poff); Y[k] = buf_load_elem<T>(ry, poff); Z[k] = buf_load_elem<T>(rz, poff);
-      }
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < PPT; ++k) {
-      const int jj = min(tid + k * NT, count - 1);
-      X[k] = px[jj]; Y[k] = py[jj]; Z[k] = pz[jj];
-    }
-  }
-  return true;
-}
 
 // the four tap weights of cr_weights alone (the same expressions: the sample is bicubic's f to the bit)
 template <typename T>
@@ -1950,33 +1829,38 @@ __device__ __forceinline__ V wave_sum1(V x) {
   x = swap_add<16>(x);
   return swap_add<32>(x);
 }
+// Two values per lane summed over the workgroup: each wavefront's sum (in the value's own type), one LDS slot per wavefront,
+// and lane 0 adds the slots in wave order -- the first in fp64.  The totals are lane 0's alone.
+template <int NT, typename A, typename B>
+__device__ __forceinline__ void workgroup_sum2(A a, B b, double &total_a, B &total_b) {
+  __shared__ double s_a[NT / 64];
+  __shared__ B s_b[NT / 64];
+  const int tid = threadIdx.x;
+  const A wa = wave_sum1<A>(a);
+  const B wb = wave_sum1<B>(b);
+  if ((tid & 63) == 0) { s_a[tid >> 6] = (double)wa; s_b[tid >> 6] = wb; }
+  __syncthreads();
+  if (tid == 0) {
+    double ta = 0.0;
+    B tb = 0;
+#pragma unroll
+    for (int v = 0; v < NT / 64; ++v) { ta += s_a[v]; tb += s_b[v]; }
+    total_a = ta; total_b = tb;
+  }
+}
 
 // one narrow partial per workgroup of the cost-only launches: 16 bytes at pose * rows + row
 struct __attribute__((aligned(16))) CostPartial { double cost, failed; };
 static_assert(sizeof(CostPartial) == kCostPartialBytes, "ea_launch.h");
 
-template <typename T, int PPT, int NT, bool BUF, bool IMG32 = false>
-__global__ __launch_bounds__(NT) void ea_cost_poses_kernel(
-    const void *__restrict__ x0, const void *__restrict__ y0, const void *__restrict__ z0, int n0,
-    int shape, int g, int rows,
-    const ProblemDesc *__restrict__ probs, const PoseState *__restrict__ poses,
-    CostPartial *__restrict__ partials) {
-  static_assert(!IMG32 || std::is_same<T, double>::value, "fp32-stored image: fp64 kernels");
+// item pc of a cost-only launch into its row; false: nothing to evaluate, nothing stored
+template <typename T, int PPT, int NT, bool BUF, bool IMG32>
+__device__ __forceinline__ bool cost_item(const void *__restrict__ x0, const void *__restrict__ y0, const void *__restrict__ z0, int n0,
+                                          const ProblemDesc *__restrict__ probs, const PoseState *__restrict__ poses,
+                                          const PosesChunk &pc, CostPartial *__restrict__ partials) {
   typedef typename ImgOf<T, IMG32>::type IT;
-  __shared__ double s_cost[NT / 64];
-  __shared__ int s_bad[NT / 64];
-  const PosesWork w = poses_work(blockIdx.x, shape, rows, g, 0);
-  if (w.kind != 2) return;  // (uniform)
-  const PosesChunk pc = poses_chunk(w, shape, rows, reinterpret_cast<const PosesRow *>(probs) - rows);
   const int tid = threadIdx.x;
-  ProblemDesc pd;
-  PoseLite<T> ps;
-  T X[PPT], Y[PPT], Z[PPT];
-  int count = 0;
-  if (!poses_item_head<T, PPT, NT, BUF, IMG32>(x0, y0, z0, n0, probs, poses, pc, pd, ps, X, Y, Z, count)) {
-    if (tid == 0) partials[pc.out_row] = CostPartial{0.0, 0.0};
-    return;
-  }
+  EA_ITEM_HEAD(false, NT * PPT, pc.chunk, pc.term, pc.slot, false, return false);
   const int pitch = pd.pitch;
   const void *img_base = IMG32 ? pd.dt32 : pd.dt;
   const GPtr<IT> gimg = (GPtr<IT>)(static_cast<const IT *>(img_base) + (size_t)kImagePad * (size_t)pitch + kImagePad);
@@ -2016,17 +1900,25 @@ __global__ __launch_bounds__(NT) void ea_cost_poses_kernel(
     acc = k == 0 ? T(0.5) * rho : t_fma<T>(T(0.5), rho, acc);
   }
   // a wavefront's sum in T, the workgroup's in fp64 through LDS in wave order: fixed by (chunk, lane, wave)
-  const T wsum = wave_sum1<T>(acc);
-  const int wbad = wave_sum1<int>(n_bad);
-  if ((tid & 63) == 0) { s_cost[tid >> 6] = (double)wsum; s_bad[tid >> 6] = wbad; }
-  __syncthreads();
-  if (tid == 0) {
-    double c = 0.0;
-    int nb = 0;
-#pragma unroll
-    for (int v = 0; v < NT / 64; ++v) { c += s_cost[v]; nb += s_bad[v]; }
-    partials[pc.out_row] = CostPartial{c, (double)nb};
-  }
+  double c;
+  int nb;
+  workgroup_sum2<NT>(acc, n_bad, c, nb);
+  if (tid == 0) partials[pc.out_row] = CostPartial{c, (double)nb};
+  return true;
+}
+
+template <typename T, int PPT, int NT, bool BUF, bool IMG32 = false>
+__global__ __launch_bounds__(NT) void ea_cost_poses_kernel(
+    const void *__restrict__ x0, const void *__restrict__ y0, const void *__restrict__ z0, int n0,
+    int shape, int g, int rows,
+    const ProblemDesc *__restrict__ probs, const PoseState *__restrict__ poses,
+    CostPartial *__restrict__ partials) {
+  static_assert(!IMG32 || std::is_same<T, double>::value, "fp32-stored image: fp64 kernels");
+  const PosesWork w = poses_work(blockIdx.x, shape, rows, g, 0);
+  if (w.kind != 2) return;  // (uniform)
+  const PosesChunk pc = poses_chunk(w, shape, rows, reinterpret_cast<const PosesRow *>(probs) - rows);
+  if (!cost_item<T, PPT, NT, BUF, IMG32>(x0, y0, z0, n0, probs, poses, pc, partials) && threadIdx.x == 0)
+    partials[pc.out_row] = CostPartial{0.0, 0.0};
 }
 
 // The fold of a cost-only launch: one 256-lane workgroup per (pose, problem) of the launch sums the pose's narrow partials
@@ -2035,7 +1927,6 @@ __global__ __launch_bounds__(NT) void ea_cost_poses_kernel(
 // arrival raises the pinned flag to the launch's sequence number (poses_fold_one's signal).
 template <int NT>
 __global__ __launch_bounds__(NT) void ea_cost_fold_kernel(PosesFold f) {
-  __shared__ double s_cost[NT / 64], s_bad[NT / 64];
   const int tid = threadIdx.x, r = blockIdx.x;
   int pose, problem;
   poses_rider(r, f.count, &pose, &problem);
@@ -2046,23 +1937,12 @@ __global__ __launch_bounds__(NT) void ea_cost_fold_kernel(PosesFold f) {
     const CostPartial p = rows[i];
     c += p.cost; nb += p.failed;
   }
-  c = wave_sum1<double>(c);
-  nb = wave_sum1<double>(nb);
-  if ((tid & 63) == 0) { s_cost[tid >> 6] = c; s_bad[tid >> 6] = nb; }
-  __syncthreads();
+  double ct, nt;
+  workgroup_sum2<NT>(c, nb, ct, nt);
   if (tid == 0) {
-    double ct = 0.0, nt = 0.0;
-#pragma unroll
-    for (int v = 0; v < NT / 64; ++v) { ct += s_cost[v]; nt += s_bad[v]; }
     f.out[r].acc[kAccCost] = ct;
     f.out[r].acc[kAccInvalid] = nt;
-    __threadfence_system();
-    const unsigned int prev = __hip_atomic_fetch_add(f.counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    if (prev == (unsigned)f.n - 1u) {
-      __hip_atomic_store(f.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __threadfence_system();
-      __hip_atomic_store(f.host_flag, f.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    signal_done(f.counter, (unsigned)f.n, f.host_flag, f.seq);
   }
 }
 
@@ -2080,7 +1960,6 @@ __global__ __launch_bounds__(NT) void ea_eval_starts_kernel(
     double *__restrict__ partials, const int *__restrict__ live, const int *__restrict__ n_live, int off) {
   static_assert((MODE == 0 || MODE == kModeExchange) && !VAR, "plain functor, stencil rows from L2");
   constexpr bool XCHG = MODE == kModeExchange;
-  constexpr int chunk = NT * PPT;
   extern __shared__ __align__(16) unsigned char smem[];
   double *s_red = reinterpret_cast<double *>(smem);
   int *s_box = reinterpret_cast<int *>(smem + kRedBytes);
@@ -2089,78 +1968,11 @@ __global__ __launch_bounds__(NT) void ea_eval_starts_kernel(
   if (!starts_position_live(off, w.pose, *n_live)) return;
   const int start_k = live[off + w.pose];
   const PosesChunk pc = starts_chunk(w, start_k, shape, rows, reinterpret_cast<const PosesRow *>(probs) - rows);
-  const int c = pc.chunk;
-  const long long start = (long long)c * chunk;
   const int tid = threadIdx.x;
-  T X[PPT], Y[PPT], Z[PPT];
-  const bool early = BUF && pc.term == 0 && n0 > 0;  // (uniform)
-  if constexpr (BUF) {
-    if (early) {
-      if (start >= n0) return;
-      const int count0 = min(chunk, (int)(n0 - start));
-      const __amdgpu_buffer_rsrc_t rx = make_raw_buffer(static_cast<const T *>(x0) + start, (unsigned)count0 * (unsigned)sizeof(T));
-      const __amdgpu_buffer_rsrc_t ry = make_raw_buffer(static_cast<const T *>(y0) + start, (unsigned)count0 * (unsigned)sizeof(T));
-      const __amdgpu_buffer_rsrc_t rz = make_raw_buffer(static_cast<const T *>(z0) + start, (unsigned)count0 * (unsigned)sizeof(T));
-#pragma unroll
-      for (int k = 0; k < PPT; ++k) {
-        const int poff = min(tid + k * NT, count0 - 1) * (int)sizeof(T);
-        X[k] = buf_load_elem<T>(rx, poff); Y[k] = buf_load_elem<T>(ry, poff); Z[k] = buf_load_elem<T>(rz, poff);
-      }
-    }
-  }
-  // descriptor and pose by value, as ONE batch of scalar loads behind one wait (eval_fused_body)
-  const ProblemDesc pd = probs[pc.term];
-  PoseLite<T> ps;
-  int active;
-  {
-    const PoseState *psp = poses + pc.slot;
-    const T *R_ = Uni<T>::R(*psp), *t_ = Uni<T>::t(*psp);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) ps.R[i] = R_[i];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) ps.t[i] = t_[i];
-    ps.unit_q = psp->unit_q;
-    ps.full = psp;
-    active = psp->active;
-    asm volatile("" ::"s"(pd.x), "s"(pd.y), "s"(pd.z), "s"(IMG32 ? pd.dt32 : pd.dt), "s"(pd.n), "s"(pd.W), "s"(pd.H), "s"(pd.pitch),
-                 "s"(Uni<T>::fx(pd)), "s"(Uni<T>::fy(pd)), "s"(Uni<T>::cx(pd)), "s"(Uni<T>::cy(pd)),
-                 "s"(Uni<T>::loss_a(pd)), "s"(Uni<T>::loss_inv_b(pd)), "s"(Uni<T>::z_guard(pd)), "s"(Uni<T>::z_eps(pd)),
-                 "s"(pd.loss_kind), "s"(pd.variant));
-    asm volatile("" : "+s"(active), "+s"(ps.unit_q), "+s"(ps.R[0]), "+s"(ps.R[1]), "+s"(ps.R[2]), "+s"(ps.R[3]), "+s"(ps.R[4]),
-                      "+s"(ps.R[5]), "+s"(ps.R[6]), "+s"(ps.R[7]), "+s"(ps.R[8]), "+s"(ps.t[0]), "+s"(ps.t[1]), "+s"(ps.t[2]));
-  }
-  if (start >= pd.n || !active) return;
-  const int count = min(chunk, (int)(pd.n - start));
-  const GPtr<T> px = (GPtr<T>)(static_cast<const T *>(pd.x) + start);
-  const GPtr<T> py = (GPtr<T>)(static_cast<const T *>(pd.y) + start);
-  const GPtr<T> pz = (GPtr<T>)(static_cast<const T *>(pd.z) + start);
-  // coalesced point loads; lanes past the end of the chunk re-read its last point
-  if constexpr (BUF) {
-    if (!early) {
-      const __amdgpu_buffer_rsrc_t rx = make_raw_buffer((const T *)px, (unsigned)count * (unsigned)sizeof(T));
-      const __amdgpu_buffer_rsrc_t ry = make_raw_buffer((const T *)py, (unsigned)count * (unsigned)sizeof(T));
-      const __amdgpu_buffer_rsrc_t rz = make_raw_buffer((const T *)pz, (unsigned)count * (unsigned)sizeof(T));
-#pragma unroll
-      for (int k = 0; k < PPT; ++k) {
-        const int poff = min(tid + k * NT, count - 1) * (int)sizeof(T);
-        X[k] = buf_load_elem<T>(rx, poff); Y[k] = buf_load_elem<T>(ry, poff); Z[k] = buf_load_elem<T>(rz, poff);
-      }
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < PPT; ++k) {
-      const int jj = min(tid + k * NT, count - 1);
-      X[k] = px[jj]; Y[k] = py[jj]; Z[k] = pz[jj];
-    }
-  }
+  EA_ITEM_HEAD(false, NT * PPT, pc.chunk, pc.term, pc.slot, false, return);
   const double sum = fused_chunk<T, PPT, 0, NT, false, BUF, IMG32, PoseLite<T>, XCHG>(pd, ps, X, Y, Z, count, s_red, s_box, (T *)nullptr, 0,
                                                                                        tid < kAccSlots ? tid : -1);
-  if constexpr (XCHG) {  // (one lane per (wavefront, slot) holds the finished sum)
-    const int slot = xchg_store_slot(tid >> 6, tid & 63);
-    if (slot >= 0) partials[(size_t)pc.out_row * kAccSlots + slot] = sum;
-  } else {
-    if (tid < kAccSlots) partials[(size_t)pc.out_row * kAccSlots + tid] = sum;
-  }
+  store_row_sum<XCHG>(partials, pc.out_row, sum);
 }
 
 // SIDE instantiations of the LM kernels.  Problem p's PriorDesc (ea_prior.h; the table sits behind the group table) is
@@ -2564,19 +2376,9 @@ __global__ __launch_bounds__(kLmThreads) void ea_lm_iter_kernel(
   // problem 0's points go out first (their addresses came with the wave), then everything uniform in one batch
   T X[PPT], Y[PPT], Z[PPT];
   const bool early = BUF && p == 0 && n0 > 0 && start < n0;  // (uniform)
-  if constexpr (BUF) {
-    if (early) {
-      const int count0 = min(chunk, (int)(n0 - start));
-      const __amdgpu_buffer_rsrc_t rx = make_raw_buffer(static_cast<const T *>(x0) + start, (unsigned)count0 * (unsigned)sizeof(T));
-      const __amdgpu_buffer_rsrc_t ry = make_raw_buffer(static_cast<const T *>(y0) + start, (unsigned)count0 * (unsigned)sizeof(T));
-      const __amdgpu_buffer_rsrc_t rz = make_raw_buffer(static_cast<const T *>(z0) + start, (unsigned)count0 * (unsigned)sizeof(T));
-#pragma unroll
-      for (int k = 0; k < PPT; ++k) {
-        const int poff = min(tid + k * NT, count0 - 1) * (int)sizeof(T);
-        X[k] = buf_load_elem<T>(rx, poff); Y[k] = buf_load_elem<T>(ry, poff); Z[k] = buf_load_elem<T>(rz, poff);
-      }
-    }
-  }
+  if (early)
+    load_chunk_points<T, PPT, NT, true>(static_cast<const T *>(x0) + start, static_cast<const T *>(y0) + start,
+                                        static_cast<const T *>(z0) + start, min(chunk, (int)(n0 - start)), X, Y, Z);
   EA_LM_CLOCK(t_enter_);  // (diagnostic build: kernel entered)
   const ProblemDesc pd = probs[p];
   const int active = poses[p].active;
@@ -2591,33 +2393,14 @@ __global__ __launch_bounds__(kLmThreads) void ea_lm_iter_kernel(
   // The rows are fetched at once, beside the uniforms above and not behind them (as ea_lm_step_kernel does): a launch that
   // finds its problem finished has folded rows nobody reads and leaves below.
   reduce_tiles<NT, 8>(rows_in, gd.tile_begin, gd.tile_end, s_part, s_acc);
-  asm volatile("" ::"s"(pd.x), "s"(pd.y), "s"(pd.z), "s"(IMG32 ? pd.dt32 : pd.dt), "s"(pd.n), "s"(pd.W), "s"(pd.H), "s"(pd.pitch),
-               "s"(Uni<T>::fx(pd)), "s"(Uni<T>::fy(pd)), "s"(Uni<T>::cx(pd)), "s"(Uni<T>::cy(pd)),
-               "s"(Uni<T>::loss_a(pd)), "s"(Uni<T>::loss_inv_b(pd)), "s"(Uni<T>::z_guard(pd)), "s"(Uni<T>::z_eps(pd)),
-               "s"(pd.loss_kind), "s"(pd.tile_begin), "s"(active), "s"(evals_before));
+  asm volatile("" ::EA_DESC_UNIFORMS(T, IMG32, pd), "s"(pd.tile_begin), "s"(active), "s"(evals_before));
   if (!active) return;  // the solve of this problem ended in an earlier launch
   const bool evaluator = start < pd.n;
   if (!evaluator && !writer) return;
   const int count = evaluator ? min(chunk, (int)(pd.n - start)) : 0;
-  if (evaluator && !early) {  // (problems behind the first of a batch, or flat addressing: their points wait for the descriptor)
-    const T *px = static_cast<const T *>(pd.x) + start, *py = static_cast<const T *>(pd.y) + start, *pz = static_cast<const T *>(pd.z) + start;
-    if constexpr (BUF) {
-      const __amdgpu_buffer_rsrc_t rx = make_raw_buffer(px, (unsigned)count * (unsigned)sizeof(T));
-      const __amdgpu_buffer_rsrc_t ry = make_raw_buffer(py, (unsigned)count * (unsigned)sizeof(T));
-      const __amdgpu_buffer_rsrc_t rz = make_raw_buffer(pz, (unsigned)count * (unsigned)sizeof(T));
-#pragma unroll
-      for (int k = 0; k < PPT; ++k) {
-        const int poff = min(tid + k * NT, count - 1) * (int)sizeof(T);
-        X[k] = buf_load_elem<T>(rx, poff); Y[k] = buf_load_elem<T>(ry, poff); Z[k] = buf_load_elem<T>(rz, poff);
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < PPT; ++k) {
-        const int jj = min(tid + k * NT, count - 1);
-        X[k] = ((GPtr<T>)px)[jj]; Y[k] = ((GPtr<T>)py)[jj]; Z[k] = ((GPtr<T>)pz)[jj];
-      }
-    }
-  }
+  if (evaluator && !early)  // (problems behind the first of a batch, or flat addressing: their points wait for the descriptor)
+    load_chunk_points<T, PPT, NT, BUF>(static_cast<const T *>(pd.x) + start, static_cast<const T *>(pd.y) + start,
+                                       static_cast<const T *>(pd.z) + start, count, X, Y, Z);
   if (tid < kStateWords) reinterpret_cast<double *>(&s_st)[tid] = state_word;
   if ((tid & 63) < kColdWords) reinterpret_cast<double *>(&s_cold[tid >> 6])[tid & 63] = cold_word;  // (own wavefront's copy)
   if constexpr (SIDE) {
@@ -2935,14 +2718,25 @@ hipError_t launch_eval_poses_grid(const EvalLaunch &s, const ProblemDesc *probs,
 // the wave-exchange instantiations (MODE = kModeExchange) of ea_eval_poses_kernel / ea_eval_starts_kernel: fp64 in 256-lane
 // workgroups, at every shape the plain ones have
 template <typename T, int NT> constexpr bool exchange_exists() { return sizeof(T) == 8 && NT == 256; }
+// launch(MODE as a std::integral_constant, dynamic LDS bytes) with the reduction `exchange` asks for
+template <typename T, int NT, typename F> static inline hipError_t launch_plain_or_exchange(int exchange, F &&launch) {
+  if (!exchange) return launch(std::integral_constant<int, 0>{}, (size_t)kHdrBytes);
+  if constexpr (!exchange_exists<T, NT>()) return hipErrorInvalidValue;
+  else return launch(std::integral_constant<int, kModeExchange>{}, (size_t)kXchgBytes);
+}
+// what the flat launches (ea_poses_map.h) ask of a batch: plain functor, L2 path, one term per problem, whole chunks per
+// workgroup, and a row index pose * rows + row that fits
+static inline bool flat_launch_ok(const EvalLaunch &s, const PosesLaunch &p, int min_rows) {
+  if (s.variant || s.lds_bytes > 0 || s.wide || !s.terms_are_groups || s.chunk != s.nt * s.ppt) return false;
+  return p.g > 0 && p.rows >= min_rows && (int64_t)p.rows * p.g <= (int64_t)1 << 28;
+}
 
 // ea_eval_poses_kernel: g poses of a batch of `rows` partial rows per pose in one launch, `fold` (fold.n riders, 0 = none)
 // riding in front (ea_poses_map.h).  Plain functor, L2 path, one term per problem.  p.exchange asks for the wave-exchange
 // reduction (fp64 in 256-lane workgroups; refused elsewhere); the launch then takes kXchgBytes of dynamic LDS.
 hipError_t launch_eval_poses(const EvalLaunch &s, const PosesLaunch &p, const ProblemDesc *probs, const PoseState *poses,
                              double *partials, const PosesFold &fold, hipStream_t stream) {
-  if (s.variant || s.lds_bytes > 0 || s.wide || !s.terms_are_groups || s.chunk != s.nt * s.ppt) return hipErrorInvalidValue;
-  if (p.g <= 0 || p.rows <= 0 || fold.n < 0 || (int64_t)p.rows * p.g > (int64_t)1 << 28) return hipErrorInvalidValue;
+  if (!flat_launch_ok(s, p, 1) || fold.n < 0) return hipErrorInvalidValue;
   const int shape = poses_shape(s.xcd_remap != 0, p.order, p.single != 0, fold.n);
   const dim3 grid(poses_grid(p.rows, p.g, fold.n));
   return dispatch_dtype(s.dtype, [&](auto TT) { return dispatch_int<1, 2, 4>(s.ppt, [&](auto PPT) {
@@ -2952,18 +2746,11 @@ hipError_t launch_eval_poses(const EvalLaunch &s, const PosesLaunch &p, const Pr
         constexpr int P = decltype(PPT)::value, N = decltype(NT)::value;
         constexpr bool B = decltype(BUF)::value, I = decltype(IMG32)::value;
         if constexpr (!fused_exists<T, P, 0, N, false, B, I>()) return hipErrorInvalidValue;
-        else if (p.exchange) {
-          if constexpr (!exchange_exists<T, N>()) return hipErrorInvalidValue;
-          else {
-            hipLaunchKernelGGL((ea_eval_poses_kernel<T, P, kModeExchange, N, false, B, I>), grid, dim3(N), (size_t)kXchgBytes, stream,
-                               s.x0, s.y0, s.z0, s.n0, shape, p.g, p.rows, probs, poses, partials, fold);
-            return hipGetLastError();
-          }
-        } else {
-          hipLaunchKernelGGL((ea_eval_poses_kernel<T, P, 0, N, false, B, I>), grid, dim3(N), (size_t)kHdrBytes, stream, s.x0, s.y0,
-                             s.z0, s.n0, shape, p.g, p.rows, probs, poses, partials, fold);
+        else return launch_plain_or_exchange<T, N>(p.exchange, [&](auto MODE, size_t shmem) {
+          hipLaunchKernelGGL((ea_eval_poses_kernel<T, P, decltype(MODE)::value, N, false, B, I>), grid, dim3(N), shmem, stream, s.x0,
+                             s.y0, s.z0, s.n0, shape, p.g, p.rows, probs, poses, partials, fold);
           return hipGetLastError();
-        }
+        });
       }); }); });
   }); });
 }
@@ -2983,8 +2770,7 @@ template <typename T, int PPT, int NT, bool IMG32> constexpr bool cost_exists() 
 }
 hipError_t launch_cost_poses(const EvalLaunch &s, const PosesLaunch &p, const ProblemDesc *probs, const PoseState *poses,
                              void *partials, hipStream_t stream) {
-  if (s.variant || s.lds_bytes > 0 || s.wide || !s.terms_are_groups || s.chunk != s.nt * s.ppt) return hipErrorInvalidValue;
-  if (p.g <= 0 || p.rows <= 0 || (int64_t)p.rows * p.g > (int64_t)1 << 28) return hipErrorInvalidValue;
+  if (!flat_launch_ok(s, p, 1)) return hipErrorInvalidValue;
   const int shape = poses_shape(s.xcd_remap != 0, p.order, p.single != 0, 0);
   const dim3 grid(poses_grid(p.rows, p.g, 0));
   return dispatch_dtype(s.dtype, [&](auto TT) { return dispatch_int<1, 2, 4>(s.ppt, [&](auto PPT) {
@@ -3013,8 +2799,7 @@ hipError_t launch_cost_fold(const PosesFold &fold, hipStream_t stream) {
 // ea_eval_starts_kernel: ea_eval_poses_kernel's launch of p.g poses over the piece [off, off + p.g) of a live list
 hipError_t launch_eval_starts(const EvalLaunch &s, const PosesLaunch &p, const ProblemDesc *probs, const PoseState *poses,
                               double *partials, const int *live, const int *n_live, int off, hipStream_t stream) {
-  if (s.variant || s.lds_bytes > 0 || s.wide || !s.terms_are_groups || s.chunk != s.nt * s.ppt || s.nt != kLmThreads) return hipErrorInvalidValue;
-  if (p.g <= 0 || p.rows < 0 || off < 0 || (int64_t)p.rows * p.g > (int64_t)1 << 28) return hipErrorInvalidValue;
+  if (!flat_launch_ok(s, p, 0) || s.nt != kLmThreads || off < 0) return hipErrorInvalidValue;
   if (p.rows == 0) return hipSuccess;  // not a single point in the batch
   const int shape = poses_shape(s.xcd_remap != 0, p.order, p.single != 0, 0);
   const dim3 grid(poses_grid(p.rows, p.g, 0));
@@ -3024,18 +2809,11 @@ hipError_t launch_eval_starts(const EvalLaunch &s, const PosesLaunch &p, const P
       constexpr int P = decltype(PPT)::value;
       constexpr bool B = decltype(BUF)::value, I = decltype(IMG32)::value;
       if constexpr (!fused_exists<T, P, 0, kLmThreads, false, B, I>()) return hipErrorInvalidValue;
-      else if (p.exchange) {
-        if constexpr (!exchange_exists<T, kLmThreads>()) return hipErrorInvalidValue;
-        else {
-          hipLaunchKernelGGL((ea_eval_starts_kernel<T, P, kModeExchange, kLmThreads, false, B, I>), grid, dim3(kLmThreads), (size_t)kXchgBytes,
-                             stream, s.x0, s.y0, s.z0, s.n0, shape, p.g, p.rows, probs, poses, partials, live, n_live, off);
-          return hipGetLastError();
-        }
-      } else {
-        hipLaunchKernelGGL((ea_eval_starts_kernel<T, P, 0, kLmThreads, false, B, I>), grid, dim3(kLmThreads), (size_t)kHdrBytes, stream,
-                           s.x0, s.y0, s.z0, s.n0, shape, p.g, p.rows, probs, poses, partials, live, n_live, off);
+      else return launch_plain_or_exchange<T, kLmThreads>(p.exchange, [&](auto MODE, size_t shmem) {
+        hipLaunchKernelGGL((ea_eval_starts_kernel<T, P, decltype(MODE)::value, kLmThreads, false, B, I>), grid, dim3(kLmThreads), shmem,
+                           stream, s.x0, s.y0, s.z0, s.n0, shape, p.g, p.rows, probs, poses, partials, live, n_live, off);
         return hipGetLastError();
-      }
+      });
     }); });
   }); });
 }

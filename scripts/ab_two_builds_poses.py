@@ -1,7 +1,10 @@
 """Two builds of the library on one box, alternating processes: kernel time per evaluation of the pose-batched launches (C5 fp32,
 C2 fp32, C2 fp64).  usage: python scripts/ab_two_builds_poses.py libA.so libB.so [--bits]
 --bits: instead of timing, the results of 20 poses on C2 fp64 from both builds, (a) at threads = 1024, where both builds fold
-with 1024-thread workgroups in the same order -- equal partial rows then mean equal bits -- and (b) at the default shape."""
+with 1024-thread workgroups in the same order -- equal partial rows then mean equal bits -- and (b) at the default shape;
+then the same poses through the other kernels that share the head of a work item, each at buffer_loads 1 and 0: cost_poses,
+one solve_starts from the first four (poses, iteration counts, it_cost), and ea_solve from the first with fused_iterations
+on and off.  Every array must be array_equal between the builds: exit status 1 otherwise."""
 import sys, os, json, subprocess
 CHILD = r'''
 import sys, numpy as np
@@ -33,6 +36,9 @@ capi.LIB_PATH = sys.argv[1]
 import bench
 cfg = synth.config_c2_twin(seed=2, n_points=50000)
 out = {}
+def pad(v):   # a trace, NaN-padded to 11 rows
+    a = np.full(11, np.nan); v = np.asarray(v, dtype=np.float64)[:11]; a[:len(v)] = v
+    return a
 for dtype, tag in ((capi.EA_F64, "f64"), (capi.EA_F32, "f32")):
     P = capi.Problem(*cfg["K"], dtype=dtype); P.set_points(cfg["xyz"]); P.set_dt_grid(cfg["grid"]); P.set_loss(capi.LOSS_CAUCHY, 1.0)
     B = capi.Batch([P])
@@ -43,6 +49,21 @@ for dtype, tag in ((capi.EA_F64, "f64"), (capi.EA_F32, "f32")):
             B.set_tuning("poses_per_launch", g)
             r = B.eval_poses(Q, T)
             np.savez(sys.argv[2] + "_%s_%d_%d.npz" % (tag, nt, g), **r)
+    B.set_tuning("poses_per_launch", 0)
+    for buf in (1, 0):
+        B.set_tuning("buffer_loads", buf)
+        r = {"eval_" + k: v for k, v in B.eval_poses(Q, T).items()}
+        r.update({"cost_" + k: v for k, v in B.cost_poses(Q, T).items()})
+        q, t, s, best = B.solve_starts(Q[:4], T[:4], max_num_iterations=10)
+        r.update(starts_q=q, starts_t=t, starts_best=best, starts_iterations=np.array([[x["num_iterations"] for x in row] for row in s]),
+                 starts_it_cost=np.array([[pad(x["it_cost"]) for x in row] for row in s]))
+        for fused in (-1, 0):
+            B.set_tuning("fused_iterations", fused)
+            q, t, s = B.solve(Q[0], T[0], max_num_iterations=10)
+            r.update({"solve%d_q" % fused: q, "solve%d_t" % fused: t, "solve%d_fused" % fused: np.array(B.info("fused_iterations")),
+                      "solve%d_iterations" % fused: np.array([x["num_iterations"] for x in s]),
+                      "solve%d_it_cost" % fused: np.array([pad(x["it_cost"]) for x in s])})
+        np.savez(sys.argv[2] + "_%s_paths_buf%d.npz" % (tag, buf), **r)
     B.close(); P.close()
 '''
 if "--bits" in sys.argv:
@@ -50,7 +71,7 @@ if "--bits" in sys.argv:
     libs = [a for a in sys.argv[1:] if a != "--bits"][:2]
     tmp = tempfile.mkdtemp()
     for i, l in enumerate(libs):
-        o = subprocess.run(["timeout", "-k", "10", "120", sys.executable, '-c', BITS, os.path.abspath(l), os.path.join(tmp, "r%d" % i)], capture_output=True, text=True)
+        o = subprocess.run(["timeout", "-k", "10", "300", sys.executable, '-c', BITS, os.path.abspath(l), os.path.join(tmp, "r%d" % i)], capture_output=True, text=True)
         if o.returncode != 0:
             print(l, 'FAILED', o.returncode, o.stderr[-1500:]); sys.exit(1)
     for tag in ("f64", "f32"):
@@ -59,14 +80,23 @@ if "--bits" in sys.argv:
                 a, b = (np.load(os.path.join(tmp, "r%d_%s_%d_%d.npz" % (i, tag, nt, g))) for i in (0, 1))
                 print(tag, "threads", nt, "poses_per_launch", g, {f: ("equal bits" if np.array_equal(a[f], b[f]) else
                       "max |d| / max |.| = %.3g" % (np.abs(a[f] - b[f]).max() / np.abs(a[f]).max())) for f in ("cost", "JtJ", "Jtr", "n_invalid")})
-    sys.exit(0)
+    differ = []
+    for tag in ("f64", "f32"):
+        for buf in (1, 0):
+            a, b = (np.load(os.path.join(tmp, "r%d_%s_paths_buf%d.npz" % (i, tag, buf))) for i in (0, 1))
+            bad = [f for f in a.files if not np.array_equal(a[f], b[f], equal_nan=True)]
+            differ += bad
+            print(tag, "buffer_loads", buf, "%d arrays (eval_poses, cost_poses, solve_starts K = 4, ea_solve fused %s / %s):" %
+                  (len(a.files), a["solve-1_fused"], a["solve0_fused"]), "DIFFER: %s" % bad if bad else "all equal bits")
+    sys.exit(1 if differ else 0)
 libs = sys.argv[1:3]
 res = {l: [] for l in libs}
 for r in range(3):
     for l in libs:
-        o = subprocess.run([sys.executable, '-c', CHILD, os.path.abspath(l)], capture_output=True, text=True)
+        o = subprocess.run(["timeout", "-k", "10", "300", sys.executable, '-c', CHILD, os.path.abspath(l)], capture_output=True, text=True)
         if o.returncode != 0:
             print(l, 'FAILED', o.stderr[-1500:]); sys.exit(1)
         res[l].append(json.loads(o.stdout.strip().splitlines()[-1]))
-for l in libs:
-    print(os.path.basename(l), {k: round(sorted(x[k] for x in res[l])[1], 4) for k in res[l][0]})
+for l in libs:   # median of the three alternating runs, then (min, max)
+    print(os.path.basename(l), {k: round(sorted(x[k] for x in res[l])[1], 4) for k in res[l][0]},
+          "min/max", {k: (round(min(x[k] for x in res[l]), 4), round(max(x[k] for x in res[l]), 4)) for k in res[l][0]})

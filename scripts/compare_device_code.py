@@ -5,6 +5,10 @@ kernels: nothing needs a GPU.)
   compare_device_code.py list  TREE OUTDIR     # device listings of TREE's kernel sources into OUTDIR (build.FLAGS of TREE)
   compare_device_code.py diff  DIR_A DIR_B     # compare two such directories; exit status 1 if a kernel of A is missing from B
                                                # or differs there (kernels only B has are listed, not counted)
+  compare_device_code.py stats DIR_A DIR_B     # a markdown table of the kernels whose bodies differ: instructions, vector
+                                               # instructions, registers, private segment, LDS, occupancy (A -> B), and the
+                                               # kernels that break a bound (exit status 1): private segment 0, LDS and occupancy
+                                               # equal, vector instructions <= A + 4, instructions <= A + 2 %
 
 A listing is `hipcc <build.FLAGS minus -fPIC> <the source's extra flags> -S --cuda-device-only`, with the per-compilation
 `__hip_cuid_<hex>` replaced by a constant.  Whole files are compared first.  Where they differ the kernels are compared one
@@ -96,8 +100,62 @@ def diff(dir_a, dir_b):
     return 1 if bad else 0
 
 
+_INSN = re.compile(r"^\t(v_|s_|ds_|global_|buffer_|flat_|scratch_)\w+", re.M)
+_FIELDS = (("VGPR", r"\.amdhsa_next_free_vgpr (\d+)"), ("SGPR", r"\.amdhsa_next_free_sgpr (\d+)"),
+           ("private", r"\.amdhsa_private_segment_fixed_size (\d+)"), ("LDS", r"\.amdhsa_group_segment_fixed_size (\d+)"),
+           ("occupancy", r"; Occupancy: (\d+)"))  # (the compiler's comment block behind the kernel)
+_OCC = re.compile(r"^\s*\.amdhsa_kernel (\S+)$.*?^; Occupancy: (\d+)$", re.M | re.S)
+
+
+def kernel_stats(body):
+    insns = [m.group(0) for m in _INSN.finditer(body)]
+    st = {"insns": len(insns), "vector": sum(1 for i in insns if i.startswith("\tv_"))}
+    for key, pat in _FIELDS[:-1]:
+        st[key] = int(re.search(pat, body).group(1))
+    return st
+
+
+def short_name(name):
+    """`_ZN2ea20ea_eval_fused_kernelIdLi1E...EEEvPKv...` -> `ea_eval_fused_kernel<d,1,0,256,1,0,0>`"""
+    m = re.match(r"_ZN2ea\d+(\w+?)I((?:[df]|Li\d+E|Lb[01]E)+)EEv", name)
+    if not m:
+        return name
+    return "%s<%s>" % (m.group(1), ",".join(a.strip("LibE") or a for a in re.findall(r"[df]|Li\d+E|Lb[01]E", m.group(2))))
+
+
+def stats(dir_a, dir_b):
+    bad = 0
+    keys = ["insns", "vector"] + [k for k, _ in _FIELDS]
+    for src in SOURCES:
+        name = os.path.basename(src) + ".s"
+        with open(os.path.join(dir_a, name)) as f:
+            ta = f.read()
+        with open(os.path.join(dir_b, name)) as f:
+            tb = f.read()
+        ka, kb, oa, ob = kernels(ta), kernels(tb), dict(_OCC.findall(ta)), dict(_OCC.findall(tb))
+        differ = sorted(n for n in set(ka) & set(kb) if ka[n] != kb[n])
+        print("\n`%s`: %d kernels, %d bodies identical after label masking, %d differ\n" % (os.path.basename(src), len(ka), len(ka) - len(differ), len(differ)))
+        if not differ:
+            continue
+        print("| kernel | " + " | ".join(keys) + " | |")
+        print("|---|" + "---|" * (len(keys) + 1))
+        for n in differ:
+            a, b = kernel_stats(ka[n]), kernel_stats(kb[n])
+            a["occupancy"], b["occupancy"] = int(oa[n]), int(ob[n])
+            broken = [k for k in ("LDS", "occupancy") if a[k] != b[k]]
+            broken += ["private"] if b["private"] else []
+            broken += ["vector"] if b["vector"] > a["vector"] + 4 else []
+            broken += ["insns"] if b["insns"] > a["insns"] * 1.02 else []
+            bad += 1 if broken else 0
+            print("| `%s` | " % short_name(n) + " | ".join(str(a[k]) if a[k] == b[k] else "%d -> %d" % (a[k], b[k]) for k in keys) +
+                  " | %s |" % ("BREAKS " + ", ".join(broken) if broken else ""))
+    return 1 if bad else 0
+
+
 if __name__ == "__main__":
-    if len(sys.argv) == 4 and sys.argv[1] == "list":
+    if len(sys.argv) == 4 and sys.argv[1] == "stats":
+        sys.exit(stats(sys.argv[2], sys.argv[3]))
+    elif len(sys.argv) == 4 and sys.argv[1] == "list":
         make_listings(sys.argv[2], sys.argv[3])
     elif len(sys.argv) == 4 and sys.argv[1] == "diff":
         sys.exit(diff(sys.argv[2], sys.argv[3]))
