@@ -45,6 +45,7 @@ EXPORTED = [
     "ea_default_covariance_options", "ea_problem_covariance", "ea_batch_covariance", "ea_tracker_set_covariance",
     "ea_tracker_last_covariance", "ea_problem_set_normal_prior", "ea_tracker_set_motion_prior",
     "ea_problem_set_constant_parameters", "ea_problem_get_constant_parameters",
+    "ea_problem_set_weights", "ea_problem_set_weights_device", "ea_problem_get_weights", "ea_problem_set_depth_weighting",
 ]
 
 # measurement hooks (edge_alignment_amd/csrc/ea_hip_dev.h): bound by bench.py, the A/B scripts and the tests that pin the
@@ -140,6 +141,10 @@ def load():
     L.ea_problem_set_points.argtypes = [vp, dp, C.c_int64, C.c_int64]
     L.ea_problem_set_points_device.argtypes = [vp, vp, vp, vp, C.c_int64]
     L.ea_problem_set_point_order.argtypes = [vp, C.c_int]
+    L.ea_problem_set_weights.argtypes = [vp, dp, C.c_int64]
+    L.ea_problem_set_weights_device.argtypes = [vp, vp, C.c_int64]
+    L.ea_problem_get_weights.argtypes = [vp, dp, C.c_int64, i64p]
+    L.ea_problem_set_depth_weighting.argtypes = [vp, C.c_double, C.c_int]
     L.ea_problem_get_point_order.argtypes = [vp, C.POINTER(C.c_int)]
     L.ea_problem_set_dt.argtypes = [vp, dp, C.c_int, C.c_int]
     L.ea_problem_set_dt_image_device.argtypes = [vp, vp, C.c_int, C.c_int]
@@ -362,6 +367,28 @@ class Problem:
 
     def set_points_device(self, x_ptr, y_ptr, z_ptr, n):
         _check(load().ea_problem_set_points_device(self._h, x_ptr, y_ptr, z_ptr, n))
+
+    def set_weights(self, w):
+        """per-point weights (ceres::ScaledLoss per block), one per point in the order of set_points; None clears them"""
+        if w is None:
+            _check(load().ea_problem_set_weights(self._h, None, 0))
+            return
+        w = _f64(w).reshape(-1)
+        _check(load().ea_problem_set_weights(self._h, _dp(w), w.shape[0]))
+
+    def set_weights_device(self, w_ptr, n):
+        _check(load().ea_problem_set_weights_device(self._h, w_ptr, n))
+
+    def get_weights(self):
+        """the stored weights (rounded to the problem dtype) in the caller's order, or None when no weights are set"""
+        w = np.zeros(self.num_points)
+        cnt = C.c_int64()
+        _check(load().ea_problem_get_weights(self._h, _dp(w), w.shape[0], C.byref(cnt)))
+        return w if cnt.value == w.shape[0] and cnt.value > 0 else None
+
+    def set_depth_weighting(self, z_ref, power):
+        """the reference-frame producers write w = min(1, (z_ref / z)^power) behind their points; power 0 = off"""
+        _check(load().ea_problem_set_depth_weighting(self._h, float(z_ref), int(power)))
 
     def set_dt_grid(self, grid):
         """grid: the Grid2D view (rows = u extent, cols = v extent), row-major float64."""
@@ -737,6 +764,11 @@ class Tracker:
     def set_motion_prior(self, sigma_rot, sigma_trans):
         """NormalPriors centred on each solve's start pose, A = I / sigma (ea_tracker_set_motion_prior); 0 = block off"""
         _check(load().ea_tracker_set_motion_prior(self._h, float(sigma_rot), float(sigma_trans)))
+
+    def set_depth_weighting(self, z_ref, power):
+        """ea_problem_set_depth_weighting on the tracker's problem: every reference step writes w = min(1, (z_ref / z)^power)"""
+        L = load()
+        _check(L.ea_problem_set_depth_weighting(L.ea_tracker_problem(self._h), float(z_ref), int(power)))
 
     def set_constant_parameters(self, mask):
         """the mask of ea_problem_set_constant_parameters on the tracker's problem: it holds for every push"""

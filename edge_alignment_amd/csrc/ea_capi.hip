@@ -269,6 +269,7 @@ struct ea_batch {
   hipEvent_t desc_done = nullptr;
   int nterms = 0, terms_cap = 0;
   int any_variant = 0, terms_are_groups = 1;
+  int weighted_terms = 0;  // terms of the current build with per-point weights (info key "weighted")
   int ntiles = 0, tiles_cap = 0;  // rows of the partial-sum array (one per workgroup with work)
   int chunk = 256, max_chunks = 0; // points per workgroup; largest per-problem workgroup count
   PoseState *d_poses = nullptr;
@@ -511,25 +512,33 @@ static void free_points(ea_problem *p) {
   p->n = 0;
   p->order.clear();
   p->order_tile_used = 0;
+  p->weighted = p->weights_from_depth = false;  // (the weights belong to the point set)
+  p->w_off = 0;
 }
 
 // Room for n points in arrays the problem owns: the previous allocation when it is large enough (and not more than
-// four times too large), a fresh one otherwise.  Leaves the problem without points (n = 0) either way.
+// four times too large), a fresh one otherwise.  Leaves the problem without points (n = 0) and without weights either way.
+// The block behind d_z has room for the weights too: [z: pts_cap bytes, rounded up to 256 | w: pts_cap bytes], so that a
+// descriptor reaches them through a 32-bit element offset from z (ProblemDesc::w_off).
 int ea::reserve_points(ea_problem *p, int64_t n) {
-  const size_t need = (size_t)n * (p->dtype == EA_F32 ? 4 : 8);
+  const size_t esz = p->dtype == EA_F32 ? 4 : 8;
+  const size_t need = (size_t)n * esz;
   if (p->own_points && p->pts_cap >= need && p->pts_cap <= 4 * need + 4096) {
     p->n = 0;
     p->order.clear();
     p->order_tile_used = 0;
+    p->weighted = p->weights_from_depth = false;
     return EA_OK;
   }
   free_points(p);
   if (n == 0) return EA_OK;
   p->own_points = true;  // (before the allocations: a failure half-way leaves what was allocated to free_points)
+  const size_t z_bytes = (need + 255) & ~(size_t)255;
   HIPCHK(cached_malloc(&p->d_x, need, p->device));
   HIPCHK(cached_malloc(&p->d_y, need, p->device));
-  HIPCHK(cached_malloc(&p->d_z, need, p->device));
+  HIPCHK(cached_malloc(&p->d_z, z_bytes + need, p->device));
   p->pts_cap = need;
+  p->w_off = (int64_t)(z_bytes / esz);
   return EA_OK;
 }
 
@@ -765,6 +774,112 @@ extern "C" int ea_problem_set_points_device(ea_problem *p, const void *x, const 
   p->own_points = false;
   p->n = n;
   p->version++;
+  return EA_OK;
+}
+
+// ---- per-point weights (ceres::ScaledLoss per residual block) --------------------------------------------------------------
+
+// borrowed point arrays (ea_problem_set_points_device) into arrays the problem owns: the weights live behind z.  Copied by a
+// kernel: the caller's arrays may belong to another HIP runtime in the process (check_device_pointer), whose pointers this
+// runtime's hipMemcpy does not know.
+static int own_borrowed_points(ea_problem *p) {
+  if (p->own_points || p->n == 0) return EA_OK;
+  const void *x = p->d_x, *y = p->d_y, *z = p->d_z;
+  const int64_t n = p->n;
+  p->d_x = p->d_y = p->d_z = nullptr;
+  int rc = reserve_points(p, n);
+  if (rc == EA_OK) {
+    const int same = p->dtype == EA_F64 ? 1 : 0;  // (source elements are the problem dtype)
+    hipError_t e = launch_store_weights(p->dtype, same, x, nullptr, n, p->d_x, nullptr);
+    if (e == hipSuccess) e = launch_store_weights(p->dtype, same, y, nullptr, n, p->d_y, nullptr);
+    if (e == hipSuccess) e = launch_store_weights(p->dtype, same, z, nullptr, n, p->d_z, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) rc = fail(EA_ERR_HIP, std::string("copying borrowed points: ") + hipGetErrorString(e));
+  }
+  if (rc != EA_OK) {  // back to the caller's arrays
+    free_points(p);
+    p->d_x = const_cast<void *>(x); p->d_y = const_cast<void *>(y); p->d_z = const_cast<void *>(z);
+    p->n = n;
+    return rc;
+  }
+  p->n = n;
+  p->version++;
+  return EA_OK;
+}
+
+// n weights in the caller's order at `src` (host doubles, or device values of the problem dtype) into the problem's storage:
+// converted and permuted into the points' order by ea_store_weights_kernel
+static int store_weights(ea_problem *p, const void *src, bool host_doubles) {
+  const int64_t n = p->n;
+  DevBuf raw, ord;
+  if (host_doubles) {
+    HIPCHK(cached_malloc(&raw.p, (size_t)n * sizeof(double), p->device));
+    HIPCHK(hipMemcpy(raw.p, src, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    src = raw.p;
+  }
+  if (!p->order.empty()) {
+    HIPCHK(cached_malloc(&ord.p, (size_t)n * sizeof(int32_t), p->device));
+    HIPCHK(hipMemcpy(ord.p, p->order.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
+  // (the staging above can fail without having touched the problem; only now do borrowed points become owned ones)
+  int rc = own_borrowed_points(p);
+  if (rc != EA_OK) return rc;
+  HIPCHK(launch_store_weights(p->dtype, host_doubles || p->dtype == EA_F64, src, ord.as<int32_t>(), n, weights_ptr(p), nullptr));
+  HIPCHK(hipDeviceSynchronize());
+  p->weights_from_depth = false;
+  if (!p->weighted) { p->weighted = true; p->version++; }  // (new values alone need no rebuild of a batch)
+  return EA_OK;
+}
+
+extern "C" int ea_problem_set_weights(ea_problem *p, const double *w, int64_t n) {
+  if (!p) return fail(EA_ERR_INVALID_ARG, "NULL problem");
+  if (!w) {
+    if (p->weighted) { p->weighted = p->weights_from_depth = false; p->version++; }
+    return EA_OK;
+  }
+  if (n != p->n) return fail(EA_ERR_INVALID_ARG, "n must equal the problem's number of points (ea_problem_num_points)");
+  const double wmax = p->dtype == EA_F32 ? (double)FLT_MAX : DBL_MAX;
+  for (int64_t i = 0; i < n; ++i)
+    if (!(w[i] >= 0.0) || !(w[i] <= wmax)) return fail(EA_ERR_INVALID_ARG, "weights must be finite and >= 0");
+  if (n == 0) return EA_OK;
+  HIPCHK(hipSetDevice(p->device));
+  return store_weights(p, w, true);
+}
+
+extern "C" int ea_problem_set_weights_device(ea_problem *p, const void *w, int64_t n) {
+  if (!p) return fail(EA_ERR_INVALID_ARG, "NULL problem");
+  if (!w) return ea_problem_set_weights(p, nullptr, 0);
+  if (n != p->n) return fail(EA_ERR_INVALID_ARG, "n must equal the problem's number of points (ea_problem_num_points)");
+  if (n == 0) return EA_OK;
+  HIPCHK(hipSetDevice(p->device));
+  return store_weights(p, w, false);
+}
+
+extern "C" int ea_problem_get_weights(ea_problem *p, double *w, int64_t capacity, int64_t *count) {
+  if (!p || !count) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  *count = 0;
+  if (!p->weighted || p->n == 0) return EA_OK;
+  if (!w) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (capacity < p->n) return fail(EA_ERR_INVALID_ARG, "capacity smaller than the number of points");
+  HIPCHK(hipSetDevice(p->device));
+  const size_t n = (size_t)p->n, esz = p->dtype == EA_F32 ? 4 : 8;
+  std::vector<unsigned char> buf(n * esz);
+  HIPCHK(hipMemcpy(buf.data(), weights_ptr(p), n * esz, hipMemcpyDeviceToHost));
+  const int32_t *ord = p->order.empty() ? nullptr : p->order.data();
+  for (size_t i = 0; i < n; ++i)
+    w[ord ? (size_t)ord[i] : i] = p->dtype == EA_F32 ? (double)reinterpret_cast<float *>(buf.data())[i]
+                                                     : reinterpret_cast<double *>(buf.data())[i];
+  *count = p->n;
+  return EA_OK;
+}
+
+extern "C" int ea_problem_set_depth_weighting(ea_problem *p, double z_ref, int power) {
+  if (!p) return fail(EA_ERR_INVALID_ARG, "NULL problem");
+  if (power < 0 || power > 8) return fail(EA_ERR_INVALID_ARG, "power must be 0 (off) or 1..8");
+  if (!(z_ref > 0.0) || !(z_ref <= DBL_MAX)) return fail(EA_ERR_INVALID_ARG, "z_ref must be finite and > 0");
+  p->dw_z_ref = z_ref;
+  p->dw_power = power;
+  if (power == 0 && p->weighted && p->weights_from_depth) { p->weighted = p->weights_from_depth = false; p->version++; }
   return EA_OK;
 }
 
@@ -1020,7 +1135,8 @@ static void fill_desc(const ea_problem *p, ProblemDesc &d) {
   d.loss_inv_b = 1.0 / (d.loss_a * d.loss_a); d.loss_inv_bf = (float)d.loss_inv_b;
   d.loss_af = (float)d.loss_a; d.z_guardf = (float)d.z_guard; d.z_epsf = (float)d.z_eps;
   d.loss_kind = p->loss_kind; d.rot_transposed = p->rot_transposed;
-  d.variant = p->variant;
+  d.variant = term_variant(p);
+  d.w_off = p->weighted ? (int32_t)p->w_off : 0;
   for (int i = 0; i < 5; ++i) { d.dist[i] = p->dist[i]; d.distf[i] = (float)p->dist[i]; }
   for (int r = 0; r < 3; ++r) {
     for (int c = 0; c < 3; ++c) {
@@ -1060,7 +1176,7 @@ static int batch_build(ea_batch *b) {
   std::vector<const ea_problem *> terms;
   std::vector<int> term_group;
   int64_t total = 0, max_n = 0;
-  int any_variant = 0;
+  int any_variant = 0, weighted_terms = 0;
   for (size_t i = 0; i < b->probs.size(); ++i) {
     std::vector<const ea_problem *> fam;
     fam.push_back(b->probs[i]);
@@ -1072,13 +1188,15 @@ static int batch_build(ea_batch *b) {
       if (p->rot_transposed != b->probs[i]->rot_transposed) return fail(EA_ERR_INVALID_ARG, "terms of one problem must agree on rot_transposed");
       total += p->n;
       max_n = std::max<int64_t>(max_n, p->n);
-      any_variant |= p->variant;
+      any_variant |= term_variant(p);
+      weighted_terms += p->weighted ? 1 : 0;
       terms.push_back(p);
       term_group.push_back((int)i);
     }
   }
   any_variant |= b->t_variant;  // a part of a larger batch runs the kernel form the whole batch runs
   b->any_variant = any_variant;
+  b->weighted_terms = weighted_terms;
   b->terms_are_groups = terms.size() == b->probs.size() ? 1 : 0;
   // Launch shape, measured on MI355X (profiles/r01_sweep*.txt, r02_single_shape_sweep.txt, r02_batch_shape_sweep.txt): what
   // counts is the (evaluate, fold) step and the LM iteration, i.e. the kernel AND the number of partial rows behind it.
@@ -1254,7 +1372,7 @@ static void host_pose_state(const ea_problem *p, const double *q, const double *
 // what the batch's build fixed about its evaluation launches; kposes: in the shape of the pose-batched evaluation (kposes_shape)
 static EvalLaunch eval_launch(const ea_batch *b, bool kposes = false) {
   EvalLaunch s;
-  s.dtype = b->dtype; s.variant = b->any_variant;
+  s.dtype = b->dtype; s.variant = b->any_variant; s.weighted = b->weighted_terms > 0 ? 1 : 0;
   s.ppt = kposes ? b->kp_ppt : b->ppt; s.nt = kposes ? b->kp_nt : b->nt;
   s.chunk = kposes ? b->kp_chunk : b->chunk; s.max_chunks = kposes ? b->kp_max_chunks : b->max_chunks;
   s.xcd_remap = b->xcd_remap; s.lds_bytes = b->lds_bytes; s.wide = b->wide; s.terms_are_groups = b->terms_are_groups;
@@ -2676,6 +2794,7 @@ extern "C" int ea_batch_get_info(const ea_batch *b, const char *key, int64_t *va
   else if (k == "dt_f32") *value = b->img32;
   else if (k == "num_points") { int64_t s = 0; for (auto *p : b->probs) s += p->n; *value = s; }
   else if (k == "num_rows") *value = b->total_rows;
+  else if (k == "weighted") *value = b->weighted_terms;  // terms with per-point weights (any: the variant kernels run)
   else if (k == "poses_per_launch") *value = b->kp_G;  // G of the last ea_batch_set_poses (0: none resident)
   else if (k == "poses_points_per_thread") *value = b->kp_ppt;   // launch shape of the pose-batched evaluation
   else if (k == "poses_threads") *value = b->kp_nt;
@@ -2822,12 +2941,12 @@ static int batch_covariance(ea_batch *b, const double *q, const double *t, const
     HIPCHK(cached_host_malloc(reinterpret_cast<void **>(&b->h_cov), (size_t)count * sizeof(ea_covariance), hipHostMallocMapped, b->device));
     HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&b->dv_cov), b->h_cov, 0));
   }
-  // raw rows: the same descriptors with the loss forced to trivial (the problems keep their loss, versions and resident poses)
+  // raw rows: the same descriptors with the loss forced to trivial and the weights dropped (the problems keep their loss, versions and resident poses)
   const ProblemDesc *probs = b->d_probs;
   if (!o->apply_loss_function) {
     const ProblemDesc *hd = reinterpret_cast<const ProblemDesc *>(b->h_desc);  // (batch_build's staging block)
     bool forced = false;
-    for (int j = 0; j < b->nterms; ++j) forced = forced || hd[j].loss_kind != EA_LOSS_TRIVIAL;
+    for (int j = 0; j < b->nterms; ++j) forced = forced || hd[j].loss_kind != EA_LOSS_TRIVIAL || (hd[j].variant & 4);
     if (forced) {
       if (b->cdesc_cap < b->nterms) {
         HIPCHK(hipStreamSynchronize(b->stream));
@@ -2838,7 +2957,8 @@ static int batch_covariance(ea_batch *b, const double *q, const double *t, const
         b->cdesc_cap = b->nterms;
       }
       ProblemDesc *cd = reinterpret_cast<ProblemDesc *>(b->h_cdesc);
-      for (int j = 0; j < b->nterms; ++j) { cd[j] = hd[j]; cd[j].loss_kind = EA_LOSS_TRIVIAL; }
+      // (the per-point weights are part of the loss -- ceres::ScaledLoss -- and go with it: bit 2 cleared, nothing loaded)
+      for (int j = 0; j < b->nterms; ++j) { cd[j] = hd[j]; cd[j].loss_kind = EA_LOSS_TRIVIAL; cd[j].variant &= ~4; cd[j].w_off = 0; }
       // (the previous call out of this staging block is complete: every call returns on its results)
       HIPCHK(hipMemcpyAsync(b->d_cprobs, cd, (size_t)b->nterms * sizeof(ProblemDesc), hipMemcpyHostToDevice, b->stream));
       probs = b->d_cprobs;

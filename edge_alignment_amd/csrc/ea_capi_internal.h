@@ -46,6 +46,15 @@ struct ea_problem {
   bool dt32_exact = false;
   size_t pts_cap = 0;  // bytes allocated behind each of d_x, d_y, d_z when own_points (hipFree / hipMalloc per frame
                        // cost more than the whole pre-processing of a 640x480 frame)
+  // Per-point weights (ceres::ScaledLoss per residual block; ea_problem_set_weights*, or written by the reference-frame
+  // producers under ea_problem_set_depth_weighting).  They belong to the point set: stored in the points' order and dtype
+  // BEHIND z in z's own allocation, w_off elements from d_z (ProblemDesc::w_off: the descriptor has four spare bytes, not
+  // eight), which is why only points the problem owns can carry weights -- borrowed arrays are copied first.  `weighted`
+  // makes the term a variant (bit 2) in every batch that holds it.
+  bool weighted = false, weights_from_depth = false;
+  int64_t w_off = 0;
+  double dw_z_ref = 1.0;  // ea_problem_set_depth_weighting: w = min(1, (z_ref / z)^power), power 0 = off
+  int dw_power = 0;
   int W = 0, H = 0, pitch = 0;
   uint64_t version = 1;  // bumped by every setter; batches rebuild their descriptors lazily
   ea_batch *self = nullptr;
@@ -89,6 +98,11 @@ struct DevBuf {
 
 // room for n points in arrays the problem owns; leaves the problem without points (n = 0)
 int reserve_points(ea_problem *p, int64_t n);
+inline void *weights_ptr(const ea_problem *p) {
+  return static_cast<unsigned char *>(p->d_z) + (size_t)p->w_off * (p->dtype == EA_F32 ? 4 : 8);
+}
+// bits of ProblemDesc::variant a problem sets as a term
+inline int term_variant(const ea_problem *p) { return p->variant | (p->weighted ? 4 : 0); }
 // the problem's padded W x H image (and its float32 mirror for fp64 problems), reusing an allocation that fits
 int alloc_dt(ea_problem *p, int W, int H);
 int check_cov_options(const ea_covariance_options *o);

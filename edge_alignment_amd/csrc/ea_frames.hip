@@ -80,9 +80,14 @@ static int ref_points_finish(ea_problem *p, const RefPointsJob &job, int height,
       HIPCHK(launch_edge_scatter(p->dtype, job.d_edges, static_cast<const uint16_t *>(job.d_depth), height, width, job.threshold,
                                  job.d_counts, p->cam.fx, p->cam.fy, p->cam.cx, p->cam.cy, z_scaling, p->d_x, p->d_y, p->d_z, total,
                                  nullptr));
+    // depth weighting (ea_problem_set_depth_weighting): the weights out of the z the scatter has just stored, behind it on
+    // the same stream
+    if (p->dw_power > 0)
+      HIPCHK(launch_depth_weights(p->dtype, p->d_z, total, p->dw_z_ref, p->dw_power, weights_ptr(p), nullptr));
     HIPCHK(hipDeviceSynchronize());
   }
   p->n = total;
+  p->weighted = p->weights_from_depth = total > 0 && p->dw_power > 0;  // (reserve_points dropped the previous frame's)
   return EA_OK;
 }
 

@@ -879,6 +879,11 @@ __device__ __forceinline__ double wave_exchange_reduce_f64(const double (&v)[32]
 // problem p, chunk = NT*PPT: every lane takes PPT points (strided by NT so loads coalesce), one
 // wavefront butterfly per wave and one cross-wave fold per workgroup -> one partial row.
 
+// the weight of stored point i of a weighted term (ProblemDesc::w_off), NULL for a term without weights
+template <typename T> __device__ __forceinline__ const T *desc_weights(const ProblemDesc &pd, long long i) {
+  return (pd.variant & 4) ? static_cast<const T *>(pd.z) + pd.w_off + i : nullptr;
+}
+
 constexpr int kMaxWaves = 16;
 // MODE of ea_eval_poses_kernel / ea_eval_starts_kernel only: MODE 0's per-point code with the wave-exchange reduction (fp64, 256
 // lanes); the dynamic LDS of such a launch is the exchange buffer (kXchgBytes)
@@ -895,7 +900,8 @@ constexpr int kHdrBytes = kRedBytes + kMaxWaves * 16;  // + bbox words, keeps th
 template <typename T, int PPT, int MODE, int NT, bool VAR, bool BUF, bool IMG32, typename PS, bool XCHG = false>
 __device__ __forceinline__ double fused_chunk(const ProblemDesc &pd, const PS &ps, const T (&X)[PPT],
                                               const T (&Y)[PPT], const T (&Z)[PPT], int count, double *s_red,
-                                              int *s_box, T *s_tile, int lds_texels, int my_slot) {
+                                              int *s_box, T *s_tile, int lds_texels, int my_slot,
+                                              const T *wts = nullptr) {
   // MODE 0: stencil rows from L2.  1: DT footprint staged in LDS.  2: as 0, and an fp32 kernel widens a lane's sums to
   // fp64 before the wavefront butterfly ("wide_accumulate": everything above a lane's <= PPT products is fp64).
   constexpr bool USE_LDS = MODE == 1;
@@ -916,6 +922,21 @@ __device__ __forceinline__ double fused_chunk(const ProblemDesc &pd, const PS &p
 
   T acc[28];
   int n_bad = 0;
+  // VAR: the per-point weights of a weighted term (ProblemDesc::variant bit 2; `wts` = the chunk's first weight, NULL for
+  // every other term: one wave-uniform branch, nothing loaded behind it), coalesced like the points.  ceres::ScaledLoss(rho, a)
+  // is a rho, a rho': the weight multiplies the IRLS pair behind loss_eval; lanes past the end and failed functors get
+  // (0, 0) anyway.  Only the weighted kernels (ea_eval_fused_w_kernel ...) hand a pointer in: everywhere else `wts` is the
+  // constant NULL and this folds away.
+  T WT[PPT];
+  if constexpr (VAR) {
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) WT[k] = T(1);
+    if (wts) {
+      const GPtr<T> gw = (GPtr<T>)wts;
+#pragma unroll
+      for (int k = 0; k < PPT; ++k) WT[k] = gw[min(tid + k * NT, count - 1)];
+    }
+  }
   // ---- phase 1: warp + projection.  Lanes past the end of the chunk and lanes whose functor fails are moved
   // to a harmless sample; both get weight 0 below, so the arithmetic needs no divergent branch.
   using ProjT = typename std::conditional<VAR, ProjV<T>, Proj<T>>::type;
@@ -1010,6 +1031,7 @@ __device__ __forceinline__ double fused_chunk(const ProblemDesc &pd, const PS &p
     else jacobian_row<T>(pd, ps, pr[k], X[k], Y[k], Z[k], Fu, Fv, J);
     T rho, w;
     loss_eval<T>(loss_kind, loss_a, loss_inv_b, f * f, rho, w);
+    if constexpr (VAR) { w *= WT[k]; rho *= WT[k]; }
     w = valid[k] ? w : T(0);
     rho = valid[k] ? rho : T(0);
     const T wr = w * f;
@@ -1187,7 +1209,7 @@ __device__ __forceinline__ void store_row_sum(double *__restrict__ partials, int
 
 // NT = workgroup size (256 or 1024).  1024 = one workgroup per CU: four times fewer partial rows
 // to fold afterwards at the same points-per-lane latency.
-template <typename T, int PPT, int MODE, int NT, bool VAR, bool BUF, bool IMG32>
+template <typename T, int PPT, int MODE, int NT, bool VAR, bool BUF, bool IMG32, bool WTD = false>
 __device__ __forceinline__ void eval_fused_body(
     const void *__restrict__ x0, const void *__restrict__ y0, const void *__restrict__ z0, int n0,
     int shape, int chunks_per_xcd,
@@ -1211,8 +1233,10 @@ __device__ __forceinline__ void eval_fused_body(
   asm volatile("" ::"v"(X[0]), "v"(Y[0]), "v"(Z[0]));
 #endif
   EA_STAMP(2);  // points arrived
+  const T *wts = nullptr;
+  if constexpr (VAR && WTD) wts = desc_weights<T>(pd, start);
   const double sum = fused_chunk<T, PPT, MODE, NT, VAR, BUF, IMG32, PoseLite<T>>(pd, ps, X, Y, Z, count, s_red, s_box, s_tile, lds_texels,
-                                                           tid < kAccSlots ? tid : -1);
+                                                           tid < kAccSlots ? tid : -1, wts);
   if (tid < kAccSlots) partials[(size_t)(pd.tile_begin + c) * kAccSlots + tid] = sum;
 #ifdef EA_STAMPS
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1246,6 +1270,28 @@ __global__ __launch_bounds__(NT) void ea_eval_poses_grid_kernel(
   eval_fused_body<T, PPT, MODE, NT, VAR, BUF, IMG32>(x0, y0, z0, n0, shape, chunks_per_xcd, probs, poses, partials, lds_texels);
 }
 
+#ifdef EA_TU_VARIANT
+// The two kernels above for batches with weighted terms (ProblemDesc::variant bit 2; EvalLaunch::weighted): the same body with
+// the weights of such terms loaded and multiplied into the IRLS pair.  Kernels of their own, not a branch in the ones above: a
+// batch of distortion / second-camera terms without weights runs the code it always ran (the branch alone cost the fp64
+// two-point kernel a wave of occupancy: profiles/LOG.md).
+template <typename T, int PPT, int MODE, int NT, bool VAR, bool BUF, bool IMG32 = false>
+__global__ __launch_bounds__(NT) void ea_eval_fused_w_kernel(
+    const void *__restrict__ x0, const void *__restrict__ y0, const void *__restrict__ z0, int n0,
+    int shape, int chunks_per_xcd,
+    const ProblemDesc *__restrict__ probs, const PoseState *__restrict__ poses,
+    double *__restrict__ partials, int lds_texels) {
+  eval_fused_body<T, PPT, MODE, NT, VAR, BUF, IMG32, true>(x0, y0, z0, n0, shape, chunks_per_xcd, probs, poses, partials, lds_texels);
+}
+template <typename T, int PPT, int MODE, int NT, bool VAR, bool BUF, bool IMG32 = false>
+__global__ __launch_bounds__(NT) void ea_eval_poses_grid_w_kernel(
+    const void *__restrict__ x0, const void *__restrict__ y0, const void *__restrict__ z0, int n0,
+    int shape, int chunks_per_xcd,
+    const ProblemDesc *__restrict__ probs, const PoseState *__restrict__ poses,
+    double *__restrict__ partials, int lds_texels) {
+  eval_fused_body<T, PPT, MODE, NT, VAR, BUF, IMG32, true>(x0, y0, z0, n0, shape, chunks_per_xcd, probs, poses, partials, lds_texels);
+}
+#endif
 
 #ifndef EA_TU_VARIANT
 // ------------------------------------------------------------------------------------------------
@@ -1281,6 +1327,7 @@ __global__ __launch_bounds__(kBlockThreads) void ea_eval_points_kernel(
     if (corrected) {
       T rho, w;
       loss_eval<T>(pd.loss_kind, Uni<T>::loss_a(pd), Uni<T>::loss_inv_b(pd), f * f, rho, w);
+      if (const T *wts = desc_weights<T>(pd, i)) w *= *wts;  // ScaledLoss: sqrt(w_i rho')
       sc = t_sqrt<T>(w);
     }
     if (r_out) r_out[i] = (double)(sc * f);
@@ -1307,6 +1354,7 @@ __global__ __launch_bounds__(kBlockThreads) void ea_eval_points_kernel(
   if (corrected) {
     T rho, w;
     loss_eval<T>(pd.loss_kind, Uni<T>::loss_a(pd), Uni<T>::loss_inv_b(pd), f * f, rho, w);
+    if (const T *wts = desc_weights<T>(pd, i)) w *= *wts;
     sc = t_sqrt<T>(w);
   }
   if (r_out) r_out[i] = (double)(sc * f);
@@ -1406,6 +1454,9 @@ void ea_eval_rows_kernel(
   if (corrected) {  // (uniform)
     T rho, w;
     loss_eval<T>(pd.loss_kind, Uni<T>::loss_a(pd), Uni<T>::loss_inv_b(pd), f * f, rho, w);
+    if constexpr (VAR) {  // (a weighted term is a variant: the plain instantiations never meet one)
+      if (const T *wts = desc_weights<T>(pd, start + j)) w *= *wts;
+    }
     sc = t_sqrt<T>(w);
   }
   const bool bad = state == 2;
@@ -2609,6 +2660,31 @@ __global__ __launch_bounds__(256) void ea_aos_to_soa_kernel(const double *__rest
   const double *s = src + i * stride;
   x[i] = (T)s[0]; y[i] = (T)s[1]; z[i] = (T)s[2];
 }
+
+// per-point weights into a problem's storage: dst[i] = (T)src[order ? order[i] : i] -- the conversion to the problem dtype
+// (S = double: ea_problem_set_weights) and the tile-order permutation of the points (order[i] = caller's index of stored point i)
+template <typename S, typename T>
+__global__ __launch_bounds__(256) void ea_store_weights_kernel(const S *__restrict__ src, const int32_t *__restrict__ order,
+                                                               long long n, T *__restrict__ dst) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  dst[i] = (T)src[order ? order[i] : i];
+}
+
+// depth weighting of a reference-frame producer (ea_problem_set_depth_weighting): w_i = min(1, (z_ref / z_i)^power) in fp64
+// from the stored z: ONE division, power - 1 multiplications left to right, the min, one rounding to the problem dtype.
+// The ROS scatter keeps edge pixels without a depth test, so z may be 0, negative or NaN: the clamp to [0, 1] keeps every
+// stored weight a valid one (z = 0 or NaN: 1, a negative power product: 0); for z > 0 the max changes nothing.
+template <typename T>
+__global__ __launch_bounds__(256) void ea_depth_weights_kernel(const T *__restrict__ z, long long n,
+                                                               double z_ref, int power, T *__restrict__ w) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double ratio = __ddiv_rn(z_ref, (double)z[i]);
+  double v = ratio;
+  for (int k = 1; k < power; ++k) v = __dmul_rn(v, ratio);
+  w[i] = (T)fmax(0.0, fmin(1.0, v));
+}
 #endif  // !EA_TU_VARIANT
 
 // ------------------------------------------------------------------------------------------------
@@ -2688,8 +2764,15 @@ static hipError_t launch_fused_family(int tag, const EvalLaunch &s, const Proble
           constexpr bool B = decltype(BUF)::value, I = decltype(IMG32)::value;
           if constexpr (!fused_exists<T, P, M, N, kVarTU, B, I>()) return hipErrorInvalidValue;
           else {
-            constexpr auto kernel = decltype(TAG)::value ? &ea_eval_poses_grid_kernel<T, P, M, N, kVarTU, B, I>
-                                                         : &ea_eval_fused_kernel<T, P, M, N, kVarTU, B, I>;
+            auto kernel = decltype(TAG)::value ? &ea_eval_poses_grid_kernel<T, P, M, N, kVarTU, B, I>
+                                               : &ea_eval_fused_kernel<T, P, M, N, kVarTU, B, I>;
+#ifdef EA_TU_VARIANT
+            if (s.weighted)
+              kernel = decltype(TAG)::value ? &ea_eval_poses_grid_w_kernel<T, P, M, N, kVarTU, B, I>
+                                            : &ea_eval_fused_w_kernel<T, P, M, N, kVarTU, B, I>;
+#else
+            if (s.weighted) return hipErrorInvalidValue;  // (weighted terms are variants: ea_kernels_var.hip)
+#endif
             hipLaunchKernelGGL(kernel, g.grid, dim3(N), g.shmem, stream, s.x0, s.y0, s.z0, s.n0, g.shape, g.chunks_per_xcd, probs,
                                poses, partials, g.lds_texels);
             return hipGetLastError();
@@ -3003,6 +3086,27 @@ hipError_t launch_aos_to_soa(int dtype, const double *src, long long n, int stri
   const dim3 grid((unsigned)((n + 255) / 256));
   if (dtype == 1) hipLaunchKernelGGL((ea_aos_to_soa_kernel<float>), grid, dim3(256), 0, stream, src, n, stride, (float *)x, (float *)y, (float *)z);
   else hipLaunchKernelGGL((ea_aos_to_soa_kernel<double>), grid, dim3(256), 0, stream, src, n, stride, (double *)x, (double *)y, (double *)z);
+  return hipGetLastError();
+}
+
+hipError_t launch_store_weights(int dtype, int src_is_double, const void *src, const int32_t *order, long long n, void *dst,
+                                hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  const dim3 grid((unsigned)((n + 255) / 256));
+  if (dtype == 1 && src_is_double)
+    hipLaunchKernelGGL((ea_store_weights_kernel<double, float>), grid, dim3(256), 0, stream, (const double *)src, order, n, (float *)dst);
+  else if (dtype == 1)
+    hipLaunchKernelGGL((ea_store_weights_kernel<float, float>), grid, dim3(256), 0, stream, (const float *)src, order, n, (float *)dst);
+  else
+    hipLaunchKernelGGL((ea_store_weights_kernel<double, double>), grid, dim3(256), 0, stream, (const double *)src, order, n, (double *)dst);
+  return hipGetLastError();
+}
+
+hipError_t launch_depth_weights(int dtype, const void *z, long long n, double z_ref, int power, void *w, hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  const dim3 grid((unsigned)((n + 255) / 256));
+  if (dtype == 1) hipLaunchKernelGGL((ea_depth_weights_kernel<float>), grid, dim3(256), 0, stream, (const float *)z, n, z_ref, power, (float *)w);
+  else hipLaunchKernelGGL((ea_depth_weights_kernel<double>), grid, dim3(256), 0, stream, (const double *)z, n, z_ref, power, (double *)w);
   return hipGetLastError();
 }
 

@@ -20,7 +20,8 @@ namespace ea {
 struct EvalLaunch {
   int dtype = 0;             // EA_F64 / EA_F32
   int ppt = 1, nt = 256;     // points per lane {1, 2, 4}, workgroup size {256, 1024}
-  int variant = 0;           // distortion / second-camera terms (the kernels of ea_kernels_var.hip)
+  int variant = 0;           // distortion / second-camera / weighted terms (the kernels of ea_kernels_var.hip)
+  int weighted = 0;          // some term carries per-point weights (variant bit 2): the weighted kernels of that file
   int chunk = 256;           // points per workgroup = nt * ppt
   int max_chunks = 0;        // workgroups of the widest term
   int xcd_remap = 1;
@@ -140,6 +141,11 @@ hipError_t launch_make_poses(const double *qt, int n, int count, const ProblemDe
 hipError_t launch_grid_to_image(int dtype, const double *grid, int W, int H, void *dst, int pitch, float *dst32, int *inexact,
                                 hipStream_t stream);
 hipError_t launch_aos_to_soa(int dtype, const double *src, long long n, int stride, void *x, void *y, void *z, hipStream_t stream);
+// ea_store_weights_kernel: dst[i] = src[order ? order[i] : i] in the problem dtype, src doubles or the problem dtype;
+// ea_depth_weights_kernel: w[i] = min(1, (z_ref / z[i])^power), fp64 from the stored z, rounded once
+hipError_t launch_store_weights(int dtype, int src_is_double, const void *src, const int32_t *order, long long n, void *dst,
+                                hipStream_t stream);
+hipError_t launch_depth_weights(int dtype, const void *z, long long n, double z_ref, int power, void *w, hipStream_t stream);
 hipError_t launch_selftest_reduce(const float *in, float *a, float *b, float *c, float *d, double *o32, double *o64,
                                   hipStream_t stream);
 // ea_kernels_var.hip (the same file under -DEA_TU_VARIANT): what launch_eval_fused (tag 0) / launch_eval_poses_grid (tag 1) hand on

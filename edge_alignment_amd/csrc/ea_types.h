@@ -45,7 +45,8 @@ struct ProblemDesc {
   int32_t tile_begin, tile_end;  // this term's rows in the partial-sum array (one per workgroup)
   int32_t group;                 // which pose / LM state this residual family belongs to
   // residual variants of standalone/utils.h:102-421 (variant != 0 selects the variant kernel)
-  int32_t variant;               // bit 0: Brown-Conrady distortion, bit 1: second camera of a rigid rig
+  int32_t variant;               // bit 0: Brown-Conrady distortion, bit 1: second camera of a rigid rig, bit 2: per-point
+                                 // weights (w_off below; a weighted term runs the variant kernels whatever its functor)
   int64_t row_begin;             // this term's first row in the batch's materialised outputs (ea_batch_eval_rows_device)
   const void *dt32;              // fp64 problems: the same padded image stored as float32 (same pitch in texels) when every
                                  // value is exactly float-representable -- true of everything the reference's producers emit
@@ -57,7 +58,12 @@ struct ProblemDesc {
   double Ai[9], di[3];           //                a' = Ai a + di,        [Ai di] = affine part of T12^-1
   float distf[5];
   float Af[9], df[3], Aif[9], dif[3];
+  // per-point weights (ceres::ScaledLoss per block), read only when bit 2 of `variant` is set: w[i] = z[w_off + i], in the
+  // problem dtype -- the library keeps z and w in one allocation.  The word fills what was the struct's tail padding: the size
+  // and every other offset are what the plain kernels' scalar loads have always fetched.
+  int32_t w_off;
 };
+static_assert(sizeof(ProblemDesc) == 536, "the plain kernels fetch the descriptor with scalar loads: its layout is fixed");
 
 // a group = the residual families (terms) that share one pose; its rows are contiguous
 struct GroupDesc {

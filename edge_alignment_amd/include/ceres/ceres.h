@@ -423,6 +423,7 @@ struct Solver {
     // the program Solve ran after constant blocks and constant coordinates were removed (blocks, ambient and tangent sizes)
     int num_parameter_blocks_reduced = 2, num_parameters_reduced = 7, num_effective_parameters_reduced = 6;
     double total_time_in_seconds = -1;
+    int ea_num_gpu_problems = 0;  // not part of Ceres: the GPU problems Solve built (one per residual family)
     ea_summary detail{};
 
     bool IsSolutionUsable() const { return termination_type == CONVERGENCE || termination_type == NO_CONVERGENCE; }
@@ -484,6 +485,40 @@ inline void Solve(const Solver::Options &options, Problem *problem, Solver::Summ
 
 class ProblemAccess {  // keeps Problem's internals private to user code
  public:
+  // A residual family: the blocks that share interpolator, intrinsics, functor variant and loss (kind and scale; a
+  // ScaledLoss factor is the block's weight, so N blocks with N different factors are still one family).  weights[j] = factor
+  // of the family's j-th block, in the order the blocks were added; weighted = some factor differs from 1.
+  struct Family { const Problem::Block *first; std::vector<double> xyz; std::vector<int> idx; std::vector<double> weights; bool weighted; };
+  // the grouping Build uploads, on the host alone (no device is touched); false with *err set
+  static bool Families(const Problem *problem, std::vector<Family> *fams_out, std::string *err) {
+    const auto &blocks = problem->blocks_;
+    std::vector<Family> &fams = *fams_out;
+    fams.clear();
+    if (blocks.empty()) { *err = "a NormalPrior needs EAResidue blocks on the same pose (a problem of priors only cannot be hosted)"; return false; }
+    const auto &b0 = blocks[0];
+    for (size_t i = 0; i < blocks.size(); ++i) {
+      const auto &b = blocks[i];
+      if (!b.ok) { *err = "residual block is not an EAResidue-family block (this facade only hosts the edge-alignment hot path)"; return false; }
+      if (b.q != b0.q || b.t != b0.t) { *err = "all residual blocks must share one (quaternion, translation) pair"; return false; }
+      Family *f = nullptr;
+      for (auto &cand : fams)
+        if (SameFamily(*cand.first, b)) { f = &cand; break; }
+      if (!f) {
+        fams.push_back(Family{&b, {}, {}, {}, false});
+        f = &fams.back();
+        f->xyz.reserve(3 * (blocks.size() - i));  // (usually the one family: no regrowth while 44 457 blocks are gathered)
+        f->idx.reserve(blocks.size() - i);
+      }
+      f->xyz.push_back(b.X); f->xyz.push_back(b.Y); f->xyz.push_back(b.Z);
+      f->idx.push_back((int)i);
+      const double w = b.loss ? b.loss->ea_weight() : 1.0;
+      if (!(w >= 0.0) || !(w <= 1.7976931348623157e308)) { *err = "ScaledLoss: the scale of a residual block's loss must be finite and >= 0"; return false; }
+      f->weights.push_back(w);
+      f->weighted = f->weighted || w != 1.0;
+    }
+    return true;
+  }
+
   // Blocks -> residual families (same interpolator, intrinsics, functor variant and loss) -> one GPU problem per
   // family, the first one carrying the others as terms: all of them share (q, t), the way the reference adds
   // camera-1 and camera-2 blocks to one ceres::Problem (standalone_edge_align.cpp:791-803).  order[k] = indices of
@@ -492,26 +527,9 @@ class ProblemAccess {  // keeps Problem's internals private to user code
   static int Build(Problem *problem, int dtype, int device, std::vector<ea_problem *> *ps_out,
                    std::vector<std::vector<int>> *order, std::string *err, int *held_out = nullptr) {
     const auto &blocks = problem->blocks_;
-    if (blocks.empty()) { *err = "a NormalPrior needs EAResidue blocks on the same pose (a problem of priors only cannot be hosted)"; return -1000; }
-    const auto &b0 = blocks[0];
-    struct Family { const Problem::Block *first; std::vector<double> xyz; std::vector<int> idx; };
     std::vector<Family> fams;
-    for (size_t i = 0; i < blocks.size(); ++i) {
-      const auto &b = blocks[i];
-      if (!b.ok) { *err = "residual block is not an EAResidue-family block (this facade only hosts the edge-alignment hot path)"; return -1000; }
-      if (b.q != b0.q || b.t != b0.t) { *err = "all residual blocks must share one (quaternion, translation) pair"; return -1000; }
-      Family *f = nullptr;
-      for (auto &cand : fams)
-        if (SameFamily(*cand.first, b)) { f = &cand; break; }
-      if (!f) {
-        fams.push_back(Family{&b, {}, {}});
-        f = &fams.back();
-        f->xyz.reserve(3 * (blocks.size() - i));  // (usually the one family: no regrowth while 44 457 blocks are gathered)
-        f->idx.reserve(blocks.size() - i);
-      }
-      f->xyz.push_back(b.X); f->xyz.push_back(b.Y); f->xyz.push_back(b.Z);
-      f->idx.push_back((int)i);
-    }
+    if (!Families(problem, &fams, err)) return -1000;
+    const auto &b0 = blocks[0];
     if (problem->quat_param_on_ != b0.q) { *err = "the quaternion block needs QuaternionParameterization (problem.SetParameterization)"; return -1000; }
     const NormalPrior *prior_on[2] = {nullptr, nullptr};  // (q, t)
     for (const auto &pb : problem->priors_) {
@@ -550,6 +568,8 @@ class ProblemAccess {  // keeps Problem's internals private to user code
         if (fams[k].first->loss) { kind = fams[k].first->loss->ea_kind(); a = fams[k].first->loss->ea_scale(); }
         rc = ea_problem_set_loss(ps[k], kind, a);
       }
+      if (rc == EA_OK && fams[k].weighted)  // ScaledLoss factors: the family's per-point weights, in block order
+        rc = ea_problem_set_weights(ps[k], fams[k].weights.data(), (int64_t)fams[k].weights.size());
       if (rc == EA_OK && k > 0) rc = ea_problem_add_term(ps[0], ps[k]);
     }
     if (rc == EA_OK && (held[0] | held[1] | held[2] | held[3] | held[4] | held[5]))  // the mask too goes on the head problem
@@ -699,6 +719,8 @@ class ProblemAccess {  // keeps Problem's internals private to user code
     int held[6] = {0, 0, 0, 0, 0, 0};
     int rc = Build(problem, options.ea_dtype, options.ea_device, &ps, &order, &berr, held);
     if (rc == -1000) return fail(berr);
+    int built = 0;
+    for (const ea_problem *p : ps) built += p ? 1 : 0;
     const auto &b0 = blocks[0];  // (Build refused a problem without EAResidue blocks)
     {
       const int free_q = 3 - held[0] - held[1] - held[2], free_t = 3 - held[3] - held[4] - held[5];
@@ -734,10 +756,12 @@ class ProblemAccess {  // keeps Problem's internals private to user code
     s.num_successful_steps = s.detail.num_successful_steps;
     s.num_unsuccessful_steps = s.detail.num_unsuccessful_steps;
     s.total_time_in_seconds = s.detail.total_time_ms * 1e-3;
+    s.ea_num_gpu_problems = built;
   }
 
  private:
-  // same functor description (by construction: same index) and an equivalent loss
+  // same functor description (by construction: same index) and an equivalent loss -- up to a ScaledLoss factor, which is
+  // the block's weight and not part of the family
   static bool SameFamily(const Problem::Block &a, const Problem::Block &b) {
     return a.fam == b.fam && (a.loss == b.loss || SameLoss(a.loss, b.loss));
   }

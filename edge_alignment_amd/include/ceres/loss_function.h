@@ -19,6 +19,9 @@ class LossFunction {
   virtual void Evaluate(double s, double rho[3]) const = 0;
   virtual int ea_kind() const = 0;
   virtual double ea_scale() const { return 1.0; }
+  // the factor a ScaledLoss puts in front of the loss named by ea_kind / ea_scale (1 for every other loss): the block's
+  // per-point weight on the device (ea_problem_set_weights)
+  virtual double ea_weight() const { return 1.0; }
 };
 
 class TrivialLoss : public LossFunction {
@@ -84,9 +87,41 @@ class LossFunctionWrapper : public LossFunction {
   }
   int ea_kind() const override { return rho_ ? rho_->ea_kind() : (int)EA_LOSS_TRIVIAL; }
   double ea_scale() const override { return rho_ ? rho_->ea_scale() : 1.0; }
+  double ea_weight() const override { return rho_ ? rho_->ea_weight() : 1.0; }
 
  private:
   LossFunction *rho_;
+  Ownership ownership_;
+};
+
+// ceres/loss_function.h: rho(s) -> a rho(s), the way to weight one residual block:
+//   problem.AddResidualBlock(cost, new ScaledLoss(new CauchyLoss(1.), w_i, TAKE_OWNERSHIP), q, t);
+// NULL = a s.  On the device the factor is block i's per-point weight (ea_problem_set_weights): blocks that differ only in
+// `a` stay ONE residual family, i.e. one GPU problem.  Nested ScaledLosses multiply.  a < 0 is refused when the problem is
+// built (Ceres would minimise a negated loss; the IRLS weights of the kernels are square-rooted).
+class ScaledLoss : public LossFunction {
+ public:
+  ScaledLoss(const LossFunction *rho, double a, Ownership ownership) : rho_(rho), a_(a), ownership_(ownership) {}
+  ScaledLoss(const ScaledLoss &) = delete;
+  ScaledLoss &operator=(const ScaledLoss &) = delete;
+  ~ScaledLoss() override {
+    if (ownership_ == TAKE_OWNERSHIP) delete rho_;
+  }
+  void Evaluate(double s, double rho[3]) const override {
+    if (rho_) {
+      rho_->Evaluate(s, rho);
+      rho[0] *= a_; rho[1] *= a_; rho[2] *= a_;
+    } else {
+      rho[0] = a_ * s; rho[1] = a_; rho[2] = 0.0;
+    }
+  }
+  int ea_kind() const override { return rho_ ? rho_->ea_kind() : (int)EA_LOSS_TRIVIAL; }
+  double ea_scale() const override { return rho_ ? rho_->ea_scale() : 1.0; }
+  double ea_weight() const override { return a_ * (rho_ ? rho_->ea_weight() : 1.0); }
+
+ private:
+  const LossFunction *rho_;
+  double a_;
   Ownership ownership_;
 };
 

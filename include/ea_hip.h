@@ -192,6 +192,43 @@ int ea_problem_set_second_camera(ea_problem *p, const double trans_1to2[16], con
 int ea_problem_add_term(ea_problem *p, ea_problem *term);
 int ea_problem_clear_terms(ea_problem *p);
 
+/* Per-point weights: ceres::ScaledLoss(loss, w_i, ...) on residual block i, i.e.
+ *   problem.AddResidualBlock(cost, new ceres::ScaledLoss(new ceres::CauchyLoss(1.), w_i, ceres::TAKE_OWNERSHIP), q, t);
+ * With weights set every evaluation of the problem computes cost = 1/2 sum w_i rho(r_i^2), JtJ = sum w_i rho'_i J_i^T J_i,
+ * Jtr = sum w_i rho'_i J_i^T r_i (trivial loss: w_i r_i^2 / 2 ...): ea_eval, ea_cost, the solves (single, batched, pyramid
+ * level by level, sharded: each rank weights its shard, multi-start, search), the pose-batched evaluations, the tracker and
+ * terms (each term its own weights); priors and constant parameters are untouched.  n_invalid does not look at the weights
+ * (a block of weight 0 whose functor returns false still counts, as in Ceres).  Per-point outputs (ea_eval_points,
+ * ea_eval_rows*, ea_batch_eval_rows*): corrected != 0 gives sqrt(w_i rho'_i) r_i and sqrt(w_i rho'_i) J_i, corrected == 0
+ * the raw, unweighted r_i and row.  ea_*_covariance with apply_loss_function = 0 drops the weights together with the loss;
+ * with 1 it inverts the weighted JtJ.  ea_problem_pixel_cost is the reference's own unweighted report and stays so.
+ * The weights belong to the point set: whatever replaces the points (ea_problem_set_points*, a reference-frame producer
+ * without depth weighting) drops them.  A weighted problem runs the kernels of the residual variants (as a problem with
+ * distortion does); a batch rebuilds when weights appear or disappear, not when their values change.
+ *
+ * ea_problem_set_weights: w = n host doubles in the caller's point order (n = ea_problem_num_points), each finite and >= 0,
+ * rounded once to the problem dtype and kept in HBM beside the points, in their storage order (ea_problem_set_point_order).
+ * A wrong n, a negative, NaN or infinite weight (fp32 problems: one that overflows float): EA_ERR_INVALID_ARG, nothing
+ * changes (a device allocation or copy that fails afterwards -- EA_ERR_HIP -- leaves the previous weights in an unspecified
+ * state, like any failed upload).  w == NULL clears the weights (n is ignored).  Points borrowed through ea_problem_set_points_device are copied
+ * into arrays the problem owns first (the weights live in the same allocation as z).
+ * ea_problem_set_weights_device: the same from n values of the problem dtype already in HBM, caller's order; copied, not
+ * borrowed; the values are the caller's responsibility.
+ * ea_problem_get_weights: the stored weights as doubles in the caller's order; *count = n, or 0 when no weights are set
+ * (nothing is written then).  capacity < n: EA_ERR_INVALID_ARG. */
+int ea_problem_set_weights(ea_problem *p, const double *w, int64_t n);
+int ea_problem_set_weights_device(ea_problem *p, const void *w, int64_t n);
+int ea_problem_get_weights(ea_problem *p, double *w, int64_t capacity, int64_t *count);
+/* Depth weighting, a setting on the problem read by every reference-frame producer (ea_problem_set_ref_frame, _masked,
+ * _canny, _ros, _ros_scaled, and the tracker's reference step through ea_tracker_problem(tr)): behind the scatter of the
+ * points a device kernel writes w_i = min(1, (z_ref / z_i)^power) -- an RGB-D sensor's depth noise grows with z^2 -- with no
+ * host round trip.  Computed in fp64 from the STORED z widened to double: one IEEE division z_ref / z_i, then power - 1
+ * multiplications by that ratio left to right, then the min with 1, then one rounding to the problem dtype (numpy
+ * reproduces it bit for bit).  Points without a usable depth (the ROS producers keep them: z = 0, NaN, negative) get a
+ * weight clamped into [0, 1]; their functor fails or not exactly as without weights.  power in 1..8; power = 0 (default) switches it off and clears weights a producer wrote;
+ * z_ref must be finite and > 0.  Takes effect at the next producer call. */
+int ea_problem_set_depth_weighting(ea_problem *p, double z_ref, int power);
+
 /* One evaluation of the whole problem at pose (q,t) — what ceres' evaluator computes from the
  * N AutoDiffCostFunction<EAResidue,1,4,3> blocks + QuaternionParameterization + loss:
  *   cost = 1/2 sum rho(r_i^2);  JtJ (6x6 row-major) and Jtr (6) of the loss-corrected 1x6 rows
@@ -200,7 +237,7 @@ int ea_problem_clear_terms(ea_problem *p);
 int ea_eval(ea_problem *p, const double q[4], const double t[3], double *cost, double JtJ[36],
             double Jtr[6], int64_t *n_invalid);
 /* per-point outputs (host, n and n*6 row-major; NaN for failed blocks).  corrected != 0:
- * sqrt(rho') r and sqrt(rho') J as handed to the minimiser; 0: raw r_i and raw row. */
+ * sqrt(rho') r and sqrt(rho') J as handed to the minimiser (sqrt(w_i rho') with weights); 0: raw r_i and raw row. */
 int ea_eval_points(ea_problem *p, const double q[4], const double t[3], double *r, double *J,
                    int corrected);
 /* residual-only evaluation (the candidate-cost evaluation inside the trust-region loop) */
@@ -212,7 +249,8 @@ int ea_cost(ea_problem *p, const double q[4], const double t[3], double *cost,
  * y / z pushed through K, truncated `(int)` to a pixel, the distance transform read there; total, mean over the points,
  * maximum and the (untruncated) pixel of the first point that attains it.  Computed on the device from the points and the
  * DT image the problem already holds.  Upstream reads outside the image unchecked (undefined behaviour): such points are
- * skipped and counted in `outside`; upstream accumulates in float in point order, this sums in double. */
+ * skipped and counted in `outside`; upstream accumulates in float in point order, this sums in double.  Per-point weights
+ * (ea_problem_set_weights) do not enter: this is the reference's report. */
 typedef struct {
   double total_cost, mean_cost, max_cost;
   double max_pixel[2];      /* (u, v) before truncation */
@@ -539,7 +577,9 @@ int ea_eval_rows_device(ea_problem *p, const double q[4], const double t[3], int
  * "wide_accumulate" = 1: an fp32 batch sums in fp64 from a lane's sum of <= points_per_thread products on (default: a
  * lane's and a wavefront's sums are fp32, everything above fp64).  Plain functor on the L2 path; ignored for fp64
  * batches, variant functors and the LDS-staged form (ea_batch_get_info "wide_accumulate" reports what is in effect).
- * Applies to ea_batch_eval and the solves; cost: profiles/r02_ab_wide_accumulate.txt. */
+ * Applies to ea_batch_eval and the solves; cost: profiles/r02_ab_wide_accumulate.txt.
+ * ea_batch_get_info "weighted": the number of terms of the current build that carry per-point weights (ea_problem_set_weights;
+ * any such term puts the batch on the variant kernels: "starts_form" and "cost_form" then report 0). */
 int ea_batch_set_tuning(ea_batch *b, const char *key, int value);
 int ea_batch_get_info(const ea_batch *b, const char *key, int64_t *value);
 
