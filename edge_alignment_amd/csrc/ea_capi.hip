@@ -1245,9 +1245,11 @@ static int batch_build(ea_batch *b) {
   int nt = (b->t_nt == 1024 || b->t_nt == 256) ? b->t_nt : nt_auto;
   int ppt = b->t_ppt;
   if (ppt != 1 && ppt != 2 && ppt != 4) ppt = ppt_auto;
+  // the variant kernel is built for this shape only -- first, so that a request for 1024 threads, which it cannot honour,
+  // does not cost an fp64 batch its second point per lane through the rule below
+  if (any_variant) { nt = 256; ppt = std::min(ppt, 2); }
   if (nt == 1024 && b->dtype == EA_F64) ppt = 1;  // 128-VGPR budget at 16 waves/CU
   if (b->dtype == EA_F64 && ppt > 2) ppt = 2;
-  if (any_variant) { nt = 256; ppt = std::min(ppt, 2); }  // the variant kernel is built for this shape only
   // raw-buffer addressing (32-bit byte offsets into the image): on unless an image reaches 2 GiB
   int buffer_loads = b->t_buf >= 0 ? (b->t_buf ? 1 : 0) : 1;
   for (const ea_problem *p : terms)
@@ -1541,9 +1543,9 @@ static void kposes_shape(ea_batch *b) {
   if (b->lds_bytes > 0 || b->wide) { nt = b->nt; ppt = b->ppt; }          // (those forms keep the shape they were tuned at)
   if (b->t_nt == 1024 || b->t_nt == 256) nt = b->t_nt;
   if (b->t_ppt == 1 || b->t_ppt == 2 || b->t_ppt == 4) ppt = b->t_ppt;
+  if (b->any_variant) { nt = 256; ppt = std::min(ppt, 2); }  // (first, as in batch_build)
   if (nt == 1024 && b->dtype == EA_F64) ppt = 1;
   if (b->dtype == EA_F64 && ppt > 2) ppt = 2;
-  if (b->any_variant) { nt = 256; ppt = std::min(ppt, 2); }
   b->kp_nt = nt; b->kp_ppt = ppt; b->kp_chunk = nt * ppt;
   // the wave-exchange reduction (ea_wave_exchange.h): the fp64, 256-lane launches of ea_eval_poses_kernel / ea_eval_starts_kernel
   b->kp_xchg = b->t_kp_xchg && b->dtype == EA_F64 && nt == 256 && kposes_flat(b);

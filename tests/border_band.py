@@ -190,9 +190,10 @@ def functor(image, K, xyz, q, t, dtype=np.longdouble, z_guard=0.01, z_eps=0.0, d
     return dict(r=r, J=J, u=u, v=v, valid=valid, band=band)
 
 
-def with_loss(raw, kind, a):
+def with_loss(raw, kind, a, weights=None):
     """Ceres' loss (rho, rho') at s = r^2 and its corrector (rho'' <= 0 for these three: both scale by sqrt(rho')) on the
-    output of `functor` -> dict(r, J corrected, rho); the arithmetic type is the one of raw['r']"""
+    output of `functor` -> dict(r, J corrected, rho); the arithmetic type is the one of raw['r'].  weights: one per point,
+    ceres::ScaledLoss(loss, w_i) per block -- rho and rho' times w_i, so rows scale by sqrt(w_i rho')"""
     r, J = raw["r"], raw["J"]
     ty = r.dtype.type
     s = r * r
@@ -206,6 +207,10 @@ def with_loss(raw, kind, a):
         rho, w = np.where(s > b, ty(2) * ty(a) * rt - b, s), np.where(s > b, ty(a) / rt, one)
     else:
         rho, w = s, np.ones_like(s)
+    if weights is not None:
+        wt = np.asarray(weights).astype(r.dtype)
+        assert wt.shape == r.shape
+        rho, w = wt * rho, wt * w
     sq = np.sqrt(w)
     return dict(r=r * sq, J=J * sq[:, None], rho=rho)
 
@@ -262,11 +267,12 @@ def bounds(ref_rows, plain_rows, base, image):
     return d
 
 
-def tolerances(pr, xyz, q, t, loss, dtype, ref_rows=None, base=None, **variant):
-    """`bounds` for a kernel of precision `dtype` on problem pr at pose (q, t) under `loss`"""
+def tolerances(pr, xyz, q, t, loss, dtype, ref_rows=None, base=None, weights=None, **variant):
+    """`bounds` for a kernel of precision `dtype` on problem pr at pose (q, t) under `loss` (with per-point `weights`:
+    weighted plain-precision rows against weighted extended-precision rows)"""
     if ref_rows is None:
-        ref_rows = with_loss(functor(pr["image"], pr["K"], xyz, q, t, np.longdouble, **variant), *loss)
-    plain = with_loss(functor(pr["image"], pr["K"], xyz, q, t, dtype, **variant), *loss)
+        ref_rows = with_loss(functor(pr["image"], pr["K"], xyz, q, t, np.longdouble, **variant), *loss, weights=weights)
+    plain = with_loss(functor(pr["image"], pr["K"], xyz, q, t, dtype, **variant), *loss, weights=weights)
     return bounds(ref_rows, plain, base or PROJECT[dtype], pr["image"])
 
 
@@ -274,6 +280,9 @@ def tolerances(pr, xyz, q, t, loss, dtype, ref_rows=None, base=None, **variant):
 
 N_GPU = 1000   # points per case in the GPU modules (the CPU module uses 4000)
 VARIANT_BASE = {np.float64: dict(r=1e-12, J=1e-11, sums=1e-11), np.float32: dict(r=5e-5, J=5e-4, sums=1e-4)}  # tests/test_gpu_rows.py
+# a problem with per-point weights runs the variant kernels with the plain functor: the bounds tests/test_gpu_weights.py holds
+# its rows to (J 1e-11; fp32 rows as the plain kernels) and this module's bounds on the sums
+WEIGHTED_BASE = {np.float64: dict(r=1e-12, J=1e-11, sums=1e-11), np.float32: dict(r=2e-5, J=2e-4, sums=1e-4)}
 _CACHE = {}   # references are pure functions of (case, precision, pose): computed once per test session
 
 
@@ -290,15 +299,17 @@ def problem(H, W, kind, n=N_GPU):
 class Case:
     """band_problem(H, W) in a Problem of dtype `dtype`.  upload: "grid" (set_dt_grid), "device image"
     (set_dt_image_device of a torch tensor) or a callable(P) that fills the image itself (a frame producer; the reference
-    then takes Problem.get_dt() as the image, and `tag` names the producer for the cache).  Raises the library's EAError
-    when the upload is refused."""
+    then takes Problem.get_dt() as the image, and `tag` names the producer for the cache).  weights: (values (n,), name)
+    -> Problem.set_weights; corrected rows, sums and bounds are then those of the weighted problem, with the weights the
+    device holds (Problem.get_weights).  Raises the library's EAError when the upload is refused."""
 
-    def __init__(self, hip, H, W, kind, dtype, tile=None, variant=None, vname="", upload="grid", tag=""):
+    def __init__(self, hip, H, W, kind, dtype, tile=None, variant=None, vname="", upload="grid", tag="", weights=None):
         self.hip, self.H, self.W, self.kind, self.dtype = hip, H, W, kind, dtype
         self.np = np.float32 if dtype == hip.EA_F32 else np.float64
         self.pr = problem(H, W, kind)
         self.variant = variant or {}
-        self.base = (VARIANT_BASE if variant else PROJECT)[self.np]
+        self.base = (VARIANT_BASE if variant else WEIGHTED_BASE if weights is not None else PROJECT)[self.np]
+        self.weights = None
         self.P = P = hip.Problem(*self.pr["K"], dtype=dtype)
         try:
             if tile is not None:
@@ -323,10 +334,14 @@ class Case:
             self.xyz = P.get_points()
             want = self.pr["xyz"] if self.np is np.float64 else self.pr["xyz"].astype(np.float32).astype(np.float64)
             assert np.array_equal(self.xyz, want)
+            if weights is not None:
+                P.set_weights(weights[0])
+                self.weights = P.get_weights()
+                assert np.array_equal(self.weights, np.asarray(weights[0]).astype(self.np).astype(np.float64))
         except BaseException:
             P.close()
             raise
-        self.key = (H, W, kind, self.np.__name__, vname, tag)
+        self.key = (H, W, kind, self.np.__name__, vname, tag, weights[1] if weights is not None else "")
 
     def name(self):
         return "%dx%d %s %s" % (self.H, self.W, self.key[5] or self.kind, "fp32" if self.np is np.float32 else "fp64")
@@ -345,14 +360,14 @@ class Case:
     def rows(self, pose, loss, corrected=True):
         if not corrected:
             return self.raw(pose, 0.0)
-        return _cached(self.key + (tuple(pose[0]), tuple(pose[1]), tuple(loss), "rows"), lambda: with_loss(self.raw(pose, 0.0), *loss))
+        return _cached(self.key + (tuple(pose[0]), tuple(pose[1]), tuple(loss), "rows"), lambda: with_loss(self.raw(pose, 0.0), *loss, weights=self.weights))
 
     def sums(self, pose, loss):
         return _cached(self.key + (tuple(pose[0]), tuple(pose[1]), tuple(loss), "sums"), lambda: sums(self.rows(pose, loss)))
 
     def tol(self, pose, loss):
         def make():
-            ref, plain = self.rows(pose, loss), with_loss(self._functor(pose, self.np), *loss)
+            ref, plain = self.rows(pose, loss), with_loss(self._functor(pose, self.np), *loss, weights=self.weights)
             return bounds(ref, plain, self.base, self.image)
         return _cached(self.key + (tuple(pose[0]), tuple(pose[1]), tuple(loss), "tol"), make)
 

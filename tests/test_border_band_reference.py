@@ -76,3 +76,36 @@ def test_cpu_checkers_match_the_extended_reference_on_the_band(oracle, H, W, kin
                              % (H, W, kind, pi, share, tol["plain_r"], tol["plain_J"], tol["plain_sums"],
                                 t32["plain_r"], t32["plain_J"], t32["plain_sums"]))
     print("\n".join(lines))   # (shown with -s or -rP)
+
+
+@pytest.mark.parametrize("H,W", bb.CORE_SHAPES, ids=["%dx%d" % s for s in bb.CORE_SHAPES])
+def test_weighted_rows_and_sums_on_the_band(oracle, H, W):
+    """per-point weights (ceres::ScaledLoss per block) through border_band: (a) integer weights in {0..3} are the cloud with
+    point i repeated w_i times, in the reference's own extended arithmetic -- the two sums differ by the order of at most
+    3 N additions, 3 N eps(longdouble) = 1.3e-15 for N = 4000, asserted 2e-15; (b) the oracle's raw rows scaled by
+    sqrt(w rho') and the sums of tests/weights_ref.py, with real weights that have exact zeros, under the rule the kernels
+    are held to: weighted plain-fp64 rows against weighted extended rows, 4x, or the project's bound"""
+    import weights_ref as wr
+    pr = bb.band_problem(H, W, N, 100 + bb.SHAPES.index((H, W)), "noise")
+    wi = np.random.default_rng(H + W).integers(0, 4, N)
+    wreal = wr.real_weights(N, H + W)
+    assert (wreal == 0).sum() >= N // 6 and (wi == 0).any()
+    for pi, (q, t) in enumerate(bb.POSES):
+        raw = bb.functor(pr["image"], pr["K"], pr["xyz"], q, t)
+        rep = bb.functor(pr["image"], pr["K"], np.repeat(pr["xyz"], wi, axis=0), q, t)
+        assert raw["valid"].all() and raw["band"].mean() >= 0.5
+        for loss in bb.LOSSES:
+            a, b = bb.sums(bb.with_loss(raw, *loss, weights=wi)), bb.sums(bb.with_loss(rep, *loss))
+            d = bb.dev_sums(a, b)
+            assert d <= 2e-15, (pi, loss, "repeated cloud", d)
+            ref = bb.with_loss(raw, *loss, weights=wreal)
+            tol = bb.tolerances(pr, pr["xyz"], q, t, loss, np.float64, ref_rows=ref, weights=wreal)
+            e = oracle.OracleProblem(pr["grid"], *pr["K"], loss=loss[0], loss_a=loss[1]).eval(pr["xyz"], q, t, oracle.JAC_JET, materialize=True)
+            sc = np.sqrt(wreal * wr.loss_pair(loss[0], loss[1], e["raw_r"] ** 2)[1])
+            assert bb.dev_r(sc * e["raw_r"], ref["r"]) <= tol["r"] and bb.dev_J(sc[:, None] * e["raw_J"], ref["J"]) <= tol["J"], (pi, loss)
+            cost, JtJ, Jtr = wr.weighted_sums(e, wreal, *loss)
+            ds = bb.dev_sums(dict(cost=cost, JtJ=JtJ, Jtr=Jtr), bb.sums(ref))
+            assert ds <= tol["sums"], (pi, loss, ds, tol["sums"])
+            if loss[0] == bb.LOSS_CAUCHY:
+                print("BAND-CPU weighted %dx%d pose %d: repeated cloud %.1e | plain fp64 r %.1e J %.1e sums %.1e | oracle sums %.1e"
+                      % (H, W, pi, d, tol["plain_r"], tol["plain_J"], tol["plain_sums"], ds))

@@ -2,7 +2,8 @@
 extended-precision restatement of tests/border_band.py (numpy.longdouble, each tap clamped on its own): the fused sums
 in every launch shape / addressing form / image form, the per-point kernel, the materialised rows, the pose-batched
 kernel, the variant functors (the reference is extended by the same distortion and rig maps, not the oracle's Jet
-rows), the riding fold, one fused-iteration solve against its pair form, and the integer-pixel cost report.  Images are
+rows), the weighted kernels (per-point weights: the reference's rows times sqrt(w_i rho')), the riding fold, one
+fused-iteration solve against its pair form, and the integer-pixel cost report.  Images are
 tall, wide, square, smaller than the stencil, and of widths either side of the upload's 32-texel tiles and of every
 residue mod 4 (border_band.SHAPES); texels are noise (every tap matters) or distance-like.
 
@@ -300,3 +301,43 @@ def test_integer_pixel_cost_on_the_band(hip, dtype_name):
             assert at_id["outside"] > N // 10 and at_id["count"] > 0, (c.name(), at_id)   # both sides of the border are populated
         finally:
             c.close()
+
+
+@pytest.mark.parametrize("dtype_name", DTYPES)
+def test_weighted_kernels_on_the_band(hip, dtype_name):
+    """per-point weights (the weighted kernels of the variant translation unit, plain functor) on the band: Batch.eval at one
+    and two points per lane and both addressing forms, the corrected rows, and the pose-batched kernel over the three poses,
+    against the reference's weighted rows (border_band.with_loss(weights=): rows times sqrt(w_i rho'), rho times w_i, with the
+    weights the device holds).  Distinct real weights with exact zeros (weights_ref.real_weights)."""
+    import weights_ref as wr
+    dtype = getattr(hip, dtype_name)
+    loss = bb.LOSSES[1]
+    for (H, W), kind in NOISE_CORE:
+        c = bb.make_case(hip, H, W, kind, dtype, weights=(wr.real_weights(N, 40 + H), "real%d" % (40 + H)))
+        if c is None:
+            continue
+        c.P.set_loss(*loss)
+        B = hip.Batch([c.P])
+        try:
+            seen = {}
+            for pi, pose in enumerate(bb.POSES):
+                c.raw(pose)   # (asserts the workload)
+                for ppt, buf in ((1, 1), (2, 1), (2, 0)):
+                    B.set_tuning("points_per_thread", ppt); B.set_tuning("buffer_loads", buf)
+                    g = B.eval(*pose)
+                    where = ("weighted eval", pi, ppt, buf)
+                    assert B.info("weighted") == 1 and B.info("points_per_thread") == ppt and B.info("buffer_loads") == buf, where
+                    assert B.info("chunk") == 256 * ppt and B.info("threads") == 256, where
+                    c.check_sums(g, pose, loss, where, seen)
+                B.set_tuning("points_per_thread", -1); B.set_tuning("buffer_loads", -1)
+                rr, JJ, bad = B.eval_rows(*pose, corrected=True)
+                assert bad == 0
+                c.check_rows(rr, JJ, pose, loss, True, ("weighted eval_rows", pi), seen)
+            q = np.stack([p[0] for p in bb.POSES]).reshape(-1, 1, 4)
+            t = np.stack([p[1] for p in bb.POSES]).reshape(-1, 1, 3)
+            got = B.eval_poses(q, t)
+            for k, p in enumerate(bb.POSES):
+                c.check_sums({f: got[f][k] for f in got}, p, loss, ("weighted eval_poses", k), seen)
+            c.report(seen, bb.POSES[1], loss, "weighted")
+        finally:
+            B.close(); c.close()

@@ -3,7 +3,10 @@
     cost = 1/2 sum w rho(r^2), JtJ = sum w rho' J^T J, Jtr = sum w rho' J^T r;
 (b) solves -- integer weights w_i in {0..3} are the problem with point i repeated w_i times, so OracleProblem.solve on
     np.repeat(xyz, w, axis=0) is the oracle of the weighted solve.
-On the three problems below (a) agrees with the oracle's own evaluation of the repeated cloud to <= 4e-15 relative."""
+(a) agrees with the oracle's own evaluation of the repeated cloud to <= 7e-15 relative (tests/test_weights_ref.py asserts 1e-13).
+Failed blocks (|b_z| < z_guard: the functor returns false, the oracle's raw rows are NaN) are left out of the sums and counted
+once each whatever their weight -- a block with ScaledLoss(..., 0) whose functor fails is still a failed block; `plant_failed`
+puts such blocks into a cloud."""
 import numpy as np
 
 from edge_alignment_amd import synth
@@ -33,13 +36,49 @@ def loss_pair(kind, a, s):
     return np.where(out, 2.0 * a * r - b, s), np.where(out, a / r, 1.0)
 
 
+def n_failed(e):
+    """failed blocks of a materialised oracle evaluation: each counts once, whatever its weight"""
+    bad = np.isnan(e["raw_r"])
+    assert int(bad.sum()) == e["n_invalid"] and np.array_equal(bad, np.isnan(e["raw_J"]).any(axis=1))
+    return int(bad.sum())
+
+
 def weighted_sums(e, w, kind=LOSS_CAUCHY, a=1.0):
-    """(cost, JtJ, Jtr) of the weighted problem from a materialised oracle evaluation `e` (no failed blocks)"""
-    r, J = e["raw_r"], e["raw_J"]
-    assert e["n_invalid"] == 0 and np.isfinite(r).all()
+    """(cost, JtJ, Jtr) of the weighted problem from a materialised oracle evaluation `e`; failed blocks (NaN raw rows, see
+    n_failed) are left out of the sums"""
+    ok = ~np.isnan(e["raw_r"])
+    assert n_failed(e) == int((~ok).sum())
+    r, J, w = e["raw_r"][ok], e["raw_J"][ok], np.asarray(w, dtype=np.float64)[ok]
+    assert np.isfinite(r).all() and np.isfinite(J).all()
     rho, rho1 = loss_pair(kind, a, r * r)
-    wr = np.asarray(w, dtype=np.float64) * rho1
+    wr = w * rho1
     return 0.5 * np.sum(w * rho), (J * wr[:, None]).T @ J, J.T @ (wr * r)
+
+
+# failed blocks: b = R X + t with |b_z| in [0.003, 0.008] -- fp32 storage of X (relative 6e-8 of coordinates below 0.1)
+# cannot move it across the 0.01 guard
+FAILED_BZ = (0.005, -0.004, 0.007)
+FAILED_W = (2, 3, 0)
+
+
+def failed_indices(n):
+    """where the failed blocks go: point 0, point n - 1 (the last lane of a partial chunk) and one index with
+    256 <= i mod 512, the k = 1 half of a two-point lane (300; for n <= 301 point n - 1 is that already when n > 256 and the
+    third block goes to the middle).  Distinct and ascending; fewer than three for n < 3."""
+    return sorted({0, n - 1, 300 if n > 301 else n // 2})
+
+
+def plant_failed(xyz, q, t, idx=None, bz=FAILED_BZ):
+    """a copy of the cloud with X_i = R^T (b - t), b = (0.02 (j + 1), -0.015, bz[j]), at the j-th index of idx: the functor
+    fails on these blocks at pose (q, t) -> (cloud, idx)"""
+    xyz = np.array(xyz, dtype=np.float64)
+    idx = failed_indices(len(xyz)) if idx is None else list(idx)
+    q = np.asarray(q, dtype=np.float64)
+    R = synth.quat_to_R(q / np.linalg.norm(q))
+    for j, i in enumerate(idx):
+        b = np.array([0.02 * (j + 1), -0.015, bz[j]])
+        xyz[i, :3] = (b - np.asarray(t, dtype=np.float64)) @ R
+    return xyz, idx
 
 
 def solve_problem(H, W, n, seed):
