@@ -46,6 +46,8 @@ EXPORTED = [
     "ea_tracker_last_covariance", "ea_problem_set_normal_prior", "ea_tracker_set_motion_prior",
     "ea_problem_set_constant_parameters", "ea_problem_get_constant_parameters",
     "ea_problem_set_weights", "ea_problem_set_weights_device", "ea_problem_get_weights", "ea_problem_set_depth_weighting",
+    "ea_problem_residual_quantiles", "ea_batch_residual_quantiles", "ea_problem_get_loss", "ea_problem_set_loss_auto_scale",
+    "ea_problem_get_loss_auto_scale", "ea_selftest_select",
 ]
 
 # measurement hooks (edge_alignment_amd/csrc/ea_hip_dev.h): bound by bench.py, the A/B scripts and the tests that pin the
@@ -247,6 +249,12 @@ def load():
     L.ea_tracker_set_motion_prior.argtypes = [vp, C.c_double, C.c_double]
     L.ea_problem_set_constant_parameters.argtypes = [vp, C.POINTER(C.c_int)]
     L.ea_problem_get_constant_parameters.argtypes = [vp, C.POINTER(C.c_int)]
+    L.ea_problem_residual_quantiles.argtypes = [vp, dp, dp, dp, C.c_int, dp, i64p]
+    L.ea_batch_residual_quantiles.argtypes = [vp, dp, dp, dp, C.c_int, dp, i64p]
+    L.ea_problem_get_loss.argtypes = [vp, C.POINTER(C.c_int), dp]
+    L.ea_problem_set_loss_auto_scale.argtypes = [vp, C.c_double, C.c_double, C.c_double]
+    L.ea_problem_get_loss_auto_scale.argtypes = [vp, dp, dp, dp]
+    L.ea_selftest_select.argtypes = [C.c_int, dp, i64p, C.c_int, dp, C.c_int, dp, i64p]
     _lib = L
     return L
 
@@ -616,6 +624,30 @@ class Problem:
     def set_loss(self, kind, a=1.0):
         _check(load().ea_problem_set_loss(self._h, kind, a))
 
+    def get_loss(self):
+        """(kind, a) the problem holds now; after a solve with auto scale: the a that solve used"""
+        kind, a = C.c_int(), C.c_double()
+        _check(load().ea_problem_get_loss(self._h, C.byref(kind), C.byref(a)))
+        return kind.value, a.value
+
+    def set_loss_auto_scale(self, factor, prob=0.5, a_min=1e-6):
+        """every solve first sets a = max(a_min, factor * Q_prob(|r|)) at its start pose (ea_problem_set_loss_auto_scale);
+        factor = 0 switches it off"""
+        _check(load().ea_problem_set_loss_auto_scale(self._h, factor, prob, a_min))
+
+    def get_loss_auto_scale(self):
+        f, p, a = C.c_double(), C.c_double(), C.c_double()
+        _check(load().ea_problem_get_loss_auto_scale(self._h, C.byref(f), C.byref(p), C.byref(a)))
+        return f.value, p.value, a.value
+
+    def residual_quantiles(self, q, t, probs):
+        """exact order statistics of |r| over the valid blocks at (q, t): (values [len(probs)], n_valid)"""
+        q, t, probs = _f64(q), _f64(t), _f64(probs).reshape(-1)
+        values = np.zeros(probs.size)
+        m = C.c_int64()
+        _check(load().ea_problem_residual_quantiles(self._h, _dp(q), _dp(t), _dp(probs), probs.size, _dp(values), C.byref(m)))
+        return values, m.value
+
     def set_flavour(self, z_guard=0.01, z_eps=0.0, rot_transposed=False):
         _check(load().ea_problem_set_flavour(self._h, z_guard, z_eps, int(rot_transposed)))
 
@@ -775,6 +807,18 @@ class Tracker:
         L = load()
         _check(L.ea_problem_set_constant_parameters(L.ea_tracker_problem(self._h), _constant_mask(mask)))
 
+    def set_loss_auto_scale(self, factor, prob=0.5, a_min=1e-6):
+        """ea_problem_set_loss_auto_scale on the tracker's problem: every push's solve estimates its own loss scale"""
+        L = load()
+        _check(L.ea_problem_set_loss_auto_scale(L.ea_tracker_problem(self._h), float(factor), float(prob), float(a_min)))
+
+    def get_loss(self):
+        """(kind, a) of the tracker's problem: after a push that aligned, the scale its solve used"""
+        L = load()
+        kind, a = C.c_int(), C.c_double()
+        _check(L.ea_problem_get_loss(L.ea_tracker_problem(self._h), C.byref(kind), C.byref(a)))
+        return kind.value, a.value
+
     def last_covariance(self):
         """the covariance of the last push (covariance_to_dict); EAError(EA_ERR_STATE) when it did not align"""
         c = Covariance()
@@ -928,6 +972,15 @@ class Batch:
         _check(load().ea_batch_eval(self._h, _dp(q), _dp(t), _dp(cost), _dp(JtJ), _dp(Jtr),
                                     bad.ctypes.data_as(C.POINTER(C.c_int64))))
         return dict(cost=cost, JtJ=JtJ, Jtr=Jtr, n_invalid=bad)
+
+    def residual_quantiles(self, q, t, probs):
+        """ea_batch_residual_quantiles at q (n, 4), t (n, 3): (values [n, len(probs)], n_valid [n]), one launch sequence"""
+        q, t, probs = _f64(q).reshape(-1, 4), _f64(t).reshape(-1, 3), _f64(probs).reshape(-1)
+        n = len(self)
+        values, m = np.zeros((n, probs.size)), np.zeros(n, dtype=np.int64)
+        _check(load().ea_batch_residual_quantiles(self._h, _dp(q), _dp(t), _dp(probs), probs.size, _dp(values),
+                                                  m.ctypes.data_as(C.POINTER(C.c_int64))))
+        return values, m
 
     def covariance(self, q, t, **opts):
         """ea_batch_covariance: one covariance per problem at q (n, 4), t (n, 3) -> list of covariance_to_dict"""
@@ -1192,3 +1245,15 @@ def selftest_wave_reduce(values, device=0):
     _check(load().ea_selftest_wave_reduce(device, v.ctypes.data_as(C.POINTER(C.c_float)), _dp(o32), _dp(o64),
                                           st.ctypes.data_as(C.POINTER(C.c_float))))
     return o32, o64, st
+
+
+def selftest_select(values, offsets, probs, device=0):
+    """the select kernels on caller-supplied doubles: segment s = values[offsets[s]:offsets[s + 1]], NaN = failed block,
+    everything else by absolute value -> (out [nseg, len(probs)], n_valid [nseg])"""
+    v, probs = _f64(values).reshape(-1), _f64(probs).reshape(-1)
+    off = np.ascontiguousarray(offsets, dtype=np.int64)
+    nseg = off.size - 1
+    out, m = np.zeros((nseg, probs.size)), np.zeros(nseg, dtype=np.int64)
+    _check(load().ea_selftest_select(device, _dp(v), off.ctypes.data_as(C.POINTER(C.c_int64)), nseg, _dp(probs), probs.size,
+                                     _dp(out), m.ctypes.data_as(C.POINTER(C.c_int64))))
+    return out, m

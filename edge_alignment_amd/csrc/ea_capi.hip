@@ -629,6 +629,8 @@ extern "C" int ea_problem_add_term(ea_problem *p, ea_problem *term) {
     return fail(EA_ERR_INVALID_ARG, "a problem with a normal prior cannot be a term (the prior belongs on the head problem)");
   if (term->held)
     return fail(EA_ERR_INVALID_ARG, "a problem with constant parameters cannot be a term (the mask belongs on the head problem)");
+  if (p->auto_factor > 0.0 || term->auto_factor > 0.0)
+    return fail(EA_ERR_INVALID_ARG, "a problem with an auto-scaled loss cannot take terms or be one (ea_problem_set_loss_auto_scale)");
   p->terms.push_back(term);
   term->term_of++;
   p->version++;
@@ -971,6 +973,34 @@ extern "C" int ea_problem_set_loss(ea_problem *p, int kind, double a) {
   p->loss_kind = kind;
   p->loss_a = a;
   p->version++;
+  return EA_OK;
+}
+
+extern "C" int ea_problem_get_loss(const ea_problem *p, int *kind, double *a) {
+  if (!p) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (kind) *kind = p->loss_kind;
+  if (a) *a = p->loss_a;
+  return EA_OK;
+}
+
+// A loss scale taken from the data at the start of every solve (ea_batch_solve: auto_scale_losses); the arguments are
+// checked first, the problem last: every check here needs no device
+extern "C" int ea_problem_set_loss_auto_scale(ea_problem *p, double factor, double prob, double a_min) {
+  if (!(std::fabs(factor) <= DBL_MAX) || factor < 0.0) return fail(EA_ERR_INVALID_ARG, "factor must be finite and >= 0 (0 = off)");
+  if (!select_prob_ok(prob)) return fail(EA_ERR_INVALID_ARG, "prob must be in [0, 1]");
+  if (!(a_min > 0.0) || !(a_min <= DBL_MAX)) return fail(EA_ERR_INVALID_ARG, "a_min must be finite and > 0");
+  if (!p) return fail(EA_ERR_INVALID_ARG, "NULL problem");
+  if (factor > 0.0 && (p->term_of > 0 || !p->terms.empty()))
+    return fail(EA_ERR_INVALID_ARG, "a problem that has terms or is a term cannot carry an auto-scaled loss");
+  p->auto_factor = factor; p->auto_prob = prob; p->auto_a_min = a_min;
+  return EA_OK;  // (no version bump: the descriptors do not change until a solve sets the loss)
+}
+
+extern "C" int ea_problem_get_loss_auto_scale(const ea_problem *p, double *factor, double *prob, double *a_min) {
+  if (!p) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (factor) *factor = p->auto_factor;
+  if (prob) *prob = p->auto_prob;
+  if (a_min) *a_min = p->auto_a_min;
   return EA_OK;
 }
 
@@ -2230,6 +2260,196 @@ static int solve_lookahead(SolveRun &r, const ea_options &o, Enqueue &enqueue_it
 
 // Sub-batches for the concurrent solve: contiguous slices of the parent's problems, each with its own stream and
 // buffers, created on first use and kept.
+// ---- exact order statistics of |r| (ea_select.h; kernels: ea_select_*_kernel) ------------------------------------------
+//
+// One launch sequence per call, whatever the number of problems: clear, key pass, six (histogram, scan) pairs -- 14 launches --
+// on the batch's stream, the bin choice staying on the device between the passes; segments and probabilities go up, values and
+// valid counts come back through one pinned block, ONE synchronisation at the end.
+namespace {
+struct SelectBuffers {
+  DevBuf dev;
+  unsigned char *pinned = nullptr;
+  SelectWork w;
+  double *d_input = nullptr;          // ea_selftest_select: the caller's values
+  size_t up_bytes = 0, down_off = 0, down_bytes = 0;  // pinned: [segs | probs || values | n_valid]; the device block starts alike
+  SelectSeg *h_segs = nullptr;
+  double *h_probs = nullptr, *h_values = nullptr;
+  int64_t *h_n_valid = nullptr;
+  ~SelectBuffers() { cached_host_free(pinned); }
+};
+size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
+}  // namespace
+
+static int select_reserve(SelectBuffers &s, int device, int nseg, int nq, int64_t total_keys, bool with_input) {
+  const size_t sq = (size_t)nseg * nq;
+  const size_t o_segs = 0, o_probs = o_segs + align16((size_t)nseg * sizeof(SelectSeg)), o_vals = o_probs + align16((size_t)nq * 8);
+  const size_t o_nv64 = o_vals + align16(sq * 8), o_prefix = o_nv64 + align16((size_t)nseg * 8), o_rank = o_prefix + align16(sq * 8);
+  const size_t o_nvalid = o_rank + align16(sq * 8), o_hist = o_nvalid + align16((size_t)nseg * 4);
+  const size_t o_keys = o_hist + sq * kSelectBins * sizeof(unsigned), o_input = o_keys + align16((size_t)total_keys * 8);
+  const size_t bytes = o_input + (with_input ? align16((size_t)total_keys * 8) : 0);
+  HIPCHK(cached_malloc(&s.dev.p, bytes, device));
+  HIPCHK(cached_host_malloc(reinterpret_cast<void **>(&s.pinned), o_prefix, hipHostMallocDefault, device));
+  unsigned char *d = s.dev.as<unsigned char>();
+  s.up_bytes = o_vals; s.down_off = o_vals; s.down_bytes = o_prefix - o_vals;
+  s.h_segs = reinterpret_cast<SelectSeg *>(s.pinned + o_segs);
+  s.h_probs = reinterpret_cast<double *>(s.pinned + o_probs);
+  s.h_values = reinterpret_cast<double *>(s.pinned + o_vals);
+  s.h_n_valid = reinterpret_cast<int64_t *>(s.pinned + o_nv64);
+  SelectWork &w = s.w;
+  w.nseg = nseg; w.nq = nq;
+  w.segs = reinterpret_cast<const SelectSeg *>(d + o_segs);
+  w.probs = reinterpret_cast<const double *>(d + o_probs);
+  w.out_values = reinterpret_cast<double *>(d + o_vals);
+  w.out_n_valid = reinterpret_cast<int64_t *>(d + o_nv64);
+  w.prefix = reinterpret_cast<uint64_t *>(d + o_prefix);
+  w.rank = reinterpret_cast<int64_t *>(d + o_rank);
+  w.n_valid = reinterpret_cast<unsigned *>(d + o_nvalid);
+  w.hist = reinterpret_cast<unsigned *>(d + o_hist);
+  w.clear_bytes = o_keys - o_nvalid;
+  w.keys = reinterpret_cast<uint64_t *>(d + o_keys);
+  s.d_input = with_input ? reinterpret_cast<double *>(d + o_input) : nullptr;
+  return EA_OK;
+}
+
+// segments and probabilities up, the counts cleared: what comes before either key pass
+static int select_begin(SelectBuffers &s, const double *probs, hipStream_t stream) {
+  int max_n = 0;
+  for (int i = 0; i < s.w.nseg; ++i) max_n = std::max(max_n, (int)s.h_segs[i].n);
+  s.w.max_n = max_n;
+  for (int i = 0; i < s.w.nq; ++i) s.h_probs[i] = probs[i];
+  HIPCHK(hipMemcpyAsync(s.dev.p, s.pinned, s.up_bytes, hipMemcpyHostToDevice, stream));
+  HIPCHK(launch_select_clear(s.w, stream));
+  return EA_OK;
+}
+
+// the six passes, the results down, the call's one synchronisation
+static int select_finish(SelectBuffers &s, hipStream_t stream, double *values, int64_t *n_valid) {
+  HIPCHK(launch_select(s.w, stream));
+  HIPCHK(hipMemcpyAsync(s.pinned + s.down_off, s.dev.as<unsigned char>() + s.down_off, s.down_bytes, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  std::memcpy(values, s.h_values, (size_t)s.w.nseg * s.w.nq * sizeof(double));
+  if (n_valid) std::memcpy(n_valid, s.h_n_valid, (size_t)s.w.nseg * sizeof(int64_t));
+  return EA_OK;
+}
+
+static int check_quantile_args(const double *probs, int nq) {
+  if (!probs) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (nq < 1 || nq > kSelectMaxQ) return fail(EA_ERR_INVALID_ARG, "nq must be in 1..16");
+  for (int i = 0; i < nq; ++i)
+    if (!select_prob_ok(probs[i])) return fail(EA_ERR_INVALID_ARG, "every prob must be in [0, 1]");
+  return EA_OK;
+}
+
+// the quantiles of the head families of problems sel[0 .. nsel) (sel == NULL: all of them) at the batch's poses q, t
+// (count x 4, count x 3: the poses of ALL problems of the batch); values: nsel x nq, n_valid: nsel or NULL
+static int batch_quantiles(ea_batch *b, const double *q, const double *t, const int *sel, int nsel, const double *probs, int nq,
+                           double *values, int64_t *n_valid) {
+  int rc = batch_build(b);
+  if (rc != EA_OK) return rc;
+  if (nsel > 65535) return fail(EA_ERR_INVALID_ARG, "more than 65535 problems in one quantile call");
+  SelectBuffers s;
+  if ((rc = select_reserve(s, b->device, nsel, nq, b->total_rows, false)) != EA_OK) return rc;
+  // (batch_build's staging block: the descriptors and groups of the current build)
+  const ProblemDesc *hd = reinterpret_cast<const ProblemDesc *>(b->h_desc);
+  const GroupDesc *hg = reinterpret_cast<const GroupDesc *>(b->h_desc + (size_t)b->nterms * sizeof(ProblemDesc));
+  for (int j = 0; j < nsel; ++j) {
+    const int term = hg[sel ? sel[j] : j].term_begin;  // the head family; its terms are not included
+    s.h_segs[j] = SelectSeg{hd[term].row_begin, hd[term].n, term};
+  }
+  if ((rc = select_begin(s, probs, b->stream)) != EA_OK) return rc;
+  if ((rc = batch_upload_poses(b, q, t)) != EA_OK) return rc;  // (d_poses: the resident poses of ea_batch_set_poses live elsewhere)
+  HIPCHK(launch_select_keys(b->dtype, s.w, b->d_probs, b->d_poses, b->stream));
+  return select_finish(s, b->stream, values, n_valid);
+}
+
+static int require_device();
+extern "C" int ea_batch_residual_quantiles(ea_batch *b, const double *q, const double *t, const double *probs, int nq,
+                                           double *values, int64_t *n_valid) {
+  if (!b || !q || !t || !values) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  int rc = check_quantile_args(probs, nq);
+  if (rc == EA_OK) rc = require_device();
+  if (rc != EA_OK) return rc;
+  return batch_quantiles(b, q, t, nullptr, (int)b->probs.size(), probs, nq, values, n_valid);
+}
+
+static int self_batch(ea_problem *p, ea_batch **out);
+extern "C" int ea_problem_residual_quantiles(ea_problem *p, const double q[4], const double t[3], const double *probs, int nq,
+                                             double *values, int64_t *n_valid) {
+  if (!p || !q || !t || !values) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  int rc = check_quantile_args(probs, nq);
+  if (rc == EA_OK) rc = require_device();
+  if (rc != EA_OK) return rc;
+  ea_batch *b;
+  if ((rc = self_batch(p, &b)) != EA_OK) return rc;
+  if ((rc = batch_build(b)) != EA_OK) return rc;  // (no DT image: EA_ERR_STATE, as ea_eval)
+  if (p->n == 0) return fail(EA_ERR_STATE, "no edge points (ea_problem_set_points)");
+  return batch_quantiles(b, q, t, nullptr, 1, probs, nq, values, n_valid);
+}
+
+// the select kernels alone, on the caller's values
+extern "C" int ea_selftest_select(int device, const double *values, const int64_t *offsets, int nseg, const double *probs, int nq,
+                                  double *out, int64_t *n_valid) {
+  if (!offsets || !out || nseg < 1 || nseg > 65535) return fail(EA_ERR_INVALID_ARG, "bad argument");
+  int rc = check_quantile_args(probs, nq);
+  if (rc != EA_OK) return rc;
+  if (offsets[0] < 0) return fail(EA_ERR_INVALID_ARG, "offsets must start at >= 0 and not decrease");
+  for (int i = 0; i < nseg; ++i)
+    if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > 0x7fffff00LL)
+      return fail(EA_ERR_INVALID_ARG, "offsets must not decrease (at most 2^31 values per segment)");
+  const int64_t total = offsets[nseg];
+  if (total > 0 && !values) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if ((rc = check_device(device)) != EA_OK) return rc;
+  HIPCHK(hipSetDevice(device));
+  SelectBuffers s;
+  if ((rc = select_reserve(s, device, nseg, nq, total, true)) != EA_OK) return rc;
+  for (int i = 0; i < nseg; ++i) s.h_segs[i] = SelectSeg{offsets[i], (int32_t)(offsets[i + 1] - offsets[i]), 0};
+  hipStream_t stream = nullptr;
+  HIPCHK(cached_stream_create(&stream, device));
+  rc = select_begin(s, probs, stream);
+  hipError_t e = hipSuccess;
+  if (rc == EA_OK && total > 0) e = hipMemcpyAsync(s.d_input, values, (size_t)total * sizeof(double), hipMemcpyHostToDevice, stream);
+  if (rc == EA_OK && e == hipSuccess) e = launch_select_keys_values(s.w, s.d_input, stream);
+  if (rc == EA_OK && e == hipSuccess) rc = select_finish(s, stream, out, n_valid);
+  (void)hipStreamSynchronize(stream);
+  cached_stream_destroy(stream, device);
+  if (e != hipSuccess) return fail(EA_ERR_HIP, hipGetErrorString(e));
+  return rc;
+}
+
+// Auto-scaled losses (ea_problem_set_loss_auto_scale): ONE quantile call over the auto-scaled problems of the batch at their
+// start poses, then, per problem, what the caller could have done by hand: ea_problem_set_loss(kind, max(a_min, factor * Q)).
+// The trivial loss is left alone; a problem without a valid block (or a product that is not finite) keeps its scale.
+static int auto_scale_losses(ea_batch *b, const double *q, const double *t) {
+  std::vector<double> probs;
+  for (const ea_problem *p : b->probs)
+    if (p->auto_factor > 0.0 && p->loss_kind != EA_LOSS_TRIVIAL && std::find(probs.begin(), probs.end(), p->auto_prob) == probs.end())
+      probs.push_back(p->auto_prob);
+  // (problems may ask for different probabilities: up to 16 of them share a call)
+  for (size_t first = 0; first < probs.size(); first += kSelectMaxQ) {
+    const int nq = (int)std::min<size_t>(kSelectMaxQ, probs.size() - first);
+    std::vector<int> sel, which;
+    for (size_t i = 0; i < b->probs.size(); ++i) {
+      const ea_problem *p = b->probs[i];
+      if (!(p->auto_factor > 0.0) || p->loss_kind == EA_LOSS_TRIVIAL) continue;
+      const size_t at = (size_t)(std::find(probs.begin(), probs.end(), p->auto_prob) - probs.begin());
+      if (at >= first && at < first + (size_t)nq) { sel.push_back((int)i); which.push_back((int)(at - first)); }
+    }
+    std::vector<double> values(sel.size() * (size_t)nq);
+    std::vector<int64_t> m(sel.size());
+    int rc = require_device();
+    if (rc == EA_OK) rc = batch_quantiles(b, q, t, sel.data(), (int)sel.size(), probs.data() + first, nq, values.data(), m.data());
+    if (rc != EA_OK) return rc;
+    for (size_t j = 0; j < sel.size(); ++j) {
+      ea_problem *p = b->probs[(size_t)sel[j]];
+      if (m[j] <= 0) continue;
+      const double a = select_loss_scale(p->auto_factor, values[j * (size_t)nq + (size_t)which[j]], p->auto_a_min);
+      if (!(a <= DBL_MAX) || a == p->loss_a) continue;
+      if ((rc = ea_problem_set_loss(p, p->loss_kind, a)) != EA_OK) return rc;
+    }
+  }
+  return EA_OK;
+}
+
 static int batch_parts(ea_batch *b, int parts) {
   if ((int)b->parts.size() == parts) return EA_OK;
   for (ea_batch *c : b->parts) ea_batch_destroy(c);
@@ -2245,12 +2465,15 @@ static int batch_parts(ea_batch *b, int parts) {
   return EA_OK;
 }
 
-extern "C" int ea_batch_solve(ea_batch *b, const ea_options *opt_in, double *q, double *t, ea_summary *summaries) {
+// auto_scale: the public call; 0 for the multi-start fall-back, whose starts run with the problem's current loss
+static int batch_solve(ea_batch *b, const ea_options *opt_in, double *q, double *t, ea_summary *summaries, bool auto_scale) {
   if (!b || !q || !t) return fail(EA_ERR_INVALID_ARG, "NULL argument");
   static_assert(EA_MAX_TRACE == kTrace, "trace length mismatch");
   const auto t0 = std::chrono::steady_clock::now();
   ea_options o;
   if (int vrc = resolve_options(opt_in, &o)) return vrc;
+  if (auto_scale)
+    if (int arc = auto_scale_losses(b, q, t)) return arc;
   const LMOptions lo = lm_options(o);
   const int count = (int)b->probs.size();
   // Concurrent halves: a batch of many problems is solved as two sub-batches on two streams, pumped by this one
@@ -2315,6 +2538,10 @@ extern "C" int ea_batch_solve(ea_batch *b, const ea_options *opt_in, double *q, 
     }
   }
   return solve_finish(runs.data(), runs.size(), o, t0, q, t, summaries);
+}
+
+extern "C" int ea_batch_solve(ea_batch *b, const ea_options *opt_in, double *q, double *t, ea_summary *summaries) {
+  return batch_solve(b, opt_in, q, t, summaries, true);
 }
 
 extern "C" int ea_batch_bench_eval(ea_batch *b, const double *q, const double *t, int warmup, int steps,
@@ -3156,7 +3383,7 @@ static int starts_fallback(ea_batch *b, int K, const ea_options *opt, double *q,
   std::vector<double> cost((size_t)K * count, 0.0);
   for (int k = 0; k < K; ++k) {
     ea_summary *sm = summaries ? summaries + (size_t)k * count : (best ? own.data() : nullptr);
-    const int rc = ea_batch_solve(b, opt, q + (size_t)k * count * 4, t + (size_t)k * count * 3, sm);
+    const int rc = batch_solve(b, opt, q + (size_t)k * count * 4, t + (size_t)k * count * 3, sm, false);
     if (rc != EA_OK) return rc;
     if (sm)
       for (int i = 0; i < count; ++i) { termination[(size_t)k * count + i] = sm[i].termination; cost[(size_t)k * count + i] = sm[i].final_cost; }

@@ -30,6 +30,9 @@ struct ea_problem {
   ea::PriorDesc prior = {};                  // NormalPriors on q / t (ea_problem_set_normal_prior; ea_prior.h)
   int term_of = 0;                       // how many problems hold this one as a term (a term carries no prior)
   int held = 0;                          // tangent coordinates held constant, bit i of [delta | t] (ea_problem_set_constant_parameters)
+  // ea_problem_set_loss_auto_scale: factor > 0 = every ea_batch_solve first sets loss_a = max(a_min, factor * Q_prob(|r|)) at
+  // the start pose; like `held` it is a setting of the problem, not of its points or image, and no producer touches it
+  double auto_factor = 0.0, auto_prob = 0.5, auto_a_min = 1e-6;
   int64_t n = 0;
   void *d_x = nullptr, *d_y = nullptr, *d_z = nullptr;
   bool own_points = false;

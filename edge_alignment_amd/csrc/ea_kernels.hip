@@ -43,6 +43,7 @@ extern __device__ int g_lm_probe_row;
 #include "ea_starts_map.h"
 #include "ea_lm.h"
 #include "ea_prior.h"
+#include "ea_select.h"
 #include "ea_types.h"
 #include "ea_wave_exchange.h"
 
@@ -2685,6 +2686,167 @@ __global__ __launch_bounds__(256) void ea_depth_weights_kernel(const T *__restri
   for (int k = 1; k < power; ++k) v = __dmul_rn(v, ratio);
   w[i] = (T)fmax(0.0, fmin(1.0, v));
 }
+
+// ------------------------------------------------------------------------------------------------
+// Exact order statistics of |r| per residual family (ea_batch_residual_quantiles; the rules are in ea_select.h).
+//
+// Key pass: one lane per point of every selected family -- the projection, the four row loads and the VALUE of the bicubic
+// patch (bicubic_value: the cost kernel's sample), no Jacobian row, no loss, no weight -- and |r| widened to double goes into
+// the key array as its bit pattern; a failed functor leaves the all-ones key.  The plain projection serves plain and weighted
+// terms (the weights do not enter, so they must not change a bit), project_point_var the distortion / second-camera functors.
+// The valid blocks are not counted here: the first pass's histogram holds the count (select_valid_count) -- one integer atomic
+// per wavefront on a segment's counter serialised the whole launch on one cache line (32 x 5e4 points: 224 us against 25).
+template <typename T>
+__global__ __launch_bounds__(kSelectThreads) void ea_select_keys_kernel(
+    const ProblemDesc *__restrict__ probs, const SelectSeg *__restrict__ segs, const PoseState *__restrict__ poses,
+    uint64_t *__restrict__ keys) {
+  const SelectSeg sg = segs[blockIdx.y];
+  const int first = blockIdx.x * kSelectThreads;
+  if (first >= sg.n) return;  // (uniform)
+  const ProblemDesc &pd = probs[sg.term];
+  const PoseState &ps = poses[pd.group];
+  const int i = first + threadIdx.x;
+  if (i < sg.n) {
+    bool ok;
+    const T x = static_cast<const T *>(pd.x)[i], y = static_cast<const T *>(pd.y)[i], z = static_cast<const T *>(pd.z)[i];
+    T fu, fv;
+    int iu, iv;
+    if (pd.variant & 3) {
+      ProjV<T> pv;
+      project_point_var<T>(pd, ps, x, y, z, pv);
+      fu = pv.fu; fv = pv.fv; iu = pv.iu; iv = pv.iv; ok = pv.state == 1;
+    } else {
+      Proj<T> pr;
+      project_point<T>(pd, ps, x, y, z, pr);
+      fu = pr.fu; fv = pr.fv; iu = pr.iu; iv = pr.iv; ok = pr.state == 1;
+    }
+    uint64_t key = kSelectFailedKey;
+    if (ok) {
+      // (iu, iv are saturated to [-2, W] x [-2, H]: every tap lies inside the padded image)
+      const int pitch = pd.pitch;
+      const T *base = static_cast<const T *>(pd.dt) + (size_t)kImagePad * (size_t)pitch + kImagePad + (ptrdiff_t)(iv - 1) * pitch + (iu - 1);
+      const T f = bicubic_value<T>(fu, fv, [&](int l) { return *reinterpret_cast<const Row4<T> *>(base + (ptrdiff_t)l * pitch); });
+      key = select_key_abs((double)f);
+    }
+    keys[sg.begin + i] = key;
+  }
+}
+
+// the key pass of ea_selftest_select: caller-supplied doubles, NaN = failed block
+__global__ __launch_bounds__(kSelectThreads) void ea_select_keys_values_kernel(
+    const double *__restrict__ values, const SelectSeg *__restrict__ segs, uint64_t *__restrict__ keys) {
+  const SelectSeg sg = segs[blockIdx.y];
+  const int first = blockIdx.x * kSelectThreads;
+  if (first >= sg.n) return;  // (uniform)
+  const int i = first + threadIdx.x;
+  if (i < sg.n) keys[sg.begin + i] = select_key(values[sg.begin + i]);
+}
+
+// Histogram pass: a workgroup holds kSelectChunk keys of one segment in registers and, for every quantile that leads a group
+// of equal prefixes, counts the keys that agree with the prefix by their digit of this pass -- integer LDS atomics -- and adds
+// the bins it touched to the (segment, quantile) histogram with integer atomics: the sums do not depend on who arrives first.
+__global__ __launch_bounds__(kSelectThreads) void ea_select_hist_kernel(
+    const uint64_t *__restrict__ keys, const SelectSeg *__restrict__ segs, const uint64_t *__restrict__ prefix, int nq, int pass,
+    unsigned *__restrict__ hist) {
+  __shared__ unsigned s_hist[kSelectBins];
+  static_assert(kSelectBins == kSelectChunk, "a lane owns as many bins as keys");
+  const int seg = blockIdx.y, tid = threadIdx.x;
+  const SelectSeg sg = segs[seg];
+  const int first = blockIdx.x * kSelectChunk;
+  if (first >= sg.n) return;  // (uniform)
+  uint64_t k[kSelectKeysPerLane];
+  unsigned have = 0;
+#pragma unroll
+  for (int j = 0; j < kSelectKeysPerLane; ++j) {
+    const int idx = first + j * kSelectThreads + tid;
+    const bool in = idx < sg.n;
+    k[j] = in ? keys[sg.begin + idx] : kSelectFailedKey;
+    have |= in ? 1u << j : 0u;
+  }
+  const uint64_t *pf = prefix + (size_t)seg * nq;
+  for (int q = 0; q < nq; ++q) {
+    if (select_leader(pf, q, pass) != q) continue;  // (uniform)
+    const uint64_t want = pf[q];
+#pragma unroll
+    for (int j = 0; j < kSelectKeysPerLane; ++j) s_hist[j * kSelectThreads + tid] = 0;
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < kSelectKeysPerLane; ++j)
+      if (((have >> j) & 1u) && select_matches(k[j], want, pass)) atomicAdd(&s_hist[select_digit(k[j], pass)], 1u);
+    __syncthreads();
+    unsigned *h = hist + ((size_t)seg * nq + q) * kSelectBins;
+#pragma unroll
+    for (int j = 0; j < kSelectKeysPerLane; ++j) {
+      const unsigned c = s_hist[j * kSelectThreads + tid];
+      if (c) atomicAdd(&h[j * kSelectThreads + tid], c);
+    }
+    __syncthreads();
+  }
+}
+
+// Scan: one workgroup per segment.  Per quantile the 2048 bins of its leader's histogram are summed 8 to a lane and 16 lanes
+// to a group, and lane 0 walks 16 groups, 16 lanes, 8 bins (select_scan) to the bin that holds the rank; the prefix takes the
+// digit, the rank becomes the rank inside the bin.  Pass 0 reads the number of valid blocks off its histogram (every quantile
+// shares it then: the keys with the top bit clear), keeps it in n_valid and turns the probabilities into ranks; the last pass
+// writes the values.  The histograms are left zeroed for the next pass.
+__global__ __launch_bounds__(kSelectThreads) void ea_select_scan_kernel(
+    const double *__restrict__ probs, int nq, int pass, unsigned *__restrict__ n_valid, uint64_t *prefix, int64_t *rank,
+    unsigned *hist, double *__restrict__ out_values, int64_t *__restrict__ out_n_valid) {
+  __shared__ unsigned s1[kSelectThreads];
+  __shared__ unsigned s2[16];
+  __shared__ int s_leader[kSelectMaxQ];
+  __shared__ uint64_t s_old[kSelectMaxQ];
+  static_assert(kSelectBins == 8 * kSelectThreads && kSelectThreads == 16 * 16, "8 bins a lane, 16 lanes a group, 16 groups");
+  const int seg = blockIdx.x, tid = threadIdx.x;
+  uint64_t *pf = prefix + (size_t)seg * nq;
+  int64_t *rk = rank + (size_t)seg * nq;
+  int64_t m = pass == 0 ? 0 : (int64_t)n_valid[seg];  // (lane 0's alone from here on)
+  if (tid < nq) {
+    s_leader[tid] = select_leader(pf, tid, pass);
+    s_old[tid] = pass == 0 ? 0 : pf[tid];
+  }
+  __syncthreads();
+  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+  for (int q = 0; q < nq; ++q) {
+    const unsigned *h = hist + ((size_t)seg * nq + s_leader[q]) * kSelectBins;
+    const u32x4 a = reinterpret_cast<const u32x4 *>(h)[2 * tid], b = reinterpret_cast<const u32x4 *>(h)[2 * tid + 1];
+    s1[tid] = a.x + a.y + a.z + a.w + b.x + b.y + b.z + b.w;
+    __syncthreads();
+    if (tid < 16) {
+      unsigned s = 0;
+#pragma unroll
+      for (int j = 0; j < 16; ++j) s += s1[16 * tid + j];
+      s2[tid] = s;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      if (pass == 0) {
+        m = select_valid_count(s2);
+        if (q == 0) n_valid[seg] = (unsigned)m;
+      }
+      int64_t r = pass == 0 ? select_rank(probs[q], m) : rk[q];
+      const int i2 = select_scan(s2, 16, r, &r);
+      const int i1 = select_scan(s1 + 16 * i2, 16, r, &r);
+      const int lane = 16 * i2 + i1;
+      const int bin = 8 * lane + select_scan(h + 8 * lane, 8, r, &r);
+      const uint64_t key = select_extend(s_old[q], pass, (unsigned)bin);
+      pf[q] = key;
+      rk[q] = r;
+      if (pass == kSelectPasses - 1) {
+        out_values[(size_t)seg * nq + q] = m > 0 ? select_value(key) : __builtin_nan("");
+        if (q == 0) out_n_valid[seg] = m;
+      }
+    }
+    __syncthreads();
+  }
+  for (int q = 0; q < nq; ++q) {
+    if (s_leader[q] != q) continue;
+    u32x4 *h = reinterpret_cast<u32x4 *>(hist + ((size_t)seg * nq + q) * kSelectBins);
+    const u32x4 zero = {0u, 0u, 0u, 0u};
+    h[2 * tid] = zero;
+    h[2 * tid + 1] = zero;
+  }
+}
 #endif  // !EA_TU_VARIANT
 
 // ------------------------------------------------------------------------------------------------
@@ -3108,6 +3270,44 @@ hipError_t launch_depth_weights(int dtype, const void *z, long long n, double z_
   if (dtype == 1) hipLaunchKernelGGL((ea_depth_weights_kernel<float>), grid, dim3(256), 0, stream, (const float *)z, n, z_ref, power, (float *)w);
   else hipLaunchKernelGGL((ea_depth_weights_kernel<double>), grid, dim3(256), 0, stream, (const double *)z, n, z_ref, power, (double *)w);
   return hipGetLastError();
+}
+
+// the select kernels' launches: x = chunks of the longest segment, y = segments
+static hipError_t select_grid(const SelectWork &w, int per_workgroup, dim3 *grid) {
+  if (w.nseg < 1 || w.nseg > 65535 || w.nq < 1 || w.nq > kSelectMaxQ || w.max_n < 0) return hipErrorInvalidValue;
+  const int64_t chunks = ((int64_t)w.max_n + per_workgroup - 1) / per_workgroup;
+  *grid = dim3((unsigned)(chunks > 0 ? chunks : 1), (unsigned)w.nseg);
+  return hipSuccess;
+}
+hipError_t launch_select_clear(const SelectWork &w, hipStream_t stream) {
+  // (n_valid and the histograms are one range: SelectWork)
+  return hipMemsetAsync(w.n_valid, 0, w.clear_bytes, stream);
+}
+hipError_t launch_select_keys(int dtype, const SelectWork &w, const ProblemDesc *probs, const PoseState *poses, hipStream_t stream) {
+  dim3 grid;
+  if (hipError_t e = select_grid(w, kSelectThreads, &grid)) return e;
+  if (w.max_n == 0) return hipSuccess;
+  if (dtype == 1) hipLaunchKernelGGL((ea_select_keys_kernel<float>), grid, dim3(kSelectThreads), 0, stream, probs, w.segs, poses, w.keys);
+  else hipLaunchKernelGGL((ea_select_keys_kernel<double>), grid, dim3(kSelectThreads), 0, stream, probs, w.segs, poses, w.keys);
+  return hipGetLastError();
+}
+hipError_t launch_select_keys_values(const SelectWork &w, const double *values, hipStream_t stream) {
+  dim3 grid;
+  if (hipError_t e = select_grid(w, kSelectThreads, &grid)) return e;
+  if (w.max_n == 0) return hipSuccess;
+  hipLaunchKernelGGL(ea_select_keys_values_kernel, grid, dim3(kSelectThreads), 0, stream, values, w.segs, w.keys);
+  return hipGetLastError();
+}
+hipError_t launch_select(const SelectWork &w, hipStream_t stream) {
+  dim3 grid;
+  if (hipError_t e = select_grid(w, kSelectChunk, &grid)) return e;
+  for (int pass = 0; pass < kSelectPasses; ++pass) {
+    if (w.max_n > 0) hipLaunchKernelGGL(ea_select_hist_kernel, grid, dim3(kSelectThreads), 0, stream, w.keys, w.segs, w.prefix, w.nq, pass, w.hist);
+    hipLaunchKernelGGL(ea_select_scan_kernel, dim3((unsigned)w.nseg), dim3(kSelectThreads), 0, stream, w.probs, w.nq, pass, w.n_valid,
+                       w.prefix, w.rank, w.hist, w.out_values, w.out_n_valid);
+    if (hipError_t e = hipGetLastError()) return e;
+  }
+  return hipSuccess;
 }
 
 hipError_t launch_grid_to_image(int dtype, const double *grid, int W, int H, void *dst, int pitch, float *dst32, int *inexact,

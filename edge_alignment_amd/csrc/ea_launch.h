@@ -11,6 +11,7 @@
 
 #include "../../include/ea_hip.h"
 #include "ea_lm.h"
+#include "ea_select.h"
 #include "ea_types.h"
 
 namespace ea {
@@ -84,6 +85,21 @@ struct StartsStep {
   int count, rows_per_pose, off, last;
   unsigned iteration, tag;
 };
+// The device workspace of one quantile call (ea_select.h): nseg segments of the key array, nq quantiles each, max_n = the
+// longest segment.  n_valid and hist are ONE range of clear_bytes bytes ([n_valid x nseg, padded | hist]) zeroed up front;
+// prefix / rank: nseg x nq, written by the scans; out_values: nseg x nq, out_n_valid: nseg.
+struct SelectWork {
+  int nseg = 0, nq = 0, max_n = 0;
+  const SelectSeg *segs = nullptr;
+  const double *probs = nullptr;
+  uint64_t *keys = nullptr;
+  unsigned *n_valid = nullptr, *hist = nullptr;
+  size_t clear_bytes = 0;
+  uint64_t *prefix = nullptr;
+  int64_t *rank = nullptr;
+  double *out_values = nullptr;
+  int64_t *out_n_valid = nullptr;
+};
 struct RowsLaunch {
   int dtype = 0, variant = 0, buffer_loads = 0, img32 = 0;
   int layout = 0;   // 0 = J row-major [rows][6], 1 = column-major [6][rows]
@@ -146,6 +162,13 @@ hipError_t launch_aos_to_soa(int dtype, const double *src, long long n, int stri
 hipError_t launch_store_weights(int dtype, int src_is_double, const void *src, const int32_t *order, long long n, void *dst,
                                 hipStream_t stream);
 hipError_t launch_depth_weights(int dtype, const void *z, long long n, double z_ref, int power, void *w, hipStream_t stream);
+// ea_select_*_kernel (ea_select.h): launch_select_clear zeroes the counts, one of the two key passes fills w.keys,
+// launch_select queues the six (histogram, scan) pairs; the first scan counts the valid blocks, the last writes out_values /
+// out_n_valid
+hipError_t launch_select_clear(const SelectWork &w, hipStream_t stream);
+hipError_t launch_select_keys(int dtype, const SelectWork &w, const ProblemDesc *probs, const PoseState *poses, hipStream_t stream);
+hipError_t launch_select_keys_values(const SelectWork &w, const double *values, hipStream_t stream);
+hipError_t launch_select(const SelectWork &w, hipStream_t stream);
 hipError_t launch_selftest_reduce(const float *in, float *a, float *b, float *c, float *d, double *o32, double *o64,
                                   hipStream_t stream);
 // ea_kernels_var.hip (the same file under -DEA_TU_VARIANT): what launch_eval_fused (tag 0) / launch_eval_poses_grid (tag 1) hand on

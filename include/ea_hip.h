@@ -171,6 +171,29 @@ int ea_problem_set_dt_image_device(ea_problem *p, const void *image, int height,
 
 /* loss_function argument of AddResidualBlock (:272 `new CauchyLoss(1.)`) */
 int ea_problem_set_loss(ea_problem *p, int loss_kind, double a);
+/* the loss the problem holds now (either output may be NULL); after a solve of an auto-scaled problem: the scale it used */
+int ea_problem_get_loss(const ea_problem *p, int *kind, double *a);
+/* Loss scale from the data.  The reference hard-codes CauchyLoss(1.) while its producers emit distance transforms in [0, 1],
+ * in [0, 255] or not normalised at all, so the same a means three different things; the usual remedy is a robust statistic of
+ * the residuals at the start pose, e.g. sigma = 1.4826 median|r| with Huber at 1.345 sigma (factor 1.994) or Cauchy at
+ * 2.385 sigma (factor 3.536).  factor > 0 switches it on: ea_batch_solve -- which is also the solver behind ea_solve, every
+ * level of ea_solve_pyramid and ea_tracker_push_frame -- starts with ONE ea_batch_residual_quantiles over the auto-scaled
+ * problems of the batch at their start poses and then does, per problem, exactly what the caller could have done by hand:
+ *   a = max(a_min, factor * Q_prob)   (one IEEE multiplication)   and   ea_problem_set_loss(kind, a)  with the current kind;
+ * ea_problem_get_loss reports that a afterwards.  A problem without a valid block at the start pose keeps its a; the trivial
+ * loss is left alone.  Cost per solve: the quantile call's 14 launches and one extra synchronisation, and -- the loss having
+ * changed -- a rebuild and upload of the batch's descriptor table (resident poses of ea_batch_set_poses are dropped, as after
+ * any ea_problem_set_loss).
+ * factor finite and >= 0 (0 = off, the default: the loss stays where the last solve left it), prob in [0, 1], a_min finite
+ * and > 0: EA_ERR_INVALID_ARG otherwise, checked before the problem is looked at.  Stored on the problem; survives
+ * ea_problem_set_points, ea_problem_set_dt and the frame producers, so a setting made on ea_tracker_problem() holds for every
+ * push and one made on a pyramid level for that level.  Refused (EA_ERR_INVALID_ARG) on a problem that has terms or is a
+ * term, and ea_problem_add_term refuses an auto-scaled problem on either side.
+ * These do NOT re-estimate, they run with the problem's current a: ea_batch_solve_starts / ea_solve_starts /
+ * ea_*search_starts (a loss belongs to a problem, not to a start), the three sharded solves (each rank would estimate from
+ * its own shard and the ranks would diverge), and every evaluation and covariance call. */
+int ea_problem_set_loss_auto_scale(ea_problem *p, double factor, double prob, double a_min);
+int ea_problem_get_loss_auto_scale(const ea_problem *p, double *factor, double *prob, double *a_min);
 /* functor flavour: standalone (utils.h:48-80) = {z_guard 0.01, z_eps 0, rot_transposed 0}
  * [default]; ROS flavour (include/EAResidue.h:86-118) = {0, 0.001, 1} */
 int ea_problem_set_flavour(ea_problem *p, double z_guard, double z_eps, int rot_transposed);
@@ -257,6 +280,22 @@ typedef struct {
   int64_t count, outside;   /* points read / points projecting outside the image */
 } ea_pixel_cost;
 int ea_problem_pixel_cost(ea_problem *p, const double q[4], const double t[3], ea_pixel_cost *out);
+
+/* Exact order statistics of |r_i| at a pose, computed on the device (no per-point copy): the inlier fraction at a threshold,
+ * a "did this alignment land" test, the scale of a robust loss.  r_i is the raw residual of block i -- per-point weights, the
+ * loss and priors do not enter -- over the VALID blocks, those whose functor returns true at the pose (the rule n_invalid
+ * counts); m = their number, returned in *n_valid (nullable).  For prob in [0, 1]: k = floor(prob * (double)(m - 1)), one
+ * IEEE multiplication (numpy's method="lower"), and values[j] is the k-th smallest |r|, 0-based -- bit for bit an element of
+ * the multiset, never an interpolated value; prob = 0.5 with even m gives the lower median.  fp32 problems: r is the float
+ * the kernels compute, widened exactly.  m == 0: the values are NaN and *n_valid = 0, a result and not an error.
+ * 1 <= nq <= 16, every prob finite and in [0, 1]: EA_ERR_INVALID_ARG otherwise, before anything touches a device; a problem
+ * without points or DT image: EA_ERR_STATE, as ea_eval.  Order statistics of p's OWN residual family: its terms are not
+ * included (call it on a term); a batched problem that has terms reports its head family only.
+ * One key pass (projection, four row loads, the value of the bicubic patch) and a six-pass most-significant-digit-first radix
+ * select over 64-bit keys with integer counts: the same bits on every run.  One launch sequence (14 launches) serves a
+ * whole batch, queued on its stream; one synchronisation.  Resident poses (ea_batch_set_poses) survive the call. */
+int ea_problem_residual_quantiles(ea_problem *p, const double q[4], const double t[3], const double *probs, int nq,
+                                  double *values /* nq */, int64_t *n_valid);
 
 /* ceres::Solve(options, &problem, &summary) (standalone_edge_align.cpp:286; SolveEA.cpp:198).
  * q,t in/out.  The whole trust-region loop runs on the device. */
@@ -347,6 +386,10 @@ int ea_batch_eval(ea_batch *b, const double *q, const double *t, double *cost, d
                   double *Jtr, int64_t *n_invalid);
 int ea_batch_solve(ea_batch *b, const ea_options *opt, double *q, double *t,
                    ea_summary *summaries);
+/* q: count x 4, t: count x 3; values: count x nq; n_valid: count or NULL (ea_problem_residual_quantiles per problem, one
+ * launch sequence, one synchronisation; a problem without points gives NaN and 0) */
+int ea_batch_residual_quantiles(ea_batch *b, const double *q, const double *t, const double *probs, int nq,
+                                double *values, int64_t *n_valid);
 
 /* K evaluations of every problem of the batch at K DIFFERENT poses, one call -- what a caller that runs its own optimiser,
  * a line search, multi-start or a cost-surface probe asks of the evaluator: ceres::Problem::Evaluate once per pose (the
@@ -654,6 +697,11 @@ int ea_problem_get_dt(ea_problem *p, double *image, int *height, int *width);
  * wave totals from the fp32 and the fp64 reduction; stages (nullable, 30 x 64 floats) = the
  * intermediate levels of the fp32 reduction. */
 int ea_selftest_wave_reduce(int device, const float *in, double *out32, double *out64, float *stages);
+/* Self-test of the select kernels behind ea_*_residual_quantiles, on caller-supplied values: values = host doubles, segment s
+ * = [offsets[s], offsets[s+1]) (nseg + 1 offsets); NaN = a failed block, everything else enters by absolute value (+Inf is
+ * valid); out: nseg x nq, n_valid: nseg or NULL. */
+int ea_selftest_select(int device, const double *values, const int64_t *offsets, int nseg, const double *probs, int nq,
+                       double *out, int64_t *n_valid);
 
 #ifdef __cplusplus
 }
