@@ -42,6 +42,7 @@ extern __device__ int g_lm_probe_row;
 #include "ea_poses_map.h"
 #include "ea_starts_map.h"
 #include "ea_lm.h"
+#include "ea_pair_log.h"
 #include "ea_prior.h"
 #include "ea_select.h"
 #include "ea_types.h"
@@ -117,32 +118,24 @@ template <> __device__ __forceinline__ double t_rcp<double>(double x) {
 template <typename T> __device__ __forceinline__ T t_log(T x);
 // v_log_f32 is log2 and needs no denormal pre-scaling here: its only caller passes 1 + s / a^2 >= 1
 template <> __device__ __forceinline__ float t_log<float>(float x) { return __builtin_amdgcn_logf(x) * 0.6931471805599453f; }
-// fp64 log for the Cauchy loss, argument 1 + s / a^2 in [1, inf): frexp to m in [sqrt(1/2), sqrt(2)), then
-// log m = 2 atanh z, z = (m - 1) / (m + 1), |z| <= 0.1716, as the odd series to z^21 (next term < 1e-18 relative).
-// ~33 instructions and ~2 ulp, against ~110 for libm's log (which was a fifth of the fp64 kernel's vector work).
-template <> __device__ __forceinline__ double t_log<double>(double x) {
-  double m = __builtin_amdgcn_frexp_mant(x);  // [0.5, 1)
-  int e = __builtin_amdgcn_frexp_exp(x);
-  const bool lo = m < 0.70710678118654752440;
-  m = __builtin_amdgcn_ldexp(m, lo ? 1 : 0);
-  e -= lo ? 1 : 0;
-  const double z = (m - 1.0) * t_rcp<double>(m + 1.0);
-  const double z2 = z * z;
-  double p = 2.0 / 21.0;
-  p = __builtin_fma(p, z2, 2.0 / 19.0);
-  p = __builtin_fma(p, z2, 2.0 / 17.0);
-  p = __builtin_fma(p, z2, 2.0 / 15.0);
-  p = __builtin_fma(p, z2, 2.0 / 13.0);
-  p = __builtin_fma(p, z2, 2.0 / 11.0);
-  p = __builtin_fma(p, z2, 2.0 / 9.0);
-  p = __builtin_fma(p, z2, 2.0 / 7.0);
-  p = __builtin_fma(p, z2, 2.0 / 5.0);
-  p = __builtin_fma(p, z2, 2.0 / 3.0);
-  const double lm = __builtin_fma(z * z2, p, z + z);
-  const double ef = (double)e;
-  // ln 2 split so that e * hi is exact for |e| < 2^11
-  return __builtin_fma(ef, 0.693147180369123816490, __builtin_fma(ef, 1.90821492927058770002e-10, lm));
-}
+
+// A floating-point literal as a scalar-register operand.  VOP3 takes no 64-bit literal on gfx950: left alone, the compiler
+// rebuilds such a constant in a VGPR pair (two v_mov_b32) in front of every v_fma_f64 that uses it; through an "s" operand
+// it is two s_mov_b32 on the scalar port and the fma reads the pair directly.  (One scalar operand per VALU instruction:
+// where an expression has two literals, only one of them goes through here.)
+__device__ __forceinline__ double s_const(double c) { asm("" : "+s"(c)); return c; }
+__device__ __forceinline__ float s_const(float c) { return c; }  // (fp32 literals are operands already)
+
+// fp64 log for the Cauchy loss (ea_pair_log.h), argument 1 + s / a^2 in [1, inf): frexp to m in [sqrt(1/2), sqrt(2)), then
+// log m = 2 atanh z as the odd series to z^21.  ~33 instructions and ~2 ulp, against ~110 for libm's log.
+struct LogOps {
+  static __device__ __forceinline__ double frexp_mant(double x) { return __builtin_amdgcn_frexp_mant(x); }
+  static __device__ __forceinline__ int frexp_exp(double x) { return __builtin_amdgcn_frexp_exp(x); }
+  static __device__ __forceinline__ double ldexp(double x, int e) { return __builtin_amdgcn_ldexp(x, e); }
+  static __device__ __forceinline__ double rcp(double x) { return __builtin_amdgcn_rcp(x); }
+  static __device__ __forceinline__ double sconst(double c) { return s_const(c); }
+};
+template <> __device__ __forceinline__ double t_log<double>(double x) { return pl_log<LogOps>(x); }
 
 template <typename T> __device__ __forceinline__ T t_sqrt(T x);
 template <> __device__ __forceinline__ float t_sqrt<float>(float x) { return __builtin_amdgcn_sqrtf(x); }
@@ -152,18 +145,21 @@ template <typename T> __device__ __forceinline__ T t_fma(T a, T b, T c) { return
 template <> __device__ __forceinline__ float t_fma<float>(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 
 // Catmull-Rom weights of the four taps at fraction x, and their derivatives
-// (ceres CubicHermiteSpline written as tap weights).
+// (ceres CubicHermiteSpline written as tap weights).  fp64: 1.5 and 4.5 are scalar operands (s_const); -2.5 and -5 share an
+// fma with one of them and stay vector literals.
 template <typename T>
 __device__ __forceinline__ void cr_weights(T x, T w[4], T d[4]) {
   const T x2 = x * x;
+  const T c15 = s_const(T(1.5));
   w[0] = x * t_fma<T>(x, t_fma<T>(T(-0.5), x, T(1)), T(-0.5));
-  w[1] = t_fma<T>(x2, t_fma<T>(T(1.5), x, T(-2.5)), T(1));
-  w[2] = x * t_fma<T>(x, t_fma<T>(T(-1.5), x, T(2)), T(0.5));
+  w[1] = t_fma<T>(x2, t_fma<T>(c15, x, T(-2.5)), T(1));
+  w[2] = x * t_fma<T>(x, t_fma<T>(-c15, x, T(2)), T(0.5));
   w[3] = x2 * t_fma<T>(T(0.5), x, T(-0.5));
-  d[0] = t_fma<T>(x, t_fma<T>(T(-1.5), x, T(2)), T(-0.5));
-  d[1] = x * t_fma<T>(T(4.5), x, T(-5));
-  d[2] = t_fma<T>(x, t_fma<T>(T(-4.5), x, T(4)), T(0.5));
-  d[3] = x * t_fma<T>(T(1.5), x, T(-1));
+  const T c45 = s_const(T(4.5));
+  d[0] = t_fma<T>(x, t_fma<T>(-c15, x, T(2)), T(-0.5));
+  d[1] = x * t_fma<T>(c45, x, T(-5));
+  d[2] = t_fma<T>(x, t_fma<T>(-c45, x, T(4)), T(0.5));
+  d[3] = x * t_fma<T>(c15, x, T(-1));
 }
 
 // uniform (per-problem / per-pose) values in the kernel's arithmetic type
@@ -434,6 +430,47 @@ __device__ __forceinline__ void loss_eval(int kind, T a, T inv_b, T s, T &rho, T
   } else {
     rho = s; w = T(1);
   }
+}
+
+// The loss of one point and its share of the lane's cost: what fused_chunk and cost_item do behind the sample, in two steps
+// because fused_chunk's products sit between them.  loss_point: rho and the IRLS weight w, both 0 for a lane without a valid
+// point; `wt` is the point's weight of a weighted term (VAR; ceres::ScaledLoss: a rho, a rho').  cost_point: point k of PPT
+// into `cost`.
+//
+// fp64 lanes with two points under an unweighted Cauchy loss (`pair`, wave-uniform) take ONE logarithm for both: the cost
+// only needs log(s0) + log(s1) (pl_log_pair, ea_pair_log.h).  There loss_point returns s = 1 + r^2 / a^2 in place of rho --
+// exactly 1 for a lane without a valid point (log 1 = 0: the select that zeroed rho, moved to s) -- point 0 leaves it in
+// `held` and point 1 sets the cost to (a^2 / 2) log(s0 s1).  w = 1 / s stays per point: JtJ and Jtr keep their bits, the
+// cost moves in its last places.  Everything else -- one point per lane, fp32, weighted terms, Huber, trivial -- is the
+// text it was.
+template <typename T, int PPT> constexpr bool kPairLog = sizeof(T) == 8 && PPT == 2;
+template <typename T, int PPT, bool VAR>
+__device__ __forceinline__ void loss_point(bool pair, int kind, T a, T inv_b, T s, bool valid, T wt, T &rho, T &w) {
+  if constexpr (kPairLog<T, PPT>) {
+    if (pair) {
+      const T x = s * inv_b;  // (loss_eval's Cauchy branch, the same expressions)
+      const T sum = x + T(1);
+      w = t_rcp<T>(sum);
+      w = valid ? w : T(0);
+      rho = valid ? sum : T(1);
+      return;
+    }
+  }
+  loss_eval<T>(kind, a, inv_b, s, rho, w);
+  if constexpr (VAR) { w *= wt; rho *= wt; }
+  w = valid ? w : T(0);
+  rho = valid ? rho : T(0);
+}
+template <typename T, int PPT>
+__device__ __forceinline__ void cost_point(int k, bool pair, T a, T rho, T &cost, T &held) {
+  if constexpr (kPairLog<T, PPT>) {
+    if (pair) {
+      if (k == 0) held = rho;
+      else cost = (T(0.5) * (a * a)) * pl_log_pair<LogOps>(held, rho);
+      return;
+    }
+  }
+  cost = k == 0 ? T(0.5) * rho : t_fma<T>(T(0.5), rho, cost);
 }
 
 // raw 1x6 row of one point from its sample gradient
@@ -967,6 +1004,10 @@ __device__ __forceinline__ double fused_chunk(const ProblemDesc &pd, const PS &p
       bb_v0 = min(bb_v0, pr[k].iv); bb_v1 = max(bb_v1, pr[k].iv);
     }
   }
+  // (fp64, two points: left to itself the compiler counts the failed functors at the very end and carries the four lane
+  // masks there -- eight scalar registers the kernel does not have: spilled to a VGPR's lanes and read back, 16 lane moves
+  // per wavefront.  Through a "v" operand the count is made here and the masks die.)
+  if constexpr (kPairLog<T, PPT>) asm volatile("" : "+v"(n_bad));
 
   // ---- phase 2: footprint of the chunk, staged through LDS when it fits
   bool in_lds = false;
@@ -1009,6 +1050,8 @@ __device__ __forceinline__ double fused_chunk(const ProblemDesc &pd, const PS &p
 
   EA_STAMP(3);  // projected
   // ---- phase 3: sample, Jacobian, weights, accumulate
+  const bool pair = loss_kind == 1 && (!VAR || wts == nullptr);  // one log per lane (loss_point)
+  T held = T(1);
 #pragma unroll
   for (int k = 0; k < PPT; ++k) {
     T f, Fu, Fv;
@@ -1030,11 +1073,20 @@ __device__ __forceinline__ double fused_chunk(const ProblemDesc &pd, const PS &p
     T J[6];
     if constexpr (VAR) jacobian_row_var<T>(pd, ps, pr[k], Fu, Fv, J);
     else jacobian_row<T>(pd, ps, pr[k], X[k], Y[k], Z[k], Fu, Fv, J);
+    // (every kernel but the fp64 two-point ones keeps the statements it had, here and at the cost below, not loss_point's
+    // copy of them: through the helper the one-point kernels came out with two instructions swapped, and they are compared
+    // byte for byte with the build before -- scripts/compare_device_code.py)
     T rho, w;
-    loss_eval<T>(loss_kind, loss_a, loss_inv_b, f * f, rho, w);
-    if constexpr (VAR) { w *= WT[k]; rho *= WT[k]; }
-    w = valid[k] ? w : T(0);
-    rho = valid[k] ? rho : T(0);
+    if constexpr (kPairLog<T, PPT>) {
+      T wt = T(1);
+      if constexpr (VAR) wt = WT[k];
+      loss_point<T, PPT, VAR>(pair, loss_kind, loss_a, loss_inv_b, f * f, valid[k], wt, rho, w);
+    } else {
+      loss_eval<T>(loss_kind, loss_a, loss_inv_b, f * f, rho, w);
+      if constexpr (VAR) { w *= WT[k]; rho *= WT[k]; }
+      w = valid[k] ? w : T(0);
+      rho = valid[k] ? rho : T(0);
+    }
     const T wr = w * f;
     int s = 0;
 #pragma unroll
@@ -1044,7 +1096,8 @@ __device__ __forceinline__ double fused_chunk(const ProblemDesc &pd, const PS &p
       for (int b = a; b < 6; ++b) { acc[s] = k == 0 ? wJa * J[b] : t_fma<T>(wJa, J[b], acc[s]); ++s; }
       acc[kAccJtr + a] = k == 0 ? J[a] * wr : t_fma<T>(J[a], wr, acc[kAccJtr + a]);
     }
-    acc[kAccCost] = k == 0 ? T(0.5) * rho : t_fma<T>(T(0.5), rho, acc[kAccCost]);
+    if constexpr (kPairLog<T, PPT>) cost_point<T, PPT>(k, pair, loss_a, rho, acc[kAccCost], held);
+    else acc[kAccCost] = k == 0 ? T(0.5) * rho : t_fma<T>(T(0.5), rho, acc[kAccCost]);
   }
 
   // ---- phase 4: wavefront reduction in the kernel's arithmetic type (a lane's accumulators and
@@ -1823,9 +1876,10 @@ __global__ __launch_bounds__(NT) void ea_poses_fold_kernel(PosesFold fold) {
 template <typename T>
 __device__ __forceinline__ void cr_weights_value(T x, T w[4]) {
   const T x2 = x * x;
+  const T c15 = s_const(T(1.5));
   w[0] = x * t_fma<T>(x, t_fma<T>(T(-0.5), x, T(1)), T(-0.5));
-  w[1] = t_fma<T>(x2, t_fma<T>(T(1.5), x, T(-2.5)), T(1));
-  w[2] = x * t_fma<T>(x, t_fma<T>(T(-1.5), x, T(2)), T(0.5));
+  w[1] = t_fma<T>(x2, t_fma<T>(c15, x, T(-2.5)), T(1));
+  w[2] = x * t_fma<T>(x, t_fma<T>(-c15, x, T(2)), T(0.5));
   w[3] = x2 * t_fma<T>(T(0.5), x, T(-0.5));
 }
 // 16 taps -> value: bicubic's f, no Fu / Fv
@@ -1934,7 +1988,8 @@ __device__ __forceinline__ bool cost_item(const void *__restrict__ x0, const voi
       pr[k].iu = 0; pr[k].iv = 0; pr[k].fu = T(0); pr[k].fv = T(0);
     }
   }
-  T acc = T(0);
+  T acc = T(0), held = T(1);
+  const bool pair = loss_kind == 1;  // one log per lane (loss_point)
 #pragma unroll
   for (int k = 0; k < PPT; ++k) {
     T f;
@@ -1947,9 +2002,8 @@ __device__ __forceinline__ bool cost_item(const void *__restrict__ x0, const voi
       f = bicubic_value<T>(pr[k].fu, pr[k].fv, [&](int l) { return RowLoad<T, IT>::flat(base + (ptrdiff_t)l * pitch); });
     }
     T rho, wt;
-    loss_eval<T>(loss_kind, loss_a, loss_inv_b, f * f, rho, wt);
-    rho = valid[k] ? rho : T(0);
-    acc = k == 0 ? T(0.5) * rho : t_fma<T>(T(0.5), rho, acc);
+    loss_point<T, PPT, false>(pair, loss_kind, loss_a, loss_inv_b, f * f, valid[k], T(1), rho, wt);
+    cost_point<T, PPT>(k, pair, loss_a, rho, acc, held);
   }
   // a wavefront's sum in T, the workgroup's in fp64 through LDS in wave order: fixed by (chunk, lane, wave)
   double c;
