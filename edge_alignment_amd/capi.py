@@ -48,6 +48,7 @@ EXPORTED = [
     "ea_problem_set_weights", "ea_problem_set_weights_device", "ea_problem_get_weights", "ea_problem_set_depth_weighting",
     "ea_problem_residual_quantiles", "ea_batch_residual_quantiles", "ea_problem_get_loss", "ea_problem_set_loss_auto_scale",
     "ea_problem_get_loss_auto_scale", "ea_selftest_select",
+    "ea_default_frame_params", "ea_batch_set_frames", "ea_batch_set_frames_device",
 ]
 
 # measurement hooks (edge_alignment_amd/csrc/ea_hip_dev.h): bound by bench.py, the A/B scripts and the tests that pin the
@@ -116,6 +117,11 @@ class Covariance(C.Structure):
     _fields_ = [("ok", C.c_int), ("why", C.c_int), ("rank", C.c_int), ("n_invalid", C.c_int64), ("cost", C.c_double),
                 ("eigenvalues", C.c_double * 6), ("tangent", C.c_double * 36), ("qq", C.c_double * 16),
                 ("qt", C.c_double * 12), ("tt", C.c_double * 9)]
+
+
+class FrameParams(C.Structure):
+    _fields_ = [("height", C.c_int), ("width", C.c_int), ("z_scaling", C.c_double), ("ref_threshold", C.c_int),
+                ("now_threshold", C.c_int), ("now_median", C.c_int), ("now_normalize", C.c_int)]
 
 
 _lib = None
@@ -255,6 +261,10 @@ def load():
     L.ea_problem_set_loss_auto_scale.argtypes = [vp, C.c_double, C.c_double, C.c_double]
     L.ea_problem_get_loss_auto_scale.argtypes = [vp, dp, dp, dp]
     L.ea_selftest_select.argtypes = [C.c_int, dp, i64p, C.c_int, dp, C.c_int, dp, i64p]
+    L.ea_default_frame_params.argtypes = [C.POINTER(FrameParams), C.c_int, C.c_int]
+    L.ea_default_frame_params.restype = None
+    L.ea_batch_set_frames.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(FrameParams)]
+    L.ea_batch_set_frames_device.argtypes = L.ea_batch_set_frames.argtypes
     _lib = L
     return L
 
@@ -972,6 +982,68 @@ class Batch:
         _check(load().ea_batch_eval(self._h, _dp(q), _dp(t), _dp(cost), _dp(JtJ), _dp(Jtr),
                                     bad.ctypes.data_as(C.POINTER(C.c_int64))))
         return dict(cost=cost, JtJ=JtJ, Jtr=Jtr, n_invalid=bad)
+
+    def set_frames(self, ref_bgr=None, ref_depth=None, now_bgr=None, z_scaling=5000.0, ref_threshold=35, now_threshold=35,
+                   median=True, normalize=True):
+        """ea_batch_set_frames[_device]: Problem.set_ref_frame + Problem.set_now_frame for every problem of the batch in one
+        launch sequence, bit for bit.  Each argument: a sequence of len(self) frames or one stacked array -- bgr (H, W, 3)
+        uint8, depth (H, W) uint16 -- of equal extent.  numpy arrays take the host entry; torch tensors on the batch's GPU
+        (contiguous; depth as torch.uint16 or int16 bits) take the device entry and are read in place.  ref_bgr and
+        ref_depth go together; a side left None is not set."""
+        n = len(self)
+        sides = [("ref_bgr", ref_bgr, 3), ("ref_depth", ref_depth, 2), ("now_bgr", now_bgr, 3)]
+        if (ref_bgr is None) != (ref_depth is None) or all(v is None for _, v, _ in sides):
+            raise ValueError("ref_bgr and ref_depth go together, and one side must be given")
+        frames = {}
+        for name, v, _ in sides:
+            if v is None:
+                continue
+            fr = list(v) if isinstance(v, (list, tuple)) else [v[i] for i in range(len(v))]
+            if len(fr) != n:
+                raise EAError(EA_ERR_INVALID_ARG, "%s: %d frames for a batch of %d problems" % (name, len(fr), n))
+            frames[name] = fr
+        present = [f for fr in frames.values() for f in fr if f is not None]
+        on_device = {type(f).__module__.split(".")[0] == "torch" for f in present}
+        if len(on_device) > 1:
+            raise ValueError("a mix of host arrays and device tensors")
+        on_device = bool(present) and on_device.pop()
+        device = self.problems[0].device
+        shape, keep, arrays = None, [], {}
+        for name, v, ch in sides:
+            if name not in frames:
+                arrays[name] = None
+                continue
+            ptrs = (C.c_void_p * n)()
+            for i, f in enumerate(frames[name]):
+                if f is None:
+                    continue  # (a NULL entry: the library refuses the call)
+                if on_device:
+                    import torch
+                    want = (torch.uint8,) if ch == 3 else (torch.int16,) + ((torch.uint16,) if hasattr(torch, "uint16") else ())
+                    if not f.is_cuda or f.device.index != device:
+                        raise ValueError("%s[%d]: not a tensor on the batch's GPU %d" % (name, i, device))
+                    if f.dtype not in want or not f.is_contiguous():
+                        raise ValueError("%s[%d]: a contiguous %s tensor is expected" % (name, i, want[-1]))
+                    ptrs[i] = f.data_ptr()
+                else:
+                    f = np.ascontiguousarray(f, dtype=np.uint8 if ch == 3 else np.uint16)
+                    keep.append(f)
+                    ptrs[i] = f.ctypes.data
+                hw = tuple(f.shape[:2])
+                if tuple(f.shape) != (hw + (3,) if ch == 3 else hw) or (shape is not None and hw != shape):
+                    raise ValueError("%s[%d]: shape %s; every frame of a call has one extent" % (name, i, tuple(f.shape)))
+                shape = hw
+            arrays[name] = ptrs
+        L = load()
+        prm = FrameParams()
+        L.ea_default_frame_params(C.byref(prm), *(shape or (0, 0)))
+        prm.z_scaling, prm.ref_threshold, prm.now_threshold = float(z_scaling), int(ref_threshold), int(now_threshold)
+        prm.now_median, prm.now_normalize = int(bool(median)), int(bool(normalize))
+        if on_device:
+            import torch
+            torch.cuda.current_stream(device).synchronize()  # the frames must be complete: the producers do not wait for torch's stream
+        fn = L.ea_batch_set_frames_device if on_device else L.ea_batch_set_frames
+        _check(fn(self._h, arrays["ref_bgr"], arrays["ref_depth"], arrays["now_bgr"], C.byref(prm)))
 
     def residual_quantiles(self, q, t, probs):
         """ea_batch_residual_quantiles at q (n, 4), t (n, 3): (values [n, len(probs)], n_valid [n]), one launch sequence"""

@@ -396,6 +396,10 @@ struct ea_batch {
   int t_starts_events = 0;       // tuning key "starts_events": an event pair around the call's queued launches (measurement)
   int last_starts_iterations = 0;
   int64_t last_starts_device_ns = 0;  // info keys "starts_iterations" (enqueued), "starts_device_ns" (0 without the events)
+  // ea_batch_set_frames (ea_frames.hip): the batched producers' device block (count frame workspaces and the slot table) and
+  // their pinned staging block (the table on its way up, the point counts on their way down); batch_frames_reserve
+  unsigned char *d_frames = nullptr, *h_frames = nullptr;
+  size_t frames_bytes = 0, h_frames_bytes = 0;
 };
 
 int ea::check_device(int device) {
@@ -1041,6 +1045,8 @@ static void starts_free(ea_batch *b) {
 static void batch_free_device(ea_batch *b) {
   kposes_free(b);
   starts_free(b);
+  cached_free(b->d_frames); cached_host_free(b->h_frames);
+  b->d_frames = b->h_frames = nullptr; b->frames_bytes = b->h_frames_bytes = 0;
   cached_free(b->d_cprobs); cached_host_free(b->h_cdesc); cached_host_free(b->h_cov);
   b->d_cprobs = nullptr; b->h_cdesc = nullptr; b->cdesc_cap = 0; b->h_cov = nullptr; b->dv_cov = nullptr;
   (void)hipFree(b->d_rows_r); (void)hipFree(b->d_rows_J); (void)hipFree(b->d_rows_invalid);
@@ -1151,6 +1157,37 @@ extern "C" int ea_batch_count(const ea_batch *b) { return b ? (int)b->probs.size
 extern "C" void *ea_internal_batch_stream(ea_batch *b, int *device) {
   if (device) *device = b ? b->device : -1;
   return b ? (void *)b->stream : nullptr;
+}
+
+void ea::batch_members(ea_batch *b, ea_problem *const **probs, int *count, int *device) {
+  *probs = b->probs.data();
+  *count = (int)b->probs.size();
+  *device = b->device;
+}
+
+int ea::batch_frames_reserve(ea_batch *b, size_t device_bytes, size_t pinned_bytes, unsigned char **device_block,
+                             unsigned char **pinned_block) {
+  if (b->frames_bytes < device_bytes) {
+    cached_free(b->d_frames);
+    b->d_frames = nullptr; b->frames_bytes = 0;
+    if (cached_malloc(reinterpret_cast<void **>(&b->d_frames), device_bytes, b->device) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(EA_ERR_ALLOC, "ea_batch_set_frames: no device memory for the frames' workspace");
+    }
+    b->frames_bytes = device_bytes;
+  }
+  if (b->h_frames_bytes < pinned_bytes) {
+    cached_host_free(b->h_frames);
+    b->h_frames = nullptr; b->h_frames_bytes = 0;
+    if (cached_host_malloc(reinterpret_cast<void **>(&b->h_frames), pinned_bytes, hipHostMallocDefault, b->device) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(EA_ERR_ALLOC, "ea_batch_set_frames: no pinned memory for the frame table");
+    }
+    b->h_frames_bytes = pinned_bytes;
+  }
+  *device_block = b->d_frames;
+  *pinned_block = b->h_frames;
+  return EA_OK;
 }
 
 // (re)build descriptors and the tile list when any problem changed

@@ -110,4 +110,12 @@ inline int term_variant(const ea_problem *p) { return p->variant | (p->weighted 
 int alloc_dt(ea_problem *p, int W, int H);
 int check_cov_options(const ea_covariance_options *o);
 
+// What ea_batch_set_frames (ea_frames.hip) needs of a batch, whose layout stays ea_capi.hip's: its problems in batch order and
+// its device; and the batch-owned memory of the batched producers -- one device block and one pinned staging block of at least
+// the sizes asked for, grown on demand, kept across calls and freed with the batch (EA_ERR_ALLOC when either cannot be had;
+// what they hold is the producers' business).
+void batch_members(ea_batch *b, ea_problem *const **probs, int *count, int *device);
+int batch_frames_reserve(ea_batch *b, size_t device_bytes, size_t pinned_bytes, unsigned char **device_block,
+                         unsigned char **pinned_block);
+
 }  // namespace ea

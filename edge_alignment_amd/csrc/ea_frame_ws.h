@@ -27,6 +27,11 @@
 //   frame_ws(H, W).total <= frame_ws_bound(H, W) = 32 np + 16 W + 19 * 256,
 // about 31.5 bytes per pixel (9.2 MiB for 640 x 480); for the largest frame any producer accepts (np <= 2^30) that is below
 // 2^36, far inside size_t.
+//
+// The batched producers (ea_batch_set_frames) use the same layout N times over: frame i of a call lives at i * total bytes
+// from frame 0 in a block the batch owns (total is a multiple of 256, so every region keeps its alignment), and a kernel
+// reaches its frame's region as `frame 0's pointer + blockIdx.z * total`.  At most 65535 frames of at most 2^30 pixels: below
+// 2^52 bytes.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

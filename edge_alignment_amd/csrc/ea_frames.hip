@@ -1,7 +1,8 @@
 // ea_frames.hip — the host side of everything that starts from raw frames: the frame producers behind
 // ea_problem_set_{ref,now}_frame* (raw images -> edge points / DT image through the kernels of ea_preprocess.hip, in a
-// workspace laid out by ea_frame_ws.h), ea_resize_half, the read-backs ea_problem_get_points / _get_dt, and the
-// frame-to-frame tracker ea_tracker_*.  Host code only: this file holds no kernel.
+// workspace laid out by ea_frame_ws.h), their batched form ea_batch_set_frames[_device] (N frame pairs, the frame a grid
+// dimension of every launch), ea_resize_half, the read-backs ea_problem_get_points / _get_dt, and the frame-to-frame
+// tracker ea_tracker_*.  Host code only: this file holds no kernel.
 
 #include <hip/hip_runtime.h>
 
@@ -63,14 +64,30 @@ static int read_count(const int *d_count, int *count) {
   return EA_OK;
 }
 
+// The host bookkeeping of the producers, shared by the per-problem calls and ea_batch_set_frames.  Reference side: room for
+// the frame's `total` points once the count is known (the problem is without points until ref_points_landed), then the
+// point count and the depth weights' flags once scatter and weights have run.  Current side: the image alloc_dt made room
+// for has been filled by launch_dt_store[_frames].
+static int ref_points_room(ea_problem *p, int total) {
+  p->version++;
+  return reserve_points(p, total);
+}
+static void ref_points_landed(ea_problem *p, int total) {
+  p->n = total;
+  p->weighted = p->weights_from_depth = total > 0 && p->dw_power > 0;  // (reserve_points dropped the previous frame's)
+}
+static void dt_landed(ea_problem *p) {
+  p->dt32_exact = p->d_dt32 != nullptr;  // the producers compute the distance transform in float32, as OpenCV does
+  p->version++;
+}
+
 // second half: the points themselves, compacted in raster order and back-projected
 static int ref_points_finish(ea_problem *p, const RefPointsJob &job, int height, int width, double z_scaling) {
   if (!job.started) return EA_ERR_STATE;
   int total = 0;
   int rc = read_count(job.d_total, &total);
   if (rc != EA_OK) return rc;
-  p->version++;
-  rc = reserve_points(p, total);
+  rc = ref_points_room(p, total);
   if (rc != EA_OK) return rc;
   if (total > 0) {
     if (job.ros)
@@ -86,8 +103,7 @@ static int ref_points_finish(ea_problem *p, const RefPointsJob &job, int height,
       HIPCHK(launch_depth_weights(p->dtype, p->d_z, total, p->dw_z_ref, p->dw_power, weights_ptr(p), nullptr));
     HIPCHK(hipDeviceSynchronize());
   }
-  p->n = total;
-  p->weighted = p->weights_from_depth = total > 0 && p->dw_power > 0;  // (reserve_points dropped the previous frame's)
+  ref_points_landed(p, total);
   return EA_OK;
 }
 
@@ -371,8 +387,7 @@ static int dt_from_mask(ea_problem *p, const FrameWs &ws, const WsRegion<uint8_t
   HIPCHK(launch_dt_store(p->dtype, d_dist, d_dist_f32, height, width, d_minmax, normalize, lo, hi, p->d_dt, p->pitch,
                          ws.plain.at(p->ws), p->d_dt32, nullptr));
   HIPCHK(hipDeviceSynchronize());
-  p->dt32_exact = p->d_dt32 != nullptr;  // the producers compute the distance transform in float32, as OpenCV does
-  p->version++;
+  dt_landed(p);
   return EA_OK;
 }
 
@@ -663,6 +678,170 @@ extern "C" int ea_problem_debug_now_frame(ea_problem *p, const uint8_t *bgr, int
   if (rc == EA_OK) rc = read_region(p, ws.dist, np * 4, chamfer_fix_out);
   if (rc == EA_OK) rc = read_region(p, ws.plain, np * 4, dt_out);
   return rc;
+}
+
+// ---- the batched producers: the Laplacian chain of ea_problem_set_ref_frame + ea_problem_set_now_frame for every problem of
+// a batch, the frame a grid dimension of each step (ea_launch.h: FramesLaunch) ----------------------------------------------
+//
+// Memory, owned by the batch (batch_frames_reserve): a device block [count x frame_ws(H, W) | FrameSlot x count] -- 31.5
+// bytes per pixel per frame -- and a pinned block [FrameSlot x count | FrameSlot x count | int x count]: two stagings of the
+// table, because it goes up twice when reference frames are given (the point arrays exist only once the counts are back),
+// and the counts.  Everything runs on the null stream, like the per-problem producers, with two waits: the counts, the end.
+
+extern "C" void ea_default_frame_params(ea_frame_params *prm, int height, int width) {
+  if (!prm) return;
+  prm->height = height; prm->width = width;
+  prm->z_scaling = 5000.0;
+  prm->ref_threshold = 35;
+  prm->now_threshold = 35; prm->now_median = 1; prm->now_normalize = 1;
+}
+
+// a frame the caller says is in device memory: of the batch's GPU, as far as the runtime can tell, and aligned for its elements
+static int check_device_frame(const void *ptr, int device, size_t align, const char *what) {
+  if (reinterpret_cast<uintptr_t>(ptr) % align != 0) return fail(EA_ERR_INVALID_ARG, std::string(what) + ": misaligned frame");
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, ptr) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(EA_ERR_INVALID_ARG, std::string(what) + ": not memory of a HIP device known to this runtime");
+  }
+  if (at.type != hipMemoryTypeDevice) return fail(EA_ERR_INVALID_ARG, std::string(what) + ": device memory expected");
+  if (at.device != device) return fail(EA_ERR_INVALID_ARG, std::string(what) + ": lives on another device than the batch");
+  return EA_OK;
+}
+
+static int batch_set_frames(ea_batch *b, const uint8_t *const *ref_bgr, const uint16_t *const *ref_depth,
+                            const uint8_t *const *now_bgr, const ea_frame_params *prm, bool on_device) {
+  // every check comes before a device or a problem is touched
+  if (!b || !prm) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  const bool ref = ref_bgr || ref_depth, now = now_bgr != nullptr;
+  if (ref && (!ref_bgr || !ref_depth)) return fail(EA_ERR_INVALID_ARG, "ref_bgr and ref_depth are given or NULL together");
+  if (!ref && !now) return fail(EA_ERR_INVALID_ARG, "neither reference nor current frames given");
+  const int H = prm->height, W = prm->width;
+  if (H < 3 || W < 3 || H > 32768 || W > 32768 || (int64_t)H * W > 0x3fffffff)
+    return fail(EA_ERR_INVALID_ARG, "image extent out of range");
+  if (now && W > 16384) return fail(EA_ERR_INVALID_ARG, "frames wider than 16384 pixels are not supported by the DT producers");
+  if (!(prm->z_scaling > 0.0)) return fail(EA_ERR_INVALID_ARG, "z_scaling must be > 0");
+  ea_problem *const *probs = nullptr;
+  int count = 0, device = 0;
+  batch_members(b, &probs, &count, &device);
+  if (count < 1 || count > 65535) return fail(EA_ERR_INVALID_ARG, "a batched producer call takes 1..65535 problems");
+  for (int i = 0; i < count; ++i)
+    if ((ref && (!ref_bgr[i] || !ref_depth[i])) || (now && !now_bgr[i])) return fail(EA_ERR_INVALID_ARG, "NULL frame in a given array");
+  {
+    std::vector<const ea_problem *> sorted(probs, probs + count);
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+      return fail(EA_ERR_INVALID_ARG, "the same problem twice in the batch: each frame pair needs a problem of its own");
+  }
+  if (on_device)
+    for (int i = 0; i < count; ++i) {
+      int rc = EA_OK;
+      if (ref) rc = check_device_frame(ref_bgr[i], device, 1, "ref_bgr");
+      if (rc == EA_OK && ref) rc = check_device_frame(ref_depth[i], device, 2, "ref_depth");
+      if (rc == EA_OK && now) rc = check_device_frame(now_bgr[i], device, 1, "now_bgr");
+      if (rc != EA_OK) return rc;
+    }
+
+  HIPCHK(hipSetDevice(device));
+  const FrameWs ws = frame_ws(H, W);
+  const size_t n = (size_t)count, np = (size_t)H * W, table_bytes = n * sizeof(FrameSlot);
+  static_assert(sizeof(FrameSlot) % 8 == 0, "slots follow the 256-byte aligned workspaces");
+  unsigned char *d_block = nullptr, *h_block = nullptr;
+  int rc = batch_frames_reserve(b, n * ws.total + table_bytes, 2 * table_bytes + n * sizeof(int), &d_block, &h_block);
+  if (rc != EA_OK) return rc;
+  unsigned char *base = d_block;  // frame 0's workspace; frame i's lies i * ws.total further on
+  FrameSlot *d_slots = reinterpret_cast<FrameSlot *>(d_block + n * ws.total);
+  FrameSlot *h_slots[2] = {reinterpret_cast<FrameSlot *>(h_block), reinterpret_cast<FrameSlot *>(h_block + table_bytes)};
+  int *h_totals = reinterpret_cast<int *>(h_block + 2 * table_bytes);
+  FramesLaunch f;
+  f.n = count; f.H = H; f.W = W; f.stride = ws.total; f.slots = d_slots;
+  const int dtype = probs[0]->dtype;
+
+  std::vector<FrameSlot> slots(n);
+  std::memset(slots.data(), 0, table_bytes);
+  for (size_t i = 0; i < n; ++i) {
+    ea_problem *p = probs[i];
+    p->ws_now_kind = 0;  // (the problem's own workspace holds nothing of this frame pair)
+    FrameSlot &sl = slots[i];
+    unsigned char *wsi = base + i * ws.total;
+    if (ref) sl.bgr[0] = on_device ? ref_bgr[i] : ws.bgr.at(wsi);
+    if (ref) sl.depth = on_device ? ref_depth[i] : ws.depth.at<uint16_t>(wsi);
+    if (now) sl.bgr[1] = on_device ? now_bgr[i] : ws.bgr.at(wsi);
+    sl.fx = p->cam.fx; sl.fy = p->cam.fy; sl.cx = p->cam.cx; sl.cy = p->cam.cy;
+    sl.z_ref = p->dw_z_ref; sl.power = p->dw_power;
+  }
+  int stage = 0;
+  auto upload_table = [&]() -> hipError_t {  // (a staging block is not written again before a wait has passed)
+    std::memcpy(h_slots[stage], slots.data(), table_bytes);
+    return hipMemcpyAsync(d_slots, h_slots[stage++], table_bytes, hipMemcpyHostToDevice, nullptr);
+  };
+
+  long long max_total = 0, max_weighted = 0;
+  if (ref) {
+    // strength -> count -> scan for every frame, the counts back in one strided copy: the first wait
+    HIPCHK(upload_table());
+    if (!on_device)
+      for (size_t i = 0; i < n; ++i) {
+        HIPCHK(hipMemcpyAsync(ws.bgr.at(base + i * ws.total), ref_bgr[i], np * 3, hipMemcpyHostToDevice, nullptr));
+        HIPCHK(hipMemcpyAsync(ws.depth.at(base + i * ws.total), ref_depth[i], np * 2, hipMemcpyHostToDevice, nullptr));
+      }
+    HIPCHK(launch_edge_strength_frames(f, 0, ws.gray.at(base), ws.lap.at(base), nullptr));
+    HIPCHK(launch_edge_count_scan_frames(f, ws.lap.at(base), prm->ref_threshold, ws.counts.at(base), nullptr));
+    HIPCHK(hipMemcpy2D(h_totals, sizeof(int), ws.counts.at(base) + frame_ws_blocks(H, W), ws.total, sizeof(int), n,
+                       hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) {
+      ea_problem *p = probs[i];
+      const int total = h_totals[i];
+      rc = ref_points_room(p, total);
+      if (rc != EA_OK) return rc;  // (the problems so far are without points, as a failed per-problem call leaves one)
+      FrameSlot &sl = slots[i];
+      sl.capacity = total;
+      if (total > 0) {
+        sl.x = p->d_x; sl.y = p->d_y; sl.z = p->d_z; sl.w = weights_ptr(p);
+        max_total = std::max<long long>(max_total, total);
+        if (p->dw_power > 0) max_weighted = std::max<long long>(max_weighted, total);
+      }
+    }
+  }
+  int rc_dt = EA_OK;
+  if (now)
+    for (size_t i = 0; i < n && rc_dt == EA_OK; ++i) {
+      ea_problem *p = probs[i];
+      rc_dt = alloc_dt(p, W, H);
+      slots[i].dt = p->d_dt; slots[i].dt32 = p->dtype == EA_F64 ? p->d_dt32 : nullptr; slots[i].pitch = p->pitch;
+    }
+  HIPCHK(upload_table());
+  if (ref) {
+    // a call whose frames have no point at all launches nothing that writes points; a frame without points among others
+    // has capacity 0 in its slot
+    if (max_total > 0) HIPCHK(launch_edge_scatter_frames(dtype, f, ws.lap.at(base), prm->ref_threshold, ws.counts.at(base), prm->z_scaling, nullptr));
+    HIPCHK(launch_depth_weights_frames(dtype, f, max_weighted, nullptr));
+  }
+  if (now && rc_dt == EA_OK) {
+    if (!on_device)
+      for (size_t i = 0; i < n; ++i)
+        HIPCHK(hipMemcpyAsync(ws.bgr.at(base + i * ws.total), now_bgr[i], np * 3, hipMemcpyHostToDevice, nullptr));
+    HIPCHK(launch_edge_strength_frames(f, 1, ws.gray.at(base), ws.lap.at(base), nullptr));
+    HIPCHK(launch_threshold_median_frames(f, ws.lap.at(base), prm->now_threshold, prm->now_median, ws.mask.at(base), nullptr));
+    HIPCHK(launch_chamfer_frames(f, ws.mask.at(base), ws.G.at(base), ws.scan.at(base), ws.dist.at(base), ws.minmax.at(base), nullptr));
+    HIPCHK(launch_dt_store_frames(dtype, f, ws.dist.at(base), ws.minmax.at(base), prm->now_normalize, 0.0, 1.0, nullptr));
+  }
+  HIPCHK(hipDeviceSynchronize());  // the second wait
+  for (size_t i = 0; i < n; ++i) {
+    if (ref) ref_points_landed(probs[i], slots[i].capacity);
+    if (now && rc_dt == EA_OK) dt_landed(probs[i]);
+  }
+  return rc_dt;  // (a failed alloc_dt: the reference frames are in place, no current frame is)
+}
+
+extern "C" int ea_batch_set_frames(ea_batch *b, const uint8_t *const *ref_bgr, const uint16_t *const *ref_depth,
+                                   const uint8_t *const *now_bgr, const ea_frame_params *prm) {
+  return batch_set_frames(b, ref_bgr, ref_depth, now_bgr, prm, false);
+}
+
+extern "C" int ea_batch_set_frames_device(ea_batch *b, const uint8_t *const *ref_bgr, const uint16_t *const *ref_depth,
+                                          const uint8_t *const *now_bgr, const ea_frame_params *prm) {
+  return batch_set_frames(b, ref_bgr, ref_depth, now_bgr, prm, true);
 }
 
 // read back what the problem holds in HBM: points as n x 3 doubles, DT as H x W doubles ([v][u])

@@ -2731,14 +2731,26 @@ __global__ __launch_bounds__(256) void ea_store_weights_kernel(const S *__restri
 // The ROS scatter keeps edge pixels without a depth test, so z may be 0, negative or NaN: the clamp to [0, 1] keeps every
 // stored weight a valid one (z = 0 or NaN: 1, a negative power product: 0); for z > 0 the max changes nothing.
 template <typename T>
-__global__ __launch_bounds__(256) void ea_depth_weights_kernel(const T *__restrict__ z, long long n,
-                                                               double z_ref, int power, T *__restrict__ w) {
+__device__ __forceinline__ void depth_weights_body(const T *__restrict__ z, long long n, double z_ref, int power, T *__restrict__ w) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const double ratio = __ddiv_rn(z_ref, (double)z[i]);
   double v = ratio;
   for (int k = 1; k < power; ++k) v = __dmul_rn(v, ratio);
   w[i] = (T)fmax(0.0, fmin(1.0, v));
+}
+template <typename T>
+__global__ __launch_bounds__(256) void ea_depth_weights_kernel(const T *__restrict__ z, long long n,
+                                                               double z_ref, int power, T *__restrict__ w) {
+  depth_weights_body<T>(z, n, z_ref, power, w);
+}
+// the same body for frame blockIdx.z of a batched producer call (ea_batch_set_frames): z, the weights behind it and the
+// weighting out of the frame's slot; a frame whose problem has no depth weighting (power 0), or no point, writes nothing
+template <typename T>
+__global__ __launch_bounds__(256) void ea_depth_weights_frames_kernel(const FrameSlot *__restrict__ slots) {
+  const FrameSlot &sl = slots[blockIdx.z];
+  if (sl.power <= 0) return;
+  depth_weights_body<T>(static_cast<const T *>(sl.z), (long long)sl.capacity, sl.z_ref, sl.power, static_cast<T *>(sl.w));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3323,6 +3335,15 @@ hipError_t launch_depth_weights(int dtype, const void *z, long long n, double z_
   const dim3 grid((unsigned)((n + 255) / 256));
   if (dtype == 1) hipLaunchKernelGGL((ea_depth_weights_kernel<float>), grid, dim3(256), 0, stream, (const float *)z, n, z_ref, power, (float *)w);
   else hipLaunchKernelGGL((ea_depth_weights_kernel<double>), grid, dim3(256), 0, stream, (const double *)z, n, z_ref, power, (double *)w);
+  return hipGetLastError();
+}
+
+hipError_t launch_depth_weights_frames(int dtype, const FramesLaunch &f, long long max_n, hipStream_t stream) {
+  if (max_n <= 0) return hipSuccess;
+  if (f.n < 1 || f.n > 65535 || !f.slots) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((max_n + 255) / 256), 1, (unsigned)f.n);
+  if (dtype == 1) hipLaunchKernelGGL((ea_depth_weights_frames_kernel<float>), grid, dim3(256), 0, stream, f.slots);
+  else hipLaunchKernelGGL((ea_depth_weights_frames_kernel<double>), grid, dim3(256), 0, stream, f.slots);
   return hipGetLastError();
 }
 

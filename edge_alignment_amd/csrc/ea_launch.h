@@ -100,6 +100,29 @@ struct SelectWork {
   double *out_values = nullptr;
   int64_t *out_n_valid = nullptr;
 };
+// The batched frame producers (ea_batch_set_frames): the frame is blockIdx.z of every launch.  What lies in the producers'
+// workspace is addressed as `pointer for frame 0` + z * stride bytes (the batch owns n consecutive frame_ws(H, W) layouts,
+// stride = frame_ws(H, W).total, a multiple of 256); what the problems or the caller own comes out of a device table with one
+// FrameSlot per frame.
+struct FrameSlot {
+  const uint8_t *bgr[2];  // the colour frame of the reference ([0]) / current ([1]) side: the workspace's copy of a host
+                          // frame, or the caller's device frame read in place
+  const uint16_t *depth;  // likewise
+  void *x, *y, *z, *w;    // the problem's point arrays and its weights (problem dtype), room for `capacity` points
+  void *dt;               // the problem's padded DT image and, for an fp64 problem, its float32 mirror (else NULL)
+  float *dt32;
+  double fx, fy, cx, cy;  // the problem's camera
+  double z_ref;           // ea_problem_set_depth_weighting
+  int power;              // (0 = off)
+  int capacity;           // = the frame's point count
+  int pitch;              // of dt / dt32, in texels
+  int pad_;
+};
+struct FramesLaunch {
+  int n = 0, H = 0, W = 0;
+  size_t stride = 0;
+  const FrameSlot *slots = nullptr;  // device
+};
 struct RowsLaunch {
   int dtype = 0, variant = 0, buffer_loads = 0, img32 = 0;
   int layout = 0;   // 0 = J row-major [rows][6], 1 = column-major [6][rows]
@@ -202,6 +225,20 @@ hipError_t launch_edge_count_scan(const uint8_t *lap, const uint16_t *depth, int
 hipError_t launch_edge_scatter(int dtype, const uint8_t *lap, const uint16_t *depth, int H, int W, int thr,
                                const int *block_offsets, double fx, double fy, double cx, double cy, double z_scaling,
                                void *X, void *Y, void *Z, int capacity, hipStream_t s);
+// The same steps for f.n frames in one launch each (grid z = frame; the kernels run the per-frame kernels' bodies).  Workspace
+// pointers are frame 0's; side: 0 = the reference frames' colour source, 1 = the current frames'.  The counts' layout is
+// launch_edge_count_scan's per frame: the total behind the per-block counts, at f.stride bytes from its neighbour's.
+hipError_t launch_edge_strength_frames(const FramesLaunch &f, int side, uint8_t *gray, uint8_t *lap, hipStream_t s);
+hipError_t launch_threshold_median_frames(const FramesLaunch &f, const uint8_t *lap, int thr, int median, uint8_t *mask, hipStream_t s);
+hipError_t launch_chamfer_frames(const FramesLaunch &f, const uint8_t *mask, int *G, int *scratch, int *dist_fix, unsigned int *minmax,
+                                 hipStream_t s);
+hipError_t launch_dt_store_frames(int dtype, const FramesLaunch &f, const int *dist_fix, const unsigned int *minmax, int normalize,
+                                  double lo, double hi, hipStream_t s);
+hipError_t launch_edge_count_scan_frames(const FramesLaunch &f, const uint8_t *lap, int thr, int *block_counts, hipStream_t s);
+hipError_t launch_edge_scatter_frames(int dtype, const FramesLaunch &f, const uint8_t *lap, int thr, const int *block_offsets,
+                                      double z_scaling, hipStream_t s);
+// ea_kernels.hip: ea_depth_weights_kernel's body for the frames whose slot has power > 0, max_n = the largest capacity among them
+hipError_t launch_depth_weights_frames(int dtype, const FramesLaunch &f, long long max_n, hipStream_t s);
 }  // namespace ea
 
 // ea_capi.hip, for the library's other translation units (ea_comm.hip): the thread-local error message, a batch's stream,

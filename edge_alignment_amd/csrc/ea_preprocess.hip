@@ -47,8 +47,17 @@ __device__ __forceinline__ int reflect101(int i, int n) {
   return min(max(i, 0), n - 1);
 }
 
+// ---- one body per step, two kernels -------------------------------------------------------------
+// Every step of the Laplacian chain is a __device__ body that takes one frame's pointers; ea_<step>_kernel runs it on the
+// pointers it is given (the per-problem producers), ea_<step>_frames_kernel on those of frame blockIdx.z of a batched call
+// (ea_batch_set_frames): workspace regions at frame 0's pointer + z * stride bytes, everything else out of the frame's slot.
+template <typename U>
+__device__ __forceinline__ U *frame_ptr(U *frame0, size_t stride) {
+  return reinterpret_cast<U *>(reinterpret_cast<uintptr_t>(frame0) + (size_t)blockIdx.z * stride);
+}
+
 // blur (3 channels) + gray in one pass
-__global__ void ea_blur_gray_kernel(const uint8_t *__restrict__ bgr, int H, int W, uint8_t *__restrict__ gray) {
+__device__ __forceinline__ void blur_gray_body(const uint8_t *__restrict__ bgr, int H, int W, uint8_t *__restrict__ gray) {
   const int u = blockIdx.x * blockDim.x + threadIdx.x, v = blockIdx.y;
   if (u >= W) return;
   int acc[3] = {0, 0, 0};
@@ -67,8 +76,14 @@ __global__ void ea_blur_gray_kernel(const uint8_t *__restrict__ bgr, int H, int 
   const int c0 = (acc[0] + 8) >> 4, c1 = (acc[1] + 8) >> 4, c2 = (acc[2] + 8) >> 4;
   gray[(size_t)v * W + u] = (uint8_t)((4899 * c0 + 9617 * c1 + 1868 * c2 + 8192) >> 14);
 }
+__global__ void ea_blur_gray_kernel(const uint8_t *__restrict__ bgr, int H, int W, uint8_t *__restrict__ gray) {
+  blur_gray_body(bgr, H, W, gray);
+}
+__global__ void ea_blur_gray_frames_kernel(const FrameSlot *__restrict__ slots, int side, int H, int W, uint8_t *gray, size_t stride) {
+  blur_gray_body(slots[blockIdx.z].bgr[side], H, W, frame_ptr(gray, stride));
+}
 
-__global__ void ea_laplacian_abs_kernel(const uint8_t *__restrict__ gray, int H, int W, uint8_t *__restrict__ lap) {
+__device__ __forceinline__ void laplacian_abs_body(const uint8_t *__restrict__ gray, int H, int W, uint8_t *__restrict__ lap) {
   const int u = blockIdx.x * blockDim.x + threadIdx.x, v = blockIdx.y;
   if (u >= W) return;
   const int ym = reflect101(v - 1, H), yp = reflect101(v + 1, H);
@@ -77,11 +92,17 @@ __global__ void ea_laplacian_abs_kernel(const uint8_t *__restrict__ gray, int H,
                      gray[(size_t)yp * W + xp]) - 8 * (int)gray[(size_t)v * W + u];
   lap[(size_t)v * W + u] = (uint8_t)min(abs(s), 255);
 }
+__global__ void ea_laplacian_abs_kernel(const uint8_t *__restrict__ gray, int H, int W, uint8_t *__restrict__ lap) {
+  laplacian_abs_body(gray, H, W, lap);
+}
+__global__ void ea_laplacian_abs_frames_kernel(const uint8_t *gray, int H, int W, uint8_t *lap, size_t stride) {
+  laplacian_abs_body(frame_ptr(gray, stride), H, W, frame_ptr(lap, stride));
+}
 
 // B = (lap > thr) ? 0 : 255, then 3x3 median with replicate border; on a two-valued image the
 // median is the majority.  mask: 0 = edge (DT source), 255 = background.
-__global__ void ea_threshold_median_kernel(const uint8_t *__restrict__ lap, int H, int W, int thr, int median,
-                                           uint8_t *__restrict__ mask) {
+__device__ __forceinline__ void threshold_median_body(const uint8_t *__restrict__ lap, int H, int W, int thr, int median,
+                                                      uint8_t *__restrict__ mask) {
   const int u = blockIdx.x * blockDim.x + threadIdx.x, v = blockIdx.y;
   if (u >= W) return;
   if (!median) {
@@ -99,6 +120,14 @@ __global__ void ea_threshold_median_kernel(const uint8_t *__restrict__ lap, int 
     }
   }
   mask[(size_t)v * W + u] = bg >= 5 ? 255 : 0;
+}
+__global__ void ea_threshold_median_kernel(const uint8_t *__restrict__ lap, int H, int W, int thr, int median,
+                                           uint8_t *__restrict__ mask) {
+  threshold_median_body(lap, H, W, thr, median, mask);
+}
+__global__ void ea_threshold_median_frames_kernel(const uint8_t *lap, int H, int W, int thr, int median, uint8_t *mask,
+                                                  size_t stride) {
+  threshold_median_body(frame_ptr(lap, stride), H, W, thr, median, frame_ptr(mask, stride));
 }
 
 // ---- Canny flavour (ref: utils.cpp:87-94 / :397-404: blur 3x3 -> CV_RGB2GRAY -> Canny(30, 90)) ----------------
@@ -291,9 +320,9 @@ __global__ void ea_canny_finish_kernel(const uint8_t *__restrict__ label, const 
 // pass chains the segment ends (kernel B: carries), and the consumer applies the carries on the fly.
 constexpr int kSegRows = 32;
 
-__global__ void ea_column_local_kernel(const uint8_t *__restrict__ mask, int H, int W, int *__restrict__ G,
-                                       int *__restrict__ end_dn /*S x W*/, int *__restrict__ end_up /*S x W*/,
-                                       unsigned int *__restrict__ minmax /* reset here for the row pass two launches on */) {
+__device__ __forceinline__ void column_local_body(const uint8_t *__restrict__ mask, int H, int W, int *__restrict__ G,
+                                                  int *__restrict__ end_dn /*S x W*/, int *__restrict__ end_up /*S x W*/,
+                                                  unsigned int *__restrict__ minmax /* reset here for the row pass two launches on */) {
   if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) { minmax[0] = 0xffffffffu; minmax[1] = 0u; }
   const int x = blockIdx.x * blockDim.x + threadIdx.x;
   if (x >= W) return;
@@ -324,11 +353,21 @@ __global__ void ea_column_local_kernel(const uint8_t *__restrict__ mask, int H, 
   }
   end_up[(size_t)s * W + x] = d;  // distance from the segment's first row to the nearest feature below
 }
+__global__ void ea_column_local_kernel(const uint8_t *__restrict__ mask, int H, int W, int *__restrict__ G,
+                                       int *__restrict__ end_dn, int *__restrict__ end_up, unsigned int *__restrict__ minmax) {
+  column_local_body(mask, H, W, G, end_dn, end_up, minmax);
+}
+// (each frame resets its own minmax pair: the body's test names block (0, 0) of the frame's own x-y plane)
+__global__ void ea_column_local_frames_kernel(const uint8_t *mask, int H, int W, int *G, int *end_dn, int *end_up,
+                                              unsigned int *minmax, size_t stride) {
+  column_local_body(frame_ptr(mask, stride), H, W, frame_ptr(G, stride), frame_ptr(end_dn, stride), frame_ptr(end_up, stride),
+                    frame_ptr(minmax, stride));
+}
 
 // carry_dn[s] = distance from the row just above segment s to the nearest feature above it;
 // carry_up[s] = distance from the row just below segment s to the nearest feature below it
-__global__ void ea_column_carry_kernel(const int *__restrict__ end_dn, const int *__restrict__ end_up, int H, int W,
-                                       int S, int *__restrict__ carry_dn, int *__restrict__ carry_up) {
+__device__ __forceinline__ void column_carry_body(const int *__restrict__ end_dn, const int *__restrict__ end_up, int H, int W,
+                                                  int S, int *__restrict__ carry_dn, int *__restrict__ carry_up) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x;
   if (x >= W) return;
   int c = kNoFeature;
@@ -343,6 +382,15 @@ __global__ void ea_column_carry_kernel(const int *__restrict__ end_dn, const int
     const int len = min(H, (s + 1) * kSegRows) - s * kSegRows;
     c = min(end_up[(size_t)s * W + x], min(c + len, kNoFeature));
   }
+}
+__global__ void ea_column_carry_kernel(const int *__restrict__ end_dn, const int *__restrict__ end_up, int H, int W,
+                                       int S, int *__restrict__ carry_dn, int *__restrict__ carry_up) {
+  column_carry_body(end_dn, end_up, H, W, S, carry_dn, carry_up);
+}
+__global__ void ea_column_carry_frames_kernel(const int *end_dn, const int *end_up, int H, int W, int S, int *carry_dn,
+                                              int *carry_up, size_t stride) {
+  column_carry_body(frame_ptr(end_dn, stride), frame_ptr(end_up, stride), H, W, S, frame_ptr(carry_dn, stride),
+                    frame_ptr(carry_up, stride));
 }
 
 // min / max of a non-negative float over the workgroup -> two atomics per workgroup (one per LANE, all on the same two
@@ -372,9 +420,9 @@ __device__ __forceinline__ int chamfer_cost(int dx, int dy) {
 
 // One workgroup per image row: G row staged in LDS, every lane searches outwards from its own
 // column and stops as soon as a*dx alone exceeds the best distance found.
-__global__ void ea_chamfer_row_kernel(const int *__restrict__ G, const int *__restrict__ carry_dn,
-                                      const int *__restrict__ carry_up, int H, int W, int *__restrict__ dist_fix,
-                                      unsigned int *__restrict__ minmax /* [0]=min bits, [1]=max bits of dist*2^-16 as float */) {
+__device__ __forceinline__ void chamfer_row_body(const int *__restrict__ G, const int *__restrict__ carry_dn,
+                                                 const int *__restrict__ carry_up, int H, int W, int *__restrict__ dist_fix,
+                                                 unsigned int *__restrict__ minmax /* [0]=min bits, [1]=max bits of dist*2^-16 as float */) {
   extern __shared__ int s_g[];
   const int y = blockIdx.x;
   const int seg = y / kSegRows, y0 = seg * kSegRows, y1 = min(H, y0 + kSegRows);
@@ -416,6 +464,16 @@ __global__ void ea_chamfer_row_kernel(const int *__restrict__ G, const int *__re
     lmin = fminf(lmin, f); lmax = fmaxf(lmax, f);
   }
   block_minmax_atomic(lmin, lmax, minmax);
+}
+__global__ void ea_chamfer_row_kernel(const int *__restrict__ G, const int *__restrict__ carry_dn,
+                                      const int *__restrict__ carry_up, int H, int W, int *__restrict__ dist_fix,
+                                      unsigned int *__restrict__ minmax) {
+  chamfer_row_body(G, carry_dn, carry_up, H, W, dist_fix, minmax);
+}
+__global__ void ea_chamfer_row_frames_kernel(const int *G, const int *carry_dn, const int *carry_up, int H, int W, int *dist_fix,
+                                             unsigned int *minmax, size_t stride) {
+  chamfer_row_body(frame_ptr(G, stride), frame_ptr(carry_dn, stride), frame_ptr(carry_up, stride), H, W,
+                   frame_ptr(dist_fix, stride), frame_ptr(minmax, stride));
 }
 
 // Exact Euclidean variant of the row pass (DIST_MASK_PRECISE): the same per-column distances G, squared cost
@@ -472,10 +530,10 @@ __global__ void ea_edt_row_kernel(const int *__restrict__ G, const int *__restri
 
 // dist (16.16 fixed) -> float32 [-> min-max normalised] -> padded image of the problem dtype
 template <typename T>
-__global__ void ea_dt_store_kernel(const int *__restrict__ dist_fix, const float *__restrict__ dist_f32 /* one of the two */,
-                                   int H, int W, const unsigned int *__restrict__ minmax, int normalize, double lo, double hi,
-                                   T *__restrict__ dst, int pitch, float *__restrict__ plain /*nullable HxW*/,
-                                   float *__restrict__ dst32 /*nullable: the float32 mirror of an fp64 problem's image, same pitch*/) {
+__device__ __forceinline__ void dt_store_body(const int *__restrict__ dist_fix, const float *__restrict__ dist_f32 /* one of the two */,
+                                              int H, int W, const unsigned int *__restrict__ minmax, int normalize, double lo, double hi,
+                                              T *__restrict__ dst, int pitch, float *__restrict__ plain /*nullable HxW*/,
+                                              float *__restrict__ dst32 /*nullable: the float32 mirror of an fp64 problem's image, same pitch*/) {
   const int pu = blockIdx.x * blockDim.x + threadIdx.x, pv = blockIdx.y;  // padded coordinates
   if (pu >= W + 2 * kImagePad) return;
   const int u = min(max(pu - kImagePad, 0), W - 1), v = min(max(pv - kImagePad, 0), H - 1);
@@ -491,6 +549,20 @@ __global__ void ea_dt_store_kernel(const int *__restrict__ dist_fix, const float
   if (dst32) dst32[(size_t)pv * pitch + pu] = f;  // (the value IS a float: the mirror is exact by construction)
   if (plain && pu >= kImagePad && pu < W + kImagePad && pv >= kImagePad && pv < H + kImagePad)
     plain[(size_t)(pv - kImagePad) * W + (pu - kImagePad)] = f;
+}
+template <typename T>
+__global__ void ea_dt_store_kernel(const int *__restrict__ dist_fix, const float *__restrict__ dist_f32, int H, int W,
+                                   const unsigned int *__restrict__ minmax, int normalize, double lo, double hi,
+                                   T *__restrict__ dst, int pitch, float *__restrict__ plain, float *__restrict__ dst32) {
+  dt_store_body<T>(dist_fix, dist_f32, H, W, minmax, normalize, lo, hi, dst, pitch, plain, dst32);
+}
+// (a batched call has the chamfer distance only, and no debug read-back: dist_f32 and plain stay NULL)
+template <typename T>
+__global__ void ea_dt_store_frames_kernel(const FrameSlot *__restrict__ slots, const int *dist_fix, int H, int W,
+                                          const unsigned int *minmax, int normalize, double lo, double hi, size_t stride) {
+  const FrameSlot &sl = slots[blockIdx.z];
+  dt_store_body<T>(frame_ptr(dist_fix, stride), nullptr, H, W, frame_ptr(minmax, stride), normalize, lo, hi,
+                   static_cast<T *>(sl.dt), sl.pitch, nullptr, sl.dt32);
 }
 
 // get_aX_mask (ref: utils.cpp:283-369): a point also needs mask > 0 -- the gradient map is zeroed elsewhere
@@ -508,8 +580,8 @@ __device__ __forceinline__ bool edge_flag(const uint8_t *lap, const uint16_t *de
   return lap[i] > thr && (!depth || depth[i] > 0);
 }
 
-__global__ void ea_edge_count_kernel(const uint8_t *__restrict__ lap, const uint16_t *__restrict__ depth, int npix,
-                                     int thr, int *__restrict__ block_counts) {
+__device__ __forceinline__ void edge_count_body(const uint8_t *__restrict__ lap, const uint16_t *__restrict__ depth, int npix,
+                                                int thr, int *__restrict__ block_counts) {
   __shared__ int s_cnt[kScanBlock / 64];
   const int i = blockIdx.x * kScanBlock + threadIdx.x;
   const bool f = i < npix && edge_flag(lap, depth, (size_t)i, thr);
@@ -522,9 +594,17 @@ __global__ void ea_edge_count_kernel(const uint8_t *__restrict__ lap, const uint
     block_counts[blockIdx.x] = s;
   }
 }
+__global__ void ea_edge_count_kernel(const uint8_t *__restrict__ lap, const uint16_t *__restrict__ depth, int npix,
+                                     int thr, int *__restrict__ block_counts) {
+  edge_count_body(lap, depth, npix, thr, block_counts);
+}
+__global__ void ea_edge_count_frames_kernel(const FrameSlot *__restrict__ slots, const uint8_t *lap, int npix, int thr,
+                                            int *block_counts, size_t stride) {
+  edge_count_body(frame_ptr(lap, stride), slots[blockIdx.z].depth, npix, thr, frame_ptr(block_counts, stride));
+}
 
 // exclusive scan of the block counts by one workgroup (sequential over chunks of 1024)
-__global__ void ea_edge_scan_kernel(int *__restrict__ block_counts, int nblocks, int *__restrict__ total) {
+__device__ __forceinline__ void edge_scan_body(int *__restrict__ block_counts, int nblocks, int *__restrict__ total) {
   __shared__ int s_buf[kScanBlock];
   __shared__ int s_carry;
   if (threadIdx.x == 0) s_carry = 0;
@@ -548,12 +628,20 @@ __global__ void ea_edge_scan_kernel(int *__restrict__ block_counts, int nblocks,
   }
   if (threadIdx.x == 0) *total = s_carry;
 }
+__global__ void ea_edge_scan_kernel(int *__restrict__ block_counts, int nblocks, int *__restrict__ total) {
+  edge_scan_body(block_counts, nblocks, total);
+}
+// one workgroup per frame; a frame's total lands behind its own block counts
+__global__ void ea_edge_scan_frames_kernel(int *block_counts, int nblocks, size_t stride) {
+  int *counts = frame_ptr(block_counts, stride);
+  edge_scan_body(counts, nblocks, counts + nblocks);
+}
 
 template <typename T>
-__global__ void ea_edge_scatter_kernel(const uint8_t *__restrict__ lap, const uint16_t *__restrict__ depth, int H, int W,
-                                       int thr, const int *__restrict__ block_offsets, double fx, double fy, double cx,
-                                       double cy, double z_scaling, T *__restrict__ X, T *__restrict__ Y, T *__restrict__ Z,
-                                       int capacity) {
+__device__ __forceinline__ void edge_scatter_body(const uint8_t *__restrict__ lap, const uint16_t *__restrict__ depth, int H, int W,
+                                                  int thr, const int *__restrict__ block_offsets, double fx, double fy, double cx,
+                                                  double cy, double z_scaling, T *__restrict__ X, T *__restrict__ Y,
+                                                  T *__restrict__ Z, int capacity) {
   __shared__ int s_cnt[kScanBlock / 64];
   const int npix = H * W;
   const int i = blockIdx.x * kScanBlock + threadIdx.x;
@@ -573,6 +661,21 @@ __global__ void ea_edge_scatter_kernel(const uint8_t *__restrict__ lap, const ui
   const double x = __dmul_rn((double)u - cx, z) / fx;
   const double y = __dmul_rn((double)v - cy, z) / fy;
   X[off] = (T)x; Y[off] = (T)y; Z[off] = (T)z;
+}
+template <typename T>
+__global__ void ea_edge_scatter_kernel(const uint8_t *__restrict__ lap, const uint16_t *__restrict__ depth, int H, int W,
+                                       int thr, const int *__restrict__ block_offsets, double fx, double fy, double cx,
+                                       double cy, double z_scaling, T *__restrict__ X, T *__restrict__ Y, T *__restrict__ Z,
+                                       int capacity) {
+  edge_scatter_body<T>(lap, depth, H, W, thr, block_offsets, fx, fy, cx, cy, z_scaling, X, Y, Z, capacity);
+}
+// (a frame without points has capacity 0: the body's capacity guard returns before any of its NULL arrays is touched)
+template <typename T>
+__global__ void ea_edge_scatter_frames_kernel(const FrameSlot *__restrict__ slots, const uint8_t *lap, int H, int W, int thr,
+                                              const int *block_offsets, double z_scaling, size_t stride) {
+  const FrameSlot &sl = slots[blockIdx.z];
+  edge_scatter_body<T>(frame_ptr(lap, stride), sl.depth, H, W, thr, frame_ptr(block_offsets, stride), sl.fx, sl.fy, sl.cx, sl.cy,
+                       z_scaling, static_cast<T *>(sl.x), static_cast<T *>(sl.y), static_cast<T *>(sl.z), sl.capacity);
 }
 
 // ROS flavour of the scatter (ref: src/SolveEA.cpp:61-78): every edge pixel, float depth in metres, Z == 0 -> 1.0,
@@ -787,6 +890,74 @@ hipError_t launch_edge_scatter(int dtype, const uint8_t *lap, const uint16_t *de
   else
     hipLaunchKernelGGL((ea_edge_scatter_kernel<double>), dim3(nblocks), dim3(kScanBlock), 0, s, lap, depth, H, W, thr,
                        block_offsets, fx, fy, cx, cy, z_scaling, (double *)X, (double *)Y, (double *)Z, capacity);
+  return hipGetLastError();
+}
+
+// ---- the batched forms: the grids of the launchers above with the frame in z ----------------------
+
+static bool frames_ok(const FramesLaunch &f) { return f.n >= 1 && f.n <= 65535 && f.slots && f.stride % 256 == 0; }
+
+hipError_t launch_edge_strength_frames(const FramesLaunch &f, int side, uint8_t *gray, uint8_t *lap, hipStream_t s) {
+  if (!frames_ok(f)) return hipErrorInvalidValue;
+  dim3 block(256), grid((f.W + 255) / 256, f.H, f.n);
+  hipLaunchKernelGGL(ea_blur_gray_frames_kernel, grid, block, 0, s, f.slots, side, f.H, f.W, gray, f.stride);
+  hipLaunchKernelGGL(ea_laplacian_abs_frames_kernel, grid, block, 0, s, gray, f.H, f.W, lap, f.stride);
+  return hipGetLastError();
+}
+
+hipError_t launch_threshold_median_frames(const FramesLaunch &f, const uint8_t *lap, int thr, int median, uint8_t *mask, hipStream_t s) {
+  if (!frames_ok(f)) return hipErrorInvalidValue;
+  dim3 block(256), grid((f.W + 255) / 256, f.H, f.n);
+  hipLaunchKernelGGL(ea_threshold_median_frames_kernel, grid, block, 0, s, lap, f.H, f.W, thr, median, mask, f.stride);
+  return hipGetLastError();
+}
+
+hipError_t launch_chamfer_frames(const FramesLaunch &f, const uint8_t *mask, int *G, int *scratch, int *dist_fix, unsigned int *minmax,
+                                 hipStream_t s) {
+  if (!frames_ok(f)) return hipErrorInvalidValue;
+  const int H = f.H, W = f.W, S = (H + kSegRows - 1) / kSegRows;
+  int *end_dn = scratch, *end_up = scratch + (size_t)S * W, *carry_dn = scratch + 2 * (size_t)S * W,
+      *carry_up = scratch + 3 * (size_t)S * W;
+  hipLaunchKernelGGL(ea_column_local_frames_kernel, dim3((W + 63) / 64, S, f.n), dim3(64), 0, s, mask, H, W, G, end_dn, end_up,
+                     minmax, f.stride);
+  hipLaunchKernelGGL(ea_column_carry_frames_kernel, dim3((W + 63) / 64, 1, f.n), dim3(64), 0, s, end_dn, end_up, H, W, S, carry_dn,
+                     carry_up, f.stride);
+  const int row_threads = std::min(1024, std::max(256, ((W + 63) / 64) * 64));
+  hipLaunchKernelGGL(ea_chamfer_row_frames_kernel, dim3(H, 1, f.n), dim3(row_threads), (size_t)W * sizeof(int), s, G, carry_dn,
+                     carry_up, H, W, dist_fix, minmax, f.stride);
+  return hipGetLastError();
+}
+
+hipError_t launch_dt_store_frames(int dtype, const FramesLaunch &f, const int *dist_fix, const unsigned int *minmax, int normalize,
+                                  double lo, double hi, hipStream_t s) {
+  if (!frames_ok(f)) return hipErrorInvalidValue;
+  dim3 block(256), grid((f.W + 2 * kImagePad + 255) / 256, f.H + 2 * kImagePad, f.n);
+  if (dtype == 1)
+    hipLaunchKernelGGL((ea_dt_store_frames_kernel<float>), grid, block, 0, s, f.slots, dist_fix, f.H, f.W, minmax, normalize, lo, hi, f.stride);
+  else
+    hipLaunchKernelGGL((ea_dt_store_frames_kernel<double>), grid, block, 0, s, f.slots, dist_fix, f.H, f.W, minmax, normalize, lo, hi, f.stride);
+  return hipGetLastError();
+}
+
+hipError_t launch_edge_count_scan_frames(const FramesLaunch &f, const uint8_t *lap, int thr, int *block_counts, hipStream_t s) {
+  if (!frames_ok(f)) return hipErrorInvalidValue;
+  const int npix = f.H * f.W, nblocks = (npix + kScanBlock - 1) / kScanBlock;
+  hipLaunchKernelGGL(ea_edge_count_frames_kernel, dim3(nblocks, 1, f.n), dim3(kScanBlock), 0, s, f.slots, lap, npix, thr, block_counts,
+                     f.stride);
+  hipLaunchKernelGGL(ea_edge_scan_frames_kernel, dim3(1, 1, f.n), dim3(kScanBlock), 0, s, block_counts, nblocks, f.stride);
+  return hipGetLastError();
+}
+
+hipError_t launch_edge_scatter_frames(int dtype, const FramesLaunch &f, const uint8_t *lap, int thr, const int *block_offsets,
+                                      double z_scaling, hipStream_t s) {
+  if (!frames_ok(f)) return hipErrorInvalidValue;
+  const int npix = f.H * f.W, nblocks = (npix + kScanBlock - 1) / kScanBlock;
+  if (dtype == 1)
+    hipLaunchKernelGGL((ea_edge_scatter_frames_kernel<float>), dim3(nblocks, 1, f.n), dim3(kScanBlock), 0, s, f.slots, lap, f.H, f.W,
+                       thr, block_offsets, z_scaling, f.stride);
+  else
+    hipLaunchKernelGGL((ea_edge_scatter_frames_kernel<double>), dim3(nblocks, 1, f.n), dim3(kScanBlock), 0, s, f.slots, lap, f.H, f.W,
+                       thr, block_offsets, z_scaling, f.stride);
   return hipGetLastError();
 }
 

@@ -647,6 +647,46 @@ int ea_problem_set_now_frame(ea_problem *p, const uint8_t *bgr, int height, int 
 int ea_problem_debug_now_frame(ea_problem *p, const uint8_t *bgr, int height, int width, int threshold, int median,
                                int normalize, uint8_t *lap_out, uint8_t *mask_out, int32_t *chamfer_fix_out,
                                float *dt_out);
+/* The two producers above for EVERY problem of a batch in one launch sequence: N = ea_batch_count(b) frame pairs of equal
+ * extent, the frame a grid dimension of each step -- the 12 launches of one pair (13 with depth weighting) and two waits for
+ * the whole batch, where the per-problem calls cost 12-13 launches and three waits per pair.
+ *
+ * Each pointer array has N entries, one per problem in batch order.  ref_bgr and ref_depth are given or NULL together; NULL:
+ * only the current frames are set.  now_bgr NULL: only the reference frames.  Both sides NULL is an error.
+ *
+ * After the call every problem p_i is in the state that
+ *     ea_problem_set_ref_frame(p_i, ref_bgr[i], ref_depth[i], height, width, z_scaling, ref_threshold);
+ *     ea_problem_set_now_frame(p_i, now_bgr[i], height, width, now_threshold, now_median, now_normalize);
+ * leave it in, in that order, bit for bit: the same points in the same order, the same padded DT image and float32 mirror
+ * (exact), the same depth weights where the problem has ea_problem_set_depth_weighting, the version bumped so that the batch
+ * rebuilds its descriptors.  Each problem uses its own camera and its own depth weighting; its terms are not touched.  The one
+ * difference: the frames pass through a workspace the batch owns (31.5 bytes per pixel per frame: 295 MB for 32 frames of
+ * 640 x 480, kept until the batch is destroyed), and what a problem's own producer workspace holds afterwards is unspecified
+ * (the tracker's short cut from the last current frame does not apply).
+ *
+ * EA_ERR_INVALID_ARG, checked before a device or a problem is touched (batch and problems unchanged): NULL batch or params; a
+ * NULL entry in a given array; height or width outside 3..32768, more than 2^30 - 1 pixels, or with current frames a width
+ * above 16384; z_scaling <= 0; the same problem twice in the batch (each pair needs a problem of its own); more than 65535
+ * problems; for the _device form an entry that hipPointerGetAttributes does not report as device memory of the batch's device
+ * (or a depth frame at an odd address).  EA_ERR_ALLOC: no memory for the workspace.  A failure past the checks leaves each
+ * problem as the per-problem producers leave a problem on the same failure: without points when its reference step did not
+ * complete, with the image of the previous frame's extent not marked exact when its current step did not.
+ *
+ * ea_batch_set_frames: host pointers (pinned memory, ea_host_alloc, goes up as direct DMA).  ea_batch_set_frames_device: every
+ * entry a device pointer on the batch's device, read in place without a staging copy; as with the other _device setters the
+ * caller's frames must be COMPLETE when the call is made (the stream that produced them synchronised: the producers run on
+ * the null stream, which does not wait for non-blocking streams), and the call returns with every read of them finished. */
+typedef struct {
+  int height, width;      /* of every frame of the call */
+  double z_scaling;       /* ea_problem_set_ref_frame's */
+  int ref_threshold;      /* ea_problem_set_ref_frame's threshold (35) */
+  int now_threshold, now_median, now_normalize; /* ea_problem_set_now_frame's (35, 1, 1) */
+} ea_frame_params;
+void ea_default_frame_params(ea_frame_params *prm, int height, int width); /* z_scaling 5000 and the values above */
+int ea_batch_set_frames(ea_batch *b, const uint8_t *const *ref_bgr, const uint16_t *const *ref_depth,
+                        const uint8_t *const *now_bgr, const ea_frame_params *prm);
+int ea_batch_set_frames_device(ea_batch *b, const uint8_t *const *ref_bgr, const uint16_t *const *ref_depth,
+                               const uint8_t *const *now_bgr, const ea_frame_params *prm);
 /* Canny flavour of the two producers -- what every standalone test after edge_align_test1 uses:
  * blur 3x3 -> CV_RGB2GRAY -> Canny(low, high) (aperture 3, L1 gradient; the reference passes 30, 90).
  * Reference frame: get_aX_canny (utils.cpp:371-462): edge pixel && depth > 0 -> back-projection, raster order. */

@@ -23,7 +23,7 @@ import re
 import subprocess
 import sys
 
-SOURCES = ("csrc/ea_kernels.hip", "csrc/ea_kernels_var.hip", "csrc/ea_capi.hip")
+SOURCES = ("csrc/ea_kernels.hip", "csrc/ea_kernels_var.hip", "csrc/ea_capi.hip", "csrc/ea_preprocess.hip")
 _ORDINAL = re.compile(r"\.(LBB|Lfunc_begin|Lfunc_end|Ltmp)\d+|\b(BB)\d+(?=_\d)")  # (BB<n>_<block>: the same label in a loop comment)
 _LABEL_PAD = re.compile(r"^(\.LBBN_\d+:)[ \t]+;", re.M)  # the comment behind a label is padded to a column: by the ordinal's digits
 
