@@ -49,6 +49,7 @@ EXPORTED = [
     "ea_problem_residual_quantiles", "ea_batch_residual_quantiles", "ea_problem_get_loss", "ea_problem_set_loss_auto_scale",
     "ea_problem_get_loss_auto_scale", "ea_selftest_select",
     "ea_default_frame_params", "ea_batch_set_frames", "ea_batch_set_frames_device",
+    "ea_default_canny_frame_params", "ea_batch_set_frames_canny", "ea_batch_set_frames_canny_device",
 ]
 
 # measurement hooks (edge_alignment_amd/csrc/ea_hip_dev.h): bound by bench.py, the A/B scripts and the tests that pin the
@@ -122,6 +123,11 @@ class Covariance(C.Structure):
 class FrameParams(C.Structure):
     _fields_ = [("height", C.c_int), ("width", C.c_int), ("z_scaling", C.c_double), ("ref_threshold", C.c_int),
                 ("now_threshold", C.c_int), ("now_median", C.c_int), ("now_normalize", C.c_int)]
+
+
+class CannyFrameParams(C.Structure):
+    _fields_ = [("height", C.c_int), ("width", C.c_int), ("z_scaling", C.c_double), ("low_threshold", C.c_double),
+                ("high_threshold", C.c_double), ("now_normalize", C.c_int), ("norm_lo", C.c_double), ("norm_hi", C.c_double)]
 
 
 _lib = None
@@ -265,6 +271,10 @@ def load():
     L.ea_default_frame_params.restype = None
     L.ea_batch_set_frames.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(FrameParams)]
     L.ea_batch_set_frames_device.argtypes = L.ea_batch_set_frames.argtypes
+    L.ea_default_canny_frame_params.argtypes = [C.POINTER(CannyFrameParams), C.c_int, C.c_int]
+    L.ea_default_canny_frame_params.restype = None
+    L.ea_batch_set_frames_canny.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(CannyFrameParams)]
+    L.ea_batch_set_frames_canny_device.argtypes = L.ea_batch_set_frames_canny.argtypes
     _lib = L
     return L
 
@@ -990,10 +1000,26 @@ class Batch:
         uint8, depth (H, W) uint16 -- of equal extent.  numpy arrays take the host entry; torch tensors on the batch's GPU
         (contiguous; depth as torch.uint16 or int16 bits) take the device entry and are read in place.  ref_bgr and
         ref_depth go together; a side left None is not set."""
-        n = len(self)
         sides = [("ref_bgr", ref_bgr, 3), ("ref_depth", ref_depth, 2), ("now_bgr", now_bgr, 3)]
         if (ref_bgr is None) != (ref_depth is None) or all(v is None for _, v, _ in sides):
             raise ValueError("ref_bgr and ref_depth go together, and one side must be given")
+        shape, on_device, arrays, keep = self._frame_arrays(sides)
+        L = load()
+        prm = FrameParams()
+        L.ea_default_frame_params(C.byref(prm), *(shape or (0, 0)))
+        prm.z_scaling, prm.ref_threshold, prm.now_threshold = float(z_scaling), int(ref_threshold), int(now_threshold)
+        prm.now_median, prm.now_normalize = int(bool(median)), int(bool(normalize))
+        if on_device:
+            import torch
+            torch.cuda.current_stream(self.problems[0].device).synchronize()  # the frames must be complete: the producers do not wait for torch's stream
+        fn = L.ea_batch_set_frames_device if on_device else L.ea_batch_set_frames
+        _check(fn(self._h, arrays["ref_bgr"], arrays["ref_depth"], arrays["now_bgr"], C.byref(prm)))
+
+    def _frame_arrays(self, sides):
+        """the arguments of a batched producer call, sides = [(name, frames or None, kind)] with kind 3: bgr (H, W, 3) uint8,
+        2: depth (H, W) uint16, 1: mask (H, W) uint8 -> (the frames' extent, whether they are device tensors, {name: array of
+        len(self) pointers or None}, what keeps the host frames alive)"""
+        n = len(self)
         frames = {}
         for name, v, _ in sides:
             if v is None:
@@ -1019,14 +1045,14 @@ class Batch:
                     continue  # (a NULL entry: the library refuses the call)
                 if on_device:
                     import torch
-                    want = (torch.uint8,) if ch == 3 else (torch.int16,) + ((torch.uint16,) if hasattr(torch, "uint16") else ())
+                    want = (torch.uint8,) if ch != 2 else (torch.int16,) + ((torch.uint16,) if hasattr(torch, "uint16") else ())
                     if not f.is_cuda or f.device.index != device:
                         raise ValueError("%s[%d]: not a tensor on the batch's GPU %d" % (name, i, device))
                     if f.dtype not in want or not f.is_contiguous():
                         raise ValueError("%s[%d]: a contiguous %s tensor is expected" % (name, i, want[-1]))
                     ptrs[i] = f.data_ptr()
                 else:
-                    f = np.ascontiguousarray(f, dtype=np.uint8 if ch == 3 else np.uint16)
+                    f = np.ascontiguousarray(f, dtype=np.uint8 if ch != 2 else np.uint16)
                     keep.append(f)
                     ptrs[i] = f.ctypes.data
                 hw = tuple(f.shape[:2])
@@ -1034,16 +1060,29 @@ class Batch:
                     raise ValueError("%s[%d]: shape %s; every frame of a call has one extent" % (name, i, tuple(f.shape)))
                 shape = hw
             arrays[name] = ptrs
+        return shape, on_device, arrays, keep
+
+    def set_frames_canny(self, ref_bgr=None, ref_depth=None, now_bgr=None, now_mask=None, z_scaling=5000.0, low=30.0, high=90.0,
+                         normalize=(0.0, 1.0)):
+        """ea_batch_set_frames_canny[_device]: Problem.set_ref_frame_canny + Problem.set_now_frame_canny for every problem of
+        the batch in one launch sequence, bit for bit.  The frames as for set_frames; now_mask: (H, W) uint8 per current
+        frame, edges survive where mask > 1.  normalize: (lo, hi), or None for no normalisation."""
+        sides = [("ref_bgr", ref_bgr, 3), ("ref_depth", ref_depth, 2), ("now_bgr", now_bgr, 3), ("now_mask", now_mask, 1)]
+        if (ref_bgr is None) != (ref_depth is None) or all(v is None for _, v, _ in sides[:3]):
+            raise ValueError("ref_bgr and ref_depth go together, and one side must be given")
+        shape, on_device, arrays, keep = self._frame_arrays(sides)
         L = load()
-        prm = FrameParams()
-        L.ea_default_frame_params(C.byref(prm), *(shape or (0, 0)))
-        prm.z_scaling, prm.ref_threshold, prm.now_threshold = float(z_scaling), int(ref_threshold), int(now_threshold)
-        prm.now_median, prm.now_normalize = int(bool(median)), int(bool(normalize))
+        prm = CannyFrameParams()
+        L.ea_default_canny_frame_params(C.byref(prm), *(shape or (0, 0)))
+        prm.z_scaling, prm.low_threshold, prm.high_threshold = float(z_scaling), float(low), float(high)
+        prm.now_normalize = int(normalize is not None)
+        if normalize is not None:
+            prm.norm_lo, prm.norm_hi = float(normalize[0]), float(normalize[1])
         if on_device:
             import torch
-            torch.cuda.current_stream(device).synchronize()  # the frames must be complete: the producers do not wait for torch's stream
-        fn = L.ea_batch_set_frames_device if on_device else L.ea_batch_set_frames
-        _check(fn(self._h, arrays["ref_bgr"], arrays["ref_depth"], arrays["now_bgr"], C.byref(prm)))
+            torch.cuda.current_stream(self.problems[0].device).synchronize()  # (as in set_frames)
+        fn = L.ea_batch_set_frames_canny_device if on_device else L.ea_batch_set_frames_canny
+        _check(fn(self._h, arrays["ref_bgr"], arrays["ref_depth"], arrays["now_bgr"], arrays["now_mask"], C.byref(prm)))
 
     def residual_quantiles(self, q, t, probs):
         """ea_batch_residual_quantiles at q (n, 4), t (n, 3): (values [n, len(probs)], n_valid [n]), one launch sequence"""

@@ -400,6 +400,7 @@ struct ea_batch {
   // their pinned staging block (the table on its way up, the point counts on their way down); batch_frames_reserve
   unsigned char *d_frames = nullptr, *h_frames = nullptr;
   size_t frames_bytes = 0, h_frames_bytes = 0;
+  int frames_rounds = 0;  // looks at the hysteresis flags of the last batched producer call (ea_batch_set_frames_canny; else 0)
 };
 
 int ea::check_device(int device) {
@@ -1189,6 +1190,8 @@ int ea::batch_frames_reserve(ea_batch *b, size_t device_bytes, size_t pinned_byt
   *pinned_block = b->h_frames;
   return EA_OK;
 }
+
+void ea::batch_frames_set_rounds(ea_batch *b, int rounds) { b->frames_rounds = rounds; }
 
 // (re)build descriptors and the tile list when any problem changed
 static void fill_desc(const ea_problem *p, ProblemDesc &d) {
@@ -3072,6 +3075,7 @@ extern "C" int ea_batch_get_info(const ea_batch *b, const char *key, int64_t *va
   else if (k == "starts_launches") *value = b->last_starts_launches;  // its evaluation launches (lock-step form)
   else if (k == "starts_iterations") *value = b->last_starts_iterations;  // iterations it enqueued (look-ahead included)
   else if (k == "starts_device_ns") *value = b->last_starts_device_ns;    // between the event pair of "starts_events" = 1
+  else if (k == "frames_hysteresis_rounds") *value = b->frames_rounds;    // the last batched producer call's looks at the hysteresis flags, both sides (0: Laplacian)
   else return fail(EA_ERR_INVALID_ARG, "unknown info key: " + k);
   return EA_OK;
 }

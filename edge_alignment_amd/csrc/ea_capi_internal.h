@@ -117,5 +117,7 @@ int check_cov_options(const ea_covariance_options *o);
 void batch_members(ea_batch *b, ea_problem *const **probs, int *count, int *device);
 int batch_frames_reserve(ea_batch *b, size_t device_bytes, size_t pinned_bytes, unsigned char **device_block,
                          unsigned char **pinned_block);
+// ea_batch_get_info's "frames_hysteresis_rounds": looks at the hysteresis flags the batch's last producer call has taken so far
+void batch_frames_set_rounds(ea_batch *b, int rounds);
 
 }  // namespace ea

@@ -14,7 +14,8 @@
 //   mask     np                     launch_threshold_median -> launch_chamfer
 //   mag      4 np                   launch_canny (ints)
 //   dir, label, edges, inv   np     launch_canny; edges -> launch_edge_count_scan / _scatter[_ros], inv -> launch_chamfer
-//   changed  16 ints                launch_canny: one change flag per launch of a hysteresis batch (8 used)
+//   changed  16 ints                launch_canny: one change flag per launch of a hysteresis batch (8 used);
+//                                   launch_canny_frames: two such halves per frame, used by the looks in turn
 //   counts   (nblocks + 1) ints     launch_edge_count_scan / launch_edge_scatter[_ros]: per-block counts, nblocks =
 //                                   ceil(np / 1024), and the total behind them
 //   G, dist  4 np                   launch_chamfer (ints; dist doubles as the float32 distance of the exact transform)

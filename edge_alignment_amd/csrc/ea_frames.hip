@@ -684,9 +684,9 @@ extern "C" int ea_problem_debug_now_frame(ea_problem *p, const uint8_t *bgr, int
 // a batch, the frame a grid dimension of each step (ea_launch.h: FramesLaunch) ----------------------------------------------
 //
 // Memory, owned by the batch (batch_frames_reserve): a device block [count x frame_ws(H, W) | FrameSlot x count] -- 31.5
-// bytes per pixel per frame -- and a pinned block [FrameSlot x count | FrameSlot x count | int x count]: two stagings of the
-// table, because it goes up twice when reference frames are given (the point arrays exist only once the counts are back),
-// and the counts.  Everything runs on the null stream, like the per-problem producers, with two waits: the counts, the end.
+// bytes per pixel per frame -- and a pinned block [FrameSlot x count | FrameSlot x count | int x count | int x 8 count]: two
+// stagings of the table, because it goes up twice when reference frames are given (the point arrays exist only once the
+// counts are back), the counts, and the hysteresis flags of the Canny flavour (further down).  Everything runs on the null stream, like the per-problem producers, with two waits: the counts, the end.
 
 extern "C" void ea_default_frame_params(ea_frame_params *prm, int height, int width) {
   if (!prm) return;
@@ -709,24 +709,42 @@ static int check_device_frame(const void *ptr, int device, size_t align, const c
   return EA_OK;
 }
 
-static int batch_set_frames(ea_batch *b, const uint8_t *const *ref_bgr, const uint16_t *const *ref_depth,
-                            const uint8_t *const *now_bgr, const ea_frame_params *prm, bool on_device) {
-  // every check comes before a device or a problem is touched
-  if (!b || !prm) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+// What the two batched calls (ea_batch_set_frames, ea_batch_set_frames_canny) share: the argument checks, the batch's memory
+// and the slot table, the reference side's counts and point arrays, the current side's images, and the tail.
+struct BatchFrames {
+  ea_problem *const *probs = nullptr;
+  int count = 0, device = 0, H = 0, W = 0, dtype = 0;
+  bool ref = false, now = false, on_device = false;
+  FrameWs ws;
+  size_t n = 0, np = 0, table_bytes = 0;
+  unsigned char *base = nullptr;  // frame 0's workspace; frame i's lies i * ws.total further on (frame(i))
+  FrameSlot *h_slots[2] = {nullptr, nullptr};
+  int *h_totals = nullptr, *h_flags = nullptr;
+  FramesLaunch f;
+  std::vector<FrameSlot> slots;
+  int stage = 0;
+  long long max_total = 0, max_weighted = 0;
+  unsigned char *frame(size_t i) const { return base + i * ws.total; }
+};
+
+// every check that both calls make, none of which touches a device or a problem.  now_mask: nullable (the Canny call's).
+static int batch_frames_check(ea_batch *b, const uint8_t *const *ref_bgr, const uint16_t *const *ref_depth,
+                              const uint8_t *const *now_bgr, const uint8_t *const *now_mask, int H, int W, double z_scaling,
+                              bool on_device, BatchFrames *j) {
   const bool ref = ref_bgr || ref_depth, now = now_bgr != nullptr;
   if (ref && (!ref_bgr || !ref_depth)) return fail(EA_ERR_INVALID_ARG, "ref_bgr and ref_depth are given or NULL together");
   if (!ref && !now) return fail(EA_ERR_INVALID_ARG, "neither reference nor current frames given");
-  const int H = prm->height, W = prm->width;
   if (H < 3 || W < 3 || H > 32768 || W > 32768 || (int64_t)H * W > 0x3fffffff)
     return fail(EA_ERR_INVALID_ARG, "image extent out of range");
   if (now && W > 16384) return fail(EA_ERR_INVALID_ARG, "frames wider than 16384 pixels are not supported by the DT producers");
-  if (!(prm->z_scaling > 0.0)) return fail(EA_ERR_INVALID_ARG, "z_scaling must be > 0");
+  if (!(z_scaling > 0.0)) return fail(EA_ERR_INVALID_ARG, "z_scaling must be > 0");
   ea_problem *const *probs = nullptr;
   int count = 0, device = 0;
   batch_members(b, &probs, &count, &device);
   if (count < 1 || count > 65535) return fail(EA_ERR_INVALID_ARG, "a batched producer call takes 1..65535 problems");
   for (int i = 0; i < count; ++i)
-    if ((ref && (!ref_bgr[i] || !ref_depth[i])) || (now && !now_bgr[i])) return fail(EA_ERR_INVALID_ARG, "NULL frame in a given array");
+    if ((ref && (!ref_bgr[i] || !ref_depth[i])) || (now && !now_bgr[i]) || (now_mask && !now_mask[i]))
+      return fail(EA_ERR_INVALID_ARG, "NULL frame in a given array");
   {
     std::vector<const ea_problem *> sorted(probs, probs + count);
     std::sort(sorted.begin(), sorted.end());
@@ -739,99 +757,161 @@ static int batch_set_frames(ea_batch *b, const uint8_t *const *ref_bgr, const ui
       if (ref) rc = check_device_frame(ref_bgr[i], device, 1, "ref_bgr");
       if (rc == EA_OK && ref) rc = check_device_frame(ref_depth[i], device, 2, "ref_depth");
       if (rc == EA_OK && now) rc = check_device_frame(now_bgr[i], device, 1, "now_bgr");
+      if (rc == EA_OK && now_mask) rc = check_device_frame(now_mask[i], device, 1, "now_mask");
       if (rc != EA_OK) return rc;
     }
+  j->probs = probs; j->count = count; j->device = device; j->H = H; j->W = W; j->dtype = probs[0]->dtype;
+  j->ref = ref; j->now = now; j->on_device = on_device;
+  return EA_OK;
+}
 
-  HIPCHK(hipSetDevice(device));
-  const FrameWs ws = frame_ws(H, W);
-  const size_t n = (size_t)count, np = (size_t)H * W, table_bytes = n * sizeof(FrameSlot);
+// The batch's device block [count x frame_ws(H, W) | FrameSlot x count] and pinned block [FrameSlot x count | FrameSlot x
+// count | int x count | int x count x kCannyFrameFlags] (two stagings of the table, the counts, the hysteresis flags of the
+// Canny call), and the slots filled with what is known before the first launch: where each side's frames are read -- the
+// workspace's copy of a host frame, the caller's device frame in place -- and the problem's camera and depth weighting.
+static int batch_frames_begin(ea_batch *b, const uint8_t *const *ref_bgr, const uint16_t *const *ref_depth,
+                              const uint8_t *const *now_bgr, const uint8_t *const *now_mask, BatchFrames *j) {
+  HIPCHK(hipSetDevice(j->device));
+  j->ws = frame_ws(j->H, j->W);
+  const FrameWs &ws = j->ws;
+  const size_t n = j->n = (size_t)j->count;
+  j->np = (size_t)j->H * j->W;
+  const size_t table_bytes = j->table_bytes = n * sizeof(FrameSlot);
   static_assert(sizeof(FrameSlot) % 8 == 0, "slots follow the 256-byte aligned workspaces");
   unsigned char *d_block = nullptr, *h_block = nullptr;
-  int rc = batch_frames_reserve(b, n * ws.total + table_bytes, 2 * table_bytes + n * sizeof(int), &d_block, &h_block);
+  const int rc = batch_frames_reserve(b, n * ws.total + table_bytes, 2 * table_bytes + n * (1 + kCannyFrameFlags) * sizeof(int),
+                                      &d_block, &h_block);
   if (rc != EA_OK) return rc;
-  unsigned char *base = d_block;  // frame 0's workspace; frame i's lies i * ws.total further on
-  FrameSlot *d_slots = reinterpret_cast<FrameSlot *>(d_block + n * ws.total);
-  FrameSlot *h_slots[2] = {reinterpret_cast<FrameSlot *>(h_block), reinterpret_cast<FrameSlot *>(h_block + table_bytes)};
-  int *h_totals = reinterpret_cast<int *>(h_block + 2 * table_bytes);
-  FramesLaunch f;
-  f.n = count; f.H = H; f.W = W; f.stride = ws.total; f.slots = d_slots;
-  const int dtype = probs[0]->dtype;
-
-  std::vector<FrameSlot> slots(n);
-  std::memset(slots.data(), 0, table_bytes);
+  j->base = d_block;
+  j->h_slots[0] = reinterpret_cast<FrameSlot *>(h_block);
+  j->h_slots[1] = reinterpret_cast<FrameSlot *>(h_block + table_bytes);
+  j->h_totals = reinterpret_cast<int *>(h_block + 2 * table_bytes);
+  j->h_flags = j->h_totals + n;
+  j->f.n = j->count; j->f.H = j->H; j->f.W = j->W; j->f.stride = ws.total;
+  j->f.slots = reinterpret_cast<FrameSlot *>(d_block + n * ws.total);
+  j->slots.resize(n);
+  std::memset(j->slots.data(), 0, table_bytes);
   for (size_t i = 0; i < n; ++i) {
-    ea_problem *p = probs[i];
+    ea_problem *p = j->probs[i];
     p->ws_now_kind = 0;  // (the problem's own workspace holds nothing of this frame pair)
-    FrameSlot &sl = slots[i];
-    unsigned char *wsi = base + i * ws.total;
-    if (ref) sl.bgr[0] = on_device ? ref_bgr[i] : ws.bgr.at(wsi);
-    if (ref) sl.depth = on_device ? ref_depth[i] : ws.depth.at<uint16_t>(wsi);
-    if (now) sl.bgr[1] = on_device ? now_bgr[i] : ws.bgr.at(wsi);
+    FrameSlot &sl = j->slots[i];
+    unsigned char *wsi = j->frame(i);
+    if (j->ref) sl.bgr[0] = j->on_device ? ref_bgr[i] : ws.bgr.at(wsi);
+    if (j->ref) sl.depth = j->on_device ? ref_depth[i] : ws.depth.at<uint16_t>(wsi);
+    if (j->now) sl.bgr[1] = j->on_device ? now_bgr[i] : ws.bgr.at(wsi);
+    if (now_mask) sl.mask = j->on_device ? now_mask[i] : ws.keep.at(wsi);
     sl.fx = p->cam.fx; sl.fy = p->cam.fy; sl.cx = p->cam.cx; sl.cy = p->cam.cy;
     sl.z_ref = p->dw_z_ref; sl.power = p->dw_power;
   }
-  int stage = 0;
-  auto upload_table = [&]() -> hipError_t {  // (a staging block is not written again before a wait has passed)
-    std::memcpy(h_slots[stage], slots.data(), table_bytes);
-    return hipMemcpyAsync(d_slots, h_slots[stage++], table_bytes, hipMemcpyHostToDevice, nullptr);
-  };
+  return EA_OK;
+}
 
-  long long max_total = 0, max_weighted = 0;
-  if (ref) {
-    // strength -> count -> scan for every frame, the counts back in one strided copy: the first wait
-    HIPCHK(upload_table());
-    if (!on_device)
-      for (size_t i = 0; i < n; ++i) {
-        HIPCHK(hipMemcpyAsync(ws.bgr.at(base + i * ws.total), ref_bgr[i], np * 3, hipMemcpyHostToDevice, nullptr));
-        HIPCHK(hipMemcpyAsync(ws.depth.at(base + i * ws.total), ref_depth[i], np * 2, hipMemcpyHostToDevice, nullptr));
-      }
-    HIPCHK(launch_edge_strength_frames(f, 0, ws.gray.at(base), ws.lap.at(base), nullptr));
-    HIPCHK(launch_edge_count_scan_frames(f, ws.lap.at(base), prm->ref_threshold, ws.counts.at(base), nullptr));
-    HIPCHK(hipMemcpy2D(h_totals, sizeof(int), ws.counts.at(base) + frame_ws_blocks(H, W), ws.total, sizeof(int), n,
-                       hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < n; ++i) {
-      ea_problem *p = probs[i];
-      const int total = h_totals[i];
-      rc = ref_points_room(p, total);
-      if (rc != EA_OK) return rc;  // (the problems so far are without points, as a failed per-problem call leaves one)
-      FrameSlot &sl = slots[i];
-      sl.capacity = total;
-      if (total > 0) {
-        sl.x = p->d_x; sl.y = p->d_y; sl.z = p->d_z; sl.w = weights_ptr(p);
-        max_total = std::max<long long>(max_total, total);
-        if (p->dw_power > 0) max_weighted = std::max<long long>(max_weighted, total);
-      }
+// the table on its way up (a staging block is not written again before a wait has passed: it goes up at most twice per call)
+static hipError_t upload_table(BatchFrames *j) {
+  std::memcpy(j->h_slots[j->stage], j->slots.data(), j->table_bytes);
+  return hipMemcpyAsync(const_cast<FrameSlot *>(j->f.slots), j->h_slots[j->stage++], j->table_bytes, hipMemcpyHostToDevice, nullptr);
+}
+
+// host frames into a region of every frame's workspace
+template <typename U, typename V>
+static int upload_frames(const BatchFrames &j, const WsRegion<U> &r, const V *const *frames, size_t bytes) {
+  for (size_t i = 0; i < j.n; ++i) HIPCHK(hipMemcpyAsync(r.at(j.frame(i)), frames[i], bytes, hipMemcpyHostToDevice, nullptr));
+  return EA_OK;
+}
+
+// Reference side, first half: count -> scan on every frame's `edges` region, the counts back in one strided copy (a wait),
+// room for each problem's points and their arrays into its slot
+static int batch_ref_counts(BatchFrames *j, const WsRegion<uint8_t> &edges, int threshold) {
+  const FrameWs &ws = j->ws;
+  HIPCHK(launch_edge_count_scan_frames(j->f, edges.at(j->base), threshold, ws.counts.at(j->base), nullptr));
+  HIPCHK(hipMemcpy2D(j->h_totals, sizeof(int), ws.counts.at(j->base) + frame_ws_blocks(j->H, j->W), ws.total, sizeof(int), j->n,
+                     hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < j->n; ++i) {
+    ea_problem *p = j->probs[i];
+    const int total = j->h_totals[i];
+    const int rc = ref_points_room(p, total);
+    if (rc != EA_OK) return rc;  // (the problems so far are without points, as a failed per-problem call leaves one)
+    FrameSlot &sl = j->slots[i];
+    sl.capacity = total;
+    if (total > 0) {
+      sl.x = p->d_x; sl.y = p->d_y; sl.z = p->d_z; sl.w = weights_ptr(p);
+      j->max_total = std::max<long long>(j->max_total, total);
+      if (p->dw_power > 0) j->max_weighted = std::max<long long>(j->max_weighted, total);
     }
   }
+  return EA_OK;
+}
+
+// Current side: every problem's image into its slot (a failure: the reference frames are put in place, no current frame is)
+static int batch_alloc_dts(BatchFrames *j) {
   int rc_dt = EA_OK;
-  if (now)
-    for (size_t i = 0; i < n && rc_dt == EA_OK; ++i) {
-      ea_problem *p = probs[i];
-      rc_dt = alloc_dt(p, W, H);
-      slots[i].dt = p->d_dt; slots[i].dt32 = p->dtype == EA_F64 ? p->d_dt32 : nullptr; slots[i].pitch = p->pitch;
-    }
-  HIPCHK(upload_table());
-  if (ref) {
-    // a call whose frames have no point at all launches nothing that writes points; a frame without points among others
-    // has capacity 0 in its slot
-    if (max_total > 0) HIPCHK(launch_edge_scatter_frames(dtype, f, ws.lap.at(base), prm->ref_threshold, ws.counts.at(base), prm->z_scaling, nullptr));
-    HIPCHK(launch_depth_weights_frames(dtype, f, max_weighted, nullptr));
+  for (size_t i = 0; i < j->n && rc_dt == EA_OK; ++i) {
+    ea_problem *p = j->probs[i];
+    rc_dt = alloc_dt(p, j->W, j->H);
+    j->slots[i].dt = p->d_dt; j->slots[i].dt32 = p->dtype == EA_F64 ? p->d_dt32 : nullptr; j->slots[i].pitch = p->pitch;
   }
-  if (now && rc_dt == EA_OK) {
-    if (!on_device)
-      for (size_t i = 0; i < n; ++i)
-        HIPCHK(hipMemcpyAsync(ws.bgr.at(base + i * ws.total), now_bgr[i], np * 3, hipMemcpyHostToDevice, nullptr));
-    HIPCHK(launch_edge_strength_frames(f, 1, ws.gray.at(base), ws.lap.at(base), nullptr));
-    HIPCHK(launch_threshold_median_frames(f, ws.lap.at(base), prm->now_threshold, prm->now_median, ws.mask.at(base), nullptr));
-    HIPCHK(launch_chamfer_frames(f, ws.mask.at(base), ws.G.at(base), ws.scan.at(base), ws.dist.at(base), ws.minmax.at(base), nullptr));
-    HIPCHK(launch_dt_store_frames(dtype, f, ws.dist.at(base), ws.minmax.at(base), prm->now_normalize, 0.0, 1.0, nullptr));
-  }
-  HIPCHK(hipDeviceSynchronize());  // the second wait
-  for (size_t i = 0; i < n; ++i) {
-    if (ref) ref_points_landed(probs[i], slots[i].capacity);
-    if (now && rc_dt == EA_OK) dt_landed(probs[i]);
+  return rc_dt;
+}
+
+// Reference side, second half: the points and their depth weights.  A call whose frames have no point at all launches
+// nothing that writes points; a frame without points among others has capacity 0 in its slot
+static int batch_ref_scatter(const BatchFrames &j, const WsRegion<uint8_t> &edges, int threshold, double z_scaling) {
+  if (j.max_total > 0)
+    HIPCHK(launch_edge_scatter_frames(j.dtype, j.f, edges.at(j.base), threshold, j.ws.counts.at(j.base), z_scaling, nullptr));
+  HIPCHK(launch_depth_weights_frames(j.dtype, j.f, j.max_weighted, nullptr));
+  return EA_OK;
+}
+
+// the last wait, and the problems' bookkeeping
+static int batch_frames_end(const BatchFrames &j, int rc_dt) {
+  HIPCHK(hipDeviceSynchronize());
+  for (size_t i = 0; i < j.n; ++i) {
+    if (j.ref) ref_points_landed(j.probs[i], j.slots[i].capacity);
+    if (j.now && rc_dt == EA_OK) dt_landed(j.probs[i]);
   }
   return rc_dt;  // (a failed alloc_dt: the reference frames are in place, no current frame is)
+}
+
+static int batch_set_frames(ea_batch *b, const uint8_t *const *ref_bgr, const uint16_t *const *ref_depth,
+                            const uint8_t *const *now_bgr, const ea_frame_params *prm, bool on_device) {
+  // every check comes before a device or a problem is touched
+  if (!b || !prm) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  BatchFrames j;
+  int rc = batch_frames_check(b, ref_bgr, ref_depth, now_bgr, nullptr, prm->height, prm->width, prm->z_scaling, on_device, &j);
+  if (rc == EA_OK) rc = batch_frames_begin(b, ref_bgr, ref_depth, now_bgr, nullptr, &j);
+  if (rc != EA_OK) return rc;
+  batch_frames_set_rounds(b, 0);  // (no hysteresis in this chain)
+  const FrameWs &ws = j.ws;
+  unsigned char *base = j.base;
+  if (j.ref) {
+    // strength -> count -> scan for every frame, the counts back in one strided copy: the first wait
+    HIPCHK(upload_table(&j));
+    if (!on_device) {
+      rc = upload_frames(j, ws.bgr, ref_bgr, j.np * 3);
+      if (rc == EA_OK) rc = upload_frames(j, ws.depth, ref_depth, j.np * 2);
+      if (rc != EA_OK) return rc;
+    }
+    HIPCHK(launch_edge_strength_frames(j.f, 0, ws.gray.at(base), ws.lap.at(base), nullptr));
+    rc = batch_ref_counts(&j, ws.lap, prm->ref_threshold);
+    if (rc != EA_OK) return rc;
+  }
+  const int rc_dt = j.now ? batch_alloc_dts(&j) : EA_OK;
+  HIPCHK(upload_table(&j));
+  if (j.ref) {
+    rc = batch_ref_scatter(j, ws.lap, prm->ref_threshold, prm->z_scaling);
+    if (rc != EA_OK) return rc;
+  }
+  if (j.now && rc_dt == EA_OK) {
+    if (!on_device) {
+      rc = upload_frames(j, ws.bgr, now_bgr, j.np * 3);
+      if (rc != EA_OK) return rc;
+    }
+    HIPCHK(launch_edge_strength_frames(j.f, 1, ws.gray.at(base), ws.lap.at(base), nullptr));
+    HIPCHK(launch_threshold_median_frames(j.f, ws.lap.at(base), prm->now_threshold, prm->now_median, ws.mask.at(base), nullptr));
+    HIPCHK(launch_chamfer_frames(j.f, ws.mask.at(base), ws.G.at(base), ws.scan.at(base), ws.dist.at(base), ws.minmax.at(base), nullptr));
+    HIPCHK(launch_dt_store_frames(j.dtype, j.f, ws.dist.at(base), ws.minmax.at(base), prm->now_normalize, 0.0, 1.0, nullptr));
+  }
+  return batch_frames_end(j, rc_dt);
 }
 
 extern "C" int ea_batch_set_frames(ea_batch *b, const uint8_t *const *ref_bgr, const uint16_t *const *ref_depth,
@@ -842,6 +922,92 @@ extern "C" int ea_batch_set_frames(ea_batch *b, const uint8_t *const *ref_bgr, c
 extern "C" int ea_batch_set_frames_device(ea_batch *b, const uint8_t *const *ref_bgr, const uint16_t *const *ref_depth,
                                           const uint8_t *const *now_bgr, const ea_frame_params *prm) {
   return batch_set_frames(b, ref_bgr, ref_depth, now_bgr, prm, true);
+}
+
+// ---- the Canny flavour of the batched producers: ea_problem_set_ref_frame_canny + ea_problem_set_now_frame_canny for every
+// problem of a batch.  Either side runs launch_canny_frames -- 3 launches, then 8 hysteresis launches and one wait per look at
+// the frames' flags, then the finish -- into the frames' `edges` / `inv`; from there on the steps are the Laplacian call's,
+// on other regions: count / scan / scatter on `edges` with threshold 0, chamfer on `inv`.  Waits: one per look, the counts,
+// the end.
+
+extern "C" void ea_default_canny_frame_params(ea_canny_frame_params *prm, int height, int width) {
+  if (!prm) return;
+  prm->height = height; prm->width = width;
+  prm->z_scaling = 5000.0;
+  prm->low_threshold = 30.0; prm->high_threshold = 90.0;
+  prm->now_normalize = 1;
+  prm->norm_lo = 0.0; prm->norm_hi = 1.0;
+}
+
+static int batch_set_frames_canny(ea_batch *b, const uint8_t *const *ref_bgr, const uint16_t *const *ref_depth,
+                                  const uint8_t *const *now_bgr, const uint8_t *const *now_mask, const ea_canny_frame_params *prm,
+                                  bool on_device) {
+  // every check comes before a device or a problem is touched
+  if (!b || !prm) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (now_mask && !now_bgr) return fail(EA_ERR_INVALID_ARG, "now_mask without now_bgr");
+  int lo, hi;
+  int rc = canny_thresholds(prm->low_threshold, prm->high_threshold, &lo, &hi);
+  if (rc != EA_OK) return rc;
+  if (prm->now_normalize && (!(std::fabs(prm->norm_lo) <= DBL_MAX) || !(std::fabs(prm->norm_hi) <= DBL_MAX)))
+    return fail(EA_ERR_INVALID_ARG, "normalisation range must be finite");
+  if (!(prm->z_scaling > 0.0) || !(prm->z_scaling <= DBL_MAX)) return fail(EA_ERR_INVALID_ARG, "z_scaling must be > 0 and finite");
+  BatchFrames j;
+  rc = batch_frames_check(b, ref_bgr, ref_depth, now_bgr, now_mask, prm->height, prm->width, prm->z_scaling, on_device, &j);
+  if (rc == EA_OK) rc = batch_frames_begin(b, ref_bgr, ref_depth, now_bgr, now_mask, &j);
+  if (rc != EA_OK) return rc;
+  const FrameWs &ws = j.ws;
+  unsigned char *base = j.base;
+  int looks = 0, total_looks = 0;
+  batch_frames_set_rounds(b, 0);
+  auto canny = [&](int side, bool masked) {
+    const hipError_t e = launch_canny_frames(j.f, side, masked, lo, hi, ws.gray.at(base), ws.mag.at(base), ws.dir.at(base), ws.label.at(base),
+                                             ws.edges.at(base), ws.inv.at(base), ws.changed.at(base), j.h_flags, &looks, nullptr);
+    if (e == hipSuccess) batch_frames_set_rounds(b, total_looks += looks);
+    return e;
+  };
+  if (j.ref) {
+    HIPCHK(upload_table(&j));
+    if (!on_device) {
+      rc = upload_frames(j, ws.bgr, ref_bgr, j.np * 3);
+      if (rc == EA_OK) rc = upload_frames(j, ws.depth, ref_depth, j.np * 2);
+      if (rc != EA_OK) return rc;
+    }
+    HIPCHK(canny(0, false));
+    // ref: utils.cpp:441 -- all_grad(i) > 0 && Z > 0 on the 0/255 edge map
+    rc = batch_ref_counts(&j, ws.edges, 0);
+    if (rc != EA_OK) return rc;
+  }
+  const int rc_dt = j.now ? batch_alloc_dts(&j) : EA_OK;
+  HIPCHK(upload_table(&j));
+  if (j.ref) {
+    rc = batch_ref_scatter(j, ws.edges, 0, prm->z_scaling);
+    if (rc != EA_OK) return rc;
+  }
+  if (j.now && rc_dt == EA_OK) {
+    if (!on_device) {
+      rc = upload_frames(j, ws.bgr, now_bgr, j.np * 3);
+      if (rc == EA_OK && now_mask) rc = upload_frames(j, ws.keep, now_mask, j.np);
+      if (rc != EA_OK) return rc;
+    }
+    // (the scatter above reads the reference side's `edges` and is in front of this on the same stream)
+    HIPCHK(canny(1, now_mask != nullptr));
+    HIPCHK(launch_chamfer_frames(j.f, ws.inv.at(base), ws.G.at(base), ws.scan.at(base), ws.dist.at(base), ws.minmax.at(base), nullptr));
+    HIPCHK(launch_dt_store_frames(j.dtype, j.f, ws.dist.at(base), ws.minmax.at(base), prm->now_normalize, prm->norm_lo, prm->norm_hi,
+                                  nullptr));
+  }
+  return batch_frames_end(j, rc_dt);
+}
+
+extern "C" int ea_batch_set_frames_canny(ea_batch *b, const uint8_t *const *ref_bgr, const uint16_t *const *ref_depth,
+                                         const uint8_t *const *now_bgr, const uint8_t *const *now_mask,
+                                         const ea_canny_frame_params *prm) {
+  return batch_set_frames_canny(b, ref_bgr, ref_depth, now_bgr, now_mask, prm, false);
+}
+
+extern "C" int ea_batch_set_frames_canny_device(ea_batch *b, const uint8_t *const *ref_bgr, const uint16_t *const *ref_depth,
+                                                const uint8_t *const *now_bgr, const uint8_t *const *now_mask,
+                                                const ea_canny_frame_params *prm) {
+  return batch_set_frames_canny(b, ref_bgr, ref_depth, now_bgr, now_mask, prm, true);
 }
 
 // read back what the problem holds in HBM: points as n x 3 doubles, DT as H x W doubles ([v][u])

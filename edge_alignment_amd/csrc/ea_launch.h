@@ -108,6 +108,7 @@ struct FrameSlot {
   const uint8_t *bgr[2];  // the colour frame of the reference ([0]) / current ([1]) side: the workspace's copy of a host
                           // frame, or the caller's device frame read in place
   const uint16_t *depth;  // likewise
+  const uint8_t *mask;    // likewise: the current side's mask of ea_batch_set_frames_canny (NULL without one)
   void *x, *y, *z, *w;    // the problem's point arrays and its weights (problem dtype), room for `capacity` points
   void *dt;               // the problem's padded DT image and, for an fp64 problem, its float32 mirror (else NULL)
   float *dt32;
@@ -237,6 +238,14 @@ hipError_t launch_dt_store_frames(int dtype, const FramesLaunch &f, const int *d
 hipError_t launch_edge_count_scan_frames(const FramesLaunch &f, const uint8_t *lap, int thr, int *block_counts, hipStream_t s);
 hipError_t launch_edge_scatter_frames(int dtype, const FramesLaunch &f, const uint8_t *lap, int thr, const int *block_offsets,
                                       double z_scaling, hipStream_t s);
+// launch_canny's chain (blur 3x3 -> gray -> Canny(low, high) [-> AND mask > 1, `masked`]) for f.n frames: every frame's edge
+// map in its `edges`, the inverse in its `inv`.  changed: frame 0's 16 flag ints (kCannyFrameFlags of them travel per look);
+// h_flags: f.n x kCannyFrameFlags ints of pinned memory, into which one strided copy brings every frame's flags per look.  The
+// hysteresis converges per frame; the loop ends when every frame has had a quiet launch.  Waits for `s`; *looks: how many
+// looks at the flags it took.
+constexpr int kCannyFrameFlags = 8;
+hipError_t launch_canny_frames(const FramesLaunch &f, int side, int masked, int low, int high, uint8_t *gray, int *mag, uint8_t *dir,
+                               uint8_t *label, uint8_t *edges, uint8_t *inv, int *changed, int *h_flags, int *looks, hipStream_t s);
 // ea_kernels.hip: ea_depth_weights_kernel's body for the frames whose slot has power > 0, max_n = the largest capacity among them
 hipError_t launch_depth_weights_frames(int dtype, const FramesLaunch &f, long long max_n, hipStream_t s);
 }  // namespace ea

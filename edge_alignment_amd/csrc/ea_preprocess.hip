@@ -132,8 +132,11 @@ __global__ void ea_threshold_median_frames_kernel(const uint8_t *lap, int H, int
 
 // ---- Canny flavour (ref: utils.cpp:87-94 / :397-404: blur 3x3 -> CV_RGB2GRAY -> Canny(30, 90)) ----------------
 
+// The Canny chain follows the pattern of the Laplacian chain above: one __device__ body per step, ea_<step>_kernel for the
+// per-problem producers, ea_<step>_batch_kernel for frame blockIdx.z of ea_batch_set_frames_canny.
+
 // box blur (3 channels) + gray in one pass
-__global__ void ea_boxblur_gray_kernel(const uint8_t *__restrict__ bgr, int H, int W, uint8_t *__restrict__ gray) {
+__device__ __forceinline__ void boxblur_gray_body(const uint8_t *__restrict__ bgr, int H, int W, uint8_t *__restrict__ gray) {
   const int u = blockIdx.x * blockDim.x + threadIdx.x, v = blockIdx.y;
   if (u >= W) return;
   int acc[3] = {0, 0, 0};
@@ -150,11 +153,17 @@ __global__ void ea_boxblur_gray_kernel(const uint8_t *__restrict__ bgr, int H, i
   const int c0 = (acc[0] + 4) / 9, c1 = (acc[1] + 4) / 9, c2 = (acc[2] + 4) / 9;
   gray[(size_t)v * W + u] = (uint8_t)((4899 * c0 + 9617 * c1 + 1868 * c2 + 8192) >> 14);
 }
+__global__ void ea_boxblur_gray_kernel(const uint8_t *__restrict__ bgr, int H, int W, uint8_t *__restrict__ gray) {
+  boxblur_gray_body(bgr, H, W, gray);
+}
+__global__ void ea_boxblur_gray_batch_kernel(const FrameSlot *__restrict__ slots, int side, int H, int W, uint8_t *gray, size_t stride) {
+  boxblur_gray_body(slots[blockIdx.z].bgr[side], H, W, frame_ptr(gray, stride));
+}
 
 // Sobel 3x3 (replicated border) -> L1 magnitude (int16 range) and the packed direction class needed by the
 // suppression test: bits 0-1 = 0 horizontal / 1 vertical / 2 diagonal, bit 2 = sign s of the diagonal (1: s = -1)
-__global__ void ea_sobel_mag_kernel(const uint8_t *__restrict__ gray, int H, int W, int *__restrict__ mag,
-                                    uint8_t *__restrict__ dir) {
+__device__ __forceinline__ void sobel_mag_body(const uint8_t *__restrict__ gray, int H, int W, int *__restrict__ mag,
+                                               uint8_t *__restrict__ dir) {
   const int u = blockIdx.x * blockDim.x + threadIdx.x, v = blockIdx.y;
   if (u >= W) return;
   const int ym = max(v - 1, 0), yp = min(v + 1, H - 1), xm = max(u - 1, 0), xp = min(u + 1, W - 1);
@@ -171,6 +180,13 @@ __global__ void ea_sobel_mag_kernel(const uint8_t *__restrict__ gray, int H, int
   else if (y > tg22x + (x << 16)) cls = 1;
   else cls = 2 | (((dx ^ dy) < 0) ? 4 : 0);
   dir[(size_t)v * W + u] = (uint8_t)cls;
+}
+__global__ void ea_sobel_mag_kernel(const uint8_t *__restrict__ gray, int H, int W, int *__restrict__ mag,
+                                    uint8_t *__restrict__ dir) {
+  sobel_mag_body(gray, H, W, mag, dir);
+}
+__global__ void ea_sobel_mag_batch_kernel(const uint8_t *gray, int H, int W, int *mag, uint8_t *dir, size_t stride) {
+  sobel_mag_body(frame_ptr(gray, stride), H, W, frame_ptr(mag, stride), frame_ptr(dir, stride));
 }
 
 // ROS flavour (ref: src/SolveEA.cpp:46, :102): cv::Canny on the 3-channel image with L2gradient = true -- the channel
@@ -200,8 +216,8 @@ __global__ void ea_sobel_mag_l2_bgr_kernel(const uint8_t *__restrict__ bgr, int 
 }
 
 // non-maximum suppression + double threshold: label 2 = strong, 0 = candidate, 1 = no edge
-__global__ void ea_canny_nms_kernel(const int *__restrict__ mag, const uint8_t *__restrict__ dir, int H, int W, int low,
-                                    int high, uint8_t *__restrict__ label, int *__restrict__ flags, int nflags) {
+__device__ __forceinline__ void canny_nms_body(const int *__restrict__ mag, const uint8_t *__restrict__ dir, int H, int W, int low,
+                                               int high, uint8_t *__restrict__ label, int *__restrict__ flags, int nflags) {
   if (blockIdx.x == 0 && blockIdx.y == 0 && (int)threadIdx.x < nflags) flags[threadIdx.x] = 0;  // hysteresis change flags
   const int u = blockIdx.x * blockDim.x + threadIdx.x, v = blockIdx.y;
   if (u >= W) return;
@@ -220,6 +236,16 @@ __global__ void ea_canny_nms_kernel(const int *__restrict__ mag, const uint8_t *
     if (is_max) out = m > high ? 2 : 0;
   }
   label[(size_t)v * W + u] = out;
+}
+__global__ void ea_canny_nms_kernel(const int *__restrict__ mag, const uint8_t *__restrict__ dir, int H, int W, int low,
+                                    int high, uint8_t *__restrict__ label, int *__restrict__ flags, int nflags) {
+  canny_nms_body(mag, dir, H, W, low, high, label, flags, nflags);
+}
+// (each frame zeroes its own flags: the body's test names block (0, 0) of the frame's own x-y plane)
+__global__ void ea_canny_nms_batch_kernel(const int *mag, const uint8_t *dir, int H, int W, int low, int high, uint8_t *label,
+                                          int *flags, int nflags, size_t stride) {
+  canny_nms_body(frame_ptr(mag, stride), frame_ptr(dir, stride), H, W, low, high, frame_ptr(label, stride),
+                 frame_ptr(flags, stride), nflags);
 }
 
 // hysteresis: candidates 8-connected to a strong pixel become strong.  One WAVEFRONT owns a tile of 62 x 62 pixels
@@ -249,9 +275,8 @@ __device__ __forceinline__ unsigned long long hyst_fill(unsigned long long seed,
   return g | h;
 }
 
-__global__ __launch_bounds__(256) void ea_canny_hysteresis_kernel(uint8_t *__restrict__ label, int H, int W, int tiles_x,
-                                                                  int tiles, const int *__restrict__ prev_changed,
-                                                                  int *__restrict__ changed) {
+__device__ __forceinline__ void canny_hysteresis_body(uint8_t *__restrict__ label, int H, int W, int tiles_x, int tiles,
+                                                      const int *__restrict__ prev_changed, int *__restrict__ changed) {
   // launches are enqueued in batches without a host look in between: once a launch has changed nothing the edge set
   // is final and the launches queued behind it have nothing to do
   if (prev_changed && *prev_changed == 0) return;
@@ -302,16 +327,45 @@ __global__ __launch_bounds__(256) void ea_canny_hysteresis_kernel(uint8_t *__res
   }
   if (lane == 0) atomicOr(changed, 1);
 }
+__global__ __launch_bounds__(256) void ea_canny_hysteresis_kernel(uint8_t *__restrict__ label, int H, int W, int tiles_x,
+                                                                  int tiles, const int *__restrict__ prev_changed,
+                                                                  int *__restrict__ changed) {
+  canny_hysteresis_body(label, H, W, tiles_x, tiles, prev_changed, changed);
+}
+// The batched form: every frame sweeps towards its own fixed point, with its own flags -- the 16 ints of its `changed` region,
+// as two halves of kHystBatch that the looks of the host use in turn.  Launch k of a look raises flag `cur` = half * 8 + k of
+// its frame and returns at once when flag `prev` of its frame is down: the flag of launch k - 1 of the same look, or for
+// k = 0 that of the last launch of the look before, in the other half (prev < 0: the very first launch).  So the chain of
+// launches runs on across the looks, and a frame that has reached its fixed point -- one quiet launch -- keeps every later
+// launch of every later look at that early exit: the flags behind a quiet launch all stay down.  `clear` is the flag of launch
+// k in the other half, which the look after this one will use and nothing reads any more: it is lowered here, early exit or
+// not, so that no memset is needed between looks.  A frame touches no flags but its own.
+__global__ __launch_bounds__(256) void ea_canny_hysteresis_batch_kernel(uint8_t *label, int H, int W, int tiles_x, int tiles,
+                                                                        int *flags, int prev, int cur, int clear, size_t stride) {
+  int *c = frame_ptr(flags, stride);
+  if (blockIdx.x == 0 && threadIdx.x == 0) c[clear] = 0;
+  canny_hysteresis_body(frame_ptr(label, stride), H, W, tiles_x, tiles, prev >= 0 ? c + prev : nullptr, c + cur);
+}
 
 // labels -> the CV_8U edge map (255 on edges) [AND the optional mask: inputmask > 1] and the DT source mask
 // (0 on edges, 255 elsewhere = `255 - edges`)
-__global__ void ea_canny_finish_kernel(const uint8_t *__restrict__ label, const uint8_t *__restrict__ keep /*nullable*/,
-                                       int npix, uint8_t *__restrict__ edges, uint8_t *__restrict__ inv) {
+__device__ __forceinline__ void canny_finish_body(const uint8_t *__restrict__ label, const uint8_t *__restrict__ keep /*nullable*/,
+                                                  int npix, uint8_t *__restrict__ edges, uint8_t *__restrict__ inv) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= npix) return;
   const bool e = label[i] == 2 && (!keep || keep[i] > 1);
   edges[i] = e ? 255 : 0;
   inv[i] = e ? 0 : 255;
+}
+__global__ void ea_canny_finish_kernel(const uint8_t *__restrict__ label, const uint8_t *__restrict__ keep /*nullable*/,
+                                       int npix, uint8_t *__restrict__ edges, uint8_t *__restrict__ inv) {
+  canny_finish_body(label, keep, npix, edges, inv);
+}
+// (masked: the frame's mask out of its slot, the workspace's copy of a host mask or the caller's device mask)
+__global__ void ea_canny_finish_batch_kernel(const FrameSlot *__restrict__ slots, int masked, const uint8_t *label, int npix,
+                                             uint8_t *edges, uint8_t *inv, size_t stride) {
+  canny_finish_body(frame_ptr(label, stride), masked ? slots[blockIdx.z].mask : nullptr, npix, frame_ptr(edges, stride),
+                    frame_ptr(inv, stride));
 }
 
 // G(x,y) = |y - y'| to the nearest feature pixel (mask == 0) of column x; kNoFeature if none.
@@ -936,6 +990,46 @@ hipError_t launch_dt_store_frames(int dtype, const FramesLaunch &f, const int *d
     hipLaunchKernelGGL((ea_dt_store_frames_kernel<float>), grid, block, 0, s, f.slots, dist_fix, f.H, f.W, minmax, normalize, lo, hi, f.stride);
   else
     hipLaunchKernelGGL((ea_dt_store_frames_kernel<double>), grid, block, 0, s, f.slots, dist_fix, f.H, f.W, minmax, normalize, lo, hi, f.stride);
+  return hipGetLastError();
+}
+
+hipError_t launch_canny_frames(const FramesLaunch &f, int side, int masked, int low, int high, uint8_t *gray, int *mag, uint8_t *dir,
+                               uint8_t *label, uint8_t *edges, uint8_t *inv, int *changed, int *h_flags, int *looks, hipStream_t s) {
+  static_assert(kCannyFrameFlags == kHystBatch, "a look brings back one flag per launch of a hysteresis batch");
+  if (!frames_ok(f) || !h_flags) return hipErrorInvalidValue;
+  const int H = f.H, W = f.W;
+  dim3 block(256), grid((W + 255) / 256, H, f.n);
+  hipLaunchKernelGGL(ea_boxblur_gray_batch_kernel, grid, block, 0, s, f.slots, side, H, W, gray, f.stride);
+  hipLaunchKernelGGL(ea_sobel_mag_batch_kernel, grid, block, 0, s, gray, H, W, mag, dir, f.stride);
+  hipLaunchKernelGGL(ea_canny_nms_batch_kernel, grid, block, 0, s, mag, dir, H, W, low, high, label, changed, 2 * kHystBatch, f.stride);
+  // hysteresis: launch_canny's batches of eight launches for all frames at once; the flags of a look are those of its half of
+  // every frame's 16 (ea_canny_hysteresis_batch_kernel), and one strided copy brings the n x 8 of them back
+  const int tiles_x = (W + kHystTile - 1) / kHystTile, tiles = tiles_x * ((H + kHystTile - 1) / kHystTile);
+  const dim3 tgrid((tiles + 3) / 4, 1, f.n);
+  int n_looks = 0;
+  for (;;) {
+    const int cur = (n_looks & 1) * kHystBatch, other = kHystBatch - cur;
+    for (int k = 0; k < kHystBatch; ++k)
+      hipLaunchKernelGGL(ea_canny_hysteresis_batch_kernel, tgrid, dim3(256), 0, s, label, H, W, tiles_x, tiles, changed,
+                         k > 0 ? cur + k - 1 : (n_looks > 0 ? other + kHystBatch - 1 : -1), cur + k, other + k, f.stride);
+    hipError_t e = hipMemcpy2DAsync(h_flags, kHystBatch * sizeof(int), changed + cur, f.stride, kHystBatch * sizeof(int), (size_t)f.n,
+                                    hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return e;
+    ++n_looks;
+    bool all_quiet = true;  // every frame has a launch in this look that changed nothing (or did not have to run)
+    for (int i = 0; i < f.n && all_quiet; ++i) {
+      bool quiet = false;
+      for (int k = 0; k < kHystBatch; ++k) quiet = quiet || h_flags[(size_t)i * kHystBatch + k] == 0;
+      all_quiet = quiet;
+    }
+    if (all_quiet) break;
+    if ((long long)n_looks * kHystBatch > ((long long)H * W) / 256 + 64) return hipErrorUnknown;  // launch_canny's safety net
+  }
+  if (looks) *looks = n_looks;
+  const int npix = H * W;
+  hipLaunchKernelGGL(ea_canny_finish_batch_kernel, dim3((npix + 255) / 256, 1, f.n), block, 0, s, f.slots, masked, label, npix, edges,
+                     inv, f.stride);
   return hipGetLastError();
 }
 

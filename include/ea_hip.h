@@ -704,6 +704,51 @@ int ea_problem_debug_now_frame_canny(ea_problem *p, const uint8_t *bgr, const ui
                                      double low_threshold, double high_threshold, int normalize, double norm_lo,
                                      double norm_hi, uint8_t *edges_out, int32_t *chamfer_fix_out, float *dt_out,
                                      int *hysteresis_launches);
+/* The two Canny producers above for EVERY problem of a batch in one launch sequence: ea_batch_set_frames for the flavour of
+ * every standalone test after edge_align_test1 and of the tracker's flavour 1.  N = ea_batch_count(b) frame pairs of equal
+ * extent, the frame a grid dimension of each step.  The hysteresis converges per frame: its launches go out eight at a time
+ * for all frames, each frame with change flags of its own, and the host looks at all N x 8 flags at once; a frame that has
+ * reached its fixed point costs the later launches an early exit, and the call goes on when every frame has.  Per side 4
+ * launches, 8 per look (one look for most frames, a second for chains that cross many 62 x 62 tiles), then 3 (reference:
+ * count, scan, scatter; 4 with depth weighting) or 4 (current: the chamfer's three, the store); waits: one per look, the
+ * counts, the end -- for the whole batch, where the per-problem calls cost the same launches and at least four waits per PAIR.
+ *
+ * The pointer arrays, the two sides and what a NULL side means are ea_batch_set_frames'.  now_mask (nullable): N masks of
+ * H x W bytes for the current frames, edges survive where mask > 1; without now_bgr it is an error, and a given array has no
+ * NULL entry.
+ *
+ * After the call every problem p_i is in the state that
+ *     ea_problem_set_ref_frame_canny(p_i, ref_bgr[i], ref_depth[i], height, width, z_scaling, low_threshold, high_threshold);
+ *     ea_problem_set_now_frame_canny(p_i, now_bgr[i], now_mask ? now_mask[i] : NULL, height, width, low_threshold,
+ *                                    high_threshold, now_normalize, norm_lo, norm_hi);
+ * leave it in, in that order, bit for bit: the same points in the same order, the same padded DT image and float32 mirror
+ * (exact), the same depth weights where the problem has ea_problem_set_depth_weighting, the version bumped.  (The fixed point
+ * of the hysteresis is unique, so the edge map does not depend on how many sweeps a frame was given.)  As with
+ * ea_batch_set_frames the frames pass through the batch's workspace, the same one, and what a problem's own producer workspace
+ * holds afterwards is unspecified: the tracker's short cut from the last current frame does not apply.
+ *
+ * EA_ERR_INVALID_ARG, checked before a device or a problem is touched (batch and problems unchanged): everything
+ * ea_batch_set_frames checks (masks included, for the _device form too); a NaN threshold; z_scaling not finite; a
+ * non-finite norm_lo or norm_hi when now_normalize is set; now_mask without now_bgr.  EA_ERR_ALLOC and a failure past the
+ * checks: as for ea_batch_set_frames.  ea_batch_get_info("frames_hysteresis_rounds"): the looks at the flags the last call
+ * took, both sides summed (0 after ea_batch_set_frames).
+ *
+ * ea_batch_set_frames_canny: host pointers.  ea_batch_set_frames_canny_device: every entry a device pointer on the batch's
+ * device, read in place, complete when the call is made (see ea_batch_set_frames_device). */
+typedef struct {
+  int height, width;                    /* of every frame of the call */
+  double z_scaling;                     /* ea_problem_set_ref_frame_canny's (5000) */
+  double low_threshold, high_threshold; /* both sides (30, 90); ordered and floored as the per-problem calls do */
+  int now_normalize;                    /* 1 */
+  double norm_lo, norm_hi;              /* (0, 1); get_distance_transform2_masked uses (0, 255) */
+} ea_canny_frame_params;
+void ea_default_canny_frame_params(ea_canny_frame_params *prm, int height, int width);
+int ea_batch_set_frames_canny(ea_batch *b, const uint8_t *const *ref_bgr, const uint16_t *const *ref_depth,
+                              const uint8_t *const *now_bgr, const uint8_t *const *now_mask,
+                              const ea_canny_frame_params *prm);
+int ea_batch_set_frames_canny_device(ea_batch *b, const uint8_t *const *ref_bgr, const uint16_t *const *ref_depth,
+                                     const uint8_t *const *now_bgr, const uint8_t *const *now_mask,
+                                     const ea_canny_frame_params *prm);
 /* ROS flavour of the two producers (src/SolveEA.cpp:29-119): cv::Canny(rgb, 150, 100, 3, true) on the 3-channel image
  * (per pixel the channel with the largest dx^2 + dy^2; squared thresholds).
  * setRefFrame (:29-82): every edge pixel gives a point; depth: H x W float32 in metres, Z == 0 -> 1.0. */

@@ -1,0 +1,521 @@
+"""ea_batch_set_frames_canny / Batch.set_frames_canny: the Canny producers for every problem of a batch in one launch
+sequence, the frame as blockIdx.z of each step.  The reference is always the per-problem producers
+(Problem.set_ref_frame_canny + Problem.set_now_frame_canny) on fresh problems, compared with np.array_equal on get_points(),
+get_dt(), get_weights() and num_points: bit equality, no tolerance.  oracle/preprocess_np.py is a second check on one
+bundled pair.
+
+Shapes are the smallest at which the frame indexing can go wrong: (3, 3) all border; (37, 70) two hysteresis tiles of 62
+across, two 32-row column segments, two full 1024-pixel scan blocks and a partial one; (64, 257) 2 x 5 tiles, past the
+256-lane row block.  Frames of one call differ in kind, so that a frame reading its neighbour's workspace, flags, minmax
+pair, counts or slot cannot go unnoticed.
+
+The hysteresis converges per frame inside one launch sequence; `_chain` is a frame whose weak edge crosses CHAIN_W / 62 tiles
+from a seed at one end, which takes the per-problem producer more than the 8 launches of one look (asserted on that code, so
+that the test cannot silently stop covering the second look).  CHAIN_W = 700 is the width the case was worked out for on
+the CPU: 36 strong pixels at columns >= 664, 664 candidates, 700 edge pixels, 12 launches in a tile-synchronous model."""
+import os
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+G = os.path.join(ROOT, "tests", "golden", "rgbd")
+K = (525.0, 525.0, 319.5, 239.5)
+SHAPES = ((3, 3), (37, 70), (64, 257))
+KINDS = ("noise", "lines", "flat", "zero_depth", "sprinkled")
+CHAIN_H, CHAIN_W = 9, 700
+
+
+def _chain(H=CHAIN_H, W=CHAIN_W, ramp=True):
+    """rows >= 4 brighter than rows < 4 by 20 (a candidate everywhere along the step, strong nowhere), ramping at +2 per
+    column up to 90 over the last ~41 columns (strong at the right end only)"""
+    col = np.arange(W)
+    amp = np.clip(20 + 2 * (col - (W - 1 - 35 - 6)), 20, 90) if ramp else np.full(W, 20)
+    bgr = np.full((H, W, 3), 100, np.uint8)
+    bgr[4:] = (100 + amp).astype(np.uint8)[None, :, None]
+    return bgr
+
+
+def _frame(kind, H, W, rng):
+    """-> (bgr H x W x 3 uint8, depth H x W uint16) of one kind"""
+    depth = rng.integers(400, 30000, (H, W)).astype(np.uint16)
+    if kind == "flat":          # no edge: no point, quiet at the first hysteresis launch, the normalisation degenerates
+        return np.full((H, W, 3), 90, np.uint8), depth
+    if kind == "chain":
+        return _chain(H, W), depth
+    if kind == "mirror":
+        return np.ascontiguousarray(_chain(H, W)[:, ::-1]), depth
+    if kind == "lines":         # a few rasterised segments on grey
+        from edge_alignment_amd import synth
+        bgr = np.full((H, W, 3), 128, np.uint8)
+        if min(H, W) >= 24:
+            p0, p1 = synth.random_segments(H, W, 4, rng, min_len=6.0, max_len=0.6 * min(H, W))
+            mask = synth.rasterize(H, W, p0, p1)
+        else:
+            mask = np.eye(H, W, dtype=bool)
+        bgr[mask] = (255, 255, 20)   # (a gray step of 100: a box-blurred line one pixel wide is still a strong edge)
+        return bgr, depth
+    bgr = rng.integers(0, 256, (H, W, 3)).astype(np.uint8)   # dense noise: strong pixels and candidates all over
+    if kind == "zero_depth":    # edges, but no pixel with a depth: zero points
+        depth[:] = 0
+    if kind == "sprinkled":
+        depth[rng.random((H, W)) < 0.3] = 0
+    return bgr, depth
+
+
+def _pairs(H, W, n, seed, kinds=KINDS):
+    rng = np.random.default_rng(seed)
+    ref = [_frame(kinds[i % len(kinds)], H, W, rng) for i in range(n)]
+    now = [_frame(kinds[(i + 1) % len(kinds)], H, W, rng)[0] for i in range(n)]
+    return [r[0] for r in ref], [r[1] for r in ref], now
+
+
+def _masks(H, W, n, seed):
+    """values from {0, 1, 2, 255}: "survives where mask > 1" is exercised at 1 and at 2"""
+    rng = np.random.default_rng(seed)
+    return [rng.choice(np.array([0, 1, 2, 255], np.uint8), size=(H, W)) for _ in range(n)]
+
+
+def _camera(i, H, W):
+    """a camera of its own per problem"""
+    return (0.9 * W + 7.0 * i, 0.8 * W + 3.0 * i, 0.5 * W - 0.5 + 0.25 * i, 0.5 * H - 0.5 - 0.125 * i)
+
+
+def _problems(hip, n, H, W, dtype, weighting=None):
+    probs = [hip.Problem(*_camera(i, H, W), dtype=dtype) for i in range(n)]
+    for i, P in enumerate(probs):
+        if weighting and weighting[i % len(weighting)]:
+            P.set_depth_weighting(*weighting[i % len(weighting)])
+    return probs
+
+
+def _state(P, points=True, image=True):
+    st = {}
+    if points:
+        st.update(n=P.num_points, points=P.get_points(), weights=P.get_weights())
+    if image:
+        st.update(dt=P.get_dt())
+    return st
+
+
+def _assert_same(got, want, where):
+    assert sorted(got) == sorted(want), where
+    for key in want:
+        a, b = got[key], want[key]
+        if key == "n":
+            assert a == b, (where, key, a, b)
+        elif a is None or b is None:
+            assert a is None and b is None, (where, key)
+        else:
+            assert a.shape == b.shape and np.array_equal(a, b), (where, key, a.shape, b.shape)
+
+
+def _per_problem(probs, ref, dep, now, mask=None, z_scaling=5000.0, low=30.0, high=90.0, normalize=(0.0, 1.0)):
+    for i, P in enumerate(probs):
+        if ref is not None:
+            P.set_ref_frame_canny(ref[i], dep[i], z_scaling=z_scaling, low=low, high=high)
+        if now is not None:
+            P.set_now_frame_canny(now[i], mask=None if mask is None else mask[i], low=low, high=high, normalize=normalize)
+
+
+def _close(*things):
+    for t in things:
+        for x in (t if isinstance(t, (list, tuple)) else [t]):
+            x.close()
+
+
+def _compare_call(hip, H, W, n, dtype, ref, dep, now, mask=None, weighting=None, where=None, rounds=None, **kw):
+    """one set_frames_canny call on fresh problems against the per-problem producers on fresh problems -> the batched states"""
+    want_p = _problems(hip, n, H, W, dtype, weighting)
+    got_p = _problems(hip, n, H, W, dtype, weighting)
+    batch = hip.Batch(got_p)
+    try:
+        _per_problem(want_p, ref, dep, now, mask, **kw)
+        batch.set_frames_canny(ref, dep, now, mask, **kw)
+        if rounds is not None:
+            rounds.append(batch.info("frames_hysteresis_rounds"))
+        states = []
+        for i in range(n):
+            st = _state(got_p[i], points=ref is not None, image=now is not None)
+            _assert_same(st, _state(want_p[i], points=ref is not None, image=now is not None), (where, H, W, n, i))
+            states.append(st)
+        return states
+    finally:
+        _close(batch, want_p, got_p)
+
+
+@pytest.mark.parametrize("dtype_name", ["EA_F64", "EA_F32"])
+@pytest.mark.parametrize("n", [1, 2, 5])
+@pytest.mark.parametrize("shape", SHAPES)
+def test_shapes_counts_and_dtypes(hip, shape, n, dtype_name):
+    H, W = shape
+    ref, dep, now = _pairs(H, W, n, seed=100 * H + n)
+    rounds = []
+    states = _compare_call(hip, H, W, n, getattr(hip, dtype_name), ref, dep, now, where=dtype_name, rounds=rounds)
+    assert rounds[0] >= 2                                    # one look per side at the least
+    if min(shape) > 3:
+        assert states[0]["n"] > 0.05 * H * W                 # dense noise with depth everywhere: thinned edges all over
+    if n == 5:
+        assert states[2]["n"] == 0 and states[3]["n"] == 0   # the flat frame, the frame without depth
+        assert states[1]["dt"].max() == 0.0                  # (the flat current frame: the normalisation degenerates to 0)
+        if min(shape) > 3:
+            assert 0 < states[4]["n"] < states[0]["n"]
+
+
+def test_a_frame_does_not_depend_on_its_neighbours_or_its_position(hip):
+    H, W, n = 37, 70, 5
+    ref, dep, now = _pairs(H, W, n, seed=7)
+    first = _compare_call(hip, H, W, n, hip.EA_F64, ref, dep, now, where="order 0")
+    for perm in ([4, 2, 0, 3, 1], [1, 0, 2, 4, 3]):
+        got = _compare_call(hip, H, W, n, hip.EA_F64, [ref[k] for k in perm], [dep[k] for k in perm], [now[k] for k in perm],
+                            where=("perm", perm))
+        for i, k in enumerate(perm):
+            assert np.array_equal(got[i]["dt"], first[k]["dt"]), (perm, i)
+            assert got[i]["n"] == first[k]["n"], (perm, i)
+            assert np.array_equal(got[i]["points"][:, 2], first[k]["points"][:, 2]), (perm, i)
+
+
+@pytest.mark.parametrize("dtype_name", ["EA_F64", "EA_F32"])
+@pytest.mark.parametrize("normalize", [(0.0, 1.0), (0.0, 255.0), None])
+@pytest.mark.parametrize("low,high", [(30.0, 90.0), (90.0, 30.0), (10.0, 200.0)])
+def test_settings_masks_cameras_and_depth_weighting_are_per_problem(hip, low, high, normalize, dtype_name):
+    """the thresholds (a pair, the same pair swapped, another pair), the normalisation ranges and off, z_scaling off its
+    default, depth weighting with powers 1 and 3 on some problems and off on others; a masked and an unmasked call on the
+    same batch, one after the other"""
+    H, W, n = 64, 257, 5
+    dtype = getattr(hip, dtype_name)
+    ref, dep, now = _pairs(H, W, n, seed=11, kinds=("noise", "sprinkled", "lines"))
+    masks = _masks(H, W, n, seed=12)
+    weighting = [(2.0, 1), (3.5, 3), None]
+    kw = dict(z_scaling=4000.0, low=low, high=high, normalize=normalize)
+    got_p = _problems(hip, n, H, W, dtype, weighting)
+    batch = hip.Batch(got_p)
+    try:
+        for mask in (masks, None, masks):
+            want_p = _problems(hip, n, H, W, dtype, weighting)
+            try:
+                _per_problem(want_p, ref, dep, now, mask, **kw)
+                batch.set_frames_canny(ref, dep, now, mask, **kw)
+                states = [_state(P) for P in got_p]
+                for i in range(n):
+                    _assert_same(states[i], _state(want_p[i]), ("masked" if mask else "unmasked", i))
+            finally:
+                _close(want_p)
+            if mask is None:
+                unmasked = states
+            else:
+                masked = states
+        assert not np.array_equal(masked[0]["dt"], unmasked[0]["dt"])   # the mask removed edges
+        assert masked[0]["n"] == unmasked[0]["n"]                       # (and is the current side's only)
+        assert states[0]["weights"] is not None and states[1]["weights"] is not None and states[2]["weights"] is None
+        if max(low, high) < 100:                                        # (a blurred line stays below a high threshold of 200)
+            assert states[2]["n"] > 0                                   # the lines: points, and no weighting on that problem
+        w = states[0]["weights"]
+        assert (w > 0).all() and (w <= 1).all() and (w < 1).any() and (w == 1).any()   # both sides of the clamp at z_ref = 2
+    finally:
+        _close(batch, got_p)
+
+
+def test_swapped_thresholds_are_the_ordered_pair(hip):
+    H, W, n = 37, 70, 2
+    ref, dep, now = _pairs(H, W, n, seed=5, kinds=("noise", "sprinkled"))
+    a = _compare_call(hip, H, W, n, hip.EA_F64, ref, dep, now, low=30.0, high=90.0)
+    b = _compare_call(hip, H, W, n, hip.EA_F64, ref, dep, now, low=90.0, high=30.0)
+    for x, y in zip(a, b):
+        _assert_same(x, y, "swapped")
+
+
+# ---- the hysteresis across several looks ----
+
+def test_the_chain_frame_needs_a_second_look_on_the_per_problem_producer(hip):
+    """the precondition of the tests below, on code they do not exercise: more than the 8 launches of one look"""
+    P = hip.Problem(*_camera(0, CHAIN_H, CHAIN_W))
+    try:
+        out = P.set_now_frame_canny(_chain(), debug=True)
+        print("hysteresis launches of the %d x %d chain frame: %d" % (CHAIN_H, CHAIN_W, out["hysteresis_launches"]))
+        assert int((out["edges"] > 0).sum()) == CHAIN_W and (out["edges"] > 0).any(axis=0).all()
+        assert out["hysteresis_launches"] > 8
+        flat = P.set_now_frame_canny(_chain(ramp=False), debug=True)
+        assert int((flat["edges"] > 0).sum()) == 0               # without the ramp: candidates only
+    finally:
+        P.close()
+
+
+@pytest.mark.parametrize("ref_kinds,now_kinds", [(("chain", "flat", "chain", "noise", "chain"), ("chain", "mirror", "chain", "flat", "chain")),
+                                                 (("chain", "flat"), ("chain", "flat"))], ids=["five", "two"])
+def test_frames_converge_each_at_its_own_pace(hip, ref_kinds, now_kinds):
+    """the chain at positions 0, 2 and last of five, beside a frame that is quiet at once, noise and the chain's mirror
+    image (whose seed is in the first tile); and the chain beside the quiet frame alone"""
+    H, W, n = CHAIN_H, CHAIN_W, len(ref_kinds)
+    rng = np.random.default_rng(21)
+    made = {k: _frame(k, H, W, rng) for k in sorted(set(ref_kinds + now_kinds))}
+    ref, dep, now = [made[k][0] for k in ref_kinds], [made[k][1] for k in ref_kinds], [made[k][0] for k in now_kinds]
+    rounds = []
+    states = _compare_call(hip, H, W, n, hip.EA_F64, ref, dep, now, where=ref_kinds, rounds=rounds)
+    print("looks, both sides:", rounds)
+    assert rounds[0] >= 2, rounds
+    for i in range(n):
+        for k in range(i + 1, n):
+            if now_kinds[i] == now_kinds[k]:                  # the same current frame at two positions: the same image
+                assert np.array_equal(states[i]["dt"], states[k]["dt"]), (i, k)
+            if ref_kinds[i] == ref_kinds[k]:
+                assert states[i]["n"] == states[k]["n"] and np.array_equal(states[i]["points"][:, 2], states[k]["points"][:, 2])
+    assert all(states[i]["n"] == CHAIN_W for i in range(n) if ref_kinds[i] == "chain")   # every pixel of the chain has a depth
+    assert all(states[i]["n"] == 0 for i in range(n) if ref_kinds[i] == "flat")
+    # one side at a time: the looks of that side only -- a second one for the chain
+    for side in ((ref, dep, None), (None, None, now)):
+        rounds = []
+        _compare_call(hip, H, W, n, hip.EA_F32, *side, where="one side", rounds=rounds)
+        print("looks, one side:", rounds)
+        assert rounds[0] >= 2, rounds
+
+
+def test_an_all_flat_call_takes_one_look_per_side(hip):
+    H, W, n = CHAIN_H, CHAIN_W, 3
+    rng = np.random.default_rng(22)
+    frames = [_frame("flat", H, W, rng) for _ in range(n)]
+    bgr, dep = [f[0] for f in frames], [f[1] for f in frames]
+    for args, want in (((bgr, dep, bgr), 2), ((bgr, dep, None), 1), ((None, None, bgr), 1)):
+        rounds = []
+        _compare_call(hip, H, W, n, hip.EA_F64, *args, where="flat", rounds=rounds)
+        assert rounds == [want]
+
+
+@pytest.fixture(scope="module")
+def bundled(hip):
+    """the five bundled frames at full size and at 160 x 120 (the library's own resize_half for colour, [::4, ::4] for depth)"""
+    from edge_alignment_amd import synth
+    full = synth.load_bundled_frames(G)
+    small = {k: (hip.resize_half(hip.resize_half(bgr)), np.ascontiguousarray(dep[::4, ::4])) for k, (bgr, dep) in full.items()}
+    return dict(full=full, small=small)
+
+
+K_SMALL = (K[0] / 4, K[1] / 4, (K[2] + 0.5) / 4 - 0.5, (K[3] + 0.5) / 4 - 0.5)
+FIVE_PAIRS = ((1, 2), (2, 3), (3, 4), (4, 5), (5, 1))
+Q0, T0 = np.array([1.0, 0, 0, 0]), np.zeros(3)
+
+
+def _small_batch(hip, bundled, batched, dtype=0):
+    probs = [hip.Problem(*K_SMALL, dtype=dtype) for _ in FIVE_PAIRS]
+    ref = [bundled["small"][a][0] for a, _ in FIVE_PAIRS]
+    dep = [bundled["small"][a][1] for a, _ in FIVE_PAIRS]
+    now = [bundled["small"][b][0] for _, b in FIVE_PAIRS]
+    batch = hip.Batch(probs)
+    if batched:
+        batch.set_frames_canny(ref, dep, now)
+    else:
+        _per_problem(probs, ref, dep, now)
+    return probs, batch, (ref, dep, now)
+
+
+def _assert_same_eval(a, b, where):
+    for key in ("cost", "JtJ", "Jtr", "n_invalid"):
+        assert np.array_equal(a[key], b[key]), (where, key)
+
+
+def test_eval_and_solve_after_set_frames_canny_are_those_of_the_per_problem_producers(hip, bundled):
+    n = len(FIVE_PAIRS)
+    q, t = np.tile(Q0, (n, 1)), np.tile(T0, (n, 1))
+    want_p, want_b, _ = _small_batch(hip, bundled, batched=False)
+    got_p, got_b, _ = _small_batch(hip, bundled, batched=True)
+    try:
+        assert all(P.num_points > 200 for P in got_p)
+        ev = got_b.eval(q, t)
+        _assert_same_eval(ev, want_b.eval(q, t), "eval")
+        assert (ev["cost"] > 0).all() and np.isfinite(ev["cost"]).all()
+        gq, gt, gs = got_b.solve(q, t, max_num_iterations=12)
+        wq, wt, ws = want_b.solve(q, t, max_num_iterations=12)
+        assert np.array_equal(gq, wq) and np.array_equal(gt, wt)
+        for a, b in zip(gs, ws):
+            for key in ("termination", "why", "num_iterations", "initial_cost", "final_cost"):
+                assert a[key] == b[key], key
+        assert any(s["num_iterations"] > 1 for s in gs)
+    finally:
+        _close(want_b, got_b, want_p, got_p)
+
+
+def test_one_side_at_a_time_another_extent_the_laplacian_call_and_a_per_problem_call_afterwards(hip, bundled):
+    n = len(FIVE_PAIRS)
+    q, t = np.tile(Q0, (n, 1)), np.tile(T0, (n, 1))
+    want_p, want_b, (ref, dep, now) = _small_batch(hip, bundled, batched=False)
+    got_p = [hip.Problem(*K_SMALL) for _ in FIVE_PAIRS]
+    got_b = hip.Batch(got_p)
+    try:
+        # only the reference frames: points as the per-problem call leaves them, still no image
+        got_b.set_frames_canny(ref_bgr=ref, ref_depth=dep)
+        for i in range(n):
+            _assert_same(_state(got_p[i], image=False), _state(want_p[i], image=False), ("ref only", i))
+            with pytest.raises(hip.EAError) as ei:
+                got_p[i].get_dt()
+            assert ei.value.code == hip.EA_ERR_STATE
+        # only the current frames: the points stay
+        got_b.set_frames_canny(now_bgr=now)
+        for i in range(n):
+            _assert_same(_state(got_p[i]), _state(want_p[i]), ("now only", i))
+        _assert_same_eval(got_b.eval(q, t), want_b.eval(q, t), "after the two halves")
+        # a larger extent, then the first one again: the workspace is laid out anew each time
+        H2, W2 = 131, 200
+        r2, d2, n2 = _pairs(H2, W2, n, seed=3)
+        big_p = _problems(hip, n, H2, W2, hip.EA_F64)
+        try:
+            _per_problem(big_p, r2, d2, n2)
+            got_b.set_frames_canny(r2, d2, n2)
+            for i in range(n):
+                want = _state(big_p[i])
+                want["points"] = None  # (the cameras differ: of the points only the count and z are comparable)
+                got = _state(got_p[i])
+                assert np.array_equal(got["points"][:, 2], big_p[i].get_points()[:, 2]), i
+                got["points"] = None
+                _assert_same(got, want, ("larger extent", i))
+        finally:
+            _close(big_p)
+        got_b.set_frames_canny(ref, dep, now)
+        for i in range(n):
+            _assert_same(_state(got_p[i]), _state(want_p[i]), ("first extent again", i))
+        # the Laplacian call and the Canny call in turn: they share the batch's workspace
+        lap_p = [hip.Problem(*K_SMALL) for _ in FIVE_PAIRS]
+        try:
+            for i, P in enumerate(lap_p):
+                P.set_ref_frame(ref[i], dep[i])
+                P.set_now_frame(now[i])
+            for turn in range(2):
+                got_b.set_frames(ref, dep, now)
+                assert got_b.info("frames_hysteresis_rounds") == 0
+                for i in range(n):
+                    _assert_same(_state(got_p[i]), _state(lap_p[i]), ("laplacian", turn, i))
+                got_b.set_frames_canny(ref, dep, now)
+                assert got_b.info("frames_hysteresis_rounds") >= 2
+                for i in range(n):
+                    _assert_same(_state(got_p[i]), _state(want_p[i]), ("canny", turn, i))
+        finally:
+            _close(lap_p)
+        # a per-problem producer call on one member afterwards: the batch sees that problem's new frame
+        a, b = bundled["small"][5], bundled["small"][2]
+        for P in (got_p[1], want_p[1]):
+            P.set_ref_frame_canny(a[0], a[1])
+            P.set_now_frame_canny(b[0])
+        _assert_same(_state(got_p[1]), _state(want_p[1]), "member")
+        _assert_same_eval(got_b.eval(q, t), want_b.eval(q, t), "after the member's own call")
+    finally:
+        _close(want_b, got_b, want_p, got_p)
+
+
+def test_bundled_pairs_at_full_size_in_one_call(hip, bundled):
+    """five pairs of the bundled 640 x 480 frames in one call"""
+    from oracle import preprocess_np as pp
+    full = bundled["full"]
+    ref, dep, now = [full[a][0] for a, _ in FIVE_PAIRS], [full[a][1] for a, _ in FIVE_PAIRS], [full[b][0] for _, b in FIVE_PAIRS]
+    got_p = [hip.Problem(*K) for _ in FIVE_PAIRS]
+    want_p = [hip.Problem(*K) for _ in FIVE_PAIRS]
+    batch = hip.Batch(got_p)
+    try:
+        batch.set_frames_canny(ref, dep, now)
+        _per_problem(want_p, ref, dep, now)
+        for i in range(len(FIVE_PAIRS)):
+            got = _state(got_p[i])
+            _assert_same(got, _state(want_p[i]), ("full size", FIVE_PAIRS[i]))
+            assert got["n"] > 5000 and got["weights"] is None
+        # one pair against the numpy restatement of get_aX_canny and of get_distance_transform2
+        i = FIVE_PAIRS.index((1, 2))
+        aX, _ = pp.get_aX_canny(full[1][0], full[1][1], *K)
+        assert np.array_equal(got_p[i].get_points(), aX[:3].T)
+        assert np.array_equal(got_p[i].get_dt(), pp.get_distance_transform2(full[2][0]).astype(np.float64))
+    finally:
+        _close(batch, got_p, want_p)
+
+
+def test_device_tensors_give_the_bits_of_the_host_entry(hip, bundled):
+    torch = pytest.importorskip("torch")
+    if not torch.cuda.is_available():
+        pytest.skip("torch has no device")
+    u16 = torch.uint16 if hasattr(torch, "uint16") else torch.int16
+    n = len(FIVE_PAIRS)
+    want_p = [hip.Problem(*K_SMALL) for _ in FIVE_PAIRS]
+    want_b = hip.Batch(want_p)
+    got_p = [hip.Problem(*K_SMALL) for _ in FIVE_PAIRS]
+    got_b = hip.Batch(got_p)
+    try:
+        ref = [bundled["small"][a][0] for a, _ in FIVE_PAIRS]
+        dep = [bundled["small"][a][1] for a, _ in FIVE_PAIRS]
+        now = [bundled["small"][b][0] for _, b in FIVE_PAIRS]
+        masks = _masks(*now[0].shape[:2], n, seed=31)
+        dev = torch.device("cuda", 0)
+        t_ref = torch.from_numpy(np.stack(ref)).to(dev)                          # one stacked tensor
+        t_dep = [torch.from_numpy(d.view(np.int16)).to(dev).view(u16) for d in dep]   # a list of tensors
+        t_now = torch.from_numpy(np.stack(now)).to(dev)
+        t_mask = [torch.from_numpy(m).to(dev) for m in masks]
+        for mask, t_m in ((None, None), (masks, t_mask)):
+            want_b.set_frames_canny(ref, dep, now, mask, normalize=(0.0, 255.0))
+            got_b.set_frames_canny(t_ref, t_dep, t_now, t_m, normalize=(0.0, 255.0))
+            for i in range(n):
+                _assert_same(_state(got_p[i]), _state(want_p[i]), ("device", mask is not None, i))
+        assert torch.equal(t_ref.cpu(), torch.from_numpy(np.stack(ref)))         # read in place, not written
+        assert torch.equal(t_now.cpu(), torch.from_numpy(np.stack(now)))
+        assert all(torch.equal(a.cpu(), torch.from_numpy(b)) for a, b in zip(t_mask, masks))
+        assert all(torch.equal(a.cpu().view(torch.int16), torch.from_numpy(b.view(np.int16))) for a, b in zip(t_dep, dep))
+        with pytest.raises(ValueError):
+            got_b.set_frames_canny(t_ref, dep, t_now)                            # a mix of host and device inputs
+        with pytest.raises(ValueError):
+            got_b.set_frames_canny(now_bgr=t_now, now_mask=masks)
+        with pytest.raises(ValueError):
+            got_b.set_frames_canny(now_bgr=t_now.permute(0, 2, 1, 3))            # not contiguous
+        with pytest.raises(ValueError):
+            got_b.set_frames_canny(now_bgr=t_now.cpu())                          # a torch tensor, but not on the GPU
+    finally:
+        _close(want_b, got_b, want_p, got_p)
+
+
+def test_misuse_is_refused_and_leaves_every_problem_as_it_was(hip, bundled):
+    import ctypes as C
+    want_p, want_b, (ref, dep, now) = _small_batch(hip, bundled, batched=True)
+    got_p, got_b, _ = _small_batch(hip, bundled, batched=True)
+    n = len(FIVE_PAIRS)
+    dup_b = hip.Batch([got_p[0], got_p[1], got_p[0]])
+    L = hip.load()
+    nan, inf = float("nan"), float("inf")
+
+    def refused(call):
+        with pytest.raises(hip.EAError) as ei:
+            call()
+        assert ei.value.code == hip.EA_ERR_INVALID_ARG, ei.value
+        for i in range(n):
+            _assert_same(_state(got_p[i]), _state(want_p[i]), ("unchanged", i))
+
+    try:
+        other = [f[::-1].copy() for f in now]   # frames that would change every image if a refused call ran
+        masks = _masks(*other[0].shape[:2], n, seed=41)
+        refused(lambda: got_b.set_frames_canny(ref, dep, other[:2] + [None] + other[3:]))       # a NULL entry
+        refused(lambda: got_b.set_frames_canny(ref, dep, other, masks[:2] + [None] + masks[3:]))  # ... in the masks
+        refused(lambda: got_b.set_frames_canny(ref[:-1], dep[:-1], other[:-1]))                # a wrong count
+        refused(lambda: got_b.set_frames_canny(ref, dep, other + other[:1]))
+        refused(lambda: dup_b.set_frames_canny(ref[:3], dep[:3], other[:3]))                   # the same problem twice
+        refused(lambda: got_b.set_frames_canny(ref, dep, other, z_scaling=0.0))
+        refused(lambda: got_b.set_frames_canny(ref, dep, other, z_scaling=inf))
+        refused(lambda: got_b.set_frames_canny(now_bgr=[f[:2].copy() for f in other]))         # an extent of 2
+        refused(lambda: got_b.set_frames_canny(now_bgr=[f[:, :2].copy() for f in other]))
+        refused(lambda: got_b.set_frames_canny(ref, dep, other, low=nan))                      # a NaN threshold
+        refused(lambda: got_b.set_frames_canny(ref, dep, other, high=nan))
+        refused(lambda: got_b.set_frames_canny(ref, dep, other, normalize=(inf, 1.0)))         # a non-finite range
+        refused(lambda: got_b.set_frames_canny(ref, dep, other, normalize=(0.0, nan)))
+        refused(lambda: got_b.set_frames_canny(ref, dep, now_mask=masks))                      # a mask without current frames
+        # host pointers handed to the device entry, as frames and as masks
+        prm = hip.CannyFrameParams()
+        L.ea_default_canny_frame_params(C.byref(prm), *other[0].shape[:2])
+        ptrs = (C.c_void_p * n)(*[f.ctypes.data for f in other])
+        mptrs = (C.c_void_p * n)(*[m.ctypes.data for m in masks])
+        refused(lambda: hip._check(L.ea_batch_set_frames_canny_device(got_b._h, None, None, ptrs, None, C.byref(prm))))
+        refused(lambda: hip._check(L.ea_batch_set_frames_canny_device(got_b._h, None, None, ptrs, mptrs, C.byref(prm))))
+        # both sides NULL; a reference colour frame without its depth
+        refused(lambda: hip._check(L.ea_batch_set_frames_canny(got_b._h, None, None, None, None, C.byref(prm))))
+        refused(lambda: hip._check(L.ea_batch_set_frames_canny(got_b._h, ptrs, None, None, None, C.byref(prm))))
+        # accepted calls in between leave what the per-problem producers leave
+        got_b.set_frames_canny(now_bgr=now, normalize=None)
+        got_b.set_frames_canny(now_bgr=now)
+        for i in range(n):
+            _assert_same(_state(got_p[i]), _state(want_p[i]), ("again", i))
+        # and the batch still works
+        got_b.set_frames_canny(now_bgr=other)
+        assert not np.array_equal(got_p[0].get_dt(), want_p[0].get_dt())
+    finally:
+        _close(dup_b, want_b, got_b, want_p, got_p)
