@@ -2113,12 +2113,138 @@ __device__ __forceinline__ void prior_into_lds(const LMState &s_st, double *s_ac
   __syncthreads();
 }
 
-// LM step: fold this problem's partial rows, advance the trust-region state machine, publish the
-// next pose to evaluate.  One workgroup per problem.  The state machine is scalar fp64 work on
-// lane 0 (pure latency: ~1/3 of an LM iteration), so everything around it is arranged to overlap:
-// the state words travel while the partial rows are fetched (sixteen 16-byte loads in flight per lane), the
-// host's progress counter is posted before the arithmetic, lane 0 works on a register copy of the
-// state, and the pose's float mirrors / the write-back are lane-parallel.
+// ---- the trust-region step, once: the pieces ea_lm_step_kernel, ea_lm_step_starts_kernel and ea_lm_iter_kernel are made of
+//
+// A step folds a problem's partial rows, advances the trust-region state machine and publishes the next pose to evaluate.
+// The state machine is scalar fp64 work on lane 0 (pure latency: ~1/3 of an LM iteration), so everything around it is
+// arranged to overlap: the state words travel while the partial rows are fetched (sixteen 16-byte loads in flight per lane),
+// the host's progress counter is posted before the arithmetic, lane 0 works on a register copy of the state, and the pose's
+// float mirrors / the write-back are lane-parallel.  In the order of a step:
+//   EA_LM_PIN_OPTIONS          the options out of the kernel argument segment, in one batch of scalar loads behind one wait
+//   lm_state_word, prior_word  one 8-byte word of the state (and of the prior record) per lane, issued IN FRONT of the fold
+//   (the fold: the caller's -- reduce_tiles<., 8> over the problem's range, or <., 4> over pose * rows + range for a start)
+//   lm_step_park               the words into LDS, the barrier, the priors and the mask into the folded sums (prior_into_lds)
+//   EA_LM_STEP_LANE0           lane 0: register copy of state and sums, lm_begin / lm_advance, the candidate pose into LDS
+//   lm_step_publish            state words and pose to memory, lane-parallel
+//   EA_LM_STEP_DELIVER         a solve that ends: final state and trace rows straight into pinned host memory
+// Every piece takes tid and derives nothing from the workgroup's shape.  What orders a kernel against the host or against
+// other workgroups (progress words, alive counts, what follows the delivery) stays in the kernel.
+// The two pieces that hold objects of their own (the register copy of the state; the row copier and the second LMPending)
+// are statement macros: as functions, in every form tried, they moved those objects in front of the kernel's and
+// ea_lm_iter_kernel -- 10 000 instructions at 384 VGPRs -- came out 5 .. 50 vector instructions longer in most instantiations
+// (profiles/step_tail_listing.md).  As macros the kernels compile to the code they had when each held its own copy.
+constexpr int kStateWords = (int)(sizeof(LMState) / 8), kColdWords = (int)(sizeof(LMCold) / 8);
+constexpr int kPoseDoubles = 4 + 3 + 9 + 27, kPoseFloats = 9 + 3 + 27;  // q | t | R | G, and Rf | tf | Gf behind them
+static_assert(sizeof(LMState) % 8 == 0 && kStateWords <= kLmThreads && kColdWords <= 64, "one 8-byte word per lane (cold: per lane of a wavefront)");
+static_assert(offsetof(PoseState, Rf) == kPoseDoubles * 8 && offsetof(PoseState, unit_q) == kPoseDoubles * 8 + kPoseFloats * 4,
+              "PoseState layout");
+
+// Everything the kernel argument segment holds is fetched where this stands, in one batch of scalar loads behind one wait:
+// left to the compiler, the options were loaded where lane 0 first uses them -- two more cold misses of the argument
+// segment on the state machine's critical path, after the fold.
+#define EA_LM_PIN_OPTIONS(opt)                                                                                              \
+  asm volatile("" : "+s"((opt).max_num_iterations), "+s"((opt).function_tolerance), "+s"((opt).gradient_tolerance),        \
+                    "+s"((opt).parameter_tolerance), "+s"((opt).initial_trust_region_radius),                              \
+                    "+s"((opt).max_trust_region_radius), "+s"((opt).min_trust_region_radius),                              \
+                    "+s"((opt).min_relative_decrease), "+s"((opt).min_lm_diagonal), "+s"((opt).max_lm_diagonal),           \
+                    "+s"((opt).max_num_consecutive_invalid_steps), "+s"((opt).jacobi_scaling), "+s"((opt).strategy))
+
+// The words of a step that travel beside the partial rows: lane tid's word of the state (and prior_word above), loaded by
+// the kernel in front of its fold, then parked in LDS behind it -- the barrier, and the priors and the mask into the sums.
+__device__ __forceinline__ double lm_state_word(const LMState *st, int tid) {
+  return tid < kStateWords ? reinterpret_cast<const double *>(st)[tid] : 0.0;
+}
+template <bool SIDE>
+__device__ __forceinline__ void lm_step_park(double state_word, double pw, LMState &s_st, double *s_acc, int tid) {
+  if (tid < kStateWords) reinterpret_cast<double *>(&s_st)[tid] = state_word;
+  if constexpr (SIDE) {
+    if (tid < kPriorWords) reinterpret_cast<double *>(&prior_lds())[tid] = pw;
+  }
+  __syncthreads();
+  if constexpr (SIDE) prior_into_lds(s_st, s_acc, tid);
+}
+
+// Lane 0 of a step (inside the caller's `if`; STRAT and SIDE are the kernel's): the state machine on st, a member-by-member
+// register copy of the state the caller declares, and on acc, a copy of the folded sums; then the candidate pose into
+// *s_ps_.  cold_ is the system at x the state machine reads and updates (global memory, or a wavefront's LDS copy), tr_
+// takes the rows of invalid steps (lm_trace) and may be null, STAMP_ is a statement between the state machine and the pose
+// (the diagnostic build's clock).  The full form (LITE_ = false) leaves the state in s_st_ and the number of the pending
+// trace row in s_trace_it_; acc_ and pend_ are the caller's, lm_flush and EA_LM_STEP_DELIVER take them.  LITE_ (an
+// evaluating wavefront of ea_lm_iter_kernel): the pose and nothing else.
+#define EA_LM_STEP_LANE0(LITE_, st_, s_st_, s_acc_, cold_, tr_, opt_, s_ps_, s_trace_it_, acc_, pend_, STAMP_)              \
+  do {                                                                                                                      \
+    lm_copy_state(&(st_), &(s_st_));                                                                                        \
+    _Pragma("unroll") for (int i = 0; i < kAccSlots; ++i) (acc_)[i] = (s_acc_)[i];                                          \
+    if (EA_UNLIKELY((st_).num_evals == 0)) lm_begin<STRAT, LITE_, SIDE>(&(st_), cold_, tr_, &(opt_), acc_, &(pend_));       \
+    else lm_advance<STRAT, LITE_, SIDE>(&(st_), cold_, tr_, &(opt_), acc_, &(pend_));                                       \
+    STAMP_;                                                                                                                 \
+    make_pose_core((st_).cand, (st_).rot_transposed, (st_).running, s_ps_, /*zero_unused_G=*/false);                        \
+    if constexpr (!(LITE_)) {                                                                                               \
+      lm_copy_state(&(s_st_), &(st_));                                                                                      \
+      s_trace_it_ = (pend_).trace_it;                                                                                       \
+    }                                                                                                                       \
+  } while (0)
+
+// State and pose of a step to memory, all lanes: the state one 8-byte word per lane; of the pose the doubles by lanes 64..,
+// the float mirrors (Rf | tf | Gf of R | t | G) converted by lanes 128.., the flags by lane 192.  G is never read when
+// unit_q is set; those lanes publish zeros.
+__device__ __forceinline__ void lm_step_publish(const LMState &s_st, const PoseState &s_ps, LMState *st_dst, PoseState *pose_dst, int tid) {
+  if (tid < kStateWords) reinterpret_cast<double *>(st_dst)[tid] = reinterpret_cast<const double *>(&s_st)[tid];
+  const double *pd_src = reinterpret_cast<const double *>(&s_ps);
+  const int a = tid - 64, f = tid - 128;
+  const bool skip_g = s_ps.unit_q != 0;
+  if (a >= 0 && a < kPoseDoubles) reinterpret_cast<double *>(pose_dst)[a] = (skip_g && a >= 16) ? 0.0 : pd_src[a];
+  if (f >= 0 && f < kPoseFloats) {
+    const double v = f < 9 ? s_ps.R[f] : (f < 12 ? s_ps.t[f - 9] : (skip_g ? 0.0 : s_ps.G[f - 12]));
+    (&pose_dst->Rf[0])[f] = (float)v;
+  }
+  if (tid == 192) { pose_dst->unit_q = s_ps.unit_q; pose_dst->active = s_ps.active; }
+}
+
+// The solve of a problem ends with this launch (the caller's uniform `if (!s_st.running)`): the result goes straight into
+// pinned host memory -- final state and the trace rows written so far -- so the host returns without a device-to-host copy
+// or a stream synchronisation behind launches that were queued ahead and now have nothing to do.  The caller lowers the flag
+// the host polls behind this.  WANTED_ / ROWS_WANTED_ are the caller's (uniform) conditions: the pair and fused forms
+// deliver when they were given host_states, a multi-start solve always delivers the state and the rows only with summaries;
+// a literal `true` costs nothing.  tr_ / host_tr_: the problem's trace on the device and in host memory; pend_ / acc_ /
+// cold_: as lm_flush took them (the system is not stored a second time).  Two arms: usually rows < last come from earlier
+// launches, one lane each, and lane 0 holds the last one; when this very launch wrote rows through lm_trace (invalid steps),
+// or the solve ran past the trace's end, lane 0 wrote them and lane 0 copies them all.
+#define EA_LM_STEP_DELIVER(WANTED_, ROWS_WANTED_, s_st_, trace_it_, pend_, acc_, cold_, tr_, host_st_, host_tr_, tid_)      \
+  do {                                                                                                                      \
+    if (WANTED_) {                                                                                                          \
+      if ((tid_) < kStateWords)                                                                                             \
+        reinterpret_cast<double *>(host_st_)[tid_] = reinterpret_cast<const double *>(&(s_st_))[tid_];                      \
+      if (ROWS_WANTED_) {                                                                                                   \
+        const int last = min((s_st_).iteration, kTrace - 1); /* rows 0 .. last exist */                                     \
+        auto copy_row = [&](int r) {                                                                                        \
+          const LMTrace &src = *(tr_);                                                                                      \
+          LMTrace &dst = *(host_tr_);                                                                                       \
+          dst.it_cost[r] = src.it_cost[r];                                                                                  \
+          dst.it_cost_change[r] = src.it_cost_change[r];                                                                    \
+          dst.it_gradient_max_norm[r] = src.it_gradient_max_norm[r];                                                        \
+          dst.it_step_norm[r] = src.it_step_norm[r];                                                                        \
+          dst.it_relative_decrease[r] = src.it_relative_decrease[r];                                                        \
+          dst.it_radius[r] = src.it_radius[r];                                                                              \
+          dst.it_successful[r] = src.it_successful[r];                                                                      \
+        };                                                                                                                  \
+        if ((trace_it_) == last) {                                                                                          \
+          if ((tid_) < last) copy_row(tid_);                                                                                \
+          if ((tid_) == 0) {                                                                                                \
+            LMPending h = (pend_);                                                                                          \
+            h.store_system = 0;                                                                                             \
+            lm_flush(&h, cold_, host_tr_, acc_);                                                                            \
+          }                                                                                                                 \
+        } else if ((tid_) == 0) {                                                                                           \
+          __threadfence();                                                                                                  \
+          for (int r = 0; r <= last; ++r) copy_row(r);                                                                      \
+        }                                                                                                                   \
+      }                                                                                                                     \
+      __threadfence_system();                                                                                               \
+    }                                                                                                                       \
+  } while (0)
+
+// LM step, the (evaluate, step) pair form: one workgroup per problem (the pieces above).
 // SIDE: the problems' NormalPriors are added to the folded sums before the state machine reads them (prior_into_lds).  The
 // prior table sits right behind the group table (one PriorDesc per problem: batch_build lays them out so), so no argument is
 // added: the SIDE = false instantiations are the code this kernel was before priors existed.
@@ -2136,11 +2262,6 @@ __global__ __launch_bounds__(kLmThreads) void ea_lm_step_kernel(
   __shared__ LMState s_st;
   __shared__ PoseState s_ps;
   __shared__ int s_trace_it;
-  constexpr int kStateWords = (int)(sizeof(LMState) / 8);
-  constexpr int kPoseDoubles = 4 + 3 + 9 + 27, kPoseFloats = 9 + 3 + 27;
-  static_assert(sizeof(LMState) % 8 == 0 && kStateWords <= kLmThreads, "one 8-byte state word per lane");
-  static_assert(offsetof(PoseState, Rf) == kPoseDoubles * 8 && offsetof(PoseState, unit_q) == kPoseDoubles * 8 + kPoseFloats * 4,
-                "PoseState layout");
   const int p = blockIdx.x, tid = threadIdx.x;
 #ifdef EA_STAMPS
   const int ev_ = states[p].num_evals;
@@ -2149,20 +2270,13 @@ __global__ __launch_bounds__(kLmThreads) void ea_lm_step_kernel(
 #ifdef EA_STAMPS
   if (threadIdx.x == 0 && blockIdx.x == 0) g_lm_probe_row = ev_ & 63;
 #endif
-  // Everything the kernel argument segment holds is fetched HERE, in one batch of scalar loads behind one wait: left to
-  // the compiler, the options were loaded where lane 0 first uses them -- two more cold misses of the argument segment
-  // on the state machine's critical path, after the fold.
   LMOptions opt = opt_arg;
-  asm volatile("" : "+s"(opt.max_num_iterations), "+s"(opt.function_tolerance), "+s"(opt.gradient_tolerance),
-                    "+s"(opt.parameter_tolerance), "+s"(opt.initial_trust_region_radius), "+s"(opt.max_trust_region_radius),
-                    "+s"(opt.min_trust_region_radius), "+s"(opt.min_relative_decrease), "+s"(opt.min_lm_diagonal),
-                    "+s"(opt.max_lm_diagonal), "+s"(opt.max_num_consecutive_invalid_steps), "+s"(opt.jacobi_scaling),
-                    "+s"(opt.strategy));
+  EA_LM_PIN_OPTIONS(opt);
   GroupDesc gd = first;
   if (p != 0) gd = groups[p];  // (uniform)
   const int running = states[p].running;
   const int evals_before = states[p].num_evals;  // (a register copy: the LDS copy is rewritten by lane 0 below)
-  const double state_word = tid < kStateWords ? reinterpret_cast<const double *>(states + p)[tid] : 0.0;
+  const double state_word = lm_state_word(states + p, tid);
   double pw = 0.0;
   if constexpr (SIDE) pw = prior_word(groups, gridDim.x, p, tid);
   EA_LM_STAMP(1, ev_);
@@ -2171,12 +2285,7 @@ __global__ __launch_bounds__(kLmThreads) void ea_lm_step_kernel(
   // problem folds rows nobody reads and leaves below.
   reduce_tiles<kLmThreads, 8>(partials, gd.tile_begin, gd.tile_end, s_part, s_acc);
   if (!running) return;  // uniform
-  if (tid < kStateWords) reinterpret_cast<double *>(&s_st)[tid] = state_word;
-  if constexpr (SIDE) {
-    if (tid < kPriorWords) reinterpret_cast<double *>(&prior_lds())[tid] = pw;
-  }
-  __syncthreads();
-  if constexpr (SIDE) prior_into_lds(s_st, s_acc, tid);
+  lm_step_park<SIDE>(state_word, pw, s_st, s_acc, tid);
   EA_LM_STAMP(2, ev_);
   // the host only uses this counter to decide how far ahead to enqueue: posted by another wavefront before the
   // arithmetic, so the PCIe write is neither the last thing the kernel waits for nor in lane 0's memory counter
@@ -2186,68 +2295,15 @@ __global__ __launch_bounds__(kLmThreads) void ea_lm_step_kernel(
   double acc[kAccSlots];
   if (tid == 0) {
     LMState st;
-    lm_copy_state(&st, &s_st);
-#pragma unroll
-    for (int i = 0; i < kAccSlots; ++i) acc[i] = s_acc[i];
-    if (EA_UNLIKELY(st.num_evals == 0)) lm_begin<STRAT, false, SIDE>(&st, cold + p, traces + p, &opt, acc, &pend);
-    else lm_advance<STRAT, false, SIDE>(&st, cold + p, traces + p, &opt, acc, &pend);
-    EA_LM_STAMP(3, ev_);
-    make_pose_core(st.cand, st.rot_transposed, st.running, &s_ps, /*zero_unused_G=*/false);
-    lm_copy_state(&s_st, &st);
-    s_trace_it = pend.trace_it;
+    EA_LM_STEP_LANE0(false, st, s_st, s_acc, cold + p, traces + p, opt, &s_ps, s_trace_it, acc, pend, EA_LM_STAMP(3, ev_));
     EA_LM_STAMP(4, ev_);
   }
   __syncthreads();
-  if (tid < kStateWords) reinterpret_cast<double *>(states + p)[tid] = reinterpret_cast<const double *>(&s_st)[tid];
-  {
-    // pose: doubles copied by lanes 64.., float mirrors converted by lanes 128.., flags by lane 192
-    // (G is never read when unit_q is set; those lanes publish zeros)
-    const double *pd_src = reinterpret_cast<const double *>(&s_ps);
-    const int a = tid - 64, f = tid - 128;
-    const bool skip_g = s_ps.unit_q != 0;
-    if (a >= 0 && a < kPoseDoubles) reinterpret_cast<double *>(poses + p)[a] = (skip_g && a >= 16) ? 0.0 : pd_src[a];
-    if (f >= 0 && f < kPoseFloats) {
-      // Rf | tf | Gf mirror R | t | G
-      const double v = f < 9 ? s_ps.R[f] : (f < 12 ? s_ps.t[f - 9] : (skip_g ? 0.0 : s_ps.G[f - 12]));
-      (&poses[p].Rf[0])[f] = (float)v;
-    }
-    if (tid == 192) { poses[p].unit_q = s_ps.unit_q; poses[p].active = s_ps.active; }
-  }
+  lm_step_publish(s_st, s_ps, states + p, poses + p, tid);
   if (tid == 0) lm_flush(&pend, cold + p, traces + p, acc);
   if (!s_st.running) {  // uniform: the solve of this problem ends with this launch
-    // Deliver the result straight into pinned host memory -- final state and the trace rows written so far -- and
-    // only then lower the flag the host polls: the host returns without a device-to-host copy or a stream
-    // synchronisation behind launches that were queued ahead and now have nothing to do.
-    if (host_states) {
-      if (tid < kStateWords) reinterpret_cast<double *>(host_states + p)[tid] = reinterpret_cast<const double *>(&s_st)[tid];
-      const int last = min(s_st.iteration, kTrace - 1);  // rows 0 .. last exist
-      auto copy_row = [&](int r) {
-        const LMTrace &src = traces[p];
-        LMTrace &dst = host_traces[p];
-        dst.it_cost[r] = src.it_cost[r];
-        dst.it_cost_change[r] = src.it_cost_change[r];
-        dst.it_gradient_max_norm[r] = src.it_gradient_max_norm[r];
-        dst.it_step_norm[r] = src.it_step_norm[r];
-        dst.it_relative_decrease[r] = src.it_relative_decrease[r];
-        dst.it_radius[r] = src.it_radius[r];
-        dst.it_successful[r] = src.it_successful[r];
-      };
-      if (s_trace_it == last) {
-        // the usual end: rows < last come from earlier launches (one lane each), lane 0 holds the last one
-        if (tid < last) copy_row(tid);
-        if (tid == 0) {
-          LMPending h = pend;
-          h.store_system = 0;
-          lm_flush(&h, cold + p, host_traces + p, acc);
-        }
-      } else if (tid == 0) {
-        // rows written by this very launch through lm_trace (invalid steps): lane 0 wrote them, lane 0 copies them
-        __threadfence();
-        for (int r = 0; r <= last; ++r) copy_row(r);
-      }
-      __threadfence_system();
-    }
-    __syncthreads();
+    EA_LM_STEP_DELIVER(host_states, true, s_st, s_trace_it, pend, acc, cold + p, traces + p, host_states + p, host_traces + p, tid);
+    __syncthreads();  // only behind every lane's delivery does the flag the host polls go down
     if (tid == 0) __hip_atomic_store(progress + p, 0, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
   // behind the flag (same lane, release order): a host that has seen "step k complete" sees the flag as step k left it
@@ -2261,13 +2317,12 @@ __global__ __launch_bounds__(kLmThreads) void ea_lm_step_kernel(
 
 // ---- K trust-region runs per problem in lock-step (ea_batch_solve_starts) ------------------------------------------------
 //
-// The step of one (live position, problem) of a multi-start solve, one 256-lane workgroup each: ea_lm_step_kernel's body on
-// the slot live[off + pose] * count + problem.  The rows of the start are folded with reduce_tiles<256, 4> over
+// The step of one (live position, problem) of a multi-start solve, one 256-lane workgroup each: the pieces of the step
+// (above) on the slot live[off + pose] * count + problem.  The rows of the start are folded with reduce_tiles<256, 4> over
 // pose * rows + the problem's range -- poses_fold_one's order, so the sums a start steps on are what ea_batch_eval_poses
-// folds for that pose, wherever in the list the start sits.  Priors and the mask enter through LDS (prior_into_lds), lane 0
-// runs lm_begin / lm_advance on a member-by-member register copy of the state, the candidate pose is published lane-parallel
-// into the start's own slot (active = 0 once its solve has ended), and a start that ends delivers its final state and trace
-// rows into pinned host memory and takes itself off its start's count of running problems (alive).
+// folds for that pose, wherever in the list the start sits.  The candidate pose goes into the start's own slot (active = 0
+// once its solve has ended); a start that ends always delivers its final state, its trace rows when the call wants
+// summaries, and takes itself off its start's count of running problems (alive).
 // Nobody waits for another workgroup: what a launch reads of the list, no launch of the same iteration writes (the list and
 // its length are ping-ponged by the iteration's parity), and the kernel boundary is the only ordering.
 template <int STRAT, bool SIDE>
@@ -2277,82 +2332,30 @@ __device__ __forceinline__ void starts_step_one(const StartsStep &a, const LMOpt
   __shared__ LMState s_st;
   __shared__ PoseState s_ps;
   __shared__ int s_trace_it;
-  constexpr int kStateWords = (int)(sizeof(LMState) / 8);
-  constexpr int kPoseDoubles = 4 + 3 + 9 + 27, kPoseFloats = 9 + 3 + 27;
   const int tid = threadIdx.x;
   const int p = start_k * a.count + problem;
   const GroupDesc gd = a.groups[problem];
   const int running = a.states[p].running;
-  const double state_word = tid < kStateWords ? reinterpret_cast<const double *>(a.states + p)[tid] : 0.0;
+  const double state_word = lm_state_word(a.states + p, tid);
   double pw = 0.0;
   if constexpr (SIDE) pw = prior_word(a.side, a.count, problem, tid);
   const int base = pose * a.rows_per_pose;
   reduce_tiles<kLmThreads, 4>(a.rows, base + gd.tile_begin, base + gd.tile_end, s_part, s_acc);
   if (!running) return;  // uniform: this problem of the start has ended, a sibling keeps the start in the list
-  if (tid < kStateWords) reinterpret_cast<double *>(&s_st)[tid] = state_word;
-  if constexpr (SIDE) {
-    if (tid < kPriorWords) reinterpret_cast<double *>(&prior_lds())[tid] = pw;
-  }
-  __syncthreads();
-  if constexpr (SIDE) prior_into_lds(s_st, s_acc, tid);
+  lm_step_park<SIDE>(state_word, pw, s_st, s_acc, tid);
   LMTrace *const tr = a.traces ? a.traces + p : nullptr;
   LMTrace *const host_tr = a.host_traces ? a.host_traces + p : nullptr;
   LMPending pend;
   double acc[kAccSlots];
   if (tid == 0) {
     LMState st;
-    lm_copy_state(&st, &s_st);
-#pragma unroll
-    for (int i = 0; i < kAccSlots; ++i) acc[i] = s_acc[i];
-    if (EA_UNLIKELY(st.num_evals == 0)) lm_begin<STRAT, false, SIDE>(&st, a.cold + p, tr, &opt, acc, &pend);
-    else lm_advance<STRAT, false, SIDE>(&st, a.cold + p, tr, &opt, acc, &pend);
-    make_pose_core(st.cand, st.rot_transposed, st.running, &s_ps, /*zero_unused_G=*/false);
-    lm_copy_state(&s_st, &st);
-    s_trace_it = pend.trace_it;
+    EA_LM_STEP_LANE0(false, st, s_st, s_acc, a.cold + p, tr, opt, &s_ps, s_trace_it, acc, pend, (void)0);
   }
   __syncthreads();
-  if (tid < kStateWords) reinterpret_cast<double *>(a.states + p)[tid] = reinterpret_cast<const double *>(&s_st)[tid];
-  {
-    // pose: doubles copied by lanes 64.., float mirrors converted by lanes 128.., flags by lane 192 (ea_lm_step_kernel)
-    const double *pd_src = reinterpret_cast<const double *>(&s_ps);
-    const int d = tid - 64, f = tid - 128;
-    const bool skip_g = s_ps.unit_q != 0;
-    if (d >= 0 && d < kPoseDoubles) reinterpret_cast<double *>(a.poses + p)[d] = (skip_g && d >= 16) ? 0.0 : pd_src[d];
-    if (f >= 0 && f < kPoseFloats) {
-      const double v = f < 9 ? s_ps.R[f] : (f < 12 ? s_ps.t[f - 9] : (skip_g ? 0.0 : s_ps.G[f - 12]));
-      (&a.poses[p].Rf[0])[f] = (float)v;
-    }
-    if (tid == 192) { a.poses[p].unit_q = s_ps.unit_q; a.poses[p].active = s_ps.active; }
-  }
+  lm_step_publish(s_st, s_ps, a.states + p, a.poses + p, tid);
   if (tid == 0) lm_flush(&pend, a.cold + p, tr, acc);
-  if (!s_st.running) {  // uniform: this solve ends with this launch -- final state and trace rows into pinned host memory
-    if (tid < kStateWords) reinterpret_cast<double *>(a.host_states + p)[tid] = reinterpret_cast<const double *>(&s_st)[tid];
-    if (host_tr) {
-      const int last = min(s_st.iteration, kTrace - 1);  // rows 0 .. last exist
-      auto copy_row = [&](int r) {
-        host_tr->it_cost[r] = tr->it_cost[r];
-        host_tr->it_cost_change[r] = tr->it_cost_change[r];
-        host_tr->it_gradient_max_norm[r] = tr->it_gradient_max_norm[r];
-        host_tr->it_step_norm[r] = tr->it_step_norm[r];
-        host_tr->it_relative_decrease[r] = tr->it_relative_decrease[r];
-        host_tr->it_radius[r] = tr->it_radius[r];
-        host_tr->it_successful[r] = tr->it_successful[r];
-      };
-      if (s_trace_it == last) {
-        // the usual end: rows < last come from earlier launches (one lane each), lane 0 holds the last one
-        if (tid < last) copy_row(tid);
-        if (tid == 0) {
-          LMPending h = pend;
-          h.store_system = 0;
-          lm_flush(&h, a.cold + p, host_tr, acc);
-        }
-      } else if (tid == 0) {
-        // rows written by this very launch through lm_trace (invalid steps): lane 0 wrote them, lane 0 copies them
-        __threadfence();
-        for (int r = 0; r <= last; ++r) copy_row(r);
-      }
-    }
-    __threadfence_system();
+  if (!s_st.running) {  // uniform: this solve ends with this launch
+    EA_LM_STEP_DELIVER(true, host_tr, s_st, s_trace_it, pend, acc, a.cold + p, tr, a.host_states + p, host_tr, tid);
     if (tid == 0) __hip_atomic_fetch_add(a.alive + start_k, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
@@ -2365,15 +2368,8 @@ template <int STRAT, bool SIDE>
 __global__ __launch_bounds__(kLmThreads) void ea_lm_step_starts_kernel(StartsStep a, LMOptions opt_arg) {
   __shared__ int s_is_last;
   __shared__ unsigned long long s_masks[4];
-  static_assert(sizeof(LMState) % 8 == 0 && (int)(sizeof(LMState) / 8) <= kLmThreads, "one 8-byte state word per lane");
-  static_assert(offsetof(PoseState, Rf) == (4 + 3 + 9 + 27) * 8 && offsetof(PoseState, unit_q) == (4 + 3 + 9 + 27) * 8 + (9 + 3 + 27) * 4,
-                "PoseState layout");
   LMOptions opt = opt_arg;
-  asm volatile("" : "+s"(opt.max_num_iterations), "+s"(opt.function_tolerance), "+s"(opt.gradient_tolerance),
-                    "+s"(opt.parameter_tolerance), "+s"(opt.initial_trust_region_radius), "+s"(opt.max_trust_region_radius),
-                    "+s"(opt.min_trust_region_radius), "+s"(opt.min_relative_decrease), "+s"(opt.min_lm_diagonal),
-                    "+s"(opt.max_lm_diagonal), "+s"(opt.max_num_consecutive_invalid_steps), "+s"(opt.jacobi_scaling),
-                    "+s"(opt.strategy));
+  EA_LM_PIN_OPTIONS(opt);
   const int tid = threadIdx.x;
   const int n_live = *a.n_in;
   int pose, problem;
@@ -2432,7 +2428,7 @@ __global__ __launch_bounds__(kLmThreads) void ea_lm_step_starts_kernel(StartsSte
 //
 // One more workgroup than chunks: the one past the last chunk has no points and is the WRITER -- state, cold system, trace row,
 // the pose (for whoever evaluates at it afterwards), the host's progress words and, when the solve ends, the final delivery
-// into pinned host memory, exactly as ea_lm_step_kernel does them.  Its stores do not sit in any evaluator's memory counter.
+// into pinned host memory, by the pieces ea_lm_step_kernel uses.  Its stores do not sit in any evaluator's memory counter.
 // A finished problem is recognised by every later launch from poses[p].active == 0 (written once, by the writer of the
 // launch in which the state machine stopped; in that launch every workgroup finds out by itself).
 // The cold system (JtJ, Jtr at x for the step after a rejected one; the dogleg's vectors) is read into LDS, one copy per
@@ -2464,9 +2460,6 @@ __global__ __launch_bounds__(kLmThreads) void ea_lm_iter_kernel(
   extern __shared__ __align__(16) unsigned char smem[];
   double *s_red = reinterpret_cast<double *>(smem);
   int *s_box = reinterpret_cast<int *>(smem + kRedBytes);
-  constexpr int kStateWords = (int)(sizeof(LMState) / 8), kColdWords = (int)(sizeof(LMCold) / 8);
-  constexpr int kPoseDoubles = 4 + 3 + 9 + 27, kPoseFloats = 9 + 3 + 27;
-  static_assert(kStateWords <= NT && kColdWords <= NT, "one 8-byte word per lane");
   const int chunk = shape & 0xffff, xcd_remap = (shape >> 16) & 1;
   const int p = blockIdx.y, tid = threadIdx.x;
   const int bx = blockIdx.x;
@@ -2474,11 +2467,7 @@ __global__ __launch_bounds__(kLmThreads) void ea_lm_iter_kernel(
   const bool writer = bx == (int)gridDim.x - 1;  // (= the last chunk index in either mapping; the launcher sizes the grid past the data)
   const long long start = (long long)c * chunk;
   LMOptions opt = opt_arg;
-  asm volatile("" : "+s"(opt.max_num_iterations), "+s"(opt.function_tolerance), "+s"(opt.gradient_tolerance),
-                    "+s"(opt.parameter_tolerance), "+s"(opt.initial_trust_region_radius), "+s"(opt.max_trust_region_radius),
-                    "+s"(opt.min_trust_region_radius), "+s"(opt.min_relative_decrease), "+s"(opt.min_lm_diagonal),
-                    "+s"(opt.max_lm_diagonal), "+s"(opt.max_num_consecutive_invalid_steps), "+s"(opt.jacobi_scaling),
-                    "+s"(opt.strategy));
+  EA_LM_PIN_OPTIONS(opt);
   // problem 0's points go out first (their addresses came with the wave), then everything uniform in one batch
   T X[PPT], Y[PPT], Z[PPT];
   const bool early = BUF && p == 0 && n0 > 0 && start < n0;  // (uniform)
@@ -2491,7 +2480,7 @@ __global__ __launch_bounds__(kLmThreads) void ea_lm_iter_kernel(
   GroupDesc gd = {tile0_begin, tile0_end, 0, 1};
   if (p != 0) gd = groups[p];  // (uniform)
   const int evals_before = st_in[p].num_evals;
-  const double state_word = tid < kStateWords ? reinterpret_cast<const double *>(st_in + p)[tid] : 0.0;
+  const double state_word = lm_state_word(st_in + p, tid);
   const double cold_word = (tid & 63) < kColdWords ? reinterpret_cast<const double *>(cold_in + p)[tid & 63] : 0.0;
   double pw = 0.0;
   if constexpr (SIDE) pw = prior_word(groups, gridDim.y, p, tid);
@@ -2507,13 +2496,8 @@ __global__ __launch_bounds__(kLmThreads) void ea_lm_iter_kernel(
   if (evaluator && !early)  // (problems behind the first of a batch, or flat addressing: their points wait for the descriptor)
     load_chunk_points<T, PPT, NT, BUF>(static_cast<const T *>(pd.x) + start, static_cast<const T *>(pd.y) + start,
                                        static_cast<const T *>(pd.z) + start, count, X, Y, Z);
-  if (tid < kStateWords) reinterpret_cast<double *>(&s_st)[tid] = state_word;
   if ((tid & 63) < kColdWords) reinterpret_cast<double *>(&s_cold[tid >> 6])[tid & 63] = cold_word;  // (own wavefront's copy)
-  if constexpr (SIDE) {
-    if (tid < kPriorWords) reinterpret_cast<double *>(&prior_lds())[tid] = pw;
-  }
-  __syncthreads();
-  if constexpr (SIDE) prior_into_lds(s_st, s_acc, tid);
+  lm_step_park<SIDE>(state_word, pw, s_st, s_acc, tid);
   EA_LM_STAMP_PUT(0, evals_before, t_enter_);
   EA_LM_STAMP(1, evals_before);  // folded
   if (writer) {
@@ -2524,63 +2508,19 @@ __global__ __launch_bounds__(kLmThreads) void ea_lm_iter_kernel(
     double acc[kAccSlots];
     if (tid == 0) {
       LMState st;
-      lm_copy_state(&st, &s_st);
-#pragma unroll
-      for (int i = 0; i < kAccSlots; ++i) acc[i] = s_acc[i];
-      if (EA_UNLIKELY(st.num_evals == 0)) lm_begin<STRAT, false, SIDE>(&st, &s_cold[0], traces + p, &opt, acc, &pend);
-      else lm_advance<STRAT, false, SIDE>(&st, &s_cold[0], traces + p, &opt, acc, &pend);
-      make_pose_core(st.cand, st.rot_transposed, st.running, &s_pose[0], /*zero_unused_G=*/false);
-      lm_copy_state(&s_st, &st);
-      s_trace_it = pend.trace_it;
+      EA_LM_STEP_LANE0(false, st, s_st, s_acc, &s_cold[0], traces + p, opt, &s_pose[0], s_trace_it, acc, pend, (void)0);
       s_store_system = pend.store_system;
     }
     __syncthreads();
     const int running = s_st.running;
-    if (tid < kStateWords) reinterpret_cast<double *>(st_out + p)[tid] = reinterpret_cast<const double *>(&s_st)[tid];
-    {
-      const double *pd_src = reinterpret_cast<const double *>(&s_pose[0]);
-      const int a = tid - 64, f = tid - 128;
-      const bool skip_g = s_pose[0].unit_q != 0;
-      if (a >= 0 && a < kPoseDoubles) reinterpret_cast<double *>(poses + p)[a] = (skip_g && a >= 16) ? 0.0 : pd_src[a];
-      if (f >= 0 && f < kPoseFloats) {
-        const double v = f < 9 ? s_pose[0].R[f] : (f < 12 ? s_pose[0].t[f - 9] : (skip_g ? 0.0 : s_pose[0].G[f - 12]));
-        (&poses[p].Rf[0])[f] = (float)v;
-      }
-      if (tid == 192) { poses[p].unit_q = s_pose[0].unit_q; poses[p].active = s_pose[0].active; }
-    }
+    lm_step_publish(s_st, s_pose[0], st_out + p, poses + p, tid);
     // the cold system of the next launch: JtJ, Jtr of this evaluation (accepted step: lm_flush) or what this launch read
     // (rejected step); the dogleg's vectors as the state machine left them
     if (tid < kColdWords && !(s_store_system && tid < 27))
       reinterpret_cast<double *>(cold_out + p)[tid] = reinterpret_cast<const double *>(&s_cold[0])[tid];
     if (tid == 0) lm_flush(&pend, cold_out + p, traces + p, acc);
     if (!running) {
-      if (host_states) {
-        if (tid < kStateWords) reinterpret_cast<double *>(host_states + p)[tid] = reinterpret_cast<const double *>(&s_st)[tid];
-        const int last = min(s_st.iteration, kTrace - 1);
-        auto copy_row = [&](int r) {
-          const LMTrace &src = traces[p];
-          LMTrace &dst = host_traces[p];
-          dst.it_cost[r] = src.it_cost[r];
-          dst.it_cost_change[r] = src.it_cost_change[r];
-          dst.it_gradient_max_norm[r] = src.it_gradient_max_norm[r];
-          dst.it_step_norm[r] = src.it_step_norm[r];
-          dst.it_relative_decrease[r] = src.it_relative_decrease[r];
-          dst.it_radius[r] = src.it_radius[r];
-          dst.it_successful[r] = src.it_successful[r];
-        };
-        if (s_trace_it == last) {
-          if (tid < last) copy_row(tid);
-          if (tid == 0) {
-            LMPending h = pend;
-            h.store_system = 0;
-            lm_flush(&h, cold_out + p, host_traces + p, acc);
-          }
-        } else if (tid == 0) {
-          __threadfence();
-          for (int r = 0; r <= last; ++r) copy_row(r);
-        }
-        __threadfence_system();
-      }
+      EA_LM_STEP_DELIVER(host_states, true, s_st, s_trace_it, pend, acc, cold_out + p, traces + p, host_states + p, host_traces + p, tid);
       __syncthreads();
       if (tid == 0) __hip_atomic_store(progress + p, 0, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
@@ -2602,14 +2542,9 @@ __global__ __launch_bounds__(kLmThreads) void ea_lm_iter_kernel(
     LMState st;
     LMPending pend;
     double acc[kAccSlots];
-    lm_copy_state(&st, &s_st);
-#pragma unroll
-    for (int i = 0; i < kAccSlots; ++i) acc[i] = s_acc[i];
-    LMCold *cold = &s_cold[tid >> 6];
-    if (EA_UNLIKELY(st.num_evals == 0)) lm_begin<STRAT, true, SIDE>(&st, cold, nullptr, &opt, acc, &pend);
-    else lm_advance<STRAT, true, SIDE>(&st, cold, nullptr, &opt, acc, &pend);
-    EA_LM_STAMP(2, evals_before);  // state machine done
-    make_pose_core(st.cand, st.rot_transposed, st.running, &s_ps, /*zero_unused_G=*/false);
+    LMCold *cold = &s_cold[tid >> 6];  // (one pointer for both arms of the macro: spelled out twice it cost the LM kernels 50 - 100 instructions)
+    EA_LM_STEP_LANE0(true, st, s_st, s_acc, cold, nullptr, opt, &s_ps, s_trace_it, acc, pend,
+                     EA_LM_STAMP(2, evals_before) /* state machine done */);
     running_v = st.running;
   }
   const int running = __builtin_amdgcn_readfirstlane(running_v);

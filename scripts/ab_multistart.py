@@ -69,7 +69,7 @@ for K in (1, 8, 64, 512):
     a, b = stats(new), stats(old)
     out["K%d" % K] = {"solve_starts": a, "sequential_ea_solve": b, "speedup_median": b["median_ms"] / a["median_ms"],
                       "faster_beyond_baseline_spread": a["median_ms"] < b["min_ms"] - (b["max_ms"] - b["min_ms"]),
-                      "starts_launches": launches, "device_us_per_queued_iteration": sorted(dev)[1],
+                      "starts_launches": launches, "device_us_per_queued_iteration": sorted(dev)[1], "device_us_per_queued_iteration_min_max": [min(dev), max(dev)],
                       "iterations_max_new": max(its_new), "iterations_sum_new": sum(its_new), "iterations_sum_old": sum(its_old),
                       "converged_new": sum(x[0]["termination"] == capi.CONVERGENCE for x in s),
                       "converged_old": sum(x[2][0]["termination"] == capi.CONVERGENCE for x in seq)}

@@ -1,8 +1,11 @@
 """Two builds of the library on one box, alternating processes of bench.py itself (EA_HIP_LIB selects the build): every
 `value` of the headline, the median and the spread (max - min) per build, and whether every run of B beats A's best run.
-With --full, one more pair of `bench.py --full` runs at the end: kernel time per evaluation launch, eval_poses_call_ms and
-the k_poses figures of the other workloads.  With --dump DIR, a pair of --dump-outputs runs compared in max-norm.
-usage: python scripts/ab_two_builds_bench.py libA.so libB.so [--steps 2000 --warmup 200 --runs 5 --full --dump DIR]
+With --full, --full-runs more alternating pairs of `bench.py --full` runs at the end: of the last pair the kernel time per
+evaluation launch, eval_poses_call_ms and the k_poses figures of the other workloads; of every pair the trust-region figures
+(LM iterations per second at 1e5 points in the fused, pair and fp32 forms, the C4 batch's solve_ms) -- per build every value,
+median, min and max, and whether B's median lies inside A's min .. max.  With --dump DIR, a pair of --dump-outputs runs
+compared in max-norm.
+usage: python scripts/ab_two_builds_bench.py libA.so libB.so [--steps 2000 --warmup 200 --runs 5 --full --full-runs 5 --dump DIR]
 Every child runs under its own time limit; the first one that fails ends the script."""
 import argparse
 import json
@@ -11,6 +14,11 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# figure -> the keys that lead to it in bench.py's result line (each looked up at any depth below the one before)
+LM_KEYS = {"lm_iters_per_s_at_1e5_pts": ("lm_iters_per_s_at_1e5_pts",),
+           "lm_iters_per_s_at_1e5_pts_pair_form": ("lm_iters_per_s_at_1e5_pts_pair_form", "iters_per_s"),
+           "lm_fp32_at_1e5_pts_iters_per_s": ("lm_fp32_at_1e5_pts", "iters_per_s"),
+           "c4_batch_solve_ms": ("c4_batch_32_pairs_per_gpu", "solve_ms")}
 
 
 def bench(lib, extra, limit):
@@ -42,6 +50,7 @@ def main():
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--workload", default="c2")
     ap.add_argument("--full", action="store_true")
+    ap.add_argument("--full-runs", type=int, default=1, help="with --full: so many alternating pairs of `bench.py --full` runs")
     ap.add_argument("--dump", default=None)
     a = ap.parse_args()
     shape = ["--steps", str(a.steps), "--warmup", str(a.warmup), "--workload", a.workload]
@@ -56,12 +65,26 @@ def main():
     if a.runs:
         out["every_B_run_beats_best_A"] = min(vals[a.libs[1]]) > max(vals[a.libs[0]])
         out["B_median_over_A_median"] = out["B"]["median"] / out["A"]["median"]
+        out["B_median_inside_A_min_max"] = {"value": min(vals[a.libs[0]]) <= out["B"]["median"] <= max(vals[a.libs[0]])}
     if a.full:
+        lm = {l: {k: [] for k in LM_KEYS} for l in a.libs}   # the trust-region solves only `bench.py --full` times
+        for _ in range(a.full_runs):
+            for tag, l in zip("AB", a.libs):
+                d = bench(l, shape + ["--full", "--no-cpu-baseline"], 600)
+                out[tag]["full"] = {"value": d["value"], "kernel_ms": find(d, "kernel_ms"), "eval_poses_call_ms": find(d, "eval_poses_call_ms"),
+                                    "evaluation_launches": find(d, "evaluation_launches_in_timed_region"),
+                                    "k_poses": {k: v.get("k_poses") for k, v in (find(d, "other_workloads") or {}).items() if isinstance(v, dict)}}
+                for k, path in LM_KEYS.items():
+                    x = d
+                    for step in path:
+                        x = find(x, step) if x is not None else None
+                    if isinstance(x, (int, float)):
+                        lm[l][k].append(x)
         for tag, l in zip("AB", a.libs):
-            d = bench(l, shape + ["--full", "--no-cpu-baseline"], 600)
-            out[tag]["full"] = {"value": d["value"], "kernel_ms": find(d, "kernel_ms"), "eval_poses_call_ms": find(d, "eval_poses_call_ms"),
-                                "evaluation_launches": find(d, "evaluation_launches_in_timed_region"),
-                                "k_poses": {k: v.get("k_poses") for k, v in (find(d, "other_workloads") or {}).items() if isinstance(v, dict)}}
+            out[tag]["lm"] = {k: {"values": x, "median": sorted(x)[len(x) // 2], "min": min(x), "max": max(x)} for k, x in lm[l].items() if x}
+        # per figure: does B's median lie inside A's own min .. max of this session?
+        out.setdefault("B_median_inside_A_min_max", {}).update(
+            {k: out["A"]["lm"][k]["min"] <= out["B"]["lm"][k]["median"] <= out["A"]["lm"][k]["max"] for k in out["A"]["lm"] if k in out["B"]["lm"]})
     if a.dump:
         import numpy as np
         dirs = []

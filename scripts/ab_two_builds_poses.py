@@ -4,7 +4,9 @@ C2 fp32, C2 fp64).  usage: python scripts/ab_two_builds_poses.py libA.so libB.so
 with 1024-thread workgroups in the same order -- equal partial rows then mean equal bits -- and (b) at the default shape;
 then the same poses through the other kernels that share the head of a work item, each at buffer_loads 1 and 0: cost_poses,
 one solve_starts from the first four (poses, iteration counts, it_cost), and ea_solve from the first with fused_iterations
-on and off.  Every array must be array_equal between the builds: exit status 1 otherwise."""
+on and off; and the three forms of the LM step (fused, pair, K = 4 starts), lm / dogleg x {no side table, NormalPrior on t, held
+coordinates}: pose, counts, costs and all seven trace arrays.  Every array must be array_equal between the builds: exit
+status 1 otherwise."""
 import sys, os, json, subprocess
 CHILD = r'''
 import sys, numpy as np
@@ -39,6 +41,34 @@ out = {}
 def pad(v):   # a trace, NaN-padded to 11 rows
     a = np.full(11, np.nan); v = np.asarray(v, dtype=np.float64)[:11]; a[:len(v)] = v
     return a
+TRACE = ("it_cost", "it_cost_change", "it_gradient_max_norm", "it_step_norm", "it_relative_decrease", "it_radius", "it_successful")
+def whole(r, name, q, t, s):   # a solve's whole result: pose, counts, costs, the seven trace arrays
+    r.update({name + "_q": q, name + "_t": t})
+    for k in ("termination", "num_iterations", "num_successful_steps", "num_unsuccessful_steps", "initial_cost", "final_cost"):
+        r[name + "_" + k] = np.array([x[k] for x in s], dtype=np.float64)
+    for k in TRACE:
+        r[name + "_" + k] = np.array([pad(x[k]) for x in s])
+def step_cells(r, dtype, buf, Q, T):   # the three forms of the LM step: lm / dogleg x {no side table, prior on t, held coordinates}
+    for strat, sname in ((capi.STRATEGY_LM, "lm"), (capi.STRATEGY_DOGLEG, "dogleg")):
+        for side in ("none", "prior", "mask"):
+            P = capi.Problem(*cfg["K"], dtype=dtype); P.set_points(cfg["xyz"]); P.set_dt_grid(cfg["grid"]); P.set_loss(capi.LOSS_CAUCHY, 1.0)
+            if side == "prior":
+                P.set_normal_prior(1, 5.0 * np.eye(3), np.array([0.01, -0.005, 0.02]))
+            elif side == "mask":
+                P.set_constant_parameters([0, 0, 1, 0, 1, 0])
+            B = capi.Batch([P])
+            B.set_tuning("buffer_loads", buf)
+            name = "step_%s_%s" % (sname, side)
+            for fused in (-1, 0):
+                B.set_tuning("fused_iterations", fused)
+                q, t, s = B.solve(Q[0], T[0], max_num_iterations=10, strategy=strat)
+                whole(r, name + ("_fused" if fused else "_pair"), q, t, s)
+                r[name + ("_fused" if fused else "_pair") + "_form"] = np.array(B.info("fused_iterations"))
+            q, t, s, best = B.solve_starts(Q[:4], T[:4], max_num_iterations=10, strategy=strat)
+            whole(r, name + "_starts", q.reshape(-1, 4), t.reshape(-1, 3), [x for row in s for x in row])
+            r[name + "_starts_best"] = best
+            r[name + "_starts_form"] = np.array(B.info("starts_form"))
+            B.close(); P.close()
 for dtype, tag in ((capi.EA_F64, "f64"), (capi.EA_F32, "f32")):
     P = capi.Problem(*cfg["K"], dtype=dtype); P.set_points(cfg["xyz"]); P.set_dt_grid(cfg["grid"]); P.set_loss(capi.LOSS_CAUCHY, 1.0)
     B = capi.Batch([P])
@@ -63,6 +93,7 @@ for dtype, tag in ((capi.EA_F64, "f64"), (capi.EA_F32, "f32")):
             r.update({"solve%d_q" % fused: q, "solve%d_t" % fused: t, "solve%d_fused" % fused: np.array(B.info("fused_iterations")),
                       "solve%d_iterations" % fused: np.array([x["num_iterations"] for x in s]),
                       "solve%d_it_cost" % fused: np.array([pad(x["it_cost"]) for x in s])})
+        step_cells(r, dtype, buf, Q, T)
         np.savez(sys.argv[2] + "_%s_paths_buf%d.npz" % (tag, buf), **r)
     B.close(); P.close()
 '''
@@ -88,6 +119,11 @@ if "--bits" in sys.argv:
             differ += bad
             print(tag, "buffer_loads", buf, "%d arrays (eval_poses, cost_poses, solve_starts K = 4, ea_solve fused %s / %s):" %
                   (len(a.files), a["solve-1_fused"], a["solve0_fused"]), "DIFFER: %s" % bad if bad else "all equal bits")
+            forms = {f: int(a[f]) for f in a.files if f.endswith("_form")}   # 18 step cells: fused 1, pair 0, starts 1
+            wrong = [f for f, v in forms.items() if v != (0 if f.endswith("_pair_form") else 1)]
+            differ += wrong
+            print(tag, "buffer_loads", buf, "LM step cells (lm / dogleg x none / prior / mask x fused / pair / starts, whole result, 7 trace arrays):",
+                  "%d, forms %s" % (len(forms), "NOT AS INTENDED: %s" % wrong if wrong else "as intended"))
     sys.exit(1 if differ else 0)
 libs = sys.argv[1:3]
 res = {l: [] for l in libs}
