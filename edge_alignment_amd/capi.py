@@ -50,6 +50,7 @@ EXPORTED = [
     "ea_problem_get_loss_auto_scale", "ea_selftest_select",
     "ea_default_frame_params", "ea_batch_set_frames", "ea_batch_set_frames_device",
     "ea_default_canny_frame_params", "ea_batch_set_frames_canny", "ea_batch_set_frames_canny_device",
+    "ea_default_ros_frame_params", "ea_batch_set_frames_ros", "ea_batch_set_frames_ros_device",
 ]
 
 # measurement hooks (edge_alignment_amd/csrc/ea_hip_dev.h): bound by bench.py, the A/B scripts and the tests that pin the
@@ -128,6 +129,11 @@ class FrameParams(C.Structure):
 class CannyFrameParams(C.Structure):
     _fields_ = [("height", C.c_int), ("width", C.c_int), ("z_scaling", C.c_double), ("low_threshold", C.c_double),
                 ("high_threshold", C.c_double), ("now_normalize", C.c_int), ("norm_lo", C.c_double), ("norm_hi", C.c_double)]
+
+
+class RosFrameParams(C.Structure):
+    _fields_ = [("full_height", C.c_int), ("full_width", C.c_int), ("halvings", C.c_int), ("threshold1", C.c_double),
+                ("threshold2", C.c_double)]
 
 
 _lib = None
@@ -275,6 +281,10 @@ def load():
     L.ea_default_canny_frame_params.restype = None
     L.ea_batch_set_frames_canny.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(CannyFrameParams)]
     L.ea_batch_set_frames_canny_device.argtypes = L.ea_batch_set_frames_canny.argtypes
+    L.ea_default_ros_frame_params.argtypes = [C.POINTER(RosFrameParams), C.c_int, C.c_int]
+    L.ea_default_ros_frame_params.restype = None
+    L.ea_batch_set_frames_ros.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(RosFrameParams)]
+    L.ea_batch_set_frames_ros_device.argtypes = L.ea_batch_set_frames_ros.argtypes
     _lib = L
     return L
 
@@ -1017,7 +1027,7 @@ class Batch:
 
     def _frame_arrays(self, sides):
         """the arguments of a batched producer call, sides = [(name, frames or None, kind)] with kind 3: bgr (H, W, 3) uint8,
-        2: depth (H, W) uint16, 1: mask (H, W) uint8 -> (the frames' extent, whether they are device tensors, {name: array of
+        2: depth (H, W) uint16, 4: depth (H, W) float32, 1: mask (H, W) uint8 -> (the frames' extent, whether they are device tensors, {name: array of
         len(self) pointers or None}, what keeps the host frames alive)"""
         n = len(self)
         frames = {}
@@ -1045,14 +1055,15 @@ class Batch:
                     continue  # (a NULL entry: the library refuses the call)
                 if on_device:
                     import torch
-                    want = (torch.uint8,) if ch != 2 else (torch.int16,) + ((torch.uint16,) if hasattr(torch, "uint16") else ())
+                    want = ((torch.float32,) if ch == 4 else (torch.uint8,) if ch != 2 else
+                            (torch.int16,) + ((torch.uint16,) if hasattr(torch, "uint16") else ()))
                     if not f.is_cuda or f.device.index != device:
                         raise ValueError("%s[%d]: not a tensor on the batch's GPU %d" % (name, i, device))
                     if f.dtype not in want or not f.is_contiguous():
                         raise ValueError("%s[%d]: a contiguous %s tensor is expected" % (name, i, want[-1]))
                     ptrs[i] = f.data_ptr()
                 else:
-                    f = np.ascontiguousarray(f, dtype=np.uint8 if ch != 2 else np.uint16)
+                    f = np.ascontiguousarray(f, dtype=np.float32 if ch == 4 else np.uint8 if ch != 2 else np.uint16)
                     keep.append(f)
                     ptrs[i] = f.ctypes.data
                 hw = tuple(f.shape[:2])
@@ -1083,6 +1094,25 @@ class Batch:
             torch.cuda.current_stream(self.problems[0].device).synchronize()  # (as in set_frames)
         fn = L.ea_batch_set_frames_canny_device if on_device else L.ea_batch_set_frames_canny
         _check(fn(self._h, arrays["ref_bgr"], arrays["ref_depth"], arrays["now_bgr"], arrays["now_mask"], C.byref(prm)))
+
+    def set_frames_ros(self, ref_bgr=None, ref_depth=None, now_bgr=None, t1=150.0, t2=100.0, halvings=0):
+        """ea_batch_set_frames_ros[_device]: Problem.set_ref_frame_ros + Problem.set_now_frame_ros (with their halvings) for
+        every problem of the batch in one launch sequence, bit for bit.  The frames as for set_frames, at FULL resolution;
+        ref_depth: (H, W) float32 in metres (numpy, or torch.float32 tensors on the batch's GPU).  A current frame without
+        any edge raises EAError(EA_ERR_STATE) after everything else has been set: info("frames_without_edges")."""
+        sides = [("ref_bgr", ref_bgr, 3), ("ref_depth", ref_depth, 4), ("now_bgr", now_bgr, 3)]
+        if (ref_bgr is None) != (ref_depth is None) or all(v is None for _, v, _ in sides):
+            raise ValueError("ref_bgr and ref_depth go together, and one side must be given")
+        shape, on_device, arrays, keep = self._frame_arrays(sides)
+        L = load()
+        prm = RosFrameParams()
+        L.ea_default_ros_frame_params(C.byref(prm), *(shape or (0, 0)))
+        prm.halvings, prm.threshold1, prm.threshold2 = int(halvings), float(t1), float(t2)
+        if on_device:
+            import torch
+            torch.cuda.current_stream(self.problems[0].device).synchronize()  # (as in set_frames)
+        fn = L.ea_batch_set_frames_ros_device if on_device else L.ea_batch_set_frames_ros
+        _check(fn(self._h, arrays["ref_bgr"], arrays["ref_depth"], arrays["now_bgr"], C.byref(prm)))
 
     def residual_quantiles(self, q, t, probs):
         """ea_batch_residual_quantiles at q (n, 4), t (n, 3): (values [n, len(probs)], n_valid [n]), one launch sequence"""

@@ -400,7 +400,8 @@ struct ea_batch {
   // their pinned staging block (the table on its way up, the point counts on their way down); batch_frames_reserve
   unsigned char *d_frames = nullptr, *h_frames = nullptr;
   size_t frames_bytes = 0, h_frames_bytes = 0;
-  int frames_rounds = 0;  // looks at the hysteresis flags of the last batched producer call (ea_batch_set_frames_canny; else 0)
+  int frames_rounds = 0;  // looks at the hysteresis flags of the last batched producer call (ea_batch_set_frames_canny / _ros; else 0)
+  int frames_without_edges = 0;  // current frames without any edge in the last ea_batch_set_frames_ros call (else 0)
 };
 
 int ea::check_device(int device) {
@@ -1192,6 +1193,7 @@ int ea::batch_frames_reserve(ea_batch *b, size_t device_bytes, size_t pinned_byt
 }
 
 void ea::batch_frames_set_rounds(ea_batch *b, int rounds) { b->frames_rounds = rounds; }
+void ea::batch_frames_set_without_edges(ea_batch *b, int frames) { b->frames_without_edges = frames; }
 
 // (re)build descriptors and the tile list when any problem changed
 static void fill_desc(const ea_problem *p, ProblemDesc &d) {
@@ -3076,6 +3078,7 @@ extern "C" int ea_batch_get_info(const ea_batch *b, const char *key, int64_t *va
   else if (k == "starts_iterations") *value = b->last_starts_iterations;  // iterations it enqueued (look-ahead included)
   else if (k == "starts_device_ns") *value = b->last_starts_device_ns;    // between the event pair of "starts_events" = 1
   else if (k == "frames_hysteresis_rounds") *value = b->frames_rounds;    // the last batched producer call's looks at the hysteresis flags, both sides (0: Laplacian)
+  else if (k == "frames_without_edges") *value = b->frames_without_edges;  // current frames the last ea_batch_set_frames_ros call left alone (0: clean, Laplacian, Canny)
   else return fail(EA_ERR_INVALID_ARG, "unknown info key: " + k);
   return EA_OK;
 }

@@ -119,5 +119,8 @@ int batch_frames_reserve(ea_batch *b, size_t device_bytes, size_t pinned_bytes, 
                          unsigned char **pinned_block);
 // ea_batch_get_info's "frames_hysteresis_rounds": looks at the hysteresis flags the batch's last producer call has taken so far
 void batch_frames_set_rounds(ea_batch *b, int rounds);
+// ea_batch_get_info's "frames_without_edges": current frames of the last ea_batch_set_frames_ros call that had no edge (every
+// batched producer call starts by setting it to 0)
+void batch_frames_set_without_edges(ea_batch *b, int frames);
 
 }  // namespace ea

@@ -90,4 +90,66 @@ inline FrameWs frame_ws(int H, int W) {
 
 inline size_t frame_ws_bound(int H, int W) { return 32 * (size_t)H * W + 16 * (size_t)W + 19 * 256; }
 
+// The halving stage of ea_batch_set_frames_ros: where the full-resolution frames of one frame pair lie on their way to the
+// working resolution (full >> halvings), `halvings` times the 2 x 2 mean.  The stage FOLLOWS the frame's workspace in the
+// frame's block -- every offset is from the start of frame_ws(full_H >> halvings, full_W >> halvings), none below its
+// total -- so one stride, frame_stage(...).total, takes a kernel from frame z's workspace and stage to frame z + 1's.
+// Like frame_ws it is a pure function, swept on the host by tests/frame_stage_host_shim.cpp.
+// With npf = full_H * full_W pixels per full-size frame:
+//
+//   region         bytes         holds
+//   bgr_full       3 npf         the uploaded full-size colour frame   (host frames only: a device frame is read in place
+//   depth_full     4 npf         the uploaded full-size float depth     by the first halving step)
+//   bgr_a, depth_a 3, 4 npf/4    what halving step 0, 2, 4, ... writes when it is not the last  (halvings >= 2)
+//   bgr_b, depth_b 3, 4 npf/16   what halving step 1, 3, 5, ... writes when it is not the last  (halvings >= 3)
+//
+// The last step writes the frame's `bgr` / `depth` regions of the workspace, and a step reads what the step before wrote,
+// so step k (extent full >> k -> full >> (k + 1), at most npf / 4^(k + 1) pixels out) fits the partner of its parity.  The
+// two sides of a pair use the stage one after the other (the current side has no depth).  halvings == 0: no stage, total
+// = the workspace's.  Per full-size pixel that is 7 bytes for host frames, 7/4 with two halvings and 7/16 more with three:
+//   frame_stage(...).total <= frame_stage_bound(...) = frame_ws_bound(working extent) + (7 + 7/4 + 7/16) npf + 6 * 256,
+// 9.19 bytes per full-size pixel at most (2.19 for device frames) on top of the workspace's 31.5 per working pixel: for
+// 640 x 480 frames halved once, 2.3 + 2.1 MiB per frame from host memory.  npf <= 2^30: below 2^34.
+struct FrameStage {
+  WsRegion<uint8_t> bgr_full;
+  WsRegion<float> depth_full;
+  WsRegion<uint8_t> bgr_a;
+  WsRegion<float> depth_a;
+  WsRegion<uint8_t> bgr_b;
+  WsRegion<float> depth_b;
+  size_t ws_total = 0;  // frame_ws(working extent).total: where the stage begins
+  size_t total = 0;     // workspace and stage: the stride from one frame's block to the next
+};
+
+inline FrameStage frame_stage(int full_H, int full_W, int halvings, bool host_frames) {
+  const size_t npf = (size_t)full_H * full_W;
+  FrameStage st;
+  st.ws_total = frame_ws(full_H >> halvings, full_W >> halvings).total;
+  size_t off = st.ws_total;
+  auto put = [&off](auto &r, size_t bytes) {
+    r.off = off;
+    r.bytes = bytes;
+    off = (off + bytes + 255) & ~(size_t)255;
+  };
+  if (halvings > 0 && host_frames) {
+    put(st.bgr_full, 3 * npf);
+    put(st.depth_full, 4 * npf);
+  }
+  if (halvings > 1) {
+    put(st.bgr_a, 3 * (npf / 4));
+    put(st.depth_a, 4 * (npf / 4));
+  }
+  if (halvings > 2) {
+    put(st.bgr_b, 3 * (npf / 16));
+    put(st.depth_b, 4 * (npf / 16));
+  }
+  st.total = off;
+  return st;
+}
+
+inline size_t frame_stage_bound(int full_H, int full_W, int halvings) {
+  const size_t npf = (size_t)full_H * full_W;
+  return frame_ws_bound(full_H >> halvings, full_W >> halvings) + 7 * npf + 7 * (npf / 4) + 7 * (npf / 16) + 6 * 256;
+}
+
 }  // namespace ea

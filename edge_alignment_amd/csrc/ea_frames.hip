@@ -1,7 +1,7 @@
 // ea_frames.hip — the host side of everything that starts from raw frames: the frame producers behind
 // ea_problem_set_{ref,now}_frame* (raw images -> edge points / DT image through the kernels of ea_preprocess.hip, in a
-// workspace laid out by ea_frame_ws.h), their batched form ea_batch_set_frames[_device] (N frame pairs, the frame a grid
-// dimension of every launch), ea_resize_half, the read-backs ea_problem_get_points / _get_dt, and the frame-to-frame
+// workspace laid out by ea_frame_ws.h), their batched forms ea_batch_set_frames[_canny|_ros][_device] (N frame pairs, the
+// frame a grid dimension of every launch), ea_resize_half, the read-backs ea_problem_get_points / _get_dt, and the frame-to-frame
 // tracker ea_tracker_*.  Host code only: this file holds no kernel.
 
 #include <hip/hip_runtime.h>
@@ -684,9 +684,12 @@ extern "C" int ea_problem_debug_now_frame(ea_problem *p, const uint8_t *bgr, int
 // a batch, the frame a grid dimension of each step (ea_launch.h: FramesLaunch) ----------------------------------------------
 //
 // Memory, owned by the batch (batch_frames_reserve): a device block [count x frame_ws(H, W) | FrameSlot x count] -- 31.5
-// bytes per pixel per frame -- and a pinned block [FrameSlot x count | FrameSlot x count | int x count | int x 8 count]: two
-// stagings of the table, because it goes up twice when reference frames are given (the point arrays exist only once the
-// counts are back), the counts, and the hysteresis flags of the Canny flavour (further down).  Everything runs on the null stream, like the per-problem producers, with two waits: the counts, the end.
+// bytes per pixel per frame; in the ROS call each frame's block is frame_stage(...), the workspace and the halving stage
+// behind it, and the frame pointers of a device call follow the slots -- and a pinned block [table | table | int x count | int x 8 count]: two stagings of the table
+// (FrameSlot x count, and behind them the ROS call's 3 x count frame pointers), because it goes up twice when reference frames
+// are given (the point arrays exist only once the counts are back), the counts, and the hysteresis flags of the Canny and ROS
+// flavours (further down).  Everything runs on the null stream, like the per-problem producers, with two waits: the counts,
+// the end.
 
 extern "C" void ea_default_frame_params(ea_frame_params *prm, int height, int width) {
   if (!prm) return;
@@ -715,20 +718,32 @@ struct BatchFrames {
   ea_problem *const *probs = nullptr;
   int count = 0, device = 0, H = 0, W = 0, dtype = 0;
   bool ref = false, now = false, on_device = false;
+  // ea_batch_set_frames_ros: the frames as handed in are full_H x full_W and come down to H x W by `halvings` halving steps
+  bool ros = false;
+  int full_H = 0, full_W = 0, halvings = 0;
   FrameWs ws;
+  FrameStage st;      // (ros) the halving stage behind each frame's workspace
+  size_t stride = 0;  // from one frame's block to the next: ws.total, or st.total with a stage
   size_t n = 0, np = 0, table_bytes = 0;
-  unsigned char *base = nullptr;  // frame 0's workspace; frame i's lies i * ws.total further on (frame(i))
+  unsigned char *base = nullptr;  // frame 0's workspace; frame i's lies i * stride further on (frame(i))
   FrameSlot *h_slots[2] = {nullptr, nullptr};
   int *h_totals = nullptr, *h_flags = nullptr;
   FramesLaunch f;
   std::vector<FrameSlot> slots;
+  // (ros, device frames, halvings > 0) the caller's full-size frames, which the first halving step reads in place: [ref_bgr x
+  // n | ref_depth x n | now_bgr x n], travelling behind the slots in every upload of the table; d_ptrs: where they land
+  std::vector<const void *> ptrs;
+  const void *const *d_ptrs = nullptr;
+  std::vector<unsigned char> no_image;  // (ros) current frames without any edge: no alloc_dt, no dt_landed
   int stage = 0;
   long long max_total = 0, max_weighted = 0;
-  unsigned char *frame(size_t i) const { return base + i * ws.total; }
+  unsigned char *frame(size_t i) const { return base + i * stride; }
 };
 
-// every check that both calls make, none of which touches a device or a problem.  now_mask: nullable (the Canny call's).
-static int batch_frames_check(ea_batch *b, const uint8_t *const *ref_bgr, const uint16_t *const *ref_depth,
+// every check that all three calls make, none of which touches a device or a problem.  now_mask: nullable (the Canny call's).
+// ref_depth: uint16 or, for the ROS call, float frames -- depth_align is the element size a device frame must be aligned to.
+// H, W: the extent the producers work at.
+static int batch_frames_check(ea_batch *b, const uint8_t *const *ref_bgr, const void *const *ref_depth, size_t depth_align,
                               const uint8_t *const *now_bgr, const uint8_t *const *now_mask, int H, int W, double z_scaling,
                               bool on_device, BatchFrames *j) {
   const bool ref = ref_bgr || ref_depth, now = now_bgr != nullptr;
@@ -755,7 +770,7 @@ static int batch_frames_check(ea_batch *b, const uint8_t *const *ref_bgr, const 
     for (int i = 0; i < count; ++i) {
       int rc = EA_OK;
       if (ref) rc = check_device_frame(ref_bgr[i], device, 1, "ref_bgr");
-      if (rc == EA_OK && ref) rc = check_device_frame(ref_depth[i], device, 2, "ref_depth");
+      if (rc == EA_OK && ref) rc = check_device_frame(ref_depth[i], device, depth_align, "ref_depth");
       if (rc == EA_OK && now) rc = check_device_frame(now_bgr[i], device, 1, "now_bgr");
       if (rc == EA_OK && now_mask) rc = check_device_frame(now_mask[i], device, 1, "now_mask");
       if (rc != EA_OK) return rc;
@@ -769,36 +784,53 @@ static int batch_frames_check(ea_batch *b, const uint8_t *const *ref_bgr, const 
 // count | int x count | int x count x kCannyFrameFlags] (two stagings of the table, the counts, the hysteresis flags of the
 // Canny call), and the slots filled with what is known before the first launch: where each side's frames are read -- the
 // workspace's copy of a host frame, the caller's device frame in place -- and the problem's camera and depth weighting.
-static int batch_frames_begin(ea_batch *b, const uint8_t *const *ref_bgr, const uint16_t *const *ref_depth,
+// The ROS call (j->ros): each frame's block is its workspace and its halving stage (ea_frame_ws.h: frame_stage), the slots'
+// colour and float depth pointers name the frame at the WORKING resolution -- the workspace's `bgr` / `depth`, or with
+// halvings == 0 the caller's device frame in place -- and device frames to be halved travel as pointers behind the slots.
+static int batch_frames_begin(ea_batch *b, const uint8_t *const *ref_bgr, const void *const *ref_depth,
                               const uint8_t *const *now_bgr, const uint8_t *const *now_mask, BatchFrames *j) {
   HIPCHK(hipSetDevice(j->device));
   j->ws = frame_ws(j->H, j->W);
   const FrameWs &ws = j->ws;
   const size_t n = j->n = (size_t)j->count;
   j->np = (size_t)j->H * j->W;
-  const size_t table_bytes = j->table_bytes = n * sizeof(FrameSlot);
-  static_assert(sizeof(FrameSlot) % 8 == 0, "slots follow the 256-byte aligned workspaces");
+  j->stride = ws.total;
+  if (j->ros) {
+    j->st = frame_stage(j->full_H, j->full_W, j->halvings, !j->on_device);
+    j->stride = j->st.total;
+    if (j->on_device && j->halvings > 0) j->ptrs.assign(3 * n, nullptr);
+  }
+  const size_t table_bytes = j->table_bytes = n * sizeof(FrameSlot) + j->ptrs.size() * sizeof(void *);
+  static_assert(sizeof(FrameSlot) % 8 == 0, "slots follow the 256-byte aligned workspaces, pointers follow the slots");
   unsigned char *d_block = nullptr, *h_block = nullptr;
-  const int rc = batch_frames_reserve(b, n * ws.total + table_bytes, 2 * table_bytes + n * (1 + kCannyFrameFlags) * sizeof(int),
+  const int rc = batch_frames_reserve(b, n * j->stride + table_bytes, 2 * table_bytes + n * (1 + kCannyFrameFlags) * sizeof(int),
                                       &d_block, &h_block);
   if (rc != EA_OK) return rc;
+  batch_frames_set_without_edges(b, 0);
   j->base = d_block;
   j->h_slots[0] = reinterpret_cast<FrameSlot *>(h_block);
   j->h_slots[1] = reinterpret_cast<FrameSlot *>(h_block + table_bytes);
   j->h_totals = reinterpret_cast<int *>(h_block + 2 * table_bytes);
   j->h_flags = j->h_totals + n;
-  j->f.n = j->count; j->f.H = j->H; j->f.W = j->W; j->f.stride = ws.total;
-  j->f.slots = reinterpret_cast<FrameSlot *>(d_block + n * ws.total);
+  j->f.n = j->count; j->f.H = j->H; j->f.W = j->W; j->f.stride = j->stride;
+  j->f.slots = reinterpret_cast<FrameSlot *>(d_block + n * j->stride);
+  j->d_ptrs = reinterpret_cast<const void *const *>(d_block + n * j->stride + n * sizeof(FrameSlot));
   j->slots.resize(n);
-  std::memset(j->slots.data(), 0, table_bytes);
+  std::memset(j->slots.data(), 0, n * sizeof(FrameSlot));
   for (size_t i = 0; i < n; ++i) {
     ea_problem *p = j->probs[i];
     p->ws_now_kind = 0;  // (the problem's own workspace holds nothing of this frame pair)
     FrameSlot &sl = j->slots[i];
     unsigned char *wsi = j->frame(i);
-    if (j->ref) sl.bgr[0] = j->on_device ? ref_bgr[i] : ws.bgr.at(wsi);
-    if (j->ref) sl.depth = j->on_device ? ref_depth[i] : ws.depth.at<uint16_t>(wsi);
-    if (j->now) sl.bgr[1] = j->on_device ? now_bgr[i] : ws.bgr.at(wsi);
+    const bool in_place = j->on_device && j->halvings == 0;  // (halvings: 0 outside the ROS call)
+    if (j->ref) sl.bgr[0] = in_place ? ref_bgr[i] : ws.bgr.at(wsi);
+    if (j->ref && !j->ros) sl.depth = in_place ? static_cast<const uint16_t *>(ref_depth[i]) : ws.depth.at<uint16_t>(wsi);
+    if (j->ref && j->ros) sl.depth_f32 = in_place ? static_cast<const float *>(ref_depth[i]) : ws.depth.at<float>(wsi);
+    if (j->now) sl.bgr[1] = in_place ? now_bgr[i] : ws.bgr.at(wsi);
+    if (!j->ptrs.empty()) {
+      if (j->ref) { j->ptrs[i] = ref_bgr[i]; j->ptrs[n + i] = ref_depth[i]; }
+      if (j->now) j->ptrs[2 * n + i] = now_bgr[i];
+    }
     if (now_mask) sl.mask = j->on_device ? now_mask[i] : ws.keep.at(wsi);
     sl.fx = p->cam.fx; sl.fy = p->cam.fy; sl.cx = p->cam.cx; sl.cy = p->cam.cy;
     sl.z_ref = p->dw_z_ref; sl.power = p->dw_power;
@@ -806,10 +838,17 @@ static int batch_frames_begin(ea_batch *b, const uint8_t *const *ref_bgr, const 
   return EA_OK;
 }
 
-// the table on its way up (a staging block is not written again before a wait has passed: it goes up at most twice per call)
+// The table on its way up: the slots and, behind them, the ROS call's frame pointers.  The rule: a staging block is not
+// written again before a wait of the null stream has passed since it last went up.  The Laplacian and Canny calls upload at
+// most twice, once from each staging.  The ROS call with both sides uploads three times -- before the reference side, with
+// the point arrays, with the images -- and the third takes the first staging again: the counts of BOTH sides come back
+// between the first and the third upload, each a blocking copy on the null stream, so the first upload has long landed.
 static hipError_t upload_table(BatchFrames *j) {
-  std::memcpy(j->h_slots[j->stage], j->slots.data(), j->table_bytes);
-  return hipMemcpyAsync(const_cast<FrameSlot *>(j->f.slots), j->h_slots[j->stage++], j->table_bytes, hipMemcpyHostToDevice, nullptr);
+  unsigned char *h = reinterpret_cast<unsigned char *>(j->h_slots[j->stage++ & 1]);
+  const size_t slot_bytes = j->n * sizeof(FrameSlot);
+  std::memcpy(h, j->slots.data(), slot_bytes);
+  if (!j->ptrs.empty()) std::memcpy(h + slot_bytes, j->ptrs.data(), j->ptrs.size() * sizeof(void *));
+  return hipMemcpyAsync(const_cast<FrameSlot *>(j->f.slots), h, j->table_bytes, hipMemcpyHostToDevice, nullptr);
 }
 
 // host frames into a region of every frame's workspace
@@ -819,13 +858,19 @@ static int upload_frames(const BatchFrames &j, const WsRegion<U> &r, const V *co
   return EA_OK;
 }
 
-// Reference side, first half: count -> scan on every frame's `edges` region, the counts back in one strided copy (a wait),
-// room for each problem's points and their arrays into its slot
-static int batch_ref_counts(BatchFrames *j, const WsRegion<uint8_t> &edges, int threshold) {
+// count -> scan on every frame's `edges` region, the totals back into h_totals in one strided copy (a wait)
+static int batch_counts_back(BatchFrames *j, const WsRegion<uint8_t> &edges, int threshold) {
   const FrameWs &ws = j->ws;
   HIPCHK(launch_edge_count_scan_frames(j->f, edges.at(j->base), threshold, ws.counts.at(j->base), nullptr));
-  HIPCHK(hipMemcpy2D(j->h_totals, sizeof(int), ws.counts.at(j->base) + frame_ws_blocks(j->H, j->W), ws.total, sizeof(int), j->n,
+  HIPCHK(hipMemcpy2D(j->h_totals, sizeof(int), ws.counts.at(j->base) + frame_ws_blocks(j->H, j->W), j->stride, sizeof(int), j->n,
                      hipMemcpyDeviceToHost));
+  return EA_OK;
+}
+
+// Reference side, first half: the counts, room for each problem's points and their arrays into its slot
+static int batch_ref_counts(BatchFrames *j, const WsRegion<uint8_t> &edges, int threshold) {
+  const int rc_counts = batch_counts_back(j, edges, threshold);
+  if (rc_counts != EA_OK) return rc_counts;
   for (size_t i = 0; i < j->n; ++i) {
     ea_problem *p = j->probs[i];
     const int total = j->h_totals[i];
@@ -842,11 +887,13 @@ static int batch_ref_counts(BatchFrames *j, const WsRegion<uint8_t> &edges, int 
   return EA_OK;
 }
 
-// Current side: every problem's image into its slot (a failure: the reference frames are put in place, no current frame is)
+// Current side: every problem's image into its slot (a failure: the reference frames are put in place, no current frame is).
+// A frame marked in no_image keeps the image it has: no alloc_dt, a slot without an image.
 static int batch_alloc_dts(BatchFrames *j) {
   int rc_dt = EA_OK;
   for (size_t i = 0; i < j->n && rc_dt == EA_OK; ++i) {
     ea_problem *p = j->probs[i];
+    if (!j->no_image.empty() && j->no_image[i]) continue;
     rc_dt = alloc_dt(p, j->W, j->H);
     j->slots[i].dt = p->d_dt; j->slots[i].dt32 = p->dtype == EA_F64 ? p->d_dt32 : nullptr; j->slots[i].pitch = p->pitch;
   }
@@ -867,7 +914,7 @@ static int batch_frames_end(const BatchFrames &j, int rc_dt) {
   HIPCHK(hipDeviceSynchronize());
   for (size_t i = 0; i < j.n; ++i) {
     if (j.ref) ref_points_landed(j.probs[i], j.slots[i].capacity);
-    if (j.now && rc_dt == EA_OK) dt_landed(j.probs[i]);
+    if (j.now && rc_dt == EA_OK && (j.no_image.empty() || !j.no_image[i])) dt_landed(j.probs[i]);
   }
   return rc_dt;  // (a failed alloc_dt: the reference frames are in place, no current frame is)
 }
@@ -877,8 +924,9 @@ static int batch_set_frames(ea_batch *b, const uint8_t *const *ref_bgr, const ui
   // every check comes before a device or a problem is touched
   if (!b || !prm) return fail(EA_ERR_INVALID_ARG, "NULL argument");
   BatchFrames j;
-  int rc = batch_frames_check(b, ref_bgr, ref_depth, now_bgr, nullptr, prm->height, prm->width, prm->z_scaling, on_device, &j);
-  if (rc == EA_OK) rc = batch_frames_begin(b, ref_bgr, ref_depth, now_bgr, nullptr, &j);
+  const void *const *ref_depth_v = reinterpret_cast<const void *const *>(ref_depth);
+  int rc = batch_frames_check(b, ref_bgr, ref_depth_v, 2, now_bgr, nullptr, prm->height, prm->width, prm->z_scaling, on_device, &j);
+  if (rc == EA_OK) rc = batch_frames_begin(b, ref_bgr, ref_depth_v, now_bgr, nullptr, &j);
   if (rc != EA_OK) return rc;
   batch_frames_set_rounds(b, 0);  // (no hysteresis in this chain)
   const FrameWs &ws = j.ws;
@@ -908,7 +956,7 @@ static int batch_set_frames(ea_batch *b, const uint8_t *const *ref_bgr, const ui
     }
     HIPCHK(launch_edge_strength_frames(j.f, 1, ws.gray.at(base), ws.lap.at(base), nullptr));
     HIPCHK(launch_threshold_median_frames(j.f, ws.lap.at(base), prm->now_threshold, prm->now_median, ws.mask.at(base), nullptr));
-    HIPCHK(launch_chamfer_frames(j.f, ws.mask.at(base), ws.G.at(base), ws.scan.at(base), ws.dist.at(base), ws.minmax.at(base), nullptr));
+    HIPCHK(launch_chamfer_frames(j.f, ws.mask.at(base), ws.G.at(base), ws.scan.at(base), ws.dist.at(base), nullptr, ws.minmax.at(base), nullptr));
     HIPCHK(launch_dt_store_frames(j.dtype, j.f, ws.dist.at(base), ws.minmax.at(base), prm->now_normalize, 0.0, 1.0, nullptr));
   }
   return batch_frames_end(j, rc_dt);
@@ -952,15 +1000,16 @@ static int batch_set_frames_canny(ea_batch *b, const uint8_t *const *ref_bgr, co
     return fail(EA_ERR_INVALID_ARG, "normalisation range must be finite");
   if (!(prm->z_scaling > 0.0) || !(prm->z_scaling <= DBL_MAX)) return fail(EA_ERR_INVALID_ARG, "z_scaling must be > 0 and finite");
   BatchFrames j;
-  rc = batch_frames_check(b, ref_bgr, ref_depth, now_bgr, now_mask, prm->height, prm->width, prm->z_scaling, on_device, &j);
-  if (rc == EA_OK) rc = batch_frames_begin(b, ref_bgr, ref_depth, now_bgr, now_mask, &j);
+  const void *const *ref_depth_v = reinterpret_cast<const void *const *>(ref_depth);
+  rc = batch_frames_check(b, ref_bgr, ref_depth_v, 2, now_bgr, now_mask, prm->height, prm->width, prm->z_scaling, on_device, &j);
+  if (rc == EA_OK) rc = batch_frames_begin(b, ref_bgr, ref_depth_v, now_bgr, now_mask, &j);
   if (rc != EA_OK) return rc;
   const FrameWs &ws = j.ws;
   unsigned char *base = j.base;
   int looks = 0, total_looks = 0;
   batch_frames_set_rounds(b, 0);
   auto canny = [&](int side, bool masked) {
-    const hipError_t e = launch_canny_frames(j.f, side, masked, lo, hi, ws.gray.at(base), ws.mag.at(base), ws.dir.at(base), ws.label.at(base),
+    const hipError_t e = launch_canny_frames(j.f, side, masked, lo, hi, /*l2_bgr=*/0, ws.gray.at(base), ws.mag.at(base), ws.dir.at(base), ws.label.at(base),
                                              ws.edges.at(base), ws.inv.at(base), ws.changed.at(base), j.h_flags, &looks, nullptr);
     if (e == hipSuccess) batch_frames_set_rounds(b, total_looks += looks);
     return e;
@@ -991,7 +1040,7 @@ static int batch_set_frames_canny(ea_batch *b, const uint8_t *const *ref_bgr, co
     }
     // (the scatter above reads the reference side's `edges` and is in front of this on the same stream)
     HIPCHK(canny(1, now_mask != nullptr));
-    HIPCHK(launch_chamfer_frames(j.f, ws.inv.at(base), ws.G.at(base), ws.scan.at(base), ws.dist.at(base), ws.minmax.at(base), nullptr));
+    HIPCHK(launch_chamfer_frames(j.f, ws.inv.at(base), ws.G.at(base), ws.scan.at(base), ws.dist.at(base), nullptr, ws.minmax.at(base), nullptr));
     HIPCHK(launch_dt_store_frames(j.dtype, j.f, ws.dist.at(base), ws.minmax.at(base), prm->now_normalize, prm->norm_lo, prm->norm_hi,
                                   nullptr));
   }
@@ -1008,6 +1057,151 @@ extern "C" int ea_batch_set_frames_canny_device(ea_batch *b, const uint8_t *cons
                                                 const uint8_t *const *now_bgr, const uint8_t *const *now_mask,
                                                 const ea_canny_frame_params *prm) {
   return batch_set_frames_canny(b, ref_bgr, ref_depth, now_bgr, now_mask, prm, true);
+}
+
+// ---- the ROS flavour of the batched producers: ea_problem_set_ref_frame_ros_scaled + ea_problem_set_now_frame_ros_scaled for
+// every problem of a batch.  Either side: the frames come down to the working resolution (batch_stage_ros: 2 launches per
+// halving for the reference side, 1 for the current side), then launch_canny_frames in its l2_bgr form -- 2 launches, 8
+// hysteresis launches and one wait per look, the finish -- then count and scan on `edges` without a depth test and the counts
+// back (a wait).  Reference side: the ROS scatter and the depth weights.  Current side: the column passes and the exact row
+// pass on `inv`, the store normalised to (0, 255), for the frames that have an edge.  Waits: one per look, the counts of each
+// side, the end -- five for a call with both sides and one look each, where the per-problem calls wait six times per PAIR.
+
+extern "C" void ea_default_ros_frame_params(ea_ros_frame_params *prm, int full_height, int full_width) {
+  if (!prm) return;
+  prm->full_height = full_height; prm->full_width = full_width;
+  prm->halvings = 0;
+  prm->threshold1 = 150.0; prm->threshold2 = 100.0;
+}
+
+// One side's frames at the working resolution: in every frame's `bgr` (and float `depth`: the reference side, depth given)
+// -- or, for device frames without halvings, nowhere: the slots name the caller's frames.  Host frames go up into the
+// workspace (halvings == 0: as they are, no NaN -> 0, like stage_scaled) or into the stage's full-size regions; the halving
+// steps then walk full -> a -> b -> a ... with the last one landing in the workspace (ea_frame_ws.h: frame_stage), the
+// first reading device frames in place through the pointer table behind the slots, NaN -> 0 on the first step only.
+static int batch_stage_ros(const BatchFrames &j, int side, const uint8_t *const *bgr, const float *const *depth) {
+  const FrameWs &ws = j.ws;
+  const FrameStage &st = j.st;
+  unsigned char *base = j.base;
+  const size_t npf = (size_t)j.full_H * j.full_W;
+  const bool has_depth = side == 0;
+  if (j.halvings == 0) {
+    if (j.on_device) return EA_OK;
+    int rc = upload_frames(j, ws.bgr, bgr, npf * 3);
+    if (rc == EA_OK && has_depth) rc = upload_frames(j, ws.depth, depth, npf * 4);
+    return rc;
+  }
+  const uint8_t *const *bgr_table = nullptr;
+  const float *const *depth_table = nullptr;
+  const uint8_t *bsrc = nullptr;
+  const float *dsrc = nullptr;
+  if (j.on_device) {
+    bgr_table = reinterpret_cast<const uint8_t *const *>(j.d_ptrs + (side == 0 ? 0 : 2 * j.n));
+    depth_table = reinterpret_cast<const float *const *>(j.d_ptrs + j.n);
+  } else {
+    int rc = upload_frames(j, st.bgr_full, bgr, npf * 3);
+    if (rc == EA_OK && has_depth) rc = upload_frames(j, st.depth_full, depth, npf * 4);
+    if (rc != EA_OK) return rc;
+    bsrc = st.bgr_full.at(base);
+    dsrc = st.depth_full.at(base);
+  }
+  int h = j.full_H, w = j.full_W;
+  for (int k = 0; k < j.halvings; ++k) {
+    const bool last = k == j.halvings - 1;
+    uint8_t *bdst = last ? ws.bgr.at(base) : (k & 1) ? st.bgr_b.at(base) : st.bgr_a.at(base);
+    float *ddst = last ? ws.depth.at<float>(base) : (k & 1) ? st.depth_b.at(base) : st.depth_a.at(base);
+    HIPCHK(launch_resize_half_bgr8_stack(j.f, k == 0 ? bgr_table : nullptr, bsrc, h, w, bdst, nullptr));
+    if (has_depth)
+      HIPCHK(launch_resize_half_f32_stack(j.f, k == 0 ? depth_table : nullptr, dsrc, h, w, ddst, /*nan_to_zero=*/k == 0 ? 1 : 0, nullptr));
+    bsrc = bdst; dsrc = ddst;
+    h /= 2; w /= 2;
+  }
+  return EA_OK;
+}
+
+static int batch_set_frames_ros(ea_batch *b, const uint8_t *const *ref_bgr, const float *const *ref_depth,
+                                const uint8_t *const *now_bgr, const ea_ros_frame_params *prm, bool on_device) {
+  // every check comes before a device or a problem is touched; the extents are checked as the per-problem _scaled calls do
+  if (!b || !prm) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  const int full_h = prm->full_height, full_w = prm->full_width;
+  if (full_h < 3 || full_w < 3 || full_h > 32768 || full_w > 32768 || (int64_t)full_h * full_w > 0x3fffffff)
+    return fail(EA_ERR_INVALID_ARG, "image extent out of range");
+  int rc = check_scaled_args(full_h, full_w, prm->halvings);
+  if (rc != EA_OK) return rc;
+  int lo, hi;
+  rc = ros_thresholds(prm->threshold1, prm->threshold2, &lo, &hi);
+  if (rc != EA_OK) return rc;
+  const int H = full_h >> prm->halvings, W = full_w >> prm->halvings;
+  if (H < 3 || W < 3) return fail(EA_ERR_INVALID_ARG, "image extent out of range");
+  BatchFrames j;
+  j.ros = true; j.full_H = full_h; j.full_W = full_w; j.halvings = prm->halvings;
+  const void *const *ref_depth_v = reinterpret_cast<const void *const *>(ref_depth);
+  rc = batch_frames_check(b, ref_bgr, ref_depth_v, sizeof(float), now_bgr, nullptr, H, W, /*z_scaling (metres already)=*/1.0, on_device, &j);
+  if (rc == EA_OK) rc = batch_frames_begin(b, ref_bgr, ref_depth_v, now_bgr, nullptr, &j);
+  if (rc != EA_OK) return rc;
+  const FrameWs &ws = j.ws;
+  unsigned char *base = j.base;
+  int looks = 0, total_looks = 0;
+  batch_frames_set_rounds(b, 0);
+  auto canny = [&](int side) {
+    const hipError_t e = launch_canny_frames(j.f, side, 0, lo, hi, /*l2_bgr=*/1, ws.gray.at(base), ws.mag.at(base), ws.dir.at(base),
+                                             ws.label.at(base), ws.edges.at(base), ws.inv.at(base), ws.changed.at(base), j.h_flags,
+                                             &looks, nullptr);
+    if (e == hipSuccess) batch_frames_set_rounds(b, total_looks += looks);
+    return e;
+  };
+  HIPCHK(upload_table(&j));  // where the frames are read, the cameras, the depth weighting
+  if (j.ref) {
+    rc = batch_stage_ros(j, 0, ref_bgr, ref_depth);
+    if (rc != EA_OK) return rc;
+    HIPCHK(canny(0));
+    // (no depth in the slots: every edge pixel is a point, src/SolveEA.cpp:61-78)
+    rc = batch_ref_counts(&j, ws.edges, 0);
+    if (rc != EA_OK) return rc;
+    HIPCHK(upload_table(&j));  // the point arrays
+    if (j.max_total > 0) HIPCHK(launch_edge_scatter_ros_stack(j.dtype, j.f, ws.edges.at(base), ws.counts.at(base), nullptr));
+    HIPCHK(launch_depth_weights_frames(j.dtype, j.f, j.max_weighted, nullptr));
+  }
+  int rc_dt = EA_OK, first_bare = -1, bare = 0;
+  if (j.now) {
+    // (the scatter above reads the reference side's `edges` and `depth` and is in front of this on the same stream; the
+    // current side writes no depth)
+    rc = batch_stage_ros(j, 1, now_bgr, nullptr);
+    if (rc != EA_OK) return rc;
+    HIPCHK(canny(1));
+    // a frame without any edge has no exact distance transform: it keeps the image it has, like the per-problem producer
+    rc = batch_counts_back(&j, ws.edges, 0);
+    if (rc != EA_OK) return rc;
+    j.no_image.assign(j.n, 0);
+    for (size_t i = 0; i < j.n; ++i)
+      if (j.h_totals[i] == 0) {
+        j.no_image[i] = 1;
+        if (bare++ == 0) first_bare = (int)i;
+      }
+    rc_dt = batch_alloc_dts(&j);
+    if (rc_dt == EA_OK && (size_t)bare < j.n) {
+      HIPCHK(upload_table(&j));  // the images; the first staging again, two waits after it last went up (upload_table)
+      HIPCHK(launch_chamfer_frames(j.f, ws.inv.at(base), ws.G.at(base), ws.scan.at(base), ws.dist.at(base), ws.dist.at<float>(base),
+                                   ws.minmax.at(base), nullptr));
+      HIPCHK(launch_dt_store_stack(j.dtype, j.f, ws.dist.at<float>(base), ws.minmax.at(base), 1, 0.0, 255.0, nullptr));
+    }
+  }
+  batch_frames_set_without_edges(b, bare);
+  rc = batch_frames_end(j, rc_dt);
+  if (rc == EA_OK && bare > 0)
+    return fail(EA_ERR_STATE, "no edge in " + std::to_string(bare) + " of the current frames, the first at index " +
+                                  std::to_string(first_bare) + ": the exact distance transform is undefined");
+  return rc;
+}
+
+extern "C" int ea_batch_set_frames_ros(ea_batch *b, const uint8_t *const *ref_bgr, const float *const *ref_depth,
+                                       const uint8_t *const *now_bgr, const ea_ros_frame_params *prm) {
+  return batch_set_frames_ros(b, ref_bgr, ref_depth, now_bgr, prm, false);
+}
+
+extern "C" int ea_batch_set_frames_ros_device(ea_batch *b, const uint8_t *const *ref_bgr, const float *const *ref_depth,
+                                              const uint8_t *const *now_bgr, const ea_ros_frame_params *prm) {
+  return batch_set_frames_ros(b, ref_bgr, ref_depth, now_bgr, prm, true);
 }
 
 // read back what the problem holds in HBM: points as n x 3 doubles, DT as H x W doubles ([v][u])

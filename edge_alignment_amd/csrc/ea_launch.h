@@ -102,13 +102,14 @@ struct SelectWork {
 };
 // The batched frame producers (ea_batch_set_frames): the frame is blockIdx.z of every launch.  What lies in the producers'
 // workspace is addressed as `pointer for frame 0` + z * stride bytes (the batch owns n consecutive frame_ws(H, W) layouts,
-// stride = frame_ws(H, W).total, a multiple of 256); what the problems or the caller own comes out of a device table with one
-// FrameSlot per frame.
+// stride = frame_ws(H, W).total, a multiple of 256 -- or frame_stage(...).total where the ROS call's halving stage follows
+// each frame's workspace); what the problems or the caller own comes out of a device table with one FrameSlot per frame.
 struct FrameSlot {
   const uint8_t *bgr[2];  // the colour frame of the reference ([0]) / current ([1]) side: the workspace's copy of a host
                           // frame, or the caller's device frame read in place
-  const uint16_t *depth;  // likewise
+  const uint16_t *depth;  // likewise (NULL in ea_batch_set_frames_ros, whose count keeps every edge pixel)
   const uint8_t *mask;    // likewise: the current side's mask of ea_batch_set_frames_canny (NULL without one)
+  const float *depth_f32; // ea_batch_set_frames_ros: the reference side's depth in metres at the working resolution
   void *x, *y, *z, *w;    // the problem's point arrays and its weights (problem dtype), room for `capacity` points
   void *dt;               // the problem's padded DT image and, for an fp64 problem, its float32 mirror (else NULL)
   float *dt32;
@@ -231,8 +232,9 @@ hipError_t launch_edge_scatter(int dtype, const uint8_t *lap, const uint16_t *de
 // launch_edge_count_scan's per frame: the total behind the per-block counts, at f.stride bytes from its neighbour's.
 hipError_t launch_edge_strength_frames(const FramesLaunch &f, int side, uint8_t *gray, uint8_t *lap, hipStream_t s);
 hipError_t launch_threshold_median_frames(const FramesLaunch &f, const uint8_t *lap, int thr, int median, uint8_t *mask, hipStream_t s);
-hipError_t launch_chamfer_frames(const FramesLaunch &f, const uint8_t *mask, int *G, int *scratch, int *dist_fix, unsigned int *minmax,
-                                 hipStream_t s);
+// (dist_f32 given: the exact Euclidean row pass into it, as in launch_chamfer, skipping the frames whose slot has no image)
+hipError_t launch_chamfer_frames(const FramesLaunch &f, const uint8_t *mask, int *G, int *scratch, int *dist_fix, float *dist_f32,
+                                 unsigned int *minmax, hipStream_t s);
 hipError_t launch_dt_store_frames(int dtype, const FramesLaunch &f, const int *dist_fix, const unsigned int *minmax, int normalize,
                                   double lo, double hi, hipStream_t s);
 hipError_t launch_edge_count_scan_frames(const FramesLaunch &f, const uint8_t *lap, int thr, int *block_counts, hipStream_t s);
@@ -244,8 +246,22 @@ hipError_t launch_edge_scatter_frames(int dtype, const FramesLaunch &f, const ui
 // hysteresis converges per frame; the loop ends when every frame has had a quiet launch.  Waits for `s`; *looks: how many
 // looks at the flags it took.
 constexpr int kCannyFrameFlags = 8;
-hipError_t launch_canny_frames(const FramesLaunch &f, int side, int masked, int low, int high, uint8_t *gray, int *mag, uint8_t *dir,
-                               uint8_t *label, uint8_t *edges, uint8_t *inv, int *changed, int *h_flags, int *looks, hipStream_t s);
+// l2_bgr != 0: launch_canny's ROS flavour (no blur / gray, (low, high) already squared).
+hipError_t launch_canny_frames(const FramesLaunch &f, int side, int masked, int low, int high, int l2_bgr, uint8_t *gray, int *mag,
+                               uint8_t *dir, uint8_t *label, uint8_t *edges, uint8_t *inv, int *changed, int *h_flags, int *looks,
+                               hipStream_t s);
+// The ROS chain's own steps for f.n frames (ea_batch_set_frames_ros; the ea_<step>_stack_kernel forms).  The store reads the
+// float distance of the exact transform and skips the frames whose slot has no image; the scatter takes camera, point arrays,
+// capacity and the float depth (depth_f32) from the slot.  The halving steps: H, W = the extent of the step's SOURCE; frame
+// z's source is table[z] (device memory: f.n device pointers, the caller's frames read in place) where a table is given, else
+// src + z * f.stride; its destination dst + z * f.stride.
+hipError_t launch_dt_store_stack(int dtype, const FramesLaunch &f, const float *dist_f32, const unsigned int *minmax, int normalize,
+                                 double lo, double hi, hipStream_t s);
+hipError_t launch_edge_scatter_ros_stack(int dtype, const FramesLaunch &f, const uint8_t *edges, const int *block_offsets, hipStream_t s);
+hipError_t launch_resize_half_bgr8_stack(const FramesLaunch &f, const uint8_t *const *table, const uint8_t *src, int H, int W,
+                                         uint8_t *dst, hipStream_t s);
+hipError_t launch_resize_half_f32_stack(const FramesLaunch &f, const float *const *table, const float *src, int H, int W, float *dst,
+                                        int nan_to_zero, hipStream_t s);
 // ea_kernels.hip: ea_depth_weights_kernel's body for the frames whose slot has power > 0, max_n = the largest capacity among them
 hipError_t launch_depth_weights_frames(int dtype, const FramesLaunch &f, long long max_n, hipStream_t s);
 }  // namespace ea

@@ -191,8 +191,12 @@ __global__ void ea_sobel_mag_batch_kernel(const uint8_t *gray, int H, int W, int
 
 // ROS flavour (ref: src/SolveEA.cpp:46, :102): cv::Canny on the 3-channel image with L2gradient = true -- the channel
 // with the largest dx^2 + dy^2 (the first one on ties) supplies dx, dy; the magnitude is that sum of squares
-__global__ void ea_sobel_mag_l2_bgr_kernel(const uint8_t *__restrict__ bgr, int H, int W, int *__restrict__ mag,
-                                           uint8_t *__restrict__ dir) {
+//
+// The ROS chain follows the pattern of the two chains above: each of its own steps -- this one, the exact row pass, the store
+// from the float distance, the ROS scatter, the two halving steps -- is a __device__ body, ea_<step>_kernel for the
+// per-problem producers, ea_<step>_stack_kernel for frame blockIdx.z of ea_batch_set_frames_ros.
+__device__ __forceinline__ void sobel_mag_l2_bgr_body(const uint8_t *__restrict__ bgr, int H, int W, int *__restrict__ mag,
+                                                      uint8_t *__restrict__ dir) {
   const int u = blockIdx.x * blockDim.x + threadIdx.x, v = blockIdx.y;
   if (u >= W) return;
   const int ym = max(v - 1, 0), yp = min(v + 1, H - 1), xm = max(u - 1, 0), xp = min(u + 1, W - 1);
@@ -213,6 +217,15 @@ __global__ void ea_sobel_mag_l2_bgr_kernel(const uint8_t *__restrict__ bgr, int 
   else if (y > tg22x + (x << 16)) cls = 1;
   else cls = 2 | (((bdx ^ bdy) < 0) ? 4 : 0);
   dir[(size_t)v * W + u] = (uint8_t)cls;
+}
+__global__ void ea_sobel_mag_l2_bgr_kernel(const uint8_t *__restrict__ bgr, int H, int W, int *__restrict__ mag,
+                                           uint8_t *__restrict__ dir) {
+  sobel_mag_l2_bgr_body(bgr, H, W, mag, dir);
+}
+// (the frame at its working resolution: the workspace's `bgr`, or the caller's device frame of a call without halvings)
+__global__ void ea_sobel_mag_l2_bgr_stack_kernel(const FrameSlot *__restrict__ slots, int side, int H, int W, int *mag, uint8_t *dir,
+                                                 size_t stride) {
+  sobel_mag_l2_bgr_body(slots[blockIdx.z].bgr[side], H, W, frame_ptr(mag, stride), frame_ptr(dir, stride));
 }
 
 // non-maximum suppression + double threshold: label 2 = strong, 0 = candidate, 1 = no edge
@@ -533,9 +546,9 @@ __global__ void ea_chamfer_row_frames_kernel(const int *G, const int *carry_dn, 
 // Exact Euclidean variant of the row pass (DIST_MASK_PRECISE): the same per-column distances G, squared cost
 // dx^2 + G(x')^2, search outwards until dx^2 alone reaches the best.  The result is formed like OpenCV's row pass:
 // sqrt((float)dx^2 + (float)dy^2) in float32.  dist_f32 takes the place of the fixed-point chamfer distance.
-__global__ void ea_edt_row_kernel(const int *__restrict__ G, const int *__restrict__ carry_dn,
-                                  const int *__restrict__ carry_up, int H, int W, float *__restrict__ dist_f32,
-                                  unsigned int *__restrict__ minmax) {
+__device__ __forceinline__ void edt_row_body(const int *__restrict__ G, const int *__restrict__ carry_dn,
+                                             const int *__restrict__ carry_up, int H, int W, float *__restrict__ dist_f32,
+                                             unsigned int *__restrict__ minmax) {
   extern __shared__ int s_g[];
   const int y = blockIdx.x;
   const int seg = y / kSegRows, y0 = seg * kSegRows, y1 = min(H, y0 + kSegRows);
@@ -581,6 +594,20 @@ __global__ void ea_edt_row_kernel(const int *__restrict__ G, const int *__restri
   }
   block_minmax_atomic(lmin, lmax, minmax);
 }
+__global__ void ea_edt_row_kernel(const int *__restrict__ G, const int *__restrict__ carry_dn,
+                                  const int *__restrict__ carry_up, int H, int W, float *__restrict__ dist_f32,
+                                  unsigned int *__restrict__ minmax) {
+  edt_row_body(G, carry_dn, carry_up, H, W, dist_f32, minmax);
+}
+// Grid (H, 1, n), the same W * 4 bytes of LDS per workgroup; each frame reduces into its own minmax pair.  A frame whose slot
+// has no image -- a current frame without any edge -- is skipped by the whole workgroup: no column of it has a feature, so
+// every lane's search would walk the full row (W / 2 trips per pixel) for a distance nobody stores.
+__global__ void ea_edt_row_stack_kernel(const FrameSlot *__restrict__ slots, const int *G, const int *carry_dn, const int *carry_up,
+                                        int H, int W, float *dist_f32, unsigned int *minmax, size_t stride) {
+  if (!slots[blockIdx.z].dt) return;
+  edt_row_body(frame_ptr(G, stride), frame_ptr(carry_dn, stride), frame_ptr(carry_up, stride), H, W, frame_ptr(dist_f32, stride),
+               frame_ptr(minmax, stride));
+}
 
 // dist (16.16 fixed) -> float32 [-> min-max normalised] -> padded image of the problem dtype
 template <typename T>
@@ -616,6 +643,17 @@ __global__ void ea_dt_store_frames_kernel(const FrameSlot *__restrict__ slots, c
                                           const unsigned int *minmax, int normalize, double lo, double hi, size_t stride) {
   const FrameSlot &sl = slots[blockIdx.z];
   dt_store_body<T>(frame_ptr(dist_fix, stride), nullptr, H, W, frame_ptr(minmax, stride), normalize, lo, hi,
+                   static_cast<T *>(sl.dt), sl.pitch, nullptr, sl.dt32);
+}
+
+// (the exact transform's float distance, normalised to (0, 255) by the ROS call; a frame without an image -- a current frame
+// without any edge, which keeps the image it had -- returns at once)
+template <typename T>
+__global__ void ea_dt_store_stack_kernel(const FrameSlot *__restrict__ slots, const float *dist_f32, int H, int W,
+                                         const unsigned int *minmax, int normalize, double lo, double hi, size_t stride) {
+  const FrameSlot &sl = slots[blockIdx.z];
+  if (!sl.dt) return;
+  dt_store_body<T>(nullptr, frame_ptr(dist_f32, stride), H, W, frame_ptr(minmax, stride), normalize, lo, hi,
                    static_cast<T *>(sl.dt), sl.pitch, nullptr, sl.dt32);
 }
 
@@ -735,9 +773,10 @@ __global__ void ea_edge_scatter_frames_kernel(const FrameSlot *__restrict__ slot
 // ROS flavour of the scatter (ref: src/SolveEA.cpp:61-78): every edge pixel, float depth in metres, Z == 0 -> 1.0,
 // X = Z * (xx - cx) / fx
 template <typename T>
-__global__ void ea_edge_scatter_ros_kernel(const uint8_t *__restrict__ edges, const float *__restrict__ depth, int H, int W,
-                                           const int *__restrict__ block_offsets, double fx, double fy, double cx, double cy,
-                                           T *__restrict__ X, T *__restrict__ Y, T *__restrict__ Z, int capacity) {
+__device__ __forceinline__ void edge_scatter_ros_body(const uint8_t *__restrict__ edges, const float *__restrict__ depth, int H, int W,
+                                                      const int *__restrict__ block_offsets, double fx, double fy, double cx,
+                                                      double cy, T *__restrict__ X, T *__restrict__ Y, T *__restrict__ Z,
+                                                      int capacity) {
   __shared__ int s_cnt[kScanBlock / 64];
   const int npix = H * W;
   const int i = blockIdx.x * kScanBlock + threadIdx.x;
@@ -758,6 +797,20 @@ __global__ void ea_edge_scatter_ros_kernel(const uint8_t *__restrict__ edges, co
   const double y = __dmul_rn(z, (double)v - cy) / fy;
   X[off] = (T)x; Y[off] = (T)y; Z[off] = (T)z;
 }
+template <typename T>
+__global__ void ea_edge_scatter_ros_kernel(const uint8_t *__restrict__ edges, const float *__restrict__ depth, int H, int W,
+                                           const int *__restrict__ block_offsets, double fx, double fy, double cx, double cy,
+                                           T *__restrict__ X, T *__restrict__ Y, T *__restrict__ Z, int capacity) {
+  edge_scatter_ros_body<T>(edges, depth, H, W, block_offsets, fx, fy, cx, cy, X, Y, Z, capacity);
+}
+// (a frame without points has capacity 0: the body's capacity guard returns before any of its NULL arrays is touched)
+template <typename T>
+__global__ void ea_edge_scatter_ros_stack_kernel(const FrameSlot *__restrict__ slots, const uint8_t *edges, int H, int W,
+                                                 const int *block_offsets, size_t stride) {
+  const FrameSlot &sl = slots[blockIdx.z];
+  edge_scatter_ros_body<T>(frame_ptr(edges, stride), sl.depth_f32, H, W, frame_ptr(block_offsets, stride), sl.fx, sl.fy, sl.cx,
+                           sl.cy, static_cast<T *>(sl.x), static_cast<T *>(sl.y), static_cast<T *>(sl.z), sl.capacity);
+}
 
 // ---- half-resolution level: cv::resize(src, dst, cv::Size(), 0.5, 0.5) as the ROS callbacks apply it to the bgr8 colour
 // frame and to the float depth frame after NaN -> 0 (ref: src/ea.cpp:38, :56-62).  At an exact factor of two OpenCV's
@@ -766,7 +819,7 @@ __global__ void ea_edge_scatter_ros_kernel(const uint8_t *__restrict__ edges, co
 // path for CV_32F (ResizeAreaFastVec_SIMD_32f: the two pixels of each source row are added first, then the rows) -- what
 // an x86 or NEON build executes for every pixel of a width that is a multiple of four; the scalar generic loop would
 // sum ((a + b) + c) + d, which differs in the last bit on some pixels.
-__global__ void ea_resize_half_bgr8_kernel(const uint8_t *__restrict__ src, int H2, int W2, uint8_t *__restrict__ dst) {
+__device__ __forceinline__ void resize_half_bgr8_body(const uint8_t *__restrict__ src, int H2, int W2, uint8_t *__restrict__ dst) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x;  // destination column x channel
   const int y = blockIdx.y;
   if (x >= W2 * 3) return;
@@ -776,9 +829,18 @@ __global__ void ea_resize_half_bgr8_kernel(const uint8_t *__restrict__ src, int 
   const uint8_t *r1 = r0 + sp;
   dst[(size_t)y * W2 * 3 + x] = (uint8_t)(((int)r0[0] + (int)r0[3] + (int)r1[0] + (int)r1[3] + 2) >> 2);
 }
+__global__ void ea_resize_half_bgr8_kernel(const uint8_t *__restrict__ src, int H2, int W2, uint8_t *__restrict__ dst) {
+  resize_half_bgr8_body(src, H2, W2, dst);
+}
+// One halving step of every frame of a batched call.  The source of frame z: table[z] where a table is given -- the caller's
+// full-size device frames, read in place by the first step -- else src + z * stride; the destination: dst + z * stride.
+__global__ void ea_resize_half_bgr8_stack_kernel(const uint8_t *const *__restrict__ table, const uint8_t *src, int H2, int W2,
+                                                 uint8_t *dst, size_t stride) {
+  resize_half_bgr8_body(table ? table[blockIdx.z] : frame_ptr(src, stride), H2, W2, frame_ptr(dst, stride));
+}
 
-__global__ void ea_resize_half_f32_kernel(const float *__restrict__ src, int H2, int W2, float *__restrict__ dst,
-                                          int nan_to_zero) {
+__device__ __forceinline__ void resize_half_f32_body(const float *__restrict__ src, int H2, int W2, float *__restrict__ dst,
+                                                     int nan_to_zero) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x;
   const int y = blockIdx.y;
   if (x >= W2) return;
@@ -790,6 +852,14 @@ __global__ void ea_resize_half_f32_kernel(const float *__restrict__ src, int H2,
     a = (a != a) ? 0.0f : a; b = (b != b) ? 0.0f : b; c = (c != c) ? 0.0f : c; d = (d != d) ? 0.0f : d;
   }
   dst[(size_t)y * W2 + x] = __fmul_rn(__fadd_rn(__fadd_rn(a, b), __fadd_rn(c, d)), 0.25f);
+}
+__global__ void ea_resize_half_f32_kernel(const float *__restrict__ src, int H2, int W2, float *__restrict__ dst,
+                                          int nan_to_zero) {
+  resize_half_f32_body(src, H2, W2, dst, nan_to_zero);
+}
+__global__ void ea_resize_half_f32_stack_kernel(const float *const *__restrict__ table, const float *src, int H2, int W2, float *dst,
+                                                int nan_to_zero, size_t stride) {
+  resize_half_f32_body(table ? table[blockIdx.z] : frame_ptr(src, stride), H2, W2, frame_ptr(dst, stride), nan_to_zero);
 }
 
 __global__ void ea_nan_to_zero_kernel(float *__restrict__ img, size_t n) {
@@ -966,8 +1036,8 @@ hipError_t launch_threshold_median_frames(const FramesLaunch &f, const uint8_t *
   return hipGetLastError();
 }
 
-hipError_t launch_chamfer_frames(const FramesLaunch &f, const uint8_t *mask, int *G, int *scratch, int *dist_fix, unsigned int *minmax,
-                                 hipStream_t s) {
+hipError_t launch_chamfer_frames(const FramesLaunch &f, const uint8_t *mask, int *G, int *scratch, int *dist_fix, float *dist_f32,
+                                 unsigned int *minmax, hipStream_t s) {
   if (!frames_ok(f)) return hipErrorInvalidValue;
   const int H = f.H, W = f.W, S = (H + kSegRows - 1) / kSegRows;
   int *end_dn = scratch, *end_up = scratch + (size_t)S * W, *carry_dn = scratch + 2 * (size_t)S * W,
@@ -977,8 +1047,12 @@ hipError_t launch_chamfer_frames(const FramesLaunch &f, const uint8_t *mask, int
   hipLaunchKernelGGL(ea_column_carry_frames_kernel, dim3((W + 63) / 64, 1, f.n), dim3(64), 0, s, end_dn, end_up, H, W, S, carry_dn,
                      carry_up, f.stride);
   const int row_threads = std::min(1024, std::max(256, ((W + 63) / 64) * 64));
-  hipLaunchKernelGGL(ea_chamfer_row_frames_kernel, dim3(H, 1, f.n), dim3(row_threads), (size_t)W * sizeof(int), s, G, carry_dn,
-                     carry_up, H, W, dist_fix, minmax, f.stride);
+  if (dist_f32)
+    hipLaunchKernelGGL(ea_edt_row_stack_kernel, dim3(H, 1, f.n), dim3(row_threads), (size_t)W * sizeof(int), s, f.slots, G, carry_dn,
+                       carry_up, H, W, dist_f32, minmax, f.stride);
+  else
+    hipLaunchKernelGGL(ea_chamfer_row_frames_kernel, dim3(H, 1, f.n), dim3(row_threads), (size_t)W * sizeof(int), s, G, carry_dn,
+                       carry_up, H, W, dist_fix, minmax, f.stride);
   return hipGetLastError();
 }
 
@@ -993,14 +1067,30 @@ hipError_t launch_dt_store_frames(int dtype, const FramesLaunch &f, const int *d
   return hipGetLastError();
 }
 
-hipError_t launch_canny_frames(const FramesLaunch &f, int side, int masked, int low, int high, uint8_t *gray, int *mag, uint8_t *dir,
-                               uint8_t *label, uint8_t *edges, uint8_t *inv, int *changed, int *h_flags, int *looks, hipStream_t s) {
+hipError_t launch_dt_store_stack(int dtype, const FramesLaunch &f, const float *dist_f32, const unsigned int *minmax, int normalize,
+                                 double lo, double hi, hipStream_t s) {
+  if (!frames_ok(f)) return hipErrorInvalidValue;
+  dim3 block(256), grid((f.W + 2 * kImagePad + 255) / 256, f.H + 2 * kImagePad, f.n);
+  if (dtype == 1)
+    hipLaunchKernelGGL((ea_dt_store_stack_kernel<float>), grid, block, 0, s, f.slots, dist_f32, f.H, f.W, minmax, normalize, lo, hi, f.stride);
+  else
+    hipLaunchKernelGGL((ea_dt_store_stack_kernel<double>), grid, block, 0, s, f.slots, dist_f32, f.H, f.W, minmax, normalize, lo, hi, f.stride);
+  return hipGetLastError();
+}
+
+hipError_t launch_canny_frames(const FramesLaunch &f, int side, int masked, int low, int high, int l2_bgr, uint8_t *gray, int *mag,
+                               uint8_t *dir, uint8_t *label, uint8_t *edges, uint8_t *inv, int *changed, int *h_flags, int *looks,
+                               hipStream_t s) {
   static_assert(kCannyFrameFlags == kHystBatch, "a look brings back one flag per launch of a hysteresis batch");
   if (!frames_ok(f) || !h_flags) return hipErrorInvalidValue;
   const int H = f.H, W = f.W;
   dim3 block(256), grid((W + 255) / 256, H, f.n);
-  hipLaunchKernelGGL(ea_boxblur_gray_batch_kernel, grid, block, 0, s, f.slots, side, H, W, gray, f.stride);
-  hipLaunchKernelGGL(ea_sobel_mag_batch_kernel, grid, block, 0, s, gray, H, W, mag, dir, f.stride);
+  if (l2_bgr) {
+    hipLaunchKernelGGL(ea_sobel_mag_l2_bgr_stack_kernel, grid, block, 0, s, f.slots, side, H, W, mag, dir, f.stride);
+  } else {
+    hipLaunchKernelGGL(ea_boxblur_gray_batch_kernel, grid, block, 0, s, f.slots, side, H, W, gray, f.stride);
+    hipLaunchKernelGGL(ea_sobel_mag_batch_kernel, grid, block, 0, s, gray, H, W, mag, dir, f.stride);
+  }
   hipLaunchKernelGGL(ea_canny_nms_batch_kernel, grid, block, 0, s, mag, dir, H, W, low, high, label, changed, 2 * kHystBatch, f.stride);
   // hysteresis: launch_canny's batches of eight launches for all frames at once; the flags of a look are those of its half of
   // every frame's 16 (ea_canny_hysteresis_batch_kernel), and one strided copy brings the n x 8 of them back
@@ -1052,6 +1142,37 @@ hipError_t launch_edge_scatter_frames(int dtype, const FramesLaunch &f, const ui
   else
     hipLaunchKernelGGL((ea_edge_scatter_frames_kernel<double>), dim3(nblocks, 1, f.n), dim3(kScanBlock), 0, s, f.slots, lap, f.H, f.W,
                        thr, block_offsets, z_scaling, f.stride);
+  return hipGetLastError();
+}
+
+hipError_t launch_edge_scatter_ros_stack(int dtype, const FramesLaunch &f, const uint8_t *edges, const int *block_offsets, hipStream_t s) {
+  if (!frames_ok(f)) return hipErrorInvalidValue;
+  const int npix = f.H * f.W, nblocks = (npix + kScanBlock - 1) / kScanBlock;
+  if (dtype == 1)
+    hipLaunchKernelGGL((ea_edge_scatter_ros_stack_kernel<float>), dim3(nblocks, 1, f.n), dim3(kScanBlock), 0, s, f.slots, edges, f.H, f.W,
+                       block_offsets, f.stride);
+  else
+    hipLaunchKernelGGL((ea_edge_scatter_ros_stack_kernel<double>), dim3(nblocks, 1, f.n), dim3(kScanBlock), 0, s, f.slots, edges, f.H, f.W,
+                       block_offsets, f.stride);
+  return hipGetLastError();
+}
+
+// (H, W: the SOURCE extent of this step, both even; f supplies the frame count and the stride only)
+hipError_t launch_resize_half_bgr8_stack(const FramesLaunch &f, const uint8_t *const *table, const uint8_t *src, int H, int W,
+                                         uint8_t *dst, hipStream_t s) {
+  if (!frames_ok(f) || H < 2 || W < 2 || (H & 1) || (W & 1) || (!table && !src) || !dst) return hipErrorInvalidValue;
+  const int H2 = H / 2, W2 = W / 2;
+  hipLaunchKernelGGL(ea_resize_half_bgr8_stack_kernel, dim3((W2 * 3 + 255) / 256, H2, f.n), dim3(256), 0, s, table, src, H2, W2, dst,
+                     f.stride);
+  return hipGetLastError();
+}
+
+hipError_t launch_resize_half_f32_stack(const FramesLaunch &f, const float *const *table, const float *src, int H, int W, float *dst,
+                                        int nan_to_zero, hipStream_t s) {
+  if (!frames_ok(f) || H < 2 || W < 2 || (H & 1) || (W & 1) || (!table && !src) || !dst) return hipErrorInvalidValue;
+  const int H2 = H / 2, W2 = W / 2;
+  hipLaunchKernelGGL(ea_resize_half_f32_stack_kernel, dim3((W2 + 255) / 256, H2, f.n), dim3(256), 0, s, table, src, H2, W2, dst,
+                     nan_to_zero, f.stride);
   return hipGetLastError();
 }
 

@@ -770,6 +770,52 @@ int ea_problem_set_ref_frame_ros_scaled(ea_problem *p, const uint8_t *bgr, const
                                         int full_width, int halvings, double threshold1, double threshold2);
 int ea_problem_set_now_frame_ros_scaled(ea_problem *p, const uint8_t *bgr, int full_height, int full_width, int halvings,
                                         double threshold1, double threshold2);
+/* The two ROS producers above for EVERY problem of a batch in one launch sequence: the third sibling of ea_batch_set_frames
+ * and ea_batch_set_frames_canny, in the shape the node runs -- N = ea_batch_count(b) full-resolution frame pairs of equal
+ * extent, halved `halvings` times on the device, the frame a grid dimension of each step.  For halvings = 0 and one look at
+ * the hysteresis flags per side: 31 launches (32 with depth weighting), 3 more per halving, and five waits (a look per side,
+ * the counts of each side, the end) for the whole batch, where the per-problem calls wait six times per PAIR.
+ *
+ * The pointer arrays, the two sides and what a NULL side means are ea_batch_set_frames'.  ref_depth: full_height x full_width
+ * float32 in metres.
+ *
+ * After the call every problem p_i is in the state that
+ *     ea_problem_set_ref_frame_ros_scaled(p_i, ref_bgr[i], ref_depth[i], full_height, full_width, halvings, threshold1, threshold2);
+ *     ea_problem_set_now_frame_ros_scaled(p_i, now_bgr[i], full_height, full_width, halvings, threshold1, threshold2);
+ * leave it in, in that order, bit for bit: the same points in the same order (Z == 0 -> 1.0; NaN and negative depths kept),
+ * the same padded DT image and float32 mirror (exact), the same depth weights where the problem has
+ * ea_problem_set_depth_weighting, each problem's own camera, the version bumped, its terms untouched.  A reference frame
+ * without edges gives a problem with zero points.  As with the other two batch calls the frames pass through the batch's
+ * workspace, the same one -- here each frame's workspace at the working extent and, behind it, the stage of the halving: at
+ * most 9.19 bytes per full-size pixel from host frames, 2.19 from device frames, none without halvings -- and what a problem's
+ * own producer workspace holds afterwards is unspecified.
+ *
+ * A current frame without any edge: the per-problem producer returns EA_ERR_STATE for it and leaves the problem's image,
+ * extent, exactness mark and version alone.  The batched call completes the reference side of every problem and the current
+ * side of every frame that has an edge, leaves each edge-less frame's problem exactly as the per-problem call would (its image
+ * is not even re-allocated: one of another extent survives), and then returns EA_ERR_STATE; ea_last_error() names the first
+ * such frame's index and how many there were, ea_batch_get_info("frames_without_edges") is their number in the last ROS call
+ * (0 after a clean one and after the other two batch calls).  "frames_hysteresis_rounds": as for ea_batch_set_frames_canny.
+ *
+ * EA_ERR_INVALID_ARG, checked before a device or a problem is touched (batch and problems unchanged): everything
+ * ea_batch_set_frames checks, with its extent limits applied to the working extent (full >> halvings, at least 3 x 3; with
+ * current frames no wider than 16384) and the full extent within 3..32768 and 2^30 - 1 pixels; halvings outside 0..8 or a
+ * full extent not divisible by 2^halvings; a NaN threshold; for the _device form a depth frame that is not device memory of
+ * the batch's device or not 4-byte aligned.  EA_ERR_ALLOC and a failure past the checks: as for ea_batch_set_frames.
+ *
+ * ea_batch_set_frames_ros: host pointers.  ea_batch_set_frames_ros_device: every entry a device pointer on the batch's device,
+ * read in place (by the first halving step, or by the producers themselves without halvings), complete when the call is made
+ * (see ea_batch_set_frames_device). */
+typedef struct {
+  int full_height, full_width;   /* of every frame as handed in */
+  int halvings;                  /* 0..8; the producers work at full >> halvings */
+  double threshold1, threshold2; /* cv::Canny(rgb, 150, 100, 3, true): (150, 100) */
+} ea_ros_frame_params;
+void ea_default_ros_frame_params(ea_ros_frame_params *prm, int full_height, int full_width); /* halvings 0 */
+int ea_batch_set_frames_ros(ea_batch *b, const uint8_t *const *ref_bgr, const float *const *ref_depth,
+                            const uint8_t *const *now_bgr, const ea_ros_frame_params *prm);
+int ea_batch_set_frames_ros_device(ea_batch *b, const uint8_t *const *ref_bgr, const float *const *ref_depth,
+                                   const uint8_t *const *now_bgr, const ea_ros_frame_params *prm);
 /* the half-resolution step by itself, host in / host out: kind 0 = bgr8 (height x width x 3 bytes), 1 = float32 with
  * NaN -> 0 first, 2 = float32 as is; dst = (height / 2) x (width / 2); height and width even */
 int ea_resize_half(int device, int kind, const void *src, int height, int width, void *dst);

@@ -1,0 +1,551 @@
+"""ea_batch_set_frames_ros / Batch.set_frames_ros: the ROS producers (SolveEA::setRefFrame / setNowFrame with the node's
+halvings) for every problem of a batch in one launch sequence, the frame as blockIdx.z of each step.  The reference is always
+the per-problem producers (Problem.set_ref_frame_ros + Problem.set_now_frame_ros with the same halvings) on fresh problems,
+compared with np.array_equal on num_points, get_points() (through an integer view: NaN depths give NaN points), get_weights()
+and get_dt(): bit equality, no tolerance.  oracle/preprocess_np.py is a second check on one bundled pair.
+
+Working shapes are the smallest at which the frame indexing can go wrong: (3, 3) all border; (37, 70) two hysteresis tiles of
+62 across, two 32-row column segments, two full 1024-pixel scan blocks and a partial one; (64, 257) past a 256-lane row block.
+Each runs without halvings and from full frames of (12, 12) halved twice, (74, 140) halved once, (256, 1028) halved twice.
+Frames of one call differ in kind, so that a frame reading its neighbour's workspace, stage, flags, minmax pair, counts or slot
+cannot go unnoticed.  `dot` is uniform 90 with a 250 block at [:2, :2] of the working frame: 3 edge pixels in one corner and a
+DT maximum of 255 in the opposite one, so the exact transform's row search and both column carries span the whole frame.
+
+A current frame without any edge (`flat`) has no exact distance transform: the per-problem producer raises EA_ERR_STATE and
+leaves the problem alone, and the batched call must do that to the same problems -- every problem starts with an image of
+another extent, which has to survive -- while completing all the others.
+
+`_chain` is a 9 x 700 frame whose weak edge (a step of 30: L2 magnitude 120, between the thresholds 100 and 150) crosses 12
+hysteresis tiles from a seed in the last one (the step rises to 60 over the last columns: 18 strong pixels), which takes more
+than the 8 launches of one look."""
+import os
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+G = os.path.join(ROOT, "tests", "golden", "rgbd")
+K = (525.0, 525.0, 319.5, 239.5)
+# (working extent, halvings) -> the full extent is the working extent << halvings
+CASES = (((3, 3), 0), ((37, 70), 0), ((64, 257), 0), ((3, 3), 2), ((37, 70), 1), ((64, 257), 2))
+KINDS = ("noise", "lines", "dot", "noise")
+CHAIN_H, CHAIN_W = 9, 700
+
+
+def _chain(H=CHAIN_H, W=CHAIN_W, ramp=True):
+    col = np.arange(W)
+    amp = np.clip(30 + 2 * (col - (W - 1 - 15 - 6)), 30, 60) if ramp else np.full(W, 30)
+    bgr = np.full((H, W, 3), 100, np.uint8)
+    bgr[4:] = (100 + amp).astype(np.uint8)[None, :, None]
+    return bgr
+
+
+def _depth(H, W, rng):
+    """metres, with zeros (-> 1.0), negatives and NaN (kept without halvings, -> 0 by the first halving step) sprinkled in"""
+    d = (rng.random((H, W)) * 4.0 + 0.4).astype(np.float32)
+    r = rng.random((H, W))
+    d[r < 0.10] = 0.0
+    d[(r >= 0.10) & (r < 0.15)] = -1.5
+    d[(r >= 0.15) & (r < 0.20)] = np.nan
+    return d
+
+
+def _frame(kind, H, W, halvings, rng):
+    """-> (bgr, depth float32) at the full extent (H << halvings, W << halvings).  dot, flat, chain and lines are defined at
+    the working extent and enlarged by pixel repetition, which the 2 x 2 mean undoes exactly.  Noise is made one halving above
+    the working extent (and enlarged from there): the last halving step averages four different values, so its rounding
+    matters, and the frame keeps the contrast that gives it edges (independent noise averaged 16 or 64 times over has none).
+    The depth is independent per full-size pixel."""
+    s = 1 << halvings
+    depth = _depth(H * s, W * s, rng)
+
+    def enlarged(img, by):
+        return np.ascontiguousarray(np.repeat(np.repeat(img, by, axis=0), by, axis=1))
+
+    if kind == "chain":
+        return enlarged(_chain(H, W), s), depth
+    if kind in ("dot", "flat"):
+        small = np.full((H, W, 3), 90, np.uint8)
+        if kind == "dot":
+            small[:2, :2] = 250
+        return enlarged(small, s), depth
+    if kind == "lines":
+        from edge_alignment_amd import synth
+        small = np.full((H, W, 3), 128, np.uint8)
+        if min(H, W) >= 24:
+            p0, p1 = synth.random_segments(H, W, 4, rng, min_len=6.0, max_len=0.6 * min(H, W))
+            mask = synth.rasterize(H, W, p0, p1)
+        else:
+            mask = np.eye(H, W, dtype=bool)
+        small[mask] = (255, 255, 20)
+        return enlarged(small, s), depth
+    if halvings == 0:
+        return rng.integers(0, 256, (H, W, 3)).astype(np.uint8), depth
+    return enlarged(rng.integers(0, 256, (2 * H, 2 * W, 3)).astype(np.uint8), s // 2), depth
+
+
+def _pairs(H, W, halvings, n, seed, ref_kinds=KINDS, now_kinds=None):
+    now_kinds = now_kinds or ref_kinds[1:] + ref_kinds[:1]
+    rng = np.random.default_rng(seed)
+    ref = [_frame(ref_kinds[i % len(ref_kinds)], H, W, halvings, rng) for i in range(n)]
+    now = [_frame(now_kinds[i % len(now_kinds)], H, W, halvings, rng)[0] for i in range(n)]
+    return [r[0] for r in ref], [r[1] for r in ref], now
+
+
+def _camera(i, H, W):
+    """a camera of its own per problem"""
+    return (0.9 * W + 7.0 * i, 0.8 * W + 3.0 * i, 0.5 * W - 0.5 + 0.25 * i, 0.5 * H - 0.5 - 0.125 * i)
+
+
+def _previous_image(i):
+    """the image every problem starts with: an extent no call of this file uses, its own values per problem"""
+    return np.arange(6 * 5, dtype=np.float64).reshape(6, 5) * 0.25 + i   # Grid2D view: a 5 x 6 image
+
+
+def _problems(hip, n, H, W, dtype, weighting=None):
+    probs = [hip.Problem(*_camera(i, H, W), dtype=dtype) for i in range(n)]
+    for i, P in enumerate(probs):
+        if weighting and weighting[i % len(weighting)]:
+            P.set_depth_weighting(*weighting[i % len(weighting)])
+        P.set_dt_grid(_previous_image(i))
+    return probs
+
+
+def _state(P, points=True, image=True):
+    st = {}
+    if points:
+        st.update(n=P.num_points, points=P.get_points(), weights=P.get_weights())
+    if image:
+        st.update(dt=P.get_dt())
+    return st
+
+
+def _same_bits(a, b):
+    a, b = np.ascontiguousarray(a, np.float64), np.ascontiguousarray(b, np.float64)
+    return a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64))
+
+
+def _assert_same(got, want, where):
+    assert sorted(got) == sorted(want), where
+    for key in want:
+        a, b = got[key], want[key]
+        if key == "n":
+            assert a == b, (where, key, a, b)
+        elif a is None or b is None:
+            assert a is None and b is None, (where, key)
+        else:
+            assert _same_bits(a, b), (where, key, a.shape, b.shape)
+
+
+def _per_problem(hip, probs, ref, dep, now, halvings=0, **kw):
+    """the per-problem producers -> the indices whose current frame they refused with EA_ERR_STATE"""
+    bare = []
+    for i, P in enumerate(probs):
+        if ref is not None:
+            P.set_ref_frame_ros(ref[i], dep[i], halvings=halvings, **kw)
+        if now is not None:
+            try:
+                P.set_now_frame_ros(now[i], halvings=halvings, **kw)
+            except hip.EAError as e:
+                assert e.code == hip.EA_ERR_STATE, e
+                bare.append(i)
+    return bare
+
+
+def _batched(hip, batch, ref, dep, now, bare, **kw):
+    """the batched call: it raises EA_ERR_STATE iff some per-problem call did, and counts the same frames"""
+    if bare:
+        with pytest.raises(hip.EAError) as ei:
+            batch.set_frames_ros(ref, dep, now, **kw)
+        assert ei.value.code == hip.EA_ERR_STATE, ei.value
+        assert "index %d" % bare[0] in str(ei.value) and "%d of" % len(bare) in str(ei.value), ei.value
+    else:
+        batch.set_frames_ros(ref, dep, now, **kw)
+    assert batch.info("frames_without_edges") == len(bare)
+
+
+def _assert_same_eval(a, b, where):
+    """(through the integer view: points with a NaN depth give a NaN cost)"""
+    for key in ("cost", "JtJ", "Jtr"):
+        assert _same_bits(a[key], b[key]), (where, key)
+    assert np.array_equal(a["n_invalid"], b["n_invalid"]), where
+
+
+def _close(*things):
+    for t in things:
+        for x in (t if isinstance(t, (list, tuple)) else [t]):
+            x.close()
+
+
+def _compare_call(hip, H, W, n, dtype, ref, dep, now, weighting=None, where=None, rounds=None, bare_out=None, **kw):
+    """one set_frames_ros call on fresh problems against the per-problem producers on fresh problems -> the batched states"""
+    want_p = _problems(hip, n, H, W, dtype, weighting)
+    got_p = _problems(hip, n, H, W, dtype, weighting)
+    batch = hip.Batch(got_p)
+    try:
+        bare = _per_problem(hip, want_p, ref, dep, now, **kw)
+        _batched(hip, batch, ref, dep, now, bare, **kw)
+        if rounds is not None:
+            rounds.append(batch.info("frames_hysteresis_rounds"))
+        if bare_out is not None:
+            bare_out.extend(bare)
+        states = []
+        for i in range(n):
+            st = _state(got_p[i], points=ref is not None)
+            _assert_same(st, _state(want_p[i], points=ref is not None), (where, H, W, n, i))
+            states.append(st)
+        return states
+    finally:
+        _close(batch, want_p, got_p)
+
+
+@pytest.mark.parametrize("dtype_name", ["EA_F64", "EA_F32"])
+@pytest.mark.parametrize("n", [1, 2, 5])
+@pytest.mark.parametrize("case", CASES, ids=lambda c: "%dx%d_h%d" % (c[0] + (c[1],)))
+def test_shapes_halvings_counts_and_dtypes(hip, case, n, dtype_name):
+    (H, W), halvings = case
+    ref, dep, now = _pairs(H, W, halvings, n, seed=100 * H + 10 * halvings + n)
+    rounds, bare = [], []
+    weighting = [None, (2.0, 1), None, (3.5, 3)]
+    states = _compare_call(hip, H, W, n, getattr(hip, dtype_name), ref, dep, now, weighting=weighting, where=dtype_name,
+                           rounds=rounds, bare_out=bare, halvings=halvings)
+    assert rounds[0] >= 2                                    # one look per side at the least
+    if min(H, W) > 3:
+        assert bare == []                                    # every kind here has an edge
+        for i, st in enumerate(states):
+            assert st["dt"].shape == (H, W) and st["dt"].min() == 0.0 and abs(st["dt"].max() - 255.0) < 1e-3, i   # (float32 scale, shift)
+        assert states[0]["n"] > 0.05 * H * W                 # dense noise: thinned edges all over
+        assert np.isnan(states[0]["points"]).any() == (halvings == 0)   # NaN depths: kept as they are, or zeroed by the halving
+        if halvings == 0:                                    # (a 2 x 2 mean of such depths is hardly ever 0)
+            assert (states[0]["points"][:, 2] == 1.0).any()  # Z == 0 -> 1.0
+            assert (states[0]["points"][:, 2] < 0).any()
+    if n >= 2:
+        assert states[0]["weights"] is None
+        if min(H, W) > 3:
+            assert states[1]["n"] > 0 and states[1]["weights"] is not None
+        assert 1 not in bare and states[1]["dt"].shape == (H, W)   # the dot as a current frame (problem 1)
+        if min(H, W) > 3:
+            assert states[1]["dt"][-1, -1] == states[1]["dt"].max()   # ... its maximum in the corner opposite the dot
+    if n == 5:
+        print("points of the dot reference frame:", states[2]["n"])
+        assert states[2]["n"] == 3                           # the dot as a reference frame: its three edge pixels
+
+
+def test_a_frame_does_not_depend_on_its_neighbours_or_its_position(hip):
+    H, W, n, halvings = 37, 70, 5, 1
+    ref, dep, now = _pairs(H, W, halvings, n, seed=7)
+    first = _compare_call(hip, H, W, n, hip.EA_F64, ref, dep, now, where="order 0", halvings=halvings)
+    for perm in ([4, 2, 0, 3, 1], [1, 0, 2, 4, 3]):
+        got = _compare_call(hip, H, W, n, hip.EA_F64, [ref[k] for k in perm], [dep[k] for k in perm], [now[k] for k in perm],
+                            where=("perm", perm), halvings=halvings)
+        for i, k in enumerate(perm):
+            assert np.array_equal(got[i]["dt"], first[k]["dt"]), (perm, i)
+            assert got[i]["n"] == first[k]["n"], (perm, i)
+            assert _same_bits(got[i]["points"][:, 2], first[k]["points"][:, 2]), (perm, i)
+
+
+@pytest.mark.parametrize("dtype_name", ["EA_F64", "EA_F32"])
+@pytest.mark.parametrize("case", CASES[1:3] + CASES[4:], ids=lambda c: "%dx%d_h%d" % (c[0] + (c[1],)))
+def test_current_frames_without_an_edge_are_left_alone_and_reported(hip, case, dtype_name):
+    """flat current frames at positions 1 and 3 of five (and, in a second call on the same batch, at every position): the
+    call raises EA_ERR_STATE exactly when a per-problem call does, reports their number, completes every other frame and
+    both sides' bookkeeping, and leaves the edge-less problems with the 5 x 6 image they had -- so that Batch.eval, which
+    rebuilds its descriptors from the problems' versions, gives what it gives after the per-problem producers"""
+    (H, W), halvings = case
+    n, dtype = 5, getattr(hip, dtype_name)
+    ref, dep, now = _pairs(H, W, halvings, n, seed=31 + H, ref_kinds=("noise", "lines", "noise", "noise", "lines"),
+                           now_kinds=("noise", "flat", "lines", "flat", "dot"))
+    weighting = [(2.0, 1), None]
+    want_p, got_p = _problems(hip, n, H, W, dtype, weighting), _problems(hip, n, H, W, dtype, weighting)
+    want_b, got_b = hip.Batch(want_p), hip.Batch(got_p)
+    q, t = np.tile([1.0, 0, 0, 0], (n, 1)), np.zeros((n, 3))
+    try:
+        bare = _per_problem(hip, want_p, ref, dep, now, halvings=halvings)
+        assert bare == [1, 3]
+        _batched(hip, got_b, ref, dep, now, bare, halvings=halvings)
+        for i in range(n):
+            _assert_same(_state(got_p[i]), _state(want_p[i]), ("some flat", i))
+            assert got_p[i].get_dt().shape == ((5, 6) if i in bare else (H, W))
+        assert np.array_equal(got_p[1].get_dt(), _previous_image(1).T)
+        ev = got_b.eval(q, t)
+        _assert_same_eval(ev, want_b.eval(q, t), "eval")
+        # a clean call on the same batch reports 0; then every current frame flat, one side only: nothing changes but the count
+        clean = [now[0], now[2], now[4], now[0], now[2]]
+        assert _per_problem(hip, want_p, None, None, clean, halvings=halvings) == []
+        _batched(hip, got_b, None, None, clean, [], halvings=halvings)
+        flat = [now[1]] * n
+        assert _per_problem(hip, want_p, None, None, flat, halvings=halvings) == list(range(n))
+        _batched(hip, got_b, None, None, flat, list(range(n)), halvings=halvings)
+        for i in range(n):
+            _assert_same(_state(got_p[i]), _state(want_p[i]), ("all flat", i))
+        ev = got_b.eval(q, t)
+        _assert_same_eval(ev, want_b.eval(q, t), "eval")
+    finally:
+        _close(want_b, got_b, want_p, got_p)
+
+
+# ---- the hysteresis across several looks ----
+
+def test_the_chain_frame_needs_a_second_look_on_the_per_problem_producer(hip):
+    """the precondition of the test below: the frame is what its description says"""
+    P = hip.Problem(*_camera(0, CHAIN_H, CHAIN_W))
+    try:
+        out = P.set_now_frame_ros(_chain(), debug=True)
+        assert int((out["edges"] > 0).sum()) == CHAIN_W and (out["edges"] > 0).any(axis=0).all()
+        with pytest.raises(hip.EAError):
+            P.set_now_frame_ros(_chain(ramp=False))            # without the ramp: candidates only, no edge
+    finally:
+        P.close()
+
+
+def test_frames_converge_each_at_its_own_pace(hip):
+    """the chain at positions 0, 2 and last of five, beside dot frames, which are quiet at the first launch"""
+    H, W, n = CHAIN_H, CHAIN_W, 5
+    kinds = ("chain", "dot", "chain", "dot", "chain")
+    ref, dep, now = _pairs(H, W, 0, n, seed=21, ref_kinds=kinds, now_kinds=kinds)
+    rounds = []
+    states = _compare_call(hip, H, W, n, hip.EA_F64, ref, dep, now, where="chain", rounds=rounds)
+    print("looks, both sides:", rounds)
+    assert rounds[0] >= 4, rounds
+    for i in range(n):
+        assert states[i]["n"] == CHAIN_W if kinds[i] == "chain" else 0 < states[i]["n"] < 10, (i, states[i]["n"])
+        for k in range(i + 1, n):
+            if kinds[i] == kinds[k]:
+                assert np.array_equal(states[i]["dt"], states[k]["dt"]), (i, k)
+    for side in ((ref, dep, None), (None, None, now)):       # one side at a time: the looks of that side only
+        rounds = []
+        _compare_call(hip, H, W, n, hip.EA_F32, *side, where="one side", rounds=rounds)
+        print("looks, one side:", rounds)
+        assert rounds[0] >= 2, rounds
+
+
+def test_an_all_dot_call_takes_one_look_per_side(hip):
+    H, W, n = CHAIN_H, CHAIN_W, 3
+    ref, dep, now = _pairs(H, W, 0, n, seed=22, ref_kinds=("dot",), now_kinds=("dot",))
+    for args, want in (((ref, dep, now), 2), ((ref, dep, None), 1), ((None, None, now), 1)):
+        rounds = []
+        _compare_call(hip, H, W, n, hip.EA_F64, *args, where="dot", rounds=rounds)
+        assert rounds == [want]
+
+
+# ---- the bundled frames ----
+
+@pytest.fixture(scope="module")
+def bundled(hip):
+    """the five bundled frames at full size, depth in metres: uint16 / 5000 as float32"""
+    from edge_alignment_amd import synth
+    full = {k: (bgr, dep.astype(np.float32) / np.float32(5000.0)) for k, (bgr, dep) in synth.load_bundled_frames(G).items()}
+    return dict(full=full)
+
+
+FIVE_PAIRS = ((1, 2), (2, 3), (3, 4), (4, 5), (5, 1))
+K_HALF = tuple(0.5 * k for k in K)                           # src/SolveEA.cpp:15-18 scales all four
+Q0, T0 = np.array([1.0, 0, 0, 0]), np.zeros(3)
+
+
+def _bundled_frames(bundled):
+    full = bundled["full"]
+    return ([full[a][0] for a, _ in FIVE_PAIRS], [full[a][1] for a, _ in FIVE_PAIRS], [full[b][0] for _, b in FIVE_PAIRS])
+
+
+def test_bundled_pairs_at_full_size_halved_once_then_eval_and_solve(hip, bundled):
+    """five pairs of the bundled 640 x 480 frames in the node's shape: one call, halvings = 1"""
+    from oracle import preprocess_np as pp
+    ref, dep, now = _bundled_frames(bundled)
+    n = len(FIVE_PAIRS)
+    got_p, want_p = [hip.Problem(*K_HALF) for _ in FIVE_PAIRS], [hip.Problem(*K_HALF) for _ in FIVE_PAIRS]
+    got_b, want_b = hip.Batch(got_p), hip.Batch(want_p)
+    try:
+        got_b.set_frames_ros(ref, dep, now, halvings=1)
+        assert got_b.info("frames_without_edges") == 0
+        assert _per_problem(hip, want_p, ref, dep, now, halvings=1) == []
+        for i in range(n):
+            got = _state(got_p[i])
+            _assert_same(got, _state(want_p[i]), ("full size", FIVE_PAIRS[i]))
+            assert got["n"] > 1000 and got["weights"] is None and got["dt"].shape == (240, 320)
+        # one pair against the numpy restatement of the node's reduction, of setRefFrame and of setNowFrame
+        i = FIVE_PAIRS.index((1, 2))
+        r, d, w = pp.resize_half_bgr8(ref[i]), pp.resize_half_f32(dep[i], nan_to_zero=True), pp.resize_half_bgr8(now[i])
+        pts, _ = pp.ros_ref_points(r, d, *K_HALF)
+        assert _same_bits(got_p[i].get_points(), pts.T)
+        assert np.array_equal(got_p[i].get_dt(), pp.ros_now_distance_transform(w).astype(np.float64))
+        q, t = np.tile(Q0, (n, 1)), np.tile(T0, (n, 1))
+        ev = got_b.eval(q, t)
+        _assert_same_eval(ev, want_b.eval(q, t), "eval")
+        assert (ev["cost"] > 0).all() and np.isfinite(ev["cost"]).all()
+        gq, gt, gs = got_b.solve(q, t, max_num_iterations=12)
+        wq, wt, ws = want_b.solve(q, t, max_num_iterations=12)
+        assert np.array_equal(gq, wq) and np.array_equal(gt, wt)
+        for a, b in zip(gs, ws):
+            for key in ("termination", "why", "num_iterations", "initial_cost", "final_cost"):
+                assert a[key] == b[key], key
+        assert any(s["num_iterations"] > 1 for s in gs)
+    finally:
+        _close(want_b, got_b, want_p, got_p)
+
+
+def test_one_side_at_a_time_another_extent_the_other_flavours_and_a_per_problem_call_afterwards(hip, bundled):
+    H, W, halvings, n = 37, 70, 1, 5
+    ref, dep, now = _pairs(H, W, halvings, n, seed=41)
+    u16 = [np.nan_to_num(np.clip(d, 0, 6) * 5000).astype(np.uint16) for d in dep]   # (a depth for the other two flavours)
+    want_p, got_p = _problems(hip, n, H, W, hip.EA_F64), _problems(hip, n, H, W, hip.EA_F64)
+    got_b = hip.Batch(got_p)
+    try:
+        assert _per_problem(hip, want_p, ref, dep, now, halvings=halvings) == []
+        # only the reference frames: points as the per-problem call leaves them, the image still the one from before
+        got_b.set_frames_ros(ref_bgr=ref, ref_depth=dep, halvings=halvings)
+        for i in range(n):
+            _assert_same(_state(got_p[i], image=False), _state(want_p[i], image=False), ("ref only", i))
+            assert np.array_equal(got_p[i].get_dt(), _previous_image(i).T), i
+        # only the current frames: the points stay
+        got_b.set_frames_ros(now_bgr=now, halvings=halvings)
+        for i in range(n):
+            _assert_same(_state(got_p[i]), _state(want_p[i]), ("now only", i))
+        # a larger extent with two halvings, then the first one again: workspace and stage are laid out anew each time
+        H2, W2 = 66, 100
+        r2, d2, n2 = _pairs(H2, W2, 2, n, seed=3)
+        big_p = _problems(hip, n, H, W, hip.EA_F64)            # (the same cameras as got_p: the points are comparable)
+        try:
+            assert _per_problem(hip, big_p, r2, d2, n2, halvings=2) == []
+            got_b.set_frames_ros(r2, d2, n2, halvings=2)
+            for i in range(n):
+                _assert_same(_state(got_p[i]), _state(big_p[i]), ("larger extent", i))
+        finally:
+            _close(big_p)
+        got_b.set_frames_ros(ref, dep, now, halvings=halvings)
+        for i in range(n):
+            _assert_same(_state(got_p[i]), _state(want_p[i]), ("first extent again", i))
+        # the Laplacian, the Canny and the ROS call in turn: they share the batch's workspace
+        lap_p, can_p = _problems(hip, n, H, W, hip.EA_F64), _problems(hip, n, H, W, hip.EA_F64)
+        try:
+            for i in range(n):
+                lap_p[i].set_ref_frame(ref[i], u16[i]); lap_p[i].set_now_frame(now[i])
+                can_p[i].set_ref_frame_canny(ref[i], u16[i]); can_p[i].set_now_frame_canny(now[i])
+            for turn in range(2):
+                got_b.set_frames(ref, u16, now)
+                assert got_b.info("frames_hysteresis_rounds") == 0 and got_b.info("frames_without_edges") == 0
+                for i in range(n):
+                    _assert_same(_state(got_p[i]), _state(lap_p[i]), ("laplacian", turn, i))
+                got_b.set_frames_ros(ref, dep, now, halvings=halvings)
+                assert got_b.info("frames_hysteresis_rounds") >= 2
+                for i in range(n):
+                    _assert_same(_state(got_p[i]), _state(want_p[i]), ("ros", turn, i))
+                got_b.set_frames_canny(ref, u16, now)
+                assert got_b.info("frames_without_edges") == 0
+                for i in range(n):
+                    _assert_same(_state(got_p[i]), _state(can_p[i]), ("canny", turn, i))
+            got_b.set_frames_ros(ref, dep, now, halvings=halvings)
+        finally:
+            _close(lap_p, can_p)
+        # a per-problem producer call on one member afterwards: the batch sees that problem's new frame
+        want_b = hip.Batch(want_p)
+        try:
+            for P in (got_p[1], want_p[1]):
+                P.set_ref_frame_ros(ref[3], dep[3], halvings=halvings)
+                P.set_now_frame_ros(now[0], halvings=halvings)
+            _assert_same(_state(got_p[1]), _state(want_p[1]), "member")
+            q, t = np.tile(Q0, (n, 1)), np.tile(T0, (n, 1))
+            _assert_same_eval(got_b.eval(q, t), want_b.eval(q, t), "after the member's own call")
+        finally:
+            _close(want_b)
+    finally:
+        _close(got_b, want_p, got_p)
+
+
+@pytest.mark.parametrize("halvings", [0, 1, 3])
+def test_device_tensors_give_the_bits_of_the_host_entry(hip, halvings):
+    torch = pytest.importorskip("torch")
+    if not torch.cuda.is_available():
+        pytest.skip("torch has no device")
+    H, W, n = 37, 70, 5
+    ref, dep, now = _pairs(H, W, halvings, n, seed=51 + halvings)
+    want_p, got_p = _problems(hip, n, H, W, hip.EA_F64), _problems(hip, n, H, W, hip.EA_F64)
+    want_b, got_b = hip.Batch(want_p), hip.Batch(got_p)
+    try:
+        dev = torch.device("cuda", 0)
+        t_ref = torch.from_numpy(np.stack(ref)).to(dev)                          # one stacked tensor
+        t_dep = [torch.from_numpy(d).to(dev) for d in dep]                       # a list of tensors
+        t_now = torch.from_numpy(np.stack(now)).to(dev)
+        want_b.set_frames_ros(ref, dep, now, halvings=halvings)
+        got_b.set_frames_ros(t_ref, t_dep, t_now, halvings=halvings)
+        for i in range(n):
+            _assert_same(_state(got_p[i]), _state(want_p[i]), ("device", i))
+        assert torch.equal(t_ref.cpu(), torch.from_numpy(np.stack(ref)))         # read in place, not written
+        assert torch.equal(t_now.cpu(), torch.from_numpy(np.stack(now)))
+        assert all(np.array_equal(a.cpu().numpy().view(np.int32), b.view(np.int32)) for a, b in zip(t_dep, dep))
+        with pytest.raises(ValueError):
+            got_b.set_frames_ros(t_ref, dep, t_now, halvings=halvings)           # a mix of host and device inputs
+        with pytest.raises(ValueError):
+            got_b.set_frames_ros(t_ref, [d.double() for d in t_dep], t_now, halvings=halvings)   # not float32
+        with pytest.raises(ValueError):
+            got_b.set_frames_ros(now_bgr=t_now.cpu(), halvings=halvings)         # a torch tensor, but not on the GPU
+    finally:
+        _close(want_b, got_b, want_p, got_p)
+
+
+def test_misuse_is_refused_and_leaves_every_problem_as_it_was(hip):
+    import ctypes as C
+    H, W, halvings, n = 36, 72, 1, 5                          # full 72 x 144: divisible by 8, not by 16
+    ref, dep, now = _pairs(H, W, halvings, n, seed=61)
+    want_p, got_p = _problems(hip, n, H, W, hip.EA_F64), _problems(hip, n, H, W, hip.EA_F64)
+    want_b, got_b = hip.Batch(want_p), hip.Batch(got_p)
+    dup_b = hip.Batch([got_p[0], got_p[1], got_p[0]])
+    L = hip.load()
+    nan = float("nan")
+    want_b.set_frames_ros(ref, dep, now, halvings=halvings)
+    got_b.set_frames_ros(ref, dep, now, halvings=halvings)
+
+    def refused(call):
+        with pytest.raises(hip.EAError) as ei:
+            call()
+        assert ei.value.code == hip.EA_ERR_INVALID_ARG, ei.value
+        for i in range(n):
+            _assert_same(_state(got_p[i]), _state(want_p[i]), ("unchanged", i))
+
+    try:
+        other = [f[::-1].copy() for f in now]   # frames that would change every image if a refused call ran
+        kw = dict(halvings=halvings)
+        refused(lambda: got_b.set_frames_ros(ref, dep, other[:2] + [None] + other[3:], **kw))       # a NULL entry
+        refused(lambda: got_b.set_frames_ros(ref, dep[:2] + [None] + dep[3:], other, **kw))
+        refused(lambda: got_b.set_frames_ros(ref[:-1], dep[:-1], other[:-1], **kw))                # a wrong count
+        refused(lambda: got_b.set_frames_ros(ref, dep, other + other[:1], **kw))
+        refused(lambda: dup_b.set_frames_ros(ref[:3], dep[:3], other[:3], **kw))                   # the same problem twice
+        refused(lambda: got_b.set_frames_ros(ref, dep, other, halvings=-1))                        # halvings outside 0..8
+        refused(lambda: got_b.set_frames_ros(ref, dep, other, halvings=9))
+        refused(lambda: got_b.set_frames_ros(ref, dep, other, halvings=4))                         # 72 x 144 is not divisible by 16
+        refused(lambda: got_b.set_frames_ros(now_bgr=[f[:37].copy() for f in other], **kw))        # an odd height, halved
+        refused(lambda: got_b.set_frames_ros(now_bgr=[f[:4, :8].copy() for f in other], **kw))     # a working extent of 2 x 4
+        refused(lambda: got_b.set_frames_ros(now_bgr=[f[:8, :4].copy() for f in other], **kw))     # ... of 4 x 2
+        refused(lambda: got_b.set_frames_ros(now_bgr=[f[:2].copy() for f in other]))               # a full extent of 2
+        refused(lambda: got_b.set_frames_ros(ref, dep, other, t1=nan, **kw))                       # a NaN threshold
+        refused(lambda: got_b.set_frames_ros(ref, dep, other, t2=nan, **kw))
+        # host pointers handed to the device entry, as colour frames and as depth frames
+        prm = hip.RosFrameParams()
+        L.ea_default_ros_frame_params(C.byref(prm), *other[0].shape[:2])
+        prm.halvings = halvings
+        ptrs = (C.c_void_p * n)(*[f.ctypes.data for f in other])
+        dptrs = (C.c_void_p * n)(*[d.ctypes.data for d in dep])
+        refused(lambda: hip._check(L.ea_batch_set_frames_ros_device(got_b._h, None, None, ptrs, C.byref(prm))))
+        refused(lambda: hip._check(L.ea_batch_set_frames_ros_device(got_b._h, ptrs, dptrs, None, C.byref(prm))))
+        # both sides NULL; a reference colour frame without its depth
+        refused(lambda: hip._check(L.ea_batch_set_frames_ros(got_b._h, None, None, None, C.byref(prm))))
+        refused(lambda: hip._check(L.ea_batch_set_frames_ros(got_b._h, ptrs, None, None, C.byref(prm))))
+        torch = pytest.importorskip("torch")
+        if torch.cuda.is_available():
+            # device colour frames with a host depth frame, and with a device depth frame at an address that is not 4-aligned
+            dev = torch.device("cuda", 0)
+            t_ref = [torch.from_numpy(f).to(dev) for f in ref]
+            t_dep = [torch.zeros(d.size + 1, dtype=torch.float32, device=dev) for d in dep]
+            rp = (C.c_void_p * n)(*[x.data_ptr() for x in t_ref])
+            odd = (C.c_void_p * n)(*[x.data_ptr() + 2 for x in t_dep])
+            refused(lambda: hip._check(L.ea_batch_set_frames_ros_device(got_b._h, rp, dptrs, None, C.byref(prm))))
+            refused(lambda: hip._check(L.ea_batch_set_frames_ros_device(got_b._h, rp, odd, None, C.byref(prm))))
+        # an accepted call in between leaves what the per-problem producers leave, and the batch still works
+        got_b.set_frames_ros(now_bgr=now, **kw)
+        for i in range(n):
+            _assert_same(_state(got_p[i]), _state(want_p[i]), ("again", i))
+        got_b.set_frames_ros(now_bgr=other, **kw)
+        assert not np.array_equal(got_p[0].get_dt(), want_p[0].get_dt())
+    finally:
+        _close(dup_b, want_b, got_b, want_p, got_p)
