@@ -250,6 +250,10 @@ extern "C" int ea_release_cached_memory(void) {
 struct KposesMark { int seq, start, g; };
 
 constexpr int kPosesWaveExchangeDefault = 1;  // tuning key "poses_wave_exchange"
+// tuning key "poses_lane_per_pose" at -1: the smallest K that takes one pose per lane.  Measured on C2 (98 rows, profiles/LOG.md):
+// a launch of that kernel has rows x ceil(K / 64) workgroups, two resident per CU, so below ~1000 poses it does not fill the
+// chip twice over and the other kernel is faster (K = 512: 0.89x); from 1024 on it is ahead.
+constexpr int kPosesLanesFromK = 1024;
 struct ea_batch {
   std::vector<ea_problem *> probs;
   std::vector<uint64_t> versions;
@@ -339,6 +343,10 @@ struct ea_batch {
   int kp_rows_cap = 0;
   int t_kp_order = 0;                 // tuning key "poses_order": 1 = an XCD walks the rows of a pose instead of the poses of a row (A/B)
   int t_kp_xchg = kPosesWaveExchangeDefault, kp_xchg = 0, last_kp_xchg = 0;  // tuning key "poses_wave_exchange"; what kposes_shape made of it; what the last pose-batched launch ran
+  // one pose per lane (ea_eval_poses_lanes_kernel): tuning key "poses_lane_per_pose" (-1 = from kPosesLanesFromK poses on, 0 =
+  // never, N = from N poses on); what ea_batch_set_poses made of it for its K; what the last pose-batched call ran.  kp_Gc: the
+  // launch size of the cost-only kernel, which keeps kposes_group's rule whatever the evaluation runs
+  int t_kp_lanes = -1, kp_lanes = 0, last_kp_lanes = 0, kp_Gc = 0;
   std::vector<KposesMark> kp_marks;   // the folds of the last call: sequence number, first pose, poses
   // ea_batch_cost_resident_poses: the narrow partials of one launch (kCostPartialBytes per row of a pose), tuning key
   // "cost_form" (0: always the fall-back, the full evaluation with only the cost fetched) and what the last call ran
@@ -1630,13 +1638,40 @@ static void kposes_shape(ea_batch *b) {
   b->kp_ntiles = rows; b->kp_max_chunks = widest;
 }
 
+static int64_t kposes_rows_bound(const ea_batch *b) {  // poses whose rows fit in 64 MB (both arrays of the flat form together)
+  const int64_t wgs = std::max<int64_t>(1, (int64_t)b->kp_ntiles);
+  return ((int64_t)64 << 20) / ((kposes_flat(b) ? 2 : 1) * wgs * kAccSlots * (int64_t)sizeof(double));
+}
 static int kposes_group(const ea_batch *b, int K) {
   const int64_t wgs = std::max<int64_t>(1, (int64_t)b->kp_ntiles);
   int64_t g = (32768 + wgs - 1) / wgs;
   g = std::min<int64_t>(g, 65535 / std::max(1, b->nterms));
-  g = std::min<int64_t>(g, ((int64_t)64 << 20) / ((kposes_flat(b) ? 2 : 1) * wgs * kAccSlots * (int64_t)sizeof(double)));
+  g = std::min<int64_t>(g, kposes_rows_bound(b));
   if (b->t_kp_G > 0) g = std::min<int64_t>(g, b->t_kp_G);
   return (int)std::max<int64_t>(1, std::min<int64_t>(g, K));
+}
+
+// One pose per lane (ea_eval_poses_lanes_kernel).  Whether a call of K poses takes it follows from the batch and K alone --
+// never from G or the split into launches, so that any split lands on the same bits: a flat fp64 batch at the 256 x 2 pose
+// shape whose rows leave room for one full group of 64 poses, and K at or above the threshold.  Its G is not the
+// 32 k-workgroup rule above (a launch has 64 times fewer, longer workgroups, and every launch ends on a tail of about one
+// workgroup lifetime): as many whole groups as the rows' 64 MB hold, launches of G with the remainder last
+// (poses_lanes_group_size / poses_lanes_launch_size, ea_poses_map.h).  "poses_per_launch" caps it; below 64 the launches have
+// one partly filled group each -- slow, the same bits.
+static bool kposes_lanes(const ea_batch *b, int K) {
+  if (!kposes_flat(b) || b->dtype != EA_F64 || b->kp_nt != 256 || b->kp_ppt != 2) return false;
+  if (kposes_rows_bound(b) < kPosesLanes) return false;
+  const int from = b->t_kp_lanes < 0 ? kPosesLanesFromK : b->t_kp_lanes;
+  return from > 0 && K >= from;
+}
+static int kposes_group_lanes(const ea_batch *b, int K) {
+  int64_t g = std::min<int64_t>(kposes_rows_bound(b), (int64_t)1 << 20);
+  if (b->t_kp_G > 0) g = std::min<int64_t>(g, b->t_kp_G);
+  return std::min(poses_lanes_group_size((int)g), K);
+}
+// poses per launch of the evaluation of the K resident poses (the last launch takes the remainder)
+static int kposes_per(const ea_batch *b, int K) {
+  return b->kp_lanes ? poses_lanes_launch_size(K, b->kp_G) : poses_launch_size(K, b->kp_G);
 }
 
 // a batch ea_eval_poses_kernel covers: the plain functor on the L2 path, one term per problem (any dtype, addressing and
@@ -1747,7 +1782,10 @@ extern "C" int ea_batch_set_poses(ea_batch *b, int K, const double *q, const dou
   b->kp_K = 0;
   if ((rc = kposes_reserve(b, K)) != EA_OK) return rc;
   if (b->kp_G == 0) kposes_shape(b);   // (once per build of the batch)
-  if ((rc = kposes_tables(b, kposes_group(b, K))) != EA_OK) return rc;
+  // (the cost-only kernel keeps its own launch size: the rows hold the larger of the two)
+  const int lanes = kposes_lanes(b, K), Gc = kposes_group(b, K), G = lanes ? kposes_group_lanes(b, K) : Gc;
+  if ((rc = kposes_tables(b, std::max(G, Gc))) != EA_OK) return rc;
+  b->kp_G = G; b->kp_Gc = Gc; b->kp_lanes = lanes;
   const size_t n = (size_t)K * b->probs.size();
   // (the previous upload out of the same staging block has been consumed: every call below ends with its pose kernel
   // enqueued behind the copy, and the evaluations that follow are synchronised before they return)
@@ -1774,9 +1812,9 @@ static bool seq_reached(int flag, int seq) { return (unsigned)flag - (unsigned)s
 // sequence number of its own (consecutive within the call; b->kp_marks keeps them for the caller that unpacks as it goes).
 // Grid form: an evaluation + fold pair per launch, the last fold raises the flag (flag_last).
 static int enqueue_resident_poses(ea_batch *b, int K, bool folds = true, bool flag_last = false) {
-  const int count = (int)b->probs.size(), per = poses_launch_size(K, b->kp_G), rows = b->kp_ntiles;
+  const int count = (int)b->probs.size(), per = kposes_per(b, K), rows = b->kp_ntiles;
   b->kp_marks.clear();
-  b->last_kp_xchg = 0;
+  b->last_kp_xchg = 0; b->last_kp_lanes = 0;
   if (!kposes_flat(b)) {
     for (int start = 0; start < K; start += per) {
       const int g = std::min(per, K - start);
@@ -1792,7 +1830,9 @@ static int enqueue_resident_poses(ea_batch *b, int K, bool folds = true, bool fl
   const EvalLaunch shape = eval_launch(b, /*kposes=*/true);
   PosesLaunch pl;
   pl.rows = rows; pl.order = b->t_kp_order; pl.single = b->nterms == 1; pl.exchange = b->kp_xchg;
-  b->last_kp_xchg = rows > 0 ? b->kp_xchg : 0;
+  const bool lanes = b->kp_lanes != 0;
+  b->last_kp_xchg = rows > 0 && !lanes ? b->kp_xchg : 0;
+  b->last_kp_lanes = rows > 0 && lanes;
   PosesFold owed;  // the fold the launches so far still owe (n = 0: none)
   owed.count = count; owed.rows_per_pose = rows; owed.groups = b->d_kgroups;
   owed.counter = b->d_done_count; owed.host_flag = b->d_progress + 3 * (size_t)count;
@@ -1808,7 +1848,8 @@ static int enqueue_resident_poses(ea_batch *b, int K, bool folds = true, bool fl
   for (int start = 0; start < K; start += per, ++i) {
     double *into = b->d_krows + (size_t)(i & 1) * (size_t)b->kp_rows_cap * (size_t)rows * kAccSlots;
     pl.g = std::min(per, K - start);
-    HIPCHK(launch_eval_poses(shape, pl, b->d_kprobs, b->d_kposes + (size_t)start * count, into, owed, b->stream));
+    if (lanes) HIPCHK(launch_eval_poses_lanes(shape, pl, b->d_kprobs, b->d_kposes + (size_t)start * count, into, owed, b->stream));
+    else HIPCHK(launch_eval_poses(shape, pl, b->d_kprobs, b->d_kposes + (size_t)start * count, into, owed, b->stream));
     if (folds) owe(start, pl.g, into);
   }
   if (folds) HIPCHK(launch_poses_fold(b->kp_nt, owed, b->stream));
@@ -1873,9 +1914,9 @@ extern "C" int ea_batch_eval_resident_poses(ea_batch *b, double *cost, double *J
 // slots of the result in pinned memory and raises the flag to the launch's sequence number.  A result is a fixed-order sum
 // over (chunk, lane, wave) and the rows of its pose: it does not depend on G, the split or the item order.
 static int enqueue_resident_cost(ea_batch *b, int K) {
-  const int count = (int)b->probs.size(), per = poses_launch_size(K, b->kp_G), rows = b->kp_ntiles;
+  const int count = (int)b->probs.size(), per = poses_launch_size(K, b->kp_Gc), rows = b->kp_ntiles;
   b->kp_marks.clear();
-  b->last_kp_xchg = 0;
+  b->last_kp_xchg = 0; b->last_kp_lanes = 0;
   if (b->done_seq > 0x7fffffff - (K + per - 1) / per - 2) b->done_seq = 0;  // (a call's sequence numbers do not straddle the wrap)
   const size_t need = std::max<size_t>(1, (size_t)per * (size_t)rows) * kCostPartialBytes;
   if (need > b->kcost_bytes) {
@@ -1951,7 +1992,7 @@ extern "C" int ea_batch_bench_resident_poses(ea_batch *b, int reps, int evaluati
   float ms = 0.f;
   HIPCHK(hipEventElapsedTime(&ms, evp.e0, evp.e1));
   *ms_per_run = (double)ms / reps;
-  if (launches) { const int per = poses_launch_size(b->kp_K, b->kp_G); *launches = (b->kp_K + per - 1) / per; }
+  if (launches) { const int per = kposes_per(b, b->kp_K); *launches = (b->kp_K + per - 1) / per; }
   return EA_OK;
 }
 
@@ -3044,6 +3085,8 @@ extern "C" int ea_batch_set_tuning(ea_batch *b, const char *key, int value) {
   else if (k == "poses_order") { b->t_kp_order = value ? 1 : 0; return EA_OK; }
   // (0: the per-wavefront butterfly; read when the pose path is shaped, so resident poses and the pose path's tables are dropped)
   else if (k == "poses_wave_exchange") { b->t_kp_xchg = value < 0 ? kPosesWaveExchangeDefault : value != 0; b->kp_K = 0; b->kp_G = 0; return EA_OK; }
+  // (read when poses are set: resident poses are dropped)
+  else if (k == "poses_lane_per_pose") { b->t_kp_lanes = value < 0 ? -1 : value; b->kp_K = 0; return EA_OK; }
   else if (k == "starts_events") { b->t_starts_events = value > 0 ? 1 : 0; return EA_OK; }
   else if (k == "cost_form") { b->t_cost_form = value ? 1 : 0; return EA_OK; }  // 0: cost-only calls run the full evaluation (A/B)
   else return fail(EA_ERR_INVALID_ARG, "unknown tuning key: " + k);
@@ -3071,6 +3114,7 @@ extern "C" int ea_batch_get_info(const ea_batch *b, const char *key, int64_t *va
   else if (k == "poses_threads") *value = b->kp_nt;
   else if (k == "poses_tiles") *value = b->kp_ntiles;            // partial rows (= workgroups with work) per pose
   else if (k == "poses_wave_exchange") *value = b->last_kp_xchg;  // the last pose-batched launch: 1 = the wave-exchange reduction
+  else if (k == "poses_lane_per_pose") *value = b->last_kp_lanes;  // the last pose-batched call: 1 = one pose per lane (ea_eval_poses_lanes_kernel)
   else if (k == "fused_iterations") *value = b->last_fused;      // the last solve ran one launch per LM iteration (ea_lm_iter_kernel)
   else if (k == "cost_form") *value = b->last_cost_form;         // the last cost-only call: 1 = ea_cost_poses_kernel, 0 = the full evaluation
   else if (k == "starts_form") *value = b->last_starts_form;     // the last ea_batch_solve_starts: 1 = lock-step, 0 = one batch solve per start

@@ -1866,6 +1866,226 @@ __global__ __launch_bounds__(NT) void ea_poses_fold_kernel(PosesFold fold) {
   poses_fold_one<NT>(fold, blockIdx.x);
 }
 
+// ---- the pose-batched fp64 evaluation with one pose per LANE ---------------------------------------------------------------
+// ea_eval_poses_kernel maps lanes to points, so each of its 28 sums crosses lanes -- exchange buffer, barriers and butterfly
+// per 512 (point, pose) pairs.  A call of many poses has a second long axis: here a lane owns a POSE (its twelve constants
+// in vector registers) and the wavefront walks points, which are wave-uniform and arrive through scalar loads.  Every sum
+// and the failed-functor count stay inside their lane from the first point to the last; nothing crosses lanes and no
+// barrier stands in the point loop.  A work item is (row of a pose, 64 consecutive poses of the launch) (ea_poses_map.h); the
+// row is the 512-point chunk it is in the other kernel, its partial row pose * rows + row, so riders, folds and the host
+// stay as they are.  The workgroup's four wavefronts hold the same 64 poses and walk the chunk's four sub-runs of 128
+// points, two points per iteration (the paired Cauchy logarithm pairs points 2i and 2i + 1 of a sub-run), sums in the order
+// of the points; at the end the per-lane sums are added through LDS as (w0 + w1) + (w2 + w3) and lane l stores the row of
+// pose l.  The summation order differs from the other kernel's (last places), and depends on nothing but the pose and the
+// row: not on the lane, the company in the wavefront, the launch or the item order.  Four wavefronts because the riding
+// fold's summation order is that of a 256-lane workgroup.  The per-point expressions are fused_chunk's, through the same
+// functions; lanes whose pose is not a unit quaternion, or whose point fails, take their branch per lane.
+template <typename T> using CPtr = const T __attribute__((address_space(4))) *;  // read-only for the kernel: uniform loads go through the scalar cache
+constexpr int kLanesWaves = 4, kLanesSub = 512 / kLanesWaves, kLanesVals = 29;  // (28 sums + failed functors)
+
+// What a lane keeps of a point between asking for its stencil rows and summing it up: the rows as loaded (an fp32-stored image
+// stays fp32 until it is used) and six words of the projection.  The other five (bx, by, fxz, fyz and the fix-up of a lane
+// without a valid point) are formed again from these by project_point's own expressions when the point is summed: four
+// instructions instead of ten registers held across the loads.
+template <typename IT> struct LanesStage {
+  double cx_, cy_, cz_, iz, fu, fv;
+  bool valid;
+  Row4<IT> row[4];
+};
+template <typename IT> __device__ __forceinline__ Row4<double> lanes_widen(const Row4<IT> &r) {
+  Row4<double> o;
+  o.p0 = (double)r.p0; o.p1 = (double)r.p1; o.p2 = (double)r.p2; o.p3 = (double)r.p3;
+  return o;
+}
+// Stage 1 of a point: project, count a failed functor, move the lanes without a valid point to a harmless sample, and issue
+// the four row loads.  inb (uniform): the point exists -- an odd sub-run ends on a copy of its last point, and the loop's last
+// look-ahead on a point that is not summed at all.
+template <bool BUF, bool IMG32>
+__device__ __forceinline__ void lanes_stage(const ProblemDesc &pd, const PoseLite<double> &ps, double x, double y, double z,
+                                            bool inb, LanesStage<typename ImgOf<double, IMG32>::type> &st, int &n_bad) {
+  typedef double T;
+  typedef typename ImgOf<T, IMG32>::type IT;
+  const int pitch = pd.pitch;
+  const void *img_base = IMG32 ? pd.dt32 : pd.dt;
+  Proj<T> pr;
+  project_point<T>(pd, ps, x, y, z, pr);
+  st.valid = inb && pr.state == 1;
+  n_bad += (inb && pr.state == 2) ? 1 : 0;
+  if (__any(!st.valid) && !st.valid) {  // (uniform test first, as in fused_chunk)
+    pr.iu = 0; pr.iv = 0; pr.fu = T(0); pr.fv = T(0);
+  }
+  st.cx_ = pr.cx_; st.cy_ = pr.cy_; st.cz_ = pr.cz_; st.iz = pr.iz; st.fu = pr.fu; st.fv = pr.fv;
+  if constexpr (BUF) {
+    const __amdgpu_buffer_rsrc_t rimg =
+        make_raw_buffer(img_base, (unsigned)pitch * (unsigned)(pd.H + 2 * kImagePad) * (unsigned)sizeof(IT));
+    const int voff = ((pr.iv + (kImagePad - 1)) * pitch + (pr.iu + (kImagePad - 1))) * (int)sizeof(IT);
+#pragma unroll
+    for (int l = 0; l < 4; ++l) st.row[l] = buf_load_row4<IT>(rimg, voff, l * pitch * (int)sizeof(IT));
+  } else {
+    const GPtr<IT> gimg = (GPtr<IT>)(static_cast<const IT *>(img_base) + (size_t)kImagePad * (size_t)pitch + kImagePad);
+    const GPtr<IT> base = gimg + ((ptrdiff_t)(pr.iv - 1) * pitch + (pr.iu - 1));
+#pragma unroll
+    for (int l = 0; l < 4; ++l) st.row[l] = load_row4<IT>(base + (ptrdiff_t)l * pitch);
+  }
+}
+// Stage 2: staged point k of its pair into the lane's sums, fused_chunk's statements.  UNIT: every lane's pose is a unit
+// quaternion (the test is made once per work item), else each lane takes its own branch of jacobian_row.
+template <bool IMG32, bool UNIT>
+__device__ __forceinline__ void lanes_sums(int k, const ProblemDesc &pd, const PoseLite<double> &ps_, double x, double y, double z,
+                                           const LanesStage<typename ImgOf<double, IMG32>::type> &st, bool pair,
+                                           double (&acc)[28], double &cost, double &held) {
+  typedef double T;
+  PoseLite<T> ps = ps_;
+  if constexpr (UNIT) ps.unit_q = 1;
+  const T loss_a = Uni<T>::loss_a(pd);
+  Proj<T> pr;
+  pr.cx_ = st.cx_; pr.cy_ = st.cy_; pr.cz_ = st.cz_; pr.iz = st.iz; pr.fu = st.fu; pr.fv = st.fv;
+  pr.bx = st.cx_ + ps.t[0]; pr.by = st.cy_ + ps.t[1];
+  pr.fxz = Uni<T>::fx(pd) * st.iz; pr.fyz = Uni<T>::fy(pd) * st.iz;
+  if (__any(!st.valid) && !st.valid) {  // (the rest of fused_chunk's fix-up; the sample was moved when the rows were asked for)
+    pr.iz = T(1);
+    pr.bx = T(0); pr.by = T(0);
+    pr.fxz = T(0); pr.fyz = T(0);
+  }
+  T f, Fu, Fv;
+  bicubic<T>(pr.fu, pr.fv, [&](int l) { return lanes_widen(st.row[l]); }, f, Fu, Fv);
+  T J[6];
+  jacobian_row<T>(pd, ps, pr, x, y, z, Fu, Fv, J);
+  T rho, w;
+  loss_point<T, 2, false>(pair, pd.loss_kind, loss_a, Uni<T>::loss_inv_b(pd), f * f, st.valid, T(1), rho, w);
+  const T wr = w * f;
+  int s = 0;
+#pragma unroll
+  for (int a = 0; a < 6; ++a) {
+    const T wJa = w * J[a];
+#pragma unroll
+    for (int b = a; b < 6; ++b) { acc[s] = t_fma<T>(wJa, J[b], acc[s]); ++s; }
+    acc[kAccJtr + a] = t_fma<T>(J[a], wr, acc[kAccJtr + a]);
+  }
+  cost_point<T, 2>(k, pair, loss_a, rho, cost, held);
+}
+
+// A wavefront's sub-run of n_sub points at px / py / pz, two per iteration (the pair of the paired logarithm): both points are
+// projected and their eight row loads issued before the first is summed -- one trip to memory per pair, which the SIMD's
+// other wavefront covers -- and the coordinates (scalar loads) are asked for two pairs ahead; that look-ahead clamps to the
+// sub-run's last point.  (Staging the NEXT pair's rows under the sums as well was tried: with 56 registers of sums it does
+// not fit 256 registers without scratch.)
+template <bool BUF, bool IMG32, bool UNIT>
+__device__ __forceinline__ void lanes_run(const ProblemDesc &pd, const PoseLite<double> &ps_, CPtr<double> px, CPtr<double> py,
+                                          CPtr<double> pz, int n_sub, bool pair, double (&acc)[28], int &n_bad,
+                                          const double (*s_pose)[64]) {
+  typedef double T;
+  typedef typename ImgOf<T, IMG32>::type IT;
+  if (n_sub <= 0) return;
+  const int lane = threadIdx.x & 63;
+  const int last = n_sub - 1;
+  T X[2], Y[2], Z[2], NX[2], NY[2], NZ[2];  // this iteration's pair, the next one's
+  {
+    const int i1 = min(1, last), i2 = min(2, last), i3 = min(3, last);
+    X[0] = px[0]; X[1] = px[i1]; Y[0] = py[0]; Y[1] = py[i1]; Z[0] = pz[0]; Z[1] = pz[i1];
+    NX[0] = px[i2]; NX[1] = px[i3]; NY[0] = py[i2]; NY[1] = py[i3]; NZ[0] = pz[i2]; NZ[1] = pz[i3];
+  }
+#pragma nounroll
+  for (int i = 0; i < n_sub; i += 2) {
+    const int i4 = min(i + 4, last), i5 = min(i + 5, last);
+    const T FX[2] = {px[i4], px[i5]}, FY[2] = {py[i4], py[i5]}, FZ[2] = {pz[i4], pz[i5]};
+    T held = T(1), cost = T(0);
+    LanesStage<IT> A, B;
+    // The rotation and t_z are read by the two projections only: they come out of the wavefront's LDS copy per pair (ten
+    // conflict-free 8-byte reads) instead of occupying twenty registers through the sums.  (The barrier keeps the reads in
+    // the loop.)
+    PoseLite<T> ps = ps_;
+    if constexpr (UNIT) {
+      asm volatile("" ::: "memory");
+#pragma unroll
+      for (int k = 0; k < 9; ++k) ps.R[k] = s_pose[k][lane];
+      ps.t[2] = s_pose[9][lane];
+    }
+    lanes_stage<BUF, IMG32>(pd, ps, X[0], Y[0], Z[0], true, A, n_bad);
+    // (both points' rows are under way before the first is summed; the rare general-quaternion form, which reads 27 more
+    // words per lane and point, takes them one after the other)
+    if constexpr (UNIT) lanes_stage<BUF, IMG32>(pd, ps, X[1], Y[1], Z[1], i + 1 < n_sub, B, n_bad);
+    lanes_sums<IMG32, UNIT>(0, pd, ps, X[0], Y[0], Z[0], A, pair, acc, cost, held);
+    if constexpr (!UNIT) lanes_stage<BUF, IMG32>(pd, ps, X[1], Y[1], Z[1], i + 1 < n_sub, B, n_bad);
+    lanes_sums<IMG32, UNIT>(1, pd, ps, X[1], Y[1], Z[1], B, pair, acc, cost, held);
+    acc[kAccCost] += cost;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) { X[k] = NX[k]; Y[k] = NY[k]; Z[k] = NZ[k]; NX[k] = FX[k]; NY[k] = FY[k]; NZ[k] = FZ[k]; }
+  }
+}
+
+// (two wavefronts per SIMD: 56 registers of sums, two staged points and the arithmetic of a third do not fit three, and
+// left to itself the register allocator goes past 256 into accumulation registers, which halves the occupancy again)
+template <bool BUF, bool IMG32>
+__global__ __launch_bounds__(64 * kLanesWaves) __attribute__((amdgpu_waves_per_eu(2, 2))) void ea_eval_poses_lanes_kernel(
+    int shape, int g, int rows, const ProblemDesc *__restrict__ probs, const PoseState *__restrict__ poses,
+    double *__restrict__ partials, PosesFold fold) {
+  typedef double T;
+  constexpr int NT = 64 * kLanesWaves;
+  __shared__ __align__(16) double s_sum[kLanesWaves / 2][kLanesVals][64];
+  __shared__ __align__(16) double s_pose[kLanesWaves][10][64];  // each wavefront's own copy of R and t_z, lane by lane
+  const PosesLanesWork w = poses_lanes_work(blockIdx.x, shape, rows, g, fold.n);
+  if (w.kind != 2) {  // (uniform)
+    if (w.kind == 1) poses_fold_one<NT>(fold, w.rider);
+    return;
+  }
+  const PosesLanesChunk pc = poses_lanes_chunk(w.row, shape, reinterpret_cast<const PosesRow *>(probs) - rows);
+  const ProblemDesc pd = probs[pc.term];
+  const long long start = (long long)pc.chunk * (kLanesWaves * kLanesSub);
+  if (start >= pd.n) return;
+  const int count = min(kLanesWaves * kLanesSub, (int)(pd.n - start));
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  // the lane's pose; lanes past the launch's last pose compute a copy of it and store nothing
+  const PoseState *psp = poses + ((size_t)(w.pose0 + min(lane, w.live - 1)) * (size_t)pc.count + (size_t)pc.term);
+  PoseLite<T> ps;
+  int active;
+  load_pose_lite<T>(psp, ps, active);
+  const bool on = lane < w.live && active != 0;
+  if (!__any(on)) return;  // (the same in the workgroup's four wavefronts: they hold the same poses)
+
+  const int first = wave * kLanesSub, n_sub = max(0, min(kLanesSub, count - first));
+  const CPtr<T> px = (CPtr<T>)(static_cast<const T *>(pd.x) + start + first);
+  const CPtr<T> py = (CPtr<T>)(static_cast<const T *>(pd.y) + start + first);
+  const CPtr<T> pz = (CPtr<T>)(static_cast<const T *>(pd.z) + start + first);
+  const bool pair = pd.loss_kind == 1;  // one log per two points (loss_point)
+  T acc[28];
+#pragma unroll
+  for (int i = 0; i < 28; ++i) acc[i] = T(0);
+  int n_bad = 0;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) s_pose[wave][k][lane] = ps.R[k];
+  s_pose[wave][9][lane] = ps.t[2];
+  if (__all(ps.unit_q != 0)) lanes_run<BUF, IMG32, true>(pd, ps, px, py, pz, n_sub, pair, acc, n_bad, s_pose[wave]);
+  else lanes_run<BUF, IMG32, false>(pd, ps, px, py, pz, n_sub, pair, acc, n_bad, s_pose[wave]);
+
+  // (w0 + w1) + (w2 + w3), lane by lane: the odd member of each pair hands its sums over, then the pair sums do the same
+  T v[kLanesVals];
+#pragma unroll
+  for (int i = 0; i < 28; ++i) v[i] = acc[i];
+  v[28] = (T)n_bad;
+#pragma unroll
+  for (int s = 1; s < kLanesWaves; s <<= 1) {
+    const int role = wave & (2 * s - 1), buf = wave / (2 * s);
+    if (role == s) {
+#pragma unroll
+      for (int i = 0; i < kLanesVals; ++i) s_sum[buf][i][lane] = v[i];
+    }
+    __syncthreads();
+    if (role == 0) {
+#pragma unroll
+      for (int i = 0; i < kLanesVals; ++i) v[i] += s_sum[buf][i][lane];
+    }
+    if (2 * s < kLanesWaves) __syncthreads();  // (read before the next level writes)
+  }
+  if (wave == 0 && on) {
+    double *o = partials + ((size_t)(w.pose0 + lane) * (size_t)rows + (size_t)w.row) * kAccSlots;
+#pragma unroll
+    for (int i = 0; i < kLanesVals; ++i) o[i] = v[i];
+#pragma unroll
+    for (int i = kLanesVals; i < kAccSlots; ++i) o[i] = 0.0;
+  }
+}
+
 // ---- cost-only pose-batched evaluation (ea_batch_cost_resident_poses) ---------------------------------------------------
 // What a ranking of candidate poses, a line search or a cost-surface probe asks for: 1/2 sum rho(r^2) and the failed-functor
 // count, nothing else.  ea_cost_poses_kernel takes ea_eval_poses_kernel's work items -- the same flat, XCD-dealt list, chunks,
@@ -2998,6 +3218,20 @@ hipError_t launch_eval_poses(const EvalLaunch &s, const PosesLaunch &p, const Pr
           return hipGetLastError();
         });
       }); }); });
+  }); });
+}
+
+// ea_eval_poses_lanes_kernel: the same launch with one pose per lane -- fp64 at the pose path's 256 x 2 shape only (the
+// row is that shape's 512-point chunk); everything else is refused
+hipError_t launch_eval_poses_lanes(const EvalLaunch &s, const PosesLaunch &p, const ProblemDesc *probs, const PoseState *poses,
+                                   double *partials, const PosesFold &fold, hipStream_t stream) {
+  if (!flat_launch_ok(s, p, 1) || fold.n < 0 || s.dtype != EA_F64 || s.nt != 64 * kLanesWaves || s.ppt != 2) return hipErrorInvalidValue;
+  const int shape = poses_shape(s.xcd_remap != 0, p.order, p.single != 0, fold.n);
+  const dim3 grid(poses_lanes_grid(p.rows, p.g, fold.n));
+  return dispatch_bool(s.buffer_loads, [&](auto BUF) { return dispatch_bool(s.img32, [&](auto IMG32) {
+    hipLaunchKernelGGL((ea_eval_poses_lanes_kernel<decltype(BUF)::value, decltype(IMG32)::value>), grid, dim3(64 * kLanesWaves), 0,
+                       stream, shape, p.g, p.rows, probs, poses, partials, fold);
+    return hipGetLastError();
   }); });
 }
 

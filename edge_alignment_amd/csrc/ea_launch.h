@@ -144,6 +144,10 @@ hipError_t launch_eval_poses_grid(const EvalLaunch &s, const ProblemDesc *probs,
 // has the batch's row table (PosesRow x rows, ea_poses_map.h) right in front of it
 hipError_t launch_eval_poses(const EvalLaunch &s, const PosesLaunch &p, const ProblemDesc *probs, const PoseState *poses,
                              double *partials, const PosesFold &fold, hipStream_t stream);
+// ea_eval_poses_lanes_kernel: that launch with one pose per lane (ea_poses_map.h: items are (row, 64 poses)); fp64 batches at
+// the 256 x 2 pose shape, the same tables, rows, riders and row indices; p.exchange is not read
+hipError_t launch_eval_poses_lanes(const EvalLaunch &s, const PosesLaunch &p, const ProblemDesc *probs, const PoseState *poses,
+                                   double *partials, const PosesFold &fold, hipStream_t stream);
 hipError_t launch_poses_fold(int nt, const PosesFold &fold, hipStream_t stream);
 // ea_cost_poses_kernel: the cost-only form of launch_eval_poses' launch (256-lane workgroups; no riders) -- one narrow
 // partial {cost, failed functors} of kCostPartialBytes per workgroup at pose * rows + row of `partials`.

@@ -82,4 +82,45 @@ EA_HD inline void poses_rider(int r, int count, int *pose, int *problem) { *pose
 EA_HD inline int poses_launches(int K, int G) { return (K + G - 1) / G; }
 EA_HD inline int poses_launch_size(int K, int G) { const int n = poses_launches(K, G); return (K + n - 1) / n; }
 
+// ---- one pose per lane (ea_eval_poses_lanes_kernel) ---------------------------------------------------------------------
+// The same launch with the mapping turned round: a work item is (row of a pose, GROUP of kPosesLanes consecutive poses of the
+// launch), lane l of every wavefront of the workgroup holds pose 64 group + l, and the row's sums never leave the lane.  The
+// list of items is the list above with `groups` in the place of g -- rider slots, the XCD deal of contiguous rows and both
+// item orders included -- so the functions above serve it unchanged; what is added is group -> (first pose, live lanes).
+// Partial row of lane l: (pose0 + l) * rows + row, the row the other kernel writes for that (pose, row).
+constexpr int kPosesLanes = 64;
+EA_HD inline int poses_lanes_groups(int g) { return (g + kPosesLanes - 1) / kPosesLanes; }
+EA_HD inline unsigned poses_lanes_grid(int rows, int g, int riders) { return poses_grid(rows, poses_lanes_groups(g), riders); }
+struct PosesLanesWork {
+  int kind;         // 0 = nothing, 1 = rider, 2 = evaluation item
+  int rider;        // kind 1
+  int row;          // kind 2: row of a pose,
+  int pose0, live;  //         first pose of the group and how many of its 64 lanes hold a pose of the launch (1..64)
+};
+EA_HD inline PosesLanesWork poses_lanes_work(unsigned L, int shape, int rows, int g, int riders) {
+  const PosesWork w = poses_work(L, shape, rows, poses_lanes_groups(g), riders);
+  PosesLanesWork o = {w.kind, w.rider, w.row, 0, 0};
+  if (w.kind == 2) {
+    o.pose0 = w.pose * kPosesLanes;
+    o.live = g - o.pose0 < kPosesLanes ? g - o.pose0 : kPosesLanes;
+  }
+  return o;
+}
+// kind 2 -> (term, chunk of the term, problems in the batch); lane l's pose slot is (pose0 + l) * count + term
+struct PosesLanesChunk { int term, chunk, count; };
+EA_HD inline PosesLanesChunk poses_lanes_chunk(int row, int shape, const PosesRow *table) {
+  PosesLanesChunk c = {0, row, 1};
+  if (!(shape & kPosesSingle)) {
+    const PosesRow r = table[row];
+    c.term = r.term; c.chunk = row - r.row0; c.count = r.count;
+  }
+  return c;
+}
+// G of this path: the bound (rows memory, tuning cap) rounded down to whole groups -- a launch that is not the call's last
+// leaves no lane idle -- and left alone below one group.  K poses then go in launches of G, the last takes the remainder:
+// with few, long workgroups a launch costs about ceil(items / CUs) workgroup lifetimes, and full launches in front keep
+// the sum of those at what one launch of K would cost (an even split can add a lifetime per launch).
+EA_HD inline int poses_lanes_group_size(int bound) { return bound >= kPosesLanes ? bound - bound % kPosesLanes : (bound > 1 ? bound : 1); }
+EA_HD inline int poses_lanes_launch_size(int K, int G) { return K < G ? K : G; }
+
 }  // namespace ea

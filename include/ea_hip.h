@@ -402,7 +402,8 @@ int ea_batch_residual_quantiles(ea_batch *b, const double *q, const double *t, c
  * 5e4-point pair from a few dozen poses on, against ~27 us through ea_batch_eval.  The sums of pose k are those
  * ea_batch_eval returns at pose k up to rounding (the pose-batched launch takes a throughput shape -- more points per
  * lane -- so the partial rows are cut differently, and the pose-dependent constants are built on the device); any split of
- * the K poses over launches gives the same bits.  Every kind of batch is covered (variant functors, shared-pose terms,
+ * the K poses over launches gives the same bits.  From 1024 poses on an fp64 batch is evaluated with one pose per lane
+ * (tuning key "poses_lane_per_pose" below).  Every kind of batch is covered (variant functors, shared-pose terms,
  * LDS staging). */
 int ea_batch_eval_poses(ea_batch *b, int K, const double *q, const double *t, double *cost, double *JtJ, double *Jtr,
                         int64_t *n_invalid);
@@ -425,7 +426,8 @@ int ea_batch_eval_resident_poses(ea_batch *b, double *cost, double *JtJ, double 
  * running and one step launch runs their state machines; finished starts leave the launches.  A start's result -- pose,
  * iterations, trace -- is bit for bit what the same start gives alone (K = 1): it does not depend on K, on the other starts,
  * on "poses_per_launch" or on when another start finished, and it_cost[0] is the cost ea_batch_eval_poses returns at the
- * start pose.  (Against ea_batch_solve from the same start the iterates agree up to rounding only: the pose-batched launch
+ * start pose -- to the bit where that call evaluates with the same kernel (fewer poses than the "poses_lane_per_pose"
+ * threshold, or the key at 0), to rounding above it.  (Against ea_batch_solve from the same start the iterates agree up to rounding only: the pose-batched launch
  * cuts the partial rows differently.)
  * Covered in lock-step: the batches ea_batch_eval_poses evaluates in its flat form -- plain functor, one term per problem,
  * any dtype -- at the pose path's default 256-thread shape; every other batch (variant functors, shared-pose terms, LDS
@@ -595,8 +597,17 @@ int ea_eval_rows_device(ea_problem *p, const double q[4], const double t[3], int
 /* ---- tuning ---------------------------------------------------------------------------- */
 /* tuning knobs: key in {"lds_bytes", "points_per_thread", "use_lds", "xcd_remap", "threads", "buffer_loads",
  * "solve_streams", "rows_staged", "rows_nontemporal", "wide_accumulate", "dt_f32", "poses_per_launch", "poll_results",
- * "fused_iterations", "zero_copy_poses", "starts_events", "cost_form", "poses_wave_exchange"};
+ * "fused_iterations", "zero_copy_poses", "starts_events", "cost_form", "poses_wave_exchange", "poses_lane_per_pose"};
  * value < 0 restores the default.
+ * "poses_lane_per_pose": which calls of ea_batch_eval_poses / ea_batch_eval_resident_poses evaluate with one pose per LANE
+ * (a lane owns a pose, the wavefront walks the points; no sum crosses lanes) instead of one point per lane: -1 (default) = from
+ * 1024 poses on, 0 = never, N >= 1 = from N poses on.  It applies to fp64 batches of the plain functor in the flat form (one
+ * term per problem, no LDS staging, no "wide_accumulate") at the pose path's 256 x 2 shape with at most 2048 partial rows per
+ * pose; every other batch keeps its kernel whatever the key says.  The choice follows from the batch and K alone, never from
+ * "poses_per_launch": on either path any split of the K poses over launches gives the same bits.  Between the paths the sums
+ * differ in the last places (another fixed summation order); n_invalid is equal.  On this path "poses_per_launch" is rounded
+ * down to a multiple of 64 (left alone below 64: launches of one partly filled group, slow).  Setting the key drops resident
+ * poses; ea_batch_get_info "poses_lane_per_pose" reports 1 if the last pose-batched call ran that kernel.
  * "poses_wave_exchange" = 0: the fp64 pose-batched evaluation in 256-lane workgroups (ea_batch_eval_poses, the evaluations of
  * ea_batch_solve_starts) reduces with one 32-value butterfly per wavefront; default 1: the four wavefronts of a workgroup
  * first add their sums lane by lane through LDS and each runs the butterfly over the 8 slots it is left with (another fixed
