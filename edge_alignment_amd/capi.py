@@ -51,6 +51,10 @@ EXPORTED = [
     "ea_default_frame_params", "ea_batch_set_frames", "ea_batch_set_frames_device",
     "ea_default_canny_frame_params", "ea_batch_set_frames_canny", "ea_batch_set_frames_canny_device",
     "ea_default_ros_frame_params", "ea_batch_set_frames_ros", "ea_batch_set_frames_ros_device",
+    "ea_tracker_batch_create", "ea_tracker_batch_destroy", "ea_tracker_batch_count", "ea_tracker_batch_problem",
+    "ea_tracker_batch_push_frames", "ea_tracker_batch_push_frames_device", "ea_tracker_batch_reset",
+    "ea_tracker_batch_set_covariance", "ea_tracker_batch_last_covariance", "ea_tracker_batch_set_motion_prior",
+    "ea_tracker_batch_get_info",
 ]
 
 # measurement hooks (edge_alignment_amd/csrc/ea_hip_dev.h): bound by bench.py, the A/B scripts and the tests that pin the
@@ -285,6 +289,20 @@ def load():
     L.ea_default_ros_frame_params.restype = None
     L.ea_batch_set_frames_ros.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(RosFrameParams)]
     L.ea_batch_set_frames_ros_device.argtypes = L.ea_batch_set_frames_ros.argtypes
+    L.ea_tracker_batch_create.argtypes = [C.POINTER(vp), C.POINTER(Camera), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.ea_tracker_batch_destroy.argtypes = [vp]
+    L.ea_tracker_batch_destroy.restype = None
+    L.ea_tracker_batch_count.argtypes = [vp]
+    L.ea_tracker_batch_problem.argtypes = [vp, C.c_int]
+    L.ea_tracker_batch_problem.restype = vp
+    L.ea_tracker_batch_push_frames.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_int, C.c_double, C.POINTER(Options),
+                                               dp, dp, C.POINTER(Summary), C.POINTER(C.c_int)]
+    L.ea_tracker_batch_push_frames_device.argtypes = L.ea_tracker_batch_push_frames.argtypes
+    L.ea_tracker_batch_reset.argtypes = [vp, C.c_int]
+    L.ea_tracker_batch_set_covariance.argtypes = [vp, covop]
+    L.ea_tracker_batch_last_covariance.argtypes = [vp, C.c_int, covp]
+    L.ea_tracker_batch_set_motion_prior.argtypes = [vp, C.c_double, C.c_double]
+    L.ea_tracker_batch_get_info.argtypes = [vp, C.c_char_p, i64p]
     _lib = L
     return L
 
@@ -859,6 +877,101 @@ class Tracker:
         if self._h:
             load().ea_tracker_destroy(self._h)
             self._h = C.c_void_p()
+
+
+class _StreamProblem(Problem):
+    """a problem owned by a TrackerBatch: every setter and read-back of Problem, no destruction"""
+
+    def __init__(self, handle, dtype, device):
+        self._h = C.c_void_p(handle)
+        self.dtype = dtype
+        self.device = device
+        self._keep = []
+
+    def close(self):
+        self._h = C.c_void_p()
+
+
+class TrackerBatch:
+    """Tracker for N streams pushed in lock-step (ea_tracker_batch_*): every pushed frame passes the batched producers once
+    and serves both sides, the aligned streams are solved by one batch solve.  cams: N (fx, fy, cx, cy); flavour 0 Laplacian,
+    1 Canny (depth uint16), 2 ROS (depth float32 in metres, the chain works at the extent >> halvings)."""
+
+    def __init__(self, cams, dtype=EA_F64, device=0, flavour=0, halvings=0, loss=None):
+        self._h = C.c_void_p()
+        cams = [tuple(float(v) for v in c) for c in cams]
+        arr = (Camera * max(len(cams), 1))(*[Camera(*c) for c in cams])
+        L = load()
+        _check(L.ea_tracker_batch_create(C.byref(self._h), arr, len(cams), dtype, device, flavour, halvings))
+        self.flavour, self.halvings, self.device = flavour, halvings, device
+        self.problems = [_StreamProblem(L.ea_tracker_batch_problem(self._h, i), dtype, device) for i in range(len(cams))]
+        if loss is not None:
+            for p in self.problems:
+                p.set_loss(loss[0], loss[1])
+
+    def __len__(self):
+        return len(self.problems)
+
+    def problem(self, i):
+        """stream i's problem: set_loss, set_loss_auto_scale, set_depth_weighting, set_constant_parameters, set_flavour;
+        get_points, get_weights, get_loss"""
+        return self.problems[i]
+
+    def push_frames(self, bgr, depth, z_scaling=5000.0, **opts):
+        """One frame per stream: sequences of len(self) frames or stacked arrays of one extent -- bgr (H, W, 3) uint8, depth
+        (H, W) uint16 (float32 for flavour 2).  numpy arrays take the host entry, torch tensors on the tracker's GPU the
+        device entry (read in place).  Returns q (N, 4), t (N, 3), [summary or None per stream], aligned (N,) int."""
+        sides = [("bgr", bgr, 3), ("depth", depth, 4 if self.flavour == 2 else 2)]
+        shape, on_device, arrays, keep = Batch._frame_arrays(self, sides)
+        n = len(self)
+        q, t = np.zeros((n, 4)), np.zeros((n, 3))
+        o = default_options(**opts)
+        sums = (Summary * n)()
+        aligned = np.zeros(n, dtype=np.int32)
+        if on_device:
+            import torch
+            torch.cuda.current_stream(self.device).synchronize()  # the frames must be complete: the producers do not wait for torch's stream
+        L = load()
+        fn = L.ea_tracker_batch_push_frames_device if on_device else L.ea_tracker_batch_push_frames
+        H, W = shape or (0, 0)
+        _check(fn(self._h, arrays["bgr"], arrays["depth"], H, W, float(z_scaling), C.byref(o), _dp(q), _dp(t), sums,
+                  aligned.ctypes.data_as(C.POINTER(C.c_int))))
+        return q, t, [summary_to_dict(sums[i]) if aligned[i] else None for i in range(n)], aligned
+
+    def reset(self, i=-1):
+        """stream i (default: every stream) forgets its reference and its prior"""
+        _check(load().ea_tracker_batch_reset(self._h, int(i)))
+
+    def set_covariance(self, enabled=True, **opts):
+        o = covariance_options(**opts) if enabled else None
+        _check(load().ea_tracker_batch_set_covariance(self._h, C.byref(o) if o is not None else None))
+
+    def last_covariance(self, i):
+        """stream i's covariance of the last push (covariance_to_dict); EAError(EA_ERR_STATE) when it was not aligned"""
+        c = Covariance()
+        _check(load().ea_tracker_batch_last_covariance(self._h, int(i), C.byref(c)))
+        return covariance_to_dict(c)
+
+    def set_motion_prior(self, sigma_rot, sigma_trans):
+        _check(load().ea_tracker_batch_set_motion_prior(self._h, float(sigma_rot), float(sigma_trans)))
+
+    def info(self, key):
+        v = C.c_int64()
+        _check(load().ea_tracker_batch_get_info(self._h, key.encode(), C.byref(v)))
+        return v.value
+
+    def close(self):
+        if self._h:
+            for p in self.problems:
+                p.close()
+            load().ea_tracker_batch_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def solve_pyramid(levels, q, t, **opts):

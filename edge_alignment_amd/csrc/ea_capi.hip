@@ -479,7 +479,7 @@ extern "C" void ea_default_options(ea_options *o) {
 // ceres::Solver::Options::IsValid for the fields carried here (solver.cc: OPTION_GE / OPTION_GT / OPTION_LE_OPTION);
 // written so that a NaN fails every test.  Ceres ends such a Solve with FAILURE before touching the problem; the C-ABI
 // returns EA_ERR_INVALID_ARG and leaves q, t and the summary alone.
-static int check_options(const ea_options &o) {
+int ea::check_options(const ea_options &o) {
   if (!(o.max_num_iterations >= 0)) return fail(EA_ERR_INVALID_ARG, "max_num_iterations < 0");
   if (o.strategy != EA_STRATEGY_LM && o.strategy != EA_STRATEGY_DOGLEG)
     return fail(EA_ERR_INVALID_ARG, "unknown trust-region strategy");

@@ -109,6 +109,8 @@ inline int term_variant(const ea_problem *p) { return p->variant | (p->weighted 
 // the problem's padded W x H image (and its float32 mirror for fp64 problems), reusing an allocation that fits
 int alloc_dt(ea_problem *p, int W, int H);
 int check_cov_options(const ea_covariance_options *o);
+// the solve options' validity (every solve checks them itself; the multi-stream tracker checks before it touches a stream)
+int check_options(const ea_options &o);
 
 // What ea_batch_set_frames (ea_frames.hip) needs of a batch, whose layout stays ea_capi.hip's: its problems in batch order and
 // its device; and the batch-owned memory of the batched producers -- one device block and one pinned staging block of at least

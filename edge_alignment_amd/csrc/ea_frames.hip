@@ -2,7 +2,8 @@
 // ea_problem_set_{ref,now}_frame* (raw images -> edge points / DT image through the kernels of ea_preprocess.hip, in a
 // workspace laid out by ea_frame_ws.h), their batched forms ea_batch_set_frames[_canny|_ros][_device] (N frame pairs, the
 // frame a grid dimension of every launch), ea_resize_half, the read-backs ea_problem_get_points / _get_dt, and the frame-to-frame
-// tracker ea_tracker_*.  Host code only: this file holds no kernel.
+// tracker ea_tracker_* with its multi-stream form ea_tracker_batch_* (N streams through the batched producers, each frame
+// processed once for both sides, one batch solve).  Host code only: this file holds no kernel.
 
 #include <hip/hip_runtime.h>
 
@@ -158,6 +159,27 @@ struct ea_tracker {
   PriorDesc installed = {};
 };
 
+// The motion prior of the trackers (ea_tracker_set_motion_prior): NormalPriors centred on the constant-velocity prediction
+// q, t the solve starts from, A = I / sigma (0 = that block off); they replace the caller's priors on the problem.
+static int motion_prior_install(ea_problem *p, double sigma_rot, double sigma_trans, const double q[4], const double t[3]) {
+  double Aq[16] = {0}, At[9] = {0};
+  for (int i = 0; i < 4; ++i) Aq[5 * i] = sigma_rot > 0.0 ? 1.0 / sigma_rot : 0.0;
+  for (int i = 0; i < 3; ++i) At[4 * i] = sigma_trans > 0.0 ? 1.0 / sigma_trans : 0.0;
+  const int rc = ea_problem_set_normal_prior(p, 0, sigma_rot > 0.0 ? Aq : nullptr, 4, q);
+  return rc != EA_OK ? rc : ea_problem_set_normal_prior(p, 1, sigma_trans > 0.0 ? At : nullptr, 3, t);
+}
+// off again: a block still holding the prior a tracker installed (`ins`) is cleared; one the caller has set since is kept
+static void motion_prior_clear(ea_problem *p, const PriorDesc &ins) {
+  const PriorDesc &cur = p->prior;
+  if (cur.has_q && ins.has_q && std::memcmp(cur.Hq, ins.Hq, sizeof(cur.Hq)) == 0 && std::memcmp(cur.bq, ins.bq, sizeof(cur.bq)) == 0)
+    (void)ea_problem_set_normal_prior(p, 0, nullptr, 0, nullptr);
+  if (cur.has_t && ins.has_t && std::memcmp(cur.Ht, ins.Ht, sizeof(cur.Ht)) == 0 && std::memcmp(cur.bt, ins.bt, sizeof(cur.bt)) == 0)
+    (void)ea_problem_set_normal_prior(p, 1, nullptr, 0, nullptr);
+}
+static bool sigmas_ok(double sigma_rot, double sigma_trans) {
+  return sigma_rot >= 0.0 && sigma_rot <= DBL_MAX && sigma_trans >= 0.0 && sigma_trans <= DBL_MAX;
+}
+
 extern "C" int ea_tracker_create(ea_tracker **out, const ea_camera *cam, int dtype, int device, int flavour) {
   if (!out) return fail(EA_ERR_INVALID_ARG, "NULL argument");
   if (flavour != 0 && flavour != 1) return fail(EA_ERR_INVALID_ARG, "unknown pre-processing flavour");
@@ -206,12 +228,7 @@ extern "C" int ea_tracker_push_frame(ea_tracker *tr, const uint8_t *bgr, const u
     std::memcpy(q, tr->q, sizeof(q));
     std::memcpy(t, tr->t, sizeof(t));
     if (tr->sigma_rot > 0.0 || tr->sigma_trans > 0.0) {
-      // the motion prior: centred on the constant-velocity prediction the solve starts from (replaces the caller's priors)
-      double Aq[16] = {0}, At[9] = {0};
-      for (int i = 0; i < 4; ++i) Aq[5 * i] = tr->sigma_rot > 0.0 ? 1.0 / tr->sigma_rot : 0.0;
-      for (int i = 0; i < 3; ++i) At[4 * i] = tr->sigma_trans > 0.0 ? 1.0 / tr->sigma_trans : 0.0;
-      rc = ea_problem_set_normal_prior(tr->p, 0, tr->sigma_rot > 0.0 ? Aq : nullptr, 4, q);
-      if (rc == EA_OK) rc = ea_problem_set_normal_prior(tr->p, 1, tr->sigma_trans > 0.0 ? At : nullptr, 3, t);
+      rc = motion_prior_install(tr->p, tr->sigma_rot, tr->sigma_trans, q, t);
       if (rc != EA_OK) {
         if (job.started) (void)hipDeviceSynchronize();
         return rc;
@@ -286,15 +303,9 @@ extern "C" int ea_tracker_set_covariance(ea_tracker *tr, const ea_covariance_opt
 
 extern "C" int ea_tracker_set_motion_prior(ea_tracker *tr, double sigma_rot, double sigma_trans) {
   if (!tr) return fail(EA_ERR_INVALID_ARG, "NULL argument");
-  if (!(sigma_rot >= 0.0 && sigma_rot <= DBL_MAX) || !(sigma_trans >= 0.0 && sigma_trans <= DBL_MAX))
-    return fail(EA_ERR_INVALID_ARG, "sigmas must be finite and >= 0");
+  if (!sigmas_ok(sigma_rot, sigma_trans)) return fail(EA_ERR_INVALID_ARG, "sigmas must be finite and >= 0");
   if (sigma_rot == 0.0 && sigma_trans == 0.0 && tr->motion_set) {
-    // off again: a block still holding the prior this tracker installed is cleared; one the caller has set since is kept
-    const PriorDesc &cur = tr->p->prior, &ins = tr->installed;
-    if (cur.has_q && ins.has_q && std::memcmp(cur.Hq, ins.Hq, sizeof(cur.Hq)) == 0 && std::memcmp(cur.bq, ins.bq, sizeof(cur.bq)) == 0)
-      (void)ea_problem_set_normal_prior(tr->p, 0, nullptr, 0, nullptr);
-    if (cur.has_t && ins.has_t && std::memcmp(cur.Ht, ins.Ht, sizeof(cur.Ht)) == 0 && std::memcmp(cur.bt, ins.bt, sizeof(cur.bt)) == 0)
-      (void)ea_problem_set_normal_prior(tr->p, 1, nullptr, 0, nullptr);
+    motion_prior_clear(tr->p, tr->installed);
     tr->motion_set = false;
   }
   tr->sigma_rot = sigma_rot;
@@ -859,18 +870,29 @@ static int upload_frames(const BatchFrames &j, const WsRegion<U> &r, const V *co
 }
 
 // count -> scan on every frame's `edges` region, the totals back into h_totals in one strided copy (a wait)
-static int batch_counts_back(BatchFrames *j, const WsRegion<uint8_t> &edges, int threshold) {
-  const FrameWs &ws = j->ws;
-  HIPCHK(launch_edge_count_scan_frames(j->f, edges.at(j->base), threshold, ws.counts.at(j->base), nullptr));
-  HIPCHK(hipMemcpy2D(j->h_totals, sizeof(int), ws.counts.at(j->base) + frame_ws_blocks(j->H, j->W), j->stride, sizeof(int), j->n,
+// (the two steps apart: the multi-stream tracker queues the first in front of its solve and fetches behind it)
+static int batch_counts_queue(BatchFrames *j, const WsRegion<uint8_t> &edges, int threshold) {
+  HIPCHK(launch_edge_count_scan_frames(j->f, edges.at(j->base), threshold, j->ws.counts.at(j->base), nullptr));
+  return EA_OK;
+}
+static int batch_counts_fetch(BatchFrames *j) {
+  HIPCHK(hipMemcpy2D(j->h_totals, sizeof(int), j->ws.counts.at(j->base) + frame_ws_blocks(j->H, j->W), j->stride, sizeof(int), j->n,
                      hipMemcpyDeviceToHost));
   return EA_OK;
 }
+static int batch_counts_back(BatchFrames *j, const WsRegion<uint8_t> &edges, int threshold) {
+  const int rc = batch_counts_queue(j, edges, threshold);
+  return rc != EA_OK ? rc : batch_counts_fetch(j);
+}
 
 // Reference side, first half: the counts, room for each problem's points and their arrays into its slot
+static int batch_ref_room(BatchFrames *j);
 static int batch_ref_counts(BatchFrames *j, const WsRegion<uint8_t> &edges, int threshold) {
   const int rc_counts = batch_counts_back(j, edges, threshold);
-  if (rc_counts != EA_OK) return rc_counts;
+  return rc_counts != EA_OK ? rc_counts : batch_ref_room(j);
+}
+// (the counts are in h_totals)
+static int batch_ref_room(BatchFrames *j) {
   for (size_t i = 0; i < j->n; ++i) {
     ea_problem *p = j->probs[i];
     const int total = j->h_totals[i];
@@ -1202,6 +1224,405 @@ extern "C" int ea_batch_set_frames_ros(ea_batch *b, const uint8_t *const *ref_bg
 extern "C" int ea_batch_set_frames_ros_device(ea_batch *b, const uint8_t *const *ref_bgr, const float *const *ref_depth,
                                               const uint8_t *const *now_bgr, const ea_ros_frame_params *prm) {
   return batch_set_frames_ros(b, ref_bgr, ref_depth, now_bgr, prm, true);
+}
+
+// ---- the multi-stream tracker: ea_tracker for N streams pushed in lock-step, on the batched producers and ONE batch solve ----
+//
+// Every pushed frame passes the edge detection once (launch_edge_strength_frames / launch_canny_frames, the frame a grid
+// dimension) and what that leaves in its workspace serves both sides: the current-side tail (threshold + chamfer, or the exact
+// transform, then the store into the stream's image) and, behind the solve, the reference-side tail (count, scan, scatter,
+// depth weights).  Both sides of a slot name the same frame, so every step is a kernel the batched producers have already.
+// The sequence of a push, all on the null stream but the solve:
+//   table and frames up (device frames: read in place) [-> ROS: halvings] -> edge pass -> [ROS: count + scan, the counts back
+//   (wait): a frame without an edge has no image] -> chamfer / exact transform -> store -> wait (the images are complete)
+//   -> [Laplacian, Canny: count + scan queued, it runs beside the solve] -> ea_batch_solve of the aligned streams on the
+//   batch's own streams [-> ea_batch_covariance] -> [Laplacian, Canny: the counts back (wait)] -> room for the points ->
+//   table up -> scatter -> depth weights -> wait.
+// (The ROS chain needs its counts before the transform, and its count has no depth test: the same counts serve the scatter.)
+// Waits per push outside the solve: the hysteresis looks (Canny, ROS), the images, the counts, the end.
+
+namespace {
+struct TrackerStream {
+  int frames = 0;
+  double q[4] = {1, 0, 0, 0}, t[3] = {0, 0, 0};
+  bool cov_valid = false;
+  ea_covariance cov_last{};
+  bool motion_set = false;
+  PriorDesc installed = {};
+};
+}  // namespace
+
+struct ea_tracker_batch {
+  std::vector<ea_problem *> probs;
+  std::vector<TrackerStream> st;
+  ea_batch *b = nullptr;    // every stream: the frame workspace is this batch's, and so is the solve when all are aligned
+  std::vector<std::pair<std::vector<int>, ea_batch *>> subs;  // (streams, their batch): the solves of fewer than all streams
+  int flavour = 0, halvings = 0, device = 0;
+  bool cov_on = false;
+  ea_covariance_options cov_opt{};
+  double sigma_rot = 0.0, sigma_trans = 0.0;
+  // ea_tracker_batch_get_info
+  int last_aligned = 0, last_bare = 0, last_rounds = 0, last_edge_passes = 0;
+  int64_t pushes = 0;
+};
+
+extern "C" int ea_tracker_batch_create(ea_tracker_batch **out, const ea_camera *cams, int count, int dtype, int device, int flavour,
+                                       int halvings) {
+  if (!out || !cams) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (count < 1 || count > 65535) return fail(EA_ERR_INVALID_ARG, "a multi-stream tracker takes 1..65535 streams");
+  if (flavour < 0 || flavour > 2) return fail(EA_ERR_INVALID_ARG, "unknown pre-processing flavour");
+  if (halvings < 0 || halvings > 8) return fail(EA_ERR_INVALID_ARG, "halvings out of range");
+  if (flavour != 2 && halvings != 0) return fail(EA_ERR_INVALID_ARG, "halvings belong to the ROS flavour (2) only");
+  ea_tracker_batch *tb = new (std::nothrow) ea_tracker_batch;
+  if (!tb) return fail(EA_ERR_ALLOC, "out of host memory");
+  tb->flavour = flavour; tb->halvings = halvings; tb->device = device;
+  int rc = EA_OK;
+  for (int i = 0; i < count && rc == EA_OK; ++i) {
+    ea_problem *p = nullptr;
+    rc = ea_problem_create(&p, cams + i, dtype, device);
+    if (rc == EA_OK) tb->probs.push_back(p);
+  }
+  if (rc == EA_OK) rc = ea_batch_create(&tb->b, tb->probs.data(), count);
+  if (rc != EA_OK) { ea_tracker_batch_destroy(tb); return rc; }
+  tb->st.resize((size_t)count);
+  *out = tb;
+  return EA_OK;
+}
+
+extern "C" void ea_tracker_batch_destroy(ea_tracker_batch *tb) {
+  if (!tb) return;
+  for (auto &s : tb->subs) ea_batch_destroy(s.second);
+  ea_batch_destroy(tb->b);
+  for (ea_problem *p : tb->probs) ea_problem_destroy(p);
+  delete tb;
+}
+
+extern "C" int ea_tracker_batch_count(const ea_tracker_batch *tb) { return tb ? (int)tb->probs.size() : 0; }
+
+extern "C" ea_problem *ea_tracker_batch_problem(ea_tracker_batch *tb, int i) {
+  return tb && i >= 0 && (size_t)i < tb->probs.size() ? tb->probs[(size_t)i] : nullptr;
+}
+
+// a stream without a reference: the next push starts a fresh chain for it
+static void tracker_stream_drop(ea_tracker_batch *tb, size_t i) {
+  (void)reserve_points(tb->probs[i], 0);
+  tb->probs[i]->version++;
+  tb->st[i].frames = 0;
+  tb->st[i].cov_valid = false;
+}
+
+// A push that failed past its checks: some streams' images are the new frame's, some references may be, nothing says which.
+// Nothing of the push stays in flight, and every stream starts a fresh chain.
+static int tracker_batch_fail(ea_tracker_batch *tb, int rc) {
+  const std::string why = ea_last_error();  // (the clean-up below may not overwrite what failed)
+  (void)hipDeviceSynchronize();
+  (void)hipGetLastError();
+  for (size_t i = 0; i < tb->probs.size(); ++i) tracker_stream_drop(tb, i);
+  tb->last_aligned = 0;
+  return fail(rc, why);
+}
+
+// the batch that solves exactly the streams in `members`: the tracker's own when that is all of them, else one of the few
+// sub-batches it keeps (the same streams tend to be aligned push after push; the oldest makes room)
+static int tracker_batch_solver(ea_tracker_batch *tb, const std::vector<int> &members, ea_batch **out) {
+  if (members.size() == tb->probs.size()) { *out = tb->b; return EA_OK; }
+  for (size_t k = 0; k < tb->subs.size(); ++k)
+    if (tb->subs[k].first == members) { *out = tb->subs[k].second; return EA_OK; }
+  constexpr size_t kKeptSubBatches = 4;
+  if (tb->subs.size() >= kKeptSubBatches) {
+    ea_batch_destroy(tb->subs.front().second);
+    tb->subs.erase(tb->subs.begin());
+  }
+  std::vector<ea_problem *> probs;
+  for (int i : members) probs.push_back(tb->probs[(size_t)i]);
+  ea_batch *sub = nullptr;
+  const int rc = ea_batch_create(&sub, probs.data(), (int)probs.size());
+  if (rc != EA_OK) return rc;
+  tb->subs.emplace_back(members, sub);
+  *out = sub;
+  return EA_OK;
+}
+
+// The aligned streams in the groups that are solved together.  A batch runs ONE kernel family for all its problems: a problem
+// with per-point weights, distortion or a second camera puts its neighbours on the variant kernels, whose sums agree with the
+// plain kernels' to rounding only.  Streams are therefore grouped by what their own problem needs (term_variant), so that each
+// is solved by the kernels, and to the bits, of a tracker of its own; a problem with further terms is a group by itself.
+// Streams with the same settings -- the usual case -- are one group: one solve.
+static std::vector<std::vector<int>> tracker_batch_groups(const ea_tracker_batch *tb, const std::vector<int> &al) {
+  std::vector<std::vector<int>> groups;
+  std::vector<int> keys;
+  for (int i : al) {
+    const ea_problem *p = tb->probs[(size_t)i];
+    const int key = p->terms.empty() ? term_variant(p) : -1 - i;
+    size_t g = 0;
+    while (g < keys.size() && keys[g] != key) ++g;
+    if (g == keys.size()) { keys.push_back(key); groups.emplace_back(); }
+    groups[g].push_back(i);
+  }
+  return groups;
+}
+
+static int tracker_batch_push(ea_tracker_batch *tb, const uint8_t *const *bgr, const void *const *depth, int height, int width,
+                              double z_scaling, const ea_options *opt, double *q_rel, double *t_rel, ea_summary *summaries,
+                              int *aligned, bool on_device) {
+  // every check comes before a device or a stream is touched: a rejected call leaves the tracker as it was
+  if (!tb || !bgr || !depth || !q_rel || !t_rel) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  const bool ros = tb->flavour == 2;
+  if (height < 3 || width < 3 || height > 32768 || width > 32768 || (int64_t)height * width > 0x3fffffff)
+    return fail(EA_ERR_INVALID_ARG, "image extent out of range");
+  int rc = check_scaled_args(height, width, tb->halvings);
+  if (rc != EA_OK) return rc;
+  const int H = height >> tb->halvings, W = width >> tb->halvings;
+  int lo = 0, hi = 0;
+  rc = tb->flavour == 0 ? EA_OK : ros ? ros_thresholds(150.0, 100.0, &lo, &hi) : canny_thresholds(30.0, 90.0, &lo, &hi);
+  if (rc != EA_OK) return rc;
+  // (as the producers of ea_tracker's flavours: the Canny reference refuses an infinite z_scaling, the Laplacian one takes it)
+  if (tb->flavour == 1 && !(z_scaling <= DBL_MAX)) return fail(EA_ERR_INVALID_ARG, "z_scaling must be > 0 and finite");
+  if (opt) {
+    rc = check_options(*opt);
+    if (rc != EA_OK) return rc;
+  }
+  BatchFrames j;
+  j.ros = ros; j.full_H = height; j.full_W = width; j.halvings = tb->halvings;
+  // (both sides of every slot are the pushed frame: `bgr` is the reference side's colour frame and the current side's)
+  rc = batch_frames_check(tb->b, bgr, depth, ros ? sizeof(float) : 2, bgr, nullptr, H, W, ros ? 1.0 : z_scaling, on_device, &j);
+  if (rc != EA_OK) return rc;
+
+  const size_t n = tb->probs.size();
+  tb->pushes++;
+  tb->last_aligned = tb->last_bare = tb->last_rounds = tb->last_edge_passes = 0;
+  for (size_t i = 0; i < n; ++i) tb->st[i].cov_valid = false;
+  if (aligned) std::fill(aligned, aligned + n, 0);
+  if (summaries) std::memset(summaries, 0, n * sizeof(*summaries));
+  auto failed = [tb](int code) { return tracker_batch_fail(tb, code); };
+#define TBCHK(expr)                                                                                              \
+  do {                                                                                                           \
+    const hipError_t e_ = (expr);                                                                                \
+    if (e_ != hipSuccess) { (void)fail(EA_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); return failed(EA_ERR_HIP); } \
+  } while (0)
+#define TBRC(expr)                      \
+  do {                                  \
+    const int rc_ = (expr);             \
+    if (rc_ != EA_OK) return failed(rc_); \
+  } while (0)
+
+  TBRC(batch_frames_begin(tb->b, bgr, depth, bgr, nullptr, &j));
+  const FrameWs &ws = j.ws;
+  unsigned char *base = j.base;
+  int looks = 0;
+  const WsRegion<uint8_t> &edges = tb->flavour == 0 ? ws.lap : ws.edges;  // what the reference side counts and scatters
+  const int ref_threshold = tb->flavour == 0 ? 35 : 0;
+  auto canny = [&](int l2_bgr) {
+    const hipError_t e = launch_canny_frames(j.f, 1, 0, lo, hi, l2_bgr, ws.gray.at(base), ws.mag.at(base), ws.dir.at(base),
+                                             ws.label.at(base), ws.edges.at(base), ws.inv.at(base), ws.changed.at(base), j.h_flags,
+                                             &looks, nullptr);
+    if (e == hipSuccess) { tb->last_rounds += looks; batch_frames_set_rounds(tb->b, tb->last_rounds); }
+    return e;
+  };
+  // ---- the frame, once: edge pass and the current-side tail into every stream's image
+  if (!ros) {
+    TBRC(batch_alloc_dts(&j));
+    TBCHK(upload_table(&j));
+    if (!on_device) {
+      TBRC(upload_frames(j, ws.bgr, bgr, j.np * 3));
+      TBRC(upload_frames(j, ws.depth, depth, j.np * 2));
+    }
+    tb->last_edge_passes++;
+    if (tb->flavour == 0) {
+      TBCHK(launch_edge_strength_frames(j.f, 1, ws.gray.at(base), ws.lap.at(base), nullptr));
+      TBCHK(launch_threshold_median_frames(j.f, ws.lap.at(base), 35, 1, ws.mask.at(base), nullptr));
+      TBCHK(launch_chamfer_frames(j.f, ws.mask.at(base), ws.G.at(base), ws.scan.at(base), ws.dist.at(base), nullptr, ws.minmax.at(base), nullptr));
+    } else {
+      TBCHK(canny(0));
+      TBCHK(launch_chamfer_frames(j.f, ws.inv.at(base), ws.G.at(base), ws.scan.at(base), ws.dist.at(base), nullptr, ws.minmax.at(base), nullptr));
+    }
+    TBCHK(launch_dt_store_frames(j.dtype, j.f, ws.dist.at(base), ws.minmax.at(base), 1, 0.0, 1.0, nullptr));
+  } else {
+    TBCHK(upload_table(&j));
+    TBRC(batch_stage_ros(j, 0, bgr, reinterpret_cast<const float *const *>(depth)));
+    tb->last_edge_passes++;
+    TBCHK(canny(1));
+    TBRC(batch_counts_back(&j, ws.edges, 0));
+    j.no_image.assign(n, 0);
+    for (size_t i = 0; i < n; ++i)
+      if (j.h_totals[i] == 0) { j.no_image[i] = 1; tb->last_bare++; }
+    batch_frames_set_without_edges(tb->b, tb->last_bare);
+    TBRC(batch_alloc_dts(&j));
+    if ((size_t)tb->last_bare < n) {
+      TBCHK(upload_table(&j));
+      TBCHK(launch_chamfer_frames(j.f, ws.inv.at(base), ws.G.at(base), ws.scan.at(base), ws.dist.at(base), ws.dist.at<float>(base),
+                                  ws.minmax.at(base), nullptr));
+      TBCHK(launch_dt_store_stack(j.dtype, j.f, ws.dist.at<float>(base), ws.minmax.at(base), 1, 0.0, 255.0, nullptr));
+    }
+  }
+  // the images are complete before a solve reads them on the batch's streams, which do not wait for the null stream
+  TBCHK(hipStreamSynchronize(nullptr));
+  for (size_t i = 0; i < n; ++i)
+    if (j.no_image.empty() || !j.no_image[i]) dt_landed(tb->probs[i]);
+  // the frame's edge pixels are counted WHILE the previous references are solved against the images just produced (null
+  // stream beside the solve's non-blocking streams; neither touches what the other uses)
+  if (!ros) TBRC(batch_counts_queue(&j, edges, ref_threshold));
+
+  // ---- the solve of the aligned streams, from their last relative poses
+  std::vector<int> al;
+  for (size_t i = 0; i < n; ++i)
+    if (tb->st[i].frames > 0 && tb->probs[i]->n > 0 && (j.no_image.empty() || !j.no_image[i])) al.push_back((int)i);
+  const size_t na = al.size();
+  // per stream: the pose its solve started from and the one it returned
+  std::vector<double> q0(4 * n), t0(3 * n), qs(4 * n), ts(3 * n);
+  for (int i : al) {
+    TrackerStream &s = tb->st[(size_t)i];
+    std::memcpy(&q0[4 * (size_t)i], s.q, sizeof(s.q));
+    std::memcpy(&t0[3 * (size_t)i], s.t, sizeof(s.t));
+    if (tb->sigma_rot > 0.0 || tb->sigma_trans > 0.0) {
+      TBRC(motion_prior_install(tb->probs[(size_t)i], tb->sigma_rot, tb->sigma_trans, s.q, s.t));
+      s.motion_set = true;
+      s.installed = tb->probs[(size_t)i]->prior;
+    }
+  }
+  for (const std::vector<int> &grp : tracker_batch_groups(tb, al)) {
+    const size_t ng = grp.size();
+    ea_batch *solver = nullptr;
+    TBRC(tracker_batch_solver(tb, grp, &solver));
+    std::vector<double> qg(4 * ng), tg(3 * ng);
+    std::vector<ea_summary> sg(ng);
+    for (size_t k = 0; k < ng; ++k) {
+      std::memcpy(&qg[4 * k], &q0[4 * (size_t)grp[k]], 4 * sizeof(double));
+      std::memcpy(&tg[3 * k], &t0[3 * (size_t)grp[k]], 3 * sizeof(double));
+    }
+    TBRC(ea_batch_solve(solver, opt, qg.data(), tg.data(), sg.data()));
+    size_t ok = 0;
+    for (size_t k = 0; k < ng; ++k) {
+      const size_t i = (size_t)grp[k];
+      if (summaries) summaries[i] = sg[k];
+      const bool failure = sg[k].termination == EA_FAILURE;
+      ok += failure ? 0 : 1;
+      // (a failed solve: the stream keeps its prior, and the covariance call below sees it at its start pose)
+      std::memcpy(&qs[4 * i], failure ? &q0[4 * i] : &qg[4 * k], 4 * sizeof(double));
+      std::memcpy(&ts[3 * i], failure ? &t0[3 * i] : &tg[3 * k], 3 * sizeof(double));
+      std::memcpy(&qg[4 * k], &qs[4 * i], 4 * sizeof(double));
+      std::memcpy(&tg[3 * k], &ts[3 * i], 3 * sizeof(double));
+    }
+    if (tb->cov_on) {
+      // At the returned poses, from the points and images the solve used: ea_batch_covariance returns once its results have
+      // landed, the scatter that overwrites the points is queued behind that.  A failed solve has no pose to take one at:
+      // its stream reports why = 4.
+      std::vector<ea_covariance> covs(ng);
+      std::memset(covs.data(), 0, ng * sizeof(ea_covariance));
+      if (ok > 0) TBRC(ea_batch_covariance(solver, qg.data(), tg.data(), &tb->cov_opt, covs.data()));
+      for (size_t k = 0; k < ng; ++k) {
+        TrackerStream &s = tb->st[(size_t)grp[k]];
+        s.cov_last = covs[k];
+        if (sg[k].termination == EA_FAILURE) {
+          std::memset(&s.cov_last, 0, sizeof(s.cov_last));
+          s.cov_last.why = 4;
+        }
+        s.cov_valid = true;
+      }
+    }
+  }
+
+  // ---- the frame's edge points become every stream's reference
+  if (!ros) TBRC(batch_counts_fetch(&j));
+  TBRC(batch_ref_room(&j));
+  TBCHK(upload_table(&j));
+  if (ros) {
+    if (j.max_total > 0) TBCHK(launch_edge_scatter_ros_stack(j.dtype, j.f, ws.edges.at(base), ws.counts.at(base), nullptr));
+    TBCHK(launch_depth_weights_frames(j.dtype, j.f, j.max_weighted, nullptr));
+  } else {
+    TBRC(batch_ref_scatter(j, edges, ref_threshold, z_scaling));
+  }
+  TBCHK(hipDeviceSynchronize());
+#undef TBCHK
+#undef TBRC
+  for (size_t i = 0; i < n; ++i) ref_points_landed(tb->probs[i], j.slots[i].capacity);
+  // priors and frame counts advance only with the new references in place
+  for (int a : al) {
+    const size_t i = (size_t)a;
+    std::memcpy(tb->st[i].q, &qs[4 * i], sizeof(tb->st[i].q));
+    std::memcpy(tb->st[i].t, &ts[3 * i], sizeof(tb->st[i].t));
+    if (aligned) aligned[i] = 1;
+  }
+  for (size_t i = 0; i < n; ++i) {
+    std::memcpy(q_rel + 4 * i, tb->st[i].q, sizeof(tb->st[i].q));
+    std::memcpy(t_rel + 3 * i, tb->st[i].t, sizeof(tb->st[i].t));
+    tb->st[i].frames += 1;
+  }
+  tb->last_aligned = (int)na;
+  return EA_OK;
+}
+
+extern "C" int ea_tracker_batch_push_frames(ea_tracker_batch *tb, const uint8_t *const *bgr, const void *const *depth, int height,
+                                            int width, double z_scaling, const ea_options *opt, double *q_rel, double *t_rel,
+                                            ea_summary *summaries, int *aligned) {
+  return tracker_batch_push(tb, bgr, depth, height, width, z_scaling, opt, q_rel, t_rel, summaries, aligned, false);
+}
+
+extern "C" int ea_tracker_batch_push_frames_device(ea_tracker_batch *tb, const uint8_t *const *bgr, const void *const *depth,
+                                                   int height, int width, double z_scaling, const ea_options *opt, double *q_rel,
+                                                   double *t_rel, ea_summary *summaries, int *aligned) {
+  return tracker_batch_push(tb, bgr, depth, height, width, z_scaling, opt, q_rel, t_rel, summaries, aligned, true);
+}
+
+extern "C" int ea_tracker_batch_reset(ea_tracker_batch *tb, int i) {
+  if (!tb) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (i >= (int)tb->probs.size()) return fail(EA_ERR_INVALID_ARG, "no such stream");
+  HIPCHK(hipSetDevice(tb->device));
+  for (size_t s = 0; s < tb->probs.size(); ++s) {
+    if (i >= 0 && s != (size_t)i) continue;
+    tracker_stream_drop(tb, s);
+    const double q[4] = {1, 0, 0, 0};
+    std::memcpy(tb->st[s].q, q, sizeof(q));
+    std::memset(tb->st[s].t, 0, sizeof(tb->st[s].t));
+  }
+  return EA_OK;
+}
+
+extern "C" int ea_tracker_batch_set_covariance(ea_tracker_batch *tb, const ea_covariance_options *o) {
+  if (!tb) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (o) {
+    const int rc = check_cov_options(o);
+    if (rc != EA_OK) return rc;
+    tb->cov_opt = *o;
+  }
+  tb->cov_on = o != nullptr;
+  for (TrackerStream &s : tb->st) s.cov_valid = false;
+  return EA_OK;
+}
+
+extern "C" int ea_tracker_batch_last_covariance(ea_tracker_batch *tb, int i, ea_covariance *out) {
+  if (!tb || !out) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (i < 0 || (size_t)i >= tb->st.size()) return fail(EA_ERR_INVALID_ARG, "no such stream");
+  if (!tb->cov_on) return fail(EA_ERR_STATE, "covariance is off (ea_tracker_batch_set_covariance)");
+  if (!tb->st[(size_t)i].cov_valid) return fail(EA_ERR_STATE, "the last push did not align this stream");
+  *out = tb->st[(size_t)i].cov_last;
+  return EA_OK;
+}
+
+extern "C" int ea_tracker_batch_set_motion_prior(ea_tracker_batch *tb, double sigma_rot, double sigma_trans) {
+  if (!tb) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (!sigmas_ok(sigma_rot, sigma_trans)) return fail(EA_ERR_INVALID_ARG, "sigmas must be finite and >= 0");
+  if (sigma_rot == 0.0 && sigma_trans == 0.0)
+    for (size_t i = 0; i < tb->st.size(); ++i)
+      if (tb->st[i].motion_set) {
+        motion_prior_clear(tb->probs[i], tb->st[i].installed);
+        tb->st[i].motion_set = false;
+      }
+  tb->sigma_rot = sigma_rot;
+  tb->sigma_trans = sigma_trans;
+  return EA_OK;
+}
+
+extern "C" int ea_tracker_batch_get_info(const ea_tracker_batch *tb, const char *key, int64_t *value) {
+  if (!tb || !key || !value) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  const std::string k = key;
+  if (k == "aligned") *value = tb->last_aligned;
+  else if (k == "frames_without_edges") *value = tb->last_bare;
+  else if (k == "hysteresis_rounds") *value = tb->last_rounds;
+  else if (k == "edge_passes") *value = tb->last_edge_passes;
+  else if (k == "frames") *value = tb->pushes;
+  else return fail(EA_ERR_INVALID_ARG, "unknown info key: " + k);
+  return EA_OK;
 }
 
 // read back what the problem holds in HBM: points as n x 3 doubles, DT as H x W doubles ([v][u])

@@ -827,6 +827,72 @@ int ea_batch_set_frames_ros(ea_batch *b, const uint8_t *const *ref_bgr, const fl
                             const uint8_t *const *now_bgr, const ea_ros_frame_params *prm);
 int ea_batch_set_frames_ros_device(ea_batch *b, const uint8_t *const *ref_bgr, const float *const *ref_depth,
                                    const uint8_t *const *now_bgr, const ea_ros_frame_params *prm);
+/* ---- multi-stream frame tracker: N cameras pushed in lock-step ---------------------------------------------------------
+ * ea_tracker for `count` independent streams of one extent (N cameras; BASELINE configuration C4's 32 pairs per GPU): every
+ * push takes one frame per stream, runs the batched producers ONCE per frame -- the frame a grid dimension of each launch,
+ * its edge strength / edge map serving first as the current side (chamfer or exact transform into the stream's image) and
+ * then as the next reference (count, scan, scatter, depth weights) -- and solves all aligned streams in one ea_batch_solve.
+ * The tracker owns its problems, one ea_batch over them (and with it the batch's frame workspace) and per stream the state
+ * ea_tracker keeps: frame count, last relative pose, installed prior, covariance.
+ *
+ * flavour 0 (Laplacian: threshold 35, median on, normalised) and 1 (Canny 30 / 90, range [0, 1]) are ea_tracker's; depth is
+ * uint16.  flavour 2 is the ROS node's chain (SolveEA::setRefFrame / setNowFrame, cv::Canny(150, 100), the exact transform
+ * normalised to [0, 255]): depth is float32 in metres at the extent handed in, z_scaling is ignored, and the chain works at
+ * (height, width) >> halvings -- the cameras belong to that working resolution, as with ea_problem_set_*_frame_ros_scaled.
+ *
+ * Per stream the semantics are ea_tracker_push_frame's.  A stream is ALIGNED in a push when it has had a frame
+ * before, its reference has more than 0 points and (flavour 2) the new frame has at least one edge; it is then solved from
+ * its last relative pose, with the motion prior centred there if one is set, the problem's own camera, loss, auto-scaled
+ * loss, depth weighting and constant mask (ea_tracker_batch_problem).  A solve that ends in EA_FAILURE keeps the prior
+ * (aligned[i] is still 1).  Aligned streams whose problems run one kernel family -- the usual case: the same settings for
+ * all -- are solved by ONE ea_batch_solve; a stream with per-point weights (depth weighting), distortion or a second camera
+ * among plain ones would put those on the variant kernels, whose sums agree with the plain kernels' to rounding only, so
+ * such families are solved one after the other, each stream by the kernels, and to the bits, of a tracker of its own.
+ * (What a stream gets is what ea_batch_solve gives its problem among those streams.  That is the lone tracker's result to the
+ * bit while the batch resolves to a lone problem's launch shape -- below 80000 points in all for fp64; a larger batch takes
+ * a throughput shape, two points per lane, and agrees with the lone tracker to rounding: 1e-16 on the poses of 32 VGA
+ * streams, profiles/tracker_batch_ab.txt.  Points, depth weights and images are the lone tracker's bits at every size.)
+ * A stream that is not aligned takes no part in any solve, returns its unchanged prior in q_rel / t_rel, a zeroed summary and aligned[i] = 0.  Then the frame's edge
+ * points become the stream's reference.  A flavour-2 frame without any edge is a result, not an error: the stream is not
+ * aligned, its image is left alone, its new reference has zero points (so the next push does not align it either) and the
+ * push returns EA_OK; ea_tracker_batch_get_info("frames_without_edges") counts such frames of the last push.
+ *
+ * q_rel: count x 4, t_rel: count x 3; summaries, aligned: count entries or NULL.  bgr / depth: count frame pointers --
+ * host memory (pinned memory, ea_host_alloc, goes up as direct DMA), or for the _device form device memory of the tracker's
+ * device, read in place and complete when the call is made (see ea_batch_set_frames_device).
+ *
+ * EA_ERR_INVALID_ARG, before a device or a stream is touched (the tracker stays exactly as it was): a NULL array or entry;
+ * an extent outside the batched producers' limits at the working extent (3..32768, at most 2^30 - 1 pixels, no wider than
+ * 16384); an extent not divisible by 2^halvings; z_scaling <= 0 (flavours 0, 1); for the _device form a frame that is not
+ * device memory of the tracker's device.  ea_tracker_batch_create: count outside 1..65535, an unknown flavour, halvings
+ * outside 0..8 or != 0 with flavours 0 and 1.
+ * A failure PAST the checks (a HIP error, no memory, a failed solve call) resets EVERY stream -- no reference, frame count 0,
+ * the prior kept -- so that the next push starts fresh chains instead of aligning against frames of different pushes.
+ *
+ * ea_tracker_batch_reset(i): stream i forgets its reference and its prior (i < 0: every stream).  set_covariance,
+ * last_covariance(i), set_motion_prior: ea_tracker's, for every stream (why = 4 after a failed solve; EA_ERR_STATE when
+ * stream i was not aligned in the last push).  get_info keys: "aligned" (streams solved in the last push),
+ * "frames_without_edges", "hysteresis_rounds" (looks at the hysteresis flags, 0 for flavour 0), "edge_passes" (N-frame
+ * edge-detection chains the last push ran: 1, whether streams were aligned or not -- the shared frame), "frames" (pushes
+ * since creation that passed the checks). */
+typedef struct ea_tracker_batch ea_tracker_batch;
+int ea_tracker_batch_create(ea_tracker_batch **out, const ea_camera *cams, int count, int dtype, int device, int flavour,
+                            int halvings);
+void ea_tracker_batch_destroy(ea_tracker_batch *tb);
+int ea_tracker_batch_count(const ea_tracker_batch *tb);
+ea_problem *ea_tracker_batch_problem(ea_tracker_batch *tb, int i); /* stream i's problem (loss, auto-scale, depth weighting, constant mask, flavour knobs) */
+int ea_tracker_batch_push_frames(ea_tracker_batch *tb, const uint8_t *const *bgr, const void *const *depth, int height,
+                                 int width, double z_scaling, const ea_options *opt, double *q_rel, double *t_rel,
+                                 ea_summary *summaries, int *aligned);
+int ea_tracker_batch_push_frames_device(ea_tracker_batch *tb, const uint8_t *const *bgr, const void *const *depth, int height,
+                                        int width, double z_scaling, const ea_options *opt, double *q_rel, double *t_rel,
+                                        ea_summary *summaries, int *aligned);
+int ea_tracker_batch_reset(ea_tracker_batch *tb, int i);
+int ea_tracker_batch_set_covariance(ea_tracker_batch *tb, const ea_covariance_options *o);
+int ea_tracker_batch_last_covariance(ea_tracker_batch *tb, int i, ea_covariance *out);
+int ea_tracker_batch_set_motion_prior(ea_tracker_batch *tb, double sigma_rot, double sigma_trans);
+int ea_tracker_batch_get_info(const ea_tracker_batch *tb, const char *key, int64_t *value);
+
 /* the half-resolution step by itself, host in / host out: kind 0 = bgr8 (height x width x 3 bytes), 1 = float32 with
  * NaN -> 0 first, 2 = float32 as is; dst = (height / 2) x (width / 2); height and width even */
 int ea_resize_half(int device, int kind, const void *src, int height, int width, void *dst);
