@@ -55,6 +55,8 @@ EXPORTED = [
     "ea_tracker_batch_push_frames", "ea_tracker_batch_push_frames_device", "ea_tracker_batch_reset",
     "ea_tracker_batch_set_covariance", "ea_tracker_batch_last_covariance", "ea_tracker_batch_set_motion_prior",
     "ea_tracker_batch_get_info",
+    "ea_batch_set_frames_ros_pyramid", "ea_batch_set_frames_ros_pyramid_device", "ea_batch_solve_pyramid", "ea_resize_half_levels",
+    "ea_tracker_batch_create_pyramid", "ea_tracker_batch_level_problem", "ea_tracker_batch_last_summaries",
 ]
 
 # measurement hooks (edge_alignment_amd/csrc/ea_hip_dev.h): bound by bench.py, the A/B scripts and the tests that pin the
@@ -289,6 +291,14 @@ def load():
     L.ea_default_ros_frame_params.restype = None
     L.ea_batch_set_frames_ros.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(RosFrameParams)]
     L.ea_batch_set_frames_ros_device.argtypes = L.ea_batch_set_frames_ros.argtypes
+    L.ea_batch_set_frames_ros_pyramid.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(RosFrameParams)]
+    L.ea_batch_set_frames_ros_pyramid_device.argtypes = L.ea_batch_set_frames_ros_pyramid.argtypes
+    L.ea_batch_solve_pyramid.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(Options), dp, dp, C.POINTER(Summary)]
+    L.ea_tracker_batch_create_pyramid.argtypes = [C.POINTER(vp), C.POINTER(Camera), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.ea_tracker_batch_level_problem.argtypes = [vp, C.c_int, C.c_int]
+    L.ea_tracker_batch_level_problem.restype = vp
+    L.ea_tracker_batch_last_summaries.argtypes = [vp, C.c_int, C.POINTER(Summary)]
+    L.ea_resize_half_levels.argtypes = [C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
     L.ea_tracker_batch_create.argtypes = [C.POINTER(vp), C.POINTER(Camera), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     L.ea_tracker_batch_destroy.argtypes = [vp]
     L.ea_tracker_batch_destroy.restype = None
@@ -897,14 +907,30 @@ class TrackerBatch:
     and serves both sides, the aligned streams are solved by one batch solve.  cams: N (fx, fy, cx, cy); flavour 0 Laplacian,
     1 Canny (depth uint16), 2 ROS (depth float32 in metres, the chain works at the extent >> halvings)."""
 
-    def __init__(self, cams, dtype=EA_F64, device=0, flavour=0, halvings=0, loss=None):
+    def __init__(self, cams, dtype=EA_F64, device=0, flavour=0, halvings=0, loss=None, levels=1):
+        """levels > 1 (flavour 2): coarse-to-fine tracking, cams = [[camera per stream] per level], level 0 first, each at its
+        level's working extent (frame extent >> (halvings + l)); levels = 1: cams = [camera per stream]"""
         self._h = C.c_void_p()
-        cams = [tuple(float(v) for v in c) for c in cams]
-        arr = (Camera * max(len(cams), 1))(*[Camera(*c) for c in cams])
         L = load()
-        _check(L.ea_tracker_batch_create(C.byref(self._h), arr, len(cams), dtype, device, flavour, halvings))
-        self.flavour, self.halvings, self.device = flavour, halvings, device
-        self.problems = [_StreamProblem(L.ea_tracker_batch_problem(self._h, i), dtype, device) for i in range(len(cams))]
+        nested = len(cams) > 0 and len(cams[0]) > 0 and isinstance(cams[0][0], (list, tuple))   # (levels = 1 given per level too)
+        if levels == 1 and not nested:
+            cams = [tuple(float(v) for v in c) for c in cams]
+            arr = (Camera * max(len(cams), 1))(*[Camera(*c) for c in cams])
+            n = len(cams)
+            _check(L.ea_tracker_batch_create(C.byref(self._h), arr, n, dtype, device, flavour, halvings))
+        else:
+            if flavour != 2:
+                raise EAError(EA_ERR_INVALID_ARG, "levels belong to the ROS flavour (2) only")
+            cams = [[tuple(float(v) for v in c) for c in lv] for lv in cams]
+            n = len(cams[0]) if cams else 0
+            if len(cams) != levels or any(len(lv) != n for lv in cams):
+                raise EAError(EA_ERR_INVALID_ARG, "cams: one list of per-stream cameras per level")
+            arr = (Camera * max(levels * n, 1))(*[Camera(*c) for lv in cams for c in lv])
+            _check(L.ea_tracker_batch_create_pyramid(C.byref(self._h), arr, n, levels, dtype, device, halvings))
+        self.flavour, self.halvings, self.device, self.levels = flavour, halvings, device, levels
+        self.problems = [_StreamProblem(L.ea_tracker_batch_problem(self._h, i), dtype, device) for i in range(n)]
+        self.level_problems = [self.problems] + [[_StreamProblem(L.ea_tracker_batch_level_problem(self._h, l, i), dtype, device)
+                                                  for i in range(n)] for l in range(1, levels)]
         if loss is not None:
             for p in self.problems:
                 p.set_loss(loss[0], loss[1])
@@ -916,6 +942,17 @@ class TrackerBatch:
         """stream i's problem: set_loss, set_loss_auto_scale, set_depth_weighting, set_constant_parameters, set_flavour;
         get_points, get_weights, get_loss"""
         return self.problems[i]
+
+    def level_problem(self, l, i):
+        """stream i's problem of pyramid level l (level 0 == problem(i))"""
+        return self.level_problems[l][i]
+
+    def last_summaries(self, i):
+        """the last push's summary of stream i on every level, level 0 first; None for a level that was not solved"""
+        sums = (Summary * self.levels)()
+        _check(load().ea_tracker_batch_last_summaries(self._h, int(i), sums))
+        zero = bytes(C.sizeof(Summary))
+        return [None if bytes(s) == zero else summary_to_dict(s) for s in sums]
 
     def push_frames(self, bgr, depth, z_scaling=5000.0, **opts):
         """One frame per stream: sequences of len(self) frames or stacked arrays of one extent -- bgr (H, W, 3) uint8, depth
@@ -962,8 +999,9 @@ class TrackerBatch:
 
     def close(self):
         if self._h:
-            for p in self.problems:
-                p.close()
+            for lv in self.level_problems:
+                for p in lv:
+                    p.close()
             load().ea_tracker_batch_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -1488,6 +1526,60 @@ def resize_half(img, nan_to_zero=False, device=0):
     _check(load().ea_resize_half(device, kind, img.ctypes.data_as(C.c_void_p), img.shape[0], img.shape[1],
                                  out.ctypes.data_as(C.c_void_p)))
     return out
+
+
+def resize_half_levels(img, skip=0, keep=1, nan_to_zero=False, device=0):
+    """ea_resize_half_levels: levels skip .. skip + keep - 1 of the halving chain of img (level k = k halvings, level 0 the frame
+    itself) -> list of arrays; img and nan_to_zero as for resize_half (NaN is replaced on the first step only)"""
+    img = np.ascontiguousarray(img)
+    if img.dtype == np.uint8 and img.ndim == 3 and img.shape[2] == 3:
+        kind = 0
+    elif img.dtype == np.float32 and img.ndim == 2:
+        kind = 1 if nan_to_zero else 2
+    else:
+        raise ValueError("resize_half_levels takes uint8 (H, W, 3) or float32 (H, W)")
+    H, W = img.shape[:2]
+    out = [np.empty((H >> k, W >> k) + img.shape[2:], dtype=img.dtype) for k in range(skip, skip + max(keep, 0))] if skip >= 0 else []
+    ptrs = (C.c_void_p * max(len(out), 1))(*[o.ctypes.data for o in out])
+    _check(load().ea_resize_half_levels(device, kind, img.ctypes.data_as(C.c_void_p), H, W, int(skip), int(keep), ptrs))
+    return out
+
+
+def set_frames_ros_pyramid(levels, ref_bgr=None, ref_depth=None, now_bgr=None, t1=150.0, t2=100.0, halvings=0):
+    """ea_batch_set_frames_ros_pyramid[_device]: levels = [Batch of the same N frame pairs' problems per pyramid level], levels[0]
+    the finest at the frames' extent >> halvings; every level ends as Batch.set_frames_ros(..., halvings=halvings + l) leaves it,
+    bit for bit, from frames that go up once.  The frames as for Batch.set_frames_ros.  A current frame without an edge at some
+    level raises EAError(EA_ERR_STATE) after everything else has been set: levels[l].info("frames_without_edges")."""
+    sides = [("ref_bgr", ref_bgr, 3), ("ref_depth", ref_depth, 4), ("now_bgr", now_bgr, 3)]
+    if (ref_bgr is None) != (ref_depth is None) or all(v is None for _, v, _ in sides):
+        raise ValueError("ref_bgr and ref_depth go together, and one side must be given")
+    levels = list(levels)
+    if not levels:
+        raise EAError(EA_ERR_INVALID_ARG, "a pyramid has at least one level")
+    shape, on_device, arrays, keep = levels[0]._frame_arrays(sides)
+    L = load()
+    prm = RosFrameParams()
+    L.ea_default_ros_frame_params(C.byref(prm), *(shape or (0, 0)))
+    prm.halvings, prm.threshold1, prm.threshold2 = int(halvings), float(t1), float(t2)
+    if on_device:
+        import torch
+        torch.cuda.current_stream(levels[0].problems[0].device).synchronize()  # (as in Batch.set_frames)
+    hs = (C.c_void_p * len(levels))(*[b._h for b in levels])
+    fn = L.ea_batch_set_frames_ros_pyramid_device if on_device else L.ea_batch_set_frames_ros_pyramid
+    _check(fn(hs, len(levels), arrays["ref_bgr"], arrays["ref_depth"], arrays["now_bgr"], C.byref(prm)))
+
+
+def solve_pyramid_batch(levels, q, t, **opts):
+    """ea_batch_solve_pyramid: solve_pyramid for every problem of the levels' batches (levels[0] = finest), one batch solve per
+    level; q (N, 4), t (N, 3) -> q, t, [[summary per problem] per level]"""
+    levels = list(levels)
+    n = len(levels[0]) if levels else 0
+    q, t = _f64(q).reshape(-1, 4).copy(), _f64(t).reshape(-1, 3).copy()
+    o = default_options(**opts)
+    hs = (C.c_void_p * max(len(levels), 1))(*[b._h for b in levels])
+    s = (Summary * max(len(levels) * n, 1))()
+    _check(load().ea_batch_solve_pyramid(hs, len(levels), C.byref(o), _dp(q), _dp(t), s))
+    return q, t, [[summary_to_dict(s[l * n + i]) for i in range(n)] for l in range(len(levels))]
 
 
 def selftest_wave_reduce(values, device=0):

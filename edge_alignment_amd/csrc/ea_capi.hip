@@ -410,6 +410,7 @@ struct ea_batch {
   size_t frames_bytes = 0, h_frames_bytes = 0;
   int frames_rounds = 0;  // looks at the hysteresis flags of the last batched producer call (ea_batch_set_frames_canny / _ros; else 0)
   int frames_without_edges = 0;  // current frames without any edge in the last ea_batch_set_frames_ros call (else 0)
+  int64_t frames_uploaded = 0;   // host-to-device frame copies of the last ea_batch_set_frames_ros_pyramid call led by this batch
 };
 
 int ea::check_device(int device) {
@@ -1202,6 +1203,7 @@ int ea::batch_frames_reserve(ea_batch *b, size_t device_bytes, size_t pinned_byt
 
 void ea::batch_frames_set_rounds(ea_batch *b, int rounds) { b->frames_rounds = rounds; }
 void ea::batch_frames_set_without_edges(ea_batch *b, int frames) { b->frames_without_edges = frames; }
+void ea::batch_frames_set_uploaded(ea_batch *b, int64_t copies) { b->frames_uploaded = copies; }
 
 // (re)build descriptors and the tile list when any problem changed
 static void fill_desc(const ea_problem *p, ProblemDesc &d) {
@@ -3123,6 +3125,7 @@ extern "C" int ea_batch_get_info(const ea_batch *b, const char *key, int64_t *va
   else if (k == "starts_device_ns") *value = b->last_starts_device_ns;    // between the event pair of "starts_events" = 1
   else if (k == "frames_hysteresis_rounds") *value = b->frames_rounds;    // the last batched producer call's looks at the hysteresis flags, both sides (0: Laplacian)
   else if (k == "frames_without_edges") *value = b->frames_without_edges;  // current frames the last ea_batch_set_frames_ros call left alone (0: clean, Laplacian, Canny)
+  else if (k == "frames_uploaded") *value = b->frames_uploaded;  // levels[0] of the last ea_batch_set_frames_ros_pyramid call: its host-to-device frame copies
   else return fail(EA_ERR_INVALID_ARG, "unknown info key: " + k);
   return EA_OK;
 }
@@ -3878,6 +3881,48 @@ extern "C" int ea_solve_pyramid(ea_problem *const *levels, int nlevels, const ea
     if (s->termination == EA_FAILURE) {
       for (int k = l - 1; k >= 0 && summaries; --k) std::memset(&summaries[k], 0, sizeof(ea_summary));
       break;
+    }
+  }
+  return EA_OK;
+}
+
+// ea_solve_pyramid for every problem of a batch: levels[l] holds the level-l counterparts of the same `count` problems, in the
+// same order; one ea_batch_solve per level, the coarsest first, carries all poses down.  A problem whose level ends in FAILURE
+// stops there: its pose stays what that level returned and its finer summaries are zero, while its neighbours go on.  Every
+// level is solved as the whole batch -- a stopped problem rides along from the pose it holds and what comes back for it is
+// thrown away (its finer counterparts see an auto-scaled loss re-estimated, nothing else) -- so every other problem is solved
+// by the launches, and to the bits, of a loop of ea_batch_solve over the levels.  summaries: nlevels x count, level-major.
+extern "C" int ea_batch_solve_pyramid(ea_batch *const *levels, int nlevels, const ea_options *opt, double *q, double *t,
+                                      ea_summary *summaries) {
+  if (!levels || nlevels < 1 || !q || !t) return fail(EA_ERR_INVALID_ARG, "bad argument");
+  for (int l = 0; l < nlevels; ++l) {
+    if (!levels[l]) return fail(EA_ERR_INVALID_ARG, "NULL level");
+    if (levels[l]->probs.size() != levels[0]->probs.size()) return fail(EA_ERR_INVALID_ARG, "the levels' batches differ in count");
+  }
+  const size_t n = levels[0]->probs.size();
+  std::vector<unsigned char> stopped(n, 0);
+  std::vector<ea_summary> local(summaries ? 0 : n);
+  std::vector<double> held_q(4 * n), held_t(3 * n);
+  size_t running = n;
+  for (int l = nlevels - 1; l >= 0; --l) {
+    ea_summary *s = summaries ? summaries + (size_t)l * n : local.data();
+    if (running == 0) {
+      if (summaries) std::memset(s, 0, n * sizeof(ea_summary));
+      continue;
+    }
+    std::memcpy(held_q.data(), q, 4 * n * sizeof(double));
+    std::memcpy(held_t.data(), t, 3 * n * sizeof(double));
+    const int rc = ea_batch_solve(levels[l], opt, q, t, s);
+    if (rc != EA_OK) return rc;
+    for (size_t i = 0; i < n; ++i) {
+      if (stopped[i]) {
+        std::memcpy(q + 4 * i, &held_q[4 * i], 4 * sizeof(double));
+        std::memcpy(t + 3 * i, &held_t[3 * i], 3 * sizeof(double));
+        std::memset(&s[i], 0, sizeof(ea_summary));
+      } else if (s[i].termination == EA_FAILURE) {
+        stopped[i] = 1;
+        --running;
+      }
     }
   }
   return EA_OK;

@@ -124,5 +124,8 @@ void batch_frames_set_rounds(ea_batch *b, int rounds);
 // ea_batch_get_info's "frames_without_edges": current frames of the last ea_batch_set_frames_ros call that had no edge (every
 // batched producer call starts by setting it to 0)
 void batch_frames_set_without_edges(ea_batch *b, int frames);
+// ea_batch_get_info's "frames_uploaded": host-to-device frame copies of the last ea_batch_set_frames_ros_pyramid call, kept by
+// the batch of level 0
+void batch_frames_set_uploaded(ea_batch *b, int64_t copies);
 
 }  // namespace ea

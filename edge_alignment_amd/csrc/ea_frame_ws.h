@@ -152,4 +152,76 @@ inline size_t frame_stage_bound(int full_H, int full_W, int halvings) {
   return frame_ws_bound(full_H >> halvings, full_W >> halvings) + 7 * npf + 7 * (npf / 4) + 7 * (npf / 16) + 6 * 256;
 }
 
+// The frame's block of ea_batch_set_frames_ros_pyramid: the workspaces of `levels` pyramid levels of one frame pair, level l
+// at the working extent full >> (halvings + l), one behind the other -- level l's regions are frame_ws of its extent shifted
+// by level_off[l] -- and behind them the stage, region for region frame_stage's of (full extent, halvings):
+//
+//   bgr_full, depth_full    the uploaded full-size frames (host frames, halvings >= 1; with halvings == 0 level 0's own
+//                           `bgr` / `depth` hold the full-size frame, uploaded as it is)
+//   bgr_a, depth_a          (halvings >= 2) the frame after 3 halvings, when that is no kept level (halvings > 3)
+//   bgr_b, depth_b          (halvings >= 3) the frame after 6 halvings, when that is no kept level (halvings > 6)
+//
+// The halving chain (ea_launch.h: launch_halving_chain_*) writes every kept level straight into that level's `bgr` /
+// `depth`; it takes kChainSteps = 3 steps per launch, counted from the full-size frame, so a chain of more steps continues
+// from what step 3 and step 6 left in HBM: a kept level, or a / b, which are larger than that needs (npf / 64 and npf / 4096
+// pixels) because the stage keeps frame_stage's sizes -- levels == 1 IS frame_stage(full, halvings, host_frames), number
+// for number, and a caller who moves from one level to several finds the stage where it was.
+// One stride, total, takes a kernel from frame z to frame z + 1 on every level and in the stage.
+//   frame_pyramid(...).total <= frame_pyramid_bound(...) = sum over l of frame_ws_bound(level l's extent)
+//                                                          + (7 + 7/4 + 7/16) npf + 6 * 256;
+// the levels' bounds sum to less than 4/3 of level 0's plus 16 W + 19 * 256 per level.  halvings + levels - 1 <= 8.
+constexpr int kPyramidMaxLevels = 9;
+struct FramePyramid {
+  int levels = 0;
+  size_t level_off[kPyramidMaxLevels] = {};
+  FrameWs ws[kPyramidMaxLevels];  // level l's layout; its regions lie at level_off[l] + their offset
+  WsRegion<uint8_t> bgr_full;
+  WsRegion<float> depth_full;
+  WsRegion<uint8_t> bgr_a;
+  WsRegion<float> depth_a;
+  WsRegion<uint8_t> bgr_b;
+  WsRegion<float> depth_b;
+  size_t ws_total = 0;  // all levels' workspaces: where the stage begins
+  size_t total = 0;     // the stride from one frame's block to the next
+};
+
+inline FramePyramid frame_pyramid(int full_H, int full_W, int halvings, int levels, bool host_frames) {
+  const size_t npf = (size_t)full_H * full_W;
+  FramePyramid py;
+  py.levels = levels;
+  size_t off = 0;
+  for (int l = 0; l < levels && l < kPyramidMaxLevels; ++l) {
+    py.level_off[l] = off;
+    py.ws[l] = frame_ws(full_H >> (halvings + l), full_W >> (halvings + l));
+    off += py.ws[l].total;  // (a multiple of 256)
+  }
+  py.ws_total = off;
+  auto put = [&off](auto &r, size_t bytes) {
+    r.off = off;
+    r.bytes = bytes;
+    off = (off + bytes + 255) & ~(size_t)255;
+  };
+  if (halvings > 0 && host_frames) {
+    put(py.bgr_full, 3 * npf);
+    put(py.depth_full, 4 * npf);
+  }
+  if (halvings > 1) {
+    put(py.bgr_a, 3 * (npf / 4));
+    put(py.depth_a, 4 * (npf / 4));
+  }
+  if (halvings > 2) {
+    put(py.bgr_b, 3 * (npf / 16));
+    put(py.depth_b, 4 * (npf / 16));
+  }
+  py.total = off;
+  return py;
+}
+
+inline size_t frame_pyramid_bound(int full_H, int full_W, int halvings, int levels) {
+  const size_t npf = (size_t)full_H * full_W;
+  size_t b = 7 * npf + 7 * (npf / 4) + 7 * (npf / 16) + 6 * 256;
+  for (int l = 0; l < levels; ++l) b += frame_ws_bound(full_H >> (halvings + l), full_W >> (halvings + l));
+  return b;
+}
+
 }  // namespace ea

@@ -1,9 +1,10 @@
 // ea_frames.hip — the host side of everything that starts from raw frames: the frame producers behind
 // ea_problem_set_{ref,now}_frame* (raw images -> edge points / DT image through the kernels of ea_preprocess.hip, in a
 // workspace laid out by ea_frame_ws.h), their batched forms ea_batch_set_frames[_canny|_ros][_device] (N frame pairs, the
-// frame a grid dimension of every launch), ea_resize_half, the read-backs ea_problem_get_points / _get_dt, and the frame-to-frame
+// frame a grid dimension of every launch) and the ROS chain's pyramid form ea_batch_set_frames_ros_pyramid (L levels from frames
+// handed in once), ea_resize_half[_levels], the read-backs ea_problem_get_points / _get_dt, and the frame-to-frame
 // tracker ea_tracker_* with its multi-stream form ea_tracker_batch_* (N streams through the batched producers, each frame
-// processed once for both sides, one batch solve).  Host code only: this file holds no kernel.
+// processed once for both sides, one batch solve; with levels: coarse to fine).  Host code only: this file holds no kernel.
 
 #include <hip/hip_runtime.h>
 
@@ -798,34 +799,55 @@ static int batch_frames_check(ea_batch *b, const uint8_t *const *ref_bgr, const 
 // The ROS call (j->ros): each frame's block is its workspace and its halving stage (ea_frame_ws.h: frame_stage), the slots'
 // colour and float depth pointers name the frame at the WORKING resolution -- the workspace's `bgr` / `depth`, or with
 // halvings == 0 the caller's device frame in place -- and device frames to be halved travel as pointers behind the slots.
+static void batch_frames_layout(BatchFrames *j);
+static void batch_frames_place(BatchFrames *j, unsigned char *base, unsigned char *d_table, unsigned char *h_block,
+                               const uint8_t *const *ref_bgr, const void *const *ref_depth, const uint8_t *const *now_bgr,
+                               const uint8_t *const *now_mask);
+static size_t batch_frames_pinned_bytes(const BatchFrames &j) {
+  return (2 * j.table_bytes + j.n * (1 + kCannyFrameFlags) * sizeof(int) + 15) & ~(size_t)15;  // (several may lie in a row)
+}
 static int batch_frames_begin(ea_batch *b, const uint8_t *const *ref_bgr, const void *const *ref_depth,
                               const uint8_t *const *now_bgr, const uint8_t *const *now_mask, BatchFrames *j) {
   HIPCHK(hipSetDevice(j->device));
+  batch_frames_layout(j);
+  unsigned char *d_block = nullptr, *h_block = nullptr;
+  const int rc = batch_frames_reserve(b, j->n * j->stride + j->table_bytes, batch_frames_pinned_bytes(*j), &d_block, &h_block);
+  if (rc != EA_OK) return rc;
+  batch_frames_set_without_edges(b, 0);
+  batch_frames_place(j, d_block, d_block + j->n * j->stride, h_block, ref_bgr, ref_depth, now_bgr, now_mask);
+  return EA_OK;
+}
+
+// the sizes: the frame's workspace, the stride between frames' blocks, the table (slots, and the frame pointers behind them)
+static void batch_frames_layout(BatchFrames *j) {
   j->ws = frame_ws(j->H, j->W);
-  const FrameWs &ws = j->ws;
   const size_t n = j->n = (size_t)j->count;
   j->np = (size_t)j->H * j->W;
-  j->stride = ws.total;
+  j->stride = j->ws.total;
   if (j->ros) {
     j->st = frame_stage(j->full_H, j->full_W, j->halvings, !j->on_device);
     j->stride = j->st.total;
     if (j->on_device && j->halvings > 0) j->ptrs.assign(3 * n, nullptr);
   }
-  const size_t table_bytes = j->table_bytes = n * sizeof(FrameSlot) + j->ptrs.size() * sizeof(void *);
+  j->table_bytes = n * sizeof(FrameSlot) + j->ptrs.size() * sizeof(void *);
   static_assert(sizeof(FrameSlot) % 8 == 0, "slots follow the 256-byte aligned workspaces, pointers follow the slots");
-  unsigned char *d_block = nullptr, *h_block = nullptr;
-  const int rc = batch_frames_reserve(b, n * j->stride + table_bytes, 2 * table_bytes + n * (1 + kCannyFrameFlags) * sizeof(int),
-                                      &d_block, &h_block);
-  if (rc != EA_OK) return rc;
-  batch_frames_set_without_edges(b, 0);
-  j->base = d_block;
+}
+
+// base: frame 0's workspace (frame i's: j->stride bytes per frame further on); d_table: where the table lies on the device;
+// h_block: batch_frames_pinned_bytes of pinned memory
+static void batch_frames_place(BatchFrames *j, unsigned char *base, unsigned char *d_table, unsigned char *h_block,
+                               const uint8_t *const *ref_bgr, const void *const *ref_depth, const uint8_t *const *now_bgr,
+                               const uint8_t *const *now_mask) {
+  const FrameWs &ws = j->ws;
+  const size_t n = j->n, table_bytes = j->table_bytes;
+  j->base = base;
   j->h_slots[0] = reinterpret_cast<FrameSlot *>(h_block);
   j->h_slots[1] = reinterpret_cast<FrameSlot *>(h_block + table_bytes);
   j->h_totals = reinterpret_cast<int *>(h_block + 2 * table_bytes);
   j->h_flags = j->h_totals + n;
   j->f.n = j->count; j->f.H = j->H; j->f.W = j->W; j->f.stride = j->stride;
-  j->f.slots = reinterpret_cast<FrameSlot *>(d_block + n * j->stride);
-  j->d_ptrs = reinterpret_cast<const void *const *>(d_block + n * j->stride + n * sizeof(FrameSlot));
+  j->f.slots = reinterpret_cast<FrameSlot *>(d_table);
+  j->d_ptrs = reinterpret_cast<const void *const *>(d_table + n * sizeof(FrameSlot));
   j->slots.resize(n);
   std::memset(j->slots.data(), 0, n * sizeof(FrameSlot));
   for (size_t i = 0; i < n; ++i) {
@@ -846,7 +868,6 @@ static int batch_frames_begin(ea_batch *b, const uint8_t *const *ref_bgr, const 
     sl.fx = p->cam.fx; sl.fy = p->cam.fy; sl.cx = p->cam.cx; sl.cy = p->cam.cy;
     sl.z_ref = p->dw_z_ref; sl.power = p->dw_power;
   }
-  return EA_OK;
 }
 
 // The table on its way up: the slots and, behind them, the ROS call's frame pointers.  The rule: a staging block is not
@@ -1226,6 +1247,283 @@ extern "C" int ea_batch_set_frames_ros_device(ea_batch *b, const uint8_t *const 
   return batch_set_frames_ros(b, ref_bgr, ref_depth, now_bgr, prm, true);
 }
 
+// ---- the pyramid form of the ROS producers: ea_batch_set_frames_ros with halvings, halvings + 1, ... on the batches of the
+// levels, from frames handed in ONCE.  The frames' blocks are laid out by frame_pyramid (ea_frame_ws.h) in the block of
+// levels[0]: every level's workspace, then the stage; each level has a BatchFrames of its own whose base is its workspace in
+// frame 0's block and whose stride is the pyramid's, a slot table of its own behind the frames, and its part of the pinned
+// block -- so every step behind the halvings is the single-level call's, launched per level.  Per side: the frames go up (host
+// frames: once, into the stage's full-size regions, or without halvings into level 0's own `bgr` / `depth` as they are), ONE
+// halving chain per kind (launch_halving_chain_*: three steps per launch) leaves every level's frame in that level's `bgr` /
+// `depth`, then per level the sequence of batch_set_frames_ros.  The reference side of all levels is queued before the
+// current side overwrites the stage and the levels' `bgr`; everything is on the null stream.
+
+// `T` halving steps of every frame from one read per launch.  dst_of(k), k = 1..T: where the frames after k steps go (frame
+// 0's pointer), NULL = nowhere; the frames after 3 and 6 steps (where a launch ends) and after T must go somewhere.
+template <typename E, typename DstOf>
+static int halving_chain(const FramesLaunch &f, const E *const *table, const E *src, int H, int W, int T, DstOf dst_of, int nan_to_zero) {
+  for (int k0 = 0; k0 < T; k0 += kChainSteps) {
+    const int steps = std::min(kChainSteps, T - k0);
+    ChainLevels lv;
+    for (int s = 0; s < steps; ++s) lv.dst[s] = dst_of(k0 + s + 1);
+    if constexpr (sizeof(E) == 1)
+      HIPCHK(launch_halving_chain_bgr8(f, k0 == 0 ? table : nullptr, src, H >> k0, W >> k0, steps, lv, nullptr));
+    else
+      HIPCHK(launch_halving_chain_f32(f, k0 == 0 ? table : nullptr, src, H >> k0, W >> k0, steps, lv, k0 == 0 ? nan_to_zero : 0, nullptr));
+    src = static_cast<const E *>(lv.dst[steps - 1]);
+  }
+  return EA_OK;
+}
+
+// One side's frames on every level.  J: the levels' jobs (J[0].base is frame 0's block); *uploads counts the frame copies.
+static int pyramid_stage_side(const std::vector<BatchFrames> &J, const FramePyramid &py, int halvings, int side,
+                              const uint8_t *const *bgr, const float *const *depth, int64_t *uploads) {
+  const BatchFrames &j0 = J[0];
+  const int T = halvings + (int)J.size() - 1;
+  const size_t npf = (size_t)j0.full_H * j0.full_W;
+  const bool has_depth = side == 0;
+  unsigned char *block = j0.base;
+  const uint8_t *bsrc = nullptr;
+  const float *dsrc = nullptr;
+  if (!j0.on_device) {
+    const WsRegion<uint8_t> &rb = halvings > 0 ? py.bgr_full : j0.ws.bgr;
+    int rc = upload_frames(j0, rb, bgr, npf * 3);
+    *uploads += (int64_t)j0.n;
+    bsrc = rb.at(block);
+    if (rc == EA_OK && has_depth) {
+      if (halvings > 0) { rc = upload_frames(j0, py.depth_full, depth, npf * 4); dsrc = py.depth_full.at(block); }
+      else { rc = upload_frames(j0, j0.ws.depth, depth, npf * 4); dsrc = j0.ws.depth.at<float>(block); }
+      *uploads += (int64_t)j0.n;
+    }
+    if (rc != EA_OK) return rc;
+  }
+  if (T == 0) return EA_OK;
+  const uint8_t *const *bgr_table = nullptr;
+  const float *const *depth_table = nullptr;
+  if (j0.on_device) {
+    bgr_table = reinterpret_cast<const uint8_t *const *>(j0.d_ptrs + (side == 0 ? 0 : 2 * j0.n));
+    depth_table = reinterpret_cast<const float *const *>(j0.d_ptrs + j0.n);
+  }
+  FramesLaunch f;
+  f.n = j0.count; f.stride = j0.stride;
+  int rc = halving_chain<uint8_t>(f, bgr_table, bsrc, j0.full_H, j0.full_W, T, [&](int k) -> void * {
+    if (k >= halvings) return J[(size_t)(k - halvings)].ws.bgr.at(J[(size_t)(k - halvings)].base);
+    return k == 3 ? py.bgr_a.at(block) : k == 6 ? py.bgr_b.at(block) : nullptr;
+  }, 0);
+  if (rc == EA_OK && has_depth)
+    rc = halving_chain<float>(f, depth_table, dsrc, j0.full_H, j0.full_W, T, [&](int k) -> void * {
+      if (k >= halvings) return J[(size_t)(k - halvings)].ws.depth.at<float>(J[(size_t)(k - halvings)].base);
+      return k == 3 ? py.depth_a.at(block) : k == 6 ? py.depth_b.at(block) : nullptr;
+    }, /*nan_to_zero=*/1);
+  return rc;
+}
+
+// The memory of a pyramid call, after its checks: the frames' blocks (frame_pyramid) and every level's slot table in the
+// device block of levels[0], every level's staging in its pinned block, and each level's job placed on its part.
+static int pyramid_frames_begin(ea_batch *const *levels, std::vector<BatchFrames> *jobs, int halvings, const uint8_t *const *ref_bgr,
+                                const void *const *ref_depth, const uint8_t *const *now_bgr, FramePyramid *py_out) {
+  std::vector<BatchFrames> &J = *jobs;
+  const int nlevels = (int)J.size(), T = halvings + nlevels - 1;
+  const bool on_device = J[0].on_device;
+  HIPCHK(hipSetDevice(J[0].device));
+  const FramePyramid py = *py_out = frame_pyramid(J[0].full_H, J[0].full_W, halvings, nlevels, !on_device);
+  const size_t n = (size_t)J[0].count;
+  size_t table_total = 0, pinned_total = 0;
+  for (int l = 0; l < nlevels; ++l) {
+    BatchFrames &j = J[(size_t)l];
+    batch_frames_layout(&j);
+    j.stride = py.total;
+    // the caller's device frames travel once, behind level 0's slots, for the chain's first launch
+    j.ptrs.clear();
+    if (l == 0 && on_device && T > 0) j.ptrs.assign(3 * n, nullptr);
+    j.table_bytes = n * sizeof(FrameSlot) + j.ptrs.size() * sizeof(void *);
+    table_total += j.table_bytes;
+    pinned_total += batch_frames_pinned_bytes(j);
+  }
+  unsigned char *d_block = nullptr, *h_block = nullptr;
+  const int rc = batch_frames_reserve(levels[0], n * py.total + table_total, pinned_total, &d_block, &h_block);
+  if (rc != EA_OK) return rc;
+  unsigned char *d_table = d_block + n * py.total, *h = h_block;
+  for (int l = 0; l < nlevels; ++l) {
+    BatchFrames &j = J[(size_t)l];
+    batch_frames_set_without_edges(levels[l], 0);
+    batch_frames_set_rounds(levels[l], 0);
+    batch_frames_place(&j, d_block + py.level_off[l], d_table, h, ref_bgr, ref_depth, now_bgr, nullptr);
+    d_table += j.table_bytes;
+    h += batch_frames_pinned_bytes(j);
+  }
+  return EA_OK;
+}
+
+static int batch_set_frames_ros_pyramid(ea_batch *const *levels, int nlevels, const uint8_t *const *ref_bgr,
+                                        const float *const *ref_depth, const uint8_t *const *now_bgr, const ea_ros_frame_params *prm,
+                                        bool on_device) {
+  // every check comes before a device or a problem is touched
+  if (!levels || !prm) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (nlevels < 1 || nlevels > kPyramidMaxLevels) return fail(EA_ERR_INVALID_ARG, "a pyramid has 1..9 levels");
+  for (int l = 0; l < nlevels; ++l)
+    if (!levels[l]) return fail(EA_ERR_INVALID_ARG, "NULL level");
+  const int full_h = prm->full_height, full_w = prm->full_width, halvings = prm->halvings;
+  if (full_h < 3 || full_w < 3 || full_h > 32768 || full_w > 32768 || (int64_t)full_h * full_w > 0x3fffffff)
+    return fail(EA_ERR_INVALID_ARG, "image extent out of range");
+  if (halvings < 0 || halvings + nlevels - 1 > 8) return fail(EA_ERR_INVALID_ARG, "halvings + levels - 1 must be within 0..8");
+  const int T = halvings + nlevels - 1;
+  int rc = check_scaled_args(full_h, full_w, T);
+  if (rc != EA_OK) return rc;
+  int lo, hi;
+  rc = ros_thresholds(prm->threshold1, prm->threshold2, &lo, &hi);
+  if (rc != EA_OK) return rc;
+  if ((full_h >> T) < 3 || (full_w >> T) < 3) return fail(EA_ERR_INVALID_ARG, "image extent out of range: the coarsest level is below 3 x 3");
+  std::vector<BatchFrames> J((size_t)nlevels);
+  const void *const *ref_depth_v = reinterpret_cast<const void *const *>(ref_depth);
+  std::vector<const ea_problem *> all;
+  for (int l = 0; l < nlevels; ++l) {
+    BatchFrames &j = J[(size_t)l];
+    j.ros = true; j.full_H = full_h; j.full_W = full_w; j.halvings = halvings + l;
+    // (the caller's device frames are looked at once, with level 0)
+    rc = batch_frames_check(levels[l], ref_bgr, ref_depth_v, sizeof(float), now_bgr, nullptr, full_h >> j.halvings, full_w >> j.halvings,
+                            /*z_scaling (metres already)=*/1.0, on_device && l == 0, &j);
+    if (rc != EA_OK) return rc;
+    j.on_device = on_device;
+    if (j.count != J[0].count) return fail(EA_ERR_INVALID_ARG, "the levels' batches differ in count");
+    if (j.device != J[0].device) return fail(EA_ERR_INVALID_ARG, "the levels' batches are on different devices");
+    for (int i = 0; i < j.count; ++i) {
+      if (j.probs[i]->dtype != J[0].dtype) return fail(EA_ERR_INVALID_ARG, "the levels' problems differ in dtype");
+      all.push_back(j.probs[i]);
+    }
+  }
+  std::sort(all.begin(), all.end());
+  if (std::adjacent_find(all.begin(), all.end()) != all.end())
+    return fail(EA_ERR_INVALID_ARG, "the same problem on two levels: each level of each frame pair needs a problem of its own");
+
+  FramePyramid py;
+  rc = pyramid_frames_begin(levels, &J, halvings, ref_bgr, ref_depth_v, now_bgr, &py);
+  if (rc != EA_OK) return rc;
+  const size_t n = (size_t)J[0].count;
+  batch_frames_set_uploaded(levels[0], 0);
+  std::vector<int> total_looks((size_t)nlevels, 0);
+  auto canny = [&](int l, int side) {
+    BatchFrames &j = J[(size_t)l];
+    const FrameWs &ws = j.ws;
+    int looks = 0;
+    const hipError_t e = launch_canny_frames(j.f, side, 0, lo, hi, /*l2_bgr=*/1, ws.gray.at(j.base), ws.mag.at(j.base), ws.dir.at(j.base),
+                                             ws.label.at(j.base), ws.edges.at(j.base), ws.inv.at(j.base), ws.changed.at(j.base), j.h_flags,
+                                             &looks, nullptr);
+    if (e == hipSuccess) batch_frames_set_rounds(levels[l], total_looks[(size_t)l] += looks);
+    return e;
+  };
+  int64_t uploads = 0;
+  for (BatchFrames &j : J) HIPCHK(upload_table(&j));  // where the frames are read, the cameras, the depth weighting
+  if (J[0].ref) {
+    rc = pyramid_stage_side(J, py, halvings, 0, ref_bgr, ref_depth, &uploads);
+    batch_frames_set_uploaded(levels[0], uploads);
+    if (rc != EA_OK) return rc;
+    for (int l = 0; l < nlevels; ++l) {
+      BatchFrames &j = J[(size_t)l];
+      const FrameWs &ws = j.ws;
+      HIPCHK(canny(l, 0));
+      rc = batch_ref_counts(&j, ws.edges, 0);
+      if (rc != EA_OK) return rc;
+      HIPCHK(upload_table(&j));  // the point arrays
+      if (j.max_total > 0) HIPCHK(launch_edge_scatter_ros_stack(j.dtype, j.f, ws.edges.at(j.base), ws.counts.at(j.base), nullptr));
+      HIPCHK(launch_depth_weights_frames(j.dtype, j.f, j.max_weighted, nullptr));
+    }
+  }
+  std::vector<int> rc_dt((size_t)nlevels, EA_OK);
+  int first_bare_level = -1, first_bare = -1, bare_all = 0;
+  if (J[0].now) {
+    // (every level's scatter reads that level's `edges` and `depth` and is in front of this on the same stream)
+    rc = pyramid_stage_side(J, py, halvings, 1, now_bgr, nullptr, &uploads);
+    batch_frames_set_uploaded(levels[0], uploads);
+    if (rc != EA_OK) return rc;
+    for (int l = 0; l < nlevels; ++l) {
+      BatchFrames &j = J[(size_t)l];
+      const FrameWs &ws = j.ws;
+      HIPCHK(canny(l, 1));
+      rc = batch_counts_back(&j, ws.edges, 0);
+      if (rc != EA_OK) return rc;
+      int bare = 0;
+      j.no_image.assign(n, 0);
+      for (size_t i = 0; i < n; ++i)
+        if (j.h_totals[i] == 0) {
+          j.no_image[i] = 1;
+          ++bare;
+          if (bare_all++ == 0) { first_bare_level = l; first_bare = (int)i; }
+        }
+      batch_frames_set_without_edges(levels[l], bare);
+      rc_dt[(size_t)l] = batch_alloc_dts(&j);
+      if (rc_dt[(size_t)l] == EA_OK && (size_t)bare < n) {
+        HIPCHK(upload_table(&j));  // the images
+        HIPCHK(launch_chamfer_frames(j.f, ws.inv.at(j.base), ws.G.at(j.base), ws.scan.at(j.base), ws.dist.at(j.base),
+                                     ws.dist.at<float>(j.base), ws.minmax.at(j.base), nullptr));
+        HIPCHK(launch_dt_store_stack(j.dtype, j.f, ws.dist.at<float>(j.base), ws.minmax.at(j.base), 1, 0.0, 255.0, nullptr));
+      }
+    }
+  }
+  rc = EA_OK;
+  for (int l = 0; l < nlevels; ++l) {
+    const int rc_l = batch_frames_end(J[(size_t)l], rc_dt[(size_t)l]);  // (the first waits, the others find the device idle)
+    if (rc == EA_OK) rc = rc_l;
+  }
+  if (rc == EA_OK && bare_all > 0)
+    return fail(EA_ERR_STATE, "no edge in " + std::to_string(bare_all) + " of the current frames' levels, the first at level " +
+                                  std::to_string(first_bare_level) + ", index " + std::to_string(first_bare) +
+                                  ": the exact distance transform is undefined");
+  return rc;
+}
+
+extern "C" int ea_batch_set_frames_ros_pyramid(ea_batch *const *levels, int nlevels, const uint8_t *const *ref_bgr,
+                                               const float *const *ref_depth, const uint8_t *const *now_bgr,
+                                               const ea_ros_frame_params *prm) {
+  return batch_set_frames_ros_pyramid(levels, nlevels, ref_bgr, ref_depth, now_bgr, prm, false);
+}
+
+extern "C" int ea_batch_set_frames_ros_pyramid_device(ea_batch *const *levels, int nlevels, const uint8_t *const *ref_bgr,
+                                                      const float *const *ref_depth, const uint8_t *const *now_bgr,
+                                                      const ea_ros_frame_params *prm) {
+  return batch_set_frames_ros_pyramid(levels, nlevels, ref_bgr, ref_depth, now_bgr, prm, true);
+}
+
+// The halving chain by itself (host in, host out), the sibling of ea_resize_half: levels skip .. skip + keep - 1 of one
+// frame, level k = k halvings, from one upload.  Level 0 (skip == 0) is the frame as handed in; kind 1 replaces NaN on the
+// chain's first step only, so from level 1 on.
+extern "C" int ea_resize_half_levels(int device, int kind, const void *src, int height, int width, int skip, int keep,
+                                     void *const *dst) {
+  if (!src || !dst) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (kind < 0 || kind > 2) return fail(EA_ERR_INVALID_ARG, "kind must be 0 (bgr8), 1 (float32, NaN -> 0) or 2 (float32)");
+  if (skip < 0 || keep < 1 || skip + keep - 1 > 8) return fail(EA_ERR_INVALID_ARG, "skip >= 0, keep >= 1, skip + keep - 1 <= 8");
+  const int T = skip + keep - 1;
+  if (height < 1 || width < 1 || height > 32768 || width > 32768 || (int64_t)height * width > 0x3fffffff || (height >> T) < 1 ||
+      (width >> T) < 1 || (height % (1 << T)) != 0 || (width % (1 << T)) != 0)
+    return fail(EA_ERR_INVALID_ARG, "frame extent must be divisible by 2^(skip + keep - 1) and in range");
+  for (int k = 0; k < keep; ++k)
+    if (!dst[k]) return fail(EA_ERR_INVALID_ARG, "NULL level");
+  const size_t np = (size_t)height * width, es = kind == 0 ? 3 : 4;
+  if (skip == 0) std::memcpy(dst[0], src, np * es);
+  if (T == 0) return EA_OK;
+  int rc = check_device(device);
+  if (rc != EA_OK) return rc;
+  HIPCHK(hipSetDevice(device));
+  // the frame, and behind it room for every level 1..T at 256-aligned offsets (levels that are passed through stay unused)
+  std::vector<size_t> off((size_t)T + 1, 0);
+  size_t bytes = (np * es + 255) & ~(size_t)255;
+  for (int k = 1; k <= T; ++k) {
+    off[(size_t)k] = bytes;
+    bytes += ((np >> (2 * k)) * es + 255) & ~(size_t)255;
+  }
+  DevBuf a;
+  HIPCHK(cached_malloc(&a.p, bytes, device));
+  HIPCHK(hipMemcpy(a.p, src, np * es, hipMemcpyHostToDevice));
+  FramesLaunch f;
+  f.n = 1;
+  auto dst_of = [&](int k) -> void * { return k >= skip || k == 3 || k == 6 ? a.as<unsigned char>() + off[(size_t)k] : nullptr; };
+  if (kind == 0) rc = halving_chain<uint8_t>(f, nullptr, a.as<uint8_t>(), height, width, T, dst_of, 0);
+  else rc = halving_chain<float>(f, nullptr, a.as<float>(), height, width, T, dst_of, kind == 1 ? 1 : 0);
+  if (rc != EA_OK) return rc;
+  for (int k = std::max(skip, 1); k <= T; ++k)
+    HIPCHK(hipMemcpy(dst[k - skip], a.as<unsigned char>() + off[(size_t)k], (np >> (2 * k)) * es, hipMemcpyDeviceToHost));
+  return EA_OK;
+}
+
 // ---- the multi-stream tracker: ea_tracker for N streams pushed in lock-step, on the batched producers and ONE batch solve ----
 //
 // Every pushed frame passes the edge detection once (launch_edge_strength_frames / launch_canny_frames, the frame a grid
@@ -1258,6 +1556,19 @@ struct ea_tracker_batch {
   ea_batch *b = nullptr;    // every stream: the frame workspace is this batch's, and so is the solve when all are aligned
   std::vector<std::pair<std::vector<int>, ea_batch *>> subs;  // (streams, their batch): the solves of fewer than all streams
   int flavour = 0, halvings = 0, device = 0;
+  // ea_tracker_batch_create_pyramid: level 0 is probs / b above; coarse[l - 1] holds level l = 1 .. levels - 1 -- its problems,
+  // the batch over them and its sub-batches
+  struct Level {
+    std::vector<ea_problem *> probs;
+    ea_batch *b = nullptr;
+    std::vector<std::pair<std::vector<int>, ea_batch *>> subs;
+  };
+  int levels = 1;
+  std::vector<Level> coarse;
+  std::vector<ea_summary> last_sums;  // levels x streams, level-major: ea_tracker_batch_last_summaries
+  const std::vector<ea_problem *> &level_probs(int l) const { return l == 0 ? probs : coarse[(size_t)l - 1].probs; }
+  ea_batch *level_batch(int l) const { return l == 0 ? b : coarse[(size_t)l - 1].b; }
+  std::vector<std::pair<std::vector<int>, ea_batch *>> &level_subs(int l) { return l == 0 ? subs : coarse[(size_t)l - 1].subs; }
   bool cov_on = false;
   ea_covariance_options cov_opt{};
   double sigma_rot = 0.0, sigma_trans = 0.0;
@@ -1266,27 +1577,44 @@ struct ea_tracker_batch {
   int64_t pushes = 0;
 };
 
-extern "C" int ea_tracker_batch_create(ea_tracker_batch **out, const ea_camera *cams, int count, int dtype, int device, int flavour,
-                                       int halvings) {
+static int tracker_batch_create(ea_tracker_batch **out, const ea_camera *cams, int count, int levels, int dtype, int device,
+                                int flavour, int halvings) {
   if (!out || !cams) return fail(EA_ERR_INVALID_ARG, "NULL argument");
   if (count < 1 || count > 65535) return fail(EA_ERR_INVALID_ARG, "a multi-stream tracker takes 1..65535 streams");
   if (flavour < 0 || flavour > 2) return fail(EA_ERR_INVALID_ARG, "unknown pre-processing flavour");
   if (halvings < 0 || halvings > 8) return fail(EA_ERR_INVALID_ARG, "halvings out of range");
   if (flavour != 2 && halvings != 0) return fail(EA_ERR_INVALID_ARG, "halvings belong to the ROS flavour (2) only");
+  if (levels < 1 || halvings + levels - 1 > 8) return fail(EA_ERR_INVALID_ARG, "levels >= 1 and halvings + levels - 1 <= 8");
   ea_tracker_batch *tb = new (std::nothrow) ea_tracker_batch;
   if (!tb) return fail(EA_ERR_ALLOC, "out of host memory");
-  tb->flavour = flavour; tb->halvings = halvings; tb->device = device;
+  tb->flavour = flavour; tb->halvings = halvings; tb->device = device; tb->levels = levels;
+  tb->coarse.resize((size_t)levels - 1);
   int rc = EA_OK;
-  for (int i = 0; i < count && rc == EA_OK; ++i) {
-    ea_problem *p = nullptr;
-    rc = ea_problem_create(&p, cams + i, dtype, device);
-    if (rc == EA_OK) tb->probs.push_back(p);
+  for (int l = 0; l < levels && rc == EA_OK; ++l) {
+    std::vector<ea_problem *> &probs = l == 0 ? tb->probs : tb->coarse[(size_t)l - 1].probs;
+    for (int i = 0; i < count && rc == EA_OK; ++i) {
+      ea_problem *p = nullptr;
+      rc = ea_problem_create(&p, cams + (size_t)l * count + i, dtype, device);
+      if (rc == EA_OK) probs.push_back(p);
+    }
+    if (rc == EA_OK) rc = ea_batch_create(l == 0 ? &tb->b : &tb->coarse[(size_t)l - 1].b, probs.data(), count);
   }
-  if (rc == EA_OK) rc = ea_batch_create(&tb->b, tb->probs.data(), count);
   if (rc != EA_OK) { ea_tracker_batch_destroy(tb); return rc; }
   tb->st.resize((size_t)count);
+  tb->last_sums.resize((size_t)levels * count);
+  std::memset(tb->last_sums.data(), 0, tb->last_sums.size() * sizeof(ea_summary));
   *out = tb;
   return EA_OK;
+}
+
+extern "C" int ea_tracker_batch_create(ea_tracker_batch **out, const ea_camera *cams, int count, int dtype, int device, int flavour,
+                                       int halvings) {
+  return tracker_batch_create(out, cams, count, 1, dtype, device, flavour, halvings);
+}
+
+extern "C" int ea_tracker_batch_create_pyramid(ea_tracker_batch **out, const ea_camera *cams, int count, int levels, int dtype,
+                                               int device, int halvings) {
+  return tracker_batch_create(out, cams, count, levels, dtype, device, /*flavour=*/2, halvings);
 }
 
 extern "C" void ea_tracker_batch_destroy(ea_tracker_batch *tb) {
@@ -1294,6 +1622,11 @@ extern "C" void ea_tracker_batch_destroy(ea_tracker_batch *tb) {
   for (auto &s : tb->subs) ea_batch_destroy(s.second);
   ea_batch_destroy(tb->b);
   for (ea_problem *p : tb->probs) ea_problem_destroy(p);
+  for (ea_tracker_batch::Level &lv : tb->coarse) {
+    for (auto &s : lv.subs) ea_batch_destroy(s.second);
+    ea_batch_destroy(lv.b);
+    for (ea_problem *p : lv.probs) ea_problem_destroy(p);
+  }
   delete tb;
 }
 
@@ -1303,10 +1636,23 @@ extern "C" ea_problem *ea_tracker_batch_problem(ea_tracker_batch *tb, int i) {
   return tb && i >= 0 && (size_t)i < tb->probs.size() ? tb->probs[(size_t)i] : nullptr;
 }
 
+extern "C" ea_problem *ea_tracker_batch_level_problem(ea_tracker_batch *tb, int level, int i) {
+  return tb && level >= 0 && level < tb->levels && i >= 0 && (size_t)i < tb->probs.size() ? tb->level_probs(level)[(size_t)i] : nullptr;
+}
+
+extern "C" int ea_tracker_batch_last_summaries(ea_tracker_batch *tb, int i, ea_summary *out) {
+  if (!tb || !out) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (i < 0 || (size_t)i >= tb->st.size()) return fail(EA_ERR_INVALID_ARG, "no such stream");
+  for (int l = 0; l < tb->levels; ++l) out[l] = tb->last_sums[(size_t)l * tb->st.size() + (size_t)i];
+  return EA_OK;
+}
+
 // a stream without a reference: the next push starts a fresh chain for it
 static void tracker_stream_drop(ea_tracker_batch *tb, size_t i) {
-  (void)reserve_points(tb->probs[i], 0);
-  tb->probs[i]->version++;
+  for (int l = 0; l < tb->levels; ++l) {
+    (void)reserve_points(tb->level_probs(l)[i], 0);
+    tb->level_probs(l)[i]->version++;
+  }
   tb->st[i].frames = 0;
   tb->st[i].cov_valid = false;
 }
@@ -1324,21 +1670,22 @@ static int tracker_batch_fail(ea_tracker_batch *tb, int rc) {
 
 // the batch that solves exactly the streams in `members`: the tracker's own when that is all of them, else one of the few
 // sub-batches it keeps (the same streams tend to be aligned push after push; the oldest makes room)
-static int tracker_batch_solver(ea_tracker_batch *tb, const std::vector<int> &members, ea_batch **out) {
-  if (members.size() == tb->probs.size()) { *out = tb->b; return EA_OK; }
-  for (size_t k = 0; k < tb->subs.size(); ++k)
-    if (tb->subs[k].first == members) { *out = tb->subs[k].second; return EA_OK; }
+static int tracker_batch_solver(ea_tracker_batch *tb, const std::vector<int> &members, ea_batch **out, int level = 0) {
+  if (members.size() == tb->probs.size()) { *out = tb->level_batch(level); return EA_OK; }
+  std::vector<std::pair<std::vector<int>, ea_batch *>> &subs = tb->level_subs(level);
+  for (size_t k = 0; k < subs.size(); ++k)
+    if (subs[k].first == members) { *out = subs[k].second; return EA_OK; }
   constexpr size_t kKeptSubBatches = 4;
-  if (tb->subs.size() >= kKeptSubBatches) {
-    ea_batch_destroy(tb->subs.front().second);
-    tb->subs.erase(tb->subs.begin());
+  if (subs.size() >= kKeptSubBatches) {
+    ea_batch_destroy(subs.front().second);
+    subs.erase(subs.begin());
   }
   std::vector<ea_problem *> probs;
-  for (int i : members) probs.push_back(tb->probs[(size_t)i]);
+  for (int i : members) probs.push_back(tb->level_probs(level)[(size_t)i]);
   ea_batch *sub = nullptr;
   const int rc = ea_batch_create(&sub, probs.data(), (int)probs.size());
   if (rc != EA_OK) return rc;
-  tb->subs.emplace_back(members, sub);
+  subs.emplace_back(members, sub);
   *out = sub;
   return EA_OK;
 }
@@ -1348,11 +1695,11 @@ static int tracker_batch_solver(ea_tracker_batch *tb, const std::vector<int> &me
 // plain kernels' to rounding only.  Streams are therefore grouped by what their own problem needs (term_variant), so that each
 // is solved by the kernels, and to the bits, of a tracker of its own; a problem with further terms is a group by itself.
 // Streams with the same settings -- the usual case -- are one group: one solve.
-static std::vector<std::vector<int>> tracker_batch_groups(const ea_tracker_batch *tb, const std::vector<int> &al) {
+static std::vector<std::vector<int>> tracker_batch_groups(const ea_tracker_batch *tb, const std::vector<int> &al, int level = 0) {
   std::vector<std::vector<int>> groups;
   std::vector<int> keys;
   for (int i : al) {
-    const ea_problem *p = tb->probs[(size_t)i];
+    const ea_problem *p = tb->level_probs(level)[(size_t)i];
     const int key = p->terms.empty() ? term_variant(p) : -1 - i;
     size_t g = 0;
     while (g < keys.size() && keys[g] != key) ++g;
@@ -1394,6 +1741,7 @@ static int tracker_batch_push(ea_tracker_batch *tb, const uint8_t *const *bgr, c
   for (size_t i = 0; i < n; ++i) tb->st[i].cov_valid = false;
   if (aligned) std::fill(aligned, aligned + n, 0);
   if (summaries) std::memset(summaries, 0, n * sizeof(*summaries));
+  std::memset(tb->last_sums.data(), 0, tb->last_sums.size() * sizeof(ea_summary));
   auto failed = [tb](int code) { return tracker_batch_fail(tb, code); };
 #define TBCHK(expr)                                                                                              \
   do {                                                                                                           \
@@ -1495,6 +1843,7 @@ static int tracker_batch_push(ea_tracker_batch *tb, const uint8_t *const *bgr, c
     for (size_t k = 0; k < ng; ++k) {
       const size_t i = (size_t)grp[k];
       if (summaries) summaries[i] = sg[k];
+      tb->last_sums[i] = sg[k];
       const bool failure = sg[k].termination == EA_FAILURE;
       ok += failure ? 0 : 1;
       // (a failed solve: the stream keeps its prior, and the covariance call below sees it at its start pose)
@@ -1552,15 +1901,217 @@ static int tracker_batch_push(ea_tracker_batch *tb, const uint8_t *const *bgr, c
   return EA_OK;
 }
 
+// The push of a tracker with several levels (ea_tracker_batch_create_pyramid; the ROS flavour): tracker_batch_push's sequence
+// with every step per level.  The frames go up once and one halving chain per kind leaves every level's frame in that level's
+// workspace (pyramid_stage_side); on each level the frame passes the edge detection once and serves both sides.  A stream is
+// aligned by level 0's rule; a coarser level takes part in its solve when that level's reference has points and that level's
+// frame has an edge.  The solve is ea_solve_pyramid per stream, run as batch solves: the coarsest level first, on each level
+// the streams still descending that can use it, grouped by kernel family as on a single level, the pose carried down.
+static int tracker_batch_push_pyramid(ea_tracker_batch *tb, const uint8_t *const *bgr, const void *const *depth, int height,
+                                      int width, const ea_options *opt, double *q_rel, double *t_rel, ea_summary *summaries,
+                                      int *aligned, bool on_device) {
+  // every check comes before a device or a stream is touched: a rejected call leaves the tracker as it was
+  if (!tb || !bgr || !depth || !q_rel || !t_rel) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (height < 3 || width < 3 || height > 32768 || width > 32768 || (int64_t)height * width > 0x3fffffff)
+    return fail(EA_ERR_INVALID_ARG, "image extent out of range");
+  const int L = tb->levels, T = tb->halvings + L - 1;
+  int rc = check_scaled_args(height, width, T);
+  if (rc != EA_OK) return rc;
+  if ((height >> T) < 3 || (width >> T) < 3) return fail(EA_ERR_INVALID_ARG, "image extent out of range: the coarsest level is below 3 x 3");
+  int lo = 0, hi = 0;
+  rc = ros_thresholds(150.0, 100.0, &lo, &hi);
+  if (rc != EA_OK) return rc;
+  if (opt) {
+    rc = check_options(*opt);
+    if (rc != EA_OK) return rc;
+  }
+  std::vector<BatchFrames> J((size_t)L);
+  std::vector<ea_batch *> batches((size_t)L);
+  for (int l = 0; l < L; ++l) {
+    BatchFrames &j = J[(size_t)l];
+    batches[(size_t)l] = tb->level_batch(l);
+    j.ros = true; j.full_H = height; j.full_W = width; j.halvings = tb->halvings + l;
+    // (both sides of every slot are the pushed frame; the caller's device frames are looked at once, with level 0)
+    rc = batch_frames_check(batches[(size_t)l], bgr, depth, sizeof(float), bgr, nullptr, height >> j.halvings, width >> j.halvings, 1.0,
+                            on_device && l == 0, &j);
+    if (rc != EA_OK) return rc;
+    j.on_device = on_device;
+  }
+
+  const size_t n = tb->probs.size();
+  tb->pushes++;
+  tb->last_aligned = tb->last_bare = tb->last_rounds = tb->last_edge_passes = 0;
+  for (size_t i = 0; i < n; ++i) tb->st[i].cov_valid = false;
+  if (aligned) std::fill(aligned, aligned + n, 0);
+  if (summaries) std::memset(summaries, 0, n * sizeof(*summaries));
+  std::memset(tb->last_sums.data(), 0, tb->last_sums.size() * sizeof(ea_summary));
+  auto failed = [tb](int code) { return tracker_batch_fail(tb, code); };
+#define TBCHK(expr)                                                                                              \
+  do {                                                                                                           \
+    const hipError_t e_ = (expr);                                                                                \
+    if (e_ != hipSuccess) { (void)fail(EA_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); return failed(EA_ERR_HIP); } \
+  } while (0)
+#define TBRC(expr)                      \
+  do {                                  \
+    const int rc_ = (expr);             \
+    if (rc_ != EA_OK) return failed(rc_); \
+  } while (0)
+
+  FramePyramid py;
+  TBRC(pyramid_frames_begin(batches.data(), &J, tb->halvings, bgr, depth, bgr, &py));
+  // ---- the frame, once: up, down the chain, and on every level the edge pass and the current-side tail
+  for (BatchFrames &j : J) TBCHK(upload_table(&j));
+  int64_t uploads = 0;
+  TBRC(pyramid_stage_side(J, py, tb->halvings, 0, bgr, reinterpret_cast<const float *const *>(depth), &uploads));
+  for (int l = 0; l < L; ++l) {
+    BatchFrames &j = J[(size_t)l];
+    const FrameWs &ws = j.ws;
+    unsigned char *base = j.base;
+    int looks = 0;
+    tb->last_edge_passes++;
+    TBCHK(launch_canny_frames(j.f, 1, 0, lo, hi, /*l2_bgr=*/1, ws.gray.at(base), ws.mag.at(base), ws.dir.at(base), ws.label.at(base),
+                              ws.edges.at(base), ws.inv.at(base), ws.changed.at(base), j.h_flags, &looks, nullptr));
+    tb->last_rounds += looks;
+    batch_frames_set_rounds(batches[(size_t)l], looks);
+    TBRC(batch_counts_back(&j, ws.edges, 0));
+    int bare = 0;
+    j.no_image.assign(n, 0);
+    for (size_t i = 0; i < n; ++i)
+      if (j.h_totals[i] == 0) { j.no_image[i] = 1; ++bare; }
+    if (l == 0) tb->last_bare = bare;
+    batch_frames_set_without_edges(batches[(size_t)l], bare);
+    TBRC(batch_alloc_dts(&j));
+    if ((size_t)bare < n) {
+      TBCHK(upload_table(&j));
+      TBCHK(launch_chamfer_frames(j.f, ws.inv.at(base), ws.G.at(base), ws.scan.at(base), ws.dist.at(base), ws.dist.at<float>(base),
+                                  ws.minmax.at(base), nullptr));
+      TBCHK(launch_dt_store_stack(j.dtype, j.f, ws.dist.at<float>(base), ws.minmax.at(base), 1, 0.0, 255.0, nullptr));
+    }
+  }
+  // the images are complete before a solve reads them on the batches' streams, which do not wait for the null stream
+  TBCHK(hipStreamSynchronize(nullptr));
+  for (int l = 0; l < L; ++l)
+    for (size_t i = 0; i < n; ++i)
+      if (!J[(size_t)l].no_image[i]) dt_landed(tb->level_probs(l)[i]);
+
+  // ---- the solve of the aligned streams, from their last relative poses, down their usable levels
+  auto usable = [&](int l, size_t i) { return tb->level_probs(l)[i]->n > 0 && !J[(size_t)l].no_image[i]; };
+  std::vector<int> al;
+  for (size_t i = 0; i < n; ++i)
+    if (tb->st[i].frames > 0 && usable(0, i)) al.push_back((int)i);
+  const size_t na = al.size();
+  // per stream: the pose its solve started from, the one it carries down, and the one it returned
+  std::vector<double> q0(4 * n), t0(3 * n), qc(4 * n), tc(3 * n), qs(4 * n), ts(3 * n);
+  std::vector<unsigned char> stopped(n, 0);
+  for (int i : al) {
+    TrackerStream &s = tb->st[(size_t)i];
+    std::memcpy(&q0[4 * (size_t)i], s.q, sizeof(s.q));
+    std::memcpy(&t0[3 * (size_t)i], s.t, sizeof(s.t));
+    if (tb->sigma_rot > 0.0 || tb->sigma_trans > 0.0) {
+      for (int l = 0; l < L; ++l)
+        if (usable(l, (size_t)i)) TBRC(motion_prior_install(tb->level_probs(l)[(size_t)i], tb->sigma_rot, tb->sigma_trans, s.q, s.t));
+      s.motion_set = true;
+      s.installed = tb->probs[(size_t)i]->prior;
+    }
+  }
+  qc = q0; tc = t0;
+  for (int l = L - 1; l >= 0; --l) {
+    std::vector<int> members;
+    for (int i : al)
+      if (!stopped[(size_t)i] && usable(l, (size_t)i)) members.push_back(i);
+    for (const std::vector<int> &grp : tracker_batch_groups(tb, members, l)) {
+      const size_t ng = grp.size();
+      ea_batch *solver = nullptr;
+      TBRC(tracker_batch_solver(tb, grp, &solver, l));
+      std::vector<double> qg(4 * ng), tg(3 * ng);
+      std::vector<ea_summary> sg(ng);
+      for (size_t k = 0; k < ng; ++k) {
+        std::memcpy(&qg[4 * k], &qc[4 * (size_t)grp[k]], 4 * sizeof(double));
+        std::memcpy(&tg[3 * k], &tc[3 * (size_t)grp[k]], 3 * sizeof(double));
+      }
+      TBRC(ea_batch_solve(solver, opt, qg.data(), tg.data(), sg.data()));
+      for (size_t k = 0; k < ng; ++k) {
+        const size_t i = (size_t)grp[k];
+        tb->last_sums[(size_t)l * n + i] = sg[k];
+        if (summaries) summaries[i] = sg[k];  // (the finest level the descent reaches comes last)
+        if (sg[k].termination == EA_FAILURE) { stopped[i] = 1; continue; }
+        std::memcpy(&qc[4 * i], &qg[4 * k], 4 * sizeof(double));
+        std::memcpy(&tc[3 * i], &tg[3 * k], 3 * sizeof(double));
+      }
+    }
+  }
+  // (a descent that stopped in a failed level: the stream keeps its prior, as after a failed solve on a single level)
+  for (int a : al) {
+    const size_t i = (size_t)a;
+    std::memcpy(&qs[4 * i], stopped[i] ? &q0[4 * i] : &qc[4 * i], 4 * sizeof(double));
+    std::memcpy(&ts[3 * i], stopped[i] ? &t0[3 * i] : &tc[3 * i], 3 * sizeof(double));
+  }
+  if (tb->cov_on)
+    // at level 0, at the returned poses, per kernel family as the solves; a stopped descent has no pose to take one at (why = 4)
+    for (const std::vector<int> &grp : tracker_batch_groups(tb, al, 0)) {
+      const size_t ng = grp.size();
+      ea_batch *solver = nullptr;
+      TBRC(tracker_batch_solver(tb, grp, &solver, 0));
+      std::vector<double> qg(4 * ng), tg(3 * ng);
+      size_t ok = 0;
+      for (size_t k = 0; k < ng; ++k) {
+        std::memcpy(&qg[4 * k], &qs[4 * (size_t)grp[k]], 4 * sizeof(double));
+        std::memcpy(&tg[3 * k], &ts[3 * (size_t)grp[k]], 3 * sizeof(double));
+        ok += stopped[(size_t)grp[k]] ? 0 : 1;
+      }
+      std::vector<ea_covariance> covs(ng);
+      std::memset(covs.data(), 0, ng * sizeof(ea_covariance));
+      if (ok > 0) TBRC(ea_batch_covariance(solver, qg.data(), tg.data(), &tb->cov_opt, covs.data()));
+      for (size_t k = 0; k < ng; ++k) {
+        TrackerStream &s = tb->st[(size_t)grp[k]];
+        s.cov_last = covs[k];
+        if (stopped[(size_t)grp[k]]) {
+          std::memset(&s.cov_last, 0, sizeof(s.cov_last));
+          s.cov_last.why = 4;
+        }
+        s.cov_valid = true;
+      }
+    }
+
+  // ---- on every level the frame's edge points become every stream's reference
+  for (int l = 0; l < L; ++l) {
+    BatchFrames &j = J[(size_t)l];
+    TBRC(batch_ref_room(&j));
+    TBCHK(upload_table(&j));
+    if (j.max_total > 0) TBCHK(launch_edge_scatter_ros_stack(j.dtype, j.f, j.ws.edges.at(j.base), j.ws.counts.at(j.base), nullptr));
+    TBCHK(launch_depth_weights_frames(j.dtype, j.f, j.max_weighted, nullptr));
+  }
+  TBCHK(hipDeviceSynchronize());
+#undef TBCHK
+#undef TBRC
+  for (int l = 0; l < L; ++l)
+    for (size_t i = 0; i < n; ++i) ref_points_landed(tb->level_probs(l)[i], J[(size_t)l].slots[i].capacity);
+  for (int a : al) {
+    const size_t i = (size_t)a;
+    std::memcpy(tb->st[i].q, &qs[4 * i], sizeof(tb->st[i].q));
+    std::memcpy(tb->st[i].t, &ts[3 * i], sizeof(tb->st[i].t));
+    if (aligned) aligned[i] = 1;
+  }
+  for (size_t i = 0; i < n; ++i) {
+    std::memcpy(q_rel + 4 * i, tb->st[i].q, sizeof(tb->st[i].q));
+    std::memcpy(t_rel + 3 * i, tb->st[i].t, sizeof(tb->st[i].t));
+    tb->st[i].frames += 1;
+  }
+  tb->last_aligned = (int)na;
+  return EA_OK;
+}
+
 extern "C" int ea_tracker_batch_push_frames(ea_tracker_batch *tb, const uint8_t *const *bgr, const void *const *depth, int height,
                                             int width, double z_scaling, const ea_options *opt, double *q_rel, double *t_rel,
                                             ea_summary *summaries, int *aligned) {
+  if (tb && tb->levels > 1) return tracker_batch_push_pyramid(tb, bgr, depth, height, width, opt, q_rel, t_rel, summaries, aligned, false);
   return tracker_batch_push(tb, bgr, depth, height, width, z_scaling, opt, q_rel, t_rel, summaries, aligned, false);
 }
 
 extern "C" int ea_tracker_batch_push_frames_device(ea_tracker_batch *tb, const uint8_t *const *bgr, const void *const *depth,
                                                    int height, int width, double z_scaling, const ea_options *opt, double *q_rel,
                                                    double *t_rel, ea_summary *summaries, int *aligned) {
+  if (tb && tb->levels > 1) return tracker_batch_push_pyramid(tb, bgr, depth, height, width, opt, q_rel, t_rel, summaries, aligned, true);
   return tracker_batch_push(tb, bgr, depth, height, width, z_scaling, opt, q_rel, t_rel, summaries, aligned, true);
 }
 
@@ -1605,7 +2156,7 @@ extern "C" int ea_tracker_batch_set_motion_prior(ea_tracker_batch *tb, double si
   if (sigma_rot == 0.0 && sigma_trans == 0.0)
     for (size_t i = 0; i < tb->st.size(); ++i)
       if (tb->st[i].motion_set) {
-        motion_prior_clear(tb->probs[i], tb->st[i].installed);
+        for (int l = 0; l < tb->levels; ++l) motion_prior_clear(tb->level_probs(l)[i], tb->st[i].installed);
         tb->st[i].motion_set = false;
       }
   tb->sigma_rot = sigma_rot;
@@ -1621,6 +2172,7 @@ extern "C" int ea_tracker_batch_get_info(const ea_tracker_batch *tb, const char 
   else if (k == "hysteresis_rounds") *value = tb->last_rounds;
   else if (k == "edge_passes") *value = tb->last_edge_passes;
   else if (k == "frames") *value = tb->pushes;
+  else if (k == "levels") *value = tb->levels;
   else return fail(EA_ERR_INVALID_ARG, "unknown info key: " + k);
   return EA_OK;
 }

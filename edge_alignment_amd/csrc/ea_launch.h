@@ -125,6 +125,11 @@ struct FramesLaunch {
   size_t stride = 0;
   const FrameSlot *slots = nullptr;  // device
 };
+// launch_halving_chain_*: where each step of one launch leaves its level (NULL: nowhere)
+constexpr int kChainSteps = 3;
+struct ChainLevels {
+  void *dst[kChainSteps] = {nullptr, nullptr, nullptr};
+};
 struct RowsLaunch {
   int dtype = 0, variant = 0, buffer_loads = 0, img32 = 0;
   int layout = 0;   // 0 = J row-major [rows][6], 1 = column-major [6][rows]
@@ -266,6 +271,16 @@ hipError_t launch_resize_half_bgr8_stack(const FramesLaunch &f, const uint8_t *c
                                          uint8_t *dst, hipStream_t s);
 hipError_t launch_resize_half_f32_stack(const FramesLaunch &f, const float *const *table, const float *src, int H, int W, float *dst,
                                         int nan_to_zero, hipStream_t s);
+// The halving chain (ea_batch_set_frames_ros_pyramid): `steps` (1..kChainSteps) successive halvings of f.n frames of H x W
+// pixels (both multiples of 2^steps) from one read of the source, which is named as for the stack launchers above.  lv.dst[k]:
+// frame 0's pointer for the level step k produces, (H >> (k + 1)) x (W >> (k + 1)), frame z's at z * f.stride bytes from it;
+// NULL = the level is passed through in LDS and never written.  The last step's level is always written.  Every level is,
+// bit for bit, what k + 1 launches of the stack launchers leave (NaN -> 0, where asked for, on the source only).  f: n and
+// stride only.
+hipError_t launch_halving_chain_bgr8(const FramesLaunch &f, const uint8_t *const *table, const uint8_t *src, int H, int W, int steps,
+                                     const ChainLevels &lv, hipStream_t s);
+hipError_t launch_halving_chain_f32(const FramesLaunch &f, const float *const *table, const float *src, int H, int W, int steps,
+                                    const ChainLevels &lv, int nan_to_zero, hipStream_t s);
 // ea_kernels.hip: ea_depth_weights_kernel's body for the frames whose slot has power > 0, max_n = the largest capacity among them
 hipError_t launch_depth_weights_frames(int dtype, const FramesLaunch &f, long long max_n, hipStream_t s);
 }  // namespace ea

@@ -862,6 +862,97 @@ __global__ void ea_resize_half_f32_stack_kernel(const float *const *__restrict__
   resize_half_f32_body(table ? table[blockIdx.z] : frame_ptr(src, stride), H2, W2, frame_ptr(dst, stride), nan_to_zero);
 }
 
+// ---- the halving chain: up to kChainSteps successive 2 x 2 means of every frame of a batched call from ONE read of the
+// source (ea_batch_set_frames_ros_pyramid, ea_resize_half_levels).  A workgroup stages a kChainTileH x kChainTileW pixel tile
+// of the source in LDS and halves it there step by step, each step the arithmetic of the bodies above -- the colour bytes
+// rounded to uint8 and fed on as uint8, the floats in the same order of additions -- so that every level holds the bits
+// `step` launches of ea_resize_half_*_stack_kernel leave.  A level that is kept goes to HBM as it is produced
+// (lv.dst[step], frame 0's pointer; frame z's lies z * stride bytes on); a level that is only passed through (NULL) never
+// leaves LDS.  Frame z's source as in the stack kernels: table[z], or src + z * stride.
+// The tile is 32 x 64 pixels: 8 x 8 source pixels make one pixel of the third level, so the tile's edges fall between the
+// means of every step, and a frame whose extent is a multiple of 2^steps cuts the last tile of a row or column between
+// them too -- an output pixel lies inside its level exactly when all the source pixels under it lie inside the frame, which
+// is why pixels outside are neither loaded nor stored and what LDS holds in their place is never looked at.  LDS: the tile
+// and the first step's output, then the two in turn (a step's input is free once the barrier behind the next step's reads
+// has passed): 7.5 KiB for colour, 10 KiB for float, so several workgroups share a CU.  Colour rows are 192 bytes of the
+// tile: they are fetched as dwords when the frame's base and pitch allow it (W a multiple of four and a frame aligned to
+// four bytes: every frame the library uploads; a caller's device frame may be anywhere) and as bytes otherwise; stores are
+// one element per lane along a row, the pattern of the single-step kernels.
+constexpr int kChainTileH = 32, kChainTileW = 64;
+
+__device__ __forceinline__ uint8_t chain_mean(uint8_t a, uint8_t b, uint8_t c, uint8_t d) {
+  return (uint8_t)(((int)a + (int)b + (int)c + (int)d + 2) >> 2);
+}
+__device__ __forceinline__ float chain_mean(float a, float b, float c, float d) {
+  return __fmul_rn(__fadd_rn(__fadd_rn(a, b), __fadd_rn(c, d)), 0.25f);
+}
+
+// E: the element, C: elements per pixel.  H, W: the source's extent, both multiples of 2^steps.
+template <typename E, int C>
+__device__ __forceinline__ void halving_chain_body(const E *__restrict__ src, int H, int W, int steps, const ChainLevels &lv,
+                                                   size_t stride, int nan_to_zero) {
+  constexpr int RE = kChainTileW * C;  // elements in a row of the tile
+  __shared__ __attribute__((aligned(16))) E lds_a[kChainTileH * RE];
+  __shared__ __attribute__((aligned(16))) E lds_b[(kChainTileH / 2) * (RE / 2)];
+  const int x0 = blockIdx.x * kChainTileW, y0 = blockIdx.y * kChainTileH;
+  const int rows = min(kChainTileH, H - y0), re = min(kChainTileW, W - x0) * C;  // the part of the tile inside the frame
+  const size_t gp = (size_t)W * C;
+  const E *g = src + (size_t)y0 * gp + (size_t)x0 * C;
+  bool by_dwords = false;
+  if constexpr (sizeof(E) == 1) by_dwords = ((reinterpret_cast<uintptr_t>(g) | gp) & 3) == 0;  // (then re is a multiple of 4 too)
+  if (by_dwords) {
+    constexpr int RD = RE / 4;
+    for (int i = threadIdx.x; i < kChainTileH * RD; i += blockDim.x) {
+      const int r = i / RD, k = i - r * RD;
+      if (r < rows && 4 * k < re)
+        reinterpret_cast<uint32_t *>(lds_a)[i] = reinterpret_cast<const uint32_t *>(g + (size_t)r * gp)[k];
+    }
+  } else {
+    for (int i = threadIdx.x; i < kChainTileH * RE; i += blockDim.x) {
+      const int r = i / RE, k = i - r * RE;
+      if (r < rows && k < re) {
+        E v = g[(size_t)r * gp + k];
+        if constexpr (sizeof(E) == 4) {  // depth.setTo(0, depth != depth) before the first resize (src/ea.cpp:56-58)
+          if (nan_to_zero) v = (v != v) ? 0.0f : v;
+        }
+        lds_a[i] = v;
+      }
+    }
+  }
+  __syncthreads();
+  const E *in = lds_a;
+  E *out = lds_b;
+#pragma unroll
+  for (int s = 0; s < kChainSteps; ++s) {
+    if (s >= steps) break;  // (uniform)
+    const int ip = RE >> s, op = RE >> (s + 1), th = kChainTileH >> (s + 1);  // pitches in elements, rows out
+    const int Hs = H >> (s + 1), Ws = W >> (s + 1), gy0 = y0 >> (s + 1), gx0 = x0 >> (s + 1);
+    E *dst = lv.dst[s] ? frame_ptr(static_cast<E *>(lv.dst[s]), stride) : nullptr;
+    for (int i = threadIdx.x; i < th * op; i += blockDim.x) {
+      const int r = i / op, k = i - r * op, u = k / C;
+      const E *p = in + (2 * r) * ip + 2 * u * C + (k - u * C);
+      const E v = chain_mean(p[0], p[C], p[ip], p[ip + C]);
+      out[i] = v;
+      if (dst && gy0 + r < Hs && gx0 + u < Ws) dst[((size_t)(gy0 + r) * Ws + gx0) * C + k] = v;
+    }
+    __syncthreads();
+    E *freed = const_cast<E *>(in);
+    in = out;
+    out = freed;
+  }
+}
+
+__global__ __launch_bounds__(256) void ea_halving_chain_bgr8_levels_kernel(const uint8_t *const *__restrict__ table,
+                                                                           const uint8_t *src, int H, int W, int steps,
+                                                                           ChainLevels lv, size_t stride) {
+  halving_chain_body<uint8_t, 3>(table ? table[blockIdx.z] : frame_ptr(src, stride), H, W, steps, lv, stride, 0);
+}
+__global__ __launch_bounds__(256) void ea_halving_chain_f32_levels_kernel(const float *const *__restrict__ table, const float *src,
+                                                                          int H, int W, int steps, ChainLevels lv, int nan_to_zero,
+                                                                          size_t stride) {
+  halving_chain_body<float, 1>(table ? table[blockIdx.z] : frame_ptr(src, stride), H, W, steps, lv, stride, nan_to_zero);
+}
+
 __global__ void ea_nan_to_zero_kernel(float *__restrict__ img, size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) { const float v = img[i]; if (v != v) img[i] = 0.0f; }
@@ -1173,6 +1264,29 @@ hipError_t launch_resize_half_f32_stack(const FramesLaunch &f, const float *cons
   const int H2 = H / 2, W2 = W / 2;
   hipLaunchKernelGGL(ea_resize_half_f32_stack_kernel, dim3((W2 + 255) / 256, H2, f.n), dim3(256), 0, s, table, src, H2, W2, dst,
                      nan_to_zero, f.stride);
+  return hipGetLastError();
+}
+
+static bool chain_ok(const FramesLaunch &f, const void *table, const void *src, int H, int W, int steps, const ChainLevels &lv) {
+  if (f.n < 1 || f.n > 65535 || f.stride % 256 != 0 || (!table && !src)) return false;
+  if (steps < 1 || steps > kChainSteps || !lv.dst[steps - 1]) return false;  // (the last step's level is what the launch is for)
+  const int m = (1 << steps) - 1;
+  return H > m && W > m && !(H & m) && !(W & m) && H <= 32768 && W <= 32768;
+}
+
+hipError_t launch_halving_chain_bgr8(const FramesLaunch &f, const uint8_t *const *table, const uint8_t *src, int H, int W, int steps,
+                                     const ChainLevels &lv, hipStream_t s) {
+  if (!chain_ok(f, table, src, H, W, steps, lv)) return hipErrorInvalidValue;
+  const dim3 grid((W + kChainTileW - 1) / kChainTileW, (H + kChainTileH - 1) / kChainTileH, f.n);
+  hipLaunchKernelGGL(ea_halving_chain_bgr8_levels_kernel, grid, dim3(256), 0, s, table, src, H, W, steps, lv, f.stride);
+  return hipGetLastError();
+}
+
+hipError_t launch_halving_chain_f32(const FramesLaunch &f, const float *const *table, const float *src, int H, int W, int steps,
+                                    const ChainLevels &lv, int nan_to_zero, hipStream_t s) {
+  if (!chain_ok(f, table, src, H, W, steps, lv)) return hipErrorInvalidValue;
+  const dim3 grid((W + kChainTileW - 1) / kChainTileW, (H + kChainTileH - 1) / kChainTileH, f.n);
+  hipLaunchKernelGGL(ea_halving_chain_f32_levels_kernel, grid, dim3(256), 0, s, table, src, H, W, steps, lv, nan_to_zero, f.stride);
   return hipGetLastError();
 }
 

@@ -827,6 +827,43 @@ int ea_batch_set_frames_ros(ea_batch *b, const uint8_t *const *ref_bgr, const fl
                             const uint8_t *const *now_bgr, const ea_ros_frame_params *prm);
 int ea_batch_set_frames_ros_device(ea_batch *b, const uint8_t *const *ref_bgr, const float *const *ref_depth,
                                    const uint8_t *const *now_bgr, const ea_ros_frame_params *prm);
+/* ---- the batched ROS producers over pyramid levels: N frame pairs, L levels, frames handed in once ----------------------
+ * levels[l] is a batch of the same N problems' level-l counterparts (levels[0] the finest, working extent full >>
+ * (prm->halvings + l); cameras are the caller's, scaled per level as for ea_solve_pyramid).  One call leaves EVERY levels[l],
+ * bit for bit, in the state
+ *     ea_batch_set_frames_ros(levels[l], ref_bgr, ref_depth, now_bgr, &prm_l),   prm_l.halvings = prm->halvings + l
+ * leaves it in -- points and their order, padded images and float32 mirrors, depth weights, cameras untouched, versions, terms
+ * -- while each side's frames go up ONCE (not at all for device frames) and one halving chain per side and kind produces all
+ * levels from one read of the full-size frames: a workgroup stages a tile in LDS, halves it up to three times there and
+ * writes each kept level straight into that level's frame workspace; the first prm->halvings - 1 steps never reach memory.
+ * The arithmetic is ea_resize_half's step by step (colour rounded to uint8 at every level, NaN -> 0 on the first step from the
+ * full-size depth frame only; with halvings = 0 level 0 of a host frame is the uploaded frame as it is).  Behind the chain
+ * every level runs the launches and waits of ea_batch_set_frames_ros; the reference side of all levels is complete before the
+ * current side reuses the stage.  All frames pass through the workspace of levels[0]: frame_pyramid (ea_frame_ws.h).
+ *
+ * A current frame without an edge at some level leaves that level's problem alone, as ea_batch_set_frames_ros does; the call
+ * completes everything else and returns EA_ERR_STATE naming the first (level, frame); "frames_without_edges" on each level's
+ * batch is that level's number.  ea_batch_get_info(levels[0], "frames_uploaded"): the host-to-device frame copies of the last
+ * pyramid call -- 3 N for a host call with both sides whatever nlevels is, 0 for device frames.
+ *
+ * EA_ERR_INVALID_ARG before anything is touched: everything ea_batch_set_frames_ros checks, on every level; nlevels < 1 or
+ * halvings + nlevels - 1 > 8; a full extent not divisible by 2^(halvings + nlevels - 1); a coarsest extent below 3 x 3;
+ * batches of different counts, devices or dtypes; a problem appearing twice across the levels.
+ *
+ * ea_batch_solve_pyramid is ea_solve_pyramid for every problem: one ea_batch_solve per level, the coarsest first, the poses
+ * (q: count x 4, t: count x 3) carried down.  A problem whose level ends in EA_FAILURE stops descending: its finer summaries
+ * are zeroed and its pose is what that level returned; the others go on, and get the bits of a loop of ea_batch_solve over
+ * the levels (a stopped problem rides along in the finer solves and its results are discarded; a finer counterpart with an
+ * auto-scaled loss has that scale re-estimated, nothing else of it changes).  A level's non-OK return is returned as is.
+ * summaries: nlevels x count, level-major, or NULL. */
+int ea_batch_set_frames_ros_pyramid(ea_batch *const *levels, int nlevels, const uint8_t *const *ref_bgr,
+                                    const float *const *ref_depth, const uint8_t *const *now_bgr, const ea_ros_frame_params *prm);
+int ea_batch_set_frames_ros_pyramid_device(ea_batch *const *levels, int nlevels, const uint8_t *const *ref_bgr,
+                                           const float *const *ref_depth, const uint8_t *const *now_bgr,
+                                           const ea_ros_frame_params *prm);
+int ea_batch_solve_pyramid(ea_batch *const *levels, int nlevels, const ea_options *opt, double *q, double *t,
+                           ea_summary *summaries);
+
 /* ---- multi-stream frame tracker: N cameras pushed in lock-step ---------------------------------------------------------
  * ea_tracker for `count` independent streams of one extent (N cameras; BASELINE configuration C4's 32 pairs per GPU): every
  * push takes one frame per stream, runs the batched producers ONCE per frame -- the frame a grid dimension of each launch,
@@ -892,10 +929,35 @@ int ea_tracker_batch_set_covariance(ea_tracker_batch *tb, const ea_covariance_op
 int ea_tracker_batch_last_covariance(ea_tracker_batch *tb, int i, ea_covariance *out);
 int ea_tracker_batch_set_motion_prior(ea_tracker_batch *tb, double sigma_rot, double sigma_trans);
 int ea_tracker_batch_get_info(const ea_tracker_batch *tb, const char *key, int64_t *value);
+/* Coarse-to-fine multi-stream tracking (flavour 2 only): `levels` pyramid levels per stream, level l working at (height,
+ * width) >> (halvings + l).  cams: levels x count, level-major, each the caller's intrinsics at that level's working extent.
+ * ea_tracker_batch_create(..., halvings) is levels = 1; the push calls keep their signatures.  Per push the frames go up once,
+ * one halving chain produces every level (ea_batch_set_frames_ros_pyramid), and on every level the frame passes the edge
+ * detection once and serves both sides: "edge_passes" is `levels`; "levels" is a key of its own; "frames_without_edges" and
+ * the ALIGNED rule are level 0's.  A coarser level is usable for a stream when that level's reference has points and that
+ * level's frame has an edge.  An aligned stream's result is ea_solve_pyramid over its usable levels, coarsest first, from its
+ * last relative pose: the motion prior, if set, is installed on every usable level's problem at that pose; a level ending in
+ * EA_FAILURE stops the descent and the stream keeps its prior; the covariance is level 0's at the returned pose; summaries[i]
+ * is the summary of the finest level the descent reached, ea_tracker_batch_last_summaries(i) gives all `levels` of them (level
+ * 0 first, zeros for levels not solved; with levels = 1 the one summary of the push).  On each level the streams to solve are
+ * grouped by kernel family and solved through that level's (sub-)batches; afterwards every level's edge points become that
+ * level's reference.  Reset and a failure past the checks drop every level.  Loss, auto-scale, depth weighting and constant
+ * masks are whatever the caller sets on each level's problem (ea_tracker_batch_level_problem; level 0 ==
+ * ea_tracker_batch_problem).  EA_ERR_INVALID_ARG from the push as before, with the extent divisible by 2^(halvings + levels - 1)
+ * and the coarsest level at least 3 x 3; from create_pyramid for levels < 1 or halvings + levels - 1 > 8. */
+int ea_tracker_batch_create_pyramid(ea_tracker_batch **out, const ea_camera *cams, int count, int levels, int dtype, int device,
+                                    int halvings);
+ea_problem *ea_tracker_batch_level_problem(ea_tracker_batch *tb, int level, int i);
+int ea_tracker_batch_last_summaries(ea_tracker_batch *tb, int i, ea_summary *out /* levels entries */);
 
 /* the half-resolution step by itself, host in / host out: kind 0 = bgr8 (height x width x 3 bytes), 1 = float32 with
  * NaN -> 0 first, 2 = float32 as is; dst = (height / 2) x (width / 2); height and width even */
 int ea_resize_half(int device, int kind, const void *src, int height, int width, void *dst);
+/* levels skip .. skip + keep - 1 of the halving chain of one frame (level k = k halvings) from one upload and one read of the
+ * frame per three steps; kind as ea_resize_half; dst[j]: (height >> (skip + j)) x (width >> (skip + j)); height, width
+ * divisible by 2^(skip + keep - 1), at most 8 steps.  skip = 0 returns the frame itself as level 0; kind 1 replaces NaN on
+ * the first step only, so from level 1 on.  Every level holds the bits of ea_resize_half applied that many times. */
+int ea_resize_half_levels(int device, int kind, const void *src, int height, int width, int skip, int keep, void *const *dst);
 /* read back what the problem holds in HBM: points (n x 3 doubles), DT image (H x W doubles, [v][u]) */
 int ea_problem_get_points(ea_problem *p, double *xyz, int64_t capacity);
 int ea_problem_get_dt(ea_problem *p, double *image, int *height, int *width);
