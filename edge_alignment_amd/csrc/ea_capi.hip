@@ -341,13 +341,20 @@ struct ea_batch {
   GroupDesc *d_kgroups = nullptr;
   double *d_krows = nullptr;          // flat form: two arrays of kp_rows_cap poses each; grid form: one
   int kp_rows_cap = 0;
-  int t_kp_order = 0;                 // tuning key "poses_order": 1 = an XCD walks the rows of a pose instead of the poses of a row (A/B)
+  int t_kp_order = -1;                // tuning key "poses_order": 1 = an XCD walks the rows of a pose instead of the poses of a row; -1 = the path's own (flat 0, lanes kPosesLanesOrder)
   int t_kp_xchg = kPosesWaveExchangeDefault, kp_xchg = 0, last_kp_xchg = 0;  // tuning key "poses_wave_exchange"; what kposes_shape made of it; what the last pose-batched launch ran
   // one pose per lane (ea_eval_poses_lanes_kernel): tuning key "poses_lane_per_pose" (-1 = from kPosesLanesFromK poses on, 0 =
   // never, N = from N poses on); what ea_batch_set_poses made of it for its K; what the last pose-batched call ran.  kp_Gc: the
   // launch size of the cost-only kernel, which keeps kposes_group's rule whatever the evaluation runs
   int t_kp_lanes = -1, kp_lanes = 0, last_kp_lanes = 0, kp_Gc = 0;
-  std::vector<KposesMark> kp_marks;   // the folds of the last call: sequence number, first pose, poses
+  std::vector<KposesMark> kp_marks;   // the folds of the last call: sequence number, first pose, poses (lanes path: one per group of the call)
+  // the fold inside the lanes launches (ea_poses_map.h): run partials and counters of kl_groups_cap groups, and the pinned
+  // flags of a call, one per (group of the call, problem), kl_flags_cap of them
+  double *d_kparts = nullptr;
+  unsigned int *d_kcount = nullptr;
+  int *h_kflags = nullptr, *dv_kflags = nullptr;
+  int kl_groups_cap = 0;
+  size_t kl_flags_cap = 0;
   // ea_batch_cost_resident_poses: the narrow partials of one launch (kCostPartialBytes per row of a pose), tuning key
   // "cost_form" (0: always the fall-back, the full evaluation with only the cost fetched) and what the last call ran
   unsigned char *d_kcost = nullptr;
@@ -1606,6 +1613,7 @@ extern "C" int ea_batch_eval(ea_batch *b, const double *q, const double *t, doub
 // of pose k are those ea_batch_eval returns at pose k up to rounding: the pose path cuts the points into chunks of its
 // own, kposes_shape.)  Every (point, pose) pair runs the whole per-point arithmetic; nothing is shared between poses but
 // the bytes of the points and the image, which the later poses find in the caches.
+// (From 1024 poses on an fp64 batch takes ea_eval_poses_lanes_kernel, which folds inside its launches: kposes_lanes below.)
 // Variant functors, LDS staging, wide_accumulate and terms that share a pose keep the form this one replaced: descriptor
 // and group tables replicated G times, a (chunks, G x terms) grid of ea_eval_fused_kernel's body under the name
 // ea_eval_poses_grid_kernel, and a stand-alone 1024-lane fold behind every launch.
@@ -1655,11 +1663,29 @@ static int kposes_group(const ea_batch *b, int K) {
 
 // One pose per lane (ea_eval_poses_lanes_kernel).  Whether a call of K poses takes it follows from the batch and K alone --
 // never from G or the split into launches, so that any split lands on the same bits: a flat fp64 batch at the 256 x 2 pose
-// shape whose rows leave room for one full group of 64 poses, and K at or above the threshold.  Its G is not the
-// 32 k-workgroup rule above (a launch has 64 times fewer, longer workgroups, and every launch ends on a tail of about one
-// workgroup lifetime): as many whole groups as the rows' 64 MB hold, launches of G with the remainder last
-// (poses_lanes_group_size / poses_lanes_launch_size, ea_poses_map.h).  "poses_per_launch" caps it; below 64 the launches have
-// one partly filled group each -- slow, the same bits.
+// shape whose rows leave room for one full group of 64 poses (kposes_rows_bound, the two-array bound of the flat form: the
+// eligibility is what it was), and K at or above the threshold.
+// Rows.  The path keeps ONE row array, lane-minor -- [group][row][slot][64 lanes], 16 KB per (group, row) -- because nothing
+// alternates: the rows of a launch are folded inside that launch.  Its G is "as many whole groups as 64 MB hold of rows and
+// run partials together, one group at least" (C2: (98 rows + 7 partials) x 16 KB = 1.6 MB per group, 39 groups = 2496
+// poses; at the eligibility's limit of 2048 rows one group, as before), launches of G with the remainder last
+// (poses_lanes_group_size / poses_lanes_launch_size); C2's K = 2000 is one launch.  "poses_per_launch" caps it; below 64 the
+// launches have one partly filled group each -- slow, the same bits.
+// Fold by tickets (ea_poses_map.h; lanes_tickets in ea_kernels.hip).  No workgroup waits for another.  An item stores its row
+// and adds one to the counter of its (group, problem, run), a run being kPosesRun = 16 consecutive rows of the problem
+// counted from its first; the workgroup that completes the run's count sums the run's rows in row order into a run partial
+// and adds one to the counter of (group, problem); the workgroup that completes THAT count sums the run partials in run
+// order, writes the group's 64 results of the problem into pinned memory and raises the pinned flag of (group of the call,
+// problem) to the call's sequence number.  16 rows: one workgroup reads another's rows at 60 - 120 GB/s, so a run
+// (256 KB) costs its last arrival 2 - 4 us and C2's 7 partials the problem's last arrival another 1 - 2 -- a whole group
+// (1.5 MB) in one workgroup would leave 12 - 23 us behind the last item of the call.  The counters are zeroed by a memset
+// node ahead of every launch.  A pose's sums are ((rows of run 0 in order) + (rows of run 1 in order) + ...): they depend
+// on the pose and the problem's row count, not on the lane, the company in the group, the split into launches, the item
+// order or the order of arrival.  A problem without a point has no item: the host writes its zero results and raises its
+// flags itself (kposes_collect_lanes).
+// Item order: pose-major by default (kPosesLanesOrder), the rows of a group adjacent in the list, so that groups complete
+// one after the other and the host unpacks a group while the kernel works on the later ones; "poses_order" overrides.
+constexpr int kPosesLanesOrder = 1;
 static bool kposes_lanes(const ea_batch *b, int K) {
   if (!kposes_flat(b) || b->dtype != EA_F64 || b->kp_nt != 256 || b->kp_ppt != 2) return false;
   if (kposes_rows_bound(b) < kPosesLanes) return false;
@@ -1667,10 +1693,14 @@ static bool kposes_lanes(const ea_batch *b, int K) {
   return from > 0 && K >= from;
 }
 static int kposes_group_lanes(const ea_batch *b, int K) {
-  int64_t g = std::min<int64_t>(kposes_rows_bound(b), (int64_t)1 << 20);
+  const int rows = std::max(1, b->kp_ntiles);
+  const int64_t per_group = ((int64_t)rows + poses_lanes_run_slots(rows, (int)b->probs.size())) * kPosesLanesBlock * (int64_t)sizeof(double);
+  int64_t g = std::min<int64_t>(std::max<int64_t>(1, ((int64_t)64 << 20) / per_group) * kPosesLanes, (int64_t)1 << 20);
   if (b->t_kp_G > 0) g = std::min<int64_t>(g, b->t_kp_G);
   return std::min(poses_lanes_group_size((int)g), K);
 }
+// the pose capacity kposes_tables is asked for so that its two arrays together hold the lanes path's one: whole groups of G
+static int kposes_lanes_rows_cap(int G) { return (poses_lanes_groups(G) * kPosesLanes + 1) / 2; }
 // poses per launch of the evaluation of the K resident poses (the last launch takes the remainder)
 static int kposes_per(const ea_batch *b, int K) {
   return b->kp_lanes ? poses_lanes_launch_size(K, b->kp_G) : poses_launch_size(K, b->kp_G);
@@ -1683,9 +1713,11 @@ static bool kposes_flat(const ea_batch *b) { return !b->any_variant && b->lds_by
 static void kposes_free_tables(ea_batch *b) {
   if (b->d_kblock) cached_free(b->d_kblock);
   else { cached_free(b->d_kprobs); cached_free(b->d_kgroups); }
-  cached_free(b->d_krows); cached_free(b->d_kcost);
+  cached_free(b->d_krows); cached_free(b->d_kcost); cached_free(b->d_kparts); cached_free(b->d_kcount);
+  cached_host_free(b->h_kflags);
   b->d_kblock = nullptr; b->d_kprobs = nullptr; b->d_kgroups = nullptr; b->d_krows = nullptr; b->d_kcost = nullptr;
-  b->kp_G = 0; b->kp_rows_cap = 0; b->kcost_bytes = 0;
+  b->d_kparts = nullptr; b->d_kcount = nullptr; b->h_kflags = nullptr; b->dv_kflags = nullptr;
+  b->kp_G = 0; b->kp_rows_cap = 0; b->kcost_bytes = 0; b->kl_groups_cap = 0; b->kl_flags_cap = 0;
 }
 
 // What the pose-batched launches read beside the batch's own tables, and the partial rows of G poses; the tables are rebuilt
@@ -1693,7 +1725,9 @@ static void kposes_free_tables(ea_batch *b) {
 //   flat form: ONE block [PosesRow x rows | ProblemDesc x nterms | GroupDesc x count] -- the row table (ea_poses_map.h), a
 //     copy of the descriptors right behind it (the kernel finds the table at probs - rows) and the group table in the pose
 //     path's own chunking -- built once per build of the batch, whatever G; two row arrays of G poses each, which the
-//     launches of a call alternate between (the riders of launch i + 1 read what launch i wrote).
+//     launches of a call alternate between (the riders of launch i + 1 read what launch i wrote).  The lanes path uses the
+//     same allocation as ONE lane-minor array of whole groups (kposes_lanes_rows_cap) and has run partials, counters and
+//     flags of its own (kposes_lanes_reserve).
 //   grid form: the descriptor / group tables replicated G times and one row array of G poses.
 static int kposes_tables(ea_batch *b, int G) {
   const bool fresh = b->kp_G == 0, flat = kposes_flat(b);
@@ -1759,6 +1793,31 @@ static int kposes_tables(ea_batch *b, int G) {
   return EA_OK;
 }
 
+// run partials and counters for launches of G poses, flags for a call of K (the lanes path)
+static int kposes_lanes_reserve(ea_batch *b, int G, int K) {
+  const int count = (int)b->probs.size(), rows = b->kp_ntiles, groups = poses_lanes_groups(G);
+  if (groups > b->kl_groups_cap) {
+    HIPCHK(hipStreamSynchronize(b->stream));
+    cached_free(b->d_kparts); cached_free(b->d_kcount);
+    b->d_kparts = nullptr; b->d_kcount = nullptr; b->kl_groups_cap = 0;
+    const size_t pb = std::max<size_t>(1, (size_t)groups * (size_t)poses_lanes_run_slots(rows, count)) * kPosesLanesBlock * sizeof(double);
+    HIPCHK(cached_malloc(reinterpret_cast<void **>(&b->d_kparts), pb, b->device));
+    HIPCHK(cached_malloc(reinterpret_cast<void **>(&b->d_kcount), std::max<size_t>(4, poses_lanes_counters(groups, rows, count)) * sizeof(unsigned int), b->device));
+    b->kl_groups_cap = groups;
+  }
+  const size_t nflags = (size_t)poses_lanes_call_groups(K, G) * (size_t)count;
+  if (nflags > b->kl_flags_cap) {
+    HIPCHK(hipStreamSynchronize(b->stream));
+    cached_host_free(b->h_kflags);
+    b->h_kflags = nullptr; b->dv_kflags = nullptr; b->kl_flags_cap = 0;
+    HIPCHK(cached_host_malloc(reinterpret_cast<void **>(&b->h_kflags), nflags * sizeof(int), hipHostMallocMapped, b->device));
+    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&b->dv_kflags), b->h_kflags, 0));
+    std::memset(b->h_kflags, 0, nflags * sizeof(int));  // (no sequence number is 0)
+    b->kl_flags_cap = nflags;
+  }
+  return EA_OK;
+}
+
 static int kposes_reserve(ea_batch *b, int K) {
   const size_t count = b->probs.size();
   if (K <= b->kp_cap) return EA_OK;
@@ -1786,7 +1845,8 @@ extern "C" int ea_batch_set_poses(ea_batch *b, int K, const double *q, const dou
   if (b->kp_G == 0) kposes_shape(b);   // (once per build of the batch)
   // (the cost-only kernel keeps its own launch size: the rows hold the larger of the two)
   const int lanes = kposes_lanes(b, K), Gc = kposes_group(b, K), G = lanes ? kposes_group_lanes(b, K) : Gc;
-  if ((rc = kposes_tables(b, std::max(G, Gc))) != EA_OK) return rc;
+  if ((rc = kposes_tables(b, lanes ? std::max(kposes_lanes_rows_cap(G), Gc) : std::max(G, Gc))) != EA_OK) return rc;
+  if (lanes && (rc = kposes_lanes_reserve(b, G, K)) != EA_OK) return rc;
   b->kp_G = G; b->kp_Gc = Gc; b->kp_lanes = lanes;
   const size_t n = (size_t)K * b->probs.size();
   // (the previous upload out of the same staging block has been consumed: every call below ends with its pose kernel
@@ -1831,8 +1891,8 @@ static int enqueue_resident_poses(ea_batch *b, int K, bool folds = true, bool fl
   if (b->done_seq > 0x7fffffff - (K + per - 1) / per - 2) b->done_seq = 0;  // (a call's sequence numbers do not straddle the wrap)
   const EvalLaunch shape = eval_launch(b, /*kposes=*/true);
   PosesLaunch pl;
-  pl.rows = rows; pl.order = b->t_kp_order; pl.single = b->nterms == 1; pl.exchange = b->kp_xchg;
   const bool lanes = b->kp_lanes != 0;
+  pl.rows = rows; pl.order = b->t_kp_order < 0 ? (lanes ? kPosesLanesOrder : 0) : b->t_kp_order; pl.single = b->nterms == 1; pl.exchange = b->kp_xchg;
   b->last_kp_xchg = rows > 0 && !lanes ? b->kp_xchg : 0;
   b->last_kp_lanes = rows > 0 && lanes;
   PosesFold owed;  // the fold the launches so far still owe (n = 0: none)
@@ -1846,12 +1906,25 @@ static int enqueue_resident_poses(ea_batch *b, int K, bool folds = true, bool fl
     if (folds) { owe(0, K, b->d_krows); HIPCHK(launch_poses_fold(b->kp_nt, owed, b->stream)); }
     return EA_OK;
   }
+  if (lanes) {  // one row array, the fold inside each launch; one sequence number for the call, a mark per group of the call
+    PosesTickets tk;
+    tk.on = folds; tk.count = count; tk.seq = folds ? next_done_seq(b) : 0;
+    tk.partials = b->d_kparts; tk.counters = b->d_kcount; tk.flags = b->dv_kflags;
+    for (int start = 0; start < K; start += per) {
+      pl.g = std::min(per, K - start);
+      tk.out = b->dv_kout + (size_t)start * count;
+      HIPCHK(launch_eval_poses_lanes(shape, pl, b->d_kprobs, b->d_kposes + (size_t)start * count, b->d_krows, tk, b->stream));
+      if (folds)
+        for (int p0 = 0; p0 < pl.g; p0 += kPosesLanes) b->kp_marks.push_back({tk.seq, start + p0, std::min(kPosesLanes, pl.g - p0)});
+      tk.group0 += poses_lanes_groups(pl.g);
+    }
+    return EA_OK;
+  }
   int i = 0;
   for (int start = 0; start < K; start += per, ++i) {
     double *into = b->d_krows + (size_t)(i & 1) * (size_t)b->kp_rows_cap * (size_t)rows * kAccSlots;
     pl.g = std::min(per, K - start);
-    if (lanes) HIPCHK(launch_eval_poses_lanes(shape, pl, b->d_kprobs, b->d_kposes + (size_t)start * count, into, owed, b->stream));
-    else HIPCHK(launch_eval_poses(shape, pl, b->d_kprobs, b->d_kposes + (size_t)start * count, into, owed, b->stream));
+    HIPCHK(launch_eval_poses(shape, pl, b->d_kprobs, b->d_kposes + (size_t)start * count, into, owed, b->stream));
     if (folds) owe(start, pl.g, into);
   }
   if (folds) HIPCHK(launch_poses_fold(b->kp_nt, owed, b->stream));
@@ -1873,8 +1946,54 @@ static void kposes_unpack(ea_batch *b, size_t first, size_t n, double *cost, dou
 // results of launch i are unpacked as soon as its fold has raised the flag -- launch i + 1 is still running then -- so that
 // only the last launch's remain behind the final wait.  The poll is bounded like wait_results: should a flag not show up,
 // the stream is synchronised (everything is complete then, and a device error surfaces as the error it is).
+// The lanes path: mark m is group m of the call, complete when the flags of its `count` problems have reached the call's
+// sequence number.  The groups are looked at round after round and each is unpacked as soon as it is complete, whatever the
+// order they finish in, while the kernel works on the others; what remains behind the last wait is the last group.  That
+// last wait is the stream's completion signal where "poll_results" is 0, as in the other path.  A problem without a point
+// has no work item: its zero results and its flags are written here.
+static int kposes_collect_lanes(ea_batch *b, double *cost, double *JtJ, double *Jtr, int64_t *n_invalid) {
+  const size_t count = b->probs.size();
+  const ProblemDesc *hd = reinterpret_cast<const ProblemDesc *>(b->h_desc);
+  for (size_t i = 0; i < count; ++i) {
+    if (hd[i].n > 0) continue;
+    for (size_t m = 0; m < b->kp_marks.size(); ++m) {
+      const KposesMark &mk = b->kp_marks[m];
+      for (int p = 0; p < mk.g; ++p) std::memset(b->h_kout + (size_t)(mk.start + p) * count + i, 0, sizeof(EvalOut));
+      __atomic_store_n(&b->h_kflags[poses_lanes_flag((int)m, (int)i, (int)count)], mk.seq, __ATOMIC_RELEASE);
+    }
+  }
+  std::vector<int> pending(b->kp_marks.size());
+  for (size_t m = 0; m < pending.size(); ++m) pending[m] = (int)m;
+  bool drained = false;
+  SpinWait wait(2000.0);
+  while (!pending.empty()) {
+    if (!drained && pending.size() == 1 && !b->t_poll) {
+      HIPCHK(hipStreamSynchronize(b->stream));
+      drained = true;
+    }
+    size_t kept = 0;
+    for (size_t j = 0; j < pending.size(); ++j) {
+      const int m = pending[j];
+      const KposesMark &mk = b->kp_marks[(size_t)m];
+      bool ready = true;
+      for (size_t i = 0; i < count && ready && !drained; ++i)
+        ready = seq_reached(__atomic_load_n(&b->h_kflags[poses_lanes_flag(m, (int)i, (int)count)], __ATOMIC_ACQUIRE), mk.seq);
+      if (ready) kposes_unpack(b, (size_t)mk.start * count, (size_t)mk.g * count, cost, JtJ, Jtr, n_invalid);
+      else pending[kept++] = m;
+    }
+    if (kept < pending.size()) wait.progress();
+    else if (wait.poll()) {
+      HIPCHK(hipStreamSynchronize(b->stream));
+      drained = true;
+    }
+    pending.resize(kept);
+  }
+  return EA_OK;
+}
+
 static int kposes_collect(ea_batch *b, int K, double *cost, double *JtJ, double *Jtr, int64_t *n_invalid) {
   int rc;
+  if (b->last_kp_lanes) return kposes_collect_lanes(b, cost, JtJ, Jtr, n_invalid);
   const size_t count = b->probs.size();
   size_t done = 0;
   bool drained = false;
@@ -1942,7 +2061,7 @@ static int enqueue_resident_cost(ea_batch *b, int K) {
   }
   const EvalLaunch shape = eval_launch(b, /*kposes=*/true);
   PosesLaunch pl;
-  pl.rows = rows; pl.order = b->t_kp_order; pl.single = b->nterms == 1;
+  pl.rows = rows; pl.order = std::max(0, b->t_kp_order); pl.single = b->nterms == 1;
   for (int start = 0; start < K; start += per) {
     pl.g = std::min(per, K - start);
     HIPCHK(launch_cost_poses(shape, pl, b->d_kprobs, b->d_kposes + (size_t)start * count, b->d_kcost, b->stream));
@@ -1976,8 +2095,9 @@ extern "C" int ea_batch_cost_poses(ea_batch *b, int K, const double *q, const do
 }
 
 // (ea_hip_dev.h) `reps` runs of the resident poses' launches between one event pair on the batch's stream: milliseconds
-// per run, the device's own view of the K evaluations; evaluations_only: without the fold launches (what bench.py divides
-// by the number of evaluation launches for the dominant kernel's duration); launches (nullable) = evaluation launches per run
+// per run, the device's own view of the K evaluations; evaluations_only: without the fold launches -- on the lanes path
+// without tickets and folds inside the launch -- (what bench.py divides by the number of evaluation launches for the
+// dominant kernel's duration); launches (nullable) = evaluation launches per run
 extern "C" int ea_batch_bench_resident_poses(ea_batch *b, int reps, int evaluations_only, double *ms_per_run, int *launches) {
   if (!b || !ms_per_run || reps < 1) return fail(EA_ERR_INVALID_ARG, "bad argument");
   int rc = ea_batch_eval_resident_poses(b, nullptr, nullptr, nullptr, nullptr);
@@ -3084,7 +3204,7 @@ extern "C" int ea_batch_set_tuning(ea_batch *b, const char *key, int value) {
   else if (k == "fused_iterations") { b->t_fused = value; return EA_OK; }
   else if (k == "zero_copy_poses") { b->t_zero_copy = value; return EA_OK; }
   else if (k == "poses_per_launch") { b->t_kp_G = value > 0 ? value : 0; b->kp_K = 0; return EA_OK; }  // (resident poses are dropped)
-  else if (k == "poses_order") { b->t_kp_order = value ? 1 : 0; return EA_OK; }
+  else if (k == "poses_order") { b->t_kp_order = value < 0 ? -1 : (value ? 1 : 0); return EA_OK; }
   // (0: the per-wavefront butterfly; read when the pose path is shaped, so resident poses and the pose path's tables are dropped)
   else if (k == "poses_wave_exchange") { b->t_kp_xchg = value < 0 ? kPosesWaveExchangeDefault : value != 0; b->kp_K = 0; b->kp_G = 0; return EA_OK; }
   // (read when poses are set: resident poses are dropped)
@@ -3550,7 +3670,7 @@ extern "C" int ea_batch_solve_starts(ea_batch *b, int K, const ea_options *opt_i
   a.count = count; a.rows_per_pose = rows; a.tag = tag;
   const EvalLaunch shape = eval_launch(b, /*kposes=*/true);
   PosesLaunch pl;
-  pl.rows = rows; pl.order = b->t_kp_order; pl.single = b->nterms == 1; pl.exchange = b->kp_xchg;
+  pl.rows = rows; pl.order = std::max(0, b->t_kp_order); pl.single = b->nterms == 1; pl.exchange = b->kp_xchg;
   b->last_kp_xchg = rows > 0 ? b->kp_xchg : 0;
   // iteration j over n (possibly stale) live positions: reads list j & 1, its last step launch writes list (j + 1) & 1
   auto enqueue_iteration = [&](int j, int n) -> int {

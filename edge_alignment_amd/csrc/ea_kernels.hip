@@ -1872,13 +1872,12 @@ __global__ __launch_bounds__(NT) void ea_poses_fold_kernel(PosesFold fold) {
 // in vector registers) and the wavefront walks points, which are wave-uniform and arrive through scalar loads.  Every sum
 // and the failed-functor count stay inside their lane from the first point to the last; nothing crosses lanes and no
 // barrier stands in the point loop.  A work item is (row of a pose, 64 consecutive poses of the launch) (ea_poses_map.h); the
-// row is the 512-point chunk it is in the other kernel, its partial row pose * rows + row, so riders, folds and the host
-// stay as they are.  The workgroup's four wavefronts hold the same 64 poses and walk the chunk's four sub-runs of 128
+// row is the 512-point chunk it is in the other kernel.  Its sums go lane-minor into the path's own row array and are folded
+// inside the launch (further down).  The workgroup's four wavefronts hold the same 64 poses and walk the chunk's four sub-runs of 128
 // points, two points per iteration (the paired Cauchy logarithm pairs points 2i and 2i + 1 of a sub-run), sums in the order
 // of the points; at the end the per-lane sums are added through LDS as (w0 + w1) + (w2 + w3) and lane l stores the row of
 // pose l.  The summation order differs from the other kernel's (last places), and depends on nothing but the pose and the
-// row: not on the lane, the company in the wavefront, the launch or the item order.  Four wavefronts because the riding
-// fold's summation order is that of a 256-lane workgroup.  The per-point expressions are fused_chunk's, through the same
+// row: not on the lane, the company in the wavefront, the launch or the item order.  The per-point expressions are fused_chunk's, through the same
 // functions; lanes whose pose is not a unit quaternion, or whose point fails, take their branch per lane.
 template <typename T> using CPtr = const T __attribute__((address_space(4))) *;  // read-only for the kernel: uniform loads go through the scalar cache
 constexpr int kLanesWaves = 4, kLanesSub = 512 / kLanesWaves, kLanesVals = 29;  // (28 sums + failed functors)
@@ -2014,76 +2013,190 @@ __device__ __forceinline__ void lanes_run(const ProblemDesc &pd, const PoseLite<
   }
 }
 
+// ---- the fold inside the launch: two levels of tickets (ea_poses_map.h, "the rows of the lanes path") --------------------
+// An arrival, by the whole workgroup behind its plain stores: every wavefront waits for its own stores, the barrier collects
+// them, thread 0 releases at agent scope, waits again (the fence's own wait is not relied on) and takes a ticket with a
+// relaxed add; the thread whose ticket completes `target` acquires at agent scope.  Whether the workgroup is that last
+// arrival comes back to everybody through `s_word`, a word of the LDS array the kernel already has (the barrier in front
+// of its store has every earlier reader of that array behind it).  Nobody waits for anybody: a workgroup that is not the
+// last one leaves.
+__device__ __forceinline__ bool lanes_ticket(unsigned int *counter, unsigned int target, volatile int *s_word) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned int prev = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int last = prev + 1u == target;
+    if (last) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    *s_word = last;
+  }
+  __syncthreads();
+  return *s_word != 0;
+}
+// n blocks of kPosesLanesBlock doubles, `stride` doubles apart, summed in block order: lane = pose, the 29 slots dealt over
+// the four wavefronts (slot = wave + 4 j), four blocks' loads in flight per slot.  v[j] = sum of slot wave + 4 j.
+constexpr int kLanesFoldSlots = (kLanesVals + kLanesWaves - 1) / kLanesWaves;
+__device__ __forceinline__ void lanes_fold_blocks(const double *src, size_t stride, int n, int wave, int lane, double (&v)[kLanesFoldSlots]) {
+#pragma unroll
+  for (int j = 0; j < kLanesFoldSlots; ++j) v[j] = 0.0;
+  const double *p = src + lane;
+  int r = 0;
+  for (; r + 4 <= n; r += 4) {
+    double x[4][kLanesFoldSlots];
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int j = 0; j < kLanesFoldSlots; ++j) {
+        const int slot = wave + kLanesWaves * j;
+        x[u][j] = slot < kLanesVals ? p[(size_t)(r + u) * stride + (size_t)slot * kPosesLanes] : 0.0;
+      }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int j = 0; j < kLanesFoldSlots; ++j) v[j] += x[u][j];
+  }
+  for (; r < n; ++r) {
+    double x[kLanesFoldSlots];
+#pragma unroll
+    for (int j = 0; j < kLanesFoldSlots; ++j) {
+      const int slot = wave + kLanesWaves * j;
+      x[j] = slot < kLanesVals ? p[(size_t)r * stride + (size_t)slot * kPosesLanes] : 0.0;
+    }
+#pragma unroll
+    for (int j = 0; j < kLanesFoldSlots; ++j) v[j] += x[j];
+  }
+}
+// What an item does behind the store of its row.  s_lds: the kernel's LDS array, free by now (>= kAccSlots x 65 doubles).
+// group: of the launch; row0 / nrows: the problem's rows; chunk: the item's row in the problem; live: poses of the group.
+__device__ __forceinline__ void lanes_tickets(const PosesTickets &tk, const double *rows_base, int rows, int group, int problem,
+                                              int row0, int nrows, int chunk, int pose0, int live, int groups, double *s_lds) {
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  volatile int *s_word = reinterpret_cast<volatile int *>(s_lds);
+  const int count = tk.count, run = poses_lanes_run(chunk), slot1 = poses_lanes_run_slot(row0, problem, run);
+  // level 1: the last row of the run to arrive sums the run
+  if (!lanes_ticket(tk.counters + poses_lanes_counter1(group, slot1, rows, count), (unsigned)poses_lanes_run_rows(nrows, run), s_word)) return;
+  double v[kLanesFoldSlots];
+  lanes_fold_blocks(rows_base + poses_lanes_row_off(group, row0 + run * kPosesRun, rows), (size_t)kPosesLanesBlock,
+                    poses_lanes_run_rows(nrows, run), wave, lane, v);
+  double *part = tk.partials + poses_lanes_partial_off(group, slot1, rows, count);
+#pragma unroll
+  for (int j = 0; j < kLanesFoldSlots; ++j) {
+    const int slot = wave + kLanesWaves * j;
+    if (slot < kLanesVals) part[(size_t)slot * kPosesLanes + lane] = v[j];
+  }
+  // level 2: the last run of the problem to arrive sums the run partials and delivers the group's results
+  if (!lanes_ticket(tk.counters + poses_lanes_counter2(groups, group, problem, rows, count), (unsigned)poses_lanes_runs(nrows), s_word)) return;
+  lanes_fold_blocks(tk.partials + poses_lanes_partial_off(group, poses_lanes_run_slot(row0, problem, 0), rows, count),
+                    (size_t)kPosesLanesBlock, poses_lanes_runs(nrows), wave, lane, v);
+  __syncthreads();  // (everybody has read s_word)
+  // through LDS, padded to 65 words per slot: in [slot][pose], out pose by pose -- each pose's 256-byte result in one piece
+  static_assert(kLanesFoldSlots * kLanesWaves == kAccSlots, "the wavefronts' slots cover a result exactly");
+#pragma unroll
+  for (int j = 0; j < kLanesFoldSlots; ++j) {
+    const int slot = wave + kLanesWaves * j;
+    s_lds[slot * 65 + lane] = slot < kLanesVals ? v[j] : 0.0;  // (slots 29 .. 31 of a result are zero)
+  }
+  __syncthreads();
+  {
+    const int s = threadIdx.x & (kAccSlots - 1), p0 = threadIdx.x / kAccSlots;
+#pragma unroll
+    for (int it = 0; it < kPosesLanes / (64 * kLanesWaves / kAccSlots); ++it) {
+      const int p = p0 + it * (64 * kLanesWaves / kAccSlots);
+      if (p < live) tk.out[(size_t)(pose0 + p) * (size_t)count + (size_t)problem].acc[s] = s_lds[s * 65 + p];
+    }
+  }
+  // the results lie in pinned host memory: every storing wavefront makes its own visible system-wide, then one thread
+  // raises the flag of (group of the call, problem) to the call's sequence number
+  __threadfence_system();
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __threadfence_system();
+    __hip_atomic_store(tk.flags + poses_lanes_flag(tk.group0 + group, problem, count), tk.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
 // (two wavefronts per SIMD: 56 registers of sums, two staged points and the arithmetic of a third do not fit three, and
 // left to itself the register allocator goes past 256 into accumulation registers, which halves the occupancy again)
+// Rows and fold.  Lane l of wavefront 0 stores its 29 values lane-minor -- rows[group][row][slot][l], one 512-byte line per
+// slot -- into the launch's ONE row array; lanes without a pose of the launch, or with an inactive one, store zeros, and an
+// item whose 64 lanes are all like that skips the points and stores zeros too: every item of the list arrives.  Behind the
+// store the item takes its tickets (lanes_tickets above): runs of kPosesRun = 16 rows -- a run is 256 KB for its last arrival
+// to read, a few microseconds, and C2's 98 rows leave 7 partials to the problem's last arrival -- summed in row order, then
+// the run partials in run order.  A pose's bits depend on the pose and the problem's row count: not on the lane, the company,
+// the split into launches, the item order or who arrived last.
 template <bool BUF, bool IMG32>
 __global__ __launch_bounds__(64 * kLanesWaves) __attribute__((amdgpu_waves_per_eu(2, 2))) void ea_eval_poses_lanes_kernel(
     int shape, int g, int rows, const ProblemDesc *__restrict__ probs, const PoseState *__restrict__ poses,
-    double *__restrict__ partials, PosesFold fold) {
+    double *rows_out, PosesTickets tk) {
   typedef double T;
-  constexpr int NT = 64 * kLanesWaves;
   __shared__ __align__(16) double s_sum[kLanesWaves / 2][kLanesVals][64];
   __shared__ __align__(16) double s_pose[kLanesWaves][10][64];  // each wavefront's own copy of R and t_z, lane by lane
-  const PosesLanesWork w = poses_lanes_work(blockIdx.x, shape, rows, g, fold.n);
-  if (w.kind != 2) {  // (uniform)
-    if (w.kind == 1) poses_fold_one<NT>(fold, w.rider);
-    return;
-  }
+  static_assert(sizeof(s_sum) >= sizeof(double) * kAccSlots * 65, "the fold's transposition fits the sums' array");
+  const PosesLanesWork w = poses_lanes_work(blockIdx.x, shape, rows, g, 0);
+  if (w.kind != 2) return;  // (uniform; not an item of the list)
   const PosesLanesChunk pc = poses_lanes_chunk(w.row, shape, reinterpret_cast<const PosesRow *>(probs) - rows);
   const ProblemDesc pd = probs[pc.term];
   const long long start = (long long)pc.chunk * (kLanesWaves * kLanesSub);
-  if (start >= pd.n) return;
-  const int count = min(kLanesWaves * kLanesSub, (int)(pd.n - start));
+  const int count = (int)max(0ll, min((long long)(kLanesWaves * kLanesSub), (long long)pd.n - start));
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  // the lane's pose; lanes past the launch's last pose compute a copy of it and store nothing
+  // the lane's pose; lanes past the launch's last pose compute a copy of it and store zeros
   const PoseState *psp = poses + ((size_t)(w.pose0 + min(lane, w.live - 1)) * (size_t)pc.count + (size_t)pc.term);
   PoseLite<T> ps;
   int active;
   load_pose_lite<T>(psp, ps, active);
   const bool on = lane < w.live && active != 0;
-  if (!__any(on)) return;  // (the same in the workgroup's four wavefronts: they hold the same poses)
 
-  const int first = wave * kLanesSub, n_sub = max(0, min(kLanesSub, count - first));
-  const CPtr<T> px = (CPtr<T>)(static_cast<const T *>(pd.x) + start + first);
-  const CPtr<T> py = (CPtr<T>)(static_cast<const T *>(pd.y) + start + first);
-  const CPtr<T> pz = (CPtr<T>)(static_cast<const T *>(pd.z) + start + first);
-  const bool pair = pd.loss_kind == 1;  // one log per two points (loss_point)
-  T acc[28];
-#pragma unroll
-  for (int i = 0; i < 28; ++i) acc[i] = T(0);
-  int n_bad = 0;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) s_pose[wave][k][lane] = ps.R[k];
-  s_pose[wave][9][lane] = ps.t[2];
-  if (__all(ps.unit_q != 0)) lanes_run<BUF, IMG32, true>(pd, ps, px, py, pz, n_sub, pair, acc, n_bad, s_pose[wave]);
-  else lanes_run<BUF, IMG32, false>(pd, ps, px, py, pz, n_sub, pair, acc, n_bad, s_pose[wave]);
-
-  // (w0 + w1) + (w2 + w3), lane by lane: the odd member of each pair hands its sums over, then the pair sums do the same
   T v[kLanesVals];
 #pragma unroll
-  for (int i = 0; i < 28; ++i) v[i] = acc[i];
-  v[28] = (T)n_bad;
+  for (int i = 0; i < kLanesVals; ++i) v[i] = T(0);
+  if (__any(on)) {  // (the same in the workgroup's four wavefronts: they hold the same poses)
+    const int first = wave * kLanesSub, n_sub = max(0, min(kLanesSub, count - first));
+    const CPtr<T> px = (CPtr<T>)(static_cast<const T *>(pd.x) + start + first);
+    const CPtr<T> py = (CPtr<T>)(static_cast<const T *>(pd.y) + start + first);
+    const CPtr<T> pz = (CPtr<T>)(static_cast<const T *>(pd.z) + start + first);
+    const bool pair = pd.loss_kind == 1;  // one log per two points (loss_point)
+    T acc[28];
 #pragma unroll
-  for (int s = 1; s < kLanesWaves; s <<= 1) {
-    const int role = wave & (2 * s - 1), buf = wave / (2 * s);
-    if (role == s) {
+    for (int i = 0; i < 28; ++i) acc[i] = T(0);
+    int n_bad = 0;
 #pragma unroll
-      for (int i = 0; i < kLanesVals; ++i) s_sum[buf][i][lane] = v[i];
+    for (int k = 0; k < 9; ++k) s_pose[wave][k][lane] = ps.R[k];
+    s_pose[wave][9][lane] = ps.t[2];
+    if (__all(ps.unit_q != 0)) lanes_run<BUF, IMG32, true>(pd, ps, px, py, pz, n_sub, pair, acc, n_bad, s_pose[wave]);
+    else lanes_run<BUF, IMG32, false>(pd, ps, px, py, pz, n_sub, pair, acc, n_bad, s_pose[wave]);
+
+    // (w0 + w1) + (w2 + w3), lane by lane: the odd member of each pair hands its sums over, then the pair sums do the same
+#pragma unroll
+    for (int i = 0; i < 28; ++i) v[i] = acc[i];
+    v[28] = (T)n_bad;
+#pragma unroll
+    for (int s = 1; s < kLanesWaves; s <<= 1) {
+      const int role = wave & (2 * s - 1), buf = wave / (2 * s);
+      if (role == s) {
+#pragma unroll
+        for (int i = 0; i < kLanesVals; ++i) s_sum[buf][i][lane] = v[i];
+      }
+      __syncthreads();
+      if (role == 0) {
+#pragma unroll
+        for (int i = 0; i < kLanesVals; ++i) v[i] += s_sum[buf][i][lane];
+      }
+      if (2 * s < kLanesWaves) __syncthreads();  // (read before the next level writes)
     }
-    __syncthreads();
-    if (role == 0) {
-#pragma unroll
-      for (int i = 0; i < kLanesVals; ++i) v[i] += s_sum[buf][i][lane];
-    }
-    if (2 * s < kLanesWaves) __syncthreads();  // (read before the next level writes)
   }
-  if (wave == 0 && on) {
-    double *o = partials + ((size_t)(w.pose0 + lane) * (size_t)rows + (size_t)w.row) * kAccSlots;
+  const int group = w.pose0 / kPosesLanes;
+  if (wave == 0) {
+    double *o = rows_out + poses_lanes_row_off(group, w.row, rows) + lane;
 #pragma unroll
-    for (int i = 0; i < kLanesVals; ++i) o[i] = v[i];
-#pragma unroll
-    for (int i = kLanesVals; i < kAccSlots; ++i) o[i] = 0.0;
+    for (int i = 0; i < kLanesVals; ++i) o[(size_t)i * kPosesLanes] = on ? v[i] : 0.0;
   }
+  if (!tk.on) return;
+  lanes_tickets(tk, rows_out, rows, group, pc.term, w.row - pc.chunk, pd.tile_end - pd.tile_begin, pc.chunk, w.pose0, w.live,
+                poses_lanes_groups(g), &s_sum[0][0][0]);
 }
 
 // ---- cost-only pose-batched evaluation (ea_batch_cost_resident_poses) ---------------------------------------------------
@@ -3224,13 +3337,19 @@ hipError_t launch_eval_poses(const EvalLaunch &s, const PosesLaunch &p, const Pr
 // ea_eval_poses_lanes_kernel: the same launch with one pose per lane -- fp64 at the pose path's 256 x 2 shape only (the
 // row is that shape's 512-point chunk); everything else is refused
 hipError_t launch_eval_poses_lanes(const EvalLaunch &s, const PosesLaunch &p, const ProblemDesc *probs, const PoseState *poses,
-                                   double *partials, const PosesFold &fold, hipStream_t stream) {
-  if (!flat_launch_ok(s, p, 1) || fold.n < 0 || s.dtype != EA_F64 || s.nt != 64 * kLanesWaves || s.ppt != 2) return hipErrorInvalidValue;
-  const int shape = poses_shape(s.xcd_remap != 0, p.order, p.single != 0, fold.n);
-  const dim3 grid(poses_lanes_grid(p.rows, p.g, fold.n));
+                                   double *rows, const PosesTickets &tickets, hipStream_t stream) {
+  if (!flat_launch_ok(s, p, 1) || s.dtype != EA_F64 || s.nt != 64 * kLanesWaves || s.ppt != 2) return hipErrorInvalidValue;
+  if (tickets.on) {
+    if (!tickets.partials || !tickets.counters || !tickets.out || !tickets.flags || tickets.count < 1) return hipErrorInvalidValue;
+    // every counter of the launch starts at zero, whatever an earlier launch left (a call that failed half way included)
+    const hipError_t e = hipMemsetAsync(tickets.counters, 0, poses_lanes_counters(poses_lanes_groups(p.g), p.rows, tickets.count) * sizeof(unsigned int), stream);
+    if (e != hipSuccess) return e;
+  }
+  const int shape = poses_shape(s.xcd_remap != 0, p.order, p.single != 0, 0);
+  const dim3 grid(poses_lanes_grid(p.rows, p.g, 0));
   return dispatch_bool(s.buffer_loads, [&](auto BUF) { return dispatch_bool(s.img32, [&](auto IMG32) {
     hipLaunchKernelGGL((ea_eval_poses_lanes_kernel<decltype(BUF)::value, decltype(IMG32)::value>), grid, dim3(64 * kLanesWaves), 0,
-                       stream, shape, p.g, p.rows, probs, poses, partials, fold);
+                       stream, shape, p.g, p.rows, probs, poses, rows, tickets);
     return hipGetLastError();
   }); });
 }

@@ -51,6 +51,17 @@ struct PosesFold {
   unsigned int *counter = nullptr;
   int *host_flag = nullptr;
 };
+// What the fold inside a launch of ea_eval_poses_lanes_kernel works on (ea_poses_map.h, "the rows of the lanes path"): the
+// run partials and the counters of the launch's groups (zeroed ahead of the launch), the results out[pose * count + problem]
+// of the launch's poses, and the pinned flags of the call -- the launch's first group is group0 of the call -- raised to seq.
+// on = 0: evaluations only, the rows are stored and nothing is counted or folded.
+struct PosesTickets {
+  int on = 0, count = 1, group0 = 0, seq = 0;
+  double *partials = nullptr;
+  unsigned int *counters = nullptr;
+  EvalOut *out = nullptr;
+  int *flags = nullptr;
+};
 // the LM state an ea_lm_step_kernel / ea_lm_iter_kernel launch works on; `side`: the side table (PriorDesc records: NormalPriors and the constant-coordinate mask) sits behind the
 // launch's `groups` (one per problem) -- some problem carries a NormalPrior or holds tangent coordinates constant
 struct LMLaunch {
@@ -150,9 +161,10 @@ hipError_t launch_eval_poses_grid(const EvalLaunch &s, const ProblemDesc *probs,
 hipError_t launch_eval_poses(const EvalLaunch &s, const PosesLaunch &p, const ProblemDesc *probs, const PoseState *poses,
                              double *partials, const PosesFold &fold, hipStream_t stream);
 // ea_eval_poses_lanes_kernel: that launch with one pose per lane (ea_poses_map.h: items are (row, 64 poses)); fp64 batches at
-// the 256 x 2 pose shape, the same tables, rows, riders and row indices; p.exchange is not read
+// the 256 x 2 pose shape, the same tables and items; its rows are lane-minor and folded in the launch itself (PosesTickets:
+// the launcher zeroes the counters ahead of the kernel); p.exchange is not read
 hipError_t launch_eval_poses_lanes(const EvalLaunch &s, const PosesLaunch &p, const ProblemDesc *probs, const PoseState *poses,
-                                   double *partials, const PosesFold &fold, hipStream_t stream);
+                                   double *rows, const PosesTickets &tickets, hipStream_t stream);
 hipError_t launch_poses_fold(int nt, const PosesFold &fold, hipStream_t stream);
 // ea_cost_poses_kernel: the cost-only form of launch_eval_poses' launch (256-lane workgroups; no riders) -- one narrow
 // partial {cost, failed functors} of kCostPartialBytes per workgroup at pose * rows + row of `partials`.

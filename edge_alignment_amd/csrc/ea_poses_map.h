@@ -85,9 +85,9 @@ EA_HD inline int poses_launch_size(int K, int G) { const int n = poses_launches(
 // ---- one pose per lane (ea_eval_poses_lanes_kernel) ---------------------------------------------------------------------
 // The same launch with the mapping turned round: a work item is (row of a pose, GROUP of kPosesLanes consecutive poses of the
 // launch), lane l of every wavefront of the workgroup holds pose 64 group + l, and the row's sums never leave the lane.  The
-// list of items is the list above with `groups` in the place of g -- rider slots, the XCD deal of contiguous rows and both
-// item orders included -- so the functions above serve it unchanged; what is added is group -> (first pose, live lanes).
-// Partial row of lane l: (pose0 + l) * rows + row, the row the other kernel writes for that (pose, row).
+// list of items is the list above with `groups` in the place of g -- the XCD deal of contiguous rows and both item orders
+// included; its launches carry no riders (riders = 0) -- so the functions above serve it unchanged; what is added is
+// group -> (first pose, live lanes).  Its rows have a layout of their own and are folded inside the launch: further down.
 constexpr int kPosesLanes = 64;
 EA_HD inline int poses_lanes_groups(int g) { return (g + kPosesLanes - 1) / kPosesLanes; }
 EA_HD inline unsigned poses_lanes_grid(int rows, int g, int riders) { return poses_grid(rows, poses_lanes_groups(g), riders); }
@@ -122,5 +122,53 @@ EA_HD inline PosesLanesChunk poses_lanes_chunk(int row, int shape, const PosesRo
 // the sum of those at what one launch of K would cost (an even split can add a lifetime per launch).
 EA_HD inline int poses_lanes_group_size(int bound) { return bound >= kPosesLanes ? bound - bound % kPosesLanes : (bound > 1 ? bound : 1); }
 EA_HD inline int poses_lanes_launch_size(int K, int G) { return K < G ? K : G; }
+
+// ---- the rows of the lanes path and their fold inside the launch (tests/poses_lanes_fold_host_shim.cpp) -----------------
+// The lanes kernel keeps ONE row array, lane-minor: [group][row][slot][lane], kPosesLanesBlock doubles per (group, row) --
+// slot s of the group's 64 poses is one 512-byte line, so the store of a row and every read of the fold are coalesced.
+// The fold runs in the launch itself, in two levels of arrival counters ("tickets"); no workgroup waits for another.
+//   level 1: the rows of problem i are cut into runs of kPosesRun consecutive rows, counted from the problem's first row.
+//     An item adds one to the counter of its (group, problem, run); the workgroup whose add completes the run's row count
+//     sums the run's rows in row order into one run partial (same lane-minor block) and adds one to the counter of
+//     (group, problem).
+//   level 2: the workgroup whose add completes the problem's run count sums the run partials in run order, writes the 64
+//     results and raises the flag of (group of the call, problem).
+// A pose's sums therefore depend on the pose and the problem's row count only.
+// Run partials and level-1 counters are addressed by a run SLOT that needs no table: problem i's run r of a batch whose
+// problem i starts at row row0 has slot row0 / kPosesRun + i + r.  Slots of different (problem, run) never collide
+// (ceil(n / R) <= floor((a + n) / R) - floor(a / R) + 1) and stay below poses_lanes_run_slots(rows, count).
+constexpr int kPosesRun = 16;
+constexpr int kPosesLanesBlock = kAccSlots * kPosesLanes;  // doubles of one (group, row) or one run partial
+EA_HD inline int poses_lanes_run(int chunk) { return chunk / kPosesRun; }                            // chunk = row - row0
+EA_HD inline int poses_lanes_runs(int nrows) { return (nrows + kPosesRun - 1) / kPosesRun; }           // level-2 ticket target
+EA_HD inline int poses_lanes_run_rows(int nrows, int run) {                                           // level-1 ticket target
+  const int left = nrows - run * kPosesRun;
+  return left < kPosesRun ? left : kPosesRun;
+}
+EA_HD inline int poses_lanes_run_slots(int rows, int count) { return rows / kPosesRun + count; }      // per group
+EA_HD inline int poses_lanes_run_slot(int row0, int problem, int run) { return row0 / kPosesRun + problem + run; }
+// offsets in doubles of a block's first word; word (slot s, lane l) of a block is at s * kPosesLanes + l
+EA_HD inline size_t poses_lanes_row_off(int group, int row, int rows) { return ((size_t)group * (size_t)rows + (size_t)row) * kPosesLanesBlock; }
+EA_HD inline size_t poses_lanes_partial_off(int group, int run_slot, int rows, int count) {
+  return ((size_t)group * (size_t)poses_lanes_run_slots(rows, count) + (size_t)run_slot) * kPosesLanesBlock;
+}
+// counters of a launch of `groups` groups, one block of 32-bit words zeroed ahead of the launch:
+// [level 1: groups x run slots | level 2: groups x count], padded to a multiple of 16 bytes
+EA_HD inline size_t poses_lanes_counter1(int group, int run_slot, int rows, int count) {
+  return (size_t)group * (size_t)poses_lanes_run_slots(rows, count) + (size_t)run_slot;
+}
+EA_HD inline size_t poses_lanes_counter2(int groups, int group, int problem, int rows, int count) {
+  return (size_t)groups * (size_t)poses_lanes_run_slots(rows, count) + (size_t)group * (size_t)count + (size_t)problem;
+}
+EA_HD inline size_t poses_lanes_counters(int groups, int rows, int count) {
+  return ((size_t)groups * (size_t)(poses_lanes_run_slots(rows, count) + count) + 3) & ~(size_t)3;
+}
+// flags in pinned memory, one per (group of the CALL, problem): launch j of a call in launches of G poses starts at group
+// j * poses_lanes_groups(G)
+EA_HD inline size_t poses_lanes_flag(int call_group, int problem, int count) { return (size_t)call_group * (size_t)count + (size_t)problem; }
+EA_HD inline int poses_lanes_call_groups(int K, int G) {
+  const int full = K / G, rest = K % G;
+  return full * poses_lanes_groups(G) + poses_lanes_groups(rest);
+}
 
 }  // namespace ea

@@ -606,7 +606,10 @@ int ea_eval_rows_device(ea_problem *p, const double q[4], const double t[3], int
  * pose; every other batch keeps its kernel whatever the key says.  The choice follows from the batch and K alone, never from
  * "poses_per_launch": on either path any split of the K poses over launches gives the same bits.  Between the paths the sums
  * differ in the last places (another fixed summation order); n_invalid is equal.  On this path "poses_per_launch" is rounded
- * down to a multiple of 64 (left alone below 64: launches of one partly filled group, slow).  Setting the key drops resident
+ * down to a multiple of 64 (left alone below 64: launches of one partly filled group, slow).  This path folds its partial
+ * rows inside the evaluation launch (runs of 16 rows in row order, then the runs in run order: a pose's sums depend on the
+ * pose and the problem's point count only) and hands the results over in groups of 64 poses while the launch still runs;
+ * its default item order is "poses_order" 1.  Setting the key drops resident
  * poses; ea_batch_get_info "poses_lane_per_pose" reports 1 if the last pose-batched call ran that kernel.
  * "poses_wave_exchange" = 0: the fp64 pose-batched evaluation in 256-lane workgroups (ea_batch_eval_poses, the evaluations of
  * ea_batch_solve_starts) reduces with one 32-value butterfly per wavefront; default 1: the four wavefronts of a workgroup
