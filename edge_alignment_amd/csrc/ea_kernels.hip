@@ -1874,9 +1874,9 @@ __global__ __launch_bounds__(NT) void ea_poses_fold_kernel(PosesFold fold) {
 // barrier stands in the point loop.  A work item is (row of a pose, 64 consecutive poses of the launch) (ea_poses_map.h); the
 // row is the 512-point chunk it is in the other kernel.  Its sums go lane-minor into the path's own row array and are folded
 // inside the launch (further down).  The workgroup's four wavefronts hold the same 64 poses and walk the chunk's four sub-runs of 128
-// points, two points per iteration (the paired Cauchy logarithm pairs points 2i and 2i + 1 of a sub-run), sums in the order
-// of the points; at the end the per-lane sums are added through LDS as (w0 + w1) + (w2 + w3) and lane l stores the row of
-// pose l.  The summation order differs from the other kernel's (last places), and depends on nothing but the pose and the
+// points, two points per iteration, sums in the order of the points (under the unweighted Cauchy loss of unit quaternions
+// the cost is ONE logarithm per sub-run, of the running product of the points' factors: lanes_sums); at the end the
+// per-lane sums are added through LDS as (w0 + w1) + (w2 + w3) and lane l stores the row of pose l.  The summation order differs from the other kernel's (last places), and depends on nothing but the pose and the
 // row: not on the lane, the company in the wavefront, the launch or the item order.  The per-point expressions are fused_chunk's, through the same
 // functions; lanes whose pose is not a unit quaternion, or whose point fails, take their branch per lane.
 template <typename T> using CPtr = const T __attribute__((address_space(4))) *;  // read-only for the kernel: uniform loads go through the scalar cache
@@ -1910,8 +1910,9 @@ __device__ __forceinline__ void lanes_stage(const ProblemDesc &pd, const PoseLit
   project_point<T>(pd, ps, x, y, z, pr);
   st.valid = inb && pr.state == 1;
   n_bad += (inb && pr.state == 2) ? 1 : 0;
-  if (__any(!st.valid) && !st.valid) {  // (uniform test first, as in fused_chunk)
-    pr.iu = 0; pr.iv = 0; pr.fu = T(0); pr.fv = T(0);
+  if (__any(!st.valid)) {  // (uniform test first, as in fused_chunk)
+    asm volatile("" ::: "memory");  // (and kept a branch, as in jacobian_row)
+    if (!st.valid) { pr.iu = 0; pr.iv = 0; pr.fu = T(0); pr.fv = T(0); }
   }
   st.cx_ = pr.cx_; st.cy_ = pr.cy_; st.cz_ = pr.cz_; st.iz = pr.iz; st.fu = pr.fu; st.fv = pr.fv;
   if constexpr (BUF) {
@@ -1929,29 +1930,69 @@ __device__ __forceinline__ void lanes_stage(const ProblemDesc &pd, const PoseLit
 }
 // Stage 2: staged point k of its pair into the lane's sums, fused_chunk's statements.  UNIT: every lane's pose is a unit
 // quaternion (the test is made once per work item), else each lane takes its own branch of jacobian_row.
+//
+// The cost under the unweighted Cauchy loss (`pair`) of the UNIT form: the lane needs sum log s_i over the 128 points of its
+// sub-run, which is log prod s_i -- so a point only multiplies its factor s = 1 + r^2 / a^2 (exactly 1 for a lane without a
+// valid point) into the lane's running product `run` (pl_run_*, ea_pair_log.h: a multiply and two fmas that carry the rounding
+// error along, one comparison that guards the range) and lanes_run takes one logarithm behind the loop, where the paired
+// logarithm cost ~22 instructions per point.  w = 1 / s stays per point: JtJ, Jtr and the failed-functor count keep their
+// bits, the cost moves in its last places.  Huber, the trivial loss and the general-quaternion form keep loss_point and
+// cost_point, the paired logarithm included.
+//
+// Every fix-up of a lane without a valid point, and the renormalisation of the product, is a uniform BRANCH (the empty asm, as
+// in jacobian_row): written as `__any(c) && c` alone the compiler turns them into moves under an exec mask, which every
+// wavefront issues for every point.  t_x and t_y are read from the wavefront's LDS pose copy where bx and by are formed.
+struct LanesLogRun { double P, L; int E; };  // the product is (P + L) 2^E
 template <bool IMG32, bool UNIT>
 __device__ __forceinline__ void lanes_sums(int k, const ProblemDesc &pd, const PoseLite<double> &ps_, double x, double y, double z,
                                            const LanesStage<typename ImgOf<double, IMG32>::type> &st, bool pair,
-                                           double (&acc)[28], double &cost, double &held) {
+                                           double (&acc)[28], double &cost, double &held, LanesLogRun &run,
+                                           const double (*s_pose)[64]) {
   typedef double T;
   PoseLite<T> ps = ps_;
   if constexpr (UNIT) ps.unit_q = 1;
   const T loss_a = Uni<T>::loss_a(pd);
   Proj<T> pr;
   pr.cx_ = st.cx_; pr.cy_ = st.cy_; pr.cz_ = st.cz_; pr.iz = st.iz; pr.fu = st.fu; pr.fv = st.fv;
+  if constexpr (UNIT) {  // (t_x and t_y out of the wavefront's LDS copy again: not held through the sums)
+    asm volatile("" ::: "memory");
+    ps.t[0] = s_pose[10][threadIdx.x & 63]; ps.t[1] = s_pose[11][threadIdx.x & 63];
+  }
   pr.bx = st.cx_ + ps.t[0]; pr.by = st.cy_ + ps.t[1];
   pr.fxz = Uni<T>::fx(pd) * st.iz; pr.fyz = Uni<T>::fy(pd) * st.iz;
-  if (__any(!st.valid) && !st.valid) {  // (the rest of fused_chunk's fix-up; the sample was moved when the rows were asked for)
-    pr.iz = T(1);
-    pr.bx = T(0); pr.by = T(0);
-    pr.fxz = T(0); pr.fyz = T(0);
+  if (__any(!st.valid)) {  // (the rest of fused_chunk's fix-up; the sample was moved when the rows were asked for)
+    asm volatile("" ::: "memory");  // (keeps the uniform branch a branch, as in jacobian_row: no masked moves on the common path)
+    if (!st.valid) {
+      pr.iz = T(1);
+      pr.bx = T(0); pr.by = T(0);
+      pr.fxz = T(0); pr.fyz = T(0);
+    }
   }
   T f, Fu, Fv;
   bicubic<T>(pr.fu, pr.fv, [&](int l) { return lanes_widen(st.row[l]); }, f, Fu, Fv);
   T J[6];
   jacobian_row<T>(pd, ps, pr, x, y, z, Fu, Fv, J);
   T rho, w;
-  loss_point<T, 2, false>(pair, pd.loss_kind, loss_a, Uni<T>::loss_inv_b(pd), f * f, st.valid, T(1), rho, w);
+  if (UNIT && pair) {
+    // loss_point's Cauchy statements; its two selects for a lane without a valid point go behind the uniform branch
+    const T xs = (f * f) * Uni<T>::loss_inv_b(pd);
+    rho = xs + T(1);
+    w = t_rcp<T>(rho);
+    if (__any(!st.valid)) {
+      asm volatile("" ::: "memory");  // (keeps the uniform branch a branch, as in jacobian_row)
+      if (!st.valid) { w = T(0); rho = T(1); }
+    }
+    // the factor into the lane's running product (ea_pair_log.h); the renormalisation is rare: uniform test first
+    T p = run.P * rho;
+    const bool high = pl_run_high<LogOps>(p);
+    if (__any(high)) {
+      asm volatile("" ::: "memory");
+      if (high) p = pl_run_renorm<LogOps>(run.P, run.L, run.E, rho);
+    }
+    pl_run_take(run.P, run.L, rho, p);
+  } else {
+    loss_point<T, 2, false>(pair, pd.loss_kind, loss_a, Uni<T>::loss_inv_b(pd), f * f, st.valid, T(1), rho, w);
+  }
   const T wr = w * f;
   int s = 0;
 #pragma unroll
@@ -1961,14 +2002,15 @@ __device__ __forceinline__ void lanes_sums(int k, const ProblemDesc &pd, const P
     for (int b = a; b < 6; ++b) { acc[s] = t_fma<T>(wJa, J[b], acc[s]); ++s; }
     acc[kAccJtr + a] = t_fma<T>(J[a], wr, acc[kAccJtr + a]);
   }
-  cost_point<T, 2>(k, pair, loss_a, rho, cost, held);
+  if (!(UNIT && pair)) cost_point<T, 2>(k, pair, loss_a, rho, cost, held);
 }
 
-// A wavefront's sub-run of n_sub points at px / py / pz, two per iteration (the pair of the paired logarithm): both points are
+// A wavefront's sub-run of n_sub points at px / py / pz, two per iteration: both points are
 // projected and their eight row loads issued before the first is summed -- one trip to memory per pair, which the SIMD's
 // other wavefront covers -- and the coordinates (scalar loads) are asked for two pairs ahead; that look-ahead clamps to the
 // sub-run's last point.  (Staging the NEXT pair's rows under the sums as well was tried: with 56 registers of sums it does
-// not fit 256 registers without scratch.)
+// not fit 256 registers without scratch.)  The running product of lanes_sums starts at 1 in front of the loop and becomes the
+// cost, (a^2 / 2) log, behind it; its three registers are paid for by t_x and t_y, which stay in LDS with R and t_z.
 template <bool BUF, bool IMG32, bool UNIT>
 __device__ __forceinline__ void lanes_run(const ProblemDesc &pd, const PoseLite<double> &ps_, CPtr<double> px, CPtr<double> py,
                                           CPtr<double> pz, int n_sub, bool pair, double (&acc)[28], int &n_bad,
@@ -1977,7 +2019,11 @@ __device__ __forceinline__ void lanes_run(const ProblemDesc &pd, const PoseLite<
   typedef typename ImgOf<T, IMG32>::type IT;
   if (n_sub <= 0) return;
   const int lane = threadIdx.x & 63;
+  // (wave-uniform, and said so: left in a vector register, the look-ahead's six clamped addresses are formed by vector
+  // instructions and read back lane 0 by lane 0 -- 24 instructions per pair in front of scalar loads)
+  n_sub = __builtin_amdgcn_readfirstlane(n_sub);
   const int last = n_sub - 1;
+  LanesLogRun run = {T(1), T(0), 0};
   T X[2], Y[2], Z[2], NX[2], NY[2], NZ[2];  // this iteration's pair, the next one's
   {
     const int i1 = min(1, last), i2 = min(2, last), i3 = min(3, last);
@@ -1990,27 +2036,28 @@ __device__ __forceinline__ void lanes_run(const ProblemDesc &pd, const PoseLite<
     const T FX[2] = {px[i4], px[i5]}, FY[2] = {py[i4], py[i5]}, FZ[2] = {pz[i4], pz[i5]};
     T held = T(1), cost = T(0);
     LanesStage<IT> A, B;
-    // The rotation and t_z are read by the two projections only: they come out of the wavefront's LDS copy per pair (ten
-    // conflict-free 8-byte reads) instead of occupying twenty registers through the sums.  (The barrier keeps the reads in
-    // the loop.)
+    // The rotation and the translation are read by the two projections (and t_x, t_y once more per point in lanes_sums):
+    // they come out of the wavefront's LDS copy per pair (twelve conflict-free 8-byte reads) instead of occupying twenty-four
+    // registers through the sums.  (The barrier keeps the reads in the loop.)
     PoseLite<T> ps = ps_;
     if constexpr (UNIT) {
       asm volatile("" ::: "memory");
 #pragma unroll
       for (int k = 0; k < 9; ++k) ps.R[k] = s_pose[k][lane];
-      ps.t[2] = s_pose[9][lane];
+      ps.t[2] = s_pose[9][lane]; ps.t[0] = s_pose[10][lane]; ps.t[1] = s_pose[11][lane];
     }
     lanes_stage<BUF, IMG32>(pd, ps, X[0], Y[0], Z[0], true, A, n_bad);
     // (both points' rows are under way before the first is summed; the rare general-quaternion form, which reads 27 more
     // words per lane and point, takes them one after the other)
     if constexpr (UNIT) lanes_stage<BUF, IMG32>(pd, ps, X[1], Y[1], Z[1], i + 1 < n_sub, B, n_bad);
-    lanes_sums<IMG32, UNIT>(0, pd, ps, X[0], Y[0], Z[0], A, pair, acc, cost, held);
+    lanes_sums<IMG32, UNIT>(0, pd, ps, X[0], Y[0], Z[0], A, pair, acc, cost, held, run, s_pose);
     if constexpr (!UNIT) lanes_stage<BUF, IMG32>(pd, ps, X[1], Y[1], Z[1], i + 1 < n_sub, B, n_bad);
-    lanes_sums<IMG32, UNIT>(1, pd, ps, X[1], Y[1], Z[1], B, pair, acc, cost, held);
-    acc[kAccCost] += cost;
+    lanes_sums<IMG32, UNIT>(1, pd, ps, X[1], Y[1], Z[1], B, pair, acc, cost, held, run, s_pose);
+    if (!(UNIT && pair)) acc[kAccCost] += cost;
 #pragma unroll
     for (int k = 0; k < 2; ++k) { X[k] = NX[k]; Y[k] = NY[k]; Z[k] = NZ[k]; NX[k] = FX[k]; NY[k] = FY[k]; NZ[k] = FZ[k]; }
   }
+  if (UNIT && pair) acc[kAccCost] = (T(0.5) * (Uni<T>::loss_a(pd) * Uni<T>::loss_a(pd))) * pl_run_log<LogOps>(run.P, run.L, run.E);
 }
 
 // ---- the fold inside the launch: two levels of tickets (ea_poses_map.h, "the rows of the lanes path") --------------------
@@ -2134,7 +2181,7 @@ __global__ __launch_bounds__(64 * kLanesWaves) __attribute__((amdgpu_waves_per_e
     double *rows_out, PosesTickets tk) {
   typedef double T;
   __shared__ __align__(16) double s_sum[kLanesWaves / 2][kLanesVals][64];
-  __shared__ __align__(16) double s_pose[kLanesWaves][10][64];  // each wavefront's own copy of R and t_z, lane by lane
+  __shared__ __align__(16) double s_pose[kLanesWaves][12][64];  // each wavefront's own copy of R, t_z, t_x and t_y, lane by lane
   static_assert(sizeof(s_sum) >= sizeof(double) * kAccSlots * 65, "the fold's transposition fits the sums' array");
   const PosesLanesWork w = poses_lanes_work(blockIdx.x, shape, rows, g, 0);
   if (w.kind != 2) return;  // (uniform; not an item of the list)
@@ -2165,7 +2212,7 @@ __global__ __launch_bounds__(64 * kLanesWaves) __attribute__((amdgpu_waves_per_e
     int n_bad = 0;
 #pragma unroll
     for (int k = 0; k < 9; ++k) s_pose[wave][k][lane] = ps.R[k];
-    s_pose[wave][9][lane] = ps.t[2];
+    s_pose[wave][9][lane] = ps.t[2]; s_pose[wave][10][lane] = ps.t[0]; s_pose[wave][11][lane] = ps.t[1];
     if (__all(ps.unit_q != 0)) lanes_run<BUF, IMG32, true>(pd, ps, px, py, pz, n_sub, pair, acc, n_bad, s_pose[wave]);
     else lanes_run<BUF, IMG32, false>(pd, ps, px, py, pz, n_sub, pair, acc, n_bad, s_pose[wave]);
 

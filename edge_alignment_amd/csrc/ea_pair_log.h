@@ -1,6 +1,7 @@
 // ea_pair_log.h — the fp64 logarithm of the Cauchy loss (fused_chunk and cost_item, ea_kernels.hip), once per point and once
 // per PAIR of points, as templates over the few machine operations they need, so that the host compiles the same text with
-// stand-ins for the intrinsics and measures it without a device (tests/pair_log_host_shim.cpp).
+// stand-ins for the intrinsics and measures it without a device (tests/pair_log_host_shim.cpp).  Further down: once per RUN
+// of points, for a lane that walks many (lanes_sums / lanes_run; tests/pair_log_run_host_shim.cpp).
 //
 // The cost of a lane with two points needs log(s0) + log(s1) = log(s0 s1) only.  log_pair multiplies the two MANTISSAS (no
 // input can overflow or underflow the product), keeps the rounding error of that product (one fma) and returns it to the
@@ -76,6 +77,57 @@ template <class Ops, bool CORRECT = true> EA_HD inline double pl_log_pair(double
   if (CORRECT) lm = __builtin_fma(err, Ops::rcp(p), lm);
   const double ef = (double)e;
   return __builtin_fma(ef, Ops::sconst(kLn2Hi), __builtin_fma(ef, Ops::sconst(kLn2Lo), lm));
+}
+
+// ---- the running product: one logarithm for a whole run of factors ---------------------------------------------------------
+// A lane that walks many points (the pose-per-lane kernel: 128 per sub-run) needs sum_i log s_i = log prod_i s_i only.  The
+// product is carried as P + L -- P the rounded product, L the accumulated rounding error (one fma per factor gives the exact
+// error of P s, a second carries the old L along) -- times 2^E, and the logarithm is taken ONCE behind the run:
+// log(P + L) = log P + L / P to second order in n 2^-53, the same correction pl_log_pair makes for its single product.
+//
+// The factors are s = 1 + x >= 1, so P stays >= 1 (>= 1/4 once renormalised) and cannot underflow; and no factor is split by
+// frexp on the common path: a factor near 1 stays near 1 (mantissas in [0.5, 1) per factor would leave E ln 2 - log P to
+// cancel, which costs 1e-4 relative at x ~ 1e-12).  Only when the rounded product p = P s passes 2^400 -- infinity included:
+// p is thrown away then -- P and s are brought back to [0.5, 1), their exponents go to E and p is formed again.  So P <= 2^400
+// before every step, whatever finite s arrives, and one comparison per factor guards the run.  From the first
+// renormalisation on the sum is >= 400 ln 2 and log P >= log(1/4): nothing of that size cancels.
+//
+// E: a renormalisation adds at most 401 + 1024, so |E| < 128 * 1425 < 2^18 over the 128 factors of a sub-run -- exact as an
+// int and as a double.  That is past the 2^11 up to which E * kLn2Hi is an exact product, and need not be inside: the
+// recombination is fma(E, hi, fma(E, lo, .)), where each product is rounded together with its sum only, and hi + lo is ln 2
+// to 2^-86 for any E.
+constexpr double kRunBound = 0x1p400;
+
+// p = P * s as rounded: does the step have to renormalise first?
+template <class Ops> EA_HD inline bool pl_run_high(double p) { return p > Ops::sconst(kRunBound); }
+// the slow path: P, L and s scaled down by the exponents of P and s, which go to E; returns the new P s
+template <class Ops> EA_HD inline double pl_run_renorm(double &P, double &L, int &E, double &s) {
+  const int eP = Ops::frexp_exp(P), es = Ops::frexp_exp(s);
+  P = Ops::frexp_mant(P);
+  L = Ops::ldexp(L, -eP);
+  s = Ops::frexp_mant(s);
+  E += eP + es;
+  return P * s;
+}
+// (P + L) *= s with p = P * s
+EA_HD inline void pl_run_take(double &P, double &L, double s, double p) {
+  const double err = __builtin_fma(P, s, -p);  // P s = p + err exactly
+  L = __builtin_fma(L, s, err);
+  P = p;
+}
+// one factor, as a lane on its own takes it (the kernel makes the test wave-uniform first); true: it renormalised
+template <class Ops> EA_HD inline bool pl_run_step(double &P, double &L, int &E, double s) {
+  double p = P * s;
+  const bool high = pl_run_high<Ops>(p);
+  if (high) p = pl_run_renorm<Ops>(P, L, E, s);
+  pl_run_take(P, L, s, p);
+  return high;
+}
+// log((P + L) 2^E); P = 1, L = 0, E = 0 (no factor, or all of them 1) gives exactly 0
+template <class Ops> EA_HD inline double pl_run_log(double P, double L, int E) {
+  const double lg = __builtin_fma(L, Ops::rcp(P), pl_log<Ops>(P));
+  const double ef = (double)E;
+  return __builtin_fma(ef, Ops::sconst(kLn2Hi), __builtin_fma(ef, Ops::sconst(kLn2Lo), lg));
 }
 
 }  // namespace ea

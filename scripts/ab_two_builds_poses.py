@@ -6,8 +6,26 @@ then the same poses through the other kernels that share the head of a work item
 one solve_starts from the first four (poses, iteration counts, it_cost), and ea_solve from the first with fused_iterations
 on and off; and the three forms of the LM step (fused, pair, K = 4 starts), lm / dogleg x {no side table, NormalPrior on t, held
 coordinates}: pose, counts, costs and all seven trace arrays.  Every array must be array_equal between the builds: exit
-status 1 otherwise."""
+status 1 otherwise.
+--poses K: instead of timing, the results of K poses on C2 fp64 (Cauchy) at the default tuning from both builds -- the
+one-pose-per-lane kernel from 1024 poses on, ea_eval_poses_kernel below -- and which kernel ran.  JtJ, Jtr and n_invalid must
+be array_equal (exit status 1 otherwise); the cost is reported: equal bits, or the largest relative difference over the poses."""
 import sys, os, json, subprocess
+POSES = r'''
+import sys, numpy as np
+sys.path.insert(0, '.')
+import torch; torch.cuda.init()
+from edge_alignment_amd import capi, synth
+capi.LIB_PATH = sys.argv[1]
+import bench
+cfg = synth.config_c2_twin(seed=2, n_points=50000)
+P = capi.Problem(*cfg["K"], dtype=capi.EA_F64); P.set_points(cfg["xyz"]); P.set_dt_grid(cfg["grid"]); P.set_loss(capi.LOSS_CAUCHY, 1.0)
+B = capi.Batch([P])
+Q, T = bench.step_poses(int(sys.argv[3]), 1000)
+r = B.eval_poses(Q, T)
+np.savez(sys.argv[2], lanes=np.array(B.info("poses_lane_per_pose")), **r)
+B.close(); P.close()
+'''
 CHILD = r'''
 import sys, numpy as np
 sys.path.insert(0, '.')
@@ -97,6 +115,20 @@ for dtype, tag in ((capi.EA_F64, "f64"), (capi.EA_F32, "f32")):
         np.savez(sys.argv[2] + "_%s_paths_buf%d.npz" % (tag, buf), **r)
     B.close(); P.close()
 '''
+if "--poses" in sys.argv:
+    import numpy as np, tempfile
+    K = sys.argv[sys.argv.index("--poses") + 1]
+    libs = sys.argv[1:3]
+    tmp = tempfile.mkdtemp()
+    for i, l in enumerate(libs):
+        o = subprocess.run(["timeout", "-k", "10", "300", sys.executable, '-c', POSES, os.path.abspath(l), os.path.join(tmp, "p%d.npz" % i), K], capture_output=True, text=True)
+        if o.returncode != 0:
+            print(l, 'FAILED', o.returncode, o.stderr[-1500:]); sys.exit(1)
+    a, b = (np.load(os.path.join(tmp, "p%d.npz" % i)) for i in (0, 1))
+    same = {f: bool(np.array_equal(a[f], b[f])) for f in ("cost", "JtJ", "Jtr", "n_invalid")}
+    rel = float((np.abs(a["cost"] - b["cost"]) / np.abs(a["cost"])).max())
+    print("K", K, "poses_lane_per_pose", int(a["lanes"]), int(b["lanes"]), "array_equal", same, "largest relative cost difference %.3g" % rel)
+    sys.exit(0 if same["JtJ"] and same["Jtr"] and same["n_invalid"] and np.all(np.isfinite(b["cost"])) else 1)
 if "--bits" in sys.argv:
     import numpy as np, tempfile
     libs = [a for a in sys.argv[1:] if a != "--bits"][:2]
