@@ -38,6 +38,7 @@ extern __device__ int g_lm_probe_row;
     }                                                                                               \
   } while (0)
 #endif
+#include "ea_lanes_stream.h"
 #include "ea_launch.h"
 #include "ea_poses_map.h"
 #include "ea_starts_map.h"
@@ -1888,17 +1889,24 @@ constexpr int kLanesWaves = 4, kLanesSub = 512 / kLanesWaves, kLanesVals = 29;  
 // instructions instead of ten registers held across the loads.
 template <typename IT> struct LanesStage {
   double cx_, cy_, cz_, iz, fu, fv;
-  bool valid;
+  unsigned long long bad;  // the lanes without a valid point, as a mask in scalar registers (lanes_any / lanes_mine)
   Row4<IT> row[4];
 };
+// "Some lane has no valid point", made once per point where the mask is formed and asked again where a fix-up stands: a scalar
+// compare and a scalar branch.  (The mask goes through an empty asm: where the compiler sees the ballot behind the test it
+// keeps the lanes' flag in a vector register instead and compares that again at every site.)
+__device__ __forceinline__ bool lanes_any(unsigned long long &m) {
+  asm volatile("" : "+s"(m));
+  return m != 0;
+}
+__device__ __forceinline__ bool lanes_mine(unsigned long long m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
 template <typename IT> __device__ __forceinline__ Row4<double> lanes_widen(const Row4<IT> &r) {
   Row4<double> o;
   o.p0 = (double)r.p0; o.p1 = (double)r.p1; o.p2 = (double)r.p2; o.p3 = (double)r.p3;
   return o;
 }
 // Stage 1 of a point: project, count a failed functor, move the lanes without a valid point to a harmless sample, and issue
-// the four row loads.  inb (uniform): the point exists -- an odd sub-run ends on a copy of its last point, and the loop's last
-// look-ahead on a point that is not summed at all.
+// the four row loads.  inb (uniform): the point exists -- an odd sub-run ends on a copy of its last point.
 template <bool BUF, bool IMG32>
 __device__ __forceinline__ void lanes_stage(const ProblemDesc &pd, const PoseLite<double> &ps, double x, double y, double z,
                                             bool inb, LanesStage<typename ImgOf<double, IMG32>::type> &st, int &n_bad) {
@@ -1908,11 +1916,12 @@ __device__ __forceinline__ void lanes_stage(const ProblemDesc &pd, const PoseLit
   const void *img_base = IMG32 ? pd.dt32 : pd.dt;
   Proj<T> pr;
   project_point<T>(pd, ps, x, y, z, pr);
-  st.valid = inb && pr.state == 1;
+  const bool valid = inb && pr.state == 1;
   n_bad += (inb && pr.state == 2) ? 1 : 0;
-  if (__any(!st.valid)) {  // (uniform test first, as in fused_chunk)
+  st.bad = __builtin_amdgcn_ballot_w64(!valid);
+  if (lanes_any(st.bad)) {  // (uniform test first, as in fused_chunk)
     asm volatile("" ::: "memory");  // (and kept a branch, as in jacobian_row)
-    if (!st.valid) { pr.iu = 0; pr.iv = 0; pr.fu = T(0); pr.fv = T(0); }
+    if (lanes_mine(st.bad)) { pr.iu = 0; pr.iv = 0; pr.fu = T(0); pr.fv = T(0); }
   }
   st.cx_ = pr.cx_; st.cy_ = pr.cy_; st.cz_ = pr.cz_; st.iz = pr.iz; st.fu = pr.fu; st.fv = pr.fv;
   if constexpr (BUF) {
@@ -1941,46 +1950,51 @@ __device__ __forceinline__ void lanes_stage(const ProblemDesc &pd, const PoseLit
 //
 // Every fix-up of a lane without a valid point, and the renormalisation of the product, is a uniform BRANCH (the empty asm, as
 // in jacobian_row): written as `__any(c) && c` alone the compiler turns them into moves under an exec mask, which every
-// wavefront issues for every point.  t_x and t_y are read from the wavefront's LDS pose copy where bx and by are formed.
+// wavefront issues for every point.  `cost` and `held` are touched behind such a branch as well: the unit Cauchy path spends no
+// instruction on them.
+//
+// `under` is called right behind bx, by and their fix-up, in front of the sixteen taps: what the caller issues there (the next
+// pair's coordinates, lanes_run) has the point's whole arithmetic to arrive in.
 struct LanesLogRun { double P, L; int E; };  // the product is (P + L) 2^E
-template <bool IMG32, bool UNIT>
+template <bool IMG32, bool UNIT, typename Under>
 __device__ __forceinline__ void lanes_sums(int k, const ProblemDesc &pd, const PoseLite<double> &ps_, double x, double y, double z,
                                            const LanesStage<typename ImgOf<double, IMG32>::type> &st, bool pair,
-                                           double (&acc)[28], double &cost, double &held, LanesLogRun &run,
-                                           const double (*s_pose)[64]) {
+                                           double (&acc)[28], double &cost, double &held, LanesLogRun &run, Under under) {
   typedef double T;
   PoseLite<T> ps = ps_;
   if constexpr (UNIT) ps.unit_q = 1;
   const T loss_a = Uni<T>::loss_a(pd);
+  unsigned long long bad = st.bad;
   Proj<T> pr;
   pr.cx_ = st.cx_; pr.cy_ = st.cy_; pr.cz_ = st.cz_; pr.iz = st.iz; pr.fu = st.fu; pr.fv = st.fv;
-  if constexpr (UNIT) {  // (t_x and t_y out of the wavefront's LDS copy again: not held through the sums)
-    asm volatile("" ::: "memory");
-    ps.t[0] = s_pose[10][threadIdx.x & 63]; ps.t[1] = s_pose[11][threadIdx.x & 63];
-  }
   pr.bx = st.cx_ + ps.t[0]; pr.by = st.cy_ + ps.t[1];
   pr.fxz = Uni<T>::fx(pd) * st.iz; pr.fyz = Uni<T>::fy(pd) * st.iz;
-  if (__any(!st.valid)) {  // (the rest of fused_chunk's fix-up; the sample was moved when the rows were asked for)
+  if (lanes_any(bad)) {  // (the rest of fused_chunk's fix-up; the sample was moved when the rows were asked for)
     asm volatile("" ::: "memory");  // (keeps the uniform branch a branch, as in jacobian_row: no masked moves on the common path)
-    if (!st.valid) {
+    if (lanes_mine(bad)) {
       pr.iz = T(1);
       pr.bx = T(0); pr.by = T(0);
       pr.fxz = T(0); pr.fyz = T(0);
     }
   }
+  under();
   T f, Fu, Fv;
   bicubic<T>(pr.fu, pr.fv, [&](int l) { return lanes_widen(st.row[l]); }, f, Fu, Fv);
   T J[6];
   jacobian_row<T>(pd, ps, pr, x, y, z, Fu, Fv, J);
+  // (The row is asked for HERE: left alone, the compiler moves the gradient and the Jacobian down behind the loss, next to the
+  // sums that use them, and the sixteen widened taps stay alive across the loss's branches -- thirty-two registers at the
+  // loop's peak, where the row takes twelve.  That difference is what lets the pose stay in registers: lanes_run.)
+  if constexpr (UNIT) asm volatile("" ::"v"(J[0]), "v"(J[1]), "v"(J[2]), "v"(J[3]), "v"(J[4]), "v"(J[5]));
   T rho, w;
   if (UNIT && pair) {
     // loss_point's Cauchy statements; its two selects for a lane without a valid point go behind the uniform branch
     const T xs = (f * f) * Uni<T>::loss_inv_b(pd);
     rho = xs + T(1);
     w = t_rcp<T>(rho);
-    if (__any(!st.valid)) {
+    if (lanes_any(bad)) {
       asm volatile("" ::: "memory");  // (keeps the uniform branch a branch, as in jacobian_row)
-      if (!st.valid) { w = T(0); rho = T(1); }
+      if (lanes_mine(bad)) { w = T(0); rho = T(1); }
     }
     // the factor into the lane's running product (ea_pair_log.h); the renormalisation is rare: uniform test first
     T p = run.P * rho;
@@ -1991,7 +2005,9 @@ __device__ __forceinline__ void lanes_sums(int k, const ProblemDesc &pd, const P
     }
     pl_run_take(run.P, run.L, rho, p);
   } else {
-    loss_point<T, 2, false>(pair, pd.loss_kind, loss_a, Uni<T>::loss_inv_b(pd), f * f, st.valid, T(1), rho, w);
+    if constexpr (UNIT) asm volatile("" ::: "memory");  // (kept a branch: nothing of `cost` and `held` on the unit Cauchy path)
+    loss_point<T, 2, false>(pair, pd.loss_kind, loss_a, Uni<T>::loss_inv_b(pd), f * f, !lanes_mine(bad), T(1), rho, w);
+    cost_point<T, 2>(k, pair, loss_a, rho, cost, held);
   }
   const T wr = w * f;
   int s = 0;
@@ -2002,60 +2018,73 @@ __device__ __forceinline__ void lanes_sums(int k, const ProblemDesc &pd, const P
     for (int b = a; b < 6; ++b) { acc[s] = t_fma<T>(wJa, J[b], acc[s]); ++s; }
     acc[kAccJtr + a] = t_fma<T>(J[a], wr, acc[kAccJtr + a]);
   }
-  if (!(UNIT && pair)) cost_point<T, 2>(k, pair, loss_a, rho, cost, held);
 }
 
-// A wavefront's sub-run of n_sub points at px / py / pz, two per iteration: both points are
-// projected and their eight row loads issued before the first is summed -- one trip to memory per pair, which the SIMD's
-// other wavefront covers -- and the coordinates (scalar loads) are asked for two pairs ahead; that look-ahead clamps to the
-// sub-run's last point.  (Staging the NEXT pair's rows under the sums as well was tried: with 56 registers of sums it does
-// not fit 256 registers without scratch.)  The running product of lanes_sums starts at 1 in front of the loop and becomes the
-// cost, (a^2 / 2) log, behind it; its three registers are paid for by t_x and t_y, which stay in LDS with R and t_z.
+// A wavefront's sub-run of n_sub points at px / py / pz, two per iteration: both points are projected and their eight row
+// loads issued before the first is summed -- one trip to memory per pair, which the SIMD's other wavefront covers.  (Staging
+// the NEXT pair's rows under the sums as well was tried: with 56 registers of sums it does not fit 256 registers without
+// scratch.)  The running product of lanes_sums starts at 1 in front of the loop and becomes the cost, (a^2 / 2) log, behind it.
+//
+// How the loop is pipelined (UNIT): nothing in it waits for anything but the pair's own eight row loads.
+//   R, t         stay in the lane's registers from the first point to the last: no read, no wait.  (They used to come out of
+//                an LDS copy per pair, and t_x, t_y once more per point, each read used at once; with the Jacobian row pinned
+//                in front of the loss -- lanes_sums -- the loop has the twenty-four registers to spare.)
+//   coordinates  wave-uniform, scalar loads (ea_lanes_stream.h says which indices in which iteration): ONE pair ahead, one
+//                16-byte load per array, straight into the scalar registers the next iteration's projections read -- x, y, z
+//                are dead once both points are projected (the unit Jacobian works on R a), so nothing is copied at the
+//                back-edge.  They are issued behind the second point's bx, by; the first instruction that needs them, and the
+//                only wait they meet, is the next iteration's first projection: the second point's taps, Jacobian, loss and
+//                27 sums later, some 170 vector instructions.  The end of a sub-run takes clamped 8-byte loads.
+// The general-quaternion form reads x, y, z in its Jacobian and copies the pair it loaded ahead.
 template <bool BUF, bool IMG32, bool UNIT>
-__device__ __forceinline__ void lanes_run(const ProblemDesc &pd, const PoseLite<double> &ps_, CPtr<double> px, CPtr<double> py,
-                                          CPtr<double> pz, int n_sub, bool pair, double (&acc)[28], int &n_bad,
-                                          const double (*s_pose)[64]) {
+__device__ __forceinline__ void lanes_run(const ProblemDesc &pd, const PoseLite<double> &ps, CPtr<double> px, CPtr<double> py,
+                                          CPtr<double> pz, int n_sub, bool pair, double (&acc)[28], int &n_bad) {
   typedef double T;
   typedef typename ImgOf<T, IMG32>::type IT;
+  typedef T T2 __attribute__((ext_vector_type(2), aligned(8)));  // two adjacent points of an array: one 16-byte scalar load
   if (n_sub <= 0) return;
-  const int lane = threadIdx.x & 63;
-  // (wave-uniform, and said so: left in a vector register, the look-ahead's six clamped addresses are formed by vector
-  // instructions and read back lane 0 by lane 0 -- 24 instructions per pair in front of scalar loads)
+  // (wave-uniform, and said so: left in a vector register, the addresses of the scalar loads are formed by vector
+  // instructions and read back lane 0 by lane 0)
   n_sub = __builtin_amdgcn_readfirstlane(n_sub);
-  const int last = n_sub - 1;
+  const int iters = lanes_stream_iters(n_sub);
   LanesLogRun run = {T(1), T(0), 0};
-  T X[2], Y[2], Z[2], NX[2], NY[2], NZ[2];  // this iteration's pair, the next one's
-  {
-    const int i1 = min(1, last), i2 = min(2, last), i3 = min(3, last);
-    X[0] = px[0]; X[1] = px[i1]; Y[0] = py[0]; Y[1] = py[i1]; Z[0] = pz[0]; Z[1] = pz[i1];
-    NX[0] = px[i2]; NX[1] = px[i3]; NY[0] = py[i2]; NY[1] = py[i3]; NZ[0] = pz[i2]; NZ[1] = pz[i3];
-  }
-#pragma nounroll
-  for (int i = 0; i < n_sub; i += 2) {
-    const int i4 = min(i + 4, last), i5 = min(i + 5, last);
-    const T FX[2] = {px[i4], px[i5]}, FY[2] = {py[i4], py[i5]}, FZ[2] = {pz[i4], pz[i5]};
-    T held = T(1), cost = T(0);
-    LanesStage<IT> A, B;
-    // The rotation and the translation are read by the two projections (and t_x, t_y once more per point in lanes_sums):
-    // they come out of the wavefront's LDS copy per pair (twelve conflict-free 8-byte reads) instead of occupying twenty-four
-    // registers through the sums.  (The barrier keeps the reads in the loop.)
-    PoseLite<T> ps = ps_;
-    if constexpr (UNIT) {
+  // slot k of the stream (ea_lanes_stream.h) into the pair (x, y, z)
+  const auto load_pair = [&](int k, T (&x)[2], T (&y)[2], T (&z)[2]) {
+    const LanesStreamLoad ld = lanes_stream_load(k, n_sub);
+    if (ld.wide) {
+      const T2 vx = *(const CPtr<T2>)(px + ld.i0), vy = *(const CPtr<T2>)(py + ld.i0), vz = *(const CPtr<T2>)(pz + ld.i0);
+      x[0] = vx.x; x[1] = vx.y; y[0] = vy.x; y[1] = vy.y; z[0] = vz.x; z[1] = vz.y;
+    } else {  // (the end of the sub-run)
       asm volatile("" ::: "memory");
-#pragma unroll
-      for (int k = 0; k < 9; ++k) ps.R[k] = s_pose[k][lane];
-      ps.t[2] = s_pose[9][lane]; ps.t[0] = s_pose[10][lane]; ps.t[1] = s_pose[11][lane];
+      x[0] = px[ld.i0]; x[1] = px[ld.i1]; y[0] = py[ld.i0]; y[1] = py[ld.i1]; z[0] = pz[ld.i0]; z[1] = pz[ld.i1];
     }
+  };
+  T X[2], Y[2], Z[2];  // this iteration's pair; UNIT: loaded by the iteration in front of it
+  load_pair(-1, X, Y, Z);
+#pragma nounroll
+  for (int k = 0; k < iters; ++k) {
+    T held, cost;  // (set and read behind the kept branch of every loss but the unit Cauchy one)
+    LanesStage<IT> A, B;
     lanes_stage<BUF, IMG32>(pd, ps, X[0], Y[0], Z[0], true, A, n_bad);
     // (both points' rows are under way before the first is summed; the rare general-quaternion form, which reads 27 more
     // words per lane and point, takes them one after the other)
-    if constexpr (UNIT) lanes_stage<BUF, IMG32>(pd, ps, X[1], Y[1], Z[1], i + 1 < n_sub, B, n_bad);
-    lanes_sums<IMG32, UNIT>(0, pd, ps, X[0], Y[0], Z[0], A, pair, acc, cost, held, run, s_pose);
-    if constexpr (!UNIT) lanes_stage<BUF, IMG32>(pd, ps, X[1], Y[1], Z[1], i + 1 < n_sub, B, n_bad);
-    lanes_sums<IMG32, UNIT>(1, pd, ps, X[1], Y[1], Z[1], B, pair, acc, cost, held, run, s_pose);
-    if (!(UNIT && pair)) acc[kAccCost] += cost;
+    if constexpr (UNIT) {
+      lanes_stage<BUF, IMG32>(pd, ps, X[1], Y[1], Z[1], 2 * k + 1 < n_sub, B, n_bad);
+      lanes_sums<IMG32, true>(0, pd, ps, T(0), T(0), T(0), A, pair, acc, cost, held, run, []() {});
+      lanes_sums<IMG32, true>(1, pd, ps, T(0), T(0), T(0), B, pair, acc, cost, held, run, [&]() { load_pair(k, X, Y, Z); });
+    } else {
+      T NX[2], NY[2], NZ[2];
+      load_pair(k, NX, NY, NZ);
+      lanes_sums<IMG32, false>(0, pd, ps, X[0], Y[0], Z[0], A, pair, acc, cost, held, run, []() {});
+      lanes_stage<BUF, IMG32>(pd, ps, X[1], Y[1], Z[1], 2 * k + 1 < n_sub, B, n_bad);
+      lanes_sums<IMG32, false>(1, pd, ps, X[1], Y[1], Z[1], B, pair, acc, cost, held, run, []() {});
 #pragma unroll
-    for (int k = 0; k < 2; ++k) { X[k] = NX[k]; Y[k] = NY[k]; Z[k] = NZ[k]; NX[k] = FX[k]; NY[k] = FY[k]; NZ[k] = FZ[k]; }
+      for (int j = 0; j < 2; ++j) { X[j] = NX[j]; Y[j] = NY[j]; Z[j] = NZ[j]; }
+    }
+    if (!(UNIT && pair)) {
+      asm volatile("" ::: "memory");  // (kept a branch, as the fix-ups are)
+      acc[kAccCost] += cost;
+    }
   }
   if (UNIT && pair) acc[kAccCost] = (T(0.5) * (Uni<T>::loss_a(pd) * Uni<T>::loss_a(pd))) * pl_run_log<LogOps>(run.P, run.L, run.E);
 }
@@ -2181,7 +2210,6 @@ __global__ __launch_bounds__(64 * kLanesWaves) __attribute__((amdgpu_waves_per_e
     double *rows_out, PosesTickets tk) {
   typedef double T;
   __shared__ __align__(16) double s_sum[kLanesWaves / 2][kLanesVals][64];
-  __shared__ __align__(16) double s_pose[kLanesWaves][12][64];  // each wavefront's own copy of R, t_z, t_x and t_y, lane by lane
   static_assert(sizeof(s_sum) >= sizeof(double) * kAccSlots * 65, "the fold's transposition fits the sums' array");
   const PosesLanesWork w = poses_lanes_work(blockIdx.x, shape, rows, g, 0);
   if (w.kind != 2) return;  // (uniform; not an item of the list)
@@ -2210,11 +2238,8 @@ __global__ __launch_bounds__(64 * kLanesWaves) __attribute__((amdgpu_waves_per_e
 #pragma unroll
     for (int i = 0; i < 28; ++i) acc[i] = T(0);
     int n_bad = 0;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) s_pose[wave][k][lane] = ps.R[k];
-    s_pose[wave][9][lane] = ps.t[2]; s_pose[wave][10][lane] = ps.t[0]; s_pose[wave][11][lane] = ps.t[1];
-    if (__all(ps.unit_q != 0)) lanes_run<BUF, IMG32, true>(pd, ps, px, py, pz, n_sub, pair, acc, n_bad, s_pose[wave]);
-    else lanes_run<BUF, IMG32, false>(pd, ps, px, py, pz, n_sub, pair, acc, n_bad, s_pose[wave]);
+    if (__all(ps.unit_q != 0)) lanes_run<BUF, IMG32, true>(pd, ps, px, py, pz, n_sub, pair, acc, n_bad);
+    else lanes_run<BUF, IMG32, false>(pd, ps, px, py, pz, n_sub, pair, acc, n_bad);
 
     // (w0 + w1) + (w2 + w3), lane by lane: the odd member of each pair hands its sums over, then the pair sums do the same
 #pragma unroll
