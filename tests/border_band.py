@@ -48,10 +48,20 @@ POSES = ((Q_ID, T_ID), (Q_SMALL, T_SMALL), (Q_NONUNIT, np.array([-0.001, 0.002, 
 POSE_FAR = (quat_from_axis_angle([0.1, 1.0, 0.0], np.deg2rad(12.0)), np.array([0.6, -0.4, 0.1]))
 
 
-def band_problem(H, W, n, seed, kind):
+def camera_C(H, W):
+    """An anisotropic, off-centre camera for an H x W image: fy = 1.37 fx, the principal point 3.25 pixels right of and
+    2.5 pixels above the centre.  Every intrinsic is float32-representable.  With fx != fy and cx - (W-1)/2 != cy - (H-1)/2
+    != 0, reading one axis' intrinsic for the other, or rebuilding the principal point from the extent, moves u or v by
+    pixels (tests/test_camera_axes_reference.py)."""
+    f = np.float32(1.1 * max(H, W))
+    return (float(f), float(np.float32(1.37 * f)), float(np.float32(0.5 * (W - 1) + 3.25)), float(np.float32(0.5 * (H - 1) - 2.5)))
+
+
+def band_problem(H, W, n, seed, kind, camera=None):
     """-> dict(image (H, W) float64 holding float32 values, grid (W, H) the Grid2D view of it, K (fx, fy, cx, cy),
     xyz (n, 3), uv (n, 2) the target pixels).  Texels and intrinsics are float32-representable, so fp32 problems, fp64
-    problems and the float32 mirror of an fp64 image hold the same numbers."""
+    problems and the float32 mirror of an fp64 image hold the same numbers.  camera: None -- fx = fy, the principal
+    point at the image centre; "C" -- camera_C(H, W), the same target pixels reached through that camera."""
     rng = np.random.default_rng(seed)
     if kind == "noise":      # every one of the 16 taps matters
         img = rng.random((H, W))
@@ -77,9 +87,14 @@ def band_problem(H, W, n, seed, kind):
     u[4 * m:5 * m] = np.where(k % 2 == 0, edge_u[rng.integers(0, 8, m)], rng.integers(-3, W + 3, m))
     v[4 * m:5 * m] = np.where(k % 3 == 0, edge_v[rng.integers(0, 8, m)], rng.integers(-3, H + 3, m))
     f = float(np.float32(1.1 * max(H, W)))
-    K = (f, f, 0.5 * (W - 1), 0.5 * (H - 1))
+    if camera is None:
+        K = (f, f, 0.5 * (W - 1), 0.5 * (H - 1))
+    elif camera == "C":
+        K = camera_C(H, W)
+    else:
+        raise ValueError(camera)
     z = rng.uniform(0.5, 5.0, n)
-    xyz = np.stack([(u - K[2]) * z / f, (v - K[3]) * z / f, z], axis=1)
+    xyz = np.stack([(u - K[2]) * z / K[0], (v - K[3]) * z / K[1], z], axis=1)
     return dict(image=img, grid=np.ascontiguousarray(img.T), K=K, xyz=xyz, uv=np.stack([u, v], axis=1), H=H, W=W, kind=kind)
 
 
@@ -109,21 +124,30 @@ def _rotation_and_derivatives(q):
     return R, [[[two * e for e in row] for row in M] for M in (dw, dx, dy, dz)]
 
 
+def _transposed(M):
+    return [[M[j][i] for j in range(3)] for i in range(3)]
+
+
 def _mat_vec(M, a):
     return [M[i][0] * a[0] + M[i][1] * a[1] + M[i][2] * a[2] for i in range(3)]
 
 
-def functor(image, K, xyz, q, t, dtype=np.longdouble, z_guard=0.01, z_eps=0.0, distortion=None, T12=None, T12inv=None):
+def functor(image, K, xyz, q, t, dtype=np.longdouble, z_guard=0.01, z_eps=0.0, distortion=None, T12=None, T12inv=None,
+            rot_transposed=False, grad_K=None):
     """Residual and raw 1x6 row of every point in arithmetic `dtype` -> dict(r (n,), J (n, 6), u, v, valid,
     band: some tap outside [0, W) x [0, H)).  image: (H, W), [v][u].  distortion: (k1, k2, p1, p2, k3) of EAResidueEx;
-    T12 (4x4): EAResidueSecondCam's rig transform (the pose acts between T12^-1 and T12)."""
+    T12 (4x4): EAResidueSecondCam's rig transform (the pose acts between T12^-1 and T12).  rot_transposed: the point is
+    warped by R(q)^T (the ROS node's functor indexes the row-major matrix column-wise), the row goes through
+    (dR/dq_i)^T; with z_guard = 0 and z_eps = 0.001 that is the ROS flavour.  grad_K: (fx, fy) taken in the row only, r
+    unchanged -- a deliberately wrong reference for tests/test_camera_axes_reference.py, never a kernel's yardstick."""
     ty = np.dtype(dtype).type
     img = np.asarray(image).astype(dtype)
     H, W = img.shape
     fx, fy, cx, cy = [ty(k) for k in K]
     P = np.asarray(xyz)[:, :3].astype(dtype)
-    q = [ty(e) for e in np.asarray(q, dtype=np.float64)]
-    t = [ty(e) for e in np.asarray(t, dtype=np.float64)]
+    # (float64 poses, as every kernel takes them, pass unchanged; a longdouble pose keeps its bits for difference quotients)
+    q = [ty(e) for e in np.asarray(q).astype(dtype)]
+    t = [ty(e) for e in np.asarray(t).astype(dtype)]
     one = ty(1)
     a = [P[:, 0], P[:, 1], P[:, 2]]
     if T12 is not None:
@@ -132,6 +156,8 @@ def functor(image, K, xyz, q, t, dtype=np.longdouble, z_guard=0.01, z_eps=0.0, d
         A, Ai = A.astype(dtype), Ai.astype(dtype)
         a = [m + Ai[i, 3] for i, m in enumerate(_mat_vec(Ai, a))]
     R, dR = _rotation_and_derivatives(q)
+    if rot_transposed:
+        R, dR = _transposed(R), [_transposed(M) for M in dR]
     c = [m + t[i] for i, m in enumerate(_mat_vec(R, a))]
     b = [m + A[i, 3] for i, m in enumerate(_mat_vec(A, c))] if T12 is not None else c
     valid = ~((b[2] < ty(z_guard)) & (b[2] > -ty(z_guard))) if z_guard > 0 else np.ones(len(P), bool)
@@ -170,8 +196,9 @@ def functor(image, K, xyz, q, t, dtype=np.longdouble, z_guard=0.01, z_eps=0.0, d
             Fu = Fu + wv[k] * du[l] * p
             Fv = Fv + dv[k] * wu[l] * p
     # d f / d b' through the projection (and the distortion), then back through T12 to the point the pose acts on
-    gx = (Fu * fx * xd_x + Fv * fy * yd_x) / bz
-    gy = (Fu * fx * xd_y + Fv * fy * yd_y) / bz
+    gfx, gfy = (fx, fy) if grad_K is None else (ty(grad_K[0]), ty(grad_K[1]))
+    gx = (Fu * gfx * xd_x + Fv * gfy * yd_x) / bz
+    gy = (Fu * gfx * xd_y + Fv * gfy * yd_y) / bz
     gb = [gx, gy, -(gx * x + gy * y)]
     g = [A[0, i] * gb[0] + A[1, i] * gb[1] + A[2, i] * gb[2] for i in range(3)] if T12 is not None else gb
     Jq = []
@@ -292,8 +319,9 @@ def _cached(key, make):
     return _CACHE[key]
 
 
-def problem(H, W, kind, n=N_GPU):
-    return _cached(("problem", H, W, kind, n), lambda: band_problem(H, W, n, 100 + SHAPES.index((H, W)) if (H, W) in SHAPES else 300 + H + W, kind))
+def problem(H, W, kind, n=N_GPU, camera=None):
+    return _cached(("problem", H, W, kind, n, camera),
+                   lambda: band_problem(H, W, n, 100 + SHAPES.index((H, W)) if (H, W) in SHAPES else 300 + H + W, kind, camera))
 
 
 class Case:
@@ -301,13 +329,18 @@ class Case:
     (set_dt_image_device of a torch tensor) or a callable(P) that fills the image itself (a frame producer; the reference
     then takes Problem.get_dt() as the image, and `tag` names the producer for the cache).  weights: (values (n,), name)
     -> Problem.set_weights; corrected rows, sums and bounds are then those of the weighted problem, with the weights the
-    device holds (Problem.get_weights).  Raises the library's EAError when the upload is refused."""
+    device holds (Problem.get_weights).  camera: as band_problem's.  flavour: (z_guard, z_eps, rot_transposed) ->
+    Problem.set_flavour, and the reference is evaluated with the same three.  Raises the library's EAError when the
+    upload is refused."""
 
-    def __init__(self, hip, H, W, kind, dtype, tile=None, variant=None, vname="", upload="grid", tag="", weights=None):
+    def __init__(self, hip, H, W, kind, dtype, tile=None, variant=None, vname="", upload="grid", tag="", weights=None,
+                 camera=None, flavour=None):
         self.hip, self.H, self.W, self.kind, self.dtype = hip, H, W, kind, dtype
         self.np = np.float32 if dtype == hip.EA_F32 else np.float64
-        self.pr = problem(H, W, kind)
-        self.variant = variant or {}
+        self.pr = problem(H, W, kind, camera=camera)
+        self.variant = dict(variant or {})
+        if flavour is not None:
+            self.variant.update(z_guard=float(flavour[0]), z_eps=float(flavour[1]), rot_transposed=bool(flavour[2]))
         self.base = (VARIANT_BASE if variant else WEIGHTED_BASE if weights is not None else PROJECT)[self.np]
         self.weights = None
         self.P = P = hip.Problem(*self.pr["K"], dtype=dtype)
@@ -330,6 +363,8 @@ class Case:
                 P.set_distortion(*self.variant["distortion"])
             if "T12" in self.variant:
                 P.set_second_camera(self.variant["T12"])
+            if flavour is not None:
+                P.set_flavour(*flavour)
             # the reference is fed the points the device holds: the caller's doubles, rounded once by an fp32 problem
             self.xyz = P.get_points()
             want = self.pr["xyz"] if self.np is np.float64 else self.pr["xyz"].astype(np.float32).astype(np.float64)
@@ -341,10 +376,12 @@ class Case:
         except BaseException:
             P.close()
             raise
-        self.key = (H, W, kind, self.np.__name__, vname, tag, weights[1] if weights is not None else "")
+        self.key = (H, W, kind, self.np.__name__, vname, tag, weights[1] if weights is not None else "", camera,
+                    tuple(flavour) if flavour is not None else None)
 
     def name(self):
-        return "%dx%d %s %s" % (self.H, self.W, self.key[5] or self.kind, "fp32" if self.np is np.float32 else "fp64")
+        return "%dx%d %s%s%s %s" % (self.H, self.W, self.key[5] or self.kind, " cam" + self.key[7] if self.key[7] else "",
+                                    " ros" if self.key[8] else "", "fp32" if self.np is np.float32 else "fp64")
 
     def _functor(self, pose, dtype):
         k = self.key + (tuple(pose[0]), tuple(pose[1]), np.dtype(dtype).name)

@@ -42,9 +42,12 @@ def _run(exe, pr, cases):
     return [np.array(l.split(), dtype=float) for l in out.strip().splitlines()]
 
 
-@pytest.fixture(scope="module")
-def small_problem():
-    return synth.make_problem(60, 80, 400, 12, 5, 65.0, 65.0, 39.5, 29.5,
+@pytest.fixture(scope="module", params=["centred", "camera_C"])
+def small_problem(request):
+    """fx == fy with the principal point at the centre, and the anisotropic, off-centre camera of tests/border_band.py"""
+    import border_band as bb
+    K = (65.0, 65.0, 39.5, 29.5) if request.param == "centred" else bb.camera_C(60, 80)
+    return synth.make_problem(60, 80, 400, 12, 5, *K,
                               planted_q=synth.quat_from_axis_angle([1, 2, 3], np.deg2rad(0.7)), planted_t=(0.004, -0.002, 0.003),
                               normalize=True)
 

@@ -549,3 +549,50 @@ def test_misuse_is_refused_and_leaves_every_problem_as_it_was(hip):
         assert not np.array_equal(got_p[0].get_dt(), want_p[0].get_dt())
     finally:
         _close(dup_b, want_b, got_b, want_p, got_p)
+
+
+# ---- anisotropic, off-centre cameras against the restatement ------------------------------------------------------------------
+# Every other comparison of this file is device against device.  fx read for fy, or cx and cy handed over in the wrong order,
+# would be the same mistake on both sides; the restatement takes the four intrinsics by name.
+AXES_CAMERAS = ((61.0, 83.5, 38.25, 14.5), (70.25, 52.0, 30.5, 21.75))
+
+
+def _held(xyz, dtype_name):
+    """what a problem of that dtype holds of the restatement's doubles"""
+    return xyz if dtype_name == "EA_F64" else xyz.astype(np.float32).astype(np.float64)
+
+
+def _ros_restatement(pp, bgr, depth, halvings, Kc):
+    """the host chain of tests/test_gpu_preprocess.py: x0.5 steps of the restatement, then SolveEA::setRefFrame's points"""
+    for k in range(halvings):
+        bgr, depth = pp.resize_half_bgr8(bgr), pp.resize_half_f32(depth, nan_to_zero=(k == 0))
+    return pp.ros_ref_points(bgr, depth, *Kc)[0].T
+
+
+@pytest.mark.parametrize("dtype_name", ["EA_F64", "EA_F32"])
+@pytest.mark.parametrize("halvings", [0, 1])
+@pytest.mark.parametrize("shape", [(37, 70), (64, 257)])
+def test_a_camera_per_problem_against_the_restatement(hip, shape, halvings, dtype_name):
+    """set_frames_ros and set_ref_frame_ros with two different cameras, at the full extent and halved once on the device: each
+    problem's points are oracle/preprocess_np.ros_ref_points with ITS camera, bit for bit; the same camera with the focal
+    lengths swapped gives other points on these frames"""
+    from oracle import preprocess_np as pp
+    H, W = shape
+    ref, dep, now = _pairs(H, W, halvings, 2, seed=31 + H + halvings, ref_kinds=("noise", "noise"))
+    dep = [np.where(d > 0, d, np.float32(0.0)) for d in dep]   # (finite: zeros stay, they become Z = 1)
+    dtype = getattr(hip, dtype_name)
+    got_p = [hip.Problem(*Kc, dtype=dtype) for Kc in AXES_CAMERAS]
+    one_p = [hip.Problem(*Kc, dtype=dtype) for Kc in AXES_CAMERAS]
+    batch = hip.Batch(got_p)
+    try:
+        batch.set_frames_ros(ref, dep, now, halvings=halvings)
+        for i, Kc in enumerate(AXES_CAMERAS):
+            one_p[i].set_ref_frame_ros(ref[i], dep[i], halvings=halvings)
+            want = _held(_ros_restatement(pp, ref[i], dep[i], halvings, Kc), dtype_name)
+            assert got_p[i].num_points == one_p[i].num_points == want.shape[0] > 100, i
+            assert np.array_equal(one_p[i].get_points(), want), ("set_ref_frame_ros", i)
+            assert np.array_equal(got_p[i].get_points(), want), ("set_frames_ros", i)
+            swapped = _held(_ros_restatement(pp, ref[i], dep[i], halvings, (Kc[1], Kc[0], Kc[2], Kc[3])), dtype_name)
+            assert not np.array_equal(swapped[:, 0], want[:, 0]) and not np.array_equal(swapped[:, 1], want[:, 1]), i
+    finally:
+        _close(batch, got_p, one_p)

@@ -56,6 +56,27 @@ def test_edge_align_test1_call_sequence(binaries, bundled_pair, golden, tmp_path
         assert int(v[16]) == int(v[13]) and v[17] < 1e-10
 
 
+def test_edge_align_test1_with_an_anisotropic_off_centre_camera(binaries, oracle, tmp_path):
+    """the facade's hand-off EAResidue::Create(fx, fy, cx, cy, ...) -> ea_problem_create with four different intrinsics,
+    read from the file: the solvable 80 x 60 problem of tests/test_gpu_camera_axes.py (fy = 1.37 fx, the principal
+    point off the centre) against the oracle's LM solve from the same start, with the pose bars of the test above"""
+    from test_gpu_camera_axes import solvable_problem
+    pr = solvable_problem()
+    assert len(set(pr["K"])) == 4
+    p = str(tmp_path / "camera_c.bin")
+    aX = np.concatenate([pr["xyz"].T, np.ones((1, pr["xyz"].shape[0]))], axis=0)
+    _write_problem(p, aX, pr["grid"], pr["K"])
+    out = subprocess.run([os.path.join(binaries, "standalone_test1"), p, "1"], capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr
+    v = [float(x) for x in out.stdout.split()]
+    q, t, term = np.array(v[:4]), np.array(v[4:7]), int(v[8])
+    qo, to, so = oracle.OracleProblem(pr["grid"], *pr["K"], loss=oracle.LOSS_CAUCHY, loss_a=1.0).solve(pr["xyz"], [1, 0, 0, 0], [0, 0, 0])
+    assert term == 0 == so["termination"] and so["num_iterations"] >= 3
+    assert synth.rotation_angle_between(q, qo) < 1e-7 and np.linalg.norm(t - to) < 1e-7
+    assert v[9] == pytest.approx(float(so["it_cost"][0]), rel=1e-10)
+    assert int(v[13]) == pr["xyz"].shape[0]
+
+
 def test_solve_ea_class_dogleg(binaries, oracle, bundled_pair, tmp_path):
     p = str(tmp_path / "pair13.bin")
     _write_problem(p, bundled_pair["aX"], bundled_pair["grids"][3], bundled_pair["K"])

@@ -8,6 +8,8 @@ import pytest
 from edge_alignment_amd import synth
 
 pytestmark = pytest.mark.gpu
+# the bars between a device solve and the oracle's from the same start (tests/test_gpu_camera_axes.py takes them from here)
+COST_RTOL, LIVE_COST, POSE_BAR = 1e-6, 1e-9, 1e-6
 
 
 def test_random_solves_follow_the_oracle(hip, oracle):
@@ -44,8 +46,8 @@ def test_random_solves_follow_the_oracle(hip, oracle):
         where = (trial, n, loss, opts)
         assert s["why"] == so["why"] and s["num_iterations"] == so["num_iterations"], where
         assert list(s["it_successful"]) == list(so["it_successful"]), where
-        live = so["it_cost"] > 1e-9 * so["initial_cost"]
-        assert np.allclose(s["it_cost"][live], so["it_cost"][live], rtol=1e-6, atol=0), where
+        live = so["it_cost"] > LIVE_COST * so["initial_cost"]
+        assert np.allclose(s["it_cost"][live], so["it_cost"][live], rtol=COST_RTOL, atol=0), where
         if live.all():
-            assert synth.rotation_angle_between(q, qo) < 1e-6 and np.linalg.norm(t - to) < 1e-6, where
+            assert synth.rotation_angle_between(q, qo) < POSE_BAR and np.linalg.norm(t - to) < POSE_BAR, where
     assert rejected_seen >= 5  # the sample does exercise the reject / shrink branch

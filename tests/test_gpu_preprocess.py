@@ -503,3 +503,51 @@ def test_ros_producers_from_full_resolution_frames(hip, oracle):
     with pytest.raises(hip.EAError):
         P = hip.Problem(*Kl)
         P.set_now_frame_ros(now[:478], halvings=2)                   # 478 is not divisible by 4
+
+
+# ---- anisotropic, off-centre cameras ------------------------------------------------------------------------------------------
+# Every camera above has fx == fy (and, but for uniform scalings, the principal point at the centre): a producer that reads fx
+# for fy or takes cx and cy in the wrong order would give the same points there.
+
+AXES_CAMERAS = ((61.0, 83.5, 38.25, 14.5), (70.25, 52.0, 30.5, 21.75))
+AXES_SIZES = ((37, 70), (64, 257))
+
+
+@pytest.mark.parametrize("dtype_name", ["f64", "f32"])
+@pytest.mark.parametrize("which", [0, 1])
+def test_reference_producers_carry_an_anisotropic_off_centre_camera(hip, frames, which, dtype_name):
+    """set_ref_frame, set_ref_frame_canny and set_ref_frame_ros (at the full extent and halved once on the device): the points
+    are the restatement's with that camera, bit for bit (an fp32 problem holds them rounded once), and the restatement
+    with the focal lengths swapped gives other points on the same frame"""
+    pp = frames["pp"]
+    Kc, (H, W) = AXES_CAMERAS[which], AXES_SIZES[which]
+    Ks = (Kc[1], Kc[0], Kc[2], Kc[3])
+    rng = np.random.default_rng(60 + which)
+
+    def held(x):
+        return x if dtype_name == "f64" else x.astype(np.float32).astype(np.float64)
+
+    def check(P, want, swapped, where):
+        assert P.num_points == want.shape[0] > 100, where
+        assert np.array_equal(P.get_points(), held(want)), where
+        assert not np.array_equal(held(swapped)[:, 0], held(want)[:, 0]) and not np.array_equal(held(swapped)[:, 1], held(want)[:, 1]), where
+
+    bgr = _random_frame(70 + which, H, W)
+    depth = rng.integers(400, 30000, (H, W)).astype(np.uint16)
+    depth[rng.random((H, W)) < 0.15] = 0
+    P = hip.Problem(*Kc, dtype=hip.EA_F64 if dtype_name == "f64" else hip.EA_F32)
+    try:
+        P.set_ref_frame(bgr, depth)
+        check(P, pp.get_aX(bgr, depth, *Kc)[0][:3].T, pp.get_aX(bgr, depth, *Ks)[0][:3].T, "laplacian")
+        P.set_ref_frame_canny(bgr, depth)
+        check(P, pp.get_aX_canny(bgr, depth, *Kc)[0][:3].T, pp.get_aX_canny(bgr, depth, *Ks)[0][:3].T, "canny")
+        for halvings in (0, 1):
+            s = 1 << halvings
+            full = _random_frame(80 + which, H * s, W * s)
+            df = (rng.random((H * s, W * s)) * 4.0 + 0.4).astype(np.float32)
+            df[rng.random((H * s, W * s)) < 0.2] = 0.0
+            r, d = (full, df) if halvings == 0 else (pp.resize_half_bgr8(full), pp.resize_half_f32(df, nan_to_zero=True))
+            P.set_ref_frame_ros(full, df, halvings=halvings)
+            check(P, pp.ros_ref_points(r, d, *Kc)[0].T, pp.ros_ref_points(r, d, *Ks)[0].T, ("ros", halvings))
+    finally:
+        P.close()

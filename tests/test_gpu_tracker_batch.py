@@ -413,3 +413,64 @@ def test_the_c_demo_prints_the_poses_of_the_python_class(hip, tmp_path):
         assert [int(v) for v in out[-1].split()] == [1, tb.info("hysteresis_rounds"), 3]
     finally:
         tb.close()
+
+
+# ---- a camera of its own per stream, against the restatement ------------------------------------------------------------------
+
+@pytest.mark.parametrize("flavour,halvings", [(0, 0), (1, 0), (2, 0), (2, 1)])
+def test_per_stream_cameras_against_the_restatement(hip, flavour, halvings):
+    """two streams with two different anisotropic, off-centre cameras, two pushes: the reference-side points of stream i are
+    oracle/preprocess_np's with camera i, bit for bit; the solved pose is that of a hand-built Problem with camera i (and,
+    for the Laplacian and Canny flavours, of the single Tracker) -- the equalities of _compare_push"""
+    from oracle import preprocess_np as pp
+    H, W = 37, 70
+    cams = ros.AXES_CAMERAS
+    s = 1 << halvings
+    rng = np.random.default_rng(40 + flavour + halvings)
+    scenes = [_random_frame(90 + 5 * i + flavour, H * s + 2, W * s + 2) for i in range(2)]
+    tb = hip.TrackerBatch(cams, dtype=hip.EA_F64, flavour=flavour, halvings=halvings)
+    hand = [hip.Problem(*cam, dtype=hip.EA_F64) for cam in cams]
+    single = [hip.Tracker(*cam, dtype=hip.EA_F64, flavour=flavour) for cam in cams] if flavour < 2 else []
+    try:
+        for i in range(2):
+            tb.problem(i).set_loss(hip.LOSS_CAUCHY, 1.0); hand[i].set_loss(hip.LOSS_CAUCHY, 1.0)
+            if single:
+                hip._StreamProblem(hip.load().ea_tracker_problem(single[i]._h), hip.EA_F64, 0).set_loss(hip.LOSS_CAUCHY, 1.0)
+        for k in range(2):
+            bgr = [sc[k:k + H * s, k:k + W * s].copy() for sc in scenes]
+            depth = [_clean_depth(H * s, W * s, rng) if flavour == 2 else _u16_depth(H, W, rng, 500) for _ in range(2)]
+            q, t, sums, aligned = tb.push_frames(bgr, depth)
+            for i, cam in enumerate(cams):
+                at = (flavour, halvings, "push", k + 1, "stream", i)
+                P = hand[i]
+                if k > 0:
+                    if flavour == 2:
+                        P.set_now_frame_ros(bgr[i], halvings=halvings)
+                    else:
+                        (P.set_now_frame if flavour == 0 else P.set_now_frame_canny)(bgr[i])
+                    qm, tm, sm = P.solve(*IDENTITY)
+                    assert aligned[i] and sm["termination"] != hip.FAILURE, at
+                    assert sm["num_successful_steps"] > 0 and not np.array_equal(qm, IDENTITY[0]), at   # (a pose that moved)
+                    assert np.array_equal(q[i], qm) and np.array_equal(t[i], tm), (at, q[i], qm, t[i], tm)
+                    assert sums[i]["num_iterations"] == sm["num_iterations"] and _bits(sums[i]["final_cost"], sm["final_cost"]), at
+                if flavour == 2:
+                    P.set_ref_frame_ros(bgr[i], depth[i], halvings=halvings)
+                else:
+                    (P.set_ref_frame if flavour == 0 else P.set_ref_frame_canny)(bgr[i], depth[i])
+                if flavour == 2:
+                    want = ros._ros_restatement(pp, bgr[i], depth[i], halvings, cam)
+                    swapped = ros._ros_restatement(pp, bgr[i], depth[i], halvings, (cam[1], cam[0], cam[2], cam[3]))
+                else:
+                    f = pp.get_aX if flavour == 0 else pp.get_aX_canny
+                    want = f(bgr[i], depth[i], *cam)[0][:3].T
+                    swapped = f(bgr[i], depth[i], cam[1], cam[0], cam[2], cam[3])[0][:3].T
+                got = tb.problem(i).get_points()
+                assert got.shape == want.shape and want.shape[0] > 50 and _bits(got, want), at
+                assert not np.array_equal(swapped[:, 0], want[:, 0]) and not np.array_equal(swapped[:, 1], want[:, 1]), at
+                if single:
+                    qs, ts, ss = single[i].push_frame(bgr[i], depth[i])
+                    assert np.array_equal(q[i], qs) and np.array_equal(t[i], ts), at
+                    sp = hip._StreamProblem(hip.load().ea_tracker_problem(single[i]._h), hip.EA_F64, 0)
+                    assert _bits(sp.get_points(), want), at
+    finally:
+        ros._close(tb, hand, single)
