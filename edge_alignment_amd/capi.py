@@ -57,6 +57,8 @@ EXPORTED = [
     "ea_tracker_batch_get_info",
     "ea_batch_set_frames_ros_pyramid", "ea_batch_set_frames_ros_pyramid_device", "ea_batch_solve_pyramid", "ea_resize_half_levels",
     "ea_tracker_batch_create_pyramid", "ea_tracker_batch_level_problem", "ea_tracker_batch_last_summaries",
+    "ea_problem_pose_stats", "ea_batch_pose_stats", "ea_default_keyframe_params", "ea_tracker_batch_set_keyframes",
+    "ea_tracker_batch_keyframe_state",
 ]
 
 # measurement hooks (edge_alignment_amd/csrc/ea_hip_dev.h): bound by bench.py, the A/B scripts and the tests that pin the
@@ -140,6 +142,27 @@ class CannyFrameParams(C.Structure):
 class RosFrameParams(C.Structure):
     _fields_ = [("full_height", C.c_int), ("full_width", C.c_int), ("halvings", C.c_int), ("threshold1", C.c_double),
                 ("threshold2", C.c_double)]
+
+
+class PoseStats(C.Structure):
+    _fields_ = [("n", C.c_int64), ("n_invalid", C.c_int64), ("n_visible", C.c_int64), ("n_inlier", C.c_int64),
+                ("n_flow", C.c_int64), ("sum_flow", C.c_double)]
+
+
+class KeyframeParams(C.Structure):
+    _fields_ = [("min_visible_fraction", C.c_double), ("min_inlier_fraction", C.c_double), ("inlier_residual", C.c_double),
+                ("max_mean_flow", C.c_double), ("max_frames", C.c_int), ("margin", C.c_int)]
+
+
+KEY_FIRST, KEY_SOLVE_FAILED, KEY_VISIBLE, KEY_INLIERS, KEY_FLOW, KEY_AGE = 1, 2, 4, 8, 16, 32
+
+
+class KeyframeState(C.Structure):
+    _fields_ = [("keyframe_push", C.c_int64), ("age", C.c_int), ("replaced", C.c_int), ("stats", PoseStats)]
+
+
+def pose_stats_to_dict(s):
+    return {k: getattr(s, k) for k, _ in PoseStats._fields_}
 
 
 _lib = None
@@ -313,6 +336,12 @@ def load():
     L.ea_tracker_batch_last_covariance.argtypes = [vp, C.c_int, covp]
     L.ea_tracker_batch_set_motion_prior.argtypes = [vp, C.c_double, C.c_double]
     L.ea_tracker_batch_get_info.argtypes = [vp, C.c_char_p, i64p]
+    L.ea_problem_pose_stats.argtypes = [vp, dp, dp, C.c_int, C.c_double, C.POINTER(PoseStats)]
+    L.ea_batch_pose_stats.argtypes = [vp, dp, dp, C.c_int, C.c_double, C.POINTER(PoseStats)]
+    L.ea_default_keyframe_params.argtypes = [C.POINTER(KeyframeParams)]
+    L.ea_default_keyframe_params.restype = None
+    L.ea_tracker_batch_set_keyframes.argtypes = [vp, C.POINTER(KeyframeParams)]
+    L.ea_tracker_batch_keyframe_state.argtypes = [vp, C.c_int, C.POINTER(KeyframeState)]
     _lib = L
     return L
 
@@ -706,6 +735,13 @@ class Problem:
         _check(load().ea_problem_residual_quantiles(self._h, _dp(q), _dp(t), _dp(probs), probs.size, _dp(values), C.byref(m)))
         return values, m.value
 
+    def pose_stats(self, q, t, margin=0, inlier_residual=float("inf")):
+        """ea_problem_pose_stats at (q, t): dict n, n_invalid, n_visible, n_inlier, n_flow, sum_flow"""
+        q, t = _f64(q), _f64(t)
+        s = PoseStats()
+        _check(load().ea_problem_pose_stats(self._h, _dp(q), _dp(t), int(margin), float(inlier_residual), C.byref(s)))
+        return pose_stats_to_dict(s)
+
     def set_flavour(self, z_guard=0.01, z_eps=0.0, rot_transposed=False):
         _check(load().ea_problem_set_flavour(self._h, z_guard, z_eps, int(rot_transposed)))
 
@@ -992,6 +1028,21 @@ class TrackerBatch:
     def set_motion_prior(self, sigma_rot, sigma_trans):
         _check(load().ea_tracker_batch_set_motion_prior(self._h, float(sigma_rot), float(sigma_trans)))
 
+    def set_keyframes(self, params="default", **fields):
+        """keyframe mode (ea_tracker_batch_set_keyframes): set_keyframes(None) = back to frame-to-frame; otherwise the defaults
+        (ea_default_keyframe_params) with the given fields of ea_keyframe_params replaced"""
+        if params is None:
+            _check(load().ea_tracker_batch_set_keyframes(self._h, None))
+            return
+        prm = keyframe_params(**fields)
+        _check(load().ea_tracker_batch_set_keyframes(self._h, C.byref(prm)))
+
+    def keyframe_state(self, i):
+        """stream i's keyframe state: dict keyframe_push, age, replaced (reason mask of the last push), stats (dict)"""
+        s = KeyframeState()
+        _check(load().ea_tracker_batch_keyframe_state(self._h, int(i), C.byref(s)))
+        return {"keyframe_push": s.keyframe_push, "age": s.age, "replaced": s.replaced, "stats": pose_stats_to_dict(s.stats)}
+
     def info(self, key):
         v = C.c_int64()
         _check(load().ea_tracker_batch_get_info(self._h, key.encode(), C.byref(v)))
@@ -1010,6 +1061,17 @@ class TrackerBatch:
             self.close()
         except Exception:
             pass
+
+
+def keyframe_params(**fields):
+    """ea_default_keyframe_params with the given fields replaced"""
+    prm = KeyframeParams()
+    load().ea_default_keyframe_params(C.byref(prm))
+    for k, v in fields.items():
+        if k not in dict(KeyframeParams._fields_):
+            raise TypeError("unknown keyframe parameter: " + k)
+        setattr(prm, k, v)
+    return prm
 
 
 def solve_pyramid(levels, q, t, **opts):
@@ -1273,6 +1335,13 @@ class Batch:
         _check(load().ea_batch_residual_quantiles(self._h, _dp(q), _dp(t), _dp(probs), probs.size, _dp(values),
                                                   m.ctypes.data_as(C.POINTER(C.c_int64))))
         return values, m
+
+    def pose_stats(self, q, t, margin=0, inlier_residual=float("inf")):
+        """ea_batch_pose_stats at q (n, 4), t (n, 3): one dict per problem (Problem.pose_stats' bits), two launches"""
+        q, t = _f64(q).reshape(-1, 4), _f64(t).reshape(-1, 3)
+        out = (PoseStats * max(len(self), 1))()
+        _check(load().ea_batch_pose_stats(self._h, _dp(q), _dp(t), int(margin), float(inlier_residual), out))
+        return [pose_stats_to_dict(out[i]) for i in range(len(self))]
 
     def covariance(self, q, t, **opts):
         """ea_batch_covariance: one covariance per problem at q (n, 4), t (n, 3) -> list of covariance_to_dict"""

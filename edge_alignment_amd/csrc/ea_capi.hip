@@ -2591,6 +2591,79 @@ extern "C" int ea_problem_residual_quantiles(ea_problem *p, const double q[4], c
   return batch_quantiles(b, q, t, nullptr, 1, probs, nq, values, n_valid);
 }
 
+// ---- how much of a reference is seen at a pose (ea_pose_stats; kernels: ea_pose_stats_kernel and its fold) ----------------
+//
+// Segments and poses up, the two launches, the rows down through one pinned block, ONE synchronisation: all on the batch's
+// stream.  The poses go through d_poses, like the quantiles': the resident poses of ea_batch_set_poses live elsewhere.
+static_assert(sizeof(PoseStatsRow) == sizeof(ea_pose_stats), "the fold writes ea_pose_stats as it stands");
+static int check_pose_stats_args(int margin, double inlier_residual) {
+  if (margin < 0) return fail(EA_ERR_INVALID_ARG, "margin must be >= 0");
+  if (!(inlier_residual >= 0.0)) return fail(EA_ERR_INVALID_ARG, "inlier_residual must be >= 0 (+Inf is allowed)");
+  return EA_OK;
+}
+
+static int batch_pose_stats(ea_batch *b, const double *q, const double *t, int margin, double inlier_residual, ea_pose_stats *out) {
+  int rc = batch_build(b);
+  if (rc != EA_OK) return rc;
+  const int nseg = (int)b->probs.size();
+  if (nseg > 65535) return fail(EA_ERR_INVALID_ARG, "more than 65535 problems in one statistics call");
+  const ProblemDesc *hd = reinterpret_cast<const ProblemDesc *>(b->h_desc);
+  const GroupDesc *hg = reinterpret_cast<const GroupDesc *>(b->h_desc + (size_t)b->nterms * sizeof(ProblemDesc));
+  const size_t o_segs = 0, o_out = o_segs + align16((size_t)nseg * sizeof(SelectSeg));
+  const size_t o_parts = o_out + align16((size_t)nseg * sizeof(PoseStatsRow));
+  struct Pinned {
+    unsigned char *p = nullptr;
+    ~Pinned() { cached_host_free(p); }
+  } pinned;
+  HIPCHK(cached_host_malloc(reinterpret_cast<void **>(&pinned.p), o_parts, hipHostMallocDefault, b->device));
+  SelectSeg *h_segs = reinterpret_cast<SelectSeg *>(pinned.p + o_segs);
+  int64_t rows = 0;
+  int max_n = 0;
+  for (int j = 0; j < nseg; ++j) {
+    const int term = hg[j].term_begin;  // the head family; its terms are not included
+    h_segs[j] = SelectSeg{rows, hd[term].n, term};
+    rows += pose_stats_rows(hd[term].n);
+    max_n = std::max(max_n, (int)hd[term].n);
+  }
+  DevBuf dev;
+  HIPCHK(cached_malloc(&dev.p, o_parts + (size_t)std::max<int64_t>(rows, 1) * sizeof(PoseStatsPartial), b->device));
+  unsigned char *d = dev.as<unsigned char>();
+  PoseStatsWork w;
+  w.nseg = nseg; w.max_n = max_n; w.margin = margin; w.inlier_residual = inlier_residual;
+  w.segs = reinterpret_cast<const SelectSeg *>(d + o_segs);
+  w.out = reinterpret_cast<PoseStatsRow *>(d + o_out);
+  w.partials = reinterpret_cast<PoseStatsPartial *>(d + o_parts);
+  HIPCHK(hipMemcpyAsync(d, pinned.p, o_out, hipMemcpyHostToDevice, b->stream));
+  if ((rc = batch_upload_poses(b, q, t)) != EA_OK) return rc;
+  HIPCHK(launch_pose_stats(b->dtype, w, b->d_probs, b->d_poses, b->stream));
+  HIPCHK(hipMemcpyAsync(pinned.p + o_out, d + o_out, (size_t)nseg * sizeof(PoseStatsRow), hipMemcpyDeviceToHost, b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  std::memcpy(out, pinned.p + o_out, (size_t)nseg * sizeof(ea_pose_stats));
+  return EA_OK;
+}
+
+extern "C" int ea_batch_pose_stats(ea_batch *b, const double *q, const double *t, int margin, double inlier_residual,
+                                   ea_pose_stats *out) {
+  if (!b || !q || !t || !out) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  int rc = check_pose_stats_args(margin, inlier_residual);
+  if (rc == EA_OK) rc = require_device();
+  if (rc != EA_OK) return rc;
+  return batch_pose_stats(b, q, t, margin, inlier_residual, out);
+}
+
+extern "C" int ea_problem_pose_stats(ea_problem *p, const double q[4], const double t[3], int margin, double inlier_residual,
+                                     ea_pose_stats *out) {
+  if (!p || !q || !t || !out) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  int rc = check_pose_stats_args(margin, inlier_residual);
+  if (rc == EA_OK) rc = require_device();
+  if (rc != EA_OK) return rc;
+  ea_batch *b;
+  if ((rc = self_batch(p, &b)) != EA_OK) return rc;
+  if ((rc = batch_build(b)) != EA_OK) return rc;  // (no DT image: EA_ERR_STATE, as ea_eval)
+  if (p->n == 0) return fail(EA_ERR_STATE, "no edge points (ea_problem_set_points)");
+  return batch_pose_stats(b, q, t, margin, inlier_residual, out);
+}
+
 // the select kernels alone, on the caller's values
 extern "C" int ea_selftest_select(int device, const double *values, const int64_t *offsets, int nseg, const double *probs, int nq,
                                   double *out, int64_t *n_valid) {

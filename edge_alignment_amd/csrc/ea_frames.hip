@@ -20,6 +20,7 @@
 #include "../../include/ea_hip.h"
 #include "ea_capi_internal.h"
 #include "ea_frame_ws.h"
+#include "ea_keyframe.h"
 #include "ea_launch.h"
 #include "ea_prior.h"
 #include "ea_types.h"
@@ -907,14 +908,16 @@ static int batch_counts_back(BatchFrames *j, const WsRegion<uint8_t> &edges, int
 }
 
 // Reference side, first half: the counts, room for each problem's points and their arrays into its slot
-static int batch_ref_room(BatchFrames *j);
+static int batch_ref_room(BatchFrames *j, const unsigned char *take = nullptr);
 static int batch_ref_counts(BatchFrames *j, const WsRegion<uint8_t> &edges, int threshold) {
   const int rc_counts = batch_counts_back(j, edges, threshold);
   return rc_counts != EA_OK ? rc_counts : batch_ref_room(j);
 }
-// (the counts are in h_totals)
-static int batch_ref_room(BatchFrames *j) {
+// (the counts are in h_totals; take: the multi-stream tracker's keyframe mode -- a problem with take[i] == 0 keeps the points
+// it has: its slot stays at capacity 0 and nothing of it is touched)
+static int batch_ref_room(BatchFrames *j, const unsigned char *take) {
   for (size_t i = 0; i < j->n; ++i) {
+    if (take && !take[i]) continue;
     ea_problem *p = j->probs[i];
     const int total = j->h_totals[i];
     const int rc = ref_points_room(p, total);
@@ -1547,6 +1550,7 @@ struct TrackerStream {
   ea_covariance cov_last{};
   bool motion_set = false;
   PriorDesc installed = {};
+  ea_keyframe_state key{};  // ea_tracker_batch_set_keyframes
 };
 }  // namespace
 
@@ -1575,6 +1579,10 @@ struct ea_tracker_batch {
   // ea_tracker_batch_get_info
   int last_aligned = 0, last_bare = 0, last_rounds = 0, last_edge_passes = 0;
   int64_t pushes = 0;
+  // keyframe mode (ea_tracker_batch_set_keyframes): off = every pushed frame becomes every stream's reference
+  bool key_on = false;
+  ea_keyframe_params key_prm{};
+  int last_taken = 0;
 };
 
 static int tracker_batch_create(ea_tracker_batch **out, const ea_camera *cams, int count, int levels, int dtype, int device,
@@ -1655,6 +1663,7 @@ static void tracker_stream_drop(ea_tracker_batch *tb, size_t i) {
   }
   tb->st[i].frames = 0;
   tb->st[i].cov_valid = false;
+  tb->st[i].key = ea_keyframe_state{};
 }
 
 // A push that failed past its checks: some streams' images are the new frame's, some references may be, nothing says which.
@@ -1737,7 +1746,7 @@ static int tracker_batch_push(ea_tracker_batch *tb, const uint8_t *const *bgr, c
 
   const size_t n = tb->probs.size();
   tb->pushes++;
-  tb->last_aligned = tb->last_bare = tb->last_rounds = tb->last_edge_passes = 0;
+  tb->last_aligned = tb->last_bare = tb->last_rounds = tb->last_edge_passes = tb->last_taken = 0;
   for (size_t i = 0; i < n; ++i) tb->st[i].cov_valid = false;
   if (aligned) std::fill(aligned, aligned + n, 0);
   if (summaries) std::memset(summaries, 0, n * sizeof(*summaries));
@@ -1818,7 +1827,15 @@ static int tracker_batch_push(ea_tracker_batch *tb, const uint8_t *const *bgr, c
   const size_t na = al.size();
   // per stream: the pose its solve started from and the one it returned
   std::vector<double> q0(4 * n), t0(3 * n), qs(4 * n), ts(3 * n);
+  // keyframe mode: per stream, was it aligned / did its solve fail, and the statistics at the pose its solve returned
+  std::vector<unsigned char> is_al(n, 0), solve_failed(n, 0);
+  std::vector<ea_pose_stats> kstats;
+  if (tb->key_on) {
+    kstats.resize(n);
+    std::memset(kstats.data(), 0, n * sizeof(ea_pose_stats));
+  }
   for (int i : al) {
+    is_al[(size_t)i] = 1;
     TrackerStream &s = tb->st[(size_t)i];
     std::memcpy(&q0[4 * (size_t)i], s.q, sizeof(s.q));
     std::memcpy(&t0[3 * (size_t)i], s.t, sizeof(s.t));
@@ -1846,6 +1863,7 @@ static int tracker_batch_push(ea_tracker_batch *tb, const uint8_t *const *bgr, c
       tb->last_sums[i] = sg[k];
       const bool failure = sg[k].termination == EA_FAILURE;
       ok += failure ? 0 : 1;
+      solve_failed[i] = failure ? 1 : 0;
       // (a failed solve: the stream keeps its prior, and the covariance call below sees it at its start pose)
       std::memcpy(&qs[4 * i], failure ? &q0[4 * i] : &qg[4 * k], 4 * sizeof(double));
       std::memcpy(&ts[3 * i], failure ? &t0[3 * i] : &tg[3 * k], 3 * sizeof(double));
@@ -1869,22 +1887,46 @@ static int tracker_batch_push(ea_tracker_batch *tb, const uint8_t *const *bgr, c
         s.cov_valid = true;
       }
     }
+    if (tb->key_on && ok > 0) {
+      // keyframe mode: how much of each reference is still seen at the returned pose -- one call for the group, on the batch
+      // that solved it, before anything overwrites points.  A failed solve has no pose to take them at: its stream keeps zeros.
+      std::vector<ea_pose_stats> stg(ng);
+      TBRC(ea_batch_pose_stats(solver, qg.data(), tg.data(), tb->key_prm.margin, tb->key_prm.inlier_residual, stg.data()));
+      for (size_t k = 0; k < ng; ++k)
+        if (sg[k].termination != EA_FAILURE) kstats[(size_t)grp[k]] = stg[k];
+    }
   }
 
-  // ---- the frame's edge points become every stream's reference
-  if (!ros) TBRC(batch_counts_fetch(&j));
-  TBRC(batch_ref_room(&j));
-  TBCHK(upload_table(&j));
-  if (ros) {
-    if (j.max_total > 0) TBCHK(launch_edge_scatter_ros_stack(j.dtype, j.f, ws.edges.at(base), ws.counts.at(base), nullptr));
-    TBCHK(launch_depth_weights_frames(j.dtype, j.f, j.max_weighted, nullptr));
-  } else {
-    TBRC(batch_ref_scatter(j, edges, ref_threshold, z_scaling));
+  // ---- the frame's edge points become the reference of every stream -- in keyframe mode, of the streams whose rule says so
+  // (keyframe_decide); a flavour-2 stream whose frame has no edge keeps what it holds
+  std::vector<unsigned char> take(n, 1);
+  std::vector<int> why(n, 0);
+  bool any_take = true;
+  if (tb->key_on) {
+    any_take = false;
+    for (size_t i = 0; i < n; ++i) {
+      const bool bare = !j.no_image.empty() && j.no_image[i];
+      why[i] = bare ? 0 : keyframe_decide(kstats[i], tb->key_prm, tb->st[i].key.age + 1, is_al[i] != 0, solve_failed[i] != 0);
+      take[i] = why[i] != 0;
+      any_take = any_take || take[i];
+    }
+  }
+  if (!ros && any_take) TBRC(batch_counts_fetch(&j));
+  TBRC(batch_ref_room(&j, tb->key_on ? take.data() : nullptr));
+  if (any_take) {
+    TBCHK(upload_table(&j));
+    if (ros) {
+      if (j.max_total > 0) TBCHK(launch_edge_scatter_ros_stack(j.dtype, j.f, ws.edges.at(base), ws.counts.at(base), nullptr));
+      TBCHK(launch_depth_weights_frames(j.dtype, j.f, j.max_weighted, nullptr));
+    } else {
+      TBRC(batch_ref_scatter(j, edges, ref_threshold, z_scaling));
+    }
   }
   TBCHK(hipDeviceSynchronize());
 #undef TBCHK
 #undef TBRC
-  for (size_t i = 0; i < n; ++i) ref_points_landed(tb->probs[i], j.slots[i].capacity);
+  for (size_t i = 0; i < n; ++i)
+    if (take[i]) ref_points_landed(tb->probs[i], j.slots[i].capacity);
   // priors and frame counts advance only with the new references in place
   for (int a : al) {
     const size_t i = (size_t)a;
@@ -1893,9 +1935,29 @@ static int tracker_batch_push(ea_tracker_batch *tb, const uint8_t *const *bgr, c
     if (aligned) aligned[i] = 1;
   }
   for (size_t i = 0; i < n; ++i) {
-    std::memcpy(q_rel + 4 * i, tb->st[i].q, sizeof(tb->st[i].q));
-    std::memcpy(t_rel + 3 * i, tb->st[i].t, sizeof(tb->st[i].t));
-    tb->st[i].frames += 1;
+    TrackerStream &s = tb->st[i];
+    if (tb->key_on) {
+      // the pose solved in this push against the keyframe in use during it (an unaligned stream: the identity); a stream that
+      // took the frame starts its next solve at the identity, a kept one at the pose just stored
+      const double q_id[4] = {1, 0, 0, 0}, t_id[3] = {0, 0, 0};
+      std::memcpy(q_rel + 4 * i, is_al[i] ? s.q : q_id, sizeof(s.q));
+      std::memcpy(t_rel + 3 * i, is_al[i] ? s.t : t_id, sizeof(s.t));
+      s.key.replaced = why[i];
+      s.key.stats = kstats[i];
+      if (take[i]) {
+        std::memcpy(s.q, q_id, sizeof(s.q));
+        std::memcpy(s.t, t_id, sizeof(s.t));
+        s.key.age = 0;
+        s.key.keyframe_push = tb->pushes;
+        tb->last_taken++;
+      } else if (is_al[i]) {
+        s.key.age += 1;
+      }
+    } else {
+      std::memcpy(q_rel + 4 * i, s.q, sizeof(s.q));
+      std::memcpy(t_rel + 3 * i, s.t, sizeof(s.t));
+    }
+    s.frames += 1;
   }
   tb->last_aligned = (int)na;
   return EA_OK;
@@ -1940,7 +2002,7 @@ static int tracker_batch_push_pyramid(ea_tracker_batch *tb, const uint8_t *const
 
   const size_t n = tb->probs.size();
   tb->pushes++;
-  tb->last_aligned = tb->last_bare = tb->last_rounds = tb->last_edge_passes = 0;
+  tb->last_aligned = tb->last_bare = tb->last_rounds = tb->last_edge_passes = tb->last_taken = 0;
   for (size_t i = 0; i < n; ++i) tb->st[i].cov_valid = false;
   if (aligned) std::fill(aligned, aligned + n, 0);
   if (summaries) std::memset(summaries, 0, n * sizeof(*summaries));
@@ -2121,7 +2183,7 @@ extern "C" int ea_tracker_batch_reset(ea_tracker_batch *tb, int i) {
   HIPCHK(hipSetDevice(tb->device));
   for (size_t s = 0; s < tb->probs.size(); ++s) {
     if (i >= 0 && s != (size_t)i) continue;
-    tracker_stream_drop(tb, s);
+    tracker_stream_drop(tb, s);  // (its keyframe state too)
     const double q[4] = {1, 0, 0, 0};
     std::memcpy(tb->st[s].q, q, sizeof(q));
     std::memset(tb->st[s].t, 0, sizeof(tb->st[s].t));
@@ -2164,6 +2226,34 @@ extern "C" int ea_tracker_batch_set_motion_prior(ea_tracker_batch *tb, double si
   return EA_OK;
 }
 
+extern "C" void ea_default_keyframe_params(ea_keyframe_params *p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->min_visible_fraction = 0.75;  // (an untuned starting value)
+}
+
+extern "C" int ea_tracker_batch_set_keyframes(ea_tracker_batch *tb, const ea_keyframe_params *p) {
+  if (!tb) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (p && !keyframe_params_ok(*p))
+    return fail(EA_ERR_INVALID_ARG, "keyframe parameters: no NaN field, margin >= 0, inlier_residual >= 0");
+  if (p && tb->levels > 1) return fail(EA_ERR_STATE, "keyframe mode is not available with pyramid levels (levels > 1)");
+  for (const TrackerStream &s : tb->st)
+    if (s.frames > 0)
+      return fail(EA_ERR_STATE, "a stream holds a reference: set the mode before the first push or after ea_tracker_batch_reset(-1)");
+  tb->key_on = p != nullptr;
+  if (p) tb->key_prm = *p;
+  for (TrackerStream &s : tb->st) s.key = ea_keyframe_state{};
+  return EA_OK;
+}
+
+extern "C" int ea_tracker_batch_keyframe_state(ea_tracker_batch *tb, int i, ea_keyframe_state *out) {
+  if (!tb || !out) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (i < 0 || (size_t)i >= tb->st.size()) return fail(EA_ERR_INVALID_ARG, "no such stream");
+  if (!tb->key_on) return fail(EA_ERR_STATE, "keyframe mode is off (ea_tracker_batch_set_keyframes)");
+  *out = tb->st[(size_t)i].key;
+  return EA_OK;
+}
+
 extern "C" int ea_tracker_batch_get_info(const ea_tracker_batch *tb, const char *key, int64_t *value) {
   if (!tb || !key || !value) return fail(EA_ERR_INVALID_ARG, "NULL argument");
   const std::string k = key;
@@ -2173,6 +2263,8 @@ extern "C" int ea_tracker_batch_get_info(const ea_tracker_batch *tb, const char 
   else if (k == "edge_passes") *value = tb->last_edge_passes;
   else if (k == "frames") *value = tb->pushes;
   else if (k == "levels") *value = tb->levels;
+  else if (k == "keyframes_taken") *value = tb->last_taken;
+  else if (k == "keyframe_mode") *value = tb->key_on ? 1 : 0;
   else return fail(EA_ERR_INVALID_ARG, "unknown info key: " + k);
   return EA_OK;
 }

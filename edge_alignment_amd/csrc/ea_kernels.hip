@@ -230,6 +230,7 @@ struct Proj {
   T fu, fv;        // fractional parts of (u, v)
   int iu, iv;      // floor(u), floor(v), saturated to [-2, W] / [-2, H]
   int state;       // 0 = lane has no point, 1 = valid, 2 = functor returned false
+  T u, v;          // the projection itself (read by ea_pose_stats_kernel alone; dead, and dropped, in every other kernel)
 };
 
 template <typename T, typename PS>
@@ -261,6 +262,7 @@ __device__ __forceinline__ void project_point(const ProblemDesc &pd, const PS &p
   o.iu = (int)fmin(fmax(uf, T(-2)), (T)pd.W);
   o.iv = (int)fmin(fmax(vf, T(-2)), (T)pd.H);
   o.state = bad ? 2 : 1;
+  o.u = u; o.v = v;
 }
 
 // ---- residual variants: EAResidueEx (Brown-Conrady distortion, utils.h:102-177),
@@ -276,6 +278,7 @@ struct ProjV {
   T fu, fv;
   int iu, iv;
   int state;
+  T u, v;           // as Proj's
 };
 
 template <typename T, typename PS>
@@ -337,6 +340,7 @@ __device__ __forceinline__ void project_point_var(const ProblemDesc &pd, const P
   o.iu = (int)fmin(fmax(uf, T(-2)), (T)pd.W);
   o.iv = (int)fmin(fmax(vf, T(-2)), (T)pd.H);
   o.state = bad ? 2 : 1;
+  o.u = u; o.v = v;
 }
 
 template <typename T, typename PS>
@@ -3253,6 +3257,122 @@ __global__ __launch_bounds__(kSelectThreads) void ea_select_scan_kernel(
     h[2 * tid + 1] = zero;
   }
 }
+
+// ------------------------------------------------------------------------------------------------
+// How much of a reference is seen at a pose (ea_batch_pose_stats; the definitions are in ea_hip.h).
+//
+// Shaped like the key pass above: one lane per point, blockIdx.y the problem's segment (sg.begin: its first partial row).
+// Per lane the projection at the pose, the visibility test on the saturated floor -- -2 and W / H, where the saturation
+// sets in, lie outside every accepted range, so the test is the unsaturated one's -- and for a visible point the four row
+// loads, the bicubic value and the projection at the identity (R = I, t = 0 in the kernel's type: what the pose kernel makes
+// of q = (1, 0, 0, 0), so the flow at the identity is exactly 0).  The divisor's sign is read off its reciprocal: 0 < iz <
+// Inf.  Counts: a ballot and a popcount per wavefront.  The flow: the fixed xor butterfly of the wavefront, then the four
+// wavefronts in order.  ONE partial row per workgroup, no atomics: a segment's partials depend on its own points alone.
+template <typename T>
+__device__ __forceinline__ bool pose_stats_project(const ProblemDesc &pd, const PoseLite<T> &ps, T x, T y, T z, T &u, T &v, T &fu,
+                                                   T &fv, int &iu, int &iv, bool &front) {
+  T iz;
+  bool ok;
+  if (pd.variant & 3) {
+    ProjV<T> pv;
+    project_point_var<T>(pd, ps, x, y, z, pv);
+    u = pv.u; v = pv.v; fu = pv.fu; fv = pv.fv; iu = pv.iu; iv = pv.iv; iz = pv.iz; ok = pv.state == 1;
+  } else {
+    Proj<T> pr;
+    project_point<T>(pd, ps, x, y, z, pr);
+    u = pr.u; v = pr.v; fu = pr.fu; fv = pr.fv; iu = pr.iu; iv = pr.iv; iz = pr.iz; ok = pr.state == 1;
+  }
+  front = iz > T(0) && iz < (T)__builtin_inf();
+  return ok;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kPoseStatsThreads) void ea_pose_stats_kernel(
+    const ProblemDesc *__restrict__ probs, const SelectSeg *__restrict__ segs, const PoseState *__restrict__ poses, int margin,
+    double inlier_residual, PoseStatsPartial *__restrict__ partials) {
+  __shared__ int s_cnt[kPoseStatsThreads / 64][4];
+  __shared__ double s_sum[kPoseStatsThreads / 64];
+  const SelectSeg sg = segs[blockIdx.y];
+  const int first = blockIdx.x * kPoseStatsThreads;
+  if (first >= sg.n) return;  // (uniform)
+  const ProblemDesc &pd = probs[sg.term];
+  const PoseState &full = poses[pd.group];
+  const int tid = threadIdx.x, i = first + tid;
+  bool invalid = false, visible = false, inlier = false, flow = false;
+  double dist = 0.0;
+  if (i < sg.n) {
+    PoseLite<T> at, id;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) { at.R[k] = Uni<T>::R(full)[k]; id.R[k] = (k % 4 == 0) ? T(1) : T(0); }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { at.t[k] = Uni<T>::t(full)[k]; id.t[k] = T(0); }
+    at.unit_q = id.unit_q = 1;  // (no Jacobian here)
+    at.full = id.full = &full;
+    const T x = static_cast<const T *>(pd.x)[i], y = static_cast<const T *>(pd.y)[i], z = static_cast<const T *>(pd.z)[i];
+    T u, v, fu, fv;
+    int iu, iv;
+    bool front;
+    const bool ok = pose_stats_project<T>(pd, at, x, y, z, u, v, fu, fv, iu, iv, front);
+    invalid = !ok;
+    visible = ok && front && iu >= margin && iu <= pd.W - 2 - margin && iv >= margin && iv <= pd.H - 2 - margin;
+    if (visible) {
+      const int pitch = pd.pitch;
+      const T *base = static_cast<const T *>(pd.dt) + (size_t)kImagePad * (size_t)pitch + kImagePad + (ptrdiff_t)(iv - 1) * pitch + (iu - 1);
+      const T f = bicubic_value<T>(fu, fv, [&](int l) { return *reinterpret_cast<const Row4<T> *>(base + (ptrdiff_t)l * pitch); });
+      inlier = fabs((double)f) <= inlier_residual;
+      T u0, v0, fu0, fv0;
+      int iu0, iv0;
+      bool front0;
+      const bool ok0 = pose_stats_project<T>(pd, id, x, y, z, u0, v0, fu0, fv0, iu0, iv0, front0);
+      flow = ok0 && front0;
+      if (flow) {
+        const double du = (double)u - (double)u0, dv = (double)v - (double)v0;
+        dist = sqrt(fma(du, du, dv * dv));
+      }
+    }
+  }
+  const int lane = tid & 63, wave = tid >> 6;
+  const int c0 = __popcll(__builtin_amdgcn_ballot_w64(invalid)), c1 = __popcll(__builtin_amdgcn_ballot_w64(visible));
+  const int c2 = __popcll(__builtin_amdgcn_ballot_w64(inlier)), c3 = __popcll(__builtin_amdgcn_ballot_w64(flow));
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) dist += __shfl_xor(dist, m, 64);
+  if (lane == 0) {
+    s_cnt[wave][0] = c0; s_cnt[wave][1] = c1; s_cnt[wave][2] = c2; s_cnt[wave][3] = c3;
+    s_sum[wave] = dist;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    PoseStatsPartial o = {0, 0, 0, 0, 0.0, 0.0};
+#pragma unroll
+    for (int w = 0; w < kPoseStatsThreads / 64; ++w) {
+      o.n_invalid += s_cnt[w][0]; o.n_visible += s_cnt[w][1]; o.n_inlier += s_cnt[w][2]; o.n_flow += s_cnt[w][3];
+      o.sum_flow += s_sum[w];
+    }
+    partials[sg.begin + blockIdx.x] = o;
+  }
+}
+
+// the fold: one wavefront per segment; lane L takes the partials L, L + 64, ... in that order, then the same butterfly.  The
+// order is a function of the segment's point count alone.
+__global__ __launch_bounds__(64) void ea_pose_stats_fold_kernel(const SelectSeg *__restrict__ segs,
+                                                                  const PoseStatsPartial *__restrict__ partials,
+                                                                  PoseStatsRow *__restrict__ out) {
+  const SelectSeg sg = segs[blockIdx.x];
+  const int rows = (sg.n + kPoseStatsThreads - 1) / kPoseStatsThreads, lane = threadIdx.x;
+  long long c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+  double sum = 0.0;
+  for (int k = lane; k < rows; k += 64) {
+    const PoseStatsPartial p = partials[sg.begin + k];
+    c0 += p.n_invalid; c1 += p.n_visible; c2 += p.n_inlier; c3 += p.n_flow;
+    sum += p.sum_flow;
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    c0 += __shfl_xor(c0, m, 64); c1 += __shfl_xor(c1, m, 64); c2 += __shfl_xor(c2, m, 64); c3 += __shfl_xor(c3, m, 64);
+    sum += __shfl_xor(sum, m, 64);
+  }
+  if (lane == 0) out[blockIdx.x] = PoseStatsRow{(int64_t)sg.n, (int64_t)c0, (int64_t)c1, (int64_t)c2, (int64_t)c3, sum};
+}
 #endif  // !EA_TU_VARIANT
 
 // ------------------------------------------------------------------------------------------------
@@ -3743,6 +3863,21 @@ hipError_t launch_select(const SelectWork &w, hipStream_t stream) {
     if (hipError_t e = hipGetLastError()) return e;
   }
   return hipSuccess;
+}
+
+hipError_t launch_pose_stats(int dtype, const PoseStatsWork &w, const ProblemDesc *probs, const PoseState *poses, hipStream_t stream) {
+  if (w.nseg < 1 || w.nseg > 65535 || w.max_n < 0 || w.margin < 0 || !w.segs || !w.partials || !w.out) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)pose_stats_rows(w.max_n), (unsigned)w.nseg);
+  if (w.max_n > 0) {
+    if (dtype == 1)
+      hipLaunchKernelGGL((ea_pose_stats_kernel<float>), grid, dim3(kPoseStatsThreads), 0, stream, probs, w.segs, poses, w.margin,
+                         w.inlier_residual, w.partials);
+    else
+      hipLaunchKernelGGL((ea_pose_stats_kernel<double>), grid, dim3(kPoseStatsThreads), 0, stream, probs, w.segs, poses, w.margin,
+                         w.inlier_residual, w.partials);
+  }
+  hipLaunchKernelGGL(ea_pose_stats_fold_kernel, dim3((unsigned)w.nseg), dim3(64), 0, stream, w.segs, w.partials, w.out);
+  return hipGetLastError();
 }
 
 hipError_t launch_grid_to_image(int dtype, const double *grid, int W, int H, void *dst, int pitch, float *dst32, int *inexact,

@@ -215,6 +215,17 @@ hipError_t launch_select_clear(const SelectWork &w, hipStream_t stream);
 hipError_t launch_select_keys(int dtype, const SelectWork &w, const ProblemDesc *probs, const PoseState *poses, hipStream_t stream);
 hipError_t launch_select_keys_values(const SelectWork &w, const double *values, hipStream_t stream);
 hipError_t launch_select(const SelectWork &w, hipStream_t stream);
+// ea_pose_stats_kernel + ea_pose_stats_fold_kernel: w.nseg segments (begin = first partial row, pose_stats_rows(n) of them),
+// w.max_n the longest; one PoseStatsRow per segment into w.out
+struct PoseStatsWork {
+  int nseg = 0, max_n = 0;
+  int margin = 0;
+  double inlier_residual = 0.0;
+  const SelectSeg *segs = nullptr;
+  PoseStatsPartial *partials = nullptr;
+  PoseStatsRow *out = nullptr;
+};
+hipError_t launch_pose_stats(int dtype, const PoseStatsWork &w, const ProblemDesc *probs, const PoseState *poses, hipStream_t stream);
 hipError_t launch_selftest_reduce(const float *in, float *a, float *b, float *c, float *d, double *o32, double *o64,
                                   hipStream_t stream);
 // ea_kernels_var.hip (the same file under -DEA_TU_VARIANT): what launch_eval_fused (tag 0) / launch_eval_poses_grid (tag 1) hand on

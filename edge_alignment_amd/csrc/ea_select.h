@@ -32,6 +32,19 @@ struct SelectSeg {
   int32_t term;
 };
 
+// ea_batch_pose_stats (ea_pose_stats_kernel) walks the same segments, `begin` being the segment's first partial row: one row
+// per workgroup of kPoseStatsThreads points, folded in index order into one PoseStatsRow (= ea_pose_stats) per segment
+constexpr int kPoseStatsThreads = 256;
+struct PoseStatsPartial {
+  int32_t n_invalid, n_visible, n_inlier, n_flow;
+  double sum_flow, pad_;
+};
+struct PoseStatsRow {
+  int64_t n, n_invalid, n_visible, n_inlier, n_flow;
+  double sum_flow;
+};
+EA_HD inline int64_t pose_stats_rows(int64_t n) { return (n + kPoseStatsThreads - 1) / kPoseStatsThreads; }
+
 EA_HD inline uint64_t select_bits(double v) { uint64_t u; memcpy(&u, &v, sizeof u); return u; }
 EA_HD inline double select_value(uint64_t key) { double v; memcpy(&v, &key, sizeof v); return v; }
 // key of the residual of a block whose functor succeeded: the bits of |r|

@@ -297,6 +297,36 @@ int ea_problem_pixel_cost(ea_problem *p, const double q[4], const double t[3], e
 int ea_problem_residual_quantiles(ea_problem *p, const double q[4], const double t[3], const double *probs, int nq,
                                   double *values /* nq */, int64_t *n_valid);
 
+/* How much of a reference is still seen at a pose -- what a keyframe rule asks after every solve -- counted on the device
+ * without a per-point copy.  The statistics cover p's OWN residual family (its terms are not included, as for the quantiles);
+ * per-point weights, the loss and priors do not enter.
+ *   Projection: (u, v) and validity are the evaluation kernels' own -- the plain functor's for plain and weighted problems,
+ *     the variant functor's for distortion / second-camera problems -- with the flavour knobs z_guard, z_eps and
+ *     rot_transposed applied, in the problem's dtype.
+ *   Visible: a valid point (functor returned true) whose divisor b_z + z_eps is > 0 and for which
+ *     margin <= floor(u) <= W - 2 - margin and margin <= floor(v) <= H - 2 - margin (the unsaturated floor: a point far
+ *     outside, or with NaN coordinates, is simply not visible).
+ *   Inlier: visible and |r| <= inlier_residual, r the raw bicubic value the cost kernel and the quantiles' key pass sample.
+ *   Flow: (u0, v0) is the same projection at the identity pose q = (1, 0, 0, 0), t = 0 (a rig: T12 I T12^-1).  A visible
+ *     point counts in n_flow when its identity projection is valid with a positive divisor; its term is
+ *     sqrt((u - u0)^2 + (v - v0)^2), formed and summed in fp64 from the dtype-typed coordinates.
+ *   Determinism: the counts are exact; sum_flow has the same bits on every run, whichever batch the problem is in and
+ *     whatever sits beside it: a problem's points are cut into fixed workgroup partials (256 points each, a fixed butterfly
+ *     inside), folded in index order by a second launch.  No floating-point atomics.
+ * Errors, before anything touches a device: NULL argument, margin < 0, inlier_residual negative or NaN (+Inf is allowed):
+ * EA_ERR_INVALID_ARG.  A problem without points or DT image: EA_ERR_STATE, as ea_eval.  Two launches and one synchronisation
+ * on the batch's stream serve a whole batch.  Resident poses (ea_batch_set_poses) survive the call. */
+typedef struct {
+  int64_t n;          /* points of the problem's own residual family */
+  int64_t n_invalid;  /* functor returned false at the pose (the rule ea_eval's n_invalid counts) */
+  int64_t n_visible;  /* valid, positive depth, inside the image by `margin` */
+  int64_t n_inlier;   /* visible and |r| <= inlier_residual */
+  int64_t n_flow;     /* visible and also visible-by-depth at the identity pose */
+  double  sum_flow;   /* sum over the n_flow points of the pixel distance between the two projections */
+} ea_pose_stats;
+int ea_problem_pose_stats(ea_problem *p, const double q[4], const double t[3], int margin, double inlier_residual,
+                          ea_pose_stats *out);
+
 /* ceres::Solve(options, &problem, &summary) (standalone_edge_align.cpp:286; SolveEA.cpp:198).
  * q,t in/out.  The whole trust-region loop runs on the device. */
 int ea_solve(ea_problem *p, const ea_options *opt, double q[4], double t[3], ea_summary *summary);
@@ -390,6 +420,9 @@ int ea_batch_solve(ea_batch *b, const ea_options *opt, double *q, double *t,
  * launch sequence, one synchronisation; a problem without points gives NaN and 0) */
 int ea_batch_residual_quantiles(ea_batch *b, const double *q, const double *t, const double *probs, int nq,
                                 double *values, int64_t *n_valid);
+/* q: count x 4, t: count x 3; out: count (ea_problem_pose_stats per problem, bit for bit; two launches, one synchronisation;
+ * a problem without points gives zeros, as the batched quantiles give NaN and 0) */
+int ea_batch_pose_stats(ea_batch *b, const double *q, const double *t, int margin, double inlier_residual, ea_pose_stats *out);
 
 /* K evaluations of every problem of the batch at K DIFFERENT poses, one call -- what a caller that runs its own optimiser,
  * a line search, multi-start or a cost-surface probe asks of the evaluator: ceres::Problem::Evaluate once per pose (the
@@ -952,6 +985,55 @@ int ea_tracker_batch_create_pyramid(ea_tracker_batch **out, const ea_camera *cam
                                     int halvings);
 ea_problem *ea_tracker_batch_level_problem(ea_tracker_batch *tb, int level, int i);
 int ea_tracker_batch_last_summaries(ea_tracker_batch *tb, int i, ea_summary *out /* levels entries */);
+
+/* Keyframe mode of the multi-stream tracker: a stream's reference is HELD while enough of it is still seen, instead of being
+ * replaced by every pushed frame.  Off by default: a tracker on which it is never switched on runs the frame-to-frame push.
+ *   set_keyframes(p): accepted only while no stream holds a reference (before the first push, or after
+ *     ea_tracker_batch_reset(-1)), else EA_ERR_STATE; EA_ERR_STATE with levels > 1 (keyframes across pyramid levels are out
+ *     of scope); a NaN field, margin < 0 or inlier_residual < 0: EA_ERR_INVALID_ARG; p == NULL: back to frame-to-frame.  All three flavours,
+ *     halvings included, host and device frames.
+ *   Current side: unchanged -- every pushed frame passes the edge detection once and its transform lands in every stream's
+ *     image.
+ *   Alignment: a stream is aligned by the frame-to-frame rule and solved from its stored pose, which is the pose of the
+ *     KEYFRAME in the previous frame's coordinates (zero-velocity start); the motion prior is centred there, the covariance is
+ *     taken as before.
+ *   Statistics: after the solves, ea_batch_pose_stats at the returned poses on the (sub-)batches that solved, one call per
+ *     solved group, for the streams whose solve did not end in EA_FAILURE, before anything overwrites points.
+ *   Decision (csrc/ea_keyframe.h, keyframe_decide): the comparisons written beside ea_keyframe_params' fields, each with one
+ *     IEEE multiplication; a stream that was not aligned: EA_KEY_FIRST; a failed solve: EA_KEY_SOLVE_FAILED; several bits may
+ *     be set.
+ *   A replaced stream takes the pushed frame's edge points as its reference (scatter, depth weights), age = 0,
+ *     keyframe_push = get_info("frames"), and its stored pose becomes the identity.  A kept stream's point, weight and
+ *     point-order arrays are not touched; age += 1 and its stored pose becomes the solved pose.  When no stream replaces, no
+ *     scatter and no depth-weight launch is issued.
+ *   q_rel / t_rel of an aligned stream: the pose solved in this push against the keyframe in use DURING this push, also when
+ *     the push then replaces it (callers chain poses themselves); a failed solve returns the pose it started from, an
+ *     unaligned stream the identity.
+ *   Flavour 2, a frame without any edge: the stream is not aligned, its image is left alone and it KEEPS the keyframe it has
+ *     (replaced = 0, age unchanged); if it holds none it stays without one.
+ *   A failure past the checks resets every stream; reset(i) also clears stream i's keyframe state.
+ *   get_info: "keyframes_taken" (streams that replaced in the last push), "keyframe_mode" (0 / 1).
+ * Out of scope: the single ea_tracker (a tracker batch of one stream is its keyframe form), pyramid levels, composing poses
+ * along the keyframe chain into a world pose, a constant-velocity start after a replacement.  The default
+ * min_visible_fraction of 0.75 is an untuned starting value. */
+typedef struct {
+  double min_visible_fraction;  /* replace when (double)n_visible < min_visible_fraction * (double)n;  <= 0: off */
+  double min_inlier_fraction;   /* replace when (double)n_inlier  < min_inlier_fraction  * (double)n;  <= 0: off */
+  double inlier_residual;       /* in the units of the stream's DT ([0,1] for flavours 0/1, [0,255] for flavour 2) */
+  double max_mean_flow;         /* replace when n_flow > 0 and sum_flow > max_mean_flow * (double)n_flow;  <= 0: off */
+  int max_frames;               /* replace when this many frames have been solved against the keyframe;   <= 0: off */
+  int margin;
+} ea_keyframe_params;
+enum { EA_KEY_FIRST = 1, EA_KEY_SOLVE_FAILED = 2, EA_KEY_VISIBLE = 4, EA_KEY_INLIERS = 8, EA_KEY_FLOW = 16, EA_KEY_AGE = 32 };
+typedef struct {
+  int64_t keyframe_push;  /* value of get_info("frames") at the push that delivered the keyframe now held; 0: none */
+  int age;                /* frames solved against it so far */
+  int replaced;           /* reason mask of the last push, 0 = the keyframe was kept */
+  ea_pose_stats stats;    /* at the pose the last push returned; zeros when the stream was not aligned or its solve failed */
+} ea_keyframe_state;
+void ea_default_keyframe_params(ea_keyframe_params *p);   /* min_visible_fraction 0.75, everything else off */
+int ea_tracker_batch_set_keyframes(ea_tracker_batch *tb, const ea_keyframe_params *p);
+int ea_tracker_batch_keyframe_state(ea_tracker_batch *tb, int i, ea_keyframe_state *out);
 
 /* the half-resolution step by itself, host in / host out: kind 0 = bgr8 (height x width x 3 bytes), 1 = float32 with
  * NaN -> 0 first, 2 = float32 as is; dst = (height / 2) x (width / 2); height and width even */
