@@ -24,6 +24,19 @@ void ea_cov_host_compute(const double A[36], double n_invalid, const double q[4]
   ea::cov_from_acc(acc, q, 1, co, out);
 }
 
+// the same with constant tangent coordinates (bit i of held = coordinate i of [delta | t]): the reduced system
+void ea_cov_host_compute_held(const double A[36], double n_invalid, const double q[4], const ea_covariance_options *o, int held,
+                              ea_covariance *out) {
+  double acc[ea::kAccSlots];
+  std::memset(acc, 0, sizeof(acc));
+  int k = 0;
+  for (int a = 0; a < 6; ++a)
+    for (int c = a; c < 6; ++c) acc[ea::kAccJtJ + k++] = A[6 * a + c];
+  acc[ea::kAccInvalid] = n_invalid;
+  const ea::CovOptions co = {o->algorithm, o->min_reciprocal_condition_number, o->null_space_rank};
+  ea::cov_from_acc(acc, q, 1, co, out, held);
+}
+
 // the facade's x (+) delta, for Jacobians by differences that do not trust the hand-written L
 void ea_cov_host_quat_plus(const double x[4], const double delta[3], double out[4]) {
   ceres::QuaternionParameterization().Plus(x, delta, out);

@@ -171,6 +171,12 @@ def test_degenerate_systems(hip, bundled_pair):
     with pytest.raises(hip.EAError) as ei:
         P0.covariance(q, t)
     assert ei.value.code == hip.EA_ERR_STATE
+    # the same problem as a member of a batch: its entry says "no points" (why 3), its neighbour's is computed
+    B = hip.Batch([P, P0])
+    cb = B.covariance(np.stack([q, q]), np.stack([t, t]))
+    assert cb[0]["ok"] and cb[0]["why"] == 0 and cb[0]["rank"] == 6
+    assert not cb[1]["ok"] and cb[1]["why"] == 3 and cb[1]["rank"] == 0
+    B.close()
     P.close(); P1.close(); P0.close()
 
 
