@@ -59,6 +59,8 @@ EXPORTED = [
     "ea_tracker_batch_create_pyramid", "ea_tracker_batch_level_problem", "ea_tracker_batch_last_summaries",
     "ea_problem_pose_stats", "ea_batch_pose_stats", "ea_default_keyframe_params", "ea_tracker_batch_set_keyframes",
     "ea_tracker_batch_keyframe_state",
+    "ea_pose_to_matrix", "ea_matrix_to_pose", "ea_problem_reproject", "ea_batch_reproject", "ea_batch_reproject_device",
+    "ea_problem_overlay", "ea_batch_overlay", "ea_batch_overlay_device",
 ]
 
 # measurement hooks (edge_alignment_amd/csrc/ea_hip_dev.h): bound by bench.py, the A/B scripts and the tests that pin the
@@ -159,6 +161,14 @@ KEY_FIRST, KEY_SOLVE_FAILED, KEY_VISIBLE, KEY_INLIERS, KEY_FLOW, KEY_AGE = 1, 2,
 
 class KeyframeState(C.Structure):
     _fields_ = [("keyframe_push", C.c_int64), ("age", C.c_int), ("replaced", C.c_int), ("stats", PoseStats)]
+
+
+class OverlayStats(C.Structure):
+    _fields_ = [("n", C.c_int64), ("inside", C.c_int64), ("outside", C.c_int64)]
+
+
+def overlay_stats_to_dict(s):
+    return {k: getattr(s, k) for k, _ in OverlayStats._fields_}
 
 
 def pose_stats_to_dict(s):
@@ -342,6 +352,15 @@ def load():
     L.ea_default_keyframe_params.restype = None
     L.ea_tracker_batch_set_keyframes.argtypes = [vp, C.POINTER(KeyframeParams)]
     L.ea_tracker_batch_keyframe_state.argtypes = [vp, C.c_int, C.POINTER(KeyframeState)]
+    u8p, ovp = C.POINTER(C.c_uint8), C.POINTER(OverlayStats)
+    L.ea_pose_to_matrix.argtypes = [dp, dp, dp]
+    L.ea_matrix_to_pose.argtypes = [dp, dp, dp]
+    L.ea_problem_reproject.argtypes = [vp, dp, dp, C.c_int64]
+    L.ea_batch_reproject.argtypes = [vp, dp, dp, C.c_int64]
+    L.ea_batch_reproject_device.argtypes = [vp, dp, vp, C.c_int64]
+    L.ea_problem_overlay.argtypes = [vp, dp, vp, C.c_int, C.c_int, u8p, vp, ovp]
+    L.ea_batch_overlay.argtypes = [vp, dp, C.POINTER(vp), C.c_int, C.c_int, u8p, C.POINTER(vp), ovp]
+    L.ea_batch_overlay_device.argtypes = [vp, dp, C.POINTER(vp), C.c_int, C.c_int, u8p, ovp]
     _lib = L
     return L
 
@@ -357,6 +376,41 @@ def _dp(a):
 
 def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def pose_to_matrix(q, t):
+    """ea_pose_to_matrix: b_T_a (4, 4) of q = (w, x, y, z) as given (not normalised) and t"""
+    q, t, m = _f64(q).reshape(4), _f64(t).reshape(3), np.zeros((4, 4))
+    _check(load().ea_pose_to_matrix(_dp(q), _dp(t), _dp(m)))
+    return m
+
+
+def matrix_to_pose(b_T_a):
+    """ea_matrix_to_pose: (q, t) of a 4x4 b_T_a"""
+    m, q, t = _f64(b_T_a).reshape(16), np.zeros(4), np.zeros(3)
+    _check(load().ea_matrix_to_pose(_dp(m), _dp(q), _dp(t)))
+    return q, t
+
+
+def _pose_matrix(M):
+    """a pose as the library's reprojection calls take it: a 4x4 matrix, or a (q, t) tuple converted with pose_to_matrix"""
+    if isinstance(M, tuple) and len(M) == 2:
+        return pose_to_matrix(*M)
+    return _f64(M).reshape(4, 4)
+
+
+def _pose_matrices(M, n):
+    """n poses: an array (n, 4, 4), or a sequence of n entries each a matrix or a (q, t) tuple"""
+    if isinstance(M, np.ndarray):
+        return _f64(M).reshape(n, 4, 4)
+    return _f64(np.stack([_pose_matrix(m) for m in M]) if n else np.zeros((0, 4, 4))).reshape(n, 4, 4)
+
+
+def _color(color):
+    if color is None:
+        return None
+    c = np.ascontiguousarray(color, dtype=np.uint8).reshape(3)
+    return c.ctypes.data_as(C.POINTER(C.c_uint8)), c
 
 
 def device_count():
@@ -741,6 +795,30 @@ class Problem:
         s = PoseStats()
         _check(load().ea_problem_pose_stats(self._h, _dp(q), _dp(t), int(margin), float(inlier_residual), C.byref(s)))
         return pose_stats_to_dict(s)
+
+    def reproject(self, M):
+        """ea_problem_reproject: (u, v) [n, 2] of the problem's own points, in the caller's order, at b_T_a = M (4x4, or a
+        (q, t) tuple)"""
+        M = _pose_matrix(M)
+        n = self.num_points
+        uv = np.zeros((max(n, 1), 2))
+        _check(load().ea_problem_reproject(self._h, _dp(M), _dp(uv), n))
+        return uv[:n]
+
+    def overlay(self, M, image, color=None, out=None):
+        """ea_problem_overlay: (painted copy of the uint8 H x W x 3 image, stats dict); out=image paints in place"""
+        M = _pose_matrix(M)
+        if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3 or not image.flags.c_contiguous:
+            raise ValueError("image must be a contiguous uint8 array (H, W, 3)")
+        if out is None:
+            out = np.empty_like(image)
+        elif out.dtype != np.uint8 or out.shape != image.shape or not out.flags.c_contiguous:
+            raise ValueError("out must be a contiguous uint8 array of the image's shape")
+        col = _color(color)
+        st = OverlayStats()
+        _check(load().ea_problem_overlay(self._h, _dp(M), image.ctypes.data_as(C.c_void_p), image.shape[0], image.shape[1],
+                                         col[0] if col else None, out.ctypes.data_as(C.c_void_p), C.byref(st)))
+        return out, overlay_stats_to_dict(st)
 
     def set_flavour(self, z_guard=0.01, z_eps=0.0, rot_transposed=False):
         _check(load().ea_problem_set_flavour(self._h, z_guard, z_eps, int(rot_transposed)))
@@ -1342,6 +1420,80 @@ class Batch:
         out = (PoseStats * max(len(self), 1))()
         _check(load().ea_batch_pose_stats(self._h, _dp(q), _dp(t), int(margin), float(inlier_residual), out))
         return [pose_stats_to_dict(out[i]) for i in range(len(self))]
+
+    def reproject(self, M, out=None):
+        """ea_batch_reproject at the poses M (n matrices, or (q, t) tuples): (u, v) [rows, 2] in the layout of row_offsets(),
+        the head families' rows in storage order (rows of terms are left as they are in `out`, zero in a fresh array)"""
+        M = _pose_matrices(M, len(self))
+        uv = np.zeros((int(self.row_offsets()[-1]), 2)) if out is None else out
+        if uv.dtype != np.float64 or not uv.flags.c_contiguous or uv.ndim != 2 or uv.shape[1] != 2:
+            raise ValueError("out must be a contiguous float64 array (rows, 2)")
+        _check(load().ea_batch_reproject(self._h, _dp(M), _dp(uv), uv.shape[0]))
+        return uv
+
+    def reproject_device(self, M, uv, capacity_rows=None):
+        """ea_batch_reproject_device into a float64 torch tensor (rows, 2) on the batch's GPU, or a raw device address (then
+        capacity_rows is required)"""
+        M = _pose_matrices(M, len(self))
+        if hasattr(uv, "data_ptr"):
+            import torch
+            if not uv.is_cuda or uv.dtype != torch.float64 or not uv.is_contiguous():
+                raise ValueError("uv must be a contiguous float64 tensor on the batch's GPU")
+            rows = uv.numel() // 2
+            capacity_rows = rows if capacity_rows is None else min(int(capacity_rows), rows)
+            torch.cuda.current_stream(uv.device).synchronize()   # the tensor's producers are done before the library writes
+            uv = uv.data_ptr()
+        if capacity_rows is None:
+            raise ValueError("capacity_rows is required with a raw address")
+        _check(load().ea_batch_reproject_device(self._h, _dp(M), C.c_void_p(uv), int(capacity_rows)))
+
+    def overlay(self, M, images, color=None, in_place=False):
+        """ea_batch_overlay: images = n uint8 (H, W, 3) arrays of one extent; returns (painted copies -- the arrays
+        themselves with in_place --, list of stats dicts)"""
+        M = _pose_matrices(M, len(self))
+        n = len(self)
+        if len(images) != n:
+            raise ValueError("one image per problem")
+        for im in images:
+            if im.dtype != np.uint8 or im.shape != images[0].shape or im.ndim != 3 or im.shape[2] != 3 or not im.flags.c_contiguous:
+                raise ValueError("images must be contiguous uint8 arrays (H, W, 3) of one extent")
+        outs = list(images) if in_place else [np.empty_like(im) for im in images]
+        src = (C.c_void_p * max(n, 1))(*[im.ctypes.data for im in images])
+        dst = (C.c_void_p * max(n, 1))(*[im.ctypes.data for im in outs])
+        col = _color(color)
+        st = (OverlayStats * max(n, 1))()
+        h, w = (images[0].shape[0], images[0].shape[1]) if n else (1, 1)
+        _check(load().ea_batch_overlay(self._h, _dp(M), src, h, w, col[0] if col else None, dst, st))
+        return outs, [overlay_stats_to_dict(st[i]) for i in range(n)]
+
+    def overlay_device(self, M, images, color=None, height=None, width=None):
+        """ea_batch_overlay_device: images = n uint8 torch tensors (H, W, 3) on the batch's GPU (or raw device addresses with
+        height, width), painted in place; returns the list of stats dicts"""
+        M = _pose_matrices(M, len(self))
+        n = len(self)
+        if len(images) != n:
+            raise ValueError("one image per problem")
+        ptrs = []
+        for im in images:
+            if hasattr(im, "data_ptr"):
+                import torch
+                if not im.is_cuda or im.dtype != torch.uint8 or not im.is_contiguous() or im.dim() != 3 or im.shape[2] != 3:
+                    raise ValueError("images must be contiguous uint8 tensors (H, W, 3) on the batch's GPU")
+                if height is None:
+                    height, width = int(im.shape[0]), int(im.shape[1])
+                if (int(im.shape[0]), int(im.shape[1])) != (height, width):
+                    raise ValueError("images must share one extent")
+                torch.cuda.current_stream(im.device).synchronize()   # the images are complete before the library paints
+                ptrs.append(im.data_ptr())
+            else:
+                ptrs.append(int(im))
+        if height is None or width is None:
+            raise ValueError("height and width are required with raw addresses")
+        arr = (C.c_void_p * max(n, 1))(*ptrs)
+        col = _color(color)
+        st = (OverlayStats * max(n, 1))()
+        _check(load().ea_batch_overlay_device(self._h, _dp(M), arr, int(height), int(width), col[0] if col else None, st))
+        return [overlay_stats_to_dict(st[i]) for i in range(n)]
 
     def covariance(self, q, t, **opts):
         """ea_batch_covariance: one covariance per problem at q (n, 4), t (n, 3) -> list of covariance_to_dict"""

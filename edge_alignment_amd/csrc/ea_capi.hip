@@ -3590,6 +3590,244 @@ extern "C" int ea_eval_points(ea_problem *p, const double q[4], const double t[3
   return EA_OK;
 }
 
+// ---- reprojection and overlay: reproject + s_overlay (ea_reproject.h; kernel: ea_reproject_kernel) -----------------------
+//
+// One segment per problem of the call (its head family) with the 3x4 matrix of step A, built here; segments and zeroed
+// counters go up in ONE copy from a pinned block, ONE launch, the counters (overlay) come back into the same block, ONE
+// synchronisation: all on the batch's stream.  The matrices travel in the segments: d_poses is not written, and no problem
+// changes, so resident poses (ea_batch_set_poses) survive.
+extern "C" int ea_pose_to_matrix(const double q[4], const double t[3], double b_T_a[16]) {
+  if (!q || !t || !b_T_a) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  pose_to_matrix(q, t, b_T_a);
+  return EA_OK;
+}
+
+extern "C" int ea_matrix_to_pose(const double b_T_a[16], double q[4], double t[3]) {
+  if (!b_T_a || !q || !t) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (!matrix_to_pose(b_T_a, q, t)) return fail(EA_ERR_INVALID_ARG, "b_T_a[15] must be 1 (the reference's assert( T(3,3) == 1 ))");
+  return EA_OK;
+}
+
+namespace {
+struct ReprojectRun {
+  unsigned char *pinned = nullptr;
+  DevBuf dev;
+  int nseg = 0;
+  size_t o_counts = 0;
+  ~ReprojectRun() { cached_host_free(pinned); }
+  const ReprojectSeg *segs() const { return reinterpret_cast<const ReprojectSeg *>(pinned); }
+  const unsigned long long *counts() const { return reinterpret_cast<const unsigned long long *>(pinned + o_counts); }
+};
+}  // namespace
+
+static int check_reproject_poses(const double *b_T_a, int count) {
+  for (int i = 0; i < count; ++i)
+    if (!reproject_pose_ok(b_T_a + 16 * (size_t)i))
+      return fail(EA_ERR_INVALID_ARG, "b_T_a must be finite with the last row exactly 0 0 0 1");
+  return EA_OK;
+}
+
+// upload + launch (+ the counters on their way back) for a batch that is built; the caller queues what else must come down
+// and synchronises.  paint: images[i] = device image of problem i (H x W x 3)
+static int reproject_enqueue(ea_batch *b, const double *b_T_a, bool paint, double *uv_dev, unsigned char *const *images,
+                             const uint8_t color[3], ReprojectRun &run) {
+  const int nseg = (int)b->probs.size();
+  if (nseg > 65535) return fail(EA_ERR_INVALID_ARG, "more than 65535 problems in one reprojection call");
+  const ProblemDesc *hd = reinterpret_cast<const ProblemDesc *>(b->h_desc);  // (batch_build's staging block)
+  const GroupDesc *hg = reinterpret_cast<const GroupDesc *>(b->h_desc + (size_t)b->nterms * sizeof(ProblemDesc));
+  run.nseg = nseg;
+  run.o_counts = align16((size_t)nseg * sizeof(ReprojectSeg));
+  const size_t bytes = run.o_counts + (size_t)nseg * 2 * sizeof(unsigned long long);
+  HIPCHK(cached_host_malloc(reinterpret_cast<void **>(&run.pinned), bytes, hipHostMallocDefault, b->device));
+  std::memset(run.pinned, 0, bytes);
+  ReprojectSeg *h_segs = reinterpret_cast<ReprojectSeg *>(run.pinned);
+  int max_n = 0;
+  for (int j = 0; j < nseg; ++j) {
+    const ea_problem *p = b->probs[(size_t)j];
+    const int term = hg[j].term_begin;  // the head family; its terms are not included
+    ReprojectSeg &sg = h_segs[j];
+    sg.row = hd[term].row_begin; sg.n = hd[term].n; sg.term = term;
+    const bool rig = (p->variant & 2) != 0;
+    reproject_matrix(b_T_a + 16 * (size_t)j, rig ? p->T12 : nullptr, rig ? p->T12inv : nullptr, sg.M);
+    sg.image = paint ? images[j] : nullptr;
+    max_n = std::max(max_n, (int)sg.n);
+  }
+  HIPCHK(cached_malloc(&run.dev.p, bytes, b->device));
+  unsigned char *d = run.dev.as<unsigned char>();
+  HIPCHK(hipMemcpyAsync(d, run.pinned, bytes, hipMemcpyHostToDevice, b->stream));
+  ReprojectWork w;
+  w.nseg = nseg; w.max_n = max_n; w.paint = paint ? 1 : 0;
+  w.color = color ? ((unsigned)color[0] | ((unsigned)color[1] << 8) | ((unsigned)color[2] << 16)) : (255u << 16);  // NULL: upstream's red
+  w.segs = reinterpret_cast<const ReprojectSeg *>(d);
+  w.uv = uv_dev;
+  w.counts = reinterpret_cast<unsigned long long *>(d + run.o_counts);
+  HIPCHK(launch_reproject(b->dtype, w, b->d_probs, b->stream));
+  if (paint)
+    HIPCHK(hipMemcpyAsync(run.pinned + run.o_counts, d + run.o_counts, bytes - run.o_counts, hipMemcpyDeviceToHost, b->stream));
+  return EA_OK;
+}
+
+static void reproject_stats(const ReprojectRun &run, ea_overlay_stats *stats) {
+  if (!stats) return;
+  for (int j = 0; j < run.nseg; ++j) {
+    stats[j].n = run.segs()[j].n;
+    stats[j].inside = (int64_t)run.counts()[2 * j];
+    stats[j].outside = (int64_t)run.counts()[2 * j + 1];
+  }
+}
+
+// rows of the batch's layout (ea_batch_row_offsets) as the problems stand, without a device
+static int64_t batch_rows_host(const ea_batch *b) {
+  int64_t rows = 0;
+  for (const ea_problem *p : b->probs) rows += problem_points(p);
+  return rows;
+}
+
+static int batch_reproject_checks(ea_batch *b, const double *b_T_a, const void *uv, int64_t capacity_rows) {
+  if (!b || !b_T_a || !uv) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  int rc = check_reproject_poses(b_T_a, (int)b->probs.size());
+  if (rc != EA_OK) return rc;
+  if (capacity_rows < batch_rows_host(b)) return fail(EA_ERR_INVALID_ARG, "capacity_rows is smaller than the batch's row count (ea_batch_row_offsets)");
+  return require_device();
+}
+
+extern "C" int ea_batch_reproject_device(ea_batch *b, const double *b_T_a, double *uv_dev, int64_t capacity_rows) {
+  int rc = batch_reproject_checks(b, b_T_a, uv_dev, capacity_rows);
+  if (rc != EA_OK) return rc;
+  if ((rc = batch_build(b)) != EA_OK) return rc;
+  if ((rc = check_device_pointer(b, uv_dev, "uv_dev")) != EA_OK) return rc;
+  ReprojectRun run;
+  if ((rc = reproject_enqueue(b, b_T_a, false, uv_dev, nullptr, nullptr, run)) != EA_OK) return rc;
+  HIPCHK(hipStreamSynchronize(b->stream));  // the rows are complete (and visible to any other stream) when this returns
+  return EA_OK;
+}
+
+extern "C" int ea_batch_reproject(ea_batch *b, const double *b_T_a, double *uv, int64_t capacity_rows) {
+  int rc = batch_reproject_checks(b, b_T_a, uv, capacity_rows);
+  if (rc != EA_OK) return rc;
+  if ((rc = batch_build(b)) != EA_OK) return rc;
+  DevBuf rows;
+  HIPCHK(cached_malloc(&rows.p, (size_t)b->total_rows * 2 * sizeof(double), b->device));
+  ReprojectRun run;
+  if ((rc = reproject_enqueue(b, b_T_a, false, rows.as<double>(), nullptr, nullptr, run)) != EA_OK) return rc;
+  // the head families' rows come down, adjacent ones in one copy; rows of terms stay as the caller left them
+  for (int j = 0; j < run.nseg;) {
+    const int64_t begin = run.segs()[j].row;
+    int64_t end = begin + run.segs()[j].n;
+    for (++j; j < run.nseg && run.segs()[j].row == end; ++j) end += run.segs()[j].n;
+    if (end > begin)
+      HIPCHK(hipMemcpyAsync(uv + 2 * begin, rows.as<double>() + 2 * begin, (size_t)(end - begin) * 2 * sizeof(double),
+                            hipMemcpyDeviceToHost, b->stream));
+  }
+  HIPCHK(hipStreamSynchronize(b->stream));
+  return EA_OK;
+}
+
+extern "C" int ea_problem_reproject(ea_problem *p, const double b_T_a[16], double *uv, int64_t capacity) {
+  if (!p || !b_T_a || !uv) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  int rc = check_reproject_poses(b_T_a, 1);
+  if (rc != EA_OK) return rc;
+  if (capacity < p->n) return fail(EA_ERR_INVALID_ARG, "capacity is smaller than ea_problem_num_points");
+  if ((rc = require_device()) != EA_OK) return rc;
+  ea_batch *b;
+  if ((rc = self_batch(p, &b)) != EA_OK) return rc;
+  if ((rc = batch_build(b)) != EA_OK) return rc;  // (no DT image: EA_ERR_STATE, as ea_eval)
+  if (p->n == 0) return fail(EA_ERR_STATE, "no edge points (ea_problem_set_points)");
+  DevBuf rows;
+  HIPCHK(cached_malloc(&rows.p, (size_t)p->n * 2 * sizeof(double), p->device));  // (the head family's rows start at 0)
+  ReprojectRun run;
+  if ((rc = reproject_enqueue(b, b_T_a, false, rows.as<double>(), nullptr, nullptr, run)) != EA_OK) return rc;
+  std::vector<double> tmp(p->order.empty() ? 0 : (size_t)p->n * 2);
+  double *dst = p->order.empty() ? uv : tmp.data();
+  HIPCHK(hipMemcpyAsync(dst, rows.p, (size_t)p->n * 2 * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  for (size_t i = 0; i < tmp.size() / 2; ++i) {  // stored in tile order: hand the rows back in the caller's order
+    uv[2 * (size_t)p->order[i]] = tmp[2 * i];
+    uv[2 * (size_t)p->order[i] + 1] = tmp[2 * i + 1];
+  }
+  return EA_OK;
+}
+
+// what the three overlay forms check before a device is looked for; entries: the pointer arrays whose `count` entries must
+// not be NULL
+static int batch_overlay_checks(ea_batch *b, const double *b_T_a, const void *const *entries_a, const void *const *entries_b,
+                                int height, int width) {
+  if (!b || !b_T_a || !entries_a || !entries_b) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (height < 1 || width < 1) return fail(EA_ERR_INVALID_ARG, "height and width must be positive");
+  int rc = check_reproject_poses(b_T_a, (int)b->probs.size());
+  if (rc != EA_OK) return rc;
+  for (size_t i = 0; i < b->probs.size(); ++i)
+    if (!entries_a[i] || !entries_b[i]) return fail(EA_ERR_INVALID_ARG, "NULL entry in an image pointer array");
+  return require_device();
+}
+
+static int batch_overlay_extent(const ea_batch *b, int height, int width) {
+  for (const ea_problem *p : b->probs)
+    if (p->H != height || p->W != width)
+      return fail(EA_ERR_INVALID_ARG, "height, width must equal the extent of every problem's distance-transform image");
+  return EA_OK;
+}
+
+extern "C" int ea_batch_overlay_device(ea_batch *b, const double *b_T_a, uint8_t *const *bgr_dev, int height, int width,
+                                       const uint8_t color[3], ea_overlay_stats *stats) {
+  int rc = batch_overlay_checks(b, b_T_a, reinterpret_cast<const void *const *>(bgr_dev),
+                                reinterpret_cast<const void *const *>(bgr_dev), height, width);
+  if (rc != EA_OK) return rc;
+  if ((rc = batch_build(b)) != EA_OK) return rc;
+  if ((rc = batch_overlay_extent(b, height, width)) != EA_OK) return rc;
+  for (size_t i = 0; i < b->probs.size(); ++i) {
+    hipPointerAttribute_t at;
+    const hipError_t e = hipPointerGetAttributes(&at, bgr_dev[i]);
+    if (e != hipSuccess) (void)hipGetLastError();
+    if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.device != b->device)
+      return fail(EA_ERR_INVALID_ARG, "an entry of bgr_dev is not device memory of the batch's device");
+  }
+  ReprojectRun run;
+  if ((rc = reproject_enqueue(b, b_T_a, true, nullptr, bgr_dev, color, run)) != EA_OK) return rc;
+  HIPCHK(hipStreamSynchronize(b->stream));  // the images are complete (and visible to any other stream) when this returns
+  reproject_stats(run, stats);
+  return EA_OK;
+}
+
+extern "C" int ea_batch_overlay(ea_batch *b, const double *b_T_a, const uint8_t *const *bgr_in, int height, int width,
+                                const uint8_t color[3], uint8_t *const *bgr_out, ea_overlay_stats *stats) {
+  int rc = batch_overlay_checks(b, b_T_a, reinterpret_cast<const void *const *>(bgr_in),
+                                reinterpret_cast<const void *const *>(bgr_out), height, width);
+  if (rc != EA_OK) return rc;
+  if ((rc = batch_build(b)) != EA_OK) return rc;
+  if ((rc = batch_overlay_extent(b, height, width)) != EA_OK) return rc;
+  // the images go up into one cached device block, are painted there and come back
+  const size_t count = b->probs.size(), image_bytes = (size_t)height * (size_t)width * 3, stride = align16(image_bytes);
+  DevBuf images;
+  HIPCHK(cached_malloc(&images.p, count * stride, b->device));
+  std::vector<unsigned char *> d_images(count);
+  for (size_t i = 0; i < count; ++i) {
+    d_images[i] = images.as<unsigned char>() + i * stride;
+    HIPCHK(hipMemcpyAsync(d_images[i], bgr_in[i], image_bytes, hipMemcpyHostToDevice, b->stream));
+  }
+  ReprojectRun run;
+  if ((rc = reproject_enqueue(b, b_T_a, true, nullptr, d_images.data(), color, run)) != EA_OK) return rc;
+  for (size_t i = 0; i < count; ++i)
+    HIPCHK(hipMemcpyAsync(bgr_out[i], d_images[i], image_bytes, hipMemcpyDeviceToHost, b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  reproject_stats(run, stats);
+  return EA_OK;
+}
+
+extern "C" int ea_problem_overlay(ea_problem *p, const double b_T_a[16], const uint8_t *bgr_in, int height, int width,
+                                  const uint8_t color[3], uint8_t *bgr_out, ea_overlay_stats *stats) {
+  if (!p || !b_T_a || !bgr_in || !bgr_out) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (height < 1 || width < 1) return fail(EA_ERR_INVALID_ARG, "height and width must be positive");
+  int rc = check_reproject_poses(b_T_a, 1);
+  if (rc == EA_OK) rc = require_device();
+  if (rc != EA_OK) return rc;
+  ea_batch *b;
+  if ((rc = self_batch(p, &b)) != EA_OK) return rc;
+  if ((rc = batch_build(b)) != EA_OK) return rc;  // (no DT image: EA_ERR_STATE, as ea_eval)
+  if (p->n == 0) return fail(EA_ERR_STATE, "no edge points (ea_problem_set_points)");
+  return ea_batch_overlay(b, b_T_a, &bgr_in, height, width, color, &bgr_out, stats);
+}
+
 extern "C" int ea_solve(ea_problem *p, const ea_options *opt, double q[4], double t[3], ea_summary *summary) {
   ea_batch *b;
   int rc = self_batch(p, &b);

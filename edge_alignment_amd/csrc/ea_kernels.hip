@@ -45,6 +45,7 @@ extern __device__ int g_lm_probe_row;
 #include "ea_lm.h"
 #include "ea_pair_log.h"
 #include "ea_prior.h"
+#include "ea_reproject.h"
 #include "ea_select.h"
 #include "ea_types.h"
 #include "ea_wave_exchange.h"
@@ -3373,6 +3374,86 @@ __global__ __launch_bounds__(64) void ea_pose_stats_fold_kernel(const SelectSeg 
   }
   if (lane == 0) out[blockIdx.x] = PoseStatsRow{(int64_t)sg.n, (int64_t)c0, (int64_t)c1, (int64_t)c2, (int64_t)c3, sum};
 }
+
+// ------------------------------------------------------------------------------------------------
+// The reference's qualitative self-check: reproject (standalone/utils.cpp:497-592, all four overloads) and s_overlay
+// (:594-608).  ea_hip.h states the arithmetic; like ea_pixel_cost_kernel it is fp64 from the stored points widened to double,
+// in the stated operation order, IEEE divisions, nothing contracted.
+//
+// Shaped like ea_pose_stats_kernel: one lane per point, blockIdx.y the segment (one per problem of the call), the segment's
+// 3x4 matrix -- built on the host, the rig product included -- and the descriptor uniform per workgroup.  No validity test:
+// bz == 0 and points behind the camera give what IEEE gives.
+//   PAINT = false: (u, v) leaves as one 16-byte store per lane at row sg.row + i, the storage order of the rows layout.
+//   PAINT = true:  pixel ((int)v, (int)u) of the segment's image takes the colour when the point is inside by
+//     ea_pixel_cost_kernel's rule, else it is counted outside.  Points that share a pixel store the same three bytes.  Counts:
+//     a ballot and a popcount per wavefront, the four wavefronts summed, ONE integer atomic pair per workgroup on the
+//     segment's two counters {inside, outside} (exact whatever the order of arrival).
+template <typename T, bool PAINT>
+__global__ __launch_bounds__(kReprojectThreads) void ea_reproject_kernel(const ProblemDesc *__restrict__ probs,
+                                                                         const ReprojectSeg *__restrict__ segs,
+                                                                         double *__restrict__ uv, unsigned int color,
+                                                                         unsigned long long *__restrict__ counts) {
+  __shared__ int s_cnt[kReprojectThreads / 64][2];
+  const ReprojectSeg &sg = segs[blockIdx.y];
+  const int n = sg.n;
+  const int first = blockIdx.x * kReprojectThreads;
+  if (first >= n) return;  // (uniform)
+  const ProblemDesc &pd = probs[sg.term];
+  const int tid = threadIdx.x, i = first + tid;
+  bool inside = false, outside = false;
+  if (i < n) {
+    const double x = (double)static_cast<const T *>(pd.x)[i], y = (double)static_cast<const T *>(pd.y)[i],
+                 z = (double)static_cast<const T *>(pd.z)[i];
+    const double *M = sg.M;
+    double u, v;
+    {
+#pragma clang fp contract(off)
+      const double bx = ((M[0] * x + M[1] * y) + M[2] * z) + M[3];
+      const double by = ((M[4] * x + M[5] * y) + M[6] * z) + M[7];
+      const double bz = ((M[8] * x + M[9] * y) + M[10] * z) + M[11];
+      double xd = bx / bz, yd = by / bz;
+      if (pd.variant & 1) {  // coefficients by name: k1, k2, p1, p2, k3 (ea_problem_set_distortion)
+        const double k1 = pd.dist[0], k2 = pd.dist[1], p1 = pd.dist[2], p2 = pd.dist[3], k3 = pd.dist[4];
+        const double xn = xd, yn = yd;
+        const double r2 = xn * xn + yn * yn, r4 = r2 * r2, r6 = r4 * r2;
+        const double rad = ((1.0 + k1 * r2) + k2 * r4) + k3 * r6;
+        xd = (xn * rad + ((2.0 * p1) * xn) * yn) + p2 * (r2 + (2.0 * xn) * xn);
+        yd = (yn * rad + ((2.0 * p2) * xn) * yn) + p1 * (r2 + (2.0 * yn) * yn);
+      }
+      u = pd.fx * xd + pd.cx;
+      v = pd.fy * yd + pd.cy;
+    }
+    if (!PAINT) {
+      typedef double D2 __attribute__((ext_vector_type(2)));
+      reinterpret_cast<D2 *>(uv)[sg.row + i] = D2{u, v};
+    } else {
+      const bool finite = (u == u) && (v == v) && fabs(u) < 1e9 && fabs(v) < 1e9;
+      const int iu = finite ? (int)u : -1, iv = finite ? (int)v : -1;  // `(int)`: truncation toward zero
+      inside = finite && iu >= 0 && iu < pd.W && iv >= 0 && iv < pd.H && !(u <= -1.0) && !(v <= -1.0);
+      outside = !inside;
+      unsigned char *img = sg.image;
+      if (inside && img) {
+        unsigned char *px = img + ((size_t)iv * (size_t)pd.W + (size_t)iu) * 3;
+        px[0] = (unsigned char)(color & 0xffu);
+        px[1] = (unsigned char)((color >> 8) & 0xffu);
+        px[2] = (unsigned char)((color >> 16) & 0xffu);
+      }
+    }
+  }
+  if (PAINT) {
+    const int lane = tid & 63, wave = tid >> 6;
+    const int c0 = __popcll(__builtin_amdgcn_ballot_w64(inside)), c1 = __popcll(__builtin_amdgcn_ballot_w64(outside));
+    if (lane == 0) { s_cnt[wave][0] = c0; s_cnt[wave][1] = c1; }
+    __syncthreads();
+    if (tid == 0) {
+      int nin = 0, nout = 0;
+#pragma unroll
+      for (int w = 0; w < kReprojectThreads / 64; ++w) { nin += s_cnt[w][0]; nout += s_cnt[w][1]; }
+      if (nin) atomicAdd(&counts[2 * blockIdx.y], (unsigned long long)nin);
+      if (nout) atomicAdd(&counts[2 * blockIdx.y + 1], (unsigned long long)nout);
+    }
+  }
+}
 #endif  // !EA_TU_VARIANT
 
 // ------------------------------------------------------------------------------------------------
@@ -3878,6 +3959,19 @@ hipError_t launch_pose_stats(int dtype, const PoseStatsWork &w, const ProblemDes
   }
   hipLaunchKernelGGL(ea_pose_stats_fold_kernel, dim3((unsigned)w.nseg), dim3(64), 0, stream, w.segs, w.partials, w.out);
   return hipGetLastError();
+}
+
+hipError_t launch_reproject(int dtype, const ReprojectWork &w, const ProblemDesc *probs, hipStream_t stream) {
+  if (w.nseg < 1 || w.nseg > 65535 || w.max_n < 0 || !w.segs || (w.paint ? !w.counts : !w.uv)) return hipErrorInvalidValue;
+  if (w.max_n == 0) return hipSuccess;
+  const dim3 grid((unsigned)((w.max_n + kReprojectThreads - 1) / kReprojectThreads), (unsigned)w.nseg);
+  return dispatch_dtype(dtype, [&](auto TT) {
+    return dispatch_bool(w.paint, [&](auto PAINT) {
+      hipLaunchKernelGGL((ea_reproject_kernel<typename decltype(TT)::type, decltype(PAINT)::value>), grid, dim3(kReprojectThreads), 0,
+                         stream, probs, w.segs, w.uv, w.color, w.counts);
+      return hipGetLastError();
+    });
+  });
 }
 
 hipError_t launch_grid_to_image(int dtype, const double *grid, int W, int H, void *dst, int pitch, float *dst32, int *inexact,

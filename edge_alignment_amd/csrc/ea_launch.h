@@ -11,6 +11,7 @@
 
 #include "../../include/ea_hip.h"
 #include "ea_lm.h"
+#include "ea_reproject.h"
 #include "ea_select.h"
 #include "ea_types.h"
 
@@ -226,6 +227,17 @@ struct PoseStatsWork {
   PoseStatsRow *out = nullptr;
 };
 hipError_t launch_pose_stats(int dtype, const PoseStatsWork &w, const ProblemDesc *probs, const PoseState *poses, hipStream_t stream);
+// ea_reproject_kernel (ea_reproject.h): w.nseg segments, w.max_n the longest.  paint == 0: (u, v) of point i of a segment
+// into uv[2 * (row + i)]; paint != 0: the segments' images painted with `color` (b | g << 8 | r << 16) and counts[2 * seg +
+// {0, 1}] += {inside, outside} (zero before the launch)
+struct ReprojectWork {
+  int nseg = 0, max_n = 0, paint = 0;
+  unsigned int color = 0;
+  const ReprojectSeg *segs = nullptr;
+  double *uv = nullptr;
+  unsigned long long *counts = nullptr;
+};
+hipError_t launch_reproject(int dtype, const ReprojectWork &w, const ProblemDesc *probs, hipStream_t stream);
 hipError_t launch_selftest_reduce(const float *in, float *a, float *b, float *c, float *d, double *o32, double *o64,
                                   hipStream_t stream);
 // ea_kernels_var.hip (the same file under -DEA_TU_VARIANT): what launch_eval_fused (tag 0) / launch_eval_poses_grid (tag 1) hand on

@@ -327,6 +327,85 @@ typedef struct {
 int ea_problem_pose_stats(ea_problem *p, const double q[4], const double t[3], int margin, double inlier_residual,
                           ea_pose_stats *out);
 
+/* ---- the reference's qualitative self-check: reproject (standalone/utils.cpp:497-592) + s_overlay (:594-608) ----------
+ * What every edge_align_test* runs before and after its solve: reproject(a_X, b_T_a, K, b_u); s_overlay(imB, b_u, "initial.png").
+ *
+ * Pose <-> matrix, host only (no device is looked for): PoseManipUtils::raw_to_eigenmat / eigenmat_to_raw, the convention of
+ * this header's first lines.  b_T_a is a row-major 4x4.
+ *   ea_pose_to_matrix: Eigen's Quaternion::toRotationMatrix arithmetic on q as given (NOT normalised): tx = 2x, ty = 2y,
+ *     tz = 2z; twx = tx w, twy = ty w, twz = tz w, txx = tx x, txy = ty x, txz = tz x, tyy = ty y, tyz = tz y, tzz = tz z;
+ *     R00 = 1 - (tyy + tzz), R01 = txy - twz, R02 = txz + twy, R10 = txy + twz, R11 = 1 - (txx + tzz), R12 = tyz - twx,
+ *     R20 = txz - twy, R21 = tyz + twx, R22 = 1 - (txx + tyy); column 3 = t; last row 0 0 0 1.
+ *   ea_matrix_to_pose: Eigen's quaternion from a matrix.  trace > 0: s = sqrt(trace + 1), w = s / 2, s = 0.5 / s,
+ *     x = (m21 - m12) s, y = (m02 - m20) s, z = (m10 - m01) s.  Otherwise the largest diagonal entry i with Eigen's tie rule
+ *     (start at 0, then m11 > m00, then m22 > m(i,i)), j = (i + 1) % 3, k = (j + 1) % 3: s = sqrt(m(i,i) - m(j,j) - m(k,k) + 1),
+ *     q[i] = s / 2, s = 0.5 / s, w = (m(k,j) - m(j,k)) s, q[j] = (m(j,i) + m(i,j)) s, q[k] = (m(k,i) + m(i,k)) s.
+ *     m33 != 1: EA_ERR_INVALID_ARG (the reference's assert( T(3,3) == 1 )).
+ *   No multiply-add of either is contracted.  NULL argument: EA_ERR_INVALID_ARG. */
+int ea_pose_to_matrix(const double q[4], const double t[3], double b_T_a[16]);
+int ea_matrix_to_pose(const double b_T_a[16], double q[4], double t[3]);
+
+/* Reprojection: the per-point (u, v) of the problem's OWN residual family (its terms are not included: call it on a term; a
+ * batched problem that has terms reports its head family) at a pose given as the matrix b_T_a, as in the reference's
+ * signature.  The overload is chosen by the problem's variant: plain = utils.cpp:497, distortion = :512, second camera =
+ * :545, both = :560.  Intrinsics are the problem's own (a rig term: K2, as at the reference's call sites).  Weights, loss,
+ * priors, constant masks, z_guard / z_eps and rot_transposed do not enter: reproject has none of them.  The constant third
+ * row of the reference's b_u is not returned.
+ * Arithmetic -- the specification; fp64 throughout, the stored points widened to double (an fp32 problem uses the floats it
+ * holds), IEEE divisions, no contracted multiply-add:
+ *   A (host)   M = rows 0-2 of b_T_a; second camera: rows 0-2 of (T12 b_T_a) T12^-1 with the matrices given to
+ *              ea_problem_set_second_camera, every 4x4 product entry ((a0 b0 + a1 b1) + a2 b2) + a3 b3 summed in k order.
+ *              Eigen's own association for that product is not pinned by the reference's build; this fixed order is this
+ *              library's definition and agrees with the reference to rounding.
+ *   B (device) bx = ((M00 x + M01 y) + M02 z) + M03, by and bz alike; xn = bx / bz, yn = by / bz; with distortion
+ *              r2 = xn xn + yn yn, r4 = r2 r2, r6 = r4 r2, rad = ((1 + k1 r2) + k2 r4) + k3 r6,
+ *              xd = (xn rad + ((2 p1) xn) yn) + p2 (r2 + (2 xn) xn), yd = (yn rad + ((2 p2) xn) yn) + p1 (r2 + (2 yn) yn);
+ *              u = fx xd + cx, v = fy yd + cy.  No validity test: bz == 0 and points behind the camera give what IEEE
+ *              gives (Inf, NaN, mirrored pixels), exactly as upstream.
+ *   DEVIATION: upstream's reproject reads its Kc positionally as (k1, k2, k3, p1, p2) while every call site fills it in
+ *   EAResidueEx::Create's order (k1, k2, p1, p2, k3) (known defects); here k1, k2, p1, p2, k3 mean what their
+ *   names say in ea_problem_set_distortion, as in EAResidueEx.
+ * Output: ea_problem_reproject -- uv[2 i], uv[2 i + 1] of point i in the CALLER's order (as ea_eval_points), capacity >= n.
+ * The batch forms -- the rows layout of ea_batch_row_offsets, the head families' rows in STORAGE order (the order of
+ * ea_batch_eval_rows*), 2 doubles per row; a head family's rows that belong to terms are left untouched; a problem without
+ * points contributes no rows.  b_T_a: count x 16.  ea_batch_reproject_device: uv_dev is 16-byte aligned device memory of the
+ * batch's device, complete when the call returns.
+ * Errors, before anything touches a device: NULL argument, a b_T_a whose last row is not exactly 0 0 0 1 or with a non-finite
+ * entry, capacity too small: EA_ERR_INVALID_ARG.  A problem without points or DT image: EA_ERR_STATE, as ea_eval.
+ * One launch and one synchronisation on the batch's stream serve a whole batch; the matrices go up in a small array of
+ * their own: resident poses (ea_batch_set_poses) survive. */
+int ea_problem_reproject(ea_problem *p, const double b_T_a[16], double *uv /* n x 2 */, int64_t capacity);
+int ea_batch_reproject(ea_batch *b, const double *b_T_a /* count x 16 */, double *uv, int64_t capacity_rows);
+int ea_batch_reproject_device(ea_batch *b, const double *b_T_a, double *uv_dev, int64_t capacity_rows);
+
+/* Overlay: s_overlay on the device.  bgr_out = a copy of bgr_in (height x width x 3 bytes; bgr_out == bgr_in is allowed) in
+ * which, for every point of the problem's own family, pixel ((int)v, (int)u) -- the cast truncates toward zero -- of the
+ * (u, v) above is set to `color` (B, G, R; NULL = {0, 0, 255}, upstream's red).  Upstream writes outside the image unchecked
+ * (undefined behaviour); here such points are skipped and counted in `outside`.  A point is `inside` by the rule of
+ * ea_problem_pixel_cost: u and v finite, |u|, |v| < 1e9, 0 <= (int)u < width, 0 <= (int)v < height, u > -1, v > -1 (a u in
+ * (-1, 0) paints column 0, as upstream's cast does); so for a plain problem and b_T_a = ea_pose_to_matrix(q, t) of a unit q,
+ * inside / outside equal ea_problem_pixel_cost's count / outside.  Points that share a pixel store the same three bytes: the
+ * image is the same on every run; the counts are exact integers.
+ * height, width must equal the DT extent of the problem (of every problem of the batch) -- imB's extent in every upstream
+ * call: EA_ERR_INVALID_ARG otherwise, as for the errors of the reprojection, a NULL entry of a pointer array and, for
+ * ea_batch_overlay_device, an entry that hipPointerGetAttributes does not report as memory of the batch's device.
+ * ea_problem_overlay on a problem without points: EA_ERR_STATE; in a batch such a problem leaves its image a plain copy and
+ * its stats zero.  stats: count entries, or NULL.
+ * Host forms: the images go up into a cached device block, are painted and come back.  ea_batch_overlay_device paints count
+ * device images in place (they must be complete when the call is made): one launch, one synchronisation, nothing but the
+ * stats crosses the bus.
+ * Out of scope: an Eigen-typed reproject in the C++ shims (Eigen and OpenCV are not dependencies of this library), overlays
+ * taken by the trackers themselves, image file formats, anti-aliased or thick marks. */
+typedef struct {
+  int64_t n, inside, outside;   /* points of the family; painted; skipped */
+} ea_overlay_stats;
+int ea_problem_overlay(ea_problem *p, const double b_T_a[16], const uint8_t *bgr_in, int height, int width,
+                       const uint8_t color[3], uint8_t *bgr_out, ea_overlay_stats *stats);
+int ea_batch_overlay(ea_batch *b, const double *b_T_a, const uint8_t *const *bgr_in, int height, int width,
+                     const uint8_t color[3], uint8_t *const *bgr_out, ea_overlay_stats *stats);
+int ea_batch_overlay_device(ea_batch *b, const double *b_T_a, uint8_t *const *bgr_dev, int height, int width,
+                            const uint8_t color[3], ea_overlay_stats *stats);
+
 /* ceres::Solve(options, &problem, &summary) (standalone_edge_align.cpp:286; SolveEA.cpp:198).
  * q,t in/out.  The whole trust-region loop runs on the device. */
 int ea_solve(ea_problem *p, const ea_options *opt, double q[4], double t[3], ea_summary *summary);
