@@ -61,6 +61,8 @@ EXPORTED = [
     "ea_tracker_batch_keyframe_state",
     "ea_pose_to_matrix", "ea_matrix_to_pose", "ea_problem_reproject", "ea_batch_reproject", "ea_batch_reproject_device",
     "ea_problem_overlay", "ea_batch_overlay", "ea_batch_overlay_device",
+    "ea_problem_set_now_depth", "ea_problem_set_now_depth_device", "ea_batch_set_now_depth", "ea_batch_set_now_depth_device",
+    "ea_default_depth_gate_params", "ea_problem_depth_gate", "ea_batch_depth_gate", "ea_batch_depth_gate_device",
 ]
 
 # measurement hooks (edge_alignment_amd/csrc/ea_hip_dev.h): bound by bench.py, the A/B scripts and the tests that pin the
@@ -165,6 +167,64 @@ class KeyframeState(C.Structure):
 
 class OverlayStats(C.Structure):
     _fields_ = [("n", C.c_int64), ("inside", C.c_int64), ("outside", C.c_int64)]
+
+
+EA_DEPTH_U16, EA_DEPTH_F32 = 0, 1
+GATE_BEHIND, GATE_OUTSIDE, GATE_UNKNOWN, GATE_CONSISTENT, GATE_OCCLUDED, GATE_FREE = range(6)
+
+
+class DepthGateParams(C.Structure):
+    _fields_ = [("radius", C.c_int), ("abs_tol", C.c_double), ("rel_tol", C.c_double), ("w_occluded", C.c_double),
+                ("w_free", C.c_double), ("w_unknown", C.c_double), ("apply", C.c_int)]
+
+
+class DepthGateStats(C.Structure):
+    _fields_ = [("n", C.c_int64), ("n_behind", C.c_int64), ("n_outside", C.c_int64), ("n_unknown", C.c_int64),
+                ("n_consistent", C.c_int64), ("n_occluded", C.c_int64), ("n_free", C.c_int64)]
+
+
+def default_depth_gate_params(**over):
+    """ea_default_depth_gate_params with the given fields replaced"""
+    prm = DepthGateParams()
+    load().ea_default_depth_gate_params(C.byref(prm))
+    for k, v in over.items():
+        if k not in dict(DepthGateParams._fields_):
+            raise TypeError("unknown depth gate parameter %r" % k)
+        setattr(prm, k, int(v) if k in ("radius", "apply") else float(v))
+    return prm
+
+
+def depth_gate_stats_to_dict(s):
+    return {k: getattr(s, k) for k, _ in DepthGateStats._fields_}
+
+
+def _depth_image(depth):
+    """(array kept alive, kind, height, width) of a host depth image: uint16 (TUM) or float32 (metres)"""
+    if depth.dtype == np.uint16:
+        kind = EA_DEPTH_U16
+    elif depth.dtype == np.float32:
+        kind = EA_DEPTH_F32
+    else:
+        raise ValueError("depth must be uint16 or float32")
+    if depth.ndim != 2:
+        raise ValueError("depth must be (H, W)")
+    depth = np.ascontiguousarray(depth)
+    return depth, kind, depth.shape[0], depth.shape[1]
+
+
+def _depth_tensor(depth):
+    """(address, kind, height, width) of a depth image in a torch tensor on the GPU: int16 bits of uint16, or float32"""
+    import torch
+    if not depth.is_cuda or not depth.is_contiguous() or depth.dim() != 2:
+        raise ValueError("depth must be a contiguous (H, W) tensor on the GPU")
+    if depth.dtype == torch.float32:
+        kind = EA_DEPTH_F32
+    elif depth.dtype in (torch.int16, getattr(torch, "uint16", torch.int16)):
+        kind = EA_DEPTH_U16
+    else:
+        raise ValueError("depth must hold uint16 (as int16 or uint16) or float32")
+    torch.cuda.current_stream(depth.device).synchronize()    # the image is complete before the library copies it
+    return depth.data_ptr(), kind, int(depth.shape[0]), int(depth.shape[1])
 
 
 def overlay_stats_to_dict(s):
@@ -361,6 +421,16 @@ def load():
     L.ea_problem_overlay.argtypes = [vp, dp, vp, C.c_int, C.c_int, u8p, vp, ovp]
     L.ea_batch_overlay.argtypes = [vp, dp, C.POINTER(vp), C.c_int, C.c_int, u8p, C.POINTER(vp), ovp]
     L.ea_batch_overlay_device.argtypes = [vp, dp, C.POINTER(vp), C.c_int, C.c_int, u8p, ovp]
+    dgp, dgs = C.POINTER(DepthGateParams), C.POINTER(DepthGateStats)
+    L.ea_problem_set_now_depth.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double]
+    L.ea_problem_set_now_depth_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double]
+    L.ea_batch_set_now_depth.argtypes = [vp, C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_double]
+    L.ea_batch_set_now_depth_device.argtypes = [vp, C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_double]
+    L.ea_default_depth_gate_params.argtypes = [dgp]
+    L.ea_default_depth_gate_params.restype = None
+    L.ea_problem_depth_gate.argtypes = [vp, dp, dgp, vp, C.c_int64, dgs]
+    L.ea_batch_depth_gate.argtypes = [vp, dp, dgp, vp, C.c_int64, dgs]
+    L.ea_batch_depth_gate_device.argtypes = [vp, dp, dgp, vp, C.c_int64, dgs]
     _lib = L
     return L
 
@@ -819,6 +889,32 @@ class Problem:
         _check(load().ea_problem_overlay(self._h, _dp(M), image.ctypes.data_as(C.c_void_p), image.shape[0], image.shape[1],
                                          col[0] if col else None, out.ctypes.data_as(C.c_void_p), C.byref(st)))
         return out, overlay_stats_to_dict(st)
+
+    def set_now_depth(self, depth, z_scaling=5000.0):
+        """ea_problem_set_now_depth[_device]: the current frame's depth, copied and kept in its own kind -- a uint16 (metres =
+        d / z_scaling) or float32 (metres) array (H, W), or a torch tensor on the GPU (int16 / uint16 bits, or float32); None
+        drops it"""
+        if depth is None:
+            _check(load().ea_problem_set_now_depth(self._h, None, 0, 0, 0, 0.0))
+        elif hasattr(depth, "data_ptr"):
+            ptr, kind, h, w = _depth_tensor(depth)
+            _check(load().ea_problem_set_now_depth_device(self._h, C.c_void_p(ptr), kind, h, w, float(z_scaling)))
+        else:
+            depth, kind, h, w = _depth_image(depth)
+            _check(load().ea_problem_set_now_depth(self._h, depth.ctypes.data_as(C.c_void_p), kind, h, w, float(z_scaling)))
+
+    def depth_gate(self, M, classes=True, **params):
+        """ea_problem_depth_gate at b_T_a = M (4x4, or a (q, t) tuple): (class bytes [n] in the caller's order -- None with
+        classes=False --, stats dict).  params: the fields of ea_depth_gate_params (radius, abs_tol, rel_tol, w_occluded,
+        w_free, w_unknown, apply) over their defaults; with apply the problem's weights are replaced"""
+        M = _pose_matrix(M)
+        prm = default_depth_gate_params(**params)
+        n = self.num_points
+        cls = np.zeros(max(n, 1), np.uint8) if classes else None
+        st = DepthGateStats()
+        _check(load().ea_problem_depth_gate(self._h, _dp(M), C.byref(prm), cls.ctypes.data_as(C.c_void_p) if classes else None,
+                                            n, C.byref(st)))
+        return (cls[:n] if classes else None), depth_gate_stats_to_dict(st)
 
     def set_flavour(self, z_guard=0.01, z_eps=0.0, rot_transposed=False):
         _check(load().ea_problem_set_flavour(self._h, z_guard, z_eps, int(rot_transposed)))
@@ -1494,6 +1590,62 @@ class Batch:
         st = (OverlayStats * max(n, 1))()
         _check(load().ea_batch_overlay_device(self._h, _dp(M), arr, int(height), int(width), col[0] if col else None, st))
         return [overlay_stats_to_dict(st[i]) for i in range(n)]
+
+    def set_now_depth(self, depths, z_scaling=5000.0):
+        """ea_batch_set_now_depth[_device]: one depth image per problem, all uint16 or all float32 arrays (H, W) of one extent,
+        or all torch tensors on the GPU; None drops every problem's image"""
+        n = len(self)
+        if depths is None:
+            _check(load().ea_batch_set_now_depth(self._h, None, 0, 0, 0, 0.0))
+            return
+        if len(depths) != n:
+            raise ValueError("one depth image per problem")
+        on_device = n > 0 and hasattr(depths[0], "data_ptr")
+        items = [_depth_tensor(d) if on_device else _depth_image(d) for d in depths]
+        if len({it[1:] for it in items}) > 1:
+            raise ValueError("the depth images must share one kind and extent")
+        _, kind, h, w = items[0] if n else (None, 0, 3, 3)
+        arr = (C.c_void_p * max(n, 1))(*[it[0] if on_device else it[0].ctypes.data for it in items])
+        fn = load().ea_batch_set_now_depth_device if on_device else load().ea_batch_set_now_depth
+        _check(fn(self._h, arr, kind, h, w, float(z_scaling)))
+
+    def depth_gate(self, M, out=None, classes=True, **params):
+        """ea_batch_depth_gate at the poses M: (class bytes [rows] in the layout of row_offsets(), the head families' rows in
+        storage order, rows of terms as they are in `out` (zero in a fresh array) -- None with classes=False --, list of
+        stats dicts)"""
+        M = _pose_matrices(M, len(self))
+        prm = default_depth_gate_params(**params)
+        n = len(self)
+        cls = None
+        if classes:
+            cls = np.zeros(int(self.row_offsets()[-1]), np.uint8) if out is None else out
+            if cls.dtype != np.uint8 or not cls.flags.c_contiguous or cls.ndim != 1:
+                raise ValueError("out must be a contiguous uint8 array (rows,)")
+        st = (DepthGateStats * max(n, 1))()
+        _check(load().ea_batch_depth_gate(self._h, _dp(M), C.byref(prm), cls.ctypes.data_as(C.c_void_p) if classes else None,
+                                          cls.shape[0] if classes else 0, st))
+        return cls, [depth_gate_stats_to_dict(st[i]) for i in range(n)]
+
+    def depth_gate_device(self, M, cls=None, capacity_rows=None, **params):
+        """ea_batch_depth_gate_device: the class bytes into a uint8 torch tensor (rows,) on the batch's GPU (or a raw device
+        address with capacity_rows), or nowhere (cls=None); nothing but the stats crosses the bus.  Returns the stats dicts"""
+        M = _pose_matrices(M, len(self))
+        prm = default_depth_gate_params(**params)
+        n = len(self)
+        if cls is not None and hasattr(cls, "data_ptr"):
+            import torch
+            if not cls.is_cuda or cls.dtype != torch.uint8 or not cls.is_contiguous():
+                raise ValueError("cls must be a contiguous uint8 tensor on the batch's GPU")
+            rows = cls.numel()
+            capacity_rows = rows if capacity_rows is None else min(int(capacity_rows), rows)
+            torch.cuda.current_stream(cls.device).synchronize()   # the tensor's producers are done before the library writes
+            cls = cls.data_ptr()
+        if cls is not None and capacity_rows is None:
+            raise ValueError("capacity_rows is required with a raw address")
+        st = (DepthGateStats * max(n, 1))()
+        _check(load().ea_batch_depth_gate_device(self._h, _dp(M), C.byref(prm), C.c_void_p(cls) if cls is not None else None,
+                                                 int(capacity_rows or 0), st))
+        return [depth_gate_stats_to_dict(st[i]) for i in range(n)]
 
     def covariance(self, q, t, **opts):
         """ea_batch_covariance: one covariance per problem at q (n, 4), t (n, 3) -> list of covariance_to_dict"""

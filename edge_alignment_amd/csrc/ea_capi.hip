@@ -418,6 +418,11 @@ struct ea_batch {
   int frames_rounds = 0;  // looks at the hysteresis flags of the last batched producer call (ea_batch_set_frames_canny / _ros; else 0)
   int frames_without_edges = 0;  // current frames without any edge in the last ea_batch_set_frames_ros call (else 0)
   int64_t frames_uploaded = 0;   // host-to-device frame copies of the last ea_batch_set_frames_ros_pyramid call led by this batch
+  // ea_batch_depth_gate*: the segments and counters of a call, [DepthGateSeg x count | 6 counters x count], on the device and
+  // in pinned memory; batch-owned and kept across calls, so that a call takes nothing from the allocator's cache (whose
+  // reuse of a freed block drains the device first: a second wait)
+  unsigned char *d_gate = nullptr, *h_gate = nullptr;
+  size_t gate_bytes = 0;
 };
 
 int ea::check_device(int device) {
@@ -602,6 +607,7 @@ extern "C" void ea_problem_destroy(ea_problem *p) {
   free_points(p);
   if (p->d_dt) cached_free(p->d_dt);
   if (p->d_dt32) cached_free(p->d_dt32);
+  if (p->d_now_depth) cached_free(p->d_now_depth);
   if (p->ws) cached_free(p->ws);
   if (p->stage) cached_free(p->stage);
   delete p;
@@ -1065,6 +1071,8 @@ static void batch_free_device(ea_batch *b) {
   starts_free(b);
   cached_free(b->d_frames); cached_host_free(b->h_frames);
   b->d_frames = b->h_frames = nullptr; b->frames_bytes = b->h_frames_bytes = 0;
+  cached_free(b->d_gate); cached_host_free(b->h_gate);
+  b->d_gate = b->h_gate = nullptr; b->gate_bytes = 0;
   cached_free(b->d_cprobs); cached_host_free(b->h_cdesc); cached_host_free(b->h_cov);
   b->d_cprobs = nullptr; b->h_cdesc = nullptr; b->cdesc_cap = 0; b->h_cov = nullptr; b->dv_cov = nullptr;
   (void)hipFree(b->d_rows_r); (void)hipFree(b->d_rows_J); (void)hipFree(b->d_rows_invalid);
@@ -3826,6 +3834,326 @@ extern "C" int ea_problem_overlay(ea_problem *p, const double b_T_a[16], const u
   if ((rc = batch_build(b)) != EA_OK) return rc;  // (no DT image: EA_ERR_STATE, as ea_eval)
   if (p->n == 0) return fail(EA_ERR_STATE, "no edge points (ea_problem_set_points)");
   return ea_batch_overlay(b, b_T_a, &bgr_in, height, width, color, &bgr_out, stats);
+}
+
+// ---- depth-consistency gate (ea_depth_gate.h; kernel: ea_depth_gate_kernel) ------------------------------------------------
+//
+// The current frame's depth is held by the problem in its own kind (a cached block, copied as it came).  It is read by the
+// gate only -- no descriptor names it -- so setting it moves no version: batches do not rebuild, resident poses survive.
+static void now_depth_drop(ea_problem *p) {
+  if (p->d_now_depth) cached_free(p->d_now_depth);
+  p->d_now_depth = nullptr;
+  p->now_depth_cap = 0;
+  p->nd_kind = p->nd_H = p->nd_W = 0;
+  p->nd_z_scaling = 1.0;
+}
+
+static size_t now_depth_bytes(int kind, int height, int width) {
+  return (size_t)height * (size_t)width * (kind == EA_DEPTH_F32 ? sizeof(float) : sizeof(uint16_t));
+}
+
+// room for the image in the problem's block (the previous allocation when it fits and is not four times too large) and the
+// image's description; the samples are the caller's to copy
+static int now_depth_reserve(ea_problem *p, int kind, int height, int width, double z_scaling) {
+  const size_t need = now_depth_bytes(kind, height, width);
+  if (!(p->d_now_depth && p->now_depth_cap >= need && p->now_depth_cap <= 4 * need + 4096)) {
+    now_depth_drop(p);
+    HIPCHK(cached_malloc(&p->d_now_depth, need, p->device));
+    p->now_depth_cap = need;
+  }
+  p->nd_kind = kind; p->nd_H = height; p->nd_W = width;
+  p->nd_z_scaling = kind == EA_DEPTH_U16 ? z_scaling : 1.0;
+  return EA_OK;
+}
+
+// a depth image the caller says is in device memory: of this device, as far as the runtime can tell, aligned for its samples
+static int check_device_depth(const void *ptr, int device, int kind) {
+  if (reinterpret_cast<uintptr_t>(ptr) % (kind == EA_DEPTH_F32 ? 4 : 2) != 0) return fail(EA_ERR_INVALID_ARG, "depth_dev: misaligned image");
+  hipPointerAttribute_t at;
+  const hipError_t e = hipPointerGetAttributes(&at, ptr);
+  if (e != hipSuccess) (void)hipGetLastError();
+  if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.device != device)
+    return fail(EA_ERR_INVALID_ARG, "depth_dev is not device memory of the problem's device");
+  return EA_OK;
+}
+
+static int problem_set_now_depth(ea_problem *p, const void *depth, int kind, int height, int width, double z_scaling, bool on_device) {
+  if (!p) return fail(EA_ERR_INVALID_ARG, "NULL problem");
+  if (!depth) { now_depth_drop(p); return EA_OK; }
+  if (const char *why = now_depth_args_error(kind, height, width, z_scaling)) return fail(EA_ERR_INVALID_ARG, why);
+  int rc = require_device();
+  if (rc != EA_OK) return rc;
+  HIPCHK(hipSetDevice(p->device));
+  if (on_device && (rc = check_device_depth(depth, p->device, kind)) != EA_OK) return rc;
+  if ((rc = now_depth_reserve(p, kind, height, width, z_scaling)) != EA_OK) return rc;
+  hipError_t e = hipMemcpy(p->d_now_depth, depth, now_depth_bytes(kind, height, width),
+                           on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipDeviceSynchronize();  // (a device-to-device copy may return before it has run)
+  if (e != hipSuccess) {
+    now_depth_drop(p);
+    return fail(EA_ERR_HIP, std::string("ea_problem_set_now_depth: ") + hipGetErrorString(e));
+  }
+  return EA_OK;
+}
+
+extern "C" int ea_problem_set_now_depth(ea_problem *p, const void *depth, int kind, int height, int width, double z_scaling) {
+  return problem_set_now_depth(p, depth, kind, height, width, z_scaling, false);
+}
+
+extern "C" int ea_problem_set_now_depth_device(ea_problem *p, const void *depth_dev, int kind, int height, int width,
+                                               double z_scaling) {
+  return problem_set_now_depth(p, depth_dev, kind, height, width, z_scaling, true);
+}
+
+static bool batch_has_duplicates(const ea_batch *b) {
+  std::vector<const ea_problem *> sorted(b->probs.begin(), b->probs.end());
+  std::sort(sorted.begin(), sorted.end());
+  return std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end();
+}
+
+// N images, one per problem: the copies on the batch's stream, ONE wait
+static int batch_set_now_depth(ea_batch *b, const void *const *depth, int kind, int height, int width, double z_scaling, bool on_device) {
+  if (!b) return fail(EA_ERR_INVALID_ARG, "NULL batch");
+  if (!depth) {
+    for (ea_problem *p : b->probs) now_depth_drop(p);
+    return EA_OK;
+  }
+  if (const char *why = now_depth_args_error(kind, height, width, z_scaling)) return fail(EA_ERR_INVALID_ARG, why);
+  for (size_t i = 0; i < b->probs.size(); ++i)
+    if (!depth[i]) return fail(EA_ERR_INVALID_ARG, "NULL entry in the depth pointer array");
+  if (batch_has_duplicates(b))
+    return fail(EA_ERR_INVALID_ARG, "the same problem twice in the batch: each depth image needs a problem of its own");
+  int rc = require_device();
+  if (rc != EA_OK) return rc;
+  HIPCHK(hipSetDevice(b->device));
+  if (on_device)
+    for (size_t i = 0; i < b->probs.size(); ++i)
+      if ((rc = check_device_depth(depth[i], b->device, kind)) != EA_OK) return rc;
+  const size_t bytes = now_depth_bytes(kind, height, width);
+  hipError_t e = hipSuccess;
+  for (size_t i = 0; i < b->probs.size() && rc == EA_OK && e == hipSuccess; ++i) {
+    ea_problem *p = b->probs[i];
+    if ((rc = now_depth_reserve(p, kind, height, width, z_scaling)) != EA_OK) break;
+    e = hipMemcpyAsync(p->d_now_depth, depth[i], bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, b->stream);
+  }
+  const hipError_t es = hipStreamSynchronize(b->stream);
+  if (e == hipSuccess) e = es;
+  if (rc != EA_OK || e != hipSuccess) {  // no problem keeps an image that may be half written
+    for (ea_problem *p : b->probs) now_depth_drop(p);
+    return rc != EA_OK ? rc : fail(EA_ERR_HIP, std::string("ea_batch_set_now_depth: ") + hipGetErrorString(e));
+  }
+  return EA_OK;
+}
+
+extern "C" int ea_batch_set_now_depth(ea_batch *b, const void *const *depth, int kind, int height, int width, double z_scaling) {
+  return batch_set_now_depth(b, depth, kind, height, width, z_scaling, false);
+}
+
+extern "C" int ea_batch_set_now_depth_device(ea_batch *b, const void *const *depth_dev, int kind, int height, int width,
+                                             double z_scaling) {
+  return batch_set_now_depth(b, depth_dev, kind, height, width, z_scaling, true);
+}
+
+extern "C" void ea_default_depth_gate_params(ea_depth_gate_params *prm) {
+  if (!prm) return;
+  prm->radius = 1;
+  prm->abs_tol = 0.02; prm->rel_tol = 0.02;
+  prm->w_occluded = 0.0; prm->w_free = 0.0; prm->w_unknown = 1.0;
+  prm->apply = 1;
+}
+
+// The gate itself.  One segment per problem of the call (its head family) with the 3x4 matrix of step A; segments and zeroed
+// counters go up in ONE copy from a pinned block, ONE launch, the counters come back into the same block, ONE synchronisation:
+// all on the batch's stream.  The matrices travel in the segments: d_poses is not written.  With `apply` the kernel writes the
+// problems' weight storage in place; a problem that had no weights becomes a weighted one afterwards (its version moves: the
+// batches that hold it rebuild, as after ea_problem_set_weights), one that had keeps its version.
+namespace {
+struct DepthGateRun {
+  unsigned char *pinned = nullptr;  // (the batch's h_gate)
+  int nseg = 0;
+  size_t o_counts = 0;
+  const DepthGateSeg *segs() const { return reinterpret_cast<const DepthGateSeg *>(pinned); }
+  const unsigned long long *counts() const { return reinterpret_cast<const unsigned long long *>(pinned + o_counts); }
+};
+}  // namespace
+
+// what needs neither a handle nor a device
+static int depth_gate_params_check(const ea_depth_gate_params *prm) {
+  if (const char *why = depth_gate_params_error(prm)) return fail(EA_ERR_INVALID_ARG, why);
+  return EA_OK;
+}
+
+// what the problems of a call must be, read off the problems themselves: nothing has touched a device or changed a problem yet
+static int depth_gate_state_checks(const ea_batch *b, const ea_depth_gate_params *prm) {
+  if (b->probs.size() > 65535) return fail(EA_ERR_INVALID_ARG, "more than 65535 problems in one depth gate call");
+  if (!depth_gate_factors_fit(prm, b->dtype == EA_F32 ? (double)FLT_MAX : DBL_MAX))
+    return fail(EA_ERR_INVALID_ARG, "a weight factor overflows the float of an fp32 problem");
+  if (prm->apply && batch_has_duplicates(b))
+    return fail(EA_ERR_INVALID_ARG, "the same problem twice in the batch: its weights can be written once per call");
+  for (const ea_problem *p : b->probs) {
+    if (!p->d_dt) return fail(EA_ERR_STATE, "distance-transform image not set (ea_problem_set_dt)");
+    if (!p->d_now_depth) return fail(EA_ERR_STATE, "current-frame depth not set (ea_problem_set_now_depth)");
+    if (p->nd_H != p->H || p->nd_W != p->W)
+      return fail(EA_ERR_STATE, "the current-frame depth and the distance-transform image differ in extent");
+    if (p->nd_kind != b->probs[0]->nd_kind)
+      return fail(EA_ERR_STATE, "the problems of one depth gate call must hold depth of one kind");
+  }
+  return EA_OK;
+}
+
+// upload + launch + the counters on their way back, for a batch that is built; the caller queues what else must come down and
+// synchronises.  cls_dev: class bytes in the rows layout, or NULL
+static int depth_gate_enqueue(ea_batch *b, const double *b_T_a, const ea_depth_gate_params *prm, unsigned char *cls_dev,
+                              DepthGateRun &run) {
+  const int nseg = (int)b->probs.size();
+  const ProblemDesc *hd = reinterpret_cast<const ProblemDesc *>(b->h_desc);  // (batch_build's staging block)
+  const GroupDesc *hg = reinterpret_cast<const GroupDesc *>(b->h_desc + (size_t)b->nterms * sizeof(ProblemDesc));
+  run.nseg = nseg;
+  run.o_counts = align16((size_t)nseg * sizeof(DepthGateSeg));
+  const size_t bytes = run.o_counts + (size_t)nseg * kDepthGateClasses * sizeof(unsigned long long);
+  if (b->gate_bytes < bytes) {
+    cached_free(b->d_gate); cached_host_free(b->h_gate);
+    b->d_gate = b->h_gate = nullptr; b->gate_bytes = 0;
+    HIPCHK(cached_malloc(reinterpret_cast<void **>(&b->d_gate), bytes, b->device));
+    HIPCHK(cached_host_malloc(reinterpret_cast<void **>(&b->h_gate), bytes, hipHostMallocDefault, b->device));
+    b->gate_bytes = bytes;
+  }
+  run.pinned = b->h_gate;
+  std::memset(run.pinned, 0, bytes);
+  DepthGateSeg *h_segs = reinterpret_cast<DepthGateSeg *>(run.pinned);
+  int max_n = 0;
+  for (int j = 0; j < nseg; ++j) {
+    const ea_problem *p = b->probs[(size_t)j];
+    const int term = hg[j].term_begin;  // the head family; its terms are not included
+    DepthGateSeg &sg = h_segs[j];
+    sg.row = hd[term].row_begin; sg.n = hd[term].n; sg.term = term;
+    const bool rig = (p->variant & 2) != 0;
+    reproject_matrix(b_T_a + 16 * (size_t)j, rig ? p->T12 : nullptr, rig ? p->T12inv : nullptr, sg.M);
+    sg.depth = p->d_now_depth;
+    sg.z_scaling = p->nd_z_scaling;
+    sg.weights = (prm->apply && sg.n > 0) ? weights_ptr(p) : nullptr;
+    sg.cls = cls_dev ? cls_dev + sg.row : nullptr;
+    sg.dw_z_ref = p->dw_z_ref;
+    sg.dw_power = p->dw_power;
+    max_n = std::max(max_n, (int)sg.n);
+  }
+  unsigned char *d = b->d_gate;
+  HIPCHK(hipMemcpyAsync(d, run.pinned, bytes, hipMemcpyHostToDevice, b->stream));
+  DepthGateWork w;
+  w.nseg = nseg; w.max_n = max_n; w.kind = b->probs[0]->nd_kind; w.radius = prm->radius;
+  w.rule = depth_gate_rule(prm);
+  w.segs = reinterpret_cast<const DepthGateSeg *>(d);
+  w.counts = reinterpret_cast<unsigned long long *>(d + run.o_counts);
+  HIPCHK(launch_depth_gate(b->dtype, w, b->d_probs, b->stream));
+  HIPCHK(hipMemcpyAsync(run.pinned + run.o_counts, d + run.o_counts, bytes - run.o_counts, hipMemcpyDeviceToHost, b->stream));
+  return EA_OK;
+}
+
+// after the synchronisation: the counts, and with `apply` the problems' new state
+static void depth_gate_finish(ea_batch *b, const ea_depth_gate_params *prm, const DepthGateRun &run, ea_depth_gate_stats *stats) {
+  for (int j = 0; j < run.nseg; ++j) {
+    if (stats) {
+      const unsigned long long *c = run.counts() + (size_t)kDepthGateClasses * j;
+      stats[j].n = run.segs()[j].n;
+      stats[j].n_behind = (int64_t)c[EA_GATE_BEHIND]; stats[j].n_outside = (int64_t)c[EA_GATE_OUTSIDE];
+      stats[j].n_unknown = (int64_t)c[EA_GATE_UNKNOWN]; stats[j].n_consistent = (int64_t)c[EA_GATE_CONSISTENT];
+      stats[j].n_occluded = (int64_t)c[EA_GATE_OCCLUDED]; stats[j].n_free = (int64_t)c[EA_GATE_FREE];
+    }
+    ea_problem *p = b->probs[(size_t)j];
+    if (prm->apply && run.segs()[j].n > 0) {
+      p->weights_from_depth = false;
+      if (!p->weighted) { p->weighted = true; p->version++; }  // (new values alone need no rebuild of a batch)
+    }
+  }
+}
+
+// the checks of the three forms and everything up to a built batch whose problems own their points (apply)
+static int depth_gate_prepare(ea_batch *b, const ea_depth_gate_params *prm) {
+  int rc = depth_gate_state_checks(b, prm);
+  if (rc == EA_OK) rc = require_device();
+  if (rc != EA_OK) return rc;
+  HIPCHK(hipSetDevice(b->device));
+  if (prm->apply)
+    for (ea_problem *p : b->probs)
+      if ((rc = own_borrowed_points(p)) != EA_OK) return rc;  // (the weights live behind z in an allocation of the problem's)
+  return batch_build(b);
+}
+
+static int batch_depth_gate_checks(ea_batch *b, const double *b_T_a, const ea_depth_gate_params *prm, const void *cls,
+                                   int64_t capacity_rows) {
+  if (!b || !b_T_a || !prm) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  int rc = depth_gate_params_check(prm);  // (the batch is looked at only for what depends on it)
+  if (rc == EA_OK) rc = check_reproject_poses(b_T_a, (int)b->probs.size());
+  if (rc != EA_OK) return rc;
+  if (cls && capacity_rows < batch_rows_host(b))
+    return fail(EA_ERR_INVALID_ARG, "capacity_rows is smaller than the batch's row count (ea_batch_row_offsets)");
+  return EA_OK;
+}
+
+extern "C" int ea_batch_depth_gate_device(ea_batch *b, const double *b_T_a, const ea_depth_gate_params *prm, uint8_t *cls_dev,
+                                          int64_t capacity_rows, ea_depth_gate_stats *stats) {
+  int rc = batch_depth_gate_checks(b, b_T_a, prm, cls_dev, capacity_rows);
+  if (rc != EA_OK) return rc;
+  if (cls_dev) {  // (before a problem is changed)
+    if ((rc = require_device()) != EA_OK) return rc;
+    hipPointerAttribute_t at;
+    const hipError_t e = hipPointerGetAttributes(&at, cls_dev);
+    if (e != hipSuccess) (void)hipGetLastError();
+    if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.device != b->device)
+      return fail(EA_ERR_INVALID_ARG, "cls_dev is not device memory of the batch's device");
+  }
+  if ((rc = depth_gate_prepare(b, prm)) != EA_OK) return rc;
+  DepthGateRun run;
+  if ((rc = depth_gate_enqueue(b, b_T_a, prm, cls_dev, run)) != EA_OK) return rc;
+  HIPCHK(hipStreamSynchronize(b->stream));  // weights and classes are complete (and visible to any other stream) when this returns
+  depth_gate_finish(b, prm, run, stats);
+  return EA_OK;
+}
+
+extern "C" int ea_batch_depth_gate(ea_batch *b, const double *b_T_a, const ea_depth_gate_params *prm, uint8_t *cls,
+                                   int64_t capacity_rows, ea_depth_gate_stats *stats) {
+  int rc = batch_depth_gate_checks(b, b_T_a, prm, cls, capacity_rows);
+  if (rc != EA_OK) return rc;
+  if ((rc = depth_gate_prepare(b, prm)) != EA_OK) return rc;
+  DevBuf rows;
+  if (cls && b->total_rows > 0) HIPCHK(cached_malloc(&rows.p, (size_t)b->total_rows, b->device));
+  DepthGateRun run;
+  if ((rc = depth_gate_enqueue(b, b_T_a, prm, rows.as<unsigned char>(), run)) != EA_OK) return rc;
+  // the head families' class bytes come down, adjacent ones in one copy; rows of terms stay as the caller left them
+  for (int j = 0; rows.p && j < run.nseg;) {
+    const int64_t begin = run.segs()[j].row;
+    int64_t end = begin + run.segs()[j].n;
+    for (++j; j < run.nseg && run.segs()[j].row == end; ++j) end += run.segs()[j].n;
+    if (end > begin)
+      HIPCHK(hipMemcpyAsync(cls + begin, rows.as<unsigned char>() + begin, (size_t)(end - begin), hipMemcpyDeviceToHost, b->stream));
+  }
+  HIPCHK(hipStreamSynchronize(b->stream));
+  depth_gate_finish(b, prm, run, stats);
+  return EA_OK;
+}
+
+extern "C" int ea_problem_depth_gate(ea_problem *p, const double b_T_a[16], const ea_depth_gate_params *prm, uint8_t *cls,
+                                     int64_t capacity, ea_depth_gate_stats *stats) {
+  if (!p || !b_T_a || !prm || !stats) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  int rc = depth_gate_params_check(prm);
+  if (rc == EA_OK) rc = check_reproject_poses(b_T_a, 1);
+  if (rc != EA_OK) return rc;
+  if (cls && capacity < p->n) return fail(EA_ERR_INVALID_ARG, "capacity is smaller than ea_problem_num_points");
+  if ((rc = require_device()) != EA_OK) return rc;
+  ea_batch *b;
+  if ((rc = self_batch(p, &b)) != EA_OK) return rc;
+  if (p->n == 0) return fail(EA_ERR_STATE, "no edge points (ea_problem_set_points)");
+  if ((rc = depth_gate_prepare(b, prm)) != EA_OK) return rc;
+  DevBuf rows;
+  if (cls) HIPCHK(cached_malloc(&rows.p, (size_t)p->n, p->device));  // (the head family's rows start at 0)
+  DepthGateRun run;
+  if ((rc = depth_gate_enqueue(b, b_T_a, prm, rows.as<unsigned char>(), run)) != EA_OK) return rc;
+  std::vector<uint8_t> tmp(cls && !p->order.empty() ? (size_t)p->n : 0);
+  if (cls) HIPCHK(hipMemcpyAsync(tmp.empty() ? cls : tmp.data(), rows.p, (size_t)p->n, hipMemcpyDeviceToHost, b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  for (size_t i = 0; i < tmp.size(); ++i) cls[(size_t)p->order[i]] = tmp[i];  // stored in tile order: the caller's order back
+  depth_gate_finish(b, prm, run, stats);
+  return EA_OK;
 }
 
 extern "C" int ea_solve(ea_problem *p, const ea_options *opt, double q[4], double t[3], ea_summary *summary) {

@@ -59,6 +59,13 @@ struct ea_problem {
   double dw_z_ref = 1.0;  // ea_problem_set_depth_weighting: w = min(1, (z_ref / z)^power), power 0 = off
   int dw_power = 0;
   int W = 0, H = 0, pitch = 0;
+  // The current frame's depth (ea_problem_set_now_depth*): nd_H x nd_W samples of their own kind (EA_DEPTH_U16 / EA_DEPTH_F32),
+  // copied as they came into a cached block.  Read by the depth gate only: no descriptor names it, so setting or dropping it
+  // moves no version, and no other setter or producer touches it.
+  void *d_now_depth = nullptr;
+  size_t now_depth_cap = 0;
+  int nd_kind = 0, nd_H = 0, nd_W = 0;
+  double nd_z_scaling = 1.0;
   uint64_t version = 1;  // bumped by every setter; batches rebuild their descriptors lazily
   ea_batch *self = nullptr;
   hipStream_t stream = nullptr;

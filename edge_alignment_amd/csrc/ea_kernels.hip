@@ -42,6 +42,7 @@ extern __device__ int g_lm_probe_row;
 #include "ea_launch.h"
 #include "ea_poses_map.h"
 #include "ea_starts_map.h"
+#include "ea_depth_gate.h"
 #include "ea_lm.h"
 #include "ea_pair_log.h"
 #include "ea_prior.h"
@@ -3454,6 +3455,57 @@ __global__ __launch_bounds__(kReprojectThreads) void ea_reproject_kernel(const P
     }
   }
 }
+
+// ------------------------------------------------------------------------------------------------
+// The depth-consistency gate (ea_*_depth_gate): every warped point's depth against the depth measured where it lands in the
+// current frame.  ea_hip.h states the arithmetic and ea_depth_gate.h holds it (gate_point: the projection of step B, the
+// inside rule, the window scan, the classification; fp64, nothing contracted), shared with the host shim.
+//
+// Shaped like ea_reproject_kernel: one lane per stored point, blockIdx.y the segment (one per problem of the call), the
+// segment -- its 3x4 matrix, depth image, weights and class pointers -- the descriptor and the rule uniform per workgroup.
+// RAW is the depth kind (uint16_t / float), R the window radius: the (2 R + 1)^2 window is that many independent 2- or 4-byte
+// gather loads per lane (a pixel outside the image reads pixel 0 and counts as "no measurement"), all issued before the
+// compare chain; a VGA depth image is 0.6-1.2 MB and stays in L2.  Per lane one coalesced weight store (apply) and one byte
+// store (classes asked for).  Counts: six ballots and popcounts per wavefront, the four wavefronts summed through LDS, at most
+// six integer atomics per workgroup on the segment's counters (exact whatever the order of arrival).
+template <typename T, typename RAW, int R>
+__global__ __launch_bounds__(kDepthGateThreads) void ea_depth_gate_kernel(const ProblemDesc *__restrict__ probs,
+                                                                          const DepthGateSeg *__restrict__ segs, DepthGateRule rule,
+                                                                          unsigned long long *__restrict__ counts) {
+  __shared__ int s_cnt[kDepthGateThreads / 64][kDepthGateClasses];
+  const DepthGateSeg &sg = segs[blockIdx.y];
+  const int n = sg.n;
+  const int first = blockIdx.x * kDepthGateThreads;
+  if (first >= n) return;  // (uniform)
+  const ProblemDesc &pd = probs[sg.term];
+  const int tid = threadIdx.x, i = first + tid;
+  int cls = -1;
+  if (i < n) {
+    typedef T __attribute__((address_space(1))) *GOutT;
+    typedef unsigned char __attribute__((address_space(1))) *GOutB;
+    const double x = (double)((GPtr<T>)static_cast<const T *>(pd.x))[i], y = (double)((GPtr<T>)static_cast<const T *>(pd.y))[i],
+                 z = (double)((GPtr<T>)static_cast<const T *>(pd.z))[i];
+    cls = gate_point<RAW, R, GPtr<RAW>>(sg.M, x, y, z, pd.fx, pd.fy, pd.cx, pd.cy, (pd.variant & 1) ? pd.dist : nullptr,
+                                        (GPtr<RAW>)static_cast<const RAW *>(sg.depth), pd.H, pd.W, sg.z_scaling, rule.abs_tol,
+                                        rule.rel_tol);
+    if (sg.cls) ((GOutB)sg.cls)[i] = (unsigned char)cls;
+    if (sg.weights)
+      ((GOutT) static_cast<T *>(sg.weights))[i] = (T)gate_weight(gate_factor(rule, cls), gate_depth_factor(z, sg.dw_z_ref, sg.dw_power));
+  }
+  const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+  for (int c = 0; c < kDepthGateClasses; ++c) {
+    const int cnt = __popcll(__builtin_amdgcn_ballot_w64(cls == c));
+    if (lane == 0) s_cnt[wave][c] = cnt;
+  }
+  __syncthreads();
+  if (tid < kDepthGateClasses) {
+    int sum = 0;
+#pragma unroll
+    for (int w = 0; w < kDepthGateThreads / 64; ++w) sum += s_cnt[w][tid];
+    if (sum) atomicAdd(&counts[(size_t)kDepthGateClasses * blockIdx.y + tid], (unsigned long long)sum);
+  }
+}
 #endif  // !EA_TU_VARIANT
 
 // ------------------------------------------------------------------------------------------------
@@ -3970,6 +4022,22 @@ hipError_t launch_reproject(int dtype, const ReprojectWork &w, const ProblemDesc
       hipLaunchKernelGGL((ea_reproject_kernel<typename decltype(TT)::type, decltype(PAINT)::value>), grid, dim3(kReprojectThreads), 0,
                          stream, probs, w.segs, w.uv, w.color, w.counts);
       return hipGetLastError();
+    });
+  });
+}
+
+hipError_t launch_depth_gate(int dtype, const DepthGateWork &w, const ProblemDesc *probs, hipStream_t stream) {
+  if (w.nseg < 1 || w.nseg > 65535 || w.max_n < 0 || !w.segs || !w.counts) return hipErrorInvalidValue;
+  if (w.max_n == 0) return hipSuccess;
+  const dim3 grid((unsigned)((w.max_n + kDepthGateThreads - 1) / kDepthGateThreads), (unsigned)w.nseg);
+  return dispatch_dtype(dtype, [&](auto TT) {
+    return dispatch_bool(w.kind == EA_DEPTH_F32, [&](auto F32) {
+      return dispatch_int<0, 1, 2, 3>(w.radius, [&](auto RR) {
+        typedef typename std::conditional<decltype(F32)::value, float, uint16_t>::type RAW;
+        hipLaunchKernelGGL((ea_depth_gate_kernel<typename decltype(TT)::type, RAW, decltype(RR)::value>), grid,
+                           dim3(kDepthGateThreads), 0, stream, probs, w.segs, w.rule, w.counts);
+        return hipGetLastError();
+      });
     });
   });
 }

@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "../../include/ea_hip.h"
+#include "ea_depth_gate.h"
 #include "ea_lm.h"
 #include "ea_reproject.h"
 #include "ea_select.h"
@@ -238,6 +239,15 @@ struct ReprojectWork {
   unsigned long long *counts = nullptr;
 };
 hipError_t launch_reproject(int dtype, const ReprojectWork &w, const ProblemDesc *probs, hipStream_t stream);
+// ea_depth_gate_kernel (ea_depth_gate.h): w.nseg segments, w.max_n the longest, the depth images of one kind (EA_DEPTH_*) and
+// the window radius 0..3; counts[6 * seg + class] += the segment's points of that class (zero before the launch)
+struct DepthGateWork {
+  int nseg = 0, max_n = 0, kind = 0, radius = 0;
+  DepthGateRule rule = {};
+  const DepthGateSeg *segs = nullptr;
+  unsigned long long *counts = nullptr;
+};
+hipError_t launch_depth_gate(int dtype, const DepthGateWork &w, const ProblemDesc *probs, hipStream_t stream);
 hipError_t launch_selftest_reduce(const float *in, float *a, float *b, float *c, float *d, double *o32, double *o64,
                                   hipStream_t stream);
 // ea_kernels_var.hip (the same file under -DEA_TU_VARIANT): what launch_eval_fused (tag 0) / launch_eval_poses_grid (tag 1) hand on

@@ -406,6 +406,85 @@ int ea_batch_overlay(ea_batch *b, const double *b_T_a, const uint8_t *const *bgr
 int ea_batch_overlay_device(ea_batch *b, const double *b_T_a, uint8_t *const *bgr_dev, int height, int width,
                             const uint8_t color[3], ea_overlay_stats *stats);
 
+/* ---- depth-consistency gate: occlusion weights from the current frame's depth ------------------------------------------
+ * No upstream equivalent: SolveEA::setNowFrame clones now_depth and never reads it (src/SolveEA.cpp:86-101).  The gate
+ * compares the depth of every warped reference point with the depth MEASURED where it lands in the current frame and, on
+ * request, writes the outcome into the problem's per-point weights (ceres::ScaledLoss per block) without a host round trip.
+ *
+ * The current frame's depth, held by the problem.  height x width, row-major.  EA_DEPTH_U16: uint16 as cv::imread gives TUM
+ * depth, metric depth = (double)d / z_scaling (one IEEE division), valid when d != 0.  EA_DEPTH_F32: float32 metres as the ROS
+ * callbacks hold it, z_scaling ignored, valid when f > 0 and finite (NaN, <= 0 and Inf are "no measurement").  The image is
+ * COPIED into a block of the library's cached allocator and kept in its own kind, nothing is converted on the way in; the
+ * _device forms copy device memory of the problem's device (complete when the call is made; anything else, as far as the
+ * runtime can tell: EA_ERR_INVALID_ARG).  depth == NULL (batch forms: the array itself) drops the held image.  The image
+ * survives ea_problem_set_points*, ea_problem_set_dt* and the frame producers: only these calls replace it.  Batch forms: one
+ * entry per problem, copies on the batch's stream and ONE wait; the same problem twice in the batch is an error, as in
+ * ea_batch_set_frames.  EA_ERR_INVALID_ARG before a problem is looked at or a device is looked for: an unknown kind, height
+ * or width outside 3..32768, for U16 a z_scaling that is not finite or <= 0; also a NULL handle or a NULL entry. */
+typedef enum { EA_DEPTH_U16 = 0, EA_DEPTH_F32 = 1 } ea_depth_kind;
+int ea_problem_set_now_depth(ea_problem *p, const void *depth, int kind, int height, int width, double z_scaling);
+int ea_problem_set_now_depth_device(ea_problem *p, const void *depth_dev, int kind, int height, int width, double z_scaling);
+int ea_batch_set_now_depth(ea_batch *b, const void *const *depth, int kind, int height, int width, double z_scaling);
+int ea_batch_set_now_depth_device(ea_batch *b, const void *const *depth_dev, int kind, int height, int width, double z_scaling);
+
+/* The gate.  ea_default_depth_gate_params: radius 1, abs_tol 0.02, rel_tol 0.02, w_occluded 0, w_free 0, w_unknown 1,
+ * apply 1.  The tolerances (2 cm + 2 %) are API defaults that nobody has measured on real sequences.
+ * Arithmetic -- the specification; fp64 throughout, the stored points widened to double, IEEE divisions, no contracted
+ * multiply-add; the problem's OWN residual family (as reproject, quantiles and pose stats: call it on a term for a term; a
+ * batched problem with terms reports its head family):
+ *   1  M = step A of ea_*_reproject (rig product included); bx, by, bz, u, v = its step B, distortion by name included.
+ *   2  BEHIND when !(bz > 0 && bz < +Inf) (NaN included).
+ *   3  else OUTSIDE when (u, v) is not inside by ea_problem_pixel_cost's rule (see ea_problem_overlay);
+ *      iu = (int)u, iv = (int)v, truncating toward zero.
+ *   4  window: the pixels (iv + dy, iu + dx), dy outer and dx inner, each from -radius to radius, that lie in
+ *      0 <= row < height, 0 <= col < width and hold a valid measurement d (converted as above); e = fabs(d - bz); the first
+ *      such pixel is kept, and any later one with a STRICTLY smaller e (a tie keeps the first in that raster order).  None:
+ *      UNKNOWN.  (Edge points sit on depth discontinuities: the single pixel under a point is the least reliable one.)
+ *   5  tol = abs_tol + rel_tol * bz, diff = d - bz of the kept d: fabs(diff) <= tol CONSISTENT; else diff < 0 OCCLUDED (a
+ *      measured surface lies in front of the point); else FREE (the point hangs in front of everything measured around it).
+ *   6  g = 1 for BEHIND, OUTSIDE and CONSISTENT (what the functor makes of those points is not the gate's business);
+ *      w_unknown, w_occluded, w_free for the other three.
+ * apply != 0: w_i = g_i * dd_i, one IEEE multiplication, rounded once to the problem dtype, where dd_i = 1, or with
+ * ea_problem_set_depth_weighting of power > 0 the fp64 value min(1, (z_ref / z_i)^power) exactly as the producers form it
+ * before their rounding (one division, power - 1 multiplications left to right, clamped to [0, 1]).  The result REPLACES the
+ * problem's weights (the storage of ea_problem_set_weights, behind z, in storage order; borrowed device points are copied
+ * into owned arrays first, as there) and the problem becomes a weighted one: a batch rebuilds when weights APPEAR and drops
+ * its resident poses then, as after ea_problem_set_weights; when only the values change nothing is rebuilt and resident poses
+ * survive.  ea_problem_set_weights(p, NULL, 0) undoes it; a reference-frame producer replaces the weights as it does today.
+ * apply == 0 changes nothing on the problem; resident poses always survive.
+ * Outputs: exact integer counts, n = the sum of the six classes; cls, one byte per point (EA_GATE_*), nullable --
+ * ea_problem_depth_gate: in the CALLER's order (as ea_eval_points), capacity >= n; the batch forms: the rows layout of
+ * ea_batch_row_offsets in STORAGE order, rows of terms untouched, a problem without points contributes none (zero stats);
+ * cls_dev is device memory of the batch's device.  stats: count entries (nullable in the batch forms).  Same bytes, counts and
+ * weight bits on every run, whichever batch a problem sits in.
+ * EA_ERR_INVALID_ARG, before anything touches a device (and before a handle is looked at where only the parameters are
+ * wrong): a NULL argument, a b_T_a that ea_*_reproject refuses, radius outside 0..3, a tolerance or weight factor that is
+ * negative, NaN or infinite, a weight factor that overflows float for an fp32 problem, a capacity that is too small, with
+ * apply the same problem twice in the batch (its weights can be written once per call), a cls_dev that is not device
+ * memory of the batch's device.
+ * EA_ERR_STATE: a problem without points (ea_problem_depth_gate only), DT image or now-depth; a now-depth whose extent differs
+ * from the DT extent (checked here, not by the setters); problems of one call that hold depth of different kinds.  In a batch
+ * a problem without depth fails the whole call before any launch.
+ * One launch and one synchronisation on the batch's stream serve a whole batch; the matrices go up in a small array of their
+ * own; no per-point data crosses the bus unless cls is asked for.
+ * Out of scope: gating inside ea_tracker_* / ea_tracker_batch_* (their pushed depth already lives in the frame workspace: the
+ * natural follow-up), gating of terms through the head, soft or continuous weights, any use of the depth as a residual. */
+typedef struct {
+  int radius;                 /* window half-width in pixels, 0..3 */
+  double abs_tol, rel_tol;    /* tol = abs_tol + rel_tol * bz, metres */
+  double w_occluded, w_free, w_unknown;   /* weight factors of the three non-consistent classes */
+  int apply;                  /* != 0: write the problem's weights */
+} ea_depth_gate_params;
+void ea_default_depth_gate_params(ea_depth_gate_params *prm);
+typedef struct { int64_t n, n_behind, n_outside, n_unknown, n_consistent, n_occluded, n_free; } ea_depth_gate_stats;
+enum { EA_GATE_BEHIND = 0, EA_GATE_OUTSIDE = 1, EA_GATE_UNKNOWN = 2, EA_GATE_CONSISTENT = 3, EA_GATE_OCCLUDED = 4, EA_GATE_FREE = 5 };
+int ea_problem_depth_gate(ea_problem *p, const double b_T_a[16], const ea_depth_gate_params *prm,
+                          uint8_t *cls /* n, caller's order, nullable */, int64_t capacity, ea_depth_gate_stats *stats);
+int ea_batch_depth_gate(ea_batch *b, const double *b_T_a /* count x 16 */, const ea_depth_gate_params *prm,
+                        uint8_t *cls /* rows layout, nullable */, int64_t capacity_rows, ea_depth_gate_stats *stats /* count, nullable */);
+int ea_batch_depth_gate_device(ea_batch *b, const double *b_T_a, const ea_depth_gate_params *prm,
+                               uint8_t *cls_dev, int64_t capacity_rows, ea_depth_gate_stats *stats);
+
 /* ceres::Solve(options, &problem, &summary) (standalone_edge_align.cpp:286; SolveEA.cpp:198).
  * q,t in/out.  The whole trust-region loop runs on the device. */
 int ea_solve(ea_problem *p, const ea_options *opt, double q[4], double t[3], ea_summary *summary);
