@@ -1,6 +1,6 @@
 // ea_capi.hip — host driver behind include/ea_hip.h: HBM residency, tile lists, launches,
-// the device-resident trust-region loop, and the measurement hooks (frame producers and tracker: ea_frames.hip; what the two
-// files share: ea_capi_internal.h).  No CPU compute fallback:
+// the device-resident trust-region loop, and the measurement hooks (frame producers and tracker: ea_frames.hip; the calls that
+// run one segment per problem: ea_segments.hip; what the three files share: ea_capi_internal.h).  No CPU compute fallback:
 // without a gfx950 device every compute entry point returns EA_ERR_NO_DEVICE.
 
 #include <hip/hip_runtime.h>
@@ -153,8 +153,7 @@ void ea::cached_free(void *p) {
   (void)hipFree(p);
 }
 
-namespace {
-hipError_t cached_host_malloc(void **out, size_t bytes, unsigned flags, int device) {
+hipError_t ea::cached_host_malloc(void **out, size_t bytes, unsigned flags, int device) {
   *out = nullptr;
   if (bytes == 0) bytes = 64;
   ResourceCache &c = cache();
@@ -179,7 +178,7 @@ hipError_t cached_host_malloc(void **out, size_t bytes, unsigned flags, int devi
   return hipSuccess;
 }
 
-void cached_host_free(void *p) {
+void ea::cached_host_free(void *p) {
   if (!p) return;
   ResourceCache &c = cache();
   {
@@ -198,7 +197,7 @@ void cached_host_free(void *p) {
   (void)hipHostFree(p);
 }
 
-hipError_t cached_stream_create(hipStream_t *out, int device) {
+hipError_t ea::cached_stream_create(hipStream_t *out, int device) {
   ResourceCache &c = cache();
   {
     std::lock_guard<std::mutex> g(c.mu);
@@ -212,7 +211,7 @@ hipError_t cached_stream_create(hipStream_t *out, int device) {
   return hipStreamCreateWithFlags(out, hipStreamNonBlocking);
 }
 
-void cached_stream_destroy(hipStream_t s, int device) {  // (the caller has synchronised it)
+void ea::cached_stream_destroy(hipStream_t s, int device) {  // (the caller has synchronised it)
   if (!s) return;
   ResourceCache &c = cache();
   {
@@ -222,6 +221,7 @@ void cached_stream_destroy(hipStream_t s, int device) {  // (the caller has sync
   (void)hipStreamDestroy(s);
 }
 
+namespace {
 void release_cached_memory_locked_free() {
   ResourceCache &c = cache();
   std::vector<CachedBlock> dev, pinned;
@@ -812,7 +812,7 @@ extern "C" int ea_problem_set_points_device(ea_problem *p, const void *x, const 
 // borrowed point arrays (ea_problem_set_points_device) into arrays the problem owns: the weights live behind z.  Copied by a
 // kernel: the caller's arrays may belong to another HIP runtime in the process (check_device_pointer), whose pointers this
 // runtime's hipMemcpy does not know.
-static int own_borrowed_points(ea_problem *p) {
+int ea::own_borrowed_points(ea_problem *p) {
   if (p->own_points || p->n == 0) return EA_OK;
   const void *x = p->d_x, *y = p->d_y, *z = p->d_z;
   const int64_t n = p->n;
@@ -1185,12 +1185,6 @@ extern "C" void *ea_internal_batch_stream(ea_batch *b, int *device) {
   return b ? (void *)b->stream : nullptr;
 }
 
-void ea::batch_members(ea_batch *b, ea_problem *const **probs, int *count, int *device) {
-  *probs = b->probs.data();
-  *count = (int)b->probs.size();
-  *device = b->device;
-}
-
 int ea::batch_frames_reserve(ea_batch *b, size_t device_bytes, size_t pinned_bytes, unsigned char **device_block,
                              unsigned char **pinned_block) {
   if (b->frames_bytes < device_bytes) {
@@ -1485,12 +1479,45 @@ static int batch_launch_eval(ea_batch *b, const PoseState *poses = nullptr) {
   return EA_OK;
 }
 
-static int batch_upload_poses(ea_batch *b, const double *q, const double *t) {
+int ea::batch_upload_poses(ea_batch *b, const double *q, const double *t, const PoseState **d_poses) {
   const int count = (int)b->probs.size();
   for (int i = 0; i < count; ++i) host_pose_state(b->probs[i], q + 4 * i, t + 3 * i, &b->h_poses[i]);
   HIPCHK(hipMemcpyAsync(b->d_poses, b->h_poses, count * sizeof(PoseState), hipMemcpyHostToDevice, b->stream));
   b->poses_uploaded = true;
   b->poses_staged = false;
+  if (d_poses) *d_poses = b->d_poses;
+  return EA_OK;
+}
+
+// ---- what ea_frames.hip and ea_segments.hip see of a batch (ea_capi_internal.h; batch_frames_*: further up) ------------------
+
+BatchView ea::batch_view(ea_batch *b) {
+  BatchView v;
+  v.device = b->device; v.dtype = b->dtype; v.stream = b->stream; v.probs = b->probs.data(); v.count = (int)b->probs.size();
+  return v;
+}
+
+int ea::batch_built(ea_batch *b, BatchView *v) {
+  int rc = batch_build(b);
+  if (rc != EA_OK) return rc;
+  *v = batch_view(b);
+  v->nterms = b->nterms; v->d_probs = b->d_probs; v->total_rows = b->total_rows;
+  // (batch_build's staging block: the descriptors and groups of the current build)
+  v->h_desc = reinterpret_cast<const ProblemDesc *>(b->h_desc);
+  v->h_groups = reinterpret_cast<const GroupDesc *>(b->h_desc + (size_t)b->nterms * sizeof(ProblemDesc));
+  return EA_OK;
+}
+
+int ea::batch_gate_reserve(ea_batch *b, size_t bytes, unsigned char **device_block, unsigned char **pinned_block) {
+  if (b->gate_bytes < bytes) {
+    cached_free(b->d_gate); cached_host_free(b->h_gate);
+    b->d_gate = b->h_gate = nullptr; b->gate_bytes = 0;
+    HIPCHK(cached_malloc(reinterpret_cast<void **>(&b->d_gate), bytes, b->device));
+    HIPCHK(cached_host_malloc(reinterpret_cast<void **>(&b->h_gate), bytes, hipHostMallocDefault, b->device));
+    b->gate_bytes = bytes;
+  }
+  *device_block = b->d_gate;
+  *pinned_block = b->h_gate;
   return EA_OK;
 }
 
@@ -2473,269 +2500,6 @@ static int solve_lookahead(SolveRun &r, const ea_options &o, Enqueue &enqueue_it
 
 // Sub-batches for the concurrent solve: contiguous slices of the parent's problems, each with its own stream and
 // buffers, created on first use and kept.
-// ---- exact order statistics of |r| (ea_select.h; kernels: ea_select_*_kernel) ------------------------------------------
-//
-// One launch sequence per call, whatever the number of problems: clear, key pass, six (histogram, scan) pairs -- 14 launches --
-// on the batch's stream, the bin choice staying on the device between the passes; segments and probabilities go up, values and
-// valid counts come back through one pinned block, ONE synchronisation at the end.
-namespace {
-struct SelectBuffers {
-  DevBuf dev;
-  unsigned char *pinned = nullptr;
-  SelectWork w;
-  double *d_input = nullptr;          // ea_selftest_select: the caller's values
-  size_t up_bytes = 0, down_off = 0, down_bytes = 0;  // pinned: [segs | probs || values | n_valid]; the device block starts alike
-  SelectSeg *h_segs = nullptr;
-  double *h_probs = nullptr, *h_values = nullptr;
-  int64_t *h_n_valid = nullptr;
-  ~SelectBuffers() { cached_host_free(pinned); }
-};
-size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
-}  // namespace
-
-static int select_reserve(SelectBuffers &s, int device, int nseg, int nq, int64_t total_keys, bool with_input) {
-  const size_t sq = (size_t)nseg * nq;
-  const size_t o_segs = 0, o_probs = o_segs + align16((size_t)nseg * sizeof(SelectSeg)), o_vals = o_probs + align16((size_t)nq * 8);
-  const size_t o_nv64 = o_vals + align16(sq * 8), o_prefix = o_nv64 + align16((size_t)nseg * 8), o_rank = o_prefix + align16(sq * 8);
-  const size_t o_nvalid = o_rank + align16(sq * 8), o_hist = o_nvalid + align16((size_t)nseg * 4);
-  const size_t o_keys = o_hist + sq * kSelectBins * sizeof(unsigned), o_input = o_keys + align16((size_t)total_keys * 8);
-  const size_t bytes = o_input + (with_input ? align16((size_t)total_keys * 8) : 0);
-  HIPCHK(cached_malloc(&s.dev.p, bytes, device));
-  HIPCHK(cached_host_malloc(reinterpret_cast<void **>(&s.pinned), o_prefix, hipHostMallocDefault, device));
-  unsigned char *d = s.dev.as<unsigned char>();
-  s.up_bytes = o_vals; s.down_off = o_vals; s.down_bytes = o_prefix - o_vals;
-  s.h_segs = reinterpret_cast<SelectSeg *>(s.pinned + o_segs);
-  s.h_probs = reinterpret_cast<double *>(s.pinned + o_probs);
-  s.h_values = reinterpret_cast<double *>(s.pinned + o_vals);
-  s.h_n_valid = reinterpret_cast<int64_t *>(s.pinned + o_nv64);
-  SelectWork &w = s.w;
-  w.nseg = nseg; w.nq = nq;
-  w.segs = reinterpret_cast<const SelectSeg *>(d + o_segs);
-  w.probs = reinterpret_cast<const double *>(d + o_probs);
-  w.out_values = reinterpret_cast<double *>(d + o_vals);
-  w.out_n_valid = reinterpret_cast<int64_t *>(d + o_nv64);
-  w.prefix = reinterpret_cast<uint64_t *>(d + o_prefix);
-  w.rank = reinterpret_cast<int64_t *>(d + o_rank);
-  w.n_valid = reinterpret_cast<unsigned *>(d + o_nvalid);
-  w.hist = reinterpret_cast<unsigned *>(d + o_hist);
-  w.clear_bytes = o_keys - o_nvalid;
-  w.keys = reinterpret_cast<uint64_t *>(d + o_keys);
-  s.d_input = with_input ? reinterpret_cast<double *>(d + o_input) : nullptr;
-  return EA_OK;
-}
-
-// segments and probabilities up, the counts cleared: what comes before either key pass
-static int select_begin(SelectBuffers &s, const double *probs, hipStream_t stream) {
-  int max_n = 0;
-  for (int i = 0; i < s.w.nseg; ++i) max_n = std::max(max_n, (int)s.h_segs[i].n);
-  s.w.max_n = max_n;
-  for (int i = 0; i < s.w.nq; ++i) s.h_probs[i] = probs[i];
-  HIPCHK(hipMemcpyAsync(s.dev.p, s.pinned, s.up_bytes, hipMemcpyHostToDevice, stream));
-  HIPCHK(launch_select_clear(s.w, stream));
-  return EA_OK;
-}
-
-// the six passes, the results down, the call's one synchronisation
-static int select_finish(SelectBuffers &s, hipStream_t stream, double *values, int64_t *n_valid) {
-  HIPCHK(launch_select(s.w, stream));
-  HIPCHK(hipMemcpyAsync(s.pinned + s.down_off, s.dev.as<unsigned char>() + s.down_off, s.down_bytes, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipStreamSynchronize(stream));
-  std::memcpy(values, s.h_values, (size_t)s.w.nseg * s.w.nq * sizeof(double));
-  if (n_valid) std::memcpy(n_valid, s.h_n_valid, (size_t)s.w.nseg * sizeof(int64_t));
-  return EA_OK;
-}
-
-static int check_quantile_args(const double *probs, int nq) {
-  if (!probs) return fail(EA_ERR_INVALID_ARG, "NULL argument");
-  if (nq < 1 || nq > kSelectMaxQ) return fail(EA_ERR_INVALID_ARG, "nq must be in 1..16");
-  for (int i = 0; i < nq; ++i)
-    if (!select_prob_ok(probs[i])) return fail(EA_ERR_INVALID_ARG, "every prob must be in [0, 1]");
-  return EA_OK;
-}
-
-// the quantiles of the head families of problems sel[0 .. nsel) (sel == NULL: all of them) at the batch's poses q, t
-// (count x 4, count x 3: the poses of ALL problems of the batch); values: nsel x nq, n_valid: nsel or NULL
-static int batch_quantiles(ea_batch *b, const double *q, const double *t, const int *sel, int nsel, const double *probs, int nq,
-                           double *values, int64_t *n_valid) {
-  int rc = batch_build(b);
-  if (rc != EA_OK) return rc;
-  if (nsel > 65535) return fail(EA_ERR_INVALID_ARG, "more than 65535 problems in one quantile call");
-  SelectBuffers s;
-  if ((rc = select_reserve(s, b->device, nsel, nq, b->total_rows, false)) != EA_OK) return rc;
-  // (batch_build's staging block: the descriptors and groups of the current build)
-  const ProblemDesc *hd = reinterpret_cast<const ProblemDesc *>(b->h_desc);
-  const GroupDesc *hg = reinterpret_cast<const GroupDesc *>(b->h_desc + (size_t)b->nterms * sizeof(ProblemDesc));
-  for (int j = 0; j < nsel; ++j) {
-    const int term = hg[sel ? sel[j] : j].term_begin;  // the head family; its terms are not included
-    s.h_segs[j] = SelectSeg{hd[term].row_begin, hd[term].n, term};
-  }
-  if ((rc = select_begin(s, probs, b->stream)) != EA_OK) return rc;
-  if ((rc = batch_upload_poses(b, q, t)) != EA_OK) return rc;  // (d_poses: the resident poses of ea_batch_set_poses live elsewhere)
-  HIPCHK(launch_select_keys(b->dtype, s.w, b->d_probs, b->d_poses, b->stream));
-  return select_finish(s, b->stream, values, n_valid);
-}
-
-static int require_device();
-extern "C" int ea_batch_residual_quantiles(ea_batch *b, const double *q, const double *t, const double *probs, int nq,
-                                           double *values, int64_t *n_valid) {
-  if (!b || !q || !t || !values) return fail(EA_ERR_INVALID_ARG, "NULL argument");
-  int rc = check_quantile_args(probs, nq);
-  if (rc == EA_OK) rc = require_device();
-  if (rc != EA_OK) return rc;
-  return batch_quantiles(b, q, t, nullptr, (int)b->probs.size(), probs, nq, values, n_valid);
-}
-
-static int self_batch(ea_problem *p, ea_batch **out);
-extern "C" int ea_problem_residual_quantiles(ea_problem *p, const double q[4], const double t[3], const double *probs, int nq,
-                                             double *values, int64_t *n_valid) {
-  if (!p || !q || !t || !values) return fail(EA_ERR_INVALID_ARG, "NULL argument");
-  int rc = check_quantile_args(probs, nq);
-  if (rc == EA_OK) rc = require_device();
-  if (rc != EA_OK) return rc;
-  ea_batch *b;
-  if ((rc = self_batch(p, &b)) != EA_OK) return rc;
-  if ((rc = batch_build(b)) != EA_OK) return rc;  // (no DT image: EA_ERR_STATE, as ea_eval)
-  if (p->n == 0) return fail(EA_ERR_STATE, "no edge points (ea_problem_set_points)");
-  return batch_quantiles(b, q, t, nullptr, 1, probs, nq, values, n_valid);
-}
-
-// ---- how much of a reference is seen at a pose (ea_pose_stats; kernels: ea_pose_stats_kernel and its fold) ----------------
-//
-// Segments and poses up, the two launches, the rows down through one pinned block, ONE synchronisation: all on the batch's
-// stream.  The poses go through d_poses, like the quantiles': the resident poses of ea_batch_set_poses live elsewhere.
-static_assert(sizeof(PoseStatsRow) == sizeof(ea_pose_stats), "the fold writes ea_pose_stats as it stands");
-static int check_pose_stats_args(int margin, double inlier_residual) {
-  if (margin < 0) return fail(EA_ERR_INVALID_ARG, "margin must be >= 0");
-  if (!(inlier_residual >= 0.0)) return fail(EA_ERR_INVALID_ARG, "inlier_residual must be >= 0 (+Inf is allowed)");
-  return EA_OK;
-}
-
-static int batch_pose_stats(ea_batch *b, const double *q, const double *t, int margin, double inlier_residual, ea_pose_stats *out) {
-  int rc = batch_build(b);
-  if (rc != EA_OK) return rc;
-  const int nseg = (int)b->probs.size();
-  if (nseg > 65535) return fail(EA_ERR_INVALID_ARG, "more than 65535 problems in one statistics call");
-  const ProblemDesc *hd = reinterpret_cast<const ProblemDesc *>(b->h_desc);
-  const GroupDesc *hg = reinterpret_cast<const GroupDesc *>(b->h_desc + (size_t)b->nterms * sizeof(ProblemDesc));
-  const size_t o_segs = 0, o_out = o_segs + align16((size_t)nseg * sizeof(SelectSeg));
-  const size_t o_parts = o_out + align16((size_t)nseg * sizeof(PoseStatsRow));
-  struct Pinned {
-    unsigned char *p = nullptr;
-    ~Pinned() { cached_host_free(p); }
-  } pinned;
-  HIPCHK(cached_host_malloc(reinterpret_cast<void **>(&pinned.p), o_parts, hipHostMallocDefault, b->device));
-  SelectSeg *h_segs = reinterpret_cast<SelectSeg *>(pinned.p + o_segs);
-  int64_t rows = 0;
-  int max_n = 0;
-  for (int j = 0; j < nseg; ++j) {
-    const int term = hg[j].term_begin;  // the head family; its terms are not included
-    h_segs[j] = SelectSeg{rows, hd[term].n, term};
-    rows += pose_stats_rows(hd[term].n);
-    max_n = std::max(max_n, (int)hd[term].n);
-  }
-  DevBuf dev;
-  HIPCHK(cached_malloc(&dev.p, o_parts + (size_t)std::max<int64_t>(rows, 1) * sizeof(PoseStatsPartial), b->device));
-  unsigned char *d = dev.as<unsigned char>();
-  PoseStatsWork w;
-  w.nseg = nseg; w.max_n = max_n; w.margin = margin; w.inlier_residual = inlier_residual;
-  w.segs = reinterpret_cast<const SelectSeg *>(d + o_segs);
-  w.out = reinterpret_cast<PoseStatsRow *>(d + o_out);
-  w.partials = reinterpret_cast<PoseStatsPartial *>(d + o_parts);
-  HIPCHK(hipMemcpyAsync(d, pinned.p, o_out, hipMemcpyHostToDevice, b->stream));
-  if ((rc = batch_upload_poses(b, q, t)) != EA_OK) return rc;
-  HIPCHK(launch_pose_stats(b->dtype, w, b->d_probs, b->d_poses, b->stream));
-  HIPCHK(hipMemcpyAsync(pinned.p + o_out, d + o_out, (size_t)nseg * sizeof(PoseStatsRow), hipMemcpyDeviceToHost, b->stream));
-  HIPCHK(hipStreamSynchronize(b->stream));
-  std::memcpy(out, pinned.p + o_out, (size_t)nseg * sizeof(ea_pose_stats));
-  return EA_OK;
-}
-
-extern "C" int ea_batch_pose_stats(ea_batch *b, const double *q, const double *t, int margin, double inlier_residual,
-                                   ea_pose_stats *out) {
-  if (!b || !q || !t || !out) return fail(EA_ERR_INVALID_ARG, "NULL argument");
-  int rc = check_pose_stats_args(margin, inlier_residual);
-  if (rc == EA_OK) rc = require_device();
-  if (rc != EA_OK) return rc;
-  return batch_pose_stats(b, q, t, margin, inlier_residual, out);
-}
-
-extern "C" int ea_problem_pose_stats(ea_problem *p, const double q[4], const double t[3], int margin, double inlier_residual,
-                                     ea_pose_stats *out) {
-  if (!p || !q || !t || !out) return fail(EA_ERR_INVALID_ARG, "NULL argument");
-  int rc = check_pose_stats_args(margin, inlier_residual);
-  if (rc == EA_OK) rc = require_device();
-  if (rc != EA_OK) return rc;
-  ea_batch *b;
-  if ((rc = self_batch(p, &b)) != EA_OK) return rc;
-  if ((rc = batch_build(b)) != EA_OK) return rc;  // (no DT image: EA_ERR_STATE, as ea_eval)
-  if (p->n == 0) return fail(EA_ERR_STATE, "no edge points (ea_problem_set_points)");
-  return batch_pose_stats(b, q, t, margin, inlier_residual, out);
-}
-
-// the select kernels alone, on the caller's values
-extern "C" int ea_selftest_select(int device, const double *values, const int64_t *offsets, int nseg, const double *probs, int nq,
-                                  double *out, int64_t *n_valid) {
-  if (!offsets || !out || nseg < 1 || nseg > 65535) return fail(EA_ERR_INVALID_ARG, "bad argument");
-  int rc = check_quantile_args(probs, nq);
-  if (rc != EA_OK) return rc;
-  if (offsets[0] < 0) return fail(EA_ERR_INVALID_ARG, "offsets must start at >= 0 and not decrease");
-  for (int i = 0; i < nseg; ++i)
-    if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > 0x7fffff00LL)
-      return fail(EA_ERR_INVALID_ARG, "offsets must not decrease (at most 2^31 values per segment)");
-  const int64_t total = offsets[nseg];
-  if (total > 0 && !values) return fail(EA_ERR_INVALID_ARG, "NULL argument");
-  if ((rc = check_device(device)) != EA_OK) return rc;
-  HIPCHK(hipSetDevice(device));
-  SelectBuffers s;
-  if ((rc = select_reserve(s, device, nseg, nq, total, true)) != EA_OK) return rc;
-  for (int i = 0; i < nseg; ++i) s.h_segs[i] = SelectSeg{offsets[i], (int32_t)(offsets[i + 1] - offsets[i]), 0};
-  hipStream_t stream = nullptr;
-  HIPCHK(cached_stream_create(&stream, device));
-  rc = select_begin(s, probs, stream);
-  hipError_t e = hipSuccess;
-  if (rc == EA_OK && total > 0) e = hipMemcpyAsync(s.d_input, values, (size_t)total * sizeof(double), hipMemcpyHostToDevice, stream);
-  if (rc == EA_OK && e == hipSuccess) e = launch_select_keys_values(s.w, s.d_input, stream);
-  if (rc == EA_OK && e == hipSuccess) rc = select_finish(s, stream, out, n_valid);
-  (void)hipStreamSynchronize(stream);
-  cached_stream_destroy(stream, device);
-  if (e != hipSuccess) return fail(EA_ERR_HIP, hipGetErrorString(e));
-  return rc;
-}
-
-// Auto-scaled losses (ea_problem_set_loss_auto_scale): ONE quantile call over the auto-scaled problems of the batch at their
-// start poses, then, per problem, what the caller could have done by hand: ea_problem_set_loss(kind, max(a_min, factor * Q)).
-// The trivial loss is left alone; a problem without a valid block (or a product that is not finite) keeps its scale.
-static int auto_scale_losses(ea_batch *b, const double *q, const double *t) {
-  std::vector<double> probs;
-  for (const ea_problem *p : b->probs)
-    if (p->auto_factor > 0.0 && p->loss_kind != EA_LOSS_TRIVIAL && std::find(probs.begin(), probs.end(), p->auto_prob) == probs.end())
-      probs.push_back(p->auto_prob);
-  // (problems may ask for different probabilities: up to 16 of them share a call)
-  for (size_t first = 0; first < probs.size(); first += kSelectMaxQ) {
-    const int nq = (int)std::min<size_t>(kSelectMaxQ, probs.size() - first);
-    std::vector<int> sel, which;
-    for (size_t i = 0; i < b->probs.size(); ++i) {
-      const ea_problem *p = b->probs[i];
-      if (!(p->auto_factor > 0.0) || p->loss_kind == EA_LOSS_TRIVIAL) continue;
-      const size_t at = (size_t)(std::find(probs.begin(), probs.end(), p->auto_prob) - probs.begin());
-      if (at >= first && at < first + (size_t)nq) { sel.push_back((int)i); which.push_back((int)(at - first)); }
-    }
-    std::vector<double> values(sel.size() * (size_t)nq);
-    std::vector<int64_t> m(sel.size());
-    int rc = require_device();
-    if (rc == EA_OK) rc = batch_quantiles(b, q, t, sel.data(), (int)sel.size(), probs.data() + first, nq, values.data(), m.data());
-    if (rc != EA_OK) return rc;
-    for (size_t j = 0; j < sel.size(); ++j) {
-      ea_problem *p = b->probs[(size_t)sel[j]];
-      if (m[j] <= 0) continue;
-      const double a = select_loss_scale(p->auto_factor, values[j * (size_t)nq + (size_t)which[j]], p->auto_a_min);
-      if (!(a <= DBL_MAX) || a == p->loss_a) continue;
-      if ((rc = ea_problem_set_loss(p, p->loss_kind, a)) != EA_OK) return rc;
-    }
-  }
-  return EA_OK;
-}
-
 static int batch_parts(ea_batch *b, int parts) {
   if ((int)b->parts.size() == parts) return EA_OK;
   for (ea_batch *c : b->parts) ea_batch_destroy(c);
@@ -3159,15 +2923,16 @@ static int rows_own_buffers(ea_batch *b) {
 
 // a caller's device pointer: non-NULL, 16-byte aligned, and -- where this runtime knows the allocation -- device memory of
 // the batch's GPU.  (Memory of another HIP runtime in the same process, e.g. the storage of a PyTorch-ROCm tensor, is
-// unknown to hipPointerGetAttributes here although kernels can address it: such pointers are taken on trust.)
-static int check_device_pointer(const ea_batch *b, const void *ptr, const char *what) {
+// unknown to this runtime's pointer query although kernels can address it: such pointers are taken on trust; the calls that
+// refuse them ask device_memory_of, ea_segments.hip.)
+int ea::check_device_pointer(int device, const void *ptr, const char *what) {
   if (!ptr) return fail(EA_ERR_INVALID_ARG, std::string(what) + " is NULL");
   if (reinterpret_cast<uintptr_t>(ptr) % 16 != 0) return fail(EA_ERR_INVALID_ARG, std::string(what) + " must be 16-byte aligned");
   hipPointerAttribute_t at;
   const hipError_t e = hipPointerGetAttributes(&at, ptr);
   if (e != hipSuccess) { (void)hipGetLastError(); return EA_OK; }
   if (at.type == hipMemoryTypeHost) return fail(EA_ERR_INVALID_ARG, std::string(what) + " is host memory (device memory expected)");
-  if ((at.type == hipMemoryTypeDevice) && at.device != b->device)
+  if ((at.type == hipMemoryTypeDevice) && at.device != device)
     return fail(EA_ERR_INVALID_ARG, std::string(what) + " lives on another device than the batch");
   return EA_OK;
 }
@@ -3189,8 +2954,8 @@ static int rows_prepare(ea_batch *b, const double *q, const double *t, int layou
   if ((*r_dev == nullptr) != (*J_dev == nullptr)) return fail(EA_ERR_INVALID_ARG, "r_dev and J_dev: both or neither");
   if (*r_dev) {
     if (capacity_rows < b->total_rows) return fail(EA_ERR_INVALID_ARG, "capacity_rows is smaller than the batch's row count (ea_batch_row_offsets)");
-    if ((rc = check_device_pointer(b, *r_dev, "r_dev")) != EA_OK) return rc;
-    if ((rc = check_device_pointer(b, *J_dev, "J_dev")) != EA_OK) return rc;
+    if ((rc = check_device_pointer(b->device, *r_dev, "r_dev")) != EA_OK) return rc;
+    if ((rc = check_device_pointer(b->device, *J_dev, "J_dev")) != EA_OK) return rc;
   } else {
     if ((rc = rows_own_buffers(b)) != EA_OK) return rc;
     *r_dev = b->d_rows_r; *J_dev = b->d_rows_J;
@@ -3345,6 +3110,14 @@ static int self_batch(ea_problem *p, ea_batch **out) {
   return EA_OK;
 }
 
+int ea::problem_call_batch(ea_problem *p, ea_batch **b, bool build) {
+  int rc = self_batch(p, b);
+  if (rc == EA_OK && build) rc = batch_build(*b);  // (no DT image: EA_ERR_STATE, as ea_eval)
+  if (rc != EA_OK) return rc;
+  if (p->n == 0) return fail(EA_ERR_STATE, "no edge points (ea_problem_set_points)");
+  return EA_OK;
+}
+
 extern "C" int ea_eval(ea_problem *p, const double q[4], const double t[3], double *cost, double JtJ[36],
                        double Jtr[6], int64_t *n_invalid) {
   ea_batch *b;
@@ -3441,14 +3214,14 @@ int ea::check_cov_options(const ea_covariance_options *o) {
 }
 
 // no problem or batch exists without a device; this answers the "no device" question before a handle is dereferenced
-static int require_device() {
+int ea::require_device() {
   int cnt = 0;
   if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0)
     return fail(EA_ERR_NO_DEVICE, "no HIP device available (libea_hip has no CPU fallback)");
   return EA_OK;
 }
 
-static int64_t problem_points(const ea_problem *p) {
+int64_t ea::problem_points(const ea_problem *p) {
   int64_t n = p->n;
   for (const ea_problem *t : p->terms) n += t->n;
   return n;
@@ -3561,6 +3334,12 @@ extern "C" int ea_problem_pixel_cost(ea_problem *p, const double q[4], const dou
   return EA_OK;
 }
 
+void ea::scatter_to_callers_order(const std::vector<int32_t> &order, size_t elem_bytes, const void *tmp, void *out) {
+  const unsigned char *src = static_cast<const unsigned char *>(tmp);
+  unsigned char *dst = static_cast<unsigned char *>(out);
+  for (size_t i = 0; i < order.size(); ++i) std::memcpy(dst + (size_t)order[i] * elem_bytes, src + i * elem_bytes, elem_bytes);
+}
+
 extern "C" int ea_eval_points(ea_problem *p, const double q[4], const double t[3], double *r, double *J, int corrected) {
   if (!q || !t) return fail(EA_ERR_INVALID_ARG, "NULL argument");
   ea_batch *b;
@@ -3577,582 +3356,14 @@ extern "C" int ea_eval_points(ea_problem *p, const double q[4], const double t[3
   double *d_r = buf_r.as<double>(), *d_J = buf_J.as<double>();
   hipError_t e = launch_eval_points(p->dtype, b->d_probs, 0, (int)p->n, b->d_poses, d_r, d_J, corrected, b->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
-  if (p->order.empty()) {
-    if (e == hipSuccess && r) e = hipMemcpy(r, d_r, p->n * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && J) e = hipMemcpy(J, d_J, p->n * 6 * sizeof(double), hipMemcpyDeviceToHost);
-  } else {  // stored in tile order: hand the rows back in the caller's order
-    std::vector<double> tmp((size_t)p->n * 6);
-    if (e == hipSuccess && r) {
-      e = hipMemcpy(tmp.data(), d_r, p->n * sizeof(double), hipMemcpyDeviceToHost);
-      if (e == hipSuccess)
-        for (int64_t i = 0; i < p->n; ++i) r[p->order[(size_t)i]] = tmp[(size_t)i];
-    }
-    if (e == hipSuccess && J) {
-      e = hipMemcpy(tmp.data(), d_J, p->n * 6 * sizeof(double), hipMemcpyDeviceToHost);
-      if (e == hipSuccess)
-        for (int64_t i = 0; i < p->n; ++i)
-          for (int a = 0; a < 6; ++a) J[(size_t)p->order[(size_t)i] * 6 + a] = tmp[(size_t)i * 6 + a];
-    }
+  std::vector<double> tmp(p->order.empty() ? 0 : (size_t)p->n * 6);  // (tile order: by way of tmp)
+  const struct { double *out; const double *dev; size_t elem; } rows[2] = {{r, d_r, sizeof(double)}, {J, d_J, 6 * sizeof(double)}};
+  for (const auto &w : rows) {
+    if (e != hipSuccess || !w.out) continue;
+    e = hipMemcpy(tmp.empty() ? w.out : tmp.data(), w.dev, (size_t)p->n * w.elem, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && !tmp.empty()) scatter_to_callers_order(p->order, w.elem, tmp.data(), w.out);
   }
   if (e != hipSuccess) return fail(EA_ERR_HIP, hipGetErrorString(e));
-  return EA_OK;
-}
-
-// ---- reprojection and overlay: reproject + s_overlay (ea_reproject.h; kernel: ea_reproject_kernel) -----------------------
-//
-// One segment per problem of the call (its head family) with the 3x4 matrix of step A, built here; segments and zeroed
-// counters go up in ONE copy from a pinned block, ONE launch, the counters (overlay) come back into the same block, ONE
-// synchronisation: all on the batch's stream.  The matrices travel in the segments: d_poses is not written, and no problem
-// changes, so resident poses (ea_batch_set_poses) survive.
-extern "C" int ea_pose_to_matrix(const double q[4], const double t[3], double b_T_a[16]) {
-  if (!q || !t || !b_T_a) return fail(EA_ERR_INVALID_ARG, "NULL argument");
-  pose_to_matrix(q, t, b_T_a);
-  return EA_OK;
-}
-
-extern "C" int ea_matrix_to_pose(const double b_T_a[16], double q[4], double t[3]) {
-  if (!b_T_a || !q || !t) return fail(EA_ERR_INVALID_ARG, "NULL argument");
-  if (!matrix_to_pose(b_T_a, q, t)) return fail(EA_ERR_INVALID_ARG, "b_T_a[15] must be 1 (the reference's assert( T(3,3) == 1 ))");
-  return EA_OK;
-}
-
-namespace {
-struct ReprojectRun {
-  unsigned char *pinned = nullptr;
-  DevBuf dev;
-  int nseg = 0;
-  size_t o_counts = 0;
-  ~ReprojectRun() { cached_host_free(pinned); }
-  const ReprojectSeg *segs() const { return reinterpret_cast<const ReprojectSeg *>(pinned); }
-  const unsigned long long *counts() const { return reinterpret_cast<const unsigned long long *>(pinned + o_counts); }
-};
-}  // namespace
-
-static int check_reproject_poses(const double *b_T_a, int count) {
-  for (int i = 0; i < count; ++i)
-    if (!reproject_pose_ok(b_T_a + 16 * (size_t)i))
-      return fail(EA_ERR_INVALID_ARG, "b_T_a must be finite with the last row exactly 0 0 0 1");
-  return EA_OK;
-}
-
-// upload + launch (+ the counters on their way back) for a batch that is built; the caller queues what else must come down
-// and synchronises.  paint: images[i] = device image of problem i (H x W x 3)
-static int reproject_enqueue(ea_batch *b, const double *b_T_a, bool paint, double *uv_dev, unsigned char *const *images,
-                             const uint8_t color[3], ReprojectRun &run) {
-  const int nseg = (int)b->probs.size();
-  if (nseg > 65535) return fail(EA_ERR_INVALID_ARG, "more than 65535 problems in one reprojection call");
-  const ProblemDesc *hd = reinterpret_cast<const ProblemDesc *>(b->h_desc);  // (batch_build's staging block)
-  const GroupDesc *hg = reinterpret_cast<const GroupDesc *>(b->h_desc + (size_t)b->nterms * sizeof(ProblemDesc));
-  run.nseg = nseg;
-  run.o_counts = align16((size_t)nseg * sizeof(ReprojectSeg));
-  const size_t bytes = run.o_counts + (size_t)nseg * 2 * sizeof(unsigned long long);
-  HIPCHK(cached_host_malloc(reinterpret_cast<void **>(&run.pinned), bytes, hipHostMallocDefault, b->device));
-  std::memset(run.pinned, 0, bytes);
-  ReprojectSeg *h_segs = reinterpret_cast<ReprojectSeg *>(run.pinned);
-  int max_n = 0;
-  for (int j = 0; j < nseg; ++j) {
-    const ea_problem *p = b->probs[(size_t)j];
-    const int term = hg[j].term_begin;  // the head family; its terms are not included
-    ReprojectSeg &sg = h_segs[j];
-    sg.row = hd[term].row_begin; sg.n = hd[term].n; sg.term = term;
-    const bool rig = (p->variant & 2) != 0;
-    reproject_matrix(b_T_a + 16 * (size_t)j, rig ? p->T12 : nullptr, rig ? p->T12inv : nullptr, sg.M);
-    sg.image = paint ? images[j] : nullptr;
-    max_n = std::max(max_n, (int)sg.n);
-  }
-  HIPCHK(cached_malloc(&run.dev.p, bytes, b->device));
-  unsigned char *d = run.dev.as<unsigned char>();
-  HIPCHK(hipMemcpyAsync(d, run.pinned, bytes, hipMemcpyHostToDevice, b->stream));
-  ReprojectWork w;
-  w.nseg = nseg; w.max_n = max_n; w.paint = paint ? 1 : 0;
-  w.color = color ? ((unsigned)color[0] | ((unsigned)color[1] << 8) | ((unsigned)color[2] << 16)) : (255u << 16);  // NULL: upstream's red
-  w.segs = reinterpret_cast<const ReprojectSeg *>(d);
-  w.uv = uv_dev;
-  w.counts = reinterpret_cast<unsigned long long *>(d + run.o_counts);
-  HIPCHK(launch_reproject(b->dtype, w, b->d_probs, b->stream));
-  if (paint)
-    HIPCHK(hipMemcpyAsync(run.pinned + run.o_counts, d + run.o_counts, bytes - run.o_counts, hipMemcpyDeviceToHost, b->stream));
-  return EA_OK;
-}
-
-static void reproject_stats(const ReprojectRun &run, ea_overlay_stats *stats) {
-  if (!stats) return;
-  for (int j = 0; j < run.nseg; ++j) {
-    stats[j].n = run.segs()[j].n;
-    stats[j].inside = (int64_t)run.counts()[2 * j];
-    stats[j].outside = (int64_t)run.counts()[2 * j + 1];
-  }
-}
-
-// rows of the batch's layout (ea_batch_row_offsets) as the problems stand, without a device
-static int64_t batch_rows_host(const ea_batch *b) {
-  int64_t rows = 0;
-  for (const ea_problem *p : b->probs) rows += problem_points(p);
-  return rows;
-}
-
-static int batch_reproject_checks(ea_batch *b, const double *b_T_a, const void *uv, int64_t capacity_rows) {
-  if (!b || !b_T_a || !uv) return fail(EA_ERR_INVALID_ARG, "NULL argument");
-  int rc = check_reproject_poses(b_T_a, (int)b->probs.size());
-  if (rc != EA_OK) return rc;
-  if (capacity_rows < batch_rows_host(b)) return fail(EA_ERR_INVALID_ARG, "capacity_rows is smaller than the batch's row count (ea_batch_row_offsets)");
-  return require_device();
-}
-
-extern "C" int ea_batch_reproject_device(ea_batch *b, const double *b_T_a, double *uv_dev, int64_t capacity_rows) {
-  int rc = batch_reproject_checks(b, b_T_a, uv_dev, capacity_rows);
-  if (rc != EA_OK) return rc;
-  if ((rc = batch_build(b)) != EA_OK) return rc;
-  if ((rc = check_device_pointer(b, uv_dev, "uv_dev")) != EA_OK) return rc;
-  ReprojectRun run;
-  if ((rc = reproject_enqueue(b, b_T_a, false, uv_dev, nullptr, nullptr, run)) != EA_OK) return rc;
-  HIPCHK(hipStreamSynchronize(b->stream));  // the rows are complete (and visible to any other stream) when this returns
-  return EA_OK;
-}
-
-extern "C" int ea_batch_reproject(ea_batch *b, const double *b_T_a, double *uv, int64_t capacity_rows) {
-  int rc = batch_reproject_checks(b, b_T_a, uv, capacity_rows);
-  if (rc != EA_OK) return rc;
-  if ((rc = batch_build(b)) != EA_OK) return rc;
-  DevBuf rows;
-  HIPCHK(cached_malloc(&rows.p, (size_t)b->total_rows * 2 * sizeof(double), b->device));
-  ReprojectRun run;
-  if ((rc = reproject_enqueue(b, b_T_a, false, rows.as<double>(), nullptr, nullptr, run)) != EA_OK) return rc;
-  // the head families' rows come down, adjacent ones in one copy; rows of terms stay as the caller left them
-  for (int j = 0; j < run.nseg;) {
-    const int64_t begin = run.segs()[j].row;
-    int64_t end = begin + run.segs()[j].n;
-    for (++j; j < run.nseg && run.segs()[j].row == end; ++j) end += run.segs()[j].n;
-    if (end > begin)
-      HIPCHK(hipMemcpyAsync(uv + 2 * begin, rows.as<double>() + 2 * begin, (size_t)(end - begin) * 2 * sizeof(double),
-                            hipMemcpyDeviceToHost, b->stream));
-  }
-  HIPCHK(hipStreamSynchronize(b->stream));
-  return EA_OK;
-}
-
-extern "C" int ea_problem_reproject(ea_problem *p, const double b_T_a[16], double *uv, int64_t capacity) {
-  if (!p || !b_T_a || !uv) return fail(EA_ERR_INVALID_ARG, "NULL argument");
-  int rc = check_reproject_poses(b_T_a, 1);
-  if (rc != EA_OK) return rc;
-  if (capacity < p->n) return fail(EA_ERR_INVALID_ARG, "capacity is smaller than ea_problem_num_points");
-  if ((rc = require_device()) != EA_OK) return rc;
-  ea_batch *b;
-  if ((rc = self_batch(p, &b)) != EA_OK) return rc;
-  if ((rc = batch_build(b)) != EA_OK) return rc;  // (no DT image: EA_ERR_STATE, as ea_eval)
-  if (p->n == 0) return fail(EA_ERR_STATE, "no edge points (ea_problem_set_points)");
-  DevBuf rows;
-  HIPCHK(cached_malloc(&rows.p, (size_t)p->n * 2 * sizeof(double), p->device));  // (the head family's rows start at 0)
-  ReprojectRun run;
-  if ((rc = reproject_enqueue(b, b_T_a, false, rows.as<double>(), nullptr, nullptr, run)) != EA_OK) return rc;
-  std::vector<double> tmp(p->order.empty() ? 0 : (size_t)p->n * 2);
-  double *dst = p->order.empty() ? uv : tmp.data();
-  HIPCHK(hipMemcpyAsync(dst, rows.p, (size_t)p->n * 2 * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-  HIPCHK(hipStreamSynchronize(b->stream));
-  for (size_t i = 0; i < tmp.size() / 2; ++i) {  // stored in tile order: hand the rows back in the caller's order
-    uv[2 * (size_t)p->order[i]] = tmp[2 * i];
-    uv[2 * (size_t)p->order[i] + 1] = tmp[2 * i + 1];
-  }
-  return EA_OK;
-}
-
-// what the three overlay forms check before a device is looked for; entries: the pointer arrays whose `count` entries must
-// not be NULL
-static int batch_overlay_checks(ea_batch *b, const double *b_T_a, const void *const *entries_a, const void *const *entries_b,
-                                int height, int width) {
-  if (!b || !b_T_a || !entries_a || !entries_b) return fail(EA_ERR_INVALID_ARG, "NULL argument");
-  if (height < 1 || width < 1) return fail(EA_ERR_INVALID_ARG, "height and width must be positive");
-  int rc = check_reproject_poses(b_T_a, (int)b->probs.size());
-  if (rc != EA_OK) return rc;
-  for (size_t i = 0; i < b->probs.size(); ++i)
-    if (!entries_a[i] || !entries_b[i]) return fail(EA_ERR_INVALID_ARG, "NULL entry in an image pointer array");
-  return require_device();
-}
-
-static int batch_overlay_extent(const ea_batch *b, int height, int width) {
-  for (const ea_problem *p : b->probs)
-    if (p->H != height || p->W != width)
-      return fail(EA_ERR_INVALID_ARG, "height, width must equal the extent of every problem's distance-transform image");
-  return EA_OK;
-}
-
-extern "C" int ea_batch_overlay_device(ea_batch *b, const double *b_T_a, uint8_t *const *bgr_dev, int height, int width,
-                                       const uint8_t color[3], ea_overlay_stats *stats) {
-  int rc = batch_overlay_checks(b, b_T_a, reinterpret_cast<const void *const *>(bgr_dev),
-                                reinterpret_cast<const void *const *>(bgr_dev), height, width);
-  if (rc != EA_OK) return rc;
-  if ((rc = batch_build(b)) != EA_OK) return rc;
-  if ((rc = batch_overlay_extent(b, height, width)) != EA_OK) return rc;
-  for (size_t i = 0; i < b->probs.size(); ++i) {
-    hipPointerAttribute_t at;
-    const hipError_t e = hipPointerGetAttributes(&at, bgr_dev[i]);
-    if (e != hipSuccess) (void)hipGetLastError();
-    if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.device != b->device)
-      return fail(EA_ERR_INVALID_ARG, "an entry of bgr_dev is not device memory of the batch's device");
-  }
-  ReprojectRun run;
-  if ((rc = reproject_enqueue(b, b_T_a, true, nullptr, bgr_dev, color, run)) != EA_OK) return rc;
-  HIPCHK(hipStreamSynchronize(b->stream));  // the images are complete (and visible to any other stream) when this returns
-  reproject_stats(run, stats);
-  return EA_OK;
-}
-
-extern "C" int ea_batch_overlay(ea_batch *b, const double *b_T_a, const uint8_t *const *bgr_in, int height, int width,
-                                const uint8_t color[3], uint8_t *const *bgr_out, ea_overlay_stats *stats) {
-  int rc = batch_overlay_checks(b, b_T_a, reinterpret_cast<const void *const *>(bgr_in),
-                                reinterpret_cast<const void *const *>(bgr_out), height, width);
-  if (rc != EA_OK) return rc;
-  if ((rc = batch_build(b)) != EA_OK) return rc;
-  if ((rc = batch_overlay_extent(b, height, width)) != EA_OK) return rc;
-  // the images go up into one cached device block, are painted there and come back
-  const size_t count = b->probs.size(), image_bytes = (size_t)height * (size_t)width * 3, stride = align16(image_bytes);
-  DevBuf images;
-  HIPCHK(cached_malloc(&images.p, count * stride, b->device));
-  std::vector<unsigned char *> d_images(count);
-  for (size_t i = 0; i < count; ++i) {
-    d_images[i] = images.as<unsigned char>() + i * stride;
-    HIPCHK(hipMemcpyAsync(d_images[i], bgr_in[i], image_bytes, hipMemcpyHostToDevice, b->stream));
-  }
-  ReprojectRun run;
-  if ((rc = reproject_enqueue(b, b_T_a, true, nullptr, d_images.data(), color, run)) != EA_OK) return rc;
-  for (size_t i = 0; i < count; ++i)
-    HIPCHK(hipMemcpyAsync(bgr_out[i], d_images[i], image_bytes, hipMemcpyDeviceToHost, b->stream));
-  HIPCHK(hipStreamSynchronize(b->stream));
-  reproject_stats(run, stats);
-  return EA_OK;
-}
-
-extern "C" int ea_problem_overlay(ea_problem *p, const double b_T_a[16], const uint8_t *bgr_in, int height, int width,
-                                  const uint8_t color[3], uint8_t *bgr_out, ea_overlay_stats *stats) {
-  if (!p || !b_T_a || !bgr_in || !bgr_out) return fail(EA_ERR_INVALID_ARG, "NULL argument");
-  if (height < 1 || width < 1) return fail(EA_ERR_INVALID_ARG, "height and width must be positive");
-  int rc = check_reproject_poses(b_T_a, 1);
-  if (rc == EA_OK) rc = require_device();
-  if (rc != EA_OK) return rc;
-  ea_batch *b;
-  if ((rc = self_batch(p, &b)) != EA_OK) return rc;
-  if ((rc = batch_build(b)) != EA_OK) return rc;  // (no DT image: EA_ERR_STATE, as ea_eval)
-  if (p->n == 0) return fail(EA_ERR_STATE, "no edge points (ea_problem_set_points)");
-  return ea_batch_overlay(b, b_T_a, &bgr_in, height, width, color, &bgr_out, stats);
-}
-
-// ---- depth-consistency gate (ea_depth_gate.h; kernel: ea_depth_gate_kernel) ------------------------------------------------
-//
-// The current frame's depth is held by the problem in its own kind (a cached block, copied as it came).  It is read by the
-// gate only -- no descriptor names it -- so setting it moves no version: batches do not rebuild, resident poses survive.
-static void now_depth_drop(ea_problem *p) {
-  if (p->d_now_depth) cached_free(p->d_now_depth);
-  p->d_now_depth = nullptr;
-  p->now_depth_cap = 0;
-  p->nd_kind = p->nd_H = p->nd_W = 0;
-  p->nd_z_scaling = 1.0;
-}
-
-static size_t now_depth_bytes(int kind, int height, int width) {
-  return (size_t)height * (size_t)width * (kind == EA_DEPTH_F32 ? sizeof(float) : sizeof(uint16_t));
-}
-
-// room for the image in the problem's block (the previous allocation when it fits and is not four times too large) and the
-// image's description; the samples are the caller's to copy
-static int now_depth_reserve(ea_problem *p, int kind, int height, int width, double z_scaling) {
-  const size_t need = now_depth_bytes(kind, height, width);
-  if (!(p->d_now_depth && p->now_depth_cap >= need && p->now_depth_cap <= 4 * need + 4096)) {
-    now_depth_drop(p);
-    HIPCHK(cached_malloc(&p->d_now_depth, need, p->device));
-    p->now_depth_cap = need;
-  }
-  p->nd_kind = kind; p->nd_H = height; p->nd_W = width;
-  p->nd_z_scaling = kind == EA_DEPTH_U16 ? z_scaling : 1.0;
-  return EA_OK;
-}
-
-// a depth image the caller says is in device memory: of this device, as far as the runtime can tell, aligned for its samples
-static int check_device_depth(const void *ptr, int device, int kind) {
-  if (reinterpret_cast<uintptr_t>(ptr) % (kind == EA_DEPTH_F32 ? 4 : 2) != 0) return fail(EA_ERR_INVALID_ARG, "depth_dev: misaligned image");
-  hipPointerAttribute_t at;
-  const hipError_t e = hipPointerGetAttributes(&at, ptr);
-  if (e != hipSuccess) (void)hipGetLastError();
-  if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.device != device)
-    return fail(EA_ERR_INVALID_ARG, "depth_dev is not device memory of the problem's device");
-  return EA_OK;
-}
-
-static int problem_set_now_depth(ea_problem *p, const void *depth, int kind, int height, int width, double z_scaling, bool on_device) {
-  if (!p) return fail(EA_ERR_INVALID_ARG, "NULL problem");
-  if (!depth) { now_depth_drop(p); return EA_OK; }
-  if (const char *why = now_depth_args_error(kind, height, width, z_scaling)) return fail(EA_ERR_INVALID_ARG, why);
-  int rc = require_device();
-  if (rc != EA_OK) return rc;
-  HIPCHK(hipSetDevice(p->device));
-  if (on_device && (rc = check_device_depth(depth, p->device, kind)) != EA_OK) return rc;
-  if ((rc = now_depth_reserve(p, kind, height, width, z_scaling)) != EA_OK) return rc;
-  hipError_t e = hipMemcpy(p->d_now_depth, depth, now_depth_bytes(kind, height, width),
-                           on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipDeviceSynchronize();  // (a device-to-device copy may return before it has run)
-  if (e != hipSuccess) {
-    now_depth_drop(p);
-    return fail(EA_ERR_HIP, std::string("ea_problem_set_now_depth: ") + hipGetErrorString(e));
-  }
-  return EA_OK;
-}
-
-extern "C" int ea_problem_set_now_depth(ea_problem *p, const void *depth, int kind, int height, int width, double z_scaling) {
-  return problem_set_now_depth(p, depth, kind, height, width, z_scaling, false);
-}
-
-extern "C" int ea_problem_set_now_depth_device(ea_problem *p, const void *depth_dev, int kind, int height, int width,
-                                               double z_scaling) {
-  return problem_set_now_depth(p, depth_dev, kind, height, width, z_scaling, true);
-}
-
-static bool batch_has_duplicates(const ea_batch *b) {
-  std::vector<const ea_problem *> sorted(b->probs.begin(), b->probs.end());
-  std::sort(sorted.begin(), sorted.end());
-  return std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end();
-}
-
-// N images, one per problem: the copies on the batch's stream, ONE wait
-static int batch_set_now_depth(ea_batch *b, const void *const *depth, int kind, int height, int width, double z_scaling, bool on_device) {
-  if (!b) return fail(EA_ERR_INVALID_ARG, "NULL batch");
-  if (!depth) {
-    for (ea_problem *p : b->probs) now_depth_drop(p);
-    return EA_OK;
-  }
-  if (const char *why = now_depth_args_error(kind, height, width, z_scaling)) return fail(EA_ERR_INVALID_ARG, why);
-  for (size_t i = 0; i < b->probs.size(); ++i)
-    if (!depth[i]) return fail(EA_ERR_INVALID_ARG, "NULL entry in the depth pointer array");
-  if (batch_has_duplicates(b))
-    return fail(EA_ERR_INVALID_ARG, "the same problem twice in the batch: each depth image needs a problem of its own");
-  int rc = require_device();
-  if (rc != EA_OK) return rc;
-  HIPCHK(hipSetDevice(b->device));
-  if (on_device)
-    for (size_t i = 0; i < b->probs.size(); ++i)
-      if ((rc = check_device_depth(depth[i], b->device, kind)) != EA_OK) return rc;
-  const size_t bytes = now_depth_bytes(kind, height, width);
-  hipError_t e = hipSuccess;
-  for (size_t i = 0; i < b->probs.size() && rc == EA_OK && e == hipSuccess; ++i) {
-    ea_problem *p = b->probs[i];
-    if ((rc = now_depth_reserve(p, kind, height, width, z_scaling)) != EA_OK) break;
-    e = hipMemcpyAsync(p->d_now_depth, depth[i], bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, b->stream);
-  }
-  const hipError_t es = hipStreamSynchronize(b->stream);
-  if (e == hipSuccess) e = es;
-  if (rc != EA_OK || e != hipSuccess) {  // no problem keeps an image that may be half written
-    for (ea_problem *p : b->probs) now_depth_drop(p);
-    return rc != EA_OK ? rc : fail(EA_ERR_HIP, std::string("ea_batch_set_now_depth: ") + hipGetErrorString(e));
-  }
-  return EA_OK;
-}
-
-extern "C" int ea_batch_set_now_depth(ea_batch *b, const void *const *depth, int kind, int height, int width, double z_scaling) {
-  return batch_set_now_depth(b, depth, kind, height, width, z_scaling, false);
-}
-
-extern "C" int ea_batch_set_now_depth_device(ea_batch *b, const void *const *depth_dev, int kind, int height, int width,
-                                             double z_scaling) {
-  return batch_set_now_depth(b, depth_dev, kind, height, width, z_scaling, true);
-}
-
-extern "C" void ea_default_depth_gate_params(ea_depth_gate_params *prm) {
-  if (!prm) return;
-  prm->radius = 1;
-  prm->abs_tol = 0.02; prm->rel_tol = 0.02;
-  prm->w_occluded = 0.0; prm->w_free = 0.0; prm->w_unknown = 1.0;
-  prm->apply = 1;
-}
-
-// The gate itself.  One segment per problem of the call (its head family) with the 3x4 matrix of step A; segments and zeroed
-// counters go up in ONE copy from a pinned block, ONE launch, the counters come back into the same block, ONE synchronisation:
-// all on the batch's stream.  The matrices travel in the segments: d_poses is not written.  With `apply` the kernel writes the
-// problems' weight storage in place; a problem that had no weights becomes a weighted one afterwards (its version moves: the
-// batches that hold it rebuild, as after ea_problem_set_weights), one that had keeps its version.
-namespace {
-struct DepthGateRun {
-  unsigned char *pinned = nullptr;  // (the batch's h_gate)
-  int nseg = 0;
-  size_t o_counts = 0;
-  const DepthGateSeg *segs() const { return reinterpret_cast<const DepthGateSeg *>(pinned); }
-  const unsigned long long *counts() const { return reinterpret_cast<const unsigned long long *>(pinned + o_counts); }
-};
-}  // namespace
-
-// what needs neither a handle nor a device
-static int depth_gate_params_check(const ea_depth_gate_params *prm) {
-  if (const char *why = depth_gate_params_error(prm)) return fail(EA_ERR_INVALID_ARG, why);
-  return EA_OK;
-}
-
-// what the problems of a call must be, read off the problems themselves: nothing has touched a device or changed a problem yet
-static int depth_gate_state_checks(const ea_batch *b, const ea_depth_gate_params *prm) {
-  if (b->probs.size() > 65535) return fail(EA_ERR_INVALID_ARG, "more than 65535 problems in one depth gate call");
-  if (!depth_gate_factors_fit(prm, b->dtype == EA_F32 ? (double)FLT_MAX : DBL_MAX))
-    return fail(EA_ERR_INVALID_ARG, "a weight factor overflows the float of an fp32 problem");
-  if (prm->apply && batch_has_duplicates(b))
-    return fail(EA_ERR_INVALID_ARG, "the same problem twice in the batch: its weights can be written once per call");
-  for (const ea_problem *p : b->probs) {
-    if (!p->d_dt) return fail(EA_ERR_STATE, "distance-transform image not set (ea_problem_set_dt)");
-    if (!p->d_now_depth) return fail(EA_ERR_STATE, "current-frame depth not set (ea_problem_set_now_depth)");
-    if (p->nd_H != p->H || p->nd_W != p->W)
-      return fail(EA_ERR_STATE, "the current-frame depth and the distance-transform image differ in extent");
-    if (p->nd_kind != b->probs[0]->nd_kind)
-      return fail(EA_ERR_STATE, "the problems of one depth gate call must hold depth of one kind");
-  }
-  return EA_OK;
-}
-
-// upload + launch + the counters on their way back, for a batch that is built; the caller queues what else must come down and
-// synchronises.  cls_dev: class bytes in the rows layout, or NULL
-static int depth_gate_enqueue(ea_batch *b, const double *b_T_a, const ea_depth_gate_params *prm, unsigned char *cls_dev,
-                              DepthGateRun &run) {
-  const int nseg = (int)b->probs.size();
-  const ProblemDesc *hd = reinterpret_cast<const ProblemDesc *>(b->h_desc);  // (batch_build's staging block)
-  const GroupDesc *hg = reinterpret_cast<const GroupDesc *>(b->h_desc + (size_t)b->nterms * sizeof(ProblemDesc));
-  run.nseg = nseg;
-  run.o_counts = align16((size_t)nseg * sizeof(DepthGateSeg));
-  const size_t bytes = run.o_counts + (size_t)nseg * kDepthGateClasses * sizeof(unsigned long long);
-  if (b->gate_bytes < bytes) {
-    cached_free(b->d_gate); cached_host_free(b->h_gate);
-    b->d_gate = b->h_gate = nullptr; b->gate_bytes = 0;
-    HIPCHK(cached_malloc(reinterpret_cast<void **>(&b->d_gate), bytes, b->device));
-    HIPCHK(cached_host_malloc(reinterpret_cast<void **>(&b->h_gate), bytes, hipHostMallocDefault, b->device));
-    b->gate_bytes = bytes;
-  }
-  run.pinned = b->h_gate;
-  std::memset(run.pinned, 0, bytes);
-  DepthGateSeg *h_segs = reinterpret_cast<DepthGateSeg *>(run.pinned);
-  int max_n = 0;
-  for (int j = 0; j < nseg; ++j) {
-    const ea_problem *p = b->probs[(size_t)j];
-    const int term = hg[j].term_begin;  // the head family; its terms are not included
-    DepthGateSeg &sg = h_segs[j];
-    sg.row = hd[term].row_begin; sg.n = hd[term].n; sg.term = term;
-    const bool rig = (p->variant & 2) != 0;
-    reproject_matrix(b_T_a + 16 * (size_t)j, rig ? p->T12 : nullptr, rig ? p->T12inv : nullptr, sg.M);
-    sg.depth = p->d_now_depth;
-    sg.z_scaling = p->nd_z_scaling;
-    sg.weights = (prm->apply && sg.n > 0) ? weights_ptr(p) : nullptr;
-    sg.cls = cls_dev ? cls_dev + sg.row : nullptr;
-    sg.dw_z_ref = p->dw_z_ref;
-    sg.dw_power = p->dw_power;
-    max_n = std::max(max_n, (int)sg.n);
-  }
-  unsigned char *d = b->d_gate;
-  HIPCHK(hipMemcpyAsync(d, run.pinned, bytes, hipMemcpyHostToDevice, b->stream));
-  DepthGateWork w;
-  w.nseg = nseg; w.max_n = max_n; w.kind = b->probs[0]->nd_kind; w.radius = prm->radius;
-  w.rule = depth_gate_rule(prm);
-  w.segs = reinterpret_cast<const DepthGateSeg *>(d);
-  w.counts = reinterpret_cast<unsigned long long *>(d + run.o_counts);
-  HIPCHK(launch_depth_gate(b->dtype, w, b->d_probs, b->stream));
-  HIPCHK(hipMemcpyAsync(run.pinned + run.o_counts, d + run.o_counts, bytes - run.o_counts, hipMemcpyDeviceToHost, b->stream));
-  return EA_OK;
-}
-
-// after the synchronisation: the counts, and with `apply` the problems' new state
-static void depth_gate_finish(ea_batch *b, const ea_depth_gate_params *prm, const DepthGateRun &run, ea_depth_gate_stats *stats) {
-  for (int j = 0; j < run.nseg; ++j) {
-    if (stats) {
-      const unsigned long long *c = run.counts() + (size_t)kDepthGateClasses * j;
-      stats[j].n = run.segs()[j].n;
-      stats[j].n_behind = (int64_t)c[EA_GATE_BEHIND]; stats[j].n_outside = (int64_t)c[EA_GATE_OUTSIDE];
-      stats[j].n_unknown = (int64_t)c[EA_GATE_UNKNOWN]; stats[j].n_consistent = (int64_t)c[EA_GATE_CONSISTENT];
-      stats[j].n_occluded = (int64_t)c[EA_GATE_OCCLUDED]; stats[j].n_free = (int64_t)c[EA_GATE_FREE];
-    }
-    ea_problem *p = b->probs[(size_t)j];
-    if (prm->apply && run.segs()[j].n > 0) {
-      p->weights_from_depth = false;
-      if (!p->weighted) { p->weighted = true; p->version++; }  // (new values alone need no rebuild of a batch)
-    }
-  }
-}
-
-// the checks of the three forms and everything up to a built batch whose problems own their points (apply)
-static int depth_gate_prepare(ea_batch *b, const ea_depth_gate_params *prm) {
-  int rc = depth_gate_state_checks(b, prm);
-  if (rc == EA_OK) rc = require_device();
-  if (rc != EA_OK) return rc;
-  HIPCHK(hipSetDevice(b->device));
-  if (prm->apply)
-    for (ea_problem *p : b->probs)
-      if ((rc = own_borrowed_points(p)) != EA_OK) return rc;  // (the weights live behind z in an allocation of the problem's)
-  return batch_build(b);
-}
-
-static int batch_depth_gate_checks(ea_batch *b, const double *b_T_a, const ea_depth_gate_params *prm, const void *cls,
-                                   int64_t capacity_rows) {
-  if (!b || !b_T_a || !prm) return fail(EA_ERR_INVALID_ARG, "NULL argument");
-  int rc = depth_gate_params_check(prm);  // (the batch is looked at only for what depends on it)
-  if (rc == EA_OK) rc = check_reproject_poses(b_T_a, (int)b->probs.size());
-  if (rc != EA_OK) return rc;
-  if (cls && capacity_rows < batch_rows_host(b))
-    return fail(EA_ERR_INVALID_ARG, "capacity_rows is smaller than the batch's row count (ea_batch_row_offsets)");
-  return EA_OK;
-}
-
-extern "C" int ea_batch_depth_gate_device(ea_batch *b, const double *b_T_a, const ea_depth_gate_params *prm, uint8_t *cls_dev,
-                                          int64_t capacity_rows, ea_depth_gate_stats *stats) {
-  int rc = batch_depth_gate_checks(b, b_T_a, prm, cls_dev, capacity_rows);
-  if (rc != EA_OK) return rc;
-  if (cls_dev) {  // (before a problem is changed)
-    if ((rc = require_device()) != EA_OK) return rc;
-    hipPointerAttribute_t at;
-    const hipError_t e = hipPointerGetAttributes(&at, cls_dev);
-    if (e != hipSuccess) (void)hipGetLastError();
-    if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.device != b->device)
-      return fail(EA_ERR_INVALID_ARG, "cls_dev is not device memory of the batch's device");
-  }
-  if ((rc = depth_gate_prepare(b, prm)) != EA_OK) return rc;
-  DepthGateRun run;
-  if ((rc = depth_gate_enqueue(b, b_T_a, prm, cls_dev, run)) != EA_OK) return rc;
-  HIPCHK(hipStreamSynchronize(b->stream));  // weights and classes are complete (and visible to any other stream) when this returns
-  depth_gate_finish(b, prm, run, stats);
-  return EA_OK;
-}
-
-extern "C" int ea_batch_depth_gate(ea_batch *b, const double *b_T_a, const ea_depth_gate_params *prm, uint8_t *cls,
-                                   int64_t capacity_rows, ea_depth_gate_stats *stats) {
-  int rc = batch_depth_gate_checks(b, b_T_a, prm, cls, capacity_rows);
-  if (rc != EA_OK) return rc;
-  if ((rc = depth_gate_prepare(b, prm)) != EA_OK) return rc;
-  DevBuf rows;
-  if (cls && b->total_rows > 0) HIPCHK(cached_malloc(&rows.p, (size_t)b->total_rows, b->device));
-  DepthGateRun run;
-  if ((rc = depth_gate_enqueue(b, b_T_a, prm, rows.as<unsigned char>(), run)) != EA_OK) return rc;
-  // the head families' class bytes come down, adjacent ones in one copy; rows of terms stay as the caller left them
-  for (int j = 0; rows.p && j < run.nseg;) {
-    const int64_t begin = run.segs()[j].row;
-    int64_t end = begin + run.segs()[j].n;
-    for (++j; j < run.nseg && run.segs()[j].row == end; ++j) end += run.segs()[j].n;
-    if (end > begin)
-      HIPCHK(hipMemcpyAsync(cls + begin, rows.as<unsigned char>() + begin, (size_t)(end - begin), hipMemcpyDeviceToHost, b->stream));
-  }
-  HIPCHK(hipStreamSynchronize(b->stream));
-  depth_gate_finish(b, prm, run, stats);
-  return EA_OK;
-}
-
-extern "C" int ea_problem_depth_gate(ea_problem *p, const double b_T_a[16], const ea_depth_gate_params *prm, uint8_t *cls,
-                                     int64_t capacity, ea_depth_gate_stats *stats) {
-  if (!p || !b_T_a || !prm || !stats) return fail(EA_ERR_INVALID_ARG, "NULL argument");
-  int rc = depth_gate_params_check(prm);
-  if (rc == EA_OK) rc = check_reproject_poses(b_T_a, 1);
-  if (rc != EA_OK) return rc;
-  if (cls && capacity < p->n) return fail(EA_ERR_INVALID_ARG, "capacity is smaller than ea_problem_num_points");
-  if ((rc = require_device()) != EA_OK) return rc;
-  ea_batch *b;
-  if ((rc = self_batch(p, &b)) != EA_OK) return rc;
-  if (p->n == 0) return fail(EA_ERR_STATE, "no edge points (ea_problem_set_points)");
-  if ((rc = depth_gate_prepare(b, prm)) != EA_OK) return rc;
-  DevBuf rows;
-  if (cls) HIPCHK(cached_malloc(&rows.p, (size_t)p->n, p->device));  // (the head family's rows start at 0)
-  DepthGateRun run;
-  if ((rc = depth_gate_enqueue(b, b_T_a, prm, rows.as<unsigned char>(), run)) != EA_OK) return rc;
-  std::vector<uint8_t> tmp(cls && !p->order.empty() ? (size_t)p->n : 0);
-  if (cls) HIPCHK(hipMemcpyAsync(tmp.empty() ? cls : tmp.data(), rows.p, (size_t)p->n, hipMemcpyDeviceToHost, b->stream));
-  HIPCHK(hipStreamSynchronize(b->stream));
-  for (size_t i = 0; i < tmp.size(); ++i) cls[(size_t)p->order[i]] = tmp[i];  // stored in tile order: the caller's order back
-  depth_gate_finish(b, prm, run, stats);
   return EA_OK;
 }
 

@@ -1,6 +1,7 @@
-// ea_capi_internal.h — what the library's host translation units share behind include/ea_hip.h: ea_capi.hip (problems,
-// batches, solves; it defines everything declared here) and ea_frames.hip (frame producers, tracker).  Not for ea_comm.hip,
-// which sees problems and batches through the C-ABI and ea_launch.h only.
+// ea_capi_internal.h — what the library's three host translation units share behind include/ea_hip.h: ea_capi.hip (problems,
+// batches, solves; it defines everything declared here but auto_scale_losses), ea_frames.hip (frame producers, tracker) and
+// ea_segments.hip (the calls that run one segment per problem: quantiles, pose statistics, reproject, overlay, depth gate).
+// Not for ea_comm.hip, which sees problems and batches through the C-ABI and ea_launch.h only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -99,6 +100,12 @@ int check_device(int device);
 // the resource cache: freed device blocks are kept and handed out again (ea_capi.hip has the rules)
 hipError_t cached_malloc(void **out, size_t bytes, int device);
 void cached_free(void *p);
+// likewise pinned host blocks (hipHostMalloc flags) and non-blocking streams (the caller has synchronised what it hands back)
+hipError_t cached_host_malloc(void **out, size_t bytes, unsigned flags, int device);
+void cached_host_free(void *p);
+hipError_t cached_stream_create(hipStream_t *out, int device);
+void cached_stream_destroy(hipStream_t s, int device);
+inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 // scope guard for a temporary device block, so that an early HIPCHK return frees it
 struct DevBuf {
   void *p = nullptr;
@@ -119,11 +126,25 @@ int check_cov_options(const ea_covariance_options *o);
 // the solve options' validity (every solve checks them itself; the multi-stream tracker checks before it touches a stream)
 int check_options(const ea_options &o);
 
-// What ea_batch_set_frames (ea_frames.hip) needs of a batch, whose layout stays ea_capi.hip's: its problems in batch order and
-// its device; and the batch-owned memory of the batched producers -- one device block and one pinned staging block of at least
+// What the other two files see of a batch, whose layout stays ea_capi.hip's: a read-only view.  batch_view: the batch as it
+// stands -- its problems in batch order, device, dtype, stream -- with the rest left empty.  batch_built: descriptors rebuilt
+// where a problem changed (EA_ERR_STATE without a DT image, as ea_eval) and the calling thread on the batch's device, then the
+// whole view: the host copies of that build's descriptor and group tables, the device's descriptors, the rows of the batch's
+// layout (ea_batch_row_offsets).
+struct BatchView {
+  int device = 0, dtype = EA_F64, count = 0, nterms = 0;
+  hipStream_t stream = nullptr;
+  ea_problem *const *probs = nullptr;                        // count
+  const ProblemDesc *h_desc = nullptr, *d_probs = nullptr;   // nterms, on the host and on the device
+  const GroupDesc *h_groups = nullptr;                       // count
+  int64_t total_rows = 0;
+};
+BatchView batch_view(ea_batch *b);
+int batch_built(ea_batch *b, BatchView *v);
+
+// The batch-owned memory of the batched producers (ea_frames.hip) -- one device block and one pinned staging block of at least
 // the sizes asked for, grown on demand, kept across calls and freed with the batch (EA_ERR_ALLOC when either cannot be had;
 // what they hold is the producers' business).
-void batch_members(ea_batch *b, ea_problem *const **probs, int *count, int *device);
 int batch_frames_reserve(ea_batch *b, size_t device_bytes, size_t pinned_bytes, unsigned char **device_block,
                          unsigned char **pinned_block);
 // ea_batch_get_info's "frames_hysteresis_rounds": looks at the hysteresis flags the batch's last producer call has taken so far
@@ -134,5 +155,25 @@ void batch_frames_set_without_edges(ea_batch *b, int frames);
 // ea_batch_get_info's "frames_uploaded": host-to-device frame copies of the last ea_batch_set_frames_ros_pyramid call, kept by
 // the batch of level 0
 void batch_frames_set_uploaded(ea_batch *b, int64_t copies);
+
+// What else the per-problem segment calls (ea_segments.hip) need.  batch_upload_poses: one pose per problem into the batch's
+// d_poses, on its stream.  batch_gate_reserve: the depth gate's block pair, batch-owned like the producers' (ea_batch says why).
+// problem_call_batch: the prologue of a single-problem call -- the problem's batch of one, built (build = false: left to the
+// caller, whose own checks come first), EA_ERR_STATE for a problem without points.
+int batch_upload_poses(ea_batch *b, const double *q, const double *t, const PoseState **d_poses = nullptr);
+int batch_gate_reserve(ea_batch *b, size_t bytes, unsigned char **device_block, unsigned char **pinned_block);
+int problem_call_batch(ea_problem *p, ea_batch **b, bool build = true);
+// no problem or batch exists without a device; this answers the "no device" question before a handle is dereferenced
+int require_device();
+// borrowed point arrays (ea_problem_set_points_device) into arrays the problem owns
+int own_borrowed_points(ea_problem *p);
+// points of the problem and its terms: its rows in a batch's layout
+int64_t problem_points(const ea_problem *p);
+// a caller's device pointer: non-NULL, 16-byte aligned, and -- where this runtime knows the allocation -- memory of `device`
+int check_device_pointer(int device, const void *ptr, const char *what);
+// rows stored in tile order (ea_problem_set_point_order) back in the caller's order: out[order[i]] = tmp[i], elem_bytes each
+void scatter_to_callers_order(const std::vector<int32_t> &order, size_t elem_bytes, const void *tmp, void *out);
+// ea_segments.hip's, for ea_batch_solve: the losses of ea_problem_set_loss_auto_scale set from the residuals at poses q, t
+int auto_scale_losses(ea_batch *b, const double *q, const double *t);
 
 }  // namespace ea

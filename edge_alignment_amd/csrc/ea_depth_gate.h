@@ -1,6 +1,6 @@
 // ea_depth_gate.h — the depth-consistency gate (ea_*_depth_gate, ea_*_set_now_depth) as pure logic: the argument checks, the
 // validity and conversion of a depth sample of either kind, the projection of step B, the window scan, the classification and
-// the weight.  Shared by the kernel (ea_depth_gate_kernel), the host driver (ea_capi.hip) and a host shim without a device
+// the weight.  Shared by the kernel (ea_depth_gate_kernel), the host driver (ea_segments.hip) and a host shim without a device
 // (tests/depth_gate_host_shim.cpp), which holds it to tests/depth_gate_ref.py bit for bit.
 //
 // include/ea_hip.h states the arithmetic.  Everything here is fp64 in that order with no contracted multiply-add (EA_FP_EXACT,

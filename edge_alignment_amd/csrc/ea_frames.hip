@@ -766,9 +766,9 @@ static int batch_frames_check(ea_batch *b, const uint8_t *const *ref_bgr, const 
     return fail(EA_ERR_INVALID_ARG, "image extent out of range");
   if (now && W > 16384) return fail(EA_ERR_INVALID_ARG, "frames wider than 16384 pixels are not supported by the DT producers");
   if (!(z_scaling > 0.0)) return fail(EA_ERR_INVALID_ARG, "z_scaling must be > 0");
-  ea_problem *const *probs = nullptr;
-  int count = 0, device = 0;
-  batch_members(b, &probs, &count, &device);
+  const BatchView view = batch_view(b);
+  ea_problem *const *probs = view.probs;
+  const int count = view.count, device = view.device;
   if (count < 1 || count > 65535) return fail(EA_ERR_INVALID_ARG, "a batched producer call takes 1..65535 problems");
   for (int i = 0; i < count; ++i)
     if ((ref && (!ref_bgr[i] || !ref_depth[i])) || (now && !now_bgr[i]) || (now_mask && !now_mask[i]))

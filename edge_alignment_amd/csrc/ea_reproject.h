@@ -1,5 +1,5 @@
 // ea_reproject.h — the host half of ea_*_reproject / ea_*_overlay and the pose <-> matrix conversions, as pure logic: shared
-// by the host driver (ea_capi.hip), the kernel's work description (ea_launch.h) and a host shim without a device
+// by the host driver (ea_segments.hip), the kernel's work description (ea_launch.h) and a host shim without a device
 // (tests/reproject_host_shim.cpp).
 //
 // Everything here is fp64 with a FIXED operation order and no contracted multiply-add (ea_pixel_cost_kernel's comment says

@@ -1,5 +1,5 @@
 // ea_select.h — exact order statistics of |r| by radix select, the part that is pure logic: shared by the select kernels
-// (ea_kernels.hip), the host driver (ea_capi.hip) and a host sweep without a device (tests/select_host_shim.cpp).
+// (ea_kernels.hip), the host driver (ea_segments.hip) and a host sweep without a device (tests/select_host_shim.cpp).
 //
 // A non-negative double orders as its bit pattern, so |r| is selected as a 64-bit key, most significant digit first: six
 // passes, five of 11 bits and a last one of 9.  A pass counts, per (segment, quantile), the keys that still agree with the

@@ -9,7 +9,7 @@ problems of 50 000 points each on 640 x 480 images.
 A leg is WARM warm-up calls and TIMED timed ones; its figure is the MEDIAN call, with the fastest and slowest beside it; the
 legs run today, new, today, new.  Every timed call ends synchronised (the library's calls return complete; the host route
 is host work), so a time is a host clock around the call.  Asserted: both routes paint the same images and count the same
-points.  Launches, synchronisations and copies per call are counted from the code (csrc/ea_capi.hip), not measured.
+points.  Launches, synchronisations and copies per call are counted from the code (csrc/ea_segments.hip), not measured.
 
 usage: python scripts/ab_overlay.py > profiles/overlay_ab.txt"""
 import sys

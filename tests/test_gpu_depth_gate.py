@@ -288,6 +288,38 @@ def test_batch_forms_agree_with_the_single_problem_calls(hip, five):
         B.depth_gate(Ts, w_unknown=1e39, apply=0)
 
 
+@pytest.mark.parametrize("dtype_name", ["f64", "f32"])
+def test_head_rows_come_down_around_a_term_in_the_middle(hip, dtype_name):
+    """three problems of 1, 257 and 64 head points, the middle one with a TERM of 5 points: the head rows are not adjacent,
+    and one segment ends a single point past a 256-lane workgroup.  Batch.reproject and the host form of Batch.depth_gate with
+    classes give every problem the bits of its single-problem call and leave the term's rows as the caller wrote them"""
+    import test_gpu_reproject as tgr
+    dtype, im = _dtype(hip, dtype_name), dc.SMALL
+    depth = dc.depth_image(im, "u16")
+    term = _problem(hip, im, "rig", dc.points(5, 31, im), dtype, depth)
+    Ps = [_problem(hip, im, "distortion", dc.points(1, 32, im), dtype, depth),
+          _problem(hip, im, "plain", dc.points(257, 33, im), dtype, depth),
+          _problem(hip, im, "rig", dc.points(64, 34, im), dtype, depth)]
+    Ps[1].add_term(term)
+    Ts = np.stack([dc.MATRICES[k] for k in ("rigid", "degenerate", "rigid")])
+    B = hip.Batch(Ps)
+    off = B.row_offsets()
+    assert list(off) == [0, 1, 1 + 257 + 5, 263 + 64]
+    prm = dict(radius=1, apply=0, **dc.TOL, **FACTORS)
+    uv = B.reproject(Ts, out=np.full((327, 2), 7.25))
+    cls, stats = B.depth_gate(Ts, out=np.full(327, 99, np.uint8), **prm)
+    for i, P in enumerate(Ps):
+        n = P.num_points
+        tgr._assert_same_bits(uv[off[i]:off[i] + n], P.reproject(Ts[i]), ("reproject", dtype_name, i))
+        single = P.depth_gate(Ts[i], **prm)
+        assert np.array_equal(cls[off[i]:off[i] + n], single[0]) and stats[i] == single[1], i
+    assert (uv[258:263] == 7.25).all() and (cls[258:263] == 99).all()                      # the term's rows are left alone
+    B.close()
+    Ps[1].clear_terms()
+    for P in Ps + [term]:
+        P.close()
+
+
 def test_batch_set_now_depth_host_and_device(hip):
     """N images in one call, from host arrays and from tensors on the device, of either kind; the image survives new points, a
     new DT image and dropped weights; NULL drops it"""
