@@ -955,6 +955,55 @@ static int batch_ref_scatter(const BatchFrames &j, const WsRegion<uint8_t> &edge
   return EA_OK;
 }
 
+// The hysteresis pass of the Canny and ROS flavours on one side (0 reference, 1 current) of the job's frames: blur / gradient,
+// non-maximum suppression, 8 hysteresis launches and one wait per look at the frames' flags, the finish -- into every frame's
+// `edges` / `inv`.  *looks: the looks it took (0 when it failed); each caller posts its own batch_frames_set_rounds.
+static int batch_canny(const BatchFrames &j, int side, bool masked, int lo, int hi, int l2_bgr, int *looks) {
+  const FrameWs &ws = j.ws;
+  unsigned char *base = j.base;
+  int taken = 0;
+  *looks = 0;
+  HIPCHK(launch_canny_frames(j.f, side, masked, lo, hi, l2_bgr, ws.gray.at(base), ws.mag.at(base), ws.dir.at(base), ws.label.at(base),
+                             ws.edges.at(base), ws.inv.at(base), ws.changed.at(base), j.h_flags, &taken, nullptr));
+  *looks = taken;
+  return EA_OK;
+}
+
+// The ROS chain's steps on one level's frames, behind the frames at the working resolution (batch_stage_ros,
+// pyramid_stage_side): the two batched producers and the multi-stream tracker's push all run these.
+// Current side: the hysteresis pass, count and scan on `edges` and the counts back (a wait) -- a frame without any edge has no
+// exact distance transform and keeps the image it has (no_image), *bare counts them -- every other problem's image into its
+// slot (*rc_dt: batch_alloc_dts's; a producer carries on to batch_frames_end with it, a push fails), and for the frames that
+// have an edge the table up, the column passes and the exact row pass on `inv`, the store normalised to (0, 255).
+static int batch_ros_now(BatchFrames *j, int lo, int hi, int *looks, int *bare, int *rc_dt) {
+  const FrameWs &ws = j->ws;
+  unsigned char *base = j->base;
+  *bare = 0;
+  *rc_dt = EA_OK;
+  int rc = batch_canny(*j, 1, false, lo, hi, /*l2_bgr=*/1, looks);
+  if (rc == EA_OK) rc = batch_counts_back(j, ws.edges, 0);
+  if (rc != EA_OK) return rc;
+  j->no_image.assign(j->n, 0);
+  for (size_t i = 0; i < j->n; ++i)
+    if (j->h_totals[i] == 0) { j->no_image[i] = 1; ++*bare; }
+  *rc_dt = batch_alloc_dts(j);
+  if (*rc_dt == EA_OK && (size_t)*bare < j->n) {
+    HIPCHK(upload_table(j));  // the images
+    HIPCHK(launch_chamfer_frames(j->f, ws.inv.at(base), ws.G.at(base), ws.scan.at(base), ws.dist.at(base), ws.dist.at<float>(base),
+                                 ws.minmax.at(base), nullptr));
+    HIPCHK(launch_dt_store_stack(j->dtype, j->f, ws.dist.at<float>(base), ws.minmax.at(base), 1, 0.0, 255.0, nullptr));
+  }
+  return EA_OK;
+}
+// Reference side, behind batch_ref_room: the table with the point arrays up, every edge pixel a point (no depth test,
+// src/SolveEA.cpp:61-78) unless no frame has one, the depth weights.
+static int batch_ros_scatter(BatchFrames *j) {
+  HIPCHK(upload_table(j));
+  if (j->max_total > 0) HIPCHK(launch_edge_scatter_ros_stack(j->dtype, j->f, j->ws.edges.at(j->base), j->ws.counts.at(j->base), nullptr));
+  HIPCHK(launch_depth_weights_frames(j->dtype, j->f, j->max_weighted, nullptr));
+  return EA_OK;
+}
+
 // the last wait, and the problems' bookkeeping
 static int batch_frames_end(const BatchFrames &j, int rc_dt) {
   HIPCHK(hipDeviceSynchronize());
@@ -1054,12 +1103,6 @@ static int batch_set_frames_canny(ea_batch *b, const uint8_t *const *ref_bgr, co
   unsigned char *base = j.base;
   int looks = 0, total_looks = 0;
   batch_frames_set_rounds(b, 0);
-  auto canny = [&](int side, bool masked) {
-    const hipError_t e = launch_canny_frames(j.f, side, masked, lo, hi, /*l2_bgr=*/0, ws.gray.at(base), ws.mag.at(base), ws.dir.at(base), ws.label.at(base),
-                                             ws.edges.at(base), ws.inv.at(base), ws.changed.at(base), j.h_flags, &looks, nullptr);
-    if (e == hipSuccess) batch_frames_set_rounds(b, total_looks += looks);
-    return e;
-  };
   if (j.ref) {
     HIPCHK(upload_table(&j));
     if (!on_device) {
@@ -1067,7 +1110,9 @@ static int batch_set_frames_canny(ea_batch *b, const uint8_t *const *ref_bgr, co
       if (rc == EA_OK) rc = upload_frames(j, ws.depth, ref_depth, j.np * 2);
       if (rc != EA_OK) return rc;
     }
-    HIPCHK(canny(0, false));
+    rc = batch_canny(j, 0, false, lo, hi, /*l2_bgr=*/0, &looks);
+    batch_frames_set_rounds(b, total_looks += looks);
+    if (rc != EA_OK) return rc;
     // ref: utils.cpp:441 -- all_grad(i) > 0 && Z > 0 on the 0/255 edge map
     rc = batch_ref_counts(&j, ws.edges, 0);
     if (rc != EA_OK) return rc;
@@ -1085,7 +1130,9 @@ static int batch_set_frames_canny(ea_batch *b, const uint8_t *const *ref_bgr, co
       if (rc != EA_OK) return rc;
     }
     // (the scatter above reads the reference side's `edges` and is in front of this on the same stream)
-    HIPCHK(canny(1, now_mask != nullptr));
+    rc = batch_canny(j, 1, now_mask != nullptr, lo, hi, /*l2_bgr=*/0, &looks);
+    batch_frames_set_rounds(b, total_looks += looks);
+    if (rc != EA_OK) return rc;
     HIPCHK(launch_chamfer_frames(j.f, ws.inv.at(base), ws.G.at(base), ws.scan.at(base), ws.dist.at(base), nullptr, ws.minmax.at(base), nullptr));
     HIPCHK(launch_dt_store_frames(j.dtype, j.f, ws.dist.at(base), ws.minmax.at(base), prm->now_normalize, prm->norm_lo, prm->norm_hi,
                                   nullptr));
@@ -1185,58 +1232,34 @@ static int batch_set_frames_ros(ea_batch *b, const uint8_t *const *ref_bgr, cons
   rc = batch_frames_check(b, ref_bgr, ref_depth_v, sizeof(float), now_bgr, nullptr, H, W, /*z_scaling (metres already)=*/1.0, on_device, &j);
   if (rc == EA_OK) rc = batch_frames_begin(b, ref_bgr, ref_depth_v, now_bgr, nullptr, &j);
   if (rc != EA_OK) return rc;
-  const FrameWs &ws = j.ws;
-  unsigned char *base = j.base;
   int looks = 0, total_looks = 0;
   batch_frames_set_rounds(b, 0);
-  auto canny = [&](int side) {
-    const hipError_t e = launch_canny_frames(j.f, side, 0, lo, hi, /*l2_bgr=*/1, ws.gray.at(base), ws.mag.at(base), ws.dir.at(base),
-                                             ws.label.at(base), ws.edges.at(base), ws.inv.at(base), ws.changed.at(base), j.h_flags,
-                                             &looks, nullptr);
-    if (e == hipSuccess) batch_frames_set_rounds(b, total_looks += looks);
-    return e;
-  };
   HIPCHK(upload_table(&j));  // where the frames are read, the cameras, the depth weighting
   if (j.ref) {
     rc = batch_stage_ros(j, 0, ref_bgr, ref_depth);
     if (rc != EA_OK) return rc;
-    HIPCHK(canny(0));
-    // (no depth in the slots: every edge pixel is a point, src/SolveEA.cpp:61-78)
-    rc = batch_ref_counts(&j, ws.edges, 0);
+    rc = batch_canny(j, 0, false, lo, hi, /*l2_bgr=*/1, &looks);
+    batch_frames_set_rounds(b, total_looks += looks);
+    if (rc == EA_OK) rc = batch_ref_counts(&j, j.ws.edges, 0);
+    if (rc == EA_OK) rc = batch_ros_scatter(&j);
     if (rc != EA_OK) return rc;
-    HIPCHK(upload_table(&j));  // the point arrays
-    if (j.max_total > 0) HIPCHK(launch_edge_scatter_ros_stack(j.dtype, j.f, ws.edges.at(base), ws.counts.at(base), nullptr));
-    HIPCHK(launch_depth_weights_frames(j.dtype, j.f, j.max_weighted, nullptr));
   }
-  int rc_dt = EA_OK, first_bare = -1, bare = 0;
+  int rc_dt = EA_OK, bare = 0;
   if (j.now) {
     // (the scatter above reads the reference side's `edges` and `depth` and is in front of this on the same stream; the
-    // current side writes no depth)
+    // current side writes no depth; its third upload of the table takes the first staging again, two waits after it last went up)
     rc = batch_stage_ros(j, 1, now_bgr, nullptr);
     if (rc != EA_OK) return rc;
-    HIPCHK(canny(1));
-    // a frame without any edge has no exact distance transform: it keeps the image it has, like the per-problem producer
-    rc = batch_counts_back(&j, ws.edges, 0);
+    rc = batch_ros_now(&j, lo, hi, &looks, &bare, &rc_dt);
+    batch_frames_set_rounds(b, total_looks += looks);
     if (rc != EA_OK) return rc;
-    j.no_image.assign(j.n, 0);
-    for (size_t i = 0; i < j.n; ++i)
-      if (j.h_totals[i] == 0) {
-        j.no_image[i] = 1;
-        if (bare++ == 0) first_bare = (int)i;
-      }
-    rc_dt = batch_alloc_dts(&j);
-    if (rc_dt == EA_OK && (size_t)bare < j.n) {
-      HIPCHK(upload_table(&j));  // the images; the first staging again, two waits after it last went up (upload_table)
-      HIPCHK(launch_chamfer_frames(j.f, ws.inv.at(base), ws.G.at(base), ws.scan.at(base), ws.dist.at(base), ws.dist.at<float>(base),
-                                   ws.minmax.at(base), nullptr));
-      HIPCHK(launch_dt_store_stack(j.dtype, j.f, ws.dist.at<float>(base), ws.minmax.at(base), 1, 0.0, 255.0, nullptr));
-    }
   }
   batch_frames_set_without_edges(b, bare);
   rc = batch_frames_end(j, rc_dt);
   if (rc == EA_OK && bare > 0)
     return fail(EA_ERR_STATE, "no edge in " + std::to_string(bare) + " of the current frames, the first at index " +
-                                  std::to_string(first_bare) + ": the exact distance transform is undefined");
+                                  std::to_string(std::find(j.no_image.begin(), j.no_image.end(), 1) - j.no_image.begin()) +
+                                  ": the exact distance transform is undefined");
   return rc;
 }
 
@@ -1401,19 +1424,9 @@ static int batch_set_frames_ros_pyramid(ea_batch *const *levels, int nlevels, co
   FramePyramid py;
   rc = pyramid_frames_begin(levels, &J, halvings, ref_bgr, ref_depth_v, now_bgr, &py);
   if (rc != EA_OK) return rc;
-  const size_t n = (size_t)J[0].count;
   batch_frames_set_uploaded(levels[0], 0);
   std::vector<int> total_looks((size_t)nlevels, 0);
-  auto canny = [&](int l, int side) {
-    BatchFrames &j = J[(size_t)l];
-    const FrameWs &ws = j.ws;
-    int looks = 0;
-    const hipError_t e = launch_canny_frames(j.f, side, 0, lo, hi, /*l2_bgr=*/1, ws.gray.at(j.base), ws.mag.at(j.base), ws.dir.at(j.base),
-                                             ws.label.at(j.base), ws.edges.at(j.base), ws.inv.at(j.base), ws.changed.at(j.base), j.h_flags,
-                                             &looks, nullptr);
-    if (e == hipSuccess) batch_frames_set_rounds(levels[l], total_looks[(size_t)l] += looks);
-    return e;
-  };
+  int looks = 0;
   int64_t uploads = 0;
   for (BatchFrames &j : J) HIPCHK(upload_table(&j));  // where the frames are read, the cameras, the depth weighting
   if (J[0].ref) {
@@ -1422,44 +1435,28 @@ static int batch_set_frames_ros_pyramid(ea_batch *const *levels, int nlevels, co
     if (rc != EA_OK) return rc;
     for (int l = 0; l < nlevels; ++l) {
       BatchFrames &j = J[(size_t)l];
-      const FrameWs &ws = j.ws;
-      HIPCHK(canny(l, 0));
-      rc = batch_ref_counts(&j, ws.edges, 0);
+      rc = batch_canny(j, 0, false, lo, hi, /*l2_bgr=*/1, &looks);
+      batch_frames_set_rounds(levels[l], total_looks[(size_t)l] += looks);
+      if (rc == EA_OK) rc = batch_ref_counts(&j, j.ws.edges, 0);
+      if (rc == EA_OK) rc = batch_ros_scatter(&j);
       if (rc != EA_OK) return rc;
-      HIPCHK(upload_table(&j));  // the point arrays
-      if (j.max_total > 0) HIPCHK(launch_edge_scatter_ros_stack(j.dtype, j.f, ws.edges.at(j.base), ws.counts.at(j.base), nullptr));
-      HIPCHK(launch_depth_weights_frames(j.dtype, j.f, j.max_weighted, nullptr));
     }
   }
   std::vector<int> rc_dt((size_t)nlevels, EA_OK);
-  int first_bare_level = -1, first_bare = -1, bare_all = 0;
+  int first_bare_level = -1, bare_all = 0;
   if (J[0].now) {
     // (every level's scatter reads that level's `edges` and `depth` and is in front of this on the same stream)
     rc = pyramid_stage_side(J, py, halvings, 1, now_bgr, nullptr, &uploads);
     batch_frames_set_uploaded(levels[0], uploads);
     if (rc != EA_OK) return rc;
     for (int l = 0; l < nlevels; ++l) {
-      BatchFrames &j = J[(size_t)l];
-      const FrameWs &ws = j.ws;
-      HIPCHK(canny(l, 1));
-      rc = batch_counts_back(&j, ws.edges, 0);
-      if (rc != EA_OK) return rc;
       int bare = 0;
-      j.no_image.assign(n, 0);
-      for (size_t i = 0; i < n; ++i)
-        if (j.h_totals[i] == 0) {
-          j.no_image[i] = 1;
-          ++bare;
-          if (bare_all++ == 0) { first_bare_level = l; first_bare = (int)i; }
-        }
+      rc = batch_ros_now(&J[(size_t)l], lo, hi, &looks, &bare, &rc_dt[(size_t)l]);
+      batch_frames_set_rounds(levels[l], total_looks[(size_t)l] += looks);
       batch_frames_set_without_edges(levels[l], bare);
-      rc_dt[(size_t)l] = batch_alloc_dts(&j);
-      if (rc_dt[(size_t)l] == EA_OK && (size_t)bare < n) {
-        HIPCHK(upload_table(&j));  // the images
-        HIPCHK(launch_chamfer_frames(j.f, ws.inv.at(j.base), ws.G.at(j.base), ws.scan.at(j.base), ws.dist.at(j.base),
-                                     ws.dist.at<float>(j.base), ws.minmax.at(j.base), nullptr));
-        HIPCHK(launch_dt_store_stack(j.dtype, j.f, ws.dist.at<float>(j.base), ws.minmax.at(j.base), 1, 0.0, 255.0, nullptr));
-      }
+      if (rc != EA_OK) return rc;
+      if (bare > 0 && bare_all == 0) first_bare_level = l;
+      bare_all += bare;
     }
   }
   rc = EA_OK;
@@ -1467,10 +1464,13 @@ static int batch_set_frames_ros_pyramid(ea_batch *const *levels, int nlevels, co
     const int rc_l = batch_frames_end(J[(size_t)l], rc_dt[(size_t)l]);  // (the first waits, the others find the device idle)
     if (rc == EA_OK) rc = rc_l;
   }
-  if (rc == EA_OK && bare_all > 0)
+  if (rc == EA_OK && bare_all > 0) {
+    const std::vector<unsigned char> &none = J[(size_t)first_bare_level].no_image;
     return fail(EA_ERR_STATE, "no edge in " + std::to_string(bare_all) + " of the current frames' levels, the first at level " +
-                                  std::to_string(first_bare_level) + ", index " + std::to_string(first_bare) +
+                                  std::to_string(first_bare_level) + ", index " +
+                                  std::to_string(std::find(none.begin(), none.end(), 1) - none.begin()) +
                                   ": the exact distance transform is undefined");
+  }
   return rc;
 }
 
@@ -1533,14 +1533,24 @@ extern "C" int ea_resize_half_levels(int device, int kind, const void *src, int 
 // dimension) and what that leaves in its workspace serves both sides: the current-side tail (threshold + chamfer, or the exact
 // transform, then the store into the stream's image) and, behind the solve, the reference-side tail (count, scan, scatter,
 // depth weights).  Both sides of a slot name the same frame, so every step is a kernel the batched producers have already.
-// The sequence of a push, all on the null stream but the solve:
-//   table and frames up (device frames: read in place) [-> ROS: halvings] -> edge pass -> [ROS: count + scan, the counts back
-//   (wait): a frame without an edge has no image] -> chamfer / exact transform -> store -> wait (the images are complete)
-//   -> [Laplacian, Canny: count + scan queued, it runs beside the solve] -> ea_batch_solve of the aligned streams on the
-//   batch's own streams [-> ea_batch_covariance] -> [Laplacian, Canny: the counts back (wait)] -> room for the points ->
-//   table up -> scatter -> depth weights -> wait.
+// A tracker has L >= 1 levels (ea_tracker_batch_create_pyramid, the ROS flavour: level l works at halvings + l), each with
+// problems, a batch and sub-batches of its own; ONE push (tracker_batch_push) serves every flavour and every L, as phases over
+// one TrackerPush, all on the null stream but the solves:
+//   checks            tracker_push_check: nothing is touched before they have passed
+//   frames in place   tracker_push_frames: table and frames up (device frames: read in place) [-> ROS: halvings; L > 1: the
+//                     frames go up once and one halving chain per kind leaves every level's frame in its workspace]
+//   images, per level tracker_push_images: edge pass -> [ROS: count + scan, the counts back (wait): a frame without an edge
+//                     has no image] -> chamfer / exact transform -> store; then ONE wait (the images are complete)
+//                     -> [Laplacian, Canny: count + scan queued, it runs beside the solves]
+//   priors            tracker_push_priors: the aligned streams (level 0's rule), their motion priors on every usable level
+//   descent           tracker_push_descent: for l = L - 1 .. 0 ea_batch_solve of the streams still descending that can use l,
+//                     on the batches' own streams, the pose carried down; a single level is this loop run once
+//   covariance        tracker_push_covariance: [ea_batch_covariance] [keyframe mode: ea_batch_pose_stats] at level 0
+//   references, per level   tracker_push_references: [Laplacian, Canny: the counts back (wait)] -> room for the points ->
+//                     table up -> scatter -> depth weights; then the last wait
+//   bookkeeping       tracker_push_book
 // (The ROS chain needs its counts before the transform, and its count has no depth test: the same counts serve the scatter.)
-// Waits per push outside the solve: the hysteresis looks (Canny, ROS), the images, the counts, the end.
+// Waits per push outside the solves: the hysteresis looks (Canny, ROS), the images, the counts, the end.
 
 namespace {
 struct TrackerStream {
@@ -1555,24 +1565,18 @@ struct TrackerStream {
 }  // namespace
 
 struct ea_tracker_batch {
-  std::vector<ea_problem *> probs;
-  std::vector<TrackerStream> st;
-  ea_batch *b = nullptr;    // every stream: the frame workspace is this batch's, and so is the solve when all are aligned
-  std::vector<std::pair<std::vector<int>, ea_batch *>> subs;  // (streams, their batch): the solves of fewer than all streams
-  int flavour = 0, halvings = 0, device = 0;
-  // ea_tracker_batch_create_pyramid: level 0 is probs / b above; coarse[l - 1] holds level l = 1 .. levels - 1 -- its problems,
-  // the batch over them and its sub-batches
+  // One level of every stream (ea_tracker_batch_create: one; _create_pyramid: levels, lv[0] the finest): its problems, the
+  // batch over them -- the solve when all are aligned; lv[0]'s also owns the frame workspace of every level -- and the
+  // sub-batches (streams, their batch) that solve fewer than all streams
   struct Level {
     std::vector<ea_problem *> probs;
     ea_batch *b = nullptr;
     std::vector<std::pair<std::vector<int>, ea_batch *>> subs;
   };
-  int levels = 1;
-  std::vector<Level> coarse;
+  std::vector<Level> lv;
+  std::vector<TrackerStream> st;
+  int flavour = 0, halvings = 0, device = 0, levels = 1;
   std::vector<ea_summary> last_sums;  // levels x streams, level-major: ea_tracker_batch_last_summaries
-  const std::vector<ea_problem *> &level_probs(int l) const { return l == 0 ? probs : coarse[(size_t)l - 1].probs; }
-  ea_batch *level_batch(int l) const { return l == 0 ? b : coarse[(size_t)l - 1].b; }
-  std::vector<std::pair<std::vector<int>, ea_batch *>> &level_subs(int l) { return l == 0 ? subs : coarse[(size_t)l - 1].subs; }
   bool cov_on = false;
   ea_covariance_options cov_opt{};
   double sigma_rot = 0.0, sigma_trans = 0.0;
@@ -1596,16 +1600,16 @@ static int tracker_batch_create(ea_tracker_batch **out, const ea_camera *cams, i
   ea_tracker_batch *tb = new (std::nothrow) ea_tracker_batch;
   if (!tb) return fail(EA_ERR_ALLOC, "out of host memory");
   tb->flavour = flavour; tb->halvings = halvings; tb->device = device; tb->levels = levels;
-  tb->coarse.resize((size_t)levels - 1);
+  tb->lv.resize((size_t)levels);
   int rc = EA_OK;
   for (int l = 0; l < levels && rc == EA_OK; ++l) {
-    std::vector<ea_problem *> &probs = l == 0 ? tb->probs : tb->coarse[(size_t)l - 1].probs;
+    ea_tracker_batch::Level &lv = tb->lv[(size_t)l];
     for (int i = 0; i < count && rc == EA_OK; ++i) {
       ea_problem *p = nullptr;
       rc = ea_problem_create(&p, cams + (size_t)l * count + i, dtype, device);
-      if (rc == EA_OK) probs.push_back(p);
+      if (rc == EA_OK) lv.probs.push_back(p);
     }
-    if (rc == EA_OK) rc = ea_batch_create(l == 0 ? &tb->b : &tb->coarse[(size_t)l - 1].b, probs.data(), count);
+    if (rc == EA_OK) rc = ea_batch_create(&lv.b, lv.probs.data(), count);
   }
   if (rc != EA_OK) { ea_tracker_batch_destroy(tb); return rc; }
   tb->st.resize((size_t)count);
@@ -1627,10 +1631,7 @@ extern "C" int ea_tracker_batch_create_pyramid(ea_tracker_batch **out, const ea_
 
 extern "C" void ea_tracker_batch_destroy(ea_tracker_batch *tb) {
   if (!tb) return;
-  for (auto &s : tb->subs) ea_batch_destroy(s.second);
-  ea_batch_destroy(tb->b);
-  for (ea_problem *p : tb->probs) ea_problem_destroy(p);
-  for (ea_tracker_batch::Level &lv : tb->coarse) {
+  for (ea_tracker_batch::Level &lv : tb->lv) {
     for (auto &s : lv.subs) ea_batch_destroy(s.second);
     ea_batch_destroy(lv.b);
     for (ea_problem *p : lv.probs) ea_problem_destroy(p);
@@ -1638,15 +1639,13 @@ extern "C" void ea_tracker_batch_destroy(ea_tracker_batch *tb) {
   delete tb;
 }
 
-extern "C" int ea_tracker_batch_count(const ea_tracker_batch *tb) { return tb ? (int)tb->probs.size() : 0; }
-
-extern "C" ea_problem *ea_tracker_batch_problem(ea_tracker_batch *tb, int i) {
-  return tb && i >= 0 && (size_t)i < tb->probs.size() ? tb->probs[(size_t)i] : nullptr;
-}
+extern "C" int ea_tracker_batch_count(const ea_tracker_batch *tb) { return tb ? (int)tb->st.size() : 0; }
 
 extern "C" ea_problem *ea_tracker_batch_level_problem(ea_tracker_batch *tb, int level, int i) {
-  return tb && level >= 0 && level < tb->levels && i >= 0 && (size_t)i < tb->probs.size() ? tb->level_probs(level)[(size_t)i] : nullptr;
+  return tb && level >= 0 && level < tb->levels && i >= 0 && (size_t)i < tb->st.size() ? tb->lv[(size_t)level].probs[(size_t)i] : nullptr;
 }
+
+extern "C" ea_problem *ea_tracker_batch_problem(ea_tracker_batch *tb, int i) { return ea_tracker_batch_level_problem(tb, 0, i); }
 
 extern "C" int ea_tracker_batch_last_summaries(ea_tracker_batch *tb, int i, ea_summary *out) {
   if (!tb || !out) return fail(EA_ERR_INVALID_ARG, "NULL argument");
@@ -1657,9 +1656,9 @@ extern "C" int ea_tracker_batch_last_summaries(ea_tracker_batch *tb, int i, ea_s
 
 // a stream without a reference: the next push starts a fresh chain for it
 static void tracker_stream_drop(ea_tracker_batch *tb, size_t i) {
-  for (int l = 0; l < tb->levels; ++l) {
-    (void)reserve_points(tb->level_probs(l)[i], 0);
-    tb->level_probs(l)[i]->version++;
+  for (const ea_tracker_batch::Level &lv : tb->lv) {
+    (void)reserve_points(lv.probs[i], 0);
+    lv.probs[i]->version++;
   }
   tb->st[i].frames = 0;
   tb->st[i].cov_valid = false;
@@ -1672,16 +1671,28 @@ static int tracker_batch_fail(ea_tracker_batch *tb, int rc) {
   const std::string why = ea_last_error();  // (the clean-up below may not overwrite what failed)
   (void)hipDeviceSynchronize();
   (void)hipGetLastError();
-  for (size_t i = 0; i < tb->probs.size(); ++i) tracker_stream_drop(tb, i);
+  for (size_t i = 0; i < tb->st.size(); ++i) tracker_stream_drop(tb, i);
   tb->last_aligned = 0;
   return fail(rc, why);
 }
+// a step of a push (its tracker: `tb`) that fails takes the push with it: tracker_batch_fail, and its code is returned
+#define TBCHK(expr)                                                                                                            \
+  do {                                                                                                                         \
+    const hipError_t e_ = (expr);                                                                                              \
+    if (e_ != hipSuccess) { (void)fail(EA_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); return tracker_batch_fail(tb, EA_ERR_HIP); } \
+  } while (0)
+#define TBRC(expr)                                          \
+  do {                                                      \
+    const int rc_ = (expr);                                 \
+    if (rc_ != EA_OK) return tracker_batch_fail(tb, rc_);   \
+  } while (0)
 
-// the batch that solves exactly the streams in `members`: the tracker's own when that is all of them, else one of the few
+// the batch that solves exactly the streams in `members`: the level's own when that is all of them, else one of the few
 // sub-batches it keeps (the same streams tend to be aligned push after push; the oldest makes room)
-static int tracker_batch_solver(ea_tracker_batch *tb, const std::vector<int> &members, ea_batch **out, int level = 0) {
-  if (members.size() == tb->probs.size()) { *out = tb->level_batch(level); return EA_OK; }
-  std::vector<std::pair<std::vector<int>, ea_batch *>> &subs = tb->level_subs(level);
+static int tracker_batch_solver(ea_tracker_batch *tb, const std::vector<int> &members, ea_batch **out, int level) {
+  ea_tracker_batch::Level &lv = tb->lv[(size_t)level];
+  if (members.size() == lv.probs.size()) { *out = lv.b; return EA_OK; }
+  std::vector<std::pair<std::vector<int>, ea_batch *>> &subs = lv.subs;
   for (size_t k = 0; k < subs.size(); ++k)
     if (subs[k].first == members) { *out = subs[k].second; return EA_OK; }
   constexpr size_t kKeptSubBatches = 4;
@@ -1690,7 +1701,7 @@ static int tracker_batch_solver(ea_tracker_batch *tb, const std::vector<int> &me
     subs.erase(subs.begin());
   }
   std::vector<ea_problem *> probs;
-  for (int i : members) probs.push_back(tb->level_probs(level)[(size_t)i]);
+  for (int i : members) probs.push_back(lv.probs[(size_t)i]);
   ea_batch *sub = nullptr;
   const int rc = ea_batch_create(&sub, probs.data(), (int)probs.size());
   if (rc != EA_OK) return rc;
@@ -1704,11 +1715,11 @@ static int tracker_batch_solver(ea_tracker_batch *tb, const std::vector<int> &me
 // plain kernels' to rounding only.  Streams are therefore grouped by what their own problem needs (term_variant), so that each
 // is solved by the kernels, and to the bits, of a tracker of its own; a problem with further terms is a group by itself.
 // Streams with the same settings -- the usual case -- are one group: one solve.
-static std::vector<std::vector<int>> tracker_batch_groups(const ea_tracker_batch *tb, const std::vector<int> &al, int level = 0) {
+static std::vector<std::vector<int>> tracker_batch_groups(const ea_tracker_batch *tb, const std::vector<int> &al, int level) {
   std::vector<std::vector<int>> groups;
   std::vector<int> keys;
   for (int i : al) {
-    const ea_problem *p = tb->level_probs(level)[(size_t)i];
+    const ea_problem *p = tb->lv[(size_t)level].probs[(size_t)i];
     const int key = p->terms.empty() ? term_variant(p) : -1 - i;
     size_t g = 0;
     while (g < keys.size() && keys[g] != key) ++g;
@@ -1718,470 +1729,376 @@ static std::vector<std::vector<int>> tracker_batch_groups(const ea_tracker_batch
   return groups;
 }
 
-static int tracker_batch_push(ea_tracker_batch *tb, const uint8_t *const *bgr, const void *const *depth, int height, int width,
-                              double z_scaling, const ea_options *opt, double *q_rel, double *t_rel, ea_summary *summaries,
-                              int *aligned, bool on_device) {
-  // every check comes before a device or a stream is touched: a rejected call leaves the tracker as it was
-  if (!tb || !bgr || !depth || !q_rel || !t_rel) return fail(EA_ERR_INVALID_ARG, "NULL argument");
-  const bool ros = tb->flavour == 2;
-  if (height < 3 || width < 3 || height > 32768 || width > 32768 || (int64_t)height * width > 0x3fffffff)
-    return fail(EA_ERR_INVALID_ARG, "image extent out of range");
-  int rc = check_scaled_args(height, width, tb->halvings);
-  if (rc != EA_OK) return rc;
-  const int H = height >> tb->halvings, W = width >> tb->halvings;
-  int lo = 0, hi = 0;
-  rc = tb->flavour == 0 ? EA_OK : ros ? ros_thresholds(150.0, 100.0, &lo, &hi) : canny_thresholds(30.0, 90.0, &lo, &hi);
-  if (rc != EA_OK) return rc;
-  // (as the producers of ea_tracker's flavours: the Canny reference refuses an infinite z_scaling, the Laplacian one takes it)
-  if (tb->flavour == 1 && !(z_scaling <= DBL_MAX)) return fail(EA_ERR_INVALID_ARG, "z_scaling must be > 0 and finite");
-  if (opt) {
-    rc = check_options(*opt);
-    if (rc != EA_OK) return rc;
+// What a push carries from phase to phase (tracker_batch_push; the block comment above names the phases)
+namespace {
+struct TrackerPush {
+  ea_tracker_batch *tb = nullptr;
+  const uint8_t *const *bgr = nullptr;  // the pushed frames: the reference side's and the current side's of every slot
+  const void *const *depth = nullptr;
+  double z_scaling = 0.0;
+  const ea_options *opt = nullptr;
+  ea_summary *summaries = nullptr;  // the caller's (nullable)
+  bool on_device = false;
+  int lo = 0, hi = 0;               // the flavour's hysteresis thresholds
+  std::vector<BatchFrames> J;       // the levels' jobs
+  std::vector<int> al;              // the aligned streams
+  // per stream: the pose its solve started from, the one it carries down the levels, and the one it returned
+  std::vector<double> q0, t0, qc, tc, qs, ts;
+  std::vector<unsigned char> stopped, is_al;  // its descent ended in a failed solve; it was aligned
+  std::vector<ea_pose_stats> kstats;          // keyframe mode: the statistics at the pose its solve returned
+  std::vector<unsigned char> take;            // the pushed frame becomes its reference: every stream's, but in keyframe mode
+  std::vector<int> why;                       // keyframe mode: why (keyframe_decide)
+  bool ros() const { return tb->flavour == 2; }
+  // what the reference side counts and scatters
+  const WsRegion<uint8_t> &ref_edges(const BatchFrames &j) const { return tb->flavour == 0 ? j.ws.lap : j.ws.edges; }
+  int ref_threshold() const { return tb->flavour == 0 ? 35 : 0; }
+  // a level takes part in a stream's solve when its reference has points and its frame has an edge
+  bool usable(int l, size_t i) const {
+    const std::vector<unsigned char> &none = J[(size_t)l].no_image;
+    return tb->lv[(size_t)l].probs[i]->n > 0 && (none.empty() || !none[i]);
   }
-  BatchFrames j;
-  j.ros = ros; j.full_H = height; j.full_W = width; j.halvings = tb->halvings;
-  // (both sides of every slot are the pushed frame: `bgr` is the reference side's colour frame and the current side's)
-  rc = batch_frames_check(tb->b, bgr, depth, ros ? sizeof(float) : 2, bgr, nullptr, H, W, ros ? 1.0 : z_scaling, on_device, &j);
-  if (rc != EA_OK) return rc;
+};
+}  // namespace
 
-  const size_t n = tb->probs.size();
-  tb->pushes++;
-  tb->last_aligned = tb->last_bare = tb->last_rounds = tb->last_edge_passes = tb->last_taken = 0;
-  for (size_t i = 0; i < n; ++i) tb->st[i].cov_valid = false;
-  if (aligned) std::fill(aligned, aligned + n, 0);
-  if (summaries) std::memset(summaries, 0, n * sizeof(*summaries));
-  std::memset(tb->last_sums.data(), 0, tb->last_sums.size() * sizeof(ea_summary));
-  auto failed = [tb](int code) { return tracker_batch_fail(tb, code); };
-#define TBCHK(expr)                                                                                              \
-  do {                                                                                                           \
-    const hipError_t e_ = (expr);                                                                                \
-    if (e_ != hipSuccess) { (void)fail(EA_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); return failed(EA_ERR_HIP); } \
-  } while (0)
-#define TBRC(expr)                      \
-  do {                                  \
-    const int rc_ = (expr);             \
-    if (rc_ != EA_OK) return failed(rc_); \
-  } while (0)
-
-  TBRC(batch_frames_begin(tb->b, bgr, depth, bgr, nullptr, &j));
-  const FrameWs &ws = j.ws;
-  unsigned char *base = j.base;
-  int looks = 0;
-  const WsRegion<uint8_t> &edges = tb->flavour == 0 ? ws.lap : ws.edges;  // what the reference side counts and scatters
-  const int ref_threshold = tb->flavour == 0 ? 35 : 0;
-  auto canny = [&](int l2_bgr) {
-    const hipError_t e = launch_canny_frames(j.f, 1, 0, lo, hi, l2_bgr, ws.gray.at(base), ws.mag.at(base), ws.dir.at(base),
-                                             ws.label.at(base), ws.edges.at(base), ws.inv.at(base), ws.changed.at(base), j.h_flags,
-                                             &looks, nullptr);
-    if (e == hipSuccess) { tb->last_rounds += looks; batch_frames_set_rounds(tb->b, tb->last_rounds); }
-    return e;
-  };
-  // ---- the frame, once: edge pass and the current-side tail into every stream's image
-  if (!ros) {
-    TBRC(batch_alloc_dts(&j));
-    TBCHK(upload_table(&j));
-    if (!on_device) {
-      TBRC(upload_frames(j, ws.bgr, bgr, j.np * 3));
-      TBRC(upload_frames(j, ws.depth, depth, j.np * 2));
-    }
-    tb->last_edge_passes++;
-    if (tb->flavour == 0) {
-      TBCHK(launch_edge_strength_frames(j.f, 1, ws.gray.at(base), ws.lap.at(base), nullptr));
-      TBCHK(launch_threshold_median_frames(j.f, ws.lap.at(base), 35, 1, ws.mask.at(base), nullptr));
-      TBCHK(launch_chamfer_frames(j.f, ws.mask.at(base), ws.G.at(base), ws.scan.at(base), ws.dist.at(base), nullptr, ws.minmax.at(base), nullptr));
-    } else {
-      TBCHK(canny(0));
-      TBCHK(launch_chamfer_frames(j.f, ws.inv.at(base), ws.G.at(base), ws.scan.at(base), ws.dist.at(base), nullptr, ws.minmax.at(base), nullptr));
-    }
-    TBCHK(launch_dt_store_frames(j.dtype, j.f, ws.dist.at(base), ws.minmax.at(base), 1, 0.0, 1.0, nullptr));
-  } else {
-    TBCHK(upload_table(&j));
-    TBRC(batch_stage_ros(j, 0, bgr, reinterpret_cast<const float *const *>(depth)));
-    tb->last_edge_passes++;
-    TBCHK(canny(1));
-    TBRC(batch_counts_back(&j, ws.edges, 0));
-    j.no_image.assign(n, 0);
-    for (size_t i = 0; i < n; ++i)
-      if (j.h_totals[i] == 0) { j.no_image[i] = 1; tb->last_bare++; }
-    batch_frames_set_without_edges(tb->b, tb->last_bare);
-    TBRC(batch_alloc_dts(&j));
-    if ((size_t)tb->last_bare < n) {
-      TBCHK(upload_table(&j));
-      TBCHK(launch_chamfer_frames(j.f, ws.inv.at(base), ws.G.at(base), ws.scan.at(base), ws.dist.at(base), ws.dist.at<float>(base),
-                                  ws.minmax.at(base), nullptr));
-      TBCHK(launch_dt_store_stack(j.dtype, j.f, ws.dist.at<float>(base), ws.minmax.at(base), 1, 0.0, 255.0, nullptr));
-    }
-  }
-  // the images are complete before a solve reads them on the batch's streams, which do not wait for the null stream
-  TBCHK(hipStreamSynchronize(nullptr));
-  for (size_t i = 0; i < n; ++i)
-    if (j.no_image.empty() || !j.no_image[i]) dt_landed(tb->probs[i]);
-  // the frame's edge pixels are counted WHILE the previous references are solved against the images just produced (null
-  // stream beside the solve's non-blocking streams; neither touches what the other uses)
-  if (!ros) TBRC(batch_counts_queue(&j, edges, ref_threshold));
-
-  // ---- the solve of the aligned streams, from their last relative poses
-  std::vector<int> al;
-  for (size_t i = 0; i < n; ++i)
-    if (tb->st[i].frames > 0 && tb->probs[i]->n > 0 && (j.no_image.empty() || !j.no_image[i])) al.push_back((int)i);
-  const size_t na = al.size();
-  // per stream: the pose its solve started from and the one it returned
-  std::vector<double> q0(4 * n), t0(3 * n), qs(4 * n), ts(3 * n);
-  // keyframe mode: per stream, was it aligned / did its solve fail, and the statistics at the pose its solve returned
-  std::vector<unsigned char> is_al(n, 0), solve_failed(n, 0);
-  std::vector<ea_pose_stats> kstats;
-  if (tb->key_on) {
-    kstats.resize(n);
-    std::memset(kstats.data(), 0, n * sizeof(ea_pose_stats));
-  }
-  for (int i : al) {
-    is_al[(size_t)i] = 1;
-    TrackerStream &s = tb->st[(size_t)i];
-    std::memcpy(&q0[4 * (size_t)i], s.q, sizeof(s.q));
-    std::memcpy(&t0[3 * (size_t)i], s.t, sizeof(s.t));
-    if (tb->sigma_rot > 0.0 || tb->sigma_trans > 0.0) {
-      TBRC(motion_prior_install(tb->probs[(size_t)i], tb->sigma_rot, tb->sigma_trans, s.q, s.t));
-      s.motion_set = true;
-      s.installed = tb->probs[(size_t)i]->prior;
-    }
-  }
-  for (const std::vector<int> &grp : tracker_batch_groups(tb, al)) {
-    const size_t ng = grp.size();
-    ea_batch *solver = nullptr;
-    TBRC(tracker_batch_solver(tb, grp, &solver));
-    std::vector<double> qg(4 * ng), tg(3 * ng);
-    std::vector<ea_summary> sg(ng);
-    for (size_t k = 0; k < ng; ++k) {
-      std::memcpy(&qg[4 * k], &q0[4 * (size_t)grp[k]], 4 * sizeof(double));
-      std::memcpy(&tg[3 * k], &t0[3 * (size_t)grp[k]], 3 * sizeof(double));
-    }
-    TBRC(ea_batch_solve(solver, opt, qg.data(), tg.data(), sg.data()));
-    size_t ok = 0;
-    for (size_t k = 0; k < ng; ++k) {
-      const size_t i = (size_t)grp[k];
-      if (summaries) summaries[i] = sg[k];
-      tb->last_sums[i] = sg[k];
-      const bool failure = sg[k].termination == EA_FAILURE;
-      ok += failure ? 0 : 1;
-      solve_failed[i] = failure ? 1 : 0;
-      // (a failed solve: the stream keeps its prior, and the covariance call below sees it at its start pose)
-      std::memcpy(&qs[4 * i], failure ? &q0[4 * i] : &qg[4 * k], 4 * sizeof(double));
-      std::memcpy(&ts[3 * i], failure ? &t0[3 * i] : &tg[3 * k], 3 * sizeof(double));
-      std::memcpy(&qg[4 * k], &qs[4 * i], 4 * sizeof(double));
-      std::memcpy(&tg[3 * k], &ts[3 * i], 3 * sizeof(double));
-    }
-    if (tb->cov_on) {
-      // At the returned poses, from the points and images the solve used: ea_batch_covariance returns once its results have
-      // landed, the scatter that overwrites the points is queued behind that.  A failed solve has no pose to take one at:
-      // its stream reports why = 4.
-      std::vector<ea_covariance> covs(ng);
-      std::memset(covs.data(), 0, ng * sizeof(ea_covariance));
-      if (ok > 0) TBRC(ea_batch_covariance(solver, qg.data(), tg.data(), &tb->cov_opt, covs.data()));
-      for (size_t k = 0; k < ng; ++k) {
-        TrackerStream &s = tb->st[(size_t)grp[k]];
-        s.cov_last = covs[k];
-        if (sg[k].termination == EA_FAILURE) {
-          std::memset(&s.cov_last, 0, sizeof(s.cov_last));
-          s.cov_last.why = 4;
-        }
-        s.cov_valid = true;
-      }
-    }
-    if (tb->key_on && ok > 0) {
-      // keyframe mode: how much of each reference is still seen at the returned pose -- one call for the group, on the batch
-      // that solved it, before anything overwrites points.  A failed solve has no pose to take them at: its stream keeps zeros.
-      std::vector<ea_pose_stats> stg(ng);
-      TBRC(ea_batch_pose_stats(solver, qg.data(), tg.data(), tb->key_prm.margin, tb->key_prm.inlier_residual, stg.data()));
-      for (size_t k = 0; k < ng; ++k)
-        if (sg[k].termination != EA_FAILURE) kstats[(size_t)grp[k]] = stg[k];
-    }
-  }
-
-  // ---- the frame's edge points become the reference of every stream -- in keyframe mode, of the streams whose rule says so
-  // (keyframe_decide); a flavour-2 stream whose frame has no edge keeps what it holds
-  std::vector<unsigned char> take(n, 1);
-  std::vector<int> why(n, 0);
-  bool any_take = true;
-  if (tb->key_on) {
-    any_take = false;
-    for (size_t i = 0; i < n; ++i) {
-      const bool bare = !j.no_image.empty() && j.no_image[i];
-      why[i] = bare ? 0 : keyframe_decide(kstats[i], tb->key_prm, tb->st[i].key.age + 1, is_al[i] != 0, solve_failed[i] != 0);
-      take[i] = why[i] != 0;
-      any_take = any_take || take[i];
-    }
-  }
-  if (!ros && any_take) TBRC(batch_counts_fetch(&j));
-  TBRC(batch_ref_room(&j, tb->key_on ? take.data() : nullptr));
-  if (any_take) {
-    TBCHK(upload_table(&j));
-    if (ros) {
-      if (j.max_total > 0) TBCHK(launch_edge_scatter_ros_stack(j.dtype, j.f, ws.edges.at(base), ws.counts.at(base), nullptr));
-      TBCHK(launch_depth_weights_frames(j.dtype, j.f, j.max_weighted, nullptr));
-    } else {
-      TBRC(batch_ref_scatter(j, edges, ref_threshold, z_scaling));
-    }
-  }
-  TBCHK(hipDeviceSynchronize());
-#undef TBCHK
-#undef TBRC
-  for (size_t i = 0; i < n; ++i)
-    if (take[i]) ref_points_landed(tb->probs[i], j.slots[i].capacity);
-  // priors and frame counts advance only with the new references in place
-  for (int a : al) {
-    const size_t i = (size_t)a;
-    std::memcpy(tb->st[i].q, &qs[4 * i], sizeof(tb->st[i].q));
-    std::memcpy(tb->st[i].t, &ts[3 * i], sizeof(tb->st[i].t));
-    if (aligned) aligned[i] = 1;
-  }
-  for (size_t i = 0; i < n; ++i) {
-    TrackerStream &s = tb->st[i];
-    if (tb->key_on) {
-      // the pose solved in this push against the keyframe in use during it (an unaligned stream: the identity); a stream that
-      // took the frame starts its next solve at the identity, a kept one at the pose just stored
-      const double q_id[4] = {1, 0, 0, 0}, t_id[3] = {0, 0, 0};
-      std::memcpy(q_rel + 4 * i, is_al[i] ? s.q : q_id, sizeof(s.q));
-      std::memcpy(t_rel + 3 * i, is_al[i] ? s.t : t_id, sizeof(s.t));
-      s.key.replaced = why[i];
-      s.key.stats = kstats[i];
-      if (take[i]) {
-        std::memcpy(s.q, q_id, sizeof(s.q));
-        std::memcpy(s.t, t_id, sizeof(s.t));
-        s.key.age = 0;
-        s.key.keyframe_push = tb->pushes;
-        tb->last_taken++;
-      } else if (is_al[i]) {
-        s.key.age += 1;
-      }
-    } else {
-      std::memcpy(q_rel + 4 * i, s.q, sizeof(s.q));
-      std::memcpy(t_rel + 3 * i, s.t, sizeof(s.t));
-    }
-    s.frames += 1;
-  }
-  tb->last_aligned = (int)na;
-  return EA_OK;
-}
-
-// The push of a tracker with several levels (ea_tracker_batch_create_pyramid; the ROS flavour): tracker_batch_push's sequence
-// with every step per level.  The frames go up once and one halving chain per kind leaves every level's frame in that level's
-// workspace (pyramid_stage_side); on each level the frame passes the edge detection once and serves both sides.  A stream is
-// aligned by level 0's rule; a coarser level takes part in its solve when that level's reference has points and that level's
-// frame has an edge.  The solve is ea_solve_pyramid per stream, run as batch solves: the coarsest level first, on each level
-// the streams still descending that can use it, grouped by kernel family as on a single level, the pose carried down.
-static int tracker_batch_push_pyramid(ea_tracker_batch *tb, const uint8_t *const *bgr, const void *const *depth, int height,
-                                      int width, const ea_options *opt, double *q_rel, double *t_rel, ea_summary *summaries,
-                                      int *aligned, bool on_device) {
-  // every check comes before a device or a stream is touched: a rejected call leaves the tracker as it was
-  if (!tb || !bgr || !depth || !q_rel || !t_rel) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+// Checks: every one comes before a device or a stream is touched -- a rejected call leaves the tracker as it was.
+static int tracker_push_check(TrackerPush *s, int height, int width) {
+  const ea_tracker_batch *tb = s->tb;
   if (height < 3 || width < 3 || height > 32768 || width > 32768 || (int64_t)height * width > 0x3fffffff)
     return fail(EA_ERR_INVALID_ARG, "image extent out of range");
   const int L = tb->levels, T = tb->halvings + L - 1;
   int rc = check_scaled_args(height, width, T);
   if (rc != EA_OK) return rc;
-  if ((height >> T) < 3 || (width >> T) < 3) return fail(EA_ERR_INVALID_ARG, "image extent out of range: the coarsest level is below 3 x 3");
-  int lo = 0, hi = 0;
-  rc = ros_thresholds(150.0, 100.0, &lo, &hi);
+  // (a coarsest level that is too small: with levels the pyramid producer's words, here; on a single level batch_frames_check's, below)
+  if (L > 1 && ((height >> T) < 3 || (width >> T) < 3))
+    return fail(EA_ERR_INVALID_ARG, "image extent out of range: the coarsest level is below 3 x 3");
+  const bool ros = s->ros();
+  rc = tb->flavour == 0 ? EA_OK : ros ? ros_thresholds(150.0, 100.0, &s->lo, &s->hi) : canny_thresholds(30.0, 90.0, &s->lo, &s->hi);
   if (rc != EA_OK) return rc;
-  if (opt) {
-    rc = check_options(*opt);
+  // (as the producers of ea_tracker's flavours: the Canny reference refuses an infinite z_scaling, the Laplacian one takes it)
+  if (tb->flavour == 1 && !(s->z_scaling <= DBL_MAX)) return fail(EA_ERR_INVALID_ARG, "z_scaling must be > 0 and finite");
+  if (s->opt) {
+    rc = check_options(*s->opt);
     if (rc != EA_OK) return rc;
   }
-  std::vector<BatchFrames> J((size_t)L);
-  std::vector<ea_batch *> batches((size_t)L);
+  s->J.resize((size_t)L);
   for (int l = 0; l < L; ++l) {
-    BatchFrames &j = J[(size_t)l];
-    batches[(size_t)l] = tb->level_batch(l);
-    j.ros = true; j.full_H = height; j.full_W = width; j.halvings = tb->halvings + l;
+    BatchFrames &j = s->J[(size_t)l];
+    j.ros = ros; j.full_H = height; j.full_W = width; j.halvings = tb->halvings + l;
     // (both sides of every slot are the pushed frame; the caller's device frames are looked at once, with level 0)
-    rc = batch_frames_check(batches[(size_t)l], bgr, depth, sizeof(float), bgr, nullptr, height >> j.halvings, width >> j.halvings, 1.0,
-                            on_device && l == 0, &j);
+    rc = batch_frames_check(tb->lv[(size_t)l].b, s->bgr, s->depth, ros ? sizeof(float) : 2, s->bgr, nullptr, height >> j.halvings,
+                            width >> j.halvings, ros ? 1.0 : s->z_scaling, s->on_device && l == 0, &j);
     if (rc != EA_OK) return rc;
-    j.on_device = on_device;
+    j.on_device = s->on_device;
   }
+  return EA_OK;
+}
 
-  const size_t n = tb->probs.size();
+// Frames in place: the jobs' memory, the table up, and every level's frame at its working resolution in that level's
+// workspace.  The one phase in which the level count selects a path: a single level is laid out by frame_stage and halved
+// one step per launch (batch_stage_ros), several by frame_pyramid and one halving chain per kind (pyramid_stage_side).
+static int tracker_push_frames(TrackerPush *s) {
+  ea_tracker_batch *tb = s->tb;
+  const float *const *depth_f32 = reinterpret_cast<const float *const *>(s->depth);
+  if (tb->levels > 1) {
+    std::vector<ea_batch *> batches;
+    for (const ea_tracker_batch::Level &lv : tb->lv) batches.push_back(lv.b);
+    FramePyramid py;
+    int64_t uploads = 0;
+    TBRC(pyramid_frames_begin(batches.data(), &s->J, tb->halvings, s->bgr, s->depth, s->bgr, &py));
+    for (BatchFrames &j : s->J) TBCHK(upload_table(&j));
+    TBRC(pyramid_stage_side(s->J, py, tb->halvings, 0, s->bgr, depth_f32, &uploads));
+    return EA_OK;
+  }
+  BatchFrames &j = s->J[0];
+  TBRC(batch_frames_begin(tb->lv[0].b, s->bgr, s->depth, s->bgr, nullptr, &j));
+  if (s->ros()) {
+    TBCHK(upload_table(&j));
+    TBRC(batch_stage_ros(j, 0, s->bgr, depth_f32));
+    return EA_OK;
+  }
+  // (Laplacian, Canny: no count comes before the transform, so the table goes up with the images in it)
+  TBRC(batch_alloc_dts(&j));
+  TBCHK(upload_table(&j));
+  if (!s->on_device) {
+    TBRC(upload_frames(j, j.ws.bgr, s->bgr, j.np * 3));
+    TBRC(upload_frames(j, j.ws.depth, s->depth, j.np * 2));
+  }
+  return EA_OK;
+}
+
+// Images: on every level the frame passes the edge detection once and the current-side tail stores every stream's image; one
+// wait, because the solves run on the batches' streams, which do not wait for the null stream.  Laplacian, Canny: the frame's
+// edge pixels are then counted WHILE the previous references are solved against the images just produced (null stream beside
+// the solve's non-blocking streams; neither touches what the other uses).
+static int tracker_push_images(TrackerPush *s) {
+  ea_tracker_batch *tb = s->tb;
+  for (int l = 0; l < tb->levels; ++l) {
+    BatchFrames &j = s->J[(size_t)l];
+    ea_batch *b = tb->lv[(size_t)l].b;
+    const FrameWs &ws = j.ws;
+    unsigned char *base = j.base;
+    int looks = 0;
+    tb->last_edge_passes++;
+    if (s->ros()) {
+      int bare = 0, rc_dt = EA_OK;
+      const int rc = batch_ros_now(&j, s->lo, s->hi, &looks, &bare, &rc_dt);
+      tb->last_rounds += looks;
+      batch_frames_set_rounds(b, looks);
+      if (l == 0) tb->last_bare = bare;
+      batch_frames_set_without_edges(b, bare);
+      TBRC(rc);
+      TBRC(rc_dt);
+      continue;
+    }
+    if (tb->flavour == 0) {
+      TBCHK(launch_edge_strength_frames(j.f, 1, ws.gray.at(base), ws.lap.at(base), nullptr));
+      TBCHK(launch_threshold_median_frames(j.f, ws.lap.at(base), 35, 1, ws.mask.at(base), nullptr));
+    } else {
+      const int rc = batch_canny(j, 1, false, s->lo, s->hi, /*l2_bgr=*/0, &looks);
+      tb->last_rounds += looks;
+      batch_frames_set_rounds(b, looks);
+      TBRC(rc);
+    }
+    TBCHK(launch_chamfer_frames(j.f, (tb->flavour == 0 ? ws.mask : ws.inv).at(base), ws.G.at(base), ws.scan.at(base), ws.dist.at(base),
+                                nullptr, ws.minmax.at(base), nullptr));
+    TBCHK(launch_dt_store_frames(j.dtype, j.f, ws.dist.at(base), ws.minmax.at(base), 1, 0.0, 1.0, nullptr));
+  }
+  TBCHK(hipStreamSynchronize(nullptr));
+  for (int l = 0; l < tb->levels; ++l) {
+    const std::vector<unsigned char> &none = s->J[(size_t)l].no_image;
+    for (size_t i = 0; i < tb->st.size(); ++i)
+      if (none.empty() || !none[i]) dt_landed(tb->lv[(size_t)l].probs[i]);
+  }
+  if (!s->ros()) TBRC(batch_counts_queue(&s->J[0], s->ref_edges(s->J[0]), s->ref_threshold()));
+  return EA_OK;
+}
+
+// Priors: a stream is aligned by level 0's rule and starts from its last relative pose; with a motion prior on, every
+// usable level of every aligned stream carries it, centred on that pose.
+static int tracker_push_priors(TrackerPush *s) {
+  ea_tracker_batch *tb = s->tb;
+  const size_t n = tb->st.size();
+  for (size_t i = 0; i < n; ++i)
+    if (tb->st[i].frames > 0 && s->usable(0, i)) s->al.push_back((int)i);
+  s->q0.resize(4 * n); s->t0.resize(3 * n); s->qs.resize(4 * n); s->ts.resize(3 * n);
+  s->stopped.assign(n, 0); s->is_al.assign(n, 0);
+  if (tb->key_on) s->kstats.assign(n, ea_pose_stats{});
+  for (int a : s->al) {
+    const size_t i = (size_t)a;
+    TrackerStream &st = tb->st[i];
+    s->is_al[i] = 1;
+    std::memcpy(&s->q0[4 * i], st.q, sizeof(st.q));
+    std::memcpy(&s->t0[3 * i], st.t, sizeof(st.t));
+    if (tb->sigma_rot > 0.0 || tb->sigma_trans > 0.0) {
+      for (int l = 0; l < tb->levels; ++l)
+        if (s->usable(l, i)) TBRC(motion_prior_install(tb->lv[(size_t)l].probs[i], tb->sigma_rot, tb->sigma_trans, st.q, st.t));
+      st.motion_set = true;
+      st.installed = tb->lv[0].probs[i]->prior;
+    }
+  }
+  s->qc = s->q0; s->tc = s->t0;
+  return EA_OK;
+}
+
+// the poses of a group's streams, in the group's order, as a batch call takes them
+static void tracker_group_poses(const std::vector<int> &grp, const std::vector<double> &q, const std::vector<double> &t,
+                                std::vector<double> *qg, std::vector<double> *tg) {
+  qg->resize(4 * grp.size()); tg->resize(3 * grp.size());
+  for (size_t k = 0; k < grp.size(); ++k) {
+    std::memcpy(&(*qg)[4 * k], &q[4 * (size_t)grp[k]], 4 * sizeof(double));
+    std::memcpy(&(*tg)[3 * k], &t[3 * (size_t)grp[k]], 3 * sizeof(double));
+  }
+}
+
+// Descent: ea_solve_pyramid per stream, run as batch solves -- the coarsest level first, on each level the streams still
+// descending that can use it, grouped by kernel family, the pose carried down.  A failed solve stops its stream's descent: it
+// keeps its prior.  A single level is this loop run once.
+static int tracker_push_descent(TrackerPush *s) {
+  ea_tracker_batch *tb = s->tb;
+  const size_t n = tb->st.size();
+  std::vector<double> qg, tg;
+  for (int l = tb->levels - 1; l >= 0; --l) {
+    std::vector<int> members;
+    for (int i : s->al)
+      if (!s->stopped[(size_t)i] && s->usable(l, (size_t)i)) members.push_back(i);
+    for (const std::vector<int> &grp : tracker_batch_groups(tb, members, l)) {
+      ea_batch *solver = nullptr;
+      TBRC(tracker_batch_solver(tb, grp, &solver, l));
+      std::vector<ea_summary> sg(grp.size());
+      tracker_group_poses(grp, s->qc, s->tc, &qg, &tg);
+      TBRC(ea_batch_solve(solver, s->opt, qg.data(), tg.data(), sg.data()));
+      for (size_t k = 0; k < grp.size(); ++k) {
+        const size_t i = (size_t)grp[k];
+        tb->last_sums[(size_t)l * n + i] = sg[k];
+        if (s->summaries) s->summaries[i] = sg[k];  // (the finest level the descent reaches comes last)
+        if (sg[k].termination == EA_FAILURE) { s->stopped[i] = 1; continue; }
+        std::memcpy(&s->qc[4 * i], &qg[4 * k], 4 * sizeof(double));
+        std::memcpy(&s->tc[3 * i], &tg[3 * k], 3 * sizeof(double));
+      }
+    }
+  }
+  for (int a : s->al) {
+    const size_t i = (size_t)a;
+    std::memcpy(&s->qs[4 * i], s->stopped[i] ? &s->q0[4 * i] : &s->qc[4 * i], 4 * sizeof(double));
+    std::memcpy(&s->ts[3 * i], s->stopped[i] ? &s->t0[3 * i] : &s->tc[3 * i], 3 * sizeof(double));
+  }
+  return EA_OK;
+}
+
+// Covariance and (keyframe mode) pose statistics: at level 0, at the returned poses, per kernel family as the solves, from the
+// points and images the solves used -- both calls return once their results have landed, and the scatter that overwrites the
+// points is queued behind that.  A stopped descent has no pose to take either at: its covariance reports why = 4, its
+// statistics stay zero, and a group without a surviving stream makes no call.
+static int tracker_push_covariance(TrackerPush *s) {
+  ea_tracker_batch *tb = s->tb;
+  if (!tb->cov_on && !tb->key_on) return EA_OK;
+  std::vector<double> qg, tg;
+  for (const std::vector<int> &grp : tracker_batch_groups(tb, s->al, 0)) {
+    const size_t ng = grp.size();
+    ea_batch *solver = nullptr;
+    TBRC(tracker_batch_solver(tb, grp, &solver, 0));
+    tracker_group_poses(grp, s->qs, s->ts, &qg, &tg);
+    size_t ok = 0;
+    for (int i : grp) ok += s->stopped[(size_t)i] ? 0 : 1;
+    if (tb->cov_on) {
+      std::vector<ea_covariance> covs(ng);
+      std::memset(covs.data(), 0, ng * sizeof(ea_covariance));
+      if (ok > 0) TBRC(ea_batch_covariance(solver, qg.data(), tg.data(), &tb->cov_opt, covs.data()));
+      for (size_t k = 0; k < ng; ++k) {
+        TrackerStream &st = tb->st[(size_t)grp[k]];
+        st.cov_last = covs[k];
+        if (s->stopped[(size_t)grp[k]]) {
+          std::memset(&st.cov_last, 0, sizeof(st.cov_last));
+          st.cov_last.why = 4;
+        }
+        st.cov_valid = true;
+      }
+    }
+    if (tb->key_on && ok > 0) {
+      // how much of each reference is still seen at the returned pose: one call for the group, on the batch that solved it
+      std::vector<ea_pose_stats> stg(ng);
+      TBRC(ea_batch_pose_stats(solver, qg.data(), tg.data(), tb->key_prm.margin, tb->key_prm.inlier_residual, stg.data()));
+      for (size_t k = 0; k < ng; ++k)
+        if (!s->stopped[(size_t)grp[k]]) s->kstats[(size_t)grp[k]] = stg[k];
+    }
+  }
+  return EA_OK;
+}
+
+// References: on every level the frame's edge points become the reference of every stream -- in keyframe mode (a single level:
+// ea_tracker_batch_set_keyframes) of the streams whose rule says so (keyframe_decide); a ROS stream whose frame has no edge
+// keeps what it holds.  Laplacian, Canny: the counts queued beside the solve come back first (a wait).  Then the last wait.
+static int tracker_push_references(TrackerPush *s) {
+  ea_tracker_batch *tb = s->tb;
+  const size_t n = tb->st.size();
+  s->take.assign(n, 1);
+  s->why.assign(n, 0);
+  bool any_take = true;
+  if (tb->key_on) {
+    const std::vector<unsigned char> &none = s->J[0].no_image;
+    any_take = false;
+    for (size_t i = 0; i < n; ++i) {
+      const bool bare = !none.empty() && none[i];
+      s->why[i] = bare ? 0 : keyframe_decide(s->kstats[i], tb->key_prm, tb->st[i].key.age + 1, s->is_al[i] != 0, s->stopped[i] != 0);
+      s->take[i] = s->why[i] != 0;
+      any_take = any_take || s->take[i];
+    }
+  }
+  for (BatchFrames &j : s->J) {
+    if (!s->ros() && any_take) TBRC(batch_counts_fetch(&j));
+    TBRC(batch_ref_room(&j, tb->key_on ? s->take.data() : nullptr));
+    if (!any_take) continue;
+    if (s->ros()) {
+      TBRC(batch_ros_scatter(&j));
+    } else {
+      TBCHK(upload_table(&j));
+      TBRC(batch_ref_scatter(j, s->ref_edges(j), s->ref_threshold(), s->z_scaling));
+    }
+  }
+  TBCHK(hipDeviceSynchronize());
+  for (int l = 0; l < tb->levels; ++l)
+    for (size_t i = 0; i < n; ++i)
+      if (s->take[i]) ref_points_landed(tb->lv[(size_t)l].probs[i], s->J[(size_t)l].slots[i].capacity);
+  return EA_OK;
+}
+
+// Bookkeeping: priors and frame counts advance only with the new references in place
+static void tracker_push_book(const TrackerPush &s, double *q_rel, double *t_rel, int *aligned) {
+  ea_tracker_batch *tb = s.tb;
+  for (size_t i = 0; i < tb->st.size(); ++i) {
+    TrackerStream &st = tb->st[i];
+    if (s.is_al[i]) {
+      std::memcpy(st.q, &s.qs[4 * i], sizeof(st.q));
+      std::memcpy(st.t, &s.ts[3 * i], sizeof(st.t));
+      if (aligned) aligned[i] = 1;
+    }
+    if (tb->key_on) {
+      // the pose solved in this push against the keyframe in use during it (an unaligned stream: the identity); a stream that
+      // took the frame starts its next solve at the identity, a kept one at the pose just stored
+      const double q_id[4] = {1, 0, 0, 0}, t_id[3] = {0, 0, 0};
+      std::memcpy(q_rel + 4 * i, s.is_al[i] ? st.q : q_id, sizeof(st.q));
+      std::memcpy(t_rel + 3 * i, s.is_al[i] ? st.t : t_id, sizeof(st.t));
+      st.key.replaced = s.why[i];
+      st.key.stats = s.kstats[i];
+      if (s.take[i]) {
+        std::memcpy(st.q, q_id, sizeof(st.q));
+        std::memcpy(st.t, t_id, sizeof(st.t));
+        st.key.age = 0;
+        st.key.keyframe_push = tb->pushes;
+        tb->last_taken++;
+      } else if (s.is_al[i]) {
+        st.key.age += 1;
+      }
+    } else {
+      std::memcpy(q_rel + 4 * i, st.q, sizeof(st.q));
+      std::memcpy(t_rel + 3 * i, st.t, sizeof(st.t));
+    }
+    st.frames += 1;
+  }
+  tb->last_aligned = (int)s.al.size();
+}
+
+// The push of every flavour and level count: the phases above, in order.  q_rel, t_rel, summaries, aligned: as ea_hip.h says.
+static int tracker_batch_push(ea_tracker_batch *tb, const uint8_t *const *bgr, const void *const *depth, int height, int width,
+                              double z_scaling, const ea_options *opt, double *q_rel, double *t_rel, ea_summary *summaries,
+                              int *aligned, bool on_device) {
+  if (!tb || !bgr || !depth || !q_rel || !t_rel) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  TrackerPush s;
+  s.tb = tb; s.bgr = bgr; s.depth = depth; s.z_scaling = z_scaling; s.opt = opt; s.summaries = summaries; s.on_device = on_device;
+  int rc = tracker_push_check(&s, height, width);
+  if (rc != EA_OK) return rc;
+  const size_t n = tb->st.size();
   tb->pushes++;
   tb->last_aligned = tb->last_bare = tb->last_rounds = tb->last_edge_passes = tb->last_taken = 0;
   for (size_t i = 0; i < n; ++i) tb->st[i].cov_valid = false;
   if (aligned) std::fill(aligned, aligned + n, 0);
   if (summaries) std::memset(summaries, 0, n * sizeof(*summaries));
   std::memset(tb->last_sums.data(), 0, tb->last_sums.size() * sizeof(ea_summary));
-  auto failed = [tb](int code) { return tracker_batch_fail(tb, code); };
-#define TBCHK(expr)                                                                                              \
-  do {                                                                                                           \
-    const hipError_t e_ = (expr);                                                                                \
-    if (e_ != hipSuccess) { (void)fail(EA_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); return failed(EA_ERR_HIP); } \
-  } while (0)
-#define TBRC(expr)                      \
-  do {                                  \
-    const int rc_ = (expr);             \
-    if (rc_ != EA_OK) return failed(rc_); \
-  } while (0)
-
-  FramePyramid py;
-  TBRC(pyramid_frames_begin(batches.data(), &J, tb->halvings, bgr, depth, bgr, &py));
-  // ---- the frame, once: up, down the chain, and on every level the edge pass and the current-side tail
-  for (BatchFrames &j : J) TBCHK(upload_table(&j));
-  int64_t uploads = 0;
-  TBRC(pyramid_stage_side(J, py, tb->halvings, 0, bgr, reinterpret_cast<const float *const *>(depth), &uploads));
-  for (int l = 0; l < L; ++l) {
-    BatchFrames &j = J[(size_t)l];
-    const FrameWs &ws = j.ws;
-    unsigned char *base = j.base;
-    int looks = 0;
-    tb->last_edge_passes++;
-    TBCHK(launch_canny_frames(j.f, 1, 0, lo, hi, /*l2_bgr=*/1, ws.gray.at(base), ws.mag.at(base), ws.dir.at(base), ws.label.at(base),
-                              ws.edges.at(base), ws.inv.at(base), ws.changed.at(base), j.h_flags, &looks, nullptr));
-    tb->last_rounds += looks;
-    batch_frames_set_rounds(batches[(size_t)l], looks);
-    TBRC(batch_counts_back(&j, ws.edges, 0));
-    int bare = 0;
-    j.no_image.assign(n, 0);
-    for (size_t i = 0; i < n; ++i)
-      if (j.h_totals[i] == 0) { j.no_image[i] = 1; ++bare; }
-    if (l == 0) tb->last_bare = bare;
-    batch_frames_set_without_edges(batches[(size_t)l], bare);
-    TBRC(batch_alloc_dts(&j));
-    if ((size_t)bare < n) {
-      TBCHK(upload_table(&j));
-      TBCHK(launch_chamfer_frames(j.f, ws.inv.at(base), ws.G.at(base), ws.scan.at(base), ws.dist.at(base), ws.dist.at<float>(base),
-                                  ws.minmax.at(base), nullptr));
-      TBCHK(launch_dt_store_stack(j.dtype, j.f, ws.dist.at<float>(base), ws.minmax.at(base), 1, 0.0, 255.0, nullptr));
-    }
-  }
-  // the images are complete before a solve reads them on the batches' streams, which do not wait for the null stream
-  TBCHK(hipStreamSynchronize(nullptr));
-  for (int l = 0; l < L; ++l)
-    for (size_t i = 0; i < n; ++i)
-      if (!J[(size_t)l].no_image[i]) dt_landed(tb->level_probs(l)[i]);
-
-  // ---- the solve of the aligned streams, from their last relative poses, down their usable levels
-  auto usable = [&](int l, size_t i) { return tb->level_probs(l)[i]->n > 0 && !J[(size_t)l].no_image[i]; };
-  std::vector<int> al;
-  for (size_t i = 0; i < n; ++i)
-    if (tb->st[i].frames > 0 && usable(0, i)) al.push_back((int)i);
-  const size_t na = al.size();
-  // per stream: the pose its solve started from, the one it carries down, and the one it returned
-  std::vector<double> q0(4 * n), t0(3 * n), qc(4 * n), tc(3 * n), qs(4 * n), ts(3 * n);
-  std::vector<unsigned char> stopped(n, 0);
-  for (int i : al) {
-    TrackerStream &s = tb->st[(size_t)i];
-    std::memcpy(&q0[4 * (size_t)i], s.q, sizeof(s.q));
-    std::memcpy(&t0[3 * (size_t)i], s.t, sizeof(s.t));
-    if (tb->sigma_rot > 0.0 || tb->sigma_trans > 0.0) {
-      for (int l = 0; l < L; ++l)
-        if (usable(l, (size_t)i)) TBRC(motion_prior_install(tb->level_probs(l)[(size_t)i], tb->sigma_rot, tb->sigma_trans, s.q, s.t));
-      s.motion_set = true;
-      s.installed = tb->probs[(size_t)i]->prior;
-    }
-  }
-  qc = q0; tc = t0;
-  for (int l = L - 1; l >= 0; --l) {
-    std::vector<int> members;
-    for (int i : al)
-      if (!stopped[(size_t)i] && usable(l, (size_t)i)) members.push_back(i);
-    for (const std::vector<int> &grp : tracker_batch_groups(tb, members, l)) {
-      const size_t ng = grp.size();
-      ea_batch *solver = nullptr;
-      TBRC(tracker_batch_solver(tb, grp, &solver, l));
-      std::vector<double> qg(4 * ng), tg(3 * ng);
-      std::vector<ea_summary> sg(ng);
-      for (size_t k = 0; k < ng; ++k) {
-        std::memcpy(&qg[4 * k], &qc[4 * (size_t)grp[k]], 4 * sizeof(double));
-        std::memcpy(&tg[3 * k], &tc[3 * (size_t)grp[k]], 3 * sizeof(double));
-      }
-      TBRC(ea_batch_solve(solver, opt, qg.data(), tg.data(), sg.data()));
-      for (size_t k = 0; k < ng; ++k) {
-        const size_t i = (size_t)grp[k];
-        tb->last_sums[(size_t)l * n + i] = sg[k];
-        if (summaries) summaries[i] = sg[k];  // (the finest level the descent reaches comes last)
-        if (sg[k].termination == EA_FAILURE) { stopped[i] = 1; continue; }
-        std::memcpy(&qc[4 * i], &qg[4 * k], 4 * sizeof(double));
-        std::memcpy(&tc[3 * i], &tg[3 * k], 3 * sizeof(double));
-      }
-    }
-  }
-  // (a descent that stopped in a failed level: the stream keeps its prior, as after a failed solve on a single level)
-  for (int a : al) {
-    const size_t i = (size_t)a;
-    std::memcpy(&qs[4 * i], stopped[i] ? &q0[4 * i] : &qc[4 * i], 4 * sizeof(double));
-    std::memcpy(&ts[3 * i], stopped[i] ? &t0[3 * i] : &tc[3 * i], 3 * sizeof(double));
-  }
-  if (tb->cov_on)
-    // at level 0, at the returned poses, per kernel family as the solves; a stopped descent has no pose to take one at (why = 4)
-    for (const std::vector<int> &grp : tracker_batch_groups(tb, al, 0)) {
-      const size_t ng = grp.size();
-      ea_batch *solver = nullptr;
-      TBRC(tracker_batch_solver(tb, grp, &solver, 0));
-      std::vector<double> qg(4 * ng), tg(3 * ng);
-      size_t ok = 0;
-      for (size_t k = 0; k < ng; ++k) {
-        std::memcpy(&qg[4 * k], &qs[4 * (size_t)grp[k]], 4 * sizeof(double));
-        std::memcpy(&tg[3 * k], &ts[3 * (size_t)grp[k]], 3 * sizeof(double));
-        ok += stopped[(size_t)grp[k]] ? 0 : 1;
-      }
-      std::vector<ea_covariance> covs(ng);
-      std::memset(covs.data(), 0, ng * sizeof(ea_covariance));
-      if (ok > 0) TBRC(ea_batch_covariance(solver, qg.data(), tg.data(), &tb->cov_opt, covs.data()));
-      for (size_t k = 0; k < ng; ++k) {
-        TrackerStream &s = tb->st[(size_t)grp[k]];
-        s.cov_last = covs[k];
-        if (stopped[(size_t)grp[k]]) {
-          std::memset(&s.cov_last, 0, sizeof(s.cov_last));
-          s.cov_last.why = 4;
-        }
-        s.cov_valid = true;
-      }
-    }
-
-  // ---- on every level the frame's edge points become every stream's reference
-  for (int l = 0; l < L; ++l) {
-    BatchFrames &j = J[(size_t)l];
-    TBRC(batch_ref_room(&j));
-    TBCHK(upload_table(&j));
-    if (j.max_total > 0) TBCHK(launch_edge_scatter_ros_stack(j.dtype, j.f, j.ws.edges.at(j.base), j.ws.counts.at(j.base), nullptr));
-    TBCHK(launch_depth_weights_frames(j.dtype, j.f, j.max_weighted, nullptr));
-  }
-  TBCHK(hipDeviceSynchronize());
-#undef TBCHK
-#undef TBRC
-  for (int l = 0; l < L; ++l)
-    for (size_t i = 0; i < n; ++i) ref_points_landed(tb->level_probs(l)[i], J[(size_t)l].slots[i].capacity);
-  for (int a : al) {
-    const size_t i = (size_t)a;
-    std::memcpy(tb->st[i].q, &qs[4 * i], sizeof(tb->st[i].q));
-    std::memcpy(tb->st[i].t, &ts[3 * i], sizeof(tb->st[i].t));
-    if (aligned) aligned[i] = 1;
-  }
-  for (size_t i = 0; i < n; ++i) {
-    std::memcpy(q_rel + 4 * i, tb->st[i].q, sizeof(tb->st[i].q));
-    std::memcpy(t_rel + 3 * i, tb->st[i].t, sizeof(tb->st[i].t));
-    tb->st[i].frames += 1;
-  }
-  tb->last_aligned = (int)na;
+  // (a phase that fails has dropped every stream: tracker_batch_fail)
+  for (int (*phase)(TrackerPush *) : {tracker_push_frames, tracker_push_images, tracker_push_priors, tracker_push_descent,
+                                      tracker_push_covariance, tracker_push_references})
+    if ((rc = phase(&s)) != EA_OK) return rc;
+  tracker_push_book(s, q_rel, t_rel, aligned);
   return EA_OK;
 }
 
 extern "C" int ea_tracker_batch_push_frames(ea_tracker_batch *tb, const uint8_t *const *bgr, const void *const *depth, int height,
                                             int width, double z_scaling, const ea_options *opt, double *q_rel, double *t_rel,
                                             ea_summary *summaries, int *aligned) {
-  if (tb && tb->levels > 1) return tracker_batch_push_pyramid(tb, bgr, depth, height, width, opt, q_rel, t_rel, summaries, aligned, false);
   return tracker_batch_push(tb, bgr, depth, height, width, z_scaling, opt, q_rel, t_rel, summaries, aligned, false);
 }
 
 extern "C" int ea_tracker_batch_push_frames_device(ea_tracker_batch *tb, const uint8_t *const *bgr, const void *const *depth,
                                                    int height, int width, double z_scaling, const ea_options *opt, double *q_rel,
                                                    double *t_rel, ea_summary *summaries, int *aligned) {
-  if (tb && tb->levels > 1) return tracker_batch_push_pyramid(tb, bgr, depth, height, width, opt, q_rel, t_rel, summaries, aligned, true);
   return tracker_batch_push(tb, bgr, depth, height, width, z_scaling, opt, q_rel, t_rel, summaries, aligned, true);
 }
 
 extern "C" int ea_tracker_batch_reset(ea_tracker_batch *tb, int i) {
   if (!tb) return fail(EA_ERR_INVALID_ARG, "NULL argument");
-  if (i >= (int)tb->probs.size()) return fail(EA_ERR_INVALID_ARG, "no such stream");
+  if (i >= (int)tb->st.size()) return fail(EA_ERR_INVALID_ARG, "no such stream");
   HIPCHK(hipSetDevice(tb->device));
-  for (size_t s = 0; s < tb->probs.size(); ++s) {
+  for (size_t s = 0; s < tb->st.size(); ++s) {
     if (i >= 0 && s != (size_t)i) continue;
     tracker_stream_drop(tb, s);  // (its keyframe state too)
     const double q[4] = {1, 0, 0, 0};
@@ -2218,7 +2135,7 @@ extern "C" int ea_tracker_batch_set_motion_prior(ea_tracker_batch *tb, double si
   if (sigma_rot == 0.0 && sigma_trans == 0.0)
     for (size_t i = 0; i < tb->st.size(); ++i)
       if (tb->st[i].motion_set) {
-        for (int l = 0; l < tb->levels; ++l) motion_prior_clear(tb->level_probs(l)[i], tb->st[i].installed);
+        for (const ea_tracker_batch::Level &lv : tb->lv) motion_prior_clear(lv.probs[i], tb->st[i].installed);
         tb->st[i].motion_set = false;
       }
   tb->sigma_rot = sigma_rot;

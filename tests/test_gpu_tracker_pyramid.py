@@ -199,6 +199,42 @@ def test_covariance_and_motion_prior(hip):
         _close(tb, refs)
 
 
+def test_failed_descent_keeps_the_prior(hip):
+    """A descent that stops above level 0.  The input is the single-level test_failed_solve_keeps_the_prior's -- stream 0's
+    second frame has zeros, negatives and NaN sprinkled into its depth -- with that frame's NaN replaced by +inf: at full
+    extent and halvings 0 the NaN fails level 0 alone (measured: level 1 solved in 39 iterations, level 0 FAILURE), because
+    the halving step that makes level 1 turns NaN into 0; an infinite depth passes it, its 2 x 2 mean is infinite, and a
+    point at infinity projects to NaN on every level.  So the solve of push 3 ends in EA_FAILURE on the coarsest level, which
+    the descent reaches first: nothing is solved below it, the stream keeps the prior push 2 gave it -- aligned all the
+    same, covariance why = 4 -- and is solved again at push 4, while its neighbours go on; the manual loop says the same."""
+    full, halvings, levels = (74, 140), 0, 2
+    tb, refs = _make(hip, full, halvings, levels, hip.EA_F64, cov=True)
+    try:
+        pushes = _ros_pushes(full[0], full[1], halvings, N, 4, 63, nan_depth={(1, 0)})
+        spoiled = pushes[1][1][0]
+        assert np.isnan(spoiled).any()
+        spoiled[np.isnan(spoiled)] = np.inf
+        logs, poses = [], []
+        for k, (bgr, depth) in enumerate(pushes):
+            logs.append([])
+            aligned = _compare_push(hip, tb, refs, bgr, depth, ("failed descent", "push", k + 1), logs[-1])
+            assert aligned == [int(k > 0)] * N
+            poses.append((refs[0].q.copy(), refs[0].t.copy()))       # (_compare_push: the poses the push returned)
+            if k == 2:
+                assert tb.last_covariance(0)["why"] == 4
+        print("TRACKER_PYRAMID failed descent: (stream, usable levels, (termination, iterations) per level) per push %s" % logs)
+        stream, usable, per_level = logs[2][0]
+        first = max(usable)                                           # the level the descent reached first
+        assert stream == 0 and first == levels - 1 and per_level[first][0] == hip.FAILURE, logs[2]
+        assert all(per_level[l] is None for l in range(first)), logs[2]
+        assert np.array_equal(poses[2][0], poses[1][0]) and np.array_equal(poses[2][1], poses[1][1])
+        assert not np.array_equal(poses[2][0], IDENTITY[0])          # (a prior worth keeping)
+        assert all(x is not None and x[0] != hip.FAILURE for x in logs[3][0][2]), logs[3]      # push 4: solved again
+        assert tb.last_covariance(0)["why"] in (0, 1, 2, 3)
+    finally:
+        _close(tb, refs)
+
+
 def test_levels_one_equals_the_single_level_tracker(hip):
     full, halvings, n = (74, 140), 1, 3
     H, W = full[0] >> halvings, full[1] >> halvings
