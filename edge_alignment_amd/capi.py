@@ -63,6 +63,7 @@ EXPORTED = [
     "ea_problem_overlay", "ea_batch_overlay", "ea_batch_overlay_device",
     "ea_problem_set_now_depth", "ea_problem_set_now_depth_device", "ea_batch_set_now_depth", "ea_batch_set_now_depth_device",
     "ea_default_depth_gate_params", "ea_problem_depth_gate", "ea_batch_depth_gate", "ea_batch_depth_gate_device",
+    "ea_tracker_batch_set_depth_gate", "ea_tracker_batch_last_depth_gate",
 ]
 
 # measurement hooks (edge_alignment_amd/csrc/ea_hip_dev.h): bound by bench.py, the A/B scripts and the tests that pin the
@@ -431,6 +432,8 @@ def load():
     L.ea_problem_depth_gate.argtypes = [vp, dp, dgp, vp, C.c_int64, dgs]
     L.ea_batch_depth_gate.argtypes = [vp, dp, dgp, vp, C.c_int64, dgs]
     L.ea_batch_depth_gate_device.argtypes = [vp, dp, dgp, vp, C.c_int64, dgs]
+    L.ea_tracker_batch_set_depth_gate.argtypes = [vp, dgp]
+    L.ea_tracker_batch_last_depth_gate.argtypes = [vp, C.c_int, C.c_int, dgs]
     _lib = L
     return L
 
@@ -1216,6 +1219,22 @@ class TrackerBatch:
         s = KeyframeState()
         _check(load().ea_tracker_batch_keyframe_state(self._h, int(i), C.byref(s)))
         return {"keyframe_push": s.keyframe_push, "age": s.age, "replaced": s.replaced, "stats": pose_stats_to_dict(s.stats)}
+
+    def set_depth_gate(self, params="default", **fields):
+        """the depth gate in front of every solve of a push (ea_tracker_batch_set_depth_gate): set_depth_gate(None) = off;
+        otherwise ea_default_depth_gate_params with the given fields of ea_depth_gate_params replaced (radius, abs_tol, rel_tol,
+        w_occluded, w_free, w_unknown, apply).  Only while no stream holds a reference."""
+        if params is None:
+            _check(load().ea_tracker_batch_set_depth_gate(self._h, None))
+            return
+        prm = default_depth_gate_params(**fields)
+        _check(load().ea_tracker_batch_set_depth_gate(self._h, C.byref(prm)))
+
+    def last_depth_gate(self, i, level=0):
+        """the gate's counts of stream i on `level` in the last push (depth_gate_stats_to_dict); zeros when it was not gated there"""
+        st = DepthGateStats()
+        _check(load().ea_tracker_batch_last_depth_gate(self._h, int(level), int(i), C.byref(st)))
+        return depth_gate_stats_to_dict(st)
 
     def info(self, key):
         v = C.c_int64()

@@ -173,6 +173,16 @@ int64_t problem_points(const ea_problem *p);
 int check_device_pointer(int device, const void *ptr, const char *what);
 // rows stored in tile order (ea_problem_set_point_order) back in the caller's order: out[order[i]] = tmp[i], elem_bytes each
 void scatter_to_callers_order(const std::vector<int32_t> &order, size_t elem_bytes, const void *tmp, void *out);
+// ea_segments.hip's, for the multi-stream tracker (ea_frames.hip): the depth gate of ea_batch_depth_gate on depth images the
+// caller names, one per problem of the batch in batch order, all of one kind (EA_DEPTH_*), z_scaling and shift (ea_depth_gate.h:
+// the image is 2^shift times the problem's DT extent); complete on the device when the call is made
+struct GateImages {
+  int kind = 0, shift = 0;
+  double z_scaling = 1.0;
+  const void *const *depth = nullptr;
+};
+int batch_depth_gate_images(ea_batch *b, const double *b_T_a, const ea_depth_gate_params *prm, const GateImages &img,
+                            ea_depth_gate_stats *stats);
 // ea_segments.hip's, for ea_batch_solve: the losses of ea_problem_set_loss_auto_scale set from the residuals at poses q, t
 int auto_scale_losses(ea_batch *b, const double *q, const double *t);
 

@@ -2,6 +2,8 @@
 // validity and conversion of a depth sample of either kind, the projection of step B, the window scan, the classification and
 // the weight.  Shared by the kernel (ea_depth_gate_kernel), the host driver (ea_segments.hip) and a host shim without a device
 // (tests/depth_gate_host_shim.cpp), which holds it to tests/depth_gate_ref.py bit for bit.
+// Step 3b -- a depth image at 2^shift times the DT extent (gate_scaled_pixel, depth_gate_shift) -- is held to
+// tests/depth_gate_scaled_ref.py by a stand-alone host program (tests/depth_gate_scaled_host_shim.cpp).
 //
 // include/ea_hip.h states the arithmetic.  Everything here is fp64 in that order with no contracted multiply-add (EA_FP_EXACT,
 // ea_reproject.h; the g++ shim is built with -ffp-contract=off) and IEEE divisions.
@@ -37,6 +39,7 @@ namespace ea {
 constexpr int kDepthGateThreads = 256;
 constexpr int kDepthGateMaxRadius = 3;
 constexpr int kDepthGateClasses = 6;
+constexpr int kDepthGateMaxShift = 8;
 
 // ---- argument checks (host; NULL = fine, else what is wrong) ---------------------------------------------------------------
 
@@ -84,12 +87,13 @@ struct DepthGateSeg {
   int64_t row;          // first class byte of the segment in the rows layout: ProblemDesc::row_begin of the term
   int32_t n, term;
   double M[12];         // step A (ea_reproject.h: reproject_matrix)
-  const void *depth;    // the problem's now-depth, H x W of the call's kind (the extent is the descriptor's)
+  const void *depth;    // the problem's now-depth of the call's kind, (H << shift) x (W << shift), H x W the descriptor's
   double z_scaling;     // U16: metres = d / z_scaling
   void *weights;        // apply: the problem's weights behind z, in the problem dtype; NULL: nothing is written
   unsigned char *cls;   // class bytes of the segment's first point, or NULL
   double dw_z_ref;      // depth weighting of the problem (power 0: dd = 1)
-  int32_t dw_power, pad;
+  int32_t dw_power;
+  int32_t shift;        // step 3b: the depth image is 2^shift times the DT extent, 0..kDepthGateMaxShift
 };
 
 // ---- a depth sample: validity and conversion -----------------------------------------------------------------------------------
@@ -138,6 +142,25 @@ EA_HD EA_INLINE bool gate_inside(double u, double v, int H, int W, int *iu_out, 
   const int iu = finite ? (int)u : -1, iv = finite ? (int)v : -1;  // `(int)`: truncation toward zero
   *iu_out = iu; *iv_out = iv;
   return finite && iu >= 0 && iu < W && iv >= 0 && iv < H && !(u <= -1.0) && !(v <= -1.0);
+}
+
+// step 3b: the pixel of a depth image at 2^shift times the DT extent under the inside point (u, v).  c = (2^shift - 1) / 2 is
+// the centre of the 2^shift x 2^shift block of depth pixels whose mean DT pixel 0 is (exact); u * 2^shift is exact, the
+// addition rounds once.  shift = 0: U = u.  (u, v) inside: |U| < 2^31 for every extent the host accepts.
+EA_HD EA_INLINE void gate_scaled_pixel(double u, double v, int shift, int *iu_out, int *iv_out) {
+  EA_FP_EXACT
+  const double scale = (double)(1 << shift), c = (scale - 1.0) * 0.5;
+  const double U = u * scale + c, V = v * scale + c;
+  *iu_out = (int)U; *iv_out = (int)V;
+}
+
+// the shift s with (nd_H, nd_W) == (H << s, W << s) and H * W << 2 s <= 2^30, or -1 (host: the extent rule of ea_*_depth_gate)
+inline int depth_gate_shift(int H, int W, int nd_H, int nd_W) {
+  for (int s = 0; s <= kDepthGateMaxShift; ++s) {
+    if (((int64_t)H * W) << (2 * s) > ((int64_t)1 << 30)) break;
+    if (((int64_t)H << s) == nd_H && ((int64_t)W << s) == nd_W) return s;
+  }
+  return -1;
 }
 
 // ---- steps 4-5: the window scan and the classification --------------------------------------------------------------------------
@@ -210,18 +233,19 @@ EA_HD EA_INLINE int gate_classify(double d, double bz, double abs_tol, double re
   return diff < 0.0 ? EA_GATE_OCCLUDED : EA_GATE_FREE;
 }
 
-// steps 1-5 for one point
+// steps 1-5 for one point; H x W: the DT extent, img: (H << shift) x (W << shift)
 template <typename RAW, int R, typename PTR = const RAW *>
 EA_HD EA_INLINE int gate_point(const double *M, double x, double y, double z, double fx, double fy, double cx, double cy,
                             const double *dist, PTR img, int H, int W, double z_scaling, double abs_tol,
-                            double rel_tol) {
+                            double rel_tol, int shift = 0) {
   double bz, u, v;
   gate_project(M, x, y, z, fx, fy, cx, cy, dist, &bz, &u, &v);
   if (gate_behind(bz)) return EA_GATE_BEHIND;
   int iu, iv;
   if (!gate_inside(u, v, H, W, &iu, &iv)) return EA_GATE_OUTSIDE;
+  gate_scaled_pixel(u, v, shift, &iu, &iv);
   double d;
-  if (!gate_scan<RAW, R, PTR>(img, H, W, iu, iv, z_scaling, bz, &d)) return EA_GATE_UNKNOWN;
+  if (!gate_scan<RAW, R, PTR>(img, H << shift, W << shift, iu, iv, z_scaling, bz, &d)) return EA_GATE_UNKNOWN;
   return gate_classify(d, bz, abs_tol, rel_tol);
 }
 

@@ -1544,7 +1544,9 @@ extern "C" int ea_resize_half_levels(int device, int kind, const void *src, int 
 //                     -> [Laplacian, Canny: count + scan queued, it runs beside the solves]
 //   priors            tracker_push_priors: the aligned streams (level 0's rule), their motion priors on every usable level
 //   descent           tracker_push_descent: for l = L - 1 .. 0 ea_batch_solve of the streams still descending that can use l,
-//                     on the batches' own streams, the pose carried down; a single level is this loop run once
+//                     on the batches' own streams, the pose carried down; a single level is this loop run once.  With a
+//                     depth gate set (ea_tracker_batch_set_depth_gate) each solve is preceded by the gate of its streams at
+//                     the pose they carry in, on the same batch and stream: one launch and one wait per solved (level, group)
 //   covariance        tracker_push_covariance: [ea_batch_covariance] [keyframe mode: ea_batch_pose_stats] at level 0
 //   references, per level   tracker_push_references: [Laplacian, Canny: the counts back (wait)] -> room for the points ->
 //                     table up -> scatter -> depth weights; then the last wait
@@ -1587,6 +1589,12 @@ struct ea_tracker_batch {
   bool key_on = false;
   ea_keyframe_params key_prm{};
   int last_taken = 0;
+  // depth gate (ea_tracker_batch_set_depth_gate): off = no launch of it
+  bool gate_on = false;
+  ea_depth_gate_params gate_prm{};
+  std::vector<ea_depth_gate_stats> last_gate;  // levels x streams, level-major: ea_tracker_batch_last_depth_gate
+  int last_gated = 0;
+  bool gate_applies() const { return gate_on && gate_prm.apply != 0; }
 };
 
 static int tracker_batch_create(ea_tracker_batch **out, const ea_camera *cams, int count, int levels, int dtype, int device,
@@ -1615,6 +1623,7 @@ static int tracker_batch_create(ea_tracker_batch **out, const ea_camera *cams, i
   tb->st.resize((size_t)count);
   tb->last_sums.resize((size_t)levels * count);
   std::memset(tb->last_sums.data(), 0, tb->last_sums.size() * sizeof(ea_summary));
+  tb->last_gate.assign((size_t)levels * count, ea_depth_gate_stats{});
   *out = tb;
   return EA_OK;
 }
@@ -1748,7 +1757,18 @@ struct TrackerPush {
   std::vector<ea_pose_stats> kstats;          // keyframe mode: the statistics at the pose its solve returned
   std::vector<unsigned char> take;            // the pushed frame becomes its reference: every stream's, but in keyframe mode
   std::vector<int> why;                       // keyframe mode: why (keyframe_decide)
+  WsRegion<float> depth_full;                 // (ROS, host frames, halvings >= 1) the stage's full-size depth in a frame's block
   bool ros() const { return tb->flavour == 2; }
+  // The depth gate's image of stream i: the pushed depth frame at full resolution where the push has put it -- the caller's
+  // device frame in place; of a host frame the `depth` region of level 0's workspace (uint16, or the ROS flavour's float
+  // frame without halvings) or the stage's depth_full.  Written by the upload alone and read-only to every kernel behind it
+  // (the halving steps and chains read it through const pointers and write other regions; no region of a frame's block
+  // shares bytes with another), so it is what was pushed until the next push.
+  const void *gate_depth(size_t i) const {
+    if (on_device) return depth[i];
+    const BatchFrames &j0 = J[0];
+    return ros() && tb->halvings > 0 ? depth_full.at<unsigned char>(j0.frame(i)) : j0.ws.depth.at<unsigned char>(j0.frame(i));
+  }
   // what the reference side counts and scatters
   const WsRegion<uint8_t> &ref_edges(const BatchFrames &j) const { return tb->flavour == 0 ? j.ws.lap : j.ws.edges; }
   int ref_threshold() const { return tb->flavour == 0 ? 35 : 0; }
@@ -1807,6 +1827,7 @@ static int tracker_push_frames(TrackerPush *s) {
     TBRC(pyramid_frames_begin(batches.data(), &s->J, tb->halvings, s->bgr, s->depth, s->bgr, &py));
     for (BatchFrames &j : s->J) TBCHK(upload_table(&j));
     TBRC(pyramid_stage_side(s->J, py, tb->halvings, 0, s->bgr, depth_f32, &uploads));
+    s->depth_full = py.depth_full;
     return EA_OK;
   }
   BatchFrames &j = s->J[0];
@@ -1814,6 +1835,7 @@ static int tracker_push_frames(TrackerPush *s) {
   if (s->ros()) {
     TBCHK(upload_table(&j));
     TBRC(batch_stage_ros(j, 0, s->bgr, depth_f32));
+    s->depth_full = j.st.depth_full;
     return EA_OK;
   }
   // (Laplacian, Canny: no count comes before the transform, so the table goes up with the images in it)
@@ -1910,6 +1932,32 @@ static void tracker_group_poses(const std::vector<int> &grp, const std::vector<d
   }
 }
 
+// The depth gate of one group in front of its solve on level l: ea_batch_depth_gate's kernel on the batch that solves the group,
+// at the poses the streams carry into the level, against the pushed depth at full resolution (the ROS flavour: 2^(halvings + l)
+// times the level's extent -- the level's own depth is the reference's reduction, NaN -> 0 and the plain mean, which a hole
+// pulls towards the camera).  apply: the weights of the group's level problems are written before the solve reads them.
+static int tracker_gate_group(TrackerPush *s, int l, const std::vector<int> &grp, ea_batch *solver, const std::vector<double> &qg,
+                              const std::vector<double> &tg) {
+  ea_tracker_batch *tb = s->tb;
+  const size_t ng = grp.size(), n = tb->st.size();
+  std::vector<double> M(16 * ng);
+  std::vector<const void *> depth(ng);
+  std::vector<ea_depth_gate_stats> stats(ng);
+  for (size_t k = 0; k < ng; ++k) {
+    (void)ea_pose_to_matrix(&qg[4 * k], &tg[3 * k], &M[16 * k]);
+    depth[k] = s->gate_depth((size_t)grp[k]);
+  }
+  GateImages img;
+  img.kind = s->ros() ? EA_DEPTH_F32 : EA_DEPTH_U16;
+  img.shift = s->ros() ? tb->halvings + l : 0;
+  img.z_scaling = s->ros() ? 1.0 : s->z_scaling;
+  img.depth = depth.data();
+  TBRC(batch_depth_gate_images(solver, M.data(), &tb->gate_prm, img, stats.data()));
+  for (size_t k = 0; k < ng; ++k) tb->last_gate[(size_t)l * n + (size_t)grp[k]] = stats[k];
+  tb->last_gated += (int)ng;
+  return EA_OK;
+}
+
 // Descent: ea_solve_pyramid per stream, run as batch solves -- the coarsest level first, on each level the streams still
 // descending that can use it, grouped by kernel family, the pose carried down.  A failed solve stops its stream's descent: it
 // keeps its prior.  A single level is this loop run once.
@@ -1926,6 +1974,10 @@ static int tracker_push_descent(TrackerPush *s) {
       TBRC(tracker_batch_solver(tb, grp, &solver, l));
       std::vector<ea_summary> sg(grp.size());
       tracker_group_poses(grp, s->qc, s->tc, &qg, &tg);
+      if (tb->gate_on) {
+        const int rc_gate = tracker_gate_group(s, l, grp, solver, qg, tg);
+        if (rc_gate != EA_OK) return rc_gate;
+      }
       TBRC(ea_batch_solve(solver, s->opt, qg.data(), tg.data(), sg.data()));
       for (size_t k = 0; k < grp.size(); ++k) {
         const size_t i = (size_t)grp[k];
@@ -2007,6 +2059,11 @@ static int tracker_push_references(TrackerPush *s) {
   for (BatchFrames &j : s->J) {
     if (!s->ros() && any_take) TBRC(batch_counts_fetch(&j));
     TBRC(batch_ref_room(&j, tb->key_on ? s->take.data() : nullptr));
+    if (tb->gate_applies()) {
+      // a gated stream is a weighted problem from its first reference on: the new reference's weights are dd, or exactly 1
+      for (FrameSlot &sl : j.slots) sl.ones = 1;
+      j.max_weighted = j.max_total;
+    }
     if (!any_take) continue;
     if (s->ros()) {
       TBRC(batch_ros_scatter(&j));
@@ -2018,7 +2075,11 @@ static int tracker_push_references(TrackerPush *s) {
   TBCHK(hipDeviceSynchronize());
   for (int l = 0; l < tb->levels; ++l)
     for (size_t i = 0; i < n; ++i)
-      if (s->take[i]) ref_points_landed(tb->lv[(size_t)l].probs[i], s->J[(size_t)l].slots[i].capacity);
+      if (s->take[i]) {
+        ea_problem *p = tb->lv[(size_t)l].probs[i];
+        ref_points_landed(p, s->J[(size_t)l].slots[i].capacity);
+        if (tb->gate_applies()) p->weighted = p->n > 0;  // (weights_from_depth: as landed -- they are dd alone, or ones)
+      }
   return EA_OK;
 }
 
@@ -2074,6 +2135,8 @@ static int tracker_batch_push(ea_tracker_batch *tb, const uint8_t *const *bgr, c
   if (aligned) std::fill(aligned, aligned + n, 0);
   if (summaries) std::memset(summaries, 0, n * sizeof(*summaries));
   std::memset(tb->last_sums.data(), 0, tb->last_sums.size() * sizeof(ea_summary));
+  std::fill(tb->last_gate.begin(), tb->last_gate.end(), ea_depth_gate_stats{});
+  tb->last_gated = 0;
   // (a phase that fails has dropped every stream: tracker_batch_fail)
   for (int (*phase)(TrackerPush *) : {tracker_push_frames, tracker_push_images, tracker_push_priors, tracker_push_descent,
                                       tracker_push_covariance, tracker_push_references})
@@ -2163,6 +2226,32 @@ extern "C" int ea_tracker_batch_set_keyframes(ea_tracker_batch *tb, const ea_key
   return EA_OK;
 }
 
+extern "C" int ea_tracker_batch_set_depth_gate(ea_tracker_batch *tb, const ea_depth_gate_params *prm) {
+  if (prm)
+    if (const char *why = depth_gate_params_error(prm)) return fail(EA_ERR_INVALID_ARG, why);
+  if (!tb) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (prm && !depth_gate_factors_fit(prm, tb->lv[0].probs[0]->dtype == EA_F32 ? (double)FLT_MAX : DBL_MAX))
+    return fail(EA_ERR_INVALID_ARG, "a weight factor overflows the float of an fp32 tracker");
+  for (const TrackerStream &s : tb->st)
+    if (s.frames > 0)
+      return fail(EA_ERR_STATE, "a stream holds a reference: set the gate before the first push or after ea_tracker_batch_reset(-1)");
+  tb->gate_on = prm != nullptr;
+  if (prm) tb->gate_prm = *prm;
+  std::fill(tb->last_gate.begin(), tb->last_gate.end(), ea_depth_gate_stats{});
+  tb->last_gated = 0;
+  return EA_OK;
+}
+
+extern "C" int ea_tracker_batch_last_depth_gate(ea_tracker_batch *tb, int level, int i, ea_depth_gate_stats *out) {
+  if (!tb || !out) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (level < 0) return fail(EA_ERR_INVALID_ARG, "no such level");  // (a negative index: before the handle is looked at)
+  if (i < 0) return fail(EA_ERR_INVALID_ARG, "no such stream");
+  if (level >= tb->levels) return fail(EA_ERR_INVALID_ARG, "no such level");
+  if ((size_t)i >= tb->st.size()) return fail(EA_ERR_INVALID_ARG, "no such stream");
+  *out = tb->last_gate[(size_t)level * tb->st.size() + (size_t)i];
+  return EA_OK;
+}
+
 extern "C" int ea_tracker_batch_keyframe_state(ea_tracker_batch *tb, int i, ea_keyframe_state *out) {
   if (!tb || !out) return fail(EA_ERR_INVALID_ARG, "NULL argument");
   if (i < 0 || (size_t)i >= tb->st.size()) return fail(EA_ERR_INVALID_ARG, "no such stream");
@@ -2182,6 +2271,8 @@ extern "C" int ea_tracker_batch_get_info(const ea_tracker_batch *tb, const char 
   else if (k == "levels") *value = tb->levels;
   else if (k == "keyframes_taken") *value = tb->last_taken;
   else if (k == "keyframe_mode") *value = tb->key_on ? 1 : 0;
+  else if (k == "depth_gate") *value = tb->gate_on ? 1 : 0;
+  else if (k == "gated") *value = tb->last_gated;
   else return fail(EA_ERR_INVALID_ARG, "unknown info key: " + k);
   return EA_OK;
 }

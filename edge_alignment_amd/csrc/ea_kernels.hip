@@ -3091,11 +3091,16 @@ __global__ __launch_bounds__(256) void ea_depth_weights_kernel(const T *__restri
   depth_weights_body<T>(z, n, z_ref, power, w);
 }
 // the same body for frame blockIdx.z of a batched producer call (ea_batch_set_frames): z, the weights behind it and the
-// weighting out of the frame's slot; a frame whose problem has no depth weighting (power 0), or no point, writes nothing
+// weighting out of the frame's slot; a frame whose problem has no depth weighting (power 0), or no point, writes nothing --
+// unless its slot asks for ones (the gated multi-stream tracker: every reference carries defined weights)
 template <typename T>
 __global__ __launch_bounds__(256) void ea_depth_weights_frames_kernel(const FrameSlot *__restrict__ slots) {
   const FrameSlot &sl = slots[blockIdx.z];
-  if (sl.power <= 0) return;
+  if (sl.power <= 0) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (sl.ones && i < (long long)sl.capacity) static_cast<T *>(sl.w)[i] = (T)1.0;
+    return;
+  }
   depth_weights_body<T>(static_cast<const T *>(sl.z), (long long)sl.capacity, sl.z_ref, sl.power, static_cast<T *>(sl.w));
 }
 
@@ -3465,7 +3470,8 @@ __global__ __launch_bounds__(kReprojectThreads) void ea_reproject_kernel(const P
 // segment -- its 3x4 matrix, depth image, weights and class pointers -- the descriptor and the rule uniform per workgroup.
 // RAW is the depth kind (uint16_t / float), R the window radius: the (2 R + 1)^2 window is that many independent 2- or 4-byte
 // gather loads per lane (a pixel outside the image reads pixel 0 and counts as "no measurement"), all issued before the
-// compare chain; a VGA depth image is 0.6-1.2 MB and stays in L2.  Per lane one coalesced weight store (apply) and one byte
+// compare chain; a VGA depth image is 0.6-1.2 MB and stays in L2.  The depth image may be 2^shift times the DT extent (step
+// 3b; the shift a run-time value of the segment, uniform per workgroup: two scalar shifts, and per lane and axis one multiplication and one addition).  Per lane one coalesced weight store (apply) and one byte
 // store (classes asked for).  Counts: six ballots and popcounts per wavefront, the four wavefronts summed through LDS, at most
 // six integer atomics per workgroup on the segment's counters (exact whatever the order of arrival).
 template <typename T, typename RAW, int R>
@@ -3487,7 +3493,7 @@ __global__ __launch_bounds__(kDepthGateThreads) void ea_depth_gate_kernel(const 
                  z = (double)((GPtr<T>)static_cast<const T *>(pd.z))[i];
     cls = gate_point<RAW, R, GPtr<RAW>>(sg.M, x, y, z, pd.fx, pd.fy, pd.cx, pd.cy, (pd.variant & 1) ? pd.dist : nullptr,
                                         (GPtr<RAW>)static_cast<const RAW *>(sg.depth), pd.H, pd.W, sg.z_scaling, rule.abs_tol,
-                                        rule.rel_tol);
+                                        rule.rel_tol, sg.shift);
     if (sg.cls) ((GOutB)sg.cls)[i] = (unsigned char)cls;
     if (sg.weights)
       ((GOutT) static_cast<T *>(sg.weights))[i] = (T)gate_weight(gate_factor(rule, cls), gate_depth_factor(z, sg.dw_z_ref, sg.dw_power));

@@ -131,7 +131,7 @@ struct FrameSlot {
   int power;              // (0 = off)
   int capacity;           // = the frame's point count
   int pitch;              // of dt / dt32, in texels
-  int pad_;
+  int ones;               // != 0: a frame without depth weighting (power 0) gets weights of exactly 1 (the gated tracker)
 };
 struct FramesLaunch {
   int n = 0, H = 0, W = 0;
@@ -326,7 +326,8 @@ hipError_t launch_halving_chain_bgr8(const FramesLaunch &f, const uint8_t *const
                                      const ChainLevels &lv, hipStream_t s);
 hipError_t launch_halving_chain_f32(const FramesLaunch &f, const float *const *table, const float *src, int H, int W, int steps,
                                     const ChainLevels &lv, int nan_to_zero, hipStream_t s);
-// ea_kernels.hip: ea_depth_weights_kernel's body for the frames whose slot has power > 0, max_n = the largest capacity among them
+// ea_kernels.hip: ea_depth_weights_kernel's body for the frames whose slot has power > 0 (and ones for those with `ones`),
+// max_n = the largest capacity among them
 hipError_t launch_depth_weights_frames(int dtype, const FramesLaunch &f, long long max_n, hipStream_t s);
 }  // namespace ea
 

@@ -697,8 +697,8 @@ static int depth_gate_state_checks(const BatchView &v, const ea_depth_gate_param
     const ea_problem *p = v.probs[i];
     if (!p->d_dt) return fail(EA_ERR_STATE, "distance-transform image not set (ea_problem_set_dt)");
     if (!p->d_now_depth) return fail(EA_ERR_STATE, "current-frame depth not set (ea_problem_set_now_depth)");
-    if (p->nd_H != p->H || p->nd_W != p->W)
-      return fail(EA_ERR_STATE, "the current-frame depth and the distance-transform image differ in extent");
+    if (depth_gate_shift(p->H, p->W, p->nd_H, p->nd_W) < 0)
+      return fail(EA_ERR_STATE, "the current-frame depth is not the distance-transform image's extent times one power of two (2^0..2^8, at most 2^30 pixels)");
     if (p->nd_kind != v.probs[0]->nd_kind)
       return fail(EA_ERR_STATE, "the problems of one depth gate call must hold depth of one kind");
   }
@@ -707,8 +707,9 @@ static int depth_gate_state_checks(const BatchView &v, const ea_depth_gate_param
 
 // upload + launch + the counters on their way back, for a batch that is built; the caller queues what else must come down and
 // synchronises.  cls_dev: class bytes in the rows layout, or NULL
+// img: the depth images of the call when they are not the problems' held now-depth (the multi-stream tracker's pushed frames)
 static int depth_gate_enqueue(ea_batch *b, const BatchView &v, const double *b_T_a, const ea_depth_gate_params *prm,
-                              unsigned char *cls_dev, SegmentBlock &blk) {
+                              unsigned char *cls_dev, SegmentBlock &blk, const GateImages *img = nullptr) {
   const int nseg = v.count;
   const size_t bytes = blk.layout((size_t)nseg * sizeof(DepthGateSeg), (size_t)nseg * kDepthGateClasses * sizeof(unsigned long long));
   blk.cached = false;  // (the batch's own pair: ea_batch says why)
@@ -722,8 +723,9 @@ static int depth_gate_enqueue(ea_batch *b, const BatchView &v, const double *b_T
     DepthGateSeg &sg = blk.records<DepthGateSeg>()[j];
     sg.row = h.row_begin; sg.n = h.n; sg.term = h.term;
     segment_matrix(p, b_T_a + 16 * (size_t)j, sg.M);
-    sg.depth = p->d_now_depth;
-    sg.z_scaling = p->nd_z_scaling;
+    sg.depth = img ? img->depth[j] : p->d_now_depth;
+    sg.z_scaling = img ? img->z_scaling : p->nd_z_scaling;
+    sg.shift = img ? img->shift : depth_gate_shift(p->H, p->W, p->nd_H, p->nd_W);
     sg.weights = (prm->apply && sg.n > 0) ? weights_ptr(p) : nullptr;
     sg.cls = cls_dev ? cls_dev + sg.row : nullptr;
     sg.dw_z_ref = p->dw_z_ref;
@@ -731,7 +733,7 @@ static int depth_gate_enqueue(ea_batch *b, const BatchView &v, const double *b_T
   }
   HIPCHK(blk.up(v.stream));
   DepthGateWork w;
-  w.nseg = nseg; w.max_n = heads.max_n; w.kind = v.probs[0]->nd_kind; w.radius = prm->radius;
+  w.nseg = nseg; w.max_n = heads.max_n; w.kind = img ? img->kind : v.probs[0]->nd_kind; w.radius = prm->radius;
   w.rule = depth_gate_rule(prm);
   w.segs = blk.dev_records<DepthGateSeg>();
   w.counts = blk.dev_results<unsigned long long>();
@@ -812,6 +814,29 @@ static int depth_gate_to_host(ea_batch *b, const BatchView &v, const double *b_T
   int rc = depth_gate_enqueue(b, v, b_T_a, prm, d_cls.as<unsigned char>(), blk);
   if (rc == EA_OK && d_cls.p) rc = download_head_rows(v, 1, d_cls.p, cls);
   if (rc != EA_OK) return rc;
+  HIPCHK(hipStreamSynchronize(v.stream));
+  depth_gate_finish(v, prm, blk, stats);
+  return EA_OK;
+}
+
+// The multi-stream tracker's gate of one solved (level, group), on the batch that solves it: the parameters were checked when
+// the gate was set, the poses are the tracker's own, every problem owns its points and has its image (usable), and the depth
+// images are the pushed frames (img) -- no held now-depth is read or touched.  One launch and one wait on the batch's stream.
+int ea::batch_depth_gate_images(ea_batch *b, const double *b_T_a, const ea_depth_gate_params *prm, const GateImages &img,
+                                ea_depth_gate_stats *stats) {
+  BatchView v = batch_view(b);
+  int rc = check_segment_count((size_t)v.count, "depth gate");
+  if (rc != EA_OK) return rc;
+  for (int i = 0; i < v.count; ++i) {
+    const ea_problem *p = v.probs[i];
+    if (!p->d_dt || !img.depth[i]) return fail(EA_ERR_STATE, "depth gate: a stream without an image or a depth frame");
+    if (img.shift < 0 || img.shift > kDepthGateMaxShift || (((int64_t)p->H * p->W) << (2 * img.shift)) > ((int64_t)1 << 30))
+      return fail(EA_ERR_STATE, "depth gate: the depth frame is more than 2^8 times the level's extent or more than 2^30 pixels");
+  }
+  HIPCHK(hipSetDevice(v.device));
+  if ((rc = batch_built(b, &v)) != EA_OK) return rc;
+  SegmentBlock blk;
+  if ((rc = depth_gate_enqueue(b, v, b_T_a, prm, nullptr, blk, &img)) != EA_OK) return rc;
   HIPCHK(hipStreamSynchronize(v.stream));
   depth_gate_finish(v, prm, blk, stats);
   return EA_OK;

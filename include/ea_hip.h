@@ -434,9 +434,17 @@ int ea_batch_set_now_depth_device(ea_batch *b, const void *const *depth_dev, int
  * batched problem with terms reports its head family):
  *   1  M = step A of ea_*_reproject (rig product included); bx, by, bz, u, v = its step B, distortion by name included.
  *   2  BEHIND when !(bz > 0 && bz < +Inf) (NaN included).
- *   3  else OUTSIDE when (u, v) is not inside by ea_problem_pixel_cost's rule (see ea_problem_overlay);
- *      iu = (int)u, iv = (int)v, truncating toward zero.
- *   4  window: the pixels (iv + dy, iu + dx), dy outer and dx inner, each from -radius to radius, that lie in
+ *   3  else OUTSIDE when (u, v) is not inside by ea_problem_pixel_cost's rule (see ea_problem_overlay), on the extent H x W of
+ *      the problem's DT image; iu = (int)u, iv = (int)v, truncating toward zero.
+ *   3b the held depth image is height x width = (H << s) x (W << s) for one s in 0..8 (each problem its own s; H * W << 2 s at
+ *      most 2^30): c = (2^s - 1) / 2 (exact), U = u * 2^s + c, V = v * 2^s + c (the multiplication is exact, the addition
+ *      rounds once, nothing is contracted), iu = (int)U, iv = (int)V, truncating toward zero.  c is the centre of the
+ *      2^s x 2^s block of depth pixels whose mean DT pixel 0 is.  s = 0: U = u -- the depth image has the DT extent.  iu or
+ *      iv may be negative or past the last column or row; nothing is clamped (step 4 treats such pixels as no measurement).
+ *      For the users of ea_problem_set_*_frame_ros_scaled and of pyramid levels: the reference's own reduction of the depth
+ *      (NaN -> 0, then the plain 2 x 2 mean) is what back-projection needs and no gate input -- a block with one hole comes
+ *      out at 3/4 of the true depth and would be classed OCCLUDED -- so hand the gate the full-resolution depth.
+ *   4  window: the pixels (iv + dy, iu + dx), dy outer and dx inner, each from -radius to radius (in depth pixels), that lie in
  *      0 <= row < height, 0 <= col < width and hold a valid measurement d (converted as above); e = fabs(d - bz); the first
  *      such pixel is kept, and any later one with a STRICTLY smaller e (a tie keeps the first in that raster order).  None:
  *      UNKNOWN.  (Edge points sit on depth discontinuities: the single pixel under a point is the least reliable one.)
@@ -462,13 +470,13 @@ int ea_batch_set_now_depth_device(ea_batch *b, const void *const *depth_dev, int
  * negative, NaN or infinite, a weight factor that overflows float for an fp32 problem, a capacity that is too small, with
  * apply the same problem twice in the batch (its weights can be written once per call), a cls_dev that is not device
  * memory of the batch's device.
- * EA_ERR_STATE: a problem without points (ea_problem_depth_gate only), DT image or now-depth; a now-depth whose extent differs
- * from the DT extent (checked here, not by the setters); problems of one call that hold depth of different kinds.  In a batch
+ * EA_ERR_STATE: a problem without points (ea_problem_depth_gate only), DT image or now-depth; a now-depth whose extent is not
+ * the DT extent times one power of two as step 3b says (checked here, not by the setters); problems of one call that hold depth of different kinds.  In a batch
  * a problem without depth fails the whole call before any launch.
  * One launch and one synchronisation on the batch's stream serve a whole batch; the matrices go up in a small array of their
  * own; no per-point data crosses the bus unless cls is asked for.
- * Out of scope: gating inside ea_tracker_* / ea_tracker_batch_* (their pushed depth already lives in the frame workspace: the
- * natural follow-up), gating of terms through the head, soft or continuous weights, any use of the depth as a residual. */
+ * ea_tracker_batch_set_depth_gate runs this gate inside the multi-stream tracker, on the pushed depth.
+ * Out of scope: gating inside the single ea_tracker_*, gating of terms through the head, soft or continuous weights, any use of the depth as a residual. */
 typedef struct {
   int radius;                 /* window half-width in pixels, 0..3 */
   double abs_tol, rel_tol;    /* tol = abs_tol + rel_tol * bz, metres */
@@ -1192,6 +1200,41 @@ typedef struct {
 void ea_default_keyframe_params(ea_keyframe_params *p);   /* min_visible_fraction 0.75, everything else off */
 int ea_tracker_batch_set_keyframes(ea_tracker_batch *tb, const ea_keyframe_params *p);
 int ea_tracker_batch_keyframe_state(ea_tracker_batch *tb, int i, ea_keyframe_state *out);
+
+/* The depth gate inside the multi-stream tracker: every solve of a push is preceded by ea_batch_depth_gate's arithmetic on the
+ * streams it solves, against the depth frame of THIS push.  Off by default: a tracker on which it is never set issues exactly
+ * the launches it issued before.
+ *   set_depth_gate(prm): prm == NULL: off.  Accepted only while no stream holds a reference (before the first push or after
+ *     ea_tracker_batch_reset(-1)), else EA_ERR_STATE -- the rule of ea_tracker_batch_set_keyframes.  Parameter errors are
+ *     ea_batch_depth_gate's (EA_ERR_INVALID_ARG), found before the handle is looked at; a factor that overflows the float of
+ *     an fp32 tracker likewise.  All flavours, halvings, pyramid levels and keyframe mode, host and device frames.
+ *   Which depth: flavours 0 and 1 the pushed uint16 frame with the push's z_scaling, s = 0; flavour 2 the pushed float32 frame
+ *     at FULL resolution, s = halvings + level (step 3b above: the level's own depth is the reference's reduction and no gate
+ *     input).  It is read where the push has put it already -- the caller's device frame in place; of a host frame the
+ *     workspace's `depth` region or the halving stage's full-size region, which the upload alone writes -- no second upload,
+ *     no copy.
+ *   When: behind the priors, inside the descent, on every level directly in front of that level's solve, for the streams that
+ *     solve on that level, at the pose they carry into it -- on the coarsest usable level the start pose, below it the pose
+ *     the level above returned -- with M = ea_pose_to_matrix(q, t).  It runs on the (sub-)batch that solves the group and on
+ *     its stream: one launch and one wait of its own per solved (level, group).
+ *   apply != 0: w = g * dd replaces the weights of each gated level problem before its solve (dd: the problem's depth
+ *     weighting, or 1).  Every stream of such a tracker is a WEIGHTED problem from its first reference on -- the reference
+ *     scatter leaves a new reference with weights dd, or exactly 1.0 without depth weighting -- so streams with otherwise
+ *     equal settings stay one kernel family, a problem never flips between weighted and unweighted from push to push, and
+ *     ea_tracker_batch_problem(i) may be evaluated between pushes.  A kept keyframe is gated again every push from its own
+ *     z: nothing accumulates.  The covariance sees the gated weights; pose statistics ignore weights, as documented.
+ *   apply == 0: counts only; poses, summaries, points, images, covariance and keyframe decisions are bit for bit those of a
+ *     tracker without a gate.
+ *   Not gated: streams that are not aligned, and levels that are not usable for a stream or that its descent did not reach;
+ *     their counts are zero (n = 0).
+ *   last_depth_gate(level, i): the counts of stream i on `level` in the last push.  get_info: "depth_gate" (0 / 1), "gated"
+ *     (the (stream, level) pairs gated in the last push).  A rejected push leaves both as they were; a failure past the checks
+ *     resets every stream, as in every phase.
+ * Out of scope: the single ea_tracker, a keyframe rule on the occlusion counts, soft or continuous weights, depth as a
+ * residual, gating of terms, overlapping the uploads with the solve.  The default tolerances remain API defaults that nobody
+ * has measured on real sequences. */
+int ea_tracker_batch_set_depth_gate(ea_tracker_batch *tb, const ea_depth_gate_params *prm);
+int ea_tracker_batch_last_depth_gate(ea_tracker_batch *tb, int level, int i, ea_depth_gate_stats *out);
 
 /* the half-resolution step by itself, host in / host out: kind 0 = bgr8 (height x width x 3 bytes), 1 = float32 with
  * NaN -> 0 first, 2 = float32 as is; dst = (height / 2) x (width / 2); height and width even */
