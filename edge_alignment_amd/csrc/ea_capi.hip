@@ -2549,9 +2549,10 @@ static int batch_solve(ea_batch *b, const ea_options *opt_in, double *q, double 
       const int use_lds = b->lds_bytes > 0 ? 1 : 0;
       if (c->t_lds_bytes != b->t_lds_bytes || c->t_ppt != b->ppt || c->t_use_lds != use_lds || c->t_xcd != b->xcd_remap ||
           c->t_nt != b->nt || c->t_variant != b->any_variant || c->t_buf != b->buffer_loads || c->t_wide != b->t_wide ||
-          c->t_img32 != (b->img32 ? -1 : 0)) {
+          c->t_img32 != (b->img32 ? -1 : 0) || c->t_fused != b->t_fused) {
         c->t_lds_bytes = b->t_lds_bytes; c->t_ppt = b->ppt; c->t_use_lds = use_lds; c->t_xcd = b->xcd_remap; c->t_nt = b->nt;
         c->t_variant = b->any_variant; c->t_buf = b->buffer_loads; c->t_wide = b->t_wide; c->t_img32 = b->img32 ? -1 : 0;
+        c->t_fused = b->t_fused;  // (solve_start reads the part's own: "fused_iterations" = 0 holds for the parts too)
         c->built = false;
       }
       runs[(size_t)k].b = c;
@@ -2562,6 +2563,10 @@ static int batch_solve(ea_batch *b, const ea_options *opt_in, double *q, double 
   for (SolveRun &r : runs) {
     int rc = solve_start(r, o, lo, q + 4 * r.first, t + 3 * r.first);
     if (rc != EA_OK) return rc;
+  }
+  if (parts > 1) {  // info key "fused_iterations" of the batch the caller holds: every part ran one launch per iteration
+    b->last_fused = 1;
+    for (const SolveRun &r : runs) b->last_fused &= r.fused ? 1 : 0;
   }
   // The host polls pinned progress words; a deadline bounds the wait: if the device shows no progress (no evaluation
   // completed, nothing to enqueue) for solve_timeout_ms, give up with an error instead of spinning for ever on a kernel
@@ -3047,7 +3052,7 @@ extern "C" int ea_batch_set_tuning(ea_batch *b, const char *key, int value) {
   else if (k == "rows_staged") { b->t_rows_staged = value; return EA_OK; }
   else if (k == "rows_nontemporal") { b->t_rows_nt = value; return EA_OK; }
   else if (k == "poll_results") { b->t_poll = value != 0; return EA_OK; }
-  else if (k == "fused_iterations") { b->t_fused = value; return EA_OK; }
+  else if (k == "fused_iterations") b->t_fused = value;  // (batch_build reads it when it picks the launch shape: rebuild)
   else if (k == "zero_copy_poses") { b->t_zero_copy = value; return EA_OK; }
   else if (k == "poses_per_launch") { b->t_kp_G = value > 0 ? value : 0; b->kp_K = 0; return EA_OK; }  // (resident poses are dropped)
   else if (k == "poses_order") { b->t_kp_order = value < 0 ? -1 : (value ? 1 : 0); return EA_OK; }

@@ -829,7 +829,9 @@ int ea_eval_rows_device(ea_problem *p, const double q[4], const double t[3], int
  * "fused_iterations" = 0: ea_solve / ea_batch_solve always run (evaluate, step) pairs; default: a solve of problems small
  * enough for one workgroup per CU (LM strategy, one plain residual family each) runs ONE launch per iteration, every workgroup
  * taking the LM step itself before it evaluates -- the same iterates bit for bit (ea_batch_get_info "fused_iterations"
- * reports which form the last solve took).
+ * reports which form the last solve took; for a batch solved as sub-batches on several streams: 1 if every part ran it).
+ * The launch shape is chosen with the key in view (the fused form needs 256-thread workgroups and at most 255 chunks), so
+ * changing it rebuilds the batch like "threads" and "points_per_thread" do, and the sub-batches of "solve_streams" take it too.
  * "wide_accumulate" = 1: an fp32 batch sums in fp64 from a lane's sum of <= points_per_thread products on (default: a
  * lane's and a wavefront's sums are fp32, everything above fp64).  Plain functor on the L2 path; ignored for fp64
  * batches, variant functors and the LDS-staged form (ea_batch_get_info "wide_accumulate" reports what is in effect).
