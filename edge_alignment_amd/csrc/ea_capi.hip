@@ -3774,7 +3774,9 @@ extern "C" int ea_solve_sharded_device(ea_problem *p, const ea_options *opt_in, 
 // Every rank folds the same bits in the same order, so the replicated state machines stay in lockstep as before.
 // Ranks may hold different numbers of rows (shards differ by a point): `agree` takes {this rank cannot, its row count} to the
 // maximum over the ranks; every rank folds the widest count, its own rows beyond its shard kept at zero.
-// *used = 0: some rank's shard does not qualify (see solve_start) -- the caller falls back to ea_solve_sharded_device.
+// *used = 0: some rank's shard does not qualify (see solve_start: another kernel family, or no point at all) -- every rank
+// alike, after `agree` and before any exchange, with q, t and the summary untouched; the caller falls back to
+// ea_solve_sharded_device.
 extern "C" int ea_internal_solve_sharded_rows(ea_problem *p, const ea_options *opt_in, ea_device_allreduce_fn allreduce,
                                               int (*agree)(int vals[2], void *user), void *user, double q[4], double t[3],
                                               ea_summary *summary, int *used) {

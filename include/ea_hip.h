@@ -501,7 +501,11 @@ int ea_solve(ea_problem *p, const ea_options *opt, double q[4], double t[3], ea_
  * the points (ea_problem_set_points with its slice) and the whole DT image.  Per iteration: local fused evaluation ->
  * 32 accumulator slots -> `allreduce` (in-place sum over all ranks; 0 = success) -> the same trust-region step on every
  * rank (deterministic: no broadcast).  Every rank must call it with the same options and initial pose.  summary->
- * num_point_evals counts the local shard. */
+ * num_point_evals counts the local shard.
+ * A rank may hold no point at all (ea_problem_set_points with n = 0, or never called), or none of one term: it takes part
+ * in every exchange with zeros and ends with the pose, summary and trace of the other ranks.  Loss, functor, flavour,
+ * terms, prior and constant parameters are set alike on every rank; the prior and the mask are applied once, to the reduced
+ * system.  A block that fails on one rank fails the evaluation on all (the count travels in the exchange). */
 typedef int (*ea_allreduce_fn)(double *buf, int count, void *user);
 int ea_solve_sharded(ea_problem *p, const ea_options *opt, ea_allreduce_fn allreduce, void *user, double q[4], double t[3],
                      ea_summary *summary);

@@ -18,7 +18,11 @@ partial chunk at two), term 1 has 130; every cloud is what get_aX makes of a syn
 a depth image that is zero off the chosen edge pixels), so that the same cloud can be uploaded (set_points) or produced on
 the device (set_ref_frame, which is what writes depth weights).  The distance transform is that of the pixels the cloud
 projects to at the planted pose through the case's own functor.  A failed block is a point at depth 1 / 5000 m: the pose's
-translation keeps |t_z| <= 0.005, so it sits inside the z guard at every pose a test uses."""
+translation keeps |t_z| <= 0.005, so it sits inside the z guard at every pose a test uses.
+
+Shards: SHARD_CUTS names the ways a case's points are cut over the ranks of a point-sharded solve, `shard_inputs` /
+`shard_reference` are a rank's part of the inputs and the reference over it (no prior: that belongs to the reduced system), and
+`sharded_runs()` lists what tests/test_gpu_feature_pairs_sharded.py runs."""
 import functools
 import itertools
 import os
@@ -46,6 +50,8 @@ DIMENSIONS = (
     ("failed", ("none", "one")),
     ("shape", ("default", "ppt2", "nt1024")),
 )
+# (`shape` does not reach the point-sharded solves: they run on the problem's own batch, which has no tuning call, so the sharded
+# forms of tests/test_gpu_feature_pairs_sharded.py run every case at the automatic shape)
 NAMES = tuple(n for n, _ in DIMENSIONS)
 VARIANT_FUNCTORS = ("Ex", "SecondCam", "SecondCamEx")
 
@@ -463,3 +469,119 @@ def tolerances(case, q, t, inputs=None, loss=None, key=None):
     ok = ~np.isnan(ref["r"]) & ~np.isnan(plain["r"])
     image = np.concatenate([s["image"].ravel() for s in (host_inputs(case) if inputs is None else inputs)])
     return bb.bounds({k: ref[k][ok] for k in ("r", "J", "rho")}, {k: plain[k][ok] for k in ("r", "J", "rho")}, base, image)
+
+
+# ---- shards of a case: the point-sharded solves ------------------------------------------------------------------------------
+def _cut_even2(case, n_per_term):
+    from edge_alignment_amd import dist as ead
+    return [[(lambda s: (s.start, s.stop))(ead.shard_slice(n, r, 2)) for n in n_per_term] for r in range(2)]
+
+
+def _cut_chunk2(case, n_per_term):
+    """rank 0: exactly one full 256-lane chunk of the head and a second term of zero points; rank 1: the partial chunk and the
+    whole second term"""
+    return [[(0, 256)] + [(0, 0)] * (len(n_per_term) - 1), [(256, n_per_term[0])] + [(0, n) for n in n_per_term[1:]]]
+
+
+def _cut_lone2(case, n_per_term):
+    """rank 0: point 0 of the head and nothing else (where failed_index is 0, the failed block is its only point)"""
+    return [[(0, 1)] + [(0, 0)] * (len(n_per_term) - 1), [(1, n_per_term[0])] + [(0, n) for n in n_per_term[1:]]]
+
+
+def _cut_empty3(case, n_per_term):
+    """ranks 0 and 2 split the head at 130 and the second term at 65; rank 1 holds nothing of any term"""
+    at = (130, 65)
+    return [[(0, at[k]) for k in range(len(n_per_term))], [(at[k], at[k]) for k in range(len(n_per_term))],
+            [(at[k], n) for k, n in enumerate(n_per_term)]]
+
+
+# name -> (world, fn(case, n_per_term) -> per rank, per term (begin, end))
+SHARD_CUTS = {"even2": (2, _cut_even2), "chunk2": (2, _cut_chunk2), "lone2": (2, _cut_lone2), "empty3": (3, _cut_empty3)}
+
+
+def shard_ranges(inputs, cut, case=None):
+    """per rank, per term (begin, end) of `cut` over the terms of `inputs`; every point belongs to exactly one rank"""
+    world, fn = SHARD_CUTS[cut]
+    n = tuple(len(s["xyz"]) for s in inputs)
+    out = fn(case, n)
+    assert len(out) == world
+    for k in range(len(n)):
+        assert out[0][k][0] == 0 and out[-1][k][1] == n[k] and all(out[r][k][1] == out[r + 1][k][0] for r in range(world - 1)), (cut, k, out)
+    return out
+
+
+def shard_inputs(inputs, cut, rank, case=None):
+    """what rank `rank` of `cut` holds of `inputs` (host_inputs, or what a device holds): its slice of the points and of the
+    weights of every term, the whole image, K and args.  A produced term (weights == "depth") is sharded as points plus the
+    weights the device produced (tests/test_gpu_feature_pairs.py holds those to depth_weights), so no shard is `produced`."""
+    out = []
+    for s, (b, e) in zip(inputs, shard_ranges(inputs, cut, case)[rank]):
+        failed = s["failed"] if (s.get("failed") is not None and b <= s["failed"] < e) else None
+        out.append(dict(s, xyz=np.ascontiguousarray(s["xyz"][b:e]), weights=None if s["weights"] is None else s["weights"][b:e].copy(),
+                        produced=False, bgr=None, depth=None, failed=None if failed is None else failed - b))
+    return out
+
+
+def shard_reference(case, q, t, dtype=np.longdouble, inputs=None, cut="even2", rank=0, loss=None, key=None):
+    """`reference` over the shard of rank `rank`, the prior left out (it belongs to the reduced system, once): cost_points,
+    JtJ_points, Jtr_points, n_invalid and the rows; all zeros for a rank that holds nothing"""
+    inputs = host_inputs(case) if inputs is None else inputs
+    return reference(case.with_(prior="none"), q, t, dtype, shard_inputs(inputs, cut, rank, case), loss,
+                     None if key is None else (key, "shard", cut, rank))
+
+
+def shard_tolerances(case, q, t, inputs=None, cut="even2", rank=0, loss=None, key=None):
+    """`tolerances` over the shard's inputs; a shard without a valid row has nothing that could round: its sums are exact zeros
+    (bars of 0)"""
+    inputs = host_inputs(case) if inputs is None else inputs
+    sh = shard_inputs(inputs, cut, rank, case)
+    ref = reference(case.with_(prior="none"), q, t, np.longdouble, sh, loss, None if key is None else (key, "shard", cut, rank))
+    if not (~np.isnan(ref["r"].astype(np.float64))).any():
+        return dict(r=0.0, J=0.0, sums=0.0)
+    return tolerances(case.with_(prior="none"), q, t, sh, loss, None if key is None else (key, "shard", cut, rank))
+
+
+def sharded_runs():
+    """what the sharded forms run, in array order: every case as solve_case (kind "solve"), every fp32 case once more as its
+    fp64 twin ("twin": the fp32 solve bars alone would not notice a prior counted twice or weights dropped on one shard), and
+    every case with a failed block as itself ("failed": every rank ends at its first evaluation, the pose untouched)"""
+    out = []
+    for c in cases():
+        out.append(("solve", solve_case(c)))
+        if c["dtype"] == "f32":
+            out.append(("twin", solve_case(c).with_(dtype="f64")))
+        if c["failed"] == "one":
+            out.append(("failed", c))
+    return out
+
+
+def sharded_system(case, q, t, cut, dtype=np.longdouble, inputs=None, loss=None, key=None, prior_per_rank=False, unit_weights_rank=None,
+                   drop_term_rank=None, loss_of_rank=None):
+    """The first exchange of a sharded solve at (q, t), restated: -> (local, reduced).  local: per rank dict(cost, JtJ, Jtr,
+    n_invalid) as the rank sends it; reduced: their sum plus the prior, once.  The keyword arguments restate the mistakes the
+    GPU tests must be able to see: the prior added once per rank (to what the rank sends), the weights of one rank's shard
+    replaced by 1, the second term left out on one rank, the loss of one rank another one ((rank, (kind, a)))."""
+    inputs = host_inputs(case) if inputs is None else inputs
+    world = SHARD_CUTS[cut][0]
+    pJ, pr, pc = prior_terms(q, t, **prior(case))
+    local = []
+    for r in range(world):
+        sh = shard_inputs(inputs, cut, r, case)
+        k = None if key is None else (key, "shard", cut, r)
+        ls = loss
+        if unit_weights_rank == r:
+            sh, k = [dict(s, weights=None if s["weights"] is None else np.ones_like(s["weights"])) for s in sh], None
+        if drop_term_rank == r:
+            sh, k = sh[:1], None
+        if loss_of_rank is not None and loss_of_rank[0] == r:
+            ls = loss_of_rank[1]
+        e = reference(case.with_(prior="none"), q, t, dtype, sh, ls, k)
+        x = dict(cost=e["cost_points"], JtJ=e["JtJ_points"], Jtr=e["Jtr_points"], n_invalid=e["n_invalid"])
+        if prior_per_rank:
+            x = dict(cost=x["cost"] + pc, JtJ=x["JtJ"] + pJ, Jtr=x["Jtr"] + pr, n_invalid=x["n_invalid"])
+        local.append(x)
+    red = dict(cost=sum(x["cost"] for x in local), JtJ=sum(x["JtJ"] for x in local), Jtr=sum(x["Jtr"] for x in local),
+               n_invalid=sum(x["n_invalid"] for x in local))
+    if not prior_per_rank:
+        red = dict(cost=red["cost"] + pc, JtJ=red["JtJ"] + pJ, Jtr=red["Jtr"] + pr, n_invalid=red["n_invalid"])
+    return local, red

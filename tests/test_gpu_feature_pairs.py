@@ -28,14 +28,15 @@ N = len(CASES)
 
 # ---- building a case on the device ---------------------------------------------------------------------------------------
 class Built:
-    """the case's problems (head first), with the inputs as the device holds them"""
+    """the case's problems (head first), with the inputs as the device holds them.  inputs: what to build from where it is not
+    fp.host_inputs(case) -- a rank's shard of them (fp.shard_inputs: uploaded points and weights, a term may have zero points)"""
 
-    def __init__(self, hip, case):
+    def __init__(self, hip, case, inputs=None):
         self.hip, self.case, self.probs, self.inputs = hip, case, [], []
         dt = hip.EA_F32 if case["dtype"] == "f32" else hip.EA_F64
         kind, a = fp.LOSS[case["loss"]]
         try:
-            for s in fp.host_inputs(case):
+            for s in (fp.host_inputs(case) if inputs is None else inputs):
                 P = hip.Problem(*s["K"], dtype=dt)
                 self.probs.append(P)
                 if s["produced"]:   # the producer's own scatter, with the depth weights written behind it
@@ -55,8 +56,9 @@ class Built:
                     P.set_flavour(0.0, 0.001, True)
                 # the reference takes what the device holds; the host's statement of it is held to the same numbers
                 xyz, w, image = P.get_points(), P.get_weights(), P.get_dt()
-                assert np.array_equal(xyz, s["xyz"]), (case.name(), s["term"], "points")
-                assert (w is None) == (s["weights"] is None) and (w is None or np.array_equal(w, s["weights"])), (case.name(), s["term"], "weights")
+                assert np.array_equal(xyz, s["xyz"]) and xyz.shape == s["xyz"].shape, (case.name(), s["term"], "points")
+                want_w = s["weights"] if len(s["xyz"]) else None   # (a term of zero points holds no weights)
+                assert (w is None) == (want_w is None) and (w is None or np.array_equal(w, want_w)), (case.name(), s["term"], "weights")
                 assert np.array_equal(image, s["image"]), (case.name(), s["term"], "image")
                 self.inputs.append(dict(s, xyz=xyz, weights=w, image=image))
             self.P = self.probs[0]
