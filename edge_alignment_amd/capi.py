@@ -64,6 +64,8 @@ EXPORTED = [
     "ea_problem_set_now_depth", "ea_problem_set_now_depth_device", "ea_batch_set_now_depth", "ea_batch_set_now_depth_device",
     "ea_default_depth_gate_params", "ea_problem_depth_gate", "ea_batch_depth_gate", "ea_batch_depth_gate_device",
     "ea_tracker_batch_set_depth_gate", "ea_tracker_batch_last_depth_gate",
+    "ea_default_point_selection", "ea_problem_select_points", "ea_batch_select_points",
+    "ea_tracker_batch_set_point_selection", "ea_tracker_batch_last_point_selection",
 ]
 
 # measurement hooks (edge_alignment_amd/csrc/ea_hip_dev.h): bound by bench.py, the A/B scripts and the tests that pin the
@@ -197,6 +199,34 @@ def default_depth_gate_params(**over):
 
 def depth_gate_stats_to_dict(s):
     return {k: getattr(s, k) for k, _ in DepthGateStats._fields_}
+
+
+CELL_FIRST, CELL_NEAREST = 0, 1
+
+
+class PointSelection(C.Structure):
+    _fields_ = [("cell_px", C.c_int), ("cell_rule", C.c_int), ("outside", C.c_int), ("height", C.c_int), ("width", C.c_int),
+                ("stride", C.c_int64), ("target", C.c_int64)]
+
+
+class PointSelectionStats(C.Structure):
+    _fields_ = [("n_before", C.c_int64), ("no_pixel", C.c_int64), ("after_cells", C.c_int64), ("n_after", C.c_int64),
+                ("stride_used", C.c_int64)]
+
+
+def default_point_selection(**over):
+    """ea_default_point_selection with the given fields of ea_point_selection replaced"""
+    prm = PointSelection()
+    load().ea_default_point_selection(C.byref(prm))
+    for k, v in over.items():
+        if k not in dict(PointSelection._fields_):
+            raise TypeError("unknown point selection parameter %r" % k)
+        setattr(prm, k, int(v))
+    return prm
+
+
+def point_selection_stats_to_dict(s):
+    return {k: getattr(s, k) for k, _ in PointSelectionStats._fields_}
 
 
 def _depth_image(depth):
@@ -434,6 +464,13 @@ def load():
     L.ea_batch_depth_gate_device.argtypes = [vp, dp, dgp, vp, C.c_int64, dgs]
     L.ea_tracker_batch_set_depth_gate.argtypes = [vp, dgp]
     L.ea_tracker_batch_last_depth_gate.argtypes = [vp, C.c_int, C.c_int, dgs]
+    psp, pss = C.POINTER(PointSelection), C.POINTER(PointSelectionStats)
+    L.ea_default_point_selection.argtypes = [psp]
+    L.ea_default_point_selection.restype = None
+    L.ea_problem_select_points.argtypes = [vp, psp, pss]
+    L.ea_batch_select_points.argtypes = [vp, C.POINTER(C.c_int), C.c_int, psp, pss]
+    L.ea_tracker_batch_set_point_selection.argtypes = [vp, psp]
+    L.ea_tracker_batch_last_point_selection.argtypes = [vp, pss, C.c_int]
     _lib = L
     return L
 
@@ -906,6 +943,15 @@ class Problem:
             depth, kind, h, w = _depth_image(depth)
             _check(load().ea_problem_set_now_depth(self._h, depth.ctypes.data_as(C.c_void_p), kind, h, w, float(z_scaling)))
 
+    def select_points(self, **params):
+        """ea_problem_select_points: thins the problem's points on the device (the reference's stride, one point per cell);
+        params: the fields of ea_point_selection (cell_px, cell_rule, outside, height, width, stride, target).  Returns the
+        stats dict (n_before, no_pixel, after_cells, n_after, stride_used)."""
+        prm = default_point_selection(**params)
+        st = PointSelectionStats()
+        _check(load().ea_problem_select_points(self._h, C.byref(prm), C.byref(st)))
+        return point_selection_stats_to_dict(st)
+
     def depth_gate(self, M, classes=True, **params):
         """ea_problem_depth_gate at b_T_a = M (4x4, or a (q, t) tuple): (class bytes [n] in the caller's order -- None with
         classes=False --, stats dict).  params: the fields of ea_depth_gate_params (radius, abs_tol, rel_tol, w_occluded,
@@ -1229,6 +1275,22 @@ class TrackerBatch:
             return
         prm = default_depth_gate_params(**fields)
         _check(load().ea_tracker_batch_set_depth_gate(self._h, C.byref(prm)))
+
+    def set_point_selection(self, params="default", **fields):
+        """point selection of every new reference (ea_tracker_batch_set_point_selection): set_point_selection(None) = off;
+        otherwise ea_default_point_selection with the given fields of ea_point_selection replaced (height, width stay 0)"""
+        if params is None:
+            _check(load().ea_tracker_batch_set_point_selection(self._h, None))
+            return
+        prm = default_point_selection(**fields)
+        _check(load().ea_tracker_batch_set_point_selection(self._h, C.byref(prm)))
+
+    def last_point_selection(self):
+        """[level][stream] stats dicts: the selection of the push that took each reference (zeros: none)"""
+        n = len(self)
+        st = (PointSelectionStats * (self.levels * n))()
+        _check(load().ea_tracker_batch_last_point_selection(self._h, st, self.levels * n))
+        return [[point_selection_stats_to_dict(st[l * n + i]) for i in range(n)] for l in range(self.levels)]
 
     def last_depth_gate(self, i, level=0):
         """the gate's counts of stream i on `level` in the last push (depth_gate_stats_to_dict); zeros when it was not gated there"""
@@ -1627,6 +1689,16 @@ class Batch:
         arr = (C.c_void_p * max(n, 1))(*[it[0] if on_device else it[0].ctypes.data for it in items])
         fn = load().ea_batch_set_now_depth_device if on_device else load().ea_batch_set_now_depth
         _check(fn(self._h, arr, kind, h, w, float(z_scaling)))
+
+    def select_points(self, sel=None, **params):
+        """ea_batch_select_points over the problems sel (batch indices, each at most once; None: every problem): one launch
+        sequence and one wait.  params: the fields of ea_point_selection.  Returns the stats dicts in the order of sel."""
+        prm = default_point_selection(**params)
+        n = len(self) if sel is None else len(sel)
+        arr = None if sel is None else (C.c_int * max(n, 1))(*[int(i) for i in sel])
+        st = (PointSelectionStats * max(n, 1))()
+        _check(load().ea_batch_select_points(self._h, arr, n, C.byref(prm), st))
+        return [point_selection_stats_to_dict(st[i]) for i in range(n)]
 
     def depth_gate(self, M, out=None, classes=True, **params):
         """ea_batch_depth_gate at the poses M: (class bytes [rows] in the layout of row_offsets(), the head families' rows in

@@ -3115,6 +3115,8 @@ static int self_batch(ea_problem *p, ea_batch **out) {
   return EA_OK;
 }
 
+int ea::problem_self_batch(ea_problem *p, ea_batch **b) { return self_batch(p, b); }
+
 int ea::problem_call_batch(ea_problem *p, ea_batch **b, bool build) {
   int rc = self_batch(p, b);
   if (rc == EA_OK && build) rc = batch_build(*b);  // (no DT image: EA_ERR_STATE, as ea_eval)

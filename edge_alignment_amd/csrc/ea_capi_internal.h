@@ -1,6 +1,7 @@
 // ea_capi_internal.h — what the library's three host translation units share behind include/ea_hip.h: ea_capi.hip (problems,
 // batches, solves; it defines everything declared here but auto_scale_losses), ea_frames.hip (frame producers, tracker) and
-// ea_segments.hip (the calls that run one segment per problem: quantiles, pose statistics, reproject, overlay, depth gate).
+// ea_segments.hip (the calls that run one segment per problem: quantiles, pose statistics, reproject, overlay, depth gate,
+// point selection).
 // Not for ea_comm.hip, which sees problems and batches through the C-ABI and ea_launch.h only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -163,6 +164,8 @@ void batch_frames_set_uploaded(ea_batch *b, int64_t copies);
 int batch_upload_poses(ea_batch *b, const double *q, const double *t, const PoseState **d_poses = nullptr);
 int batch_gate_reserve(ea_batch *b, size_t bytes, unsigned char **device_block, unsigned char **pinned_block);
 int problem_call_batch(ea_problem *p, ea_batch **b, bool build = true);
+// the problem's batch of one as it stands, not built: for point selection, to which a problem without points is a result
+int problem_self_batch(ea_problem *p, ea_batch **b);
 // no problem or batch exists without a device; this answers the "no device" question before a handle is dereferenced
 int require_device();
 // borrowed point arrays (ea_problem_set_points_device) into arrays the problem owns

@@ -1595,6 +1595,11 @@ struct ea_tracker_batch {
   std::vector<ea_depth_gate_stats> last_gate;  // levels x streams, level-major: ea_tracker_batch_last_depth_gate
   int last_gated = 0;
   bool gate_applies() const { return gate_on && gate_prm.apply != 0; }
+  // point selection (ea_tracker_batch_set_point_selection): off = no launch of it
+  bool sel_on = false;
+  ea_point_selection sel_prm{};
+  std::vector<ea_point_selection_stats> last_sel;  // levels x streams, level-major: the push that selected each reference
+  int last_selected = 0;
 };
 
 static int tracker_batch_create(ea_tracker_batch **out, const ea_camera *cams, int count, int levels, int dtype, int device,
@@ -1624,6 +1629,7 @@ static int tracker_batch_create(ea_tracker_batch **out, const ea_camera *cams, i
   tb->last_sums.resize((size_t)levels * count);
   std::memset(tb->last_sums.data(), 0, tb->last_sums.size() * sizeof(ea_summary));
   tb->last_gate.assign((size_t)levels * count, ea_depth_gate_stats{});
+  tb->last_sel.assign((size_t)levels * count, ea_point_selection_stats{});
   *out = tb;
   return EA_OK;
 }
@@ -1669,6 +1675,7 @@ static void tracker_stream_drop(ea_tracker_batch *tb, size_t i) {
     (void)reserve_points(lv.probs[i], 0);
     lv.probs[i]->version++;
   }
+  for (int l = 0; l < tb->levels; ++l) tb->last_sel[(size_t)l * tb->st.size() + i] = ea_point_selection_stats{};
   tb->st[i].frames = 0;
   tb->st[i].cov_valid = false;
   tb->st[i].key = ea_keyframe_state{};
@@ -2080,6 +2087,18 @@ static int tracker_push_references(TrackerPush *s) {
         ref_points_landed(p, s->J[(size_t)l].slots[i].capacity);
         if (tb->gate_applies()) p->weighted = p->n > 0;  // (weights_from_depth: as landed -- they are dd alone, or ones)
       }
+  if (tb->sel_on && any_take) {
+    // the new references are thinned where they landed: per level one ea_batch_select_points over the streams that took one
+    std::vector<int> sel;
+    for (size_t i = 0; i < n; ++i)
+      if (s->take[i]) sel.push_back((int)i);
+    std::vector<ea_point_selection_stats> stats(sel.size());
+    for (int l = 0; l < tb->levels; ++l) {
+      TBRC(ea_batch_select_points(tb->lv[(size_t)l].b, sel.data(), (int)sel.size(), &tb->sel_prm, stats.data()));
+      for (size_t k = 0; k < sel.size(); ++k) tb->last_sel[(size_t)l * n + (size_t)sel[k]] = stats[k];
+    }
+    tb->last_selected = (int)sel.size();
+  }
   return EA_OK;
 }
 
@@ -2137,6 +2156,7 @@ static int tracker_batch_push(ea_tracker_batch *tb, const uint8_t *const *bgr, c
   std::memset(tb->last_sums.data(), 0, tb->last_sums.size() * sizeof(ea_summary));
   std::fill(tb->last_gate.begin(), tb->last_gate.end(), ea_depth_gate_stats{});
   tb->last_gated = 0;
+  tb->last_selected = 0;
   // (a phase that fails has dropped every stream: tracker_batch_fail)
   for (int (*phase)(TrackerPush *) : {tracker_push_frames, tracker_push_images, tracker_push_priors, tracker_push_descent,
                                       tracker_push_covariance, tracker_push_references})
@@ -2252,6 +2272,25 @@ extern "C" int ea_tracker_batch_last_depth_gate(ea_tracker_batch *tb, int level,
   return EA_OK;
 }
 
+extern "C" int ea_tracker_batch_set_point_selection(ea_tracker_batch *tb, const ea_point_selection *prm) {
+  if (prm) {
+    if (const char *why = point_selection_error(prm)) return fail(EA_ERR_INVALID_ARG, why);
+    if (prm->height != 0 || prm->width != 0)
+      return fail(EA_ERR_INVALID_ARG, "height and width must be 0: every level uses the extent of its own DT image");
+  }
+  if (!tb) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  tb->sel_on = prm != nullptr;
+  if (prm) tb->sel_prm = *prm;
+  return EA_OK;
+}
+
+extern "C" int ea_tracker_batch_last_point_selection(const ea_tracker_batch *tb, ea_point_selection_stats *stats, int capacity) {
+  if (!tb || !stats) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (capacity < 0 || (size_t)capacity < tb->last_sel.size()) return fail(EA_ERR_INVALID_ARG, "capacity is smaller than levels x streams");
+  std::copy(tb->last_sel.begin(), tb->last_sel.end(), stats);
+  return EA_OK;
+}
+
 extern "C" int ea_tracker_batch_keyframe_state(ea_tracker_batch *tb, int i, ea_keyframe_state *out) {
   if (!tb || !out) return fail(EA_ERR_INVALID_ARG, "NULL argument");
   if (i < 0 || (size_t)i >= tb->st.size()) return fail(EA_ERR_INVALID_ARG, "no such stream");
@@ -2273,6 +2312,8 @@ extern "C" int ea_tracker_batch_get_info(const ea_tracker_batch *tb, const char 
   else if (k == "keyframe_mode") *value = tb->key_on ? 1 : 0;
   else if (k == "depth_gate") *value = tb->gate_on ? 1 : 0;
   else if (k == "gated") *value = tb->last_gated;
+  else if (k == "point_selection") *value = tb->sel_on ? 1 : 0;
+  else if (k == "selected") *value = tb->last_selected;
   else return fail(EA_ERR_INVALID_ARG, "unknown info key: " + k);
   return EA_OK;
 }

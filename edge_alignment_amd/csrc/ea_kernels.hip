@@ -43,6 +43,7 @@ extern __device__ int g_lm_probe_row;
 #include "ea_poses_map.h"
 #include "ea_starts_map.h"
 #include "ea_depth_gate.h"
+#include "ea_point_select.h"
 #include "ea_lm.h"
 #include "ea_pair_log.h"
 #include "ea_prior.h"
@@ -3512,6 +3513,149 @@ __global__ __launch_bounds__(kDepthGateThreads) void ea_depth_gate_kernel(const 
     if (sum) atomicAdd(&counts[(size_t)kDepthGateClasses * blockIdx.y + tid], (unsigned long long)sum);
   }
 }
+
+// ------------------------------------------------------------------------------------------------
+// Point selection (ea_*_select_points): the reference's stride and one point per cell, on the points a problem holds.
+// ea_hip.h states the rule and ea_point_select.h holds it (select_pixel, select_cell; fp64, nothing contracted), shared with
+// the host shim.
+//
+// Shaped like ea_depth_gate_kernel: one lane per stored point, blockIdx.y the segment (one per problem of the call), the
+// segment uniform per workgroup.  The passes of a call, in stream order:
+//   keys (cell_px > 0)  NEAREST first: atomicMin of the bits of z into the segment's 64-bit cell table (positive doubles order
+//                       like their bit patterns).  Then every rule: atomicMin of the point index into the 32-bit cell table,
+//                       from all points of the cell, or for NEAREST from those whose z bits are the cell's minimum.  Minima of
+//                       integers: the same tables whatever the order of arrival.  The tables are all ones before the pass.
+//   count               a point is flagged when it won its cell, or has no pixel and `outside` keeps those (cell_px == 0: every
+//                       point).  A ballot and a popcount per wavefront, the four wavefronts summed through LDS: one count per
+//                       workgroup, and ONE integer atomic per workgroup on the segment's no_pixel counter.
+//   scan                one workgroup per segment turns its counts into offsets, 1024 at a time with a carry between the
+//                       chunks (ea_edge_scan_kernel's pattern), and leaves the total: the survivors of the cell step.
+//   compact             the flags again (the tables are unchanged), ordinal = block offset + wave prefix + lane rank; the point
+//                       is kept iff ordinal % stride_used == 0 and goes to slot ordinal / stride_used of the segment's new
+//                       arrays: x, y, z and the weight, as stored, by plain vector stores.
+// Ordinals and strides fit 32 bits: a problem holds fewer than 2^31 points, and the host clamps stride and target to 2^31 - 1,
+// which no ordinal reaches.
+template <typename T>
+__device__ __forceinline__ bool point_select_pixel(const PointSelectSeg &sg, int i, int cell_px, int *cell, unsigned long long *zbits) {
+  const double x = (double)((GPtr<T>)static_cast<const T *>(sg.x))[i], y = (double)((GPtr<T>)static_cast<const T *>(sg.y))[i],
+               z = (double)((GPtr<T>)static_cast<const T *>(sg.z))[i];
+  int pu, pv;
+  const bool has = select_pixel(x, y, z, sg.fx, sg.fy, sg.cx, sg.cy, sg.height, sg.width, &pu, &pv);
+  *cell = has ? select_cell(pu, pv, cell_px, sg.cells_x) : 0;
+  *zbits = (unsigned long long)__double_as_longlong(z);
+  return has;
+}
+
+// PASS 0: the cells' smallest z bits (NEAREST only).  PASS 1: the cells' winning index
+template <typename T, int PASS>
+__global__ __launch_bounds__(kPointSelectThreads) void ea_point_select_keys_kernel(const PointSelectSeg *__restrict__ segs, int cell_px,
+                                                                                   int nearest) {
+  const PointSelectSeg &sg = segs[blockIdx.y];
+  const int i = blockIdx.x * kPointSelectThreads + threadIdx.x;
+  if (i >= sg.n) return;
+  int cell;
+  unsigned long long zbits;
+  if (!point_select_pixel<T>(sg, i, cell_px, &cell, &zbits)) return;
+  if (PASS == 0) atomicMin(&sg.zmin[cell], zbits);
+  else if (!nearest || sg.zmin[cell] == zbits) atomicMin(&sg.imin[cell], (unsigned int)i);
+}
+
+template <typename T>
+__device__ __forceinline__ bool point_select_flag(const PointSelectSeg &sg, int i, int cell_px, int outside, bool *no_pixel) {
+  *no_pixel = false;
+  if (cell_px == 0) return true;  // (uniform)
+  int cell;
+  unsigned long long zbits;
+  if (!point_select_pixel<T>(sg, i, cell_px, &cell, &zbits)) { *no_pixel = true; return outside != 0; }
+  return sg.imin[cell] == (unsigned int)i;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kPointSelectThreads) void ea_point_select_count_kernel(const PointSelectSeg *__restrict__ segs, int cell_px,
+                                                                                    int outside, PointSelectOut *__restrict__ out) {
+  __shared__ int s_cnt[kPointSelectThreads / 64][2];
+  const PointSelectSeg &sg = segs[blockIdx.y];
+  const int n = sg.n;
+  const int first = blockIdx.x * kPointSelectThreads;
+  if (first >= n) return;  // (uniform)
+  const int tid = threadIdx.x, i = first + tid;
+  bool flag = false, none = false;
+  if (i < n) flag = point_select_flag<T>(sg, i, cell_px, outside, &none);
+  const int lane = tid & 63, wave = tid >> 6;
+  const int c0 = __popcll(__builtin_amdgcn_ballot_w64(flag)), c1 = __popcll(__builtin_amdgcn_ballot_w64(none));
+  if (lane == 0) { s_cnt[wave][0] = c0; s_cnt[wave][1] = c1; }
+  __syncthreads();
+  if (tid == 0) {
+    int kept = 0, nopix = 0;
+#pragma unroll
+    for (int w = 0; w < kPointSelectThreads / 64; ++w) { kept += s_cnt[w][0]; nopix += s_cnt[w][1]; }
+    sg.block_counts[blockIdx.x] = kept;
+    if (nopix) atomicAdd(&out[blockIdx.y].no_pixel, (unsigned long long)nopix);
+  }
+}
+
+// exclusive scan of a segment's block counts by one workgroup, sequential over chunks of 1024 with a carry
+__global__ __launch_bounds__(kPointSelectScan) void ea_point_select_scan_kernel(const PointSelectSeg *__restrict__ segs,
+                                                                                PointSelectOut *__restrict__ out) {
+  __shared__ int s_buf[kPointSelectScan];
+  __shared__ int s_carry;
+  const PointSelectSeg &sg = segs[blockIdx.x];
+  const int nblocks = (sg.n + kPointSelectThreads - 1) / kPointSelectThreads;
+  int *counts = sg.block_counts;
+  if (threadIdx.x == 0) s_carry = 0;
+  __syncthreads();
+  for (int base = 0; base < nblocks; base += kPointSelectScan) {
+    const int i = base + threadIdx.x;
+    const int v = i < nblocks ? counts[i] : 0;
+    s_buf[threadIdx.x] = v;
+    __syncthreads();
+    for (int off = 1; off < kPointSelectScan; off <<= 1) {  // Hillis-Steele inclusive scan
+      const int t = threadIdx.x >= off ? s_buf[threadIdx.x - off] : 0;
+      __syncthreads();
+      s_buf[threadIdx.x] += t;
+      __syncthreads();
+    }
+    const int incl = s_buf[threadIdx.x], carry = s_carry;
+    if (i < nblocks) counts[i] = carry + incl - v;
+    __syncthreads();
+    if (threadIdx.x == kPointSelectScan - 1) s_carry = carry + incl;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[blockIdx.x].after_cells = s_carry;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kPointSelectThreads) void ea_point_select_compact_kernel(const PointSelectSeg *__restrict__ segs, int cell_px,
+                                                                                      int outside, unsigned int stride, unsigned int target,
+                                                                                      const PointSelectOut *__restrict__ out) {
+  __shared__ int s_cnt[kPointSelectThreads / 64];
+  const PointSelectSeg &sg = segs[blockIdx.y];
+  const int n = sg.n;
+  const int first = blockIdx.x * kPointSelectThreads;
+  if (first >= n) return;  // (uniform)
+  const int tid = threadIdx.x, i = first + tid;
+  bool flag = false, none;
+  if (i < n) flag = point_select_flag<T>(sg, i, cell_px, outside, &none);
+  const int lane = tid & 63, wave = tid >> 6;
+  const unsigned long long m = __builtin_amdgcn_ballot_w64(flag);
+  if (lane == 0) s_cnt[wave] = __popcll(m);
+  __syncthreads();
+  if (!flag) return;
+  unsigned int ordinal = (unsigned int)sg.block_counts[blockIdx.x];
+  for (int w = 0; w < wave; ++w) ordinal += (unsigned int)s_cnt[w];
+  ordinal += (unsigned int)__popcll(m & ((1ull << lane) - 1ull));
+  const unsigned int survivors = (unsigned int)out[blockIdx.y].after_cells;
+  const unsigned int s = (unsigned int)select_stride_used((int64_t)survivors, (int64_t)stride, (int64_t)target);
+  const unsigned int slot = ordinal / s;
+  if (slot * s != ordinal) return;
+  typedef T __attribute__((address_space(1))) *GOutT;
+  const GPtr<T> gz = (GPtr<T>)static_cast<const T *>(sg.z);
+  const GOutT goz = (GOutT) static_cast<T *>(sg.oz);
+  ((GOutT) static_cast<T *>(sg.ox))[slot] = ((GPtr<T>)static_cast<const T *>(sg.x))[i];
+  ((GOutT) static_cast<T *>(sg.oy))[slot] = ((GPtr<T>)static_cast<const T *>(sg.y))[i];
+  goz[slot] = gz[i];
+  if (sg.weighted) goz[sg.w_out + slot] = gz[sg.w_in + i];
+}
 #endif  // !EA_TU_VARIANT
 
 // ------------------------------------------------------------------------------------------------
@@ -4045,6 +4189,28 @@ hipError_t launch_depth_gate(int dtype, const DepthGateWork &w, const ProblemDes
         return hipGetLastError();
       });
     });
+  });
+}
+
+hipError_t launch_point_select(int dtype, const PointSelectWork &w, hipStream_t stream) {
+  if (w.nseg < 1 || w.nseg > 65535 || w.max_n < 0 || !w.segs || !w.out || w.stride < 1 || (w.cell_px > 0 && !w.tables))
+    return hipErrorInvalidValue;
+  if (w.max_n == 0) return hipSuccess;
+  const dim3 grid((unsigned)((w.max_n + kPointSelectThreads - 1) / kPointSelectThreads), (unsigned)w.nseg);
+  if (w.cell_px > 0)
+    if (hipError_t e = hipMemsetAsync(w.tables, 0xFF, w.table_bytes, stream)) return e;
+  return dispatch_dtype(dtype, [&](auto TT) {
+    typedef typename decltype(TT)::type T;
+    if (w.cell_px > 0) {
+      if (w.nearest)
+        hipLaunchKernelGGL((ea_point_select_keys_kernel<T, 0>), grid, dim3(kPointSelectThreads), 0, stream, w.segs, w.cell_px, 1);
+      hipLaunchKernelGGL((ea_point_select_keys_kernel<T, 1>), grid, dim3(kPointSelectThreads), 0, stream, w.segs, w.cell_px, w.nearest);
+    }
+    hipLaunchKernelGGL((ea_point_select_count_kernel<T>), grid, dim3(kPointSelectThreads), 0, stream, w.segs, w.cell_px, w.outside, w.out);
+    hipLaunchKernelGGL(ea_point_select_scan_kernel, dim3((unsigned)w.nseg), dim3(kPointSelectScan), 0, stream, w.segs, w.out);
+    hipLaunchKernelGGL((ea_point_select_compact_kernel<T>), grid, dim3(kPointSelectThreads), 0, stream, w.segs, w.cell_px, w.outside,
+                       w.stride, w.target, w.out);
+    return hipGetLastError();
   });
 }
 

@@ -11,6 +11,7 @@
 
 #include "../../include/ea_hip.h"
 #include "ea_depth_gate.h"
+#include "ea_point_select.h"
 #include "ea_lm.h"
 #include "ea_reproject.h"
 #include "ea_select.h"
@@ -248,6 +249,18 @@ struct DepthGateWork {
   unsigned long long *counts = nullptr;
 };
 hipError_t launch_depth_gate(int dtype, const DepthGateWork &w, const ProblemDesc *probs, hipStream_t stream);
+// ea_point_select_*_kernel (ea_point_select.h): w.nseg segments, w.max_n the longest.  cell_px > 0: `tables` (every segment's
+// cell tables, table_bytes in all) is set to all ones, then the key pass(es); then count, scan and compaction.  out[seg]: zero
+// before the launch; stride and target as the rule has them, clamped to 2^31 - 1 (target 0: off)
+struct PointSelectWork {
+  int nseg = 0, max_n = 0, cell_px = 0, nearest = 0, outside = 0;
+  unsigned int stride = 1, target = 0;
+  const PointSelectSeg *segs = nullptr;
+  PointSelectOut *out = nullptr;
+  void *tables = nullptr;
+  size_t table_bytes = 0;
+};
+hipError_t launch_point_select(int dtype, const PointSelectWork &w, hipStream_t stream);
 hipError_t launch_selftest_reduce(const float *in, float *a, float *b, float *c, float *d, double *o32, double *o64,
                                   hipStream_t stream);
 // ea_kernels_var.hip (the same file under -DEA_TU_VARIANT): what launch_eval_fused (tag 0) / launch_eval_poses_grid (tag 1) hand on

@@ -1,6 +1,6 @@
 // ea_segments.hip — the host side of the calls that run one launch over "one segment per problem of the call: the head
 // family of that problem": residual quantiles and the auto-scaled losses, pose visibility statistics, reproject, overlay and
-// the depth-consistency gate (with the current-frame depth it reads).  Host code only: this file holds no kernel, and it sees
+// the depth-consistency gate (with the current-frame depth it reads) and point selection.  Host code only: this file holds no kernel, and it sees
 // a batch through the functions and the read-only BatchView of ea_capi_internal.h; ea_batch's layout stays ea_capi.hip's.
 
 #include <hip/hip_runtime.h>
@@ -867,4 +867,199 @@ extern "C" int ea_problem_depth_gate(ea_problem *p, const double b_T_a[16], cons
   rc = depth_gate_to_host(b, v, b_T_a, prm, p->n, tmp.empty() ? cls : tmp.data(), stats);  // (the head family's rows start at 0)
   if (rc == EA_OK && cls) scatter_to_callers_order(p->order, 1, tmp.data(), cls);
   return rc;
+}
+
+// ---- point selection (ea_point_select.h; kernels: ea_point_select_*_kernel) -------------------------------------------------
+//
+// One segment per problem of the call: its own points, read where the problem holds them -- no descriptor is needed, so the
+// batch is not built and a problem needs a DT image only for the extent of the cell step.  The survivors are written out of
+// place into arrays sized for the points there are (known without a wait), which replace the problem's after the call's ONE
+// synchronisation; the old ones go back to the cache.  The weights keep living behind z (ea_capi_internal.h: w_off).
+extern "C" void ea_default_point_selection(ea_point_selection *prm) {
+  if (!prm) return;
+  std::memset(prm, 0, sizeof(*prm));
+  prm->cell_rule = EA_CELL_FIRST;
+  prm->stride = 1;
+}
+
+namespace {
+// the new arrays of one problem until the problem takes them
+struct SelectedArrays {
+  void *x = nullptr, *y = nullptr, *z = nullptr;
+  size_t cap = 0;
+  int64_t w_off = 0;
+  SelectedArrays() = default;
+  SelectedArrays(const SelectedArrays &) = delete;
+  SelectedArrays(SelectedArrays &&o) noexcept : x(o.x), y(o.y), z(o.z), cap(o.cap), w_off(o.w_off) { o.x = o.y = o.z = nullptr; }
+  ~SelectedArrays() { drop(); }
+  void drop() {
+    if (x) cached_free(x);
+    if (y) cached_free(y);
+    if (z) cached_free(z);
+    x = y = z = nullptr;
+  }
+};
+}  // namespace
+
+// the layout of reserve_points: [z: cap bytes, rounded up to 256 | w: cap bytes]
+static int selected_arrays_take(SelectedArrays &a, int64_t n, size_t esz, int device) {
+  a.cap = (size_t)n * esz;
+  const size_t z_bytes = (a.cap + 255) & ~(size_t)255;
+  HIPCHK(cached_malloc(&a.x, a.cap, device));
+  HIPCHK(cached_malloc(&a.y, a.cap, device));
+  HIPCHK(cached_malloc(&a.z, z_bytes + a.cap, device));
+  a.w_off = (int64_t)(z_bytes / esz);
+  return EA_OK;
+}
+
+static int batch_select_points(ea_batch *b, const int *sel, int nsel, const ea_point_selection *prm, ea_point_selection_stats *stats) {
+  const BatchView v = batch_view(b);
+  if (!sel) nsel = v.count;
+  if (nsel < 0) return fail(EA_ERR_INVALID_ARG, "nsel must be >= 0");
+  std::vector<ea_problem *> probs((size_t)nsel);
+  for (int j = 0; j < nsel; ++j) {
+    const int i = sel ? sel[j] : j;
+    if (i < 0 || i >= v.count) return fail(EA_ERR_INVALID_ARG, "sel: no such problem in the batch");
+    probs[(size_t)j] = v.probs[i];
+  }
+  {
+    std::vector<const ea_problem *> sorted(probs.begin(), probs.end());
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+      return fail(EA_ERR_INVALID_ARG, "the same problem twice in one selection: its points can be replaced once per call");
+  }
+  int rc = check_segment_count((size_t)nsel, "point selection");
+  if (rc != EA_OK) return rc;
+  // what the problems must be, read off the problems themselves: nothing has touched a device or changed a problem yet
+  std::vector<int> ext_h((size_t)nsel, 0), ext_w((size_t)nsel, 0);
+  for (int j = 0; j < nsel; ++j) {
+    const ea_problem *p = probs[(size_t)j];
+    if (!p->order.empty())
+      return fail(EA_ERR_STATE, "the points are held in a storage order (tiles): set them under ea_problem_set_point_order(p, 0) to select");
+    if (prm->cell_px == 0) continue;
+    const bool given = prm->height > 0;
+    if (!given && !(p->d_dt && p->H > 0 && p->W > 0))
+      return fail(EA_ERR_STATE, "cell_px > 0 needs an extent: height, width or a distance-transform image (ea_problem_set_dt)");
+    ext_h[(size_t)j] = given ? prm->height : p->H;
+    ext_w[(size_t)j] = given ? prm->width : p->W;
+    if (point_selection_cells(prm->cell_px, ext_h[(size_t)j], ext_w[(size_t)j]) > kPointSelectMaxCells)
+      return fail(EA_ERR_INVALID_ARG, "more than 2^26 cells");
+  }
+  if (point_selection_is_identity(prm)) {
+    for (int j = 0; stats && j < nsel; ++j) {
+      const int64_t n = probs[(size_t)j]->n;
+      stats[j] = ea_point_selection_stats{n, 0, n, n, 1};
+    }
+    return EA_OK;
+  }
+  int max_n = 0;
+  for (const ea_problem *p : probs) max_n = std::max(max_n, (int)p->n);
+  if (max_n == 0) {
+    for (int j = 0; stats && j < nsel; ++j) stats[j] = ea_point_selection_stats{0, 0, 0, 0, 1};
+    return EA_OK;
+  }
+  if ((rc = require_device()) != EA_OK) return rc;
+  HIPCHK(hipSetDevice(v.device));
+  const size_t esz = v.dtype == EA_F32 ? 4 : 8;
+  const bool nearest = prm->cell_px > 0 && prm->cell_rule == EA_CELL_NEAREST;
+  // the work block: [z tables (NEAREST) | index tables | block counts], one of each per segment
+  std::vector<size_t> cells((size_t)nsel, 0), blocks((size_t)nsel, 0);
+  size_t total_cells = 0, total_blocks = 0;
+  for (int j = 0; j < nsel; ++j) {
+    const ea_problem *p = probs[(size_t)j];
+    if (p->n == 0) continue;
+    if (prm->cell_px > 0) cells[(size_t)j] = (size_t)point_selection_cells(prm->cell_px, ext_h[(size_t)j], ext_w[(size_t)j]);
+    blocks[(size_t)j] = (size_t)((p->n + kPointSelectThreads - 1) / kPointSelectThreads);
+    total_cells += cells[(size_t)j]; total_blocks += blocks[(size_t)j];
+  }
+  const size_t o_imin = nearest ? total_cells * sizeof(unsigned long long) : 0;
+  const size_t table_bytes = o_imin + total_cells * sizeof(unsigned int), o_counts = align16(table_bytes);
+  DevBuf work;
+  HIPCHK(cached_malloc(&work.p, o_counts + total_blocks * sizeof(int32_t), v.device));
+  std::vector<SelectedArrays> fresh((size_t)nsel);
+  SegmentBlock blk;
+  const size_t bytes = blk.layout((size_t)nsel * sizeof(PointSelectSeg), (size_t)nsel * sizeof(PointSelectOut));
+  HIPCHK(blk.take_pinned(bytes, v.device));
+  std::memset(blk.pinned, 0, bytes);
+  size_t at_cell = 0, at_block = 0;
+  for (int j = 0; j < nsel; ++j) {
+    const ea_problem *p = probs[(size_t)j];
+    PointSelectSeg &sg = blk.records<PointSelectSeg>()[j];
+    sg.n = (int32_t)p->n;
+    if (p->n == 0) continue;
+    SelectedArrays &a = fresh[(size_t)j];
+    if ((rc = selected_arrays_take(a, p->n, esz, v.device)) != EA_OK) return rc;
+    sg.x = p->d_x; sg.y = p->d_y; sg.z = p->d_z;
+    sg.ox = a.x; sg.oy = a.y; sg.oz = a.z;
+    sg.weighted = p->weighted ? 1 : 0;
+    sg.w_in = p->weighted ? p->w_off : 0; sg.w_out = a.w_off;
+    sg.fx = p->cam.fx; sg.fy = p->cam.fy; sg.cx = p->cam.cx; sg.cy = p->cam.cy;
+    sg.height = ext_h[(size_t)j]; sg.width = ext_w[(size_t)j];
+    if (prm->cell_px > 0) {
+      sg.cells_x = select_cells_x(prm->cell_px, sg.width);
+      sg.zmin = nearest ? work.as<unsigned long long>() + at_cell : nullptr;
+      sg.imin = reinterpret_cast<unsigned int *>(work.as<unsigned char>() + o_imin) + at_cell;
+    }
+    sg.block_counts = reinterpret_cast<int32_t *>(work.as<unsigned char>() + o_counts) + at_block;
+    at_cell += cells[(size_t)j]; at_block += blocks[(size_t)j];
+  }
+  HIPCHK(blk.take_device(bytes, v.device));
+  HIPCHK(blk.up(v.stream));
+  PointSelectWork w;
+  w.nseg = nsel; w.max_n = max_n; w.cell_px = prm->cell_px; w.nearest = nearest ? 1 : 0; w.outside = prm->outside;
+  w.stride = (unsigned int)std::min<int64_t>(prm->stride, 0x7fffffff);
+  w.target = (unsigned int)std::min<int64_t>(prm->target, 0x7fffffff);
+  w.segs = blk.dev_records<PointSelectSeg>();
+  w.out = blk.dev_results<PointSelectOut>();
+  w.tables = work.p; w.table_bytes = table_bytes;
+  hipError_t e = launch_point_select(v.dtype, w, v.stream);
+  if (e == hipSuccess) e = blk.down(v.stream);
+  const hipError_t es = hipStreamSynchronize(v.stream);  // (nothing of the call stays in flight when the new arrays are dropped)
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return fail(EA_ERR_HIP, std::string("ea_batch_select_points: ") + hipGetErrorString(e));
+  // the survivors become the problems' points
+  for (int j = 0; j < nsel; ++j) {
+    ea_problem *p = probs[(size_t)j];
+    const PointSelectOut &o = blk.results<PointSelectOut>()[j];
+    ea_point_selection_stats st{p->n, 0, 0, 0, 1};
+    if (p->n > 0) {
+      st.no_pixel = (int64_t)o.no_pixel;
+      st.after_cells = (int64_t)o.after_cells;
+      st.stride_used = select_stride_used(st.after_cells, prm->stride, prm->target);
+      st.n_after = select_count_after(st.after_cells, st.stride_used);
+      SelectedArrays &a = fresh[(size_t)j];
+      if (st.n_after == 0) {  // (a problem without points holds no arrays and no weights)
+        a.drop();
+        (void)reserve_points(p, 0);
+      } else {
+        if (p->own_points) { cached_free(p->d_x); cached_free(p->d_y); cached_free(p->d_z); }
+        p->d_x = a.x; p->d_y = a.y; p->d_z = a.z;
+        a.x = a.y = a.z = nullptr;
+        p->own_points = true;
+        p->pts_cap = a.cap;
+        p->w_off = a.w_off;
+        p->n = st.n_after;
+      }
+      p->version++;
+    }
+    if (stats) stats[j] = st;
+  }
+  return EA_OK;
+}
+
+extern "C" int ea_batch_select_points(ea_batch *b, const int *sel, int nsel, const ea_point_selection *prm,
+                                      ea_point_selection_stats *stats) {
+  if (!b || !prm) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (const char *why = point_selection_error(prm)) return fail(EA_ERR_INVALID_ARG, why);
+  return batch_select_points(b, sel, nsel, prm, stats);
+}
+
+extern "C" int ea_problem_select_points(ea_problem *p, const ea_point_selection *prm, ea_point_selection_stats *stats) {
+  if (!prm) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (const char *why = point_selection_error(prm)) return fail(EA_ERR_INVALID_ARG, why);
+  if (!p) return fail(EA_ERR_INVALID_ARG, "NULL problem");
+  ea_batch *b;
+  int rc = problem_self_batch(p, &b);
+  if (rc != EA_OK) return rc;
+  return batch_select_points(b, nullptr, 1, prm, stats);
 }

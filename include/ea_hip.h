@@ -493,6 +493,59 @@ int ea_batch_depth_gate(ea_batch *b, const double *b_T_a /* count x 16 */, const
 int ea_batch_depth_gate_device(ea_batch *b, const double *b_T_a, const ea_depth_gate_params *prm,
                                uint8_t *cls_dev, int64_t capacity_rows, ea_depth_gate_stats *stats);
 
+/* ---- point selection: the reference's stride, and one point per cell ------------------------------------------------------
+ * Every standalone test of the reference thins its edge points before it builds the problem: `i += 30`
+ * (standalone_edge_align.cpp:267), `i += 10` (:470), iterStep = N / minNumOfPointsPerimage when N exceeds it (:1216-1221,
+ * :2590-2596).  These calls do it to the points a problem holds, on the device: no point or weight crosses the bus.
+ * The rule -- the specification; fp64 throughout, the STORED points (the problem dtype) widened to double, IEEE divisions, no
+ * contracted multiply-add; the problem's OWN residual family (call it on a term to thin the term):
+ *   pixel   the plain pinhole of the problem's own camera at the identity pose, no distortion and no rig (what is wanted is
+ *           the reference frame's own pixel): a = x / z, b = y / z; u = fx * a, rounded, then + cx; v = fy * b, rounded, then
+ *           + cy; pu = floor(u + 0.5), pv = floor(v + 0.5).  The point HAS A PIXEL iff z > 0 (false for NaN), u and v are
+ *           finite, 0 <= pu < width and 0 <= pv < height, compared in double before any conversion to int.  (+ 0.5: a
+ *           producer's point lands on the pixel it came from in spite of the rounding of back- and re-projection.)
+ *           height x width: as given, or with 0 x 0 the extent of the problem's DT image.
+ *   cell    (pv / cell_px) * ceil(width / cell_px) + pu / cell_px, integer divisions.
+ *   index   a point's position in the problem's order: the caller's, which for producer points is raster order.
+ *   1  cell step (cell_px > 0): of the points that have a pixel one winner per occupied cell -- EA_CELL_FIRST the lowest
+ *      index, EA_CELL_NEAREST the smallest z (positive doubles order like their bit patterns), ties by lowest index.  Points
+ *      without a pixel: outside == 0 dropped, outside == 1 all kept (they bypass the cell step).  cell_px == 0: no cell step,
+ *      no pixel is computed, every point survives it and no_pixel reports 0.
+ *   2  stride step, on the ordinal among the survivors of step 1 in point order: ordinals 0, s, 2 s, ... are kept, s = stride,
+ *      or with target > 0 the reference's iterStep rule s = m > target ? m / target : 1 (integer division, m = survivors of
+ *      step 1).  The survivors keep their relative order.
+ *   stats: n_before, no_pixel, after_cells = m, n_after = ceil(m / stride_used), stride_used = s.
+ * After the call the problem holds exactly the surviving points, in their order, bit for bit as they were stored, in arrays it
+ * owns (borrowed device points are not written); their weights are compacted by the same flags, `weighted` and the origin of
+ * the weights unchanged; the version moves: batches rebuild and drop resident poses as after any points setter.  Loss,
+ * auto-scale, priors, held coordinates, DT image, now-depth, depth-weighting setting and terms are not touched.  With
+ * cell_px == 0, stride == 1, target == 0 the call changes nothing and moves no version.  A problem without points is a
+ * result: all stats zero, stride_used 1.
+ * One launch sequence -- clear, key pass(es), flag + count, scan, compaction -- and ONE synchronisation on the batch's stream
+ * serve a whole call; the same bits on every run.  sel: the problems of the batch the call thins, each at most once, in the
+ * order of `stats`; NULL: every problem (nsel ignored).
+ * EA_ERR_INVALID_ARG, before a device or a problem is touched: a NULL handle or prm, cell_px outside 0..4096, an unknown
+ * cell_rule or outside, stride < 1, target < 0, stride > 1 together with target > 0, a negative extent or only one of
+ * height / width, more than 2^26 cells; then: an index of sel out of range or twice.  EA_ERR_STATE, before any problem
+ * changes: cell_px > 0 with no extent given and no DT image on a problem; a problem whose points are held in a storage order
+ * (tiles: ea_problem_set_point_order(p, 0) before the points are set keeps the caller's order).
+ * Out of scope: the single ea_tracker, a knob on the per-problem producers, storage-ordered point sets, selection by residual
+ * or by gate class (which composes through the depth gate's weights). */
+enum { EA_CELL_FIRST = 0, EA_CELL_NEAREST = 1 };
+typedef struct {
+  int cell_px;        /* 0: no cell step.  1..4096: side of the square cells, in pixels */
+  int cell_rule;      /* EA_CELL_FIRST: lowest point index in the cell; EA_CELL_NEAREST: smallest z, ties by lowest index */
+  int outside;        /* points that have no pixel: 0 dropped, 1 all kept (they bypass the cell step) */
+  int height, width;  /* pixel grid of the cell step; 0, 0: the extent of the problem's DT image */
+  int64_t stride;     /* >= 1: of the survivors of the cell step, in point order, keep ordinals 0, stride, 2 stride, ... */
+  int64_t target;     /* 0: off.  > 0: stride_used = m > target ? m / target : 1.  Needs stride == 1 */
+} ea_point_selection;
+typedef struct { int64_t n_before, no_pixel, after_cells, n_after, stride_used; } ea_point_selection_stats;
+void ea_default_point_selection(ea_point_selection *prm);   /* cell 0, FIRST, outside 0, 0 x 0, stride 1, target 0 */
+int ea_problem_select_points(ea_problem *p, const ea_point_selection *prm, ea_point_selection_stats *stats /* nullable */);
+int ea_batch_select_points(ea_batch *b, const int *sel /* nullable: every problem */, int nsel, const ea_point_selection *prm,
+                           ea_point_selection_stats *stats /* nullable, one per selected problem */);
+
 /* ceres::Solve(options, &problem, &summary) (standalone_edge_align.cpp:286; SolveEA.cpp:198).
  * q,t in/out.  The whole trust-region loop runs on the device. */
 int ea_solve(ea_problem *p, const ea_options *opt, double q[4], double t[3], ea_summary *summary);
@@ -1241,6 +1294,23 @@ int ea_tracker_batch_keyframe_state(ea_tracker_batch *tb, int i, ea_keyframe_sta
  * has measured on real sequences. */
 int ea_tracker_batch_set_depth_gate(ea_tracker_batch *tb, const ea_depth_gate_params *prm);
 int ea_tracker_batch_last_depth_gate(ea_tracker_batch *tb, int level, int i, ea_depth_gate_stats *out);
+
+/* Point selection inside the multi-stream tracker: every new reference is thinned by ea_batch_select_points' rule before it is
+ * first solved against.  Off by default: a tracker on which it is never set issues no launch, wait or copy more than before.
+ *   set_point_selection(prm): prm == NULL: off.  May be set at any time; it acts on the references taken from then on.
+ *     Parameter errors are ea_batch_select_points' (EA_ERR_INVALID_ARG, found before the handle is looked at); prm->height and
+ *     prm->width must be 0 -- each level uses the extent of its own DT image, and cell_px is in that level's pixels.
+ *   Where: in every push, directly after a level's references have landed (scatter, then depth weights), over the streams
+ *     that TOOK a new reference on that level, on that level's batch: one ea_batch_select_points launch sequence and one wait
+ *     per level.  A kept keyframe's points are not touched.  With a depth gate, the gate's weights are written before the
+ *     NEXT push's solve: they see the selected points.  A push equals, bit for bit, the batched producer followed by
+ *     ea_batch_select_points and ea_batch_solve by hand.
+ *   last_point_selection(stats, capacity): levels x streams rows, level-major (capacity >= that many).  The row of a (level,
+ *     stream) holds the stats of the push that last selected that reference: a kept keyframe keeps its row; a reset or a
+ *     stream without a reference reports zeros.  get_info("selected"): the streams thinned by the last push (on every
+ *     level); get_info("point_selection"): 0 / 1. */
+int ea_tracker_batch_set_point_selection(ea_tracker_batch *tb, const ea_point_selection *prm /* NULL: off */);
+int ea_tracker_batch_last_point_selection(const ea_tracker_batch *tb, ea_point_selection_stats *stats, int capacity);
 
 /* the half-resolution step by itself, host in / host out: kind 0 = bgr8 (height x width x 3 bytes), 1 = float32 with
  * NaN -> 0 first, 2 = float32 as is; dst = (height / 2) x (width / 2); height and width even */
