@@ -14,7 +14,7 @@ SOURCES = [("csrc/ea_kernels.hip", ["-mllvm", "-amdgpu-sched-strategy=max-ilp"])
            ("csrc/ea_preprocess.hip", []), ("csrc/ea_capi.hip", []), ("csrc/ea_frames.hip", []), ("csrc/ea_segments.hip", []),
            ("csrc/ea_comm.hip", [])]
 HEADERS = ["csrc/ea_types.h", "csrc/ea_lm.h", "csrc/ea_cov.h", "csrc/ea_prior.h", "csrc/ea_spin.h", "csrc/ea_hip_dev.h",
-           "csrc/ea_launch.h", "csrc/ea_poses_map.h", "csrc/ea_lanes_stream.h", "csrc/ea_wave_exchange.h", "csrc/ea_pair_log.h", "csrc/ea_starts_map.h", "csrc/ea_search_rank.h", "csrc/ea_select.h", "csrc/ea_reproject.h", "csrc/ea_depth_gate.h", "csrc/ea_point_select.h", "csrc/ea_frame_ws.h", "csrc/ea_keyframe.h", "csrc/ea_capi_internal.h", "../include/ea_hip.h"]
+           "csrc/ea_launch.h", "csrc/ea_poses_map.h", "csrc/ea_lanes_stream.h", "csrc/ea_wave_exchange.h", "csrc/ea_pair_log.h", "csrc/ea_starts_map.h", "csrc/ea_search_rank.h", "csrc/ea_select.h", "csrc/ea_reproject.h", "csrc/ea_depth_gate.h", "csrc/ea_point_select.h", "csrc/ea_point_merge.h", "csrc/ea_frame_ws.h", "csrc/ea_keyframe.h", "csrc/ea_capi_internal.h", "../include/ea_hip.h"]
 LIB = os.path.join(_HERE, "lib", "libea_hip.so")
 # -amdgpu-kernarg-preload-count: the command processor hands the first 16 dwords of the kernel-argument segment to
 # every wave in SGPRs, so a kernel does not start with a scalar load of its own pointers and a wait (gfx950; kernels

@@ -66,6 +66,8 @@ EXPORTED = [
     "ea_tracker_batch_set_depth_gate", "ea_tracker_batch_last_depth_gate",
     "ea_default_point_selection", "ea_problem_select_points", "ea_batch_select_points",
     "ea_tracker_batch_set_point_selection", "ea_tracker_batch_last_point_selection",
+    "ea_default_point_merge", "ea_problem_transform_points", "ea_batch_transform_points", "ea_problem_merge_points",
+    "ea_batch_merge_points", "ea_tracker_batch_set_point_carry", "ea_tracker_batch_last_point_carry",
 ]
 
 # measurement hooks (edge_alignment_amd/csrc/ea_hip_dev.h): bound by bench.py, the A/B scripts and the tests that pin the
@@ -227,6 +229,32 @@ def default_point_selection(**over):
 
 def point_selection_stats_to_dict(s):
     return {k: getattr(s, k) for k, _ in PointSelectionStats._fields_}
+
+
+class PointMerge(C.Structure):
+    _fields_ = [("require_pixel", C.c_int), ("margin", C.c_int), ("max_dt", C.c_double), ("cell_px", C.c_int), ("cell_rule", C.c_int),
+                ("height", C.c_int), ("width", C.c_int), ("max_carried", C.c_int64), ("weight_scale", C.c_double)]
+
+
+class PointMergeStats(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("n_dst", "n_src", "no_pixel", "off_edge", "occupied", "lost_cell", "capped", "carried",
+                                         "n_after")]
+
+
+def default_point_merge(**over):
+    """ea_default_point_merge with the given fields of ea_point_merge replaced"""
+    prm = PointMerge()
+    load().ea_default_point_merge(C.byref(prm))
+    kinds = dict(PointMerge._fields_)
+    for k, v in over.items():
+        if k not in kinds:
+            raise TypeError("unknown point merge parameter %r" % k)
+        setattr(prm, k, float(v) if kinds[k] is C.c_double else int(v))
+    return prm
+
+
+def point_merge_stats_to_dict(s):
+    return {k: getattr(s, k) for k, _ in PointMergeStats._fields_}
 
 
 def _depth_image(depth):
@@ -471,6 +499,15 @@ def load():
     L.ea_batch_select_points.argtypes = [vp, C.POINTER(C.c_int), C.c_int, psp, pss]
     L.ea_tracker_batch_set_point_selection.argtypes = [vp, psp]
     L.ea_tracker_batch_last_point_selection.argtypes = [vp, pss, C.c_int]
+    pmp, pms = C.POINTER(PointMerge), C.POINTER(PointMergeStats)
+    L.ea_default_point_merge.argtypes = [pmp]
+    L.ea_default_point_merge.restype = None
+    L.ea_problem_transform_points.argtypes = [vp, dp]
+    L.ea_batch_transform_points.argtypes = [vp, C.POINTER(C.c_int), C.c_int, dp]
+    L.ea_problem_merge_points.argtypes = [vp, vp, dp, pmp, pms]
+    L.ea_batch_merge_points.argtypes = [vp, C.POINTER(C.c_int), C.c_int, C.POINTER(vp), dp, pmp, pms]
+    L.ea_tracker_batch_set_point_carry.argtypes = [vp, pmp]
+    L.ea_tracker_batch_last_point_carry.argtypes = [vp, pms, C.c_int]
     _lib = L
     return L
 
@@ -952,6 +989,21 @@ class Problem:
         _check(load().ea_problem_select_points(self._h, C.byref(prm), C.byref(st)))
         return point_selection_stats_to_dict(st)
 
+    def transform_points(self, M):
+        """ea_problem_transform_points: the problem's points moved in place by a_T_o = M (4x4, or a (q, t) tuple), fp64, each
+        coordinate rounded once to the problem dtype; n, order and weights stay"""
+        _check(load().ea_problem_transform_points(self._h, _dp(np.ascontiguousarray(_pose_matrix(M)))))
+
+    def merge_points(self, src, M, **params):
+        """ea_problem_merge_points: the points of Problem src, moved by dst_T_src = M and filtered by the fields of
+        ea_point_merge (require_pixel, margin, max_dt, cell_px, cell_rule, height, width, max_carried, weight_scale), appended
+        behind this problem's own.  Returns the stats dict (n_dst, n_src, no_pixel, off_edge, occupied, lost_cell, capped,
+        carried, n_after)."""
+        prm = default_point_merge(**params)
+        st = PointMergeStats()
+        _check(load().ea_problem_merge_points(self._h, src._h, _dp(np.ascontiguousarray(_pose_matrix(M))), C.byref(prm), C.byref(st)))
+        return point_merge_stats_to_dict(st)
+
     def depth_gate(self, M, classes=True, **params):
         """ea_problem_depth_gate at b_T_a = M (4x4, or a (q, t) tuple): (class bytes [n] in the caller's order -- None with
         classes=False --, stats dict).  params: the fields of ea_depth_gate_params (radius, abs_tol, rel_tol, w_occluded,
@@ -1284,6 +1336,22 @@ class TrackerBatch:
             return
         prm = default_point_selection(**fields)
         _check(load().ea_tracker_batch_set_point_selection(self._h, C.byref(prm)))
+
+    def set_point_carry(self, params="default", **fields):
+        """points carried across a keyframe replacement (ea_tracker_batch_set_point_carry): set_point_carry(None) = off;
+        otherwise ea_default_point_merge with the given fields of ea_point_merge replaced (height, width stay 0)"""
+        if params is None:
+            _check(load().ea_tracker_batch_set_point_carry(self._h, None))
+            return
+        prm = default_point_merge(**fields)
+        _check(load().ea_tracker_batch_set_point_carry(self._h, C.byref(prm)))
+
+    def last_point_carry(self):
+        """[stream] stats dicts of the last push's merge (zeros: the stream did not carry)"""
+        n = len(self)
+        st = (PointMergeStats * max(n, 1))()
+        _check(load().ea_tracker_batch_last_point_carry(self._h, st, n))
+        return [point_merge_stats_to_dict(st[i]) for i in range(n)]
 
     def last_point_selection(self):
         """[level][stream] stats dicts: the selection of the push that took each reference (zeros: none)"""
@@ -1699,6 +1767,29 @@ class Batch:
         st = (PointSelectionStats * max(n, 1))()
         _check(load().ea_batch_select_points(self._h, arr, n, C.byref(prm), st))
         return [point_selection_stats_to_dict(st[i]) for i in range(n)]
+
+    def transform_points(self, M, sel=None):
+        """ea_batch_transform_points: the points of the problems sel (batch indices, each at most once; None: every problem)
+        moved in place, problem sel[j] by M[j]: one launch and one wait"""
+        n = len(self) if sel is None else len(sel)
+        M = np.ascontiguousarray(_pose_matrices(M, n))
+        arr = None if sel is None else (C.c_int * max(n, 1))(*[int(i) for i in sel])
+        _check(load().ea_batch_transform_points(self._h, arr, n, _dp(M)))
+
+    def merge_points(self, src, M, sel=None, **params):
+        """ea_batch_merge_points: problem sel[j] of the batch (None: every problem) takes the points of Problem src[j] moved by
+        dst_T_src = M[j]: one launch sequence and one wait.  params: the fields of ea_point_merge.  Returns the stats dicts in
+        the order of sel."""
+        prm = default_point_merge(**params)
+        n = len(self) if sel is None else len(sel)
+        if len(src) != n:
+            raise ValueError("one src problem per dst problem")
+        M = np.ascontiguousarray(_pose_matrices(M, n))
+        arr = None if sel is None else (C.c_int * max(n, 1))(*[int(i) for i in sel])
+        srcs = (C.c_void_p * max(n, 1))(*[s._h for s in src])
+        st = (PointMergeStats * max(n, 1))()
+        _check(load().ea_batch_merge_points(self._h, arr, n, srcs, _dp(M), C.byref(prm), st))
+        return [point_merge_stats_to_dict(st[i]) for i in range(n)]
 
     def depth_gate(self, M, out=None, classes=True, **params):
         """ea_batch_depth_gate at the poses M: (class bytes [rows] in the layout of row_offsets(), the head families' rows in

@@ -1,7 +1,7 @@
 // ea_capi_internal.h — what the library's three host translation units share behind include/ea_hip.h: ea_capi.hip (problems,
 // batches, solves; it defines everything declared here but auto_scale_losses), ea_frames.hip (frame producers, tracker) and
 // ea_segments.hip (the calls that run one segment per problem: quantiles, pose statistics, reproject, overlay, depth gate,
-// point selection).
+// point selection, point transform and merge).
 // Not for ea_comm.hip, which sees problems and batches through the C-ABI and ea_launch.h only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -186,6 +186,16 @@ struct GateImages {
 };
 int batch_depth_gate_images(ea_batch *b, const double *b_T_a, const ea_depth_gate_params *prm, const GateImages &img,
                             ea_depth_gate_stats *stats);
+// ea_segments.hip's, for the multi-stream tracker: ea_batch_merge_points with the carried points named as device arrays (the
+// detached arrays of a replaced keyframe) instead of problems; src[j] belongs to problem sel[j].  The parameters have been
+// checked (point_merge_error), the arrays are of the batch's dtype and device and in the caller's order
+struct MergeSource {
+  const void *x = nullptr, *y = nullptr, *z = nullptr;
+  int64_t n = 0, w_off = 0;  // the weights: w_off elements behind z
+  bool weighted = false;
+};
+int batch_merge_arrays(ea_batch *b, const int *sel, int nsel, const MergeSource *src, const double *dst_T_src,
+                       const ea_point_merge *prm, ea_point_merge_stats *stats);
 // ea_segments.hip's, for ea_batch_solve: the losses of ea_problem_set_loss_auto_scale set from the residuals at poses q, t
 int auto_scale_losses(ea_batch *b, const double *q, const double *t);
 

@@ -1600,6 +1600,11 @@ struct ea_tracker_batch {
   ea_point_selection sel_prm{};
   std::vector<ea_point_selection_stats> last_sel;  // levels x streams, level-major: the push that selected each reference
   int last_selected = 0;
+  // points carried across a keyframe replacement (ea_tracker_batch_set_point_carry): off = no launch of it
+  bool carry_on = false;
+  ea_point_merge carry_prm{};
+  std::vector<ea_point_merge_stats> last_carry;  // per stream: the merge of the last push (zeros: it did not carry)
+  int last_carried = 0;
 };
 
 static int tracker_batch_create(ea_tracker_batch **out, const ea_camera *cams, int count, int levels, int dtype, int device,
@@ -1630,6 +1635,7 @@ static int tracker_batch_create(ea_tracker_batch **out, const ea_camera *cams, i
   std::memset(tb->last_sums.data(), 0, tb->last_sums.size() * sizeof(ea_summary));
   tb->last_gate.assign((size_t)levels * count, ea_depth_gate_stats{});
   tb->last_sel.assign((size_t)levels * count, ea_point_selection_stats{});
+  tb->last_carry.assign((size_t)count, ea_point_merge_stats{});
   *out = tb;
   return EA_OK;
 }
@@ -1676,6 +1682,7 @@ static void tracker_stream_drop(ea_tracker_batch *tb, size_t i) {
     lv.probs[i]->version++;
   }
   for (int l = 0; l < tb->levels; ++l) tb->last_sel[(size_t)l * tb->st.size() + i] = ea_point_selection_stats{};
+  tb->last_carry[i] = ea_point_merge_stats{};
   tb->st[i].frames = 0;
   tb->st[i].cov_valid = false;
   tb->st[i].key = ea_keyframe_state{};
@@ -2047,8 +2054,35 @@ static int tracker_push_covariance(TrackerPush *s) {
 // References: on every level the frame's edge points become the reference of every stream -- in keyframe mode (a single level:
 // ea_tracker_batch_set_keyframes) of the streams whose rule says so (keyframe_decide); a ROS stream whose frame has no edge
 // keeps what it holds.  Laplacian, Canny: the counts queued beside the solve come back first (a wait).  Then the last wait.
+namespace {
+// the point arrays of the keyframes a push replaces, detached from their problems until the merge has read them; they go back
+// to the cache with the push, however it ends
+struct DetachedReferences {
+  std::vector<int> streams;
+  std::vector<MergeSource> src;
+  ~DetachedReferences() {
+    for (const MergeSource &m : src) {
+      cached_free(const_cast<void *>(m.x)); cached_free(const_cast<void *>(m.y)); cached_free(const_cast<void *>(m.z));
+    }
+  }
+  // moved, not copied: the problem is left without points and without arrays, as reserve_points(p, 0) leaves one
+  void take(ea_problem *p, int stream) {
+    streams.push_back(stream);
+    src.push_back(MergeSource{p->d_x, p->d_y, p->d_z, p->n, p->weighted ? p->w_off : 0, p->weighted});
+    p->d_x = p->d_y = p->d_z = nullptr;
+    p->own_points = false;
+    p->pts_cap = 0;
+    p->n = 0;
+    p->w_off = 0;
+    p->weighted = p->weights_from_depth = false;
+    p->version++;
+  }
+};
+}  // namespace
+
 static int tracker_push_references(TrackerPush *s) {
   ea_tracker_batch *tb = s->tb;
+  DetachedReferences old;
   const size_t n = tb->st.size();
   s->take.assign(n, 1);
   s->why.assign(n, 0);
@@ -2063,6 +2097,13 @@ static int tracker_push_references(TrackerPush *s) {
       any_take = any_take || s->take[i];
     }
   }
+  if (tb->carry_on && tb->key_on)
+    for (size_t i = 0; i < n; ++i) {
+      // a stream that replaces a keyframe it solved against keeps that keyframe's arrays for the merge below
+      ea_problem *p = tb->lv[0].probs[i];
+      if (s->take[i] && !(s->why[i] & (EA_KEY_FIRST | EA_KEY_SOLVE_FAILED)) && p->n > 0 && p->own_points && p->order.empty())
+        old.take(p, (int)i);
+    }
   for (BatchFrames &j : s->J) {
     if (!s->ros() && any_take) TBRC(batch_counts_fetch(&j));
     TBRC(batch_ref_room(&j, tb->key_on ? s->take.data() : nullptr));
@@ -2087,6 +2128,20 @@ static int tracker_push_references(TrackerPush *s) {
         ref_points_landed(p, s->J[(size_t)l].slots[i].capacity);
         if (tb->gate_applies()) p->weighted = p->n > 0;  // (weights_from_depth: as landed -- they are dd alone, or ones)
       }
+  if (!old.streams.empty()) {
+    // the replaced keyframes' points into the new references, by the pose this push solved: ONE ea_batch_merge_points-equivalent
+    // call over the streams that carry, before point selection
+    const size_t m = old.streams.size();
+    std::vector<double> T(16 * m);
+    std::vector<ea_point_merge_stats> stats(m);
+    for (size_t k = 0; k < m; ++k) {
+      const size_t i = (size_t)old.streams[k];
+      pose_to_matrix(&s->qs[4 * i], &s->ts[3 * i], &T[16 * k]);
+    }
+    TBRC(batch_merge_arrays(tb->lv[0].b, old.streams.data(), (int)m, old.src.data(), T.data(), &tb->carry_prm, stats.data()));
+    for (size_t k = 0; k < m; ++k) tb->last_carry[(size_t)old.streams[k]] = stats[k];
+    tb->last_carried = (int)m;
+  }
   if (tb->sel_on && any_take) {
     // the new references are thinned where they landed: per level one ea_batch_select_points over the streams that took one
     std::vector<int> sel;
@@ -2157,6 +2212,8 @@ static int tracker_batch_push(ea_tracker_batch *tb, const uint8_t *const *bgr, c
   std::fill(tb->last_gate.begin(), tb->last_gate.end(), ea_depth_gate_stats{});
   tb->last_gated = 0;
   tb->last_selected = 0;
+  std::fill(tb->last_carry.begin(), tb->last_carry.end(), ea_point_merge_stats{});
+  tb->last_carried = 0;
   // (a phase that fails has dropped every stream: tracker_batch_fail)
   for (int (*phase)(TrackerPush *) : {tracker_push_frames, tracker_push_images, tracker_push_priors, tracker_push_descent,
                                       tracker_push_covariance, tracker_push_references})
@@ -2291,6 +2348,29 @@ extern "C" int ea_tracker_batch_last_point_selection(const ea_tracker_batch *tb,
   return EA_OK;
 }
 
+extern "C" int ea_tracker_batch_set_point_carry(ea_tracker_batch *tb, const ea_point_merge *prm) {
+  if (prm) {
+    if (const char *why = point_merge_error(prm)) return fail(EA_ERR_INVALID_ARG, why);
+    if (prm->height != 0 || prm->width != 0)
+      return fail(EA_ERR_INVALID_ARG, "height and width must be 0: a stream uses the extent of its own DT image");
+  }
+  if (!tb) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (prm && !tb->key_on) return fail(EA_ERR_STATE, "keyframe mode is off (ea_tracker_batch_set_keyframes)");
+  for (const TrackerStream &s : tb->st)
+    if (s.frames > 0)
+      return fail(EA_ERR_STATE, "a stream holds a reference: set the carry before the first push or after ea_tracker_batch_reset(-1)");
+  tb->carry_on = prm != nullptr;
+  if (prm) tb->carry_prm = *prm;
+  return EA_OK;
+}
+
+extern "C" int ea_tracker_batch_last_point_carry(const ea_tracker_batch *tb, ea_point_merge_stats *stats, int capacity) {
+  if (!tb || !stats) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (capacity < 0 || (size_t)capacity < tb->last_carry.size()) return fail(EA_ERR_INVALID_ARG, "capacity is smaller than the number of streams");
+  std::copy(tb->last_carry.begin(), tb->last_carry.end(), stats);
+  return EA_OK;
+}
+
 extern "C" int ea_tracker_batch_keyframe_state(ea_tracker_batch *tb, int i, ea_keyframe_state *out) {
   if (!tb || !out) return fail(EA_ERR_INVALID_ARG, "NULL argument");
   if (i < 0 || (size_t)i >= tb->st.size()) return fail(EA_ERR_INVALID_ARG, "no such stream");
@@ -2314,6 +2394,8 @@ extern "C" int ea_tracker_batch_get_info(const ea_tracker_batch *tb, const char 
   else if (k == "gated") *value = tb->last_gated;
   else if (k == "point_selection") *value = tb->sel_on ? 1 : 0;
   else if (k == "selected") *value = tb->last_selected;
+  else if (k == "point_carry") *value = tb->carry_on ? 1 : 0;
+  else if (k == "carried") *value = tb->last_carried;
   else return fail(EA_ERR_INVALID_ARG, "unknown info key: " + k);
   return EA_OK;
 }

@@ -44,6 +44,7 @@ extern __device__ int g_lm_probe_row;
 #include "ea_starts_map.h"
 #include "ea_depth_gate.h"
 #include "ea_point_select.h"
+#include "ea_point_merge.h"
 #include "ea_lm.h"
 #include "ea_pair_log.h"
 #include "ea_prior.h"
@@ -3656,6 +3657,174 @@ __global__ __launch_bounds__(kPointSelectThreads) void ea_point_select_compact_k
   goz[slot] = gz[i];
   if (sg.weighted) goz[sg.w_out + slot] = gz[sg.w_in + i];
 }
+// ------------------------------------------------------------------------------------------------
+// Carrying reference points between frames (ea_*_transform_points, ea_*_merge_points).  ea_hip.h states the rule and
+// ea_point_merge.h holds it (merge_transform, merge_pixel, merge_weight on top of ea_point_select.h's select_pixel and
+// select_cell; fp64, nothing contracted), shared with the host shim.
+//
+// Shaped like the point selection passes: one lane per stored point, blockIdx.y the segment (one per problem of the call), the
+// segment uniform per workgroup.  ea_point_transform_kernel rewrites a problem's points in place: a lane reads its own point,
+// then writes it.  The passes of a merge, in stream order:
+//   occupancy (cell_px > 0)  every dst point that has a pixel clears its cell's byte (all ones before the pass): plain stores
+//                            of one value, the same table whatever the order of arrival.
+//   keys (cell_px > 0)       over the src points that pass steps 1-3 and whose cell is free: NEAREST first the atomicMin of the
+//                            bits of z' (positive doubles order like their bit patterns), then every rule the atomicMin of the
+//                            src index.  Minima of integers.
+//   count                    steps 1-4 again; a ballot and a popcount per wavefront, summed through LDS: one count of survivors
+//                            per workgroup, and at most one integer atomic per workgroup and counter of the segment.
+//   scan                     ea_point_select_scan_kernel on the block counts: offsets, and the survivors of the segment.
+//   copy                     workgroups [0, dst_blocks): dst's points as stored to the front of the new arrays, its weights or
+//                            exactly 1.  Workgroups behind them: a surviving src point whose ordinal is below the cap goes to
+//                            slot n_dst + ordinal -- the rounded x', y', z' and w_src * weight_scale.  Plain vector stores.
+template <typename T>
+__global__ __launch_bounds__(kPointMergeThreads) void ea_point_transform_kernel(const PointTransformSeg *__restrict__ segs) {
+  const PointTransformSeg &sg = segs[blockIdx.y];
+  const int i = blockIdx.x * kPointMergeThreads + threadIdx.x;
+  if (i >= sg.n) return;
+  typedef T __attribute__((address_space(1))) *GOutT;
+  const GOutT gx = (GOutT) static_cast<T *>(sg.x), gy = (GOutT) static_cast<T *>(sg.y), gz = (GOutT) static_cast<T *>(sg.z);
+  double ox, oy, oz;
+  merge_transform(sg.M, (double)gx[i], (double)gy[i], (double)gz[i], &ox, &oy, &oz);
+  gx[i] = (T)ox; gy[i] = (T)oy; gz[i] = (T)oz;
+}
+
+// what steps 1-3 make of src point i: 0 a candidate (pu, pv, cell and the bits of z' set where a pixel was asked for),
+// 1 no pixel, 2 off the edges.  The rounded point comes back in r[3]
+template <typename T>
+__device__ __forceinline__ int point_merge_candidate(const PointMergeSeg &sg, int i, int need_pixel, int margin, double max_dt, int cell_px,
+                                                     T r[3], int *cell, unsigned long long *zbits) {
+  double ox, oy, oz;
+  merge_transform(sg.M, (double)((GPtr<T>)static_cast<const T *>(sg.sx))[i], (double)((GPtr<T>)static_cast<const T *>(sg.sy))[i],
+                  (double)((GPtr<T>)static_cast<const T *>(sg.sz))[i], &ox, &oy, &oz);
+  r[0] = (T)ox; r[1] = (T)oy; r[2] = (T)oz;
+  *cell = 0;
+  *zbits = (unsigned long long)__double_as_longlong((double)r[2]);
+  if (!need_pixel) return 0;  // (uniform)
+  int pu, pv;
+  if (!merge_pixel((double)r[0], (double)r[1], (double)r[2], sg.fx, sg.fy, sg.cx, sg.cy, sg.height, sg.width, margin, &pu, &pv)) return 1;
+  if (max_dt >= 0.0) {
+    const double d = (double)((GPtr<T>)static_cast<const T *>(sg.dt))[(size_t)(pv + kImagePad) * (size_t)sg.pitch + (size_t)(pu + kImagePad)];
+    if (!(d <= max_dt)) return 2;  // (NaN fails)
+  }
+  if (cell_px > 0) *cell = select_cell(pu, pv, cell_px, sg.cells_x);
+  return 0;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kPointMergeThreads) void ea_point_merge_occupancy_kernel(const PointMergeSeg *__restrict__ segs, int cell_px) {
+  const PointMergeSeg &sg = segs[blockIdx.y];
+  const int i = blockIdx.x * kPointMergeThreads + threadIdx.x;
+  if (i >= sg.n_dst) return;
+  int pu, pv;
+  if (!select_pixel((double)((GPtr<T>)static_cast<const T *>(sg.x))[i], (double)((GPtr<T>)static_cast<const T *>(sg.y))[i],
+                    (double)((GPtr<T>)static_cast<const T *>(sg.z))[i], sg.fx, sg.fy, sg.cx, sg.cy, sg.height, sg.width, &pu, &pv))
+    return;
+  sg.occ[select_cell(pu, pv, cell_px, sg.cells_x)] = 0;
+}
+
+// PASS 0: the free cells' smallest z' bits (NEAREST only).  PASS 1: the free cells' winning src index
+template <typename T, int PASS>
+__global__ __launch_bounds__(kPointMergeThreads) void ea_point_merge_keys_kernel(const PointMergeSeg *__restrict__ segs, int margin,
+                                                                                 double max_dt, int cell_px, int nearest) {
+  const PointMergeSeg &sg = segs[blockIdx.y];
+  const int i = blockIdx.x * kPointMergeThreads + threadIdx.x;
+  if (i >= sg.n_src) return;
+  T r[3];
+  int cell;
+  unsigned long long zbits;
+  if (point_merge_candidate<T>(sg, i, 1, margin, max_dt, cell_px, r, &cell, &zbits) != 0) return;
+  if (sg.occ[cell] == 0) return;
+  if (PASS == 0) atomicMin(&sg.zmin[cell], zbits);
+  else if (!nearest || sg.zmin[cell] == zbits) atomicMin(&sg.imin[cell], (unsigned int)i);
+}
+
+// steps 1-4 of src point i: 0 survives, 1 no pixel, 2 off the edges, 3 its cell is occupied, 4 it lost its cell
+template <typename T>
+__device__ __forceinline__ int point_merge_fate(const PointMergeSeg &sg, int i, int need_pixel, int margin, double max_dt, int cell_px, T r[3]) {
+  int cell;
+  unsigned long long zbits;
+  const int c = point_merge_candidate<T>(sg, i, need_pixel, margin, max_dt, cell_px, r, &cell, &zbits);
+  if (c != 0 || cell_px == 0) return c;
+  if (sg.occ[cell] == 0) return 3;
+  return sg.imin[cell] == (unsigned int)i ? 0 : 4;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kPointMergeThreads) void ea_point_merge_count_kernel(const PointMergeSeg *__restrict__ segs, int need_pixel,
+                                                                                  int margin, double max_dt, int cell_px,
+                                                                                  PointMergeOut *__restrict__ out) {
+  __shared__ int s_cnt[kPointMergeThreads / 64][5];
+  const PointMergeSeg &sg = segs[blockIdx.y];
+  const int n = sg.n_src;
+  const int first = blockIdx.x * kPointMergeThreads;
+  if (first >= n) return;  // (uniform)
+  const int tid = threadIdx.x, i = first + tid;
+  int fate = -1;
+  T r[3];
+  if (i < n) fate = point_merge_fate<T>(sg, i, need_pixel, margin, max_dt, cell_px, r);
+  const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    const int c = __popcll(__builtin_amdgcn_ballot_w64(fate == k));
+    if (lane == 0) s_cnt[wave][k] = c;
+  }
+  __syncthreads();
+  if (tid < 5) {
+    int sum = 0;
+#pragma unroll
+    for (int w = 0; w < kPointMergeThreads / 64; ++w) sum += s_cnt[w][tid];
+    if (tid == 0) sg.block_counts[blockIdx.x] = sum;
+    else if (sum) {
+      PointMergeOut &o = out[blockIdx.y];
+      unsigned long long *slot = tid == 1 ? &o.no_pixel : tid == 2 ? &o.off_edge : tid == 3 ? &o.occupied : &o.lost_cell;
+      atomicAdd(slot, (unsigned long long)sum);
+    }
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kPointMergeThreads) void ea_point_merge_copy_kernel(const PointMergeSeg *__restrict__ segs, int dst_blocks,
+                                                                                 int need_pixel, int margin, double max_dt, int cell_px,
+                                                                                 unsigned int cap, double weight_scale) {
+  __shared__ int s_cnt[kPointMergeThreads / 64];
+  typedef T __attribute__((address_space(1))) *GOutT;
+  const PointMergeSeg &sg = segs[blockIdx.y];
+  const int tid = threadIdx.x;
+  const GOutT gox = (GOutT) static_cast<T *>(sg.ox), goy = (GOutT) static_cast<T *>(sg.oy), goz = (GOutT) static_cast<T *>(sg.oz);
+  if ((int)blockIdx.x < dst_blocks) {  // (uniform) dst's own points, as stored
+    const int i = blockIdx.x * kPointMergeThreads + tid;
+    if (i >= sg.n_dst) return;
+    const GPtr<T> gz = (GPtr<T>)static_cast<const T *>(sg.z);
+    gox[i] = ((GPtr<T>)static_cast<const T *>(sg.x))[i];
+    goy[i] = ((GPtr<T>)static_cast<const T *>(sg.y))[i];
+    goz[i] = gz[i];
+    if (sg.out_weighted) goz[sg.w_out + i] = sg.dst_weighted ? gz[sg.w_dst + i] : (T)1;
+    return;
+  }
+  const int block = (int)blockIdx.x - dst_blocks;
+  const int n = sg.n_src;
+  const int first = block * kPointMergeThreads;
+  if (first >= n) return;  // (uniform)
+  const int i = first + tid;
+  bool flag = false;
+  T r[3];
+  if (i < n) flag = point_merge_fate<T>(sg, i, need_pixel, margin, max_dt, cell_px, r) == 0;
+  const int lane = tid & 63, wave = tid >> 6;
+  const unsigned long long m = __builtin_amdgcn_ballot_w64(flag);
+  if (lane == 0) s_cnt[wave] = __popcll(m);
+  __syncthreads();
+  if (!flag) return;
+  unsigned int ordinal = (unsigned int)sg.block_counts[block];
+  for (int w = 0; w < wave; ++w) ordinal += (unsigned int)s_cnt[w];
+  ordinal += (unsigned int)__popcll(m & ((1ull << lane) - 1ull));
+  if (cap && ordinal >= cap) return;
+  const size_t slot = (size_t)sg.n_dst + ordinal;
+  gox[slot] = r[0]; goy[slot] = r[1]; goz[slot] = r[2];
+  if (sg.out_weighted) {
+    const double w = sg.src_weighted ? (double)((GPtr<T>)static_cast<const T *>(sg.sz))[sg.w_src + i] : 1.0;
+    goz[sg.w_out + slot] = (T)merge_weight(w, weight_scale);
+  }
+}
 #endif  // !EA_TU_VARIANT
 
 // ------------------------------------------------------------------------------------------------
@@ -4210,6 +4379,40 @@ hipError_t launch_point_select(int dtype, const PointSelectWork &w, hipStream_t 
     hipLaunchKernelGGL(ea_point_select_scan_kernel, dim3((unsigned)w.nseg), dim3(kPointSelectScan), 0, stream, w.segs, w.out);
     hipLaunchKernelGGL((ea_point_select_compact_kernel<T>), grid, dim3(kPointSelectThreads), 0, stream, w.segs, w.cell_px, w.outside,
                        w.stride, w.target, w.out);
+    return hipGetLastError();
+  });
+}
+
+hipError_t launch_point_transform(int dtype, const PointTransformSeg *segs, int nseg, int max_n, hipStream_t stream) {
+  if (nseg < 1 || nseg > 65535 || max_n < 0 || !segs) return hipErrorInvalidValue;
+  if (max_n == 0) return hipSuccess;
+  const dim3 grid((unsigned)((max_n + kPointMergeThreads - 1) / kPointMergeThreads), (unsigned)nseg);
+  return dispatch_dtype(dtype, [&](auto TT) {
+    hipLaunchKernelGGL((ea_point_transform_kernel<typename decltype(TT)::type>), grid, dim3(kPointMergeThreads), 0, stream, segs);
+    return hipGetLastError();
+  });
+}
+
+hipError_t launch_point_merge(int dtype, const PointMergeWork &w, hipStream_t stream) {
+  if (w.nseg < 1 || w.nseg > 65535 || w.max_dst < 0 || w.max_src < 1 || !w.segs || !w.out || !w.scan_segs || !w.scan_out ||
+      (w.cell_px > 0 && !w.tables))
+    return hipErrorInvalidValue;
+  const unsigned dst_blocks = (unsigned)((w.max_dst + kPointMergeThreads - 1) / kPointMergeThreads);
+  const unsigned src_blocks = (unsigned)((w.max_src + kPointMergeThreads - 1) / kPointMergeThreads);
+  const dim3 block(kPointMergeThreads), grid_dst(dst_blocks, (unsigned)w.nseg), grid_src(src_blocks, (unsigned)w.nseg);
+  if (w.cell_px > 0)
+    if (hipError_t e = hipMemsetAsync(w.tables, 0xFF, w.table_bytes, stream)) return e;
+  return dispatch_dtype(dtype, [&](auto TT) {
+    typedef typename decltype(TT)::type T;
+    if (w.cell_px > 0) {
+      if (dst_blocks) hipLaunchKernelGGL((ea_point_merge_occupancy_kernel<T>), grid_dst, block, 0, stream, w.segs, w.cell_px);
+      if (w.nearest) hipLaunchKernelGGL((ea_point_merge_keys_kernel<T, 0>), grid_src, block, 0, stream, w.segs, w.margin, w.max_dt, w.cell_px, 1);
+      hipLaunchKernelGGL((ea_point_merge_keys_kernel<T, 1>), grid_src, block, 0, stream, w.segs, w.margin, w.max_dt, w.cell_px, w.nearest);
+    }
+    hipLaunchKernelGGL((ea_point_merge_count_kernel<T>), grid_src, block, 0, stream, w.segs, w.need_pixel, w.margin, w.max_dt, w.cell_px, w.out);
+    hipLaunchKernelGGL(ea_point_select_scan_kernel, dim3((unsigned)w.nseg), dim3(kPointSelectScan), 0, stream, w.scan_segs, w.scan_out);
+    hipLaunchKernelGGL((ea_point_merge_copy_kernel<T>), dim3(dst_blocks + src_blocks, (unsigned)w.nseg), block, 0, stream, w.segs,
+                       (int)dst_blocks, w.need_pixel, w.margin, w.max_dt, w.cell_px, w.cap, w.weight_scale);
     return hipGetLastError();
   });
 }

@@ -12,6 +12,7 @@
 #include "../../include/ea_hip.h"
 #include "ea_depth_gate.h"
 #include "ea_point_select.h"
+#include "ea_point_merge.h"
 #include "ea_lm.h"
 #include "ea_reproject.h"
 #include "ea_select.h"
@@ -261,6 +262,25 @@ struct PointSelectWork {
   size_t table_bytes = 0;
 };
 hipError_t launch_point_select(int dtype, const PointSelectWork &w, hipStream_t stream);
+// ea_point_transform_kernel (ea_point_merge.h): nseg segments, max_n the longest; every segment's points rewritten in place
+hipError_t launch_point_transform(int dtype, const PointTransformSeg *segs, int nseg, int max_n, hipStream_t stream);
+// ea_point_merge_*_kernel (ea_point_merge.h): w.nseg segments, max_dst / max_src the longest dst and src (max_src >= 1).
+// cell_px > 0: `tables` (every segment's occupancy bytes and cell tables, table_bytes in all) is set to all ones, then the
+// occupancy pass over the dst points and the key pass(es) over the src points; then count, scan (ea_point_select_scan_kernel on
+// scan_segs, whose n and block_counts are the segments' n_src and block_counts: its total is the survivors) and the copy.
+// out[seg], scan_out[seg]: zero before the launch; cap: max_carried clamped to 2^31 - 1 (0: off)
+struct PointMergeWork {
+  int nseg = 0, max_dst = 0, max_src = 0, need_pixel = 0, margin = 0, cell_px = 0, nearest = 0;
+  double max_dt = -1.0, weight_scale = 1.0;
+  unsigned int cap = 0;
+  const PointMergeSeg *segs = nullptr;
+  PointMergeOut *out = nullptr;
+  const PointSelectSeg *scan_segs = nullptr;
+  PointSelectOut *scan_out = nullptr;
+  void *tables = nullptr;
+  size_t table_bytes = 0;
+};
+hipError_t launch_point_merge(int dtype, const PointMergeWork &w, hipStream_t stream);
 hipError_t launch_selftest_reduce(const float *in, float *a, float *b, float *c, float *d, double *o32, double *o64,
                                   hipStream_t stream);
 // ea_kernels_var.hip (the same file under -DEA_TU_VARIANT): what launch_eval_fused (tag 0) / launch_eval_poses_grid (tag 1) hand on

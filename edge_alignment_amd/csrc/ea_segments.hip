@@ -1,6 +1,7 @@
 // ea_segments.hip — the host side of the calls that run one launch over "one segment per problem of the call: the head
 // family of that problem": residual quantiles and the auto-scaled losses, pose visibility statistics, reproject, overlay and
-// the depth-consistency gate (with the current-frame depth it reads) and point selection.  Host code only: this file holds no kernel, and it sees
+// the depth-consistency gate (with the current-frame depth it reads), point selection and the transform and merge of point
+// sets.  Host code only: this file holds no kernel, and it sees
 // a batch through the functions and the read-only BatchView of ea_capi_internal.h; ea_batch's layout stays ea_capi.hip's.
 
 #include <hip/hip_runtime.h>
@@ -1062,4 +1063,268 @@ extern "C" int ea_problem_select_points(ea_problem *p, const ea_point_selection 
   int rc = problem_self_batch(p, &b);
   if (rc != EA_OK) return rc;
   return batch_select_points(b, nullptr, 1, prm, stats);
+}
+
+// ---- carrying points between frames (ea_point_merge.h; kernels: ea_point_transform_kernel, ea_point_merge_*_kernel) ---------
+//
+// Like point selection these calls read the points where the problems hold them and build no batch.  The transform rewrites
+// the arrays in place; the merge writes dst's points and the carried ones out of place into arrays sized n_dst + n_src (known
+// without a wait), which replace dst's after the call's ONE synchronisation.
+extern "C" void ea_default_point_merge(ea_point_merge *prm) {
+  if (!prm) return;
+  std::memset(prm, 0, sizeof(*prm));
+  prm->max_dt = -1.0;
+  prm->cell_rule = EA_CELL_FIRST;
+  prm->weight_scale = 1.0;
+}
+
+static const char *kStorageOrderMessage =
+    "the points are held in a storage order (tiles): set them under ea_problem_set_point_order(p, 0) to select";
+
+// the problems sel names, each at most once
+static int selected_problems(const BatchView &v, const int *sel, int nsel, const char *twice, std::vector<ea_problem *> *probs) {
+  if (nsel < 0) return fail(EA_ERR_INVALID_ARG, "nsel must be >= 0");
+  probs->resize((size_t)nsel);
+  for (int j = 0; j < nsel; ++j) {
+    const int i = sel ? sel[j] : j;
+    if (i < 0 || i >= v.count) return fail(EA_ERR_INVALID_ARG, "sel: no such problem in the batch");
+    (*probs)[(size_t)j] = v.probs[i];
+  }
+  std::vector<const ea_problem *> sorted(probs->begin(), probs->end());
+  std::sort(sorted.begin(), sorted.end());
+  if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return fail(EA_ERR_INVALID_ARG, twice);
+  return EA_OK;
+}
+
+static int batch_transform_points(ea_batch *b, const int *sel, int nsel, const double *a_T_o) {
+  const BatchView v = batch_view(b);
+  if (!sel) nsel = v.count;
+  std::vector<ea_problem *> probs;
+  int rc = selected_problems(v, sel, nsel, "the same problem twice in one transform: chain two calls instead", &probs);
+  if (rc != EA_OK) return rc;
+  for (int j = 0; j < nsel; ++j)
+    if (const char *why = point_transform_error(a_T_o + 16 * (size_t)j)) return fail(EA_ERR_INVALID_ARG, why);
+  if ((rc = check_segment_count((size_t)nsel, "point transform")) != EA_OK) return rc;
+  int max_n = 0;
+  for (const ea_problem *p : probs) {
+    if (!p->order.empty()) return fail(EA_ERR_STATE, kStorageOrderMessage);
+    max_n = std::max(max_n, (int)p->n);
+  }
+  if (max_n == 0) return EA_OK;
+  if ((rc = require_device()) != EA_OK) return rc;
+  HIPCHK(hipSetDevice(v.device));
+  for (ea_problem *p : probs)
+    if ((rc = own_borrowed_points(p)) != EA_OK) return rc;
+  SegmentBlock blk;
+  const size_t bytes = blk.layout((size_t)nsel * sizeof(PointTransformSeg), 0);
+  HIPCHK(blk.take_pinned(bytes, v.device));
+  std::memset(blk.pinned, 0, bytes);
+  for (int j = 0; j < nsel; ++j) {
+    ea_problem *p = probs[(size_t)j];
+    PointTransformSeg &sg = blk.records<PointTransformSeg>()[j];
+    sg.x = p->d_x; sg.y = p->d_y; sg.z = p->d_z;
+    sg.n = (int32_t)p->n;
+    std::memcpy(sg.M, a_T_o + 16 * (size_t)j, sizeof(sg.M));
+  }
+  HIPCHK(blk.take_device(bytes, v.device));
+  hipError_t e = blk.up(v.stream);
+  if (e == hipSuccess) e = launch_point_transform(v.dtype, blk.dev_records<PointTransformSeg>(), nsel, max_n, v.stream);
+  const hipError_t es = hipStreamSynchronize(v.stream);
+  if (e == hipSuccess) e = es;
+  for (ea_problem *p : probs)
+    if (p->n > 0) p->version++;  // (also after a failure: the points may have been written)
+  if (e != hipSuccess) return fail(EA_ERR_HIP, std::string("ea_batch_transform_points: ") + hipGetErrorString(e));
+  return EA_OK;
+}
+
+extern "C" int ea_batch_transform_points(ea_batch *b, const int *sel, int nsel, const double *a_T_o) {
+  if (!b || !a_T_o) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  return batch_transform_points(b, sel, nsel, a_T_o);
+}
+
+extern "C" int ea_problem_transform_points(ea_problem *p, const double a_T_o[16]) {
+  if (!a_T_o) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (const char *why = point_transform_error(a_T_o)) return fail(EA_ERR_INVALID_ARG, why);
+  if (!p) return fail(EA_ERR_INVALID_ARG, "NULL problem");
+  ea_batch *b;
+  int rc = problem_self_batch(p, &b);
+  if (rc != EA_OK) return rc;
+  return batch_transform_points(b, nullptr, 1, a_T_o);
+}
+
+int ea::batch_merge_arrays(ea_batch *b, const int *sel, int nsel, const MergeSource *src, const double *dst_T_src,
+                           const ea_point_merge *prm, ea_point_merge_stats *stats) {
+  const BatchView v = batch_view(b);
+  if (!sel) nsel = v.count;
+  std::vector<ea_problem *> probs;
+  int rc = selected_problems(v, sel, nsel, "the same dst twice in one merge: its points can be replaced once per call", &probs);
+  if (rc != EA_OK) return rc;
+  for (int j = 0; j < nsel; ++j)
+    if (const char *why = point_transform_error(dst_T_src + 16 * (size_t)j)) return fail(EA_ERR_INVALID_ARG, why);
+  if ((rc = check_segment_count((size_t)nsel, "point merge")) != EA_OK) return rc;
+  // what the problems must be, read off the problems themselves: nothing has touched a device or changed a problem yet
+  const bool need_pixel = point_merge_needs_pixel(prm), edge = prm->max_dt >= 0.0;
+  std::vector<int> ext_h((size_t)nsel, 0), ext_w((size_t)nsel, 0);
+  for (int j = 0; j < nsel; ++j) {
+    const ea_problem *p = probs[(size_t)j];
+    if (!p->order.empty()) return fail(EA_ERR_STATE, kStorageOrderMessage);
+    if (p->n + src[j].n >= ((int64_t)1 << 31)) return fail(EA_ERR_INVALID_ARG, "dst and src together hold 2^31 points or more");
+    if (!need_pixel) continue;
+    const bool given = prm->height > 0, image = p->d_dt && p->H > 0 && p->W > 0;
+    if (edge && !image) return fail(EA_ERR_STATE, "max_dt >= 0 needs dst's distance-transform image (ea_problem_set_dt)");
+    if (!given && !image)
+      return fail(EA_ERR_STATE, "the pixel test needs an extent: height, width or a distance-transform image (ea_problem_set_dt)");
+    ext_h[(size_t)j] = given ? prm->height : p->H;
+    ext_w[(size_t)j] = given ? prm->width : p->W;
+    if (edge && (ext_h[(size_t)j] > p->H || ext_w[(size_t)j] > p->W))
+      return fail(EA_ERR_INVALID_ARG, "max_dt >= 0: height x width must lie inside dst's distance-transform image");
+    if (prm->cell_px > 0 && point_selection_cells(prm->cell_px, ext_h[(size_t)j], ext_w[(size_t)j]) > kPointSelectMaxCells)
+      return fail(EA_ERR_INVALID_ARG, "more than 2^26 cells");
+  }
+  int max_dst = 0, max_src = 0;
+  for (int j = 0; j < nsel; ++j) {
+    const ea_problem *p = probs[(size_t)j];
+    if (stats) stats[j] = ea_point_merge_stats{p->n, src[j].n, 0, 0, 0, 0, 0, 0, p->n};
+    if (src[j].n == 0) continue;  // (nothing to carry: the segment launches nothing)
+    max_dst = std::max(max_dst, (int)p->n);
+    max_src = std::max(max_src, (int)src[j].n);
+  }
+  if (max_src == 0) return EA_OK;
+  if ((rc = require_device()) != EA_OK) return rc;
+  HIPCHK(hipSetDevice(v.device));
+  const size_t esz = v.dtype == EA_F32 ? 4 : 8;
+  const bool nearest = prm->cell_px > 0 && prm->cell_rule == EA_CELL_NEAREST;
+  // the work block: [z tables (NEAREST) | index tables | occupancy bytes || block counts], one of each per segment
+  std::vector<size_t> cells((size_t)nsel, 0), blocks((size_t)nsel, 0);
+  size_t total_cells = 0, total_blocks = 0;
+  for (int j = 0; j < nsel; ++j) {
+    if (src[j].n == 0) continue;
+    if (prm->cell_px > 0) cells[(size_t)j] = (size_t)point_selection_cells(prm->cell_px, ext_h[(size_t)j], ext_w[(size_t)j]);
+    blocks[(size_t)j] = (size_t)((src[j].n + kPointMergeThreads - 1) / kPointMergeThreads);
+    total_cells += cells[(size_t)j]; total_blocks += blocks[(size_t)j];
+  }
+  const size_t o_imin = nearest ? total_cells * sizeof(unsigned long long) : 0, o_occ = o_imin + total_cells * sizeof(unsigned int);
+  const size_t table_bytes = o_occ + total_cells, o_counts = align16(table_bytes);
+  DevBuf work;
+  HIPCHK(cached_malloc(&work.p, o_counts + total_blocks * sizeof(int32_t), v.device));
+  std::vector<SelectedArrays> fresh((size_t)nsel);
+  SegmentBlock blk;
+  const size_t o_scan_segs = align16((size_t)nsel * sizeof(PointMergeSeg)), o_scan_out = (size_t)nsel * sizeof(PointMergeOut);
+  const size_t bytes = blk.layout(o_scan_segs + (size_t)nsel * sizeof(PointSelectSeg), o_scan_out + (size_t)nsel * sizeof(PointSelectOut));
+  HIPCHK(blk.take_pinned(bytes, v.device));
+  std::memset(blk.pinned, 0, bytes);
+  PointSelectSeg *scan_segs = reinterpret_cast<PointSelectSeg *>(blk.pinned + o_scan_segs);
+  size_t at_cell = 0, at_block = 0;
+  for (int j = 0; j < nsel; ++j) {
+    const ea_problem *p = probs[(size_t)j];
+    const MergeSource &s = src[j];
+    PointMergeSeg &sg = blk.records<PointMergeSeg>()[j];
+    if (s.n == 0) continue;  // (n_dst = n_src = 0: every pass skips the segment)
+    SelectedArrays &a = fresh[(size_t)j];
+    if ((rc = selected_arrays_take(a, p->n + s.n, esz, v.device)) != EA_OK) return rc;
+    sg.x = p->d_x; sg.y = p->d_y; sg.z = p->d_z;
+    sg.sx = s.x; sg.sy = s.y; sg.sz = s.z;
+    sg.ox = a.x; sg.oy = a.y; sg.oz = a.z;
+    sg.n_dst = (int32_t)p->n; sg.n_src = (int32_t)s.n;
+    sg.dst_weighted = p->weighted ? 1 : 0; sg.src_weighted = s.weighted ? 1 : 0;
+    sg.out_weighted = merge_weighted(p->weighted, s.weighted, prm->weight_scale) ? 1 : 0;
+    sg.w_dst = p->weighted ? p->w_off : 0; sg.w_src = s.weighted ? s.w_off : 0; sg.w_out = a.w_off;
+    std::memcpy(sg.M, dst_T_src + 16 * (size_t)j, sizeof(sg.M));
+    sg.fx = p->cam.fx; sg.fy = p->cam.fy; sg.cx = p->cam.cx; sg.cy = p->cam.cy;
+    sg.height = ext_h[(size_t)j]; sg.width = ext_w[(size_t)j];
+    if (edge) { sg.dt = p->d_dt; sg.pitch = p->pitch; }
+    if (prm->cell_px > 0) {
+      sg.cells_x = select_cells_x(prm->cell_px, sg.width);
+      sg.zmin = nearest ? work.as<unsigned long long>() + at_cell : nullptr;
+      sg.imin = reinterpret_cast<unsigned int *>(work.as<unsigned char>() + o_imin) + at_cell;
+      sg.occ = work.as<unsigned char>() + o_occ + at_cell;
+    }
+    sg.block_counts = reinterpret_cast<int32_t *>(work.as<unsigned char>() + o_counts) + at_block;
+    scan_segs[j].n = sg.n_src;
+    scan_segs[j].block_counts = sg.block_counts;
+    at_cell += cells[(size_t)j]; at_block += blocks[(size_t)j];
+  }
+  HIPCHK(blk.take_device(bytes, v.device));
+  HIPCHK(blk.up(v.stream));
+  PointMergeWork w;
+  w.nseg = nsel; w.max_dst = max_dst; w.max_src = max_src;
+  w.need_pixel = need_pixel ? 1 : 0; w.margin = prm->margin; w.max_dt = edge ? prm->max_dt : -1.0;
+  w.cell_px = prm->cell_px; w.nearest = nearest ? 1 : 0; w.weight_scale = prm->weight_scale;
+  w.cap = (unsigned int)std::min<int64_t>(prm->max_carried, 0x7fffffff);
+  w.segs = blk.dev_records<PointMergeSeg>();
+  w.out = blk.dev_results<PointMergeOut>();
+  w.scan_segs = reinterpret_cast<const PointSelectSeg *>(blk.dev + o_scan_segs);
+  w.scan_out = reinterpret_cast<PointSelectOut *>(blk.dev + blk.o_results + o_scan_out);
+  w.tables = work.p; w.table_bytes = table_bytes;
+  hipError_t e = launch_point_merge(v.dtype, w, v.stream);
+  if (e == hipSuccess) e = blk.down(v.stream);
+  const hipError_t es = hipStreamSynchronize(v.stream);  // (nothing of the call stays in flight when the new arrays are dropped)
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return fail(EA_ERR_HIP, std::string("ea_batch_merge_points: ") + hipGetErrorString(e));
+  // dst's points and the carried ones become dst's points
+  const PointSelectOut *scan_out = reinterpret_cast<const PointSelectOut *>(blk.pinned + blk.o_results + o_scan_out);
+  for (int j = 0; j < nsel; ++j) {
+    ea_problem *p = probs[(size_t)j];
+    if (src[j].n == 0) continue;
+    const PointMergeOut &o = blk.results<PointMergeOut>()[j];
+    ea_point_merge_stats st{p->n, src[j].n, (int64_t)o.no_pixel, (int64_t)o.off_edge, (int64_t)o.occupied, (int64_t)o.lost_cell, 0, 0, 0};
+    const int64_t survivors = (int64_t)scan_out[j].after_cells;
+    st.carried = merge_carried(survivors, prm->max_carried);
+    st.capped = survivors - st.carried;
+    st.n_after = st.n_dst + st.carried;
+    if (st.carried > 0) {
+      SelectedArrays &a = fresh[(size_t)j];
+      const bool weighted = merge_weighted(p->weighted, src[j].weighted, prm->weight_scale);
+      if (p->own_points) { cached_free(p->d_x); cached_free(p->d_y); cached_free(p->d_z); }
+      p->d_x = a.x; p->d_y = a.y; p->d_z = a.z;
+      a.x = a.y = a.z = nullptr;
+      p->own_points = true;
+      p->pts_cap = a.cap;
+      p->w_off = a.w_off;
+      p->n = st.n_after;
+      p->weighted = weighted;
+      p->weights_from_depth = false;
+      p->version++;
+    }
+    if (stats) stats[j] = st;
+  }
+  return EA_OK;
+}
+
+extern "C" int ea_batch_merge_points(ea_batch *dst, const int *sel, int nsel, ea_problem *const *src, const double *dst_T_src,
+                                     const ea_point_merge *prm, ea_point_merge_stats *stats) {
+  if (!prm) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (const char *why = point_merge_error(prm)) return fail(EA_ERR_INVALID_ARG, why);
+  if (!dst || !src || !dst_T_src) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  const BatchView v = batch_view(dst);
+  if (!sel) nsel = v.count;
+  if (nsel < 0) return fail(EA_ERR_INVALID_ARG, "nsel must be >= 0");
+  std::vector<MergeSource> from((size_t)nsel);
+  for (int j = 0; j < nsel; ++j) {
+    const ea_problem *s = src[j];
+    if (!s) return fail(EA_ERR_INVALID_ARG, "NULL src problem");
+    for (int k = 0; k < nsel; ++k) {
+      const int i = sel ? sel[k] : k;
+      if (i >= 0 && i < v.count && v.probs[i] == s)
+        return fail(EA_ERR_INVALID_ARG, k == j ? "dst == src" : "a src problem is also a dst of the call");
+    }
+    if (s->dtype != v.dtype || s->device != v.device) return fail(EA_ERR_INVALID_ARG, "dst and src differ in dtype or device");
+    if (!s->order.empty()) return fail(EA_ERR_STATE, kStorageOrderMessage);
+    from[(size_t)j] = MergeSource{s->d_x, s->d_y, s->d_z, s->n, s->weighted ? s->w_off : 0, s->weighted};
+  }
+  return batch_merge_arrays(dst, sel, nsel, from.data(), dst_T_src, prm, stats);
+}
+
+extern "C" int ea_problem_merge_points(ea_problem *dst, const ea_problem *src, const double dst_T_src[16], const ea_point_merge *prm,
+                                       ea_point_merge_stats *stats) {
+  if (!prm || !dst_T_src) return fail(EA_ERR_INVALID_ARG, "NULL argument");
+  if (const char *why = point_merge_error(prm)) return fail(EA_ERR_INVALID_ARG, why);
+  if (const char *why = point_transform_error(dst_T_src)) return fail(EA_ERR_INVALID_ARG, why);
+  if (!dst || !src) return fail(EA_ERR_INVALID_ARG, "NULL problem");
+  if (dst == src) return fail(EA_ERR_INVALID_ARG, "dst == src");
+  ea_batch *b;
+  int rc = problem_self_batch(dst, &b);
+  if (rc != EA_OK) return rc;
+  ea_problem *from = const_cast<ea_problem *>(src);
+  return ea_batch_merge_points(b, nullptr, 1, &from, dst_T_src, prm, stats);
 }

@@ -546,6 +546,79 @@ int ea_problem_select_points(ea_problem *p, const ea_point_selection *prm, ea_po
 int ea_batch_select_points(ea_batch *b, const int *sel /* nullable: every problem */, int nsel, const ea_point_selection *prm,
                            ea_point_selection_stats *stats /* nullable, one per selected problem */);
 
+/* ---- carrying reference points between frames: transform in place, and merge -------------------------------------------------
+ * The reference places its model points before its main solve: a_X = TransformPrior * o_X (standalone_edge_align.cpp:2385), then
+ * a_X2 = TransformFromFirstCam * a_X (:2388).  These calls do both to the points a problem holds, on the device: no point or
+ * weight crosses the bus.  The problem's OWN residual family only (call it on a term for a term).
+ *
+ * TRANSFORM (ea_*_transform_points) -- the specification; fp64 throughout, the STORED point widened to double, no contracted
+ * multiply-add:
+ *   x' = ((M00 x + M01 y) + M02 z) + M03,  y' = ((M10 x + M11 y) + M12 z) + M13,  z' = ((M20 x + M21 y) + M22 z) + M23
+ * (step B's first line of ea_*_reproject), each rounded ONCE to the problem dtype on store.  A point with NaN or Inf gives what
+ * IEEE gives.  n, the order and the weights are unchanged; a problem with points has its version moved: batches rebuild and
+ * drop resident poses as after any points setter.  Borrowed device points are first copied into arrays the problem owns and
+ * are never written.  Two calls round twice: the chain is not the product matrix.  One launch and ONE synchronisation per call
+ * for any number of problems; the matrices travel in the call's records.
+ * EA_ERR_INVALID_ARG, before a device or a problem is touched: a NULL argument, a non-finite entry, a last row that is not
+ * exactly 0 0 0 1, an index of sel out of range or twice.  EA_ERR_STATE: points held in a storage order (tiles).
+ *
+ * MERGE (ea_*_merge_points).  After the call dst holds its own points first -- unchanged, bit for bit, in their order -- and
+ * behind them the carried points of src, in src order.  src is not touched.  The rule for a src point; every step fp64 in the
+ * stated order:
+ *   1  transform as above with dst_T_src and round to dst's dtype.  Every later step sees this rounded value widened again, so
+ *      the pixel and cell of a carried point are exactly what ea_problem_select_points computes for it afterwards.
+ *   2  pixel test, with require_pixel, and implied by max_dt >= 0 or cell_px > 0: the point must HAVE A PIXEL (point selection's
+ *      rule above) under dst's camera on height x width -- as given, or with 0 x 0 the extent of dst's DT image -- with
+ *      margin <= pu < width - margin and margin <= pv < height - margin.  A failing point counts in no_pixel.
+ *   3  edge test (max_dt >= 0): the value ea_problem_get_dt returns at (pv, pu) -- the image in the problem dtype, not its
+ *      float32 mirror --, widened to double, must be <= max_dt; NaN fails.  A failing point counts in off_edge.  A given extent
+ *      must lie inside the DT image's.
+ *   4  cell step (cell_px > 0), on point selection's cells: a cell that holds any dst point with a pixel (no margin) is
+ *      occupied, and candidates there count in `occupied`; a free cell takes one winner -- EA_CELL_FIRST the lowest src index,
+ *      EA_CELL_NEAREST the smallest z', ties by lowest index -- and the losers count in lost_cell.
+ *   5  cap (max_carried > 0): of the survivors in src order those whose ordinal is >= max_carried count in `capped`.
+ *   stats: n_dst, n_src, the five counts, carried, n_after = n_dst + carried;
+ *          n_src = no_pixel + off_edge + occupied + lost_cell + capped + carried.
+ * Weights: the result is weighted iff dst is, src is, or weight_scale != 1.  Then the own points of a dst that was not weighted
+ * get exactly 1, and a carried point w_src * weight_scale (w_src = 1 for an unweighted src): one IEEE multiplication in double,
+ * rounded to the dtype.  weights_from_depth is cleared when any point is carried.
+ * carried == 0 changes nothing and moves no version.  Otherwise dst's points live in fresh arrays it owns (borrowed ones are
+ * not written) and its version moves.  A dst without points and every filter off is the reference's a_X2 = T * a_X copy.
+ * One launch sequence -- clear, occupancy, key pass(es), flag + count, scan, copy + compaction -- and ONE synchronisation on
+ * the batch's stream serve a whole call; plain stores and integer minima: the same bits on every run.
+ * sel: the dst problems of the batch, each at most once, in the order of src, dst_T_src and stats; NULL: every problem.
+ * EA_ERR_INVALID_ARG, before a device or a problem is touched: a NULL argument, require_pixel outside 0 / 1, margin < 0, max_dt
+ * NaN, cell_px outside 0..4096, an unknown cell_rule, a negative extent or only one of height / width, more than 2^26 cells,
+ * max_carried < 0, weight_scale not finite or <= 0, a bad matrix (as above); then: an index of sel out of range or twice,
+ * dst == src, a src that is also a dst of the call, differing dtypes or devices, a given extent beyond the DT image with
+ * max_dt >= 0.  EA_ERR_STATE, before any problem changes: a pixel test without an extent (no height / width, no DT image),
+ * max_dt >= 0 without a DT image, points held in a storage order on either side.
+ * Out of scope: per-point age or observation counts, depth fusion of a carried point with the new frame's depth, pyramid
+ * levels and the single ea_tracker (see ea_tracker_batch_set_point_carry), storage-ordered point sets, merging terms through
+ * the head. */
+typedef struct {
+  int require_pixel;    /* 1: a carried point must have a pixel in dst (select_pixel) */
+  int margin;           /* >= 0: ... at least this many pixels inside the extent */
+  double max_dt;        /* >= 0: and dst's DT image at that pixel must be <= max_dt; < 0: off */
+  int cell_px;          /* 0: off; else carried points never enter a cell dst already occupies,
+                           and at most one carried point enters a free cell */
+  int cell_rule;        /* EA_CELL_FIRST / EA_CELL_NEAREST among the candidates of one free cell */
+  int height, width;    /* 0, 0: dst's DT extent */
+  int64_t max_carried;  /* 0: no cap; else the first max_carried survivors in src order */
+  double weight_scale;  /* > 0, finite; 1 by default */
+} ea_point_merge;
+typedef struct { int64_t n_dst, n_src, no_pixel, off_edge, occupied, lost_cell, capped,
+                 carried, n_after; } ea_point_merge_stats;
+void ea_default_point_merge(ea_point_merge *prm);   /* everything off, weight_scale 1 */
+int ea_problem_transform_points(ea_problem *p, const double a_T_o[16]);
+int ea_batch_transform_points(ea_batch *b, const int *sel /* NULL: all */, int nsel,
+                              const double *a_T_o /* nsel x 16 */);
+int ea_problem_merge_points(ea_problem *dst, const ea_problem *src, const double dst_T_src[16],
+                            const ea_point_merge *prm, ea_point_merge_stats *stats /* nullable */);
+int ea_batch_merge_points(ea_batch *dst, const int *sel, int nsel, ea_problem *const *src,
+                          const double *dst_T_src /* nsel x 16 */, const ea_point_merge *prm,
+                          ea_point_merge_stats *stats /* nullable, one per dst */);
+
 /* ceres::Solve(options, &problem, &summary) (standalone_edge_align.cpp:286; SolveEA.cpp:198).
  * q,t in/out.  The whole trust-region loop runs on the device. */
 int ea_solve(ea_problem *p, const ea_options *opt, double q[4], double t[3], ea_summary *summary);
@@ -1311,6 +1384,31 @@ int ea_tracker_batch_last_depth_gate(ea_tracker_batch *tb, int level, int i, ea_
  *     level); get_info("point_selection"): 0 / 1. */
 int ea_tracker_batch_set_point_selection(ea_tracker_batch *tb, const ea_point_selection *prm /* NULL: off */);
 int ea_tracker_batch_last_point_selection(const ea_tracker_batch *tb, ea_point_selection_stats *stats, int capacity);
+
+/* Points carried across a keyframe replacement.  In keyframe mode a replaced reference is only the pushed frame's own edge
+ * points: an edge pixel of that frame without a depth reading is lost (flavours 0 and 1; in flavour 2 it carries the fake depth
+ * 1.0), though the old keyframe may have held a 3-D point for that edge.  With a carry set, the old keyframe's points are moved
+ * into the new frame by the pose the push solved and merged behind the new reference by ea_batch_merge_points' rule.  Off by
+ * default: a tracker on which it is never set issues no launch, wait or copy more than before.
+ *   set_point_carry(prm): prm == NULL: off.  Keyframe mode only (EA_ERR_STATE otherwise; so: a single level), all three
+ *     flavours, host and device frames; and, as ea_tracker_batch_set_keyframes, only while no stream holds a reference
+ *     (EA_ERR_STATE).  Parameter errors are ea_batch_merge_points' (EA_ERR_INVALID_ARG, found before the handle is looked at);
+ *     prm->height and prm->width must be 0: a stream uses the extent of its own DT image -- the new frame's, which the push has
+ *     already put in place.
+ *   Where: a stream CARRIES in a push when it replaces its keyframe and its solve did not fail (the reason mask holds neither
+ *     EA_KEY_FIRST nor EA_KEY_SOLVE_FAILED).  Its old point arrays are detached -- moved, not copied -- before the new
+ *     reference takes room; after the new references have landed (scatter, depth weights, the depth gate's ones) ONE merge call
+ *     runs over the carrying streams: src the detached arrays, dst_T_src the matrix ea_pose_to_matrix gives for the pose this
+ *     push solved (the q_rel, t_rel it returns).  Then point selection, when set: a `target` caps the merged reference.  A kept
+ *     keyframe, a first keyframe and a failed solve launch nothing.  A push equals, bit for bit, the batched producer followed
+ *     by ea_batch_merge_points (and ea_batch_select_points) and ea_batch_solve by hand.  The carried weights follow the merge's
+ *     rule.  Flavour 2's fake-depth points occupy cells like any other point.  A push that fails past its checks resets every
+ *     stream as before; the detached arrays are freed either way.
+ *   last_point_carry(stats, capacity): one row per stream (capacity >= streams): the merge of the last push, zeros for a stream
+ *     that did not carry in it.  get_info("carried"): the streams that carried in the last push; get_info("point_carry"): 0 / 1.
+ * Out of scope: pyramid levels, the single ea_tracker, per-point age or observation counts, depth fusion. */
+int ea_tracker_batch_set_point_carry(ea_tracker_batch *tb, const ea_point_merge *prm /* NULL: off */);
+int ea_tracker_batch_last_point_carry(const ea_tracker_batch *tb, ea_point_merge_stats *stats, int capacity);
 
 /* the half-resolution step by itself, host in / host out: kind 0 = bgr8 (height x width x 3 bytes), 1 = float32 with
  * NaN -> 0 first, 2 = float32 as is; dst = (height / 2) x (width / 2); height and width even */
